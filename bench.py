@@ -8,9 +8,16 @@ N ranks through torch.distributed.run; WORLD_SIZE != --gpus or fewer visible GPU
 ``env.reset()`` + 9 x ``env.step(offline_action)`` including the reward forward, i.e. B*T = 36 864
 env-steps.  Inputs (parsed log + catalogue + weights) are resident in HBM before the timed region.
 Ranks run independent env batches (weak scaling, no collective on the data path); rank 0 prints ONE
-JSON line with the whole-job env-steps/s, the roofline of the dominant kernel (the AUGRU recurrence,
-MFMA-bound, timed live with HIP events on the launch stream) and a CPU baseline (the numpy oracle port
-timed on this box's host cores, rank 0 / N=1 only).
+JSON line with the whole-job env-steps/s, ``ms_per_step`` and the roofline of the dominant kernel (the AUGRU
+recurrence, MFMA-bound, timed live with HIP events on the launch stream).
+
+A plain run does only that: set-up, ``--warmup`` untimed steps, ``--steps`` timed steps, the line.  ``--full`` adds
+everything that takes runs of its own: the per-kernel breakdown pass, the feature-gather roofline, the extra
+workloads, the exact-fp32 scorer leg, the CPU baseline (the numpy oracle port timed on the host cores, rank 0 /
+N=1 only) and the parameter digests of the data-parallel learners.
+
+``--dump-outputs DIR`` writes what the last timed step returned to its caller as ``DIR/<name>.npy`` (float32 /
+float64; rank 0's): the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -463,6 +470,99 @@ def bcq_leg(env, cfg, rank, update_steps=200, rollouts=3):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def step_outputs(last, trainer):
+    """What the caller of the timed step received in the last step, as named host arrays.  Replay: the observation the last
+    ``env.step`` returned and the episode's summed reward; A2C / PPO: the train call's statistics and the updated policy
+    parameters; BCQ: the rollout's last reward, the learner's last losses and the parameters of its networks."""
+    import numpy as np
+    out = {}
+    if trainer is None:
+        obs, reward = last
+        out['obs'], out['episode_reward'] = obs, reward
+    elif hasattr(trainer, 'policy'):
+        for k, v in sorted(dict(last).items()):
+            out['stats_' + k] = np.float64(v)
+        out['policy_params'] = trainer.policy.params()
+    else:
+        out['reward'] = last
+        for k, v in sorted((trainer.last_losses or {}).items()):
+            out['loss_' + k] = v
+        for i, n in enumerate(trainer.bcq.nets):
+            out['net%d_params' % i] = n.flat_params()
+    return out
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT_BYTES):
+    """DIR/<name>.npy per array: float16 / float32 as float32, everything else (float64, integers) as float64.  Over ``limit``
+    bytes in all, each array larger than its share keeps a fixed seeded sample of its flattened elements (in index order)."""
+    import numpy as np
+    import torch
+    host = {}
+    for name, v in arrays.items():
+        if isinstance(v, torch.Tensor):
+            v = v.detach().cpu().numpy()
+        a = np.asarray(v)
+        host[name] = a.astype(np.float32 if a.dtype in (np.float16, np.float32) else np.float64)
+    if sum(a.nbytes for a in host.values()) > limit:
+        share = limit // max(len(host), 1)
+        for name, a in host.items():
+            if a.nbytes > share:
+                keep = np.sort(np.random.RandomState(0).choice(a.size, share // a.itemsize, replace=False))
+                host[name] = a.reshape(-1)[keep]
+    os.makedirs(path, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(path, name + '.npy'), a)
+
+
+def gather_roofline(env, cfg, B, T, seq):
+    """HBM roofline of the feature-gather kernel (k_env_rows<complete>), timed in launches of its own (rank 0 only: no
+    collective in here)."""
+    import torch
+    # the HBM-bound gather kernel in isolation (complete-state rows, 9B rows x 2016 algorithmic bytes)
+    samples = env.samples
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    reps = 50
+    samples._env.build_complete()
+    ev0.record()
+    for _ in range(reps):
+        samples._env.build_complete()
+    ev1.record()
+    torch.cuda.synchronize()
+    g_ms = ev0.elapsed_time(ev1) / reps
+    # the same launch IN SITU: once per episode-batch, right behind an episode's scorer kernels (caches hold the scorer's
+    # data, not the previous gather's output) - one launch between two events, averaged over 5 episodes
+    situ = []
+    for _ in range(5):
+        episode(env, T)         # (never run_step here: this block is rank 0's alone, a train step would enter a collective)
+        ev0.record()
+        samples._env.build_complete()
+        ev1.record()
+        torch.cuda.synchronize()
+        situ.append(ev0.elapsed_time(ev1))
+    g_situ_ms = sum(situ) / len(situ)
+    g_rows = B * samples._env.n_complete
+    g_bytes = g_rows * (cfg['dense_feature_num'] * 4 + cfg['category_feature_num'] * 4 + 32 * 4 + 10 * 4 + 36)
+    g_gbs = g_bytes / (g_ms * 1e-3) / 1e9
+    # the figure that LEADS is the in-situ one (a single launch behind a whole episode-batch: cold caches, what the episode pays);
+    # the back-to-back figure (50 launches onto the same buffers: Infinity-Cache warm) is kept beside it as `burst`
+    g_situ_gbs = g_bytes / (g_situ_ms * 1e-3) / 1e9
+    gather = {"bound": "hbm", "kernel": "k_env_rows<complete>", "achieved": g_situ_gbs, "peak": HBM_PEAK_GBS,
+              "unit": "GB/s", "frac": g_situ_gbs / HBM_PEAK_GBS, "traffic": None, "avg_launch_ms": g_situ_ms,
+              "rows": g_rows,
+              "what": "one launch behind a whole episode-batch (event pair around the single launch, mean of 5)",
+              "burst": {"avg_launch_ms": g_ms, "achieved": g_gbs, "frac": g_gbs / HBM_PEAK_GBS,
+                        "what": "50 back-to-back launches onto the same buffers (Infinity-Cache warm)"}}
+    if not seq and B == 4096 and T == 9:
+        # rocprofv3 WRITE_SIZE 64.15 MB + FETCH_SIZE 0.65 MB per launch of this exact shape against 66.8 MB of algorithmic
+        # writes + 7.5 MB of (L2-resident) reads: no wasted traffic
+        gather["traffic"] = GATHER_TRAFFIC_B
+        gather["traffic_source"] = "constant from " + TRAFFIC_SOURCE_FILE + " (WRITE_SIZE + FETCH_SIZE per launch), not re-measured in this run"
+    return gather
+
+
 def _free_port():
     import socket
     s = socket.socket()
@@ -495,12 +595,12 @@ def main():
     ap.add_argument('--horizon', type=int, default=None)
     ap.add_argument('--log-records', type=int, default=8193)
     ap.add_argument('--cpu-batch', type=int, default=2048,
-                    help='envs of the vectorised cpu_baseline sample (one episode-batch; the faithful 1-core leg uses 64)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+                    help='--full: envs of the vectorised cpu_baseline sample (one episode-batch; the faithful 1-core leg uses 64)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline')
     ap.add_argument('--no-fp32-leg', action='store_true',
-                    help='skip the short extra run of the same workload with the exact-fp32 recurrence (N=1, default mode only)')
+                    help='--full: skip the short extra run of the same workload with the exact-fp32 recurrence (N=1, default mode only)')
     ap.add_argument('--no-extra-legs', action='store_true',
-                    help='skip the extra workloads of the default N=1 run (seq_t32, seq_t32_ppo, conti, all_distinct)')
+                    help='--full: skip the extra workloads of the default N=1 run (seq_t32, seq_t32_ppo, conti, all_distinct)')
     ap.add_argument('--conti', action='store_true',
                     help="continuous-action env (support_conti_env): actions are 32-d embeddings resolved by the masked K-NN")
     ap.add_argument('--algo', choices=['dien', 'dnn', 'widedeep', 'lstm'], default='dien',
@@ -517,6 +617,11 @@ def main():
                     help='--train ppo: SGD minibatch per rank (RLlib: 256).  With N > 1 every minibatch costs one gradient '
                          'all-reduce (synchronous SGD over N x minibatch samples): 512 / 1024 halve / quarter the collectives '
                          'per pass at the price of a larger effective minibatch (DESIGN.md 6)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what takes runs of its own: per-kernel breakdown, gather roofline, extra legs, exact-fp32 '
+                         'leg, CPU baseline, parameter digests of the learners (--no-* options above trim it)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write what the last timed step returned (rank 0's) as DIR/<name>.npy, float32 / float64, at most 64 MB")
     args = ap.parse_args()
     if args.horizon is None:
         args.horizon = 9 if args.env == 'slate' else 32
@@ -576,9 +681,10 @@ def main():
     rdist.barrier()
     sclk = SclkSampler(local_rank)
     t0 = time.perf_counter()
+    last = None
     with sclk:
         for _ in range(args.steps):
-            run_step()
+            last = run_step()
         torch.cuda.synchronize()
     my_elapsed = time.perf_counter() - t0            # this rank's own clock up to ITS last step (before the closing barrier)
     rdist.barrier()
@@ -589,11 +695,15 @@ def main():
     if ranks_seen != args.gpus:
         raise SystemExit('bench.py: %d ranks joined the process group but --gpus is %d: nothing is reported' % (ranks_seen, args.gpus))
     per_rank = rdist.gather_floats(B * T * args.steps / my_elapsed, device='cuda')
+    prof = net.profile()
+    net.set_profiling(0)
+    if args.dump_outputs and rank == 0 and last is not None:
+        dump_outputs(args.dump_outputs, step_outputs(last, trainer))
     # data-parallel training: every rank must hold the SAME learner after the same all-reduced steps - a position-weighted float64
     # digest of each rank's parameters, gathered (equal digests on all ranks = replicas in step; the first N > 1 run on real
     # hardware cannot be debugged from here, so the line carries the evidence)
     param_digests = None
-    if trainer is not None:
+    if trainer is not None and args.full:
         nets = [trainer.policy] if hasattr(trainer, 'policy') else list(trainer.bcq.nets)
         dig = 0.0
         for net_ in nets:
@@ -601,14 +711,12 @@ def main():
             w_ = (torch.arange(p_.numel(), device=p_.device, dtype=torch.float64) % 977.0) + 1.0
             dig += float(torch.dot(p_, w_))
         param_digests = rdist.gather_floats(dig, device='cuda')
-    prof = net.profile()
-    net.set_profiling(0)
     breakdown, breakdown_steps = None, 3
     # the per-kernel breakdown pass is rank 0's - except that a train step with world > 1 contains collectives (the gradient
     # all-reduce), so then every rank has to take the same steps (only rank 0 records events)
     if args.train == 'bcq' and rank == 0:
         out_bcq = {"updates_per_step": args.bcq_updates, "last_losses": dict((k, float(v[-1])) for k, v in (trainer.last_losses or {}).items() if len(v))}
-    if rank == 0 or (trainer is not None and world > 1):
+    if args.full and (rank == 0 or (trainer is not None and world > 1)):
         if rank == 0:
             net.set_profiling(1)
             net.profile_reset()
@@ -657,48 +765,12 @@ def main():
                 # and the 1 reward-sized launch of an episode-batch
                 roofline["traffic"] = TRAFFIC_B_PER_LAUNCH[net.scorer_mode]
                 roofline["traffic_source"] = "constant from the PMC passes of " + TRAFFIC_SOURCE_FILE + " (not re-measured in this run): " + TRAFFIC_NOTE
-        # per-kernel breakdown of ONE episode-batch (separate pass, event pairs around every kernel class)
-        kernels = dict((k, {"ms": round(v[0] / breakdown_steps, 3), "launches": int(v[1] // breakdown_steps)}) for k, v in breakdown.items())
-        kernel_sum = sum(v["ms"] for v in kernels.values())
-        # the HBM-bound gather kernel in isolation (complete-state rows, 9B rows x 2016 algorithmic bytes)
-        samples = env.samples
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        reps = 50
-        samples._env.build_complete()
-        ev0.record()
-        for _ in range(reps):
-            samples._env.build_complete()
-        ev1.record()
-        torch.cuda.synchronize()
-        g_ms = ev0.elapsed_time(ev1) / reps
-        # the same launch IN SITU: once per episode-batch, right behind an episode's scorer kernels (caches hold the scorer's
-        # data, not the previous gather's output) - one launch between two events, averaged over 5 episodes
-        situ = []
-        for _ in range(5):
-            episode(env, T)         # (never run_step here: this block is rank 0's alone, a train step would enter a collective)
-            ev0.record()
-            samples._env.build_complete()
-            ev1.record()
-            torch.cuda.synchronize()
-            situ.append(ev0.elapsed_time(ev1))
-        g_situ_ms = sum(situ) / len(situ)
-        g_rows = B * samples._env.n_complete
-        g_bytes = g_rows * (cfg['dense_feature_num'] * 4 + cfg['category_feature_num'] * 4 + 32 * 4 + 10 * 4 + 36)
-        g_gbs = g_bytes / (g_ms * 1e-3) / 1e9
-        # the figure that LEADS is the in-situ one (a single launch behind a whole episode-batch: cold caches, what the episode pays);
-        # the back-to-back figure (50 launches onto the same buffers: Infinity-Cache warm) is kept beside it as `burst`
-        g_situ_gbs = g_bytes / (g_situ_ms * 1e-3) / 1e9
-        gather = {"bound": "hbm", "kernel": "k_env_rows<complete>", "achieved": g_situ_gbs, "peak": HBM_PEAK_GBS,
-                  "unit": "GB/s", "frac": g_situ_gbs / HBM_PEAK_GBS, "traffic": None, "avg_launch_ms": g_situ_ms,
-                  "rows": g_rows,
-                  "what": "one launch behind a whole episode-batch (event pair around the single launch, mean of 5)",
-                  "burst": {"avg_launch_ms": g_ms, "achieved": g_gbs, "frac": g_gbs / HBM_PEAK_GBS,
-                            "what": "50 back-to-back launches onto the same buffers (Infinity-Cache warm)"}}
-        if not seq and B == 4096 and T == 9:
-            # rocprofv3 WRITE_SIZE 64.15 MB + FETCH_SIZE 0.65 MB per launch of this exact shape against 66.8 MB of algorithmic
-            # writes + 7.5 MB of (L2-resident) reads: no wasted traffic
-            gather["traffic"] = GATHER_TRAFFIC_B
-            gather["traffic_source"] = "constant from " + TRAFFIC_SOURCE_FILE + " (WRITE_SIZE + FETCH_SIZE per launch), not re-measured in this run"
+        kernels = gather = None
+        if args.full:
+            # per-kernel breakdown of ONE episode-batch (separate pass, event pairs around every kernel class)
+            kernels = dict((k, {"ms": round(v[0] / breakdown_steps, 3), "launches": int(v[1] // breakdown_steps)}) for k, v in breakdown.items())
+            kernel_sum = sum(v["ms"] for v in kernels.values())
+            gather = gather_roofline(env, cfg, B, T, seq)
         out = {
             "metric": "env-steps/s (batch=%d, %d-slot slate)" % (B, 9),
             "value": env_steps / elapsed,
@@ -728,17 +800,18 @@ def main():
             # dien: the AUGRU recurrence; the GEMM-only families (dnn / widedeep / lstm) have no dominant matrix kernel,
             # their line carries the HBM roofline of the feature-gather kernel
             "roofline": roofline if roofline is not None else gather,
-            "roofline_gather": gather,
-            "kernels": kernels,
+        }
+        if args.full:
+            out["roofline_gather"] = gather
+            out["kernels"] = kernels
             # everything in an episode-batch that is not one of the scorer's kernels: env-state kernels, torch glue,
             # launch gaps, host (ms_per_step of the timed region - the scorer kernels' sum from the breakdown pass)
-            "non_scorer_ms_per_step": round(elapsed / args.steps * 1e3 - kernel_sum, 3),
-        }
+            out["non_scorer_ms_per_step"] = round(elapsed / args.steps * 1e3 - kernel_sum, 3)
         hu = getattr(env.samples, '_hist_unique', None)
         # RecDataBase.sample draws WITH replacement from the 2048-line cache window (base.py:92-100): distinct user histories
         # of the last batch (the first GRU / projections run once per distinct history; the AUGRU runs per env row)
         out["config"]["distinct_histories"] = int(hu[0].shape[0]) if hu is not None else B
-        default_run = world == 1 and is_dien and not trainer and not seq and not args.conti
+        default_run = args.full and world == 1 and is_dien and not trainer and not seq and not args.conti
         if default_run and not args.no_extra_legs:
             out["extra"] = dict((name, extra_leg(args, workdir, rank, name))
                                 for name in ('seq_t32', 'seq_t32_ppo', 'seq_t32_a2c', 'conti', 'bcq_conti', 'all_distinct', 'compat_numpy',
@@ -756,7 +829,7 @@ def main():
             out["exact_fp32_scorer"] = extra_leg(args, workdir, rank, 'fp32')
         if args.train == 'bcq':
             out["bcq"] = out_bcq
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg, records, seq, args.cpu_batch)
         print(json.dumps(out))
     if world > 1:

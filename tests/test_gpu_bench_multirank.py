@@ -30,7 +30,7 @@ def test_bench_two_ranks_over_gloo(leg):
     env = dict(os.environ, RL4RS_DIST_BACKEND='gloo', MASTER_ADDR='127.0.0.1')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
            '--master-port', str(_free_port()), os.path.join(REPO, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1',
-           '--batch', '256', '--log-records', '700', '--no-cpu-baseline'] + leg
+           '--batch', '256', '--log-records', '700', '--full', '--no-cpu-baseline'] + leg
     out = subprocess.run(cmd, cwd=REPO, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=420)
     assert out.returncode == 0, out.stderr.decode()[-3000:]
     lines = [l for l in out.stdout.decode().splitlines() if l.startswith('{')]
@@ -70,7 +70,7 @@ def test_plain_launch_eight_ranks(leg):
     env = dict((k, v) for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT'))
     env.update(RL4RS_DIST_BACKEND='gloo')
     cmd = [sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '8', '--steps', '2', '--warmup', '1', '--batch', '256',
-           '--log-records', '700', '--no-cpu-baseline'] + leg
+           '--log-records', '700', '--full', '--no-cpu-baseline'] + leg
     out = subprocess.run(cmd, cwd=REPO, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert out.returncode == 0, out.stderr.decode()[-3000:]
     lines = [l for l in out.stdout.decode().splitlines() if l.startswith('{')]

@@ -8,7 +8,7 @@ mkdir -p gpurun_out
 for rep in 1 2; do
   for o in "$@"; do
     if [ "$o" = "-" ]; then opts=""; else opts="$o"; fi
-    RL4RS_DIEN_OPTS="$opts" python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-fp32-leg --no-extra-legs 2>/dev/null | python -c "
+    RL4RS_DIEN_OPTS="$opts" python bench.py --steps 10 --warmup 2 --full --no-cpu-baseline --no-fp32-leg --no-extra-legs 2>/dev/null | python -c "
 import json,sys
 r=json.loads(sys.stdin.read().strip().splitlines()[-1])
 k=r['kernels']

@@ -8,7 +8,7 @@ mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 for algo in a2c ppo; do
   rm -rf /tmp/prof_tr_$algo
-  cmd="python $repo/bench.py --train $algo --steps 2 --warmup 1 --no-cpu-baseline --no-extra-legs --no-fp32-leg"
+  cmd="python $repo/bench.py --train $algo --steps 2 --warmup 1 --full --no-cpu-baseline --no-extra-legs --no-fp32-leg"
   timeout -k 10 150 rocprofv3 --kernel-trace -d /tmp/prof_tr_$algo -o tr -- $cmd > $out/${tag}_train_${algo}.log 2>&1
   echo "rc=$?" >> $out/${tag}_train_${algo}.log
   db=$(find /tmp/prof_tr_$algo -name '*.db' | head -1)
