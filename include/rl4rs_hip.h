@@ -431,7 +431,15 @@ int rl4rs_simnet_head_prob(rl4rs_simnet* net, int32_t R, const float* obs_dev, f
  * (bit-identical results); nothing is allocated, nothing synchronises inside.
  *   slots_dev  int32 [seq_num, batch_size]: cache slot of every env row per sequence input (caller-owned; the caller
  *              encodes the history sequences with rl4rs_dien_encode after every rl4rs_env_load_batch and keeps row 0
- *              current; SeqSlate's second input is re-encoded here on the first act of a page, seqslate.py:107-108)
+ *              current).  SeqSlate's second input (items of the previous pages, seqslate.py:107-108) is re-encoded here
+ *              into slots [0, batch_size) on the first act of every page but the first; rows 1.. must then read
+ *              0, 1, .., batch_size - 1.  On the first page of every episode it is the constant [0] and is NOT encoded
+ *              here: the caller supplies it, either by encoding batch_size all-zero rows into slots [0, batch_size)
+ *              after every rl4rs_env_load_batch, or (the Python wrapper's recipe) by encoding one all-zero row once into
+ *              a spare slot (slot batch_size: the net needs max_slots >= batch_size + 1), pointing rows 1.. at it after
+ *              every rl4rs_env_load_batch and writing 0 .. batch_size - 1 back before the first act of the second page
+ *              (on the stream the steps run on).  Slate's second input is that constant [0] at every step
+ *              (slate.py:77), supplied the same way.
  *   obs_dev    float32 [B, D]    'simulator_obs' of the new state (slate.py:265-267); D = 256 for the DIEN scorer,
  *              rl4rs_simnet_obs_dim() for an attached simnet (widedeep: 256 + hidden_units + Cn * emb_size)
  *   reward_dev float64 [B] (optional)  0 unless a reward is due (slate.py:283, seqslate.py:138)

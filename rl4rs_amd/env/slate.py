@@ -336,7 +336,8 @@ class SlateState(RecState):
         if env.cur_steps < self.max_steps:
             return [0, ] * self.batch_size
         r = env.offline_reward()
-        return r if self._tensor_mode() else r.cpu().numpy().tolist()
+        # a list of np.float64: the reference sums np.float64 price * int label products (slate.py:164-174)
+        return r if self._tensor_mode() else list(r.cpu().numpy())
 
     @staticmethod
     def get_nearest_neighbor(actions, action_emb, temperature=None):

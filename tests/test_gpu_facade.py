@@ -8,6 +8,8 @@ import os
 import numpy as np
 import pytest
 
+from helpers import FACADE_SCENARIOS
+
 pytestmark = pytest.mark.gpu
 
 
@@ -116,6 +118,31 @@ def test_episode_matches_oracle(tmp_path, seq, T, mode):
     assert np.array_equal(env.samples.special_mask, orc.samples.special_mask)
 
 
+@pytest.mark.parametrize('precision', ['fp32', 'fp16x2'])
+@pytest.mark.parametrize('name', FACADE_SCENARIOS)
+def test_facade_replays_the_reference_episodes(tmp_path, name, precision):
+    """tests/golden/facade_<name>.npz: whole episodes of the reference's own RecEnvBase(SlateRecEnv | SeqSlateRecEnv), its net
+    the fp64 oracle DIEN with the same seeded weights.  The HIP facade replays the recorded actions on the committed inputs:
+    every value's type signature (the stale state's included), ints, masks, done, user_id, offline fields and sampled records
+    exactly; the scorer's observations - returned or held as the stale state - within 5e-5, rewards and click_p within
+    rtol / atol 1e-5."""
+    from helpers import load_facade, facade_weights, run_facade_script, recorded_action, compare_facade
+    from rl4rs_amd.nets.dien import save_weights
+    from rl4rs_amd.utils.rllib_vector_env import MyVectorEnvWrapper
+    m, cfg, want, script, sigs = load_facade('facade_' + name)
+    wpath = os.path.join(str(tmp_path), 'dien.npz')
+    save_weights(wpath, facade_weights(m))
+    cfg = dict(cfg, model_file=wpath, scorer_precision=precision)
+    np.random.seed(0)                     # as the recording: the constructor samples before any seed() in train mode
+    env = _make(cfg, m['seq'])
+    vector = MyVectorEnvWrapper(env, cfg['batch_size']) if any(op['op'] == 'reset_at' for op in script) else None
+    got, got_sigs = run_facade_script(env, script, lambda i, e: recorded_action(want, sigs, i), vector=vector)
+    assert env.sim.model.device_net.scorer_mode == precision
+    assert got_sigs == sigs
+    want = dict((k, v) for k, v in want.items() if not k.endswith('.net_rows'))     # pinned on the oracle (test_oracle_golden.py)
+    compare_facade(want, got, obs_atol=5e-5, rtol=1e-5, atol=1e-5)
+
+
 def test_rawstate_and_tensor_modes(tmp_path):
     import torch
     B, T = 6, 9
@@ -163,18 +190,8 @@ def test_batch_of_one_and_sampling_semantics(tmp_path):
     assert isinstance(a, int)
     obs, reward, done, info = env.step(a)
     assert obs.shape == (256,) and reward == 0 and done == 0 and info == {}
-    # train-mode sampling draws np.random.choice from the global RNG exactly like the reference
-    cfg, records, w = _setup(tmp_path, False, 4, 9, is_eval=False, cache_size=6)
-    env = _make(cfg, False)
-    env.seed(123)
-    env.reset(reset_file=True)
-    np.random.seed(123)
-    cache = records[:6]
-    expect = np.random.choice(cache, 4)
-    assert list(env.samples.records) == list(expect)
-    # the file has 9 lines + trailing newline: the next reset wraps (base.py:84-88: skip line 0, take line 1)
-    env.reset()
-    assert env.sim._recData.sample_list == records[6:9] + [records[1]] + records[2:4]
+    # train-mode sampling (np.random.choice from the global RNG after seed(), the cache window, the wrap at EOF that skips
+    # line 0): test_facade_replays_the_reference_episodes[sampling-*] against the reference's own RecEnvBase
 
 
 def test_vector_env_wrapper(tmp_path):
@@ -662,3 +679,70 @@ def test_record_entry_points_validate_and_agree(tmp_path):
     assert np.array_equal(mask, samples._obs_mask())
     obs = first[lo:hi].numpy().view(np.float32).reshape(24, 256)
     assert np.array_equal(obs, np.stack([o['obs'] for o in env.state]))
+
+
+def test_c_api_seqslate_episodes_follow_the_header_contract(tmp_path):
+    """rl4rs_env_step_discrete driven at the C ABI exactly as include/rl4rs_hip.h (slots_dev of rl4rs_env_attach_scorer) tells
+    a caller to: a caller-owned slot table; the histories encoded into input 0 after every rl4rs_env_load_batch; SeqSlate's
+    second input supplied by the caller for the first page (one all-zero row encoded once into the spare slot B, rows 1..
+    pointed at it after every load, 0 .. B-1 written back before the first act of the second page) and re-encoded by the
+    library from then on.  Two episodes of different records (T = 18, B = 8): obs and rewards of every step against the oracle
+    env - the first page of the second episode is where stale encodings of the first episode's last page would show."""
+    import ctypes as C
+    import torch
+    from rl4rs_amd import _lib, synth, device as D
+    from rl4rs_amd.data import CatalogTables, parse_records_native
+    from rl4rs_amd.nets.dien import init_dien_weights
+    from oracle.dien import OracleDien
+    from oracle.env import OracleEnv
+    B, T = 8, 18
+    cat_path = os.path.join(str(tmp_path), 'item_info.csv')
+    cat_text = synth.make_catalog_text(seed=21)
+    synth.write_text(cat_path, cat_text)
+    records = synth.make_records(2 * B, pages=2, seed=9, illegal_frac=0.3, hash_size=5000,
+                                 special_ids=synth.special_ids_from_text(cat_text))
+    cfg = {"maxlen": 64, "batch_size": B, "action_size": 284, "class_num": 2, "dense_feature_num": 432,
+           "category_feature_num": 21, "category_hash_size": 5000, "seq_num": 2, "emb_size": 128,
+           "page_items": 9, "hidden_units": 128, "max_steps": T, "action_emb_size": 32, "iteminfo_file": cat_path}
+    w = init_dien_weights(cfg, seed=5, emb_scale=0.5, bias_noise=0.2)
+    lib = _lib.load()
+    stream = D._stream()
+    catalog = CatalogTables(cat_path, 284, 32, False)
+    cols = [parse_records_native(records[e * B:(e + 1) * B], 64) for e in range(2)]
+    env = D.DeviceEnv(cfg, catalog, True, cols[0].exposed.shape[1], False)
+    net = D.DeviceDien(cfg, w, B * env.n_complete, B + 1)                  # B slots per input + the spare slot B
+    slots = torch.arange(B, dtype=torch.int32, device='cuda').repeat(2, 1).contiguous()      # [seq_num, B], caller-owned
+    zero = torch.zeros((1, 64), dtype=torch.int32, device='cuda')
+    _lib.check(lib.rl4rs_dien_encode(net.h, 1, zero.data_ptr(), 1, B, stream))       # [first-page recipe]
+    stepper = C.c_void_p()
+    _lib.check(lib.rl4rs_env_attach_scorer(env.h, net.h, slots.data_ptr(), 2, C.byref(stepper)))
+    obs = torch.empty((B, 256), dtype=torch.float32, device='cuda')
+    reward = torch.empty(B, dtype=torch.float64, device='cuda')
+    done = torch.empty(B, dtype=torch.uint8, device='cuda')
+    rs = np.random.RandomState(3)
+    try:
+        for e in range(2):
+            c = cols[e]
+            env.load_batch(c.exposed, c.feedback, c.history, c.user_dense, c.user_cat)
+            hist = torch.from_numpy(np.ascontiguousarray(c.history, dtype=np.int32)).cuda()
+            _lib.check(lib.rl4rs_dien_encode(net.h, 0, hist.data_ptr(), B, 0, stream))
+            slots[1].fill_(B)                                                           # [first-page recipe]
+            env.reset()
+            orc = OracleEnv(dict(cfg), records[e * B:(e + 1) * B], OracleDien(w, cfg, np.float64), seq=True)
+            for t in range(T):
+                a = np.asarray(orc.samples.offline_action, dtype=np.int64)
+                if t % 4 == 3:
+                    a[B // 2:] = rs.randint(0, 284, size=B - B // 2)
+                if t == 9:                                                              # [first-page recipe]
+                    slots[1].copy_(torch.arange(B, dtype=torch.int32, device='cuda'))  # [first-page recipe]
+                acts = torch.from_numpy(a.astype(np.int32)).cuda()
+                _lib.check(lib.rl4rs_env_step_discrete(stepper, acts.data_ptr(), obs.data_ptr(), reward.data_ptr(),
+                                                       done.data_ptr(), None, stream))
+                o_obs, o_reward, o_done, _ = orc.step(a)
+                torch.cuda.synchronize()
+                assert np.abs(obs.cpu().numpy() - o_obs['obs']).max() < 5e-5, (e, t)
+                assert np.allclose(reward.cpu().numpy(), o_reward, rtol=1e-5, atol=1e-5), (e, t, reward, o_reward)
+                assert done.cpu().numpy().tolist() == o_done, (e, t)
+            assert any(r != 0 for r in o_reward)
+    finally:
+        lib.rl4rs_stepper_destroy(stepper)

@@ -287,49 +287,92 @@ def test_scorer_kernel_option_names():
         assert m and int(m.group(1)) == val, name
 
 
-def test_cache_window_with_blank_lines_matches_the_line_by_line_loop(tmp_path):
-    """base.py:82-90 read line by line (readline().rstrip(); on an empty read: seek(0), skip one line, take the next) against
-    the bulk form RecDataBase.sample_cache uses (slices of the blank-free runs), on files with blank lines in odd places."""
+def test_cache_window_with_blank_lines_matches_the_reference(tmp_path):
+    """base.py:82-90 (readline().rstrip(); on an empty read: seek(0), skip one line, take the next) against the bulk form
+    RecDataBase.sample_cache uses (slices of the blank-free runs): six windows per file of tests/golden/cache_windows.json,
+    recorded from the reference's own RecDataBase over files with blank lines in odd places."""
+    import json
     from rl4rs_amd.env.base import RecDataBase
-    rng = np.random.RandomState(5)
-    for trial in range(30):
-        n = int(rng.randint(3, 40))
-        lines = ['rec%d  ' % i if rng.rand() > 0.15 else ('' if rng.rand() > 0.5 else '   ') for i in range(n)]
-        lines[1] = 'rec1'                                  # the line taken after a wrap
-        text = '\n'.join(lines) + ('\n' if rng.rand() > 0.3 else '')
+    with open(os.path.join(GOLDEN, 'cache_windows.json')) as f:
+        cases = json.load(f)
+    assert len(cases) == 30
+    for trial, case in enumerate(cases):
         p = tmp_path / ('log%d.csv' % trial)
-        p.write_text(text)
-        file_lines = text.split('\n')
-
-        class Loop(object):                                # the reference's loop over a file object
-            def __init__(self):
-                self.c = 0
-
-            def readline(self):
-                if self.c >= len(file_lines):
-                    return ''
-                self.c += 1
-                return file_lines[self.c - 1].rstrip()
-
-            def window(self, num):
-                out = []
-                for _ in range(num):
-                    tmp = self.readline()
-                    if len(tmp) < 1:
-                        self.c = 0
-                        self.readline()
-                        tmp = self.readline()
-                    out.append(tmp)
-                return out
-
-        cache = int(rng.randint(1, 25))
+        p.write_text(case['text'])
+        file_lines = case['text'].split('\n')
+        cache = case['cache_size']
         db = RecDataBase({'sample_file': str(p), 'maxlen': 64, 'cache_size': cache, 'is_eval': False}, _CaptureState)
-        ref = Loop()
-        for _ in range(6):
+        for want in case['windows']:
             db.reset()
-            want = ref.window(cache)
-            assert db.sample_list == want, (trial, lines, cache)
+            assert db.sample_list == want, (trial, case['text'], cache)
             assert [file_lines[r].rstrip() if r >= 0 else '' for r in db.sample_rows] == want
+
+
+def test_recdatabase_reproduces_the_reference_sampling_stream():
+    """tests/golden/facade_sampling.npz (the reference's RecEnvBase, is_eval=False, cache 7 over an 11-line file): the cache
+    windows across EOF wraps and past the header-line skip, the np.random.choice draws after seed(123) and after the two
+    resets of the constructor, and reset(reset_file=True) - through rl4rs_amd's own RecEnvBase / RecSimBase / RecDataBase,
+    with a host-only simulator (no net, no device state) so that the constructor's call order is the product's."""
+    from helpers import load_facade
+    from rl4rs_amd.env.base import RecEnvBase, RecSimBase
+
+    class HostSim(RecSimBase):
+        def get_model(self, config):
+            return None
+
+        def obs_fn(self, state):
+            return np.zeros((self.batch_size, 4), dtype=np.float32)
+
+        def forward(self, model, samples):
+            return [0] * self.batch_size
+
+    class HostState(_CaptureState):
+        state = None
+
+    m, cfg, vals, script, sigs = load_facade('facade_sampling')
+    B = cfg['batch_size']
+    assert not cfg['is_eval'] and cfg['cache_size'] == 7 and B == 6
+    np.random.seed(0)                                 # as the recording: the constructor samples before any seed()
+    env = RecEnvBase(HostSim(cfg, HostState))
+    checked = 0
+    for i, op in enumerate(script):
+        if op['op'] == 'seed':
+            env.seed(op['seed'])
+            continue
+        if op['op'] == 'reset':
+            env.reset(reset_file=op.get('reset_file', False))
+        elif op['op'] != 'construct':
+            continue
+        assert env.sim._recData.sample_list == vals['e%d.sample_list' % i].tolist(), i
+        assert list(env.samples.records) == vals['e%d.records' % i].tolist(), i
+        checked += 1
+    assert checked == 6
+    wraps = [vals['e%d.sample_list' % i].tolist() for i, op in enumerate(script) if op['op'] in ('construct', 'reset')]
+    with open(cfg['sample_file']) as f:
+        lines = f.read().split('\n')
+    assert lines[0] not in sum(wraps[:-1], [])      # line 0 is skipped on every wrap, read only from the top of the file
+    assert wraps[-1][0] == lines[0]
+
+
+def test_single_elem_support_matches_the_recorded_batch_of_one():
+    """single_elem_support (base.py:9-23) on every value RecEnvBase hands out at B = 1 (tests/golden/facade_slate_b1.npz):
+    the recorded type signatures of reset/step/state/user_id/offline_action/offline_reward (step returns a list, a
+    non-reward step an int 0, a reward step a float, info a dict)."""
+    from helpers import oracle_facade_run
+
+    class Zeros(object):
+        def obs(self, seq, dense, cat):
+            return np.zeros((len(cat), 256), dtype=np.float32)
+
+        def prob(self, seq, dense, cat):
+            return np.full(len(cat), 0.5, dtype=np.float32)
+
+    want, want_sigs, got, got_sigs = oracle_facade_run('facade_slate_b1', scorer=Zeros())
+    assert got_sigs == want_sigs
+    step = [s['ret'] for s in want_sigs if 'action' in s]
+    assert step[0] == {'t': 'list', 'len': 4, 'each': [{'t': 'ndarray', 'dtype': 'float32', 'shape': [256]}, {'t': 'int'},
+                                                      {'t': 'int'}, {'t': 'dict', 'keys': [], 'items': []}]}
+    assert step[8]['each'][1] == {'t': 'float'}
 
 
 def test_ranks_sharing_device(monkeypatch):

@@ -5,7 +5,7 @@ import pytest
 
 from oracle.env import reward_from_probs, is_reward_step
 from oracle.state import OracleState, nearest_neighbor
-from helpers import SCENARIOS, load_scenario, golden_equal, golden_has
+from helpers import SCENARIOS, load_scenario, golden_equal, golden_has, FACADE_SCENARIOS, oracle_facade_run, compare_facade
 
 
 @pytest.mark.parametrize('name', SCENARIOS)
@@ -114,3 +114,13 @@ def test_faithful_per_sample_loop_matches_reference(name):
     cs, cd, cc = env._features(env.complete_states())
     assert np.array_equal(cs, g['c_seq_%d' % (T - 1)]) and golden_equal(g, 'c_dense_%d' % (T - 1), cd) and np.array_equal(cc, g['c_cat_%d' % (T - 1)])
     assert np.array_equal(env.violation(), g['violation_end'])
+
+
+@pytest.mark.parametrize('name', FACADE_SCENARIOS)
+def test_oracle_env_reproduces_reference_facade(name):
+    """oracle/env.py (+ the reference's obs_fn packaging) with the fp64 OracleDien replays whole episodes of the reference's own
+    RecEnvBase(SlateRecEnv | SeqSlateRecEnv) (tests/golden/facade_*.npz) bit for bit: observations, rewards, done, masks, info,
+    the stale state, offline fields, the rows the net scored per call and every value's type signature."""
+    want, want_sigs, got, got_sigs = oracle_facade_run('facade_' + name)
+    assert got_sigs == want_sigs
+    compare_facade(want, got)
