@@ -687,7 +687,11 @@ int rl4rs_simtrain_step(rl4rs_simtrain* tr, int32_t N, const float* dense_dev, c
 /* Supervised training of the DIEN simulator (rl4rs/nets/dien.py; script/supervised_train.py with model_type='dien') on the
  * device: training-mode forward (Dropout after each dense-tower layer), keras binary_crossentropy, backward through the
  * head, the category self-attention, the dense tower and, per sequence input, the DIN attention MLP, the AUGRU and the
- * first GRU (explicit BPTT), Adam.  Weights / sizes as for rl4rs_dien_create (max_rows, max_slots, scorer_mode unused).
+ * first GRU (explicit BPTT), Adam.  Weights as for rl4rs_dien_create (max_rows, max_slots, scorer_mode unused).  The
+ * trainer's own size limits, refused at create: emb_size = 128 (the recurrences are built for widths 128 / 256),
+ * 10 <= category_feature_num <= 32, 1 <= seq_num <= 4, 2 <= class_num <= 8, 1 <= maxlen <= 64 (the persistent training
+ * recurrences; no step-by-step form), and max_batch * maxlen * 3 * 256 * 4 < 2^31 (the AUGRU's pre-activations:
+ * max_batch <= 10922 at maxlen 64).
  * Flat parameter / gradient layout:
  *   [ cat_emb | seq_emb | dense_w1 | dense_b1 | dense_w2 | dense_b2 | obs_w | obs_b | out_w | out_b |
  *     per sequence input: gru_gate_w, gru_gate_b, gru_cand_w, gru_cand_b, att_w1, att_b1, att_w2, att_b2, att_w3, att_b3,

@@ -294,6 +294,16 @@ int rl4rs_dientrain_create(const rl4rs_dien_cfg* c, const rl4rs_dien_weights* w,
     RL4RS_REQUIRE(c->emb_size > 0 && c->emb_size % 2 == 0 && c->hidden_units > 0 && c->maxlen >= 1 && c->seq_num >= 1 && c->seq_num <= 4 &&
                   c->category_feature_num >= 10 && c->category_feature_num <= 32 && c->category_hash_size > 0 &&
                   c->dense_feature_num > 0 && c->class_num >= 2 && c->class_num <= 8, "dientrain: bad sizes");
+    // the limits of the persistent training recurrences (launch_recur_train_fwd / _bwd; there is no step-by-step form for DIEN), refused
+    // here rather than at the first grad: a whole sequence per workgroup, and the AUGRU's [max_batch * maxlen, 3 * 256] fp32
+    // pre-activations addressed below 2^31 bytes
+    RL4RS_REQUIRE(c->maxlen <= 64, "dientrain: maxlen must be <= 64 (the persistent training recurrences), got %d", c->maxlen);
+    {
+        const int64_t row_bytes = (int64_t)c->maxlen * 3 * (2 * c->emb_size) * 4;
+        RL4RS_REQUIRE((int64_t)max_batch * row_bytes < (int64_t)0x7fffffff,
+                      "dientrain: max_batch %d too large: max_batch * maxlen * 3 * 256 * 4 bytes must stay below 2^31 (max_batch <= %lld at maxlen %d)",
+                      max_batch, (long long)(((int64_t)0x7fffffff - 1) / row_bytes), c->maxlen);
+    }
     RL4RS_REQUIRE(w->cat_emb && w->seq_emb && w->dense_w1 && w->dense_b1 && w->dense_w2 && w->dense_b2 && w->obs_w && w->obs_b &&
                   w->out_w && w->out_b, "dientrain_create: weights missing");
     for (int s = 0; s < c->seq_num; ++s)

@@ -536,9 +536,12 @@ int rl4rs_simtrain_create(const rl4rs_simnet_cfg* c, const rl4rs_simnet_weights*
     if (U * 3 * U > wmax) wmax = U * 3 * U;
     const int64_t maxlen_any = ls ? (c->maxlen > Cn ? c->maxlen : Cn) : 1;
     const int nz_all = (int)((B * maxlen_any + t->chunk - 1) / t->chunk);       // the GRU gradients reduce over N * len samples
+    // partials per chunk: the widest weight gradient, and for a GRU's input kernel (st_tn_cs) its [E x 3U] weight partial followed by
+    // the 3U bias columns
+    const int64_t pmax = ls && (E + 1) * 3 * U > wmax ? (E + 1) * 3 * U : wmax;
     ST_FAIL(al(&t->wt, wmax));
-    ST_FAIL(al(&t->part, (size_t)(nz_all > t->nz ? nz_all : t->nz) * wmax));
-    t->part_cap = (size_t)(nz_all > t->nz ? nz_all : t->nz) * wmax;
+    ST_FAIL(al(&t->part, (size_t)(nz_all > t->nz ? nz_all : t->nz) * pmax));
+    t->part_cap = (size_t)(nz_all > t->nz ? nz_all : t->nz) * pmax;
     for (int g = 0; g < 5; ++g) memset(&t->gru[g], 0, sizeof(GruSave));
     if (ls) {
         for (int g = 0; g < n_gru; ++g) {
@@ -557,11 +560,14 @@ int rl4rs_simtrain_create(const rl4rs_simnet_cfg* c, const rl4rs_simnet_weights*
         ST_FAIL(al(&t->g_dhg, B * U)); ST_FAIL(al(&t->g_drh, B * U)); ST_FAIL(al(&t->g_zero, B * U));
         ST_FAIL(al(&t->g_uzrT, 2 * U * U)); ST_FAIL(al(&t->g_uhT, U * U)); ST_FAIL(al(&t->g_tmpw, U * 2 * U));
         ST_HIP(hipMemsetAsync(t->g_zero, 0, B * U * 4, st));
-        {   // second stream + its scratch (only GRU gradient chains run there: widest reduction [E x 3U] / [U x 3U])
+        {   // second stream + its scratch (only GRU gradient chains run there: widest transpose [E x 3U] / [U x 3U]; partials per chunk
+            // [E x 3U] + 3U bias columns (st_tn_cs of the input kernel) or [U x 2U].  Sized without the bias columns, a chunked
+            // reduction (1024 < N * len < 4096 samples) wrote 3U floats per chunk past `part2` whenever E >= U)
             const int64_t wmax2 = (E > U ? E : U) * 3 * U;
+            const int64_t pmax2 = (E + 1) * 3 * U > 2 * U * U ? (E + 1) * 3 * U : 2 * U * U;
             ST_FAIL(al(&t->g_dX2, nm * E)); ST_FAIL(al(&t->g_hprev2, nm * U)); ST_FAIL(al(&t->g_tmpw2, U * 2 * U));
-            ST_FAIL(al(&t->wt2, wmax2)); ST_FAIL(al(&t->part2, (size_t)nz_all * wmax2));
-            t->part_cap2 = (size_t)nz_all * wmax2;
+            ST_FAIL(al(&t->wt2, wmax2)); ST_FAIL(al(&t->part2, (size_t)nz_all * pmax2));
+            t->part_cap2 = (size_t)nz_all * pmax2;
             ST_HIP(hipStreamCreateWithFlags(&t->side, hipStreamNonBlocking));
             ST_HIP(hipEventCreateWithFlags(&t->ev_fork, hipEventDisableTiming));
             ST_HIP(hipEventCreateWithFlags(&t->ev_mid, hipEventDisableTiming));

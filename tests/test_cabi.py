@@ -86,3 +86,40 @@ def test_header_is_plain_c(tmp_path):
     r = subprocess.run(['gcc', '-std=c99', '-Wall', '-Wextra', '-pedantic', '-Werror', '-fsyntax-only', '-I', inc, str(src)],
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
+
+
+def test_dientrain_create_refuses_what_its_recurrences_cannot_run(lib):
+    """rl4rs_dientrain_create refuses maxlen > 64 (the persistent training recurrences; DIEN has no step-by-step form) and a
+    max_batch whose AUGRU pre-activations [max_batch * maxlen, 3 * 256] fp32 reach 2^31 bytes - with its size checks, before it
+    looks for a device (or reads a weight: the pointers only have to be non-null).  Refused shapes only: with a device present, an
+    admitted one would go on to copy the (dummy) weights."""
+    import ctypes as C
+    import numpy as np
+    from rl4rs_amd import _lib
+    dummy = np.zeros(1, dtype=np.float32)
+    p = dummy.ctypes.data_as(_lib._FP)
+    w = _lib.DienWeights()
+    for name, typ in _lib.DienWeights._fields_:
+        if typ is _lib._FP4:
+            for i in range(4):
+                getattr(w, name)[i] = p
+        else:
+            setattr(w, name, p)
+
+    def create(maxlen, max_batch):
+        cfg = _lib.DienCfg(maxlen, 128, 128, 432, 21, 3000, 2, 2, 1, 1, 0, 0)
+        h = C.c_void_p()
+        rc = lib.rl4rs_dientrain_create(C.byref(cfg), C.byref(w), max_batch, None, C.byref(h))
+        return rc, lib.rl4rs_last_error().decode(), h
+
+    for maxlen, max_batch, words in ((65, 256, ('maxlen', '64')), (1000, 1, ('maxlen', '64')),
+                                     (64, 10923, ('max_batch', '2^31', '10922')), (1, 699051, ('max_batch', '2^31', '699050'))):
+        rc, msg, h = create(maxlen, max_batch)
+        assert rc == -1 and not h.value, (maxlen, max_batch, rc, msg)          # RL4RS_EINVAL, no handle
+        for word in words:
+            assert word in msg, (maxlen, max_batch, msg)
+    if lib.rl4rs_device_count() <= 0:
+        # the bounds themselves are admitted: the call gets as far as the device check
+        for maxlen, max_batch in ((64, 10922), (1, 699050)):
+            rc, msg, h = create(maxlen, max_batch)
+            assert rc == -2 and 'no HIP device' in msg, (maxlen, max_batch, rc, msg)

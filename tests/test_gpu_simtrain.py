@@ -10,11 +10,27 @@ CFG = {"maxlen": 64, "class_num": 2, "dense_feature_num": 432, "category_feature
        "seq_num": 2, "emb_size": 128, "hidden_units": 128}
 
 
-def _batch(N, rs):
-    dense = np.abs(rs.randn(N, 432)).astype(np.float32)
-    cat = rs.randint(0, 3000, size=(N, 21)).astype(np.int32)
-    labels = rs.randint(0, 2, size=N).astype(np.int32)
+def _batch(N, rs, cfg=CFG):
+    dense = np.abs(rs.randn(N, cfg['dense_feature_num'])).astype(np.float32)
+    cat = rs.randint(0, cfg['category_hash_size'], size=(N, cfg['category_feature_num'])).astype(np.int32)
+    labels = rs.randint(0, cfg['class_num'], size=N).astype(np.int32)
     return dense, cat, labels
+
+
+# fp64 references by configuration: the row-tile forms of one configuration see the same inputs and (the counter RNG is a pure
+# function of seed, step, row and column) the same dropout masks, so their autograd reference is computed once
+_REFS = {}
+
+
+def _reference(key, masks, compute):
+    if key not in _REFS:
+        while len(_REFS) >= 8:
+            _REFS.pop(next(iter(_REFS)))
+        _REFS[key] = (masks, compute())
+    cached, ref = _REFS[key]
+    for a, b in zip(cached, masks):
+        assert (a is None and b is None) or np.array_equal(a, b), 'dropout masks differ from the cached reference inputs'
+    return ref
 
 
 @pytest.fixture
@@ -47,17 +63,23 @@ def test_lstm_gradients_in_both_recurrence_tile_forms(recur_rows, rows, N):
         recur_rows(16)
 
 
-def _check_simnet_gradients(algo, rate, N):
+def _check_simnet_gradients(algo, rate, N, cfg=CFG, front_pad=False):
+    """cfg: any configuration rl4rs_simtrain_create admits; front_pad: the first third of the rows of sequence input 0 start with
+    padding ids (short histories)"""
     import torch
     from rl4rs_amd.nets.simnets import init_simnet_weights
     from rl4rs_amd.device import DeviceSimTrainer
     from oracle.simnets import loss_and_grad
     rs = np.random.RandomState(N + int(rate * 10))
-    w = init_simnet_weights(CFG, algo, seed=3, emb_scale=0.5, bias_noise=0.2)
-    dense, cat, labels = _batch(N, rs)
-    seqs = [rs.randint(0, 284, size=(N, 64)).astype(np.int32) for _ in range(2)]
-    seqs[1][::2] = 0
-    tr = DeviceSimTrainer(CFG, w, max_batch=N, algo=algo)
+    w = init_simnet_weights(cfg, algo, seed=3, emb_scale=0.5, bias_noise=0.2)
+    dense, cat, labels = _batch(N, rs, cfg)
+    L, S = cfg['maxlen'], cfg['seq_num']
+    seqs = [rs.randint(0, 284, size=(N, L)).astype(np.int32) for _ in range(S)]
+    if S > 1:
+        seqs[1][::2] = 0
+    if front_pad:
+        seqs[0][: N // 3, : (2 * L) // 3] = 0
+    tr = DeviceSimTrainer(cfg, w, max_batch=N, algo=algo)
     t = lambda a: torch.from_numpy(a).cuda()
     dseqs = [t(q) for q in seqs] if algo != 'dnn' else None
     loss = tr.grad(t(dense), t(cat), t(labels), dseqs, dropout_rate=rate, seed=5, step=2)
@@ -71,7 +93,9 @@ def _check_simnet_gradients(algo, rate, N):
         assert not np.array_equal(m1, m2)
         keep = np.mean(m1)
         assert abs(keep - (1 - rate)) < 0.02
-    loss_ref, g_ref = loss_and_grad(algo, w, dense, cat, labels, seqs, m1, m2, rate)
+    key = ('simnet', algo, tuple(sorted(cfg.items())), N, rate, front_pad)
+    loss_ref, g_ref = _reference(key, (m1, m2), lambda: loss_and_grad(algo, w, dense, cat, labels, seqs, m1, m2, rate,
+                                                                      class_num=cfg['class_num']))
     assert abs(float(loss.item()) - loss_ref) < 1e-5 * max(1.0, abs(loss_ref))
     assert set(g) == set(g_ref)
     for k in g_ref:
@@ -201,27 +225,34 @@ def test_dien_gradients_in_both_recurrence_tile_forms(recur_rows, rows, N):
     _check_dien_gradients(0.2, N)
 
 
-def _check_dien_gradients(rate, N):
+def _check_dien_gradients(rate, N, cfg=DIEN_CFG):
+    """cfg: any configuration rl4rs_dientrain_create admits.  Inputs: front-padded histories in the first third of the rows of
+    sequence input 0 (every step of them but the last at maxlen <= 20), every other row of input 1 all zero (seq_num > 1), the
+    last (up to) 11 category ids item ids (the query reads the last 10)."""
     import torch
     from rl4rs_amd.nets.dien import init_dien_weights
     from rl4rs_amd.device import DeviceDienTrainer
     from oracle.dien import loss_and_grad
     rs = np.random.RandomState(7)
-    w = init_dien_weights(DIEN_CFG, seed=3, emb_scale=0.5, bias_noise=0.2)
-    dense, cat, labels = _batch(N, rs)
-    cat[:, 10:] = rs.randint(0, 284, size=(N, 11))
-    seq = rs.randint(0, 284, size=(N, 2, 64)).astype(np.int32)
-    seq[: N // 3, 0, :20] = 0
-    seq[::2, 1, :] = 0
-    tr = DeviceDienTrainer(DIEN_CFG, w, max_batch=N)
+    w = init_dien_weights(cfg, seed=3, emb_scale=0.5, bias_noise=0.2)
+    dense, cat, labels = _batch(N, rs, cfg)
+    L, S, Cn = cfg['maxlen'], cfg['seq_num'], cfg['category_feature_num']
+    nq = min(11, Cn)
+    cat[:, Cn - nq:] = rs.randint(0, 284, size=(N, nq))
+    seq = rs.randint(0, 284, size=(N, S, L)).astype(np.int32)
+    seq[: N // 3, 0, :min(20, L - 1)] = 0
+    if S > 1:
+        seq[::2, 1, :] = 0
+    tr = DeviceDienTrainer(cfg, w, max_batch=N)
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
-    dseqs = [t(seq[:, i]) for i in range(2)]
+    dseqs = [t(seq[:, i]) for i in range(S)]
     loss = tr.grad(t(dense), t(cat), t(labels), dseqs, dropout_rate=rate, seed=5, step=2)
     g = dict((k, v.cpu().numpy()) for k, v in tr.gradients().items())
     m1 = m2 = None
     if rate > 0:
         m1, m2 = [m.cpu().numpy().astype(np.float64) for m in tr.masks(N)]
-    loss_ref, g_ref = loss_and_grad(w, DIEN_CFG, seq, dense, cat, labels, m1, m2, rate)
+    key = ('dien', tuple(sorted(cfg.items())), N, rate)
+    loss_ref, g_ref = _reference(key, (m1, m2), lambda: loss_and_grad(w, cfg, seq, dense, cat, labels, m1, m2, rate))
     assert abs(float(loss.item()) - loss_ref) < 1e-5 * max(1.0, abs(loss_ref))
     assert set(g) == set(g_ref)
     for k in sorted(g_ref):
