@@ -520,6 +520,10 @@ int rl4rs_set_host_mirror(int32_t on);
 typedef struct rl4rs_policy rl4rs_policy;
 
 int rl4rs_policy_param_count(int32_t obs_dim, int32_t hidden, int32_t action_size);
+/* Limits: obs_dim > 0, 0 < hidden <= 1024, action_size > 1, and 16 * (obs_dim + hidden + 2 * (action_size + 1)) bytes <= 160 KB,
+ * the LDS of one workgroup that the one-wave training kernel needs (obs_dim 256 / hidden 64: action_size <= 4959); create refuses
+ * other shapes.  The tiled kernels (hidden % 64 == 0, hidden / 32 in {2, 4, 8}, obs_dim % 32 == 0, ...) run an entry point only
+ * where their own LDS for it fits too; elsewhere the one-wave kernels do. */
 int rl4rs_policy_create(int32_t obs_dim, int32_t hidden, int32_t action_size, int32_t max_rows,
                         const float* params_host, void* stream, rl4rs_policy** out);
 int rl4rs_policy_destroy(rl4rs_policy* pol);
@@ -591,7 +595,7 @@ int rl4rs_policy_status_words(rl4rs_policy* pol, uint32_t** words_dev);
  * Kernel-path selection of ONE handle, for A/B measurements and tests (defaults in brackets):
  *   TILE          [1] 0 = one-wave-per-sample forward / loss kernels instead of k_policy_tile
  *   PPO_FUSED     [1] 0 = per-minibatch kernel chain instead of the persistent k_ppo_pass
- *   PPO_ROWS      [automatic] samples per workgroup of k_ppo_pass: 8, 16 or 32 pin the all-runtime instantiation's (automatic: 8);
+ *   PPO_ROWS      [0 = automatic] samples per workgroup of k_ppo_pass: 8, 16 or 32 pin the all-runtime instantiation's (automatic: 8);
  *                     where the compile-time instantiation applies: 4 or 8 (automatic: 4 while MB / 4 <= 126 workgroups, else 8)
  *   RESIDENT_WGS [-1] >= 0: pretend the device holds only this many workgroups of k_ppo_pass at once (co-residency tests)
  *   PPO_STD       [1] 0 = the all-runtime instantiation of k_ppo_pass even at the default shape (256 -> 64 -> 284 + 1, 8 rows,

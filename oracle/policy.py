@@ -19,28 +19,33 @@ def _split(flat, od, hid, A):
     return W1, b1, W2, b2
 
 
-def forward(flat, obs, mask, od=256, hid=64, A=284):
-    """-> masked logits [N,A] (float64), value [N].  mask: [N,A] in {0,1} or None."""
-    W1, b1, W2, b2 = _split(np.asarray(flat, dtype=np.float64), od, hid, A)
-    h = np.tanh(np.asarray(obs, dtype=np.float64) @ W1 + b1)
+def forward(flat, obs, mask, od=256, hid=64, A=284, dtype=np.float64):
+    """-> masked logits [N,A], value [N] in ``dtype`` (float64; float32 evaluates the same formula in single precision, for
+    the tests' error bars).  mask: [N,A] in {0,1} or None."""
+    W1, b1, W2, b2 = _split(np.asarray(flat, dtype=dtype), od, hid, A)
+    h = np.tanh(np.asarray(obs, dtype=dtype) @ W1 + b1)
     out = h @ W2 + b2
     logits = out[:, :A]
     if mask is not None:
         with np.errstate(divide='ignore'):
-            logits = logits + np.maximum(np.log(np.asarray(mask, dtype=np.float64)), F32_MIN)   # rllib_mask_model.py:61-62
+            logits = logits + np.maximum(np.log(np.asarray(mask, dtype=dtype)), dtype(F32_MIN))   # rllib_mask_model.py:61-62
     return logits, out[:, A]
 
 
 def log_softmax(l):
-    m = l.max(axis=1, keepdims=True)
-    return l - (m + np.log(np.exp(l - m).sum(axis=1, keepdims=True)))
+    """(l - max) - log(sum(exp(l - max))), tf.nn.log_softmax's form: a row with no allowed action (every logit float32.min)
+    is the uniform -log(A), where l - (max + log(sum)) rounds to 0 for every action."""
+    s = l - l.max(axis=1, keepdims=True)
+    return s - np.log(np.exp(s).sum(axis=1, keepdims=True))
 
 
 def loss_and_grad(algo, flat, obs, mask, actions, adv, ret, old_logp=None, old_value=None, old_logits=None,
-                  vf_coeff=0.5, ent_coeff=0.01, clip=0.3, vf_clip=500.0, kl_coeff=0.2, od=256, hid=64, A=284):
-    """float64 autograd of the A2C (algo 0) / PPO (algo 1) loss -> (grad flat, stats[4] sums)."""
+                  vf_coeff=0.5, ent_coeff=0.01, clip=0.3, vf_clip=500.0, kl_coeff=0.2, od=256, hid=64, A=284, dtype=np.float64):
+    """float64 autograd of the A2C (algo 0) / PPO (algo 1) loss -> (grad flat, stats[4] sums).  dtype=np.float32 evaluates the
+    same formula in single precision (the tests' error bars)."""
     import torch
-    t = lambda x: torch.as_tensor(np.asarray(x), dtype=torch.float64)
+    tdt = torch.float32 if np.dtype(dtype) == np.float32 else torch.float64
+    t = lambda x: torch.as_tensor(np.asarray(x), dtype=tdt)
     p = t(flat).clone().requires_grad_(True)
     ae = A + 1
     o = 0
@@ -100,30 +105,32 @@ def predict_with_mask(scores, obs, location_mask, special_items, page_items=9):
     return action_probs.argmax(axis=1)
 
 
-def rawstate_forward(weights, cat, dense, seqs, mask=None):
+def rawstate_forward(weights, cat, dense, seqs, mask=None, dtype=np.float64):
     """Raw-state policy encoder (rl4rs/nets/rllib/rllib_rawstate_model.py:49-76; PARITY UNPINNED like the rest of this
     module): context = ELU([mean seq embs | dense tower | mean category emb] @ ctx_w + ctx_b); logits = context @ out_w +
     out_b (+ the mask term of rllib_mask_model.py:61-62); value = context @ value_w + value_b.
-    cat [N,Cn] ids, dense [N,Dn], seqs = list of [N,L] ids.  -> masked logits [N,A] float64, value [N]."""
-    w = dict((k, np.asarray(v, dtype=np.float64)) for k, v in weights.items())
+    cat [N,Cn] ids, dense [N,Dn], seqs = list of [N,L] ids.  -> masked logits [N,A], value [N] in ``dtype`` (float64)."""
+    w = dict((k, np.asarray(v, dtype=dtype)) for k, v in weights.items())
     elu = lambda x: np.where(x > 0, x, np.expm1(np.minimum(x, 0)))
     seq_feat = [w['seq_emb'][np.asarray(s, dtype=np.int64)].mean(axis=1) for s in seqs]     # utils.py:57-77
-    d = elu(elu(np.asarray(dense, dtype=np.float64) @ w['dense_w1'] + w['dense_b1']) @ w['dense_w2'] + w['dense_b2'])
+    d = elu(elu(np.asarray(dense, dtype=dtype) @ w['dense_w1'] + w['dense_b1']) @ w['dense_w2'] + w['dense_b2'])
     c = w['cat_emb'][np.asarray(cat, dtype=np.int64)].mean(axis=1)                          # utils.py:7-14
     ctx = elu(np.concatenate(seq_feat + [d, c], axis=1) @ w['ctx_w'] + w['ctx_b'])
     logits = ctx @ w['out_w'] + w['out_b']
     if mask is not None:
         with np.errstate(divide='ignore'):
-            logits = logits + np.maximum(np.log(np.asarray(mask, dtype=np.float64)), F32_MIN)
+            logits = logits + np.maximum(np.log(np.asarray(mask, dtype=dtype)), dtype(F32_MIN))
     return logits, (ctx @ w['value_w'] + w['value_b'])[:, 0]
 
 
 def rawstate_loss_and_grad(algo, weights, cat, dense, seqs, mask, actions, adv, ret, old_logp=None, old_value=None,
-                           old_logits=None, vf_coeff=0.5, ent_coeff=0.01, clip=0.3, vf_clip=500.0, kl_coeff=0.2):
+                           old_logits=None, vf_coeff=0.5, ent_coeff=0.01, clip=0.3, vf_clip=500.0, kl_coeff=0.2, dtype=np.float64):
     """float64 autograd of RLlib's A2C (algo 0) / PPO (algo 1) loss on the raw-state policy (rawstate_forward above) -> dict of
-    gradients (with head_w = [out_w | value_w], head_b = [out_b | value_b]), stats[4] sums."""
+    gradients (with head_w = [out_w | value_w], head_b = [out_b | value_b]), stats[4] sums.  dtype=np.float32: the same formula
+    in single precision."""
     import torch
-    t = lambda x: torch.as_tensor(np.asarray(x), dtype=torch.float64)
+    tdt = torch.float32 if np.dtype(dtype) == np.float32 else torch.float64
+    t = lambda x: torch.as_tensor(np.asarray(x), dtype=tdt)
     w = dict((k, t(v).clone().requires_grad_(True)) for k, v in weights.items())
     elu = torch.nn.functional.elu
     seq_feat = [w['seq_emb'][torch.as_tensor(np.asarray(s), dtype=torch.int64)].mean(dim=1) for s in seqs]

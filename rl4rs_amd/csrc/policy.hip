@@ -68,9 +68,20 @@ __device__ __forceinline__ float wave_sum(float v) {
     return (r0 + r1) + (r2 + r3);
 }
 
+// Log-sum-exp of one row's masked logits as hi + lo, from their max mx and sum se of exp(logit - mx); log-probabilities are
+// lsub(logit, lse) = (logit - hi) - lo.  A row with no allowed action has every logit at float32.min (the mask term swamps the
+// logit), so mx + log(se) rounds back to mx and logit - lse would be 0 for every action; the reference's log-softmax
+// ((logit - mx) - log(se)) gives the uniform -log(A).  Wherever mx + log(se) rounds back to mx (that row above all), hi = mx and
+// lo = log(se); everywhere else lo = 0 and hi = mx + log(se), the single value used before.
+__device__ __forceinline__ float2 row_lse(float mx, float se) {
+    const float ls = logf(se), s = mx + ls;
+    return (s == mx && ls > 0.f) ? make_float2(mx, ls) : make_float2(s, 0.f);
+}
+__device__ __forceinline__ float lsub(float l, float2 lse) { return (l - lse.x) - lse.y; }
+
 // Shared forward of one sample by one wave.  s_obs[OD], s_h[HID], s_out[AE] are this wave's LDS slots.
-// On return: s_h = tanh hidden, s_out[0..A) = masked logits, s_out[A] = value; returns log-sum-exp of the logits.
-__device__ __forceinline__ float policy_row_forward(const PolDims& d, const float* __restrict__ prm,
+// On return: s_h = tanh hidden, s_out[0..A) = masked logits, s_out[A] = value; returns log-sum-exp of the logits (row_lse).
+__device__ __forceinline__ float2 policy_row_forward(const PolDims& d, const float* __restrict__ prm,
                                                     const float* __restrict__ obs_row,
                                                     const uint32_t* __restrict__ mask_row,
                                                     float* s_obs, float* s_h, float* s_out, int lane) {
@@ -108,13 +119,13 @@ __device__ __forceinline__ float policy_row_forward(const PolDims& d, const floa
     float se = 0.f;
     for (int a = lane; a < d.A; a += 64) se += expf(s_out[a] - mx);
     se = wave_sum(se);
-    return mx + logf(se);
+    return row_lse(mx, se);
 }
 
 // Outputs of one sample from its masked logits / value in s_out (shared by the FC policy and the raw-state policy):
 // entropy, optional logits copy, Gumbel-max draw (SAMPLE) or the given action, log-prob, value.
 template <bool SAMPLE>
-__device__ __forceinline__ void policy_row_outputs(const PolDims& d, const float* s_out, float lse, int n, int lane,
+__device__ __forceinline__ void policy_row_outputs(const PolDims& d, const float* s_out, float2 lse, int n, int lane,
                                                    uint32_t seed, uint32_t step, int32_t* __restrict__ actions,
                                                    float* __restrict__ logp, float* __restrict__ value,
                                                    float* __restrict__ entropy, float* __restrict__ logits_out) {
@@ -122,7 +133,7 @@ __device__ __forceinline__ void policy_row_outputs(const PolDims& d, const float
     int best_a = 0x7fffffff;
     for (int a = lane; a < d.A; a += 64) {
         const float l = s_out[a];
-        const float lp = l - lse;
+        const float lp = lsub(l, lse);
         const float p = expf(lp);
         if (p > 0.f) ent -= p * lp;
         if (logits_out) logits_out[(size_t)n * d.A + a] = l;
@@ -146,7 +157,7 @@ __device__ __forceinline__ void policy_row_outputs(const PolDims& d, const float
     }
     if (lane == 0) {
         if (SAMPLE) actions[n] = act;
-        if (logp) logp[n] = s_out[act] - lse;
+        if (logp) logp[n] = lsub(s_out[act], lse);
         if (value) value[n] = s_out[d.A];
         if (entropy) entropy[n] = ent;
     }
@@ -168,7 +179,7 @@ __global__ __launch_bounds__(256) void k_policy_forward(PolDims d, const float* 
     const int n = blockIdx.x * 4 + wave;
     if (n >= N) return;
     const uint32_t* mrow = mask ? mask + (size_t)n * d.W : nullptr;
-    const float lse = policy_row_forward(d, prm, obs + (size_t)n * d.OD, mrow, s_obs, s_h, s_out, lane);
+    const float2 lse = policy_row_forward(d, prm, obs + (size_t)n * d.OD, mrow, s_obs, s_h, s_out, lane);
     policy_row_outputs<SAMPLE>(d, s_out, lse, n, lane, seed, step, actions, logp, value, entropy, logits_out);
 }
 
@@ -201,7 +212,7 @@ __global__ __launch_bounds__(256) void k_rawpolicy_head(PolDims d, int N, const 
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     float se = 0.f;
     for (int a = lane; a < d.A; a += 64) se += expf(s_out[a] - mx);
-    const float lse = mx + logf(wave_sum(se));
+    const float2 lse = row_lse(mx, wave_sum(se));
     policy_row_outputs<SAMPLE>(d, s_out, lse, n, lane, seed, step, actions, logp, value, entropy, logits_out);
 }
 
@@ -223,13 +234,13 @@ __device__ __forceinline__ void store_wt(float* p, float v) {
 }
 
 template <bool WT = false>
-__device__ __forceinline__ float4 policy_row_loss(const PolDims& d, const LossArgs& L, const float* s_out, float lse, int n, int lane,
+__device__ __forceinline__ float4 policy_row_loss(const PolDims& d, const LossArgs& L, const float* s_out, float2 lse, int n, int lane,
                                                   float* s_d, float* __restrict__ dOut) {
     const int act = L.actions[n];
     const float adv = L.adv[n], ret = L.ret[n];
     const float old_lp = L.algo == 1 ? L.old_logp[n] : 0.f, old_v = L.algo == 1 ? L.old_value[n] : 0.f;
     const float v = s_out[d.A];
-    const float lp_a = s_out[act] - lse;
+    const float lp_a = lsub(s_out[act], lse);
     // PPO: this lane's old logits (columns lane, lane + 64, ...) are fetched ONCE, all loads in flight together; the four
     // passes below then run from registers (columns past 64 * OLR fall back to memory)
     constexpr int OLR = 8;
@@ -241,7 +252,8 @@ __device__ __forceinline__ float4 policy_row_loss(const PolDims& d, const LossAr
         for (int c = 0; c < OLR; ++c) olr[c] = L.old_logits[(size_t)n * d.A + min(lane + 64 * c, d.A - 1)];
     }
     // entropy and (PPO) KL(old || new) need full sums first
-    float ent = 0.f, kl = 0.f, old_lse = 0.f;
+    float ent = 0.f, kl = 0.f;
+    float2 old_lse = make_float2(0.f, 0.f);
     if (L.algo == 1) {
         float om = -3.4028235e38f;
 #pragma unroll
@@ -254,7 +266,7 @@ __device__ __forceinline__ float4 policy_row_loss(const PolDims& d, const LossAr
         for (int c = 0; c < OLR; ++c)
             if (lane + 64 * c < d.A) os += expf(olr[c] - om);
         for (int a = lane + 64 * OLR; a < d.A; a += 64) os += expf(L.old_logits[(size_t)n * d.A + a] - om);
-        old_lse = om + logf(wave_sum(os));
+        old_lse = row_lse(om, wave_sum(os));
     }
     // p = softmax probability and q = old probability of this lane's columns are kept for the gradient pass below (round 5: they
     // were recomputed there - 10 of the 30 libm expf per lane of a 284-action row; same expressions, same values)
@@ -264,12 +276,12 @@ __device__ __forceinline__ float4 policy_row_loss(const PolDims& d, const LossAr
         const int a = lane + 64 * c;
         pr[c] = 0.f; qr[c] = 0.f;
         if (a < d.A) {
-            const float lp = s_out[a] - lse;
+            const float lp = lsub(s_out[a], lse);
             const float p = expf(lp);
             pr[c] = p;
             if (p > 0.f) ent -= p * lp;
             if (L.algo == 1) {
-                const float olp = olr[c] - old_lse;
+                const float olp = lsub(olr[c], old_lse);
                 const float q = expf(olp);
                 qr[c] = q;
                 if (q > 0.f) kl += q * (olp - lp);
@@ -277,11 +289,11 @@ __device__ __forceinline__ float4 policy_row_loss(const PolDims& d, const LossAr
         }
     }
     for (int a = lane + 64 * OLR; a < d.A; a += 64) {
-        const float lp = s_out[a] - lse;
+        const float lp = lsub(s_out[a], lse);
         const float p = expf(lp);
         if (p > 0.f) ent -= p * lp;
         if (L.algo == 1) {
-            const float olp = L.old_logits[(size_t)n * d.A + a] - old_lse;
+            const float olp = lsub(L.old_logits[(size_t)n * d.A + a], old_lse);
             const float q = expf(olp);
             if (q > 0.f) kl += q * (olp - lp);
         }
@@ -315,13 +327,13 @@ __device__ __forceinline__ float4 policy_row_loss(const PolDims& d, const LossAr
     for (int a = lane, c = 0; a < d.AE; a += 64, ++c) {
         float g;
         if (a < d.A) {
-            const float lp = s_out[a] - lse;
+            const float lp = lsub(s_out[a], lse);
             float p, q;
             switch (c) {                // register file is not indexable: select the lane's c-th kept pair
                 case 0: p = pr[0]; q = qr[0]; break; case 1: p = pr[1]; q = qr[1]; break; case 2: p = pr[2]; q = qr[2]; break;
                 case 3: p = pr[3]; q = qr[3]; break; case 4: p = pr[4]; q = qr[4]; break; case 5: p = pr[5]; q = qr[5]; break;
                 case 6: p = pr[6]; q = qr[6]; break; case 7: p = pr[7]; q = qr[7]; break;
-                default: p = expf(lp); q = L.algo == 1 ? expf(L.old_logits[(size_t)n * d.A + a] - old_lse) : 0.f;
+                default: p = expf(lp); q = L.algo == 1 ? expf(lsub(L.old_logits[(size_t)n * d.A + a], old_lse)) : 0.f;
             }
             // d logp_act/dl_a = [a==act] - p ; dH/dl_a = -p (log p + H) ; dKL/dl_a = p - q
             g = g_lp * ((a == act ? 1.f : 0.f) - p);
@@ -363,7 +375,7 @@ __global__ __launch_bounds__(256) void k_policy_train(PolDims d, const float* __
     const int n = blockIdx.x * 4 + wave;
     if (n >= N) return;
     const uint32_t* mrow = mask ? mask + (size_t)n * d.W : nullptr;
-    const float lse = policy_row_forward(d, prm, obs + (size_t)n * d.OD, mrow, s_obs, s_h, s_out, lane);
+    const float2 lse = policy_row_forward(d, prm, obs + (size_t)n * d.OD, mrow, s_obs, s_h, s_out, lane);
     const float4 tm = policy_row_loss(d, L, s_out, lse, n, lane, s_d, dOut);
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -854,7 +866,7 @@ __global__ __launch_bounds__(512) void k_policy_tile(TileArgs a) {
         mx = wave_max(mx);
         float se = 0.f;
         for (int c = lane; c < d.A; c += 64) se += expf(so[c] - mx);
-        const float lse = mx + logf(wave_sum(se));
+        const float2 lse = row_lse(mx, wave_sum(se));
         if (MODE != 2) {
             if (row < nrow)
                 policy_row_outputs<MODE == 0>(d, so, lse, r0 + row, lane, a.seed, a.step, a.actions, a.logp, a.value, a.entropy, a.logits_out);
@@ -905,6 +917,9 @@ __global__ __launch_bounds__(512) void k_policy_tile(TileArgs a) {
 
 using namespace rl4rs;
 
+// LDS of one workgroup on gfx950 (the shape-sized policy kernels hold no static LDS, so all of it is dynamic)
+constexpr size_t POLICY_LDS_MAX = (size_t)160 * 1024;
+
 struct rl4rs_policy {
     PolDims d;
     int max_rows, n_params, nz, chunk;
@@ -932,6 +947,13 @@ int rl4rs_policy_create(int32_t obs_dim, int32_t hidden, int32_t action_size, in
                         const float* params_host, void* stream, rl4rs_policy** out) {
     RL4RS_REQUIRE(out && params_host && obs_dim > 0 && hidden > 0 && hidden <= 1024 && action_size > 1 && max_rows > 0,
                   "policy_create: bad argument");
+    // k_policy_train (fwd_smem(d, AE): 4 waves x [obs | hidden | out | d out]) is the largest form any entry point may need; a shape
+    // the tiled kernels take always fits it too, so a shape it does not fit cannot be trained at all
+    const size_t train_lds = (size_t)16 * ((size_t)obs_dim + hidden + 2 * ((size_t)action_size + 1));
+    RL4RS_REQUIRE(train_lds <= POLICY_LDS_MAX,
+                  "policy_create: obs_dim %d, hidden %d, action_size %d need %zu bytes of LDS per workgroup, more than the %zu one "
+                  "workgroup can use (obs_dim + hidden + 2 * (action_size + 1) must be <= %zu)", obs_dim, hidden, action_size, train_lds,
+                  POLICY_LDS_MAX, POLICY_LDS_MAX / 16);
     if (rl4rs_device_count() <= 0) {
         set_error("no HIP device visible: librl4rs_hip has no CPU fallback");
         return RL4RS_EHIP;
@@ -1017,15 +1039,17 @@ static size_t fwd_smem(const PolDims& d, int extra) { return (size_t)4 * (d.OD +
 
 namespace {
 
-// does k_policy_tile's tiling fit this policy?  (RL4RS_POLICY_OPT_TILE = 0 keeps the one-wave-per-sample kernels: A/B measurements)
-bool tile_fits(const rl4rs_policy* p) {
-    const PolDims& d = p->d;
-    const int NT1 = d.HID / 32;
-    return p->opt_tile && d.HID % 64 == 0 && (NT1 == 1 || NT1 == 2 || NT1 == 4 || NT1 == 8) && d.OD % 32 == 0 && (d.OD / (8 / NT1)) % 64 == 0;
-}
 size_t tile_smem(const PolDims& d, int mode) {
     return (size_t)(8 * ((d.OD | 1) + (d.HID | 1) + (mode == 2 ? 2 : 1) * (d.AE | 1) + d.W) + 8 * 1024) * 4;
 }
+// does k_policy_tile<mode>'s tiling fit this shape, its LDS included?
+bool tile_shape_fits(const PolDims& d, int mode) {
+    const int NT1 = d.HID / 32;
+    return d.HID % 64 == 0 && (NT1 == 1 || NT1 == 2 || NT1 == 4 || NT1 == 8) && d.OD % 32 == 0 && (d.OD / (8 / NT1)) % 64 == 0 &&
+           tile_smem(d, mode) <= POLICY_LDS_MAX;
+}
+// (RL4RS_POLICY_OPT_TILE = 0 keeps the one-wave-per-sample kernels: A/B measurements)
+bool tile_fits(const rl4rs_policy* p, int mode) { return p->opt_tile && tile_shape_fits(p->d, mode); }
 // the default shape takes the 4x4x1 form (policy_tile_std.hpp); RL4RS_POLICY_OPT_PPO_STD = 0 keeps the 32x32x2 one for A/B runs
 bool tile_is_std(const rl4rs_policy* p) {
     const PolDims& d = p->d;
@@ -1059,7 +1083,7 @@ int rl4rs_policy_act(rl4rs_policy* p, int32_t N, const float* obs, const uint32_
                      uint32_t step, int32_t* actions, float* logp, float* value, float* entropy, float* logits,
                      void* stream) {
     RL4RS_REQUIRE(p && obs && actions && N > 0, "policy_act: bad argument");
-    if (tile_fits(p)) {
+    if (tile_fits(p, 0)) {
         TileArgs a;
         memset(&a, 0, sizeof(a));
         a.d = p->d; a.N = N; a.prm = p->params; a.obs = obs; a.mask = mask_bits; a.seed = seed; a.step = step;
@@ -1076,7 +1100,7 @@ int rl4rs_policy_evaluate(rl4rs_policy* p, int32_t N, const float* obs, const ui
                           const int32_t* actions, float* logp, float* value, float* entropy, float* logits,
                           void* stream) {
     RL4RS_REQUIRE(p && obs && actions && N > 0, "policy_evaluate: bad argument");
-    if (tile_fits(p)) {
+    if (tile_fits(p, 1)) {
         TileArgs a;
         memset(&a, 0, sizeof(a));
         a.d = p->d; a.N = N; a.prm = p->params; a.obs = obs; a.mask = mask_bits;
@@ -1105,7 +1129,7 @@ int rl4rs_policy_loss_grad(rl4rs_policy* p, int32_t algo, int32_t N, const float
     L.actions = actions; L.adv = adv; L.ret = ret; L.old_logp = old_logp; L.old_value = old_value; L.old_logits = old_logits;
     const size_t w2_bytes = (size_t)d.HID * d.AE * 4;
     const int stage_w2 = (fwd_smem(d, d.AE) + w2_bytes <= (size_t)150 * 1024) ? 1 : 0;
-    const bool tiled = tile_fits(p);
+    const bool tiled = tile_fits(p, 2);
     if (tiled) {
         hipLaunchKernelGGL(k_w2_transpose, dim3((d.HID * d.AE + 255) / 256), dim3(256), 0, st, p->params + (size_t)d.OD * d.HID + d.HID,
                            d.HID, d.AE, p->w2t);
@@ -1590,7 +1614,8 @@ int rl4rs_policy_set_option(rl4rs_policy* p, int32_t which, int32_t value) {
         case RL4RS_POLICY_OPT_TILE: p->opt_tile = value != 0; break;
         case RL4RS_POLICY_OPT_PPO_FUSED: p->opt_ppo_fused = value != 0; break;
         case RL4RS_POLICY_OPT_PPO_ROWS:
-            RL4RS_REQUIRE(value == 4 || value == 8 || value == 16 || value == 32, "policy_set_option: PPO_ROWS must be 4, 8, 16 or 32 (got %d)", value);
+            RL4RS_REQUIRE(value == 0 || value == 4 || value == 8 || value == 16 || value == 32,
+                          "policy_set_option: PPO_ROWS must be 0 (automatic), 4, 8, 16 or 32 (got %d)", value);
             p->opt_ppo_rows = value; p->pass_resident_wgs = -1; break;
         case RL4RS_POLICY_OPT_RESIDENT_WGS: p->opt_resident_cap = value; p->pass_resident_wgs = -1; break;
         case RL4RS_POLICY_OPT_PPO_STD: p->opt_ppo_std = value != 0; break;

@@ -109,7 +109,7 @@ __global__ __launch_bounds__(512) void k_policy_tile_std(TileArgs a) {
         mx = wave_max(mx);
         float se = 0.f;
         for (int c = lane; c < 284; c += 64) se += expf(so[c] - mx);
-        const float lse = mx + logf(wave_sum(se));
+        const float2 lse = row_lse(mx, wave_sum(se));
         if (MODE != 2) {
             if (wave < nrow)
                 policy_row_outputs<MODE == 0>(d, so, lse, r0 + wave, lane, a.seed, a.step, a.actions, a.logp, a.value, a.entropy, a.logits_out);

@@ -463,7 +463,7 @@ __global__ __launch_bounds__(512) void k_ppo_pass(PassArgs a) {
                 mx = wave_max(mx);
                 float se = 0.f;
                 for (int c = lane; c < 284; c += 64) se += expf(so[c] - mx);
-                const float lse = mx + logf(wave_sum(se));
+                const float2 lse = row_lse(mx, wave_sum(se));
                 if (wave == 0) RL4RS_PT(15);
                 const float4 tm = policy_row_loss<RL4RS_PASS_WT != 0>(d, L, so, lse, wave, lane, s_g + wave * 288, a.dOut + (size_t)r0 * AE);
                 if (lane == 0) a.terms[lo + r0 + wave] = tm;       // per-sample loss terms of the whole pass (KL mean -> kl_coeff rule)
@@ -611,7 +611,7 @@ __global__ __launch_bounds__(512) void k_ppo_pass(PassArgs a) {
                     mx = wave_max(mx);
                     float se = 0.f;
                     for (int c = lane; c < d.A; c += 64) se += expf(so[c] - mx);
-                    const float lse = mx + logf(wave_sum(se));
+                    const float2 lse = row_lse(mx, wave_sum(se));
                     const float4 tm = policy_row_loss<RL4RS_PASS_WT != 0>(d, L, so, lse, row, lane, s_d + row * SA, a.dOut + (size_t)r0 * AE);
                     if (lane == 0) a.terms[lo + r0 + row] = tm;       // per-sample loss terms of the whole pass (KL mean -> kl_coeff rule)
                     if (row == 0) RL4RS_PT(11);

@@ -34,7 +34,7 @@ __global__ __launch_bounds__(256) void k_rawpolicy_loss(PolDims d, int N, const 
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     float se = 0.f;
     for (int a = lane; a < d.A; a += 64) se += expf(s_out[a] - mx);
-    const float lse = mx + logf(wave_sum(se));
+    const float2 lse = row_lse(mx, wave_sum(se));
     const float4 tm = policy_row_loss(d, L, s_out, lse, n, lane, s_d, dOut);
     if (lane == 0) terms[n] = tm;
 }

@@ -318,7 +318,11 @@ class Trainer(_DeferredStats):
             # by zero, ranks failing at different points around a collective)
             raise ValueError("PPO needs at least one full minibatch per train call: %d rollouts x batch_size x max_steps = %d < "
                              "minibatch = %d" % (self.R, N, minibatch))
-        self.policy = D.DevicePolicy(256, hidden, self.A, max_rows=N, seed=init_seed)
+        # the observation width the env reports (base.py:206-213): 256 for the DIEN / dnn / lstm simulators, 3072 for widedeep
+        space = env.observation_space
+        space = space.spaces['obs'] if hasattr(space, 'spaces') else space
+        self.OD = int(space.shape[0])
+        self.policy = D.DevicePolicy(self.OD, hidden, self.A, max_rows=N, seed=init_seed)
         share = rdist.ranks_sharing_device()
         if share > 1:
             # several ranks on ONE GPU (gloo dry runs only): the persistent PPO pass may use its grid barrier only while the grids of
@@ -328,7 +332,7 @@ class Trainer(_DeferredStats):
         self.iteration = 0
         self._rollouts = 0
         dev = self.policy.device
-        self.buf = dict(obs=torch.empty((N, 256), dtype=torch.float32, device=dev),
+        self.buf = dict(obs=torch.empty((N, self.OD), dtype=torch.float32, device=dev),
                         mask=torch.empty((N, self.policy.W), dtype=torch.int32, device=dev),
                         act=torch.empty(N, dtype=torch.int32, device=dev),
                         logp=torch.empty(N, dtype=torch.float32, device=dev),
