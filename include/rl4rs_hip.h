@@ -970,6 +970,96 @@ int rl4rs_gemm_h16_packed(const float* a_dev, int64_t lda, const float* w_host, 
  * (pack_gemm_weight_h16, used when a scorer is loaded): number of 32-bit words that differ, 0 = bit-identical. */
 int rl4rs_pack_h16_selftest(const float* w_host, int64_t ldw, int32_t K, int32_t N, int64_t* mismatches, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Off-policy evaluation: the estimators of rl4rs/utils/offline_policy_metrics.py:8-184 over the per-step log that
+ * script/offline_evaluation.py:16-36 (ope_eval) collects, and the propensity rules of rl4rs/policy/policy_model.py:75-83 and
+ * rl4rs/policy/behavior_model.py:44-58.  The reference pulls a [B, A] probability matrix to the host at every step and runs its
+ * numpy passes over [B, T] arrays per epoch; here one step's record is a few [B] columns written into a [T, B] float64 log
+ * owned by the handle, and one epoch's estimate is four launches that end in one vector of float64 statistics.  All arithmetic
+ * is float64; sums over episodes are reduced per wave, per block, then over the block partials in a fixed order (no atomics): the
+ * result is bit-identical from run to run and the same for the handle and the array forms.  Variances are two-pass.
+ * ---------------------------------------------------------------------------------------------- */
+
+typedef struct rl4rs_ope rl4rs_ope;
+
+/* columns of the handle's log, each [T, B] float64 */
+enum {
+    RL4RS_OPE_COL_PI = 0,         /* evaluated policy's probability of the logged action   offline_evaluation.py:27-30 */
+    RL4RS_OPE_COL_MU = 1,         /* logged policy's probability of the logged action      offline_evaluation.py:31-32 */
+    RL4RS_OPE_COL_Q = 2,          /* policy.predict_q(obs, action)                         offline_evaluation.py:29 */
+    RL4RS_OPE_COL_REWARD = 3,     /* the simulator's reward of the evaluated action        offline_evaluation.py:33,35 */
+    RL4RS_OPE_COL_LOGGED_REWARD = 4, /* eval_env.offline_reward                            offline_evaluation.py:34 */
+    RL4RS_OPE_N_COLS = 5
+};
+
+/* slots of the statistics vector (host double[RL4RS_OPE_N_STATS]); a slot whose inputs were not given is NaN */
+enum {
+    RL4RS_OPE_CIPS = 0,           /* eval_CIPS: E_t over ratios clipped to [0.1, 10]       offline_policy_metrics.py:69-94 */
+    RL4RS_OPE_CIPS_C = 1,         /*   its confidence half-width cv * stddev / sqrt(int(n_e)) */
+    RL4RS_OPE_IPS = 2,            /* eval_IPS (unclipped ratios, their own n_e and cv)     offline_policy_metrics.py:47-66 */
+    RL4RS_OPE_IPS_C = 3,
+    RL4RS_OPE_SNIPS = 4,          /* eval_SNIPS                                            offline_policy_metrics.py:97-122 */
+    RL4RS_OPE_SNIPS_C = 5,
+    RL4RS_OPE_DR = 6,             /* eval_doubly_robust: mean(dr) / mean(rewards)          offline_policy_metrics.py:145-162 */
+    RL4RS_OPE_DR_SE = 7,          /*   scipy.stats.sem(dr) (ddof = 1; NaN for one episode) */
+    RL4RS_OPE_WIPS = 8,           /* eval_WIPS(gamma)                                      offline_policy_metrics.py:125-142 */
+    RL4RS_OPE_WIPS_2 = 9,         /*   the reference's constant second element, 0 */
+    RL4RS_OPE_SEQDR = 10,         /* eval_seq_doubly_robust                                offline_policy_metrics.py:165-184 */
+    RL4RS_OPE_SEQDR_2 = 11,       /*   0 */
+    RL4RS_OPE_N_E = 12,           /* effective sample size of the clipped ratios           offline_policy_metrics.py:34 */
+    RL4RS_OPE_CV = 13,            /* t.ppf(1 - 0.00125, int(n_e) - 1) for it               offline_policy_metrics.py:37-38 */
+    RL4RS_OPE_N_E_RAW = 14,       /* the same two for the unclipped ratios (eval_IPS) */
+    RL4RS_OPE_CV_RAW = 15,
+    RL4RS_OPE_SIM_REWARD = 16,    /* mean over episodes of the summed simulator reward     offline_evaluation.py:38-39 */
+    RL4RS_OPE_N_STATS = 17
+};
+
+/* scipy.stats.t.ppf(p, df) (offline_policy_metrics.py:38): quantile of Student's t, host arithmetic (regularised incomplete
+ * beta, bisection); NaN for df <= 0 or p outside [0, 1] like scipy, and for df = +inf (scipy: the normal quantile; the
+ * estimators never get there, df < 2^28).  Needs no device. */
+double rl4rs_student_t_ppf(double p, double df);
+
+/* A log for up to max_batch episodes of up to max_steps steps (max_steps <= 256: one lane walks an episode's steps). */
+int rl4rs_ope_create(int32_t max_batch, int32_t max_steps, rl4rs_ope** out);
+int rl4rs_ope_destroy(rl4rs_ope* h);
+/* Start an epoch of B episodes x T steps (offline_evaluation.py:17-20): forgets what was recorded. */
+int rl4rs_ope_begin(rl4rs_ope* h, int32_t B, int32_t T);
+
+/* pi[t, b] from the learner's score matrix scores_dev [B, A] float32 (row stride ld floats) and the logged action action_dev [B]
+ * int32 (offline_evaluation.py:27-28: action_prob[range(batch_size), off_action]).  is_logits = 0: the scores are probabilities,
+ * taken as they are; 1: Q values / logits, pi = softmax(scores[b])[a] (policy_model.py:78-82) computed per row in float64
+ * without the [B, A] softmax.  An action outside [0, A) gives NaN (the reference raises IndexError). */
+int rl4rs_ope_record_policy(rl4rs_ope* h, int32_t t, const float* scores_dev, int32_t A, int64_t ld, const int32_t* action_dev,
+                            int32_t is_logits, void* stream);
+/* mu[t, b] = y[b, lo + clip(a - lo, 0, hi - lo - 1)] / sum(y[b, lo:hi]) from a behaviour score matrix y_dev [B, A_b] float32
+ * (behavior_model.py:49-58; the caller maps `layer` to [lo, hi)).  is_logits = 1: exp(y_a - m) / sum_{[lo, hi)} exp(y - m), m the
+ * maximum over the range: a full softmax followed by the reference's renormalisation, without the intermediate. */
+int rl4rs_ope_record_behavior(rl4rs_ope* h, int32_t t, const float* y_dev, int32_t A_b, int64_t ld, int32_t lo, int32_t hi,
+                              const int32_t* action_dev, int32_t is_logits, void* stream);
+/* Column `col` (RL4RS_OPE_COL_*) of step t from a device array src_dev [B], float32 (src_is_f64 = 0) or float64 (1). */
+int rl4rs_ope_record_column(rl4rs_ope* h, int32_t t, int32_t col, const void* src_dev, int32_t src_is_f64, void* stream);
+/* Q[t, b] = scores_dev[b, action_dev[b]] (AlgoBase.predict_value of a discrete Q learner, policy_model.py:55-61) */
+int rl4rs_ope_record_q(rl4rs_ope* h, int32_t t, const float* scores_dev, int32_t A, int64_t ld, const int32_t* action_dev,
+                       void* stream);
+/* Device address of one column's [T, B] float64 log (T, B of the last rl4rs_ope_begin). */
+int rl4rs_ope_log(rl4rs_ope* h, int32_t col, double** dev_out, int64_t* n_out);
+
+/* One epoch's estimators from the log, assembled like offline_evaluation.py:38-67: the per-episode products of probs * 100, the
+ * summed logged reward, the summed simulator reward as DR's action_rhat_rewards and the per-episode mean Q as its
+ * state_rewards.  Waits for `stream`; stats_host double[RL4RS_OPE_N_STATS].  Slots whose columns are incomplete are NaN. */
+int rl4rs_ope_estimate(rl4rs_ope* h, double gamma, double* stats_host, void* stream);
+
+/* The same estimators on caller-supplied float64 device arrays, without a handle (they allocate their scratch).
+ * Per-episode arrays [B]: eval_IPS / eval_CIPS / eval_SNIPS(rewards, policy_prob, behavior_prob) and
+ * eval_doubly_robust(action_rhat_rewards, state_rewards, rewards, ...); rhat_dev / state_dev may be NULL (DR slots NaN). */
+int rl4rs_ope_episode_stats(int32_t B, const double* rewards_dev, const double* policy_prob_dev, const double* behavior_prob_dev,
+                            const double* rhat_dev, const double* state_dev, double* stats_host, void* stream);
+/* Per-step arrays [B, T] row-major: eval_WIPS(step_rewards, policy_prob, behavior_prob, gamma) and
+ * eval_seq_doubly_robust(action_rhat_rewards, state_rewards, rewards = step_rewards, ...); rhat / state may be NULL. */
+int rl4rs_ope_step_stats(int32_t B, int32_t T, const double* step_rewards_dev, const double* policy_prob_dev,
+                         const double* behavior_prob_dev, const double* rhat_dev, const double* state_dev, double gamma,
+                         double* stats_host, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -284,7 +284,24 @@ SIGNATURES = {
     'rl4rs_gemm_f32_packed': (_I, [_P, _I64, _P, _I64, _P, _P, _I64, _I32, _I32, _I32, _I, _P]),
     'rl4rs_gemm_h16_packed': (_I, [_P, _I64, _P, _I64, _P, _P, _I64, _I32, _I32, _I32, _I, _P]),
     'rl4rs_gemm_f32': (_I, [_P, _I64, _P, _I64, _P, _P, _I64, _I32, _I32, _I32, _I, _P]),
+    'rl4rs_student_t_ppf': (C.c_double, [C.c_double, C.c_double]),
+    'rl4rs_ope_create': (_I, [_I32, _I32, C.POINTER(_P)]),
+    'rl4rs_ope_destroy': (_I, [_P]),
+    'rl4rs_ope_begin': (_I, [_P, _I32, _I32]),
+    'rl4rs_ope_record_policy': (_I, [_P, _I32, _P, _I32, _I64, _P, _I32, _P]),
+    'rl4rs_ope_record_behavior': (_I, [_P, _I32, _P, _I32, _I64, _I32, _I32, _P, _I32, _P]),
+    'rl4rs_ope_record_column': (_I, [_P, _I32, _I32, _P, _I32, _P]),
+    'rl4rs_ope_record_q': (_I, [_P, _I32, _P, _I32, _I64, _P, _P]),
+    'rl4rs_ope_log': (_I, [_P, _I32, C.POINTER(_P), C.POINTER(_I64)]),
+    'rl4rs_ope_estimate': (_I, [_P, C.c_double, C.POINTER(C.c_double), _P]),
+    'rl4rs_ope_episode_stats': (_I, [_I32, _P, _P, _P, _P, _P, C.POINTER(C.c_double), _P]),
+    'rl4rs_ope_step_stats': (_I, [_I32, _I32, _P, _P, _P, _P, _P, C.c_double, C.POINTER(C.c_double), _P]),
 }
+
+# include/rl4rs_hip.h RL4RS_OPE_COL_* / RL4RS_OPE_* (statistics slots)
+OPE_COLS = {'pi': 0, 'mu': 1, 'q': 2, 'reward': 3, 'logged_reward': 4}
+OPE_STATS = ('cips', 'cips_c', 'ips', 'ips_c', 'snips', 'snips_c', 'dr', 'dr_se', 'wips', 'wips_2', 'seqdr', 'seqdr_2', 'n_e', 'cv',
+             'n_e_raw', 'cv_raw', 'sim_reward')
 
 
 def load():
