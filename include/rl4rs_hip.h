@@ -245,7 +245,9 @@ typedef struct rl4rs_dien_cfg {
  *                   per CU) instead of k_cat_attn2 (half-K image, 16+ rows per CU; E = 128 and Cn <= 24 only)
  *   NO_CAT_GROUP    launches whose rows come in groups of 8 or 9 per cache slot (the reward forward over the complete states):
  *                   category branch per row (k_cat_attn2) instead of one workgroup per group that gathers the category rows the
- *                   group shares once (k_cat_attn2g; a group that shares nothing takes the per-row body inside it) (=) */
+ *                   group shares once (k_cat_attn2g; a group that shares nothing takes the per-row body inside it) (=)
+ *   NO_GEMM_GROUP   the chained dense tower and the q-side term of the DIN scores (independent GEMMs, half-chip grids at observation
+ *                   size) as two launches instead of one grid that holds both problems' workgroups (k_gemm_h16_pair) (=) */
 enum {
     RL4RS_DIEN_OPT_AUGRU_H16 = 1 << 0,
     RL4RS_DIEN_OPT_AUGRU_ROWS32 = 1 << 1,
@@ -263,7 +265,9 @@ enum {
     RL4RS_DIEN_OPT_DENSE_FORK = 1 << 13,       /* the dense tower on a second stream of the handle, joined in front of the head GEMM */
     RL4RS_DIEN_OPT_NO_GRU_PAD = 1 << 14,       /* first GRU: compute the steps on leading zero ids (front padding) per row instead of
                                                   taking them from the handle's table of pad states (bit-identical either way) */
-    RL4RS_DIEN_OPT_ALL = (1 << 15) - 1
+    RL4RS_DIEN_OPT_NO_GEMM_GROUP = 1 << 15,    /* fp16x2 mode: the dense tower and the q-side term of the DIN scores as two launches
+                                                  instead of one grid that holds both problems' workgroups (bit-identical either way) */
+    RL4RS_DIEN_OPT_ALL = (1 << 16) - 1
 };
 
 /* Every mode accumulates in fp32 and meets the fp32 parity bar against the fp64 oracle (same measured error):

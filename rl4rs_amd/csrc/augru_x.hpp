@@ -73,6 +73,12 @@ constexpr bool after_barrier(int i) { return i == 0 || i == 24 || i == 40; }
 #ifndef RL4RS_X_SPLITPAIR
 #define RL4RS_X_SPLITPAIR 1     // plane_store through split_h16_pair (v_cvt_pk_f16_f32 + v_fma_mix_f32: 2 VALU per element instead of
 #endif                          // ~3; same roundings, bit-identical planes; same-box A/B: 0.8595 -> 0.8503 ms per launch) - 0: the C++ casts
+#ifndef RL4RS_X_PEEL
+#define RL4RS_X_PEEL 1          // boundary steps without their vanishing products (see "BOUNDARY STEPS" at the step loop); 0: every step runs all
+#endif                          // 48 items.  RL4RS_X_PEEL_MT2: the same switch for the 64-row form alone
+#ifndef RL4RS_X_PEEL_MT2
+#define RL4RS_X_PEEL_MT2 RL4RS_X_PEEL
+#endif
 #ifndef RL4RS_X_AMAX
 #define RL4RS_X_AMAX 0          // 1: track max |h| over the steps for the range check (0: the final state alone decides, see the epilogue)
 #endif
@@ -133,6 +139,7 @@ __global__ __launch_bounds__(512) void k_augru_x(RecurArgs a) {
     constexpr int NS = NI - NRES, LA = RING - 1, WINDOW = 40 - NRES;     // WINDOW: the item the projection requests are issued in front of
 #endif
     constexpr Sched SC = make_sched<NRES>();
+    constexpr bool PEEL = MT == 1 ? RL4RS_X_PEEL != 0 : RL4RS_X_PEEL_MT2 != 0;
     static_assert(NS > 0 && NS % RING == 0 && RING >= 2 && NRES >= 1 && NRES <= 14 && (!RL4RS_X_SPREAD || NI % NRES == 0), "weight ring / resident items");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // planes in slab order [kb 16][k-half 2][row 32][8 halfs]; tile m's four planes (h hi/lo, r*h hi/lo) at m * 4 * PLANE
@@ -234,11 +241,13 @@ __global__ __launch_bounds__(512) void k_augru_x(RecurArgs a) {
 #pragma unroll
     for (int i = 0; i < NI; ++i)
         if (is_res<NRES>(i)) wload(i, res_h[SC.res_idx[i]], res_l[SC.res_idx[i]]);
+    if constexpr (!PEEL) {
 #pragma unroll
-    for (int k = 0; k < LA; ++k) {
-        const int js = (SC.js_first + k) % NS;
-        wload(SC.item_of[js], ring_h[js % RING], ring_l[js % RING]);
-    }
+        for (int k = 0; k < LA; ++k) {
+            const int js = (SC.js_first + k) % NS;
+            wload(SC.item_of[js], ring_h[js % RING], ring_l[js % RING]);
+        }
+    }                                                              // (PEEL: step 0's first streamed item is 40; its look-ahead requests ride in step 0's own slots)
 #pragma unroll
     for (int m = 0; m < MT; ++m) {
         att_cur[m] = att_row[m][0];
@@ -322,15 +331,12 @@ __global__ __launch_bounds__(512) void k_augru_x(RecurArgs a) {
     if (!early) __builtin_amdgcn_s_setprio(RL4RS_X_PRIO);
 #endif
     const int TL = a.steps > 0 ? a.steps : L;
-#pragma unroll 1
-    for (int t = 0; t < TL; ++t) {
-        asm volatile("" : "+s"(sb_r), "+s"(sb_u), "+s"(sb_c));     // keep the per-item scalar offsets out of SGPR-hoisting
-        RL4RS_XT(0);
+    // items [lo, hi) of step t.  light: the items' matrix products are known to vanish or to be dead (BOUNDARY STEPS below) - no
+    // MFMAs, no state-fragment reads and no weight requests for them; projections, epilogues, plane stores, barriers and the
+    // projection issue window stay in their slots
+    auto items = [&](const int t, const int lo, const int hi, const bool light) __attribute__((always_inline)) {
 #pragma unroll
-        for (int m = 0; m < MT; ++m) oma[m] = 1.0f - att_cur[m];
-        hfrag(0, 0);
-#pragma unroll
-        for (int i = 0; i < NI; ++i) {
+        for (int i = lo; i < hi; ++i) {
             const int g = gate(i), cur = i & 1;
             if (i == 8) RL4RS_XT(1);
             if (i == RL4RS_X_XU_AT) {
@@ -361,7 +367,7 @@ __global__ __launch_bounds__(512) void k_augru_x(RecurArgs a) {
                     __builtin_amdgcn_s_setprio(1);        // ... and then must not lose every MFMA arbitration to the (older) early wave
 #endif
                 }
-                hfrag(cur, i);
+                if (!light) hfrag(cur, i);
             }
             if (i == 40) {
                 if (early) {
@@ -375,30 +381,35 @@ __global__ __launch_bounds__(512) void k_augru_x(RecurArgs a) {
 #endif
                 if (!(RL4RS_X_AB & 16)) __syncthreads();           // early half of the new state complete
                 RL4RS_XT(5);
-                if (!(RL4RS_X_AB & (4 | 128))) {                  // x_r(t+1) (requested 12+ items ago)
+                if (!(RL4RS_X_AB & (4 | 128)) && !light) {        // x_r(t+1) (requested 12+ items ago)
 #pragma unroll
                     for (int m = 0; m < MT; ++m) x_read(acc_r[m], 0, m);
                 }
-                hfrag(cur, i);
+                if (!light) hfrag(cur, i);
             }
             if (i == WINDOW && t + 1 < L && !(RL4RS_X_AB & (4 | 64))) {       // 64: no projection DMA (reads keep going)
                 // ---- the ONE projection issue window of the step: the register-resident items follow (no vector-memory wait)
+                // (light: no MFMA has waited for the x_u / x_c reads above yet - they must have left the staging before it is rewritten)
+                if (light) __builtin_amdgcn_s_waitcnt(0xc07f);            // lgkmcnt(0)
                 x_dma(t + 1);
 #pragma unroll
                 for (int m = 0; m < MT; ++m) att_next[m] = att_row[m][t + 1];
             }
             // ---- fetch ahead: state fragments of the next item, streamed weights LA items ahead
-            if (i + 1 < NI && !after_barrier(i + 1) && !(RL4RS_X_AB & 8)) hfrag(cur ^ 1, i + 1);
+            if (i + 1 < NI && !after_barrier(i + 1) && !(RL4RS_X_AB & 8) && !light) hfrag(cur ^ 1, i + 1);
             const bool resident = is_res<NRES>(i);
             const int js = resident ? 0 : SC.js_of[i];             // position in the streamed sequence (if streamed)
             const int ridx = resident ? SC.res_idx[i] : 0;
-            if (!resident && !(RL4RS_X_AB & 2)) wload(SC.item_of[(js + LA) % NS], ring_h[(js + LA) % RING], ring_l[(js + LA) % RING]);
+            const int ahead = resident ? 0 : SC.item_of[(js + LA) % NS];
+            // light: nothing for an item that is skipped itself (below 40 in the first step; the last step's tail requests nothing at all)
+            const bool fetch = !resident && !(RL4RS_X_AB & 2) && !(light && (i >= 40 || (ahead > i && ahead < 40)));
+            if (fetch) wload(ahead, ring_h[(js + LA) % RING], ring_l[(js + LA) % RING]);
             __builtin_amdgcn_sched_barrier(0);
             const half8_t wh = resident ? res_h[ridx] : ring_h[js % RING];
             const half8_t wl = resident ? res_l[ridx] : ring_l[js % RING];
             // product terms outermost: with two row tiles the dependent MFMAs of one accumulator are a tile apart
 #pragma unroll
-            for (int term = 0; term < 3; ++term)
+            for (int term = 0; term < (light ? 0 : 3); ++term)
 #pragma unroll
                 for (int m = 0; m < MT; ++m) {
                     f32x16& acc = g == 0 ? acc_r[m] : (g == 1 ? acc_u[m] : acc_c[m]);
@@ -426,11 +437,55 @@ __global__ __launch_bounds__(512) void k_augru_x(RecurArgs a) {
 #endif
             __builtin_amdgcn_sched_barrier(0);
         }
+    };
+    auto step_begin = [&](const int t, const bool light) __attribute__((always_inline)) {
+        RL4RS_XT(0);
+#pragma unroll
+        for (int m = 0; m < MT; ++m) oma[m] = 1.0f - att_cur[m];
+        if (!light) hfrag(0, 0);
+    };
+    auto step_end = [&](const int t) __attribute__((always_inline)) {
 #pragma unroll
         for (int m = 0; m < MT; ++m) att_cur[m] = att_next[m];
         RL4RS_XT(6);
         if (!(RL4RS_X_AB & 16)) __syncthreads();                   // late half of the new state complete
         RL4RS_XT(7);
+    };
+    if constexpr (PEEL) {
+        // ---- BOUNDARY STEPS.  The recurrence starts from h = 0, so in step 0 the B operand of items 0-39 (h planes, r*h planes) is
+        // all zeros: each of their MFMAs would add w * 0 to an accumulator element that already holds x_u(0) / x_c(0) / x_r(0).
+        // Weights are finite (non-finite checkpoints never reach this mode), so every such sum of products is a zero and x + 0 = x
+        // bit for bit for x != 0; where x is itself a zero only its sign can differ, and exp2(k * x) in both gate functions
+        // (gate_sigmoid_k / gate_tanh_k) maps +0, -0 - and a subnormal x, should the matrix pipe flush one on its way through an
+        // accumulator - to exactly 1.  Items 40-47 of the LAST step are the reset-gate product of a step that does not exist: they
+        // only write acc_r, which nothing reads after the loop.  So the loop is rotated - its body is items 40-47 of step t followed
+        // by items 0-39 of step t + 1, the same code in the same order as the plain loop - and the two boundary stretches run
+        // `light`: 48 of the 64 x 48 items' MFMAs, weight fragments and state-fragment reads are not issued.  Step 0 enters the
+        // streamed weight sequence at item 40 (position 0): the LA requests in front of it are the ones the slots below 40 issue
+        // in every step, so the ring reaches the loop in its steady state and no slot index depends on the step.  One step
+        // (maxlen 1, RecurArgs::steps = 1) is both stretches back to back.
+        int t = 0;
+        step_begin(0, true);
+        items(0, 0, 40, true);
+#pragma unroll 1
+        while (t + 1 < TL) {
+            asm volatile("" : "+s"(sb_r), "+s"(sb_u), "+s"(sb_c));     // keep the per-item scalar offsets out of SGPR-hoisting
+            items(t, 40, NI, false);
+            step_end(t);
+            ++t;
+            step_begin(t, false);
+            items(t, 0, 40, false);
+        }
+        items(t, 40, NI, true);
+        step_end(t);
+    } else {
+#pragma unroll 1
+        for (int t = 0; t < TL; ++t) {
+            asm volatile("" : "+s"(sb_r), "+s"(sb_u), "+s"(sb_c));     // keep the per-item scalar offsets out of SGPR-hoisting
+            step_begin(t, false);
+            items(t, 0, NI, false);
+            step_end(t);
+        }
     }
     // ---- poison rows that left the fp16 range (or went NaN) and write the final state (16-byte stores).  The final state alone
     // decides: a state element beyond the largest finite fp16 number becomes +-inf in the hi plane and -+inf in the lo plane at

@@ -81,6 +81,14 @@ std::vector<float> pack_gemm_weight_h16(const float* w, int64_t ldw, int K, int 
 // two chained layers in one launch (N1 <= 128, N1 % 16 == 0, N2 <= 128): c2 = act2(act1(a W1 + b1) W2 + b2)
 int launch_gemm_h16_chain(const float* a, int64_t lda, const float* wp1, const float* bias1, int N1, int K1, int act1,
                           const float* wp2, const float* bias2, float* c2, int64_t ldc2, int N2, int act2, int M, hipStream_t st);
+// two independent fp16x2 GEMMs in one launch when both take the same tile form of k_gemm_h16 (else two launches); wp2 != null:
+// the problem is a chained pair of layers as in launch_gemm_h16_chain (c / ldc unused, N = N1, output c2 [M, N2])
+struct GemmH16Desc {
+    const float* a; int64_t lda; const float* wp; const float* bias; float* c; int64_t ldc; int M, N, K, act;
+    const float* addend; int64_t ldadd;
+    const float* wp2; const float* bias2; float* c2; int64_t ldc2; int N2, act2;
+};
+int launch_gemm_h16_pair(const GemmH16Desc& x, const GemmH16Desc& y, hipStream_t st);
 
 // device-side pack_gemm_weight_h16 (weights that change between launches): up to 4 matrices per launch, out = NT * KB * 512 + NT * 32 floats
 struct PackH16Desc { const float* w; float* out; int ldw, K, N; };

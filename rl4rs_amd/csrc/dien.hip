@@ -1754,6 +1754,7 @@ struct rl4rs_dien {
     bool din_x;            // fp16x2 DIN scores through k_din_x (RL4RS_DIN=v1 keeps k_din_scores<*, true>)
     bool dense_chain;      // fp16x2 mode: both dense-tower layers in one launch (RL4RS_DENSE_FUSED=0 at create: two GEMMs)
     float* tsum;           // [max_rows, 256]: obs_b + the per-slot head tables' rows, built by k_cat_attn (table form, Cn <= 24)
+    bool gemm_group;       // fp16x2 mode: the chained dense tower and the q-side term of the DIN scores in one launch (RL4RS_DIEN_OPT_NO_GEMM_GROUP: two)
     bool dense_fork;       // RL4RS_DIEN_OPT_DENSE_FORK: the dense tower (depends on nothing before the head) on side_stream, beside the category / DIN / AUGRU launches
     hipStream_t side_stream; hipEvent_t ev_fork, ev_join;
     bool cat_group;        // reward-sized launches (rows in groups of 8 / 9): k_cat_attn2g, one workgroup per group (RL4RS_DIEN_OPT_NO_CAT_GROUP: per row)
@@ -1940,6 +1941,7 @@ int rl4rs_dien_create(const rl4rs_dien_cfg* c, const rl4rs_dien_weights* w, void
     n->dense_fork = (opts & RL4RS_DIEN_OPT_DENSE_FORK) != 0;
     n->side_stream = nullptr; n->ev_fork = nullptr; n->ev_join = nullptr;
     n->dense_chain = !(opts & RL4RS_DIEN_OPT_NO_DENSE_CHAIN);
+    n->gemm_group = !(opts & RL4RS_DIEN_OPT_NO_GEMM_GROUP);
     n->gru16 = false;
     n->gru16_attr = false;
     if (want_fp16x2) {      // the DIN layer-1 split needs |q * h1| <= max |seq_emb| and the q*k rows of att_w1 inside fp16 range
@@ -2271,6 +2273,11 @@ int rl4rs_dien_encode(rl4rs_dien* n, int32_t s, const int32_t* ids, int32_t cnt,
     return RL4RS_OK;
 }
 
+// fp16x2 GEMMs, the dense tower chained, no second stream: the forward issues the dense tower and the q-side term as one launch
+static bool dien_gemm_grouped(const rl4rs_dien* n) {
+    return n->fp16x2 && n->gemm16 && n->gemm_group && n->dense_chain && n->U <= 128 && n->U % 16 == 0 && !n->dense_fork;
+}
+
 int rl4rs_dien_forward(rl4rs_dien* n, int32_t R, int32_t group, const float* dense, const int32_t* cat,
                        const int32_t* slots, float* obs, float* prob, void* stream) {
     RL4RS_REQUIRE(n && dense && cat && slots, "dien_forward: null argument");
@@ -2338,7 +2345,19 @@ int rl4rs_dien_forward(rl4rs_dien* n, int32_t R, int32_t group, const float* den
         }
         RL4RS_LAUNCH_CHECK();
     }
-    if (!forked) {
+    // The dense tower and the q-side term of the DIN scores (qa = q W1ac_all, q written by the category kernel above) are
+    // independent and, at observation size, half-chip grids of the same kernel: one launch for both (launch_gemm_h16_pair)
+    const bool grouped = dien_gemm_grouped(n) && !forked;
+    if (grouped) {
+        Prof p(n, KID_DENSE, st);
+        GemmH16Desc dt, qs;
+        memset(&dt, 0, sizeof(dt));
+        memset(&qs, 0, sizeof(qs));
+        dt.a = dense; dt.lda = n->Dn; dt.wp = n->dense_w1; dt.bias = n->dense_b1; dt.M = R; dt.N = U; dt.K = n->Dn; dt.act = 1;
+        dt.wp2 = n->dense_w2; dt.bias2 = n->dense_b2; dt.c2 = n->allf + off_d; dt.ldc2 = F; dt.N2 = U; dt.act2 = 1;
+        qs.a = n->q; qs.lda = E; qs.wp = n->w1ac_all; qs.c = n->qa; qs.ldc = S * ATT_H1; qs.M = R; qs.N = S * ATT_H1; qs.K = E; qs.act = 0;
+        if ((rc = launch_gemm_h16_pair(dt, qs, st))) return rc;
+    } else if (!forked) {
         Prof p(n, KID_DENSE, st);
         if ((rc = dense_tower(st))) return rc;
     }
@@ -2350,7 +2369,7 @@ int rl4rs_dien_forward(rl4rs_dien* n, int32_t R, int32_t group, const float* den
         a.slots = slots; a.slots_stride = ngroups; a.pld = n->PLD; a.q = n->q;
         a.qa = n->qa; a.qa_stride = ATT_H1; a.qa_ld = S * ATT_H1;       // one GEMM for the q-side term of every input: [R, S*64]
         const bool h16 = n->fp16x2 && n->din16;
-        if ((rc = scorer_gemm(n, n->q, E, n->w1ac_all, nullptr, n->qa, S * ATT_H1, R, S * ATT_H1, E, 0, st))) return rc;
+        if (!grouped && (rc = scorer_gemm(n, n->q, E, n->w1ac_all, nullptr, n->qa, S * ATT_H1, R, S * ATT_H1, E, 0, st))) return rc;
         for (int s = 0; s < S; ++s) {
             a.h1[s] = n->h1[s]; a.h1f[s] = n->h1f[s]; a.proj[s] = n->proj[s]; a.w1ac[s] = n->w1ac[s]; a.w1d[s] = n->w1d[s]; a.w1d16[s] = n->w1d16[s];
             a.w2[s] = n->att_w2[s]; a.b2[s] = n->att_b2[s]; a.w3[s] = n->att_w3[s]; a.b3[s] = n->att_b3[s];
@@ -2574,11 +2593,13 @@ int rl4rs_dien_kernel_label(rl4rs_dien* n, int which, char* buf, int32_t cap) {
     switch (which) {
         case KID_CAT: s = (n->cat_v2 && n->E == 128 && n->Cn <= 24) ? (n->cat_group ? "k_cat_attn2 / k_cat_attn2g (grouped rows)" : "k_cat_attn2") : "k_cat_attn"; break;
         case KID_DENSE:
-            s = (n->gemm16 && n->dense_chain && n->U <= 128 && n->U % 16 == 0) ? "k_gemm_h16<chain>(dense tower, both layers)"
-                                                                                : std::string(gemm) + " x2 (dense tower)";
+            s = dien_gemm_grouped(n) ? "k_gemm_h16_pair(dense tower, both layers + q-side term of the DIN scores)"
+                : (n->gemm16 && n->dense_chain && n->U <= 128 && n->U % 16 == 0) ? "k_gemm_h16<chain>(dense tower, both layers)"
+                                                                                  : std::string(gemm) + " x2 (dense tower)";
             break;
         case KID_DIN:
-            s = std::string(din_x ? "k_din_x" : (n->fp16x2 && n->din16 ? "k_din_scores<h16>" : "k_din_scores")) + " + " + gemm + "(q-side term)";
+            s = std::string(din_x ? "k_din_x" : (n->fp16x2 && n->din16 ? "k_din_scores<h16>" : "k_din_scores"));
+            if (!dien_gemm_grouped(n)) s += std::string(" + ") + gemm + "(q-side term)";
             break;
         case KID_AUGRU:
             s = !n->fp16x2 ? "k_recur<256,augru>" : (n->augru_x ? "k_augru_x" : "k_augru_h16");
