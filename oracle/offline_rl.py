@@ -68,15 +68,20 @@ def imitation_loss(logits, actions, beta):
     return torch.nn.functional.nll_loss(logp, a) + beta * (logits ** 2).mean()
 
 
-def best_action(q, imitator_logits=None, action_flexibility=0.3):
+def action_scores(q, imitator_logits=None, action_flexibility=0.3):
+    """what the greedy rule takes the (first) arg-max of: Q, or the BCQ product when imitator logits are given."""
     q = q.detach()
     if imitator_logits is None:
-        return q.argmax(dim=1)
+        return q
     logp = torch.log_softmax(imitator_logits.detach(), dim=1)
     ratio = logp - logp.max(dim=1, keepdim=True).values
     mask = (ratio > np.log(action_flexibility)).to(q.dtype)
     value = q - q.min(dim=1, keepdim=True).values
-    return (value * mask).argmax(dim=1)
+    return value * mask
+
+
+def best_action(q, imitator_logits=None, action_flexibility=0.3):
+    return action_scores(q, imitator_logits, action_flexibility).argmax(dim=1)
 
 
 def huber(y, target, beta=1.0):
@@ -86,10 +91,14 @@ def huber(y, target, beta=1.0):
 
 
 def dqn_loss(q_t, actions, rewards, terminals, q_next, q_next_target, imitator_next=None, action_flexibility=0.3, gamma=0.99,
-             cql_alpha=0.0):
-    """returns (td, conservative, best next action); total = td + cql_alpha * conservative."""
+             cql_alpha=0.0, best=None):
+    """returns (td, conservative, best next action); total = td + cql_alpha * conservative.  ``best``: next actions to use in
+    place of the greedy rule's (tests: the device's choice on rows where float32 and float64 scores tie)."""
     a = torch.as_tensor(np.asarray(actions), dtype=torch.int64)
-    best = best_action(q_next, imitator_next, action_flexibility)
+    if best is None:
+        best = best_action(q_next, imitator_next, action_flexibility)
+    else:
+        best = torch.as_tensor(np.asarray(best), dtype=torch.int64)
     q_tp1 = q_next_target.detach().gather(1, best[:, None])
     r = torch.as_tensor(np.asarray(rewards), dtype=q_t.dtype)[:, None]
     ter = torch.as_tensor(np.asarray(terminals), dtype=q_t.dtype)[:, None]

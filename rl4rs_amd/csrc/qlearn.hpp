@@ -252,6 +252,7 @@ struct rl4rs_qnet {
     uint32_t *bits, *loc_bits, *special_bits;
     int* err;
     int64_t adam_t;
+    size_t part_floats;         // floats behind cx.part (checked by rl4rs_qnet_backward before the chunked reductions write there)
     std::vector<void*> owned;
 };
 
@@ -334,7 +335,8 @@ int rl4rs_qnet_create(const rl4rs_qnet_cfg* c, const float* params_host, const u
     for (int i = 0; i < QP_COUNT; ++i) if (sizes[i] > wmax) wmax = sizes[i];
     p->cx.chunk = 512;
     QN_FAIL(al(&p->cx.wt, wmax));
-    QN_FAIL(al(&p->cx.part, (size_t)((B + 511) / 512) * (wmax + std::max<int64_t>(std::max<int64_t>(A, H1), n2))));      // + the bias partials (st_tn_cs)
+    p->part_floats = (size_t)((B + 511) / 512) * (wmax + std::max<int64_t>(std::max<int64_t>(A, H1), n2));      // + the bias partials (st_tn_cs)
+    QN_FAIL(al(&p->cx.part, p->part_floats));
     QN_HIP(hipStreamSynchronize(st));
 #undef QN_HIP
 #undef QN_FAIL
@@ -412,6 +414,14 @@ int rl4rs_qnet_backward(rl4rs_qnet* p, int32_t N, const float* obs, const float*
     auto ew = [](int n) { return dim3((n + 255) / 256); };
     const dim3 b256(256);
     int rc;
+    if (N > TN4_MAX_SAMPLES) {
+        // beyond one workgroup's rows st_tn_cs keeps one [M x Nc] weight partial + Nc bias columns per chunk in cx.part (every form
+        // of it: the 128 x 128 one plans its chunk count within the same product): refuse rather than write past the allocation
+        const size_t nz = (size_t)((N + p->cx.chunk - 1) / p->cx.chunk);
+        const size_t widest = std::max(std::max((size_t)FH * A + A, (size_t)F2 * FH + FH), (size_t)D * H1 + H1);
+        RL4RS_REQUIRE(nz * widest <= p->part_floats, "qnet_backward: the gradient scratch holds %zu floats, %d rows need %zu",
+                      p->part_floats, N, nz * widest);
+    }
     st_tn_cs(p->cx, st, p->enc, FH, FH, dout, A, A, N, G + o[QP_HW], G + o[QP_HB]);      // weight + bias gradient: one launch
     if (p->custom) {
         if ((rc = st_back(p->cx, st, dout, A, A, P + o[QP_HW], A, FH, p->d_enc, FH, N))) return rc;

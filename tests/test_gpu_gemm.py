@@ -7,7 +7,10 @@ pytestmark = pytest.mark.gpu
 
 @pytest.mark.parametrize('M,N,K,act', [(1, 2, 3, 0), (33, 65, 17, 1), (128, 64, 32, 0), (300, 284, 64, 3),
                                        (257, 128, 432, 1), (1000, 256, 3456, 1), (4096, 832, 128, 0),
-                                       (77, 2, 256, 2)])
+                                       (77, 2, 256, 2),
+                                       # relu (act 4, the offline-RL Q-net's fc1) through each form: k_gemm_small (N <= 32),
+                                       # k_gemm_f32 (25 x 4 tiles, K not a multiple of 4), k_gemm_f32_t128 (>= 2048 rows, aligned)
+                                       (77, 2, 256, 4), (3100, 256, 266, 4), (4100, 284, 576, 4)])
 def test_gemm_f32(M, N, K, act):
     import torch
     from rl4rs_amd.device import gemm_f32
@@ -23,6 +26,8 @@ def test_gemm_f32(M, N, K, act):
         ref = torch.sigmoid(ref)
     elif act == 3:
         ref = torch.tanh(ref)
+    elif act == 4:
+        ref = torch.relu(ref)
     err = (c.double() - ref).abs().max().item()
     assert err < 2e-5, err
     from rl4rs_amd.device import gemm_f32_packed
