@@ -612,6 +612,79 @@ int rl4rs_policy_set_option(rl4rs_policy* pol, int32_t which, int32_t value);
 int rl4rs_policy_adam_state(rl4rs_policy* pol, float** m_dev, float** v_dev, int64_t* step);
 int rl4rs_policy_set_adam_step(rl4rs_policy* pol, int64_t step);
 
+/* ------------------------------------------------------------------------------------------------
+ * On-device DQN on the action-masked net: script/modelfree_train.py:106-133 (algo "DQN": hiddens [], dueling False,
+ * double_q True, n_step 1, target_network_update_freq 200, buffer_size 100000, custom_model mask_model).  With those settings the
+ * Q values are the masked logits of rl4rs_policy, and RLlib's SoftQ exploration (temperature 1) is rl4rs_policy_act's draw.
+ * RLlib 1.5.1's dqn_tf_policy and PrioritizedReplayBuffer are restated from their published form (ray is absent: parity unpinned).
+ *
+ * Replay memory (replaces ray's PrioritizedReplayBuffer behind modelfree_train.py:121 buffer_size): a ring of WHOLE rollouts in
+ * the trainers' row order (r * T + t) * B + b.  A row holds obs float32 [obs_dim], packed mask words, action int32, reward float32,
+ * done int32 and priority float64; the successor of a non-terminal row is row idx + B of the same rollout, so no next_obs is
+ * stored.  Capacity is max(1, buffer_size / (T * B)) rollouts and the oldest rollout is evicted whole: the one deviation from
+ * RLlib's per-timestep ring.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct rl4rs_replay rl4rs_replay;
+
+/* alpha: the priority exponent (RLlib prioritized_replay_alpha 0.6) */
+int rl4rs_replay_create(int32_t obs_dim, int32_t action_size, int32_t max_steps, int32_t batch_size, int64_t buffer_size,
+                        double alpha, rl4rs_replay** out);
+int rl4rs_replay_destroy(rl4rs_replay* h);
+/* filled rows n (always rows [0, n) of the buffers), capacity in rows, rollouts pushed so far; any may be NULL */
+int rl4rs_replay_rows(rl4rs_replay* h, int32_t* rows, int32_t* capacity_rows, int64_t* pushes);
+/* device address and element count of one column of the ring (tests, checkpoints) */
+enum { RL4RS_REPLAY_BUF_OBS = 0, RL4RS_REPLAY_BUF_MASK = 1, RL4RS_REPLAY_BUF_ACTION = 2, RL4RS_REPLAY_BUF_REWARD = 3,
+       RL4RS_REPLAY_BUF_DONE = 4, RL4RS_REPLAY_BUF_PRIORITY = 5, RL4RS_REPLAY_BUF_MAX_PRIORITY = 6 };
+int rl4rs_replay_buffer(rl4rs_replay* h, int32_t which, void** dev_out, int64_t* count_out);
+/* Append one rollout (T * B rows in row order t * B + b) from device pointers, no host round trip: obs float32, mask words,
+ * actions int32, rewards float64 (what the env returns; stored as float32).  done = (t == T - 1).  New rows get priority
+ * max_priority ^ alpha; max_priority starts at 1.0 and is the largest |td| + 1e-6 ever set. */
+int rl4rs_replay_push(rl4rs_replay* h, const float* obs_dev, const uint32_t* mask_bits_dev, const int32_t* action_dev,
+                      const double* reward_dev, void* stream);
+/* Draw M rows and gather them into contiguous minibatch buffers: obs / next obs float32 [M, obs_dim], next mask words [M, W],
+ * action int32, reward float32, done int32, idx int32 (row in the ring), weight float32 (optional) and u float32 (optional: the
+ * uniform variate of each draw = the policy net's counter RNG keyed (seed, step, draw, 0)).
+ *   prioritized 0: idx = floor(u * n), weight 1.
+ *   prioritized 1: RLlib's proportional buffer, not stratified: idx = the smallest i whose inclusive float64 prefix sum of the
+ *     priorities exceeds u * total; weight = (n p_i / total)^-beta / (n p_min / total)^-beta.  Prefix sums, total and minimum are
+ *     float64 reductions in a fixed order (per 1024-row tile, then over the tiles in order): bit-identical from run to run.
+ * Next obs / next mask of a terminal row are a copy of the row itself (finite, never to be used). */
+int rl4rs_replay_sample(rl4rs_replay* h, int32_t M, int32_t prioritized, double beta, uint32_t seed, uint32_t step,
+                        float* obs_out, float* next_obs_out, uint32_t* next_mask_out, int32_t* action_out, float* reward_out,
+                        int32_t* done_out, int32_t* idx_out, float* weight_out, float* u_out, void* stream);
+/* priority[idx_i] = (|td_i| + 1e-6)^alpha; where idx repeats within the batch the HIGHEST batch position wins (deterministic);
+ * max_priority = max(max_priority, |td_i| + 1e-6) over the whole batch.  A non-finite td leaves its row alone. */
+int rl4rs_replay_update_priorities(rl4rs_replay* h, int32_t M, const int32_t* idx_dev, const float* td_dev, void* stream);
+
+/* DQN loss and gradient on the net of `pol` (replaces ray's dqn_tf_policy build_q_losses behind modelfree_train.py:106-133);
+ * target_params_dev: the target net's parameters, a device buffer in the same flat layout.
+ *   Q(s)[a] from the online net (a was legal: its mask term is 0)
+ *   a* = first maximum of the masked online Q(s') (double_q 1) or of the masked target Q(s') (double_q 0)
+ *   y  = r + gamma * Q_target(s')[a*] for a non-terminal row, r for a terminal one: a select, so nothing of a terminal row's
+ *        successor (which may hold anything, NaN included) reaches the result
+ *   td = Q(s)[a] - y,  loss = mean(w * huber(td, delta 1)),  w = weights_dev or 1
+ * A NON-terminal row whose successor allows no action at all bootstraps nothing either: y = r, like a terminal row (every
+ * Q(s') of it is the mask's -3.4e38, not a value).
+ * Outputs: grad_dev (flat layout; the value-head column and every action nobody took get exactly 0), td_dev [N] for the
+ * priority update, next_action_dev [N] (optional: a*, -1 for terminal rows), stats_dev float[4] (optional) = sums of
+ * {w * huber, Q(s)[a], y, |td|}.  N <= max_rows; the first call allocates the loss's scratch on the handle.
+ * Rank-sparse backward: one non-zero d loss / d Q per row, so dW2e is gathered column by column and the s' forwards are never
+ * differentiated.  Bit-reproducible like rl4rs_policy_loss_grad (fixed sample chunks, fixed summation order).  The forwards
+ * run as MFMA GEMMs for every shape rl4rs_policy_create admits; RL4RS_POLICY_OPT_TILE = 0 selects the one-wave-per-row kernel. */
+int rl4rs_policy_dqn_loss_grad(rl4rs_policy* pol, const float* target_params_dev, int32_t N, const float* obs_dev,
+                               const int32_t* actions_dev, const float* rewards_dev, const int32_t* dones_dev,
+                               const float* next_obs_dev, const uint32_t* next_mask_bits_dev, const float* weights_dev,
+                               float gamma, int32_t double_q, float* grad_dev, float* td_dev, int32_t* next_action_dev,
+                               float* stats_dev, void* stream);
+/* Greedy action (RLlib explore: False): the first maximum of the masked Q row; q_dev (optional) receives the masked row
+ * [N, action_size].  A row that allows nothing returns action 0. */
+int rl4rs_policy_greedy(rl4rs_policy* pol, int32_t N, const float* obs_dev, const uint32_t* mask_bits_dev,
+                        int32_t* actions_dev, float* q_dev, void* stream);
+/* rl4rs_policy_adam_step with tf.clip_by_norm applied to EACH variable (W1, b1, W2e, b2e) by its own norm - RLlib DQN's
+ * minimize_and_clip (grad_clip 40) - instead of the global norm; var_clip <= 0: no clipping. */
+int rl4rs_policy_adam_step_clip_by_var(rl4rs_policy* pol, const float* grad_dev, float lr, float beta1, float beta2,
+                                       float eps, float var_clip, void* stream);
+
 /* Raw-state policy encoder: rl4rs/nets/rllib/rllib_rawstate_model.py:25-86 (and its action-mask wrapper,
  * rllib_mask_model.py:67-115) for envs with config['rawstate_as_obs'] (rl4rs/env/slate.py:250-262):
  *   context = ELU([mean seq emb (per sequence, one shared table) | dense tower | mean category emb] @ ctx_w + ctx_b)  (256)

@@ -297,7 +297,20 @@ SIGNATURES = {
     'rl4rs_ope_estimate': (_I, [_P, C.c_double, C.POINTER(C.c_double), _P]),
     'rl4rs_ope_episode_stats': (_I, [_I32, _P, _P, _P, _P, _P, C.POINTER(C.c_double), _P]),
     'rl4rs_ope_step_stats': (_I, [_I32, _I32, _P, _P, _P, _P, _P, C.c_double, C.POINTER(C.c_double), _P]),
+    'rl4rs_replay_create': (_I, [_I32, _I32, _I32, _I32, _I64, C.c_double, C.POINTER(_P)]),
+    'rl4rs_replay_destroy': (_I, [_P]),
+    'rl4rs_replay_rows': (_I, [_P, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I64)]),
+    'rl4rs_replay_buffer': (_I, [_P, _I32, C.POINTER(_P), C.POINTER(_I64)]),
+    'rl4rs_replay_push': (_I, [_P, _P, _P, _P, _P, _P]),
+    'rl4rs_replay_sample': (_I, [_P, _I32, _I32, C.c_double, C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    'rl4rs_replay_update_priorities': (_I, [_P, _I32, _P, _P, _P]),
+    'rl4rs_policy_dqn_loss_grad': (_I, [_P, _P, _I32, _P, _P, _P, _P, _P, _P, _P, C.c_float, _I32, _P, _P, _P, _P, _P]),
+    'rl4rs_policy_greedy': (_I, [_P, _I32, _P, _P, _P, _P, _P]),
+    'rl4rs_policy_adam_step_clip_by_var': (_I, [_P, _P, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _P]),
 }
+
+# include/rl4rs_hip.h RL4RS_REPLAY_BUF_*
+REPLAY_BUFS = {'obs': 0, 'mask': 1, 'action': 2, 'reward': 3, 'done': 4, 'priority': 5, 'max_priority': 6}
 
 # include/rl4rs_hip.h RL4RS_OPE_COL_* / RL4RS_OPE_* (statistics slots)
 OPE_COLS = {'pi': 0, 'mu': 1, 'q': 2, 'reward': 3, 'logged_reward': 4}

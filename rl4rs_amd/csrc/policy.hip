@@ -934,6 +934,7 @@ struct rl4rs_policy {
     // rl4rs_policy_set_option (include/rl4rs_hip.h RL4RS_POLICY_OPT_*): kernel-path selection for A/B runs and tests
     bool opt_tile, opt_ppo_fused, opt_ppo_std;
     int opt_ppo_rows, opt_resident_cap;
+    float *dqn_Hn, *dqn_Hnt, *dqn_g;      // scratch of rl4rs_policy_dqn_loss_grad (dqn.hpp), allocated by its first call
     std::vector<void*> owned;
 };
 
@@ -970,6 +971,7 @@ int rl4rs_policy_create(int32_t obs_dim, int32_t hidden, int32_t action_size, in
     p->pass_resident_wgs = -1;
     p->opt_tile = true; p->opt_ppo_fused = true; p->opt_ppo_std = true; p->opt_ppo_rows = 0; p->opt_resident_cap = -1;
     p->dead_host = nullptr;
+    p->dqn_Hn = p->dqn_Hnt = p->dqn_g = nullptr;
     p->tile_attr[0] = p->tile_attr[1] = p->tile_attr[2] = false;
     int rc;
     auto alloc = [&](float** dst, size_t n) {
@@ -1631,3 +1633,4 @@ int rl4rs_policy_set_option(rl4rs_policy* p, int32_t which, int32_t value) {
 #include "rawtrain.hpp"
 #include "qlearn.hpp"
 #include "contirl.hpp"
+#include "dqn.hpp"

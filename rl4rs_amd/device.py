@@ -1202,12 +1202,14 @@ class DevicePolicy(object):
         except Exception:
             pass
 
-    def params(self):
-        """Copy of the flat parameter buffer (device tensor)."""
+    def params(self, out=None):
+        """Copy of the flat parameter buffer (device tensor); ``out``: a contiguous float32 device tensor to copy into."""
         p = C.c_void_p()
         n = C.c_int32()
         check(self.lib.rl4rs_policy_params(self.h, C.byref(p), C.byref(n)))
-        out = torch.empty(n.value, dtype=torch.float32, device=self.device)
+        if out is None:
+            out = torch.empty(n.value, dtype=torch.float32, device=self.device)
+        assert out.dtype == torch.float32 and out.numel() == n.value and out.is_contiguous() and out.is_cuda
         check(self.lib.rl4rs_copy_d2d(_ptr(out), p, n.value * 4, _stream()))
         return out
 
@@ -1311,6 +1313,43 @@ class DevicePolicy(object):
     def adam_step(self, grad, lr=1e-4, beta1=0.9, beta2=0.999, eps=1e-8, grad_clip=0.0):
         check(self.lib.rl4rs_policy_adam_step(self.h, _ptr(grad), lr, beta1, beta2, eps, grad_clip, _stream()))
 
+    def dqn_loss_grad(self, target_params, obs, actions, rewards, dones, next_obs, next_mask_bits=None, weights=None, gamma=1.0,
+                      double_q=True, grad_out=None, td_out=None, want_next_action=False):
+        """(Double-)DQN Huber loss and gradient (rl4rs_policy_dqn_loss_grad).  All inputs are contiguous device tensors: obs /
+        next_obs / rewards / weights float32, actions / dones int32, target_params float32 [n_params].
+        -> (grad, td [N], stats[4] sums of {w * huber, Q(s)[a], y, |td|}, a* [N] or None)."""
+        N = obs.shape[0]
+        for t in (target_params, obs, rewards, next_obs) + ((weights,) if weights is not None else ()):
+            assert t.dtype == torch.float32 and t.is_contiguous()
+        assert actions.dtype == torch.int32 and dones.dtype == torch.int32 and actions.is_contiguous() and dones.is_contiguous()
+        assert target_params.numel() == self.n_params and obs.shape == (N, self.obs_dim) and next_obs.shape == (N, self.obs_dim)
+        assert actions.shape == (N,) and rewards.shape == (N,) and dones.shape == (N,) and (weights is None or weights.shape == (N,))
+        m = self._mask(next_mask_bits, N)
+        g = grad_out if grad_out is not None else torch.empty(self.n_params, dtype=torch.float32, device=self.device)
+        td = td_out if td_out is not None else torch.empty(N, dtype=torch.float32, device=self.device)
+        assert td.dtype == torch.float32 and td.shape == (N,) and td.is_contiguous()
+        stats = torch.empty(4, dtype=torch.float32, device=self.device)
+        astar = torch.empty(N, dtype=torch.int32, device=self.device) if want_next_action else None
+        check(self.lib.rl4rs_policy_dqn_loss_grad(self.h, _ptr(target_params), N, _ptr(obs), _ptr(actions), _ptr(rewards), _ptr(dones),
+                                                  _ptr(next_obs), _ptr(m), _ptr(weights), gamma, 1 if double_q else 0, _ptr(g), _ptr(td),
+                                                  _ptr(astar), _ptr(stats), _stream()))
+        return g, td, stats, astar
+
+    def greedy(self, obs, mask_bits=None, want_q=False, out=None):
+        """First maximum of the masked Q row (rl4rs_policy_greedy) -> (actions int32 [N], masked Q [N, A] or None)."""
+        N = obs.shape[0]
+        assert obs.dtype == torch.float32 and obs.shape == (N, self.obs_dim) and obs.is_contiguous()
+        m = self._mask(mask_bits, N)
+        a = out if out is not None else torch.empty(N, dtype=torch.int32, device=self.device)
+        assert a.dtype == torch.int32 and a.shape == (N,) and a.is_contiguous()
+        q = torch.empty((N, self.action_size), dtype=torch.float32, device=self.device) if want_q else None
+        check(self.lib.rl4rs_policy_greedy(self.h, N, _ptr(obs), _ptr(m), _ptr(a), _ptr(q), _stream()))
+        return a, q
+
+    def adam_step_clip_by_var(self, grad, lr=5e-4, beta1=0.9, beta2=0.999, eps=1e-8, var_clip=40.0):
+        """Adam with every variable (W1, b1, W2e, b2e) clipped by its own norm (rl4rs_policy_adam_step_clip_by_var)."""
+        check(self.lib.rl4rs_policy_adam_step_clip_by_var(self.h, _ptr(grad), lr, beta1, beta2, eps, var_clip, _stream()))
+
     def check_status(self):
         """Synchronises; raises if a persistent PPO pass gave up at a grid barrier (its workgroups were not co-resident)."""
         f = C.c_int32()
@@ -1350,6 +1389,105 @@ class DevicePolicy(object):
         check(self.lib.rl4rs_copy_d2d(pv, _ptr(v), self.n_params * 4, _stream()))
         check(self.lib.rl4rs_policy_set_adam_step(self.h, int(step)))
         self._keep_adam = (m, v)
+
+
+class DeviceReplay(object):
+    """rl4rs_replay handle: a ring of whole rollouts on the device with uniform / proportional-prioritized sampling."""
+    _DTYPES = {'obs': torch.float32, 'mask': torch.int32, 'action': torch.int32, 'reward': torch.float32, 'done': torch.int32,
+               'priority': torch.float64, 'max_priority': torch.float64}
+
+    def __init__(self, obs_dim, action_size, max_steps, batch_size, buffer_size=100000, alpha=0.6, device=None):
+        _lib.require_device()
+        self.lib = _lib.load()
+        self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        self.obs_dim, self.action_size, self.T, self.B = int(obs_dim), int(action_size), int(max_steps), int(batch_size)
+        self.W = (self.action_size + 31) // 32
+        self.alpha = float(alpha)
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            check(self.lib.rl4rs_replay_create(self.obs_dim, self.action_size, self.T, self.B, int(buffer_size), self.alpha, C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, 'h', None) is not None and self.h:
+            self.lib.rl4rs_replay_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def counts(self):
+        """(filled rows, capacity in rows, rollouts pushed so far): host bookkeeping, no synchronisation."""
+        n, cap, pushes = C.c_int32(), C.c_int32(), C.c_int64()
+        check(self.lib.rl4rs_replay_rows(self.h, C.byref(n), C.byref(cap), C.byref(pushes)))
+        return n.value, cap.value, pushes.value
+
+    @property
+    def rows(self):
+        return self.counts()[0]
+
+    def _buffer(self, name):
+        p, n = C.c_void_p(), C.c_int64()
+        check(self.lib.rl4rs_replay_buffer(self.h, _lib.REPLAY_BUFS[name], C.byref(p), C.byref(n)))
+        return p, n.value
+
+    def column(self, name):
+        """Copy of one column of the whole ring (capacity rows; ``max_priority``: one float64)."""
+        p, n = self._buffer(name)
+        out = torch.empty(n, dtype=self._DTYPES[name], device=self.device)
+        check(self.lib.rl4rs_copy_d2d(_ptr(out), p, n * out.element_size(), _stream()))
+        cap = self.counts()[1]
+        return out.view(cap, -1) if name in ('obs', 'mask') else out
+
+    def set_priorities(self, values):
+        """Overwrite the first len(values) priorities (tests: a buffer with known priorities)."""
+        v = values.to(device=self.device, dtype=torch.float64).contiguous()
+        p, n = self._buffer('priority')
+        assert v.numel() <= n
+        check(self.lib.rl4rs_copy_d2d(p, _ptr(v), v.numel() * 8, _stream()))
+        self._keep = v
+
+    def push(self, obs, mask_bits, actions, rewards):
+        """One rollout: obs f32 [T * B, obs_dim], mask words i32 [T * B, W], actions i32, rewards f64, all in row order t * B + b."""
+        R = self.T * self.B
+        assert obs.dtype == torch.float32 and obs.shape == (R, self.obs_dim) and obs.is_contiguous()
+        assert mask_bits.dtype == torch.int32 and mask_bits.shape == (R, self.W) and mask_bits.is_contiguous()
+        assert actions.dtype == torch.int32 and actions.shape == (R,) and actions.is_contiguous()
+        assert rewards.dtype == torch.float64 and rewards.shape == (R,) and rewards.is_contiguous()
+        check(self.lib.rl4rs_replay_push(self.h, _ptr(obs), _ptr(mask_bits), _ptr(actions), _ptr(rewards), _stream()))
+
+    def new_batch(self, M, want_u=False):
+        """Minibatch buffers for ``sample(out=...)``."""
+        dev = self.device
+        b = dict(obs=torch.empty((M, self.obs_dim), dtype=torch.float32, device=dev),
+                 next_obs=torch.empty((M, self.obs_dim), dtype=torch.float32, device=dev),
+                 next_mask=torch.empty((M, self.W), dtype=torch.int32, device=dev),
+                 action=torch.empty(M, dtype=torch.int32, device=dev), reward=torch.empty(M, dtype=torch.float32, device=dev),
+                 done=torch.empty(M, dtype=torch.int32, device=dev), idx=torch.empty(M, dtype=torch.int32, device=dev),
+                 weight=torch.empty(M, dtype=torch.float32, device=dev))
+        b['u'] = torch.empty(M, dtype=torch.float32, device=dev) if want_u else None
+        return b
+
+    def sample(self, M, prioritized=True, beta=0.4, seed=0, step=0, out=None, want_u=False):
+        """Draw and gather M rows (rl4rs_replay_sample) -> dict obs, next_obs, next_mask, action, reward, done, idx, weight, u."""
+        b = out if out is not None else self.new_batch(M, want_u)
+        assert b['obs'].shape[0] == M
+        check(self.lib.rl4rs_replay_sample(self.h, M, 1 if prioritized else 0, float(beta), seed & 0xffffffff, step & 0xffffffff,
+                                           _ptr(b['obs']), _ptr(b['next_obs']), _ptr(b['next_mask']), _ptr(b['action']), _ptr(b['reward']),
+                                           _ptr(b['done']), _ptr(b['idx']), _ptr(b['weight']), _ptr(b.get('u')), _stream()))
+        return b
+
+    def update_priorities(self, idx, td):
+        M = idx.shape[0]
+        assert idx.dtype == torch.int32 and td.dtype == torch.float32 and td.shape == (M,) and idx.is_contiguous() and td.is_contiguous()
+        check(self.lib.rl4rs_replay_update_priorities(self.h, M, _ptr(idx), _ptr(td), _stream()))
+
+    def max_priority(self):
+        """The largest |td| + 1e-6 ever set (1.0 at start); waits for the stream."""
+        return float(self.column('max_priority').cpu()[0])
 
 
 class DeviceQNet(object):

@@ -1,10 +1,14 @@
-"""On-device policy training loop over the GPU env (A2C / PPO with the reference's RLlib hyper-parameters,
+"""On-device policy training loops over the GPU env (A2C / PPO with the reference's RLlib hyper-parameters,
 script/modelfree_train.py:179-304: gamma = 1, GAE lambda = 1, lr 1e-4, vf_loss_coeff 0.5; A2C entropy 0.01 and
 grad_clip 10; PPO clip 0.3, kl_coeff 0.2 adapted towards kl_target 0.01, vf_clip 500, one SGD pass over minibatches of 256;
 train_batch_size = min(B * T, 1024) timesteps per train call, :409).
 
 Rollout, policy forward/backward and Adam run through librl4rs_hip.so; torch is used for buffers, the reversed
 cumulative sum of rewards and (data-parallel) the RCCL all-reduce of the flat gradient buffer.
+
+``DQNTrainer`` is the value-based learner of the same driver (script/modelfree_train.py:106-133: RLlib DQN with double_q, n_step 1,
+target_network_update_freq 200, buffer_size 100000 on the mask model): replay memory, TD loss, per-variable-clipped Adam and
+the target copy all stay on the device (rl4rs_replay_*, rl4rs_policy_dqn_loss_grad).
 
 Data parallelism: every rank owns its own env batch and sampling stream (``seed`` differs per rank) and a replica
 of the policy that is IDENTICAL on all ranks: initialised from the shared ``init_seed``, rank 0's parameters / Adam state are
@@ -449,3 +453,172 @@ class Trainer(_DeferredStats):
         stats8 = torch.cat([stats.reshape(-1)[:4], torch.zeros(3, dtype=stats.dtype, device=stats.device), kl_sum.reshape(1).to(stats.dtype)])
         rdist.allreduce_sum_(stats8[7:8])
         return LazyStats(self, self._submit(mean_reward, stats8, nmb * MB * world, dict(ppo=True, kl_mean=None)))
+
+
+class DQNTrainer(_DeferredStats):
+    """Online DQN on the action-masked FC net (rllib_mask_model.py:7-64) over the zero-copy discrete-action env, with the
+    reference's merged RLlib 1.5.1 configuration (script/modelfree_train.py:106-133 over the DQN defaults) as defaults: gamma 1,
+    lr 5e-4, Adam eps 1e-8, grad_clip 40 per variable, double_q, n_step 1, buffer_size 100000, target_network_update_freq 200
+    sampled timesteps, learning_starts 1000, train_batch_size min(B * T, 1024), prioritized replay alpha 0.6 / beta 0.4 (constant),
+    SoftQ exploration at temperature 1 (= the net's own categorical draw, ``DevicePolicy.act``).  RLlib parity is unpinned (ray is
+    absent), as for A2C and PPO.
+
+    seed / init_seed        as in ``Trainer`` (this rank's sampling streams / the shared parameter initialisation)
+    updates_per_rollout     updates after every rollout once learning_starts is reached.  1 is RLlib's round-robin (one train op per
+                            sample op); at B = 4096, T = 9 that is one update per 36 864 env steps, which starves the learner, so this
+                            is a knob
+    The replay ring holds whole rollouts: max(1, buffer_size // (B * T)) of them (the one deviation from RLlib's per-timestep
+    ring)."""
+
+    def __init__(self, env, hidden=64, seed=0, init_seed=0, lr=5e-4, gamma=1.0, adam_eps=1e-8, grad_clip=40.0, double_q=True, n_step=1,
+                 buffer_size=100000, target_network_update_freq=200, learning_starts=1000, train_batch_size=None,
+                 prioritized_replay=True, prioritized_replay_alpha=0.6, prioritized_replay_beta=0.4, softq_temperature=1.0,
+                 updates_per_rollout=1, keep_last_batch=False):
+        cfg = env.config
+        assert cfg.get('return_tensors', False) and not cfg.get('support_conti_env', False), \
+            "DQNTrainer needs the zero-copy discrete-action env (config['return_tensors'] = True)"
+        if n_step != 1:
+            raise ValueError("DQNTrainer implements n_step = 1 (the reference's setting, modelfree_train.py:117); got %r" % (n_step,))
+        if softq_temperature != 1.0:
+            raise ValueError("DQNTrainer explores with SoftQ at temperature 1.0 (RLlib's default); got %r" % (softq_temperature,))
+        self.env = env
+        self.B, self.T, self.A = cfg['batch_size'], cfg['max_steps'], cfg['action_size']
+        self.seed, self.lr, self.gamma, self.adam_eps, self.grad_clip = seed, float(lr), float(gamma), float(adam_eps), float(grad_clip)
+        self.double_q, self.prioritized, self.beta = bool(double_q), bool(prioritized_replay), float(prioritized_replay_beta)
+        self.target_network_update_freq, self.learning_starts = int(target_network_update_freq), int(learning_starts)
+        self.updates_per_rollout = int(updates_per_rollout)
+        self.M = int(train_batch_size) if train_batch_size is not None else min(self.B * self.T, 1024)
+        self.keep_last_batch, self.last_batch = keep_last_batch, None
+        self._pending = []
+        self._kl_coeff, self.kl_target = 0.0, 0.0            # (unused: the deferred-statistics base carries PPO's)
+        space = env.observation_space
+        space = space.spaces['obs'] if hasattr(space, 'spaces') else space
+        self.OD = int(space.shape[0])
+        self.policy = D.DevicePolicy(self.OD, hidden, self.A, max_rows=max(self.M, self.B), seed=init_seed)
+        dev = self.policy.device
+        self.replay = D.DeviceReplay(self.OD, self.A, self.T, self.B, buffer_size=buffer_size, alpha=prioritized_replay_alpha, device=dev)
+        N = self.B * self.T
+        self.buf = dict(obs=torch.empty((N, self.OD), dtype=torch.float32, device=dev),
+                        mask=torch.empty((N, self.policy.W), dtype=torch.int32, device=dev),
+                        act=torch.empty(N, dtype=torch.int32, device=dev),
+                        rew=torch.empty(N, dtype=torch.float64, device=dev))
+        self._logp = torch.empty(self.B, dtype=torch.float32, device=dev)
+        self._val = torch.empty(self.B, dtype=torch.float32, device=dev)
+        self._batch = self.replay.new_batch(self.M)
+        self._td = torch.empty(self.M, dtype=torch.float32, device=dev)
+        self.grad = torch.empty(self.policy.n_params, dtype=torch.float32, device=dev)
+        self.iteration = 0
+        self._rollouts = 0
+        self.timesteps = 0                  # sampled env steps (RLlib's num_steps_sampled)
+        self.num_updates = 0
+        self.num_target_updates = 0
+        self._last_target_sync = 0
+        if rdist.collectives_active():
+            Trainer.sync_replicas(self)
+        self.target = self.policy.params()                  # the target net starts as a copy of the online one
+
+    def params(self):
+        self._settle()
+        return self.policy.params()
+
+    def close(self):
+        try:
+            self._settle()
+        finally:
+            self.policy.close()
+            self.replay.close()
+
+    def _episode(self, greedy, step0, reset_file=False):
+        """One complete-episode rollout into the rollout buffers -> mean episode reward (device scalar)."""
+        B, T = self.B, self.T
+        b = self.buf
+        obs = self.env.reset(reset_file=True) if reset_file else self.env.reset()
+        for t in range(T):
+            obs_t = obs['obs'] if isinstance(obs, dict) else obs
+            sl = slice(t * B, (t + 1) * B)
+            mask = self.env.samples._live().obs_mask_bits(out=b['mask'][sl])
+            b['obs'][sl] = obs_t
+            if greedy:
+                a = self.policy.greedy(b['obs'][sl], mask, out=b['act'][sl])[0]
+            else:
+                a = self.policy.act(b['obs'][sl], mask, seed=self.seed, step=step0 + t, out=(b['act'][sl], self._logp, self._val, None))[0]
+            obs, reward, done, info = self.env.step(a)
+            b['rew'][sl] = reward
+        return b['rew'].view(T, B).sum(dim=0).mean()
+
+    def sync_target(self):
+        """target <- online, a device-to-device copy."""
+        self.policy.params(out=self.target)
+        self._last_target_sync = self.timesteps
+        self.num_target_updates += 1
+
+    def update(self):
+        """One learner step: sample -> loss / gradient -> all-reduce (data parallel) -> per-variable-clipped Adam -> priorities.
+        -> stats[4] device sums of {w * huber, Q(s)[a], y, |td|} over the minibatch."""
+        # (the replay draws share the policy's counter RNG: a seed of their own keeps them apart from the action noise of row = draw)
+        b = self.replay.sample(self.M, prioritized=self.prioritized, beta=self.beta, seed=self.seed + 0x5bd1e995, step=self.num_updates,
+                               out=self._batch)
+        w = b['weight'] if self.prioritized else None
+        g, td, stats, astar = self.policy.dqn_loss_grad(self.target, b['obs'], b['action'], b['reward'], b['done'], b['next_obs'],
+                                                        b['next_mask'], weights=w, gamma=self.gamma, double_q=self.double_q,
+                                                        grad_out=self.grad, td_out=self._td, want_next_action=self.keep_last_batch)
+        if self.keep_last_batch:
+            self.last_batch = dict((k, v.clone()) for k, v in b.items() if v is not None)
+            self.last_batch.update(td=td.clone(), next_action=astar)
+        if rdist.collectives_active():
+            rdist.allreduce_mean_(g)
+        self.policy.adam_step_clip_by_var(g, lr=self.lr, eps=self.adam_eps, var_clip=self.grad_clip)
+        if self.prioritized:
+            self.replay.update_priorities(b['idx'], td)
+        self.num_updates += 1
+        return stats
+
+    def train_iteration(self):
+        """One rollout, one push, ``updates_per_rollout`` updates once ``learning_starts`` sampled steps are reached, the target copy
+        when due.  Returns a ``LazyStats`` mapping (episode_reward_mean, td_loss, mean_q, mean_td_abs of the last update - 0 before the
+        first -, buffer_rows, num_updates, num_target_updates, iteration); nothing here waits for the GPU."""
+        mean_reward = self._episode(False, self._rollouts * self.T)
+        self._rollouts += 1
+        self._settle()
+        b = self.buf
+        self.replay.push(b['obs'], b['mask'], b['act'], b['rew'])
+        self.timesteps += self.B * self.T
+        self.iteration += 1
+        stats = torch.zeros(4, dtype=torch.float32, device=b['obs'].device)
+        trained = self.timesteps >= self.learning_starts
+        if trained:
+            for _ in range(self.updates_per_rollout):
+                stats = self.update()
+        if self.timesteps - self._last_target_sync >= self.target_network_update_freq:
+            self.sync_target()
+        extra = dict(ppo=False, kl_mean=None, rows=self.M if trained and self.updates_per_rollout > 0 else 0,
+                     buffer_rows=self.replay.rows, num_updates=self.num_updates, num_target_updates=self.num_target_updates)
+        return LazyStats(self, self._submit(mean_reward, stats, 1, extra))
+
+    def _settle(self):
+        while self._pending:
+            tok = self._pending.pop(0)
+            tok['ev'].synchronize()
+            v = tok['pin'].numpy().copy()
+            if v[-1] >= 1000.0:
+                raise RuntimeError(rdist.ROW_OVERFLOW_MESSAGE)
+            s, n = v[1:-1], max(tok['rows'], 1)
+            tok['values'] = {'episode_reward_mean': float(v[0]), 'td_loss': float(s[0]) / n, 'mean_q': float(s[1]) / n,
+                             'mean_td_abs': float(s[3]) / n, 'buffer_rows': tok['buffer_rows'], 'num_updates': tok['num_updates'],
+                             'num_target_updates': tok['num_target_updates'], 'iteration': tok['iteration']}
+
+    def evaluate(self, episodes=None, seed=0):
+        """Mean episode reward of greedy (explore: False) episodes: ceil(episodes / B) batches from the start of the record file
+        with the env's record sampling seeded by ``seed``, so two calls on the same parameters give the same number.  Leaves the
+        global numpy RNG as it found it; the env's record cursor restarts."""
+        self._settle()
+        n = 1 if episodes is None else max(1, int(math.ceil(float(episodes) / self.B)))
+        state = np.random.get_state()
+        try:
+            np.random.seed(seed)
+            total = torch.zeros((), dtype=torch.float64, device=self.buf['obs'].device)
+            for k in range(n):
+                total += self._episode(True, 0, reset_file=k == 0)
+        finally:
+            np.random.set_state(state)
+        return float(total.item()) / n
