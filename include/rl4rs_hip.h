@@ -634,7 +634,8 @@ int rl4rs_replay_destroy(rl4rs_replay* h);
 int rl4rs_replay_rows(rl4rs_replay* h, int32_t* rows, int32_t* capacity_rows, int64_t* pushes);
 /* device address and element count of one column of the ring (tests, checkpoints) */
 enum { RL4RS_REPLAY_BUF_OBS = 0, RL4RS_REPLAY_BUF_MASK = 1, RL4RS_REPLAY_BUF_ACTION = 2, RL4RS_REPLAY_BUF_REWARD = 3,
-       RL4RS_REPLAY_BUF_DONE = 4, RL4RS_REPLAY_BUF_PRIORITY = 5, RL4RS_REPLAY_BUF_MAX_PRIORITY = 6 };
+       RL4RS_REPLAY_BUF_DONE = 4, RL4RS_REPLAY_BUF_PRIORITY = 5, RL4RS_REPLAY_BUF_MAX_PRIORITY = 6,
+       RL4RS_REPLAY_BUF_ACTION_F32 = 7 /* continuous ring only; MASK and ACTION are the discrete ring's */ };
 int rl4rs_replay_buffer(rl4rs_replay* h, int32_t which, void** dev_out, int64_t* count_out);
 /* Append one rollout (T * B rows in row order t * B + b) from device pointers, no host round trip: obs float32, mask words,
  * actions int32, rewards float64 (what the env returns; stored as float32).  done = (t == T - 1).  New rows get priority
@@ -655,6 +656,18 @@ int rl4rs_replay_sample(rl4rs_replay* h, int32_t M, int32_t prioritized, double 
 /* priority[idx_i] = (|td_i| + 1e-6)^alpha; where idx repeats within the batch the HIGHEST batch position wins (deterministic);
  * max_priority = max(max_priority, |td_i| + 1e-6) over the whole batch.  A non-finite td leaves its row alone. */
 int rl4rs_replay_update_priorities(rl4rs_replay* h, int32_t M, const int32_t* idx_dev, const float* td_dev, void* stream);
+/* The same ring for the continuous-action env (support_conti_env: the action is a float32 vector of act_dim values in Box(-1, 1),
+ * rl4rs/env/base.py:214-215): the same handle type, row order, successor rule, whole-rollout eviction, scans, draw rule and
+ * rl4rs_replay_rows / _buffer / _update_priorities / _destroy; a row holds obs, action float32 [act_dim]
+ * (RL4RS_REPLAY_BUF_ACTION_F32), reward, done and priority, and no mask words.  push_conti: obs float32, action float32
+ * [T * B, act_dim], reward float64.  sample_conti: obs / next obs float32 [M, obs_dim], action float32 [M, act_dim], reward, done,
+ * idx, weight (optional), u (optional).  The discrete push / sample on a continuous ring, or the reverse, is refused. */
+int rl4rs_replay_create_conti(int32_t obs_dim, int32_t act_dim, int32_t max_steps, int32_t batch_size, int64_t buffer_size,
+                              double alpha, rl4rs_replay** out);
+int rl4rs_replay_push_conti(rl4rs_replay* h, const float* obs_dev, const float* action_dev, const double* reward_dev, void* stream);
+int rl4rs_replay_sample_conti(rl4rs_replay* h, int32_t M, int32_t prioritized, double beta, uint32_t seed, uint32_t step,
+                              float* obs_out, float* next_obs_out, float* action_out, float* reward_out, int32_t* done_out,
+                              int32_t* idx_out, float* weight_out, float* u_out, void* stream);
 
 /* DQN loss and gradient on the net of `pol` (replaces ray's dqn_tf_policy build_q_losses behind modelfree_train.py:106-133);
  * target_params_dev: the target net's parameters, a device buffer in the same flat layout.
@@ -1025,6 +1038,76 @@ typedef struct rl4rs_cql_step {
 } rl4rs_cql_step;
 int64_t rl4rs_cql_workspace_floats(int32_t B, int32_t n, int32_t A);
 int rl4rs_cql_update(const rl4rs_cql_step* step, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * On-device TD3 / DDPG on the continuous-action env: script/modelfree_train.py:46-48,79-105 (algo "TD3" / "DDPG" with
+ * support_conti_env; rl4rs/env/base.py:214-215 Box(-1, 1) of action_emb_size values, resolved by the env's masked K-NN).  RLlib
+ * 1.5.1's ddpg_tf_policy / ddpg_tf_model / OrnsteinUhlenbeckNoise are restated from their published form (ray is absent: PARITY
+ * UNPINNED, checked against the fp64 restatement of tests/td3_ref.py).  The reference driver's DDPG branch is an `if` in front of
+ * a separate `if TD3 / elif ... / else: raise` chain, so algo "DDPG" raises there; DDPG here is TD3 with the twin critic, the
+ * policy delay and the target smoothing off.
+ * Networks: two kinds of rl4rs_amlp.  Actor obs -> Dense relu -> Dense relu -> Dense(E), then RLlib's sigmoid(2x) * (high - low)
+ * + low, which on Box(-1, 1) is tanh(x): head_act tanh, act_dim 0.  Critics cat([obs, action]) -> relu -> relu -> 1.
+ * ---------------------------------------------------------------------------------------------- */
+/* RLlib OrnsteinUhlenbeckNoise on a deterministic action det_action_dev [N, E]:
+ *   eps ~ N(0, 1) by Box-Muller on the policy net's counter RNG keyed (seed, step, state row, column); written to eps_out_dev
+ *   [N, E] when that is not NULL
+ *   ou_state += theta * (-ou_state) + sigma * eps
+ *   action = clip(det_action + scale * ou_state * (high - low), -1, 1), high - low = 2; scale = ou_base_scale * the annealed scale
+ * random_phase 1 (RLlib random_timesteps): action = 2u - 1 with u uniform from the same RNG keyed (seed, step, row, column); the
+ * state does not advance and eps_out_dev is not written.
+ * state_rows N: ou_state_dev [N, E], one state per row.  state_rows 1: ou_state_dev [E] is shared by all rows (RLlib's single
+ * variable shaped like one action): eps is keyed by column only and the state advances once per call, not once per row. */
+int rl4rs_explore_ou(int32_t N, int32_t E, int32_t state_rows, const float* det_action_dev, float* ou_state_dev, float theta,
+                     float sigma, float scale, uint32_t seed, uint32_t step, int32_t random_phase, float* action_out_dev,
+                     float* eps_out_dev, void* stream);
+/* TD3 target-policy smoothing: out = clip(action + clip(target_noise * eps, -noise_clip, noise_clip), -1, 1); eps_dev [N, E] is
+ * the caller's N(0, 1).  out_dev may be action_dev. */
+int rl4rs_td3_smooth_action(int32_t N, int32_t E, const float* action_dev, const float* eps_dev, float target_noise,
+                            float noise_clip, float* out_dev, void* stream);
+/* RLlib ddpg_tf_policy's critic loss.  q' = min(q1_targ, q2_targ) (q2_targ_dev NULL: q1_targ); y = r for a terminal row
+ * (dones_dev int32 != 0) and r + gamma * q' otherwise - a select, so nothing of a terminal row's target Q (NaN included) reaches
+ * any output; td_c = q_c - y; per-row error huber(td1, threshold) + huber(td2, threshold) (use_huber) or 0.5 td1^2 + 0.5 td2^2
+ * (q2_dev / dq2_dev NULL: the single critic's one term); loss = mean(w * error), w = weights_dev or 1; dq_c = its gradient wrt q_c.
+ * y_out_dev / td_out_dev (optional) [N]: y and the FIRST critic's td (what the priorities use).  stats4_dev (optional) = sums of
+ * {w * error, q1, y, |td1|}; one workgroup, fixed order: bit-identical from run to run. */
+int rl4rs_td3_critic_loss(int32_t N, const float* q1_dev, const float* q2_dev, const float* q1_targ_dev, const float* q2_targ_dev,
+                          const float* rewards_dev, const int32_t* dones_dev, const float* weights_dev, float gamma,
+                          int32_t use_huber, float huber_threshold, float* dq1_dev, float* dq2_dev, float* y_out_dev,
+                          float* td_out_dev, float* stats4_dev, void* stream);
+/* d_pre = d_out * (1 - tanh_out^2): the gradient wrt a tanh head's pre-activation (what rl4rs_amlp_backward takes) */
+int rl4rs_tanh_head_grad(int32_t N, int32_t E, const float* tanh_out_dev, const float* d_out_dev, float* d_pre_dev, void* stream);
+/* grad += l2 * W on the three weight matrices of the handle's gradient, biases untouched: the gradient of RLlib's
+ * l2_reg * tf.nn.l2_loss(var) over the non-bias variables.  l2 = 0: nothing is launched. */
+int rl4rs_amlp_add_l2(rl4rs_amlp* net, float l2, void* stream);
+
+/* One whole TD3 / DDPG update as ONE host call; both gradients come from the parameters BEFORE the step, as in RLlib's TF policy:
+ *   1. a' = actor_targ(s'), smoothed with noise_dev [M, E] (N(0, 1)) when smooth_target_policy
+ *   2. q' from the target critics on (s', a')                                            (one rl4rs_amlp_forward_multi)
+ *   3. q1, q2 on (s, a), rl4rs_td3_critic_loss, backward of both critics, L2 on both
+ *   4. do_actor: a_pi = actor(s); q1(s, a_pi) forward, backward with dout = -1 / M for the action gradient only; tanh head; actor
+ *      backward; L2 on the actor
+ *   5. ONE rl4rs_amlp_adam_multi for {q1, q2, actor} (the actor steps only when do_actor) with the soft updates of ALL THREE targets
+ *      (RLlib update_target at target_network_update_freq 0: the actor's target moves even when the actor did not step); Adam
+ *      beta 0.9 / 0.999, eps 1e-7 (tf.keras's value, in rl4rs_amlp_adam_step's form)
+ * q2 / q2_targ NULL: DDPG's single critic.  weights_dev NULL: 1.  td_out_dev [M]: the first critic's TD errors.
+ * metrics_dev float[6] = {sum w * error, sum q1, sum y, sum |td1|, -sum q1(s, a_pi) (written only when do_actor), spare}; the L2
+ * terms are not part of them.  workspace_dev: rl4rs_td3_workspace_floats(M, E) floats, 16-byte aligned.  Single process only:
+ * the data-parallel trainer issues the same sequence as per-phase calls around its all-reduce. */
+typedef struct rl4rs_td3_step {
+    rl4rs_amlp *actor, *actor_targ, *q1, *q2, *q1_targ, *q2_targ;
+    int32_t M, E;
+    float gamma, tau, actor_lr, critic_lr, target_noise, target_noise_clip, l2_reg, huber_threshold;
+    int32_t smooth_target_policy, use_huber, do_actor, reserved;
+    const float *obs_dev, *act_dev, *rew_dev;
+    const int32_t* done_dev;
+    const float *nxt_dev, *weights_dev, *noise_dev;
+    float* workspace_dev;
+    float* td_out_dev;
+    float* metrics_dev;
+} rl4rs_td3_step;
+int64_t rl4rs_td3_workspace_floats(int32_t M, int32_t E);
+int rl4rs_td3_update(const rl4rs_td3_step* step, void* stream);
 
 /* Plain fp32 GEMM used by the scorer, exposed for tests: C[M,N] = act(A[M,K] @ W[K,N] + bias).
  * act: 0 none, 1 ELU, 2 sigmoid, 3 tanh, 4 ReLU. */

@@ -90,6 +90,17 @@ class BcqStep(C.Structure):
                 [(n, C.c_void_p) for n in ('obs_dev', 'act_dev', 'rew_dev', 'nxt_dev', 'ter_dev', 'noise_dev', 'workspace_dev', 'metrics_dev')])
 
 
+class Td3Step(C.Structure):
+    """rl4rs_td3_step (include/rl4rs_hip.h)"""
+    _fields_ = ([(n, C.c_void_p) for n in ('actor', 'actor_targ', 'q1', 'q2', 'q1_targ', 'q2_targ')] +
+                [(n, C.c_int32) for n in ('M', 'E')] +
+                [(n, C.c_float) for n in ('gamma', 'tau', 'actor_lr', 'critic_lr', 'target_noise', 'target_noise_clip', 'l2_reg',
+                                          'huber_threshold')] +
+                [(n, C.c_int32) for n in ('smooth_target_policy', 'use_huber', 'do_actor', 'reserved')] +
+                [(n, C.c_void_p) for n in ('obs_dev', 'act_dev', 'rew_dev', 'done_dev', 'nxt_dev', 'weights_dev', 'noise_dev',
+                                           'workspace_dev', 'td_out_dev', 'metrics_dev')])
+
+
 class CqlStep(C.Structure):
     """rl4rs_cql_step (include/rl4rs_hip.h)"""
     _fields_ = ([(n, C.c_void_p) for n in ('policy', 'q1', 'q2', 'q1_targ', 'q2_targ')] +
@@ -304,13 +315,23 @@ SIGNATURES = {
     'rl4rs_replay_push': (_I, [_P, _P, _P, _P, _P, _P]),
     'rl4rs_replay_sample': (_I, [_P, _I32, _I32, C.c_double, C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'rl4rs_replay_update_priorities': (_I, [_P, _I32, _P, _P, _P]),
+    'rl4rs_replay_create_conti': (_I, [_I32, _I32, _I32, _I32, _I64, C.c_double, C.POINTER(_P)]),
+    'rl4rs_replay_push_conti': (_I, [_P, _P, _P, _P, _P]),
+    'rl4rs_replay_sample_conti': (_I, [_P, _I32, _I32, C.c_double, C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    'rl4rs_explore_ou': (_I, [_I32, _I32, _I32, _P, _P, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_uint32, _I32, _P, _P, _P]),
+    'rl4rs_td3_smooth_action': (_I, [_I32, _I32, _P, _P, C.c_float, C.c_float, _P, _P]),
+    'rl4rs_td3_critic_loss': (_I, [_I32, _P, _P, _P, _P, _P, _P, _P, C.c_float, _I32, C.c_float, _P, _P, _P, _P, _P, _P]),
+    'rl4rs_tanh_head_grad': (_I, [_I32, _I32, _P, _P, _P, _P]),
+    'rl4rs_amlp_add_l2': (_I, [_P, C.c_float, _P]),
+    'rl4rs_td3_workspace_floats': (_I64, [_I32, _I32]),
+    'rl4rs_td3_update': (_I, [C.POINTER(Td3Step), _P]),
     'rl4rs_policy_dqn_loss_grad': (_I, [_P, _P, _I32, _P, _P, _P, _P, _P, _P, _P, C.c_float, _I32, _P, _P, _P, _P, _P]),
     'rl4rs_policy_greedy': (_I, [_P, _I32, _P, _P, _P, _P, _P]),
     'rl4rs_policy_adam_step_clip_by_var': (_I, [_P, _P, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _P]),
 }
 
 # include/rl4rs_hip.h RL4RS_REPLAY_BUF_*
-REPLAY_BUFS = {'obs': 0, 'mask': 1, 'action': 2, 'reward': 3, 'done': 4, 'priority': 5, 'max_priority': 6}
+REPLAY_BUFS = {'obs': 0, 'mask': 1, 'action': 2, 'reward': 3, 'done': 4, 'priority': 5, 'max_priority': 6, 'action_f32': 7}
 
 # include/rl4rs_hip.h RL4RS_OPE_COL_* / RL4RS_OPE_* (statistics slots)
 OPE_COLS = {'pi': 0, 'mu': 1, 'q': 2, 'reward': 3, 'logged_reward': 4}

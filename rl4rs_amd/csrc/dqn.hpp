@@ -1,6 +1,7 @@
 // On-device DQN for the action-masked FC net (include/rl4rs_hip.h, "On-device DQN"): a replay ring of whole rollouts with
 // uniform / proportional-prioritized sampling, the (double-)Q Huber loss and its rank-sparse backward on rl4rs_policy, the masked
-// greedy action, and an Adam step that clips every variable by its own norm.  Compiled into policy.hip (uniform01, wave
+// greedy action, and an Adam step that clips every variable by its own norm.  The same ring stores the continuous actions of TD3 /
+// DDPG (td3.hpp): rl4rs_replay_*_conti share the handle, the scans, the draw rule and k_replay_sample.  Compiled into policy.hip (uniform01, wave
 // reductions, policy_row_forward, the fixed-order sample-axis reductions and the rl4rs_policy handle live there).
 //
 // Reference: script/modelfree_train.py:106-133 (algo "DQN": hiddens [], dueling False, double_q True, n_step 1,
@@ -85,12 +86,12 @@ __global__ void k_prio_scan_offsets(const double* __restrict__ tile_sum, const d
 }
 
 struct ReplaySample {
-    int M, n, B, OD, W, prioritized, vec4;
+    int M, n, B, OD, W, E, prioritized, vec4;      // E > 0: a ring of continuous actions (no mask words, no int32 action)
     double beta;
     uint32_t seed, step;
-    const float* obs; const uint32_t* mask; const int32_t* act; const float* rew; const int32_t* done;
+    const float* obs; const uint32_t* mask; const int32_t* act; const float* actf; const float* rew; const int32_t* done;
     const double* prio; const double* local; const double* tile_off; const double* tot;
-    float* obs_out; float* next_obs_out; uint32_t* next_mask_out; int32_t* act_out; float* rew_out; int32_t* done_out;
+    float* obs_out; float* next_obs_out; uint32_t* next_mask_out; int32_t* act_out; float* actf_out; float* rew_out; int32_t* done_out;
     int32_t* idx_out; float* w_out; float* u_out;
 };
 
@@ -148,8 +149,9 @@ __global__ __launch_bounds__(256) void k_replay_sample(ReplaySample a) {
         }
     }
     for (int k = lane; k < a.W; k += 64) a.next_mask_out[(size_t)m * a.W + k] = a.mask[(size_t)nxt * a.W + k];
+    for (int k = lane; k < a.E; k += 64) a.actf_out[(size_t)m * a.E + k] = a.actf[(size_t)idx * a.E + k];
     if (lane == 0) {
-        a.act_out[m] = a.act[idx];
+        if (a.act) a.act_out[m] = a.act[idx];
         a.rew_out[m] = a.rew[idx];
         a.done_out[m] = dn;
         a.idx_out[m] = idx;
@@ -421,10 +423,10 @@ __global__ void k_adam_vars(float* __restrict__ p, const float* __restrict__ g, 
 }  // namespace rl4rs
 
 struct rl4rs_replay {
-    int OD, A, W, T, B, cap_rollouts, rows_per, cap_rows, n_tiles;
+    int OD, A, W, E, T, B, cap_rollouts, rows_per, cap_rows, n_tiles;      // E > 0: continuous actions float32 [E] (then A = W = 0)
     int64_t pushes;
     double alpha;
-    float* obs; uint32_t* mask; int32_t* act; float* rew; int32_t* done; double* prio;
+    float* obs; uint32_t* mask; int32_t* act; float* actf; float* rew; int32_t* done; double* prio;
     double* state;          // [0] max_priority, [1] total, [2] smallest priority (of the last prioritized sample)
     double *local, *tile_sum, *tile_min, *tile_off;
     int32_t* claim;
@@ -448,10 +450,9 @@ static int dqn_scratch(rl4rs_policy* p) {
 
 extern "C" {
 
-int rl4rs_replay_create(int32_t obs_dim, int32_t action_size, int32_t max_steps, int32_t batch_size, int64_t buffer_size, double alpha,
-                        rl4rs_replay** out) {
-    RL4RS_REQUIRE(out && obs_dim > 0 && action_size > 1 && max_steps > 0 && batch_size > 0 && buffer_size > 0 && alpha >= 0.0,
-                  "replay_create: bad argument");
+// one ring for both action kinds: action_size > 1 and act_dim = 0 (discrete: mask words + int32 action), or act_dim > 0 (continuous)
+static int replay_create(int32_t obs_dim, int32_t action_size, int32_t act_dim, int32_t max_steps, int32_t batch_size, int64_t buffer_size,
+                         double alpha, rl4rs_replay** out) {
     const int64_t per = (int64_t)max_steps * batch_size;
     const int64_t cap = std::max<int64_t>(1, buffer_size / per);
     RL4RS_REQUIRE(cap * per < ((int64_t)1 << 30), "replay_create: %lld rollouts of %lld rows exceed 2^30 rows", (long long)cap, (long long)per);
@@ -460,11 +461,12 @@ int rl4rs_replay_create(int32_t obs_dim, int32_t action_size, int32_t max_steps,
         return RL4RS_EHIP;
     }
     rl4rs_replay* h = new rl4rs_replay();
-    h->OD = obs_dim; h->A = action_size; h->W = (action_size + 31) / 32; h->T = max_steps; h->B = batch_size;
+    h->OD = obs_dim; h->A = action_size; h->W = (action_size + 31) / 32; h->E = act_dim; h->T = max_steps; h->B = batch_size;
     h->cap_rollouts = (int)cap; h->rows_per = (int)per; h->cap_rows = (int)(cap * per);
     h->n_tiles = (h->cap_rows + PRIO_TILE - 1) / PRIO_TILE;
     h->pushes = 0;
     h->alpha = alpha;
+    h->mask = nullptr; h->act = nullptr; h->actf = nullptr;
     int rc = RL4RS_OK;
     auto alloc = [&](auto** dst, size_t n) {
         if (rc) return;
@@ -473,8 +475,12 @@ int rl4rs_replay_create(int32_t obs_dim, int32_t action_size, int32_t max_steps,
     };
     const size_t R = (size_t)h->cap_rows;
     alloc(&h->obs, R * obs_dim);
-    alloc(&h->mask, R * h->W);
-    alloc(&h->act, R);
+    if (act_dim > 0) {
+        alloc(&h->actf, R * act_dim);
+    } else {
+        alloc(&h->mask, R * h->W);
+        alloc(&h->act, R);
+    }
     alloc(&h->rew, R);
     alloc(&h->done, R);
     alloc(&h->prio, R);
@@ -497,6 +503,20 @@ int rl4rs_replay_create(int32_t obs_dim, int32_t action_size, int32_t max_steps,
     return RL4RS_OK;
 }
 
+int rl4rs_replay_create(int32_t obs_dim, int32_t action_size, int32_t max_steps, int32_t batch_size, int64_t buffer_size, double alpha,
+                        rl4rs_replay** out) {
+    RL4RS_REQUIRE(out && obs_dim > 0 && action_size > 1 && max_steps > 0 && batch_size > 0 && buffer_size > 0 && alpha >= 0.0,
+                  "replay_create: bad argument");
+    return replay_create(obs_dim, action_size, 0, max_steps, batch_size, buffer_size, alpha, out);
+}
+
+int rl4rs_replay_create_conti(int32_t obs_dim, int32_t act_dim, int32_t max_steps, int32_t batch_size, int64_t buffer_size, double alpha,
+                              rl4rs_replay** out) {
+    RL4RS_REQUIRE(out && obs_dim > 0 && act_dim > 0 && max_steps > 0 && batch_size > 0 && buffer_size > 0 && alpha >= 0.0,
+                  "replay_create_conti: bad argument");
+    return replay_create(obs_dim, 0, act_dim, max_steps, batch_size, buffer_size, alpha, out);
+}
+
 int rl4rs_replay_destroy(rl4rs_replay* h) {
     if (!h) return RL4RS_OK;
     for (void* q : h->owned) (void)hipFree(q);
@@ -517,8 +537,15 @@ int rl4rs_replay_buffer(rl4rs_replay* h, int32_t which, void** dev, int64_t* cou
     const int64_t R = h->cap_rows;
     switch (which) {
         case RL4RS_REPLAY_BUF_OBS: *dev = h->obs; if (count) *count = R * h->OD; break;
-        case RL4RS_REPLAY_BUF_MASK: *dev = h->mask; if (count) *count = R * h->W; break;
-        case RL4RS_REPLAY_BUF_ACTION: *dev = h->act; if (count) *count = R; break;
+        case RL4RS_REPLAY_BUF_MASK:
+            RL4RS_REQUIRE(h->E == 0, "replay_buffer: a ring of continuous actions has no mask column");
+            *dev = h->mask; if (count) *count = R * h->W; break;
+        case RL4RS_REPLAY_BUF_ACTION:
+            RL4RS_REQUIRE(h->E == 0, "replay_buffer: a ring of continuous actions has no int32 action column (RL4RS_REPLAY_BUF_ACTION_F32)");
+            *dev = h->act; if (count) *count = R; break;
+        case RL4RS_REPLAY_BUF_ACTION_F32:
+            RL4RS_REQUIRE(h->E > 0, "replay_buffer: a ring of discrete actions has no float32 action column (RL4RS_REPLAY_BUF_ACTION)");
+            *dev = h->actf; if (count) *count = R * h->E; break;
         case RL4RS_REPLAY_BUF_REWARD: *dev = h->rew; if (count) *count = R; break;
         case RL4RS_REPLAY_BUF_DONE: *dev = h->done; if (count) *count = R; break;
         case RL4RS_REPLAY_BUF_PRIORITY: *dev = h->prio; if (count) *count = R; break;
@@ -528,14 +555,17 @@ int rl4rs_replay_buffer(rl4rs_replay* h, int32_t which, void** dev, int64_t* cou
     return RL4RS_OK;
 }
 
-int rl4rs_replay_push(rl4rs_replay* h, const float* obs_dev, const uint32_t* mask_dev, const int32_t* action_dev,
-                      const double* reward_dev, void* stream) {
-    RL4RS_REQUIRE(h && obs_dev && mask_dev && action_dev && reward_dev, "replay_push: null argument");
-    hipStream_t st = (hipStream_t)stream;
+// shared by the two action kinds: the rollout's columns into the slot, derived columns by k_replay_push
+static int replay_push(rl4rs_replay* h, const float* obs_dev, const uint32_t* mask_dev, const int32_t* action_dev, const float* actf_dev,
+                       const double* reward_dev, hipStream_t st) {
     const size_t slot = (size_t)(h->pushes % h->cap_rollouts), r0 = slot * h->rows_per, R = (size_t)h->rows_per;
     RL4RS_HIP_TRY(hipMemcpyAsync(h->obs + r0 * h->OD, obs_dev, R * h->OD * 4, hipMemcpyDeviceToDevice, st));
-    RL4RS_HIP_TRY(hipMemcpyAsync(h->mask + r0 * h->W, mask_dev, R * h->W * 4, hipMemcpyDeviceToDevice, st));
-    RL4RS_HIP_TRY(hipMemcpyAsync(h->act + r0, action_dev, R * 4, hipMemcpyDeviceToDevice, st));
+    if (h->E > 0) {
+        RL4RS_HIP_TRY(hipMemcpyAsync(h->actf + r0 * h->E, actf_dev, R * h->E * 4, hipMemcpyDeviceToDevice, st));
+    } else {
+        RL4RS_HIP_TRY(hipMemcpyAsync(h->mask + r0 * h->W, mask_dev, R * h->W * 4, hipMemcpyDeviceToDevice, st));
+        RL4RS_HIP_TRY(hipMemcpyAsync(h->act + r0, action_dev, R * 4, hipMemcpyDeviceToDevice, st));
+    }
     hipLaunchKernelGGL(k_replay_push, dim3((h->rows_per + 255) / 256), dim3(256), 0, st, h->rows_per, h->B, h->T, reward_dev,
                        h->rew + r0, h->done + r0, h->prio + r0, h->state, h->alpha);
     RL4RS_LAUNCH_CHECK();
@@ -543,13 +573,23 @@ int rl4rs_replay_push(rl4rs_replay* h, const float* obs_dev, const uint32_t* mas
     return RL4RS_OK;
 }
 
-int rl4rs_replay_sample(rl4rs_replay* h, int32_t M, int32_t prioritized, double beta, uint32_t seed, uint32_t step, float* obs_out,
-                        float* next_obs_out, uint32_t* next_mask_out, int32_t* action_out, float* reward_out, int32_t* done_out,
-                        int32_t* idx_out, float* weight_out, float* u_out, void* stream) {
-    RL4RS_REQUIRE(h && M > 0 && obs_out && next_obs_out && next_mask_out && action_out && reward_out && done_out && idx_out,
-                  "replay_sample: bad argument");
+int rl4rs_replay_push(rl4rs_replay* h, const float* obs_dev, const uint32_t* mask_dev, const int32_t* action_dev,
+                      const double* reward_dev, void* stream) {
+    RL4RS_REQUIRE(h && obs_dev && mask_dev && action_dev && reward_dev, "replay_push: null argument");
+    RL4RS_REQUIRE(h->E == 0, "replay_push: this ring stores continuous actions (rl4rs_replay_push_conti)");
+    return replay_push(h, obs_dev, mask_dev, action_dev, nullptr, reward_dev, (hipStream_t)stream);
+}
+
+int rl4rs_replay_push_conti(rl4rs_replay* h, const float* obs_dev, const float* action_dev, const double* reward_dev, void* stream) {
+    RL4RS_REQUIRE(h && obs_dev && action_dev && reward_dev, "replay_push_conti: null argument");
+    RL4RS_REQUIRE(h->E > 0, "replay_push_conti: this ring stores discrete actions (rl4rs_replay_push)");
+    return replay_push(h, obs_dev, nullptr, nullptr, action_dev, reward_dev, (hipStream_t)stream);
+}
+
+static int replay_sample(rl4rs_replay* h, int32_t M, int32_t prioritized, double beta, uint32_t seed, uint32_t step, float* obs_out,
+                         float* next_obs_out, uint32_t* next_mask_out, int32_t* action_out, float* actf_out, float* reward_out,
+                         int32_t* done_out, int32_t* idx_out, float* weight_out, float* u_out, hipStream_t st) {
     RL4RS_REQUIRE(h->pushes > 0, "replay_sample: the memory is empty");
-    hipStream_t st = (hipStream_t)stream;
     const int n = (int)(std::min<int64_t>(h->pushes, h->cap_rollouts) * h->rows_per);
     if (prioritized) {
         const int nt = (n + PRIO_TILE - 1) / PRIO_TILE;
@@ -558,16 +598,35 @@ int rl4rs_replay_sample(rl4rs_replay* h, int32_t M, int32_t prioritized, double 
         RL4RS_LAUNCH_CHECK();
     }
     ReplaySample a;
-    a.M = M; a.n = n; a.B = h->B; a.OD = h->OD; a.W = h->W; a.prioritized = prioritized ? 1 : 0;
+    a.M = M; a.n = n; a.B = h->B; a.OD = h->OD; a.W = h->W; a.E = h->E; a.prioritized = prioritized ? 1 : 0;
     a.vec4 = (h->OD % 4 == 0 && ((reinterpret_cast<uintptr_t>(obs_out) | reinterpret_cast<uintptr_t>(next_obs_out)) & 15) == 0) ? 1 : 0;
     a.beta = beta; a.seed = seed; a.step = step;
-    a.obs = h->obs; a.mask = h->mask; a.act = h->act; a.rew = h->rew; a.done = h->done;
+    a.obs = h->obs; a.mask = h->mask; a.act = h->act; a.actf = h->actf; a.rew = h->rew; a.done = h->done;
     a.prio = h->prio; a.local = h->local; a.tile_off = h->tile_off; a.tot = h->state + 1;
-    a.obs_out = obs_out; a.next_obs_out = next_obs_out; a.next_mask_out = next_mask_out; a.act_out = action_out; a.rew_out = reward_out;
-    a.done_out = done_out; a.idx_out = idx_out; a.w_out = weight_out; a.u_out = u_out;
+    a.obs_out = obs_out; a.next_obs_out = next_obs_out; a.next_mask_out = next_mask_out; a.act_out = action_out; a.actf_out = actf_out;
+    a.rew_out = reward_out; a.done_out = done_out; a.idx_out = idx_out; a.w_out = weight_out; a.u_out = u_out;
     hipLaunchKernelGGL(k_replay_sample, dim3((M + 3) / 4), dim3(256), 0, st, a);
     RL4RS_LAUNCH_CHECK();
     return RL4RS_OK;
+}
+
+int rl4rs_replay_sample(rl4rs_replay* h, int32_t M, int32_t prioritized, double beta, uint32_t seed, uint32_t step, float* obs_out,
+                        float* next_obs_out, uint32_t* next_mask_out, int32_t* action_out, float* reward_out, int32_t* done_out,
+                        int32_t* idx_out, float* weight_out, float* u_out, void* stream) {
+    RL4RS_REQUIRE(h && M > 0 && obs_out && next_obs_out && next_mask_out && action_out && reward_out && done_out && idx_out,
+                  "replay_sample: bad argument");
+    RL4RS_REQUIRE(h->E == 0, "replay_sample: this ring stores continuous actions (rl4rs_replay_sample_conti)");
+    return replay_sample(h, M, prioritized, beta, seed, step, obs_out, next_obs_out, next_mask_out, action_out, nullptr, reward_out, done_out,
+                         idx_out, weight_out, u_out, (hipStream_t)stream);
+}
+
+int rl4rs_replay_sample_conti(rl4rs_replay* h, int32_t M, int32_t prioritized, double beta, uint32_t seed, uint32_t step, float* obs_out,
+                              float* next_obs_out, float* action_out, float* reward_out, int32_t* done_out, int32_t* idx_out,
+                              float* weight_out, float* u_out, void* stream) {
+    RL4RS_REQUIRE(h && M > 0 && obs_out && next_obs_out && action_out && reward_out && done_out && idx_out, "replay_sample_conti: bad argument");
+    RL4RS_REQUIRE(h->E > 0, "replay_sample_conti: this ring stores discrete actions (rl4rs_replay_sample)");
+    return replay_sample(h, M, prioritized, beta, seed, step, obs_out, next_obs_out, nullptr, nullptr, action_out, reward_out, done_out,
+                         idx_out, weight_out, u_out, (hipStream_t)stream);
 }
 
 int rl4rs_replay_update_priorities(rl4rs_replay* h, int32_t M, const int32_t* idx_dev, const float* td_dev, void* stream) {

@@ -1490,6 +1490,61 @@ class DeviceReplay(object):
         return float(self.column('max_priority').cpu()[0])
 
 
+class DeviceContiReplay(DeviceReplay):
+    """The same ring for the continuous-action env (rl4rs_replay_create_conti): ``DeviceReplay``'s methods with a float32 action
+    column [act_dim] (``column('action')``) and no mask column.  The handle refuses the discrete push / sample."""
+    _DTYPES = {'obs': torch.float32, 'action': torch.float32, 'reward': torch.float32, 'done': torch.int32, 'priority': torch.float64,
+               'max_priority': torch.float64}
+
+    def __init__(self, obs_dim, act_dim, max_steps, batch_size, buffer_size=100000, alpha=0.6, device=None):
+        _lib.require_device()
+        self.lib = _lib.load()
+        self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        self.obs_dim, self.act_dim, self.T, self.B = int(obs_dim), int(act_dim), int(max_steps), int(batch_size)
+        self.alpha = float(alpha)
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            check(self.lib.rl4rs_replay_create_conti(self.obs_dim, self.act_dim, self.T, self.B, int(buffer_size), self.alpha, C.byref(h)))
+        self.h = h
+
+    def _buffer(self, name):
+        return DeviceReplay._buffer(self, 'action_f32' if name == 'action' else name)
+
+    def column(self, name):
+        p, n = self._buffer(name)
+        out = torch.empty(n, dtype=self._DTYPES[name], device=self.device)
+        check(self.lib.rl4rs_copy_d2d(_ptr(out), p, n * out.element_size(), _stream()))
+        cap = self.counts()[1]
+        return out.view(cap, -1) if name in ('obs', 'action') else out
+
+    def push(self, obs, actions, rewards):
+        """One rollout: obs f32 [T * B, obs_dim], actions f32 [T * B, act_dim], rewards f64, all in row order t * B + b."""
+        R = self.T * self.B
+        assert obs.dtype == torch.float32 and obs.shape == (R, self.obs_dim) and obs.is_contiguous()
+        assert actions.dtype == torch.float32 and actions.shape == (R, self.act_dim) and actions.is_contiguous()
+        assert rewards.dtype == torch.float64 and rewards.shape == (R,) and rewards.is_contiguous()
+        check(self.lib.rl4rs_replay_push_conti(self.h, _ptr(obs), _ptr(actions), _ptr(rewards), _stream()))
+
+    def new_batch(self, M, want_u=False):
+        dev = self.device
+        b = dict(obs=torch.empty((M, self.obs_dim), dtype=torch.float32, device=dev),
+                 next_obs=torch.empty((M, self.obs_dim), dtype=torch.float32, device=dev),
+                 action=torch.empty((M, self.act_dim), dtype=torch.float32, device=dev),
+                 reward=torch.empty(M, dtype=torch.float32, device=dev), done=torch.empty(M, dtype=torch.int32, device=dev),
+                 idx=torch.empty(M, dtype=torch.int32, device=dev), weight=torch.empty(M, dtype=torch.float32, device=dev))
+        b['u'] = torch.empty(M, dtype=torch.float32, device=dev) if want_u else None
+        return b
+
+    def sample(self, M, prioritized=True, beta=0.4, seed=0, step=0, out=None, want_u=False):
+        """Draw and gather M rows (rl4rs_replay_sample_conti) -> dict obs, next_obs, action, reward, done, idx, weight, u."""
+        b = out if out is not None else self.new_batch(M, want_u)
+        assert b['obs'].shape[0] == M
+        check(self.lib.rl4rs_replay_sample_conti(self.h, M, 1 if prioritized else 0, float(beta), seed & 0xffffffff, step & 0xffffffff,
+                                                 _ptr(b['obs']), _ptr(b['next_obs']), _ptr(b['action']), _ptr(b['reward']), _ptr(b['done']),
+                                                 _ptr(b['idx']), _ptr(b['weight']), _ptr(b.get('u')), _stream()))
+        return b
+
+
 class DeviceQNet(object):
     """rl4rs_qnet handle: one offline-RL network (the reference's ``CustomVectorEncoder`` of rl4rs/nets/cql/encoder.py:9-67,
     or d3rlpy's plain ``VectorEncoder``, + d3rlpy's Linear head) with forward, backward and torch-style Adam on the device.
@@ -2004,3 +2059,63 @@ def cql_critic_loss(q1, q2, offs, m, y=None, alpha_w=None):
     check(lib.rl4rs_cql_critic_loss(B, m, _ptr(q1), _ptr(q2), _ptr(offs), _ptr(y), _ptr(alpha_w), _ptr(dq1), _ptr(dq2), _ptr(rows), _ptr(sums),
                                     _stream()))
     return sums, dq1, dq2
+
+
+# ---- TD3 / DDPG (csrc/td3.hpp) ------------------------------------------------------------------------------------------------
+def explore_ou(det_action, ou_state, theta=0.15, sigma=0.2, scale=0.1, seed=0, step=0, random_phase=False, out=None, want_eps=False):
+    """RLlib's OrnsteinUhlenbeckNoise on a deterministic action [N, E] (rl4rs_explore_ou): advances ``ou_state`` ([N, E], or [E] /
+    [1, E] shared by all rows) in place and returns (action, eps or None).  ``random_phase``: uniform actions, the state stays."""
+    lib = _lib.load()
+    N, E = det_action.shape
+    rows = 1 if ou_state.numel() == E else N
+    assert ou_state.numel() == rows * E and ou_state.dtype == torch.float32 and ou_state.is_contiguous() and ou_state.is_cuda
+    assert det_action.dtype == torch.float32 and det_action.is_contiguous() and det_action.is_cuda
+    if out is None:
+        out = torch.empty_like(det_action)
+    eps = torch.empty_like(det_action) if want_eps else None
+    check(lib.rl4rs_explore_ou(N, E, rows, _ptr(det_action), _ptr(ou_state), theta, sigma, scale, seed & 0xffffffff, step & 0xffffffff,
+                               1 if random_phase else 0, _ptr(out), _ptr(eps), _stream()))
+    return out, eps
+
+
+def td3_smooth_action(action, eps, target_noise=0.2, noise_clip=0.5, out=None):
+    """clip(action + clip(target_noise * eps, -noise_clip, noise_clip), -1, 1)."""
+    lib = _lib.load()
+    N, E = action.shape
+    assert eps.shape == action.shape and eps.dtype == torch.float32 and eps.is_contiguous() and action.is_contiguous()
+    if out is None:
+        out = torch.empty_like(action)
+    check(lib.rl4rs_td3_smooth_action(N, E, _ptr(action), _ptr(eps), target_noise, noise_clip, _ptr(out), _stream()))
+    return out
+
+
+def td3_critic_loss(q1, q2, q1_targ, q2_targ, rewards, dones, weights=None, gamma=1.0, use_huber=False, huber_threshold=1.0,
+                    td_out=None, stats_out=None):
+    """RLlib DDPG / TD3 critic loss (rl4rs_td3_critic_loss) -> dict dq1, dq2 (None for a single critic), y, td, stats
+    (sums of {w * error, q1, y, |td1|})."""
+    lib = _lib.load()
+    N = q1.numel()
+    assert dones.dtype == torch.int32 and rewards.dtype == torch.float32 and dones.numel() == N and rewards.numel() == N
+    dev = q1.device
+    dq1 = torch.empty(N, dtype=torch.float32, device=dev)
+    dq2 = torch.empty(N, dtype=torch.float32, device=dev) if q2 is not None else None
+    y = torch.empty(N, dtype=torch.float32, device=dev)
+    td = td_out if td_out is not None else torch.empty(N, dtype=torch.float32, device=dev)
+    stats = stats_out if stats_out is not None else torch.empty(4, dtype=torch.float32, device=dev)
+    check(lib.rl4rs_td3_critic_loss(N, _ptr(q1), _ptr(q2), _ptr(q1_targ), _ptr(q2_targ), _ptr(rewards), _ptr(dones), _ptr(weights), gamma,
+                                    1 if use_huber else 0, huber_threshold, _ptr(dq1), _ptr(dq2), _ptr(y), _ptr(td), _ptr(stats), _stream()))
+    return dict(dq1=dq1, dq2=dq2, y=y, td=td, stats=stats)
+
+
+def tanh_head_grad(tanh_out, d_out):
+    """d_out * (1 - tanh_out^2): the gradient wrt a tanh head's pre-activation."""
+    lib = _lib.load()
+    N, E = tanh_out.shape
+    d = torch.empty_like(tanh_out)
+    check(lib.rl4rs_tanh_head_grad(N, E, _ptr(tanh_out), _ptr(d_out), _ptr(d), _stream()))
+    return d
+
+
+def amlp_add_l2(net, l2):
+    """grad += l2 * W on the three weight matrices of ``net``'s gradient (biases untouched)."""
+    check(_lib.load().rl4rs_amlp_add_l2(net.h, float(l2), _stream()))

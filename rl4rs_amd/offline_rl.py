@@ -343,6 +343,22 @@ def init_amlp_params(obs_dim, act_dim, out_dim, hidden1=256, hidden2=256, seed=0
     return p
 
 
+def init_ddpg_params(obs_dim, act_dim, out_dim, hidden1=400, hidden2=300, seed=0):
+    """Keras Dense defaults, what RLlib's ddpg_tf_model builds its actor and critics from: ``glorot_uniform`` kernels
+    (U(+-sqrt(6 / (fan_in + fan_out)))) and zero biases, stored [in, out] in ``DeviceAMLP``'s layout."""
+    rs = np.random.RandomState(seed)
+
+    def dense(fan_in, fan_out):
+        k = np.sqrt(6.0 / (fan_in + fan_out))
+        return rs.uniform(-k, k, size=(fan_in, fan_out)).astype(np.float32), np.zeros(fan_out, dtype=np.float32)
+
+    p = {}
+    p['fc1_w'], p['fc1_b'] = dense(obs_dim + act_dim, hidden1)
+    p['fc2_w'], p['fc2_b'] = dense(hidden1, hidden2)
+    p['head_w'], p['head_b'] = dense(hidden2, out_dim)
+    return p
+
+
 def _check_transitions(device, D, E, obs, act, rew, nxt, ter):
     """The one-call updates hand raw pointers to the library (which only knows the row count): everything DeviceAMLP._rows asserts
     on the per-phase path is asserted here - device, float32, shapes [B, D] / [B, E] / [B] - before any data_ptr() is taken."""

@@ -10,6 +10,9 @@ cumulative sum of rewards and (data-parallel) the RCCL all-reduce of the flat gr
 target_network_update_freq 200, buffer_size 100000 on the mask model): replay memory, TD loss, per-variable-clipped Adam and
 the target copy all stay on the device (rl4rs_replay_*, rl4rs_policy_dqn_loss_grad).
 
+``TD3Trainer`` is the continuous actor-critic learner of that driver (script/modelfree_train.py:46-48,79-105: RLlib TD3 / DDPG on
+support_conti_env): OU exploration, a replay ring of float actions and the whole update (rl4rs_td3_update) stay on the device.
+
 Data parallelism: every rank owns its own env batch and sampling stream (``seed`` differs per rank) and a replica
 of the policy that is IDENTICAL on all ranks: initialised from the shared ``init_seed``, rank 0's parameters / Adam state are
 broadcast at construction, and every optimiser step applies the rank-mean gradient.  A2C: one all-reduce per iteration.
@@ -113,11 +116,17 @@ class _DeferredStats(object):
         self._settle()
         self._kl_coeff = float(v)
 
+    def _status_word(self, dev):
+        """float64 [1]: non-zero when a persistent pass of this call timed out.  The default reads the policy handle's status words;
+        a trainer whose networks have none returns zero."""
+        if hasattr(self.policy, 'status_words'):
+            return self.policy.status_words()[1:2].to(torch.float64)
+        return torch.zeros(1, dtype=torch.float64, device=dev)
+
     def _submit(self, mean_reward, stats, kl_div, extra):
         """Enqueue the device -> pinned copy of one train call's numbers [mean_reward, stats..., status word] and an event."""
         dev = stats.device
-        status = (self.policy.status_words()[1:2].to(torch.float64) if hasattr(self.policy, 'status_words')
-                  else torch.zeros(1, dtype=torch.float64, device=dev))
+        status = self._status_word(dev)
         overflow = rdist.take_row_overflow(dev)
         if overflow is not None:
             status = status + 1000.0 * overflow.to(torch.float64)
@@ -619,6 +628,336 @@ class DQNTrainer(_DeferredStats):
             total = torch.zeros((), dtype=torch.float64, device=self.buf['obs'].device)
             for k in range(n):
                 total += self._episode(True, 0, reset_file=k == 0)
+        finally:
+            np.random.set_state(state)
+        return float(total.item()) / n
+
+
+# ---- TD3 / DDPG -----------------------------------------------------------------------------------------------------------------
+# What the reference's merged config makes of RLlib 1.5.1's TD3 / DDPG defaults (script/modelfree_train.py:79-105): every value is a
+# constructor argument of TD3Trainer, None = the preset of its ``algo``.
+TD3_PRESETS = {
+    'TD3': dict(twin_q=True, policy_delay=2, smooth_target_policy=True, target_noise=0.2, target_noise_clip=0.5, tau=5e-3, l2_reg=0.0,
+                buffer_size=1000000, prioritized_replay=False, learning_starts=10000, random_timesteps=10000),
+    'DDPG': dict(twin_q=False, policy_delay=1, smooth_target_policy=False, target_noise=0.2, target_noise_clip=0.5, tau=2e-3, l2_reg=1e-6,
+                 buffer_size=50000, prioritized_replay=True, learning_starts=1500, random_timesteps=1000),
+}
+
+
+def ou_scale(timestep, random_timesteps=0, initial_scale=1.0, final_scale=0.02, scale_timesteps=10000):
+    """RLlib's exploration scale (GaussianNoise / OrnsteinUhlenbeckNoise: PiecewiseSchedule from (random_timesteps, initial_scale) to
+    (random_timesteps + scale_timesteps, final_scale), final_scale outside): linear in the sampled timestep."""
+    t = float(timestep) - float(random_timesteps)
+    if t < 0.0 or t >= scale_timesteps:
+        return float(final_scale)
+    return float(initial_scale) + (float(final_scale) - float(initial_scale)) * t / float(scale_timesteps)
+
+
+class TD3Learner(object):
+    """The networks and one update of TD3 / DDPG on minibatches the caller supplies (``TD3Trainer`` feeds it from its replay ring):
+    actor / critics as ``DeviceAMLP`` with RLlib's ddpg_tf_model shapes, their targets, and ``update`` = rl4rs_td3_update on a single
+    process (``one_call``) or the same sequence as per-phase calls with the data-parallel all-reduce in front of the one Adam launch.
+    ``params``: optional dict name -> DeviceAMLP parameter dict for actor, actor_targ, q1, q1_targ (and q2, q2_targ), replacing
+    ``init_ddpg_params(seed=init_seed ...)`` and the target = online copy (tests)."""
+
+    def __init__(self, obs_dim, act_dim, batch_size, twin_q=True, smooth_target_policy=True, target_noise=0.2, target_noise_clip=0.5,
+                 tau=5e-3, l2_reg=0.0, gamma=1.0, actor_lr=1e-3, critic_lr=1e-3, use_huber=False, huber_threshold=1.0,
+                 actor_hiddens=(400, 300), critic_hiddens=(400, 300), init_seed=0, max_act_rows=0, params=None, device=None):
+        from .offline_rl import init_ddpg_params
+        if len(actor_hiddens) != 2 or len(critic_hiddens) != 2:
+            raise ValueError('TD3Learner: actor_hiddens / critic_hiddens are two layers each')
+        self.OD, self.E, self.M = int(obs_dim), int(act_dim), int(batch_size)
+        self.twin_q, self.smooth = bool(twin_q), bool(smooth_target_policy)
+        self.target_noise, self.target_noise_clip = float(target_noise), float(target_noise_clip)
+        self.tau, self.l2_reg, self.gamma = float(tau), float(l2_reg), float(gamma)
+        self.actor_lr, self.critic_lr = float(actor_lr), float(critic_lr)
+        self.use_huber, self.huber_threshold = bool(use_huber), float(huber_threshold)
+        OD, E, M = self.OD, self.E, self.M
+        ah, ch = [int(x) for x in actor_hiddens], [int(x) for x in critic_hiddens]
+        params = params or {}
+
+        def actor(name, grad_rows):
+            prm = params.get(name) or init_ddpg_params(OD, 0, E, ah[0], ah[1], seed=init_seed)
+            return D.DeviceAMLP(OD, 0, E, prm, hidden1=ah[0], hidden2=ah[1], head_act='tanh', max_rows=max(M, int(max_act_rows)),
+                                max_grad_rows=grad_rows, device=device)
+
+        def critic(name, k, grad_rows):
+            prm = params.get(name) or init_ddpg_params(OD, E, 1, ch[0], ch[1], seed=init_seed + 1 + k)
+            return D.DeviceAMLP(OD, E, 1, prm, hidden1=ch[0], hidden2=ch[1], max_rows=M, max_grad_rows=grad_rows, device=device)
+
+        self.actor, self.actor_targ = actor('actor', M), actor('actor_targ', 0)
+        self.q1, self.q1_targ = critic('q1', 0, M), critic('q1_targ', 0, 0)
+        self.q2, self.q2_targ = (critic('q2', 1, M), critic('q2_targ', 1, 0)) if self.twin_q else (None, None)
+        self.critics = [self.q1, self.q2] if self.twin_q else [self.q1]
+        self.critic_targs = [self.q1_targ, self.q2_targ] if self.twin_q else [self.q1_targ]
+        self.named = [('actor', self.actor), ('actor_targ', self.actor_targ), ('q1', self.q1), ('q1_targ', self.q1_targ)]
+        if self.twin_q:
+            self.named += [('q2', self.q2), ('q2_targ', self.q2_targ)]
+        dev = self.device = self.actor.device
+        self.td = torch.empty(M, dtype=torch.float32, device=dev)
+        self.metrics = torch.zeros(6, dtype=torch.float32, device=dev)
+        self._ws = torch.empty(int(self.actor.lib.rl4rs_td3_workspace_floats(M, E)), dtype=torch.float32, device=dev)
+        self._minus_inv_m = torch.full((M, 1), float(np.float32(-1.0) / np.float32(M)), dtype=torch.float32, device=dev)
+        self.one_call = True             # update() as one library call on a single rank (False: the per-phase calls; tests compare the two)
+
+    def sync_replicas(self, src=0):
+        """Data parallel: every rank's online parameters become those of rank ``src`` (the Adam state is still zero)."""
+        for net in [self.actor] + self.critics:
+            p = net.flat_params()
+            rdist.broadcast_(p, src)
+            net.set_flat_params(p)
+
+    def sync_targets(self):
+        self.actor_targ.copy_from(self.actor)
+        for t, s in zip(self.critic_targs, self.critics):
+            t.copy_from(s)
+
+    def flat_params(self):
+        """dict name -> flat float32 parameters of every network (actor, actor_targ, q1, q1_targ and, with twin_q, q2, q2_targ)."""
+        return dict((name, net.flat_params()) for name, net in self.named)
+
+    def close(self):
+        for _, net in self.named:
+            net.close()
+
+    def _update_one_call(self, b, noise, weights, do_actor):
+        from . import _lib
+        import ctypes as C
+        h = lambda net: (net.h.value if net is not None else None)
+        p = lambda t: (t.data_ptr() if t is not None else None)
+        st = _lib.Td3Step(h(self.actor), h(self.actor_targ), h(self.q1), h(self.q2), h(self.q1_targ), h(self.q2_targ), self.M, self.E,
+                          self.gamma, self.tau, self.actor_lr, self.critic_lr, self.target_noise, self.target_noise_clip, self.l2_reg,
+                          self.huber_threshold, 1 if self.smooth else 0, 1 if self.use_huber else 0, 1 if do_actor else 0, 0,
+                          p(b['obs']), p(b['action']), p(b['reward']), p(b['done']), p(b['next_obs']), p(weights), p(noise), p(self._ws),
+                          p(self.td), p(self.metrics))
+        _lib.check(self.actor.lib.rl4rs_td3_update(C.byref(st), D._stream()))
+
+    def _update_phases(self, b, noise, weights, do_actor):
+        """The sequence of rl4rs_td3_update as per-phase calls, with the all-reduce of the data-parallel learner in front of Adam."""
+        from .offline_rl import _allreduce_group
+        obs, act, nxt = b['obs'], b['action'], b['next_obs']
+        a_next = self.actor_targ.forward(nxt)
+        if self.smooth:
+            D.td3_smooth_action(a_next, noise, self.target_noise, self.target_noise_clip, out=a_next)
+        qn = D.amlp_forward_multi(self.critic_targs, nxt, a_next)
+        qv = D.amlp_forward_multi(self.critics, obs, act)
+        twin = self.twin_q
+        r = D.td3_critic_loss(qv[0], qv[1] if twin else None, qn[0], qn[1] if twin else None, b['reward'], b['done'], weights=weights,
+                              gamma=self.gamma, use_huber=self.use_huber, huber_threshold=self.huber_threshold, td_out=self.td,
+                              stats_out=self.metrics[:4])
+        D.amlp_backward_multi(self.critics, obs, act, [r['dq1'], r['dq2']] if twin else [r['dq1']])
+        for q in self.critics:
+            D.amlp_add_l2(q, self.l2_reg)
+        if do_actor:
+            a_pi = self.actor.forward(obs)
+            q_pi = self.q1.forward(obs, a_pi)
+            da = self.q1.backward(obs, a_pi, self._minus_inv_m, want_dact=True, want_param_grad=False)
+            self.actor.backward(obs, None, D.tanh_head_grad(a_pi, da))
+            D.amlp_add_l2(self.actor, self.l2_reg)
+            self.metrics[4] = -q_pi.sum()
+        _allreduce_group(self.critics + ([self.actor] if do_actor else []))
+        D.amlp_adam_multi(self.critics + [self.actor], [self.critic_lr] * len(self.critics) + [self.actor_lr],
+                          targets=self.critic_targs + [self.actor_targ], tau=self.tau, step=[True] * len(self.critics) + [do_actor],
+                          eps=1e-7)
+
+    def update(self, batch, noise=None, weights=None, do_actor=True):
+        """One update on ``batch`` (dict obs, action, reward, done int32, next_obs: float32 device tensors of ``batch_size`` rows),
+        ``noise`` [M, E] N(0, 1) for the target smoothing, ``weights`` [M] or None.  -> the metrics buffer float[6] = sums of
+        {w * error, q1, y, |td1|}, -sum q1(s, pi(s)) of the last actor step, spare; ``self.td`` holds the first critic's TD errors."""
+        M, E = self.M, self.E
+        for k, shape, dt in (('obs', (M, self.OD), torch.float32), ('next_obs', (M, self.OD), torch.float32), ('action', (M, E), torch.float32),
+                             ('reward', (M,), torch.float32), ('done', (M,), torch.int32)):
+            t = batch[k]
+            assert t.is_cuda and t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous(), (k, t.dtype, tuple(t.shape))
+        if self.smooth:
+            assert noise is not None and noise.is_cuda and noise.dtype == torch.float32 and tuple(noise.shape) == (M, E) and noise.is_contiguous()
+        if weights is not None:
+            assert weights.is_cuda and weights.dtype == torch.float32 and tuple(weights.shape) == (M,) and weights.is_contiguous()
+        if self.one_call and not rdist.collectives_active():
+            self._update_one_call(batch, noise, weights, do_actor)
+        else:
+            self._update_phases(batch, noise, weights, do_actor)
+        return self.metrics
+
+
+class TD3Trainer(_DeferredStats):
+    """Online TD3 / DDPG over the zero-copy continuous-action env (``support_conti_env``, plain 256-wide observations): the third
+    learner family of script/modelfree_train.py (:46-48, :79-105; modelfree_trainer.py:25-28).  The action is the 32-d vector in
+    Box(-1, 1) that the env resolves with its masked K-NN.  Defaults are the reference's merged RLlib 1.5.1 configuration
+    (``TD3_PRESETS`` by ``algo``; common: gamma 1, actor_lr = critic_lr = 1e-3, use_huber False, n_step 1, train_batch_size
+    min(B * T, 1024), OU theta 0.15 / sigma 0.2 / ou_base_scale 0.1, scale 1.0 -> 0.02 over 10 000 sampled steps, Adam eps 1e-7).
+    The reference driver's own DDPG branch raises (an ``if`` in front of a separate if / elif / else chain); ``algo='DDPG'`` here is
+    TD3 with twin_q, policy_delay and smooth_target_policy off.  RLlib parity is unpinned (ray is absent), as for A2C / PPO / DQN.
+
+    One rollout is actor forward -> OU exploration -> env.step for T steps; then the push; then ``updates_per_rollout`` updates once
+    ``learning_starts`` sampled steps are reached, ``do_actor = num_updates % policy_delay == 0``.  All three targets move on every
+    update (target_network_update_freq 0).  Networks and update are ``TD3Learner``'s (``self.learner``): ONE library call
+    (rl4rs_td3_update) on a single process; with ``torch.distributed`` initialised the same sequence as per-phase calls, the
+    gradients of the critics and the actor mean-all-reduced together before the one Adam launch.
+
+    Deviations from RLlib: the replay ring holds whole rollouts (max(1, buffer_size // (B * T)) of them); the OU state is one [E]
+    vector PER ENV (RLlib: one variable shaped like a single action), never reset between episodes."""
+
+    def __init__(self, env, algo='TD3', actor_hiddens=(400, 300), critic_hiddens=(400, 300), seed=0, init_seed=0, actor_lr=1e-3,
+                 critic_lr=1e-3, gamma=1.0, twin_q=None, policy_delay=None, smooth_target_policy=None, target_noise=None,
+                 target_noise_clip=None, tau=None, l2_reg=None, use_huber=False, huber_threshold=1.0, n_step=1, buffer_size=None,
+                 prioritized_replay=None, prioritized_replay_alpha=0.6, prioritized_replay_beta=0.4, learning_starts=None,
+                 random_timesteps=None, train_batch_size=None, ou_theta=0.15, ou_sigma=0.2, ou_base_scale=0.1, initial_scale=1.0,
+                 final_scale=0.02, scale_timesteps=10000, updates_per_rollout=1, keep_last_batch=False):
+        if algo not in TD3_PRESETS:
+            raise ValueError("TD3Trainer: algo must be 'TD3' or 'DDPG'; got %r" % (algo,))
+        if n_step != 1:
+            raise ValueError("TD3Trainer implements n_step = 1 (the reference's setting); got %r" % (n_step,))
+        cfg = env.config
+        assert cfg.get('return_tensors', False) and cfg.get('support_conti_env', False), \
+            "TD3Trainer needs the zero-copy continuous-action env (config['return_tensors'] and ['support_conti_env'] = True)"
+        pre = dict(TD3_PRESETS[algo])
+        given = dict(twin_q=twin_q, policy_delay=policy_delay, smooth_target_policy=smooth_target_policy, target_noise=target_noise,
+                     target_noise_clip=target_noise_clip, tau=tau, l2_reg=l2_reg, buffer_size=buffer_size,
+                     prioritized_replay=prioritized_replay, learning_starts=learning_starts, random_timesteps=random_timesteps)
+        pre.update((k, v) for k, v in given.items() if v is not None)
+        self.algo, self.env = algo, env
+        self.policy_delay, self.buffer_size = int(pre['policy_delay']), int(pre['buffer_size'])
+        self.prioritized, self.beta = bool(pre['prioritized_replay']), float(prioritized_replay_beta)
+        self.learning_starts, self.random_timesteps = int(pre['learning_starts']), int(pre['random_timesteps'])
+        self.ou_theta, self.ou_sigma, self.ou_base_scale = float(ou_theta), float(ou_sigma), float(ou_base_scale)
+        self.initial_scale, self.final_scale, self.scale_timesteps = float(initial_scale), float(final_scale), int(scale_timesteps)
+        self.updates_per_rollout = int(updates_per_rollout)
+        self.B, self.T, self.E = cfg['batch_size'], cfg['max_steps'], cfg['action_emb_size']
+        self.M = int(train_batch_size) if train_batch_size is not None else min(self.B * self.T, 1024)
+        self.seed = seed
+        self.keep_last_batch, self.last_batch = keep_last_batch, None
+        self._pending = []
+        space = env.observation_space
+        space = space.spaces['obs'] if hasattr(space, 'spaces') else space
+        self.OD = int(space.shape[0])
+        OD, E, M = self.OD, self.E, self.M
+        self.learner = TD3Learner(OD, E, M, twin_q=pre['twin_q'], smooth_target_policy=pre['smooth_target_policy'],
+                                  target_noise=pre['target_noise'], target_noise_clip=pre['target_noise_clip'], tau=pre['tau'],
+                                  l2_reg=pre['l2_reg'], gamma=gamma, actor_lr=actor_lr, critic_lr=critic_lr, use_huber=use_huber,
+                                  huber_threshold=huber_threshold, actor_hiddens=actor_hiddens, critic_hiddens=critic_hiddens,
+                                  init_seed=init_seed, max_act_rows=self.B)
+        self.actor = self.learner.actor
+        dev = self.device = self.actor.device
+        self.replay = D.DeviceContiReplay(OD, E, self.T, self.B, buffer_size=self.buffer_size, alpha=prioritized_replay_alpha, device=dev)
+        N = self.B * self.T
+        self.buf = dict(obs=torch.empty((N, OD), dtype=torch.float32, device=dev), act=torch.empty((N, E), dtype=torch.float32, device=dev),
+                        rew=torch.empty(N, dtype=torch.float64, device=dev))
+        self._det = torch.empty((self.B, E), dtype=torch.float32, device=dev)
+        self.ou_state = torch.zeros((self.B, E), dtype=torch.float32, device=dev)
+        self._batch = self.replay.new_batch(M)
+        self._gen = torch.Generator(device=dev)
+        self._gen.manual_seed(int(seed) * 7919 + 17)
+        self.iteration = 0
+        self._rollouts = 0
+        self.timesteps = 0                  # sampled env steps (RLlib's num_steps_sampled)
+        self.num_updates = 0
+        if rdist.collectives_active():
+            self.learner.sync_replicas(0)                   # replicas start identical (shared init_seed; the Adam state is zero)
+        self.learner.sync_targets()
+
+    def params(self):
+        """dict name -> flat float32 parameters of every network (``TD3Learner.flat_params``)."""
+        self._settle()
+        return self.learner.flat_params()
+
+    def close(self):
+        try:
+            self._settle()
+        finally:
+            self.learner.close()
+            self.replay.close()
+
+    def scale_at(self, timestep):
+        """ou_base_scale x the annealed scale at a sampled timestep: the ``scale`` of rl4rs_explore_ou, computed on the host."""
+        return self.ou_base_scale * ou_scale(timestep, self.random_timesteps, self.initial_scale, self.final_scale, self.scale_timesteps)
+
+    def _episode(self, explore, step0, reset_file=False):
+        """One complete-episode rollout into the rollout buffers -> mean episode reward (device scalar)."""
+        B, T = self.B, self.T
+        b = self.buf
+        obs = self.env.reset(reset_file=True) if reset_file else self.env.reset()
+        for t in range(T):
+            obs_t = obs['obs'] if isinstance(obs, dict) else obs
+            sl = slice(t * B, (t + 1) * B)
+            b['obs'][sl] = obs_t
+            a = b['act'][sl]
+            if explore:
+                ts = self.timesteps + t * B
+                random_phase = ts < self.random_timesteps
+                if not random_phase:
+                    self.actor.forward(b['obs'][sl], out=self._det)
+                D.explore_ou(self._det, self.ou_state, self.ou_theta, self.ou_sigma, self.scale_at(ts), seed=self.seed, step=step0 + t,
+                             random_phase=random_phase, out=a)
+            else:
+                self.actor.forward(b['obs'][sl], out=a)
+            obs, reward, done, info = self.env.step(a)
+            b['rew'][sl] = reward
+        return b['rew'].view(T, B).sum(dim=0).mean()
+
+    def update(self):
+        """One learner step: sample -> ``TD3Learner.update`` -> priorities.  -> the learner's metrics buffer."""
+        M, L = self.M, self.learner
+        # (the replay draws share the counter RNG of the exploration noise: a seed of their own keeps them apart)
+        b = self.replay.sample(M, prioritized=self.prioritized, beta=self.beta, seed=self.seed + 0x5bd1e995, step=self.num_updates,
+                               out=self._batch)
+        noise = torch.randn((M, self.E), generator=self._gen, device=self.device, dtype=torch.float32) if L.smooth else None
+        do_actor = self.num_updates % self.policy_delay == 0
+        if self.keep_last_batch:
+            self.last_batch = dict((k, v.clone()) for k, v in b.items() if v is not None)
+            self.last_batch.update(noise=noise.clone() if noise is not None else None, do_actor=do_actor)
+        L.update(b, noise=noise, weights=b['weight'] if self.prioritized else None, do_actor=do_actor)
+        if self.prioritized:
+            self.replay.update_priorities(b['idx'], L.td)
+        if self.keep_last_batch:
+            self.last_batch['td'] = L.td.clone()
+        self.num_updates += 1
+        return L.metrics
+
+    def train_iteration(self):
+        """One rollout, one push, ``updates_per_rollout`` updates once ``learning_starts`` sampled steps are reached.  Returns a
+        ``LazyStats`` mapping (episode_reward_mean; critic_loss, mean_q, mean_td_abs of the last update and actor_loss of the last
+        actor step, without the L2 terms, 0 before the first; buffer_rows, num_updates, iteration); nothing here waits for the GPU."""
+        mean_reward = self._episode(True, self._rollouts * self.T)
+        self._rollouts += 1
+        self._settle()
+        b = self.buf
+        self.replay.push(b['obs'], b['act'], b['rew'])
+        self.timesteps += self.B * self.T
+        self.iteration += 1
+        if self.timesteps >= self.learning_starts:
+            for _ in range(self.updates_per_rollout):
+                self.update()
+        extra = dict(rows=self.M, buffer_rows=self.replay.rows, num_updates=self.num_updates)
+        return LazyStats(self, self._submit(mean_reward, self.learner.metrics, 1, extra))
+
+    def _status_word(self, dev):
+        return torch.zeros(1, dtype=torch.float64, device=dev)      # (the amlp networks run no persistent pass)
+
+    def _settle(self):
+        while self._pending:
+            tok = self._pending.pop(0)
+            tok['ev'].synchronize()
+            v = tok['pin'].numpy().copy()
+            if v[-1] >= 1000.0:
+                raise RuntimeError(rdist.ROW_OVERFLOW_MESSAGE)
+            s, n = v[1:-1], float(tok['rows'])
+            tok['values'] = {'episode_reward_mean': float(v[0]), 'critic_loss': float(s[0]) / n, 'actor_loss': float(s[4]) / n,
+                             'mean_q': float(s[1]) / n, 'mean_td_abs': float(s[3]) / n, 'buffer_rows': tok['buffer_rows'],
+                             'num_updates': tok['num_updates'], 'iteration': tok['iteration']}
+
+    def evaluate(self, episodes=None, seed=0):
+        """Mean episode reward of deterministic episodes (the actor's own action, no noise): ceil(episodes / B) batches from the start
+        of the record file with the env's record sampling seeded by ``seed``, so two calls on the same parameters give the same
+        number.  Leaves the global numpy RNG as it found it; the env's record cursor restarts."""
+        self._settle()
+        n = 1 if episodes is None else max(1, int(math.ceil(float(episodes) / self.B)))
+        state = np.random.get_state()
+        try:
+            np.random.seed(seed)
+            total = torch.zeros((), dtype=torch.float64, device=self.device)
+            for k in range(n):
+                total += self._episode(False, 0, reset_file=k == 0)
         finally:
             np.random.set_state(state)
         return float(total.item()) / n
