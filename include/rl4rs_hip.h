@@ -247,7 +247,11 @@ typedef struct rl4rs_dien_cfg {
  *                   category branch per row (k_cat_attn2) instead of one workgroup per group that gathers the category rows the
  *                   group shares once (k_cat_attn2g; a group that shares nothing takes the per-row body inside it) (=)
  *   NO_GEMM_GROUP   the chained dense tower and the q-side term of the DIN scores (independent GEMMs, half-chip grids at observation
- *                   size) as two launches instead of one grid that holds both problems' workgroups (k_gemm_h16_pair) (=) */
+ *                   size) as two launches instead of one grid that holds both problems' workgroups (k_gemm_h16_pair) (=)
+ *   NO_ROW_DEDUP    k_din_x and k_augru_x over every row of a forward instead of one representative per set of bit-identical row
+ *                   groups (equal cache slots, category ids and dense bit patterns: k_row_dedup finds them on the device at the top
+ *                   of every forward, k_row_expand copies the representative's AUGRU states and attention scores to its duplicates
+ *                   in front of the head GEMM).  Active only where k_din_x and k_augru_x are the selected kernels (=) */
 enum {
     RL4RS_DIEN_OPT_AUGRU_H16 = 1 << 0,
     RL4RS_DIEN_OPT_AUGRU_ROWS32 = 1 << 1,
@@ -267,7 +271,9 @@ enum {
                                                   taking them from the handle's table of pad states (bit-identical either way) */
     RL4RS_DIEN_OPT_NO_GEMM_GROUP = 1 << 15,    /* fp16x2 mode: the dense tower and the q-side term of the DIN scores as two launches
                                                   instead of one grid that holds both problems' workgroups (bit-identical either way) */
-    RL4RS_DIEN_OPT_ALL = (1 << 16) - 1
+    RL4RS_DIEN_OPT_NO_ROW_DEDUP = 1 << 16,     /* fp16x2 mode: k_din_x / k_augru_x score duplicate row groups of a forward too
+                                                  (bit-identical either way) */
+    RL4RS_DIEN_OPT_ALL = (1 << 17) - 1
 };
 
 /* Every mode accumulates in fp32 and meets the fp32 parity bar against the fp64 oracle (same measured error):
@@ -348,7 +354,11 @@ enum {
                                      Flatten(category_emb) part lives in the head tables */
     RL4RS_DIEN_SCORES = 1,        /* float32 [seq_num, max_rows, maxlen] attention scores */
     RL4RS_DIEN_QUERY = 2,         /* float32 [max_rows, E] */
-    RL4RS_DIEN_H1 = 3             /* float32 [seq_num, max_slots, maxlen, E] first-GRU states */
+    RL4RS_DIEN_H1 = 3,            /* float32 [seq_num, max_slots, maxlen, E] first-GRU states */
+    RL4RS_DIEN_N_ACTIVE = 4,      /* int32 [1] row groups k_din_x / k_augru_x scored in the last forward (row dedup; an error
+                                     on a handle where it is off) */
+    RL4RS_DIEN_ROW_REP = 5        /* int32 [max_rows] representative group of every row group of the last forward, first
+                                     R / group entries (rep[g] == g: scored itself) */
 };
 int rl4rs_dien_buffer(rl4rs_dien* net, int which, void** dev_ptr, int64_t* n_bytes);
 

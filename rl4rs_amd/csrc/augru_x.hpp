@@ -153,6 +153,11 @@ __global__ __launch_bounds__(512) void k_augru_x(RecurArgs a) {
     const int half = lane >> 5, li = lane & 31;
     const int row0 = blockIdx.x * 32 * MT;
     const int sq = blockIdx.y;
+    // row dedup (row_dedup.hpp): the launch works on the first n_active entries of a.order only - the grid is sized for a.n_rows
+    // on the host, a workgroup behind the bound leaves here
+    // (read again in the epilogue rather than kept across the recurrence: the 64-row form has no register to spare)
+    int n_rows = a.n_active ? min(a.n_rows, a.n_active[0] * a.group) : a.n_rows;
+    if (row0 >= n_rows) return;
     const int L = a.L;
     const int xld4 = (int)a.xld * 4;
     char* stage = smem + MT * TILE + wave * STG;                   // this wave's projection staging: gate g at + g * STG / 3
@@ -171,7 +176,7 @@ __global__ __launch_bounds__(512) void k_augru_x(RecurArgs a) {
     // processing order: tile position p works on batch row phys(p) - with a row order (rl4rs_dien_set_row_order: env groups sorted
     // by their history's cache slot) the rows of a tile, and of tiles that run at the same time, share projection rows in L2
     auto phys = [&](int p) {
-        p = min(p, a.n_rows - 1);
+        p = min(p, n_rows - 1);
         return a.order ? a.order[p / a.group] * a.group + p % a.group : p;
     };
     int dma_off[4];
@@ -507,11 +512,12 @@ __global__ __launch_bounds__(512) void k_augru_x(RecurArgs a) {
         any_bad |= bad;
     }
     __syncthreads();
+    if (a.n_active) n_rows = min(a.n_rows, *const_cast<const volatile int32_t*>(a.n_active) * a.group);
 #pragma unroll
     for (int m = 0; m < MT; ++m) {
         const int row = phys(row0 + m * 32 + li);
         const bool poison = s_bad[m * 32 + li] != 0u;
-        if (row0 + m * 32 + li < a.n_rows) {
+        if (row0 + m * 32 + li < n_rows) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 float4 v = make_float4(h_own[m][4 * q], h_own[m][4 * q + 1], h_own[m][4 * q + 2], h_own[m][4 * q + 3]);

@@ -1409,6 +1409,7 @@ struct DinArgs {
     const float* w2[4]; const float* b2[4]; const float* w3[4]; const float* b3[4];
     float* scores; int64_t scores_stride;           // [n_seq][scores_stride] rows of L
     const int32_t* order;        // processing order of the row groups (NULL = identity): rl4rs_dien_set_row_order
+    const int32_t* n_active;     // k_din_x: device int, only the first n_active[0] entries of `order` are scored (row_dedup.hpp; NULL = all)
     unsigned long long* trace;   // -DRL4RS_DINX_TRACE timing experiments only
     // k_din_x: leading zero ids of the sequence in every cache slot and the slot of the all-zero sequence (RecurArgs::lead / pad_slot):
     // the steps of a row's front padding read the pad slot's states and projections - the same bytes, shared by all rows.  NULL = off
@@ -1658,6 +1659,7 @@ __global__ __launch_bounds__(256) void k_din_scores(DinArgs a) {
 #define RL4RS_DINX_WPE 4        // waves per SIMD the register allocation aims at
 #endif
 #include "din_x.hpp"
+#include "row_dedup.hpp"
 namespace rl4rs {
 
 // softmax(obs @ out_w + out_b)[:, 1]  (dien.py:36, slate.py:298).  One wave per row.
@@ -1710,10 +1712,10 @@ __global__ __launch_bounds__(256) void k_head_finish(float* __restrict__ obs, in
 using namespace rl4rs;
 
 namespace {
-enum { KID_CAT = 0, KID_DENSE, KID_DIN, KID_AUGRU, KID_HEAD, KID_PROB, KID_GRU1, KID_PROJ, KID_COUNT };
+enum { KID_CAT = 0, KID_DENSE, KID_DIN, KID_AUGRU, KID_HEAD, KID_PROB, KID_GRU1, KID_PROJ, KID_DEDUP, KID_COUNT };
 const char* kKernelNames[KID_COUNT] = {"k_cat_attn", "k_gemm_f32(dense tower)", "k_din_scores",
                                        "augru", "k_gemm_f32(simulator_obs)", "k_head_prob",
-                                       "k_recur<128,gru>", "k_gemm_f32(seq projections)"};
+                                       "k_recur<128,gru>", "k_gemm_f32(seq projections)", "k_row_dedup"};
 struct EvPair { int id; hipEvent_t a, b; };
 }  // namespace
 
@@ -1764,6 +1766,11 @@ struct rl4rs_dien {
     bool din16;            // fp16x2 mode: the DIN layer-1 operands (q*h1 bounded by the embedding table, W1d) fit fp16 too
     int* range_flag;       // device int: a k_augru_h16 state left the fp16 range (sticky until read)
     const int32_t* row_order; int row_order_n;    // processing order of the row groups of a forward (caller-owned), or NULL
+    // row dedup (row_dedup.hpp): k_din_x and k_augru_x score one representative per set of bit-identical row groups
+    bool row_dedup;        // on wherever k_din_x and k_augru_x are the selected kernels (RL4RS_DIEN_OPT_NO_ROW_DEDUP: off)
+    int32_t* dd_rep;       // [max_rows] representative of every row group of the last forward
+    int32_t* dd_active;    // [max_rows] the representatives in processing order
+    int32_t* dd_nact;      // [0] their number, [1] k_row_dedup's workgroup ticket
     float* augru_wg[4];    // packed [2*NH2/32][NH2/8][64][4]
     float* augru_wc[4];
     // caches
@@ -2150,6 +2157,17 @@ int rl4rs_dien_create(const rl4rs_dien_cfg* c, const rl4rs_dien_weights* w, void
     AL(qa, (size_t)S * c->max_rows * ATT_H1);
     AL(scores, (size_t)S * c->max_rows * L);
     AL(obs_tmp, (size_t)c->max_rows * OBS_DIM);
+    // row dedup: only where both kernels that read the active list are the selected ones
+    n->row_dedup = !(opts & RL4RS_DIEN_OPT_NO_ROW_DEDUP) && n->fp16x2 && n->augru_x && n->din16 && n->h1f[0] != nullptr;
+    n->dd_rep = n->dd_active = n->dd_nact = nullptr;
+    if (n->row_dedup) {
+        float* f = nullptr;
+        if ((rc = alloc_f(n, &f, (size_t)2 * c->max_rows + 2)) != RL4RS_OK) return rc;
+        n->dd_rep = reinterpret_cast<int32_t*>(f);
+        n->dd_active = n->dd_rep + c->max_rows;
+        n->dd_nact = n->dd_active + c->max_rows;
+        RL4RS_HIP_TRY(hipMemsetAsync(f, 0, ((size_t)2 * c->max_rows + 2) * 4, st));
+    }
     n->tsum = nullptr;
     if (n->ptab && Cn <= 24 && !(opts & RL4RS_DIEN_OPT_NO_HEAD_FUSED)) AL(tsum, (size_t)c->max_rows * OBS_DIM);
     // first GRU: the states after 1 .. L leading zero ids, per sequence input (RecurArgs::pad) - the kernel itself on ONE all-zero row
@@ -2316,6 +2334,20 @@ int rl4rs_dien_forward(rl4rs_dien* n, int32_t R, int32_t group, const float* den
         RL4RS_HIP_TRY(hipEventRecord(n->ev_join, n->side_stream));
         forked = true;
     }
+    // duplicate row groups of this forward (row_dedup.hpp): k_din_x and k_augru_x then work on the representatives only
+    const int32_t* order_in = (n->row_order && n->row_order_n == ngroups) ? n->row_order : nullptr;
+    const bool dedup = n->row_dedup;
+    if (dedup) {
+        Prof p(n, KID_DEDUP, st);
+        RowDedupArgs a;
+        memset(&a, 0, sizeof(a));
+        a.n_groups = ngroups; a.group = group; a.Cn = Cn; a.Dn = n->Dn; a.S = S;
+        a.slots = slots; a.slots_stride = ngroups; a.cat = cat; a.dense = dense; a.order = order_in;
+        a.rep = n->dd_rep; a.active = n->dd_active; a.n_active = n->dd_nact;
+        constexpr int per_wg = ROW_DEDUP_THREADS / 64;
+        hipLaunchKernelGGL(k_row_dedup, dim3((ngroups + per_wg - 1) / per_wg), dim3(ROW_DEDUP_THREADS), 0, st, a);
+        RL4RS_LAUNCH_CHECK();
+    }
     {
         Prof p(n, KID_CAT, st);
         if (n->cat_v2 && n->cat_group && E == 128 && Cn >= 11 && Cn <= 24 && (group == 8 || group == 9)) {
@@ -2375,7 +2407,8 @@ int rl4rs_dien_forward(rl4rs_dien* n, int32_t R, int32_t group, const float* den
             a.w2[s] = n->att_w2[s]; a.b2[s] = n->att_b2[s]; a.w3[s] = n->att_w3[s]; a.b3[s] = n->att_b3[s];
         }
         a.scores = n->scores; a.scores_stride = (int64_t)n->c.max_rows * L;
-        a.order = (n->row_order && n->row_order_n == ngroups) ? n->row_order : nullptr;
+        a.order = order_in;
+        if (dedup && h16 && n->h1f[0]) { a.order = n->dd_active; a.n_active = n->dd_nact; }
         for (int s = 0; s < S; ++s) a.lead[s] = n->lead[s];
         a.pad_slot = n->c.max_slots;
 #ifdef RL4RS_DINX_TRACE      // timing experiments only (tools/dinx_trace.py)
@@ -2431,7 +2464,8 @@ int rl4rs_dien_forward(rl4rs_dien* n, int32_t R, int32_t group, const float* den
                     a.k_u[s][t] = -1.4426950408889634f / n->augru_s[s][1][t];
                     a.k_c[s][t] = 2.8853900817779268f / n->augru_s[s][2][t];
                 }
-            a.order = (n->augru_x && n->row_order && n->row_order_n == ngroups) ? n->row_order : nullptr;
+            a.order = n->augru_x ? order_in : nullptr;
+            if (dedup) { a.order = n->dd_active; a.n_active = n->dd_nact; }
             a.steps = 0;
 #if defined(RL4RS_H16_TRACE) || defined(RL4RS_X_TRACE)
             static unsigned long long* trace_buf = nullptr;
@@ -2469,6 +2503,16 @@ int rl4rs_dien_forward(rl4rs_dien* n, int32_t R, int32_t group, const float* den
         hipLaunchKernelGGL((k_recur<256, true, AUGRU_U, 0>), grid, block, smem, st, a);
 #endif
         ;
+        RL4RS_LAUNCH_CHECK();
+    }
+    if (dedup) {     // the duplicates' AUGRU states and attention scores, in front of the head GEMM
+        Prof p(n, KID_DEDUP, st);
+        RowExpandArgs a;
+        memset(&a, 0, sizeof(a));
+        a.R = R; a.group = group; a.n_groups = ngroups; a.S = S; a.L = L; a.ncol = S * NH2;
+        a.rep = n->dd_rep; a.n_active = n->dd_nact;
+        a.allf = n->allf; a.ld = F; a.scores = n->scores; a.scores_stride = (int64_t)n->c.max_rows * L;
+        hipLaunchKernelGGL(k_row_expand, dim3((R + 3) / 4), dim3(256), 0, st, a);
         RL4RS_LAUNCH_CHECK();
     }
     float* obs_out = obs ? obs : n->obs_tmp;
@@ -2520,6 +2564,12 @@ int rl4rs_dien_buffer(rl4rs_dien* n, int which, void** p, int64_t* bytes) {
         case RL4RS_DIEN_SCORES: ptr = n->scores; b = (int64_t)n->S * n->c.max_rows * n->L * 4; break;
         case RL4RS_DIEN_QUERY: ptr = n->q; b = (int64_t)n->c.max_rows * n->E * 4; break;
         case RL4RS_DIEN_H1: ptr = n->h1[0]; b = (int64_t)n->c.max_slots * n->L * n->E * 4; break;
+        case RL4RS_DIEN_N_ACTIVE:
+        case RL4RS_DIEN_ROW_REP:
+            if (!n->row_dedup) { set_error("dien_buffer: row dedup is off on this handle"); return RL4RS_EINVAL; }
+            if (which == RL4RS_DIEN_N_ACTIVE) { ptr = n->dd_nact; b = 4; }
+            else { ptr = n->dd_rep; b = (int64_t)n->c.max_rows * 4; }
+            break;
         default: set_error("dien_buffer: unknown buffer id %d", which); return RL4RS_EINVAL;
     }
     *p = ptr;
@@ -2612,6 +2662,7 @@ int rl4rs_dien_kernel_label(rl4rs_dien* n, int which, char* buf, int32_t cap) {
             s = n->gru16 ? "k_gru_h16" : "k_recur<128,gru>";
             if (n->h1f[0]) s += " + k_h1_frag";
             break;
+        case KID_DEDUP: s = n->row_dedup ? "k_row_dedup + k_row_expand" : "k_row_dedup (off)"; break;
         case KID_PROJ: s = n->gemm16 ? "k_gemm_h16 / k_gemm_h16_wres(seq projections)" : "k_gemm_pk(seq projections)"; break;
     }
     snprintf(buf, (size_t)cap, "%s", s.c_str());

@@ -56,7 +56,10 @@ __global__ __launch_bounds__(512, RL4RS_DINX_WPE) void k_din_x(DinArgs a, int ro
     constexpr int E = 128, KB = 8, NW = 8;
     const int L = a.L;
     const int sq = blockIdx.y;
-    char* s_w1 = smem;                                                  // [(m*8 + kb)*2 + plane][lane][8 halfs]: 32 KB
+    // row dedup (row_dedup.hpp): only the first n_active entries of a.order are scored; the grid is sized for a.R on the host
+    const int n_rows = a.n_active ? min(a.R, a.n_active[0] * a.group) : a.R;
+    if (blockIdx.x * rows_per_wg >= n_rows) return;
+    char* s_w1 = smem;                                                 // [(m*8 + kb)*2 + plane][lane][8 halfs]: 32 KB
     char* s_w2b = smem + 32768;                                         // [(m*2 + kb2)*2 + plane][lane][8 halfs]: 8 KB
     float* s_misc = reinterpret_cast<float*>(smem + 40960);             // b2[16] w3[16] b3 pad -> 48
     float* s_wave = s_misc + 48;                                        // per wave: q[E] + qa[64]
@@ -108,7 +111,7 @@ __global__ __launch_bounds__(512, RL4RS_DINX_WPE) void k_din_x(DinArgs a, int ro
     for (int j = wave; j < rows_per_wg; j += NW) {
         // row groups (rows that share a cache slot) in the caller's processing order, rows of a group consecutive
         const int idx = blockIdx.x * rows_per_wg + j;
-        if (idx >= a.R) break;
+        if (idx >= n_rows) break;
         const int g = idx / grp;
         const int gs = a.order ? a.order[g] : g;
         const int row = gs * grp + (idx - g * grp);

@@ -15,7 +15,7 @@ from ._lib import check
 # rl4rs_env_buffer ids (include/rl4rs_hip.h)
 BUF_PREV_ACTIONS, BUF_ACTION_MASK, BUF_SPECIAL_MASK, BUF_DENSE, BUF_CATEGORY, BUF_SEQ0, BUF_SEQ1, \
     BUF_C_DENSE, BUF_C_CATEGORY, BUF_ERROR_FLAG = range(10)
-DIEN_ALL_FEATURE, DIEN_SCORES, DIEN_QUERY, DIEN_H1 = range(4)
+DIEN_ALL_FEATURE, DIEN_SCORES, DIEN_QUERY, DIEN_H1, DIEN_N_ACTIVE, DIEN_ROW_REP = range(6)
 
 _MASK_DTYPES = {torch.uint8: 0, torch.int32: 1, torch.int64: 2, torch.float32: 3}
 
@@ -590,6 +590,10 @@ class DeviceDien(object):
         p = C.c_void_p()
         n = C.c_int64()
         check(self.lib.rl4rs_dien_buffer(self.h, which, C.byref(p), C.byref(n)))
+        if which in (DIEN_N_ACTIVE, DIEN_ROW_REP):      # int32: row dedup of the last forward (an error where it is off)
+            out = torch.empty(n.value // 4, dtype=torch.int32, device=self.device)
+            check(self.lib.rl4rs_copy_d2d(_ptr(out), p, n.value, _stream()))
+            return out
         if which == DIEN_ALL_FEATURE:
             shape = (self.max_rows, n.value // (4 * self.max_rows))      # F, or the Kh columns of the table form
         elif which == DIEN_SCORES:
