@@ -708,6 +708,76 @@ int rl4rs_policy_greedy(rl4rs_policy* pol, int32_t N, const float* obs_dev, cons
 int rl4rs_policy_adam_step_clip_by_var(rl4rs_policy* pol, const float* grad_dev, float lr, float beta1, float beta2,
                                        float eps, float var_clip, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * On-device Rainbow: script/modelfree_train.py:50-53,146-178 (algo "RAINBOW": num_atoms 8 over [v_min 0, v_max 1000] on RLlib
+ * 1.5.1's DQN defaults - dueling, double_q, n_step 3, gamma 1, no custom model, support_rllib_mask forced False).  RLlib's
+ * dqn_tf_policy / distributional_q_tf_model are restated from their published form (ray is absent: parity unpinned).
+ *
+ * Network (RLlib's default model): obs -> Dense(trunk, tanh) -> Dense(trunk, tanh); advantage stream Dense(stream_hidden, relu) ->
+ * Dense(A * atoms) with column a * atoms + j; value stream (dueling) Dense(stream_hidden, relu) -> Dense(atoms);
+ *   logits[a, j] = V[j] + Adv[a, j] - mean_a' Adv[a', j]   (dueling 0: logits = Adv)
+ *   p[a, :] = softmax_j logits[a, :],  z_j = v_min + j (v_max - v_min) / (atoms - 1),  Q[a] = sum_j z_j p[a, j]
+ * Flat fp32 layout: W1, b1, W2, b2, Wa1, ba1, Wa2, ba2 [, Wv1, bv1, Wv2, bv2], every matrix [in, out] row-major.
+ * The [rows, A * atoms] logits are never written to memory: acting and the double-Q argmax run one fused head kernel (fp32 MFMA
+ * GEMM, dueling centring through the action-mean of Wa2, softmax over atoms, sum z p, then the draw or the first maximum), and an
+ * update touches the logits of one action per row only.
+ * Two deviations from the reference: the replay ring holds whole rollouts (above), and an OPTIONAL packed action mask (NULL = the
+ * reference's unmasked behaviour) sets a disallowed action's Q to -3.4028235e38 before the draw / the maximum; the logits are not
+ * altered.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct rl4rs_distq rl4rs_distq;
+typedef struct rl4rs_distq_cfg {
+    int32_t obs_dim, action_size /* 2..512 */, atoms /* 2..64 */, trunk /* % 32 == 0 */, stream_hidden /* % 32 == 0, <= 256 */,
+        dueling /* 0 / 1 */;
+    float v_min, v_max;
+    int32_t max_rows;                     /* most rows of one act / greedy / loss_grad call */
+} rl4rs_distq_cfg;
+/* floats of the flat layout, -1 for a config rl4rs_distq_create refuses */
+int64_t rl4rs_distq_param_count(const rl4rs_distq_cfg* cfg);
+int rl4rs_distq_create(const rl4rs_distq_cfg* cfg, const float* params_host, void* stream, rl4rs_distq** out);
+int rl4rs_distq_destroy(rl4rs_distq* net);
+/* device pointers owned by the handle (any may be NULL); like rl4rs_amlp_params / _copy_params / _adam_state */
+int rl4rs_distq_params(rl4rs_distq* net, float** params_dev, float** grad_dev, int64_t* count);
+int rl4rs_distq_copy_params(rl4rs_distq* dst, const rl4rs_distq* src, void* stream);
+int rl4rs_distq_adam_state(rl4rs_distq* net, float** m_dev, float** v_dev, int64_t* step);
+int rl4rs_distq_set_adam_step(rl4rs_distq* net, int64_t step);
+/* SoftQ exploration (RLlib's default for DQN): a draw from softmax(Q / temperature) over the allowed actions by inverse CDF,
+ * action = the smallest a whose inclusive prefix sum of exp((Q - max Q) / temperature), in action order, exceeds u * total, with
+ * u = the policy net's counter RNG keyed (seed, step, row, 0).  u_out [N], q_out [N, A] (masked Q) are optional.  A row whose mask
+ * allows nothing returns action 0. */
+int rl4rs_distq_act(rl4rs_distq* net, int32_t N, const float* obs_dev, const uint32_t* mask_bits_dev, float temperature, uint32_t seed,
+                    uint32_t step, int32_t* actions_dev, float* u_out_dev, float* q_out_dev, void* stream);
+/* Greedy action (explore: False): the first maximum of the masked Q row; a row that allows nothing returns 0. */
+int rl4rs_distq_greedy(rl4rs_distq* net, int32_t N, const float* obs_dev, const uint32_t* mask_bits_dev, int32_t* actions_dev,
+                       float* q_out_dev, void* stream);
+/* Categorical (C51) loss and gradient of RLlib's QLoss with num_atoms > 1; target_params_dev: the target net, same flat layout.
+ *   a*  = first maximum of the (masked) Q(s') of the online net (double_q 1) or of the target net (double_q 0)
+ *   p'  = the target net's p(s')[a*, :]
+ *   r_tau_j = clip(R + gamma_n * z_j, v_min, v_max) for a row that bootstraps, clip(R) for every j otherwise (terminal row, or a
+ *             successor whose mask allows nothing): a select, nothing of such a row's successor - NaN included - reaches any output
+ *   b_j = (r_tau_j - v_min) / dz, l = floor(b_j), u = ceil(b_j), eq = (u - l < 0.5)
+ *   m[l] += p'_j (u - b_j + eq),  m[u] += p'_j (b_j - l)
+ *   td = -sum_i m_i log_softmax(logits(s)[a, :])_i,   loss = mean(w * td),  w = weights_dev or 1
+ * rewards_dev holds the n-step return R, dones_dev the n-step done, gamma_n = gamma ^ n_step (rl4rs_replay_sample_nstep).
+ * Outputs: grad_dev (flat layout), td_dev [N] (the new priorities), next_action_dev [N] (optional: a*, -1 on terminal rows),
+ * stats_dev float[4] (optional) = sums of {w * td, Q(s)[a], sum_i z_i m_i, td}.  N <= max_rows.  Fixed sample chunks and a fixed
+ * summation order: bit-identical from run to run. */
+int rl4rs_distq_loss_grad(rl4rs_distq* net, const float* target_params_dev, int32_t N, const float* obs_dev, const int32_t* actions_dev,
+                          const float* rewards_dev, const int32_t* dones_dev, const float* next_obs_dev,
+                          const uint32_t* next_mask_bits_dev, const float* weights_dev, float gamma_n, int32_t double_q, float* grad_dev,
+                          float* td_dev, int32_t* next_action_dev, float* stats_dev, void* stream);
+/* Adam (tf.train.AdamOptimizer form) with tf.clip_by_norm on each of the 8 (12 with dueling) variables; var_clip <= 0: no clipping */
+int rl4rs_distq_adam_step_clip_by_var(rl4rs_distq* net, const float* grad_dev, float lr, float beta1, float beta2, float eps,
+                                      float var_clip, void* stream);
+/* rl4rs_replay_sample with RLlib's adjust_nstep on the discrete ring's complete episodes.  The index draw and the weights are
+ * rl4rs_replay_sample's; for a row at step t of its T-step rollout, k = min(n_step, T - t):
+ *   reward = sum_{j < k} gamma^j r_{t + j} (the ring's float32 rewards, accumulated in float64 in step order, stored float32)
+ *   done   = (t + n_step >= T);  next obs / next mask = row idx + k * B when not done (a copy of the row itself otherwise)
+ * n_step = 1 is rl4rs_replay_sample bit for bit.  The bootstrap factor of the loss is gamma ^ n_step, not gamma ^ k. */
+int rl4rs_replay_sample_nstep(rl4rs_replay* h, int32_t M, int32_t n_step, double gamma, int32_t prioritized, double beta, uint32_t seed,
+                              uint32_t step, float* obs_out, float* next_obs_out, uint32_t* next_mask_out, int32_t* action_out,
+                              float* reward_out, int32_t* done_out, int32_t* idx_out, float* weight_out, float* u_out, void* stream);
+
 /* Raw-state policy encoder: rl4rs/nets/rllib/rllib_rawstate_model.py:25-86 (and its action-mask wrapper,
  * rllib_mask_model.py:67-115) for envs with config['rawstate_as_obs'] (rl4rs/env/slate.py:250-262):
  *   context = ELU([mean seq emb (per sequence, one shared table) | dense tower | mean category emb] @ ctx_w + ctx_b)  (256)

@@ -81,6 +81,12 @@ class AmlpCfg(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ('obs_dim', 'act_dim', 'hidden1', 'hidden2', 'out_dim', 'head_act', 'max_rows', 'max_grad_rows')]
 
 
+class DistqCfg(C.Structure):
+    """rl4rs_distq_cfg (include/rl4rs_hip.h)"""
+    _fields_ = ([(n, C.c_int32) for n in ('obs_dim', 'action_size', 'atoms', 'trunk', 'stream_hidden', 'dueling')] +
+                [('v_min', C.c_float), ('v_max', C.c_float), ('max_rows', C.c_int32)])
+
+
 class BcqStep(C.Structure):
     """rl4rs_bcq_step (include/rl4rs_hip.h)"""
     _fields_ = ([(n, C.c_void_p) for n in ('imit_enc', 'imit_dec', 'policy', 'policy_targ', 'q1', 'q2', 'q1_targ', 'q2_targ')] +
@@ -328,6 +334,19 @@ SIGNATURES = {
     'rl4rs_policy_dqn_loss_grad': (_I, [_P, _P, _I32, _P, _P, _P, _P, _P, _P, _P, C.c_float, _I32, _P, _P, _P, _P, _P]),
     'rl4rs_policy_greedy': (_I, [_P, _I32, _P, _P, _P, _P, _P]),
     'rl4rs_policy_adam_step_clip_by_var': (_I, [_P, _P, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _P]),
+    'rl4rs_distq_param_count': (_I64, [C.POINTER(DistqCfg)]),
+    'rl4rs_distq_create': (_I, [C.POINTER(DistqCfg), _P, _P, C.POINTER(_P)]),
+    'rl4rs_distq_destroy': (_I, [_P]),
+    'rl4rs_distq_params': (_I, [_P, _P, _P, _P]),
+    'rl4rs_distq_copy_params': (_I, [_P, _P, _P]),
+    'rl4rs_distq_adam_state': (_I, [_P, _P, _P, _P]),
+    'rl4rs_distq_set_adam_step': (_I, [_P, _I64]),
+    'rl4rs_distq_act': (_I, [_P, _I32, _P, _P, C.c_float, C.c_uint32, C.c_uint32, _P, _P, _P, _P]),
+    'rl4rs_distq_greedy': (_I, [_P, _I32, _P, _P, _P, _P, _P]),
+    'rl4rs_distq_loss_grad': (_I, [_P, _P, _I32, _P, _P, _P, _P, _P, _P, _P, C.c_float, _I32, _P, _P, _P, _P, _P]),
+    'rl4rs_distq_adam_step_clip_by_var': (_I, [_P, _P, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _P]),
+    'rl4rs_replay_sample_nstep': (_I, [_P, _I32, _I32, C.c_double, _I32, C.c_double, C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P,
+                                       _P, _P]),
 }
 
 # include/rl4rs_hip.h RL4RS_REPLAY_BUF_*

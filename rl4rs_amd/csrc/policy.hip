@@ -1635,3 +1635,4 @@ int rl4rs_policy_set_option(rl4rs_policy* p, int32_t which, int32_t value) {
 #include "contirl.hpp"
 #include "dqn.hpp"
 #include "td3.hpp"
+#include "rainbow.hpp"

@@ -1475,10 +1475,18 @@ class DeviceReplay(object):
         b['u'] = torch.empty(M, dtype=torch.float32, device=dev) if want_u else None
         return b
 
-    def sample(self, M, prioritized=True, beta=0.4, seed=0, step=0, out=None, want_u=False):
-        """Draw and gather M rows (rl4rs_replay_sample) -> dict obs, next_obs, next_mask, action, reward, done, idx, weight, u."""
+    def sample(self, M, prioritized=True, beta=0.4, seed=0, step=0, out=None, want_u=False, n_step=1, gamma=1.0):
+        """Draw and gather M rows (rl4rs_replay_sample) -> dict obs, next_obs, next_mask, action, reward, done, idx, weight, u.
+        ``n_step`` > 1 (rl4rs_replay_sample_nstep): the same draw with RLlib's adjust_nstep - reward = the discounted sum of the
+        next min(n_step, T - t) rewards, done = (t + n_step >= T), successor = that many steps on."""
         b = out if out is not None else self.new_batch(M, want_u)
         assert b['obs'].shape[0] == M
+        if int(n_step) != 1:
+            check(self.lib.rl4rs_replay_sample_nstep(self.h, M, int(n_step), float(gamma), 1 if prioritized else 0, float(beta),
+                                                     seed & 0xffffffff, step & 0xffffffff, _ptr(b['obs']), _ptr(b['next_obs']),
+                                                     _ptr(b['next_mask']), _ptr(b['action']), _ptr(b['reward']), _ptr(b['done']),
+                                                     _ptr(b['idx']), _ptr(b['weight']), _ptr(b.get('u')), _stream()))
+            return b
         check(self.lib.rl4rs_replay_sample(self.h, M, 1 if prioritized else 0, float(beta), seed & 0xffffffff, step & 0xffffffff,
                                            _ptr(b['obs']), _ptr(b['next_obs']), _ptr(b['next_mask']), _ptr(b['action']), _ptr(b['reward']),
                                            _ptr(b['done']), _ptr(b['idx']), _ptr(b['weight']), _ptr(b.get('u')), _stream()))
@@ -1492,6 +1500,149 @@ class DeviceReplay(object):
     def max_priority(self):
         """The largest |td| + 1e-6 ever set (1.0 at start); waits for the stream."""
         return float(self.column('max_priority').cpu()[0])
+
+
+class DeviceDistQ(object):
+    """rl4rs_distq handle: the dueling distributional (C51) Q network of Rainbow with flat parameters
+    W1, b1, W2, b2, Wa1, ba1, Wa2, ba2 [, Wv1, bv1, Wv2, bv2] (include/rl4rs_hip.h, "On-device Rainbow").  RLlib parity is
+    unpinned (ray is absent).  ``params``: flat float32 host array, default ``init_distq_params(..., seed)``."""
+
+    def __init__(self, obs_dim, action_size, max_rows, num_atoms=8, v_min=0.0, v_max=1000.0, dueling=True, trunk=256, stream_hidden=128,
+                 params=None, seed=0, device=None):
+        _lib.require_device()
+        self.lib = _lib.load()
+        self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        self.obs_dim, self.action_size, self.max_rows, self.num_atoms = int(obs_dim), int(action_size), int(max_rows), int(num_atoms)
+        self.dueling, self.trunk, self.stream_hidden = bool(dueling), int(trunk), int(stream_hidden)
+        self.v_min, self.v_max = float(v_min), float(v_max)
+        self.cfg = _lib.DistqCfg(self.obs_dim, self.action_size, self.num_atoms, self.trunk, self.stream_hidden, 1 if self.dueling else 0,
+                                 self.v_min, self.v_max, self.max_rows)
+        n = self.lib.rl4rs_distq_param_count(C.byref(self.cfg))
+        if n < 0:
+            raise _lib.Rl4rsHipError(self.lib.rl4rs_last_error().decode())
+        self.n_params = int(n)
+        if params is None:
+            from .nets.distq import init_distq_params
+            params = init_distq_params(self.obs_dim, self.action_size, self.num_atoms, self.trunk, self.stream_hidden, self.dueling, seed)
+        params = np.ascontiguousarray(params, dtype=np.float32)
+        assert params.shape == (self.n_params,), (params.shape, self.n_params)
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            check(self.lib.rl4rs_distq_create(C.byref(self.cfg), params.ctypes.data_as(C.c_void_p), _stream(), C.byref(h)))
+        self.h = h
+        self.W = (self.action_size + 31) // 32
+
+    def close(self):
+        if getattr(self, 'h', None) is not None and self.h:
+            self.lib.rl4rs_distq_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _params_ptr(self):
+        p, n = C.c_void_p(), C.c_int64()
+        check(self.lib.rl4rs_distq_params(self.h, C.byref(p), None, C.byref(n)))
+        return p, n.value
+
+    def params(self, out=None):
+        """Copy of the flat parameter buffer (device tensor); ``out``: a contiguous float32 device tensor to copy into."""
+        p, n = self._params_ptr()
+        if out is None:
+            out = torch.empty(n, dtype=torch.float32, device=self.device)
+        assert out.dtype == torch.float32 and out.numel() == n and out.is_contiguous() and out.is_cuda
+        check(self.lib.rl4rs_copy_d2d(_ptr(out), p, n * 4, _stream()))
+        return out
+
+    def set_params(self, flat):
+        p, n = self._params_ptr()
+        flat = flat.to(device=self.device, dtype=torch.float32).contiguous()
+        assert flat.numel() == n
+        check(self.lib.rl4rs_copy_d2d(p, _ptr(flat), n * 4, _stream()))
+        self._keep = flat
+
+    def copy_from(self, other):
+        check(self.lib.rl4rs_distq_copy_params(self.h, other.h, _stream()))
+
+    def _mask(self, mask_bits, N):
+        if mask_bits is None:
+            return None
+        assert mask_bits.dtype == torch.int32 and mask_bits.shape == (N, self.W) and mask_bits.is_contiguous()
+        return mask_bits
+
+    def _rows(self, obs, out):
+        N = obs.shape[0]
+        assert obs.dtype == torch.float32 and obs.shape == (N, self.obs_dim) and obs.is_contiguous()
+        a = out if out is not None else torch.empty(N, dtype=torch.int32, device=self.device)
+        assert a.dtype == torch.int32 and a.shape == (N,) and a.is_contiguous()
+        return N, a
+
+    def act(self, obs, mask_bits=None, temperature=1.0, seed=0, step=0, want_u=False, want_q=False, out=None):
+        """SoftQ draw (rl4rs_distq_act) -> (actions int32 [N], u [N] or None, masked Q [N, A] or None)."""
+        N, a = self._rows(obs, out)
+        u = torch.empty(N, dtype=torch.float32, device=self.device) if want_u else None
+        q = torch.empty((N, self.action_size), dtype=torch.float32, device=self.device) if want_q else None
+        check(self.lib.rl4rs_distq_act(self.h, N, _ptr(obs), _ptr(self._mask(mask_bits, N)), float(temperature), seed & 0xffffffff,
+                                       step & 0xffffffff, _ptr(a), _ptr(u), _ptr(q), _stream()))
+        return a, u, q
+
+    def greedy(self, obs, mask_bits=None, want_q=False, out=None):
+        """First maximum of the masked Q row (rl4rs_distq_greedy) -> (actions int32 [N], masked Q [N, A] or None)."""
+        N, a = self._rows(obs, out)
+        q = torch.empty((N, self.action_size), dtype=torch.float32, device=self.device) if want_q else None
+        check(self.lib.rl4rs_distq_greedy(self.h, N, _ptr(obs), _ptr(self._mask(mask_bits, N)), _ptr(a), _ptr(q), _stream()))
+        return a, q
+
+    def loss_grad(self, target_params, obs, actions, rewards, dones, next_obs, next_mask_bits=None, weights=None, gamma_n=1.0,
+                  double_q=True, grad_out=None, td_out=None, want_next_action=False):
+        """Categorical loss and gradient (rl4rs_distq_loss_grad).  All inputs are contiguous device tensors: obs / next_obs /
+        rewards (the n-step return) / weights float32, actions / dones int32, target_params float32 [n_params]; gamma_n = gamma ^ n_step.
+        -> (grad, td [N], stats[4] sums of {w * td, Q(s)[a], sum_i z_i m_i, td}, a* [N] or None)."""
+        N = obs.shape[0]
+        for t in (target_params, obs, rewards, next_obs) + ((weights,) if weights is not None else ()):
+            assert t.dtype == torch.float32 and t.is_contiguous()
+        assert actions.dtype == torch.int32 and dones.dtype == torch.int32 and actions.is_contiguous() and dones.is_contiguous()
+        assert target_params.numel() == self.n_params and obs.shape == (N, self.obs_dim) and next_obs.shape == (N, self.obs_dim)
+        assert actions.shape == (N,) and rewards.shape == (N,) and dones.shape == (N,) and (weights is None or weights.shape == (N,))
+        m = self._mask(next_mask_bits, N)
+        g = grad_out if grad_out is not None else torch.empty(self.n_params, dtype=torch.float32, device=self.device)
+        assert g.dtype == torch.float32 and g.numel() == self.n_params and g.is_contiguous()
+        td = td_out if td_out is not None else torch.empty(N, dtype=torch.float32, device=self.device)
+        assert td.dtype == torch.float32 and td.shape == (N,) and td.is_contiguous()
+        stats = torch.empty(4, dtype=torch.float32, device=self.device)
+        astar = torch.empty(N, dtype=torch.int32, device=self.device) if want_next_action else None
+        check(self.lib.rl4rs_distq_loss_grad(self.h, _ptr(target_params), N, _ptr(obs), _ptr(actions), _ptr(rewards), _ptr(dones),
+                                             _ptr(next_obs), _ptr(m), _ptr(weights), float(gamma_n), 1 if double_q else 0, _ptr(g), _ptr(td),
+                                             _ptr(astar), _ptr(stats), _stream()))
+        return g, td, stats, astar
+
+    def adam_step_clip_by_var(self, grad, lr=5e-4, beta1=0.9, beta2=0.999, eps=1e-8, var_clip=40.0):
+        """Adam with every variable clipped by its own norm (rl4rs_distq_adam_step_clip_by_var)."""
+        check(self.lib.rl4rs_distq_adam_step_clip_by_var(self.h, _ptr(grad), lr, beta1, beta2, eps, var_clip, _stream()))
+
+    def adam_state(self):
+        """(m, v) copies of the Adam moments and the step counter."""
+        m, v, t = C.c_void_p(), C.c_void_p(), C.c_int64()
+        check(self.lib.rl4rs_distq_adam_state(self.h, C.byref(m), C.byref(v), C.byref(t)))
+        om = torch.empty(self.n_params, dtype=torch.float32, device=self.device)
+        ov = torch.empty(self.n_params, dtype=torch.float32, device=self.device)
+        check(self.lib.rl4rs_copy_d2d(_ptr(om), m, self.n_params * 4, _stream()))
+        check(self.lib.rl4rs_copy_d2d(_ptr(ov), v, self.n_params * 4, _stream()))
+        return om, ov, int(t.value)
+
+    def set_adam_state(self, m, v, step):
+        pm, pv, t = C.c_void_p(), C.c_void_p(), C.c_int64()
+        check(self.lib.rl4rs_distq_adam_state(self.h, C.byref(pm), C.byref(pv), C.byref(t)))
+        m = m.to(device=self.device, dtype=torch.float32).contiguous()
+        v = v.to(device=self.device, dtype=torch.float32).contiguous()
+        assert m.numel() == self.n_params and v.numel() == self.n_params
+        check(self.lib.rl4rs_copy_d2d(pm, _ptr(m), self.n_params * 4, _stream()))
+        check(self.lib.rl4rs_copy_d2d(pv, _ptr(v), self.n_params * 4, _stream()))
+        check(self.lib.rl4rs_distq_set_adam_step(self.h, int(step)))
+        self._keep_adam = (m, v)
 
 
 class DeviceContiReplay(DeviceReplay):

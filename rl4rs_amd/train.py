@@ -10,6 +10,10 @@ cumulative sum of rewards and (data-parallel) the RCCL all-reduce of the flat gr
 target_network_update_freq 200, buffer_size 100000 on the mask model): replay memory, TD loss, per-variable-clipped Adam and
 the target copy all stay on the device (rl4rs_replay_*, rl4rs_policy_dqn_loss_grad).
 
+``RainbowTrainer`` is that driver's RAINBOW (script/modelfree_train.py:50-53,146-178: RLlib DQN with num_atoms 8, dueling, double_q,
+n_step 3 on RLlib's default model): the distributional network has a handle of its own (rl4rs_distq_*), the ring's n-step draw is
+rl4rs_replay_sample_nstep, everything else is ``DQNTrainer``'s loop.
+
 ``TD3Trainer`` is the continuous actor-critic learner of that driver (script/modelfree_train.py:46-48,79-105: RLlib TD3 / DDPG on
 support_conti_env): OU exploration, a replay ring of float actions and the whole update (rl4rs_td3_update) stay on the device.
 
@@ -631,6 +635,128 @@ class DQNTrainer(_DeferredStats):
         finally:
             np.random.set_state(state)
         return float(total.item()) / n
+
+
+class RainbowTrainer(DQNTrainer):
+    """Online Rainbow - distributional (C51), dueling, double-Q, n-step DQN - over the zero-copy discrete-action env, with what the
+    reference's driver makes of RLlib 1.5.1's DQN defaults (script/modelfree_train.py:50-53,146-178) as defaults: num_atoms 8 over
+    [v_min 0, v_max 1000], dueling, double_q, n_step 3, gamma 1, lr 5e-4, Adam eps 1e-8, grad_clip 40 per variable,
+    target_network_update_freq 500 sampled timesteps, learning_starts 1000, buffer_size 100000, train_batch_size min(B * T, 1024),
+    prioritized replay alpha 0.6 / beta 0.4, SoftQ exploration at temperature 1 over Q, noisy False.  The network is RLlib's
+    default model (``DeviceDistQ``), initialised by ``init_distq_params(seed=init_seed)``.  RLlib parity is unpinned (ray is
+    absent), as for DQN / A2C / PPO.
+
+    The env may be the plain-observation one (the reference's setting: it forces support_rllib_mask False, because its
+    distributional model "will make action masking not work") or the support_rllib_mask one.
+    masked      False: the reference's unmasked behaviour.  True: the env's packed action mask goes to act / greedy / a*, where it
+                sets a disallowed action's Q to -3.4e38 (the logits are untouched) - the second deviation from the reference
+    The replay ring holds whole rollouts (``DQNTrainer``); without ``masked`` its mask words are all ones.
+    Structure, statistics and the data-parallel all-reduce of the flat gradient are ``DQNTrainer``'s; ``train_iteration`` reports
+    td_loss (the mean weighted cross-entropy), mean_q, mean_target (the mean of the projected target distribution) and
+    mean_td_abs (the mean cross-entropy = the new priorities) of the last update."""
+
+    def __init__(self, env, seed=0, init_seed=0, lr=5e-4, gamma=1.0, adam_eps=1e-8, grad_clip=40.0, double_q=True, n_step=3, num_atoms=8,
+                 v_min=0.0, v_max=1000.0, dueling=True, noisy=False, masked=False, trunk=256, stream_hidden=128, buffer_size=100000,
+                 target_network_update_freq=500, learning_starts=1000, train_batch_size=None, prioritized_replay=True,
+                 prioritized_replay_alpha=0.6, prioritized_replay_beta=0.4, softq_temperature=1.0, updates_per_rollout=1,
+                 keep_last_batch=False):
+        cfg = env.config
+        assert cfg.get('return_tensors', False) and not cfg.get('support_conti_env', False), \
+            "RainbowTrainer needs the zero-copy discrete-action env (config['return_tensors'] = True)"
+        if noisy:
+            raise ValueError("RainbowTrainer: noisy layers are not implemented (the reference leaves RLlib's noisy = False)")
+        if int(num_atoms) < 2:
+            raise ValueError("RainbowTrainer is the distributional learner (num_atoms >= 2); num_atoms = 1 is DQNTrainer")
+        if int(n_step) < 1 or float(softq_temperature) <= 0.0:
+            raise ValueError("RainbowTrainer: n_step >= 1 and softq_temperature > 0 (got %r, %r)" % (n_step, softq_temperature))
+        self.env = env
+        self.B, self.T, self.A = cfg['batch_size'], cfg['max_steps'], cfg['action_size']
+        self.seed, self.lr, self.gamma, self.adam_eps, self.grad_clip = seed, float(lr), float(gamma), float(adam_eps), float(grad_clip)
+        self.double_q, self.prioritized, self.beta = bool(double_q), bool(prioritized_replay), float(prioritized_replay_beta)
+        self.n_step, self.masked, self.temperature = int(n_step), bool(masked), float(softq_temperature)
+        self.gamma_n = float(np.float32(self.gamma ** self.n_step))
+        self.target_network_update_freq, self.learning_starts = int(target_network_update_freq), int(learning_starts)
+        self.updates_per_rollout = int(updates_per_rollout)
+        self.M = int(train_batch_size) if train_batch_size is not None else min(self.B * self.T, 1024)
+        self.keep_last_batch, self.last_batch = keep_last_batch, None
+        self._pending = []
+        self._kl_coeff, self.kl_target = 0.0, 0.0            # (unused: the deferred-statistics base carries PPO's)
+        space = env.observation_space
+        space = space.spaces['obs'] if hasattr(space, 'spaces') else space
+        self.OD = int(space.shape[0])
+        self.policy = D.DeviceDistQ(self.OD, self.A, max_rows=max(self.M, self.B), num_atoms=num_atoms, v_min=v_min, v_max=v_max,
+                                    dueling=dueling, trunk=trunk, stream_hidden=stream_hidden, seed=init_seed)
+        dev = self.policy.device
+        self.replay = D.DeviceReplay(self.OD, self.A, self.T, self.B, buffer_size=buffer_size, alpha=prioritized_replay_alpha, device=dev)
+        N = self.B * self.T
+        self.buf = dict(obs=torch.empty((N, self.OD), dtype=torch.float32, device=dev),
+                        mask=torch.full((N, self.policy.W), -1, dtype=torch.int32, device=dev),       # all ones unless ``masked``
+                        act=torch.empty(N, dtype=torch.int32, device=dev),
+                        rew=torch.empty(N, dtype=torch.float64, device=dev))
+        self._batch = self.replay.new_batch(self.M)
+        self._td = torch.empty(self.M, dtype=torch.float32, device=dev)
+        self.grad = torch.empty(self.policy.n_params, dtype=torch.float32, device=dev)
+        self.iteration = 0
+        self._rollouts = 0
+        self.timesteps = 0
+        self.num_updates = 0
+        self.num_target_updates = 0
+        self._last_target_sync = 0
+        if rdist.collectives_active():
+            Trainer.sync_replicas(self)
+        self.target = self.policy.params()                  # the target net starts as a copy of the online one
+
+    def _episode(self, greedy, step0, reset_file=False):
+        """One complete-episode rollout into the rollout buffers -> mean episode reward (device scalar)."""
+        B, T = self.B, self.T
+        b = self.buf
+        obs = self.env.reset(reset_file=True) if reset_file else self.env.reset()
+        for t in range(T):
+            obs_t = obs['obs'] if isinstance(obs, dict) else obs
+            sl = slice(t * B, (t + 1) * B)
+            mask = self.env.samples._live().obs_mask_bits(out=b['mask'][sl]) if self.masked else None
+            b['obs'][sl] = obs_t
+            if greedy:
+                a = self.policy.greedy(b['obs'][sl], mask, out=b['act'][sl])[0]
+            else:
+                a = self.policy.act(b['obs'][sl], mask, temperature=self.temperature, seed=self.seed, step=step0 + t, out=b['act'][sl])[0]
+            obs, reward, done, info = self.env.step(a)
+            b['rew'][sl] = reward
+        return b['rew'].view(T, B).sum(dim=0).mean()
+
+    def update(self):
+        """One learner step: n-step sample -> loss / gradient -> all-reduce (data parallel) -> per-variable-clipped Adam ->
+        priorities.  -> stats[4] device sums of {w * td, Q(s)[a], sum_i z_i m_i, td} over the minibatch."""
+        b = self.replay.sample(self.M, prioritized=self.prioritized, beta=self.beta, seed=self.seed + 0x5bd1e995, step=self.num_updates,
+                               out=self._batch, n_step=self.n_step, gamma=self.gamma)
+        w = b['weight'] if self.prioritized else None
+        g, td, stats, astar = self.policy.loss_grad(self.target, b['obs'], b['action'], b['reward'], b['done'], b['next_obs'],
+                                                    b['next_mask'] if self.masked else None, weights=w, gamma_n=self.gamma_n,
+                                                    double_q=self.double_q, grad_out=self.grad, td_out=self._td,
+                                                    want_next_action=self.keep_last_batch)
+        if self.keep_last_batch:
+            self.last_batch = dict((k, v.clone()) for k, v in b.items() if v is not None)
+            self.last_batch.update(td=td.clone(), next_action=astar)
+        if rdist.collectives_active():
+            rdist.allreduce_mean_(g)
+        self.policy.adam_step_clip_by_var(g, lr=self.lr, eps=self.adam_eps, var_clip=self.grad_clip)
+        if self.prioritized:
+            self.replay.update_priorities(b['idx'], td)
+        self.num_updates += 1
+        return stats
+
+    def _settle(self):
+        while self._pending:
+            tok = self._pending.pop(0)
+            tok['ev'].synchronize()
+            v = tok['pin'].numpy().copy()
+            if v[-1] >= 1000.0:
+                raise RuntimeError(rdist.ROW_OVERFLOW_MESSAGE)
+            s, n = v[1:-1], max(tok['rows'], 1)
+            tok['values'] = {'episode_reward_mean': float(v[0]), 'td_loss': float(s[0]) / n, 'mean_q': float(s[1]) / n,
+                             'mean_target': float(s[2]) / n, 'mean_td_abs': float(s[3]) / n, 'buffer_rows': tok['buffer_rows'],
+                             'num_updates': tok['num_updates'], 'num_target_updates': tok['num_target_updates'],
+                             'iteration': tok['iteration']}
 
 
 # ---- TD3 / DDPG -----------------------------------------------------------------------------------------------------------------
