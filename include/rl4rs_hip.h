@@ -778,6 +778,43 @@ int rl4rs_replay_sample_nstep(rl4rs_replay* h, int32_t M, int32_t n_step, double
                               uint32_t step, float* obs_out, float* next_obs_out, uint32_t* next_mask_out, int32_t* action_out,
                               float* reward_out, int32_t* done_out, int32_t* idx_out, float* weight_out, float* u_out, void* stream);
 
+/* --------------------------------------------------------------------------------------------------
+ * V-trace (the off-policy correction of script/modelfree_train.py:345-390, algo "IMPALA"; restates RLlib 1.5.1's
+ * vtrace_tf.from_importance_weights, parity unpinned).  All arrays are time-major [T, B] with row stride B; T is the number of
+ * steps the loss runs over (RLlib's "drop the last step, bootstrap from its value" is the caller's business: pass T - 1 and
+ * the dropped step's values as bootstrap_value).
+ *   rho_t    = exp(target_logp_t - behaviour_logp_t)
+ *   disc_t   = gamma * (1 - done_t)
+ *   V_{t+1}  = values_{t+1} (t < T-1), bootstrap_value (t = T-1)
+ *   delta_t  = min(clip_rho, rho_t) * (r_t + disc_t * V_{t+1} - V_t)
+ *   acc_t    = delta_t + disc_t * min(1, rho_t) * acc_{t+1},   acc_T = 0
+ *   vs_t     = V_t + acc_t
+ *   vs_{t+1} = vs at t+1 (t < T-1), bootstrap_value (t = T-1)
+ *   pg_adv_t = min(clip_pg_rho, rho_t) * (r_t + disc_t * vs_{t+1} - V_t)
+ * bootstrap_value [B] (NULL = zeros), rewards float64 (the env's), dones int32 (NULL = none).  The scan runs in float64 and
+ * rounds once on the store.  stats_out (optional) double[4] = {sum rho, sum min(rho, clip_rho), sum vs_out, sum pg_adv_out}
+ * over all T * B entries, summed in a fixed order: bit-identical from run to run.  Refuses T < 1, B < 1, null required pointers. */
+int rl4rs_vtrace(int32_t T, int32_t B, const float* behaviour_logp, const float* target_logp, const float* values,
+                 const float* bootstrap_value, const double* rewards, const int32_t* dones, float gamma, float clip_rho,
+                 float clip_pg_rho, float* vs_out, float* pg_adv_out, double* stats_out, void* stream);
+/* V-trace loss and gradient on the net of `pol` in one call (RLlib 1.5.1's VTraceLoss).  Rows are [R, T, B]: R rollouts of T
+ * time-major steps of B envs, row (r * T + t) * B + b; R * T * B <= max_rows.
+ *   1. target_logp, values = the forward of rl4rs_policy_evaluate on every row
+ *   2. rl4rs_vtrace per rollout.  drop_last 1 (RLlib): the loss runs over steps 0 .. T-2, the bootstrap is values[T-1] and
+ *      nothing else of step T-1 is seen (T = 1 is refused); drop_last 0: all T steps, zero bootstrap
+ *   3. rl4rs_policy_loss_grad(algo 0) on the kept rows with adv = pg_adv, ret = vs (both constants):
+ *      -sum(logp * pg_adv) + vf_coeff * 0.5 * sum((V - vs)^2) - ent_coeff * sum(H)
+ * The rows of a dropped step contribute nothing to grad_dev, the entropy sum or stats_dev (float[4] as rl4rs_policy_loss_grad).
+ * vtrace_stats_dev (optional) double[4]: rl4rs_vtrace's sums, added up over the R rollouts.  vs_out / pg_adv_out (optional)
+ * float [R * T * B]: the V-trace outputs in row order, zeros on dropped rows.  No Adam step inside: a data-parallel trainer
+ * all-reduces grad_dev first.  The first call allocates the scratch on the handle.  behaviour_logp_dev float32, rewards_dev
+ * float64, dones_dev int32 or NULL. */
+int rl4rs_policy_vtrace_loss_grad(rl4rs_policy* pol, int32_t R, int32_t T, int32_t B, const float* obs_dev,
+                                  const uint32_t* mask_bits_dev, const int32_t* actions_dev, const float* behaviour_logp_dev,
+                                  const double* rewards_dev, const int32_t* dones_dev, float gamma, float clip_rho,
+                                  float clip_pg_rho, int32_t drop_last, float vf_coeff, float ent_coeff, float* grad_dev,
+                                  float* stats_dev, double* vtrace_stats_dev, float* vs_out, float* pg_adv_out, void* stream);
+
 /* Raw-state policy encoder: rl4rs/nets/rllib/rllib_rawstate_model.py:25-86 (and its action-mask wrapper,
  * rllib_mask_model.py:67-115) for envs with config['rawstate_as_obs'] (rl4rs/env/slate.py:250-262):
  *   context = ELU([mean seq emb (per sequence, one shared table) | dense tower | mean category emb] @ ctx_w + ctx_b)  (256)

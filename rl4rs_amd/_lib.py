@@ -347,6 +347,9 @@ SIGNATURES = {
     'rl4rs_distq_adam_step_clip_by_var': (_I, [_P, _P, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _P]),
     'rl4rs_replay_sample_nstep': (_I, [_P, _I32, _I32, C.c_double, _I32, C.c_double, C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P,
                                        _P, _P]),
+    'rl4rs_vtrace': (_I, [_I32, _I32, _P, _P, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float, _P, _P, _P, _P]),
+    'rl4rs_policy_vtrace_loss_grad': (_I, [_P, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float, _I32, C.c_float,
+                                           C.c_float, _P, _P, _P, _P, _P, _P]),
 }
 
 # include/rl4rs_hip.h RL4RS_REPLAY_BUF_*

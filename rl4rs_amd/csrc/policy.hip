@@ -935,6 +935,11 @@ struct rl4rs_policy {
     bool opt_tile, opt_ppo_fused, opt_ppo_std;
     int opt_ppo_rows, opt_resident_cap;
     float *dqn_Hn, *dqn_Hnt, *dqn_g;      // scratch of rl4rs_policy_dqn_loss_grad (dqn.hpp), allocated by its first call
+    // scratch of rl4rs_policy_vtrace_loss_grad (vtrace.hpp), allocated by its first call: target log-probs, values, vs, pg_adv
+    // [max_rows] and, for several rollouts with a dropped last step, the kept rows' observations / mask words / actions
+    float *vt_logp, *vt_val, *vt_vs, *vt_pg, *vt_obs;
+    uint32_t* vt_mask;
+    int32_t* vt_act;
     std::vector<void*> owned;
 };
 
@@ -972,6 +977,9 @@ int rl4rs_policy_create(int32_t obs_dim, int32_t hidden, int32_t action_size, in
     p->opt_tile = true; p->opt_ppo_fused = true; p->opt_ppo_std = true; p->opt_ppo_rows = 0; p->opt_resident_cap = -1;
     p->dead_host = nullptr;
     p->dqn_Hn = p->dqn_Hnt = p->dqn_g = nullptr;
+    p->vt_logp = p->vt_val = p->vt_vs = p->vt_pg = p->vt_obs = nullptr;
+    p->vt_mask = nullptr;
+    p->vt_act = nullptr;
     p->tile_attr[0] = p->tile_attr[1] = p->tile_attr[2] = false;
     int rc;
     auto alloc = [&](float** dst, size_t n) {
@@ -1636,3 +1644,4 @@ int rl4rs_policy_set_option(rl4rs_policy* p, int32_t which, int32_t value) {
 #include "dqn.hpp"
 #include "td3.hpp"
 #include "rainbow.hpp"
+#include "vtrace.hpp"

@@ -1163,6 +1163,28 @@ def gemm_h16_packed(a, w_host, bias=None, act=0):
     return c
 
 
+def vtrace(behaviour_logp, target_logp, values, rewards, bootstrap_value=None, dones=None, gamma=1.0, clip_rho=1.0, clip_pg_rho=1.0,
+           want_stats=True):
+    """V-trace targets of time-major [T, B] device tensors (rl4rs_vtrace): log-probs / values float32, rewards float64,
+    bootstrap_value float32 [B] or None (zeros), dones int32 or None.
+    -> (vs [T, B], pg_adv [T, B], stats float64 [4] sums of {rho, min(rho, clip_rho), vs, pg_adv} or None)."""
+    lib = _lib.load()
+    T, B = values.shape
+    for t in (behaviour_logp, target_logp, values):
+        assert t.dtype == torch.float32 and tuple(t.shape) == (T, B) and t.is_contiguous() and t.is_cuda
+    assert rewards.dtype == torch.float64 and tuple(rewards.shape) == (T, B) and rewards.is_contiguous()
+    assert bootstrap_value is None or (bootstrap_value.dtype == torch.float32 and tuple(bootstrap_value.shape) == (B,)
+                                       and bootstrap_value.is_contiguous())
+    assert dones is None or (dones.dtype == torch.int32 and tuple(dones.shape) == (T, B) and dones.is_contiguous())
+    vs = torch.empty((T, B), dtype=torch.float32, device=values.device)
+    pg = torch.empty((T, B), dtype=torch.float32, device=values.device)
+    stats = torch.empty(4, dtype=torch.float64, device=values.device) if want_stats else None
+    with torch.cuda.device(values.device):
+        check(lib.rl4rs_vtrace(T, B, _ptr(behaviour_logp), _ptr(target_logp), _ptr(values), _ptr(bootstrap_value), _ptr(rewards),
+                               _ptr(dones), gamma, clip_rho, clip_pg_rho, _ptr(vs), _ptr(pg), _ptr(stats), _stream()))
+    return vs, pg, stats
+
+
 class DevicePolicy(object):
     """rl4rs_policy handle: action-masked policy net (rllib_mask_model.py:7-64) with flat parameters."""
     A2C, PPO = 0, 1
@@ -1338,6 +1360,39 @@ class DevicePolicy(object):
                                                   _ptr(next_obs), _ptr(m), _ptr(weights), gamma, 1 if double_q else 0, _ptr(g), _ptr(td),
                                                   _ptr(astar), _ptr(stats), _stream()))
         return g, td, stats, astar
+
+    def vtrace_loss_grad(self, R, T, B, obs, actions, behaviour_logp, rewards, mask_bits=None, dones=None, gamma=1.0, clip_rho=1.0,
+                         clip_pg_rho=1.0, drop_last=True, vf_coeff=0.5, ent_coeff=0.01, grad_out=None, stats_out=None,
+                         vtrace_stats_out=None, want_vtrace=False):
+        """V-trace loss and gradient over R rollouts of [T, B] time-major rows (rl4rs_policy_vtrace_loss_grad).  All inputs are
+        contiguous device tensors: obs / behaviour_logp float32, actions (and dones) int32, rewards float64.
+        -> (grad, stats[4] sums of {policy loss, value loss, entropy, 0} over the kept rows, vtrace_stats float64 [4] sums of
+        {rho, min(rho, clip_rho), vs, pg_adv}, (vs, pg_adv) float32 [R * T * B] or None)."""
+        N = R * T * B
+        assert obs.dtype == torch.float32 and obs.shape == (N, self.obs_dim) and obs.is_contiguous()
+        assert actions.dtype == torch.int32 and actions.shape == (N,) and actions.is_contiguous()
+        assert behaviour_logp.dtype == torch.float32 and behaviour_logp.shape == (N,) and behaviour_logp.is_contiguous()
+        assert rewards.dtype == torch.float64 and rewards.shape == (N,) and rewards.is_contiguous()
+        assert dones is None or (dones.dtype == torch.int32 and dones.shape == (N,) and dones.is_contiguous())
+        m = self._mask(mask_bits, N)
+        g = grad_out if grad_out is not None else torch.empty(self.n_params, dtype=torch.float32, device=self.device)
+        stats = stats_out if stats_out is not None else torch.empty(4, dtype=torch.float32, device=self.device)
+        vstats = vtrace_stats_out if vtrace_stats_out is not None else torch.empty(4, dtype=torch.float64, device=self.device)
+        assert stats.dtype == torch.float32 and stats.numel() == 4 and vstats.dtype == torch.float64 and vstats.numel() == 4
+        vs = torch.empty(N, dtype=torch.float32, device=self.device) if want_vtrace else None
+        pg = torch.empty(N, dtype=torch.float32, device=self.device) if want_vtrace else None
+        check(self.lib.rl4rs_policy_vtrace_loss_grad(self.h, R, T, B, _ptr(obs), _ptr(m), _ptr(actions), _ptr(behaviour_logp), _ptr(rewards),
+                                                     _ptr(dones), gamma, clip_rho, clip_pg_rho, 1 if drop_last else 0, vf_coeff, ent_coeff,
+                                                     _ptr(g), _ptr(stats), _ptr(vstats), _ptr(vs), _ptr(pg), _stream()))
+        return g, stats, vstats, ((vs, pg) if want_vtrace else None)
+
+    def copy_params_from(self, other):
+        """This handle's parameters <- ``other``'s, a device-to-device copy (IMPALA's learner -> actor broadcast)."""
+        src, dst, n = C.c_void_p(), C.c_void_p(), C.c_int32()
+        check(self.lib.rl4rs_policy_params(other.h, C.byref(src), C.byref(n)))
+        assert n.value == self.n_params
+        check(self.lib.rl4rs_policy_params(self.h, C.byref(dst), C.byref(n)))
+        check(self.lib.rl4rs_copy_d2d(dst, src, self.n_params * 4, _stream()))
 
     def greedy(self, obs, mask_bits=None, want_q=False, out=None):
         """First maximum of the masked Q row (rl4rs_policy_greedy) -> (actions int32 [N], masked Q [N, A] or None)."""

@@ -1,7 +1,9 @@
 """On-device policy training loops over the GPU env (A2C / PPO with the reference's RLlib hyper-parameters,
 script/modelfree_train.py:179-304: gamma = 1, GAE lambda = 1, lr 1e-4, vf_loss_coeff 0.5; A2C entropy 0.01 and
 grad_clip 10; PPO clip 0.3, kl_coeff 0.2 adapted towards kl_target 0.01, vf_clip 500, one SGD pass over minibatches of 256;
-train_batch_size = min(B * T, 1024) timesteps per train call, :409).
+train_batch_size = min(B * T, 1024) timesteps per train call, :409).  The same ``Trainer`` runs that driver's PG (:306-343: lr 4e-4,
+the plain policy gradient on the return-to-go) and IMPALA (:345-390: V-trace, rl4rs_policy_vtrace_loss_grad, with an actor copy of
+the policy that trails the learner by a fixed number of updates).
 
 Rollout, policy forward/backward and Adam run through librl4rs_hip.so; torch is used for buffers, the reversed
 cumulative sum of rewards and (data-parallel) the RCCL all-reduce of the flat gradient buffer.
@@ -163,6 +165,9 @@ class _DeferredStats(object):
             tok['values'] = {'episode_reward_mean': float(v[0]), 'policy_loss': float(s[0]), 'vf_loss': float(s[1]),
                              'entropy': float(s[2]), 'kl': float(s[3]), 'kl_mean': kl_mean, 'kl_coeff': self._kl_coeff,
                              'iteration': tok['iteration']}
+            if tok.get('vtrace_rows'):                      # IMPALA: s[4:8] = sums of {rho, min(rho, clip_rho), vs, pg_adv} over the kept rows
+                n = float(tok['vtrace_rows'])
+                tok['values'].update(rho_mean=float(s[4]) / n, rho_clipped_mean=float(s[5]) / n, vs_mean=float(s[6]) / n)
 
     def _resolve(self, token):
         if token['values'] is None:
@@ -307,24 +312,56 @@ class RawStateTrainer(_DeferredStats):
 
 
 class Trainer(_DeferredStats):
-    """A2C / PPO on the action-masked FC policy (rllib_mask_model.py:7-64) over the zero-copy discrete-action env.
+    """A2C / PPO / PG / IMPALA on the action-masked FC policy (rllib_mask_model.py:7-64) over the zero-copy discrete-action env.
 
     seed       sampling stream of this rank (Gumbel noise, PPO shuffle): pass a different value per rank
     init_seed  parameter initialisation, shared by all ranks (and rank 0's parameters are broadcast anyway)
+    lr         None = the driver's value for ``algo`` (DRIVER_LR: 1e-4 for A2C / PPO / IMPALA, 4e-4 for PG); a number is used as given
     kl_coeff / kl_target   PPO's adaptive KL penalty (update_kl_coeff above)
     train_batch_size       timesteps per train call (rollouts_per_train_call above; the reference's value = one rollout)
-    keep_last_batch        keep the shuffled tensors of the last iteration in ``last_batch`` (tests)"""
+    keep_last_batch        keep the shuffled tensors of the last iteration in ``last_batch`` (tests)
 
-    def __init__(self, env, algo='A2C', hidden=64, seed=0, lr=1e-4, minibatch=256, init_seed=0, kl_coeff=0.2, kl_target=0.01,
-                 train_batch_size=None, keep_last_batch=False):
+    algo='PG' (RLlib pg_tf_policy, parity unpinned): loss = -mean(logp * return-to-go) with gamma 1 (``_returns``), Adam, no critic, no
+    entropy term, no gradient clip.  It is the A2C loss with vf_coeff = ent_coeff = 0 and advantages = returns / N, so the value head
+    receives an exactly zero gradient and keeps its initial bits; ``vf_loss`` / ``entropy`` are still reported (sums, as for A2C),
+    ``policy_loss`` is the mean.
+
+    algo='IMPALA' (RLlib impala with vtrace, parity unpinned): the rollout samples from a second handle, the ACTOR, and the learner's
+    update is rl4rs_policy_vtrace_loss_grad on the whole rollout batch (no minibatches, no replay slots), the rank-mean gradient,
+    Adam with global-norm clip 10.  After every ``broadcast_interval``-th update the learner's parameters are copied into the actor on
+    the device: with 1 the run is on-policy up to kernel rounding (every importance weight is 1), with k the actor is stale in k - 1
+    of every k train calls - a deterministic stand-in for RLlib's asynchronous workers.  ``vtrace_clip_rho`` /
+    ``vtrace_clip_pg_rho`` / ``vf_coeff`` / ``ent_coeff`` are RLlib's vtrace_clip_rho_threshold / vtrace_clip_pg_rho_threshold /
+    vf_loss_coeff / entropy_coeff.  ``drop_last=True`` is RLlib's behaviour: the last step of every rollout only supplies the
+    bootstrap value.  On SlateRecEnv-v0 the only reward arrives at that last step, so with drop_last=True THE LEARNER SEES NO REWARD
+    (what the reference's IMPALA branch does as written); pass drop_last=False (all T steps, zero bootstrap) to train on it.
+    ``train_iteration`` adds rho_mean, rho_clipped_mean and vs_mean (means over the kept rows) to the A2C statistics."""
+
+    DRIVER_LR = {'A2C': 1e-4, 'PPO': 1e-4, 'IMPALA': 1e-4, 'PG': 4e-4}          # script/modelfree_train.py:204,261,354,309
+
+    def __init__(self, env, algo='A2C', hidden=64, seed=0, lr=None, minibatch=256, init_seed=0, kl_coeff=0.2, kl_target=0.01,
+                 train_batch_size=None, keep_last_batch=False, broadcast_interval=1, vtrace_clip_rho=1.0, vtrace_clip_pg_rho=1.0,
+                 drop_last=True, vf_coeff=0.5, ent_coeff=0.01, grad_clip=10.0):
         cfg = env.config
         assert cfg.get('return_tensors', False) and not cfg.get('support_conti_env', False), \
             "Trainer needs the zero-copy discrete-action env (config['return_tensors'] = True)"
         self.env = env
-        self.algo = {'A2C': D.DevicePolicy.A2C, 'PPO': D.DevicePolicy.PPO}[algo]
+        # PG and IMPALA run on the A2C form of the loss kernels
+        self.algo = {'A2C': D.DevicePolicy.A2C, 'PPO': D.DevicePolicy.PPO, 'PG': D.DevicePolicy.A2C, 'IMPALA': D.DevicePolicy.A2C}[algo]
+        self.algo_name = algo
         self.B, self.T, self.A = cfg['batch_size'], cfg['max_steps'], cfg['action_size']
         self.R = rollouts_per_train_call(self.B, self.T, train_batch_size)
+        if lr is None:
+            lr = self.DRIVER_LR[algo]
         self.seed, self.lr, self.minibatch = seed, lr, minibatch
+        self.broadcast_interval, self.drop_last = int(broadcast_interval), bool(drop_last)
+        self.vtrace_clip_rho, self.vtrace_clip_pg_rho = float(vtrace_clip_rho), float(vtrace_clip_pg_rho)
+        self.vf_coeff, self.ent_coeff, self.grad_clip = float(vf_coeff), float(ent_coeff), float(grad_clip)
+        if algo == 'IMPALA':
+            if self.broadcast_interval < 1:
+                raise ValueError("IMPALA: broadcast_interval must be >= 1 (got %r)" % (broadcast_interval,))
+            if self.drop_last and self.T < 2:
+                raise ValueError("IMPALA: drop_last needs max_steps >= 2 (the dropped step's value is the bootstrap)")
         self._kl_coeff, self.kl_target = float(kl_coeff), float(kl_target)
         self._pending = []          # train calls whose statistics have not been looked at yet (oldest first)
         self.keep_last_batch = keep_last_batch
@@ -358,8 +395,15 @@ class Trainer(_DeferredStats):
                         logits=torch.empty((N, self.A), dtype=torch.float32, device=dev))
         self.grad = torch.empty(self.policy.n_params, dtype=torch.float32, device=dev)
         self._mb_stats = torch.empty(4, dtype=torch.float32, device=dev)
+        self.actor = None
+        self.num_updates = 0
         if rdist.collectives_active():
             self.sync_replicas()
+        if algo == 'IMPALA':
+            # the actor: the handle rollouts sample from; it only ever sees one env batch per call
+            self.actor = D.DevicePolicy(self.OD, hidden, self.A, max_rows=self.B, seed=init_seed)
+            self.actor.copy_params_from(self.policy)
+            self._vt_stats = torch.empty(4, dtype=torch.float64, device=dev)
 
     def sync_replicas(self, src=0):
         """Make every rank's parameters, Adam moments and step counter those of rank ``src``."""
@@ -389,6 +433,8 @@ class Trainer(_DeferredStats):
             self.policy.check_status()
         finally:
             self.policy.close()
+            if self.actor is not None:
+                self.actor.close()
 
     def _mask_bits(self):
         """Packed obs-side action mask (action_mask & location_mask[layer] & special_mask, slate.py:92-97)."""
@@ -398,6 +444,7 @@ class Trainer(_DeferredStats):
         B, T, R = self.B, self.T, self.R
         b = self.buf
         ppo = self.algo == D.DevicePolicy.PPO
+        actor = self.actor if self.actor is not None else self.policy          # IMPALA samples from the (possibly stale) actor
         for r in range(R):
             obs = self.env.reset()
             for t in range(T):
@@ -406,8 +453,8 @@ class Trainer(_DeferredStats):
                 # mask, sampled actions, log-probs, values (and PPO's logits) are written straight into the rollout buffers
                 mask = self.env.samples._live().obs_mask_bits(out=b['mask'][sl])
                 b['obs'][sl] = obs_t
-                a = self.policy.act(b['obs'][sl], mask, seed=self.seed, step=self._rollouts * T + t, want_logits=ppo,
-                                    out=(b['act'][sl], b['logp'][sl], b['val'][sl], b['logits'][sl] if ppo else None))[0]
+                a = actor.act(b['obs'][sl], mask, seed=self.seed, step=self._rollouts * T + t, want_logits=ppo,
+                              out=(b['act'][sl], b['logp'][sl], b['val'][sl], b['logits'][sl] if ppo else None))[0]
                 obs, reward, done, info = self.env.step(a)
                 b['rew'][sl] = reward
             self._rollouts += 1
@@ -426,6 +473,33 @@ class Trainer(_DeferredStats):
         N = self.R * self.B * self.T
         world = rdist.world_size()
         self.iteration += 1
+        if self.algo_name == 'IMPALA':
+            # V-trace needs neither the returns nor the actor's values: the learner re-evaluates every row
+            g, stats, vstats, _ = self.policy.vtrace_loss_grad(self.R, self.T, self.B, b['obs'], b['act'], b['logp'], b['rew'],
+                                                               mask_bits=b['mask'], gamma=1.0, clip_rho=self.vtrace_clip_rho,
+                                                               clip_pg_rho=self.vtrace_clip_pg_rho, drop_last=self.drop_last,
+                                                               vf_coeff=self.vf_coeff, ent_coeff=self.ent_coeff, grad_out=self.grad,
+                                                               stats_out=self._mb_stats, vtrace_stats_out=self._vt_stats)
+            if self.keep_last_batch:
+                self.last_batch = dict(obs=b['obs'].clone(), act=b['act'].clone(), mask=b['mask'].clone(), logp=b['logp'].clone(),
+                                       rew=b['rew'].clone())
+            rdist.allreduce_mean_(g)
+            self.policy.adam_step(g, lr=self.lr, grad_clip=self.grad_clip)
+            self.num_updates += 1
+            if self.num_updates % self.broadcast_interval == 0:
+                self.actor.copy_params_from(self.policy)            # device to device, in stream order behind the Adam step
+            kept = self.R * (self.T - 1 if self.drop_last else self.T) * self.B
+            return LazyStats(self, self._submit(mean_reward, torch.cat([stats.to(torch.float64), vstats]), 1,
+                                                dict(ppo=False, kl_mean=None, vtrace_rows=kept)))
+        if self.algo_name == 'PG':
+            # -mean(logp * return): the A2C kernels with the critic and the entropy term off and the 1 / N folded into the advantages
+            g, stats = self.policy.loss_grad(self.algo, b['obs'], b['act'], ret * (1.0 / N), ret, mask_bits=b['mask'],
+                                             vf_coeff=0.0, ent_coeff=0.0, grad_out=self.grad)
+            if self.keep_last_batch:
+                self.last_batch = dict(obs=b['obs'].clone(), act=b['act'].clone(), mask=b['mask'].clone(), adv=ret * (1.0 / N), ret=ret.clone())
+            rdist.allreduce_mean_(g)
+            self.policy.adam_step(g, lr=self.lr, grad_clip=0.0)
+            return LazyStats(self, self._submit(mean_reward, stats[:4], 1, dict(ppo=False, kl_mean=None)))
         if self.algo == D.DevicePolicy.A2C:
             g, stats = self.policy.loss_grad(self.algo, b['obs'], b['act'], adv, ret, mask_bits=b['mask'],
                                              vf_coeff=0.5, ent_coeff=0.01, grad_out=self.grad)
