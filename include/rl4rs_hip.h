@@ -1337,6 +1337,77 @@ int rl4rs_ope_step_stats(int32_t B, int32_t T, const double* step_rewards_dev, c
                          const double* behavior_prob_dev, const double* rhat_dev, const double* state_dev, double gamma,
                          double* stats_host, void* stream);
 
+/* ---- On-device Exact-K (rl4rs/nets/exact_k, script/exact_k_train.py): the pointer-network slate generator and its critic ----
+ *
+ * Generator: enc_user = relu(obs W + b) [hidden]; enc[n, a] = dropout(concat(enc_user[n], item_table[a] * sqrt(hidden))) over the
+ * ONE shared candidate list 0..action_size-1 (both reference scripts feed the identity list; only the first action_size table rows
+ * are used and trained); `blocks` blocks of multi-head self-attention (relu Q / K / V, key and query masking on an exactly-zero row
+ * sum, dropout on the probabilities, residual, layer norm with population variance and eps 1e-8 under the root) + feed-forward
+ * (D -> 4 hidden relu -> D, residual, layer norm), D = 2 hidden; TF LSTMCell(D) pointer decoder with trainable initial state and
+ * first input, intra-attention over the earlier cell outputs, one glimpse over all candidates and the pointer scores; candidates
+ * outside the allowed set of step t get -2^32 + 1:  allowed = not yet picked, in location_mask[t / 3], and no special item once a
+ * special item has been picked (the env's own action mask).  Slate length 9.
+ *
+ * Flat parameter layout (float32):
+ *   user W [obs_dim, H], b [H] | item table [vocab, H] |
+ *   per block: Wq [D, D], bq, Wk, bk, Wv, bv | ln1 gamma, beta | W1 [D, 4H], b1 | W2 [4H, D], b2 | ln2 gamma, beta |
+ *   LSTM kernel [2D, 4D] (gates i, j, f, o), bias [4D] | init c [D], init h [D], first input [D] |
+ *   intra: W_b [D, D], v_dec [D], W_bef [D, D], bias_dec [D] |
+ *   glimpse: W_q [D, D], W_dec [D, D], v [D], bias [D], W_ref [D, D] | pointer: the same five.
+ *
+ * Dropout keep masks are a pure function of the policy net's counter RNG: an element is kept when
+ *   uniform01(seed, step, row, site * 65536 + col) >= rate   and then scaled by 1 / (1 - rate),
+ * site = 32 * pass + 0 for enc (row = n * A + a, col = feature) and 32 * pass + 1 + block for the attention probabilities
+ * (row = (n * heads + head) * A + query, col = key); pass = 0 in rl4rs_exactk_loss_grad and 1 in rl4rs_exactk_decode, so a rollout
+ * and the update draw different masks from the same (seed, step).  Dropout is on in every call, greedy decoding included (the
+ * reference builds its generator with is_training = True for its eval stage too).
+ *
+ * Refused by rl4rs_exactk_create (and rl4rs_exactk_param_count = -1), before a device is looked for: hidden not a multiple of 16,
+ * a head width D / heads that is not a multiple of 8, action_size > vocab, a max_rows whose [max_rows * action_size, 4 hidden] fp32
+ * activations (or, for small action_size, the decoder's [9 * max_rows, 8 hidden] gates) reach 2^31 bytes, shapes whose kernels need more than 160 KiB of LDS, and a location mask with fewer than 9 allowed
+ * non-special items (9 keep every position's allowed set non-empty). */
+typedef struct rl4rs_exactk rl4rs_exactk;
+typedef struct rl4rs_exactk_critic rl4rs_exactk_critic;
+typedef struct rl4rs_exactk_cfg {
+    int32_t obs_dim, hidden /* H */, heads, blocks, action_size /* A */, vocab, max_rows;
+    float dropout_rate;
+} rl4rs_exactk_cfg;
+int64_t rl4rs_exactk_param_count(const rl4rs_exactk_cfg* cfg);
+/* location_mask_host uint8 [3, A], is_special_host uint8 [A] */
+int rl4rs_exactk_create(const rl4rs_exactk_cfg* cfg, const float* params_host, const uint8_t* location_mask_host,
+                        const uint8_t* is_special_host, void* stream, rl4rs_exactk** out);
+int rl4rs_exactk_destroy(rl4rs_exactk* net);
+int rl4rs_exactk_params(rl4rs_exactk* net, float** params_dev, float** grad_dev, int64_t* count);
+int rl4rs_exactk_adam_state(rl4rs_exactk* net, float** m_dev, float** v_dev, int64_t* step);
+int rl4rs_exactk_set_adam_step(rl4rs_exactk* net, int64_t step);
+/* A slate per row from obs_dev [N, obs_dim] -> path_dev int32 [N, 9] (candidate indices).  greedy = 0: one inverse-CDF draw per
+ * step from softmax(logits): the smallest allowed a whose inclusive prefix sum of exp(logit - max), in candidate order, exceeds
+ * u * total, u = uniform01(seed, step, row, t); greedy = 1: the first maximum.  logits_out_dev [N, 9, A] optional. */
+int rl4rs_exactk_decode(rl4rs_exactk* net, int32_t N, const float* obs_dev, int32_t greedy, uint32_t seed, uint32_t step,
+                        int32_t* path_dev, float* logits_out_dev, void* stream);
+/* Teacher-forced forward along path_dev [N, 9], loss = mean_n(w_n * sum_t CE(logits[n, t], path[n, t])) and its full gradient into
+ * the handle's flat gradient buffer (bit-identical between identical calls).  loss_dev float[2] = {loss, number of (row, step)
+ * targets outside the allowed set (such a path is the caller's error; indices are clamped into range)}. */
+int rl4rs_exactk_loss_grad(rl4rs_exactk* net, int32_t N, const float* obs_dev, const int32_t* path_dev, const float* weights_dev,
+                           uint32_t seed, uint32_t step, float* logits_out_dev, float* loss_dev, void* stream);
+/* Adam in tf.train.AdamOptimizer's form on the handle's gradient.  skip_dev (optional) int32[1] on the device: non-zero = leave
+ * parameters and moments alone (the step counter still advances). */
+int rl4rs_exactk_adam_step(rl4rs_exactk* net, float lr, float beta1, float beta2, float eps, const int32_t* skip_dev, void* stream);
+/* Critic (the reference's Discriminator): obs -> hidden relu -> hidden relu -> hidden relu -> 1; flat layout W1, b1, W2, b2, W3, b3,
+ * W4 [hidden, 1], b4.  loss_grad: the gradient of the SUM over rows of (value - target)^2 (TF's minimize of a vector loss);
+ * value_out_dev [N] (the values BEFORE any update) and err_out_dev [N] (squared errors) are optional. */
+int64_t rl4rs_exactk_critic_param_count(int32_t obs_dim, int32_t hidden);
+int rl4rs_exactk_critic_create(int32_t obs_dim, int32_t hidden, int32_t max_rows, const float* params_host, void* stream,
+                               rl4rs_exactk_critic** out);
+int rl4rs_exactk_critic_destroy(rl4rs_exactk_critic* net);
+int rl4rs_exactk_critic_params(rl4rs_exactk_critic* net, float** params_dev, float** grad_dev, int64_t* count);
+int rl4rs_exactk_critic_adam_state(rl4rs_exactk_critic* net, float** m_dev, float** v_dev, int64_t* step);
+int rl4rs_exactk_critic_set_adam_step(rl4rs_exactk_critic* net, int64_t step);
+int rl4rs_exactk_critic_forward(rl4rs_exactk_critic* net, int32_t N, const float* obs_dev, float* value_dev, void* stream);
+int rl4rs_exactk_critic_loss_grad(rl4rs_exactk_critic* net, int32_t N, const float* obs_dev, const float* target_dev,
+                                  float* value_out_dev, float* err_out_dev, void* stream);
+int rl4rs_exactk_critic_adam_step(rl4rs_exactk_critic* net, float lr, float beta1, float beta2, float eps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

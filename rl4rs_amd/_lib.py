@@ -87,6 +87,12 @@ class DistqCfg(C.Structure):
                 [('v_min', C.c_float), ('v_max', C.c_float), ('max_rows', C.c_int32)])
 
 
+class ExactKCfg(C.Structure):
+    """rl4rs_exactk_cfg (include/rl4rs_hip.h)"""
+    _fields_ = ([(n, C.c_int32) for n in ('obs_dim', 'hidden', 'heads', 'blocks', 'action_size', 'vocab', 'max_rows')] +
+                [('dropout_rate', C.c_float)])
+
+
 class BcqStep(C.Structure):
     """rl4rs_bcq_step (include/rl4rs_hip.h)"""
     _fields_ = ([(n, C.c_void_p) for n in ('imit_enc', 'imit_dec', 'policy', 'policy_targ', 'q1', 'q2', 'q1_targ', 'q2_targ')] +
@@ -350,6 +356,24 @@ SIGNATURES = {
     'rl4rs_vtrace': (_I, [_I32, _I32, _P, _P, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float, _P, _P, _P, _P]),
     'rl4rs_policy_vtrace_loss_grad': (_I, [_P, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float, _I32, C.c_float,
                                            C.c_float, _P, _P, _P, _P, _P, _P]),
+    'rl4rs_exactk_param_count': (_I64, [C.POINTER(ExactKCfg)]),
+    'rl4rs_exactk_create': (_I, [C.POINTER(ExactKCfg), _P, _P, _P, _P, C.POINTER(_P)]),
+    'rl4rs_exactk_destroy': (_I, [_P]),
+    'rl4rs_exactk_params': (_I, [_P, _P, _P, _P]),
+    'rl4rs_exactk_adam_state': (_I, [_P, _P, _P, _P]),
+    'rl4rs_exactk_set_adam_step': (_I, [_P, _I64]),
+    'rl4rs_exactk_decode': (_I, [_P, _I32, _P, _I32, C.c_uint32, C.c_uint32, _P, _P, _P]),
+    'rl4rs_exactk_loss_grad': (_I, [_P, _I32, _P, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P]),
+    'rl4rs_exactk_adam_step': (_I, [_P, C.c_float, C.c_float, C.c_float, C.c_float, _P, _P]),
+    'rl4rs_exactk_critic_param_count': (_I64, [_I32, _I32]),
+    'rl4rs_exactk_critic_create': (_I, [_I32, _I32, _I32, _P, _P, C.POINTER(_P)]),
+    'rl4rs_exactk_critic_destroy': (_I, [_P]),
+    'rl4rs_exactk_critic_params': (_I, [_P, _P, _P, _P]),
+    'rl4rs_exactk_critic_adam_state': (_I, [_P, _P, _P, _P]),
+    'rl4rs_exactk_critic_set_adam_step': (_I, [_P, _I64]),
+    'rl4rs_exactk_critic_forward': (_I, [_P, _I32, _P, _P, _P]),
+    'rl4rs_exactk_critic_loss_grad': (_I, [_P, _I32, _P, _P, _P, _P, _P]),
+    'rl4rs_exactk_critic_adam_step': (_I, [_P, C.c_float, C.c_float, C.c_float, C.c_float, _P]),
 }
 
 # include/rl4rs_hip.h RL4RS_REPLAY_BUF_*

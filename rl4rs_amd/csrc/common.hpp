@@ -47,6 +47,21 @@ inline int dev_alloc(T** p, size_t n) {
     return RL4RS_OK;
 }
 
+// The library's counter RNG (policy.hip's sampling, the trainers' dropout and noise, exactk.hip): one definition for every unit.
+__device__ __forceinline__ uint32_t mix32(uint32_t x) {
+    x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
+    return x;
+}
+// counter-based uniform STRICTLY inside (0,1): a pure function of (seed, step, row, action).  23 random bits + 0.5 is exactly
+// representable in fp32, so the largest value is 1 - 2^-24; with 24 bits the top value rounded to 1.0f, and the Gumbel draw
+// logit - log(-log(u)) became +inf - which let a MASKED action (logit -3.4e38) win about once per 2^24 draws
+// (tests/test_gpu_policy.py::test_wider_hidden_layer_takes_the_same_paths caught it).
+__device__ __forceinline__ float uniform01(uint32_t seed, uint32_t step, uint32_t row, uint32_t a) {
+    uint32_t h = mix32(seed ^ mix32(step * 0x9E3779B9U + 0x85EBCA6BU) ^ mix32(row * 0xC2B2AE35U + a * 0x27D4EB2FU + 1U));
+    h = mix32(h + a);
+    return ((float)(h >> 9) + 0.5f) * (1.0f / 8388608.0f);
+}
+
 inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
 // activation codes of the GEMM epilogues (the `act` argument of rl4rs_gemm_f32 in include/rl4rs_hip.h)
@@ -66,6 +81,11 @@ int launch_gemm_small(const float* a, int64_t lda, const float* w, int64_t ldw, 
 // dX [M, Kin] = dY [M, Nout] W[Kin, Nout]^T, zeroed where relu_of [M, Kin] (optional: the layer's forward output) is not > 0
 int launch_gemm_nt(const float* dy, int64_t ldy, const float* w, int64_t ldw, float* dx, int64_t ldx, int M, int Kin, int Nout,
                    hipStream_t st, const float* relu_of = nullptr, int64_t ldr = 0);
+
+// dW [M, Nc] = A^T B over the Ns rows of A [Ns, lda] and B [Ns, ldb], db [Nc] (optional) = column sums of B: the trainers'
+// weight-gradient reduction (policy.hip), chunk partials summed in a fixed order.  part / part_b: ceil(Ns / chunk) * M * Nc / * Nc floats.
+int launch_gemm_tn(const float* A, int lda, int M, const float* B, int ldb, int Nc, int Ns, int chunk, float* part, float* part_b,
+                   float* dW, float* db, hipStream_t st);
 
 // GEMM against a weight matrix pre-packed by pack_gemm_weight (gemm.hip); C = act(A W + bias + addend) with an optional
 // row-major addend [M, ldadd]

@@ -26,19 +26,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct PolDims { int OD, HID, A, AE, W; };   // AE = A + 1 (logits | value), W = mask words
 
-__device__ __forceinline__ uint32_t mix32(uint32_t x) {
-    x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
-    return x;
-}
-// counter-based uniform STRICTLY inside (0,1): a pure function of (seed, step, row, action).  23 random bits + 0.5 is exactly
-// representable in fp32, so the largest value is 1 - 2^-24; with 24 bits the top value rounded to 1.0f, and the Gumbel draw
-// logit - log(-log(u)) became +inf - which let a MASKED action (logit -3.4e38) win about once per 2^24 draws
-// (tests/test_gpu_policy.py::test_wider_hidden_layer_takes_the_same_paths caught it).
-__device__ __forceinline__ float uniform01(uint32_t seed, uint32_t step, uint32_t row, uint32_t a) {
-    uint32_t h = mix32(seed ^ mix32(step * 0x9E3779B9U + 0x85EBCA6BU) ^ mix32(row * 0xC2B2AE35U + a * 0x27D4EB2FU + 1U));
-    h = mix32(h + a);
-    return ((float)(h >> 9) + 0.5f) * (1.0f / 8388608.0f);
-}
+// (mix32 / uniform01, the library's counter RNG, live in common.hpp: exactk.hip draws from the same function)
 
 // Wave-wide reductions, result in every lane.  DPP row operations (quad_perm, row_half_mirror, row_mirror) reduce each row of
 // 16 lanes in 4 steps of a few cycles, the four row results meet through v_readlane: ~10x less latency than the six dependent
@@ -662,6 +650,24 @@ __global__ __launch_bounds__(256) void k_reduce_chunks4(const float* __restrict_
     sm[w][l] = s;
     __syncthreads();
     if (w == 0 && i < count) dst[i] = ((sm[0][l] + sm[1][l]) + sm[2][l]) + sm[3][l];
+}
+
+// dW [M, Nc] = A^T B over Ns samples (db [Nc]: the column sums of B, optional) for the other translation units (exactk.hip):
+// k_gemm_tn over chunks of `chunk` samples, the chunk partials summed in chunk order.  part / part_b: scratch of
+// ceil(Ns / chunk) * M * Nc / * Nc floats.
+int launch_gemm_tn(const float* A, int lda, int M, const float* B, int ldb, int Nc, int Ns, int chunk, float* part, float* part_b,
+                   float* dW, float* db, hipStream_t st) {
+    if (M <= 0 || Nc <= 0 || Ns <= 0 || chunk <= 0) return RL4RS_OK;
+    const int nz = (Ns + chunk - 1) / chunk;
+    const int tiles = ((M + 31) / 32) * ((Nc + 31) / 32);
+    hipLaunchKernelGGL(k_gemm_tn, dim3((tiles + 3) / 4, nz), dim3(256), 0, st, A, lda, M, B, ldb, Nc, Ns, chunk, nz == 1 ? dW : part,
+                       db ? (nz == 1 ? db : part_b) : (float*)nullptr);
+    if (nz > 1) {
+        hipLaunchKernelGGL(k_reduce_chunks, dim3((M * Nc + 255) / 256), dim3(256), 0, st, part, M * Nc, nz, dW);
+        if (db) hipLaunchKernelGGL(k_reduce_chunks, dim3((Nc + 255) / 256), dim3(256), 0, st, part_b, Nc, nz, db);
+    }
+    RL4RS_LAUNCH_CHECK();
+    return RL4RS_OK;
 }
 
 // stats[0..3] = sum over samples of {pi_loss, vf_loss, entropy, kl}; single block, fixed order

@@ -2329,3 +2329,188 @@ def tanh_head_grad(tanh_out, d_out):
 def amlp_add_l2(net, l2):
     """grad += l2 * W on the three weight matrices of ``net``'s gradient (biases untouched)."""
     check(_lib.load().rl4rs_amlp_add_l2(net.h, float(l2), _stream()))
+
+
+class _FlatNet(object):
+    """Shared plumbing of the rl4rs_exactk / rl4rs_exactk_critic handles: flat parameters, gradient and Adam state."""
+    _prefix = None
+
+    def _call(self, name):
+        return getattr(self.lib, self._prefix + name)
+
+    def close(self):
+        if getattr(self, 'h', None) is not None and self.h:
+            self._call('destroy')(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _ptrs(self):
+        p, g, n = C.c_void_p(), C.c_void_p(), C.c_int64()
+        check(self._call('params')(self.h, C.byref(p), C.byref(g), C.byref(n)))
+        return p, g, n.value
+
+    def _copy_out(self, src, n, out):
+        if out is None:
+            out = torch.empty(n, dtype=torch.float32, device=self.device)
+        assert out.dtype == torch.float32 and out.numel() == n and out.is_contiguous() and out.is_cuda
+        check(self.lib.rl4rs_copy_d2d(_ptr(out), src, n * 4, _stream()))
+        return out
+
+    def params(self, out=None):
+        """Copy of the flat parameter buffer (device tensor)."""
+        p, _, n = self._ptrs()
+        return self._copy_out(p, n, out)
+
+    def grad(self, out=None):
+        """Copy of the flat gradient of the last loss_grad (device tensor)."""
+        _, g, n = self._ptrs()
+        return self._copy_out(g, n, out)
+
+    def set_params(self, flat):
+        p, _, n = self._ptrs()
+        flat = flat.to(device=self.device, dtype=torch.float32).contiguous()
+        assert flat.numel() == n
+        check(self.lib.rl4rs_copy_d2d(p, _ptr(flat), n * 4, _stream()))
+        self._keep = flat
+
+    def adam_state(self):
+        """(m, v, step): copies of the Adam moments (device tensors) and the step counter - what a checkpoint keeps."""
+        m, v, t = C.c_void_p(), C.c_void_p(), C.c_int64()
+        check(self._call('adam_state')(self.h, C.byref(m), C.byref(v), C.byref(t)))
+        return self._copy_out(m, self.n_params, None), self._copy_out(v, self.n_params, None), int(t.value)
+
+    def set_adam_state(self, m, v, step):
+        pm, pv, t = C.c_void_p(), C.c_void_p(), C.c_int64()
+        check(self._call('adam_state')(self.h, C.byref(pm), C.byref(pv), C.byref(t)))
+        for dst, src in ((pm, m), (pv, v)):
+            src = src.to(device=self.device, dtype=torch.float32).contiguous()
+            assert src.numel() == self.n_params
+            check(self.lib.rl4rs_copy_d2d(dst, _ptr(src), self.n_params * 4, _stream()))
+            wait_stream()
+        check(self._call('set_adam_step')(self.h, int(step)))
+
+
+class DeviceExactK(_FlatNet):
+    """rl4rs_exactk handle: Exact-K's pointer-network slate generator (include/rl4rs_hip.h, "On-device Exact-K"; flat layout in
+    ``rl4rs_amd/nets/exactk.py``).  One shared candidate list 0..action_size-1.  Dropout is on in every call, as in the reference,
+    whose eval stage also builds the generator with is_training=True.  TF parity is unpinned (TensorFlow 1.15 is absent).
+    ``location_mask`` [3, A] and ``is_special`` [A]: ``CatalogTables.location_mask[:3]`` / ``.is_special``."""
+    _prefix = 'rl4rs_exactk_'
+    SLATE = 9
+
+    def __init__(self, location_mask, is_special, max_rows, obs_dim=256, action_size=284, hidden_units=64, num_heads=4, num_blocks=2,
+                 vocab=500, dropout_rate=0.1, params=None, seed=0, device=None):
+        self.lib = _lib.load()
+        self.obs_dim, self.action_size, self.hidden, self.heads, self.blocks = (int(obs_dim), int(action_size), int(hidden_units),
+                                                                                 int(num_heads), int(num_blocks))
+        self.vocab, self.max_rows, self.dropout_rate = int(vocab), int(max_rows), float(dropout_rate)
+        self.cfg = _lib.ExactKCfg(self.obs_dim, self.hidden, self.heads, self.blocks, self.action_size, self.vocab, self.max_rows,
+                                  self.dropout_rate)
+        loc = np.ascontiguousarray(np.asarray(location_mask)[:3] >= 0.5, dtype=np.uint8)
+        spc = np.ascontiguousarray(np.asarray(is_special) != 0, dtype=np.uint8)
+        if loc.shape != (3, self.action_size) or spc.shape != (self.action_size,):
+            raise ValueError('location_mask must be [3, action_size] and is_special [action_size]')
+        n = self.lib.rl4rs_exactk_param_count(C.byref(self.cfg))
+        if n < 0:
+            raise _lib.Rl4rsHipError(self.lib.rl4rs_last_error().decode())
+        self.n_params = int(n)
+        if params is None:
+            from .nets.exactk import init_exactk_params
+            params = init_exactk_params(self.obs_dim, self.hidden, self.blocks, self.vocab, seed)
+        params = np.ascontiguousarray(params, dtype=np.float32)
+        assert params.shape == (self.n_params,), (params.shape, self.n_params)
+        self.device = None
+        h = C.c_void_p()
+        if torch.cuda.is_available():
+            self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+            with torch.cuda.device(self.device):
+                check(self.lib.rl4rs_exactk_create(C.byref(self.cfg), params.ctypes.data_as(C.c_void_p), loc.ctypes.data_as(C.c_void_p),
+                                                   spc.ctypes.data_as(C.c_void_p), _stream(), C.byref(h)))
+        else:       # the shape and mask refusals come first; with neither a refusal nor a device this raises "no HIP device"
+            check(self.lib.rl4rs_exactk_create(C.byref(self.cfg), params.ctypes.data_as(C.c_void_p), loc.ctypes.data_as(C.c_void_p),
+                                               spc.ctypes.data_as(C.c_void_p), None, C.byref(h)))
+        self.h = h
+
+    def _obs(self, obs):
+        N = obs.shape[0]
+        assert obs.dtype == torch.float32 and obs.shape == (N, self.obs_dim) and obs.is_contiguous() and obs.is_cuda
+        assert 1 <= N <= self.max_rows, (N, self.max_rows)
+        return N
+
+    def decode(self, obs, greedy=False, seed=0, step=0, want_logits=False, out=None):
+        """A slate per row -> (path int32 [N, 9], logits [N, 9, A] or None): an inverse-CDF draw per step at
+        u = uniform01(seed, step, row, t), or the first maximum (greedy)."""
+        N = self._obs(obs)
+        path = out if out is not None else torch.empty((N, self.SLATE), dtype=torch.int32, device=self.device)
+        assert path.dtype == torch.int32 and path.shape == (N, self.SLATE) and path.is_contiguous()
+        lg = torch.empty((N, self.SLATE, self.action_size), dtype=torch.float32, device=self.device) if want_logits else None
+        check(self.lib.rl4rs_exactk_decode(self.h, N, _ptr(obs), 1 if greedy else 0, seed & 0xffffffff, step & 0xffffffff, _ptr(path),
+                                           _ptr(lg), _stream()))
+        return path, lg
+
+    def loss_grad(self, obs, path, weights, seed=0, step=0, want_logits=False):
+        """Teacher-forced loss mean_n(w_n sum_t CE) and its gradient into the handle's buffer (``grad()``)
+        -> (stats float32[2] = {loss, targets outside the allowed set}, logits [N, 9, A] or None)."""
+        N = self._obs(obs)
+        assert path.dtype == torch.int32 and path.shape == (N, self.SLATE) and path.is_contiguous()
+        assert weights.dtype == torch.float32 and weights.shape == (N,) and weights.is_contiguous()
+        lg = torch.empty((N, self.SLATE, self.action_size), dtype=torch.float32, device=self.device) if want_logits else None
+        stats = torch.empty(2, dtype=torch.float32, device=self.device)
+        check(self.lib.rl4rs_exactk_loss_grad(self.h, N, _ptr(obs), _ptr(path), _ptr(weights), seed & 0xffffffff, step & 0xffffffff,
+                                              _ptr(lg), _ptr(stats), _stream()))
+        return stats, lg
+
+    def adam_step(self, lr=1e-3, beta1=0.9, beta2=0.98, eps=1e-8, skip=None):
+        """tf.train.AdamOptimizer step on the last gradient; ``skip``: int32[1] device tensor, non-zero = leave everything alone."""
+        assert skip is None or (skip.dtype == torch.int32 and skip.numel() == 1 and skip.is_cuda)
+        check(self.lib.rl4rs_exactk_adam_step(self.h, lr, beta1, beta2, eps, _ptr(skip), _stream()))
+
+
+class DeviceExactKCritic(_FlatNet):
+    """rl4rs_exactk_critic handle: the reference's Discriminator, obs -> 128 relu x 3 -> 1, the REINFORCE baseline of Exact-K."""
+    _prefix = 'rl4rs_exactk_critic_'
+
+    def __init__(self, max_rows, obs_dim=256, hidden=128, params=None, seed=0, device=None):
+        _lib.require_device()
+        self.lib = _lib.load()
+        self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        self.obs_dim, self.hidden, self.max_rows = int(obs_dim), int(hidden), int(max_rows)
+        self.n_params = int(self.lib.rl4rs_exactk_critic_param_count(self.obs_dim, self.hidden))
+        if params is None:
+            from .nets.exactk import init_critic_params
+            params = init_critic_params(self.obs_dim, self.hidden, seed)
+        params = np.ascontiguousarray(params, dtype=np.float32)
+        assert params.shape == (self.n_params,), (params.shape, self.n_params)
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            check(self.lib.rl4rs_exactk_critic_create(self.obs_dim, self.hidden, self.max_rows, params.ctypes.data_as(C.c_void_p),
+                                                      _stream(), C.byref(h)))
+        self.h = h
+
+    def _obs(self, obs):
+        N = obs.shape[0]
+        assert obs.dtype == torch.float32 and obs.shape == (N, self.obs_dim) and obs.is_contiguous() and 1 <= N <= self.max_rows
+        return N
+
+    def forward(self, obs, out=None):
+        N = self._obs(obs)
+        v = out if out is not None else torch.empty(N, dtype=torch.float32, device=self.device)
+        check(self.lib.rl4rs_exactk_critic_forward(self.h, N, _ptr(obs), _ptr(v), _stream()))
+        return v
+
+    def loss_grad(self, obs, target):
+        """Gradient of sum_n (value_n - target_n)^2 into the handle's buffer -> (value [N] before any update, squared errors [N])."""
+        N = self._obs(obs)
+        assert target.dtype == torch.float32 and target.shape == (N,) and target.is_contiguous()
+        v = torch.empty(N, dtype=torch.float32, device=self.device)
+        err = torch.empty(N, dtype=torch.float32, device=self.device)
+        check(self.lib.rl4rs_exactk_critic_loss_grad(self.h, N, _ptr(obs), _ptr(target), _ptr(v), _ptr(err), _stream()))
+        return v, err
+
+    def adam_step(self, lr=5e-3, beta1=0.9, beta2=0.98, eps=1e-8):
+        check(self.lib.rl4rs_exactk_critic_adam_step(self.h, lr, beta1, beta2, eps, _stream()))

@@ -1161,3 +1161,169 @@ class TD3Trainer(_DeferredStats):
         finally:
             np.random.set_state(state)
         return float(total.item()) / n
+
+
+class ExactKTrainer(_DeferredStats):
+    """Exact-K (script/exact_k_train.py, rl4rs/nets/exact_k) over the zero-copy discrete ``SlateRecEnv-v0`` (T = 9): the pointer-network
+    generator emits the whole 9-item slate from the first observation, REINFORCE with the critic's prediction of the batch reward as
+    baseline and a hill climb over ``samples`` sampled slates per user.  Defaults are the reference's: hidden_units 64, 4 heads,
+    2 blocks, dropout 0.1 (on in every pass, greedy evaluation included: the reference builds its generator with is_training=True
+    for its eval stage too), Adam lr 1e-3 (generator) / 5e-3 (critic) with beta2 0.98.  TF parity is unpinned (TensorFlow 1.15 is
+    absent).
+
+    One ``train_iteration`` is the reference's episode (exact_k_train.py:72-114): reset and keep obs0; per climb decode a sampled
+    slate from obs0, play its 9 actions and keep the last step's reward (the episode reward on this env); per row keep the climb with
+    the larger reward (ties: the first); baseline = critic(obs0) BEFORE the critic's update toward the kept reward; advantage =
+    (reward - baseline) / its population std; generator update with w = advantage on the kept paths.
+
+    Deviations: (1) ``same_users=True`` (default) replays the SAME batch of users for every climb (the record cursor and the global
+    numpy RNG state are saved before the first reset and restored before the later ones).  The reference calls env.reset() between
+    its two climbs and keeps the old observation, so its second slate is scored on different users than it was generated for;
+    ``same_users=False`` is the reference as written.  (2) A batch whose advantage has zero or non-finite std skips the generator
+    update (the reference would divide by zero); the decision is a device flag that gates the Adam step, counted in the statistics
+    (``skipped``, ``skipped_total``)."""
+
+    def __init__(self, env, seed=0, init_seed=0, lr=1e-3, critic_lr=5e-3, dropout_rate=0.1, samples=2, same_users=True, hidden_units=64,
+                 num_heads=4, num_blocks=2, vocab=500, critic_hidden=128, temperature=1, num_glimpse=1, num_layers=1, use_mha=True):
+        cfg = env.config
+        if getattr(getattr(env, 'samples', None), 'is_seq', False) or cfg['max_steps'] != D.DeviceExactK.SLATE:
+            raise ValueError("ExactKTrainer runs SlateRecEnv-v0 (max_steps 9) only: on SeqSlateRecEnv-v0 the reference script indexes its "
+                             "9-wide slate with 36 steps and cannot run either")
+        if not cfg.get('return_tensors', False) or cfg.get('support_conti_env', False):
+            raise ValueError("ExactKTrainer needs the zero-copy discrete-action env (config['return_tensors'] = True, no conti env)")
+        for name, val, want in (('temperature', temperature, 1), ('num_glimpse', num_glimpse, 1), ('num_layers', num_layers, 1),
+                                ('use_mha', bool(use_mha), True)):
+            if val != want:
+                raise ValueError('ExactKTrainer implements %s = %r (the reference default); got %r' % (name, want, val))
+        if int(samples) < 1:
+            raise ValueError('samples must be >= 1')
+        if rdist.collectives_active():
+            raise RuntimeError('ExactKTrainer is single-process: data-parallel training is out of scope')
+        self.env = env
+        self.B, self.T, self.A = cfg['batch_size'], cfg['max_steps'], cfg['action_size']
+        self.seed, self.lr, self.critic_lr = seed, float(lr), float(critic_lr)
+        self.samples, self.same_users = int(samples), bool(same_users)
+        self._pending = []
+        self._kl_coeff, self.kl_target = 0.0, 0.0            # (unused: the deferred-statistics base carries PPO's)
+        space = env.observation_space
+        space = space.spaces['obs'] if hasattr(space, 'spaces') else space
+        self.OD = int(space.shape[0])
+        catalog = env.samples._catalog
+        self.policy = D.DeviceExactK(catalog.location_mask[:3], catalog.is_special, max_rows=self.B, obs_dim=self.OD, action_size=self.A,
+                                     hidden_units=hidden_units, num_heads=num_heads, num_blocks=num_blocks, vocab=max(vocab, self.A),
+                                     dropout_rate=dropout_rate, seed=init_seed)
+        self.critic = D.DeviceExactKCritic(self.B, obs_dim=self.OD, hidden=critic_hidden, seed=init_seed + 1, device=self.policy.device)
+        self.iteration = 0
+        self._decodes = 0
+        self.skipped_total = 0
+        self.last = None                   # the last iteration (tests): rewards [samples, B], paths, the kept ones, every climb's env state
+
+    def params(self):
+        self._settle()
+        return self.policy.params()
+
+    def close(self):
+        try:
+            self._settle()
+        finally:
+            self.policy.close()
+            self.critic.close()
+
+    def _obs(self, obs):
+        obs = obs['obs'] if isinstance(obs, dict) else obs
+        return obs.to(torch.float32).contiguous()
+
+    def _play(self, path):
+        """The 9 actions of every row's slate -> the last step's reward [B] float32."""
+        cols = path.t().contiguous()
+        reward = None
+        for t in range(self.T):
+            _, reward, _, _ = self.env.step(cols[t])
+        return reward.to(torch.float32).reshape(-1)
+
+    @staticmethod
+    def select_best(rewards, paths):
+        """Per row the climb with the larger reward, ties to the first: rewards [S, B], paths [S, B, 9] -> (reward [B], path [B, 9])."""
+        best_r, best_p = rewards[0], paths[0]
+        for s in range(1, rewards.shape[0]):
+            better = rewards[s] > best_r
+            best_r = torch.where(better, rewards[s], best_r)
+            best_p = torch.where(better[:, None], paths[s], best_p)
+        return best_r.contiguous(), best_p.contiguous()
+
+    @staticmethod
+    def normalise_advantage(reward, baseline):
+        """(reward - baseline) / its population std -> (w [B] float32, skip int32 [1]): skip = 1 (and w = 0) when the std is 0 or not
+        finite.  Device tensors in, device tensors out, nothing waits."""
+        adv = reward - baseline
+        sd = adv.std(unbiased=False)
+        bad = ~torch.isfinite(sd) | (sd == 0)
+        w = torch.where(bad, torch.zeros_like(adv), adv / torch.where(bad, torch.ones_like(sd), sd))
+        return w.to(torch.float32).contiguous(), bad.to(torch.int32).reshape(1)
+
+    def train_iteration(self):
+        """One episode of the reference's loop.  Returns a ``LazyStats`` mapping (episode_reward_mean of the kept slates,
+        reward_first_climb, baseline_mean, critic_loss, policy_loss, invalid_targets, skipped, skipped_total, iteration); nothing here
+        waits for the GPU."""
+        data = self.env.sim._recData
+        saved = (data._cursor, np.random.get_state()) if self.same_users else None
+        obs0 = self._obs(self.env.reset()).clone()
+        rewards, paths, states = [], [], []
+        for s in range(self.samples):
+            if s > 0 and self.same_users:
+                data._cursor = saved[0]
+                np.random.set_state(saved[1])
+                self.env.reset()
+            path, _ = self.policy.decode(obs0, greedy=False, seed=self.seed, step=self._decodes)
+            self._decodes += 1
+            states.append(self.env.samples)        # (its .user is read lazily on the host: tests only)
+            rewards.append(self._play(path))
+            paths.append(path)
+            if not self.same_users:
+                self.env.reset()                   # exact_k_train.py:85: the next climb (and nothing else) sees this batch
+        self._settle()
+        rewards, paths = torch.stack(rewards), torch.stack(paths)
+        reward, path = self.select_best(rewards, paths)
+        baseline, err = self.critic.loss_grad(obs0, reward)
+        self.critic.adam_step(lr=self.critic_lr)
+        w, skip = self.normalise_advantage(reward, baseline)
+        stats, _ = self.policy.loss_grad(obs0, path, w, seed=self.seed, step=self.iteration)
+        self.policy.adam_step(lr=self.lr, skip=skip)
+        self.iteration += 1
+        self.last = dict(rewards=rewards, paths=paths, reward=reward, path=path, baseline=baseline, weights=w, states=states, obs0=obs0)
+        vec = torch.stack([rewards[0].mean(), baseline.mean(), err.mean(), stats[0], stats[1], skip[0].to(torch.float32)])
+        return LazyStats(self, self._submit(reward.mean(), vec, 1, {}))
+
+    def _status_word(self, dev):
+        return torch.zeros(1, dtype=torch.float64, device=dev)
+
+    def _settle(self):
+        while self._pending:
+            tok = self._pending.pop(0)
+            tok['ev'].synchronize()
+            v = tok['pin'].numpy().copy()
+            if v[-1] >= 1000.0:
+                raise RuntimeError(rdist.ROW_OVERFLOW_MESSAGE)
+            s = v[1:-1]
+            self.skipped_total += int(s[5] != 0)
+            tok['values'] = {'episode_reward_mean': float(v[0]), 'reward_first_climb': float(s[0]), 'baseline_mean': float(s[1]),
+                             'critic_loss': float(s[2]), 'policy_loss': float(s[3]), 'invalid_targets': int(s[4]),
+                             'skipped': int(s[5] != 0), 'skipped_total': self.skipped_total, 'iteration': tok['iteration']}
+
+    def evaluate(self, episodes=None, seed=0):
+        """Mean episode reward of greedy slates: ceil(episodes / B) batches from the start of the record file with the env's record
+        sampling seeded by ``seed``; dropout stays on (as in the reference's eval stage) with a fixed mask stream, so two calls on the
+        same parameters give the same number.  Leaves the global numpy RNG as it found it; the env's record cursor restarts."""
+        self._settle()
+        n = 1 if episodes is None else max(1, int(math.ceil(float(episodes) / self.B)))
+        state = np.random.get_state()
+        try:
+            np.random.seed(seed)
+            total = torch.zeros((), dtype=torch.float64, device=self.policy.device)
+            for k in range(n):
+                obs0 = self._obs(self.env.reset(reset_file=True) if k == 0 else self.env.reset())
+                path, _ = self.policy.decode(obs0, greedy=True, seed=self.seed, step=k)
+                total += self._play(path).to(torch.float64).mean()
+        finally:
+            np.random.set_state(state)
+        return float(total.item()) / n
