@@ -251,7 +251,14 @@ typedef struct rl4rs_dien_cfg {
  *   NO_ROW_DEDUP    k_din_x and k_augru_x over every row of a forward instead of one representative per set of bit-identical row
  *                   groups (equal cache slots, category ids and dense bit patterns: k_row_dedup finds them on the device at the top
  *                   of every forward, k_row_expand copies the representative's AUGRU states and attention scores to its duplicates
- *                   in front of the head GEMM).  Active only where k_din_x and k_augru_x are the selected kernels (=) */
+ *                   in front of the head GEMM).  Active only where k_din_x and k_augru_x are the selected kernels (=)
+ *   DUP_STORE       row dedup: k_din_x and k_augru_x store every score / final-state piece of a representative to the same row of
+ *                   its duplicates where it is produced (k_row_dedup then leaves the duplicates of every representative as a
+ *                   list) and no k_row_expand is launched (=).  OFF by default: measured slower than the copy launch (building
+ *                   the lists costs the one compacting workgroup more than the launch it saves)
+ *   NO_DUP_STORE    pins that default: k_row_expand copies the representatives' rows to the duplicates (=)
+ *   DIN_ROWS16      k_din_x with 16 rows per workgroup whatever the row dedup left, instead of 8 (one row per wave) when the active
+ *                   rows of an observation-sized launch fit one round that way (decided on the device) (=) */
 enum {
     RL4RS_DIEN_OPT_AUGRU_H16 = 1 << 0,
     RL4RS_DIEN_OPT_AUGRU_ROWS32 = 1 << 1,
@@ -273,7 +280,11 @@ enum {
                                                   instead of one grid that holds both problems' workgroups (bit-identical either way) */
     RL4RS_DIEN_OPT_NO_ROW_DEDUP = 1 << 16,     /* fp16x2 mode: k_din_x / k_augru_x score duplicate row groups of a forward too
                                                   (bit-identical either way) */
-    RL4RS_DIEN_OPT_ALL = (1 << 17) - 1
+    RL4RS_DIEN_OPT_NO_DUP_STORE = 1 << 17,     /* row dedup: k_row_expand as its own launch (the default; bit-identical either way) */
+    RL4RS_DIEN_OPT_DIN_ROWS16 = 1 << 18,       /* k_din_x: 16 rows per workgroup for every launch (bit-identical either way) */
+    RL4RS_DIEN_OPT_DUP_STORE = 1 << 19,        /* row dedup: the duplicates' stores inside k_din_x / k_augru_x, no k_row_expand launch
+                                                  (bit-identical either way) */
+    RL4RS_DIEN_OPT_ALL = (1 << 20) - 1
 };
 
 /* Every mode accumulates in fp32 and meets the fp32 parity bar against the fp64 oracle (same measured error):
@@ -469,6 +480,15 @@ int rl4rs_env_attach_simnet(rl4rs_env* env, rl4rs_simnet* net, const int32_t* sl
 int rl4rs_stepper_destroy(rl4rs_stepper* s);
 int rl4rs_env_step_discrete(rl4rs_stepper* s, const int32_t* actions_dev, float* obs_dev, double* reward_dev,
                             uint8_t* done_dev, uint32_t* mask_bits_dev, void* stream);
+/* rl4rs_env_step_discrete lets the act kernel write done_dev, the zero of reward_dev on a step on which no reward is due and the
+ * logged item ids of the NEXT step (the rule of rl4rs_env_offline_action, past the horizon included) instead of launching a kernel
+ * for the first two and leaving the third to a call between two steps.  rl4rs_stepper_next_offline_action: *step = the step whose
+ * logged ids the last rl4rs_env_step_discrete wrote (-1: none - another kind of transition, or the option is off), *ids_dev =
+ * int32 [B] device memory of the stepper holding them: a row of its own per step of an episode, rewritten by the same step of
+ * the next one.  rl4rs_stepper_set_act_tail(s, 0): the launches as they were (k_step_tail, no next-step ids); bit-identical
+ * outputs either way. */
+int rl4rs_stepper_set_act_tail(rl4rs_stepper* s, int32_t on);
+int rl4rs_stepper_next_offline_action(rl4rs_stepper* s, const int32_t** ids_dev, int32_t* step);
 /* continuous actions: [B, action_emb_size] float32 / float64 resolved by the masked float64 K-NN first (slate.py:187-197);
  * chosen_dev (optional) receives the item ids played */
 int rl4rs_env_step_conti(rl4rs_stepper* s, const void* actions_dev, int is_f64, int32_t* chosen_dev, float* obs_dev,

@@ -524,6 +524,19 @@ __global__ __launch_bounds__(512) void k_augru_x(RecurArgs a) {
                 if (poison) v = make_float4(__builtin_nanf(""), __builtin_nanf(""), __builtin_nanf(""), __builtin_nanf(""));
                 *reinterpret_cast<float4*>(a.out + (int64_t)row * a.out_ld + a.out_off + sq * a.out_seq_off + wave * 32 + 8 * q + 4 * half) = v;
             }
+            if (a.dup_start) {      // row dedup: the same pieces to the same row of every duplicate of this row's group
+                const int pos = row0 + m * 32 + li, gi = pos / a.group, sub = pos - gi * a.group;
+                const int d1 = a.dup_start[gi + 1];
+                for (int d = a.dup_start[gi]; d < d1; ++d) {
+                    const int drow = a.dup_list[d] * a.group + sub;
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        float4 v = make_float4(h_own[m][4 * q], h_own[m][4 * q + 1], h_own[m][4 * q + 2], h_own[m][4 * q + 3]);
+                        if (poison) v = make_float4(__builtin_nanf(""), __builtin_nanf(""), __builtin_nanf(""), __builtin_nanf(""));
+                        *reinterpret_cast<float4*>(a.out + (int64_t)drow * a.out_ld + a.out_off + sq * a.out_seq_off + wave * 32 + 8 * q + 4 * half) = v;
+                    }
+                }
+            }
         }
     }
     if (any_bad && a.range_flag) atomicOr(a.range_flag, 1);

@@ -129,6 +129,16 @@ int launch_amlp_fwd_h16(const AmlpFwdH16& a, hipStream_t st);
 int raise_dyn_smem(const void* fn, size_t bytes);
 int current_device();
 
+// What the act kernel writes besides the act itself when a fused transition asks for it (step.hip; env.hip k_env_rows<1>, one wave
+// per env, lane 0): the constant outputs of the transition and the logged action of the step after it.  A NULL member is left out.
+struct ActTail {
+    uint8_t* done; uint8_t done_v;       // done[b] = done_v
+    double* zero_reward;                 // zero_reward[b] = 0.0: the reward of a step on which none is due
+    int32_t* next_action; int next_cur;  // next_action[b] = the logged item id of step next_cur (the rule of rl4rs_env_offline_action)
+};
+// rl4rs_env_act_discrete with that tail (defined in env.hip)
+int env_act_discrete_tail(rl4rs_env* e, const int32_t* actions, const ActTail& tail, void* stream);
+
 // The NEXT rl4rs_dien_forward's observation also goes to `host_visible` (device-visible pinned host memory, [R, 256] floats) from
 // the head GEMM's epilogue - step.hip's reference-shaped records (dien.hip); dien_obs_mirror_used: did that forward take it?
 void dien_set_obs_mirror(rl4rs_dien* n, float* host_visible);

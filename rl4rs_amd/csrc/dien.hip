@@ -1410,6 +1410,8 @@ struct DinArgs {
     float* scores; int64_t scores_stride;           // [n_seq][scores_stride] rows of L
     const int32_t* order;        // processing order of the row groups (NULL = identity): rl4rs_dien_set_row_order
     const int32_t* n_active;     // k_din_x: device int, only the first n_active[0] entries of `order` are scored (row_dedup.hpp; NULL = all)
+    const int32_t* dup_start;    // k_din_x: duplicates of the group at index i of `order`: dup_list[dup_start[i] .. dup_start[i + 1]); their rows take
+    const int32_t* dup_list;     // the score with the row's own (row_dedup.hpp).  NULL = own rows only
     unsigned long long* trace;   // -DRL4RS_DINX_TRACE timing experiments only
     // k_din_x: leading zero ids of the sequence in every cache slot and the slot of the all-zero sequence (RecurArgs::lead / pad_slot):
     // the steps of a row's front padding read the pad slot's states and projections - the same bytes, shared by all rows.  NULL = off
@@ -1767,6 +1769,9 @@ struct rl4rs_dien {
     int* range_flag;       // device int: a k_augru_h16 state left the fp16 range (sticky until read)
     const int32_t* row_order; int row_order_n;    // processing order of the row groups of a forward (caller-owned), or NULL
     // row dedup (row_dedup.hpp): k_din_x and k_augru_x score one representative per set of bit-identical row groups
+    bool dup_store;        // row dedup: k_din_x / k_augru_x store a representative's rows to its duplicates (RL4RS_DIEN_OPT_DUP_STORE; default: k_row_expand copies them)
+    bool din_rows_auto;    // k_din_x at group == 1: 8 or 16 rows per workgroup from the active row count, on the device (RL4RS_DIEN_OPT_DIN_ROWS16: always 16)
+    int32_t *dd_dstart, *dd_dlist, *dd_dcur;      // duplicate lists of the last forward (RowDedupArgs)
     bool row_dedup;        // on wherever k_din_x and k_augru_x are the selected kernels (RL4RS_DIEN_OPT_NO_ROW_DEDUP: off)
     int32_t* dd_rep;       // [max_rows] representative of every row group of the last forward
     int32_t* dd_active;    // [max_rows] the representatives in processing order
@@ -1935,6 +1940,7 @@ int rl4rs_dien_create(const rl4rs_dien_cfg* c, const rl4rs_dien_weights* w, void
     // run holds handles with different paths side by side
     const uint32_t opts = c->kernel_opts;
     RL4RS_REQUIRE((opts & ~(uint32_t)RL4RS_DIEN_OPT_ALL) == 0, "dien: unknown kernel_opts bits 0x%x", opts & ~(uint32_t)RL4RS_DIEN_OPT_ALL);
+    RL4RS_REQUIRE(!((opts & RL4RS_DIEN_OPT_DUP_STORE) && (opts & RL4RS_DIEN_OPT_NO_DUP_STORE)), "dien: dup_store and no_dup_store are exclusive");
     RL4RS_REQUIRE(!((opts & RL4RS_DIEN_OPT_AUGRU_ROWS32) && (opts & RL4RS_DIEN_OPT_AUGRU_ROWS64)),
                   "dien: kernel_opts asks for both the 32-row and the 64-row AUGRU form");
     n->augru_x = !(opts & RL4RS_DIEN_OPT_AUGRU_H16);
@@ -2160,6 +2166,9 @@ int rl4rs_dien_create(const rl4rs_dien_cfg* c, const rl4rs_dien_weights* w, void
     // row dedup: only where both kernels that read the active list are the selected ones
     n->row_dedup = !(opts & RL4RS_DIEN_OPT_NO_ROW_DEDUP) && n->fp16x2 && n->augru_x && n->din16 && n->h1f[0] != nullptr;
     n->dd_rep = n->dd_active = n->dd_nact = nullptr;
+    n->dd_dstart = n->dd_dlist = n->dd_dcur = nullptr;
+    n->dup_store = n->row_dedup && (opts & RL4RS_DIEN_OPT_DUP_STORE) != 0;
+    n->din_rows_auto = !(opts & RL4RS_DIEN_OPT_DIN_ROWS16);
     if (n->row_dedup) {
         float* f = nullptr;
         if ((rc = alloc_f(n, &f, (size_t)2 * c->max_rows + 2)) != RL4RS_OK) return rc;
@@ -2167,6 +2176,14 @@ int rl4rs_dien_create(const rl4rs_dien_cfg* c, const rl4rs_dien_weights* w, void
         n->dd_active = n->dd_rep + c->max_rows;
         n->dd_nact = n->dd_active + c->max_rows;
         RL4RS_HIP_TRY(hipMemsetAsync(f, 0, ((size_t)2 * c->max_rows + 2) * 4, st));
+    }
+    if (n->dup_store) {
+        float* f = nullptr;
+        if ((rc = alloc_f(n, &f, (size_t)3 * c->max_rows + 1)) != RL4RS_OK) return rc;
+        n->dd_dlist = reinterpret_cast<int32_t*>(f);
+        n->dd_dcur = n->dd_dlist + c->max_rows;
+        n->dd_dstart = n->dd_dcur + c->max_rows;
+        RL4RS_HIP_TRY(hipMemsetAsync(f, 0, ((size_t)3 * c->max_rows + 1) * 4, st));
     }
     n->tsum = nullptr;
     if (n->ptab && Cn <= 24 && !(opts & RL4RS_DIEN_OPT_NO_HEAD_FUSED)) AL(tsum, (size_t)c->max_rows * OBS_DIM);
@@ -2344,6 +2361,7 @@ int rl4rs_dien_forward(rl4rs_dien* n, int32_t R, int32_t group, const float* den
         a.n_groups = ngroups; a.group = group; a.Cn = Cn; a.Dn = n->Dn; a.S = S;
         a.slots = slots; a.slots_stride = ngroups; a.cat = cat; a.dense = dense; a.order = order_in;
         a.rep = n->dd_rep; a.active = n->dd_active; a.n_active = n->dd_nact;
+        if (n->dup_store) { a.dup_start = n->dd_dstart; a.dup_list = n->dd_dlist; a.dup_cur = n->dd_dcur; }
         constexpr int per_wg = ROW_DEDUP_THREADS / 64;
         hipLaunchKernelGGL(k_row_dedup, dim3((ngroups + per_wg - 1) / per_wg), dim3(ROW_DEDUP_THREADS), 0, st, a);
         RL4RS_LAUNCH_CHECK();
@@ -2409,6 +2427,7 @@ int rl4rs_dien_forward(rl4rs_dien* n, int32_t R, int32_t group, const float* den
         a.scores = n->scores; a.scores_stride = (int64_t)n->c.max_rows * L;
         a.order = order_in;
         if (dedup && h16 && n->h1f[0]) { a.order = n->dd_active; a.n_active = n->dd_nact; }
+        if (dedup && n->dup_store) { a.dup_start = n->dd_dstart; a.dup_list = n->dd_dlist; }
         for (int s = 0; s < S; ++s) a.lead[s] = n->lead[s];
         a.pad_slot = n->c.max_slots;
 #ifdef RL4RS_DINX_TRACE      // timing experiments only (tools/dinx_trace.py)
@@ -2426,8 +2445,12 @@ int rl4rs_dien_forward(rl4rs_dien* n, int32_t R, int32_t group, const float* den
         }
 #endif
         if (h16 && n->h1f[0]) {
-            // 16 rows per 8-wave workgroup: an obs-sized launch (R = 4096, two inputs) is two workgroups per CU, one round
-            hipLaunchKernelGGL(k_din_x, dim3((R + 15) / 16, S), dim3(512), din_x_smem(), st, a, 16);
+            // 16 rows per 8-wave workgroup: an obs-sized launch (R = 4096, two inputs) is two workgroups per CU, one round.
+            // group == 1: the grid is sized for 8 and the kernel picks 8 or 16 from the rows the dedup left (din_x.hpp)
+            if (group == 1 && n->din_rows_auto)
+                hipLaunchKernelGGL(k_din_x, dim3((R + 7) / 8, S), dim3(512), din_x_smem(), st, a, 16, n->n_cu);
+            else
+                hipLaunchKernelGGL(k_din_x, dim3((R + 15) / 16, S), dim3(512), din_x_smem(), st, a, 16, 0);
         } else if (group == 1) {
             const int nw = 4;
             size_t smem = ((size_t)2 * 16 * 64 + 48 + (size_t)nw * (E + ATT_H1)) * 4;
@@ -2466,6 +2489,7 @@ int rl4rs_dien_forward(rl4rs_dien* n, int32_t R, int32_t group, const float* den
                 }
             a.order = n->augru_x ? order_in : nullptr;
             if (dedup) { a.order = n->dd_active; a.n_active = n->dd_nact; }
+            if (dedup && n->dup_store && n->augru_x) { a.dup_start = n->dd_dstart; a.dup_list = n->dd_dlist; }
             a.steps = 0;
 #if defined(RL4RS_H16_TRACE) || defined(RL4RS_X_TRACE)
             static unsigned long long* trace_buf = nullptr;
@@ -2505,7 +2529,7 @@ int rl4rs_dien_forward(rl4rs_dien* n, int32_t R, int32_t group, const float* den
         ;
         RL4RS_LAUNCH_CHECK();
     }
-    if (dedup) {     // the duplicates' AUGRU states and attention scores, in front of the head GEMM
+    if (dedup && !n->dup_store) {     // the duplicates' AUGRU states and attention scores, in front of the head GEMM
         Prof p(n, KID_DEDUP, st);
         RowExpandArgs a;
         memset(&a, 0, sizeof(a));

@@ -9,7 +9,8 @@
 //
 //   * W1d fragments (32 KB, both planes) are staged ONCE per workgroup in LDS and read with ds_read_b128 right behind their
 //     use; a workgroup is 8 waves and takes rows_per_wg rows (obs-sized launches: 16, so that
-//     two workgroups per CU = 4 waves per SIMD cover the launch in one round, no tail).
+//     two workgroups per CU = 4 waves per SIMD cover the launch in one round, no tail; 8 when the rows the row dedup leaves
+//     fit that round at one row per wave - half the workgroup life, the staging being per workgroup either way).
 //   * one 32-step tile at a time (32 accumulator registers instead of 64) and no double buffers, so that the kernel fits 128
 //     registers = 4 waves per SIMD, which overlap each other's VALU (operand split, sigmoids) and MFMA stretches; the cache
 //     rows are requested RING k-blocks ahead.
@@ -51,13 +52,17 @@ __global__ __launch_bounds__(256) void k_h1_frag(const float* __restrict__ h1, f
     }
 }
 
-__global__ __launch_bounds__(512, RL4RS_DINX_WPE) void k_din_x(DinArgs a, int rows_per_wg) {
+__global__ __launch_bounds__(512, RL4RS_DINX_WPE) void k_din_x(DinArgs a, int rows_per_wg, int n_cu) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int E = 128, KB = 8, NW = 8;
     const int L = a.L;
     const int sq = blockIdx.y;
     // row dedup (row_dedup.hpp): only the first n_active entries of a.order are scored; the grid is sized for a.R on the host
     const int n_rows = a.n_active ? min(a.R, a.n_active[0] * a.group) : a.R;
+    // n_cu > 0 (group == 1 launches, grid sized for 8 rows per workgroup): one row per wave while that still fits one round of two
+    // workgroups per CU, otherwise two rows per wave as before; decided here because the row count is a device value.  A row's
+    // arithmetic does not depend on the mapping.
+    if (n_cu > 0) rows_per_wg = ((n_rows + 7) / 8) * (int)gridDim.y <= 2 * n_cu ? 8 : 16;
     if (blockIdx.x * rows_per_wg >= n_rows) return;
     char* s_w1 = smem;                                                 // [(m*8 + kb)*2 + plane][lane][8 halfs]: 32 KB
     char* s_w2b = smem + 32768;                                         // [(m*2 + kb2)*2 + plane][lane][8 halfs]: 8 KB
@@ -113,6 +118,10 @@ __global__ __launch_bounds__(512, RL4RS_DINX_WPE) void k_din_x(DinArgs a, int ro
         const int idx = blockIdx.x * rows_per_wg + j;
         if (idx >= n_rows) break;
         const int g = idx / grp;
+        // the duplicates of this row's group (row_dedup.hpp): their rows take the score where the row's own is stored.  Requested
+        // with the order entry, first looked at behind the first tile
+        int dup0 = 0, dup1 = 0;
+        if (a.dup_start) { dup0 = a.dup_start[g]; dup1 = a.dup_start[g + 1]; }
         const int gs = a.order ? a.order[g] : g;
         const int row = gs * grp + (idx - g * grp);
 #if RL4RS_DINX_AB & 1       // timing ablation (results WRONG): every row reads cache slot 0 - the cache traffic becomes L1 / L2 hits
@@ -246,6 +255,10 @@ __global__ __launch_bounds__(512, RL4RS_DINX_WPE) void k_din_x(DinArgs a, int ro
             sc += __shfl_xor(sc, 32);
             sc += s_misc[32];
             if (half == 0 && t < L) a.scores[(size_t)sq * a.scores_stride + (size_t)row * L + t] = sc;
+            for (int d = __builtin_amdgcn_readfirstlane(dup0), d1 = __builtin_amdgcn_readfirstlane(dup1); d < d1; ++d) {
+                const int drow = a.dup_list[d] * grp + (idx - g * grp);
+                if (half == 0 && t < L) a.scores[(size_t)sq * a.scores_stride + (size_t)drow * L + t] = sc;
+            }
             DINX_TR((j / NW) * 2 + n, 5);
         }
     }

@@ -138,9 +138,14 @@ __device__ __forceinline__ void stage_items(const EnvDev& e, float* s_item) {
 // LDS slot, ordered by wave-level fences only), so after the one-time catalogue staging there is no
 // workgroup barrier on the row loop.  USE_LDS = false reads the 45 KB catalogue through L1/L2 instead of
 // staging it (kept for A/B measurements).
+// the logged item id of step `cur` of env b (slate.py:152-161): 0 past the horizon or the end of the logged slate
+__device__ __forceinline__ int offline_action_id(const EnvDev& e, int b, int cur) {
+    return (cur < e.T && cur < e.logT) ? e.exposed[(size_t)b * e.logT + cur] : 0;
+}
+
 template <int MODE, bool USE_LDS>
 __global__ __launch_bounds__(1024) void k_env_rows(EnvDev e, const int32_t* __restrict__ actions,
-                                                   int cur, int n_complete, int j_base) {
+                                                   int cur, int n_complete, int j_base, ActTail tail) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* s_item_lds = reinterpret_cast<float*>(smem);
     const size_t item_bytes = USE_LDS ? (((size_t)e.A * e.D * 4 + 15) & ~size_t(15)) : 0;
@@ -200,6 +205,10 @@ __global__ __launch_bounds__(1024) void k_env_rows(EnvDev e, const int32_t* __re
             if (lane == 0) {
                 e.prev[(size_t)b * e.T + cur] = a;
                 e.amask[(size_t)b * e.W + (a >> 5)] &= ~(1u << (a & 31));
+                // the transition's constant outputs and the next step's logged action (ActTail): this wave owns env b
+                if (tail.done) tail.done[b] = tail.done_v;
+                if (tail.zero_reward) tail.zero_reward[b] = 0.0;
+                if (tail.next_action) tail.next_action[b] = offline_action_id(e, b, tail.next_cur);
             }
             bool hit = false;
             for (int j = lane; j < e.T; j += 64) hit |= (e.is_special[s_prev[j]] != 0);
@@ -487,7 +496,7 @@ __global__ void k_obs_mask_bits(EnvDev e, int layer, uint32_t* out) {
 __global__ void k_offline_action(EnvDev e, int cur, int32_t* ids, double* emb) {
     int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= e.B) return;
-    int id = (cur < e.T && cur < e.logT) ? e.exposed[(size_t)b * e.logT + cur] : 0;   // slate.py:152-161
+    int id = offline_action_id(e, b, cur);
     if (ids) ids[b] = id;
     if (emb) {
         if (id < 0 || id >= e.A) { atomicExch(e.err, 1); id = 0; }
@@ -604,13 +613,14 @@ static RowsLaunch rows_launch(const rl4rs_env* e, int R, int mode) {
     return L;
 }
 template <int MODE>
-static int launch_rows(rl4rs_env* e, int R, const int32_t* actions, int cur, int n_complete, int j_base, hipStream_t st) {
+static int launch_rows(rl4rs_env* e, int R, const int32_t* actions, int cur, int n_complete, int j_base, hipStream_t st,
+                       const ActTail& tail = ActTail()) {
     if (MODE == 1) e->state_fresh = false;      // an act writes prev_actions / the masks: the next reset must clear them again
     RowsLaunch L = rows_launch(e, R, MODE);
     if (L.lds)
-        hipLaunchKernelGGL((k_env_rows<MODE, true>), dim3(L.grid), dim3(L.threads), L.smem, st, e->d, actions, cur, n_complete, j_base);
+        hipLaunchKernelGGL((k_env_rows<MODE, true>), dim3(L.grid), dim3(L.threads), L.smem, st, e->d, actions, cur, n_complete, j_base, tail);
     else
-        hipLaunchKernelGGL((k_env_rows<MODE, false>), dim3(L.grid), dim3(L.threads), L.smem, st, e->d, actions, cur, n_complete, j_base);
+        hipLaunchKernelGGL((k_env_rows<MODE, false>), dim3(L.grid), dim3(L.threads), L.smem, st, e->d, actions, cur, n_complete, j_base, tail);
     RL4RS_LAUNCH_CHECK();
     return RL4RS_OK;
 }
@@ -818,17 +828,22 @@ int rl4rs_env_reset(rl4rs_env* e, void* stream) {
     return launch_rows<0>(e, d.B, nullptr, 0, 0, 0, st);
 }
 
-int rl4rs_env_act_discrete(rl4rs_env* e, const int32_t* actions, void* stream) {
+}  // extern "C"
+int rl4rs::env_act_discrete_tail(rl4rs_env* e, const int32_t* actions, const ActTail& tail, void* stream) {
     RL4RS_REQUIRE(e && actions, "act_discrete: null argument");
     if (e->cur_steps >= e->d.T) {    // prev_actions[:, cur_steps] would raise IndexError (slate.py:198)
         set_error("act at cur_steps=%d >= max_steps=%d", e->cur_steps, e->d.T);
         return RL4RS_ESTATE;
     }
     hipStream_t st = (hipStream_t)stream;
-    int rc = launch_rows<1>(e, e->d.B, actions, e->cur_steps, 0, 0, st);
+    int rc = launch_rows<1>(e, e->d.B, actions, e->cur_steps, 0, 0, st, tail);
     if (rc) return rc;
     e->cur_steps += 1;
     return RL4RS_OK;
+}
+extern "C" {
+int rl4rs_env_act_discrete(rl4rs_env* e, const int32_t* actions, void* stream) {
+    return rl4rs::env_act_discrete_tail(e, actions, ActTail(), stream);
 }
 
 static int knn_launch(const void* actions, int is_f64, int n, const double* emb, int A, int E,

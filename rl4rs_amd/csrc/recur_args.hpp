@@ -55,6 +55,8 @@ struct RecurArgs {
     int steps;                   // debug: run only the first `steps` recurrence steps (0 = all L)
     const int32_t* order;        // k_augru_x: processing order of the row groups (NULL = identity)
     const int32_t* n_active;     // k_augru_x: device int, only the first n_active[0] entries of `order` are processed (row_dedup.hpp; NULL = all n_rows / group)
+    const int32_t* dup_start;    // k_augru_x: duplicates of the group at index i of `order`: dup_list[dup_start[i] .. dup_start[i + 1]); their rows take
+    const int32_t* dup_list;     // the final state with the row's own (row_dedup.hpp).  NULL = own rows only
     int final_only;              // GRU mode: write only the last state, to out[(slot_base + row) * out_ld + out_off]
     // k_gru_h16: [L][NH] - row t = the state after t + 1 steps on item id 0 from h = 0 (the same for every row: pad_sequences pads in
     // FRONT, rl4rs/utils/datautil.py:44).  A workgroup whose rows all start with at least t0 zero ids copies rows 0 .. t0 - 1 of this

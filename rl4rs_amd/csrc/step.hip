@@ -22,6 +22,12 @@ struct rl4rs_stepper {
     float* probs;              // [B * (n_complete - 1)] click probabilities of the complete-state rows
     float* p_last;             // [B] probability of the state row just scored (= the last complete-state row)
     const float* dense; const int32_t* cat; const int32_t* seq1; const float* c_dense; const int32_t* c_cat;
+    // rl4rs_env_step_discrete: the act kernel also writes done, the zero reward and the NEXT step's logged action (ActTail) - no
+    // k_step_tail launch, and a replay loop needs no rl4rs_env_offline_action launch between two steps
+    bool act_tail;             // rl4rs_stepper_set_act_tail (default on)
+    int32_t* next_off;         // [max_steps + 1][B]: row c = the logged item ids of step c, written by the step that led to it - a row
+                               // of its own per step of an episode, so a caller may hold what it was handed until the episode ends
+    int next_off_cur;          // the step whose row the last transition wrote, -1 = none
     hipStream_t copy_stream;   // rl4rs_env_step_record_host: early device-to-host copies run here, beside the scorer's kernels
     hipEvent_t ev_ready, ev_copied;
 };
@@ -69,7 +75,7 @@ __global__ void k_step_tail(uint8_t* done, uint8_t v, double* zero_reward, int n
 struct NoHook { int operator()() const { return RL4RS_OK; } };
 template <typename Hook = NoHook>
 int after_act(rl4rs_stepper* s, int cur_before, float* obs, double* reward, uint8_t* done, uint32_t* mask_bits, void* stream,
-              Hook on_obs = Hook()) {
+              Hook on_obs = Hook(), bool tail_done = false) {
     hipStream_t st = (hipStream_t)stream;
     rl4rs_env* e = s->env;
     const int B = s->cfg.batch_size;
@@ -97,7 +103,7 @@ int after_act(rl4rs_stepper* s, int cur_before, float* obs, double* reward, uint
             zero_reward = reward;
         }
     }
-    if (done || zero_reward) {
+    if ((done || zero_reward) && !tail_done) {      // (tail_done: the act kernel wrote both, ActTail)
         hipLaunchKernelGGL(k_step_tail, dim3((B + 255) / 256), dim3(256), 0, st, done, (uint8_t)(cur_before >= s->cfg.max_steps - 1 ? 1 : 0),
                            zero_reward, B);
         RL4RS_LAUNCH_CHECK();
@@ -144,11 +150,17 @@ int attach(rl4rs_env* env, rl4rs_dien* dien, rl4rs_simnet* simnet, const int32_t
     if (rc) { delete s; return rc; }
     s->n_complete = rl4rs_env_complete_rows(env);
     const size_t B = (size_t)s->cfg.batch_size;
-    if ((rc = dev_alloc(&s->probs, B * (size_t)(s->n_complete > 1 ? s->n_complete - 1 : 1))) || (rc = dev_alloc(&s->p_last, B))) {
+    float* ring = nullptr;
+    if ((rc = dev_alloc(&s->probs, B * (size_t)(s->n_complete > 1 ? s->n_complete - 1 : 1))) || (rc = dev_alloc(&s->p_last, B)) ||
+        (rc = dev_alloc(&ring, B * (size_t)(s->cfg.max_steps + 1)))) {
         if (s->probs) (void)hipFree(s->probs);
+        if (s->p_last) (void)hipFree(s->p_last);
         delete s;
         return rc;
     }
+    s->next_off = reinterpret_cast<int32_t*>(ring);
+    s->next_off_cur = -1;
+    s->act_tail = true;
     void* p;
     int64_t nb;
 #define BUF(which, field, type) if ((rc = rl4rs_env_buffer(env, which, &p, &nb))) { rl4rs_stepper_destroy(s); return rc; } s->field = reinterpret_cast<type>(p)
@@ -177,6 +189,7 @@ int rl4rs_stepper_destroy(rl4rs_stepper* s) {
     if (!s) return RL4RS_OK;
     if (s->probs) (void)hipFree(s->probs);
     if (s->p_last) (void)hipFree(s->p_last);
+    if (s->next_off) (void)hipFree(s->next_off);
     if (s->ev_ready) (void)hipEventDestroy(s->ev_ready);
     if (s->ev_copied) (void)hipEventDestroy(s->ev_copied);
     if (s->copy_stream) (void)hipStreamDestroy(s->copy_stream);
@@ -188,15 +201,47 @@ int rl4rs_env_step_discrete(rl4rs_stepper* s, const int32_t* actions_dev, float*
                             uint32_t* mask_bits_dev, void* stream) {
     RL4RS_REQUIRE(s && actions_dev && obs_dev, "env_step_discrete: null argument");
     const int cur = rl4rs_env_cur_steps(s->env);
-    int rc = rl4rs_env_act_discrete(s->env, actions_dev, stream);
+    s->next_off_cur = -1;
+    if (!s->act_tail) {
+        int rc = rl4rs_env_act_discrete(s->env, actions_dev, stream);
+        if (rc) return rc;
+        return after_act(s, cur, obs_dev, reward_dev, done_dev, mask_bits_dev, stream);
+    }
+    // is a reward due after this act?  (rl4rs_env_is_reward_step at cur + 1; checked against it below)
+    const int T = s->cfg.max_steps;
+    const int due = s->cfg.is_seq ? ((cur + 1) % s->cfg.page_items == 0 ? 1 : 0) : (cur + 1 >= T ? 1 : 0);
+    ActTail tail;
+    tail.done = done_dev; tail.done_v = (uint8_t)(cur >= T - 1 ? 1 : 0);
+    tail.zero_reward = (reward_dev && !due) ? reward_dev : nullptr;
+    tail.next_action = (cur + 1 <= T) ? s->next_off + (size_t)(cur + 1) * s->cfg.batch_size : nullptr;
+    tail.next_cur = cur + 1;
+    int rc = rl4rs::env_act_discrete_tail(s->env, actions_dev, tail, stream);
     if (rc) return rc;
-    return after_act(s, cur, obs_dev, reward_dev, done_dev, mask_bits_dev, stream);
+    if (tail.next_action) s->next_off_cur = cur + 1;
+    // (a different answer from the env itself: k_step_tail runs as before and has the last word)
+    const bool covered = rl4rs_env_is_reward_step(s->env) == due;
+    return after_act(s, cur, obs_dev, reward_dev, done_dev, mask_bits_dev, stream, NoHook(), covered);
+}
+
+int rl4rs_stepper_set_act_tail(rl4rs_stepper* s, int32_t on) {
+    RL4RS_REQUIRE(s, "stepper_set_act_tail: null argument");
+    s->act_tail = on != 0;
+    s->next_off_cur = -1;
+    return RL4RS_OK;
+}
+
+int rl4rs_stepper_next_offline_action(rl4rs_stepper* s, const int32_t** ids_dev, int32_t* step) {
+    RL4RS_REQUIRE(s && ids_dev && step, "stepper_next_offline_action: null argument");
+    *step = s->next_off_cur;
+    *ids_dev = s->next_off_cur >= 0 ? s->next_off + (size_t)s->next_off_cur * s->cfg.batch_size : nullptr;
+    return RL4RS_OK;
 }
 
 int rl4rs_env_step_conti(rl4rs_stepper* s, const void* actions_dev, int is_f64, int32_t* chosen_dev, float* obs_dev,
                          double* reward_dev, uint8_t* done_dev, uint32_t* mask_bits_dev, void* stream) {
     RL4RS_REQUIRE(s && actions_dev && obs_dev, "env_step_conti: null argument");
     const int cur = rl4rs_env_cur_steps(s->env);
+    s->next_off_cur = -1;
     int rc = rl4rs_env_act_conti(s->env, actions_dev, is_f64, chosen_dev, stream);
     if (rc) return rc;
     return after_act(s, cur, obs_dev, reward_dev, done_dev, mask_bits_dev, stream);
@@ -258,6 +303,7 @@ static int step_record(rl4rs_stepper* s, bool observe, const void* actions_dev, 
         rc = RL4RS_OK;
     } else if (action_kind == 0) {
         RL4RS_HIP_TRY(hipMemcpyAsync(chosen, actions_dev, (size_t)B * 4, hipMemcpyDeviceToDevice, st));
+        s->next_off_cur = -1;
         rc = rl4rs_env_act_discrete(s->env, reinterpret_cast<const int32_t*>(actions_dev), stream);
     } else {
         rc = rl4rs_env_act_conti(s->env, actions_dev, action_kind == 2 ? 1 : 0, chosen, stream);

@@ -331,7 +331,9 @@ class DeviceStepper(object):
     """rl4rs_stepper handle: an env bound to its scorer so that one call runs a whole transition
     (rl4rs_env_step_discrete / rl4rs_env_step_conti = RecSimBase._step, base.py:157-170)."""
 
-    def __init__(self, env, net, slots):
+    def __init__(self, env, net, slots, act_tail=True):
+        """``act_tail=False`` (config['no_act_tail'] / RL4RS_NO_ACT_TAIL=1): rl4rs_env_step_discrete launches k_step_tail as it
+        did and leaves no next-step logged actions (rl4rs_stepper_set_act_tail)."""
         self.lib = _lib.load()
         self.env, self.net, self.slots = env, net, slots          # keep the handles and the slot table alive
         assert slots.dtype == torch.int32 and slots.is_contiguous() and slots.shape[1] == env.B
@@ -339,6 +341,9 @@ class DeviceStepper(object):
         attach = self.lib.rl4rs_env_attach_simnet if isinstance(net, DeviceSimnet) else self.lib.rl4rs_env_attach_scorer
         check(attach(env.h, net.h, _ptr(slots), int(slots.shape[0]), C.byref(h)))
         self.h = h
+        self.act_tail = bool(act_tail)
+        if not self.act_tail:
+            check(self.lib.rl4rs_stepper_set_act_tail(self.h, 0))
         self.B, self.A, self.E, self.W, self.device = env.B, env.A, env.E, env.W, env.device
         self.obs_dim = int(getattr(net, 'obs_dim', 256))         # 256 for DIEN / dnn / lstm, 256 + U + Cn*E for widedeep
 
@@ -372,6 +377,24 @@ class DeviceStepper(object):
             assert chosen.numel() == self.B, (chosen.shape, self.B)
             check(self.lib.rl4rs_env_step_discrete(self.h, _ptr(chosen), _ptr(obs), _ptr(reward), None, _ptr(bits), _stream()))
         return obs, reward, bits, chosen
+
+    def next_offline_action(self, rows=None):
+        """(step, int32 [B] device tensor) - the logged item ids of ``step`` the LAST ``step`` with discrete actions left in the
+        stepper's memory (rl4rs_stepper_next_offline_action), or None.  The tensor aliases a row the stepper keeps for that step
+        of an episode: it is rewritten by the same step of the next episode.  ``rows``: a dict of the caller's that remembers the
+        alias tensors by address (kept outside the stepper: the aliases refer to it)."""
+        if not self.act_tail:
+            return None
+        ptr, step = C.c_void_p(), C.c_int32(-1)
+        check(self.lib.rl4rs_stepper_next_offline_action(self.h, C.byref(ptr), C.byref(step)))
+        if step.value < 0 or not ptr.value:
+            return None
+        t = None if rows is None else rows.get(ptr.value)
+        if t is None:
+            t = _alias_i32(ptr.value, self.B, self.device, self)      # keeps this stepper (the owner of the memory) alive
+            if rows is not None:
+                rows[ptr.value] = t
+        return int(step.value), t
 
     def offline_action_view(self):
         """Device view of the logged next-step actions the LAST step_record left in its record (int32 [B]; None if it wrote
@@ -1015,6 +1038,15 @@ class _DevAlias(object):
     def __init__(self, ptr, count, owner):
         self.owner = owner
         self.__cuda_array_interface__ = {'shape': (int(count),), 'typestr': '<f4', 'data': (int(ptr), False), 'version': 2}
+
+
+def _alias_i32(ptr, count, device, owner):
+    a = _DevAlias(ptr, count, owner)
+    a.__cuda_array_interface__['typestr'] = '<i4'
+    with torch.cuda.device(device):
+        t = torch.as_tensor(a, device=device)
+    assert t.data_ptr() == int(ptr) and t.dtype == torch.int32
+    return t
 
 
 def _alias_f32(ptr, count, device, owner):

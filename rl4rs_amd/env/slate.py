@@ -10,6 +10,8 @@ Config keys are the reference's; two additions select the zero-copy mode:
 ``return_tensors`` (bool, default False): return torch CUDA tensors instead of numpy/list objects;
 ``model_seed`` (int): seed for synthetic DIEN weights when ``model_file`` is empty.
 """
+import os
+
 import numpy as np
 
 from .base import RecSimBase, RecState, RecordBatch
@@ -294,6 +296,9 @@ class SlateState(RecState):
             raise IndexError('list index out of range')       # exposed_items[cur_step], slate.py:154-156
         conti = bool(self.config.get("support_conti_env", False))
         if self._tensor_mode():
+            nxt = getattr(self, '_next_offline_dev', None)
+            if not conti and nxt is not None and nxt[0] == (self._batch_version, env.cur_steps):
+                return nxt[1]           # written by the act kernel of the transition that led here (SlateRecEnv._step)
             return env.offline_action(conti=conti)
         nxt = getattr(self, '_next_offline', None)
         if nxt is not None and nxt[0] == (self._batch_version, env.cur_steps):
@@ -596,9 +601,13 @@ class SlateRecEnv(RecSimBase):
         net, slots = self._net_for(samples)                 # history encoded for this batch, slot table current
         key = (id(env), id(net), slots.data_ptr())
         if getattr(self, '_stepper_key', None) != key:
-            if getattr(self, '_stepper', None) is not None:
-                self._stepper.close()
-            self._stepper = D.DeviceStepper(env, net, slots)
+            # (dropped, not closed: a logged-action tensor handed out by offline_action aliases the old stepper's memory and keeps
+            # it alive; the handle is destroyed with its last reference)
+            self._stepper = None
+            self._next_rows = {}
+            # config['no_act_tail'] (RL4RS_NO_ACT_TAIL=1): k_step_tail and k_offline_action as launches of their own
+            no_tail = self.config.get('no_act_tail', os.environ.get('RL4RS_NO_ACT_TAIL', '') not in ('', '0'))
+            self._stepper = D.DeviceStepper(env, net, slots, act_tail=not no_tail)
             self._stepper_key = key
         return env, net, self._stepper
 
@@ -682,6 +691,8 @@ class SlateRecEnv(RecSimBase):
         if samples._tensor_mode():
             obs, reward, _, chosen = stepper.step(action, conti=conti)
             samples.last_actions = chosen
+            nxt = None if conti else stepper.next_offline_action(self.__dict__.setdefault('_next_rows', {}))
+            samples._next_offline_dev = None if nxt is None else ((samples._batch_version, nxt[0]), nxt[1])
             if masked:
                 obs = {"action_mask": samples._obs_mask(), "obs": obs}
         else:
