@@ -31,7 +31,11 @@ class OracleAMLP(object):
         h = torch.relu(x @ p['fc1_w'] + p['fc1_b'])
         h = torch.relu(h @ p['fc2_w'] + p['fc2_b'])
         out = h @ p['head_w'] + p['head_b']
-        return torch.tanh(out) if self.head_act == 'tanh' else out
+        return self.HEAD_ACTS[self.head_act](out)
+
+    # the head activations rl4rs_amlp_create accepts (rl4rs_amd.device.DeviceAMLP.HEAD_ACTS)
+    HEAD_ACTS = {'none': lambda o: o, 'tanh': torch.tanh, 'relu': torch.relu, 'sigmoid': torch.sigmoid,
+                 'elu': torch.nn.functional.elu}
 
     def grads(self):
         return dict((k, (v.grad.numpy() if v.grad is not None else np.zeros(tuple(v.shape)))) for k, v in self.p.items())

@@ -135,15 +135,43 @@ __global__ __launch_bounds__(256) void k_amlp_fwd4(AmlpFwd4x x) {
         return s;
     };
     // ---- layer 1
-    zero();
+    f32x4_t sum1[MTW];
+    if constexpr (MTW == 1) {
+        zero();
 #pragma unroll
-    for (int m = 0; m < MTW; ++m) ap[m] = xs + (m * 4 + (lane & 3)) * LDX;
-    phase_rt<1, MTW, P>(acc, ap, ring, ld1, head2, KXP / 64);
+        for (int m = 0; m < MTW; ++m) ap[m] = xs + (m * 4 + (lane & 3)) * LDX;
+        phase_rt<1, MTW, P>(acc, ap, ring, ld1, head2, KXP / 64);
+#pragma unroll
+        for (int m = 0; m < MTW; ++m) sum1[m] = total(m);
+    } else {
+        // The 8-row form has P = 2 chains per tile: at KX = 4096 each would add 2048 products in a row, twice the 4-row form's
+        // chain and 1.16 x the forward bar of tests/test_gpu_conti_shapes.py there.  The first layer therefore adds in blocks of
+        // L1_BLOCK ring rounds (512 k: chains of 256) whose totals are summed in block order; one block (KX <= 512, every
+        // learner's network) is the same sequence of operations as before, bit for bit.  The ring runs on across the blocks.
+        constexpr int L1_BLOCK = 8;
+        const int rounds = KXP / 64;
+#pragma unroll
+        for (int m = 0; m < MTW; ++m) sum1[m] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll 1
+        for (int r0 = 0; r0 < rounds; r0 += L1_BLOCK) {
+            const int nr = min(L1_BLOCK, rounds - r0);
+            const bool last_block = r0 + nr >= rounds;
+            const int q0 = r0 * (64 / 4), q1 = (r0 + nr) * (64 / 4);           // first quad of this block / of the next one
+            auto cur = [&](int q, int) { return ld1(q0 + q, 0); };
+            auto next = [&](int i) { return last_block ? ld2(i, 0) : ld1(q1 + i, 0); };
+            zero();
+#pragma unroll
+            for (int m = 0; m < MTW; ++m) ap[m] = xs + (m * 4 + (lane & 3)) * LDX + r0 * 64;
+            phase_rt<1, MTW, P>(acc, ap, ring, cur, next, nr);
+#pragma unroll
+            for (int m = 0; m < MTW; ++m) sum1[m] += total(m);
+        }
+    }
     {
         const float b = a.b1[col];
 #pragma unroll
         for (int m = 0; m < MTW; ++m) {
-            const f32x4_t s = total(m);
+            const f32x4_t s = sum1[m];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const float v = fmaxf(s[i] + b, 0.f);

@@ -16,6 +16,10 @@ def _ref(params, obs, act, rep, head_act):
     h = np.maximum(x @ p['fc1_w'] + p['fc1_b'], 0.0)
     h = np.maximum(h @ p['fc2_w'] + p['fc2_b'], 0.0)
     o = h @ p['head_w'] + p['head_b']
+    if head_act == 'relu':
+        return np.maximum(o, 0.0)
+    if head_act == 'sigmoid':
+        return 1.0 / (1.0 + np.exp(-o))
     return np.tanh(o) if head_act == 'tanh' else o
 
 
@@ -54,11 +58,22 @@ def test_device_pack_is_bit_identical_to_the_host_pack(K, N):
     assert bad.value == 0
 
 
-@pytest.mark.parametrize('E,K,head_act,rep,rows', [(32, 32, 'tanh', 100, 41 * 100), (32, 1, 'none', 100, 64 * 100), (32, 32, 'tanh', 1, 4099),
-                                                   (64, 64, 'none', 10, 330), (8, 33, 'none', 1, 65), (32, 1, 'none', 1, 1)])
-def test_fused_forward_matches_float64(E, K, head_act, rep, rows):
+def _d266(E, K, head_act, rep, rows):
+    """a row at the learners' observation width (its id names no D: the ids of these six predate the D parameter)"""
+    return pytest.param(266, E, K, head_act, rep, rows, id='%d-%d-%s-%d-%d' % (E, K, head_act, rep, rows))
+
+
+@pytest.mark.parametrize('D,E,K,head_act,rep,rows', [
+    _d266(32, 32, 'tanh', 100, 41 * 100), _d266(32, 1, 'none', 100, 64 * 100), _d266(32, 32, 'tanh', 1, 4099),
+    _d266(64, 64, 'none', 10, 330), _d266(8, 33, 'none', 1, 65), _d266(32, 1, 'none', 1, 1),
+    # away from that width: >= 1024 distinct observations send the observation-side projection through launch_gemm_h16 (w1xp is
+    # sized by (D + 15) / 16) with D no multiple of 16, directly and through rep; action widths that leave a partial k-block in
+    # both KBX forms (16, 24 / 40, 48, 56); a nearly empty and a nearly full head column tile (2, 31, 33); rep values that do not
+    # divide the 64-row workgroup
+    (37, 16, 2, 'relu', 1, 1030), (10, 24, 31, 'sigmoid', 2, 2060), (266, 40, 64, 'none', 7, 133), (266, 56, 1, 'tanh', 3, 63),
+    (300, 48, 33, 'none', 1, 64), (266, 8, 1, 'none', 5, 325)])
+def test_fused_forward_matches_float64(D, E, K, head_act, rep, rows):
     import torch
-    D = 266
     net, params = _net(D, E, K, head_act, max_rows=max(rows, 256), seed=E + K)
     assert net.h16_ok
     rs = np.random.RandomState(rows)
@@ -75,8 +90,11 @@ def test_fused_forward_matches_float64(E, K, head_act, rep, rows):
     assert np.abs(got - want).max() <= 4 * np.abs(f32 - want).max() + 2e-6 * scale
     # rows are independent of their position in the launch (same rows, other offset)
     if rep == 1 and rows > 200:
-        again = net.forward(o[70:].contiguous(), a[70:].contiguous(), nograd='fp16x2').cpu().numpy()
-        assert np.array_equal(again, got[70:])
+        # (an offset that keeps the second call on the same side of the 1024 distinct observations where the projection changes
+        # its GEMM, and the views 16-byte aligned: 4 rows where 70 would cross that count)
+        off = 70 if (rows >= 1024) == (rows - 70 >= 1024) else 4
+        again = net.forward(o[off:].contiguous(), a[off:].contiguous(), nograd='fp16x2').cpu().numpy()
+        assert np.array_equal(again, got[off:])
     net.close()
 
 

@@ -24,25 +24,51 @@ def _close(got, want, rel, what):
     assert err <= rel * scale, '%s: max err %.3e vs scale %.3e' % (what, err, scale)
 
 
-def _pair(act_dim, out_dim, seed, head_act='none', max_rows=512, heads=1, obs_dim=D):
+# whole updates away from the default widths (BCQ: obs_dim D, action E, latent L, minibatch B, sampled actions n)
+#   (40, 8, 16, 70, 67)   every network has the fp16x2 form (action / latent widths 8 and 16), n > 64: a second trip of the target's loop
+#   (37, 5, 7, 300, 3)    no network has it ('fp16x2' must fall back and still equal the per-phase path); every workspace take() and
+#                         noise offset has an odd size, and E != L tells the two apart; B > 256: the single-block reductions loop
+BCQ_DIMS = [(40, 8, 16, 70, 67), (37, 5, 7, 300, 3)]
+
+
+def _dims_id(d):
+    return 'x'.join(str(v) for v in d)
+
+
+def _nograd_and_dims():
+    """[fp32], [fp16x2]: today's geometry under the ids those cases always had; then every extra geometry with both"""
+    return [pytest.param(g, None, id=g) for g in ('fp32', 'fp16x2')] + \
+           [pytest.param(g, d, id='%s-%s' % (g, _dims_id(d))) for d in BCQ_DIMS for g in ('fp32', 'fp16x2')]
+
+
+def _pair(act_dim, out_dim, seed, head_act='none', max_rows=512, heads=1, obs_dim=D, D=None, E=None, L=None):
+    """(``D``: the same as ``obs_dim``; ``E`` / ``L`` are whatever the caller passes as act_dim / out_dim)"""
     from oracle.offline_conti import OracleAMLP
     from rl4rs_amd import device as Dv
     from rl4rs_amd.offline_rl import init_amlp_params
+    obs_dim = obs_dim if D is None else D
     p = init_amlp_params(obs_dim, act_dim, out_dim, seed=seed, heads=heads)
     return Dv.DeviceAMLP(obs_dim, act_dim, out_dim, p, head_act=head_act, max_rows=max_rows), OracleAMLP(p, head_act), p
 
 
-def _batch(n, seed):
-    """rows shaped like the d3rl-mode observation (256 floats | 9 ids | step) with unit-norm 32-d actions"""
+def _batch(n, seed, D=D, E=E, L=L):
+    """rows shaped like the d3rl-mode observation (256 floats | 9 ids | step) with unit-norm 32-d actions; at another ``D`` the
+    observation is unit-scale noise with its last column a step count, at another ``E`` the actions are unit-norm E-vectors"""
     rs = np.random.RandomState(seed)
     x = rs.randn(n, D).astype(np.float32)
-    x[:, 256:265] = rs.randint(0, 284, size=(n, 9))
-    x[:, 265] = rs.randint(0, 10, size=n)
+    if D == 266:
+        x[:, 256:265] = rs.randint(0, 284, size=(n, 9))
+        x[:, 265] = rs.randint(0, 10, size=n)
+    else:
+        x[:, D - 1] = rs.randint(0, 10, size=n)
     a = rs.randn(n, E).astype(np.float32)
     a /= np.linalg.norm(a, axis=1, keepdims=True)
     rew = (rs.rand(n) * 5).astype(np.float32)
     ter = (rs.rand(n) < 0.15).astype(np.float32)
     return x, a, rew, ter
+
+
+_batch_ = _batch
 
 
 @pytest.fixture
@@ -124,15 +150,17 @@ def test_twin_networks_in_one_launch_equal_single_calls(amlp_fused, fused):
         q.close()
 
 
-@pytest.mark.parametrize('nograd', ['fp32', 'fp16x2'])
-def test_update_as_one_library_call_equals_the_per_phase_calls(nograd):
+@pytest.mark.parametrize('nograd,dims', _nograd_and_dims())
+def test_update_as_one_library_call_equals_the_per_phase_calls(nograd, dims):
     """rl4rs_bcq_update (the whole update as one host call, the default on one rank) issues the same launches with the same
     arguments as BCQ.update's per-phase path: parameters and Adam state bit-identical over four updates with shared noise,
-    with and without the actor phase (update_actor_interval = 2)"""
+    with and without the actor phase (update_actor_interval = 2).  ``dims``: BCQ_DIMS - the workspace carving and the noise
+    offsets of the one call at widths where no take() is a multiple of 4 floats and E != L"""
     import torch
-    B, n = 64, 8
-    a, _ = _learner_pair(61, B, n, nograd=nograd)
-    b, _ = _learner_pair(61, B, n, nograd=nograd)
+    D, E, L, B, n = dims or (266, 32, 32, 64, 8)
+    _batch = lambda rows, seed: _batch_(rows, seed, D=D, E=E)
+    a, _ = _learner_pair(61, B, n, nograd=nograd, D=D, E=E, L=L)
+    b, _ = _learner_pair(61, B, n, nograd=nograd, D=D, E=E, L=L)
     a.update_actor_interval = b.update_actor_interval = 2
     assert a.one_call
     b.one_call = False
@@ -324,16 +352,17 @@ def test_logstd_clamp_blocks_the_gradient():
     assert (d[0, L:] == 0).all() and (d[1, L:] == 0).all() and (d[2, L:] != 0).all() and (d[3, L:] != 0).all()
 
 
-def _learner_pair(seed, B, n, scale=None, nograd='fp32'):
+def _learner_pair(seed, B, n, scale=None, nograd='fp32', D=D, E=E, L=L):
     """a device BCQ learner and float64 oracle networks holding the same parameters (``scale``: {network: factor} applied to
     its initial parameters first).  ``nograd='fp16x2'``: the sampled-action forwards through the fused fp16x2 kernel at ANY row
-    count (by default it takes over from 4096 rows: the bench's 25 600 / 409 600, not a test's few hundred)"""
+    count (by default it takes over from 4096 rows: the bench's 25 600 / 409 600, not a test's few hundred) - in every network
+    whose action width has that form (8 .. 64 in multiples of 8: all of them at the default widths); the others fall back"""
     from oracle.offline_conti import OracleAMLP
     from rl4rs_amd.offline_rl import BCQ
-    bcq = BCQ({'action_emb_size': E}, D, batch_size=B, n_action_samples=n, predict_rows=64, seed=seed, nograd_precision=nograd)
+    bcq = BCQ({'action_emb_size': E}, D, batch_size=B, n_action_samples=n, predict_rows=64, seed=seed, nograd_precision=nograd, latent_size=L)
     if nograd == 'fp16x2':
         for net in bcq.nets:
-            assert net.h16_ok
+            assert net.h16_ok == (net.E % 8 == 0 and 8 <= net.E <= 64), (net.E, net.h16_ok)
             net.H16_MIN_ROWS = 0
     for k, f in (scale or {}).items():
         net = getattr(bcq, k)
@@ -419,14 +448,17 @@ def test_residual_clamp_and_target_rules():
     assert best.cpu().tolist() == [1] and float(v) == 5.0
 
 
-@pytest.mark.parametrize('nograd', ['fp32', 'fp16x2'])
-def test_updates_track_the_fp64_restatement(nograd):
-    """three whole updates (imitator, critic, actor, soft target updates) with the same noise on both sides"""
+@pytest.mark.parametrize('nograd,dims', _nograd_and_dims())
+def test_updates_track_the_fp64_restatement(nograd, dims):
+    """three whole updates (imitator, critic, actor, soft target updates) with the same noise on both sides; ``dims``: BCQ_DIMS -
+    the loss and metrics kernels inside a whole update past one wave trip (n = 67) and one block (B = 300), same bars"""
     import torch
     from oracle import offline_conti as O
     from oracle.offline_rl import torch_adam
-    B, n, steps = 64, 8, 3
-    bcq, orc = _learner_pair(41, B, n, nograd=nograd)
+    steps = 3
+    D, E, L, B, n = dims or (266, 32, 32, 64, 8)
+    _batch = lambda rows, seed: _batch_(rows, seed, D=D, E=E)
+    bcq, orc = _learner_pair(41, B, n, nograd=nograd, D=D, E=E, L=L)
     P = dict((k, v.numpy_params()) for k, v in orc.items())
     heads = dict((k, v.head_act) for k, v in orc.items())
     M = dict((k, dict((pk, np.zeros_like(pv)) for pk, pv in P[k].items())) for k in P)

@@ -16,7 +16,16 @@ from test_gpu_offline_conti import D, E, _batch, _close, _make_cfg          # no
 pytestmark = pytest.mark.gpu
 
 
-def _learner_pair(seed, B, n, **kw):
+# whole updates away from the default widths (CQL: obs_dim D, action A, minibatch B, sampled actions n; m = 1 + 3n rows per observation)
+#   (37, 5, 33, 22)   m = 67: a second trip of the one-wave-per-row loops of k_cql_rows; odd widths in every workspace take()
+#   (40, 8, 300, 2)   B > 256: a second trip of the single-block reductions (k_sum6, k_sac_temp_step, k_cql_metrics)
+CQL_DIMS = [(37, 5, 33, 22), (40, 8, 300, 2)]
+_dims_id = lambda d: 'x'.join(str(v) for v in d)
+_batch_ = _batch
+
+
+def _learner_pair(seed, B, n, D=D, E=E, L=None, **kw):
+    """(``E``: the action width A; CQL has no latent, ``L`` is accepted for symmetry with the BCQ helper and unused)"""
     from oracle.offline_conti import OracleAMLP
     from rl4rs_amd.offline_rl import CQL
     cql = CQL({'action_emb_size': E}, D, batch_size=B, n_action_samples=n, seed=seed, **kw)
@@ -29,11 +38,14 @@ def _learner_pair(seed, B, n, **kw):
     return cql, orc
 
 
-def _noise(rs, B, n):
+def _noise(rs, B, n, D=None, E=E, L=None):
     import torch
     f = lambda *s: torch.from_numpy(rs.randn(*s).astype(np.float32))
     u = lambda: torch.from_numpy(rs.uniform(-1, 1, size=(B, n, E)).astype(np.float32))
     return dict(eps_temp=f(B, E), alpha=(f(B * n, E), f(B * n, E), u()), critic=(f(B * n, E), f(B * n, E), u()), eps_actor=f(B, E))
+
+
+_noise_ = _noise
 
 
 def test_squashed_sample_and_log_prob():
@@ -81,11 +93,24 @@ def test_log_prob_is_stable_at_saturated_actions():
 
 
 def test_critic_actor_temperature_and_alpha_gradients():
+    _check_critic_actor_temperature_and_alpha_gradients(D, E, 48, 5)
+
+
+@pytest.mark.parametrize('dims', CQL_DIMS[:1], ids=_dims_id)
+def test_critic_actor_temperature_and_alpha_gradients_off_the_default_widths(dims):
+    """m = 67 rows per observation (a second trip of k_cql_rows' lane loops inside the learner's own phases), A = 5.  (Learner
+    seed 13: with 11 the first critic is the smaller one on all 33 rows of this geometry and the selector would go unexercised;
+    with 13 the float64 critics split the rows 9 / 24, the closest pair 6e-3 apart.)"""
+    _check_critic_actor_temperature_and_alpha_gradients(*dims, seed=13)
+
+
+def _check_critic_actor_temperature_and_alpha_gradients(D, E, B, n, seed=11):
     import torch
     from oracle import offline_conti as O
     from rl4rs_amd import device as Dv
-    B, n = 48, 5
-    cql, orc = _learner_pair(11, B, n, gamma=1.0)
+    _batch = lambda rows, seed: _batch_(rows, seed, D=D, E=E)
+    _noise = lambda rs, B, n: _noise_(rs, B, n, E=E)
+    cql, orc = _learner_pair(seed, B, n, gamma=1.0, D=D, E=E)
     m = cql.m
     x, a, rew, ter = _batch(B, 12)
     nx = _batch(B, 13)[0]
@@ -153,11 +178,24 @@ def test_critic_actor_temperature_and_alpha_gradients():
 
 def test_updates_track_the_fp64_restatement():
     """three whole updates (temperature, alpha, critic, actor, soft target update) with the same noise on both sides"""
+    _check_updates_track_the_fp64_restatement(D, E, 48, 4)
+
+
+@pytest.mark.parametrize('dims', CQL_DIMS, ids=_dims_id)
+def test_updates_track_the_fp64_restatement_off_the_default_widths(dims):
+    """the same three updates at CQL_DIMS, same bars: the device-side scalar steps and metrics (k_sac_temp_step, k_cql_alpha_step,
+    k_cql_metrics) are reachable only through the whole update"""
+    _check_updates_track_the_fp64_restatement(*dims)
+
+
+def _check_updates_track_the_fp64_restatement(D, E, B, n):
     import torch
     from oracle import offline_conti as O
     from oracle.offline_rl import torch_adam
-    B, n, steps = 48, 4, 3
-    cql, orc = _learner_pair(21, B, n, gamma=1.0)
+    steps = 3
+    _batch = lambda rows, seed: _batch_(rows, seed, D=D, E=E)
+    _noise = lambda rs, B, n: _noise_(rs, B, n, E=E)
+    cql, orc = _learner_pair(21, B, n, gamma=1.0, D=D, E=E)
     P = dict((k, v.numpy_params()) for k, v in orc.items())
     M = dict((k, dict((pk, np.zeros_like(pv)) for pk, pv in P[k].items())) for k in P)
     V = dict((k, dict((pk, np.zeros_like(pv)) for pk, pv in P[k].items())) for k in P)
@@ -226,10 +264,21 @@ def test_update_as_one_library_call_equals_the_per_phase_calls():
     """rl4rs_cql_update (the whole update as one host call with the learned scalars' Adam on the device; the default on one rank)
     against CQL.update's per-phase path over four updates with shared noise: the networks bit-identical wherever the two paths run
     the same kernels, the scalars and everything downstream of them equal to float32 rounding (device expf against torch.exp)"""
+    _check_update_as_one_library_call(D, E, 32, 4)
+
+
+@pytest.mark.parametrize('dims', CQL_DIMS, ids=_dims_id)
+def test_update_as_one_library_call_equals_the_per_phase_calls_off_the_default_widths(dims):
+    """the same at CQL_DIMS: the workspace carving and the noise-buffer offsets of the one call where no size is a multiple of 4"""
+    _check_update_as_one_library_call(*dims)
+
+
+def _check_update_as_one_library_call(D, E, B, n):
     import torch
-    B, n = 32, 4
-    a, _ = _learner_pair(71, B, n, gamma=1.0)
-    b, _ = _learner_pair(71, B, n, gamma=1.0)
+    _batch = lambda rows, seed: _batch_(rows, seed, D=D, E=E)
+    _noise = lambda rs, B, n: _noise_(rs, B, n, E=E)
+    a, _ = _learner_pair(71, B, n, gamma=1.0, D=D, E=E)
+    b, _ = _learner_pair(71, B, n, gamma=1.0, D=D, E=E)
     assert a.one_call
     b.one_call = False
     rs = np.random.RandomState(72)
