@@ -234,7 +234,8 @@ typedef struct rl4rs_dien_cfg {
  *   AUGRU_H16       first-generation fp16x2 recurrence k_augru_h16 instead of k_augru_x
  *   AUGRU_ROWS32    k_augru_x: 32-row workgroups for every launch (=)
  *   AUGRU_ROWS64    k_augru_x: 64-row workgroups whenever the launch shape admits them (R % 64 == 0, rows in whole groups
- *                   of 8 per cache slot), not only when that still fills the chip twice over (=); see rl4rs_dien_set_augru_rows
+ *                   of 8 per cache slot, or in groups of 9: 63 rows per workgroup), not only when that still fills the chip
+ *                   twice over (=); see rl4rs_dien_set_augru_rows
  *   DIN_V1          first-generation attention-score kernel k_din_scores instead of k_din_x
  *   NO_DIN16 / NO_GRU16 / NO_GEMM16 / NO_CAT16   keep the exact-fp32 MFMA form of the attention MLP / first GRU / plain GEMMs /
  *                   category self-attention in fp16x2 mode
@@ -353,6 +354,11 @@ int rl4rs_dien_encode(rl4rs_dien* net, int32_t s, const int32_t* ids_dev, int32_
 int rl4rs_dien_forward(rl4rs_dien* net, int32_t R, int32_t group, const float* dense_dev,
                        const int32_t* cat_dev, const int32_t* slot_dev, float* obs_dev,
                        float* prob_dev, void* stream);
+
+/* The NEXT rl4rs_dien_forward of this handle (one call, and one that returns probabilities) also stores the 'simulator_obs'
+ * activations of the LAST row of each group: obs_last_dev [R / group, 256] f32 - without writing all R rows to the caller.  The
+ * values are the head's own rows: bit-identical to a group-1 forward of that row.  NULL disarms. */
+int rl4rs_dien_set_obs_last(rl4rs_dien* net, float* obs_last_dev);
 
 /* softmax(obs @ out_w + out_b)[:, 1] of already computed 'simulator_obs' activations (dien.py:36):
  * obs_dev [R, 256] -> prob_dev [R]. */
@@ -488,6 +494,22 @@ int rl4rs_env_step_discrete(rl4rs_stepper* s, const int32_t* actions_dev, float*
  * the next one.  rl4rs_stepper_set_act_tail(s, 0): the launches as they were (k_step_tail, no next-step ids); bit-identical
  * outputs either way. */
 int rl4rs_stepper_set_act_tail(rl4rs_stepper* s, int32_t on);
+/* On a reward step of rl4rs_env_step_discrete / _conti with the DIEN scorer in fp16x2 mode (k_augru_x), the state row is scored
+ * INSIDE the reward forward - one forward of n_complete rows per env that returns every row's probability and, through
+ * rl4rs_dien_set_obs_last, the observation - instead of an observation forward followed by a forward of n_complete - 1 rows.
+ * Taken only when that forward's k_augru_x launch runs 64-row workgroups (a batch large enough to fill the chip twice over, or the
+ * form pinned) and needs no more rounds of workgroups over the chip than the smaller one, counted on
+ * rl4rs_stepper_set_distinct_hint's number of envs the scorer's row dedup is expected to leave (default: the batch size; a
+ * batch drawn with replacement passes its number of distinct log lines).  rl4rs_stepper_set_obs_fold(s, 0): the two-forward order
+ * as it was; bit-identical outputs either way.  rl4rs_env_step_record* keep the two-forward order. */
+int rl4rs_stepper_set_obs_fold(rl4rs_stepper* s, int32_t on);
+int rl4rs_stepper_set_distinct_hint(rl4rs_stepper* s, int32_t n_distinct);
+/* Click probabilities of the complete-state rows of the LAST reward step, slate order: out_dev [B, n_complete] f32 - the same
+ * numbers in either order of the forwards (the record form's click_p part, for rl4rs_env_step_discrete / _conti). */
+int rl4rs_stepper_click_probs(rl4rs_stepper* s, float* out_dev, void* stream);
+/* Rows per env the reward forward of the last reward step scored: n_complete (the state row inside it), n_complete - 1 (the
+ * two-forward order), 0 before the first reward step. */
+int rl4rs_stepper_reward_rows(const rl4rs_stepper* s);
 int rl4rs_stepper_next_offline_action(rl4rs_stepper* s, const int32_t** ids_dev, int32_t* step);
 /* continuous actions: [B, action_emb_size] float32 / float64 resolved by the masked float64 K-NN first (slate.py:187-197);
  * chosen_dev (optional) receives the item ids played */

@@ -238,6 +238,7 @@ SIGNATURES = {
     'rl4rs_rawtrain_adam_step': (_I, [_P, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _P]),
     'rl4rs_policy_ppo_epoch': (_I, [_P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P] + [C.c_float] * 10 + [_P, _P, _P]),
     'rl4rs_dien_set_row_order': (_I, [_P, _P, _I32]),
+    'rl4rs_dien_set_obs_last': (_I, [_P, _P]),
     'rl4rs_dien_set_augru_rows': (_I, [_P, _I32]),
     'rl4rs_dien_status_word': (_I, [_P, C.POINTER(_P)]),
     'rl4rs_stepper_record_layout': (_I, [_P, C.c_uint32, _I32, C.POINTER(StepRecord)]),
@@ -252,6 +253,10 @@ SIGNATURES = {
     'rl4rs_env_attach_simnet': (_I, [_P, _P, _P, _I32, _P]),
     'rl4rs_stepper_destroy': (_I, [_P]),
     'rl4rs_stepper_set_act_tail': (_I, [_P, _I32]),
+    'rl4rs_stepper_set_obs_fold': (_I, [_P, _I32]),
+    'rl4rs_stepper_set_distinct_hint': (_I, [_P, _I32]),
+    'rl4rs_stepper_click_probs': (_I, [_P, _P, _P]),
+    'rl4rs_stepper_reward_rows': (_I, [_P]),
     'rl4rs_stepper_next_offline_action': (_I, [_P, _P, _P]),
     'rl4rs_env_step_discrete': (_I, [_P, _P, _P, _P, _P, _P, _P]),
     'rl4rs_env_step_conti': (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _P]),

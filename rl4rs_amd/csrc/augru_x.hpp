@@ -129,7 +129,11 @@ typedef __attribute__((address_space(3))) void* lds_ptr_t;
 // fragment feeds two row tiles (half the weight bytes per row through the L1 return path), and the 8 distinct projection rows
 // of the workgroup are staged once (1 KB per gate and wave, one DMA instruction).
 // PAD (instantiated for MT = 1): steps below a row's count of leading zero ids read the projections of the pad slot (RecurArgs::lead / pad_slot).
-template <int MT, int NRES, int RING, bool PAD = false>
+// GRP (MT = 2 only): consecutive rows per cache slot.  8: a tile is 8 whole groups.  9 (a reward forward that also scores the state
+// row: 9 complete-state rows per env): a tile is 7 whole groups = 63 positions, row0 advances by 63, tile row r reads staged row
+// r / 9, and tile position 63 is a clamped position - it computes batch position min(row0 + 63, n_rows - 1), whose slot lane group
+// 7 of the projection DMA stages, and is not stored (the workgroup of the next tile stores that row).  The step loop is the same.
+template <int MT, int NRES, int RING, bool PAD = false, int GRP = 8>
 __global__ __launch_bounds__(512) void k_augru_x(RecurArgs a) {
     using namespace xk;
     constexpr int NH = 256, KB = 16, PLANE = 32 * NH * 2;          // bytes per plane (16 KB)
@@ -140,6 +144,8 @@ __global__ __launch_bounds__(512) void k_augru_x(RecurArgs a) {
 #endif
     constexpr Sched SC = make_sched<NRES>();
     constexpr bool PEEL = MT == 1 ? RL4RS_X_PEEL != 0 : RL4RS_X_PEEL_MT2 != 0;
+    static_assert(GRP == 8 || (GRP == 9 && MT == 2 && !PAD), "rows per cache slot of the 64-row form");
+    constexpr int ROWS = GRP == 9 ? 63 : 32 * MT;                  // positions a workgroup stores
     static_assert(NS > 0 && NS % RING == 0 && RING >= 2 && NRES >= 1 && NRES <= 14 && (!RL4RS_X_SPREAD || NI % NRES == 0), "weight ring / resident items");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // planes in slab order [kb 16][k-half 2][row 32][8 halfs]; tile m's four planes (h hi/lo, r*h hi/lo) at m * 4 * PLANE
@@ -151,7 +157,7 @@ __global__ __launch_bounds__(512) void k_augru_x(RecurArgs a) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int half = lane >> 5, li = lane & 31;
-    const int row0 = blockIdx.x * 32 * MT;
+    const int row0 = blockIdx.x * ROWS;
     const int sq = blockIdx.y;
     // row dedup (row_dedup.hpp): the launch works on the first n_active entries of a.order only - the grid is sized for a.n_rows
     // on the host, a workgroup behind the bound leaves here
@@ -184,8 +190,8 @@ __global__ __launch_bounds__(512) void k_augru_x(RecurArgs a) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         // MT = 1: row r = 8j + l/8, rotated chunk.  MT = 2 (only j = 0 is used): lane l fetches chunk l%8 of distinct row d = l/8,
-        // i.e. of batch row row0 + 8d (rows 8d .. 8d+7 share its cache slot)
-        const int r = MT == 1 ? 8 * j + (lane >> 3) : 8 * (lane >> 3);
+        // i.e. of batch row row0 + GRP d (rows GRP d .. GRP d + GRP - 1 share its cache slot)
+        const int r = MT == 1 ? 8 * j + (lane >> 3) : GRP * (lane >> 3);
         const int gr = phys(row0 + r);
         const int c = MT == 1 ? (((lane & 7) - (r >> 1)) & 7) : (lane & 7);
         const uint32_t slot = (uint32_t)a.slots[(size_t)sq * a.slots_stride + gr / a.group];
@@ -213,10 +219,16 @@ __global__ __launch_bounds__(512) void k_augru_x(RecurArgs a) {
     };
     auto x_read = [&](f32x16& dst, int g, int m) {                 // staged projection rows -> accumulator (MFMA C-in)
         const int rot = half + (li >> 1);
+        int srow = 4 * m + (li >> 3);                              // staged row of tile row 32 m + li
+        if constexpr (GRP == 9) {
+            int tr = 32 * m + li;
+            asm volatile("" : "+v"(tr));                           // recomputed at every read: held across the step it costs a register the form does not have
+            srow = (tr * 57) >> 9;                                 // tr / 9 for tr < 64
+        }
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const char* src = MT == 1 ? stage + g * 4096 + li * 128 + (((2 * q + rot) & 7) << 4)
-                                      : stage + g * 1024 + (4 * m + (li >> 3)) * 128 + ((2 * q + half) << 4);
+                                      : stage + g * 1024 + srow * 128 + ((2 * q + half) << 4);
             const float4 v = *reinterpret_cast<const float4*>(src);
             dst[4 * q + 0] = v.x; dst[4 * q + 1] = v.y; dst[4 * q + 2] = v.z; dst[4 * q + 3] = v.w;
         }
@@ -517,7 +529,7 @@ __global__ __launch_bounds__(512) void k_augru_x(RecurArgs a) {
     for (int m = 0; m < MT; ++m) {
         const int row = phys(row0 + m * 32 + li);
         const bool poison = s_bad[m * 32 + li] != 0u;
-        if (row0 + m * 32 + li < n_rows) {
+        if (row0 + m * 32 + li < n_rows && m * 32 + li < ROWS) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 float4 v = make_float4(h_own[m][4 * q], h_own[m][4 * q + 1], h_own[m][4 * q + 2], h_own[m][4 * q + 3]);

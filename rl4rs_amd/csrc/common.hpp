@@ -143,6 +143,13 @@ int env_act_discrete_tail(rl4rs_env* e, const int32_t* actions, const ActTail& t
 // the head GEMM's epilogue - step.hip's reference-shaped records (dien.hip); dien_obs_mirror_used: did that forward take it?
 void dien_set_obs_mirror(rl4rs_dien* n, float* host_visible);
 bool dien_obs_mirror_used(const rl4rs_dien* n);
+// Rounds (waves of workgroups over the chip's CUs) of the k_augru_x launch of a forward of B groups of `group` rows of which `live`
+// are expected to be distinct (row_dedup.hpp), under the row-tile form rl4rs_dien_forward would pick for it; -1: the forward does not
+// run k_augru_x (fp32 mode, augru_h16) or does not fit the handle's max_rows.  step.hip decides with it whether a reward step
+// scores the state row inside the reward forward.
+int64_t dien_augru_rounds(const rl4rs_dien* n, int B, int live, int group);
+// Would that forward's k_augru_x launch run the 64-row form (automatic rule or pinned)?
+bool dien_augru_rows64(const rl4rs_dien* n, int B, int group);
 
 // Training-mode recurrences as persistent kernels (recur_train.hpp, compiled into dien.hip; called from dientrain.hpp).
 // Arrays are per sequence input (S <= 4 inputs run in ONE launch, grid.y = S); saved tensors are [N * L, Hd] row-major.

@@ -1667,10 +1667,13 @@ namespace rl4rs {
 // softmax(obs @ out_w + out_b)[:, 1]  (dien.py:36, slate.py:298).  One wave per row.
 __global__ __launch_bounds__(256) void k_head_prob(const float* __restrict__ obs, int R, int D, int K,
                                                    const float* __restrict__ w, const float* __restrict__ b,
-                                                   float* __restrict__ prob) {
+                                                   float* __restrict__ prob, int group, float* __restrict__ obs_last) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + wave;
     if (row >= R) return;
+    // obs_last [R / group, D]: the activations of the last row of each group of `group` rows, copied as they are (rl4rs_dien_set_obs_last)
+    if (obs_last && row % group == group - 1)
+        for (int k = lane; k < D; k += 64) obs_last[(size_t)(row / group) * D + k] = obs[(size_t)row * D + k];
     float logit[8];
     for (int c = 0; c < K; ++c) {
         float s = 0.f;
@@ -1786,6 +1789,7 @@ struct rl4rs_dien {
     float *allf, *dh, *q, *scores, *obs_tmp;
     float* obs_mirror;     // rl4rs_dien_set_obs_mirror: device-visible host memory [R, OBS_DIM] for the NEXT forward's observation
     bool obs_mirror_used;  // ... whether that forward's head kernel took it (only the fp16x2 GEMM with the table addend writes mirrors)
+    float* obs_last;       // rl4rs_dien_set_obs_last: [R / group, OBS_DIM] for the NEXT forward's observation of each group's last row
     std::vector<void*> owned;
     // profiling
     int profiling;         // 0 off, 1 every kernel class, 2 only the AUGRU recurrence (two event records per forward)
@@ -2313,6 +2317,19 @@ static bool dien_gemm_grouped(const rl4rs_dien* n) {
     return n->fp16x2 && n->gemm16 && n->gemm_group && n->dense_chain && n->U <= 128 && n->U % 16 == 0 && !n->dense_fork;
 }
 
+// k_augru_x: 64-row workgroups when the rows come in whole groups of 8 per cache slot (the reward forward), or in groups of 9 (the
+// reward forward that also scores the state row: 7 groups = 63 rows per workgroup), and there are enough workgroups to fill the chip
+// twice over; 32-row workgroups otherwise (obs-sized launches: one 32-row tile per CU)
+// (n->augru_rows = 32 / 64 pins the form: rl4rs_dien_cfg.kernel_opts, rl4rs_dien_set_augru_rows)
+static bool augru_rows64(const rl4rs_dien* n, int R, int group) {
+    if (n->augru_rows == 32) return false;
+    int64_t tiles;
+    if (group == 9) tiles = (R / 9 + 6) / 7;
+    else if (group % 8 == 0 && R % 64 == 0) tiles = R / 64;
+    else return false;
+    return n->augru_rows == 64 || tiles * n->S >= 2 * (int64_t)n->n_cu;
+}
+
 int rl4rs_dien_forward(rl4rs_dien* n, int32_t R, int32_t group, const float* dense, const int32_t* cat,
                        const int32_t* slots, float* obs, float* prob, void* stream) {
     RL4RS_REQUIRE(n && dense && cat && slots, "dien_forward: null argument");
@@ -2324,7 +2341,8 @@ int rl4rs_dien_forward(rl4rs_dien* n, int32_t R, int32_t group, const float* den
     const int ngroups = R / group;
     int rc;
     n->obs_mirror_used = false;
-    struct MirrorOnce { rl4rs_dien* n; ~MirrorOnce() { n->obs_mirror = nullptr; } } mirror_once{n};       // one forward only
+    struct MirrorOnce { rl4rs_dien* n; ~MirrorOnce() { n->obs_mirror = nullptr; n->obs_last = nullptr; } } mirror_once{n};       // one forward only
+    RL4RS_REQUIRE(!n->obs_last || prob, "dien_forward: rl4rs_dien_set_obs_last needs a forward that returns probabilities");
     auto dense_tower = [&](hipStream_t s2) -> int {
         int r2;
         if (n->gemm16 && n->dense_chain && U <= 128 && U % 16 == 0) {      // both layers in one launch, the hidden tile stays in LDS
@@ -2503,11 +2521,7 @@ int rl4rs_dien_forward(rl4rs_dien* n, int32_t R, int32_t group, const float* den
                 if (f) { fwrite(host, 1, sizeof(host), f); fclose(f); }
             }
 #endif
-            // 64-row workgroups when the rows come in whole groups of 8 per cache slot (the reward forward) and there are enough
-            // of them to keep every CU busy; 32-row workgroups otherwise (obs-sized launches: one 32-row tile per CU)
-            // (n->augru_rows = 32 / 64 pins the form: rl4rs_dien_cfg.kernel_opts, rl4rs_dien_set_augru_rows)
-            const bool mt2 = n->augru_rows != 32 && group % 8 == 0 && R % 64 == 0 &&
-                             (n->augru_rows == 64 || (int64_t)(R / 64) * S >= 2 * (int64_t)n->n_cu);
+            const bool mt2 = augru_rows64(n, R, group);
             if (n->augru_x)
                 augru_x_launch(mt2 ? 64 : 32, S, st, a);
             else
@@ -2564,7 +2578,7 @@ int rl4rs_dien_forward(rl4rs_dien* n, int32_t R, int32_t group, const float* den
     if (prob) {
         Prof p(n, KID_PROB, st);
         hipLaunchKernelGGL(k_head_prob, dim3((R + 3) / 4), dim3(256), 0, st, obs_out, R, OBS_DIM, n->K, n->out_w,
-                           n->out_b, prob);
+                           n->out_b, prob, group, n->obs_last);
         RL4RS_LAUNCH_CHECK();
     }
     return RL4RS_OK;
@@ -2574,7 +2588,7 @@ int rl4rs_dien_head_prob(rl4rs_dien* n, int32_t R, const float* obs, float* prob
     RL4RS_REQUIRE(n && obs && prob && R > 0, "dien_head_prob: bad argument");
     hipStream_t st = (hipStream_t)stream;
     Prof p(n, KID_PROB, st);
-    hipLaunchKernelGGL(k_head_prob, dim3((R + 3) / 4), dim3(256), 0, st, obs, R, OBS_DIM, n->K, n->out_w, n->out_b, prob);
+    hipLaunchKernelGGL(k_head_prob, dim3((R + 3) / 4), dim3(256), 0, st, obs, R, OBS_DIM, n->K, n->out_w, n->out_b, prob, 1, nullptr);
     RL4RS_LAUNCH_CHECK();
     return RL4RS_OK;
 }
@@ -2614,11 +2628,19 @@ int rl4rs_dien_set_row_order(rl4rs_dien* n, const int32_t* order_dev, int32_t n_
 }
 
 // Row-tile form of k_augru_x for the following forwards: 0 = automatic (64-row workgroups for reward-sized launches, see
-// rl4rs_dien_forward), 32 = always 32-row workgroups, 64 = 64-row workgroups whenever the launch shape admits them (rows in
-// whole groups of 8 per cache slot, R % 64 == 0).  Both forms run the same MFMA sequence per row: results are bit-identical.
+// augru_rows64), 32 = always 32-row workgroups, 64 = 64-row workgroups whenever the launch shape admits them (rows in
+// whole groups of 8 per cache slot and R % 64 == 0, or groups of 9).  Both forms run the same MFMA sequence per row: results are bit-identical.
 int rl4rs_dien_set_augru_rows(rl4rs_dien* n, int32_t rows) {
     RL4RS_REQUIRE(n && (rows == 0 || rows == 32 || rows == 64), "dien_set_augru_rows: rows must be 0, 32 or 64");
     n->augru_rows = rows;
+    return RL4RS_OK;
+}
+
+// The NEXT forward (one that returns probabilities) also stores the 'simulator_obs' activations of the last row of each group:
+// obs_last_dev [R / group, 256].  The values are the head GEMM's own rows, copied by k_head_prob.
+int rl4rs_dien_set_obs_last(rl4rs_dien* n, float* obs_last_dev) {
+    RL4RS_REQUIRE(n, "dien_set_obs_last: null handle");
+    n->obs_last = obs_last_dev;
     return RL4RS_OK;
 }
 
@@ -2647,6 +2669,15 @@ int rl4rs_dien_status(rl4rs_dien* n, int32_t* flags, void* stream) {
 namespace rl4rs {
 void dien_set_obs_mirror(rl4rs_dien* n, float* host_visible) { if (n) n->obs_mirror = host_visible; }
 bool dien_obs_mirror_used(const rl4rs_dien* n) { return n && n->obs_mirror_used; }
+bool dien_augru_rows64(const rl4rs_dien* n, int B, int group) {
+    return n && n->fp16x2 && n->augru_x && (int64_t)B * group <= n->c.max_rows && augru_rows64(n, B * group, group);
+}
+int64_t dien_augru_rounds(const rl4rs_dien* n, int B, int live, int group) {
+    if (!n || !n->fp16x2 || !n->augru_x || (int64_t)B * group > n->c.max_rows) return -1;
+    const int64_t G = n->row_dedup ? (live < B ? live : B) : B;
+    const int64_t tiles = !augru_rows64(n, B * group, group) ? (G * group + 31) / 32 : (group == 9 ? (G + 6) / 7 : (G * group + 63) / 64);
+    return (tiles * n->S + n->n_cu - 1) / n->n_cu;
+}
 }  // namespace rl4rs
 extern "C" {
 // The status word itself (device pointer owned by the handle, != 0 <=> RL4RS_DIEN_STATUS_FP16_RANGE pending): a caller that

@@ -223,7 +223,7 @@ int rl4rs_simnet_encode(rl4rs_simnet* n, int32_t s, const int32_t* ids, int32_t 
 int rl4rs_simnet_head_prob(rl4rs_simnet* n, int32_t R, const float* obs, float* prob, void* stream) {
     RL4RS_REQUIRE(n && obs && prob && R > 0, "simnet_head_prob: bad argument");
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_head_prob, dim3((R + 3) / 4), dim3(256), 0, st, obs, R, n->obs_dim, n->c.class_num, n->out_w, n->out_b, prob);
+    hipLaunchKernelGGL(k_head_prob, dim3((R + 3) / 4), dim3(256), 0, st, obs, R, n->obs_dim, n->c.class_num, n->out_w, n->out_b, prob, 1, nullptr);
     RL4RS_LAUNCH_CHECK();
     return RL4RS_OK;
 }
@@ -272,7 +272,7 @@ int rl4rs_simnet_forward(rl4rs_simnet* n, int32_t R, int32_t group, const float*
         if ((rc = launch_gemm_packed(n->feat, F, n->obs_w, n->obs_b, o, OD, R, 256, F, 1, st))) return rc;
     }
     if (prob) {
-        hipLaunchKernelGGL(k_head_prob, dim3((R + 3) / 4), dim3(256), 0, st, o, R, OD, n->c.class_num, n->out_w, n->out_b, prob);
+        hipLaunchKernelGGL(k_head_prob, dim3((R + 3) / 4), dim3(256), 0, st, o, R, OD, n->c.class_num, n->out_w, n->out_b, prob, 1, nullptr);
         RL4RS_LAUNCH_CHECK();
     }
     return RL4RS_OK;

@@ -5,7 +5,8 @@
 //   done     = step >= max_steps-1 base.py:165-168
 // composed from the same entry points the host facade uses one by one (rl4rs_env_act_*, rl4rs_dien_forward / rl4rs_simnet_forward,
 // rl4rs_env_build_complete_rows, *_head_prob, rl4rs_env_reward_split, rl4rs_env_obs_mask): identical kernels in identical order,
-// so the results are bit-identical to the composed path (tests/test_gpu_facade.py::test_fused_step_is_bit_identical).  Nothing is
+// so the results are bit-identical to the composed path (tests/test_gpu_facade.py::test_fused_step_is_bit_identical).  One
+// exception in order, not in results: a reward step may score the state row inside the reward forward (fold_obs below).  Nothing is
 // allocated and nothing synchronises inside: all scratch belongs to the binding created by rl4rs_env_attach_scorer.
 #include "common.hpp"
 
@@ -19,12 +20,15 @@ struct rl4rs_stepper {
     int32_t seq_num;
     rl4rs_env_cfg cfg;
     int n_complete;
-    float* probs;              // [B * (n_complete - 1)] click probabilities of the complete-state rows
+    float* probs;              // [B * n_complete] click probabilities of the complete-state rows (n_complete - 1 per env in the two-forward order)
     float* p_last;             // [B] probability of the state row just scored (= the last complete-state row)
     const float* dense; const int32_t* cat; const int32_t* seq1; const float* c_dense; const int32_t* c_cat;
     // rl4rs_env_step_discrete: the act kernel also writes done, the zero reward and the NEXT step's logged action (ActTail) - no
     // k_step_tail launch, and a replay loop needs no rl4rs_env_offline_action launch between two steps
     bool act_tail;             // rl4rs_stepper_set_act_tail (default on)
+    bool obs_fold;             // rl4rs_stepper_set_obs_fold (default on): a reward step scores the state row inside the reward forward
+    int distinct_hint;         // rl4rs_stepper_set_distinct_hint: envs expected to stay distinct under the scorer's row dedup (default B)
+    int probs_rows;            // rows per env the last reward step left in `probs`: n_complete (folded), n_complete - 1 (+ p_last), 0 = none yet
     int32_t* next_off;         // [max_steps + 1][B]: row c = the logged item ids of step c, written by the step that led to it - a row
                                // of its own per step of an episode, so a caller may hold what it was handed until the episode ends
     int next_off_cur;          // the step whose row the last transition wrote, -1 = none
@@ -73,9 +77,25 @@ __global__ void k_step_tail(uint8_t* done, uint8_t v, double* zero_reward, int n
 // observation forward has been enqueued (the record form sends the observation home from there on a reward step, beside the
 // reward forward).
 struct NoHook { int operator()() const { return RL4RS_OK; } };
+
+// A reward step's observation row is the last complete-state row of its env (same prev_actions, its action the item just played):
+// ONE forward of n_complete rows per env gives the probabilities of all rows and, through rl4rs_dien_set_obs_last, the observation -
+// the observation-sized forward (bound by one workgroup's 64-step chain, the chip mostly idle) is not launched.  Taken when the
+// scorer is the DIEN with k_augru_x, the n-row forward runs the 64-row form of k_augru_x (where a row costs about a quarter of what it
+// costs in the chain-bound observation launch: the regime the fold was measured in; a small batch, whose n-row launch falls to 32-row
+// workgroups, keeps the two-forward order) and the n-row launch needs no more rounds over the chip than the (n - 1)-row one.
+bool fold_obs(const rl4rs_stepper* s) {
+    const int n = s->n_complete, B = s->cfg.batch_size;
+    if (!s->obs_fold || !s->dien || n < 2) return false;
+    if (!rl4rs::dien_augru_rows64(s->dien, B, n)) return false;
+    const int64_t with = rl4rs::dien_augru_rounds(s->dien, B, s->distinct_hint, n);
+    const int64_t without = rl4rs::dien_augru_rounds(s->dien, B, s->distinct_hint, n - 1);
+    return with > 0 && without > 0 && with <= without;
+}
+
 template <typename Hook = NoHook>
 int after_act(rl4rs_stepper* s, int cur_before, float* obs, double* reward, uint8_t* done, uint32_t* mask_bits, void* stream,
-              Hook on_obs = Hook(), bool tail_done = false) {
+              Hook on_obs = Hook(), bool tail_done = false, bool may_fold = false) {
     hipStream_t st = (hipStream_t)stream;
     rl4rs_env* e = s->env;
     const int B = s->cfg.batch_size;
@@ -85,6 +105,21 @@ int after_act(rl4rs_stepper* s, int cur_before, float* obs, double* reward, uint
         // but the first (prev_actions[:0] is the [0] the episode started with: nothing to re-encode)
         for (int q = 1; q < s->seq_num; ++q)
             if ((rc = scorer_encode(s, q, s->seq1, B, stream))) return rc;
+    }
+    if (may_fold && reward && rl4rs_env_is_reward_step(e) == 1 && fold_obs(s)) {
+        const int n = s->n_complete;
+        if ((rc = rl4rs_env_build_complete_rows(e, n, stream))) return rc;
+        if ((rc = rl4rs_dien_set_obs_last(s->dien, obs))) return rc;
+        if ((rc = scorer_forward(s, B * n, n, s->c_dense, s->c_cat, nullptr, s->probs, stream))) return rc;
+        if ((rc = rl4rs_env_reward_split(e, s->probs, nullptr, reward, stream))) return rc;
+        s->probs_rows = n;
+        if (done && !tail_done) {
+            hipLaunchKernelGGL(k_step_tail, dim3((B + 255) / 256), dim3(256), 0, st, done, (uint8_t)(cur_before >= s->cfg.max_steps - 1 ? 1 : 0),
+                               (double*)nullptr, B);
+            RL4RS_LAUNCH_CHECK();
+        }
+        if (mask_bits && (rc = rl4rs_env_obs_mask(e, mask_bits, 4, stream))) return rc;
+        return RL4RS_OK;
     }
     if ((rc = scorer_forward(s, B, 1, s->dense, s->cat, obs, nullptr, stream))) return rc;
     if ((rc = on_obs())) return rc;
@@ -99,6 +134,7 @@ int after_act(rl4rs_stepper* s, int cur_before, float* obs, double* reward, uint
             }
             if ((rc = scorer_head_prob(s, B, obs, s->p_last, stream))) return rc;
             if ((rc = rl4rs_env_reward_split(e, m > 0 ? s->probs : s->p_last, m > 0 ? s->p_last : nullptr, reward, stream))) return rc;
+            s->probs_rows = m;
         } else {
             zero_reward = reward;
         }
@@ -151,7 +187,7 @@ int attach(rl4rs_env* env, rl4rs_dien* dien, rl4rs_simnet* simnet, const int32_t
     s->n_complete = rl4rs_env_complete_rows(env);
     const size_t B = (size_t)s->cfg.batch_size;
     float* ring = nullptr;
-    if ((rc = dev_alloc(&s->probs, B * (size_t)(s->n_complete > 1 ? s->n_complete - 1 : 1))) || (rc = dev_alloc(&s->p_last, B)) ||
+    if ((rc = dev_alloc(&s->probs, B * (size_t)s->n_complete)) || (rc = dev_alloc(&s->p_last, B)) ||
         (rc = dev_alloc(&ring, B * (size_t)(s->cfg.max_steps + 1)))) {
         if (s->probs) (void)hipFree(s->probs);
         if (s->p_last) (void)hipFree(s->p_last);
@@ -161,6 +197,8 @@ int attach(rl4rs_env* env, rl4rs_dien* dien, rl4rs_simnet* simnet, const int32_t
     s->next_off = reinterpret_cast<int32_t*>(ring);
     s->next_off_cur = -1;
     s->act_tail = true;
+    s->obs_fold = true;
+    s->distinct_hint = s->cfg.batch_size;
     void* p;
     int64_t nb;
 #define BUF(which, field, type) if ((rc = rl4rs_env_buffer(env, which, &p, &nb))) { rl4rs_stepper_destroy(s); return rc; } s->field = reinterpret_cast<type>(p)
@@ -205,7 +243,7 @@ int rl4rs_env_step_discrete(rl4rs_stepper* s, const int32_t* actions_dev, float*
     if (!s->act_tail) {
         int rc = rl4rs_env_act_discrete(s->env, actions_dev, stream);
         if (rc) return rc;
-        return after_act(s, cur, obs_dev, reward_dev, done_dev, mask_bits_dev, stream);
+        return after_act(s, cur, obs_dev, reward_dev, done_dev, mask_bits_dev, stream, NoHook(), false, true);
     }
     // is a reward due after this act?  (rl4rs_env_is_reward_step at cur + 1; checked against it below)
     const int T = s->cfg.max_steps;
@@ -220,13 +258,41 @@ int rl4rs_env_step_discrete(rl4rs_stepper* s, const int32_t* actions_dev, float*
     if (tail.next_action) s->next_off_cur = cur + 1;
     // (a different answer from the env itself: k_step_tail runs as before and has the last word)
     const bool covered = rl4rs_env_is_reward_step(s->env) == due;
-    return after_act(s, cur, obs_dev, reward_dev, done_dev, mask_bits_dev, stream, NoHook(), covered);
+    return after_act(s, cur, obs_dev, reward_dev, done_dev, mask_bits_dev, stream, NoHook(), covered, true);
 }
 
 int rl4rs_stepper_set_act_tail(rl4rs_stepper* s, int32_t on) {
     RL4RS_REQUIRE(s, "stepper_set_act_tail: null argument");
     s->act_tail = on != 0;
     s->next_off_cur = -1;
+    return RL4RS_OK;
+}
+
+int rl4rs_stepper_set_obs_fold(rl4rs_stepper* s, int32_t on) {
+    RL4RS_REQUIRE(s, "stepper_set_obs_fold: null argument");
+    s->obs_fold = on != 0;
+    return RL4RS_OK;
+}
+
+int rl4rs_stepper_reward_rows(const rl4rs_stepper* s) { return s ? s->probs_rows : RL4RS_EINVAL; }
+
+int rl4rs_stepper_click_probs(rl4rs_stepper* s, float* out_dev, void* stream) {
+    RL4RS_REQUIRE(s && out_dev, "stepper_click_probs: null argument");
+    RL4RS_REQUIRE(s->n_complete >= 2 && s->probs_rows > 0, "stepper_click_probs: no reward step yet");
+    const int B = s->cfg.batch_size, n = s->n_complete;
+    hipStream_t st = (hipStream_t)stream;
+    if (s->probs_rows == n) {
+        RL4RS_HIP_TRY(hipMemcpyAsync(out_dev, s->probs, (size_t)B * n * 4, hipMemcpyDeviceToDevice, st));
+    } else {
+        hipLaunchKernelGGL(k_record_click, dim3((B * n + 255) / 256), dim3(256), 0, st, s->probs, s->p_last, n - 1, out_dev, B);
+        RL4RS_LAUNCH_CHECK();
+    }
+    return RL4RS_OK;
+}
+
+int rl4rs_stepper_set_distinct_hint(rl4rs_stepper* s, int32_t n_distinct) {
+    RL4RS_REQUIRE(s && n_distinct >= 1, "stepper_set_distinct_hint: bad argument");
+    s->distinct_hint = n_distinct < s->cfg.batch_size ? n_distinct : s->cfg.batch_size;
     return RL4RS_OK;
 }
 
@@ -244,7 +310,7 @@ int rl4rs_env_step_conti(rl4rs_stepper* s, const void* actions_dev, int is_f64, 
     s->next_off_cur = -1;
     int rc = rl4rs_env_act_conti(s->env, actions_dev, is_f64, chosen_dev, stream);
     if (rc) return rc;
-    return after_act(s, cur, obs_dev, reward_dev, done_dev, mask_bits_dev, stream);
+    return after_act(s, cur, obs_dev, reward_dev, done_dev, mask_bits_dev, stream, NoHook(), false, true);
 }
 
 // ---- reference-shaped (host-returning) transition ---------------------------------------------------------------------

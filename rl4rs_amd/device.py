@@ -331,9 +331,11 @@ class DeviceStepper(object):
     """rl4rs_stepper handle: an env bound to its scorer so that one call runs a whole transition
     (rl4rs_env_step_discrete / rl4rs_env_step_conti = RecSimBase._step, base.py:157-170)."""
 
-    def __init__(self, env, net, slots, act_tail=True):
+    def __init__(self, env, net, slots, act_tail=True, obs_fold=True):
         """``act_tail=False`` (config['no_act_tail'] / RL4RS_NO_ACT_TAIL=1): rl4rs_env_step_discrete launches k_step_tail as it
-        did and leaves no next-step logged actions (rl4rs_stepper_set_act_tail)."""
+        did and leaves no next-step logged actions (rl4rs_stepper_set_act_tail).  ``obs_fold=False``
+        (config['no_reward_obs_fold'] / RL4RS_NO_REWARD_OBS_FOLD=1): a reward step runs its observation forward and then the
+        reward forward of n - 1 rows per env, as it did (rl4rs_stepper_set_obs_fold)."""
         self.lib = _lib.load()
         self.env, self.net, self.slots = env, net, slots          # keep the handles and the slot table alive
         assert slots.dtype == torch.int32 and slots.is_contiguous() and slots.shape[1] == env.B
@@ -344,6 +346,9 @@ class DeviceStepper(object):
         self.act_tail = bool(act_tail)
         if not self.act_tail:
             check(self.lib.rl4rs_stepper_set_act_tail(self.h, 0))
+        if not obs_fold:
+            check(self.lib.rl4rs_stepper_set_obs_fold(self.h, 0))
+        self._distinct_hint = None
         self.B, self.A, self.E, self.W, self.device = env.B, env.A, env.E, env.W, env.device
         self.obs_dim = int(getattr(net, 'obs_dim', 256))         # 256 for DIEN / dnn / lstm, 256 + U + Cn*E for widedeep
 
@@ -357,6 +362,24 @@ class DeviceStepper(object):
             self.close()
         except Exception:
             pass
+
+    def set_distinct_hint(self, n):
+        """Envs of the bound batch the scorer's row dedup is expected to leave (the batch's distinct log lines): decides whether a
+        reward step folds its observation into the reward forward (rl4rs_stepper_set_distinct_hint).  None = the batch size."""
+        n = self.B if n is None else max(1, min(int(n), self.B))
+        if n != self._distinct_hint:
+            check(self.lib.rl4rs_stepper_set_distinct_hint(self.h, n))
+            self._distinct_hint = n
+
+    def reward_rows(self):
+        """Rows per env the last reward step's reward forward scored (rl4rs_stepper_reward_rows)."""
+        return int(self.lib.rl4rs_stepper_reward_rows(self.h))
+
+    def click_probs(self):
+        """f32 [B, n_complete]: the click probabilities of the last reward step's complete-state rows (rl4rs_stepper_click_probs)."""
+        out = torch.empty((self.B, self.env.n_complete), dtype=torch.float32, device=self.device)
+        check(self.lib.rl4rs_stepper_click_probs(self.h, _ptr(out), _stream()))
+        return out
 
     def step(self, actions, conti=False, want_reward=True, want_mask_bits=False):
         """-> (obs f32 [B, obs_dim], reward f64 [B] or None, mask_bits i32 [B, W] or None, chosen i32 [B])."""
@@ -590,8 +613,10 @@ class DeviceDien(object):
             self._keep_ids = ids
         check(self.lib.rl4rs_dien_encode(self.h, s, ptr, n, slot_base, _stream()))
 
-    def forward(self, R, group, dense, cat, slots, want_obs=True, want_prob=False, obs_out=None):
-        """dense/cat: device tensors or raw c_void_p pointers; slots: int32 device tensor [S, R/group]."""
+    def forward(self, R, group, dense, cat, slots, want_obs=True, want_prob=False, obs_out=None, want_obs_last=False):
+        """dense/cat: device tensors or raw c_void_p pointers; slots: int32 device tensor [S, R/group].
+        ``want_obs_last`` (with ``want_prob``): -> (obs, prob, obs_last f32 [R / group, 256]), the observation of the last row of
+        each group (rl4rs_dien_set_obs_last)."""
         dp = dense if isinstance(dense, C.c_void_p) else _ptr(dense)
         cp = cat if isinstance(cat, C.c_void_p) else _ptr(cat)
         assert slots.dtype == torch.int32 and slots.numel() == self.S * (R // group)
@@ -599,8 +624,12 @@ class DeviceDien(object):
         if want_obs:
             obs = obs_out if obs_out is not None else torch.empty((R, 256), dtype=torch.float32, device=self.device)
         prob = torch.empty(R, dtype=torch.float32, device=self.device) if want_prob else None
+        last = None
+        if want_obs_last:
+            last = torch.empty((R // group, 256), dtype=torch.float32, device=self.device)
+            check(self.lib.rl4rs_dien_set_obs_last(self.h, _ptr(last)))
         check(self.lib.rl4rs_dien_forward(self.h, R, group, dp, cp, _ptr(slots), _ptr(obs), _ptr(prob), _stream()))
-        return obs, prob
+        return (obs, prob, last) if want_obs_last else (obs, prob)
 
     def head_prob(self, obs):
         R = obs.shape[0]

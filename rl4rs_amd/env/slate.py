@@ -121,6 +121,7 @@ class SlateState(RecState):
             # the env -> history map, the scorer encodes each distinct sequence once
             uniq, inv = _unique_lines(rows, store.n)
             dedup = len(uniq) < len(rows)
+            self._n_lines = len(uniq)            # envs of one line stay equal under a deterministic policy: the stepper's distinct-env hint
             # ONE pinned block, one host-to-device copy: [line of every env | distinct lines | env -> history slot | envs sorted
             # by slot]; ONE gather launch (rl4rs_env_load_lines) instead of a dozen index_select / copy / memset launches
             B, U = len(rows), (len(uniq) if dedup else 0)
@@ -146,6 +147,7 @@ class SlateState(RecState):
             self._exposed_host = np.ascontiguousarray(rc.exposed, dtype=np.int32)
             self._users = rc.users
             self._feedback_cols = cols['feedback']
+            self._n_lines = None
         key = ('env', self.is_seq, log_steps, self.batch_size, self.max_steps, self._violation_zeroes_reward())
         env = self._ctx.get(key)
         if env is None:
@@ -607,8 +609,14 @@ class SlateRecEnv(RecSimBase):
             self._next_rows = {}
             # config['no_act_tail'] (RL4RS_NO_ACT_TAIL=1): k_step_tail and k_offline_action as launches of their own
             no_tail = self.config.get('no_act_tail', os.environ.get('RL4RS_NO_ACT_TAIL', '') not in ('', '0'))
-            self._stepper = D.DeviceStepper(env, net, slots, act_tail=not no_tail)
+            # config['no_reward_obs_fold'] (RL4RS_NO_REWARD_OBS_FOLD=1): the observation forward of a reward step as a forward of its own
+            no_fold = self.config.get('no_reward_obs_fold', os.environ.get('RL4RS_NO_REWARD_OBS_FOLD', '') not in ('', '0'))
+            self._stepper = D.DeviceStepper(env, net, slots, act_tail=not no_tail, obs_fold=not no_fold)
             self._stepper_key = key
+        # envs the scorer's row dedup is expected to leave: the batch's distinct log lines - but SeqSlate gives every env a slot of
+        # its own for the second sequence input from the second page on (_seq_slots_own): no two envs are duplicates there
+        own = samples.is_seq and env.cur_steps >= samples.page_items
+        self._stepper.set_distinct_hint(None if own else getattr(samples, '_n_lines', None))
         return env, net, self._stepper
 
     def _mask_dicts(self, rec):
