@@ -1450,6 +1450,65 @@ int rl4rs_exactk_critic_loss_grad(rl4rs_exactk_critic* net, int32_t N, const flo
                                   float* value_out_dev, float* err_out_dev, void* stream);
 int rl4rs_exactk_critic_adam_step(rl4rs_exactk_critic* net, float lr, float beta1, float beta2, float eps, void* stream);
 
+/* ---- On-device ensemble dynamics model (d3rlpy 0.91's ProbabilisticEnsembleDynamics as restated in DESIGN.md; parity unpinned) ----
+ * `members` networks on the shared input xa = [scaled x | a] (continuous actions only):
+ *   h1 = dropout(bn1(relu(xa W1 + b1)));  h2 = dropout(bn2(relu([h1 | xa] W2 + b2)))   (use_dense = 0: h1 W2)
+ *   mu = h2 Wmu + bmu;  ls = h2 Wls + bls;  ls = max_ls - softplus(max_ls - ls);  ls = min_ls + softplus(ls - min_ls)
+ * with O = obs_dim + 1 outputs per head (the change of the scaled observation, then the scaled reward).  W1, W2 and Wmu are spectrally
+ * normalised (spectral_norm = 1): a training forward runs one power iteration on the stored u / v and every product is scaled by
+ * 1 / sigma; W / sigma is never materialised.  Batch norm is torch.nn.BatchNorm1d (eps 1e-5, momentum 0.1).  The dropout keep mask of
+ * member m, layer l (0 / 1) is  uniform01(seed, step, row, (2 m + l) * 65536 + col) >= rate,  kept values scaled by 1 / (1 - rate).
+ *
+ * Flat parameters, members consecutive, matrices [in, out]:  W1 [D + E, H1], b1, bn1 weight, bn1 bias, W2 [H1 + D + E, H2] (rows of
+ * h1 first; [H1, H2] without use_dense), b2, bn2 weight, bn2 bias, Wh [H2, 2 O] = [Wmu | Wls], bh [2 O], max_ls [O], min_ls [O].
+ * Non-trained state, members consecutive: u1 [H1], v1 [D + E], u2 [H2], v2 [rows of W2], u3 [O], v3 [H2], running mean1, var1 [H1],
+ * running mean2, var2 [H2]; after the last member the scaler constants: observation min [D], observation range max - min [D] (0: a
+ * constant column, which maps to 0), reward mean, reward scale (std + eps).  No scaler = min 0, range 1, mean 0, scale 1.
+ * Statistics of the last forward, per member: sigma [3], batch mean1, biased batch var1 [H1], mean2, var2 [H2].
+ *
+ * rl4rs_dyn_create refuses (and the *_count functions return -1), before a device is looked for: more than 16 members, widths
+ * outside [1, 65536], a max_rows whose widest fp32 scratch array [members, max_rows, max(2 O, D + E, H1, H2)] would reach 2^31
+ * bytes, and shapes whose power-iteration or loss kernels would need more than 160 KiB of LDS. */
+typedef struct rl4rs_dyn rl4rs_dyn;
+typedef struct rl4rs_dyn_cfg {
+    int32_t obs_dim /* D */, act_dim /* E */, hidden1, hidden2, members, max_rows, max_grad_rows, use_batch_norm, use_dense, spectral_norm;
+    float dropout_rate;
+} rl4rs_dyn_cfg;
+int64_t rl4rs_dyn_param_count(const rl4rs_dyn_cfg* cfg);
+int64_t rl4rs_dyn_state_count(const rl4rs_dyn_cfg* cfg);
+int64_t rl4rs_dyn_stats_count(const rl4rs_dyn_cfg* cfg);
+int rl4rs_dyn_create(const rl4rs_dyn_cfg* cfg, const float* params_host, const float* state_host, void* stream, rl4rs_dyn** out);
+int rl4rs_dyn_destroy(rl4rs_dyn* net);
+int rl4rs_dyn_params(rl4rs_dyn* net, float** params_dev, float** grad_dev, int64_t* count);
+int rl4rs_dyn_adam_state(rl4rs_dyn* net, float** m_dev, float** v_dev, int64_t* step);
+int rl4rs_dyn_set_adam_step(rl4rs_dyn* net, int64_t step);
+int rl4rs_dyn_state(rl4rs_dyn* net, float** state_dev, int64_t* count, float** stats_dev, int64_t* stats_count);
+/* x_dev [N, D] and a_dev [N, E] in raw units -> out_dev [members, N, 2 O] = [mu | bounded ls].  train != 0: batch statistics,
+ * dropout, one power iteration; u / v and the running statistics move. */
+int rl4rs_dyn_forward(rl4rs_dyn* net, int32_t N, const float* x_dev, const float* a_dev, int32_t train, uint32_t seed, uint32_t step,
+                      float* out_dev, void* stream);
+/* Training forward, then per member i:  loss_i = mean_b(mask[i, b] * (like_b + sum_o ls[b, o] + 0.01 (sum max_ls - sum min_ls))),
+ * like_b = mean_d((x + mu[:D] - o')^2 exp(-ls[:D])) + (mu[D] - r')^2 exp(-ls[D])  on the scaled targets of next_x_dev [N, D] and
+ * next_r_dev [N]; loss_dev [members]; the gradient of sum_i loss_i goes to the handle's flat gradient (bit-identical between
+ * identical calls from the same state).  mask_dev float [members, N]. */
+int rl4rs_dyn_loss_grad(rl4rs_dyn* net, int32_t N, const float* x_dev, const float* a_dev, const float* next_x_dev,
+                        const float* next_r_dev, const float* mask_dev, uint32_t seed, uint32_t step, float* loss_dev, void* stream);
+/* torch.optim.Adam on the handle's gradient, all members at once */
+int rl4rs_dyn_adam_step(rl4rs_dyn* net, float lr, float beta1, float beta2, float eps, void* stream);
+/* Eval forward, then per row the prediction of ONE member: indices_dev int32 [N] or NULL = floor(uniform01(seed, step, row,
+ * 1000 * 65536) * members); pred = mu + exp(ls) * eps with eps = noise_dev [members, N, O], or NULL = Box-Muller of
+ * uniform01(seed, step, row, (1001 + 2 m) * 65536 + o) and (1002 + 2 m) * 65536 + o, or 0 (deterministic).  next_x_dev [N, D] and
+ * reward_dev [N] are reverse-scaled; variance_dev [N] stays in scaled units: variance_type 0 = max over members of sum_o exp(2 ls),
+ * 1 = sum_o of the unbiased variance over members of their sampled [next x | reward].  penalise != 0: reward -= lam * variance
+ * (MOPO).  indices_out_dev (optional) receives the member used. */
+int rl4rs_dyn_predict(rl4rs_dyn* net, int32_t N, const float* x_dev, const float* a_dev, const int32_t* indices_dev,
+                      const float* noise_dev, uint32_t seed, uint32_t step, int32_t deterministic, int32_t variance_type,
+                      int32_t penalise, float lam, float* next_x_dev, float* reward_dev, float* variance_dev, int32_t* indices_out_dev,
+                      void* stream);
+/* SAC's soft target  y = r + gamma (1 - terminal) (min(q1, q2) - exp(log_temp[0]) logp),  all arrays float [N] on the device */
+int rl4rs_sac_target(const float* q1_dev, const float* q2_dev, const float* logp_dev, const float* log_temp_dev, const float* rew_dev,
+                     const float* ter_dev, float gamma, int32_t N, float* y_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -87,6 +87,12 @@ class DistqCfg(C.Structure):
                 [('v_min', C.c_float), ('v_max', C.c_float), ('max_rows', C.c_int32)])
 
 
+class DynCfg(C.Structure):
+    """rl4rs_dyn_cfg (include/rl4rs_hip.h)"""
+    _fields_ = ([(n, C.c_int32) for n in ('obs_dim', 'act_dim', 'hidden1', 'hidden2', 'members', 'max_rows', 'max_grad_rows',
+                                          'use_batch_norm', 'use_dense', 'spectral_norm')] + [('dropout_rate', C.c_float)])
+
+
 class ExactKCfg(C.Structure):
     """rl4rs_exactk_cfg (include/rl4rs_hip.h)"""
     _fields_ = ([(n, C.c_int32) for n in ('obs_dim', 'hidden', 'heads', 'blocks', 'action_size', 'vocab', 'max_rows')] +
@@ -381,6 +387,20 @@ SIGNATURES = {
     'rl4rs_exactk_critic_forward': (_I, [_P, _I32, _P, _P, _P]),
     'rl4rs_exactk_critic_loss_grad': (_I, [_P, _I32, _P, _P, _P, _P, _P]),
     'rl4rs_exactk_critic_adam_step': (_I, [_P, C.c_float, C.c_float, C.c_float, C.c_float, _P]),
+    'rl4rs_dyn_param_count': (_I64, [C.POINTER(DynCfg)]),
+    'rl4rs_dyn_state_count': (_I64, [C.POINTER(DynCfg)]),
+    'rl4rs_dyn_stats_count': (_I64, [C.POINTER(DynCfg)]),
+    'rl4rs_dyn_create': (_I, [C.POINTER(DynCfg), _P, _P, _P, C.POINTER(_P)]),
+    'rl4rs_dyn_destroy': (_I, [_P]),
+    'rl4rs_dyn_params': (_I, [_P, _P, _P, _P]),
+    'rl4rs_dyn_adam_state': (_I, [_P, _P, _P, _P]),
+    'rl4rs_dyn_set_adam_step': (_I, [_P, _I64]),
+    'rl4rs_dyn_state': (_I, [_P, _P, _P, _P, _P]),
+    'rl4rs_dyn_forward': (_I, [_P, _I32, _P, _P, _I32, C.c_uint32, C.c_uint32, _P, _P]),
+    'rl4rs_dyn_loss_grad': (_I, [_P, _I32, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, _P, _P]),
+    'rl4rs_dyn_adam_step': (_I, [_P, C.c_float, C.c_float, C.c_float, C.c_float, _P]),
+    'rl4rs_dyn_predict': (_I, [_P, _I32, _P, _P, _P, _P, C.c_uint32, C.c_uint32, _I32, _I32, _I32, C.c_float, _P, _P, _P, _P, _P]),
+    'rl4rs_sac_target': (_I, [_P, _P, _P, _P, _P, _P, C.c_float, _I32, _P, _P]),
 }
 
 # include/rl4rs_hip.h RL4RS_REPLAY_BUF_*

@@ -2575,3 +2575,127 @@ class DeviceExactKCritic(_FlatNet):
 
     def adam_step(self, lr=5e-3, beta1=0.9, beta2=0.98, eps=1e-8):
         check(self.lib.rl4rs_exactk_critic_adam_step(self.h, lr, beta1, beta2, eps, _stream()))
+
+
+def sac_target(q1, q2, logp, log_temp, rewards, terminals, gamma):
+    """SAC's soft target y = r + gamma (1 - terminal) (min(q1, q2) - exp(log_temp) logp)  (rl4rs_sac_target)."""
+    lib = _lib.load()
+    N = rewards.numel()
+    for t in (q1, q2, logp, rewards, terminals):
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == N
+    assert log_temp.is_cuda and log_temp.dtype == torch.float32 and log_temp.numel() >= 1
+    y = torch.empty(N, dtype=torch.float32, device=rewards.device)
+    check(lib.rl4rs_sac_target(_ptr(q1), _ptr(q2), _ptr(logp), _ptr(log_temp), _ptr(rewards), _ptr(terminals), float(gamma), N, _ptr(y),
+                               _stream()))
+    return y
+
+
+class DeviceDynamics(_FlatNet):
+    """rl4rs_dyn handle: the probabilistic ensemble dynamics model (include/rl4rs_hip.h, "On-device ensemble dynamics model";
+    layouts and initialisers in ``rl4rs_amd/dynamics.py``).  ``params`` / ``state``: flat float32 arrays in the header's layout."""
+    _prefix = 'rl4rs_dyn_'
+    VARIANCE_TYPES = {'max': 0, 'data': 1}
+
+    def __init__(self, obs_dim, act_dim, params, state, hidden_units=(256, 128), members=5, max_rows=4096, max_grad_rows=512,
+                 use_batch_norm=True, dropout_rate=0.2, use_dense=True, spectral_norm=True, device=None):
+        self.lib = _lib.load()
+        self.D, self.E, self.M = int(obs_dim), int(act_dim), int(members)
+        self.H1, self.H2 = int(hidden_units[0]), int(hidden_units[1])
+        self.O = self.D + 1
+        self.max_rows, self.max_grad_rows = int(max_rows), int(max_grad_rows)
+        self.cfg = _lib.DynCfg(self.D, self.E, self.H1, self.H2, self.M, self.max_rows, self.max_grad_rows, 1 if use_batch_norm else 0,
+                               1 if use_dense else 0, 1 if spectral_norm else 0, float(dropout_rate))
+        n = self.lib.rl4rs_dyn_param_count(C.byref(self.cfg))
+        if n < 0:
+            raise _lib.Rl4rsHipError(self.lib.rl4rs_last_error().decode())
+        self.n_params = int(n)
+        self.n_state = int(self.lib.rl4rs_dyn_state_count(C.byref(self.cfg)))
+        self.n_stats = int(self.lib.rl4rs_dyn_stats_count(C.byref(self.cfg)))
+        params = np.ascontiguousarray(params, dtype=np.float32)
+        state = np.ascontiguousarray(state, dtype=np.float32)
+        assert params.shape == (self.n_params,) and state.shape == (self.n_state,), (params.shape, self.n_params, state.shape, self.n_state)
+        self.device = None
+        h = C.c_void_p()
+        if torch.cuda.is_available():
+            self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+            with torch.cuda.device(self.device):
+                check(self.lib.rl4rs_dyn_create(C.byref(self.cfg), params.ctypes.data_as(C.c_void_p), state.ctypes.data_as(C.c_void_p),
+                                                _stream(), C.byref(h)))
+        else:       # the shape refusals come first; with neither a refusal nor a device this raises "no HIP device"
+            check(self.lib.rl4rs_dyn_create(C.byref(self.cfg), params.ctypes.data_as(C.c_void_p), state.ctypes.data_as(C.c_void_p), None,
+                                            C.byref(h)))
+        self.h = h
+
+    # the names _ModelIO and the data-parallel helpers use
+    flat_params = _FlatNet.params
+    flat_gradient = _FlatNet.grad
+
+    def set_flat_params(self, flat):
+        self.set_params(flat)
+
+    def _state_ptrs(self):
+        s, n, t, nt = C.c_void_p(), C.c_int64(), C.c_void_p(), C.c_int64()
+        check(self.lib.rl4rs_dyn_state(self.h, C.byref(s), C.byref(n), C.byref(t), C.byref(nt)))
+        return s, n.value, t, nt.value
+
+    def state(self):
+        """Copy of the non-trained state: u / v, running statistics, scaler constants (device tensor)."""
+        s, n, _, _ = self._state_ptrs()
+        return self._copy_out(s, n, None)
+
+    def set_state(self, flat):
+        s, n, _, _ = self._state_ptrs()
+        flat = flat.to(device=self.device, dtype=torch.float32).contiguous()
+        assert flat.numel() == n
+        check(self.lib.rl4rs_copy_d2d(s, _ptr(flat), n * 4, _stream()))
+        wait_stream()
+
+    def stats(self):
+        """Copy of the last forward's statistics [members, 3 + 2 H1 + 2 H2]: sigma, batch mean / biased variance of both layers."""
+        _, _, t, nt = self._state_ptrs()
+        return self._copy_out(t, nt, None).view(self.M, -1)
+
+    def _rows(self, x, a, cap):
+        N = x.shape[0]
+        assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and tuple(x.shape) == (N, self.D), tuple(x.shape)
+        assert a.is_cuda and a.dtype == torch.float32 and a.is_contiguous() and tuple(a.shape) == (N, self.E), tuple(a.shape)
+        assert 1 <= N <= cap, (N, cap)
+        return N
+
+    def forward(self, x, a, train=False, seed=0, step=0):
+        """[members, N, 2 O] = [mu | bounded ls]; ``train``: batch statistics, dropout, one power iteration (the state moves)."""
+        N = self._rows(x, a, self.max_grad_rows if train and self.max_grad_rows else self.max_rows)
+        out = torch.empty((self.M, N, 2 * self.O), dtype=torch.float32, device=self.device)
+        check(self.lib.rl4rs_dyn_forward(self.h, N, _ptr(x), _ptr(a), 1 if train else 0, seed & 0xffffffff, step & 0xffffffff, _ptr(out),
+                                         _stream()))
+        return out
+
+    def loss_grad(self, x, a, next_x, next_r, mask, seed=0, step=0):
+        """Per-member loss [members] and the gradient of their sum into the handle (``grad()``); ``mask`` float [members, N]."""
+        N = self._rows(x, a, self.max_grad_rows)
+        assert next_x.is_cuda and next_x.dtype == torch.float32 and next_x.is_contiguous() and tuple(next_x.shape) == (N, self.D)
+        assert next_r.is_cuda and next_r.dtype == torch.float32 and next_r.is_contiguous() and next_r.numel() == N
+        assert mask.is_cuda and mask.dtype == torch.float32 and mask.is_contiguous() and tuple(mask.shape) == (self.M, N)
+        loss = torch.empty(self.M, dtype=torch.float32, device=self.device)
+        check(self.lib.rl4rs_dyn_loss_grad(self.h, N, _ptr(x), _ptr(a), _ptr(next_x), _ptr(next_r), _ptr(mask), seed & 0xffffffff,
+                                           step & 0xffffffff, _ptr(loss), _stream()))
+        return loss
+
+    def adam_step(self, lr=1e-4, beta1=0.9, beta2=0.999, eps=1e-8):
+        check(self.lib.rl4rs_dyn_adam_step(self.h, lr, beta1, beta2, eps, _stream()))
+
+    def predict(self, x, a, indices=None, noise=None, seed=0, step=0, deterministic=False, variance_type='max', lam=None):
+        """(next_x [N, D], reward [N], variance [N], member used int32 [N]) of one member per row; ``lam``: reward -= lam * variance."""
+        N = self._rows(x, a, self.max_rows)
+        if indices is not None:
+            assert indices.is_cuda and indices.dtype == torch.int32 and indices.is_contiguous() and indices.numel() == N
+        if noise is not None:
+            assert noise.is_cuda and noise.dtype == torch.float32 and noise.is_contiguous() and tuple(noise.shape) == (self.M, N, self.O)
+        nx = torch.empty((N, self.D), dtype=torch.float32, device=self.device)
+        r = torch.empty(N, dtype=torch.float32, device=self.device)
+        var = torch.empty(N, dtype=torch.float32, device=self.device)
+        used = torch.empty(N, dtype=torch.int32, device=self.device)
+        check(self.lib.rl4rs_dyn_predict(self.h, N, _ptr(x), _ptr(a), _ptr(indices), _ptr(noise), seed & 0xffffffff, step & 0xffffffff,
+                                         1 if deterministic else 0, self.VARIANCE_TYPES[variance_type], 0 if lam is None else 1,
+                                         0.0 if lam is None else float(lam), _ptr(nx), _ptr(r), _ptr(var), _ptr(used), _stream()))
+        return nx, r, var, used

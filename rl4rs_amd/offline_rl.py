@@ -888,3 +888,247 @@ class CQL(_ModelIO):
     def close(self):
         for net in self.nets:
             net.close()
+
+
+class GeneratedFIFO(object):
+    """MOPO's buffer of model-generated transitions: (s, a, r, s', terminal) rows in tensors on one device, first in first out at
+    ``maxlen`` rows.  Storage grows with what is actually generated (doubling, never past ``maxlen``); once full the oldest rows
+    are overwritten in place."""
+
+    def __init__(self, maxlen, device=None):
+        self.maxlen = int(maxlen)
+        assert self.maxlen >= 1
+        self.device = device
+        self.size, self.pos = 0, 0          # rows held; where the next row goes (== size until the buffer is full)
+        self.cols = None
+
+    def __len__(self):
+        return self.size
+
+    def _reserve(self, rows):
+        cap = 0 if self.cols is None else self.cols[0].shape[0]
+        if rows <= cap:
+            return
+        new_cap = min(self.maxlen, max(rows, 2 * cap))
+        self.cols = [torch.cat([c, torch.empty((new_cap - cap,) + tuple(c.shape[1:]), dtype=c.dtype, device=c.device)]) for c in self.cols]
+
+    def append(self, obs, act, rew, nxt, ter):
+        rows = [t if t.dim() > 1 else t.reshape(-1) for t in (obs, act, rew, nxt, ter)]
+        b = rows[0].shape[0]
+        if b > self.maxlen:                  # only the newest maxlen rows can survive
+            rows = [t[b - self.maxlen:] for t in rows]
+            b = self.maxlen
+        if self.cols is None:
+            self.cols = [torch.empty((0,) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device) for t in rows]
+        self._reserve(min(self.maxlen, self.size + b))
+        cap = self.cols[0].shape[0]
+        first = min(b, cap - self.pos)
+        for c, t in zip(self.cols, rows):
+            c[self.pos:self.pos + first] = t[:first]
+            if first < b:                    # wraps: cap == maxlen here
+                c[:b - first] = t[first:]
+        self.size = min(self.maxlen, self.size + b)
+        self.pos = (self.pos + b) % self.maxlen if self.size == self.maxlen else self.pos + b
+
+    def rows(self, idx):
+        return [c[idx] for c in self.cols]
+
+    def oldest_first(self):
+        """Every held row in insertion order (tests)."""
+        if self.size < self.maxlen:
+            return [c[:self.size] for c in self.cols]
+        return [torch.cat([c[self.pos:self.size], c[:self.pos]]) for c in self.cols]
+
+
+def mixed_minibatch(real, fifo, batch_size, real_ratio, gen):
+    """round(real_ratio * batch_size) rows of the real transitions and the rest from the generated ones, both drawn with replacement
+    from ``gen`` (real rows first).  Without generated rows the whole minibatch is real.  -> ([obs, act, rew, nxt, ter], n_real)"""
+    n_real = int(round(real_ratio * batch_size)) if len(fifo) else batch_size
+    dev = real[0].device
+    out = [[] for _ in range(5)]
+    if n_real:
+        idx = torch.randint(0, real[0].shape[0], (n_real,), generator=gen, device=dev)
+        for o, t in zip(out, real):
+            o.append(t[idx])
+    if batch_size - n_real:
+        idx = torch.randint(0, len(fifo), (batch_size - n_real,), generator=gen, device=dev)
+        for o, t in zip(out, fifo.rows(idx)):
+            o.append(t)
+    return [torch.cat(o).contiguous() for o in out], n_real
+
+
+def model_rollout(sample_action, dynamics, start_obs, horizon, lam, fifo, step0=0, given=None):
+    """MOPO's ``generate_new_data`` from ``start_obs`` [N, D]: ``horizon`` times a = sample_action(s, h), (s', r, var) =
+    dynamics.predict(s, a, with_variance=True) with r - lam * var as the reward, (s, a, r, s', 0) appended to ``fifo``, s <- s'.
+    ``given`` (tests): dict of per-step lists ``indices`` / ``noise`` handed to ``dynamics.predict``."""
+    s = start_obs
+    for h in range(int(horizon)):
+        a = sample_action(s, h)
+        kw = {}
+        if given is not None:
+            kw = {'indices': given['indices'][h], 'noise': given['noise'][h]}
+        nx, r, _ = dynamics.predict(s, a, with_variance=True, lam=lam, step=step0 + h, **kw)
+        fifo.append(s, a, r.reshape(-1), nx, torch.zeros(s.shape[0], dtype=torch.float32, device=s.device))
+        s = nx
+    return s
+
+
+class MOPO(_ModelIO):
+    """d3rlpy.algos.MOPO as 'MOPO' instantiates it (script/batchrl_trainer.py:108-129; the script passes batch_size=256, gamma=1.0,
+    update_actor_interval=2000): SAC on default ``[256, 256]`` encoders - actor / critic / temperature lr 3e-4, tau 0.005, two
+    critics, initial temperature 1 - trained on minibatches of ``real_ratio`` real and 1 - ``real_ratio`` model-generated rows.
+    Every ``rollout_interval`` updates ``rollout_batch_size`` real observations are rolled ``rollout_horizon`` steps through
+    ``dynamics`` under the current policy with the reward r - ``lam`` * variance.  d3rlpy 0.91 defaults as published; PARITY UNPINNED.
+
+    One ``update``: critic step on y = r + gamma (1 - terminal) (min_c Q_targ_c(s', a') - exp(log_temp) log pi(a' | s')), a' sampled;
+    then on every ``update_actor_interval``-th update (counted from 0) the actor step through min(Q1, Q2), the temperature step
+    (target entropy -A) and the soft target update.  Composed of the library's entry points (``rl4rs_amlp_*``,
+    ``rl4rs_squashed_sample``, ``rl4rs_sac_target``, ``rl4rs_critic_mse``, ``rl4rs_twin_min``, ``rl4rs_sac_actor_grad``); no one-call
+    form.  ``noise`` (tests): dict with ``eps_next``, ``eps_actor``, ``eps_temp``, each [B, A]."""
+
+    def __init__(self, config, obs_dim, dynamics, action_size=None, batch_size=100, actor_learning_rate=3e-4, critic_learning_rate=3e-4,
+                 temp_learning_rate=3e-4, gamma=0.99, tau=0.005, initial_temperature=1.0, update_actor_interval=1, rollout_interval=1000,
+                 rollout_horizon=5, rollout_batch_size=50000, lam=1.0, real_ratio=0.05, generated_maxlen=50000 * 5 * 5,
+                 reward_scaler=None, predict_rows=4096, seed=0, device=None):
+        self.config = config
+        self.dynamics = dynamics
+        self.D = int(obs_dim)
+        self.A = int(action_size if action_size is not None else config['action_emb_size'])
+        self.batch_size = int(batch_size)
+        self.actor_lr, self.critic_lr, self.temp_lr = float(actor_learning_rate), float(critic_learning_rate), float(temp_learning_rate)
+        self.gamma, self.tau = float(gamma), float(tau)
+        self.update_actor_interval = max(int(update_actor_interval), 1)
+        self.rollout_interval, self.rollout_horizon = max(int(rollout_interval), 1), int(rollout_horizon)
+        self.rollout_batch_size, self.lam, self.real_ratio = int(rollout_batch_size), float(lam), float(real_ratio)
+        self.reward_scaler = reward_scaler
+        self.predict_rows = max(int(predict_rows), 1)
+        self.seed = int(seed)
+        self.total_step = 0
+        B, D, A = self.batch_size, self.D, self.A
+
+        def net(act_dim, out_dim, seed_off, max_rows, grad_rows, heads=1):
+            return D_.DeviceAMLP(D, act_dim, out_dim, init_amlp_params(D, act_dim, out_dim, seed=seed + seed_off, heads=heads),
+                                 max_rows=max_rows, max_grad_rows=grad_rows, device=device)
+
+        self.policy = net(0, 2 * A, 0, max(B, self.predict_rows), B, heads=2)
+        self.q1 = net(A, 1, 1, B, B)
+        self.q2 = net(A, 1, 2, B, B)
+        self.q1_targ = net(A, 1, 1, B, 0)
+        self.q2_targ = net(A, 1, 2, B, 0)
+        self.q1_targ.copy_from(self.q1)
+        self.q2_targ.copy_from(self.q2)
+        self.nets = [self.policy, self.q1, self.q2, self.q1_targ, self.q2_targ]
+        self.device = self.q1.device
+        self.log_temp = _ScalarParam(np.log(initial_temperature), self.device)
+        self._gen = torch.Generator(device=self.device)
+        self._gen.manual_seed(self.seed + 1000003 * rdist.rank())
+        self.generated = GeneratedFIFO(generated_maxlen, self.device)
+
+    def _randn(self, shape, given):
+        if given is not None:
+            return given.to(device=self.device, dtype=torch.float32).contiguous()
+        return torch.randn(shape, generator=self._gen, device=self.device, dtype=torch.float32)
+
+    def soft_target(self, rew, nxt, ter, eps_next=None):
+        """y [B] of the critic step"""
+        B, A = nxt.shape[0], self.A
+        a_next, logp = D_.squashed_sample(self.policy.forward(nxt), self._randn((B, A), eps_next))
+        q1t, q2t = self.q1_targ.forward(nxt, a_next), self.q2_targ.forward(nxt, a_next)
+        return D_.sac_target(q1t, q2t, logp, self.log_temp.p, rew.reshape(-1).contiguous(), ter.reshape(-1).contiguous(), self.gamma)
+
+    def update(self, obs, act, rew, nxt, ter, noise=None):
+        noise = noise or {}
+        B, A = obs.shape[0], self.A
+        if self.reward_scaler is not None:
+            if isinstance(self.reward_scaler, str):
+                raise ValueError("reward_scaler=%r is fitted by fit_mdp(dataset); pass StandardRewardScaler(rewards) to use update / fit "
+                                 "directly" % self.reward_scaler)
+            rew = self.reward_scaler.transform(rew)
+        obs, act, rew, nxt, ter = _check_transitions(self.device, self.D, self.A, obs, act, rew, nxt, ter)
+        metrics = {}
+        # --- critic (SACImpl.compute_target / DDPGBaseImpl.update_critic)
+        y = self.soft_target(rew, nxt, ter, noise.get('eps_next'))
+        q1v, q2v = D_.amlp_forward_multi([self.q1, self.q2], obs, act)
+        loss2, dq1, dq2 = D_.critic_mse(q1v, q2v, y)
+        D_.amlp_backward_multi([self.q1, self.q2], obs, act, [dq1, dq2])
+        _allreduce_group([self.q1, self.q2])
+        D_.amlp_adam_multi([self.q1, self.q2], [self.critic_lr] * 2)
+        metrics['critic_loss'] = loss2[0] + loss2[1]
+        if self.total_step % self.update_actor_interval == 0:
+            # --- actor (SACImpl.compute_actor_loss): (exp(log_temp) * logp - min_c Q_c(s, a)).mean()
+            head_obs = self.policy.forward(obs)
+            eps = self._randn((B, A), noise.get('eps_actor'))
+            a_pi, logp = D_.squashed_sample(head_obs, eps)
+            q1p, q2p = D_.amlp_forward_multi([self.q1, self.q2], obs, a_pi)
+            qmin, dq1, dq2 = D_.twin_min(q1p, q2p, want_grad=True)
+            g1, g2 = D_.amlp_backward_multi([self.q1, self.q2], obs, a_pi, [dq1.view(B, 1), dq2.view(B, 1)], want_dact=True,
+                                            want_param_grad=False)
+            d_head = D_.sac_actor_grad(head_obs, eps, a_pi, g1.add_(g2), self.log_temp.p)
+            self.policy.backward(obs, None, d_head)
+            _allreduce_group([self.policy])
+            metrics['actor_loss'] = (self.log_temp.p.exp() * logp - qmin).mean()
+            D_.amlp_adam_multi([self.policy], [self.actor_lr])
+            # --- temperature (SACImpl.update_temp, on the stepped policy): -(exp(log_temp) * (logp - A)).mean(), gradient wrt log_temp
+            if self.temp_lr > 0:
+                _, logp_t = D_.squashed_sample(self.policy.forward(obs), self._randn((B, A), noise.get('eps_temp')))
+                targ = (logp_t - A).mean()
+                temp = self.log_temp.p.exp()
+                metrics['temp_loss'] = -(temp * targ)[0]
+                self.log_temp.adam_step(-(temp * targ), self.temp_lr)
+            # --- soft target update
+            D_.amlp_adam_multi([self.q1, self.q2], [0.0, 0.0], targets=[self.q1_targ, self.q2_targ], tau=self.tau, step=[False, False])
+        self.total_step += 1
+        return metrics
+
+    def sample_action(self, obs, eps=None):
+        """a ~ pi(. | obs) for any number of rows"""
+        out = torch.empty((obs.shape[0], self.A), dtype=torch.float32, device=self.device)
+        rows = self.policy.max_rows
+        for lo in range(0, obs.shape[0], rows):
+            x = obs[lo:lo + rows].contiguous()
+            e = self._randn((x.shape[0], self.A), None if eps is None else eps[lo:lo + rows])
+            D_.squashed_sample(self.policy.forward(x), e, act_out=out[lo:lo + x.shape[0]])
+        return out
+
+    def generate_new_data(self, real_obs, given=None):
+        """One rollout of ``rollout_batch_size`` start observations drawn with replacement from ``real_obs`` into ``self.generated``.
+        ``given`` (tests): dict with ``start`` (row indices), ``eps`` [H][N, A], ``indices`` [H][N], ``noise`` [H][members, N, D + 1]."""
+        if given is not None:
+            idx = given['start'].to(self.device)
+        else:
+            idx = torch.randint(0, real_obs.shape[0], (self.rollout_batch_size,), generator=self._gen, device=self.device)
+        start = real_obs.to(self.device)[idx].contiguous()
+        sample = (lambda s, h: self.sample_action(s, None if given is None else given['eps'][h]))
+        return model_rollout(sample, self.dynamics, start, self.rollout_horizon, self.lam, self.generated,
+                             step0=self.total_step * 64, given=given)
+
+    def fit(self, transitions, n_steps, shuffle_seed=None, to_host=True):
+        """``n_steps`` updates on mixed minibatches; a rollout before every ``rollout_interval``-th update (the first included)."""
+        real = [t.to(self.device) for t in transitions]
+        assert real[1].dim() == 2 and real[1].shape[1] == self.A and real[1].dtype == torch.float32, 'continuous actions [N, %d] needed' % self.A
+        hist = []
+        for _ in range(n_steps):
+            if self.total_step % self.rollout_interval == 0:
+                self.generate_new_data(real[0])
+            batch, _ = mixed_minibatch(real, self.generated, self.batch_size, self.real_ratio, self._gen)
+            hist.append(self.update(*batch))
+        out = {}
+        for k in self._LOSS_KEYS:
+            vals = [h[k] for h in hist if k in h]
+            out[k] = ([float(x) for x in torch.stack(vals).cpu()] if to_host else torch.stack(vals)) if vals else []
+        return out
+
+    _LOSS_KEYS = ('critic_loss', 'actor_loss', 'temp_loss')
+
+    def fit_mdp(self, data, n_epochs=1, **kw):
+        tr = transitions_from_mdp(data['observations'], data['actions'], data['rewards'], data['terminals'], discrete_action=False)
+        if self.reward_scaler == 'standard':
+            self.reward_scaler = StandardRewardScaler(tr[2])
+        return self.fit(tr, int(n_epochs) * max(tr[0].shape[0] // self.batch_size, 1), **kw)
+
+    predict = CQL.predict
+    predict_value = CQL.predict_value
+
+    def close(self):
+        for net in self.nets:
+            net.close()

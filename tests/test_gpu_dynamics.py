@@ -1,0 +1,372 @@
+"""The ensemble dynamics model (csrc/dynamics.hip, rl4rs_amd/dynamics.py) against the float64 torch restatement in
+tests/dynamics_ref.py (PARITY UNPINNED: d3rlpy is absent).  Every case hands masks, member indices, noise and seeds to both sides.
+
+Shapes (D, E, H1, H2, M, B):
+  (266, 32, 256, 128, 5, 64)   the default widths once
+  (37, 5, 24, 12, 3, 33)       nothing a multiple of a tile, odd O = 38, a ragged last wave in every row loop
+  (40, 8, 32, 16, 5, 300)      B > 256: a second trip of every single-workgroup reduction
+  (266, 32, 256, 128, 2, 8)    the real widths at the smallest batch: the GEMMs' small-M form
+
+Tolerances are not fixed in advance: the bar of a comparison is 4 x the largest difference between the restatement run in float32
+and in float64 on the case's own inputs (the 4 covers another summation order), computed here, per compared quantity.  The inputs
+are conditioned (asserted on the float64 restatement): every batch-norm column has batch variance above 1e-3 and |u^T W v| > 0.1."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+import dynamics_ref as R
+
+pytestmark = pytest.mark.gpu
+
+SHAPES = {'default': (266, 32, 256, 128, 5, 64), 'ragged': (37, 5, 24, 12, 3, 33), 'batch300': (40, 8, 32, 16, 5, 300),
+          'rows8': (266, 32, 256, 128, 2, 8)}
+SEEDS = {'default': 11, 'ragged': 12, 'batch300': 13, 'rows8': 14}
+SWITCHES = {'all_on': {}, 'no_batch_norm': dict(use_bn=False), 'no_dropout': dict(rate=0.0), 'no_dense': dict(use_dense=False),
+            'no_spectral': dict(spectral=False)}
+HASH_SEED, HASH_STEP = 77, 5
+F64, F32 = torch.float64, torch.float32
+
+
+def _cfg(switch):
+    return R.default_cfg(seed=HASH_SEED, step=HASH_STEP, **SWITCHES[switch])
+
+
+@functools.lru_cache(maxsize=None)
+def _case(shape, switch='all_on'):
+    D, E, H1, H2, M, B = SHAPES[shape]
+    return R.make_case(D, E, H1, H2, M, B, SEEDS[shape], use_dense=_cfg(switch)['use_dense'])
+
+
+def _net(case, switch='all_on', max_rows=None):
+    from rl4rs_amd.device import DeviceDynamics
+    D, E, H1, H2, M, B = case['shape']
+    c = _cfg(switch)
+    return DeviceDynamics(D, E, R.flat_params(case), R.flat_state(case), (H1, H2), M, max_rows=max_rows or B, max_grad_rows=B,
+                          use_batch_norm=c['use_bn'], dropout_rate=c['rate'], use_dense=c['use_dense'], spectral_norm=c['spectral'])
+
+
+def _dev(case, *names):
+    return [torch.from_numpy(np.ascontiguousarray(case[n])).cuda() for n in names]
+
+
+class Check(object):
+    """collects (what, device error, bar) and fails at the end with every miss; prints each figure"""
+
+    def __init__(self, tag):
+        self.tag, self.bad = tag, []
+
+    def __call__(self, what, got, ref64, ref32):
+        got = got.detach().cpu().numpy() if torch.is_tensor(got) else np.asarray(got)
+        ref64 = ref64.detach().numpy() if torch.is_tensor(ref64) else np.asarray(ref64)
+        ref32 = ref32.detach().numpy() if torch.is_tensor(ref32) else np.asarray(ref32)
+        assert got.shape == ref64.shape, (what, got.shape, ref64.shape)
+        err, bar = R.maxdiff(got, ref64), R.BAR_FACTOR * R.maxdiff(ref32, ref64)
+        print('%-28s %-12s device %.3e  bar %.3e  (scale %.3e)' % (self.tag, what, err, bar, float(np.abs(ref64).max())))
+        if not err <= bar:
+            self.bad.append((what, err, bar))
+
+    def done(self):
+        assert not self.bad, (self.tag, self.bad)
+
+
+def _stack(outs, key):
+    return torch.stack([o[key].detach() for o in outs])
+
+
+@functools.lru_cache(maxsize=None)
+def _ref_forward(shape, switch, dt):
+    """two training forwards (the state moves in between) and an eval forward from the state after them"""
+    case, cfg = _case(shape, switch), _cfg(switch)
+    o1, _, _ = R.forward(case['P'], case['S'], case['x'], case['a'], True, cfg, dt, case['sc'])
+    S1 = R.new_state(case['S'], o1)
+    o2, _, _ = R.forward(case['P'], S1, case['x'], case['a'], True, cfg, dt, case['sc'])
+    S2 = R.new_state(S1, o2)
+    ev, _, _ = R.forward(case['P'], S2, case['x'], case['a'], False, cfg, dt, case['sc'])
+    return o1, S1, o2, S2, ev
+
+
+@functools.lru_cache(maxsize=None)
+def _ref_loss(shape, switch, dt, zero_member=False):
+    case, cfg = _case(shape, switch), _cfg(switch)
+    mask = case['mask'].copy()
+    if zero_member:
+        mask[0] = 0
+    return R.loss_grad(case['P'], case['S'], case['x'], case['a'], case['nxt'], case['rew'], mask, cfg, dt, case['sc'])
+
+
+def _state_dicts(net, case):
+    from rl4rs_amd import dynamics as dyn
+    D, E, H1, H2, M, B = case['shape']
+    return dyn.unflatten(net.state().cpu().numpy(), dyn.state_shapes(D, E, H1, H2, case['use_dense']), M)
+
+
+def _stats_dicts(net, case):
+    from rl4rs_amd import dynamics as dyn
+    D, E, H1, H2, M, B = case['shape']
+    return dyn.unflatten(net.stats().cpu().numpy().reshape(-1), dyn.stats_shapes(H1, H2), M)
+
+
+def _check_forward(shape, switch):
+    case, cfg = _case(shape, switch), _cfg(switch)
+    D, E, H1, H2, M, B = case['shape']
+    O = D + 1
+    r64, r32 = _ref_forward(shape, switch, F64), _ref_forward(shape, switch, F32)
+    R.check_conditions(r64[0] + r64[2] + r64[4])
+    net = _net(case, switch)
+    x, a = _dev(case, 'x', 'a')
+    ck = Check('%s/%s' % (shape, switch))
+    out = net.forward(x, a, train=True, seed=HASH_SEED, step=HASH_STEP)
+    ck('train mu', out[:, :, :O], _stack(r64[0], 'mu'), _stack(r32[0], 'mu'))
+    ck('train ls', out[:, :, O:], _stack(r64[0], 'ls'), _stack(r32[0], 'ls'))
+    st, sd = _stats_dicts(net, case), _state_dicts(net, case)
+    ck('sigma', np.stack([s['sigma'] for s in st]), _stack(r64[0], 'sigma'), _stack(r32[0], 'sigma'))
+    if cfg['use_bn']:
+        for k in ('mean1', 'var1', 'mean2', 'var2'):
+            ck('batch ' + k, np.stack([s[k] for s in st]), _stack(r64[0], k), _stack(r32[0], k))
+    if cfg['spectral']:
+        for k in ('u1', 'v1', 'u2', 'v2', 'u3', 'v3'):
+            ck(k, np.stack([s[k] for s in sd]), np.stack([s[k] for s in r64[1]]), np.stack([s[k] for s in r32[1]]))
+    out = net.forward(x, a, train=True, seed=HASH_SEED, step=HASH_STEP)
+    ck('2nd train mu', out[:, :, :O], _stack(r64[2], 'mu'), _stack(r32[2], 'mu'))
+    sd = _state_dicts(net, case)
+    for k in (('rm1', 'rv1', 'rm2', 'rv2') if cfg['use_bn'] else ()) + (('u1', 'v3') if cfg['spectral'] else ()):
+        ck('after two: ' + k, np.stack([s[k] for s in sd]), np.stack([s[k] for s in r64[3]]), np.stack([s[k] for s in r32[3]]))
+    out = net.forward(x, a, train=False)
+    ck('eval mu', out[:, :, :O], _stack(r64[4], 'mu'), _stack(r32[4], 'mu'))
+    ck('eval ls', out[:, :, O:], _stack(r64[4], 'ls'), _stack(r32[4], 'ls'))
+    sd2 = _state_dicts(net, case)
+    for k in sd[0]:
+        assert all((a_[k] == b_[k]).all() for a_, b_ in zip(sd, sd2)), 'an eval forward moved ' + k
+    net.close()
+    ck.done()
+
+
+def _check_loss_grad(shape, switch):
+    from rl4rs_amd import dynamics as dyn
+    case = _case(shape, switch)
+    D, E, H1, H2, M, B = case['shape']
+    r64, r32 = _ref_loss(shape, switch, F64), _ref_loss(shape, switch, F32)
+    R.check_conditions(r64['outs'])
+    net = _net(case, switch)
+    x, a, nxt, rew, mask = _dev(case, 'x', 'a', 'nxt', 'rew', 'mask')
+    ck = Check('%s/%s' % (shape, switch))
+    loss = net.loss_grad(x, a, nxt, rew, mask, seed=HASH_SEED, step=HASH_STEP)
+    g_flat = net.grad()
+    ck('loss', loss, r64['loss'], r32['loss'])
+    G = dyn.unflatten(g_flat.cpu().numpy(), dyn.param_shapes(D, E, H1, H2, case['use_dense']), M)
+    for name, _ in dyn.param_shapes(D, E, H1, H2, case['use_dense']):
+        ck('d ' + name, np.stack([g[name] for g in G]), np.stack([g[name] for g in r64['grads']]), np.stack([g[name] for g in r32['grads']]))
+    # identical calls from the same state: identical bits
+    net.set_state(torch.from_numpy(R.flat_state(case)))
+    loss2 = net.loss_grad(x, a, nxt, rew, mask, seed=HASH_SEED, step=HASH_STEP)
+    assert torch.equal(loss, loss2) and torch.equal(g_flat, net.grad())
+    net.close()
+    ck.done()
+
+
+@pytest.mark.parametrize('shape', list(SHAPES))
+def test_forward_train_and_eval(shape):
+    _check_forward(shape, 'all_on')
+
+
+@pytest.mark.parametrize('switch', [s for s in SWITCHES if s != 'all_on'])
+def test_each_switch_off(switch):
+    _check_forward('ragged', switch)
+    _check_loss_grad('ragged', switch)
+
+
+@pytest.mark.parametrize('shape', list(SHAPES))
+def test_loss_and_every_gradient(shape):
+    _check_loss_grad(shape, 'all_on')
+
+
+def test_a_member_with_an_all_zero_mask_gets_zero_gradient():
+    from rl4rs_amd import dynamics as dyn
+    case = _case('ragged')
+    D, E, H1, H2, M, B = case['shape']
+    net = _net(case)
+    x, a, nxt, rew, mask = _dev(case, 'x', 'a', 'nxt', 'rew', 'mask')
+    mask[0] = 0
+    loss = net.loss_grad(x, a, nxt, rew, mask.contiguous(), seed=HASH_SEED, step=HASH_STEP)
+    r64, r32 = _ref_loss('ragged', 'all_on', F64, True), _ref_loss('ragged', 'all_on', F32, True)
+    G = dyn.unflatten(net.grad().cpu().numpy(), dyn.param_shapes(D, E, H1, H2), M)
+    assert float(loss[0]) == 0.0 and r64['loss'][0] == 0.0
+    for name, g in G[0].items():
+        assert (g == 0).all(), name                                     # the penalty is inside the masked mean: nothing is left
+        assert (r64['grads'][0][name] == 0).all(), name
+    ck = Check('ragged/zero-mask')
+    for name in G[1]:
+        ck('d ' + name, np.stack([g[name] for g in G[1:]]), np.stack([g[name] for g in r64['grads'][1:]]),
+           np.stack([g[name] for g in r32['grads'][1:]]))
+    net.close()
+    ck.done()
+
+
+ADAM_SEEDS = {'ragged': 23, 'batch300': 22}
+
+
+@functools.lru_cache(maxsize=None)
+def _adam_case(shape):
+    """Centred observations (no scaler) and biases around zero: every hidden unit is active on some rows and inactive on others.  With
+    the unit-interval inputs of the other cases a column is active on every row or on none, and the bias ahead of a batch norm then
+    has a gradient that is zero but for rounding - which Adam (eps 1e-8) turns into steps of the size of the learning rate on either
+    side, a comparison of rounding noise.  Asserted below on the float64 restatement: |d b1|, |d b2| > 1e-6 everywhere."""
+    D, E, H1, H2, M, B = SHAPES[shape]
+    return R.make_case(D, E, H1, H2, M, B, ADAM_SEEDS[shape], scalers=False, bias_shift=(0.0, 0.0))
+
+
+@functools.lru_cache(maxsize=None)
+def _ref_adam(shape, dt, steps=3, lr=1e-3):
+    from rl4rs_amd import dynamics as dyn
+    case = _adam_case(shape)
+    P, S = case['P'], case['S']
+    zeros = [dict((k, np.zeros_like(np.asarray(v, np.float64))) for k, v in p.items()) for p in P]
+    Mo, Vo = zeros, zeros
+    losses = []
+    for t in range(steps):
+        cfg = R.default_cfg(seed=HASH_SEED, step=t)
+        r = R.loss_grad(P, S, case['x'], case['a'], case['nxt'], case['rew'], case['mask'], cfg, dt, case['sc'])
+        if dt == F64:
+            R.check_conditions(r['outs'])
+            assert min(float(np.abs(g[k]).min()) for g in r['grads'] for k in ('b1', 'b2')) > 1e-6
+        S = R.new_state(S, r['outs'])
+        P, Mo, Vo = R.adam(P, r['grads'], Mo, Vo, t + 1, lr, dt)
+        losses.append(r['loss'])
+    D, E, H1, H2, M, B = case['shape']
+    flat = np.concatenate([np.asarray(d[name], np.float64).reshape(-1) for d in P for name, _ in dyn.param_shapes(D, E, H1, H2)])
+    return flat, np.stack(losses)
+
+
+@pytest.mark.parametrize('shape', ['ragged', 'batch300'])
+def test_three_adam_steps_track_the_restatement(shape):
+    from rl4rs_amd import dynamics as dyn
+    case = _adam_case(shape)
+    (p64, l64), (p32, l32) = _ref_adam(shape, F64), _ref_adam(shape, F32)
+    net = _net(case)
+    x, a, nxt, rew, mask = _dev(case, 'x', 'a', 'nxt', 'rew', 'mask')
+    losses = []
+    for t in range(3):
+        losses.append(net.loss_grad(x, a, nxt, rew, mask, seed=HASH_SEED, step=t))
+        net.adam_step(1e-3)
+    ck = Check(shape + '/adam')
+    ck('losses', torch.stack(losses), l64, l32)
+    D, E, H1, H2, M, B = case['shape']
+    shapes = dyn.param_shapes(D, E, H1, H2)
+    got, w64, w32 = [dyn.unflatten(np.asarray(v), shapes, M) for v in (net.params().cpu().numpy(), p64, p32)]
+    for name, _ in shapes:           # per parameter: each against its own yardstick
+        ck(name, np.stack([g[name] for g in got]), np.stack([g[name] for g in w64]), np.stack([g[name] for g in w32]))
+    assert float(np.abs(p64 - R.flat_params(case)).max()) > 2e-3          # three steps of lr 1e-3 moved something
+    net.close()
+    ck.done()
+
+
+@pytest.mark.parametrize('scalers', [True, False])
+@pytest.mark.parametrize('shape', ['default', 'ragged', 'rows8'])
+def test_predict_with_given_indices_and_noise(shape, scalers):
+    D, E, H1, H2, M, B = SHAPES[shape]
+    case = _case(shape) if scalers else R.make_case(D, E, H1, H2, M, B, SEEDS[shape], scalers=False)
+    cfg = _cfg('all_on')
+    net = _net(case)
+    x, a, idx, noise = _dev(case, 'x', 'a', 'indices', 'noise')
+    ck = Check('%s/predict%s' % (shape, '' if scalers else '/raw'))
+    ev, _, _ = R.forward(case['P'], case['S'], case['x'], case['a'], False, cfg, F64, case['sc'])
+    R.check_conditions(ev)
+    for vt, det, lam in (('max', False, None), ('data', False, None), ('max', True, None), ('max', False, 0.7), ('data', True, 1.0)):
+        got = net.predict(x, a, indices=idx, noise=noise, deterministic=det, variance_type=vt, lam=lam)
+        r64 = R.predict(case['P'], case['S'], case['x'], case['a'], case['indices'], case['noise'], cfg, F64, case['sc'], vt, det, lam)
+        r32 = R.predict(case['P'], case['S'], case['x'], case['a'], case['indices'], case['noise'], cfg, F32, case['sc'], vt, det, lam)
+        tag = '%s%s%s ' % (vt, ' det' if det else '', ' lam' if lam else '')
+        for name, g, w64, w32 in zip(('next_x', 'reward', 'variance'), got, r64, r32):
+            ck(tag + name, g, w64, w32)
+        assert torch.equal(got[3], idx)
+    net.close()
+    ck.done()
+
+
+def test_predict_without_indices_uses_every_member_and_is_reproducible():
+    D, E, H1, H2, M, B = SHAPES['ragged']
+    N = 4096
+    case = _case('ragged')
+    net = _net(case, max_rows=N)
+    rs = np.random.RandomState(5)
+    x = torch.from_numpy(rs.standard_normal((N, D)).astype(np.float32)).cuda()
+    a = torch.from_numpy(np.tanh(rs.standard_normal((N, E))).astype(np.float32)).cuda()
+    one = net.predict(x, a, seed=9, step=3)
+    two = net.predict(x, a, seed=9, step=3)
+    assert all(torch.equal(p, q) for p, q in zip(one, two))
+    used = one[3].cpu().numpy()
+    assert sorted(set(used.tolist())) == list(range(M))
+    assert (used == R.member_index(9, 3, N, M)).all()                    # the rule, restated in numpy
+    other = net.predict(x, a, seed=9, step=4)
+    assert not torch.equal(other[3], one[3]) and not torch.equal(other[0], one[0])
+    det = net.predict(x, a, seed=9, step=3, deterministic=True)
+    assert torch.equal(det[3], one[3]) and torch.equal(det[2], one[2]) and not torch.equal(det[0], one[0])
+    # the sampled noise is standard normal: (sample - mean) / sigma of the chosen member over 4096 x 38 draws
+    out = net.forward(x, a, train=False)
+    O = D + 1
+    pick = out[one[3].long(), torch.arange(N, device=out.device)]
+    sc = case['sc']
+    rg = torch.from_numpy(sc['obs_range']).cuda()
+    z = ((one[0] - det[0]) / rg) / pick[:, O:O + D].exp()
+    assert abs(float(z.mean())) < 0.02 and abs(float(z.std()) - 1.0) < 0.02, (float(z.mean()), float(z.std()))
+    net.close()
+
+
+def _toy_dataset(n_episodes, seed, D=12, E=4, T=9):
+    """episodes of a smooth deterministic system: x' = 0.9 x + 0.3 tanh(a W), r = mean(x' ^ 2) - in MDPDataset-style arrays"""
+    rs = np.random.RandomState(seed)
+    W = np.random.RandomState(0).standard_normal((E, D)).astype(np.float32)
+    obs, act, rew, ter = [], [], [], []
+    for _ in range(n_episodes):
+        x = rs.standard_normal(D).astype(np.float32)
+        r = 0.0
+        for t in range(T):
+            a = np.tanh(rs.standard_normal(E)).astype(np.float32)
+            obs.append(x); act.append(a); rew.append(r); ter.append(1.0 if t == T - 1 else 0.0)
+            x = (0.9 * x + 0.3 * np.tanh(a @ W)).astype(np.float32)
+            r = float((x ** 2).mean())
+    return dict(observations=np.stack(obs), actions=np.stack(act), rewards=np.array(rew, np.float32), terminals=np.array(ter, np.float32))
+
+
+def test_fit_lowers_the_loss_and_the_scorers_are_what_predict_gives(tmp_path):
+    from rl4rs_amd.dynamics import ProbabilisticEnsembleDynamics
+    from rl4rs_amd.offline_rl import transitions_from_mdp
+    data, ev = _toy_dataset(60, 1), _toy_dataset(10, 2)
+    model = ProbabilisticEnsembleDynamics({'action_emb_size': 4}, 12, hidden_units=(32, 16), n_ensembles=3, batch_size=64,
+                                          learning_rate=3e-3, predict_rows=40, seed=4)
+    hist = model.fit_mdp(data, n_epochs=8, eval_data=ev)
+    n = len(hist['loss'])
+    assert n == 8 * (540 // 64) and np.isfinite(hist['loss']).all()
+    assert np.mean(hist['loss'][-8:]) < np.mean(hist['loss'][:8]), (hist['loss'][:8], hist['loss'][-8:])
+    for k in ('observation_error', 'reward_error', 'variance'):
+        assert len(hist[k]) == 8 and np.isfinite(hist[k]).all()
+    # the last epoch's scorers, recomputed in torch from predict at the same (seed, step): 90 rows in chunks of 64
+    tr = [t.cuda() for t in transitions_from_mdp(ev['observations'], ev['actions'], ev['rewards'], ev['terminals'], discrete_action=False)]
+    nx, r, var = model.predict(tr[0], tr[1], with_variance=True, step=8)
+    want = {'observation_error': ((nx - tr[3]) ** 2).sum(dim=1).mean(), 'reward_error': ((r[:, 0] - tr[2]) ** 2).mean(),
+            'variance': var.mean()}
+    for k, v in want.items():
+        assert float(v) == hist[k][-1], (k, float(v), hist[k][-1])
+    # raw units in, raw units out; the scalers were fitted on the dataset
+    assert float((model.scaler.min - torch.from_numpy(data['observations']).min(dim=0).values).abs().max()) == 0.0
+    assert nx.shape == tr[3].shape and r.shape == (tr[0].shape[0], 1) and float(var.min()) > 0
+    # save / load: parameters, u / v, running statistics, scaler constants and Adam state all travel
+    path = str(tmp_path / 'dyn.npz')
+    model.save_model(path)
+    other = ProbabilisticEnsembleDynamics({'action_emb_size': 4}, 12, hidden_units=(32, 16), n_ensembles=3, batch_size=64,
+                                          learning_rate=3e-3, predict_rows=40, seed=99)
+    other.load_model(path)
+    assert torch.equal(other.net.params(), model.net.params()) and torch.equal(other.net.state(), model.net.state())
+    assert all(torch.equal(p, q) if torch.is_tensor(p) else p == q for p, q in zip(other.net.adam_state(), model.net.adam_state()))
+    got = other.predict(tr[0], tr[1], with_variance=True, step=8, seed=4)
+    assert all(torch.equal(p, q) for p, q in zip(got, (nx, r, var)))
+    b = [t[:64].contiguous() for t in tr]
+    m = (torch.rand((3, 64), device='cuda') < 0.5).float()
+    assert torch.equal(model.update(b[0], b[1], b[2], b[3], mask=m, seed=4), other.update(b[0], b[1], b[2], b[3], mask=m, seed=4))
+    assert torch.equal(other.net.params(), model.net.params())
+    with pytest.raises(ValueError):
+        ProbabilisticEnsembleDynamics({'action_emb_size': 4}, 12, hidden_units=(32, 16), n_ensembles=2, batch_size=64).load_model(path)
+    model.close()
+    other.close()
