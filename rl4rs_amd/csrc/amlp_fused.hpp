@@ -364,12 +364,7 @@ __global__ void k_adam_multi(AdamMulti a) {
     const long long j = i - a.start[t];
     float pj = d.p[j];
     if (d.g) {
-        const float gj = d.g[j];
-        const float mj = a.b1 * d.m[j] + (1.f - a.b1) * gj;
-        const float vj = a.b2 * d.v[j] + (1.f - a.b2) * gj * gj;
-        d.m[j] = mj;
-        d.v[j] = vj;
-        pj -= d.lr_t * mj / (sqrtf(vj) + d.eps_t);
+        pj = adam_elem(pj, d.m, d.v, j, d.g[j], d.lr_t, a.b1, a.b2, d.eps_t);
         d.p[j] = pj;
     }
     if (d.targ) d.targ[j] = (1.f - a.tau) * d.targ[j] + a.tau * pj;

@@ -312,9 +312,9 @@ enum { AP_W1 = 0, AP_B1, AP_W2, AP_B2, AP_W3, AP_B3, AP_COUNT };
 
 struct rl4rs_amlp {
     rl4rs_amlp_cfg c;
-    int64_t n_params, off[AP_COUNT], size[AP_COUNT];
+    int64_t off[AP_COUNT], size[AP_COUNT];
     TrainCtx cx;
-    float *params, *grad, *adam_m, *adam_v;
+    OptBlock opt;
     float *proj, *h1, *h2;              // forward: [max_rows, hidden1] observation-side projection (one row per DISTINCT observation), activations
     float *d_h1, *d_h2, *d_proj;        // backward scratch, [max_grad_rows, ...]
     int last_n, last_rep;               // rows of the last forward (the backward must match)
@@ -323,7 +323,6 @@ struct rl4rs_amlp {
                                         // cleared by everything that may write the parameters (Adam, copies, soft updates, handing out the
                                         // raw pointer) and by a non-fused forward; the fused backward rebuilds them when it is unset
     float *w1p, *w2p, *w3p, *w1xp;      // fp16 hi / lo fragment planes of W1's action rows, W2, W3 (and W1's observation rows) for rl4rs_amlp_forward_h16 (NULL: shape not eligible)
-    int64_t adam_t;
     std::vector<void*> owned;
 };
 
@@ -355,7 +354,7 @@ static int amlp_forward_fused(int n, rl4rs_amlp* const* nets, int N, const float
     int t_elems = 0;
     for (int i = 0; i < n; ++i) {
         rl4rs_amlp* p = nets[i];
-        const float* P = p->params;
+        const float* P = p->opt.params;
         const int64_t* o = p->off;
         const int D = p->c.obs_dim, E = p->c.act_dim, K = p->c.out_dim;
         x.n[i] = AmlpFwd4{obs, act, P + o[AP_W1], P + o[AP_B1], P + o[AP_W2], P + o[AP_B2], P + o[AP_W3], P + o[AP_B3], p->h1, p->h2, outs[i],
@@ -386,12 +385,12 @@ static int amlp_backward_fused(int n, rl4rs_amlp* const* nets, int N, const floa
     for (int i = 0; i < n; ++i) {
         rl4rs_amlp* p = nets[i];
         const int64_t* o = p->off;
-        float* G = p->grad;
+        float* G = p->opt.grad;
         const int D = p->c.obs_dim, E = p->c.act_dim, K = p->c.out_dim, H1 = 256, H2 = 256;
         if (!p->t_valid) {
             // the forward of these rows did not take the fused path (rl4rs_amlp_set_fused toggled in between, a rep > 1 forward) or the
             // parameters may have been written since: nothing tracked that before ADVICE r5 and the chain read stale transposes
-            const float* P = p->params;
+            const float* P = p->opt.params;
             const int t_elems = 256 * 256 + 256 * K + 256 * E;
             hipLaunchKernelGGL(k_amlp_transposes, dim3((t_elems + 255) / 256), dim3(256), 0, st, P + o[AP_W3], K, p->w3t, P + o[AP_W2], p->w2t,
                                P + o[AP_W1] + (size_t)D * 256, E, p->w1at);
@@ -439,7 +438,7 @@ int rl4rs_amlp_create(const rl4rs_amlp_cfg* c, const float* params_host, void* s
     const int64_t D = c->obs_dim, E = c->act_dim, H1 = c->hidden1, H2 = c->hidden2, K = c->out_dim;
     rl4rs_amlp* p = new rl4rs_amlp();
     p->c = *c;
-    p->adam_t = 0;
+    p->opt.t = 0;
     p->last_n = p->last_rep = 0;
     p->w1p = p->w2p = p->w3p = p->w1xp = nullptr;
     p->w2t = p->w3t = p->w1at = nullptr;
@@ -447,7 +446,7 @@ int rl4rs_amlp_create(const rl4rs_amlp_cfg* c, const float* params_host, void* s
     const int64_t sizes[AP_COUNT] = {(D + E) * H1, H1, H1 * H2, H2, H2 * K, K};
     int64_t o = 0;
     for (int i = 0; i < AP_COUNT; ++i) { p->off[i] = o; p->size[i] = sizes[i]; o += sizes[i]; }
-    p->n_params = o;
+    p->opt.n = o;
     int rc;
     auto al = [&](float** dst, size_t n) {
         int r = dev_alloc(dst, n);
@@ -457,12 +456,12 @@ int rl4rs_amlp_create(const rl4rs_amlp_cfg* c, const float* params_host, void* s
 #define AM_FAIL(expr) do { if ((rc = (expr)) != RL4RS_OK) { rl4rs_amlp_destroy(p); return rc; } } while (0)
 #define AM_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { set_error("%s failed: %s", #expr, hipGetErrorString(e_)); \
         rl4rs_amlp_destroy(p); return RL4RS_EHIP; } } while (0)
-    AM_FAIL(al(&p->params, p->n_params)); AM_FAIL(al(&p->grad, p->n_params));
-    AM_FAIL(al(&p->adam_m, p->n_params)); AM_FAIL(al(&p->adam_v, p->n_params));
-    AM_HIP(hipMemcpyAsync(p->params, params_host, (size_t)p->n_params * 4, hipMemcpyHostToDevice, st));
-    AM_HIP(hipMemsetAsync(p->grad, 0, (size_t)p->n_params * 4, st));
-    AM_HIP(hipMemsetAsync(p->adam_m, 0, (size_t)p->n_params * 4, st));
-    AM_HIP(hipMemsetAsync(p->adam_v, 0, (size_t)p->n_params * 4, st));
+    AM_FAIL(al(&p->opt.params, p->opt.n)); AM_FAIL(al(&p->opt.grad, p->opt.n));
+    AM_FAIL(al(&p->opt.m, p->opt.n)); AM_FAIL(al(&p->opt.v, p->opt.n));
+    AM_HIP(hipMemcpyAsync(p->opt.params, params_host, (size_t)p->opt.n * 4, hipMemcpyHostToDevice, st));
+    AM_HIP(hipMemsetAsync(p->opt.grad, 0, (size_t)p->opt.n * 4, st));
+    AM_HIP(hipMemsetAsync(p->opt.m, 0, (size_t)p->opt.n * 4, st));
+    AM_HIP(hipMemsetAsync(p->opt.v, 0, (size_t)p->opt.n * 4, st));
     const size_t B = c->max_rows, G = c->max_grad_rows;
     AM_FAIL(al(&p->proj, B * H1)); AM_FAIL(al(&p->h1, B * H1)); AM_FAIL(al(&p->h2, B * H2));
     if (G > 0) {
@@ -489,37 +488,26 @@ int rl4rs_amlp_create(const rl4rs_amlp_cfg* c, const float* params_host, void* s
 }
 
 int rl4rs_amlp_params(rl4rs_amlp* p, float** params_dev, float** grad_dev, int64_t* count) {
-    RL4RS_REQUIRE(p, "amlp_params: null handle");
-    if (params_dev) { *params_dev = p->params; p->t_valid = false; }       // (a writable pointer leaves the library)
-    if (grad_dev) *grad_dev = p->grad;
-    if (count) *count = p->n_params;
-    return RL4RS_OK;
+    if (p && params_dev) p->t_valid = false;       // (a writable pointer leaves the library)
+    return opt_params(RL4RS_OPT(p), params_dev, grad_dev, count, "amlp_params");
 }
 
 int rl4rs_amlp_adam_state(rl4rs_amlp* p, float** m_dev, float** v_dev, int64_t* step) {
-    RL4RS_REQUIRE(p, "amlp_adam_state: null handle");
-    if (m_dev) *m_dev = p->adam_m;
-    if (v_dev) *v_dev = p->adam_v;
-    if (step) *step = p->adam_t;
-    return RL4RS_OK;
+    return opt_adam_state(RL4RS_OPT(p), m_dev, v_dev, step, "amlp_adam_state");
 }
 int rl4rs_amlp_set_adam_step(rl4rs_amlp* p, int64_t step) {
-    RL4RS_REQUIRE(p && step >= 0, "amlp_set_adam_step: bad argument");
-    p->adam_t = step;
-    return RL4RS_OK;
+    return opt_set_adam_step(RL4RS_OPT(p), step, "amlp_set_adam_step");
 }
 
 int rl4rs_amlp_copy_params(rl4rs_amlp* dst, const rl4rs_amlp* src, void* stream) {
-    RL4RS_REQUIRE(dst && src && dst->n_params == src->n_params, "amlp_copy_params: handles differ");
-    RL4RS_HIP_TRY(hipMemcpyAsync(dst->params, src->params, (size_t)src->n_params * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    dst->t_valid = false;
-    return RL4RS_OK;
+    if (dst) dst->t_valid = false;
+    return opt_copy_params(RL4RS_OPT(dst), RL4RS_OPT(src), stream, "amlp_copy_params");
 }
 
 int rl4rs_amlp_soft_update(rl4rs_amlp* targ, const rl4rs_amlp* src, float tau, void* stream) {
-    RL4RS_REQUIRE(targ && src && targ->n_params == src->n_params, "amlp_soft_update: handles differ");
-    hipLaunchKernelGGL(k_soft_update, dim3((unsigned)((src->n_params + 255) / 256)), dim3(256), 0, (hipStream_t)stream, targ->params,
-                       src->params, src->n_params, tau);
+    RL4RS_REQUIRE(targ && src && targ->opt.n == src->opt.n, "amlp_soft_update: handles differ");
+    hipLaunchKernelGGL(k_soft_update, dim3((unsigned)((src->opt.n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, targ->opt.params,
+                       src->opt.params, src->opt.n, tau);
     RL4RS_LAUNCH_CHECK();
     targ->t_valid = false;
     return RL4RS_OK;
@@ -531,7 +519,7 @@ int rl4rs_amlp_forward(rl4rs_amlp* p, int32_t N, int32_t rep, const float* obs, 
                   (p->c.act_dim > 0 || rep == 1), "amlp_forward: bad argument (N=%d, rep=%d, max_rows=%d)", N, rep, p ? p->c.max_rows : -1);
     hipStream_t st = (hipStream_t)stream;
     const int D = p->c.obs_dim, E = p->c.act_dim, H1 = p->c.hidden1, H2 = p->c.hidden2, K = p->c.out_dim, R = N / rep;
-    const float* P = p->params;
+    const float* P = p->opt.params;
     const int64_t* o = p->off;
     int rc;
     if (amlp_fused_call(p, N, rep)) {
@@ -577,7 +565,7 @@ int rl4rs_amlp_forward_h16(rl4rs_amlp* p, int32_t N, int32_t rep, const float* o
     RL4RS_REQUIRE(p->w1p, "amlp_forward_h16: this network's shape has no fp16x2 form (rl4rs_amlp_h16_ok)");
     hipStream_t st = (hipStream_t)stream;
     const int D = p->c.obs_dim, E = p->c.act_dim, H1 = p->c.hidden1, H2 = p->c.hidden2, K = p->c.out_dim, R = N / rep;
-    const float* P = p->params;
+    const float* P = p->opt.params;
     const int64_t* o = p->off;
     int rc;
     // the observation-side projection: a few hundred distinct rows (a training minibatch) through the small fp32 form, thousands (an
@@ -609,8 +597,8 @@ int rl4rs_amlp_backward(rl4rs_amlp* p, int32_t N, int32_t rep, const float* obs,
     RL4RS_REQUIRE(!dact || p->c.act_dim > 0, "amlp_backward: no action input to differentiate");
     hipStream_t st = (hipStream_t)stream;
     const int D = p->c.obs_dim, E = p->c.act_dim, H1 = p->c.hidden1, H2 = p->c.hidden2, K = p->c.out_dim, R = N / rep;
-    const float* P = p->params;
-    float* G = p->grad;
+    const float* P = p->opt.params;
+    float* G = p->opt.grad;
     const int64_t* o = p->off;
     auto ew = [](int n) { return dim3((n + 255) / 256); };
     const dim3 b256(256);
@@ -646,13 +634,7 @@ int rl4rs_amlp_backward(rl4rs_amlp* p, int32_t N, int32_t rep, const float* obs,
 // torch.optim.Adam (see rl4rs_qnet_adam_step)
 int rl4rs_amlp_adam_step(rl4rs_amlp* p, float lr, float beta1, float beta2, float eps, void* stream) {
     RL4RS_REQUIRE(p, "amlp_adam_step: null handle");
-    hipStream_t st = (hipStream_t)stream;
-    p->adam_t += 1;
-    const double t = (double)p->adam_t;
-    const double c2 = sqrt(1.0 - pow((double)beta2, t));
-    const float lr_t = (float)(lr * c2 / (1.0 - pow((double)beta1, t)));
-    hipLaunchKernelGGL(k_adam, dim3((unsigned)((p->n_params + 255) / 256)), dim3(256), 0, st, p->params, p->grad, p->adam_m, p->adam_v,
-                       (int)p->n_params, lr_t, beta1, beta2, (float)(eps * c2), (const float*)nullptr, 0.f);
+    adam_step(p->opt, p->opt.grad, ADAM_TORCH, lr, beta1, beta2, eps, nullptr, 0.f, nullptr, (hipStream_t)stream);
     RL4RS_LAUNCH_CHECK();
     p->t_valid = false;
     return RL4RS_OK;
@@ -672,20 +654,17 @@ int rl4rs_amlp_adam_multi(int32_t n, rl4rs_amlp* const* nets, const float* lr, c
         RL4RS_REQUIRE(p, "amlp_adam_multi: null handle %d", i);
         rl4rs_amlp* tg = targets ? targets[i] : nullptr;
         RL4RS_REQUIRE(do_adam[i] || tg, "amlp_adam_multi: network %d has neither a step nor a target", i);
-        RL4RS_REQUIRE(!tg || tg->n_params == p->n_params, "amlp_adam_multi: target %d has another shape", i);
+        RL4RS_REQUIRE(!tg || tg->opt.n == p->opt.n, "amlp_adam_multi: target %d has another shape", i);
         AdamMultiDesc& d = a.d[i];
-        d.p = p->params; d.targ = tg ? tg->params : nullptr;
+        d.p = p->opt.params; d.targ = tg ? tg->opt.params : nullptr;
         if (tg) tg->t_valid = false;
         if (do_adam[i]) {
             p->t_valid = false;
-            p->adam_t += 1;
-            const double t = (double)p->adam_t;
-            const double c2 = sqrt(1.0 - pow((double)beta2, t));
-            d.g = p->grad; d.m = p->adam_m; d.v = p->adam_v;
-            d.lr_t = (float)(lr[i] * c2 / (1.0 - pow((double)beta1, t)));
-            d.eps_t = (float)(eps * c2);
+            const AdamTerms s = adam_advance(p->opt, ADAM_TORCH, lr[i], beta1, beta2, eps);
+            d.g = p->opt.grad; d.m = p->opt.m; d.v = p->opt.v;
+            d.lr_t = s.lr_t; d.eps_t = s.eps_or_bc2;
         }
-        a.start[i + 1] = a.start[i] + p->n_params;
+        a.start[i + 1] = a.start[i] + p->opt.n;
     }
     hipLaunchKernelGGL(k_adam_multi, dim3((unsigned)((a.start[n] + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
     RL4RS_LAUNCH_CHECK();

@@ -149,10 +149,10 @@ struct CellSave {      // one recurrent layer of one sequence input, training mo
 
 struct rl4rs_dientrain {
     rl4rs_dien_cfg c;
-    int64_t n_params, off[DP_COUNT], size[DP_COUNT];
+    int64_t off[DP_COUNT], size[DP_COUNT];
     int max_batch, F;
     TrainCtx cx;
-    float *params, *grad, *adam_m, *adam_v;
+    OptBlock opt;
     // saved forward
     float *X[4], *inp[4], *hid1[4], *hid2[4], *score[4];
     CellSave gru[4], aug[4];
@@ -164,8 +164,7 @@ struct rl4rs_dientrain {
     float *d_score[4], *dK[4], *dAg[4], *dAc[4];            // per sequence input: the inputs' recurrences run in one launch
     float *pk_g[4], *pk_c[4], *pkT_g[4], *pkT_c[4];         // h-side weights in MFMA fragment order (forward) / transposed (backward)
     int32_t* iota;
-    float *s_tmpw, *loss_rows, *lr_dummy;
-    int64_t adam_t;
+    float *s_tmpw, *loss_rows;
     std::vector<void*> owned;
     // Round 6: the work that follows a recurrent layer is a chain of ~35 small launches PER SEQUENCE INPUT (sample-axis reductions,
     // transposes, the attention MLP): 570 + 570 + 280 + 280 us of a 3.97 ms step, most of them far from filling the chip.  The odd
@@ -195,10 +194,10 @@ int layer_forward(rl4rs_dientrain* t, int N, int which, const float* const* Xin,
         const CellSave& cl = which == 0 ? t->gru[s] : t->aug[s];
         const int Hd = cl.Hd;
         f.Hd = Hd;
-        const float* Wg = t->params + t->off[cl.pgw];
-        const float* bg = t->params + t->off[cl.pgw + 1];
-        const float* Wc = t->params + t->off[cl.pgw + 2];
-        const float* bc = t->params + t->off[cl.pgw + 3];
+        const float* Wg = t->opt.params + t->off[cl.pgw];
+        const float* bg = t->opt.params + t->off[cl.pgw + 1];
+        const float* Wc = t->opt.params + t->off[cl.pgw + 2];
+        const float* bc = t->opt.params + t->off[cl.pgw + 3];
         if ((rc = launch_gemm_f32(Xin[s], E, Wg, 2 * Hd, bg, cl.A1, 3 * Hd, N * L, 2 * Hd, E, 0, st))) return rc;
         if ((rc = launch_gemm_f32(Xin[s], E, Wc, Hd, bc, cl.A1 + 2 * Hd, 3 * Hd, N * L, Hd, E, 0, st))) return rc;
         if ((rc = launch_pack_frag(Wg, 2 * Hd, E, Hd, 2 * Hd, 0, t->pk_g[s], st))) return rc;
@@ -223,8 +222,8 @@ int layer_backward(rl4rs_dientrain* t, int N, int which, const float* const* up_
         const CellSave& cl = which == 0 ? t->gru[s] : t->aug[s];
         const int Hd = cl.Hd;
         b.Hd = Hd;
-        const float* Wg = t->params + t->off[cl.pgw];
-        const float* Wc = t->params + t->off[cl.pgw + 2];
+        const float* Wg = t->opt.params + t->off[cl.pgw];
+        const float* Wc = t->opt.params + t->off[cl.pgw + 2];
         // h-side weights transposed, in fragment order: Wc[E:, :]^T [Hd x Hd], Wg[E:, :]^T [2Hd x Hd]
         if ((rc = launch_pack_frag(Wc, Hd, E, Hd, Hd, 1, t->pkT_c[s], st))) return rc;
         if ((rc = launch_pack_frag(Wg, 2 * Hd, E, 2 * Hd, Hd, 1, t->pkT_g[s], st))) return rc;
@@ -243,12 +242,12 @@ int layer_backward(rl4rs_dientrain* t, int N, int which, const float* const* up_
 int cell_backward_post(rl4rs_dientrain* t, int N, const CellSave& cl, const float* Xin, const float* dAg, const float* dAc,
                        float* dXin_acc, bool accumulate, hipStream_t st, const InputScratch& sc) {
     const int E = t->c.emb_size, L = t->c.maxlen, Hd = cl.Hd;
-    const float* Wg = t->params + t->off[cl.pgw];
-    const float* Wc = t->params + t->off[cl.pgw + 2];
-    float* gWg = t->grad + t->off[cl.pgw];
-    float* gbg = t->grad + t->off[cl.pgw + 1];
-    float* gWc = t->grad + t->off[cl.pgw + 2];
-    float* gbc = t->grad + t->off[cl.pgw + 3];
+    const float* Wg = t->opt.params + t->off[cl.pgw];
+    const float* Wc = t->opt.params + t->off[cl.pgw + 2];
+    float* gWg = t->opt.grad + t->off[cl.pgw];
+    float* gbg = t->opt.grad + t->off[cl.pgw + 1];
+    float* gWc = t->opt.grad + t->off[cl.pgw + 2];
+    float* gbc = t->opt.grad + t->off[cl.pgw + 3];
     int rc;
     const dim3 b256(256);
     const int Ns = N * L;
@@ -320,7 +319,7 @@ int rl4rs_dientrain_create(const rl4rs_dien_cfg* c, const rl4rs_dien_weights* w,
     rl4rs_dientrain* t = new rl4rs_dientrain();
     t->c = *c;
     t->max_batch = max_batch;
-    t->adam_t = 0;
+    t->opt.t = 0;
     t->F = (int)(S * NH2 + U + (Cn + 1) * E);
     int64_t sizes[DP_COUNT];
     const float* src[DP_COUNT];
@@ -340,7 +339,7 @@ int rl4rs_dientrain_create(const rl4rs_dien_cfg* c, const rl4rs_dien_weights* w,
     }
     int64_t o = 0;
     for (int i = 0; i < DP_COUNT; ++i) { t->off[i] = o; t->size[i] = sizes[i]; o += sizes[i]; }
-    t->n_params = o;
+    t->opt.n = o;
     int rc = RL4RS_OK;
     auto al = [&](float** dst, size_t n) {
         int r = dev_alloc(dst, n);
@@ -350,14 +349,14 @@ int rl4rs_dientrain_create(const rl4rs_dien_cfg* c, const rl4rs_dien_weights* w,
 #define DT_FAIL(expr) do { if ((rc = (expr)) != RL4RS_OK) { rl4rs_dientrain_destroy(t); return rc; } } while (0)
 #define DT_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { set_error("%s failed: %s", #expr, hipGetErrorString(e_)); \
         rl4rs_dientrain_destroy(t); return RL4RS_EHIP; } } while (0)
-    DT_FAIL(al(&t->params, t->n_params));
-    DT_FAIL(al(&t->grad, t->n_params));
-    DT_FAIL(al(&t->adam_m, t->n_params));
-    DT_FAIL(al(&t->adam_v, t->n_params));
+    DT_FAIL(al(&t->opt.params, t->opt.n));
+    DT_FAIL(al(&t->opt.grad, t->opt.n));
+    DT_FAIL(al(&t->opt.m, t->opt.n));
+    DT_FAIL(al(&t->opt.v, t->opt.n));
     for (int i = 0; i < DP_COUNT; ++i)
-        if (sizes[i]) DT_HIP(hipMemcpyAsync(t->params + t->off[i], src[i], (size_t)sizes[i] * 4, hipMemcpyHostToDevice, st));
-    DT_HIP(hipMemsetAsync(t->adam_m, 0, (size_t)t->n_params * 4, st));
-    DT_HIP(hipMemsetAsync(t->adam_v, 0, (size_t)t->n_params * 4, st));
+        if (sizes[i]) DT_HIP(hipMemcpyAsync(t->opt.params + t->off[i], src[i], (size_t)sizes[i] * 4, hipMemcpyHostToDevice, st));
+    DT_HIP(hipMemsetAsync(t->opt.m, 0, (size_t)t->opt.n * 4, st));
+    DT_HIP(hipMemsetAsync(t->opt.v, 0, (size_t)t->opt.n * 4, st));
     const size_t B = max_batch, Ns = B * L;
     for (int s = 0; s < S; ++s) {
         DT_FAIL(al(&t->X[s], Ns * E)); DT_FAIL(al(&t->inp[s], Ns * 4 * E)); DT_FAIL(al(&t->hid1[s], Ns * 64));
@@ -391,7 +390,6 @@ int rl4rs_dientrain_create(const rl4rs_dien_cfg* c, const rl4rs_dien_weights* w,
     DT_FAIL(al(&t->d_inp, Ns * 4 * E)); DT_FAIL(al(&t->dq, B * E));
     DT_FAIL(al(&t->dX, Ns * E)); DT_FAIL(al(&t->hprev, Ns * NH2));
     DT_FAIL(al(&t->s_tmpw, 4)); DT_FAIL(al(&t->loss_rows, B));
-    DT_FAIL(al(&t->lr_dummy, 4));
     // reduction scratch: the largest M x Nc of any weight gradient, times the number of 512-sample chunks of N * L
     int64_t wmax = (int64_t)t->F * 256;
     if (Dn * U > wmax) wmax = Dn * U;
@@ -423,11 +421,7 @@ int rl4rs_dientrain_create(const rl4rs_dien_cfg* c, const rl4rs_dien_weights* w,
 }
 
 int rl4rs_dientrain_params(rl4rs_dientrain* t, float** params_dev, float** grad_dev, int64_t* count) {
-    RL4RS_REQUIRE(t, "dientrain_params: null handle");
-    if (params_dev) *params_dev = t->params;
-    if (grad_dev) *grad_dev = t->grad;
-    if (count) *count = t->n_params;
-    return RL4RS_OK;
+    return opt_params(RL4RS_OPT(t), params_dev, grad_dev, count, "dientrain_params");
 }
 
 int rl4rs_dientrain_masks(rl4rs_dientrain* t, uint8_t** mask1_dev, uint8_t** mask2_dev) {
@@ -447,8 +441,8 @@ int rl4rs_dientrain_grad(rl4rs_dientrain* t, int32_t N, const float* dense, cons
     const int E = t->c.emb_size, U = t->c.hidden_units, H = t->c.category_hash_size, Dn = t->c.dense_feature_num;
     const int Cn = t->c.category_feature_num, K = t->c.class_num, S = t->c.seq_num, L = t->c.maxlen, NH2 = 2 * E, F = t->F;
     const int Ns = N * L;
-    float* P = t->params;
-    float* G = t->grad;
+    float* P = t->opt.params;
+    float* G = t->opt.grad;
     const int64_t* o = t->off;
     const int off_d = S * NH2, off_c = S * NH2 + U, off_f = S * NH2 + U + E;
     int rc;
@@ -588,12 +582,7 @@ int rl4rs_dientrain_step(rl4rs_dientrain* t, int32_t N, const float* dense, cons
                          uint32_t step, float* loss_dev, void* stream) {
     int rc = rl4rs_dientrain_grad(t, N, dense, cat, seq, labels, dropout_rate, seed, step, loss_dev, stream);
     if (rc) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    t->adam_t += 1;
-    const double tt = (double)t->adam_t;
-    const float lr_t = (float)(lr * sqrt(1.0 - pow((double)beta2, tt)) / (1.0 - pow((double)beta1, tt)));
-    hipLaunchKernelGGL(k_adam, dim3((unsigned)((t->n_params + 255) / 256)), dim3(256), 0, st, t->params, t->grad, t->adam_m, t->adam_v,
-                       (int)t->n_params, lr_t, beta1, beta2, eps, t->lr_dummy, 0.f);
+    adam_step(t->opt, t->opt.grad, ADAM_TF, lr, beta1, beta2, eps, nullptr, 0.f, nullptr, (hipStream_t)stream);
     RL4RS_LAUNCH_CHECK();
     return RL4RS_OK;
 }

@@ -387,39 +387,6 @@ __global__ __launch_bounds__(256) void k_greedy_simple(PolDims d, const float* _
     if (lane == 0) actions[n] = best;
 }
 
-// Adam with tf.clip_by_norm per VARIABLE (RLlib's minimize_and_clip): sumsq[v] of the four segments W1 | b1 | W2e | b2e, one
-// workgroup each, fixed order; then k_adam's arithmetic with the norm of the element's own variable.
-struct VarSegs { int end[4]; };
-__global__ __launch_bounds__(256) void k_sumsq_vars(const float* __restrict__ g, VarSegs sg, float* __restrict__ out) {
-    __shared__ float sm[256];
-    const int v = blockIdx.x, lo = v == 0 ? 0 : sg.end[v - 1], hi = sg.end[v];
-    float s = 0.f;
-    for (int i = lo + threadIdx.x; i < hi; i += 256) s += g[i] * g[i];
-    sm[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sm[threadIdx.x] += sm[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[v] = sm[0];
-}
-__global__ void k_adam_vars(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int count,
-                            VarSegs sg, float lr_t, float b1, float b2, float eps, const float* __restrict__ sumsq, float clip) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= count) return;
-    float gi = g[i];
-    if (clip > 0.f) {
-        const int var = (i >= sg.end[0]) + (i >= sg.end[1]) + (i >= sg.end[2]);
-        const float norm = sqrtf(sumsq[var]);
-        if (norm > clip) gi *= clip / norm;          // tf.clip_by_norm
-    }
-    const float mi = b1 * m[i] + (1.f - b1) * gi;
-    const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-    m[i] = mi;
-    v[i] = vi;
-    p[i] -= lr_t * mi / (sqrtf(vi) + eps);
-}
-
 }  // namespace rl4rs
 
 struct rl4rs_replay {
@@ -652,10 +619,10 @@ int rl4rs_policy_dqn_loss_grad(rl4rs_policy* p, const float* target_params_dev, 
     DqnRows a;
     memset(&a, 0, sizeof(a));
     a.d = d; a.N = N; a.double_q = double_q ? 1 : 0; a.gamma = gamma;
-    a.prm = p->params; a.tprm = target_params_dev;
+    a.prm = p->opt.params; a.tprm = target_params_dev;
     a.obs = obs; a.next_obs = next_obs; a.next_mask = next_mask_bits; a.act = actions; a.rew = rewards; a.done = dones; a.w = weights;
     a.H = p->H; a.dHpre = p->dHpre; a.g = p->dqn_g; a.td = td_dev; a.astar = next_action_dev; a.terms = p->terms;
-    const float* W1 = p->params;
+    const float* W1 = p->opt.params;
     const float* b1 = W1 + (size_t)d.OD * d.HID;
     const float* W2 = b1 + d.HID;
     const float* b2 = W2 + (size_t)d.HID * d.AE;
@@ -714,7 +681,7 @@ int rl4rs_policy_greedy(rl4rs_policy* p, int32_t N, const float* obs, const uint
     hipStream_t st = (hipStream_t)stream;
     const PolDims& d = p->d;
     if (p->opt_tile && N <= p->max_rows) {
-        const float* W1 = p->params;
+        const float* W1 = p->opt.params;
         const float* b1 = W1 + (size_t)d.OD * d.HID;
         const float* W2 = b1 + d.HID;
         const float* b2 = W2 + (size_t)d.HID * d.AE;
@@ -726,7 +693,7 @@ int rl4rs_policy_greedy(rl4rs_policy* p, int32_t N, const float* obs, const uint
         const size_t smem = fwd_smem(d, 0);
         int rc = raise_dyn_smem(reinterpret_cast<const void*>(&k_greedy_simple), smem);
         if (rc) return rc;
-        hipLaunchKernelGGL(k_greedy_simple, dim3((N + 3) / 4), dim3(256), smem, st, d, p->params, N, obs, mask_bits, actions, q_out);
+        hipLaunchKernelGGL(k_greedy_simple, dim3((N + 3) / 4), dim3(256), smem, st, d, p->opt.params, N, obs, mask_bits, actions, q_out);
     }
     RL4RS_LAUNCH_CHECK();
     return RL4RS_OK;
@@ -742,12 +709,10 @@ int rl4rs_policy_adam_step_clip_by_var(rl4rs_policy* p, const float* grad_dev, f
     sg.end[1] = sg.end[0] + d.HID;
     sg.end[2] = sg.end[1] + d.HID * d.AE;
     sg.end[3] = sg.end[2] + d.AE;
-    p->adam_t += 1;
-    const double t = (double)p->adam_t;
-    const float lr_t = (float)(lr * sqrt(1.0 - pow((double)beta2, t)) / (1.0 - pow((double)beta1, t)));
+    const float lr_t = adam_advance(p->opt, ADAM_TF, lr, beta1, beta2, eps).lr_t;
     if (var_clip > 0.f) hipLaunchKernelGGL(k_sumsq_vars, dim3(4), dim3(256), 0, st, grad_dev, sg, p->sumsq);
-    hipLaunchKernelGGL(k_adam_vars, dim3((p->n_params + 255) / 256), dim3(256), 0, st, p->params, grad_dev, p->adam_m, p->adam_v,
-                       p->n_params, sg, lr_t, beta1, beta2, eps, p->sumsq, var_clip);
+    hipLaunchKernelGGL(k_adam_vars, dim3((p->opt.n + 255) / 256), dim3(256), 0, st, p->opt.params, grad_dev, p->opt.m, p->opt.v,
+                       p->opt.n, sg, lr_t, beta1, beta2, eps, p->sumsq, var_clip);
     RL4RS_LAUNCH_CHECK();
     return RL4RS_OK;
 }

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "optim.hpp"
 
 namespace rl4rs {
 namespace {
@@ -407,19 +408,6 @@ __global__ __launch_bounds__(256) void k_dyn_sn_bwd(DynDims d, const float* __re
     }
 }
 
-// torch.optim.Adam: p -= (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
-__global__ void k_dyn_adam(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t count,
-                           float step_size, float inv_sqrt_bc2, float b1, float b2, float eps) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= count) return;
-    const float gi = g[i];
-    const float mi = b1 * m[i] + (1.f - b1) * gi;
-    const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-    m[i] = mi;
-    v[i] = vi;
-    p[i] -= step_size * (mi / (sqrtf(vi) * inv_sqrt_bc2 + eps));
-}
-
 __device__ __forceinline__ float dyn_gauss(uint32_t seed, uint32_t step, uint32_t row, int m, int o) {
     const float u1 = uniform01(seed, step, row, (DYN_SITE_NOISE + 2u * (uint32_t)m) * 65536u + (uint32_t)o);
     const float u2 = uniform01(seed, step, row, (DYN_SITE_NOISE + 2u * (uint32_t)m + 1u) * 65536u + (uint32_t)o);
@@ -504,11 +492,6 @@ __global__ void k_sac_target(const float* __restrict__ q1, const float* __restri
     y[i] = rew[i] + gamma * (1.f - ter[i]) * soft;
 }
 
-__global__ void k_dyn_fill(float* __restrict__ p, float v, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) p[i] = v;
-}
-
 inline dim3 dyn_ew(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
 
 }  // namespace
@@ -519,9 +502,10 @@ using namespace rl4rs;
 struct rl4rs_dyn {
     rl4rs_dyn_cfg c;
     DynDims d;
-    int64_t n_params, n_state, adam_t;
+    int64_t n_state;
+    OptBlock opt;
     void* arena;
-    float *params, *grad, *adam_m, *adam_v, *state, *stats, *inv_sigma;
+    float *state, *stats, *inv_sigma;
     float *xa, *P1, *h1, *T, *P2, *h2, *PH, *xhat1, *xhat2, *part;
     int tn_chunks;
 };
@@ -592,20 +576,20 @@ static int dyn_forward(rl4rs_dyn* p, int N, const float* x, const float* a, int 
         const size_t lds = dyn_power_lds(d);
         int rc = raise_dyn_smem(reinterpret_cast<const void*>(&k_dyn_power), lds);
         if (rc) return rc;
-        hipLaunchKernelGGL(k_dyn_power, dim3(3, d.M), dim3(256), lds, st, d, p->params, p->state, p->stats, p->inv_sigma, train);
+        hipLaunchKernelGGL(k_dyn_power, dim3(3, d.M), dim3(256), lds, st, d, p->opt.params, p->state, p->stats, p->inv_sigma, train);
     }
     RL4RS_LAUNCH_CHECK();
     const bool keep = train && p->c.max_grad_rows > 0;
     for (int m = 0; m < d.M; ++m) {
-        const float* pm = p->params + (size_t)m * d.psize;
+        const float* pm = p->opt.params + (size_t)m * d.psize;
         int rc = launch_gemm_f32(p->xa, d.K1, pm + d.w1, d.H1, nullptr, p->P1 + (size_t)m * N * d.H1, d.H1, N, d.H1, d.K1, ACT_NONE, st);
         if (rc) return rc;
     }
-    hipLaunchKernelGGL(k_dyn_bn_fwd, dim3((d.H1 + 63) / 64, d.M), dim3(256), 0, st, d, 0, N, d.H1, p->params, p->state, p->stats,
+    hipLaunchKernelGGL(k_dyn_bn_fwd, dim3((d.H1 + 63) / 64, d.M), dim3(256), 0, st, d, 0, N, d.H1, p->opt.params, p->state, p->stats,
                        p->inv_sigma, p->P1, keep ? p->xhat1 : (float*)nullptr, p->h1, train, seed, step);
     RL4RS_LAUNCH_CHECK();
     for (int m = 0; m < d.M; ++m) {
-        const float* pm = p->params + (size_t)m * d.psize;
+        const float* pm = p->opt.params + (size_t)m * d.psize;
         float* P2 = p->P2 + (size_t)m * N * d.H2;
         const float* h1 = p->h1 + (size_t)m * N * d.H1;
         int rc;
@@ -619,11 +603,11 @@ static int dyn_forward(rl4rs_dyn* p, int N, const float* x, const float* a, int 
         }
         if (rc) return rc;
     }
-    hipLaunchKernelGGL(k_dyn_bn_fwd, dim3((d.H2 + 63) / 64, d.M), dim3(256), 0, st, d, 1, N, d.H2, p->params, p->state, p->stats,
+    hipLaunchKernelGGL(k_dyn_bn_fwd, dim3((d.H2 + 63) / 64, d.M), dim3(256), 0, st, d, 1, N, d.H2, p->opt.params, p->state, p->stats,
                        p->inv_sigma, p->P2, keep ? p->xhat2 : (float*)nullptr, p->h2, train, seed, step);
     RL4RS_LAUNCH_CHECK();
     for (int m = 0; m < d.M; ++m) {
-        const float* pm = p->params + (size_t)m * d.psize;
+        const float* pm = p->opt.params + (size_t)m * d.psize;
         int rc = launch_gemm_f32(p->h2 + (size_t)m * N * d.H2, d.H2, pm + d.wh, 2 * d.O, nullptr, p->PH + (size_t)m * N * 2 * d.O, 2 * d.O, N,
                                  2 * d.O, d.H2, ACT_NONE, st);
         if (rc) return rc;
@@ -671,12 +655,12 @@ int rl4rs_dyn_create(const rl4rs_dyn_cfg* cfg, const float* params_host, const f
         return RL4RS_EHIP;
     }
     rl4rs_dyn* p = new rl4rs_dyn();
-    p->c = *cfg; p->d = d; p->arena = nullptr; p->adam_t = 0;
-    p->n_params = d.psize * d.M; p->n_state = d.sc_rew + 2;
-    const size_t R = (size_t)cfg->max_rows, G = (size_t)cfg->max_grad_rows, M = d.M, np = (size_t)p->n_params;
+    p->c = *cfg; p->d = d; p->arena = nullptr; p->opt.t = 0;
+    p->opt.n = d.psize * d.M; p->n_state = d.sc_rew + 2;
+    const size_t R = (size_t)cfg->max_rows, G = (size_t)cfg->max_grad_rows, M = d.M, np = (size_t)p->opt.n;
     std::vector<std::pair<void**, size_t>> reqs;
     auto req = [&](float** slot, size_t n) { reqs.emplace_back(reinterpret_cast<void**>(slot), n * sizeof(float)); };
-    req(&p->params, np); req(&p->grad, np); req(&p->adam_m, np); req(&p->adam_v, np);
+    req(&p->opt.params, np); req(&p->opt.grad, np); req(&p->opt.m, np); req(&p->opt.v, np);
     req(&p->state, (size_t)p->n_state); req(&p->stats, (size_t)d.stsize * M); req(&p->inv_sigma, 3 * M);
     req(&p->xa, R * d.K1); req(&p->P1, M * R * d.H1); req(&p->h1, M * R * d.H1); req(&p->T, d.use_dense ? M * R * d.H2 : 1);
     req(&p->P2, M * R * d.H2); req(&p->h2, M * R * d.H2); req(&p->PH, M * R * 2 * d.O);
@@ -696,15 +680,15 @@ int rl4rs_dyn_create(const rl4rs_dyn_cfg* cfg, const float* params_host, const f
     size_t off = 0;
     for (auto& r : reqs) { *r.first = static_cast<char*>(p->arena) + off; off += (r.second + 255) / 256 * 256; }
     hipStream_t st = (hipStream_t)stream;
-    e = hipMemcpyAsync(p->params, params_host, np * 4, hipMemcpyHostToDevice, st);
+    e = hipMemcpyAsync(p->opt.params, params_host, np * 4, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(p->state, state_host, (size_t)p->n_state * 4, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemsetAsync(p->grad, 0, np * 4, st);
-    if (e == hipSuccess) e = hipMemsetAsync(p->adam_m, 0, np * 4, st);
-    if (e == hipSuccess) e = hipMemsetAsync(p->adam_v, 0, np * 4, st);
+    if (e == hipSuccess) e = hipMemsetAsync(p->opt.grad, 0, np * 4, st);
+    if (e == hipSuccess) e = hipMemsetAsync(p->opt.m, 0, np * 4, st);
+    if (e == hipSuccess) e = hipMemsetAsync(p->opt.v, 0, np * 4, st);
     if (e == hipSuccess) e = hipMemsetAsync(p->stats, 0, (size_t)d.stsize * M * 4, st);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_dyn_fill, dim3(1), dim3(64), 0, st, p->inv_sigma, 1.f, 3 * d.M);     // spectral_norm off: sigma = 1
-        for (int m = 0; m < d.M; ++m) hipLaunchKernelGGL(k_dyn_fill, dim3(1), dim3(64), 0, st, p->stats + (size_t)m * d.stsize, 1.f, 3);
+        hipLaunchKernelGGL(k_fill, dim3(1), dim3(64), 0, st, p->inv_sigma, 3 * d.M, 1.f);     // spectral_norm off: sigma = 1
+        for (int m = 0; m < d.M; ++m) hipLaunchKernelGGL(k_fill, dim3(1), dim3(64), 0, st, p->stats + (size_t)m * d.stsize, 3, 1.f);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -718,23 +702,13 @@ int rl4rs_dyn_create(const rl4rs_dyn_cfg* cfg, const float* params_host, const f
 }
 
 int rl4rs_dyn_params(rl4rs_dyn* p, float** params_dev, float** grad_dev, int64_t* count) {
-    RL4RS_REQUIRE(p, "dyn_params: null handle");
-    if (params_dev) *params_dev = p->params;
-    if (grad_dev) *grad_dev = p->grad;
-    if (count) *count = p->n_params;
-    return RL4RS_OK;
+    return opt_params(RL4RS_OPT(p), params_dev, grad_dev, count, "dyn_params");
 }
 int rl4rs_dyn_adam_state(rl4rs_dyn* p, float** m_dev, float** v_dev, int64_t* step) {
-    RL4RS_REQUIRE(p, "dyn_adam_state: null handle");
-    if (m_dev) *m_dev = p->adam_m;
-    if (v_dev) *v_dev = p->adam_v;
-    if (step) *step = p->adam_t;
-    return RL4RS_OK;
+    return opt_adam_state(RL4RS_OPT(p), m_dev, v_dev, step, "dyn_adam_state");
 }
 int rl4rs_dyn_set_adam_step(rl4rs_dyn* p, int64_t step) {
-    RL4RS_REQUIRE(p && step >= 0, "dyn_set_adam_step: bad argument");
-    p->adam_t = step;
-    return RL4RS_OK;
+    return opt_set_adam_step(RL4RS_OPT(p), step, "dyn_set_adam_step");
 }
 int rl4rs_dyn_state(rl4rs_dyn* p, float** state_dev, int64_t* count, float** stats_dev, int64_t* stats_count) {
     RL4RS_REQUIRE(p, "dyn_state: null handle");
@@ -754,7 +728,7 @@ int rl4rs_dyn_forward(rl4rs_dyn* p, int32_t N, const float* x_dev, const float* 
     hipStream_t st = (hipStream_t)stream;
     int rc = dyn_forward(p, N, x_dev, a_dev, train ? 1 : 0, seed, step, st);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_dyn_head, dyn_ew((int64_t)p->d.M * N * p->d.O), dim3(256), 0, st, p->d, N, p->params, p->inv_sigma, p->PH, out_dev);
+    hipLaunchKernelGGL(k_dyn_head, dyn_ew((int64_t)p->d.M * N * p->d.O), dim3(256), 0, st, p->d, N, p->opt.params, p->inv_sigma, p->PH, out_dev);
     RL4RS_LAUNCH_CHECK();
     return RL4RS_OK;
 }
@@ -771,13 +745,13 @@ int rl4rs_dyn_loss_grad(rl4rs_dyn* p, int32_t N, const float* x_dev, const float
     const size_t lds = dyn_nll_lds(d);
     rc = raise_dyn_smem(reinterpret_cast<const void*>(&k_dyn_nll), lds);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_dyn_nll, dim3(d.M), dim3(DYN_NLL_WAVES * 64), lds, st, d, N, p->params, p->state, p->inv_sigma, p->xa, next_x_dev,
-                       next_r_dev, mask_dev, p->PH, p->grad, loss_dev);
+    hipLaunchKernelGGL(k_dyn_nll, dim3(d.M), dim3(DYN_NLL_WAVES * 64), lds, st, d, N, p->opt.params, p->state, p->inv_sigma, p->xa, next_x_dev,
+                       next_r_dev, mask_dev, p->PH, p->opt.grad, loss_dev);
     RL4RS_LAUNCH_CHECK();
     // head: dWh = h2^T dPH; dh2 = dPH Wh^T (into the h2 buffer's place: P2 keeps z2, xhat2 keeps the normalised values)
     for (int m = 0; m < d.M; ++m) {
-        const float* pm = p->params + (size_t)m * d.psize;
-        float* gm = p->grad + (size_t)m * d.psize;
+        const float* pm = p->opt.params + (size_t)m * d.psize;
+        float* gm = p->opt.grad + (size_t)m * d.psize;
         const float* dPH = p->PH + (size_t)m * N * 2 * d.O;
         float* h2 = p->h2 + (size_t)m * N * d.H2;
         rc = dyn_tn(p, h2, d.H2, d.H2, dPH, 2 * d.O, 2 * d.O, N, gm + d.wh, st);
@@ -785,13 +759,13 @@ int rl4rs_dyn_loss_grad(rl4rs_dyn* p, int32_t N, const float* x_dev, const float
         rc = launch_gemm_nt(dPH, 2 * d.O, pm + d.wh, 2 * d.O, h2, d.H2, N, d.H2, 2 * d.O, st);
         if (rc) return rc;
     }
-    hipLaunchKernelGGL(k_dyn_bn_bwd, dim3((d.H2 + 63) / 64, d.M), dim3(256), 0, st, d, 1, N, d.H2, p->params, p->stats, p->inv_sigma, p->P2,
-                       p->xhat2, p->h2, p->grad, seed, step);
+    hipLaunchKernelGGL(k_dyn_bn_bwd, dim3((d.H2 + 63) / 64, d.M), dim3(256), 0, st, d, 1, N, d.H2, p->opt.params, p->stats, p->inv_sigma, p->P2,
+                       p->xhat2, p->h2, p->opt.grad, seed, step);
     RL4RS_LAUNCH_CHECK();
     // layer 2: dW2[:H1] = h1^T dP2, dW2[H1:] = xa^T dP2, dh1 = dP2 W2[:H1]^T (h1 is read by the TN product before it is overwritten)
     for (int m = 0; m < d.M; ++m) {
-        const float* pm = p->params + (size_t)m * d.psize;
-        float* gm = p->grad + (size_t)m * d.psize;
+        const float* pm = p->opt.params + (size_t)m * d.psize;
+        float* gm = p->opt.grad + (size_t)m * d.psize;
         const float* dP2 = p->h2 + (size_t)m * N * d.H2;
         float* h1 = p->h1 + (size_t)m * N * d.H1;
         rc = dyn_tn(p, h1, d.H1, d.H1, dP2, d.H2, d.H2, N, gm + d.w2, st);
@@ -803,16 +777,16 @@ int rl4rs_dyn_loss_grad(rl4rs_dyn* p, int32_t N, const float* x_dev, const float
         rc = launch_gemm_nt(dP2, d.H2, pm + d.w2, d.H2, h1, d.H1, N, d.H1, d.H2, st);
         if (rc) return rc;
     }
-    hipLaunchKernelGGL(k_dyn_bn_bwd, dim3((d.H1 + 63) / 64, d.M), dim3(256), 0, st, d, 0, N, d.H1, p->params, p->stats, p->inv_sigma, p->P1,
-                       p->xhat1, p->h1, p->grad, seed, step);
+    hipLaunchKernelGGL(k_dyn_bn_bwd, dim3((d.H1 + 63) / 64, d.M), dim3(256), 0, st, d, 0, N, d.H1, p->opt.params, p->stats, p->inv_sigma, p->P1,
+                       p->xhat1, p->h1, p->opt.grad, seed, step);
     RL4RS_LAUNCH_CHECK();
     for (int m = 0; m < d.M; ++m) {
-        float* gm = p->grad + (size_t)m * d.psize;
+        float* gm = p->opt.grad + (size_t)m * d.psize;
         rc = dyn_tn(p, p->xa, d.K1, d.K1, p->h1 + (size_t)m * N * d.H1, d.H1, d.H1, N, gm + d.w1, st);
         if (rc) return rc;
     }
     if (d.spectral) {
-        hipLaunchKernelGGL(k_dyn_sn_bwd, dim3(3, d.M), dim3(256), 0, st, d, p->params, p->state, p->inv_sigma, p->grad);
+        hipLaunchKernelGGL(k_dyn_sn_bwd, dim3(3, d.M), dim3(256), 0, st, d, p->opt.params, p->state, p->inv_sigma, p->opt.grad);
         RL4RS_LAUNCH_CHECK();
     }
     return RL4RS_OK;
@@ -820,12 +794,9 @@ int rl4rs_dyn_loss_grad(rl4rs_dyn* p, int32_t N, const float* x_dev, const float
 
 int rl4rs_dyn_adam_step(rl4rs_dyn* p, float lr, float beta1, float beta2, float eps, void* stream) {
     RL4RS_REQUIRE(p && lr >= 0.f, "dyn_adam_step: bad argument");
-    p->adam_t += 1;
-    const double t = (double)p->adam_t;
-    const float step_size = (float)((double)lr / (1.0 - std::pow((double)beta1, t)));
-    const float inv_sqrt_bc2 = (float)(1.0 / std::sqrt(1.0 - std::pow((double)beta2, t)));
-    hipLaunchKernelGGL(k_dyn_adam, dyn_ew(p->n_params), dim3(256), 0, (hipStream_t)stream, p->params, p->grad, p->adam_m, p->adam_v,
-                       p->n_params, step_size, inv_sqrt_bc2, beta1, beta2, eps);
+    const AdamTerms s = adam_advance(p->opt, ADAM_TORCH_DIV, lr, beta1, beta2, eps);
+    hipLaunchKernelGGL(k_adam_div, dyn_ew(p->opt.n), dim3(256), 0, (hipStream_t)stream, p->opt.params, p->opt.grad, p->opt.m, p->opt.v,
+                       p->opt.n, s.lr_t, s.eps_or_bc2, beta1, beta2, eps);
     RL4RS_LAUNCH_CHECK();
     return RL4RS_OK;
 }
@@ -840,7 +811,7 @@ int rl4rs_dyn_predict(rl4rs_dyn* p, int32_t N, const float* x_dev, const float* 
     int rc = dyn_forward(p, N, x_dev, a_dev, 0, seed, step, st);
     if (rc) return rc;
     // the bounded [mu | ls] of every member take the place of the raw product
-    hipLaunchKernelGGL(k_dyn_head, dyn_ew((int64_t)p->d.M * N * p->d.O), dim3(256), 0, st, p->d, N, p->params, p->inv_sigma, p->PH, p->PH);
+    hipLaunchKernelGGL(k_dyn_head, dyn_ew((int64_t)p->d.M * N * p->d.O), dim3(256), 0, st, p->d, N, p->opt.params, p->inv_sigma, p->PH, p->PH);
     hipLaunchKernelGGL(k_dyn_predict, dim3((N + 3) / 4), dim3(256), 0, st, p->d, N, p->state, p->xa, p->PH, indices_dev, noise_dev, seed, step,
                        deterministic ? 1 : 0, variance_type, penalise ? 1 : 0, lam, next_x_dev, reward_dev, variance_dev, indices_out_dev);
     RL4RS_LAUNCH_CHECK();

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "optim.hpp"
 
 namespace rl4rs {
 
@@ -319,13 +320,6 @@ __global__ void k_xk_colsum(const float* __restrict__ X, const float* __restrict
             if (n + u < hi) s += x[u];
     }
     part[(size_t)z * Nc + j] = s;
-}
-__global__ void k_xk_reduce(const float* __restrict__ part, int count, int nz, float* __restrict__ dst) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= count) return;
-    float s = 0.f;
-    for (int z = 0; z < nz; ++z) s += part[(size_t)z * count + i];
-    dst[i] = s;
 }
 // y += a (+ b)
 __global__ void k_xk_add(float* __restrict__ y, const float* __restrict__ a, const float* __restrict__ b, size_t n) {
@@ -726,18 +720,6 @@ __global__ __launch_bounds__(256) void k_xk_loss(const float* __restrict__ ce, c
     if (threadIdx.x == 0) { out[0] = s0[0] / (float)N; out[1] = s1[0]; }
 }
 
-// Adam, tf.train.AdamOptimizer form; skip != null and *skip != 0: nothing moves
-__global__ void k_xk_adam(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t count,
-                          float lr_t, float b1, float b2, float eps, const int32_t* __restrict__ skip) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= count || (skip && *skip)) return;
-    const float gi = g[i];
-    const float mi = b1 * m[i] + (1.f - b1) * gi;
-    const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-    m[i] = mi;
-    v[i] = vi;
-    p[i] -= lr_t * mi / (sqrtf(vi) + eps);
-}
 // critic: dv = 2 (v - target) (gradient of the SUM of the squared errors), err = (v - target)^2
 __global__ void k_xk_critic_err(const float* __restrict__ v, const float* __restrict__ target, float* __restrict__ dv, float* __restrict__ err,
                                 int N) {
@@ -797,8 +779,7 @@ struct rl4rs_exactk {
     rl4rs_exactk_cfg c;
     XkDims d;
     XkLayout L;
-    int64_t n_params, adam_t;
-    float *params, *grad, *adam_m, *adam_v;
+    OptBlock opt;
     uint8_t *loc, *special;
     void* arena;
     // encoder
@@ -815,8 +796,7 @@ struct rl4rs_exactk {
 
 struct rl4rs_exactk_critic {
     int OD, HC, max_rows;
-    int64_t n_params, adam_t;
-    float *params, *grad, *adam_m, *adam_v;
+    OptBlock opt;
     float *h[3], *dh[3], *v, *dv, *part, *part_b;
     std::vector<void*> owned;
 };
@@ -858,7 +838,7 @@ static int xk_colsum(rl4rs_exactk* p, const float* X, const float* Y, int ld, in
     const int chunk = std::max(64, (Ns + XK_COLSUM_CHUNKS - 1) / XK_COLSUM_CHUNKS);       // at most XK_COLSUM_CHUNKS partials
     const int nz = (Ns + chunk - 1) / chunk;
     hipLaunchKernelGGL(k_xk_colsum, dim3((Nc + 63) / 64, nz), dim3(64), 0, st, X, Y, ld, Nc, Ns, chunk, nz == 1 ? dst : p->part_b);
-    if (nz > 1) hipLaunchKernelGGL(k_xk_reduce, dim3((Nc + 255) / 256), dim3(256), 0, st, p->part_b, Nc, nz, dst);
+    if (nz > 1) hipLaunchKernelGGL(k_reduce_chunks, dim3((Nc + 255) / 256), dim3(256), 0, st, p->part_b, Nc, nz, dst);
     RL4RS_LAUNCH_CHECK();
     return RL4RS_OK;
 }
@@ -876,7 +856,7 @@ static int xk_forward(rl4rs_exactk* p, int N, const float* obs, int mode, int32_
                       uint32_t pass, float* logits_out, hipStream_t st) {
     const XkDims& d = p->d;
     const XkLayout& L = p->L;
-    const float* P = p->params;
+    const float* P = p->opt.params;
     const int A = d.A, D = d.D, H = d.H, F = d.F, M = N * A;
     const float rate = p->c.dropout_rate;
     const uint32_t site0 = pass * 32u;
@@ -944,8 +924,8 @@ static int xk_backward(rl4rs_exactk* p, int N, const float* obs, const int32_t* 
                        hipStream_t st) {
     const XkDims& d = p->d;
     const XkLayout& L = p->L;
-    const float* P = p->params;
-    float* Gd = p->grad;
+    const float* P = p->opt.params;
+    float* Gd = p->opt.grad;
     const int A = d.A, D = d.D, H = d.H, F = d.F, M = N * A, TN = XK_T * N;
     const float rate = p->c.dropout_rate;
     const uint32_t site0 = pass * 32u;
@@ -1094,12 +1074,12 @@ int rl4rs_exactk_create(const rl4rs_exactk_cfg* cfg, const float* params_host, c
     }
     rl4rs_exactk* p = new rl4rs_exactk();
     p->c = *cfg; p->d = d; p->L = xk_layout(d);
-    p->n_params = (int64_t)p->L.total; p->adam_t = 0; p->arena = nullptr;
+    p->opt.n = (int64_t)p->L.total; p->opt.t = 0; p->arena = nullptr;
     p->blk.resize(d.blocks);
     const size_t R = (size_t)cfg->max_rows, A = d.A, D = d.D, F = d.F, M = R * A, MD = M * D, ND = R * D, np = p->L.total, T = XK_T;
     std::vector<std::pair<void**, size_t>> reqs;                 // (pointer slot, bytes)
     auto req = [&](auto** slot, size_t n) { reqs.emplace_back(reinterpret_cast<void**>(slot), n * sizeof(**slot)); };
-    req(&p->params, np); req(&p->grad, np); req(&p->adam_m, np); req(&p->adam_v, np);
+    req(&p->opt.params, np); req(&p->opt.grad, np); req(&p->opt.m, np); req(&p->opt.v, np);
     req(&p->loc, 3 * A); req(&p->special, A);
     req(&p->EU, R * d.H); req(&p->dEU, R * d.H); req(&p->X0, MD); req(&p->AO, MD); req(&p->Z, MD);
     for (auto& b : p->blk) {
@@ -1129,12 +1109,12 @@ int rl4rs_exactk_create(const rl4rs_exactk_cfg* cfg, const float* params_host, c
     size_t off = 0;
     for (auto& r : reqs) { *r.first = static_cast<char*>(p->arena) + off; off += (r.second + 255) / 256 * 256; }
     hipStream_t st = (hipStream_t)stream;
-    e = hipMemcpyAsync(p->params, params_host, np * 4, hipMemcpyHostToDevice, st);
+    e = hipMemcpyAsync(p->opt.params, params_host, np * 4, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(p->loc, location_mask, 3 * A, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(p->special, is_special, A, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemsetAsync(p->grad, 0, np * 4, st);
-    if (e == hipSuccess) e = hipMemsetAsync(p->adam_m, 0, np * 4, st);
-    if (e == hipSuccess) e = hipMemsetAsync(p->adam_v, 0, np * 4, st);
+    if (e == hipSuccess) e = hipMemsetAsync(p->opt.grad, 0, np * 4, st);
+    if (e == hipSuccess) e = hipMemsetAsync(p->opt.m, 0, np * 4, st);
+    if (e == hipSuccess) e = hipMemsetAsync(p->opt.v, 0, np * 4, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) {
         set_error("exactk_create: initialisation failed: %s", hipGetErrorString(e));
@@ -1146,23 +1126,13 @@ int rl4rs_exactk_create(const rl4rs_exactk_cfg* cfg, const float* params_host, c
 }
 
 int rl4rs_exactk_params(rl4rs_exactk* p, float** params_dev, float** grad_dev, int64_t* count) {
-    RL4RS_REQUIRE(p, "exactk_params: null handle");
-    if (params_dev) *params_dev = p->params;
-    if (grad_dev) *grad_dev = p->grad;
-    if (count) *count = p->n_params;
-    return RL4RS_OK;
+    return opt_params(RL4RS_OPT(p), params_dev, grad_dev, count, "exactk_params");
 }
 int rl4rs_exactk_adam_state(rl4rs_exactk* p, float** m_dev, float** v_dev, int64_t* step) {
-    RL4RS_REQUIRE(p, "exactk_adam_state: null handle");
-    if (m_dev) *m_dev = p->adam_m;
-    if (v_dev) *v_dev = p->adam_v;
-    if (step) *step = p->adam_t;
-    return RL4RS_OK;
+    return opt_adam_state(RL4RS_OPT(p), m_dev, v_dev, step, "exactk_adam_state");
 }
 int rl4rs_exactk_set_adam_step(rl4rs_exactk* p, int64_t step) {
-    RL4RS_REQUIRE(p && step >= 0, "exactk_set_adam_step: bad argument");
-    p->adam_t = step;
-    return RL4RS_OK;
+    return opt_set_adam_step(RL4RS_OPT(p), step, "exactk_set_adam_step");
 }
 
 int rl4rs_exactk_decode(rl4rs_exactk* p, int32_t N, const float* obs_dev, int32_t greedy, uint32_t seed, uint32_t step, int32_t* path_dev,
@@ -1181,18 +1151,14 @@ int rl4rs_exactk_loss_grad(rl4rs_exactk* p, int32_t N, const float* obs_dev, con
     int rc = xk_forward(p, N, obs_dev, 2, p->path_tmp, weights_dev, seed, step, 0u, logits_out_dev, st);
     if (rc) return rc;
     hipLaunchKernelGGL(k_xk_loss, dim3(1), dim3(256), 0, st, p->ce, p->invalid, weights_dev, N, loss_dev);
-    RL4RS_HIP_TRY(hipMemsetAsync(p->grad, 0, (size_t)p->n_params * 4, st));
+    RL4RS_HIP_TRY(hipMemsetAsync(p->opt.grad, 0, (size_t)p->opt.n * 4, st));
     return xk_backward(p, N, obs_dev, p->path_tmp, seed, step, 0u, st);
 }
 
 int rl4rs_exactk_adam_step(rl4rs_exactk* p, float lr, float beta1, float beta2, float eps, const int32_t* skip_dev, void* stream) {
     RL4RS_REQUIRE(p && lr >= 0.f, "exactk_adam_step: bad argument");
     // the step counter advances on the host whether or not the device flag skips the update: a skipped update keeps its slot
-    p->adam_t += 1;
-    const double t = (double)p->adam_t;
-    const float lr_t = (float)((double)lr * std::sqrt(1.0 - std::pow((double)beta2, t)) / (1.0 - std::pow((double)beta1, t)));
-    hipLaunchKernelGGL(k_xk_adam, ew((size_t)p->n_params), dim3(256), 0, (hipStream_t)stream, p->params, p->grad, p->adam_m, p->adam_v,
-                       p->n_params, lr_t, beta1, beta2, eps, skip_dev);
+    adam_step(p->opt, p->opt.grad, ADAM_TF, lr, beta1, beta2, eps, nullptr, 0.f, skip_dev, (hipStream_t)stream);
     RL4RS_LAUNCH_CHECK();
     return RL4RS_OK;
 }
@@ -1232,25 +1198,25 @@ int rl4rs_exactk_critic_create(int32_t obs_dim, int32_t hidden, int32_t max_rows
         return RL4RS_EHIP;
     }
     rl4rs_exactk_critic* c = new rl4rs_exactk_critic();
-    c->OD = obs_dim; c->HC = hidden; c->max_rows = max_rows; c->adam_t = 0;
-    c->n_params = rl4rs_exactk_critic_param_count(obs_dim, hidden);
+    c->OD = obs_dim; c->HC = hidden; c->max_rows = max_rows; c->opt.t = 0;
+    c->opt.n = rl4rs_exactk_critic_param_count(obs_dim, hidden);
     int rc = RL4RS_OK;
     auto alloc = [&](float** dst, size_t n) {
         if (rc) return;
         rc = dev_alloc(dst, n);
         if (rc == RL4RS_OK) c->owned.push_back(*dst);
     };
-    const size_t np = (size_t)c->n_params, R = (size_t)max_rows, HC = (size_t)hidden;
-    alloc(&c->params, np); alloc(&c->grad, np); alloc(&c->adam_m, np); alloc(&c->adam_v, np);
+    const size_t np = (size_t)c->opt.n, R = (size_t)max_rows, HC = (size_t)hidden;
+    alloc(&c->opt.params, np); alloc(&c->opt.grad, np); alloc(&c->opt.m, np); alloc(&c->opt.v, np);
     for (int i = 0; i < 3; ++i) { alloc(&c->h[i], R * HC); alloc(&c->dh[i], R * HC); }
     alloc(&c->v, R); alloc(&c->dv, R);
     alloc(&c->part, 64 * std::max((size_t)obs_dim * HC, HC * HC)); alloc(&c->part_b, 64 * HC);
     if (rc) { rl4rs_exactk_critic_destroy(c); return rc; }
     hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipMemcpyAsync(c->params, params_host, np * 4, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemsetAsync(c->grad, 0, np * 4, st);
-    if (e == hipSuccess) e = hipMemsetAsync(c->adam_m, 0, np * 4, st);
-    if (e == hipSuccess) e = hipMemsetAsync(c->adam_v, 0, np * 4, st);
+    hipError_t e = hipMemcpyAsync(c->opt.params, params_host, np * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemsetAsync(c->opt.grad, 0, np * 4, st);
+    if (e == hipSuccess) e = hipMemsetAsync(c->opt.m, 0, np * 4, st);
+    if (e == hipSuccess) e = hipMemsetAsync(c->opt.v, 0, np * 4, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) {
         set_error("exactk_critic_create: initialisation failed: %s", hipGetErrorString(e));
@@ -1262,28 +1228,18 @@ int rl4rs_exactk_critic_create(int32_t obs_dim, int32_t hidden, int32_t max_rows
 }
 
 int rl4rs_exactk_critic_params(rl4rs_exactk_critic* c, float** params_dev, float** grad_dev, int64_t* count) {
-    RL4RS_REQUIRE(c, "exactk_critic_params: null handle");
-    if (params_dev) *params_dev = c->params;
-    if (grad_dev) *grad_dev = c->grad;
-    if (count) *count = c->n_params;
-    return RL4RS_OK;
+    return opt_params(RL4RS_OPT(c), params_dev, grad_dev, count, "exactk_critic_params");
 }
 int rl4rs_exactk_critic_adam_state(rl4rs_exactk_critic* c, float** m_dev, float** v_dev, int64_t* step) {
-    RL4RS_REQUIRE(c, "exactk_critic_adam_state: null handle");
-    if (m_dev) *m_dev = c->adam_m;
-    if (v_dev) *v_dev = c->adam_v;
-    if (step) *step = c->adam_t;
-    return RL4RS_OK;
+    return opt_adam_state(RL4RS_OPT(c), m_dev, v_dev, step, "exactk_critic_adam_state");
 }
 int rl4rs_exactk_critic_set_adam_step(rl4rs_exactk_critic* c, int64_t step) {
-    RL4RS_REQUIRE(c && step >= 0, "exactk_critic_set_adam_step: bad argument");
-    c->adam_t = step;
-    return RL4RS_OK;
+    return opt_set_adam_step(RL4RS_OPT(c), step, "exactk_critic_set_adam_step");
 }
 
 static int xkc_forward(rl4rs_exactk_critic* c, int N, const float* obs, float* out, hipStream_t st) {
     float *W[4], *b[4];
-    xkc_ptrs(c, c->params, W, b);
+    xkc_ptrs(c, c->opt.params, W, b);
     const int HC = c->HC;
     int rc;
     if ((rc = launch_gemm_f32(obs, c->OD, W[0], HC, b[0], c->h[0], HC, N, HC, c->OD, ACT_RELU, st))) return rc;
@@ -1308,8 +1264,8 @@ int rl4rs_exactk_critic_loss_grad(rl4rs_exactk_critic* c, int32_t N, const float
     if (value_out_dev) RL4RS_HIP_TRY(hipMemcpyAsync(value_out_dev, c->v, (size_t)N * 4, hipMemcpyDeviceToDevice, st));
     hipLaunchKernelGGL(k_xk_critic_err, ew((size_t)N), dim3(256), 0, st, c->v, target_dev, c->dv, err_out_dev, N);
     float *W[4], *b[4], *gW[4], *gb[4];
-    xkc_ptrs(c, c->params, W, b);
-    xkc_ptrs(c, c->grad, gW, gb);
+    xkc_ptrs(c, c->opt.params, W, b);
+    xkc_ptrs(c, c->opt.grad, gW, gb);
     const int HC = c->HC;
     const int chunk = std::max(256, ((N + 63) / 64 + 15) / 16 * 16);
     if ((rc = launch_gemm_tn(c->h[2], HC, HC, c->dv, 1, 1, N, chunk, c->part, c->part_b, gW[3], gb[3], st))) return rc;
@@ -1323,11 +1279,7 @@ int rl4rs_exactk_critic_loss_grad(rl4rs_exactk_critic* c, int32_t N, const float
 
 int rl4rs_exactk_critic_adam_step(rl4rs_exactk_critic* c, float lr, float beta1, float beta2, float eps, void* stream) {
     RL4RS_REQUIRE(c && lr >= 0.f, "exactk_critic_adam_step: bad argument");
-    c->adam_t += 1;
-    const double t = (double)c->adam_t;
-    const float lr_t = (float)((double)lr * std::sqrt(1.0 - std::pow((double)beta2, t)) / (1.0 - std::pow((double)beta1, t)));
-    hipLaunchKernelGGL(k_xk_adam, ew((size_t)c->n_params), dim3(256), 0, (hipStream_t)stream, c->params, c->grad, c->adam_m, c->adam_v,
-                       c->n_params, lr_t, beta1, beta2, eps, (const int32_t*)nullptr);
+    adam_step(c->opt, c->opt.grad, ADAM_TF, lr, beta1, beta2, eps, nullptr, 0.f, nullptr, (hipStream_t)stream);
     RL4RS_LAUNCH_CHECK();
     return RL4RS_OK;
 }

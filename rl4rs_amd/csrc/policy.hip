@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "optim.hpp"
 #include "gather_kernels.hpp"
 #include "mfma4.hpp"
 
@@ -619,16 +620,7 @@ __global__ void k_colsum(const float* __restrict__ X, int ld, int Nc, int Ns, in
     part[(size_t)z * Nc + j] = s;
 }
 
-// dst[i] = sum_z part[z][i] in chunk order (fixed order => reproducible)
-__global__ void k_reduce_chunks(const float* __restrict__ part, int count, int nz, float* __restrict__ dst) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= count) return;
-    float s = 0.f;
-    for (int z = 0; z < nz; ++z) s += part[(size_t)z * count + i];
-    dst[i] = s;
-}
-
-// The same sum for MANY chunks (the 128 x 128 form splits the sample axis into up to 64): 64 outputs per workgroup, its four waves
+// k_reduce_chunks' sum (optim.hpp) for MANY chunks (the 128 x 128 form splits the sample axis into up to 64): 64 outputs per workgroup, its four waves
 // take the chunks z = w, w + 4, ... (eight independent loads in flight each) and meet in LDS; dst = ((w0 + w1) + w2) + w3 with
 // every w a sum in ascending z: a fixed order, reproducible.
 __global__ __launch_bounds__(256) void k_reduce_chunks4(const float* __restrict__ part, int count, int nz, float* __restrict__ dst) {
@@ -707,38 +699,6 @@ __global__ __launch_bounds__(256) void k_reduce_terms(const float4* __restrict__
 __global__ void k_axpy4(const float* __restrict__ x, float* __restrict__ acc) {
     if (threadIdx.x < 4) acc[threadIdx.x] += x[threadIdx.x];
 }
-
-// sum of squares of a flat buffer -> out[0] (single block, fixed order)
-__global__ __launch_bounds__(256) void k_sumsq(const float* __restrict__ g, int count, float* __restrict__ out) {
-    __shared__ float sm[256];
-    float s = 0.f;
-    for (int i = threadIdx.x; i < count; i += 256) s += g[i] * g[i];
-    sm[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sm[threadIdx.x] += sm[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[0] = sm[0];
-}
-
-// Adam (tf.train.AdamOptimizer semantics: lr_t = lr * sqrt(1-b2^t)/(1-b1^t)); optional global-norm clipping
-__global__ void k_adam(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                       int count, float lr_t, float b1, float b2, float eps, const float* __restrict__ sumsq, float clip) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= count) return;
-    float gi = g[i];
-    if (clip > 0.f) {
-        const float norm = sqrtf(sumsq[0]);
-        if (norm > clip) gi *= clip / norm;      // tf.clip_by_global_norm
-    }
-    const float mi = b1 * m[i] + (1.f - b1) * gi;
-    const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-    m[i] = mi;
-    v[i] = vi;
-    p[i] -= lr_t * mi / (sqrtf(vi) + eps);
-}
-
 
 #include "ppo_pass.hpp"
 
@@ -928,13 +888,12 @@ constexpr size_t POLICY_LDS_MAX = (size_t)160 * 1024;
 
 struct rl4rs_policy {
     PolDims d;
-    int max_rows, n_params, nz, chunk;
-    float *params, *adam_m, *adam_v;
+    int max_rows, nz, chunk;
+    OptBlock opt;              // grad stays null: the gradient is the caller's buffer
     float *H, *dOut, *dHpre, *part, *sumsq, *w2t;
     float4* terms;
     unsigned* bar;
     unsigned* dead_host;       // pinned host mirror of bar[1] (a persistent pass gave up): read before every pass launch, no sync
-    int64_t adam_t;
     bool train_attr, pass_launched, tile_attr[3];
     int pass_resident_wgs;     // workgroups of k_ppo_pass the device can hold at once (-1 = not queried yet)
     // rl4rs_policy_set_option (include/rl4rs_hip.h RL4RS_POLICY_OPT_*): kernel-path selection for A/B runs and tests
@@ -973,10 +932,10 @@ int rl4rs_policy_create(int32_t obs_dim, int32_t hidden, int32_t action_size, in
     rl4rs_policy* p = new rl4rs_policy();
     p->d.OD = obs_dim; p->d.HID = hidden; p->d.A = action_size; p->d.AE = action_size + 1; p->d.W = (action_size + 31) / 32;
     p->max_rows = max_rows;
-    p->n_params = rl4rs_policy_param_count(obs_dim, hidden, action_size);
+    p->opt.n = rl4rs_policy_param_count(obs_dim, hidden, action_size);
     p->chunk = 512;
     p->nz = (max_rows + p->chunk - 1) / p->chunk;
-    p->adam_t = 0;
+    p->opt.t = 0; p->opt.grad = nullptr;
     p->train_attr = false;
     p->pass_launched = false;
     p->pass_resident_wgs = -1;
@@ -993,9 +952,9 @@ int rl4rs_policy_create(int32_t obs_dim, int32_t hidden, int32_t action_size, in
         if (r == RL4RS_OK) p->owned.push_back(*dst);
         return r;
     };
-    if ((rc = alloc(&p->params, p->n_params))) return rc;
-    if ((rc = alloc(&p->adam_m, p->n_params))) return rc;
-    if ((rc = alloc(&p->adam_v, p->n_params))) return rc;
+    if ((rc = alloc(&p->opt.params, p->opt.n))) return rc;
+    if ((rc = alloc(&p->opt.m, p->opt.n))) return rc;
+    if ((rc = alloc(&p->opt.v, p->opt.n))) return rc;
     if ((rc = alloc(&p->H, (size_t)max_rows * hidden))) return rc;
     if ((rc = alloc(&p->dOut, (size_t)max_rows * p->d.AE))) return rc;
     if ((rc = alloc(&p->dHpre, (size_t)max_rows * hidden))) return rc;
@@ -1009,9 +968,9 @@ int rl4rs_policy_create(int32_t obs_dim, int32_t hidden, int32_t action_size, in
     if ((rc = alloc(&t4, (size_t)max_rows * 4))) return rc;
     p->terms = reinterpret_cast<float4*>(t4);
     hipStream_t st = (hipStream_t)stream;
-    RL4RS_HIP_TRY(hipMemcpyAsync(p->params, params_host, (size_t)p->n_params * 4, hipMemcpyHostToDevice, st));
-    RL4RS_HIP_TRY(hipMemsetAsync(p->adam_m, 0, (size_t)p->n_params * 4, st));
-    RL4RS_HIP_TRY(hipMemsetAsync(p->adam_v, 0, (size_t)p->n_params * 4, st));
+    RL4RS_HIP_TRY(hipMemcpyAsync(p->opt.params, params_host, (size_t)p->opt.n * 4, hipMemcpyHostToDevice, st));
+    RL4RS_HIP_TRY(hipMemsetAsync(p->opt.m, 0, (size_t)p->opt.n * 4, st));
+    RL4RS_HIP_TRY(hipMemsetAsync(p->opt.v, 0, (size_t)p->opt.n * 4, st));
     RL4RS_HIP_TRY(hipMemsetAsync(p->bar, 0, 320 * 4, st));
     RL4RS_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&p->dead_host), 64, hipHostMallocDefault));
     *p->dead_host = 0u;
@@ -1030,23 +989,16 @@ int rl4rs_policy_destroy(rl4rs_policy* p) {
 
 int rl4rs_policy_params(rl4rs_policy* p, float** params_dev, int32_t* count) {
     RL4RS_REQUIRE(p && params_dev, "policy_params: null argument");
-    *params_dev = p->params;
-    if (count) *count = p->n_params;
-    return RL4RS_OK;
+    if (count) *count = (int32_t)p->opt.n;
+    return opt_params(&p->opt, params_dev, nullptr, nullptr, "policy_params");
 }
 
 int rl4rs_policy_adam_state(rl4rs_policy* p, float** m_dev, float** v_dev, int64_t* step) {
-    RL4RS_REQUIRE(p, "policy_adam_state: null handle");
-    if (m_dev) *m_dev = p->adam_m;
-    if (v_dev) *v_dev = p->adam_v;
-    if (step) *step = p->adam_t;
-    return RL4RS_OK;
+    return opt_adam_state(RL4RS_OPT(p), m_dev, v_dev, step, "policy_adam_state");
 }
 
 int rl4rs_policy_set_adam_step(rl4rs_policy* p, int64_t step) {
-    RL4RS_REQUIRE(p && step >= 0, "policy_set_adam_step: bad argument");
-    p->adam_t = step;
-    return RL4RS_OK;
+    return opt_set_adam_step(RL4RS_OPT(p), step, "policy_set_adam_step");
 }
 
 static size_t fwd_smem(const PolDims& d, int extra) { return (size_t)4 * (d.OD + d.HID + d.AE + extra) * 4; }
@@ -1102,12 +1054,12 @@ int rl4rs_policy_act(rl4rs_policy* p, int32_t N, const float* obs, const uint32_
     if (tile_fits(p, 0)) {
         TileArgs a;
         memset(&a, 0, sizeof(a));
-        a.d = p->d; a.N = N; a.prm = p->params; a.obs = obs; a.mask = mask_bits; a.seed = seed; a.step = step;
+        a.d = p->d; a.N = N; a.prm = p->opt.params; a.obs = obs; a.mask = mask_bits; a.seed = seed; a.step = step;
         a.actions = actions; a.logp = logp; a.value = value; a.entropy = entropy; a.logits_out = logits;
         return launch_policy_tile<0>(p, a, (hipStream_t)stream);
     }
     hipLaunchKernelGGL(k_policy_forward<true>, dim3((N + 3) / 4), dim3(256), fwd_smem(p->d, 0), (hipStream_t)stream, p->d,
-                       p->params, N, obs, mask_bits, seed, step, actions, logp, value, entropy, logits);
+                       p->opt.params, N, obs, mask_bits, seed, step, actions, logp, value, entropy, logits);
     RL4RS_LAUNCH_CHECK();
     return RL4RS_OK;
 }
@@ -1119,12 +1071,12 @@ int rl4rs_policy_evaluate(rl4rs_policy* p, int32_t N, const float* obs, const ui
     if (tile_fits(p, 1)) {
         TileArgs a;
         memset(&a, 0, sizeof(a));
-        a.d = p->d; a.N = N; a.prm = p->params; a.obs = obs; a.mask = mask_bits;
+        a.d = p->d; a.N = N; a.prm = p->opt.params; a.obs = obs; a.mask = mask_bits;
         a.actions = const_cast<int32_t*>(actions); a.logp = logp; a.value = value; a.entropy = entropy; a.logits_out = logits;
         return launch_policy_tile<1>(p, a, (hipStream_t)stream);
     }
     hipLaunchKernelGGL(k_policy_forward<false>, dim3((N + 3) / 4), dim3(256), fwd_smem(p->d, 0), (hipStream_t)stream, p->d,
-                       p->params, N, obs, mask_bits, 0u, 0u, const_cast<int32_t*>(actions), logp, value, entropy, logits);
+                       p->opt.params, N, obs, mask_bits, 0u, 0u, const_cast<int32_t*>(actions), logp, value, entropy, logits);
     RL4RS_LAUNCH_CHECK();
     return RL4RS_OK;
 }
@@ -1147,11 +1099,11 @@ int rl4rs_policy_loss_grad(rl4rs_policy* p, int32_t algo, int32_t N, const float
     const int stage_w2 = (fwd_smem(d, d.AE) + w2_bytes <= (size_t)150 * 1024) ? 1 : 0;
     const bool tiled = tile_fits(p, 2);
     if (tiled) {
-        hipLaunchKernelGGL(k_w2_transpose, dim3((d.HID * d.AE + 255) / 256), dim3(256), 0, st, p->params + (size_t)d.OD * d.HID + d.HID,
+        hipLaunchKernelGGL(k_w2_transpose, dim3((d.HID * d.AE + 255) / 256), dim3(256), 0, st, p->opt.params + (size_t)d.OD * d.HID + d.HID,
                            d.HID, d.AE, p->w2t);
         TileArgs a;
         memset(&a, 0, sizeof(a));
-        a.d = d; a.N = N; a.prm = p->params; a.w2t = p->w2t; a.obs = obs; a.mask = mask_bits; a.L = L;
+        a.d = d; a.N = N; a.prm = p->opt.params; a.w2t = p->w2t; a.obs = obs; a.mask = mask_bits; a.L = L;
         a.H = p->H; a.dOut = p->dOut; a.dHpre = p->dHpre; a.terms = p->terms;
         int rc = launch_policy_tile<2>(p, a, st);
         if (rc) return rc;
@@ -1162,7 +1114,7 @@ int rl4rs_policy_loss_grad(rl4rs_policy* p, int32_t algo, int32_t N, const float
         p->train_attr = true;
     }
     if (!tiled)
-        hipLaunchKernelGGL(k_policy_train, dim3((N + 3) / 4), dim3(256), fwd_smem(d, d.AE) + (stage_w2 ? w2_bytes : 0), st, d, p->params,
+        hipLaunchKernelGGL(k_policy_train, dim3((N + 3) / 4), dim3(256), fwd_smem(d, d.AE) + (stage_w2 ? w2_bytes : 0), st, d, p->opt.params,
                            N, obs, mask_bits, L, p->H, p->dOut, p->dHpre, p->terms, stage_w2);
     RL4RS_LAUNCH_CHECK();
     // sample chunks of the gradient reductions: 512 samples each up to 64 chunks, then longer chunks - a SeqSlate train batch (131 072
@@ -1199,13 +1151,7 @@ int rl4rs_policy_loss_grad(rl4rs_policy* p, int32_t algo, int32_t N, const float
 int rl4rs_policy_adam_step(rl4rs_policy* p, const float* grad_dev, float lr, float beta1, float beta2, float eps,
                            float grad_clip, void* stream) {
     RL4RS_REQUIRE(p && grad_dev, "policy_adam_step: null argument");
-    hipStream_t st = (hipStream_t)stream;
-    p->adam_t += 1;
-    const double t = (double)p->adam_t;
-    const float lr_t = (float)(lr * sqrt(1.0 - pow((double)beta2, t)) / (1.0 - pow((double)beta1, t)));
-    if (grad_clip > 0.f) hipLaunchKernelGGL(k_sumsq, dim3(1), dim3(256), 0, st, grad_dev, p->n_params, p->sumsq);
-    hipLaunchKernelGGL(k_adam, dim3((p->n_params + 255) / 256), dim3(256), 0, st, p->params, grad_dev, p->adam_m, p->adam_v,
-                       p->n_params, lr_t, beta1, beta2, eps, p->sumsq, grad_clip);
+    adam_step(p->opt, grad_dev, ADAM_TF, lr, beta1, beta2, eps, p->sumsq, grad_clip, nullptr, (hipStream_t)stream);
     RL4RS_LAUNCH_CHECK();
     return RL4RS_OK;
 }
@@ -1465,13 +1411,13 @@ int launch_ppo_pass(rl4rs_policy* p, const PpoCall& c, int mb_begin, int mb_end,
     memset(&a, 0, sizeof(a));
     a.d = d; a.N = c.N; a.MB = c.minibatch;
     a.rows = pass_rows_per_wg(p);
-    a.prm = p->params; a.am = p->adam_m; a.av = p->adam_v; a.w2t = p->w2t;
+    a.prm = p->opt.params; a.am = p->opt.m; a.av = p->opt.v; a.w2t = p->w2t;
     a.obs = c.obs; a.mask = c.mask_bits;
     a.L.algo = 1; a.L.vf_coeff = c.vf_coeff; a.L.ent_coeff = c.ent_coeff; a.L.clip = c.clip; a.L.vf_clip = c.vf_clip; a.L.kl_coeff = c.kl_coeff;
     a.L.scale = 1.0f / (float)c.minibatch;
     a.L.actions = c.actions; a.L.adv = c.adv; a.L.ret = c.ret; a.L.old_logp = c.old_logp; a.L.old_value = c.old_value; a.L.old_logits = c.old_logits;
     a.H = p->H; a.dOut = p->dOut; a.dHpre = p->dHpre; a.terms = p->terms; a.grad = grad_dev; a.bar = p->bar; a.dead_host = p->dead_host;
-    a.lr = c.lr; a.b1 = c.beta1; a.b2 = c.beta2; a.eps = c.eps; a.t0 = p->adam_t;
+    a.lr = c.lr; a.b1 = c.beta1; a.b2 = c.beta2; a.eps = c.eps; a.t0 = p->opt.t;
     a.mb_begin = mb_begin; a.mb_end = mb_end; a.apply = apply;
     a.trace = nullptr;
 #ifdef RL4RS_PASS_TRACE
@@ -1540,7 +1486,7 @@ int rl4rs_policy_ppo_epoch(rl4rs_policy* p, int32_t N, int32_t minibatch, const 
                      vf_coeff, ent_coeff, clip, vf_clip, kl_coeff, lr, beta1, beta2, eps};
         int rc = launch_ppo_pass(p, c, 0, nmb, 1, grad_dev, st);
         if (rc) return rc;
-        p->adam_t += nmb;
+        p->opt.t += nmb;
         if (stats_dev) {
             hipLaunchKernelGGL(k_reduce_terms, dim3(1), dim3(256), 0, st, p->terms + (size_t)(nmb - 1) * minibatch, minibatch, stats_dev);
             hipLaunchKernelGGL(k_reduce_terms, dim3(1), dim3(256), 0, st, p->terms, nmb * minibatch, stats_dev + 4);

@@ -245,13 +245,12 @@ struct rl4rs_qnet {
     rl4rs_qnet_cfg c;
     bool custom;
     int W, F2, FH;              // mask words; fc2 input width; head input width
-    int64_t n_params, off[QP_COUNT], size[QP_COUNT];
+    int64_t off[QP_COUNT], size[QP_COUNT];
     TrainCtx cx;
-    float *params, *grad, *adam_m, *adam_v;
+    OptBlock opt;
     float *cat, *enc, *d_enc, *d_cat;   // custom: cat = [h1 | tail emb], enc = masked fc2 output; plain: cat = h1, enc = h2
     uint32_t *bits, *loc_bits, *special_bits;
     int* err;
-    int64_t adam_t;
     size_t part_floats;         // floats behind cx.part (checked by rl4rs_qnet_backward before the chunked reductions write there)
     std::vector<void*> owned;
 };
@@ -290,12 +289,12 @@ int rl4rs_qnet_create(const rl4rs_qnet_cfg* c, const float* params_host, const u
     p->W = (int)((A + 31) / 32);
     p->F2 = (int)(custom ? H1 + M * ES : H1);
     p->FH = (int)(custom ? A : c->hidden2);
-    p->adam_t = 0;
+    p->opt.t = 0;
     const int64_t n2 = custom ? A : c->hidden2;
     const int64_t sizes[QP_COUNT] = {D * H1, H1, custom ? A * ES : 0, (int64_t)p->F2 * n2, n2, (int64_t)p->FH * A, A};
     int64_t o = 0;
     for (int i = 0; i < QP_COUNT; ++i) { p->off[i] = o; p->size[i] = sizes[i]; o += sizes[i]; }
-    p->n_params = o;
+    p->opt.n = o;
     int rc;
     auto al = [&](float** dst, size_t n) {
         int r = dev_alloc(dst, n);
@@ -305,12 +304,12 @@ int rl4rs_qnet_create(const rl4rs_qnet_cfg* c, const float* params_host, const u
 #define QN_FAIL(expr) do { if ((rc = (expr)) != RL4RS_OK) { rl4rs_qnet_destroy(p); return rc; } } while (0)
 #define QN_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { set_error("%s failed: %s", #expr, hipGetErrorString(e_)); \
         rl4rs_qnet_destroy(p); return RL4RS_EHIP; } } while (0)
-    QN_FAIL(al(&p->params, p->n_params)); QN_FAIL(al(&p->grad, p->n_params));
-    QN_FAIL(al(&p->adam_m, p->n_params)); QN_FAIL(al(&p->adam_v, p->n_params));
-    QN_HIP(hipMemcpyAsync(p->params, params_host, (size_t)p->n_params * 4, hipMemcpyHostToDevice, st));
-    QN_HIP(hipMemsetAsync(p->grad, 0, (size_t)p->n_params * 4, st));
-    QN_HIP(hipMemsetAsync(p->adam_m, 0, (size_t)p->n_params * 4, st));
-    QN_HIP(hipMemsetAsync(p->adam_v, 0, (size_t)p->n_params * 4, st));
+    QN_FAIL(al(&p->opt.params, p->opt.n)); QN_FAIL(al(&p->opt.grad, p->opt.n));
+    QN_FAIL(al(&p->opt.m, p->opt.n)); QN_FAIL(al(&p->opt.v, p->opt.n));
+    QN_HIP(hipMemcpyAsync(p->opt.params, params_host, (size_t)p->opt.n * 4, hipMemcpyHostToDevice, st));
+    QN_HIP(hipMemsetAsync(p->opt.grad, 0, (size_t)p->opt.n * 4, st));
+    QN_HIP(hipMemsetAsync(p->opt.m, 0, (size_t)p->opt.n * 4, st));
+    QN_HIP(hipMemsetAsync(p->opt.v, 0, (size_t)p->opt.n * 4, st));
     const size_t B = c->max_rows;
     QN_FAIL(al(&p->cat, B * p->F2)); QN_FAIL(al(&p->enc, B * p->FH)); QN_FAIL(al(&p->d_enc, B * p->FH)); QN_FAIL(al(&p->d_cat, B * p->F2));
     { float* t; QN_FAIL(al(&t, 1)); p->err = reinterpret_cast<int*>(t); }
@@ -345,31 +344,19 @@ int rl4rs_qnet_create(const rl4rs_qnet_cfg* c, const float* params_host, const u
 }
 
 int rl4rs_qnet_params(rl4rs_qnet* p, float** params_dev, float** grad_dev, int64_t* count) {
-    RL4RS_REQUIRE(p, "qnet_params: null handle");
-    if (params_dev) *params_dev = p->params;
-    if (grad_dev) *grad_dev = p->grad;
-    if (count) *count = p->n_params;
-    return RL4RS_OK;
+    return opt_params(RL4RS_OPT(p), params_dev, grad_dev, count, "qnet_params");
 }
 
 // Adam moments (device pointers, n_params floats each) and the step count: checkpointing (offline_rl save_model / load_model)
 int rl4rs_qnet_adam_state(rl4rs_qnet* p, float** m_dev, float** v_dev, int64_t* step) {
-    RL4RS_REQUIRE(p, "qnet_adam_state: null handle");
-    if (m_dev) *m_dev = p->adam_m;
-    if (v_dev) *v_dev = p->adam_v;
-    if (step) *step = p->adam_t;
-    return RL4RS_OK;
+    return opt_adam_state(RL4RS_OPT(p), m_dev, v_dev, step, "qnet_adam_state");
 }
 int rl4rs_qnet_set_adam_step(rl4rs_qnet* p, int64_t step) {
-    RL4RS_REQUIRE(p && step >= 0, "qnet_set_adam_step: bad argument");
-    p->adam_t = step;
-    return RL4RS_OK;
+    return opt_set_adam_step(RL4RS_OPT(p), step, "qnet_set_adam_step");
 }
 
 int rl4rs_qnet_copy_params(rl4rs_qnet* dst, const rl4rs_qnet* src, void* stream) {
-    RL4RS_REQUIRE(dst && src && dst->n_params == src->n_params, "qnet_copy_params: handles differ");
-    RL4RS_HIP_TRY(hipMemcpyAsync(dst->params, src->params, (size_t)src->n_params * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    return RL4RS_OK;
+    return opt_copy_params(RL4RS_OPT(dst), RL4RS_OPT(src), stream, "qnet_copy_params");
 }
 
 int rl4rs_qnet_status(rl4rs_qnet* p, int32_t* flags, void* stream) {
@@ -385,7 +372,7 @@ int rl4rs_qnet_forward(rl4rs_qnet* p, int32_t N, const float* obs, float* out, v
     RL4RS_REQUIRE(p && obs && out && N > 0 && N <= p->c.max_rows, "qnet_forward: bad argument (N=%d, max_rows=%d)", N, p ? p->c.max_rows : -1);
     hipStream_t st = (hipStream_t)stream;
     const int D = p->c.obs_dim, A = p->c.action_size, H1 = p->c.hidden1, M = p->c.mask_size, ES = p->c.emb_size;
-    const float* P = p->params;
+    const float* P = p->opt.params;
     const int64_t* o = p->off;
     int rc;
     if ((rc = launch_gemm_f32(obs, D, P + o[QP_W1], H1, P + o[QP_B1], p->cat, p->F2, N, H1, D, 4, st))) return rc;     // relu
@@ -408,8 +395,8 @@ int rl4rs_qnet_backward(rl4rs_qnet* p, int32_t N, const float* obs, const float*
     RL4RS_REQUIRE(p && obs && dout && N > 0 && N <= p->c.max_rows, "qnet_backward: bad argument (N=%d, max_rows=%d)", N, p ? p->c.max_rows : -1);
     hipStream_t st = (hipStream_t)stream;
     const int D = p->c.obs_dim, A = p->c.action_size, H1 = p->c.hidden1, M = p->c.mask_size, ES = p->c.emb_size, FH = p->FH, F2 = p->F2;
-    const float* P = p->params;
-    float* G = p->grad;
+    const float* P = p->opt.params;
+    float* G = p->opt.grad;
     const int64_t* o = p->off;
     auto ew = [](int n) { return dim3((n + 255) / 256); };
     const dim3 b256(256);
@@ -442,16 +429,10 @@ int rl4rs_qnet_backward(rl4rs_qnet* p, int32_t N, const float* obs, const float*
     return RL4RS_OK;
 }
 
-// torch.optim.Adam: p -= lr / (1 - b1^t) * m / (sqrt(v / (1 - b2^t)) + eps)  ==  the keras form of k_adam with eps * sqrt(1 - b2^t)
+// torch.optim.Adam (optim.hpp, ADAM_TORCH)
 int rl4rs_qnet_adam_step(rl4rs_qnet* p, float lr, float beta1, float beta2, float eps, void* stream) {
     RL4RS_REQUIRE(p, "qnet_adam_step: null handle");
-    hipStream_t st = (hipStream_t)stream;
-    p->adam_t += 1;
-    const double t = (double)p->adam_t;
-    const double c2 = sqrt(1.0 - pow((double)beta2, t));
-    const float lr_t = (float)(lr * c2 / (1.0 - pow((double)beta1, t)));
-    hipLaunchKernelGGL(k_adam, dim3((unsigned)((p->n_params + 255) / 256)), dim3(256), 0, st, p->params, p->grad, p->adam_m, p->adam_v,
-                       (int)p->n_params, lr_t, beta1, beta2, (float)(eps * c2), (const float*)nullptr, 0.f);
+    adam_step(p->opt, p->opt.grad, ADAM_TORCH, lr, beta1, beta2, eps, nullptr, 0.f, nullptr, (hipStream_t)stream);
     RL4RS_LAUNCH_CHECK();
     return RL4RS_OK;
 }

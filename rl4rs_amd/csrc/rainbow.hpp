@@ -1,7 +1,7 @@
 // On-device Rainbow (include/rl4rs_hip.h, "On-device Rainbow"): the distributional (C51) dueling Q network on a handle of its own
 // (rl4rs_distq), its fused head (MFMA GEMM + dueling centring + softmax over atoms + sum z p + SoftQ draw / first maximum), the
 // categorical Bellman projection with the cross-entropy loss and its rank-sparse backward, and the n-step form of the replay draw.
-// Compiled into policy.hip behind dqn.hpp: the replay ring, masked_first_max, k_sumsq_vars / k_adam_vars, the sample-axis
+// Compiled into policy.hip behind dqn.hpp: the replay ring, masked_first_max, the sample-axis
 // reductions (k_gemm_tn, k_reduce_chunks, k_reduce_terms), uniform01 and the wave reductions live there.
 //
 // Reference: script/modelfree_train.py:50-53,146-178 (algo "RAINBOW": num_atoms 8 over [0, 1000], everything else RLlib 1.5.1's DQN
@@ -398,8 +398,9 @@ struct rl4rs_distq {
     rl4rs_distq_cfg c;
     DistqDims d;
     int nseg, AP, chunk_cap;              // Adam variables (8 or 12); pow2 >= atoms; most sample chunks of a reduction
-    int64_t seg_end[12], n_params, adam_t;
-    float *params, *grad, *adam_m, *adam_v, *sumsq;
+    int64_t seg_end[12];
+    OptBlock opt;
+    float* sumsq;
     float *wbar, *twbar;                  // [(SH + 1) * AT] of the handle's parameters / of the last loss call's target parameters
     bool wbar_valid;
     float *H1, *H2, *Ha, *Hv, *tH1, *tH2, *tHa, *tHv, *nH1, *nH2, *nHa, *nHv;
@@ -482,11 +483,11 @@ static int distq_forward_act(rl4rs_distq* p, int N, const float* obs, const uint
                              uint32_t step, int32_t* actions, float* u_out, float* q_out, hipStream_t st) {
     int rc;
     if (!p->wbar_valid) {
-        if ((rc = distq_wbar(p, p->params, p->wbar, st))) return rc;
+        if ((rc = distq_wbar(p, p->opt.params, p->wbar, st))) return rc;
         p->wbar_valid = true;
     }
-    if ((rc = distq_hidden(p, p->params, N, obs, p->nH1, p->nH2, p->nHa, p->nHv, st))) return rc;
-    return distq_head(p, p->params, p->wbar, N, p->nHa, p->nHv, mask, mode, temperature, seed, step, actions, u_out, q_out, st);
+    if ((rc = distq_hidden(p, p->opt.params, N, obs, p->nH1, p->nH2, p->nHa, p->nHv, st))) return rc;
+    return distq_head(p, p->opt.params, p->wbar, N, p->nHa, p->nHv, mask, mode, temperature, seed, step, actions, u_out, q_out, st);
 }
 
 extern "C" {
@@ -525,8 +526,8 @@ int rl4rs_distq_create(const rl4rs_distq_cfg* cfg, const float* params_host, voi
     rl4rs_distq* p = new rl4rs_distq();
     p->c = *cfg; p->d = d;
     p->nseg = cfg->dueling ? 12 : 8;
-    p->n_params = distq_layout(*cfg, p->seg_end);
-    p->adam_t = 0;
+    p->opt.n = distq_layout(*cfg, p->seg_end);
+    p->opt.t = 0;
     p->wbar_valid = false;
     p->AP = 2;
     while (p->AP < d.AT) p->AP <<= 1;
@@ -538,8 +539,8 @@ int rl4rs_distq_create(const rl4rs_distq_cfg* cfg, const float* params_host, voi
         rc = dev_alloc(dst, n);
         if (rc == RL4RS_OK) p->owned.push_back(*dst);
     };
-    const size_t np = (size_t)p->n_params, TR = (size_t)d.TR, SH = (size_t)d.SH, AT = (size_t)d.AT;
-    alloc(&p->params, np); alloc(&p->grad, np); alloc(&p->adam_m, np); alloc(&p->adam_v, np); alloc(&p->sumsq, 12);
+    const size_t np = (size_t)p->opt.n, TR = (size_t)d.TR, SH = (size_t)d.SH, AT = (size_t)d.AT;
+    alloc(&p->opt.params, np); alloc(&p->opt.grad, np); alloc(&p->opt.m, np); alloc(&p->opt.v, np); alloc(&p->sumsq, 12);
     alloc(&p->wbar, (SH + 1) * AT); alloc(&p->twbar, (SH + 1) * AT);
     float** trunk[6] = {&p->H1, &p->H2, &p->tH1, &p->tH2, &p->nH1, &p->nH2};
     for (float** b : trunk) alloc(b, R * TR);
@@ -554,10 +555,10 @@ int rl4rs_distq_create(const rl4rs_distq_cfg* cfg, const float* params_host, voi
     alloc(&p->terms, R); alloc(&p->astar, R);
     if (rc) { rl4rs_distq_destroy(p); return rc; }
     hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipMemcpyAsync(p->params, params_host, np * 4, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemsetAsync(p->adam_m, 0, np * 4, st);
-    if (e == hipSuccess) e = hipMemsetAsync(p->adam_v, 0, np * 4, st);
-    if (e == hipSuccess) e = hipMemsetAsync(p->grad, 0, np * 4, st);
+    hipError_t e = hipMemcpyAsync(p->opt.params, params_host, np * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemsetAsync(p->opt.m, 0, np * 4, st);
+    if (e == hipSuccess) e = hipMemsetAsync(p->opt.v, 0, np * 4, st);
+    if (e == hipSuccess) e = hipMemsetAsync(p->opt.grad, 0, np * 4, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) {
         set_error("distq_create: initialisation failed: %s", hipGetErrorString(e));
@@ -569,34 +570,23 @@ int rl4rs_distq_create(const rl4rs_distq_cfg* cfg, const float* params_host, voi
 }
 
 int rl4rs_distq_params(rl4rs_distq* p, float** params_dev, float** grad_dev, int64_t* count) {
-    RL4RS_REQUIRE(p, "distq_params: null handle");
-    p->wbar_valid = false;                 // the caller may write through the pointer
-    if (params_dev) *params_dev = p->params;
-    if (grad_dev) *grad_dev = p->grad;
-    if (count) *count = p->n_params;
-    return RL4RS_OK;
+    if (p) p->wbar_valid = false;          // the caller may write through the pointer
+    return opt_params(RL4RS_OPT(p), params_dev, grad_dev, count, "distq_params");
 }
 
 int rl4rs_distq_copy_params(rl4rs_distq* dst, const rl4rs_distq* src, void* stream) {
-    RL4RS_REQUIRE(dst && src && dst->n_params == src->n_params && dst->c.dueling == src->c.dueling && dst->c.atoms == src->c.atoms &&
+    RL4RS_REQUIRE(dst && src && dst->opt.n == src->opt.n && dst->c.dueling == src->c.dueling && dst->c.atoms == src->c.atoms &&
                   dst->c.action_size == src->c.action_size, "distq_copy_params: the two networks differ in shape");
-    RL4RS_HIP_TRY(hipMemcpyAsync(dst->params, src->params, (size_t)src->n_params * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     dst->wbar_valid = false;
-    return RL4RS_OK;
+    return opt_copy_params(&dst->opt, &src->opt, stream, "distq_copy_params");
 }
 
 int rl4rs_distq_adam_state(rl4rs_distq* p, float** m_dev, float** v_dev, int64_t* step) {
-    RL4RS_REQUIRE(p, "distq_adam_state: null handle");
-    if (m_dev) *m_dev = p->adam_m;
-    if (v_dev) *v_dev = p->adam_v;
-    if (step) *step = p->adam_t;
-    return RL4RS_OK;
+    return opt_adam_state(RL4RS_OPT(p), m_dev, v_dev, step, "distq_adam_state");
 }
 
 int rl4rs_distq_set_adam_step(rl4rs_distq* p, int64_t step) {
-    RL4RS_REQUIRE(p && step >= 0, "distq_set_adam_step: bad argument");
-    p->adam_t = step;
-    return RL4RS_OK;
+    return opt_set_adam_step(RL4RS_OPT(p), step, "distq_set_adam_step");
 }
 
 int rl4rs_distq_act(rl4rs_distq* p, int32_t N, const float* obs, const uint32_t* mask_bits, float temperature, uint32_t seed, uint32_t step,
@@ -622,23 +612,23 @@ int rl4rs_distq_loss_grad(rl4rs_distq* p, const float* target_params_dev, int32_
     const DistqDims& d = p->d;
     int rc;
     if (!p->wbar_valid) {
-        if ((rc = distq_wbar(p, p->params, p->wbar, st))) return rc;
+        if ((rc = distq_wbar(p, p->opt.params, p->wbar, st))) return rc;
         p->wbar_valid = true;
     }
     if ((rc = distq_wbar(p, target_params_dev, p->twbar, st))) return rc;
     // forwards: the online net on s, the target net on s', and a* from the online net on s' (double_q) or from the target's
-    if ((rc = distq_hidden(p, p->params, N, obs, p->H1, p->H2, p->Ha, p->Hv, st))) return rc;
+    if ((rc = distq_hidden(p, p->opt.params, N, obs, p->H1, p->H2, p->Ha, p->Hv, st))) return rc;
     if ((rc = distq_hidden(p, target_params_dev, N, next_obs, p->tH1, p->tH2, p->tHa, p->tHv, st))) return rc;
     if (double_q) {
-        if ((rc = distq_hidden(p, p->params, N, next_obs, p->nH1, p->nH2, p->nHa, p->nHv, st))) return rc;
-        if ((rc = distq_head(p, p->params, p->wbar, N, p->nHa, p->nHv, next_mask_bits, DISTQ_GREEDY, 1.f, 0u, 0u, p->astar, nullptr, nullptr, st)))
+        if ((rc = distq_hidden(p, p->opt.params, N, next_obs, p->nH1, p->nH2, p->nHa, p->nHv, st))) return rc;
+        if ((rc = distq_head(p, p->opt.params, p->wbar, N, p->nHa, p->nHv, next_mask_bits, DISTQ_GREEDY, 1.f, 0u, 0u, p->astar, nullptr, nullptr, st)))
             return rc;
     } else {
         if ((rc = distq_head(p, target_params_dev, p->twbar, N, p->tHa, p->tHv, next_mask_bits, DISTQ_GREEDY, 1.f, 0u, 0u, p->astar, nullptr,
                              nullptr, st)))
             return rc;
     }
-    const DistqPtrs<const float> q = distq_ptrs<const float>(p->params, d);
+    const DistqPtrs<const float> q = distq_ptrs<const float>(p->opt.params, d);
     const DistqPtrs<const float> tq = distq_ptrs<const float>(target_params_dev, d);
     DistqRows a;
     memset(&a, 0, sizeof(a));
@@ -697,9 +687,7 @@ int rl4rs_distq_adam_step_clip_by_var(rl4rs_distq* p, const float* grad_dev, flo
                                       void* stream) {
     RL4RS_REQUIRE(p && grad_dev, "distq_adam_step_clip_by_var: null argument");
     hipStream_t st = (hipStream_t)stream;
-    p->adam_t += 1;
-    const double t = (double)p->adam_t;
-    const float lr_t = (float)(lr * sqrt(1.0 - pow((double)beta2, t)) / (1.0 - pow((double)beta1, t)));
+    const float lr_t = adam_advance(p->opt, ADAM_TF, lr, beta1, beta2, eps).lr_t;
     // k_sumsq_vars / k_adam_vars take four variables: the 8 (12) of this layout go through them four at a time
     for (int v0 = 0; v0 < p->nseg; v0 += 4) {
         const int64_t base = v0 == 0 ? 0 : p->seg_end[v0 - 1];
@@ -707,8 +695,8 @@ int rl4rs_distq_adam_step_clip_by_var(rl4rs_distq* p, const float* grad_dev, flo
         VarSegs sg;
         for (int i = 0; i < 4; ++i) sg.end[i] = (int)(p->seg_end[v0 + i] - base);
         if (var_clip > 0.f) hipLaunchKernelGGL(k_sumsq_vars, dim3(4), dim3(256), 0, st, grad_dev + base, sg, p->sumsq + v0);
-        hipLaunchKernelGGL(k_adam_vars, dim3((count + 255) / 256), dim3(256), 0, st, p->params + base, grad_dev + base, p->adam_m + base,
-                           p->adam_v + base, count, sg, lr_t, beta1, beta2, eps, p->sumsq + v0, var_clip);
+        hipLaunchKernelGGL(k_adam_vars, dim3((count + 255) / 256), dim3(256), 0, st, p->opt.params + base, grad_dev + base, p->opt.m + base,
+                           p->opt.v + base, count, sg, lr_t, beta1, beta2, eps, p->sumsq + v0, var_clip);
     }
     RL4RS_LAUNCH_CHECK();
     p->wbar_valid = false;

@@ -47,12 +47,12 @@ struct rl4rs_rawtrain {
     rl4rs_rawpolicy_cfg c;
     PolDims d;
     int F;
-    int64_t n_params, off[RT_COUNT];
+    int64_t off[RT_COUNT];
     TrainCtx cx;
-    float *params, *grad, *adam_m, *adam_v, *sumsq;
+    OptBlock opt;
+    float* sumsq;
     float *feat, *h1, *ctx, *ext, *dOut, *d_ctx, *d_feat, *d_h1;
     float4* terms;
-    int64_t adam_t;
     std::vector<void*> owned;
 };
 
@@ -61,7 +61,7 @@ namespace {
 int rawtrain_forward(rl4rs_rawtrain* p, int N, const int32_t* cat, const float* dense, const int32_t* const* seq, hipStream_t st) {
     const int E = p->c.emb_size, U = p->c.hidden_units, H = p->c.category_hash_size, S = p->c.seq_num, Dn = p->c.dense_feature_num;
     const int F = p->F, L = p->c.maxlen, Cn = p->c.category_feature_num, AE = p->d.AE;
-    const float* P = p->params;
+    const float* P = p->opt.params;
     const int64_t* o = p->off;
     const dim3 g4((N + 3) / 4), b256(256);
     int rc;
@@ -104,11 +104,11 @@ int rl4rs_rawtrain_create(const rl4rs_rawpolicy_cfg* c, const rl4rs_rawpolicy_we
     p->c = *c;
     p->d.OD = 256; p->d.HID = 0; p->d.A = (int)A; p->d.AE = (int)AE; p->d.W = (int)((A + 31) / 32);
     p->F = (int)(S * E + U + E);
-    p->adam_t = 0;
+    p->opt.t = 0;
     const int64_t sizes[RT_COUNT] = {H * E, H * E, Dn * U, U, U * U, U, (int64_t)p->F * 256, 256, 256 * AE, AE};
     int64_t o = 0;
     for (int i = 0; i < RT_COUNT; ++i) { p->off[i] = o; o += sizes[i]; }
-    p->n_params = o;
+    p->opt.n = o;
     int rc;
     auto al = [&](float** dst, size_t n) {
         int r = dev_alloc(dst, n);
@@ -118,10 +118,10 @@ int rl4rs_rawtrain_create(const rl4rs_rawpolicy_cfg* c, const rl4rs_rawpolicy_we
 #define RT_FAIL(expr) do { if ((rc = (expr)) != RL4RS_OK) { rl4rs_rawtrain_destroy(p); return rc; } } while (0)
 #define RT_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { set_error("%s failed: %s", #expr, hipGetErrorString(e_)); \
         rl4rs_rawtrain_destroy(p); return RL4RS_EHIP; } } while (0)
-    RT_FAIL(al(&p->params, p->n_params)); RT_FAIL(al(&p->grad, p->n_params)); RT_FAIL(al(&p->adam_m, p->n_params));
-    RT_FAIL(al(&p->adam_v, p->n_params)); RT_FAIL(al(&p->sumsq, 4));
+    RT_FAIL(al(&p->opt.params, p->opt.n)); RT_FAIL(al(&p->opt.grad, p->opt.n)); RT_FAIL(al(&p->opt.m, p->opt.n));
+    RT_FAIL(al(&p->opt.v, p->opt.n)); RT_FAIL(al(&p->sumsq, 4));
     const float* src[8] = {w->cat_emb, w->seq_emb, w->dense_w1, w->dense_b1, w->dense_w2, w->dense_b2, w->ctx_w, w->ctx_b};
-    for (int i = 0; i < 8; ++i) RT_HIP(hipMemcpyAsync(p->params + p->off[i], src[i], (size_t)sizes[i] * 4, hipMemcpyHostToDevice, st));
+    for (int i = 0; i < 8; ++i) RT_HIP(hipMemcpyAsync(p->opt.params + p->off[i], src[i], (size_t)sizes[i] * 4, hipMemcpyHostToDevice, st));
     std::vector<float> hw((size_t)256 * AE), hb(AE);       // [out_w | value_w], [out_b | value_b]
     for (int k = 0; k < 256; ++k) {
         for (int a = 0; a < A; ++a) hw[(size_t)k * AE + a] = w->out_w[(size_t)k * A + a];
@@ -129,10 +129,10 @@ int rl4rs_rawtrain_create(const rl4rs_rawpolicy_cfg* c, const rl4rs_rawpolicy_we
     }
     for (int a = 0; a < A; ++a) hb[a] = w->out_b[a];
     hb[A] = w->value_b[0];
-    RT_HIP(hipMemcpyAsync(p->params + p->off[RT_HEAD_W], hw.data(), hw.size() * 4, hipMemcpyHostToDevice, st));
-    RT_HIP(hipMemcpyAsync(p->params + p->off[RT_HEAD_B], hb.data(), hb.size() * 4, hipMemcpyHostToDevice, st));
-    RT_HIP(hipMemsetAsync(p->adam_m, 0, (size_t)p->n_params * 4, st));
-    RT_HIP(hipMemsetAsync(p->adam_v, 0, (size_t)p->n_params * 4, st));
+    RT_HIP(hipMemcpyAsync(p->opt.params + p->off[RT_HEAD_W], hw.data(), hw.size() * 4, hipMemcpyHostToDevice, st));
+    RT_HIP(hipMemcpyAsync(p->opt.params + p->off[RT_HEAD_B], hb.data(), hb.size() * 4, hipMemcpyHostToDevice, st));
+    RT_HIP(hipMemsetAsync(p->opt.m, 0, (size_t)p->opt.n * 4, st));
+    RT_HIP(hipMemsetAsync(p->opt.v, 0, (size_t)p->opt.n * 4, st));
     const size_t B = c->max_rows;
     RT_FAIL(al(&p->feat, B * p->F)); RT_FAIL(al(&p->h1, B * U)); RT_FAIL(al(&p->ctx, B * 256)); RT_FAIL(al(&p->ext, B * AE));
     RT_FAIL(al(&p->dOut, B * AE)); RT_FAIL(al(&p->d_ctx, B * 256)); RT_FAIL(al(&p->d_feat, B * p->F)); RT_FAIL(al(&p->d_h1, B * U));
@@ -151,11 +151,7 @@ int rl4rs_rawtrain_create(const rl4rs_rawpolicy_cfg* c, const rl4rs_rawpolicy_we
 }
 
 int rl4rs_rawtrain_params(rl4rs_rawtrain* p, float** params_dev, float** grad_dev, int64_t* count) {
-    RL4RS_REQUIRE(p, "rawtrain_params: null handle");
-    if (params_dev) *params_dev = p->params;
-    if (grad_dev) *grad_dev = p->grad;
-    if (count) *count = p->n_params;
-    return RL4RS_OK;
+    return opt_params(RL4RS_OPT(p), params_dev, grad_dev, count, "rawtrain_params");
 }
 
 int rl4rs_rawtrain_act(rl4rs_rawtrain* p, int32_t N, const int32_t* cat, const float* dense, const int32_t* const* seq,
@@ -197,8 +193,8 @@ int rl4rs_rawtrain_loss_grad(rl4rs_rawtrain* p, int32_t algo, int32_t N, const i
     hipStream_t st = (hipStream_t)stream;
     const int E = p->c.emb_size, U = p->c.hidden_units, H = p->c.category_hash_size, S = p->c.seq_num, Dn = p->c.dense_feature_num;
     const int F = p->F, L = p->c.maxlen, Cn = p->c.category_feature_num, AE = p->d.AE;
-    const float* P = p->params;
-    float* G = p->grad;
+    const float* P = p->opt.params;
+    float* G = p->opt.grad;
     const int64_t* o = p->off;
     int rc = rawtrain_forward(p, N, cat, dense, seq, st);
     if (rc) return rc;
@@ -238,13 +234,7 @@ int rl4rs_rawtrain_loss_grad(rl4rs_rawtrain* p, int32_t algo, int32_t N, const i
 
 int rl4rs_rawtrain_adam_step(rl4rs_rawtrain* p, float lr, float beta1, float beta2, float eps, float grad_clip, void* stream) {
     RL4RS_REQUIRE(p, "rawtrain_adam_step: null handle");
-    hipStream_t st = (hipStream_t)stream;
-    p->adam_t += 1;
-    const double t = (double)p->adam_t;
-    const float lr_t = (float)(lr * sqrt(1.0 - pow((double)beta2, t)) / (1.0 - pow((double)beta1, t)));
-    if (grad_clip > 0.f) hipLaunchKernelGGL(k_sumsq, dim3(1), dim3(256), 0, st, p->grad, (int)p->n_params, p->sumsq);
-    hipLaunchKernelGGL(k_adam, dim3((unsigned)((p->n_params + 255) / 256)), dim3(256), 0, st, p->params, p->grad, p->adam_m, p->adam_v,
-                       (int)p->n_params, lr_t, beta1, beta2, eps, p->sumsq, grad_clip);
+    adam_step(p->opt, p->opt.grad, ADAM_TF, lr, beta1, beta2, eps, p->sumsq, grad_clip, nullptr, (hipStream_t)stream);
     RL4RS_LAUNCH_CHECK();
     return RL4RS_OK;
 }

@@ -199,15 +199,13 @@ static int g_dientrain_fork = 1;       // rl4rs_dientrain_set_fork: per-input la
 
 struct rl4rs_simtrain {
     rl4rs_simnet_cfg c;
-    int64_t n_params;
     int64_t off[SP_COUNT], size[SP_COUNT];       // offsets / sizes in the flat buffers (size 0 = the family has no such array)
     size_t part_cap;                             // floats behind `part`
     int max_batch, chunk, nz, OD, FCK;           // OD = width of 'simulator_obs', FCK = input width of the fc layer
-    float *params, *grad, *adam_m, *adam_v;
+    OptBlock opt;
     float *feat, *h1, *h1d, *h2, *a1, *obs, *logits;            // activations (feat = input of fc, a1 = its output for dnn)
-    float *d_logits, *d_obs, *d_a, *d_feat, *d_h1, *d_h2, *wt, *part, *loss_rows, *lr_dummy;
+    float *d_logits, *d_obs, *d_a, *d_feat, *d_h1, *d_h2, *wt, *part, *loss_rows;
     uint8_t *mask1, *mask2;
-    int64_t adam_t;
     // lstm: saved forwards of the 1 + seq_num GRUs and BPTT scratch
     GruSave gru[5];
     float *g_dA, *g_dX, *g_hprev, *g_G, *g_Gh, *g_dh, *g_dhp, *g_dhg, *g_drh, *g_zero, *g_uzrT, *g_uhT, *g_tmpw;
@@ -322,10 +320,10 @@ int gru_forward_multi(rl4rs_simtrain* t, int N, GruSave* const* gs, int n, hipSt
     int rc;
     for (int k = 0; k < n; ++k) {
         GruSave& g = *gs[k];
-        const float* K = t->params + t->off[g.pk];
-        const float* Rw = t->params + t->off[g.pk + 1];
-        const float* b = t->params + t->off[g.pk + 2];
-        hipLaunchKernelGGL(k_emb_flatten, dim3((N + 3) / 4), dim3(256), 0, st, g.ids, N, len, H, E, t->params + t->off[g.emb], g.X,
+        const float* K = t->opt.params + t->off[g.pk];
+        const float* Rw = t->opt.params + t->off[g.pk + 1];
+        const float* b = t->opt.params + t->off[g.pk + 2];
+        hipLaunchKernelGGL(k_emb_flatten, dim3((N + 3) / 4), dim3(256), 0, st, g.ids, N, len, H, E, t->opt.params + t->off[g.emb], g.X,
                            (int64_t)len * E, 0);
         if ((rc = launch_gemm_f32(g.X, E, K, 3 * U, b, g.A1, 3 * U, N * len, 3 * U, E, 0, st))) return rc;
         if ((rc = launch_pack_frag(Rw + U, 3 * U, 0, U, U, 0, g.pkg, st))) return rc;                         // reset columns
@@ -340,11 +338,11 @@ int gru_forward_multi(rl4rs_simtrain* t, int N, GruSave* const* gs, int n, hipSt
 // keras GRU forward over `len` steps for N rows, keeping gates and states (utils.py:34,91: layers.GRU(units=U))
 int gru_forward(rl4rs_simtrain* t, int N, GruSave& g, hipStream_t st) {
     const int E = t->c.emb_size, U = t->c.hidden_units, H = t->c.category_hash_size, len = g.len;
-    const float* K = t->params + t->off[g.pk];
-    const float* Rw = t->params + t->off[g.pk + 1];
-    const float* b = t->params + t->off[g.pk + 2];
+    const float* K = t->opt.params + t->off[g.pk];
+    const float* Rw = t->opt.params + t->off[g.pk + 1];
+    const float* b = t->opt.params + t->off[g.pk + 2];
     int rc;
-    hipLaunchKernelGGL(k_emb_flatten, dim3((N + 3) / 4), dim3(256), 0, st, g.ids, N, len, H, E, t->params + t->off[g.emb], g.X,
+    hipLaunchKernelGGL(k_emb_flatten, dim3((N + 3) / 4), dim3(256), 0, st, g.ids, N, len, H, E, t->opt.params + t->off[g.emb], g.X,
                        (int64_t)len * E, 0);
     if ((rc = launch_gemm_f32(g.X, E, K, 3 * U, b, g.A1, 3 * U, N * len, 3 * U, E, 0, st))) return rc;
     const dim3 ew((N * U + 255) / 256), b256(256);
@@ -373,7 +371,7 @@ int gru_backward_launch_multi(rl4rs_simtrain* t, int N, GruSave* const* gs, cons
     int rc;
     for (int k = 0; k < n; ++k) {
         GruSave& g = *gs[k];
-        const float* Rw = t->params + t->off[g.pk + 1];
+        const float* Rw = t->opt.params + t->off[g.pk + 1];
         if ((rc = launch_pack_frag(Rw + 2 * U, 3 * U, 0, U, U, 1, g.pkc, st))) return rc;                                   // U_h^T
         if ((rc = launch_pack_frag_slice(Rw + U, 3 * U, 0, U, U, 1, g.pkg, 2 * U, 0, st))) return rc;                       // U_r^T
         if ((rc = launch_pack_frag_slice(Rw, 3 * U, 0, U, U, 1, g.pkg, 2 * U, U, st))) return rc;                           // U_z^T
@@ -388,11 +386,11 @@ int gru_backward_launch_multi(rl4rs_simtrain* t, int N, GruSave* const* gs, cons
 // parameter gradients and the embedding scatter remain
 int gru_backward(rl4rs_simtrain* t, int N, GruSave& g, const float* up, int64_t ld_up, float* use_dA, hipStream_t st, const GruScratch& sc) {
     const int E = t->c.emb_size, U = t->c.hidden_units, H = t->c.category_hash_size, len = g.len;
-    const float* K = t->params + t->off[g.pk];
-    const float* Rw = t->params + t->off[g.pk + 1];
-    float* gK = t->grad + t->off[g.pk];
-    float* gR = t->grad + t->off[g.pk + 1];
-    float* gb = t->grad + t->off[g.pk + 2];
+    const float* K = t->opt.params + t->off[g.pk];
+    const float* Rw = t->opt.params + t->off[g.pk + 1];
+    float* gK = t->opt.grad + t->off[g.pk];
+    float* gR = t->opt.grad + t->off[g.pk + 1];
+    float* gb = t->opt.grad + t->off[g.pk + 2];
     int rc;
     const dim3 ew((N * U + 255) / 256), b256(256);
     float* dA = use_dA ? use_dA : t->g_dA;
@@ -429,7 +427,7 @@ int gru_backward(rl4rs_simtrain* t, int N, GruSave& g, const float* up, int64_t 
     RL4RS_HIP_TRY(hipMemcpy2DAsync(gR + 2 * U, (size_t)3 * U * 4, sc.tmpw, (size_t)U * 4, (size_t)U * 4, U, hipMemcpyDeviceToDevice, st));
     if ((rc = st_back(cx, st, dA, 3 * U, 3 * U, K, 3 * U, E, sc.dX, E, Ns))) return rc;
     hipLaunchKernelGGL(k_emb_flatten_bwd, dim3((N + 3) / 4), b256, 0, st, g.ids, N, len, H, E, sc.dX, (int64_t)len * E,
-                       t->grad + t->off[g.emb]);
+                       t->opt.grad + t->off[g.emb]);
     RL4RS_LAUNCH_CHECK();
     return RL4RS_OK;
 }
@@ -478,7 +476,7 @@ int rl4rs_simtrain_create(const rl4rs_simnet_cfg* c, const rl4rs_simnet_weights*
     t->max_batch = max_batch;
     t->chunk = 512;
     t->nz = (max_batch + t->chunk - 1) / t->chunk;
-    t->adam_t = 0;
+    t->opt.t = 0;
     t->OD = wd ? (int)(256 + U + Cn * E) : 256;
     // FCK = width of the concat that feeds the first dense layer above the branches (fc for dnn / widedeep, obs for lstm)
     t->FCK = wd ? (int)(S * E) : (ls ? (int)(S * U + 2 * U + Cn * E) : (int)(E + U));
@@ -496,7 +494,7 @@ int rl4rs_simtrain_create(const rl4rs_simnet_cfg* c, const rl4rs_simnet_weights*
     }
     int64_t o = 0;
     for (int i = 0; i < SP_COUNT; ++i) { t->off[i] = o; t->size[i] = sizes[i]; o += sizes[i]; }
-    t->n_params = o;
+    t->opt.n = o;
     int rc = RL4RS_OK;
     auto al = [&](float** dst, size_t n) {
         int r = dev_alloc(dst, n);
@@ -506,14 +504,14 @@ int rl4rs_simtrain_create(const rl4rs_simnet_cfg* c, const rl4rs_simnet_weights*
 #define ST_FAIL(expr) do { if ((rc = (expr)) != RL4RS_OK) { rl4rs_simtrain_destroy(t); return rc; } } while (0)
 #define ST_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { set_error("%s failed: %s", #expr, hipGetErrorString(e_)); \
         rl4rs_simtrain_destroy(t); return RL4RS_EHIP; } } while (0)
-    ST_FAIL(al(&t->params, t->n_params));
-    ST_FAIL(al(&t->grad, t->n_params));
-    ST_FAIL(al(&t->adam_m, t->n_params));
-    ST_FAIL(al(&t->adam_v, t->n_params));
+    ST_FAIL(al(&t->opt.params, t->opt.n));
+    ST_FAIL(al(&t->opt.grad, t->opt.n));
+    ST_FAIL(al(&t->opt.m, t->opt.n));
+    ST_FAIL(al(&t->opt.v, t->opt.n));
     for (int i = 0; i < SP_COUNT; ++i)
-        if (sizes[i]) ST_HIP(hipMemcpyAsync(t->params + t->off[i], src[i], (size_t)sizes[i] * 4, hipMemcpyHostToDevice, st));
-    ST_HIP(hipMemsetAsync(t->adam_m, 0, (size_t)t->n_params * 4, st));
-    ST_HIP(hipMemsetAsync(t->adam_v, 0, (size_t)t->n_params * 4, st));
+        if (sizes[i]) ST_HIP(hipMemcpyAsync(t->opt.params + t->off[i], src[i], (size_t)sizes[i] * 4, hipMemcpyHostToDevice, st));
+    ST_HIP(hipMemsetAsync(t->opt.m, 0, (size_t)t->opt.n * 4, st));
+    ST_HIP(hipMemsetAsync(t->opt.v, 0, (size_t)t->opt.n * 4, st));
     const size_t B = max_batch;
     ST_FAIL(al(&t->feat, B * t->FCK));
     ST_FAIL(al(&t->h1, B * U));
@@ -582,7 +580,6 @@ int rl4rs_simtrain_create(const rl4rs_simnet_cfg* c, const rl4rs_simnet_weights*
         }
     }
     ST_FAIL(al(&t->loss_rows, B));
-    ST_FAIL(al(&t->lr_dummy, 4));
     {
         float* m;
         ST_FAIL(al(&m, (B * U + 3) / 4 + 1));
@@ -598,11 +595,7 @@ int rl4rs_simtrain_create(const rl4rs_simnet_cfg* c, const rl4rs_simnet_weights*
 }
 
 int rl4rs_simtrain_params(rl4rs_simtrain* t, float** params_dev, float** grad_dev, int64_t* count) {
-    RL4RS_REQUIRE(t, "simtrain_params: null handle");
-    if (params_dev) *params_dev = t->params;
-    if (grad_dev) *grad_dev = t->grad;
-    if (count) *count = t->n_params;
-    return RL4RS_OK;
+    return opt_params(RL4RS_OPT(t), params_dev, grad_dev, count, "simtrain_params");
 }
 
 // the keep-masks (uint8 [N, hidden_units] each) the last rl4rs_simtrain_grad / _step drew for the two tower layers
@@ -629,8 +622,8 @@ int rl4rs_simtrain_grad(rl4rs_simtrain* t, int32_t N, const float* dense, const 
     const int E = t->c.emb_size, U = t->c.hidden_units, H = t->c.category_hash_size, Dn = t->c.dense_feature_num;
     const int Cn = t->c.category_feature_num, K = t->c.class_num, S = t->c.seq_num, L = t->c.maxlen;
     const int FCK = t->FCK, OD = t->OD;
-    float* P = t->params;
-    float* G = t->grad;
+    float* P = t->opt.params;
+    float* G = t->opt.grad;
     const int64_t* o = t->off;
     int rc;
     auto ew = [](int n) { return dim3((n + 255) / 256); };
@@ -778,12 +771,7 @@ int rl4rs_simtrain_step(rl4rs_simtrain* t, int32_t N, const float* dense, const 
                         uint32_t step, float* loss_dev, void* stream) {
     int rc = rl4rs_simtrain_grad(t, N, dense, cat, seq, labels, dropout_rate, seed, step, loss_dev, stream);
     if (rc) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    t->adam_t += 1;
-    const double tt = (double)t->adam_t;
-    const float lr_t = (float)(lr * sqrt(1.0 - pow((double)beta2, tt)) / (1.0 - pow((double)beta1, tt)));
-    hipLaunchKernelGGL(k_adam, dim3((unsigned)((t->n_params + 255) / 256)), dim3(256), 0, st, t->params, t->grad, t->adam_m, t->adam_v,
-                       (int)t->n_params, lr_t, beta1, beta2, eps, t->lr_dummy, 0.f);
+    adam_step(t->opt, t->opt.grad, ADAM_TF, lr, beta1, beta2, eps, nullptr, 0.f, nullptr, (hipStream_t)stream);
     RL4RS_LAUNCH_CHECK();
     return RL4RS_OK;
 }

@@ -83,11 +83,6 @@ __global__ void k_amlp_add_l2(float* __restrict__ g, const float* __restrict__ p
     if (weight) g[i] += l2 * p[i];
 }
 
-__global__ void k_fill(float* __restrict__ x, int n, float v) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) x[i] = v;
-}
-
 struct Td3Loss {
     int N, use_huber;
     float gamma, delta;
@@ -214,8 +209,8 @@ int rl4rs_amlp_add_l2(rl4rs_amlp* p, float l2, void* stream) {
     RL4RS_REQUIRE(p, "amlp_add_l2: null handle");
     if (l2 == 0.f) return RL4RS_OK;
     const int64_t* o = p->off;
-    hipLaunchKernelGGL(k_amlp_add_l2, dim3((unsigned)((p->n_params + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p->grad, p->params,
-                       (long long)p->n_params, (long long)o[AP_B1], (long long)o[AP_W2], (long long)o[AP_B2], (long long)o[AP_W3],
+    hipLaunchKernelGGL(k_amlp_add_l2, dim3((unsigned)((p->opt.n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p->opt.grad, p->opt.params,
+                       (long long)p->opt.n, (long long)o[AP_B1], (long long)o[AP_W2], (long long)o[AP_B2], (long long)o[AP_W3],
                        (long long)o[AP_B3], l2);
     RL4RS_LAUNCH_CHECK();
     return RL4RS_OK;

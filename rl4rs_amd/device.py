@@ -833,9 +833,117 @@ def _simtrain_names(algo, seq_num):
     return names
 
 
-class DeviceSimTrainer(object):
+class _FlatNet(object):
+    """Shared plumbing of every trainable handle ``<_prefix>*``: flat parameters, gradient and Adam state, copied device to device
+    on the current stream.  The setters keep their source tensors alive until the next call (no host wait: they sit on the
+    data-parallel step path).  ``shapes``: (name, shape) of the arrays in flat order, where the wrapper knows them."""
+    _prefix = None
+    shapes = ()
+
+    def _call(self, name):
+        return getattr(self.lib, self._prefix + name)
+
+    def close(self):
+        if getattr(self, 'h', None) is not None and self.h:
+            self._call('destroy')(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _ptrs(self):
+        """(parameters, gradient, count) of the handle's flat buffers"""
+        p, g, n = C.c_void_p(), C.c_void_p(), C.c_int64()
+        check(self._call('params')(self.h, C.byref(p), C.byref(g), C.byref(n)))
+        return p, g, n.value
+
+    def _grad_ptr(self):
+        _, g, n = self._ptrs()
+        if g is None:
+            raise TypeError('%s keeps no gradient of its own: it is the buffer its loss calls fill' % type(self).__name__)
+        return g, n
+
+    def _adam_ptrs(self):
+        m, v, t = C.c_void_p(), C.c_void_p(), C.c_int64()
+        check(self._call('adam_state')(self.h, C.byref(m), C.byref(v), C.byref(t)))
+        return m, v, int(t.value)
+
+    def _copy_out(self, src, n, out=None):
+        if out is None:
+            out = torch.empty(n, dtype=torch.float32, device=self.device)
+        assert out.dtype == torch.float32 and out.numel() == n and out.is_contiguous() and out.is_cuda
+        check(self.lib.rl4rs_copy_d2d(_ptr(out), src, n * 4, _stream()))
+        return out
+
+    def _copy_in(self, which, dst, n, src):
+        src = src.to(device=self.device, dtype=torch.float32).contiguous()
+        assert src.numel() == n, (src.numel(), n)
+        check(self.lib.rl4rs_copy_d2d(dst, _ptr(src), n * 4, _stream()))
+        self.__dict__.setdefault('_keep', {})[which] = src       # alive until the next copy into the same buffer
+
+    def params(self, out=None):
+        """Copy of the flat parameter buffer (device tensor); ``out``: a contiguous float32 device tensor to copy into."""
+        p, _, n = self._ptrs()
+        return self._copy_out(p, n, out)
+
+    def flat_gradient(self, out=None):
+        """Copy of the flat gradient the handle holds (device tensor)."""
+        g, n = self._grad_ptr()
+        return self._copy_out(g, n, out)
+
+    def set_params(self, flat):
+        p, _, n = self._ptrs()
+        self._copy_in('params', p, n, flat)
+
+    def set_flat_gradient(self, flat):
+        g, n = self._grad_ptr()
+        self._copy_in('grad', g, n, flat)
+
+    flat_params, set_flat_params, grad = params, set_params, flat_gradient
+
+    def _flat(self, which):
+        """'params' or 'grad': the copy by name, as the trainers' tests ask for it"""
+        return self.params() if which == 'params' else self.flat_gradient()
+
+    def _split(self, flat):
+        out, o = {}, 0
+        for name, shape in self.shapes:
+            k = int(np.prod(shape))
+            out[name] = flat[o:o + k].reshape(shape)
+            o += k
+        return out
+
+    def weights(self):
+        """Current parameters as a dict of device tensors, by the names of ``shapes``."""
+        return self._split(self.params())
+
+    def gradients(self):
+        return self._split(self.flat_gradient())
+
+    def copy_from(self, other):
+        """This handle's parameters <- ``other``'s, device to device."""
+        check(self._call('copy_params')(self.h, other.h, _stream()))
+
+    def adam_state(self):
+        """(m, v, step): copies of the Adam moments (device tensors) and the step counter - what a checkpoint keeps."""
+        m, v, t = self._adam_ptrs()
+        return self._copy_out(m, self.n_params), self._copy_out(v, self.n_params), t
+
+    def set_adam_state(self, m, v, step):
+        pm, pv, _ = self._adam_ptrs()
+        self._copy_in('adam_m', pm, self.n_params, m)
+        self._copy_in('adam_v', pv, self.n_params, v)
+        check(self._call('set_adam_step')(self.h, int(step)))
+
+
+class DeviceSimTrainer(_FlatNet):
     """rl4rs_simtrain handle: supervised training of the 'dnn' / 'widedeep' / 'lstm' simulators on the device
-    (script/supervised_train.py): forward with dropout, keras binary_crossentropy, backward, Adam."""
+    (script/supervised_train.py): forward with dropout, keras binary_crossentropy, backward, Adam.  ``weights()`` carries the
+    names of rl4rs_amd.nets.simnets.simnet_spec; ``grad`` is the forward + backward here, the flat gradient is ``flat_gradient()``."""
+    _prefix = 'rl4rs_simtrain_'
 
     def __init__(self, config, weights, max_batch=256, algo=None, device=None):
         _lib.require_device()
@@ -868,46 +976,11 @@ class DeviceSimTrainer(object):
             check(self.lib.rl4rs_simtrain_create(C.byref(cfg), C.byref(w), self.max_batch, _stream(), C.byref(h)))
         self.h = h
         self.iteration = 0
-        self._fn = dict(destroy=self.lib.rl4rs_simtrain_destroy, params=self.lib.rl4rs_simtrain_params,
-                        masks=self.lib.rl4rs_simtrain_masks, grad=self.lib.rl4rs_simtrain_grad, step=self.lib.rl4rs_simtrain_step)
-
-    def close(self):
-        if getattr(self, 'h', None) is not None and self.h:
-            self._fn['destroy'](self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _flat(self, which):
-        p, g, n = C.c_void_p(), C.c_void_p(), C.c_int64()
-        check(self._fn['params'](self.h, C.byref(p), C.byref(g), C.byref(n)))
-        out = torch.empty(n.value, dtype=torch.float32, device=self.device)
-        check(self.lib.rl4rs_copy_d2d(_ptr(out), p if which == 'params' else g, n.value * 4, _stream()))
-        return out
-
-    def _split(self, flat):
-        out, o = {}, 0
-        for name, shape in self.shapes:
-            k = int(np.prod(shape))
-            out[name] = flat[o:o + k].reshape(shape)
-            o += k
-        return out
-
-    def weights(self):
-        """Current parameters as a dict of device tensors (same names as rl4rs_amd.nets.simnets.simnet_spec)."""
-        return self._split(self._flat('params'))
-
-    def gradients(self):
-        return self._split(self._flat('grad'))
 
     def masks(self, N):
         """The dropout keep-masks [N, hidden_units] (uint8) of the last grad / step call."""
         m1, m2 = C.c_void_p(), C.c_void_p()
-        check(self._fn['masks'](self.h, C.byref(m1), C.byref(m2)))
+        check(self._call('masks')(self.h, C.byref(m1), C.byref(m2)))
         U = int(self.config['hidden_units'])
         out = []
         for m in (m1, m2):
@@ -934,14 +1007,14 @@ class DeviceSimTrainer(object):
         """Forward + loss + backward; returns the mean loss (device scalar tensor)."""
         N, labels, sp = self._batch(dense, cat, labels, seqs)
         loss = torch.empty(1, dtype=torch.float32, device=self.device)
-        check(self._fn['grad'](self.h, N, _ptr(dense), _ptr(cat), sp, _ptr(labels), dropout_rate, seed, step,
+        check(self._call('grad')(self.h, N, _ptr(dense), _ptr(cat), sp, _ptr(labels), dropout_rate, seed, step,
                                            _ptr(loss), _stream()))
         return loss
 
     def step(self, dense, cat, labels, seqs=None, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-7, dropout_rate=0.2, seed=0):
         N, labels, sp = self._batch(dense, cat, labels, seqs)
         loss = torch.empty(1, dtype=torch.float32, device=self.device)
-        check(self._fn['step'](self.h, N, _ptr(dense), _ptr(cat), sp, _ptr(labels), lr, beta1, beta2, eps,
+        check(self._call('step')(self.h, N, _ptr(dense), _ptr(cat), sp, _ptr(labels), lr, beta1, beta2, eps,
                                            dropout_rate, seed, self.iteration, _ptr(loss), _stream()))
         self.iteration += 1
         return loss
@@ -954,6 +1027,7 @@ DIENTRAIN_SEQ = ('gru%d_gate_w', 'gru%d_gate_b', 'gru%d_cand_w', 'gru%d_cand_b',
 
 class DeviceDienTrainer(DeviceSimTrainer):
     """rl4rs_dientrain handle: supervised training of the DIEN simulator on the device (same interface as DeviceSimTrainer)."""
+    _prefix = 'rl4rs_dientrain_'
 
     def __init__(self, config, weights, max_batch=256, device=None):
         _lib.require_device()
@@ -986,8 +1060,6 @@ class DeviceDienTrainer(DeviceSimTrainer):
             check(self.lib.rl4rs_dientrain_create(C.byref(cfg), C.byref(w), self.max_batch, _stream(), C.byref(h)))
         self.h = h
         self.iteration = 0
-        self._fn = dict(destroy=self.lib.rl4rs_dientrain_destroy, params=self.lib.rl4rs_dientrain_params,
-                        masks=self.lib.rl4rs_dientrain_masks, grad=self.lib.rl4rs_dientrain_grad, step=self.lib.rl4rs_dientrain_step)
 
 
 class DeviceRawPolicy(object):
@@ -1085,10 +1157,11 @@ def _alias_f32(ptr, count, device, owner):
     return t
 
 
-class DeviceRawTrainer(DeviceRawPolicy):
+class DeviceRawTrainer(_FlatNet, DeviceRawPolicy):
     """rl4rs_rawtrain handle: the raw-state policy with A2C / PPO loss, backward and Adam on the device."""
     A2C, PPO = 0, 1
     ORDER = ('cat_emb', 'seq_emb', 'dense_w1', 'dense_b1', 'dense_w2', 'dense_b2', 'ctx_w', 'ctx_b', 'head_w', 'head_b')
+    _prefix = 'rl4rs_rawtrain_'         # weights(): head_w = [out_w | value_w], head_b = [out_b | value_b]
 
     def __init__(self, config, weights, max_rows, device=None):
         _lib.require_device()
@@ -1115,39 +1188,11 @@ class DeviceRawTrainer(DeviceRawPolicy):
                        ('dense_b2', (U,)), ('ctx_w', (self.S * E + U + E, 256)), ('ctx_b', (256,)), ('head_w', (256, self.A + 1)),
                        ('head_b', (self.A + 1,))]
 
-    def close(self):
-        if getattr(self, 'h', None) is not None and self.h:
-            self.lib.rl4rs_rawtrain_destroy(self.h)
-            self.h = None
-
-    def _flat(self, which):
-        p, g, n = C.c_void_p(), C.c_void_p(), C.c_int64()
-        check(self.lib.rl4rs_rawtrain_params(self.h, C.byref(p), C.byref(g), C.byref(n)))
-        out = torch.empty(n.value, dtype=torch.float32, device=self.device)
-        check(self.lib.rl4rs_copy_d2d(_ptr(out), p if which == 'params' else g, n.value * 4, _stream()))
-        return out
-
-    def _split(self, flat):
-        out, o = {}, 0
-        for name, shape in self.shapes:
-            k = int(np.prod(shape))
-            out[name] = flat[o:o + k].reshape(shape)
-            o += k
-        return out
-
-    def weights(self):
-        """head_w = [out_w | value_w], head_b = [out_b | value_b]."""
-        return self._split(self._flat('params'))
-
-    def gradients(self):
-        return self._split(self._flat('grad'))
-
     def flat_view(self, which):
         """ZERO-COPY torch view of the handle's flat parameter ('params') or gradient ('grad') buffer: a data-parallel trainer
         all-reduces the gradient in place between loss_grad and adam_step, and broadcasts the parameters at start."""
-        p, g, n = C.c_void_p(), C.c_void_p(), C.c_int64()
-        check(self.lib.rl4rs_rawtrain_params(self.h, C.byref(p), C.byref(g), C.byref(n)))
-        return _alias_f32((p if which == 'params' else g).value, n.value, self.device, self)
+        p, g, n = self._ptrs()
+        return _alias_f32((p if which == 'params' else g).value, n, self.device, self)
 
     def table_rows(self):
         """(offset, rows, width) of the two embedding tables inside the flat buffers (cat_emb, seq_emb come first)."""
@@ -1246,9 +1291,10 @@ def vtrace(behaviour_logp, target_logp, values, rewards, bootstrap_value=None, d
     return vs, pg, stats
 
 
-class DevicePolicy(object):
+class DevicePolicy(_FlatNet):
     """rl4rs_policy handle: action-masked policy net (rllib_mask_model.py:7-64) with flat parameters."""
     A2C, PPO = 0, 1
+    _prefix = 'rl4rs_policy_'
 
     def __init__(self, obs_dim, hidden, action_size, max_rows, params=None, seed=0, device=None):
         _lib.require_device()
@@ -1278,36 +1324,11 @@ class DevicePolicy(object):
             raise ValueError("unknown policy option %r; known: %s" % (name, sorted(_lib.POLICY_OPTS)))
         check(self.lib.rl4rs_policy_set_option(self.h, _lib.POLICY_OPTS[name], int(value)))
 
-    def close(self):
-        if getattr(self, 'h', None) is not None and self.h:
-            self.lib.rl4rs_policy_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def params(self, out=None):
-        """Copy of the flat parameter buffer (device tensor); ``out``: a contiguous float32 device tensor to copy into."""
-        p = C.c_void_p()
-        n = C.c_int32()
+    def _ptrs(self):
+        """rl4rs_policy_params has no gradient pointer (the gradient is the caller's buffer) and an int32 count"""
+        p, n = C.c_void_p(), C.c_int32()
         check(self.lib.rl4rs_policy_params(self.h, C.byref(p), C.byref(n)))
-        if out is None:
-            out = torch.empty(n.value, dtype=torch.float32, device=self.device)
-        assert out.dtype == torch.float32 and out.numel() == n.value and out.is_contiguous() and out.is_cuda
-        check(self.lib.rl4rs_copy_d2d(_ptr(out), p, n.value * 4, _stream()))
-        return out
-
-    def set_params(self, flat):
-        p = C.c_void_p()
-        n = C.c_int32()
-        check(self.lib.rl4rs_policy_params(self.h, C.byref(p), C.byref(n)))
-        flat = flat.to(device=self.device, dtype=torch.float32).contiguous()
-        assert flat.numel() == n.value
-        check(self.lib.rl4rs_copy_d2d(p, _ptr(flat), n.value * 4, _stream()))
-        self._keep = flat
+        return p, None, n.value
 
     def _mask(self, mask_bits, N):
         if mask_bits is None:
@@ -1449,11 +1470,9 @@ class DevicePolicy(object):
 
     def copy_params_from(self, other):
         """This handle's parameters <- ``other``'s, a device-to-device copy (IMPALA's learner -> actor broadcast)."""
-        src, dst, n = C.c_void_p(), C.c_void_p(), C.c_int32()
-        check(self.lib.rl4rs_policy_params(other.h, C.byref(src), C.byref(n)))
-        assert n.value == self.n_params
-        check(self.lib.rl4rs_policy_params(self.h, C.byref(dst), C.byref(n)))
-        check(self.lib.rl4rs_copy_d2d(dst, src, self.n_params * 4, _stream()))
+        src, _, n = other._ptrs()
+        assert n == self.n_params
+        check(self.lib.rl4rs_copy_d2d(self._ptrs()[0], src, n * 4, _stream()))
 
     def greedy(self, obs, mask_bits=None, want_q=False, out=None):
         """First maximum of the masked Q row (rl4rs_policy_greedy) -> (actions int32 [N], masked Q [N, A] or None)."""
@@ -1488,28 +1507,6 @@ class DevicePolicy(object):
 
     PASS_TIMEOUT_MESSAGE = ("the persistent PPO pass timed out at a grid barrier (workgroups not co-resident: the GPU is shared or "
                             "partitioned); the pass is incomplete - use DevicePolicy.set_option('ppo_fused', 0) for the per-minibatch kernels")
-
-    def adam_state(self):
-        """(m, v) copies of the Adam moments and the step counter."""
-        m, v, t = C.c_void_p(), C.c_void_p(), C.c_int64()
-        check(self.lib.rl4rs_policy_adam_state(self.h, C.byref(m), C.byref(v), C.byref(t)))
-        om = torch.empty(self.n_params, dtype=torch.float32, device=self.device)
-        ov = torch.empty(self.n_params, dtype=torch.float32, device=self.device)
-        check(self.lib.rl4rs_copy_d2d(_ptr(om), m, self.n_params * 4, _stream()))
-        check(self.lib.rl4rs_copy_d2d(_ptr(ov), v, self.n_params * 4, _stream()))
-        return om, ov, int(t.value)
-
-    def set_adam_state(self, m, v, step):
-        pm, pv, t = C.c_void_p(), C.c_void_p(), C.c_int64()
-        check(self.lib.rl4rs_policy_adam_state(self.h, C.byref(pm), C.byref(pv), C.byref(t)))
-        m = m.to(device=self.device, dtype=torch.float32).contiguous()
-        v = v.to(device=self.device, dtype=torch.float32).contiguous()
-        assert m.numel() == self.n_params and v.numel() == self.n_params
-        check(self.lib.rl4rs_copy_d2d(pm, _ptr(m), self.n_params * 4, _stream()))
-        check(self.lib.rl4rs_copy_d2d(pv, _ptr(v), self.n_params * 4, _stream()))
-        check(self.lib.rl4rs_policy_set_adam_step(self.h, int(step)))
-        self._keep_adam = (m, v)
-
 
 class DeviceReplay(object):
     """rl4rs_replay handle: a ring of whole rollouts on the device with uniform / proportional-prioritized sampling."""
@@ -1618,10 +1615,11 @@ class DeviceReplay(object):
         return float(self.column('max_priority').cpu()[0])
 
 
-class DeviceDistQ(object):
+class DeviceDistQ(_FlatNet):
     """rl4rs_distq handle: the dueling distributional (C51) Q network of Rainbow with flat parameters
     W1, b1, W2, b2, Wa1, ba1, Wa2, ba2 [, Wv1, bv1, Wv2, bv2] (include/rl4rs_hip.h, "On-device Rainbow").  RLlib parity is
     unpinned (ray is absent).  ``params``: flat float32 host array, default ``init_distq_params(..., seed)``."""
+    _prefix = 'rl4rs_distq_'
 
     def __init__(self, obs_dim, action_size, max_rows, num_atoms=8, v_min=0.0, v_max=1000.0, dueling=True, trunk=256, stream_hidden=128,
                  params=None, seed=0, device=None):
@@ -1647,41 +1645,6 @@ class DeviceDistQ(object):
             check(self.lib.rl4rs_distq_create(C.byref(self.cfg), params.ctypes.data_as(C.c_void_p), _stream(), C.byref(h)))
         self.h = h
         self.W = (self.action_size + 31) // 32
-
-    def close(self):
-        if getattr(self, 'h', None) is not None and self.h:
-            self.lib.rl4rs_distq_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _params_ptr(self):
-        p, n = C.c_void_p(), C.c_int64()
-        check(self.lib.rl4rs_distq_params(self.h, C.byref(p), None, C.byref(n)))
-        return p, n.value
-
-    def params(self, out=None):
-        """Copy of the flat parameter buffer (device tensor); ``out``: a contiguous float32 device tensor to copy into."""
-        p, n = self._params_ptr()
-        if out is None:
-            out = torch.empty(n, dtype=torch.float32, device=self.device)
-        assert out.dtype == torch.float32 and out.numel() == n and out.is_contiguous() and out.is_cuda
-        check(self.lib.rl4rs_copy_d2d(_ptr(out), p, n * 4, _stream()))
-        return out
-
-    def set_params(self, flat):
-        p, n = self._params_ptr()
-        flat = flat.to(device=self.device, dtype=torch.float32).contiguous()
-        assert flat.numel() == n
-        check(self.lib.rl4rs_copy_d2d(p, _ptr(flat), n * 4, _stream()))
-        self._keep = flat
-
-    def copy_from(self, other):
-        check(self.lib.rl4rs_distq_copy_params(self.h, other.h, _stream()))
 
     def _mask(self, mask_bits, N):
         if mask_bits is None:
@@ -1739,28 +1702,6 @@ class DeviceDistQ(object):
         """Adam with every variable clipped by its own norm (rl4rs_distq_adam_step_clip_by_var)."""
         check(self.lib.rl4rs_distq_adam_step_clip_by_var(self.h, _ptr(grad), lr, beta1, beta2, eps, var_clip, _stream()))
 
-    def adam_state(self):
-        """(m, v) copies of the Adam moments and the step counter."""
-        m, v, t = C.c_void_p(), C.c_void_p(), C.c_int64()
-        check(self.lib.rl4rs_distq_adam_state(self.h, C.byref(m), C.byref(v), C.byref(t)))
-        om = torch.empty(self.n_params, dtype=torch.float32, device=self.device)
-        ov = torch.empty(self.n_params, dtype=torch.float32, device=self.device)
-        check(self.lib.rl4rs_copy_d2d(_ptr(om), m, self.n_params * 4, _stream()))
-        check(self.lib.rl4rs_copy_d2d(_ptr(ov), v, self.n_params * 4, _stream()))
-        return om, ov, int(t.value)
-
-    def set_adam_state(self, m, v, step):
-        pm, pv, t = C.c_void_p(), C.c_void_p(), C.c_int64()
-        check(self.lib.rl4rs_distq_adam_state(self.h, C.byref(pm), C.byref(pv), C.byref(t)))
-        m = m.to(device=self.device, dtype=torch.float32).contiguous()
-        v = v.to(device=self.device, dtype=torch.float32).contiguous()
-        assert m.numel() == self.n_params and v.numel() == self.n_params
-        check(self.lib.rl4rs_copy_d2d(pm, _ptr(m), self.n_params * 4, _stream()))
-        check(self.lib.rl4rs_copy_d2d(pv, _ptr(v), self.n_params * 4, _stream()))
-        check(self.lib.rl4rs_distq_set_adam_step(self.h, int(step)))
-        self._keep_adam = (m, v)
-
-
 class DeviceContiReplay(DeviceReplay):
     """The same ring for the continuous-action env (rl4rs_replay_create_conti): ``DeviceReplay``'s methods with a float32 action
     column [act_dim] (``column('action')``) and no mask column.  The handle refuses the discrete push / sample."""
@@ -1816,10 +1757,11 @@ class DeviceContiReplay(DeviceReplay):
         return b
 
 
-class DeviceQNet(object):
+class DeviceQNet(_FlatNet):
     """rl4rs_qnet handle: one offline-RL network (the reference's ``CustomVectorEncoder`` of rl4rs/nets/cql/encoder.py:9-67,
     or d3rlpy's plain ``VectorEncoder``, + d3rlpy's Linear head) with forward, backward and torch-style Adam on the device.
     ``params``: dict of float32 arrays stored [in, out]: fc1_w, fc1_b, (emb,) fc2_w, fc2_b, head_w, head_b."""
+    _prefix = 'rl4rs_qnet_'
 
     def __init__(self, obs_dim, action_size, params, mask_size=0, emb_size=32, hidden1=256, hidden2=256, location_mask=None,
                  special_items=None, max_rows=256, device=None):
@@ -1860,81 +1802,6 @@ class DeviceQNet(object):
                                              sp.ctypes.data_as(C.c_void_p) if sp is not None else None, _stream(), C.byref(h)))
         self.h = h
         self.n_params = int(flat.size)
-
-    def close(self):
-        if getattr(self, 'h', None) is not None and self.h:
-            self.lib.rl4rs_qnet_destroy(self.h)
-            self.h = None
-
-    __del__ = close
-
-    def _buffers(self):
-        p, g, n = C.c_void_p(), C.c_void_p(), C.c_int64()
-        check(self.lib.rl4rs_qnet_params(self.h, C.byref(p), C.byref(g), C.byref(n)))
-        return p, g, n.value
-
-    def _flat(self, which):
-        p, g, n = self._buffers()
-        out = torch.empty(n, dtype=torch.float32, device=self.device)
-        check(self.lib.rl4rs_copy_d2d(_ptr(out), p if which == 'params' else g, n * 4, _stream()))
-        return out
-
-    def _split(self, flat):
-        out, o = {}, 0
-        for name, shape in self.shapes:
-            k = int(np.prod(shape))
-            out[name] = flat[o:o + k].reshape(shape)
-            o += k
-        return out
-
-    def weights(self):
-        return self._split(self._flat('params'))
-
-    def gradients(self):
-        return self._split(self._flat('grad'))
-
-    def flat_gradient(self):
-        return self._flat('grad')
-
-    def set_flat_gradient(self, flat):
-        _, g, n = self._buffers()
-        assert flat.numel() == n and flat.dtype == torch.float32 and flat.is_contiguous()
-        check(self.lib.rl4rs_copy_d2d(g, _ptr(flat), n * 4, _stream()))
-
-    _PREFIX = 'rl4rs_qnet'
-
-    def flat_params(self):
-        return self._flat('params')
-
-    def set_flat_params(self, flat):
-        p, _, n = self._buffers()
-        assert flat.numel() == n and flat.dtype == torch.float32 and flat.is_contiguous()
-        check(self.lib.rl4rs_copy_d2d(p, _ptr(flat), n * 4, _stream()))
-
-    def adam_state(self):
-        """(m, v, step): copies of the Adam moments and the step count (checkpointing)."""
-        pm, pv, t = C.c_void_p(), C.c_void_p(), C.c_int64()
-        check(getattr(self.lib, self._PREFIX + '_adam_state')(self.h, C.byref(pm), C.byref(pv), C.byref(t)))
-        n = self.n_params
-        m = torch.empty(n, dtype=torch.float32, device=self.device)
-        v = torch.empty(n, dtype=torch.float32, device=self.device)
-        check(self.lib.rl4rs_copy_d2d(_ptr(m), pm, n * 4, _stream()))
-        check(self.lib.rl4rs_copy_d2d(_ptr(v), pv, n * 4, _stream()))
-        return m, v, int(t.value)
-
-    def set_adam_state(self, m, v, step):
-        pm, pv, t = C.c_void_p(), C.c_void_p(), C.c_int64()
-        check(getattr(self.lib, self._PREFIX + '_adam_state')(self.h, C.byref(pm), C.byref(pv), C.byref(t)))
-        n = self.n_params
-        m = m.to(device=self.device, dtype=torch.float32).contiguous()
-        v = v.to(device=self.device, dtype=torch.float32).contiguous()
-        assert m.numel() == n and v.numel() == n
-        check(self.lib.rl4rs_copy_d2d(pm, _ptr(m), n * 4, _stream()))
-        check(self.lib.rl4rs_copy_d2d(pv, _ptr(v), n * 4, _stream()))
-        check(getattr(self.lib, self._PREFIX + '_set_adam_step')(self.h, int(step)))
-
-    def copy_from(self, other):
-        check(self.lib.rl4rs_qnet_copy_params(self.h, other.h, _stream()))
 
     def check_status(self):
         flags = C.c_int32(0)
@@ -1999,7 +1866,7 @@ class DeviceQNet(object):
         return out
 
 
-class DeviceAMLP(object):
+class DeviceAMLP(_FlatNet):
     """rl4rs_amlp handle: d3rlpy's default continuous-control network - ``VectorEncoderWithAction([256, 256], relu)`` on
     ``cat([x, action])`` (``act_dim = 0``: plain ``VectorEncoder``) + one Linear head - with forward, backward (parameter and
     action-input gradients) and torch-style Adam on the device.  ``params``: dict of float32 arrays stored [in, out]:
@@ -2007,6 +1874,7 @@ class DeviceAMLP(object):
     ``head_act``: 'none' or 'tanh'.  The building block of the continuous BCQ / CQL learners (``offline_rl.BCQ`` / ``CQL``)."""
 
     HEAD_ACTS = {'none': 0, 'elu': 1, 'sigmoid': 2, 'tanh': 3, 'relu': 4}
+    _prefix = 'rl4rs_amlp_'
 
     def __init__(self, obs_dim, act_dim, out_dim, params, hidden1=256, hidden2=256, head_act='none', max_rows=256, max_grad_rows=None,
                  device=None):
@@ -2032,81 +1900,6 @@ class DeviceAMLP(object):
         self.h = h
         self.n_params = int(flat.size)
         self.h16_ok = bool(self.lib.rl4rs_amlp_h16_ok(self.h))
-
-    def close(self):
-        if getattr(self, 'h', None) is not None and self.h:
-            self.lib.rl4rs_amlp_destroy(self.h)
-            self.h = None
-
-    __del__ = close
-
-    def _buffers(self):
-        p, g, n = C.c_void_p(), C.c_void_p(), C.c_int64()
-        check(self.lib.rl4rs_amlp_params(self.h, C.byref(p), C.byref(g), C.byref(n)))
-        return p, g, n.value
-
-    def _flat(self, which):
-        p, g, n = self._buffers()
-        out = torch.empty(n, dtype=torch.float32, device=self.device)
-        check(self.lib.rl4rs_copy_d2d(_ptr(out), p if which == 'params' else g, n * 4, _stream()))
-        return out
-
-    def _split(self, flat):
-        out, o = {}, 0
-        for name, shape in self.shapes:
-            k = int(np.prod(shape))
-            out[name] = flat[o:o + k].reshape(shape)
-            o += k
-        return out
-
-    def weights(self):
-        return self._split(self._flat('params'))
-
-    def gradients(self):
-        return self._split(self._flat('grad'))
-
-    def flat_gradient(self):
-        return self._flat('grad')
-
-    def flat_params(self):
-        return self._flat('params')
-
-    def set_flat_gradient(self, flat):
-        _, g, n = self._buffers()
-        assert flat.numel() == n and flat.dtype == torch.float32 and flat.is_contiguous()
-        check(self.lib.rl4rs_copy_d2d(g, _ptr(flat), n * 4, _stream()))
-
-    def set_flat_params(self, flat):
-        p, _, n = self._buffers()
-        assert flat.numel() == n and flat.dtype == torch.float32 and flat.is_contiguous()
-        check(self.lib.rl4rs_copy_d2d(p, _ptr(flat), n * 4, _stream()))
-
-    _PREFIX = 'rl4rs_amlp'
-
-    def adam_state(self):
-        """(m, v, step): copies of the Adam moments and the step count (checkpointing)."""
-        pm, pv, t = C.c_void_p(), C.c_void_p(), C.c_int64()
-        check(getattr(self.lib, self._PREFIX + '_adam_state')(self.h, C.byref(pm), C.byref(pv), C.byref(t)))
-        n = self.n_params
-        m = torch.empty(n, dtype=torch.float32, device=self.device)
-        v = torch.empty(n, dtype=torch.float32, device=self.device)
-        check(self.lib.rl4rs_copy_d2d(_ptr(m), pm, n * 4, _stream()))
-        check(self.lib.rl4rs_copy_d2d(_ptr(v), pv, n * 4, _stream()))
-        return m, v, int(t.value)
-
-    def set_adam_state(self, m, v, step):
-        pm, pv, t = C.c_void_p(), C.c_void_p(), C.c_int64()
-        check(getattr(self.lib, self._PREFIX + '_adam_state')(self.h, C.byref(pm), C.byref(pv), C.byref(t)))
-        n = self.n_params
-        m = m.to(device=self.device, dtype=torch.float32).contiguous()
-        v = v.to(device=self.device, dtype=torch.float32).contiguous()
-        assert m.numel() == n and v.numel() == n
-        check(self.lib.rl4rs_copy_d2d(pm, _ptr(m), n * 4, _stream()))
-        check(self.lib.rl4rs_copy_d2d(pv, _ptr(v), n * 4, _stream()))
-        check(getattr(self.lib, self._PREFIX + '_set_adam_step')(self.h, int(step)))
-
-    def copy_from(self, other):
-        check(self.lib.rl4rs_amlp_copy_params(self.h, other.h, _stream()))
 
     def soft_update_from(self, other, tau):
         check(self.lib.rl4rs_amlp_soft_update(self.h, other.h, tau, _stream()))
@@ -2392,70 +2185,6 @@ def amlp_add_l2(net, l2):
     check(_lib.load().rl4rs_amlp_add_l2(net.h, float(l2), _stream()))
 
 
-class _FlatNet(object):
-    """Shared plumbing of the rl4rs_exactk / rl4rs_exactk_critic handles: flat parameters, gradient and Adam state."""
-    _prefix = None
-
-    def _call(self, name):
-        return getattr(self.lib, self._prefix + name)
-
-    def close(self):
-        if getattr(self, 'h', None) is not None and self.h:
-            self._call('destroy')(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _ptrs(self):
-        p, g, n = C.c_void_p(), C.c_void_p(), C.c_int64()
-        check(self._call('params')(self.h, C.byref(p), C.byref(g), C.byref(n)))
-        return p, g, n.value
-
-    def _copy_out(self, src, n, out):
-        if out is None:
-            out = torch.empty(n, dtype=torch.float32, device=self.device)
-        assert out.dtype == torch.float32 and out.numel() == n and out.is_contiguous() and out.is_cuda
-        check(self.lib.rl4rs_copy_d2d(_ptr(out), src, n * 4, _stream()))
-        return out
-
-    def params(self, out=None):
-        """Copy of the flat parameter buffer (device tensor)."""
-        p, _, n = self._ptrs()
-        return self._copy_out(p, n, out)
-
-    def grad(self, out=None):
-        """Copy of the flat gradient of the last loss_grad (device tensor)."""
-        _, g, n = self._ptrs()
-        return self._copy_out(g, n, out)
-
-    def set_params(self, flat):
-        p, _, n = self._ptrs()
-        flat = flat.to(device=self.device, dtype=torch.float32).contiguous()
-        assert flat.numel() == n
-        check(self.lib.rl4rs_copy_d2d(p, _ptr(flat), n * 4, _stream()))
-        self._keep = flat
-
-    def adam_state(self):
-        """(m, v, step): copies of the Adam moments (device tensors) and the step counter - what a checkpoint keeps."""
-        m, v, t = C.c_void_p(), C.c_void_p(), C.c_int64()
-        check(self._call('adam_state')(self.h, C.byref(m), C.byref(v), C.byref(t)))
-        return self._copy_out(m, self.n_params, None), self._copy_out(v, self.n_params, None), int(t.value)
-
-    def set_adam_state(self, m, v, step):
-        pm, pv, t = C.c_void_p(), C.c_void_p(), C.c_int64()
-        check(self._call('adam_state')(self.h, C.byref(pm), C.byref(pv), C.byref(t)))
-        for dst, src in ((pm, m), (pv, v)):
-            src = src.to(device=self.device, dtype=torch.float32).contiguous()
-            assert src.numel() == self.n_params
-            check(self.lib.rl4rs_copy_d2d(dst, _ptr(src), self.n_params * 4, _stream()))
-            wait_stream()
-        check(self._call('set_adam_step')(self.h, int(step)))
-
-
 class DeviceExactK(_FlatNet):
     """rl4rs_exactk handle: Exact-K's pointer-network slate generator (include/rl4rs_hip.h, "On-device Exact-K"; flat layout in
     ``rl4rs_amd/nets/exactk.py``).  One shared candidate list 0..action_size-1.  Dropout is on in every call, as in the reference,
@@ -2626,13 +2355,6 @@ class DeviceDynamics(_FlatNet):
                                             C.byref(h)))
         self.h = h
 
-    # the names _ModelIO and the data-parallel helpers use
-    flat_params = _FlatNet.params
-    flat_gradient = _FlatNet.grad
-
-    def set_flat_params(self, flat):
-        self.set_params(flat)
-
     def _state_ptrs(self):
         s, n, t, nt = C.c_void_p(), C.c_int64(), C.c_void_p(), C.c_int64()
         check(self.lib.rl4rs_dyn_state(self.h, C.byref(s), C.byref(n), C.byref(t), C.byref(nt)))
@@ -2645,10 +2367,7 @@ class DeviceDynamics(_FlatNet):
 
     def set_state(self, flat):
         s, n, _, _ = self._state_ptrs()
-        flat = flat.to(device=self.device, dtype=torch.float32).contiguous()
-        assert flat.numel() == n
-        check(self.lib.rl4rs_copy_d2d(s, _ptr(flat), n * 4, _stream()))
-        wait_stream()
+        self._copy_in('state', s, n, flat)
 
     def stats(self):
         """Copy of the last forward's statistics [members, 3 + 2 H1 + 2 H2]: sigma, batch mean / biased variance of both layers."""
