@@ -1198,6 +1198,58 @@ typedef struct rl4rs_cql_step {
 int64_t rl4rs_cql_workspace_floats(int32_t B, int32_t n, int32_t A);
 int rl4rs_cql_update(const rl4rs_cql_step* step, void* stream);
 
+/* COMBO (d3rlpy.algos.COMBO, 'COMBO' of script/batchrl_trainer.py:130-151: SAC + a conservative critic term over a minibatch of
+ * n_real real rows followed by F = B - n_real model-generated rows; d3rlpy absent, PARITY UNPINNED).  The critic step runs two
+ * passes through the twin critics: pass T = the B rows (s, a) (rep = 1), pass C = the F * k sample rows of the generated
+ * observations (k = 3 n_action_samples, rep = k); csrc/combo.hpp says why.
+ * amlp_grad_stash: the join of the two passes (rl4rs_amlp_backward WRITES a handle's flat gradient).  For n <= 4 handles in ONE
+ * launch: mode 0 copies each handle's flat gradient to bufs_dev[i] (its parameter count floats), mode 1 adds bufs_dev[i] into it. */
+int rl4rs_amlp_grad_stash(int32_t n, rl4rs_amlp* const* nets, float* const* bufs_dev, int32_t mode, void* stream);
+/* combo_critic_loss: both gradient sets and the six sums of the critic loss
+ *     sum_c mean_b (q_c[b] - y_b)^2 + w [ sum_c mean_f logsumexp_j (q_c[f,j] - offs[f,j]) - sum_c mean_{b < n_real} q_c[b] ].
+ *   pass-T half  q*t_dev, y_dev [B] -> dq*t_dev [B] = 2 (q - y) / B - [b < n_real] w / n_real   (one thread per row)
+ *   pass-C half  q*c_dev, offs_dev [F, k] -> dq*c_dev [F, k] = (w / F) softmax_j                  (one wave per generated row)
+ *   sums6_dev = {sum_b (q1 - y)^2, same for q2, sum_f logsumexp for q1, for q2, sum_{b < n_real} q1, same for q2}, reduced in a
+ *   fixed order (no atomics) from rows_scratch_dev [4 B + 2 F].
+ * Either half may be left out by passing ALL of its pointers NULL: a forward of pass C overwrites the activations pass T's backward
+ * needs, so an update calls the T half after forward T and the C half after forward C with the SAME rows_scratch_dev; the sums are
+ * written by the call that has the C half.  w_dev: the conservative weight, a device scalar.  n_real <= 0, n_real >= B and k < 1
+ * are refused (d3rlpy's mean over an empty half is NaN), each with its own message, before anything touches a device. */
+int rl4rs_combo_critic_loss(int32_t B, int32_t n_real, int32_t k, const float* q1t_dev, const float* q2t_dev, const float* y_dev,
+                            const float* q1c_dev, const float* q2c_dev, const float* offs_dev, const float* w_dev, float* dq1t_dev,
+                            float* dq2t_dev, float* dq1c_dev, float* dq2c_dev, float* rows_scratch_dev, float* sums6_dev, void* stream);
+/* One whole COMBO update as ONE host call: target, critic step (forward T, backward T, stash, forward C, backward C, add, Adam) and,
+ * when do_actor (total_step % update_actor_interval == 0), the SAC actor step, the temperature step on the STEPPED policy and the
+ * soft critic-target update - the sequence rl4rs_amd/offline_rl.py::COMBO.update issues.  Single-process only.  Rows 0 .. n_real - 1
+ * of the five transition columns are real, the rest generated.
+ *   log_temp_dev   device float[3] = {value, Adam m, Adam v}; temp_step = the number of its Adam steps so far (host)
+ *   normal_dev     N(0, 1), 16-byte aligned: eps_t [F n, A] | eps_tp1 [F n, A] | eps_actor [B, A] | eps_temp [B, A]
+ *   uniform_dev    U[-1, 1): [F, n, A]
+ *   rew_dev        rewards as the critic sees them (the caller applies the reward scaler)
+ *   stash_dev      2 * round_up(critic parameter count, 4) floats, 16-byte aligned: pass T's gradients while pass C runs
+ *   workspace_dev  rl4rs_combo_workspace_floats(B, n_real, n, A) floats (-1: bad sizes), 16-byte aligned
+ *   metrics_dev    float[4] = {critic loss, actor loss, temp loss, conservative term} (entries of skipped phases are left alone)
+ * Refused with a message each, before any device is needed: n_real <= 0, n_real >= B, n < 1, a null handle, a misaligned workspace. */
+typedef struct rl4rs_combo_step {
+    rl4rs_amlp *policy, *q1, *q2, *q1_targ, *q2_targ;
+    int32_t B, n_real, n, A;
+    float gamma, tau, actor_lr, critic_lr, temp_lr, conservative_weight;
+    int32_t do_actor, reserved;
+    int64_t temp_step;
+    float* log_temp_dev;
+    const float *obs_dev, *act_dev, *rew_dev, *nxt_dev, *ter_dev;
+    const float* normal_dev;
+    const float* uniform_dev;
+    float* stash_dev;
+    float* workspace_dev;
+    float* metrics_dev;
+} rl4rs_combo_step;
+int64_t rl4rs_combo_workspace_floats(int32_t B, int32_t n_real, int32_t n, int32_t A);
+/* where the last update left its target y [B] (what = 0) and the six sums of rl4rs_combo_critic_loss (what = 1): offsets in floats
+ * into workspace_dev (tests, tools); -1: bad sizes / what */
+int64_t rl4rs_combo_workspace_offset(int32_t B, int32_t n_real, int32_t n, int32_t A, int32_t what);
+int rl4rs_combo_update(const rl4rs_combo_step* step, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * On-device TD3 / DDPG on the continuous-action env: script/modelfree_train.py:46-48,79-105 (algo "TD3" / "DDPG" with
  * support_conti_env; rl4rs/env/base.py:214-215 Box(-1, 1) of action_emb_size values, resolved by the env's masked K-NN).  RLlib

@@ -130,6 +130,17 @@ class CqlStep(C.Structure):
                                            'uniform_dev', 'workspace_dev', 'metrics_dev')])
 
 
+class ComboStep(C.Structure):
+    """rl4rs_combo_step (include/rl4rs_hip.h)"""
+    _fields_ = ([(n, C.c_void_p) for n in ('policy', 'q1', 'q2', 'q1_targ', 'q2_targ')] +
+                [(n, C.c_int32) for n in ('B', 'n_real', 'n', 'A')] +
+                [(n, C.c_float) for n in ('gamma', 'tau', 'actor_lr', 'critic_lr', 'temp_lr', 'conservative_weight')] +
+                [(n, C.c_int32) for n in ('do_actor', 'reserved')] +
+                [('temp_step', C.c_int64)] +
+                [(n, C.c_void_p) for n in ('log_temp_dev', 'obs_dev', 'act_dev', 'rew_dev', 'nxt_dev', 'ter_dev', 'normal_dev', 'uniform_dev',
+                                           'stash_dev', 'workspace_dev', 'metrics_dev')])
+
+
 class RawPolicyCfg(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         'maxlen', 'emb_size', 'hidden_units', 'dense_feature_num', 'category_feature_num', 'category_hash_size',
@@ -303,6 +314,11 @@ SIGNATURES = {
     'rl4rs_cql_workspace_floats': (_I64, [_I32, _I32, _I32]),
     'rl4rs_cql_update': (_I, [C.POINTER(CqlStep), _P]),
     'rl4rs_bcq_workspace_floats': (_I64, [_I32, _I32, _I32, _I32]),
+    'rl4rs_amlp_grad_stash': (_I, [_I32, _P, _P, _I32, _P]),
+    'rl4rs_combo_critic_loss': (_I, [_I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    'rl4rs_combo_workspace_floats': (_I64, [_I32, _I32, _I32, _I32]),
+    'rl4rs_combo_workspace_offset': (_I64, [_I32, _I32, _I32, _I32, _I32]),
+    'rl4rs_combo_update': (_I, [C.POINTER(ComboStep), _P]),
     'rl4rs_bcq_update': (_I, [C.POINTER(BcqStep), _P]),
     'rl4rs_amlp_forward_multi': (_I, [_I32, C.POINTER(_P), _I32, _P, _P, C.POINTER(_P), _P]),
     'rl4rs_amlp_backward_multi': (_I, [_I32, C.POINTER(_P), _I32, _P, _P, C.POINTER(_P), C.POINTER(_P), _I32, _P]),

@@ -1041,3 +1041,5 @@ int rl4rs_cql_update(const rl4rs_cql_step* s, void* stream) {
 }
 
 }  // extern "C"
+
+#include "combo.hpp"

@@ -2125,6 +2125,42 @@ def cql_critic_loss(q1, q2, offs, m, y=None, alpha_w=None):
     return sums, dq1, dq2
 
 
+# ---- COMBO (csrc/combo.hpp) ------------------------------------------------------------------------------------------------------
+def amlp_grad_stash(nets, bufs, add=False):
+    """The join of two backward passes through the same handles (rl4rs_amlp_grad_stash; a backward WRITES the flat gradient): copy
+    each net's flat gradient to ``bufs[i]``, or with ``add`` add ``bufs[i]`` into it - one launch for up to 4 nets."""
+    lib = _lib.load()
+    for net, b in zip(nets, bufs):
+        assert b.is_cuda and b.dtype == torch.float32 and b.is_contiguous() and b.numel() >= net.n_params
+    H = (C.c_void_p * len(nets))(*[net.h for net in nets])
+    Bf = (C.c_void_p * len(nets))(*[_ptr(b) for b in bufs])
+    check(lib.rl4rs_amlp_grad_stash(len(nets), H, Bf, 1 if add else 0, _stream()))
+
+
+def combo_critic_loss(B, n_real, k, w, rows, t=None, c=None):
+    """COMBO's critic loss (rl4rs_combo_critic_loss) over a minibatch of ``n_real`` real rows then F = B - n_real generated ones.
+    ``t`` = (q1 [B], q2 [B], y [B]): the pass-T half -> (dq1, dq2).  ``c`` = (q1 [F * k], q2 [F * k], offs [F * k]): the pass-C half
+    -> (sums6, dq1, dq2); the sums count the T half of the LAST call that had one with the same ``rows`` [4 B + 2 F] (this call's,
+    when both halves are given: then -> (sums6, dq1t, dq2t, dq1c, dq2c)).  ``w``: the conservative weight, a one-element device tensor."""
+    lib = _lib.load()
+    F = B - n_real
+    assert rows.is_cuda and rows.dtype == torch.float32 and rows.is_contiguous() and rows.numel() >= 4 * B + 2 * max(F, 0)
+    tp, cp, out_t, out_c = [None] * 5, [None] * 5, (), ()
+    if t is not None:
+        assert all(x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.numel() == B for x in t)
+        out_t = (torch.empty_like(t[0]), torch.empty_like(t[1]))
+        tp = [_ptr(x) for x in tuple(t) + out_t]
+    sums = None
+    if c is not None:
+        assert all(x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.numel() == F * k for x in c)
+        out_c = (torch.empty_like(c[0]), torch.empty_like(c[1]))
+        cp = [_ptr(x) for x in tuple(c) + out_c]
+        sums = torch.empty(6, dtype=torch.float32, device=rows.device)
+    check(lib.rl4rs_combo_critic_loss(B, n_real, k, tp[0], tp[1], tp[2], cp[0], cp[1], cp[2], _ptr(w), tp[3], tp[4], cp[3], cp[4], _ptr(rows),
+                                      _ptr(sums), _stream()))
+    return out_t if c is None else (sums,) + out_t + out_c
+
+
 # ---- TD3 / DDPG (csrc/td3.hpp) ------------------------------------------------------------------------------------------------
 def explore_ou(det_action, ou_state, theta=0.15, sigma=0.2, scale=0.1, seed=0, step=0, random_phase=False, out=None, want_eps=False):
     """RLlib's OrnsteinUhlenbeckNoise on a deterministic action [N, E] (rl4rs_explore_ou): advances ``ou_state`` ([N, E], or [E] /

@@ -1011,8 +1011,9 @@ class MOPO(_ModelIO):
                                  max_rows=max_rows, max_grad_rows=grad_rows, device=device)
 
         self.policy = net(0, 2 * A, 0, max(B, self.predict_rows), B, heads=2)
-        self.q1 = net(A, 1, 1, B, B)
-        self.q2 = net(A, 1, 2, B, B)
+        critic_rows = self._critic_rows()
+        self.q1 = net(A, 1, 1, critic_rows, critic_rows)
+        self.q2 = net(A, 1, 2, critic_rows, critic_rows)
         self.q1_targ = net(A, 1, 1, B, 0)
         self.q2_targ = net(A, 1, 2, B, 0)
         self.q1_targ.copy_from(self.q1)
@@ -1023,6 +1024,16 @@ class MOPO(_ModelIO):
         self._gen = torch.Generator(device=self.device)
         self._gen.manual_seed(self.seed + 1000003 * rdist.rank())
         self.generated = GeneratedFIFO(generated_maxlen, self.device)
+
+    def _critic_rows(self):
+        """the most rows a critic sees in one forward / backward"""
+        return self.batch_size
+
+    def _rollout_due(self):
+        return self.total_step % self.rollout_interval == 0
+
+    def _update_minibatch(self, batch, n_real):
+        return self.update(*batch)
 
     def _randn(self, shape, given):
         if given is not None:
@@ -1108,10 +1119,10 @@ class MOPO(_ModelIO):
         assert real[1].dim() == 2 and real[1].shape[1] == self.A and real[1].dtype == torch.float32, 'continuous actions [N, %d] needed' % self.A
         hist = []
         for _ in range(n_steps):
-            if self.total_step % self.rollout_interval == 0:
+            if self._rollout_due():
                 self.generate_new_data(real[0])
-            batch, _ = mixed_minibatch(real, self.generated, self.batch_size, self.real_ratio, self._gen)
-            hist.append(self.update(*batch))
+            batch, n_real = mixed_minibatch(real, self.generated, self.batch_size, self.real_ratio, self._gen)
+            hist.append(self._update_minibatch(batch, n_real))
         out = {}
         for k in self._LOSS_KEYS:
             vals = [h[k] for h in hist if k in h]
@@ -1132,3 +1143,212 @@ class MOPO(_ModelIO):
     def close(self):
         for net in self.nets:
             net.close()
+
+
+class COMBO(MOPO):
+    """d3rlpy.algos.COMBO as 'COMBO' instantiates it (script/batchrl_trainer.py:130-151; the script passes batch_size=256, gamma=1.0,
+    update_actor_interval=2000, reward_scaler='standard'): SAC on default ``[256, 256]`` encoders - actor lr 1e-4, critic lr 3e-4,
+    temperature lr 1e-4, tau 0.005, two critics, initial temperature 1 - whose critic loss is TD + a conservative term, trained on
+    minibatches of ``n_real`` real rows followed by F = B - n_real rows generated by MOPO's rollouts with the reward NOT penalised:
+
+        TD            = sum_c mean_{b < B} (Q_c(s_b, a_b) - y_b)^2,  y_b = r_b + gamma (1 - ter_b) min_c Qtarg_c(s'_b, tanh(mu(s'_b)))
+        conservative  = w [ sum_c mean_{f generated} logsumexp_j (Q_c(s_f, a_fj) - off_fj) - sum_c mean_{b real} Q_c(s_b, a_b) ]
+
+    with CQL's 3n sampled actions per generated row (n of pi(.|s_f), n of pi(.|s'_f), n uniform; offsets: the sample's log-prob, or
+    A log 0.5) and no learned alpha (d3rlpy fixes it at 1 and never steps it).  After the critic step, on every
+    ``update_actor_interval``-th update counted from 0: the SAC actor step, the temperature step on the STEPPED policy, the soft
+    critic-target update (``MOPO.update``'s order).  d3rlpy 0.91 defaults as published; PARITY UNPINNED.
+
+    The critic step is two passes through the twin critics joined by ``rl4rs_amlp_grad_stash`` (csrc/combo.hpp): pass T over the B
+    rows (s, a), pass C over the F * 3n sample rows with the observation side of the first layer once per generated observation.
+    ``update`` is one library call (``rl4rs_combo_update``) on a single rank, or the per-phase calls with ``_allreduce_group`` around
+    each Adam when collectives are active or ``one_call`` is False.  ``noise`` (tests): dict with any of ``critic`` = (eps_t [F n, A],
+    eps_tp1 [F n, A], uniform [F, n, A]), ``eps_actor`` [B, A], ``eps_temp`` [B, A]; the rest is drawn.
+
+    Stated deviations and unpinned points: (a) d3rlpy splits the batch at int(B * real_ratio); here the split is the ``n_real`` the
+    minibatch was built with (``mixed_minibatch``: round), so the two cannot disagree.  (b) Whether 0.91's COMBOImpl multiplies its
+    conservative loss by ``conservative_weight`` cannot be verified here; it is applied (at the default 1.0 both readings
+    coincide).  (c) As for MOPO (points 2, 4, 6): both parts of a minibatch are drawn with replacement, the
+    learner's own observation scaler is not applied, the noise comes from this library's sources.  A half without rows (d3rlpy: NaN)
+    is an error here."""
+
+    def __init__(self, config, obs_dim, dynamics, action_size=None, batch_size=256, actor_learning_rate=1e-4, critic_learning_rate=3e-4,
+                 temp_learning_rate=1e-4, gamma=0.99, tau=0.005, initial_temperature=1.0, update_actor_interval=1, conservative_weight=1.0,
+                 n_action_samples=10, soft_q_backup=False, rollout_interval=1000, rollout_horizon=5, rollout_batch_size=50000, lam=0.0,
+                 real_ratio=0.5, generated_maxlen=50000 * 5 * 5, reward_scaler=None, discrete_action=False, predict_rows=4096, seed=0,
+                 device=None):
+        # (the refusals come first: none of them needs a device)
+        if soft_q_backup:
+            raise NotImplementedError('COMBO(soft_q_backup=True) is not built: the backup is the deterministic one, min_c Qtarg_c(s\', tanh(mu(s\')))')
+        if float(lam) != 0.0:
+            raise ValueError('COMBO does not penalise the generated reward: lam must be 0 (got %r); MOPO is the learner with r - lam * variance' % (lam,))
+        if discrete_action:
+            raise ValueError('COMBO here learns continuous actions only (the reference reaches it with support_conti_env); discrete_action=True is not built')
+        self.n = int(n_action_samples)
+        self.conservative_weight = float(conservative_weight)
+        n_real = int(round(float(real_ratio) * int(batch_size)))
+        if self.n < 1 or not 0 < n_real < int(batch_size):
+            raise ValueError('COMBO needs n_action_samples >= 1 and both real and generated rows in a minibatch: n_action_samples=%d, '
+                             'round(real_ratio * batch_size) = %d of %d' % (self.n, n_real, int(batch_size)))
+        MOPO.__init__(self, config, obs_dim, dynamics, action_size=action_size, batch_size=batch_size, actor_learning_rate=actor_learning_rate,
+                      critic_learning_rate=critic_learning_rate, temp_learning_rate=temp_learning_rate, gamma=gamma, tau=tau,
+                      initial_temperature=initial_temperature, update_actor_interval=update_actor_interval, rollout_interval=rollout_interval,
+                      rollout_horizon=rollout_horizon, rollout_batch_size=rollout_batch_size, lam=0.0, real_ratio=real_ratio,
+                      generated_maxlen=generated_maxlen, reward_scaler=reward_scaler, predict_rows=predict_rows, seed=seed, device=device)
+        self.lam = None                  # model_rollout: dynamics.predict's reward as it is, no variance penalty
+        self._w = torch.full((1,), self.conservative_weight, dtype=torch.float32, device=self.device)
+        self._log_uniform = float(self.A * np.log(0.5))          # log of the uniform density on [-1, 1]^A
+        self._stash_n = (self.q1.n_params + 3) // 4 * 4
+        self._stash = torch.empty(2 * self._stash_n, dtype=torch.float32, device=self.device)
+        self.one_call = True             # update() as one library call on a single rank (False: the per-phase calls; tests compare the two)
+        self._ws = {}                    # (B, n_real) -> workspace of rl4rs_combo_update
+
+    def _critic_rows(self):
+        # pass C: at most batch_size - 1 generated rows with 3n samples each
+        return max(self.batch_size, (self.batch_size - 1) * 3 * self.n)
+
+    def _rollout_due(self):
+        # (a learner restored in the middle of an interval has no generated rows yet: the generated half is never empty in fit)
+        return MOPO._rollout_due(self) or len(self.generated) == 0
+
+    def _update_minibatch(self, batch, n_real):
+        return self.update(*batch, n_real=n_real)
+
+    def _noise(self, noise, B, F):
+        """(eps_t, eps_tp1, uniform) of the critic step: what ``noise['critic']`` gives, the rest drawn"""
+        n, A = self.n, self.A
+        e_t, e_tp1, uni = noise.get('critic') or (None, None, None)
+        for x in (e_t, e_tp1, uni):
+            assert x is None or x.numel() == F * n * A, 'critic noise of %d values where %d x %d x %d are needed' % (x.numel(), F, n, A)
+        e_t, e_tp1 = self._randn((F * n, A), e_t), self._randn((F * n, A), e_tp1)
+        if uni is None:
+            uni = torch.empty((F, n, A), dtype=torch.float32, device=self.device).uniform_(-1.0, 1.0, generator=self._gen)
+        else:
+            uni = uni.to(device=self.device, dtype=torch.float32).reshape(F, n, A).contiguous()
+        return e_t, e_tp1, uni
+
+    def _update_one_call(self, obs, act, rew, nxt, ter, n_real, noise, do_actor):
+        from . import _lib
+        B, n, A, F = obs.shape[0], self.n, self.A, obs.shape[0] - n_real
+        lib = _lib.load()
+        ws = self._ws.get((B, n_real))
+        if ws is None:
+            ws = self._ws[(B, n_real)] = torch.empty(int(lib.rl4rs_combo_workspace_floats(B, n_real, n, A)), dtype=torch.float32, device=self.device)
+        if noise:
+            e_t, e_tp1, uniform = self._noise(noise, B, F)
+            parts = [e_t.reshape(-1), e_tp1.reshape(-1)]
+            if do_actor:
+                for key in ('eps_actor', 'eps_temp'):
+                    x = noise.get(key)
+                    assert x is None or x.numel() == B * A, '%s of %d values where %d x %d are needed' % (key, x.numel(), B, A)
+                    parts.append(self._randn((B, A), x).reshape(-1))
+            normal = torch.cat(parts)
+        else:
+            normal = torch.randn((2 * F * n + (2 * B if do_actor else 0)) * A, generator=self._gen, device=self.device, dtype=torch.float32)
+            uniform = torch.empty(F * n * A, dtype=torch.float32, device=self.device).uniform_(-1.0, 1.0, generator=self._gen)
+        metrics = torch.zeros(4, dtype=torch.float32, device=self.device)
+        st = _lib.ComboStep(*[net.h.value for net in (self.policy, self.q1, self.q2, self.q1_targ, self.q2_targ)], B, n_real, n, A,
+                            self.gamma, self.tau, self.actor_lr, self.critic_lr, self.temp_lr, self.conservative_weight,
+                            1 if do_actor else 0, 0, self.log_temp.t, self.log_temp.state.data_ptr(), *[t.data_ptr() for t in (obs, act, rew, nxt, ter)],
+                            normal.data_ptr(), uniform.data_ptr(), self._stash.data_ptr(), ws.data_ptr(), metrics.data_ptr())
+        _lib.check(lib.rl4rs_combo_update(C.byref(st), D_._stream()))
+        out = {'critic_loss': metrics[0], 'conservative_loss': metrics[3]}
+        if do_actor:
+            out['actor_loss'] = metrics[1]
+            if self.temp_lr > 0:
+                self.log_temp.t += 1
+                out['temp_loss'] = metrics[2]
+        self.total_step += 1
+        return out
+
+    def update(self, obs, act, rew, nxt, ter, n_real, noise=None):
+        noise = noise or {}
+        B, A, n = obs.shape[0], self.A, self.n
+        n_real = int(n_real)
+        F, k = B - n_real, 3 * n
+        if not 0 < n_real < B:
+            raise ValueError('COMBO.update: n_real=%d of %d rows: the data term needs real rows and the logsumexp term generated ones' % (n_real, B))
+        if max(B, F * k) > self.q1.max_rows:
+            raise ValueError('COMBO.update: a minibatch of %d rows (%d generated) where the learner was built for batch_size=%d' % (B, F, self.batch_size))
+        if self.reward_scaler is not None:
+            if isinstance(self.reward_scaler, str):
+                raise ValueError("reward_scaler=%r is fitted by fit_mdp(dataset); pass StandardRewardScaler(rewards) to use update / fit "
+                                 "directly" % self.reward_scaler)
+            rew = self.reward_scaler.transform(rew)
+        obs, act, rew, nxt, ter = _check_transitions(self.device, self.D, self.A, obs, act, rew, nxt, ter)
+        do_actor = self.total_step % self.update_actor_interval == 0
+        if self.one_call and not rdist.collectives_active():
+            return self._update_one_call(obs, act, rew, nxt, ter, n_real, noise, do_actor)
+        metrics = {}
+        twin = [self.q1, self.q2]
+        # the policy does not change until the actor step: its heads on s' and s are computed once (s last: the handle keeps the
+        # activations of s for the actor's backward); the generated rows' heads are rows n_real .. of these
+        head_nxt = self.policy.forward(nxt)
+        head_obs = self.policy.forward(obs)
+        # --- target (deterministic backup)
+        a_next, _ = D_.squashed_sample(head_nxt, None)
+        q1n, q2n = D_.amlp_forward_multi([self.q1_targ, self.q2_targ], nxt, a_next)
+        yq, _ = D_.bcq_target(q1n, q2n, 1, 1.0, rew.reshape(-1), ter.reshape(-1), self.gamma)
+        # --- the F * 3n rows of pass C: [pi(s_f) | pi(s'_f) | uniform] and their importance offsets
+        e_t, e_tp1, uni = self._noise(noise, B, F)
+        acts = torch.empty((F, k, A), dtype=torch.float32, device=self.device)
+        offs = torch.empty((F, k), dtype=torch.float32, device=self.device)
+        flat_a, flat_o = acts.view(F * k, A), offs.view(F * k)
+        D_.squashed_sample(head_obs[n_real:], e_t, rep=n, act_out=flat_a, logp_out=flat_o, out_rep=k, out_off=0)
+        D_.squashed_sample(head_nxt[n_real:], e_tp1, rep=n, act_out=flat_a, logp_out=flat_o, out_rep=k, out_off=n)
+        acts[:, 2 * n:] = uni
+        offs[:, 2 * n:] = self._log_uniform
+        # --- critic: forward T, backward T, stash, forward C, backward C, add (a backward WRITES the handle's gradient)
+        rows = torch.empty(4 * B + 2 * F, dtype=torch.float32, device=self.device)
+        stash = [self._stash[:self._stash_n], self._stash[self._stash_n:]]
+        q1t, q2t = D_.amlp_forward_multi(twin, obs, act)
+        dq1t, dq2t = D_.combo_critic_loss(B, n_real, k, self._w, rows, t=(q1t, q2t, yq))
+        D_.amlp_backward_multi(twin, obs, act, [dq1t, dq2t])
+        D_.amlp_grad_stash(twin, stash)
+        obs_f = obs[n_real:]
+        q1c, q2c = self.q1.forward(obs_f, flat_a, rep=k), self.q2.forward(obs_f, flat_a, rep=k)
+        sums, dq1c, dq2c = D_.combo_critic_loss(B, n_real, k, self._w, rows, c=(q1c, q2c, flat_o))
+        self.q1.backward(obs_f, flat_a, dq1c, rep=k)
+        self.q2.backward(obs_f, flat_a, dq2c, rep=k)
+        D_.amlp_grad_stash(twin, stash, add=True)
+        _allreduce_group(twin)
+        D_.amlp_adam_multi(twin, [self.critic_lr] * 2)
+        self.last_sums, self.last_y = sums, yq
+        s64 = sums.double()              # (combined in double and rounded once, as k_combo_metrics does)
+        cons = self.conservative_weight * ((s64[2] + s64[3]) / F - (s64[4] + s64[5]) / n_real)
+        metrics['conservative_loss'] = cons.float()
+        metrics['critic_loss'] = ((s64[0] + s64[1]) / B + cons).float()
+        if do_actor:
+            # --- actor (SACImpl.compute_actor_loss): (exp(log_temp) * logp - min_c Q_c(s, a)).mean()
+            eps = self._randn((B, A), noise.get('eps_actor'))
+            a_pi, logp = D_.squashed_sample(head_obs, eps)
+            q1p, q2p = D_.amlp_forward_multi(twin, obs, a_pi)
+            qmin, dq1, dq2 = D_.twin_min(q1p, q2p, want_grad=True)
+            g1, g2 = D_.amlp_backward_multi(twin, obs, a_pi, [dq1.view(B, 1), dq2.view(B, 1)], want_dact=True, want_param_grad=False)
+            d_head = D_.sac_actor_grad(head_obs, eps, a_pi, g1.add_(g2), self.log_temp.p)
+            self.policy.backward(obs, None, d_head)
+            _allreduce_group([self.policy])
+            metrics['actor_loss'] = (self.log_temp.p.exp() * logp - qmin).mean()
+            D_.amlp_adam_multi([self.policy], [self.actor_lr])
+            # --- temperature (SACImpl.update_temp, on the stepped policy)
+            if self.temp_lr > 0:
+                _, logp_t = D_.squashed_sample(self.policy.forward(obs), self._randn((B, A), noise.get('eps_temp')))
+                targ = (logp_t - A).mean()
+                temp = self.log_temp.p.exp()
+                metrics['temp_loss'] = -(temp * targ)[0]
+                self.log_temp.adam_step(-(temp * targ), self.temp_lr)
+            # --- soft target update
+            D_.amlp_adam_multi(twin, [0.0, 0.0], targets=[self.q1_targ, self.q2_targ], tau=self.tau, step=[False, False])
+        self.total_step += 1
+        return metrics
+
+    def critic_step_outputs(self, B, n_real):
+        """(y [B], sums6) of the LAST update's critic step (tests; the one-call path leaves them in its workspace)"""
+        if not (self.one_call and not rdist.collectives_active()):
+            return self.last_y, self.last_sums
+        from . import _lib
+        lib, ws = _lib.load(), self._ws[(B, n_real)]
+        y0, s0 = [int(lib.rl4rs_combo_workspace_offset(B, n_real, self.n, self.A, what)) for what in (0, 1)]
+        return ws[y0:y0 + B], ws[s0:s0 + 6]
+
+    _LOSS_KEYS = ('critic_loss', 'conservative_loss', 'actor_loss', 'temp_loss')
