@@ -36,14 +36,16 @@ def _hard_sigmoid(x):
     return np.clip(0.2 * x + 0.5, 0.0, 1.0)
 
 
-def keras_gru_last(X, kernel, recurrent, bias):
-    """X [R, L, E] -> last hidden state [R, U]."""
+def keras_gru_last(X, kernel, recurrent, bias, pre=None):
+    """X [R, L, E] -> last hidden state [R, U].  pre: a list that receives the z | r gate pre-activations [R, 2U] of every step."""
     R, L, _ = X.shape
     U = recurrent.shape[0]
     h = np.zeros((R, U), dtype=X.dtype)
     for t in range(L):
         xp = X[:, t] @ kernel + bias
         hz = h @ recurrent[:, :2 * U]
+        if pre is not None:
+            pre.append(xp[:, :2 * U] + hz)
         z = _hard_sigmoid(xp[:, :U] + hz[:, :U])
         r = _hard_sigmoid(xp[:, U:2 * U] + hz[:, U:])
         hh = np.tanh(xp[:, 2 * U:] + (r * h) @ recurrent[:, 2 * U:])
@@ -67,7 +69,13 @@ class OracleSimnet(object):
         h = _elu(dense.astype(self.dtype) @ w['dense_w1'] + w['dense_b1'])
         return _elu(h @ w['dense_w2'] + w['dense_b2'])
 
-    def obs(self, seq, dense, cat):
+    def gate_preacts(self, seq, dense, cat):
+        """lstm: every hard_sigmoid gate pre-activation of a forward (all GRUs, steps, rows, z and r), flattened in a fixed order"""
+        pre = []
+        self.obs(seq, dense, cat, pre=pre)
+        return np.concatenate([p.ravel() for p in pre])
+
+    def obs(self, seq, dense, cat, pre=None):
         w = self.w
         cat = np.asarray(cat).astype(np.int64)
         seq = np.asarray(seq).astype(np.int64)
@@ -83,8 +91,8 @@ class OracleSimnet(object):
             s = _elu(pooled @ w['fc_w'] + w['fc_b'])
             return np.concatenate([s, d, cat_emb.reshape(R, -1)], axis=1)
         finals = [keras_gru_last(w['seq_emb'][seq[:, i]], w['seq%d_gru_kernel' % i], w['seq%d_gru_recurrent' % i],
-                                 w['seq%d_gru_bias' % i]) for i in range(self.seq_num)]
-        cg = keras_gru_last(cat_emb, w['cat_gru_kernel'], w['cat_gru_recurrent'], w['cat_gru_bias'])
+                                 w['seq%d_gru_bias' % i], pre) for i in range(self.seq_num)]
+        cg = keras_gru_last(cat_emb, w['cat_gru_kernel'], w['cat_gru_recurrent'], w['cat_gru_bias'], pre)
         feat = np.concatenate(finals + [d, cg, cat_emb.reshape(R, -1)], axis=1)
         return _elu(feat @ w['obs_w'] + w['obs_b'])
 
@@ -95,27 +103,30 @@ class OracleSimnet(object):
         return self.reward_probs(seq, dense, cat)[:, 1]
 
 
-def loss_and_grad(algo, weights, dense, cat, labels, seqs=None, mask1=None, mask2=None, rate=0.0, class_num=2):
-    """Training-mode forward + keras binary_crossentropy + gradients of the dnn / widedeep / lstm model by torch float64 autograd -
+def loss_and_grad(algo, weights, dense, cat, labels, seqs=None, mask1=None, mask2=None, rate=0.0, class_num=2,
+                  dtype=np.float64):
+    """Training-mode forward + keras binary_crossentropy + gradients of the dnn / widedeep / lstm model by torch autograd in `dtype`
+    (float64: the reference; float32: the yardstick of what the number format alone costs) -
     the checker for the hand-written HIP backward (rl4rs/nets/dnn.py:31-37, widedeep.py:31-38 +
     model.compile(loss='binary_crossentropy'); Dropout(0.2) after each dense-tower layer, utils.py:51,53).
     mask1 / mask2: the keep masks [N, U] the device drew (None = no dropout).  -> mean loss, dict of gradients."""
     import torch
-    w = dict((k, torch.tensor(np.asarray(v, dtype=np.float64), requires_grad=True)) for k, v in weights.items())
+    tdt = torch.float64 if np.dtype(dtype) == np.float64 else torch.float32
+    w = dict((k, torch.tensor(np.asarray(v, dtype=dtype), requires_grad=True)) for k, v in weights.items())
     elu = torch.nn.functional.elu
-    x = torch.tensor(np.asarray(dense, dtype=np.float64))
+    x = torch.tensor(np.asarray(dense, dtype=dtype))
     ids = torch.tensor(np.asarray(cat, dtype=np.int64))
     h = elu(x @ w['dense_w1'] + w['dense_b1'])
     if mask1 is not None:
-        h = h * torch.tensor(np.asarray(mask1, dtype=np.float64)) / (1.0 - rate)
+        h = h * torch.tensor(np.asarray(mask1, dtype=dtype)) / (1.0 - rate)
     h = elu(h @ w['dense_w2'] + w['dense_b2'])
     if mask2 is not None:
-        h = h * torch.tensor(np.asarray(mask2, dtype=np.float64)) / (1.0 - rate)
+        h = h * torch.tensor(np.asarray(mask2, dtype=dtype)) / (1.0 - rate)
     def gru_last(X, i):      # keras GRU (see keras_gru_last above) in torch
         k, r, b = w[i + '_kernel'], w[i + '_recurrent'], w[i + '_bias']
         U = r.shape[0]
         hs = lambda v: torch.clamp(0.2 * v + 0.5, 0.0, 1.0)
-        hst = torch.zeros((X.shape[0], U), dtype=torch.float64)
+        hst = torch.zeros((X.shape[0], U), dtype=tdt)
         for t in range(X.shape[1]):
             xp = X[:, t] @ k + b
             hz = hst @ r[:, :2 * U]
@@ -138,7 +149,7 @@ def loss_and_grad(algo, weights, dense, cat, labels, seqs=None, mask1=None, mask
         pooled = torch.cat([w['seq_emb'][torch.tensor(np.asarray(q, dtype=np.int64))].mean(dim=1) for q in seqs], dim=1)
         obs = torch.cat([elu(pooled @ w['fc_w'] + w['fc_b']), h, w['cat_emb'][ids].reshape(ids.shape[0], -1)], dim=1)
     p = torch.softmax(obs @ w['out_w'] + w['out_b'], dim=1)
-    y = torch.nn.functional.one_hot(torch.tensor(np.asarray(labels, dtype=np.int64)), class_num).double()
+    y = torch.nn.functional.one_hot(torch.tensor(np.asarray(labels, dtype=np.int64)), class_num).to(tdt)
     pc = torch.clamp(p, 1e-7, 1.0 - 1e-7)
     loss = (-(y * torch.log(pc) + (1.0 - y) * torch.log(1.0 - pc)).mean(dim=1)).mean()
     loss.backward()

@@ -756,12 +756,15 @@ __global__ __launch_bounds__(NH * 2) void k_recur(RecurArgs a) {
     const int so_r = wave * KB * 1024, so_u = (NW + wave) * KB * 1024, so_c = wave * KB * 1024;   // + kb * 1024
 
     for (int i = tid; i < 32 * LDH; i += NH * 2) hb[i] = 0.f;
+    // GRU mode: ids outside the x table clamp to its first / last row like every other embedding gather (k_emb_mean, k_emb_flatten,
+    // the category kernels) - unclamped, the descriptor's bounds check would hand such an id an all-zero projection, bias included
+    const int id_max = (AUGRU || SAVE) ? 0 : (int)(a.xbytes / (a.xld * 4)) - 1;
     for (int i = tid; i < 32 * L; i += NH * 2) {
         int r = i / L, t = i - r * L;
         int gr = min(row0 + r, a.n_rows - 1);
         if (SAVE) s_att[r * LDT + t] = a.sv_att[sq] ? a.sv_att[sq][(size_t)gr * L + t] : 0.f;
         else if (AUGRU) s_att[r * LDT + t] = a.att[(size_t)sq * a.att_stride + (size_t)gr * L + t];
-        else s_ids[r * LDT + t] = a.ids[(size_t)gr * L + t];
+        else s_ids[r * LDT + t] = min(max(a.ids[(size_t)gr * L + t], 0), id_max);
     }
     // byte offset of each row's x-projection at t = 0 (AUGRU: slot * L * xld)
     uint32_t* s_xoff = reinterpret_cast<uint32_t*>(s_att + 32 * LDT);

@@ -2,12 +2,15 @@
 classes, 21 categories, 432 dense features - the only one tests/test_gpu_simtrain.py runs): every gradient of
 rl4rs_dientrain_grad / rl4rs_simtrain_grad against torch float64 autograd at E != U, odd widths, lengths 1 / 16 / 33 / 80,
 1 / 3 / 4 sequence inputs, 3 / 8 classes, the DIEN trainer's own minibatch (256), every row-tile form of the persistent
-recurrences, both GRU paths of the lstm trainer; the trainer -> scorer hand-off; the DIEN trainer's create-time limits.
+recurrences, both GRU paths of the lstm trainer; every GRU implementation of the lstm trainer with keras hard_sigmoid gates on
+both clamps (no other input of these files reaches +-2.5: tests/test_simnet_shapes_host.py); the trainer -> scorer hand-off; the DIEN
+trainer's create-time limits.
 Same bars as tests/test_gpu_simtrain.py: loss 1e-5 relative, gradients 2e-4 (simnets) / 5e-4 (dien) of each array's largest
 entry, scorer obs 5e-5 and probabilities 5e-6 absolute."""
 import numpy as np
 import pytest
 
+from simnet_cases import SHAPES, scale_gru
 from test_gpu_simtrain import CFG, DIEN_CFG, _check_dien_gradients, _check_simnet_gradients, recur_rows  # noqa: F401
 
 pytestmark = pytest.mark.gpu
@@ -104,14 +107,54 @@ def test_lstm_gradients_other_configurations(name):
     _check_simnet_gradients('lstm', 0.2, N, cfg, front_pad=True)
 
 
-@pytest.mark.parametrize('algo', ['dnn', 'widedeep', 'dien'])
+# keras hard_sigmoid gates on both clamps: the GRU matrices of the seeded weights times 8 (simnet_cases.scale_gru) put about a third
+# of the gate pre-activations beyond +-2.5, where the gate's derivative is 0 instead of 0.2.  N = 9: two 8-row tiles, three 4-row
+# tiles, one 32-row tile - the last one ragged in every form; maxlen 4, 3 categories; no dropout (the probability condition below is
+# then a statement about the restatement alone).  name -> (configuration, persistent, seed of the weights and of the batch).  The
+# gradient is discontinuous at the kinks, so a seed qualifies only if, in the float64 restatement, no gate pre-activation lies closer
+# to +-2.5 than 10 x the largest float32-vs-float64 difference of one, and every class probability stays inside [1e-6, 1 - 1e-6]
+# (the loss clamp is no second kink).  tests/test_simnet_shapes_host.py checks both on the CPU; measured there:
+#   w128  seed 10: kink margin 4.6e-4, float32 pre-activation error 9.3e-6, saturated 18.4 % / 18.4 %
+#   w256  seed 14: kink margin 2.6e-4, float32 pre-activation error 9.7e-6, saturated 15.4 % / 16.0 %
+#   steps seed 7: kink margin 6.3e-4, float32 pre-activation error 7.0e-6, saturated 17.9 % / 17.1 %
+# (of seeds 0..19, 10 / 7 / 16 qualify; these have the widest margin.)  float32 autograd of the restatement on these cases: loss off
+# by at most 1.5e-7, a gradient array by at most 3.1e-6 of its largest entry - under a quarter of the bars, so the file's own hold.
+SATURATED_N = 9
+SATURATED = {
+    'w128': (dict(CFG, maxlen=4, category_feature_num=3), True, 10),
+    'w256': (dict(CFG, hidden_units=256, maxlen=4, category_feature_num=3), True, 14),
+    'steps': (dict(CFG, emb_size=72, hidden_units=96, maxlen=4, category_feature_num=3), False, 7),
+}
+
+
+def saturated_case(name):
+    """-> the arguments of _simnet_case / _check_simnet_gradients for one saturated-gate case"""
+    cfg, _, seed = SATURATED[name]
+    return dict(algo='lstm', rate=0.0, N=SATURATED_N, cfg=cfg, front_pad=True, seed=seed, input_seed=seed, weight_hook=scale_gru)
+
+
+@pytest.mark.parametrize('name,rows', [('w128', 0), ('w128', 8), ('w128', 32), ('w256', 0), ('w256', 4), ('w256', 8), ('w256', 32),
+                                       ('steps', 0)])
+def test_lstm_gradients_with_saturated_gates(recur_rows, name, rows):
+    """every GRU implementation of the lstm trainer with gates on both clamps of hard_sigmoid: the persistent recurrences at width 128
+    (8- and 32-row tiles) and 256 (4-, 8- and 32-row tiles; 0 = what the library picks itself), and the step-by-step form (E 72, U 96).
+    Bars: the file's own; a figure the float32 autograd of the restatement itself misses by more than a quarter of its bar takes 4 x that
+    miss (_check_simnet_gradients prints every such figure)."""
+    cfg, persistent, _ = SATURATED[name]
+    assert _gru_persistent(cfg, SATURATED_N) == persistent, name
+    recur_rows(rows)
+    _check_simnet_gradients(**saturated_case(name))
+
+
+@pytest.mark.parametrize('algo', ['dnn', 'widedeep', 'dien', 'lstm'])
 def test_trained_weights_drop_into_the_scorer(algo):
-    """Trainer -> scorer at an odd configuration (dnn / widedeep: ODD, dien: D1): one step() is keras Adam's first update of
+    """Trainer -> scorer at an odd configuration (dnn / widedeep: ODD, dien: D1, lstm: L3 of simnet_cases - E = U = 128 as its
+    scorer requires): one step() is keras Adam's first update of
     every array; after three steps weights() - the export layout - loads into DeviceSimnet / DeviceDien at the same configuration,
     whose obs / probabilities match the float64 oracle of those exported weights (dien: both scorer modes)."""
     import torch
     from rl4rs_amd.device import DeviceSimTrainer, DeviceDienTrainer, DeviceSimnet, DeviceDien
-    cfg = DIEN_VARIANTS['D1'] if algo == 'dien' else ODD
+    cfg = DIEN_VARIANTS['D1'] if algo == 'dien' else (SHAPES['L3'][1] if algo == 'lstm' else ODD)
     L, S, Cn, Dn, K = cfg['maxlen'], cfg['seq_num'], cfg['category_feature_num'], cfg['dense_feature_num'], cfg['class_num']
     N = 45
     if algo == 'dien':
