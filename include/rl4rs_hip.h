@@ -258,6 +258,11 @@ typedef struct rl4rs_dien_cfg {
  *                   list) and no k_row_expand is launched (=).  OFF by default: measured slower than the copy launch (building
  *                   the lists costs the one compacting workgroup more than the launch it saves)
  *   NO_DUP_STORE    pins that default: k_row_expand copies the representatives' rows to the duplicates (=)
+ *   NO_TIER2_ROWS   row dedup: the category kernel, the dense tower / q-side GEMMs and the head GEMM over every row of a forward
+ *                   instead of the representatives' rows only (they take the active list as k_din_x / k_augru_x do; k_row_expand
+ *                   then runs behind the head GEMM and copies a duplicate's whole all-feature row, scores, query row and head
+ *                   output).  The active-row form is used only with the default category / GEMM forms, without
+ *                   DUP_STORE and DENSE_FORK, and not in a forward whose head GEMM writes a host mirror (=)
  *   DIN_ROWS16      k_din_x with 16 rows per workgroup whatever the row dedup left, instead of 8 (one row per wave) when the active
  *                   rows of an observation-sized launch fit one round that way (decided on the device) (=) */
 enum {
@@ -285,7 +290,9 @@ enum {
     RL4RS_DIEN_OPT_DIN_ROWS16 = 1 << 18,       /* k_din_x: 16 rows per workgroup for every launch (bit-identical either way) */
     RL4RS_DIEN_OPT_DUP_STORE = 1 << 19,        /* row dedup: the duplicates' stores inside k_din_x / k_augru_x, no k_row_expand launch
                                                   (bit-identical either way) */
-    RL4RS_DIEN_OPT_ALL = (1 << 20) - 1
+    RL4RS_DIEN_OPT_NO_TIER2_ROWS = 1 << 20,    /* row dedup: category kernel, dense / q-side GEMMs and head GEMM over all R rows, k_row_expand
+                                                  in front of the head GEMM (bit-identical either way) */
+    RL4RS_DIEN_OPT_ALL = (1 << 21) - 1
 };
 
 /* Every mode accumulates in fp32 and meets the fp32 parity bar against the fp64 oracle (same measured error):

@@ -94,13 +94,19 @@ int launch_gemm_packed(const float* a, int64_t lda, const float* wp, const float
 std::vector<float> pack_gemm_weight(const float* w, int64_t ldw, int K, int N);
 // fp16x2 form (scorer_mode FP16X2): weights pre-split into fp16 hi / lo fragment planes, activations split while staged
 // mirror (optional): device-visible HOST memory that receives the same output elements from the epilogue, row stride ldm
+// map (optional, the three launchers below): the row map of a scorer forward (row_dedup.hpp) - tile position p works on
+// row active[p / group] * group + p % group of a, c / c2 and the addend, only the first min(M, n_active[0] * group) positions are
+// computed (bound read on the device, grid sized for M).  Ignored - every row computed - where a launch cannot take it (the
+// weights-resident kernel, a mirror, matrices beyond 2 GB)
+struct G16RowMap { const int32_t* active; const int32_t* n_active; int group; };
 int launch_gemm_h16(const float* a, int64_t lda, const float* wp16, const float* bias, float* c, int64_t ldc,
                     int M, int N, int K, int act, hipStream_t st, const float* addend = nullptr, int64_t ldadd = 0,
-                    float* mirror = nullptr, int64_t ldm = 0);
+                    float* mirror = nullptr, int64_t ldm = 0, const G16RowMap* map = nullptr);
 std::vector<float> pack_gemm_weight_h16(const float* w, int64_t ldw, int K, int N);
 // two chained layers in one launch (N1 <= 128, N1 % 16 == 0, N2 <= 128): c2 = act2(act1(a W1 + b1) W2 + b2)
 int launch_gemm_h16_chain(const float* a, int64_t lda, const float* wp1, const float* bias1, int N1, int K1, int act1,
-                          const float* wp2, const float* bias2, float* c2, int64_t ldc2, int N2, int act2, int M, hipStream_t st);
+                          const float* wp2, const float* bias2, float* c2, int64_t ldc2, int N2, int act2, int M, hipStream_t st,
+                          const G16RowMap* map = nullptr);
 // two independent fp16x2 GEMMs in one launch when both take the same tile form of k_gemm_h16 (else two launches); wp2 != null:
 // the problem is a chained pair of layers as in launch_gemm_h16_chain (c / ldc unused, N = N1, output c2 [M, N2])
 struct GemmH16Desc {
@@ -108,7 +114,7 @@ struct GemmH16Desc {
     const float* addend; int64_t ldadd;
     const float* wp2; const float* bias2; float* c2; int64_t ldc2; int N2, act2;
 };
-int launch_gemm_h16_pair(const GemmH16Desc& x, const GemmH16Desc& y, hipStream_t st);
+int launch_gemm_h16_pair(const GemmH16Desc& x, const GemmH16Desc& y, hipStream_t st, const G16RowMap* map = nullptr);
 
 // device-side pack_gemm_weight_h16 (weights that change between launches): up to 4 matrices per launch, out = NT * KB * 512 + NT * 32 floats
 struct PackH16Desc { const float* w; float* out; int ldw, K, N; };

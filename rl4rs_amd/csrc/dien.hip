@@ -444,11 +444,18 @@ __global__ __launch_bounds__(256, 4) void k_cat_attn2(const int32_t* __restrict_
                                                       const float* __restrict__ cat_emb, const float* __restrict__ seq_emb,
                                                       float* __restrict__ allf, int ldf, int off_c, float* __restrict__ q, int write_flat,
                                                       int h16, const float* __restrict__ ptab, const float* __restrict__ obs_b,
-                                                      float* __restrict__ tsum) {
+                                                      float* __restrict__ tsum, const int32_t* __restrict__ order,
+                                                      const int32_t* __restrict__ n_active, int group) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int row = blockIdx.x * 4 + wave;
-    if (row >= R) return;
+    int row = blockIdx.x * 4 + wave;
+    // order != NULL: the active list of the row dedup (row_dedup.hpp) - position `row` works on physical row
+    // order[row / group] * group + row % group, positions behind min(R, n_active * group) leave (all wave-uniform; no barrier here)
+    if (order) {
+        if (row >= min(R, n_active[0] * group)) return;
+        const int g = row / group;
+        row = order[g] * group + (row - g * group);
+    } else if (row >= R) return;
     cat_attn2_row<MAXC, EXACT>(reinterpret_cast<float*>(smem) + (size_t)wave * (Cn * (64 + 4) + 32), row, lane, cat, Cn, H, cat_emb, seq_emb, allf, ldf,
                   off_c, q, write_flat, h16, ptab, obs_b, tsum);
 }
@@ -470,15 +477,25 @@ __global__ __launch_bounds__(256, 4) void k_cat_attn2(const int32_t* __restrict_
 //     k_cat_attn2 (tests/test_gpu_dien.py::test_group_category_kernel_is_bit_identical).
 // Nothing is assumed about the ids: each wave compares its row's with the staged ("lead") row's while the loads are in flight,
 // and rows that differ are served by further passes of the same loop with the next open row as the lead.
-template <int G>
-__global__ __launch_bounds__(64 * G, 4) void k_cat_attn2g(const int32_t* __restrict__ cat, int Cn, int H,
+// W waves serve the G rows (W = G up to 8 rows; the 9-row group of the reward forward that scores the state row too runs on 8
+// waves, wave 0 takes the ninth row behind its first: a 9-wave workgroup puts three waves on one SIMD, and two such workgroups
+// do not fit a CU's register file side by side - DESIGN 25).  Row r is served by wave r % W from its own registers and its own
+// LDS block, in the operation order it always had.
+template <int G, int W>
+__global__ __launch_bounds__(64 * W, 4) void k_cat_attn2g(const int32_t* __restrict__ cat, int Cn, int H,
                                                           const float* __restrict__ cat_emb, const float* __restrict__ seq_emb,
                                                           float* __restrict__ allf, int ldf, int off_c, float* __restrict__ q, int write_flat,
                                                           int h16, const float* __restrict__ ptab, const float* __restrict__ obs_b,
-                                                          float* __restrict__ tsum) {
+                                                          float* __restrict__ tsum, const int32_t* __restrict__ order,
+                                                          const int32_t* __restrict__ n_active) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    // order != NULL: the active list of the row dedup (row_dedup.hpp) - workgroup p takes group order[p], the
+    // workgroups behind n_active leave here, before the first barrier
+    if (order && (int)blockIdx.x >= n_active[0]) return;
+    const int grp = order ? order[blockIdx.x] : (int)blockIdx.x;
     constexpr int E = 128, LE = E + 4, MAXS = 23;              // MAXS: shared rows at most (Cn <= 24)
-    constexpr int RJ = (MAXS + G - 1) / G, RQ = (9 + G - 1) / G;   // shared rows / shared query rows per wave
+    constexpr int RJ = (MAXS + W - 1) / W, RQ = (9 + W - 1) / W;   // shared rows / shared query rows per wave
+    constexpr int NR = (G + W - 1) / W;                        // rows per wave at most
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int half = lane >> 5, li = lane & 31;
     const int CS = Cn - 1;                                     // shared rows
@@ -487,17 +504,28 @@ __global__ __launch_bounds__(64 * G, 4) void k_cat_attn2g(const int32_t* __restr
     float* sQ = fs + 16;                                       // [9][E] the nine shared query rows
     float* sT = sQ + 9 * E;                                    // [CS][OBS_DIM] shared head-table rows
     float* sE = sT + (size_t)CS * OBS_DIM;                     // [CS][LE] shared embedding rows
-    float* sP = sE + (size_t)CS * LE + (size_t)wave * (LE + 32);   // per wave: own last row [LE] + column weights [32]
-    float* sW = sP + LE;
-    const int row0 = blockIdx.x * G, row = row0 + wave;
-    const int myid = (lane < Cn) ? min(max(cat[(size_t)row * Cn + lane], 0), H - 1) : 0;
+    float* sPb = sE + (size_t)CS * LE;                         // per row: own last row [LE] + column weights [32]
+    const int row0 = grp * G;
     const bool do_t = tsum != nullptr;
-    // this row's own last id: embedding row, query row, head-table row (requested once, kept across passes)
-    const int last = __builtin_amdgcn_readlane(myid, Cn - 1);
-    const float pc0 = cat_emb[(size_t)last * E + lane], pc1 = cat_emb[(size_t)last * E + lane + 64];
-    const float pq0 = seq_emb[(size_t)last * E + lane], pq1 = seq_emb[(size_t)last * E + lane + 64];
-    float4 pt = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (do_t) pt = reinterpret_cast<const float4*>(ptab + ((size_t)CS * H + last) * OBS_DIM)[lane];
+    // this wave's rows (wave, wave + W): their ids and their own last id's embedding row, query row, head-table row (requested
+    // once, kept across passes)
+    int myid_a[NR];
+    float pc0_a[NR], pc1_a[NR], pq0_a[NR], pq1_a[NR];
+    float4 pt_a[NR];
+#pragma unroll
+    for (int k = 0; k < NR; ++k) {
+        const int rw = wave + k * W;                           // wave-uniform
+        myid_a[k] = 0;
+        pc0_a[k] = pc1_a[k] = pq0_a[k] = pq1_a[k] = 0.f;
+        pt_a[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (rw < G) {
+            myid_a[k] = (lane < Cn) ? min(max(cat[(size_t)(row0 + rw) * Cn + lane], 0), H - 1) : 0;
+            const int last = __builtin_amdgcn_readlane(myid_a[k], Cn - 1);
+            pc0_a[k] = cat_emb[(size_t)last * E + lane]; pc1_a[k] = cat_emb[(size_t)last * E + lane + 64];
+            pq0_a[k] = seq_emb[(size_t)last * E + lane]; pq1_a[k] = seq_emb[(size_t)last * E + lane + 64];
+            if (do_t) pt_a[k] = reinterpret_cast<const float4*>(ptab + ((size_t)CS * H + last) * OBS_DIM)[lane];
+        }
+    }
     // Pass p stages the shared rows of the first row not served yet (the "lead"; pass 0: row 0) and serves every row whose
     // shared ids equal the lead's.  A group of complete states is one pass; a group that shares nothing is G passes - the same
     // results either way (each row is always computed from exactly its own ids), the sharing only decides the speed.
@@ -505,15 +533,15 @@ __global__ __launch_bounds__(64 * G, 4) void k_cat_attn2g(const int32_t* __restr
     int lead = 0;
     while (true) {
         const int id0 = (lane < Cn) ? min(max(cat[(size_t)(row0 + lead) * Cn + lane], 0), H - 1) : 0;
-        // every wave gathers its share of the lead's shared rows into LDS: embedding rows and head-table rows j = wave, wave + G, ..,
-        // query rows u = wave, wave + G (all requested before the first is stored)
+        // every wave gathers its share of the lead's shared rows into LDS: embedding rows and head-table rows j = wave, wave + W, ..,
+        // query rows u = wave, wave + W (all requested before the first is stored)
         {
             float v0[RJ], v1[RJ];
             float4 tv[RJ];
             float qv0[RQ], qv1[RQ];
 #pragma unroll
             for (int u = 0; u < RJ; ++u) {
-                const int j = wave + u * G;                    // wave-uniform
+                const int j = wave + u * W;                    // wave-uniform
                 v0[u] = 0.f;
                 v1[u] = 0.f;
                 tv[u] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -526,7 +554,7 @@ __global__ __launch_bounds__(64 * G, 4) void k_cat_attn2g(const int32_t* __restr
             }
 #pragma unroll
             for (int u = 0; u < RQ; ++u) {
-                const int k = wave + u * G;
+                const int k = wave + u * W;
                 qv0[u] = 0.f;
                 qv1[u] = 0.f;
                 if (k < 9) {
@@ -537,7 +565,7 @@ __global__ __launch_bounds__(64 * G, 4) void k_cat_attn2g(const int32_t* __restr
             }
 #pragma unroll
             for (int u = 0; u < RJ; ++u) {
-                const int j = wave + u * G;
+                const int j = wave + u * W;
                 if (j < CS) {
                     sE[j * LE + lane] = v0[u];
                     sE[j * LE + lane + 64] = v1[u];
@@ -546,120 +574,134 @@ __global__ __launch_bounds__(64 * G, 4) void k_cat_attn2g(const int32_t* __restr
             }
 #pragma unroll
             for (int u = 0; u < RQ; ++u) {
-                const int k = wave + u * G;
+                const int k = wave + u * W;
                 if (k < 9) { sQ[k * E + lane] = qv0[u]; sQ[k * E + lane + 64] = qv1[u]; }
             }
         }
-        sP[lane] = pc0;                                        // (behind the pass's requests; the same values every pass)
-        sP[lane + 64] = pc1;
-        {
-            const bool same = __all((lane >= CS) || (myid == id0));
-            if (lane == 0) s_flag[wave] = same ? 1 : 0;
+#pragma unroll
+        for (int k = 0; k < NR; ++k) {
+            const int rw = wave + k * W;
+            if (rw < G) {
+                float* sP = sPb + (size_t)rw * (LE + 32);
+                sP[lane] = pc0_a[k];                               // (behind the pass's requests; the same values every pass)
+                sP[lane + 64] = pc1_a[k];
+                const bool same = __all((lane >= CS) || (myid_a[k] == id0));
+                if (lane == 0) s_flag[rw] = same ? 1 : 0;
+            }
         }
         __syncthreads();
         uint32_t hit = 0;
 #pragma unroll
         for (int w = 0; w < G; ++w) hit |= (s_flag[w] != 0 ? 1u : 0u) << w;
         hit &= ~done;
-        if ((hit >> wave) & 1u) {                              // this row is served by this pass
-            float* frow = allf + (size_t)row * ldf + off_c;
-            if (write_flat) {                                          // Flatten()(category_emb) of the GEMM-form head
-                for (int u = 0; u < Cn; ++u) {
-                    const float* er = (u < CS) ? sE + u * LE : sP;
-                    frow[E + u * E + lane] = er[lane];
-                    frow[E + u * E + lane + 64] = er[lane + 64];
-                }
-            }
-            f32x16 acc;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-            const bool row_ok = li < Cn;
-            const float* erow = (li < CS) ? sE + li * LE : sP;         // lanes beyond Cn read the private row, results unused
-            if (h16) {
-                const float* er16 = erow + half * 8;
-#pragma unroll
-                for (int kb = 0; kb < E / 16; ++kb) {
-                    float4 f0 = make_float4(0.f, 0.f, 0.f, 0.f), f1 = f0;
-                    if (row_ok) { f0 = *reinterpret_cast<const float4*>(er16 + kb * 16); f1 = *reinterpret_cast<const float4*>(er16 + kb * 16 + 4); }
-                    const float x[8] = {f0.x, f0.y, f0.z, f0.w, f1.x, f1.y, f1.z, f1.w};
-                    half8_t fh, fl;
-#pragma unroll
-                    for (int e = 0; e < 8; e += 2) {
-                        half2_t h2, l2;
-                        split_h16_pair(x[e], x[e + 1], h2, l2);
-                        fh[e] = h2[0]; fh[e + 1] = h2[1];
-                        fl[e] = l2[0]; fl[e + 1] = l2[1];
+        for (int kr = 0; kr < NR; ++kr) {
+            const int rw = wave + kr * W;                          // wave-uniform
+            if (rw < G && ((hit >> rw) & 1u)) {                    // this row is served by this pass
+                const int row = row0 + rw;
+                float* sP = sPb + (size_t)rw * (LE + 32);
+                float* sW = sP + LE;
+                const float pc0 = pc0_a[kr], pc1 = pc1_a[kr], pq0 = pq0_a[kr], pq1 = pq1_a[kr];
+                const float4 pt = pt_a[kr];
+                float* frow = allf + (size_t)row * ldf + off_c;
+                if (write_flat) {                                          // Flatten()(category_emb) of the GEMM-form head
+                    for (int u = 0; u < Cn; ++u) {
+                        const float* er = (u < CS) ? sE + u * LE : sP;
+                        frow[E + u * E + lane] = er[lane];
+                        frow[E + u * E + lane + 64] = er[lane + 64];
                     }
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(fh, fh, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(fl, fh, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(fh, fl, acc, 0, 0, 0);
                 }
-            } else {
-                const float* er32 = erow + half * 4;
-#pragma unroll
-                for (int kb = 0; kb < E / 8; ++kb) {
-                    float4 f = row_ok ? *reinterpret_cast<const float4*>(er32 + kb * 8) : make_float4(0.f, 0.f, 0.f, 0.f);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(f.x, f.x, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(f.y, f.y, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(f.z, f.z, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(f.w, f.w, acc, 0, 0, 0);
+                f32x16 acc;
+    #pragma unroll
+                for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+                const bool row_ok = li < Cn;
+                const float* erow = (li < CS) ? sE + li * LE : sP;         // lanes beyond Cn read the private row, results unused
+                if (h16) {
+                    const float* er16 = erow + half * 8;
+    #pragma unroll
+                    for (int kb = 0; kb < E / 16; ++kb) {
+                        float4 f0 = make_float4(0.f, 0.f, 0.f, 0.f), f1 = f0;
+                        if (row_ok) { f0 = *reinterpret_cast<const float4*>(er16 + kb * 16); f1 = *reinterpret_cast<const float4*>(er16 + kb * 16 + 4); }
+                        const float x[8] = {f0.x, f0.y, f0.z, f0.w, f1.x, f1.y, f1.z, f1.w};
+                        half8_t fh, fl;
+    #pragma unroll
+                        for (int e = 0; e < 8; e += 2) {
+                            half2_t h2, l2;
+                            split_h16_pair(x[e], x[e + 1], h2, l2);
+                            fh[e] = h2[0]; fh[e + 1] = h2[1];
+                            fl[e] = l2[0]; fl[e + 1] = l2[1];
+                        }
+                        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(fh, fh, acc, 0, 0, 0);
+                        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(fl, fh, acc, 0, 0, 0);
+                        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(fh, fl, acc, 0, 0, 0);
+                    }
+                } else {
+                    const float* er32 = erow + half * 4;
+    #pragma unroll
+                    for (int kb = 0; kb < E / 8; ++kb) {
+                        float4 f = row_ok ? *reinterpret_cast<const float4*>(er32 + kb * 8) : make_float4(0.f, 0.f, 0.f, 0.f);
+                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(f.x, f.x, acc, 0, 0, 0);
+                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(f.y, f.y, acc, 0, 0, 0);
+                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(f.z, f.z, acc, 0, 0, 0);
+                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(f.w, f.w, acc, 0, 0, 0);
+                    }
                 }
-            }
-            float m = -3.4e38f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-                if (crow(r, half) < Cn) m = fmaxf(m, acc[r]);
-            m = fmaxf(m, __shfl_xor(m, 32));
-            float z = 0.f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                float ev = (crow(r, half) < Cn) ? CAT_EXP(acc[r] - m) : 0.f;
-                acc[r] = ev;
-                z += ev;
-            }
-            z += __shfl_xor(z, 32);
-            const float inv = row_ok ? 1.f / z : 0.f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                float v = acc[r] * inv;
-                v += __shfl_xor(v, 1);
-                v += __shfl_xor(v, 2);
-                v += __shfl_xor(v, 4);
-                v += __shfl_xor(v, 8);
-                v += __shfl_xor(v, 16);
-                if (li == 0) sW[crow(r, half)] = v;
-            }
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            {
-                const float invc = 1.f / (float)Cn;
-                float s0 = 0.f, s1 = 0.f;
-                for (int j = 0; j < CS; ++j) {
-                    const float w = sW[j];
-                    s0 = fmaf(w, sE[j * LE + lane], s0);
-                    s1 = fmaf(w, sE[j * LE + lane + 64], s1);
+                float m = -3.4e38f;
+    #pragma unroll
+                for (int r = 0; r < 16; ++r)
+                    if (crow(r, half) < Cn) m = fmaxf(m, acc[r]);
+                m = fmaxf(m, __shfl_xor(m, 32));
+                float z = 0.f;
+    #pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    float ev = (crow(r, half) < Cn) ? CAT_EXP(acc[r] - m) : 0.f;
+                    acc[r] = ev;
+                    z += ev;
                 }
-                s0 = fmaf(sW[CS], pc0, s0);
-                s1 = fmaf(sW[CS], pc1, s1);
-                frow[lane] = s0 * invc;
-                frow[lane + 64] = s1 * invc;
-            }
-            // query = mean of the last ten ids' rows, head addend = bias + table rows: both summed in the per-row kernel's order
-            // (shared rows in id order, this row's own one last)
-            const float invq = 1.f / (float)min(10, Cn);
-            float q0 = 0.f, q1 = 0.f;
-#pragma unroll
-            for (int u = 0; u < 9; ++u) { q0 += sQ[u * E + lane]; q1 += sQ[u * E + lane + 64]; }
-            q[(size_t)row * E + lane] = (q0 + pq0) * invq;
-            q[(size_t)row * E + lane + 64] = (q1 + pq1) * invq;
-            if (do_t) {
-                float4 t = reinterpret_cast<const float4*>(obs_b)[lane];
-                for (int j = 0; j < CS; ++j) {
-                    const float4 v = reinterpret_cast<const float4*>(sT + (size_t)j * OBS_DIM)[lane];
-                    t.x += v.x; t.y += v.y; t.z += v.z; t.w += v.w;
+                z += __shfl_xor(z, 32);
+                const float inv = row_ok ? 1.f / z : 0.f;
+    #pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    float v = acc[r] * inv;
+                    v += __shfl_xor(v, 1);
+                    v += __shfl_xor(v, 2);
+                    v += __shfl_xor(v, 4);
+                    v += __shfl_xor(v, 8);
+                    v += __shfl_xor(v, 16);
+                    if (li == 0) sW[crow(r, half)] = v;
                 }
-                t.x += pt.x; t.y += pt.y; t.z += pt.z; t.w += pt.w;
-                reinterpret_cast<float4*>(tsum + (size_t)row * OBS_DIM)[lane] = t;
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                {
+                    const float invc = 1.f / (float)Cn;
+                    float s0 = 0.f, s1 = 0.f;
+                    for (int j = 0; j < CS; ++j) {
+                        const float w = sW[j];
+                        s0 = fmaf(w, sE[j * LE + lane], s0);
+                        s1 = fmaf(w, sE[j * LE + lane + 64], s1);
+                    }
+                    s0 = fmaf(sW[CS], pc0, s0);
+                    s1 = fmaf(sW[CS], pc1, s1);
+                    frow[lane] = s0 * invc;
+                    frow[lane + 64] = s1 * invc;
+                }
+                // query = mean of the last ten ids' rows, head addend = bias + table rows: both summed in the per-row kernel's order
+                // (shared rows in id order, this row's own one last)
+                const float invq = 1.f / (float)min(10, Cn);
+                float q0 = 0.f, q1 = 0.f;
+    #pragma unroll
+                for (int u = 0; u < 9; ++u) { q0 += sQ[u * E + lane]; q1 += sQ[u * E + lane + 64]; }
+                q[(size_t)row * E + lane] = (q0 + pq0) * invq;
+                q[(size_t)row * E + lane + 64] = (q1 + pq1) * invq;
+                if (do_t) {
+                    float4 t = reinterpret_cast<const float4*>(obs_b)[lane];
+                    for (int j = 0; j < CS; ++j) {
+                        const float4 v = reinterpret_cast<const float4*>(sT + (size_t)j * OBS_DIM)[lane];
+                        t.x += v.x; t.y += v.y; t.z += v.z; t.w += v.w;
+                    }
+                    t.x += pt.x; t.y += pt.y; t.z += pt.z; t.w += pt.w;
+                    reinterpret_cast<float4*>(tsum + (size_t)row * OBS_DIM)[lane] = t;
+                }
             }
         }
         done |= hit;
@@ -669,6 +711,10 @@ __global__ __launch_bounds__(64 * G, 4) void k_cat_attn2g(const int32_t* __restr
     }
 }
 
+// waves of the 9-row form: 8 (wave 0 serves the ninth row as well); -DRL4RS_CAT9_WAVES=9 builds the one-wave-per-row form for A/B runs
+#ifndef RL4RS_CAT9_WAVES
+#define RL4RS_CAT9_WAVES 8
+#endif
 inline size_t cat_attn2g_smem(int G, int Cn) {
     const size_t grp = 16 + 9 * 128 + (size_t)(Cn - 1) * (OBS_DIM + 132) + (size_t)G * (132 + 32);
     return grp * 4;
@@ -1746,7 +1792,7 @@ struct rl4rs_dien {
     float* bproj[4];       // [PLD]
     float* w1ac[4];        // [E, 64]
     float* w1ac_all;       // [E, S*64]: the q-side matrices of all sequence inputs side by side, packed (one GEMM per forward)
-    float* qa;             // [S, max_rows, 64]
+    float* qa;             // [S, max_rows, 64]  (internal; second tier on the active rows, DESIGN 25: rows of duplicate groups are stale)
     float* w1d[4];         // packed [2][E/8][64][4]
     float* w1d16[4];       // fp16 hi/lo planes of the same fragments (fp16x2 mode)
     float *att_w2[4], *att_b2[4], *att_w3[4], *att_b3[4];
@@ -1764,6 +1810,7 @@ struct rl4rs_dien {
     bool din_x;            // fp16x2 DIN scores through k_din_x (RL4RS_DIN=v1 keeps k_din_scores<*, true>)
     bool dense_chain;      // fp16x2 mode: both dense-tower layers in one launch (RL4RS_DENSE_FUSED=0 at create: two GEMMs)
     float* tsum;           // [max_rows, 256]: obs_b + the per-slot head tables' rows, built by k_cat_attn (table form, Cn <= 24)
+                           // (internal; second tier on the active rows, DESIGN 25: rows of duplicate groups are stale)
     bool gemm_group;       // fp16x2 mode: the chained dense tower and the q-side term of the DIN scores in one launch (RL4RS_DIEN_OPT_NO_GEMM_GROUP: two)
     bool dense_fork;       // RL4RS_DIEN_OPT_DENSE_FORK: the dense tower (depends on nothing before the head) on side_stream, beside the category / DIN / AUGRU launches
     hipStream_t side_stream; hipEvent_t ev_fork, ev_join;
@@ -1779,6 +1826,8 @@ struct rl4rs_dien {
     bool din_rows_auto;    // k_din_x at group == 1: 8 or 16 rows per workgroup from the active row count, on the device (RL4RS_DIEN_OPT_DIN_ROWS16: always 16)
     int32_t *dd_dstart, *dd_dlist, *dd_dcur;      // duplicate lists of the last forward (RowDedupArgs)
     bool row_dedup;        // on wherever k_din_x and k_augru_x are the selected kernels (RL4RS_DIEN_OPT_NO_ROW_DEDUP: off)
+    bool tier2_rows;       // row dedup: the category kernel, the dense / q-side GEMMs and the head GEMM on the active rows too (DESIGN 25;
+                           // RL4RS_DIEN_OPT_NO_TIER2_ROWS: over all R rows).  Decided per forward (rl4rs_dien_forward: tier2)
     int32_t* dd_rep;       // [max_rows] representative of every row group of the last forward
     int32_t* dd_active;    // [max_rows] the representatives in processing order
     int32_t* dd_nact;      // [0] their number, [1] k_row_dedup's workgroup ticket
@@ -2175,6 +2224,7 @@ int rl4rs_dien_create(const rl4rs_dien_cfg* c, const rl4rs_dien_weights* w, void
     n->dd_rep = n->dd_active = n->dd_nact = nullptr;
     n->dd_dstart = n->dd_dlist = n->dd_dcur = nullptr;
     n->dup_store = n->row_dedup && (opts & RL4RS_DIEN_OPT_DUP_STORE) != 0;
+    n->tier2_rows = n->row_dedup && !(opts & RL4RS_DIEN_OPT_NO_TIER2_ROWS);
     n->din_rows_auto = !(opts & RL4RS_DIEN_OPT_DIN_ROWS16);
     if (n->row_dedup) {
         float* f = nullptr;
@@ -2346,11 +2396,20 @@ int rl4rs_dien_forward(rl4rs_dien* n, int32_t R, int32_t group, const float* den
     n->obs_mirror_used = false;
     struct MirrorOnce { rl4rs_dien* n; ~MirrorOnce() { n->obs_mirror = nullptr; n->obs_last = nullptr; } } mirror_once{n};       // one forward only
     RL4RS_REQUIRE(!n->obs_last || prob, "dien_forward: rl4rs_dien_set_obs_last needs a forward that returns probabilities");
+    // Second tier on the active rows only: with the row dedup on, the category kernel, the dense tower, the q-side term
+    // and the head GEMM take the active list too and k_row_expand, behind the head GEMM, gives a duplicate everything it lacks.
+    // Only in the default forms of those launches, and never with the head's host mirror armed, dup_store or dense_fork:
+    // everywhere else the forward issues the launches it issued before (as with RL4RS_DIEN_OPT_NO_TIER2_ROWS)
+    const bool tier2 = n->row_dedup && n->tier2_rows && !n->dup_store && !n->dense_fork && !(obs && n->obs_mirror) &&
+                       n->gemm16 && n->ptab && n->tsum && n->cat_v2 && E == 128 && Cn <= 24 && n->dense_chain && U <= 128 && U % 16 == 0;
+    const G16RowMap rmap = {n->dd_active, n->dd_nact, group};
+    const G16RowMap* const map2 = tier2 ? &rmap : nullptr;
+    const int32_t* const t2_order = tier2 ? n->dd_active : nullptr;
     auto dense_tower = [&](hipStream_t s2) -> int {
         int r2;
         if (n->gemm16 && n->dense_chain && U <= 128 && U % 16 == 0) {      // both layers in one launch, the hidden tile stays in LDS
             if ((r2 = launch_gemm_h16_chain(dense, n->Dn, n->dense_w1, n->dense_b1, U, n->Dn, 1, n->dense_w2, n->dense_b2,
-                                            n->allf + off_d, F, U, 1, R, s2))) return r2;
+                                            n->allf + off_d, F, U, 1, R, s2, map2))) return r2;
         } else {
             if ((r2 = scorer_gemm(n, dense, n->Dn, n->dense_w1, n->dense_b1, n->dh, U, R, U, n->Dn, 1, s2))) return r2;
             if ((r2 = scorer_gemm(n, n->dh, U, n->dense_w2, n->dense_b2, n->allf + off_d, F, R, U, U, 1, s2))) return r2;
@@ -2393,21 +2452,21 @@ int rl4rs_dien_forward(rl4rs_dien* n, int32_t R, int32_t group, const float* den
             // rows in groups that (normally) share all but the last category id: one workgroup per group, shared gathers once
             const size_t smem = cat_attn2g_smem(group, Cn);
             if (group == 8)
-                hipLaunchKernelGGL(k_cat_attn2g<8>, dim3(ngroups), dim3(512), smem, st, cat, Cn, n->H, n->cat_emb, n->seq_emb, n->allf, F,
-                                   off_c, n->q, n->ptab ? 0 : 1, (n->fp16x2 && n->cat16) ? 1 : 0, n->ptab, n->obs_b, n->tsum);
+                hipLaunchKernelGGL((k_cat_attn2g<8, 8>), dim3(ngroups), dim3(512), smem, st, cat, Cn, n->H, n->cat_emb, n->seq_emb, n->allf, F,
+                                   off_c, n->q, n->ptab ? 0 : 1, (n->fp16x2 && n->cat16) ? 1 : 0, n->ptab, n->obs_b, n->tsum, t2_order, n->dd_nact);
             else
-                hipLaunchKernelGGL(k_cat_attn2g<9>, dim3(ngroups), dim3(576), smem, st, cat, Cn, n->H, n->cat_emb, n->seq_emb, n->allf, F,
-                                   off_c, n->q, n->ptab ? 0 : 1, (n->fp16x2 && n->cat16) ? 1 : 0, n->ptab, n->obs_b, n->tsum);
+                hipLaunchKernelGGL((k_cat_attn2g<9, RL4RS_CAT9_WAVES>), dim3(ngroups), dim3(64 * RL4RS_CAT9_WAVES), smem, st, cat, Cn, n->H, n->cat_emb, n->seq_emb, n->allf, F,
+                                   off_c, n->q, n->ptab ? 0 : 1, (n->fp16x2 && n->cat16) ? 1 : 0, n->ptab, n->obs_b, n->tsum, t2_order, n->dd_nact);
         } else if (n->cat_v2 && E == 128 && Cn <= 24) {
             size_t smem = (size_t)4 * (Cn * (64 + 4) + 32) * 4;
             if (Cn == 21)
                 hipLaunchKernelGGL((k_cat_attn2<21, true>), dim3((R + 3) / 4), dim3(256), smem, st, cat, R, Cn, n->H, n->cat_emb,
                                    n->seq_emb, n->allf, F, off_c, n->q, n->ptab ? 0 : 1, (n->fp16x2 && n->cat16) ? 1 : 0,
-                                   n->ptab, n->obs_b, n->tsum);
+                                   n->ptab, n->obs_b, n->tsum, t2_order, n->dd_nact, group);
             else
                 hipLaunchKernelGGL((k_cat_attn2<24, false>), dim3((R + 3) / 4), dim3(256), smem, st, cat, R, Cn, n->H, n->cat_emb,
                                    n->seq_emb, n->allf, F, off_c, n->q, n->ptab ? 0 : 1, (n->fp16x2 && n->cat16) ? 1 : 0,
-                                   n->ptab, n->obs_b, n->tsum);
+                                   n->ptab, n->obs_b, n->tsum, t2_order, n->dd_nact, group);
         } else {
             size_t smem = (size_t)4 * (Cn * (E + 4) + 32) * 4;
             hipLaunchKernelGGL(k_cat_attn, dim3((R + 3) / 4), dim3(256), smem, st, cat, R, Cn, E, n->H, n->cat_emb,
@@ -2427,7 +2486,7 @@ int rl4rs_dien_forward(rl4rs_dien* n, int32_t R, int32_t group, const float* den
         dt.a = dense; dt.lda = n->Dn; dt.wp = n->dense_w1; dt.bias = n->dense_b1; dt.M = R; dt.N = U; dt.K = n->Dn; dt.act = 1;
         dt.wp2 = n->dense_w2; dt.bias2 = n->dense_b2; dt.c2 = n->allf + off_d; dt.ldc2 = F; dt.N2 = U; dt.act2 = 1;
         qs.a = n->q; qs.lda = E; qs.wp = n->w1ac_all; qs.c = n->qa; qs.ldc = S * ATT_H1; qs.M = R; qs.N = S * ATT_H1; qs.K = E; qs.act = 0;
-        if ((rc = launch_gemm_h16_pair(dt, qs, st))) return rc;
+        if ((rc = launch_gemm_h16_pair(dt, qs, st, map2))) return rc;
     } else if (!forked) {
         Prof p(n, KID_DENSE, st);
         if ((rc = dense_tower(st))) return rc;
@@ -2440,7 +2499,11 @@ int rl4rs_dien_forward(rl4rs_dien* n, int32_t R, int32_t group, const float* den
         a.slots = slots; a.slots_stride = ngroups; a.pld = n->PLD; a.q = n->q;
         a.qa = n->qa; a.qa_stride = ATT_H1; a.qa_ld = S * ATT_H1;       // one GEMM for the q-side term of every input: [R, S*64]
         const bool h16 = n->fp16x2 && n->din16;
-        if (!grouped && (rc = scorer_gemm(n, n->q, E, n->w1ac_all, nullptr, n->qa, S * ATT_H1, R, S * ATT_H1, E, 0, st))) return rc;
+        if (!grouped) {
+            rc = tier2 ? launch_gemm_h16(n->q, E, n->w1ac_all, nullptr, n->qa, S * ATT_H1, R, S * ATT_H1, E, 0, st, nullptr, 0, nullptr, 0, map2)
+                       : scorer_gemm(n, n->q, E, n->w1ac_all, nullptr, n->qa, S * ATT_H1, R, S * ATT_H1, E, 0, st);
+            if (rc) return rc;
+        }
         for (int s = 0; s < S; ++s) {
             a.h1[s] = n->h1[s]; a.h1f[s] = n->h1f[s]; a.proj[s] = n->proj[s]; a.w1ac[s] = n->w1ac[s]; a.w1d[s] = n->w1d[s]; a.w1d16[s] = n->w1d16[s];
             a.w2[s] = n->att_w2[s]; a.b2[s] = n->att_b2[s]; a.w3[s] = n->att_w3[s]; a.b3[s] = n->att_b3[s];
@@ -2546,17 +2609,22 @@ int rl4rs_dien_forward(rl4rs_dien* n, int32_t R, int32_t group, const float* den
         ;
         RL4RS_LAUNCH_CHECK();
     }
-    if (dedup && !n->dup_store) {     // the duplicates' AUGRU states and attention scores, in front of the head GEMM
+    float* obs_out = obs ? obs : n->obs_tmp;
+    // the duplicates' rows: in front of the head GEMM (AUGRU states and attention scores), or - second tier on the active rows -
+    // behind it (the whole all-feature row, the scores, q and the head output)
+    auto row_expand = [&]() -> int {
         Prof p(n, KID_DEDUP, st);
         RowExpandArgs a;
         memset(&a, 0, sizeof(a));
-        a.R = R; a.group = group; a.n_groups = ngroups; a.S = S; a.L = L; a.ncol = S * NH2;
+        a.R = R; a.group = group; a.n_groups = ngroups; a.S = S; a.L = L; a.ncol = tier2 ? S * NH2 + U + E : S * NH2;
         a.rep = n->dd_rep; a.n_active = n->dd_nact;
         a.allf = n->allf; a.ld = F; a.scores = n->scores; a.scores_stride = (int64_t)n->c.max_rows * L;
+        if (tier2) { a.q = n->q; a.E = E; a.obs = obs_out; a.obs_dim = OBS_DIM; }
         hipLaunchKernelGGL(k_row_expand, dim3((R + 3) / 4), dim3(256), 0, st, a);
         RL4RS_LAUNCH_CHECK();
-    }
-    float* obs_out = obs ? obs : n->obs_tmp;
+        return RL4RS_OK;
+    };
+    if (dedup && !n->dup_store && !tier2 && (rc = row_expand())) return rc;
     if (forked) RL4RS_HIP_TRY(hipStreamWaitEvent(st, n->ev_join, 0));
     {
         Prof p(n, KID_HEAD, st);
@@ -2564,7 +2632,7 @@ int rl4rs_dien_forward(rl4rs_dien* n, int32_t R, int32_t group, const float* den
             const int Kh = S * NH2 + U + E;
             if (n->gemm16) {
                 float* mirror = (obs && n->obs_mirror) ? n->obs_mirror : nullptr;
-                rc = launch_gemm_h16(n->allf, F, n->obs_w, nullptr, obs_out, OBS_DIM, R, OBS_DIM, Kh, 1, st, n->tsum, OBS_DIM, mirror, OBS_DIM);
+                rc = launch_gemm_h16(n->allf, F, n->obs_w, nullptr, obs_out, OBS_DIM, R, OBS_DIM, Kh, 1, st, n->tsum, OBS_DIM, mirror, OBS_DIM, map2);
                 n->obs_mirror_used = mirror != nullptr;
             }
             else rc = launch_gemm_packed(n->allf, F, n->obs_w, nullptr, obs_out, OBS_DIM, R, OBS_DIM, Kh, 1, st, n->tsum, OBS_DIM);
@@ -2578,6 +2646,7 @@ int rl4rs_dien_forward(rl4rs_dien* n, int32_t R, int32_t group, const float* den
             if ((rc = scorer_gemm(n, n->allf, F, n->obs_w, n->obs_b, obs_out, OBS_DIM, R, OBS_DIM, n->F, 1, st))) return rc;
         }
     }
+    if (tier2 && (rc = row_expand())) return rc;
     if (prob) {
         Prof p(n, KID_PROB, st);
         hipLaunchKernelGGL(k_head_prob, dim3((R + 3) / 4), dim3(256), 0, st, obs_out, R, OBS_DIM, n->K, n->out_w,

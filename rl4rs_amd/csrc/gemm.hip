@@ -578,6 +578,24 @@ __global__ __launch_bounds__(256) void k_gemm_h16(const float* __restrict__ A, i
                                                   const float* __restrict__ bias, float* __restrict__ C,
                                                   int64_t ldc, int M, int N, int K, int act,
                                                   const float* __restrict__ addend, int64_t ldadd, G16Chain chain) {
+    constexpr bool MAP = false;
+    const G16RowMap rmap = {};
+    int* const s_row = nullptr;
+#define RL4RS_G16_BX blockIdx.x
+#include "gemm_h16_tile.inc"
+#undef RL4RS_G16_BX
+}
+
+// The same tile body over the ACTIVE rows of a scorer forward (row_dedup.hpp): its own instantiations, so that
+// k_gemm_h16 above - shared with every caller outside the scorer - keeps its code.  Grid sized for M on the host.
+template <int WM, bool VEC>
+__global__ __launch_bounds__(256) void k_gemm_h16_map(const float* __restrict__ A, int64_t lda,
+                                                      const char* __restrict__ Wp, int KB,
+                                                      const float* __restrict__ bias, float* __restrict__ C,
+                                                      int64_t ldc, int M, int N, int K, int act,
+                                                      const float* __restrict__ addend, int64_t ldadd, G16Chain chain, G16RowMap rmap) {
+    constexpr bool MAP = true;
+    __shared__ int s_row[32 * WM];
 #define RL4RS_G16_BX blockIdx.x
 #include "gemm_h16_tile.inc"
 #undef RL4RS_G16_BX
@@ -602,6 +620,25 @@ __global__ __launch_bounds__(256) void k_gemm_h16_pair(G16Pair g) {
     const float* __restrict__ bias = p.bias; float* __restrict__ C = p.C; const int64_t ldc = p.ldc;
     const int M = p.M, N = p.N, K = p.K, act = p.act;
     const float* __restrict__ addend = p.addend; const int64_t ldadd = p.ldadd; const G16Chain chain = p.chain;
+    constexpr bool MAP = false;
+    const G16RowMap rmap = {};
+    int* const s_row = nullptr;
+#define RL4RS_G16_BX bx
+#include "gemm_h16_tile.inc"
+#undef RL4RS_G16_BX
+}
+// ... and over the active rows of a scorer forward: both problems share the row map (the dense tower and the q-side term)
+template <int WM, bool VEC>
+__global__ __launch_bounds__(256) void k_gemm_h16_pair_map(G16Pair g, G16RowMap rmap) {
+    const unsigned second = blockIdx.x >= g.tiles0 ? 1u : 0u;
+    const unsigned bx = blockIdx.x - (second ? g.tiles0 : 0u);
+    const G16Problem& p = g.p[second];
+    const float* __restrict__ A = p.A; const int64_t lda = p.lda; const char* __restrict__ Wp = p.Wp; const int KB = p.KB;
+    const float* __restrict__ bias = p.bias; float* __restrict__ C = p.C; const int64_t ldc = p.ldc;
+    const int M = p.M, N = p.N, K = p.K, act = p.act;
+    const float* __restrict__ addend = p.addend; const int64_t ldadd = p.ldadd; const G16Chain chain = p.chain;
+    constexpr bool MAP = true;
+    __shared__ int s_row[32 * WM];
 #define RL4RS_G16_BX bx
 #include "gemm_h16_tile.inc"
 #undef RL4RS_G16_BX
@@ -777,24 +814,35 @@ std::vector<float> pack_gemm_weight_h16(const float* w, int64_t ldw, int K, int 
 }
 
 static int launch_gemm_h16_impl(const float* a, int64_t lda, const float* wp16, const float* bias, float* c, int64_t ldc,
-                                int M, int N, int K, int act, hipStream_t st, const float* addend, int64_t ldadd, G16Chain chain);
+                                int M, int N, int K, int act, hipStream_t st, const float* addend, int64_t ldadd, G16Chain chain,
+                                const G16RowMap* map = nullptr);
+
+// the mapped form addresses whole matrices through one buffer descriptor each: every row must lie inside its 31-bit byte offsets
+static bool g16_map_fits(int M, int64_t ld, int ncol) { return ld <= 0x7fffffff && ((int64_t)M - 1) * ld + ncol < ((int64_t)1 << 29); }
+static bool g16_map_ok(const G16RowMap* map, const float* a, int64_t lda, float* c, int64_t ldc, int M, int N, int K,
+                       const float* addend, int64_t ldadd, const G16Chain& ch) {
+    return map && map->active && map->n_active && map->group >= 1 && !ch.mirror && g16_map_fits(M, lda, K) &&
+           (ch.wp2 ? g16_map_fits(M, ch.ldc2, ch.n2) : (c && g16_map_fits(M, ldc, N))) && (!addend || g16_map_fits(M, ldadd, N));
+}
 
 int launch_gemm_h16(const float* a, int64_t lda, const float* wp16, const float* bias, float* c, int64_t ldc,
-                    int M, int N, int K, int act, hipStream_t st, const float* addend, int64_t ldadd, float* mirror, int64_t ldm) {
+                    int M, int N, int K, int act, hipStream_t st, const float* addend, int64_t ldadd, float* mirror, int64_t ldm,
+                    const G16RowMap* map) {
     G16Chain none = {};
     none.mirror = mirror; none.ldm = ldm;
-    return launch_gemm_h16_impl(a, lda, wp16, bias, c, ldc, M, N, K, act, st, addend, ldadd, none);
+    return launch_gemm_h16_impl(a, lda, wp16, bias, c, ldc, M, N, K, act, st, addend, ldadd, none, map);
 }
 
 // c2 = act2(act1(a W1 + b1) W2 + b2) in one launch; N1 <= 128 and a multiple of 16, N2 <= 128 (else RL4RS_EINVAL)
 int launch_gemm_h16_chain(const float* a, int64_t lda, const float* wp1, const float* bias1, int N1, int K1, int act1,
-                          const float* wp2, const float* bias2, float* c2, int64_t ldc2, int N2, int act2, int M, hipStream_t st) {
+                          const float* wp2, const float* bias2, float* c2, int64_t ldc2, int N2, int act2, int M, hipStream_t st,
+                          const G16RowMap* map) {
     if (N1 > 128 || (N1 & 15) || N2 > 128 || N1 <= 0 || N2 <= 0) {
         set_error("gemm_h16_chain: unsupported widths %d -> %d", N1, N2);
         return RL4RS_EINVAL;
     }
     G16Chain ch = {reinterpret_cast<const char*>(wp2), (N1 + 15) / 16, bias2, c2, ldc2, N2, act2, nullptr, 0};
-    return launch_gemm_h16_impl(a, lda, wp1, bias1, nullptr, 0, M, N1, K1, act1, st, nullptr, 0, ch);
+    return launch_gemm_h16_impl(a, lda, wp1, bias1, nullptr, 0, M, N1, K1, act1, st, nullptr, 0, ch, map);
 }
 
 // the kernel a problem goes to: 0 k_gemm_h16_wres, else k_gemm_h16 with WM (1: 32-row tiles, 2: 64-row tiles); ny = gridDim.y
@@ -810,7 +858,7 @@ static int gemm_h16_route(const float* a, int64_t lda, int M, int N, int K, bool
 // x and y are independent (neither reads what the other writes): ONE launch (k_gemm_h16_pair) when both take the same tile
 // form of k_gemm_h16 with gridDim.y == 1, the two launches of launch_gemm_h16 / launch_gemm_h16_chain otherwise.  Bit-identical
 // either way.  The problem with more k-tiles goes first in the grid (its workgroups run longest).
-int launch_gemm_h16_pair(const GemmH16Desc& x, const GemmH16Desc& y, hipStream_t st) {
+int launch_gemm_h16_pair(const GemmH16Desc& x, const GemmH16Desc& y, hipStream_t st, const G16RowMap* map) {
     const GemmH16Desc* d[2] = {&x, &y};
     bool vec[2], ok = true;
     int ny[2], wm[2];
@@ -828,7 +876,7 @@ int launch_gemm_h16_pair(const GemmH16Desc& x, const GemmH16Desc& y, hipStream_t
             G16Chain ch = {};
             if (d[i]->wp2) ch = G16Chain{reinterpret_cast<const char*>(d[i]->wp2), (d[i]->N + 15) / 16, d[i]->bias2, d[i]->c2, d[i]->ldc2, d[i]->N2, d[i]->act2, nullptr, 0};
             int rc = launch_gemm_h16_impl(d[i]->a, d[i]->lda, d[i]->wp, d[i]->bias, d[i]->c, d[i]->ldc, d[i]->M, d[i]->N, d[i]->K, d[i]->act, st,
-                                          d[i]->addend, d[i]->ldadd, ch);
+                                          d[i]->addend, d[i]->ldadd, ch, map);
             if (rc) return rc;
         }
         return RL4RS_OK;
@@ -846,6 +894,15 @@ int launch_gemm_h16_pair(const GemmH16Desc& x, const GemmH16Desc& y, hipStream_t
     }
     g.tiles0 = (unsigned)((g.p[0].M + rows - 1) / rows);
     const dim3 grid(g.tiles0 + (unsigned)((g.p[1].M + rows - 1) / rows), 1);
+    bool mapped = map != nullptr;
+    for (int i = 0; i < 2; ++i)
+        mapped = mapped && g16_map_ok(map, g.p[i].A, g.p[i].lda, g.p[i].C, g.p[i].ldc, g.p[i].M, g.p[i].N, g.p[i].K, g.p[i].addend, g.p[i].ldadd, g.p[i].chain);
+    if (mapped) {       // the row map of a scorer forward: same grid, the workgroups behind the active rows leave at once
+        if (wm[0] == 1) { if (vec[0]) hipLaunchKernelGGL((k_gemm_h16_pair_map<1, true>), grid, dim3(256), 0, st, g, *map); else hipLaunchKernelGGL((k_gemm_h16_pair_map<1, false>), grid, dim3(256), 0, st, g, *map); }
+        else { if (vec[0]) hipLaunchKernelGGL((k_gemm_h16_pair_map<2, true>), grid, dim3(256), 0, st, g, *map); else hipLaunchKernelGGL((k_gemm_h16_pair_map<2, false>), grid, dim3(256), 0, st, g, *map); }
+        RL4RS_LAUNCH_CHECK();
+        return RL4RS_OK;
+    }
     if (wm[0] == 1) { if (vec[0]) hipLaunchKernelGGL((k_gemm_h16_pair<1, true>), grid, dim3(256), 0, st, g); else hipLaunchKernelGGL((k_gemm_h16_pair<1, false>), grid, dim3(256), 0, st, g); }
     else { if (vec[0]) hipLaunchKernelGGL((k_gemm_h16_pair<2, true>), grid, dim3(256), 0, st, g); else hipLaunchKernelGGL((k_gemm_h16_pair<2, false>), grid, dim3(256), 0, st, g); }
     RL4RS_LAUNCH_CHECK();
@@ -862,7 +919,8 @@ static int device_cus() {
 }
 
 static int launch_gemm_h16_impl(const float* a, int64_t lda, const float* wp16, const float* bias, float* c, int64_t ldc,
-                                int M, int N, int K, int act, hipStream_t st, const float* addend, int64_t ldadd, G16Chain chain) {
+                                int M, int N, int K, int act, hipStream_t st, const float* addend, int64_t ldadd, G16Chain chain,
+                                const G16RowMap* map) {
     if (M <= 0 || N <= 0 || K <= 0) return RL4RS_OK;
     const int KB = (K + 15) / 16;
     const char* wp = reinterpret_cast<const char*>(wp16);
@@ -880,6 +938,14 @@ static int launch_gemm_h16_impl(const float* a, int64_t lda, const float* wp16, 
     }
     const bool small = wm == 1;
     const dim3 grid(small ? (M + 31) / 32 : (M + 63) / 64, ny);
+    if (g16_map_ok(map, a, lda, c, ldc, M, N, K, addend, ldadd, chain)) {
+#define RL4RS_G16_LAUNCH(WM_, VEC_) hipLaunchKernelGGL((k_gemm_h16_map<WM_, VEC_>), grid, dim3(256), 0, st, a, lda, wp, KB, bias, c, ldc, M, N, K, act, addend, ldadd, chain, *map)
+        if (small) { if (vec) RL4RS_G16_LAUNCH(1, true); else RL4RS_G16_LAUNCH(1, false); }
+        else { if (vec) RL4RS_G16_LAUNCH(2, true); else RL4RS_G16_LAUNCH(2, false); }
+#undef RL4RS_G16_LAUNCH
+        RL4RS_LAUNCH_CHECK();
+        return RL4RS_OK;
+    }
 #define RL4RS_G16_LAUNCH(WM_, VEC_) hipLaunchKernelGGL((k_gemm_h16<WM_, VEC_>), grid, dim3(256), 0, st, a, lda, wp, KB, bias, c, ldc, M, N, K, act, addend, ldadd, chain)
     if (small) { if (vec) RL4RS_G16_LAUNCH(1, true); else RL4RS_G16_LAUNCH(1, false); }
     else { if (vec) RL4RS_G16_LAUNCH(2, true); else RL4RS_G16_LAUNCH(2, false); }

@@ -1,6 +1,12 @@
 // The tile body of k_gemm_h16 and k_gemm_h16_pair (gemm.hip), included into both kernels as TEXT so that k_gemm_h16 compiles to
 // exactly the code it had as a single kernel.  Expects in scope: WM, VEC; A, lda, Wp, KB, bias, C, ldc, M, N, K, act, addend,
-// ldadd, chain (all wave-uniform) and RL4RS_G16_BX = the workgroup's row-tile index within its problem.
+// ldadd, chain (all wave-uniform) and RL4RS_G16_BX = the workgroup's row-tile index within its problem; MAP (constexpr bool), rmap
+// (G16RowMap) and s_row (int[BM] in LDS when MAP).  MAP = false (k_gemm_h16, k_gemm_h16_pair): every `if constexpr (MAP)` below is
+// no code and the kernels compile to the instruction text they had without it.  MAP = true (k_gemm_h16_map, k_gemm_h16_pair_map;
+// DESIGN 25): tile position p works on physical row active[p / group] * group + p % group of A, C, c2 and the addend, the row
+// bound is min(M, n_active * group) read here, a workgroup whose first position lies behind it leaves before its first barrier,
+// positions of a partial last tile behind the bound recompute the last active row and store nothing.  Per output element the
+// k-blocks, the MFMA order and the epilogue expression are those of the unmapped form.
     constexpr int BM = 32 * WM, BK = 64, KBT = BK / 16;
     constexpr int SLAB = BM * 16 + 16, PLANE = 2 * KBT * SLAB;
     __shared__ __attribute__((aligned(16))) char As[2][2][PLANE];          // [buffer][hi / lo]
@@ -8,6 +14,31 @@
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int half = lane >> 5, li = lane & 31;
     const int m0 = RL4RS_G16_BX * BM;
+    int Mb = M;
+    int arow[WM];                                  // MAP: the physical rows of this thread's A chunks
+    if constexpr (MAP) {
+        // the list entries of this thread's positions are requested BESIDE the bound, not behind it (the list is allocated for
+        // every group; entries behind n_active are stale and then unused): one memory round trip in front of the first A tile
+        int apos[WM], agrp[WM], aent[WM];
+#pragma unroll
+        for (int p = 0; p < WM; ++p) {
+            apos[p] = min(m0 + ((tid + p * 256) >> 3), M - 1);
+            agrp[p] = rmap.group == 1 ? apos[p] : apos[p] / rmap.group;
+            aent[p] = rmap.active[agrp[p]];
+        }
+        Mb = min(M, rmap.n_active[0] * rmap.group);
+        if (m0 >= Mb) return;
+#pragma unroll
+        for (int p = 0; p < WM; ++p) {
+            if (apos[p] >= Mb) {                   // a position behind the bound (partial last tile only): the last active row
+                apos[p] = Mb - 1;
+                agrp[p] = apos[p] / rmap.group;
+                aent[p] = rmap.active[agrp[p]];
+            }
+            arow[p] = aent[p] * rmap.group + (apos[p] - agrp[p] * rmap.group);
+            if ((tid & 7) == 0) s_row[(tid + p * 256) >> 3] = arow[p];       // for the epilogue, behind the main loop's barriers
+        }
+    }
     const int nt = blockIdx.y * 4 + wave;
     const int NT = (N + 31) / 32;
     const bool tile_ok = nt < NT;
@@ -34,13 +65,14 @@
     // waits with exact counts; guarded loads had forced a full drain of the weight ring at every k-tile); columns >= K of
     // a row (they exist when lda > K) are cleared with selects
     const int rows_here = min(BM, M - m0);
+    // (MAP: the descriptor spans all M rows, the launcher has checked that they fit its 32-bit offsets)
     const __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(A + (size_t)m0 * lda), 0, (int)((((int64_t)rows_here - 1) * lda + K) * 4), 0x00020000);
+        const_cast<float*>(A + (size_t)(MAP ? 0 : m0) * lda), 0, (int)((((int64_t)(MAP ? M : rows_here) - 1) * lda + K) * 4), 0x00020000);
     auto gload = [&](float4 (&st)[WM][2], int kt) {
 #pragma unroll
         for (int p = 0; p < WM; ++p) {
             const int c = tid + p * 256;
-            const int r = c >> 3, gk = kt * BK + (c & 7) * 8;
+            const int r = MAP ? arow[p] : c >> 3, gk = kt * BK + (c & 7) * 8;
             const int voff = (int)(((int64_t)r * lda + gk) * 4);
             float x[8];
             if (VEC) {
@@ -174,6 +206,22 @@
             }
         }
         const int col2 = wave * 32 + li;
+        if constexpr (MAP) {
+            if (tile2_ok && col2 < chain.n2) {
+                const float bv2 = chain.bias2 ? chain.bias2[col2] : 0.f;
+                const __amdgpu_buffer_rsrc_t rs_c2 = __builtin_amdgcn_make_buffer_rsrc(chain.c2, 0, (int)((((int64_t)M - 1) * chain.ldc2 + chain.n2) * 4), 0x00020000);
+#pragma unroll
+                for (int w = 0; w < WM; ++w)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int rl = 32 * w + (r & 3) + 8 * (r >> 2) + 4 * half;
+                        if (m0 + rl < Mb)
+                            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, apply_act(acc2[w][r] * inv_s2 + bv2, chain.act2)), rs_c2,
+                                                                  (s_row[rl] * (int)chain.ldc2 + col2) * 4, 0, 0);
+                    }
+            }
+            return;
+        }
         if (tile2_ok && col2 < chain.n2) {
             const float bv2 = chain.bias2 ? chain.bias2[col2] : 0.f;
             const __amdgpu_buffer_rsrc_t rs_c2 = __builtin_amdgcn_make_buffer_rsrc(chain.c2 + (size_t)m0 * chain.ldc2, 0,
@@ -193,6 +241,34 @@
         // the hardware and the row part of an address is a scalar - one instruction per element instead of a compare, an exec
         // mask and a 64-bit address (see k_gemm_h16_wres: that VALU work was comparable to the tile's MFMA time)
         const float bv = bias ? bias[col] : 0.f;
+        if constexpr (MAP) {                       // (no mirror in this form: the launcher keeps such launches unmapped)
+            const __amdgpu_buffer_rsrc_t rs_c = __builtin_amdgcn_make_buffer_rsrc(C, 0, (int)((((int64_t)M - 1) * ldc + N) * 4), 0x00020000);
+            float add[WM][16];
+            if (addend) {
+                const __amdgpu_buffer_rsrc_t rs_d = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(addend), 0, (int)((((int64_t)M - 1) * ldadd + N) * 4), 0x00020000);
+#pragma unroll
+                for (int w = 0; w < WM; ++w)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r)
+                        add[w][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
+                            rs_d, (s_row[32 * w + (r & 3) + 8 * (r >> 2) + 4 * half] * (int)ldadd + col) * 4, 0, 0));
+            } else {
+#pragma unroll
+                for (int w = 0; w < WM; ++w)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) add[w][r] = 0.f;
+            }
+#pragma unroll
+            for (int w = 0; w < WM; ++w)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int rl = 32 * w + (r & 3) + 8 * (r >> 2) + 4 * half;
+                    if (m0 + rl < Mb)
+                        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, apply_act(acc[w][r] * inv_s + bv + add[w][r], act)), rs_c,
+                                                              (s_row[rl] * (int)ldc + col) * 4, 0, 0);
+                }
+            return;
+        }
         const __amdgpu_buffer_rsrc_t rs_c = __builtin_amdgcn_make_buffer_rsrc(C + (size_t)m0 * ldc, 0, (int)((((int64_t)rows_here - 1) * ldc + N) * 4), 0x00020000);
         const int ldc4 = (int)ldc * 4, c_voff = (4 * half * (int)ldc + col) * 4;
         if (addend) {

@@ -243,15 +243,21 @@ __global__ __launch_bounds__(ROW_DEDUP_THREADS) void k_row_dedup(RowDedupArgs a)
 }
 
 struct RowExpandArgs {
-    int R, group, n_groups, S, L, ncol;             // ncol = S * NH2: the AUGRU final-state columns of an all-feature row
+    int R, group, n_groups, S, L, ncol;             // ncol: the leading columns of an all-feature row to copy (S * NH2 = the AUGRU final
+                                                    // states; second tier on the active rows: S * NH2 + U + E = the whole row)
     const int32_t* rep;
     const int32_t* n_active;
     float* allf; int64_t ld;
     float* scores; int64_t scores_stride;           // [S][scores_stride] rows of L
+    // second tier on the active rows (NULL otherwise): the query row [R, E] and the head output [R, obs_dim] as well
+    float* q; int E;
+    float* obs; int obs_dim;
 };
 
 // one wave per row: a row of a non-representative group takes its AUGRU states and attention scores from the same row of the
-// representative.  Nothing to do (one scalar load per wave) when every group is its own representative.
+// representative - and, when the second tier ran on the active rows only (the launch then sits behind the head GEMM), the rest of
+// its all-feature row, its query row and its head output.  Nothing to do (one scalar load per wave) when every group is its own
+// representative.
 __global__ __launch_bounds__(256) void k_row_expand(RowExpandArgs a) {
     if (a.n_active[0] == a.n_groups) return;
     const int lane = threadIdx.x & 63;
@@ -271,6 +277,18 @@ __global__ __launch_bounds__(256) void k_row_expand(RowExpandArgs a) {
     for (int sq = 0; sq < a.S; ++sq) {
         float* sc = a.scores + (int64_t)sq * a.scores_stride;
         for (int i = lane; i < a.L; i += 64) sc[(int64_t)row * a.L + i] = sc[(int64_t)src * a.L + i];
+    }
+    if (a.q) {
+        for (int i = lane; i < a.E; i += 64) a.q[(int64_t)row * a.E + i] = a.q[(int64_t)src * a.E + i];
+    }
+    if (a.obs) {
+        float* od = a.obs + (int64_t)row * a.obs_dim;
+        const float* os = a.obs + (int64_t)src * a.obs_dim;
+        if ((a.obs_dim & 3) == 0 && ((uintptr_t)a.obs & 15) == 0) {
+            for (int i = lane; i < a.obs_dim / 4; i += 64) reinterpret_cast<float4*>(od)[i] = reinterpret_cast<const float4*>(os)[i];
+        } else {
+            for (int i = lane; i < a.obs_dim; i += 64) od[i] = os[i];
+        }
     }
 }
 
