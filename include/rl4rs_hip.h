@@ -264,7 +264,11 @@ typedef struct rl4rs_dien_cfg {
  *                   output).  The active-row form is used only with the default category / GEMM forms, without
  *                   DUP_STORE and DENSE_FORK, and not in a forward whose head GEMM writes a host mirror (=)
  *   DIN_ROWS16      k_din_x with 16 rows per workgroup whatever the row dedup left, instead of 8 (one row per wave) when the active
- *                   rows of an observation-sized launch fit one round that way (decided on the device) (=) */
+ *                   rows of an observation-sized launch fit one round that way (decided on the device) (=)
+ *   NO_AUGRU_SHADOW an observation-sized forward (group == 1, 32-row k_augru_x, active-row second tier) keeps its seven launches:
+ *                   category kernel and dense / q-side pair in front of k_din_x, instead of k_din_xq forming q and qa for its own
+ *                   rows and the category branch and the dense tower running as a shadow plane of the AUGRU launch (k_augru_xs)
+ *                   where ceil(G / 32) * (S + 1) workgroups fit the chip, G = rl4rs_dien_set_distinct_hint (=) */
 enum {
     RL4RS_DIEN_OPT_AUGRU_H16 = 1 << 0,
     RL4RS_DIEN_OPT_AUGRU_ROWS32 = 1 << 1,
@@ -292,7 +296,9 @@ enum {
                                                   (bit-identical either way) */
     RL4RS_DIEN_OPT_NO_TIER2_ROWS = 1 << 20,    /* row dedup: category kernel, dense / q-side GEMMs and head GEMM over all R rows, k_row_expand
                                                   in front of the head GEMM (bit-identical either way) */
-    RL4RS_DIEN_OPT_ALL = (1 << 21) - 1
+    RL4RS_DIEN_OPT_NO_AUGRU_SHADOW = 1 << 21,  /* observation-sized forwards: category kernel and dense / q-side pair as launches of their own
+                                                  in front of k_din_x, no shadow plane in the AUGRU launch (bit-identical either way) */
+    RL4RS_DIEN_OPT_ALL = (1 << 22) - 1
 };
 
 /* Every mode accumulates in fp32 and meets the fp32 parity bar against the fp64 oracle (same measured error):
@@ -331,6 +337,10 @@ int rl4rs_dien_scorer_mode(rl4rs_dien* net, int32_t* mode);
 /* Row-tile form of k_augru_x for the following forwards of this handle: 0 automatic, 32, 64 (the AUGRU_ROWS* options above,
  * switchable on a live handle so that one cache can be scored by both forms). */
 int rl4rs_dien_set_augru_rows(rl4rs_dien* net, int32_t rows);
+/* Distinct row groups the row dedup is expected to leave in the following forwards of this handle (0 = no expectation: the rows of
+ * the forward).  Only sizes decisions, never results: an observation-sized forward takes the shadow-plane order (NO_AUGRU_SHADOW above)
+ * where ceil(min(n_groups, R) / 32) * (S + 1) workgroups fit the chip.  rl4rs_stepper_set_distinct_hint passes its hint on. */
+int rl4rs_dien_set_distinct_hint(rl4rs_dien* net, int32_t n_groups);
 /* Status bits since the last call (synchronises `stream`, then clears them).  RL4RS_DIEN_STATUS_FP16_RANGE: in
  * FP16X2 mode a recurrent state left the fp16 range (|h| >= 6e4, or NaN) - possible only when the attention scores
  * push the update gate outside [0, 1] until the state diverges; results of the affected forwards are invalid, use

@@ -35,7 +35,8 @@ DIEN_OPTS = {'augru_h16': 1 << 0, 'augru_rows32': 1 << 1, 'augru_rows64': 1 << 2
              'no_gru16': 1 << 5, 'no_gemm16': 1 << 6, 'no_cat16': 1 << 7, 'no_dense_chain': 1 << 8, 'no_head_tables': 1 << 9,
              'no_head_fused': 1 << 10, 'cat_v1': 1 << 11, 'no_cat_group': 1 << 12, 'dense_fork': 1 << 13, 'no_gru_pad': 1 << 14,
              'no_gemm_group': 1 << 15, 'no_row_dedup': 1 << 16, 'no_dup_store': 1 << 17, 'din_rows16': 1 << 18, 'dup_store': 1 << 19,
-             'no_tier2_rows': 1 << 20}
+             'no_tier2_rows': 1 << 20,
+             'no_augru_shadow': 1 << 21}
 POLICY_OPTS = {'tile': 0, 'ppo_fused': 1, 'ppo_rows': 2, 'resident_wgs': 3, 'ppo_std': 4}          # RL4RS_POLICY_OPT_*
 ENV_OPTS = {'rows_variant': 0}                                                       # RL4RS_ENV_OPT_*
 
@@ -258,6 +259,7 @@ SIGNATURES = {
     'rl4rs_dien_set_row_order': (_I, [_P, _P, _I32]),
     'rl4rs_dien_set_obs_last': (_I, [_P, _P]),
     'rl4rs_dien_set_augru_rows': (_I, [_P, _I32]),
+    'rl4rs_dien_set_distinct_hint': (_I, [_P, _I32]),
     'rl4rs_dien_status_word': (_I, [_P, C.POINTER(_P)]),
     'rl4rs_stepper_record_layout': (_I, [_P, C.c_uint32, _I32, C.POINTER(StepRecord)]),
     'rl4rs_env_step_record': (_I, [_P, _P, _I32, C.c_uint32, _P, _P]),

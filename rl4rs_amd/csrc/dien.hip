@@ -17,15 +17,17 @@
 
 #include "common.hpp"
 #include "recur_args.hpp"
+#include "cat_attn2_row.hpp"
+#include "augru_xs.hpp"      // AugruShadowArgs (the kernels themselves are instantiated in augru_x.hip / augru_xs.hip)
 
 namespace rl4rs {
 
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
 __device__ __forceinline__ float eluf_(float x) { return x > 0.f ? x : expm1f(x); }
-__device__ __forceinline__ int crow(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
 
-constexpr int ATT_H1 = 64, ATT_H2 = 16, OBS_DIM = 256;
+
+
 #ifndef RL4RS_AUGRU_U
 #define RL4RS_AUGRU_U 2
 #endif
@@ -43,14 +45,6 @@ constexpr int AUGRU_U = RL4RS_AUGRU_U, GRU_U = 2;   // k-blocks per register-rin
 
 
 
-#ifndef RL4RS_CAT_FAST_EXP
-#define RL4RS_CAT_FAST_EXP 0     // 1: the softmax of the category self-attention on the hardware exp2 (timing A/B, round 4)
-#endif
-#if RL4RS_CAT_FAST_EXP
-#define CAT_EXP(x) __builtin_amdgcn_exp2f(1.4426950408889634f * (x))
-#else
-#define CAT_EXP(x) expf(x)
-#endif
 // -------------------------------------------------------------------------------------------------
 // Category branch (utils.py:16-25) + attention query (dien.py:29-30, utils.py:114-115).
 // One wave per row; 4 rows per block.  Writes allf[row, off_c : off_c + E] = mean_i(softmax(E E^T) E),
@@ -243,201 +237,7 @@ __global__ __launch_bounds__(256) void k_cat_attn(const int32_t* __restrict__ ca
     }
 }
 
-// -------------------------------------------------------------------------------------------------
-// k_cat_attn2: the same category branch for the default shape (E = 128, Cn <= 24) with HALF the LDS per row.
-// k_cat_attn keeps a [Cn, E + 4] fp32 image of the row's embedding block in LDS (11.2 KB for Cn = 21): 4-row workgroups of
-// 44.8 KB fit three to a CU = 12 rows in flight per CU, but an obs-sized launch at B = 4096 has 16 rows per CU, so it ran
-// as one full round plus a one-third-full second round of the same dependent chain (ids -> gathers -> LDS -> Gram MFMAs ->
-// softmax -> pooled row), and the reward-sized launch had 12 chains per CU in flight where the register file allows 16+.
-// Here the image holds one 64-column half of the block at a time (5.8 KB per row): the Gram matrix S = E E^T is accumulated
-// over the two halves (the k order of an MFMA sum is free), and the pooled row comes from the gathered registers (lane e
-// still holds E[j][e], E[j][e + 64] of every row j) instead of re-reading the image.  22.9 KB per workgroup: seven fit a CU,
-// the register file (<= 128 VGPRs) allows 16 waves = 16 rows: an obs-sized launch is ONE round.  Bit-identical arithmetic to
-// k_cat_attn except the pooled row (register FMAs in the same j order: identical too).
-template <int MAXC, bool EXACT>
-__device__ __forceinline__ void cat_attn2_row(float* sE, int row, int lane, const int32_t* __restrict__ cat, int Cn_arg, int H,
-                                              const float* __restrict__ cat_emb, const float* __restrict__ seq_emb,
-                                              float* __restrict__ allf, int ldf, int off_c, float* __restrict__ q, int write_flat,
-                                              int h16, const float* __restrict__ ptab, const float* __restrict__ obs_b,
-                                              float* __restrict__ tsum) {
-    constexpr int E = 128, HK = 64, LE = HK + 4, TCH = 4;       // MAXC: rows held in registers; EXACT: Cn == MAXC at compile time
-    const int Cn = EXACT ? MAXC : Cn_arg;                       // (the default shape, Cn = 21: no clamps, no guards, fewer registers)
-    const int half = lane >> 5, li = lane & 31;
-    float* sW = sE + Cn * LE;
-    const int32_t* crowp = cat + (size_t)row * Cn;
-    float* frow = allf + (size_t)row * ldf + off_c;
-    const int myid = (lane < Cn) ? min(max(crowp[lane], 0), H - 1) : 0;
-    const int nq = min(10, Cn);
-    // register budget (<= 128 for four waves per SIMD): the query rows are requested first and folded into two sums as soon as
-    // they are there (they return in request order, ahead of the 48 category-row requests behind them); the head-table rows
-    // come as two chunks of 4 (requested at the top and at the half-K boundary) and the rest in one go behind the MFMAs
-    float qv0[10], qv1[10];
-#pragma unroll
-    for (int u = 0; u < 10; ++u) {
-        const float* src = seq_emb + (size_t)__builtin_amdgcn_readlane(myid, max(Cn - 10 + u, 0)) * E;      // wave-uniform: scalar base
-        qv0[u] = src[lane];
-        qv1[u] = src[lane + 64];
-    }
-    float v0[MAXC], v1[MAXC];
-#pragma unroll
-    for (int u = 0; u < MAXC; ++u) {
-        const float* src = cat_emb + (size_t)__builtin_amdgcn_readlane(myid, min(u, Cn - 1)) * E;
-        v0[u] = src[lane];
-        v1[u] = src[lane + 64];
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    float q0 = 0.f, q1 = 0.f;
-#pragma unroll
-    for (int u = 0; u < 10; ++u)
-        if (u >= 10 - nq) { q0 += qv0[u]; q1 += qv1[u]; }
-    // pinned HERE: the sums are only stored at the very end, and LLVM's sinking pass otherwise moves the twenty adds down there -
-    // which kept the twenty loaded values alive across the whole kernel and made the allocator spill eight of them, each spill a
-    // "s_waitcnt vmcnt(0); scratch_store" right behind its load: eight serialised memory round trips at the top of every row
-    asm volatile("" : "+v"(q0), "+v"(q1));
-    __builtin_amdgcn_sched_barrier(0);
-    const bool do_t = tsum != nullptr;
-    float4 tacc = make_float4(0.f, 0.f, 0.f, 0.f), tv[TCH];
-    auto t_request = [&](int c) {
-#pragma unroll
-        for (int u = 0; u < TCH; ++u) {
-            const int j = min(c * TCH + u, Cn - 1);
-            tv[u] = reinterpret_cast<const float4*>(ptab + ((size_t)j * H + __builtin_amdgcn_readlane(myid, j)) * OBS_DIM)[lane];
-        }
-    };
-    auto t_add = [&](int c) {
-#pragma unroll
-        for (int u = 0; u < TCH; ++u)
-            if (c * TCH + u < Cn) { tacc.x += tv[u].x; tacc.y += tv[u].y; tacc.z += tv[u].z; tacc.w += tv[u].w; }
-    };
-    // stage c: sum chunk c - 1, request chunk c (same summation order as k_cat_attn: bias, then rows 0, 1, 2, ...)
-#define CAT2_T_STAGE(c) do { if (do_t) { if ((c) > 0) t_add((c) - 1); if ((c) * TCH < Cn && (c) * TCH < MAXC) t_request(c); } } while (0)
-    if (do_t) tacc = reinterpret_cast<const float4*>(obs_b)[lane];
-    CAT2_T_STAGE(0);
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    const bool row_ok = li < Cn;
-    const float* er32 = sE + (row_ok ? li : 0) * LE + half * 4;
-    const float* er16 = sE + (row_ok ? li : 0) * LE + half * 8;
-#pragma unroll
-    for (int ph = 0; ph < 2; ++ph) {
-        if (ph) {                                   // every lane has finished reading the first half
-            CAT2_T_STAGE(1);
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        }
-#pragma unroll
-        for (int u = 0; u < MAXC; ++u)
-            if (u < Cn) {
-                sE[u * LE + lane] = ph ? v1[u] : v0[u];
-                if (write_flat) frow[E + u * E + ph * 64 + lane] = ph ? v1[u] : v0[u];       // Flatten()(category_emb)
-            }
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        if (h16) {
-#pragma unroll
-            for (int kb = 0; kb < HK / 16; ++kb) {
-                float4 f0 = make_float4(0.f, 0.f, 0.f, 0.f), f1 = f0;
-                if (row_ok) { f0 = *reinterpret_cast<const float4*>(er16 + kb * 16); f1 = *reinterpret_cast<const float4*>(er16 + kb * 16 + 4); }
-                const float x[8] = {f0.x, f0.y, f0.z, f0.w, f1.x, f1.y, f1.z, f1.w};
-                half8_t fh, fl;
-#pragma unroll
-                for (int e = 0; e < 8; e += 2) {
-                    half2_t h2, l2;
-                    split_h16_pair(x[e], x[e + 1], h2, l2);
-                    fh[e] = h2[0]; fh[e + 1] = h2[1];
-                    fl[e] = l2[0]; fl[e + 1] = l2[1];
-                }
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(fh, fh, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(fl, fh, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(fh, fl, acc, 0, 0, 0);
-            }
-        } else {
-#pragma unroll
-            for (int kb = 0; kb < HK / 8; ++kb) {
-                float4 f = row_ok ? *reinterpret_cast<const float4*>(er32 + kb * 8) : make_float4(0.f, 0.f, 0.f, 0.f);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(f.x, f.x, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(f.y, f.y, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(f.z, f.z, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(f.w, f.w, acc, 0, 0, 0);
-            }
-        }
-    }
-    // (the second half of the block stays in the LDS image: the pooled row reads its columns 64..127 from there, columns
-    // 0..63 from the registers - the v1 registers are free from here on)
-    // the rest of the head-table rows (8 .. Cn-1) are requested HERE - the second-half registers and the MFMA operands are dead -
-    // instead of one chunk of 4 per later stage, each of which exposed a memory round trip in front of the next.  Default shape
-    // (EXACT): all 13 in one go, summed at the end; other shapes: two batches of 8 (the second behind the softmax).
-    constexpr int TW = MAXC - 2 * TCH, TWB = EXACT ? TW : 8;
-    float4 tw[TWB];
-    auto rest_request = [&](int b0) {
-#pragma unroll
-        for (int u = 0; u < TWB; ++u) {
-            const int j = min(2 * TCH + b0 + u, Cn - 1);
-            tw[u] = reinterpret_cast<const float4*>(ptab + ((size_t)j * H + __builtin_amdgcn_readlane(myid, j)) * OBS_DIM)[lane];
-        }
-    };
-    auto rest_add = [&](int b0) {
-#pragma unroll
-        for (int u = 0; u < TWB; ++u)
-            if (2 * TCH + b0 + u < Cn) { tacc.x += tw[u].x; tacc.y += tw[u].y; tacc.z += tw[u].z; tacc.w += tw[u].w; }
-    };
-    if (do_t) {
-        t_add(1);
-        rest_request(0);
-    }
-    float m = -3.4e38f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r)
-        if (crow(r, half) < Cn) m = fmaxf(m, acc[r]);
-    m = fmaxf(m, __shfl_xor(m, 32));
-    float z = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        float ev = (crow(r, half) < Cn) ? CAT_EXP(acc[r] - m) : 0.f;
-        acc[r] = ev;
-        z += ev;
-    }
-    z += __shfl_xor(z, 32);
-    const float inv = row_ok ? 1.f / z : 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        float v = acc[r] * inv;
-        v += __shfl_xor(v, 1);
-        v += __shfl_xor(v, 2);
-        v += __shfl_xor(v, 4);
-        v += __shfl_xor(v, 8);
-        v += __shfl_xor(v, 16);
-        if (li == 0) sW[crow(r, half)] = v;
-    }
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    if (do_t && TWB < TW) {
-        rest_add(0);
-        if (2 * TCH + TWB < Cn) rest_request(TWB);
-    }
-    {
-        const float invc = 1.f / (float)Cn;
-        float s0 = 0.f, s1 = 0.f;
-#pragma unroll
-        for (int j = 0; j < MAXC; ++j)
-            if (j < Cn) {
-                const float w = sW[j];
-                s0 = fmaf(w, v0[j], s0);
-                s1 = fmaf(w, sE[j * LE + lane], s1);
-            }
-        frow[lane] = s0 * invc;
-        frow[lane + 64] = s1 * invc;
-    }
-    const float invq = 1.f / (float)nq;
-    q[(size_t)row * E + lane] = q0 * invq;
-    q[(size_t)row * E + lane + 64] = q1 * invq;
-    if (do_t) {
-        rest_add(TWB < TW ? TWB : 0);
-        reinterpret_cast<float4*>(tsum + (size_t)row * OBS_DIM)[lane] = tacc;
-    }
-#undef CAT2_T_STAGE
-}
+// (k_cat_attn2's row function cat_attn2_row: cat_attn2_row.hpp)
 
 template <int MAXC, bool EXACT>
 __global__ __launch_bounds__(256, 4) void k_cat_attn2(const int32_t* __restrict__ cat, int R, int Cn, int H,
@@ -1243,6 +1043,8 @@ __global__ __launch_bounds__(512) void k_augru_h16(RecurArgs a) {
 // k_augru_x (augru_x.hpp) lives in its own translation unit, augru_x.hip (built WITH SLP vectorisation, see there)
 int augru_x_prepare();
 void augru_x_launch(int rows_per_wg, int n_seq, hipStream_t st, const RecurArgs& a);
+int augru_xs_prepare();
+void augru_xs_launch(int n_seq, hipStream_t st, const RecurArgs& a, const AugruShadowArgs& sh);
 
 // -------------------------------------------------------------------------------------------------
 // First-layer GRU with the same fp16x2 operand splitting (scorer_mode fp16x2): NH = E = 128, 4 waves, 32 rows per
@@ -1466,6 +1268,10 @@ struct DinArgs {
     // the steps of a row's front padding read the pad slot's states and projections - the same bytes, shared by all rows.  NULL = off
     const int32_t* lead[4]; int pad_slot;
 };
+// k_din_xq (din_x.hpp), an argument of its own so that DinArgs and the kernels that take it keep their text: the rows'
+// category ids [R, Cn], the sequence-embedding table and the packed q-side weights of every input (w1ac_all) to form q and qa
+// from; q_out [R, E] and qa_out [R, qa_ld] receive them
+struct DinQArgs { const int32_t* cat; int Cn, H; const float* seq_emb; const char* w1ac_all; float* q_out; float* qa_out; };
 
 template <bool STAGE, bool H16>
 __global__ __launch_bounds__(256) void k_din_scores(DinArgs a) {
@@ -1823,6 +1629,10 @@ struct rl4rs_dien {
     const int32_t* row_order; int row_order_n;    // processing order of the row groups of a forward (caller-owned), or NULL
     // row dedup (row_dedup.hpp): k_din_x and k_augru_x score one representative per set of bit-identical row groups
     bool dup_store;        // row dedup: k_din_x / k_augru_x store a representative's rows to its duplicates (RL4RS_DIEN_OPT_DUP_STORE; default: k_row_expand copies them)
+    bool augru_shadow;     // observation-sized forwards: k_din_xq + k_augru_xs (category branch and dense tower as a shadow plane of the AUGRU launch;
+                           // DESIGN 26; RL4RS_DIEN_OPT_NO_AUGRU_SHADOW: off).  Decided per forward (rl4rs_dien_forward: shadow)
+    bool last_shadow;      // the last forward took the shadow-plane order (rl4rs_dien_kernel_label reports it)
+    int distinct_hint;     // rl4rs_dien_set_distinct_hint: row groups the dedup is expected to leave (0 = the forward's)
     bool din_rows_auto;    // k_din_x at group == 1: 8 or 16 rows per workgroup from the active row count, on the device (RL4RS_DIEN_OPT_DIN_ROWS16: always 16)
     int32_t *dd_dstart, *dd_dlist, *dd_dcur;      // duplicate lists of the last forward (RowDedupArgs)
     bool row_dedup;        // on wherever k_din_x and k_augru_x are the selected kernels (RL4RS_DIEN_OPT_NO_ROW_DEDUP: off)
@@ -2226,6 +2036,9 @@ int rl4rs_dien_create(const rl4rs_dien_cfg* c, const rl4rs_dien_weights* w, void
     n->dup_store = n->row_dedup && (opts & RL4RS_DIEN_OPT_DUP_STORE) != 0;
     n->tier2_rows = n->row_dedup && !(opts & RL4RS_DIEN_OPT_NO_TIER2_ROWS);
     n->din_rows_auto = !(opts & RL4RS_DIEN_OPT_DIN_ROWS16);
+    n->augru_shadow = !(opts & RL4RS_DIEN_OPT_NO_AUGRU_SHADOW);
+    n->distinct_hint = 0;
+    n->last_shadow = false;
     if (n->row_dedup) {
         float* f = nullptr;
         if ((rc = alloc_f(n, &f, (size_t)2 * c->max_rows + 2)) != RL4RS_OK) return rc;
@@ -2299,8 +2112,10 @@ int rl4rs_dien_create(const rl4rs_dien_cfg* c, const rl4rs_dien_weights* w, void
             if ((rc = raise_dyn_smem(f, sm_aug))) return rc;
         if ((rc = raise_dyn_smem(reinterpret_cast<const void*>(&k_augru_h16<1, RL4RS_H16_RING1, RL4RS_H16_NRES>), augru_h16_smem(1, NH2, L)))) return rc;
         if ((rc = augru_x_prepare())) return rc;
+        if ((rc = augru_xs_prepare())) return rc;
         if ((rc = raise_dyn_smem(reinterpret_cast<const void*>(&k_recur<128, false, GRU_U>), sm_gru))) return rc;
         if ((rc = raise_dyn_smem(reinterpret_cast<const void*>(&k_din_x), din_x_smem()))) return rc;
+        if ((rc = raise_dyn_smem(reinterpret_cast<const void*>(&k_din_xq), din_x_smem()))) return rc;
         if ((rc = raise_dyn_smem(reinterpret_cast<const void*>(&k_din_scores<true, false>), 96 * 1024))) return rc;
         if ((rc = raise_dyn_smem(reinterpret_cast<const void*>(&k_din_scores<true, true>), 96 * 1024))) return rc;
     }
@@ -2383,6 +2198,11 @@ static bool augru_rows64(const rl4rs_dien* n, int R, int group) {
     return n->augru_rows == 64 || tiles * n->S >= 2 * (int64_t)n->n_cu;
 }
 
+// the shadow plane's dense tile addresses `dense` and allf through one buffer descriptor each (as k_gemm_h16_map does)
+static bool g16_shadow_fits(int R, int Dn, int F, int U) {
+    return ((int64_t)R - 1) * Dn + Dn < ((int64_t)1 << 29) && ((int64_t)R - 1) * F + U < ((int64_t)1 << 29);
+}
+
 int rl4rs_dien_forward(rl4rs_dien* n, int32_t R, int32_t group, const float* dense, const int32_t* cat,
                        const int32_t* slots, float* obs, float* prob, void* stream) {
     RL4RS_REQUIRE(n && dense && cat && slots, "dien_forward: null argument");
@@ -2402,6 +2222,16 @@ int rl4rs_dien_forward(rl4rs_dien* n, int32_t R, int32_t group, const float* den
     // everywhere else the forward issues the launches it issued before (as with RL4RS_DIEN_OPT_NO_TIER2_ROWS)
     const bool tier2 = n->row_dedup && n->tier2_rows && !n->dup_store && !n->dense_fork && !(obs && n->obs_mirror) &&
                        n->gemm16 && n->ptab && n->tsum && n->cat_v2 && E == 128 && Cn <= 24 && n->dense_chain && U <= 128 && U % 16 == 0;
+    // Shadow-plane order of an observation-sized forward: k_din_xq forms q and qa for its own rows, the category branch and
+    // the dense tower run on the CUs the 32-row AUGRU launch leaves idle (k_augru_xs) - k_row_dedup, k_din_xq, k_augru_xs, head GEMM,
+    // k_row_expand.  Only on top of the second tier above, in the default forms of every launch involved, and only where the
+    // expected tiles * (S + 1) workgroups (one per CU: the launch's dynamic LDS) fit the chip; everywhere else - the reward forward,
+    // a handle without a useful hint, every non-default option - the forward issues what it issued before
+    const int hint_groups = n->distinct_hint > 0 && n->distinct_hint < ngroups ? n->distinct_hint : ngroups;
+    const bool shadow = tier2 && n->augru_shadow && group == 1 && Cn == 21 && S <= 2 && n->fp16x2 && n->augru_x && n->din16 && n->h1f[0] &&
+                        n->din_x && n->din_rows_auto && n->gemm_group && !augru_rows64(n, R, group) && n->augru_rows != 64 &&
+                        dien_gemm_grouped(n) && (int64_t)((hint_groups + 31) / 32) * (S + 1) <= n->n_cu &&
+                        g16_shadow_fits(R, n->Dn, F, U);
     const G16RowMap rmap = {n->dd_active, n->dd_nact, group};
     const G16RowMap* const map2 = tier2 ? &rmap : nullptr;
     const int32_t* const t2_order = tier2 ? n->dd_active : nullptr;
@@ -2446,7 +2276,13 @@ int rl4rs_dien_forward(rl4rs_dien* n, int32_t R, int32_t group, const float* den
         hipLaunchKernelGGL(k_row_dedup, dim3((ngroups + per_wg - 1) / per_wg), dim3(ROW_DEDUP_THREADS), 0, st, a);
         RL4RS_LAUNCH_CHECK();
     }
-    {
+    n->last_shadow = shadow;
+    if (shadow) {
+        // the category branch and the dense tower are part of the AUGRU launch below, the q-side term of k_din_xq: their profile
+        // classes keep one (empty) entry per forward, so that a class still counts the forwards it took part in
+        { Prof p(n, KID_CAT, st); }
+        { Prof p(n, KID_DENSE, st); }
+    } else {
         Prof p(n, KID_CAT, st);
         if (n->cat_v2 && n->cat_group && E == 128 && Cn >= 11 && Cn <= 24 && (group == 8 || group == 9)) {
             // rows in groups that (normally) share all but the last category id: one workgroup per group, shared gathers once
@@ -2478,7 +2314,8 @@ int rl4rs_dien_forward(rl4rs_dien* n, int32_t R, int32_t group, const float* den
     // The dense tower and the q-side term of the DIN scores (qa = q W1ac_all, q written by the category kernel above) are
     // independent and, at observation size, half-chip grids of the same kernel: one launch for both (launch_gemm_h16_pair)
     const bool grouped = dien_gemm_grouped(n) && !forked;
-    if (grouped) {
+    if (shadow) {
+    } else if (grouped) {
         Prof p(n, KID_DENSE, st);
         GemmH16Desc dt, qs;
         memset(&dt, 0, sizeof(dt));
@@ -2499,7 +2336,7 @@ int rl4rs_dien_forward(rl4rs_dien* n, int32_t R, int32_t group, const float* den
         a.slots = slots; a.slots_stride = ngroups; a.pld = n->PLD; a.q = n->q;
         a.qa = n->qa; a.qa_stride = ATT_H1; a.qa_ld = S * ATT_H1;       // one GEMM for the q-side term of every input: [R, S*64]
         const bool h16 = n->fp16x2 && n->din16;
-        if (!grouped) {
+        if (!grouped && !shadow) {
             rc = tier2 ? launch_gemm_h16(n->q, E, n->w1ac_all, nullptr, n->qa, S * ATT_H1, R, S * ATT_H1, E, 0, st, nullptr, 0, nullptr, 0, map2)
                        : scorer_gemm(n, n->q, E, n->w1ac_all, nullptr, n->qa, S * ATT_H1, R, S * ATT_H1, E, 0, st);
             if (rc) return rc;
@@ -2528,7 +2365,10 @@ int rl4rs_dien_forward(rl4rs_dien* n, int32_t R, int32_t group, const float* den
             }
         }
 #endif
-        if (h16 && n->h1f[0]) {
+        if (shadow) {
+            const DinQArgs qx = {cat, Cn, n->H, n->seq_emb, reinterpret_cast<const char*>(n->w1ac_all), n->q, n->qa};
+            hipLaunchKernelGGL(k_din_xq, dim3((R + 7) / 8, S), dim3(512), din_x_smem(), st, a, 16, n->n_cu, qx);
+        } else if (h16 && n->h1f[0]) {
             // 16 rows per 8-wave workgroup: an obs-sized launch (R = 4096, two inputs) is two workgroups per CU, one round.
             // group == 1: the grid is sized for 8 and the kernel picks 8 or 16 from the rows the dedup left (din_x.hpp)
             if (group == 1 && n->din_rows_auto)
@@ -2588,7 +2428,18 @@ int rl4rs_dien_forward(rl4rs_dien* n, int32_t R, int32_t group, const float* den
             }
 #endif
             const bool mt2 = augru_rows64(n, R, group);
-            if (n->augru_x)
+            if (shadow) {
+                AugruShadowArgs sh;
+                memset(&sh, 0, sizeof(sh));
+                sh.cat = cat; sh.Cn = Cn; sh.H = n->H; sh.cat_emb = n->cat_emb; sh.seq_emb = n->seq_emb; sh.allf = n->allf; sh.ldf = F; sh.off_c = off_c;
+                sh.q = n->q; sh.write_flat = n->ptab ? 0 : 1; sh.h16 = (n->fp16x2 && n->cat16) ? 1 : 0; sh.ptab = n->ptab; sh.obs_b = n->obs_b; sh.tsum = n->tsum;
+                sh.dense = dense; sh.lda = n->Dn; sh.w1 = reinterpret_cast<const char*>(n->dense_w1); sh.kb1 = (n->Dn + 15) / 16; sh.b1 = n->dense_b1;
+                sh.N1 = U; sh.K1 = n->Dn; sh.act1 = 1;
+                sh.vec = ((n->Dn & 3) == 0 && (reinterpret_cast<uintptr_t>(dense) & 15) == 0) ? 1 : 0;
+                sh.chain = G16Chain{reinterpret_cast<const char*>(n->dense_w2), (U + 15) / 16, n->dense_b2, n->allf + off_d, F, U, 1, nullptr, 0};
+                sh.R = R; sh.rmap = rmap;
+                augru_xs_launch(S, st, a, sh);
+            } else if (n->augru_x)
                 augru_x_launch(mt2 ? 64 : 32, S, st, a);
             else
                 hipLaunchKernelGGL((k_augru_h16<1, RL4RS_H16_RING1, RL4RS_H16_NRES>), grid, block, augru_h16_smem(1, NH2, L), st, a);
@@ -2710,6 +2561,12 @@ int rl4rs_dien_set_augru_rows(rl4rs_dien* n, int32_t rows) {
 
 // The NEXT forward (one that returns probabilities) also stores the 'simulator_obs' activations of the last row of each group:
 // obs_last_dev [R / group, 256].  The values are the head GEMM's own rows, copied by k_head_prob.
+int rl4rs_dien_set_distinct_hint(rl4rs_dien* n, int32_t n_groups) {
+    RL4RS_REQUIRE(n && n_groups >= 0, "dien_set_distinct_hint: bad argument");
+    n->distinct_hint = n_groups;
+    return RL4RS_OK;
+}
+
 int rl4rs_dien_set_obs_last(rl4rs_dien* n, float* obs_last_dev) {
     RL4RS_REQUIRE(n, "dien_set_obs_last: null handle");
     n->obs_last = obs_last_dev;
@@ -2780,6 +2637,7 @@ int rl4rs_dien_kernel_label(rl4rs_dien* n, int which, char* buf, int32_t cap) {
             break;
         case KID_AUGRU:
             s = !n->fp16x2 ? "k_recur<256,augru>" : (n->augru_x ? "k_augru_x" : "k_augru_h16");
+            if (n->last_shadow) s = "k_augru_xs (last forward: category branch and dense tower in the shadow plane)";
             break;
         case KID_HEAD:
             s = std::string(gemm) + "(simulator_obs)" + ((n->ptab && !n->tsum) ? " + k_head_finish" : "");

@@ -15,20 +15,11 @@
 #include <vector>
 
 #include "common.hpp"
+#include "gemm_h16_defs.hpp"
 
 namespace rl4rs {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ float apply_act(float x, int act) {
-    switch (act) {
-        case ACT_ELU: return x > 0.f ? x : expm1f(x);
-        case ACT_SIGMOID: return 1.f / (1.f + expf(-x));
-        case ACT_TANH: return tanhf(x);
-        case ACT_RELU: return fmaxf(x, 0.f);
-        default: return x;
-    }
-}
 
 constexpr int GBM = 128, GBN = 64, GBK = 32, GLD = GBK + 4;
 
@@ -407,13 +398,6 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f32_t128(const float* __restric
 // K zero-padded to a multiple of 8, N to a multiple of 32.  One 16-byte load feeds four MFMAs; the next
 // k-block's fragment is requested before the current block's MFMAs (register ring).
 // WM = 32-row tiles per wave: block tile = (64*WM) x 64, 2x2 waves.
-struct f4bits_g { float x, y, z, w; };
-__device__ __forceinline__ float4 gbuf_load4(__amdgpu_buffer_rsrc_t rsrc, int voff, int soff) {
-    auto v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, soff, 0);   // result must be bit_cast (see dien.hip)
-    f4bits_g f = __builtin_bit_cast(f4bits_g, v);
-    return make_float4(f.x, f.y, f.z, f.w);
-}
-
 template <int WM>
 __global__ __launch_bounds__(256) void k_gemm_pk(const float* __restrict__ A, int64_t lda,
                                                  const float4* __restrict__ Wp, int KB,
@@ -553,24 +537,8 @@ __global__ __launch_bounds__(256) void k_gemm_pk(const float* __restrict__ A, in
 // A value outside the fp16 range becomes inf in the hi plane and -inf in the lo plane, i.e. NaN in its whole output row:
 // out-of-range inputs can never come back as plausible numbers.
 // Block = 4 waves, wave w owns n-tile blockIdx.y*4 + w for all BM = 32*WM rows; k-tile = 64.
-typedef _Float16 ghalf8_t __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ ghalf8_t gbuf_load_h8(__amdgpu_buffer_rsrc_t rsrc, int voff, int soff) {
-    auto v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, soff, 0);
-    return __builtin_bit_cast(ghalf8_t, v);
-}
-
-// Optional second layer chained onto the first (the dense tower: Dense+ELU twice, utils.py:48-54): when the first layer's N
-// fits one workgroup (N <= 128, a multiple of 16) its activated output tile never leaves the CU - it is split into the LDS
-// planes the main loop has finished with and multiplied by the second weight matrix (K2 = N, N2 <= 128).  Same values, same
-// k-blocks and the same MFMA sequence as two launches with the intermediate in HBM: bit-identical results, one launch less.
-struct G16Chain {
-    const char* wp2; int kb2; const float* bias2; float* c2; int64_t ldc2; int n2; int act2;
-    // (unchained launches) second destination of the SAME output elements, row stride ldm: device-visible pinned HOST memory - the
-    // observation of a reference-shaped step leaves for the host from the head GEMM's epilogue, as its tiles finish, instead of
-    // through a device-to-host copy that can only start when the whole GEMM has ended
-    float* mirror; int64_t ldm;
-};
-
+// (ghalf8_t, gbuf_load_h8, gbuf_load4, apply_act and G16Chain - the optional second layer chained onto the first - live in
+// gemm_h16_defs.hpp: the shadow plane of k_augru_xs runs the same tile text)
 // VEC: rows of A are 16-byte aligned (decided by the host: lda % 4 == 0 and A aligned) -> two 16-byte loads per chunk
 template <int WM, bool VEC>
 __global__ __launch_bounds__(256) void k_gemm_h16(const float* __restrict__ A, int64_t lda,

@@ -1,6 +1,7 @@
 // The tile body of k_gemm_h16 and k_gemm_h16_pair (gemm.hip), included into both kernels as TEXT so that k_gemm_h16 compiles to
 // exactly the code it had as a single kernel.  Expects in scope: WM, VEC; A, lda, Wp, KB, bias, C, ldc, M, N, K, act, addend,
-// ldadd, chain (all wave-uniform) and RL4RS_G16_BX = the workgroup's row-tile index within its problem; MAP (constexpr bool), rmap
+// ldadd, chain (all wave-uniform) and RL4RS_G16_BX = the workgroup's row-tile index within its problem (RL4RS_G16_BY, optional: its column-group
+// index instead of blockIdx.y; RL4RS_G16_AS_LDS, optional: where the tile buffers lie instead of in static LDS); MAP (constexpr bool), rmap
 // (G16RowMap) and s_row (int[BM] in LDS when MAP).  MAP = false (k_gemm_h16, k_gemm_h16_pair): every `if constexpr (MAP)` below is
 // no code and the kernels compile to the instruction text they had without it.  MAP = true (k_gemm_h16_map, k_gemm_h16_pair_map;
 // DESIGN 25): tile position p works on physical row active[p / group] * group + p % group of A, C, c2 and the addend, the row
@@ -9,7 +10,11 @@
 // k-blocks, the MFMA order and the epilogue expression are those of the unmapped form.
     constexpr int BM = 32 * WM, BK = 64, KBT = BK / 16;
     constexpr int SLAB = BM * 16 + 16, PLANE = 2 * KBT * SLAB;
+#ifdef RL4RS_G16_AS_LDS        // the shadow plane of k_augru_xs: the tile buffers are a piece of the launch's dynamic LDS
+    char (*const As)[2][PLANE] = reinterpret_cast<char (*)[2][PLANE]>(RL4RS_G16_AS_LDS);
+#else
     __shared__ __attribute__((aligned(16))) char As[2][2][PLANE];          // [buffer][hi / lo]
+#endif
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int half = lane >> 5, li = lane & 31;
@@ -39,7 +44,10 @@
             if ((tid & 7) == 0) s_row[(tid + p * 256) >> 3] = arow[p];       // for the epilogue, behind the main loop's barriers
         }
     }
-    const int nt = blockIdx.y * 4 + wave;
+#ifndef RL4RS_G16_BY
+#define RL4RS_G16_BY blockIdx.y
+#endif
+    const int nt = RL4RS_G16_BY * 4 + wave;
     const int NT = (N + 31) / 32;
     const bool tile_ok = nt < NT;
     const int col = nt * 32 + li;

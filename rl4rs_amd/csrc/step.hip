@@ -293,6 +293,7 @@ int rl4rs_stepper_click_probs(rl4rs_stepper* s, float* out_dev, void* stream) {
 int rl4rs_stepper_set_distinct_hint(rl4rs_stepper* s, int32_t n_distinct) {
     RL4RS_REQUIRE(s && n_distinct >= 1, "stepper_set_distinct_hint: bad argument");
     s->distinct_hint = n_distinct < s->cfg.batch_size ? n_distinct : s->cfg.batch_size;
+    if (s->dien) return rl4rs_dien_set_distinct_hint(s->dien, s->distinct_hint);     // sizes the scorer's shadow-plane order
     return RL4RS_OK;
 }
 

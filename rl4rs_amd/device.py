@@ -672,6 +672,10 @@ class DeviceDien(object):
         """Row-tile form of k_augru_x for the following forwards: 0 automatic, 32 or 64 (rl4rs_dien_set_augru_rows)."""
         check(self.lib.rl4rs_dien_set_augru_rows(self.h, int(rows)))
 
+    def set_distinct_hint(self, n):
+        """Distinct row groups the row dedup is expected to leave (rl4rs_dien_set_distinct_hint; None / 0 = the forward's rows)."""
+        check(self.lib.rl4rs_dien_set_distinct_hint(self.h, int(n or 0)))
+
     def set_profiling(self, on):
         """0 / False off, 1 / True every kernel class, 2 only the AUGRU recurrence (rl4rs_dien_set_profiling)."""
         check(self.lib.rl4rs_dien_set_profiling(self.h, 2 if on == 2 else (1 if on else 0)))
