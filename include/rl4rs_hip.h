@@ -429,7 +429,8 @@ int rl4rs_dien_profile_reset(rl4rs_dien* net);
  * Weight arrays (host float32, shapes in rl4rs_amd/nets/simnets.py); unused ones may be NULL.
  * ---------------------------------------------------------------------------------------------- */
 typedef struct rl4rs_simnet rl4rs_simnet;
-enum { RL4RS_SIMNET_DNN = 1, RL4RS_SIMNET_WIDEDEEP = 2, RL4RS_SIMNET_LSTM = 3 };
+enum { RL4RS_SIMNET_DNN = 1, RL4RS_SIMNET_WIDEDEEP = 2, RL4RS_SIMNET_LSTM = 3,
+       RL4RS_SIMNET_ADVERSARIAL = 4 /* trainer only (rl4rs_simtrain_create_head with RL4RS_HEAD_ADVERSARIAL); no scorer */ };
 
 typedef struct rl4rs_simnet_cfg {
     int32_t algo;                  /* RL4RS_SIMNET_* */
@@ -954,6 +955,31 @@ int rl4rs_simtrain_step(rl4rs_simtrain* tr, int32_t N, const float* dense_dev, c
                         const int32_t* const* seq_dev, const int32_t* labels_dev, float lr, float beta1, float beta2,
                         float eps, float dropout_rate, uint32_t seed, uint32_t step, float* loss_dev, void* stream);
 
+/* The slate-wise models of script/supervised_train.py (rl4rs/nets/{dnn,widedeep,lstm,dien}_slate.py, *_slate_multiclass.py,
+ * adversarial_slate.py): the item-wise trunk with another output layer and loss, one sample per page.
+ *   ITEM              the handle of rl4rs_simtrain_create / rl4rs_dientrain_create (labels_dev [N] in [0, class_num))
+ *   SLATE             Dense(9, sigmoid) + binary_crossentropy: row loss = mean_j [max(x,0) - x y + log1p(exp(-|x|))] of the logits x
+ *   SLATE_MULTICLASS  Dense(22, softmax) + categorical crossentropy of class c = sum_j y_j [1,2,4,1,2,4,1,2,4][j]:
+ *                     row loss = logsumexp(x) - x[c]
+ *   ADVERSARIAL       rl4rs_simtrain only, cfg->algo = RL4RS_SIMNET_ADVERSARIAL: features [mean of each sequence's embeddings
+ *                     (seq_num * E) | dense tower (U) | mean of the category embeddings of the first category_feature_num - 1 ids (E)]
+ *                     -> Dense(9); s = sigmoid(x), row loss = 0.1 * (the SLATE loss) + sum_j softmax(s)_j (1 - y_j).
+ *                     Arrays: cat_emb, seq_emb, dense_w1, dense_b1, dense_w2, dense_b2, out_w, out_b.
+ * For every head but ITEM the output layer is [obs_dim, 9] / [obs_dim, 22] whatever cfg->class_num says (only out_w / out_b change
+ * width in the flat layout) and labels_dev of grad / step / eval is int32 [N, 9] of 0 / 1.  All losses are taken from the logits
+ * (keras does so for a Sigmoid / Softmax output op), so nothing is clipped. */
+enum { RL4RS_HEAD_ITEM = 0, RL4RS_HEAD_SLATE = 1, RL4RS_HEAD_SLATE_MULTICLASS = 2, RL4RS_HEAD_ADVERSARIAL = 3 };
+int rl4rs_simtrain_create_head(const rl4rs_simnet_cfg* cfg, const rl4rs_simnet_weights* w, int32_t head, int32_t max_batch,
+                               void* stream, rl4rs_simtrain** out);
+/* device pointers of the Adam moments (owned by the handle) and the number of steps taken */
+int rl4rs_simtrain_adam_state(rl4rs_simtrain* tr, float** m_dev, float** v_dev, int64_t* step);
+/* Inference pass on a trainer handle (validation): forward without dropout, no backward; parameters, gradient buffer and Adam state
+ * are left untouched.  pred_dev [N, K] f32 = the model output (softmax for ITEM with K = class_num and SLATE_MULTICLASS with K = 22,
+ * sigmoid with K = 9 otherwise); loss_rows_dev [N] (may be NULL) = the head's row losses, which need labels_dev (else may be NULL). */
+int rl4rs_simtrain_eval(rl4rs_simtrain* tr, int32_t N, const float* dense_dev, const int32_t* cat_dev,
+                        const int32_t* const* seq_dev, const int32_t* labels_dev, float* pred_dev, float* loss_rows_dev,
+                        void* stream);
+
 /* Supervised training of the DIEN simulator (rl4rs/nets/dien.py; script/supervised_train.py with model_type='dien') on the
  * device: training-mode forward (Dropout after each dense-tower layer), keras binary_crossentropy, backward through the
  * head, the category self-attention, the dense tower and, per sequence input, the DIN attention MLP, the AUGRU and the
@@ -977,6 +1003,14 @@ int rl4rs_recur_train_set_rows(int32_t rows);
 typedef struct rl4rs_dientrain rl4rs_dientrain;
 int rl4rs_dientrain_create(const rl4rs_dien_cfg* cfg, const rl4rs_dien_weights* w, int32_t max_batch, void* stream,
                            rl4rs_dientrain** out);
+/* head: RL4RS_HEAD_ITEM (= rl4rs_dientrain_create), RL4RS_HEAD_SLATE or RL4RS_HEAD_SLATE_MULTICLASS (dien_slate.py,
+ * dien_slate_multiclass.py); _adam_state and _eval as for rl4rs_simtrain_* */
+int rl4rs_dientrain_create_head(const rl4rs_dien_cfg* cfg, const rl4rs_dien_weights* w, int32_t head, int32_t max_batch,
+                                void* stream, rl4rs_dientrain** out);
+int rl4rs_dientrain_adam_state(rl4rs_dientrain* tr, float** m_dev, float** v_dev, int64_t* step);
+int rl4rs_dientrain_eval(rl4rs_dientrain* tr, int32_t N, const float* dense_dev, const int32_t* cat_dev,
+                         const int32_t* const* seq_dev, const int32_t* labels_dev, float* pred_dev, float* loss_rows_dev,
+                         void* stream);
 int rl4rs_dientrain_destroy(rl4rs_dientrain* tr);
 /* The launch chains that follow a recurrent layer (parameter-gradient reductions, the attention MLP's forward / backward) of the
  * ODD sequence inputs run on a second stream of the handle, beside the even inputs' (each ~35 small launches; own scratch; joined in
@@ -991,6 +1025,25 @@ int rl4rs_dientrain_grad(rl4rs_dientrain* tr, int32_t N, const float* dense_dev,
 int rl4rs_dientrain_step(rl4rs_dientrain* tr, int32_t N, const float* dense_dev, const int32_t* cat_dev,
                          const int32_t* const* seq_dev, const int32_t* labels_dev, float lr, float beta1, float beta2,
                          float eps, float dropout_rate, uint32_t seed, uint32_t step, float* loss_dev, void* stream);
+
+/* Streaming classifier metrics (script/supervised_train.py:38-42 and the slate models' compile calls: keras AUC, Precision, Recall,
+ * 'acc', categorical accuracy): int64 confusion counts on the device, integer atomics only - exact, and the same from run to run.
+ * No update waits for the host.  thresholds: host float32 [num_thresholds], non-decreasing - for keras AUC(num_thresholds = T) the table
+ * [-1e-7] + [(i + 1) / (T - 1) for i in range(T - 2)] + [1 + 1e-7].  A prediction counts as positive at a threshold iff pred > thr in
+ * float32 (a NaN never does).
+ *   update_binary      n elements: pred_dev f32 [n], label_dev i32 [n] (non-zero = positive); TP / FP / TN / FN at every threshold
+ *                      and at 0.5 (Precision, Recall, binary accuracy)
+ *   update_multiclass  pred_dev f32 [N, K], label_dev i32 [N]: rows whose first maximum is the label, and rows
+ *   read               waits for the stream; counts_host int64 [4 T + 6] = TP [T] | FP [T] | TN [T] | FN [T] | tp, fp, tn, fn at 0.5 |
+ *                      multiclass correct, rows.  The metrics themselves are the host's (rl4rs_amd/metrics.py). */
+typedef struct rl4rs_clfmetrics rl4rs_clfmetrics;
+int rl4rs_clfmetrics_create(int32_t num_thresholds, const float* thresholds, void* stream, rl4rs_clfmetrics** out);
+int rl4rs_clfmetrics_destroy(rl4rs_clfmetrics* m);
+int rl4rs_clfmetrics_reset(rl4rs_clfmetrics* m, void* stream);
+int rl4rs_clfmetrics_update_binary(rl4rs_clfmetrics* m, int64_t n, const float* pred_dev, const int32_t* label_dev, void* stream);
+int rl4rs_clfmetrics_update_multiclass(rl4rs_clfmetrics* m, int64_t N, int32_t K, const float* pred_dev, const int32_t* label_dev,
+                                       void* stream);
+int rl4rs_clfmetrics_read(rl4rs_clfmetrics* m, int64_t* counts_host, void* stream);
 
 /* Offline-RL learner networks and losses: what script/batchrl_trainer.py:34-90 trains with d3rlpy (DiscreteBC, DiscreteBCQ,
  * DiscreteCQL) on the logged-policy dataset, BASELINE configs[4].  A qnet is one encoder + d3rlpy's Linear head:

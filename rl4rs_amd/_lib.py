@@ -228,6 +228,9 @@ SIGNATURES = {
                                     C.c_float, C.c_float, _P, _P, _P]),
     'rl4rs_policy_adam_step': (_I, [_P, _P, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _P]),
     'rl4rs_simtrain_create': (_I, [C.POINTER(SimnetCfg), C.POINTER(SimnetWeights), _I32, _P, C.POINTER(_P)]),
+    'rl4rs_simtrain_create_head': (_I, [C.POINTER(SimnetCfg), C.POINTER(SimnetWeights), _I32, _I32, _P, C.POINTER(_P)]),
+    'rl4rs_simtrain_adam_state': (_I, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_I64)]),
+    'rl4rs_simtrain_eval': (_I, [_P, _I32, _P, _P, C.POINTER(_P), _P, _P, _P, _P]),
     'rl4rs_simtrain_destroy': (_I, [_P]),
     'rl4rs_simtrain_params': (_I, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_I64)]),
     'rl4rs_simtrain_masks': (_I, [_P, C.POINTER(_P), C.POINTER(_P)]),
@@ -236,7 +239,16 @@ SIGNATURES = {
                                  C.c_uint32, C.c_uint32, _P, _P]),
     'rl4rs_recur_train_set_rows': (_I, [_I32]),
     'rl4rs_dientrain_create': (_I, [C.POINTER(DienCfg), C.POINTER(DienWeights), _I32, _P, C.POINTER(_P)]),
+    'rl4rs_dientrain_create_head': (_I, [C.POINTER(DienCfg), C.POINTER(DienWeights), _I32, _I32, _P, C.POINTER(_P)]),
+    'rl4rs_dientrain_adam_state': (_I, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_I64)]),
+    'rl4rs_dientrain_eval': (_I, [_P, _I32, _P, _P, C.POINTER(_P), _P, _P, _P, _P]),
     'rl4rs_dientrain_destroy': (_I, [_P]),
+    'rl4rs_clfmetrics_create': (_I, [_I32, _FP, _P, C.POINTER(_P)]),
+    'rl4rs_clfmetrics_destroy': (_I, [_P]),
+    'rl4rs_clfmetrics_reset': (_I, [_P, _P]),
+    'rl4rs_clfmetrics_update_binary': (_I, [_P, _I64, _P, _P, _P]),
+    'rl4rs_clfmetrics_update_multiclass': (_I, [_P, _I64, _I32, _P, _P, _P]),
+    'rl4rs_clfmetrics_read': (_I, [_P, C.POINTER(_I64), _P]),
     'rl4rs_dientrain_set_fork': (_I, [_I32]),
     'rl4rs_dientrain_params': (_I, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_I64)]),
     'rl4rs_dientrain_masks': (_I, [_P, C.POINTER(_P), C.POINTER(_P)]),

@@ -151,6 +151,7 @@ struct rl4rs_dientrain {
     rl4rs_dien_cfg c;
     int64_t off[DP_COUNT], size[DP_COUNT];
     int max_batch, F;
+    int head, K;           // RL4RS_HEAD_*; width of the output layer (class_num, 9 or 22)
     TrainCtx cx;
     OptBlock opt;
     // saved forward
@@ -268,6 +269,23 @@ int cell_backward_post(rl4rs_dientrain* t, int N, const CellSave& cl, const floa
     return RL4RS_OK;
 }
 
+// the odd sequence inputs' chains on the handle's second stream (fork / join = one event each way)
+struct DtFork {
+    rl4rs_dientrain* t;
+    hipStream_t st;
+    bool two;
+    DtFork(rl4rs_dientrain* t_, hipStream_t st_) : t(t_), st(st_), two(t_->side != nullptr && g_dientrain_fork && t_->c.seq_num > 1) {}
+    int fork() const {
+        if (two) { RL4RS_HIP_TRY(hipEventRecord(t->ev_fork, st)); RL4RS_HIP_TRY(hipStreamWaitEvent(t->side, t->ev_fork, 0)); }
+        return RL4RS_OK;
+    }
+    int join() const {
+        if (two) { RL4RS_HIP_TRY(hipEventRecord(t->ev_join, t->side)); RL4RS_HIP_TRY(hipStreamWaitEvent(st, t->ev_join, 0)); }
+        return RL4RS_OK;
+    }
+    hipStream_t stream_of(int s) const { return (two && (s & 1)) ? t->side : st; }
+};
+
 }  // namespace
 
 extern "C" {
@@ -285,14 +303,18 @@ int rl4rs_dientrain_destroy(rl4rs_dientrain* t) {
     return RL4RS_OK;
 }
 
-int rl4rs_dientrain_create(const rl4rs_dien_cfg* c, const rl4rs_dien_weights* w, int32_t max_batch, void* stream,
-                           rl4rs_dientrain** out) {
+// head = RL4RS_HEAD_ITEM: rl4rs_dientrain_create itself; RL4RS_HEAD_SLATE / _SLATE_MULTICLASS: output layer [256, 9] / [256, 22]
+// (cfg->class_num is not read), labels int32 [N, 9]
+static int dientrain_create_impl(const rl4rs_dien_cfg* c, const rl4rs_dien_weights* w, int head, int32_t max_batch, void* stream,
+                                 rl4rs_dientrain** out) {
     RL4RS_REQUIRE(c && w && out && max_batch > 0, "dientrain_create: bad argument");
+    RL4RS_REQUIRE(head >= RL4RS_HEAD_ITEM && head <= RL4RS_HEAD_SLATE_MULTICLASS,
+                  "dientrain_create_head: head must be 0 (item), 1 (slate) or 2 (slate multiclass), got %d", head);
     RL4RS_REQUIRE(c->emb_size == 128, "dientrain: emb_size must be 128 (the recurrence kernels are built for hidden widths 128 / 256), got %d",
                   c->emb_size);
     RL4RS_REQUIRE(c->emb_size > 0 && c->emb_size % 2 == 0 && c->hidden_units > 0 && c->maxlen >= 1 && c->seq_num >= 1 && c->seq_num <= 4 &&
                   c->category_feature_num >= 10 && c->category_feature_num <= 32 && c->category_hash_size > 0 &&
-                  c->dense_feature_num > 0 && c->class_num >= 2 && c->class_num <= 8, "dientrain: bad sizes");
+                  c->dense_feature_num > 0 && (head != RL4RS_HEAD_ITEM || (c->class_num >= 2 && c->class_num <= 8)), "dientrain: bad sizes");
     // the limits of the persistent training recurrences (launch_recur_train_fwd / _bwd; there is no step-by-step form for DIEN), refused
     // here rather than at the first grad: a whole sequence per workgroup, and the AUGRU's [max_batch * maxlen, 3 * 256] fp32
     // pre-activations addressed below 2^31 bytes
@@ -314,10 +336,13 @@ int rl4rs_dientrain_create(const rl4rs_dien_cfg* c, const rl4rs_dien_weights* w,
         return RL4RS_EHIP;
     }
     hipStream_t st = (hipStream_t)stream;
-    const int64_t E = c->emb_size, U = c->hidden_units, H = c->category_hash_size, Dn = c->dense_feature_num, K = c->class_num;
+    const int64_t E = c->emb_size, U = c->hidden_units, H = c->category_hash_size, Dn = c->dense_feature_num;
+    const int64_t K = head_width(head, c->class_num);
     const int64_t S = c->seq_num, Cn = c->category_feature_num, L = c->maxlen, NH2 = 2 * E;
     rl4rs_dientrain* t = new rl4rs_dientrain();
     t->c = *c;
+    t->head = head;
+    t->K = (int)K;
     t->max_batch = max_batch;
     t->opt.t = 0;
     t->F = (int)(S * NH2 + U + (Cn + 1) * E);
@@ -420,6 +445,20 @@ int rl4rs_dientrain_create(const rl4rs_dien_cfg* c, const rl4rs_dien_weights* w,
     return RL4RS_OK;
 }
 
+int rl4rs_dientrain_create(const rl4rs_dien_cfg* c, const rl4rs_dien_weights* w, int32_t max_batch, void* stream,
+                           rl4rs_dientrain** out) {
+    return dientrain_create_impl(c, w, RL4RS_HEAD_ITEM, max_batch, stream, out);
+}
+
+int rl4rs_dientrain_create_head(const rl4rs_dien_cfg* c, const rl4rs_dien_weights* w, int32_t head, int32_t max_batch, void* stream,
+                                rl4rs_dientrain** out) {
+    return dientrain_create_impl(c, w, head, max_batch, stream, out);
+}
+
+int rl4rs_dientrain_adam_state(rl4rs_dientrain* t, float** m_dev, float** v_dev, int64_t* step) {
+    return opt_adam_state(RL4RS_OPT(t), m_dev, v_dev, step, "dientrain_adam_state");
+}
+
 int rl4rs_dientrain_params(rl4rs_dientrain* t, float** params_dev, float** grad_dev, int64_t* count) {
     return opt_params(RL4RS_OPT(t), params_dev, grad_dev, count, "dientrain_params");
 }
@@ -431,18 +470,18 @@ int rl4rs_dientrain_masks(rl4rs_dientrain* t, uint8_t** mask1_dev, uint8_t** mas
     return RL4RS_OK;
 }
 
-int rl4rs_dientrain_grad(rl4rs_dientrain* t, int32_t N, const float* dense, const int32_t* cat, const int32_t* const* seq,
-                         const int32_t* labels, float dropout_rate, uint32_t seed, uint32_t step, float* loss_dev, void* stream) {
-    RL4RS_REQUIRE(t && dense && cat && seq && labels && N > 0 && N <= t->max_batch, "dientrain_grad: bad argument (N=%d, max_batch=%d)", N,
+// The forward of grad (training mode) and of eval (dropout_rate = 0: the inference forward) up to the logits [N, K]; keeps every
+// activation the backward needs.  Checks the arguments the two share.
+static int dientrain_forward(rl4rs_dientrain* t, int32_t N, const float* dense, const int32_t* cat, const int32_t* const* seq,
+                             float dropout_rate, uint32_t seed, uint32_t step, hipStream_t st) {
+    RL4RS_REQUIRE(t && dense && cat && seq && N > 0 && N <= t->max_batch, "dientrain: bad argument (N=%d, max_batch=%d)", N,
                   t ? t->max_batch : -1);
     RL4RS_REQUIRE(dropout_rate >= 0.f && dropout_rate < 1.f, "dientrain_grad: dropout_rate must be in [0, 1)");
     for (int s = 0; s < t->c.seq_num; ++s) RL4RS_REQUIRE(seq[s], "dientrain_grad: sequence input %d is NULL", s);
-    hipStream_t st = (hipStream_t)stream;
     const int E = t->c.emb_size, U = t->c.hidden_units, H = t->c.category_hash_size, Dn = t->c.dense_feature_num;
-    const int Cn = t->c.category_feature_num, K = t->c.class_num, S = t->c.seq_num, L = t->c.maxlen, NH2 = 2 * E, F = t->F;
+    const int Cn = t->c.category_feature_num, K = t->K, S = t->c.seq_num, L = t->c.maxlen, NH2 = 2 * E, F = t->F;
     const int Ns = N * L;
     float* P = t->opt.params;
-    float* G = t->opt.grad;
     const int64_t* o = t->off;
     const int off_d = S * NH2, off_c = S * NH2 + U, off_f = S * NH2 + U + E;
     int rc;
@@ -461,20 +500,11 @@ int rl4rs_dientrain_grad(rl4rs_dientrain* t, int32_t N, const float* dense, cons
         Xs[s] = t->X[s]; Ks[s] = t->gru[s].Hs; scs[s] = t->score[s];
     }
     if ((rc = layer_forward(t, N, 0, Xs, nullptr, st))) return rc;         // first GRU of every sequence input: one launch
-    // the chains of the odd sequence inputs on the second stream (fork / join = one event each way)
-    const bool two = t->side != nullptr && g_dientrain_fork && S > 1;
-    auto fork = [&]() -> int {
-        if (two) { RL4RS_HIP_TRY(hipEventRecord(t->ev_fork, st)); RL4RS_HIP_TRY(hipStreamWaitEvent(t->side, t->ev_fork, 0)); }
-        return RL4RS_OK;
-    };
-    auto join = [&]() -> int {
-        if (two) { RL4RS_HIP_TRY(hipEventRecord(t->ev_join, t->side)); RL4RS_HIP_TRY(hipStreamWaitEvent(st, t->ev_join, 0)); }
-        return RL4RS_OK;
-    };
-    auto stream_of = [&](int s) { return (two && (s & 1)) ? t->side : st; };
-    const InputScratch sc_main = {&t->cx, t->hprev, t->dX, t->d_hid2, t->d_hid1, t->d_inp, t->dq};
-    const InputScratch sc_side = {&t->cx2, t->hprev2, t->dX2, t->d_hid2b, t->d_hid1b, t->d_inp2, t->dq2};
-    auto scratch_of = [&](int s) -> const InputScratch& { return (two && (s & 1)) ? sc_side : sc_main; };
+    // the chains of the odd sequence inputs on the second stream
+    const DtFork fk(t, st);
+    auto fork = [&]() { return fk.fork(); };
+    auto join = [&]() { return fk.join(); };
+    auto stream_of = [&](int s) { return fk.stream_of(s); };
     if ((rc = fork())) return rc;
     for (int s = 0; s < S; ++s) {
         const int pb = DP_SEQ0 + s * DP_PER_SEQ;
@@ -502,7 +532,38 @@ int rl4rs_dientrain_grad(rl4rs_dientrain* t, int32_t N, const float* dense, cons
     hipLaunchKernelGGL(k_emb_flatten, g4, b256, 0, st, cat, N, Cn, H, E, P + o[DP_CAT_EMB], t->allf, (int64_t)F, off_f);
     if ((rc = launch_gemm_f32(t->allf, F, P + o[DP_OBS_W], 256, P + o[DP_OBS_B], t->obs, 256, N, 256, F, 1, st))) return rc;
     if ((rc = launch_gemm_f32(t->obs, 256, P + o[DP_OUT_W], K, P + o[DP_OUT_B], t->logits, K, N, K, 256, 0, st))) return rc;
-    hipLaunchKernelGGL(k_bce_softmax, ew(N), b256, 0, st, t->logits, labels, N, K, t->d_logits, t->loss_rows);
+    RL4RS_LAUNCH_CHECK();
+    return RL4RS_OK;
+}
+
+int rl4rs_dientrain_grad(rl4rs_dientrain* t, int32_t N, const float* dense, const int32_t* cat, const int32_t* const* seq,
+                         const int32_t* labels, float dropout_rate, uint32_t seed, uint32_t step, float* loss_dev, void* stream) {
+    RL4RS_REQUIRE(t && dense && cat && seq && labels && N > 0 && N <= t->max_batch, "dientrain_grad: bad argument (N=%d, max_batch=%d)", N,
+                  t ? t->max_batch : -1);
+    hipStream_t st = (hipStream_t)stream;
+    int rc;
+    if ((rc = dientrain_forward(t, N, dense, cat, seq, dropout_rate, seed, step, st))) return rc;
+    const int E = t->c.emb_size, U = t->c.hidden_units, H = t->c.category_hash_size, Dn = t->c.dense_feature_num;
+    const int Cn = t->c.category_feature_num, K = t->K, S = t->c.seq_num, L = t->c.maxlen, NH2 = 2 * E, F = t->F;
+    const int Ns = N * L;
+    float* P = t->opt.params;
+    float* G = t->opt.grad;
+    const int64_t* o = t->off;
+    const int off_d = S * NH2, off_c = S * NH2 + U;
+    auto ew = [](int n) { return dim3((n + 255) / 256); };
+    const dim3 g4((N + 3) / 4), b256(256);
+    const size_t sm_cat = (size_t)(Cn * E + 2 * Cn * Cn + 2 * Cn) * 4;
+    const float* scs[4] = {nullptr, nullptr, nullptr, nullptr};
+    for (int s = 0; s < S; ++s) scs[s] = t->score[s];
+    const DtFork fk(t, st);
+    const bool two = fk.two;
+    auto fork = [&]() { return fk.fork(); };
+    auto join = [&]() { return fk.join(); };
+    auto stream_of = [&](int s) { return fk.stream_of(s); };
+    const InputScratch sc_main = {&t->cx, t->hprev, t->dX, t->d_hid2, t->d_hid1, t->d_inp, t->dq};
+    const InputScratch sc_side = {&t->cx2, t->hprev2, t->dX2, t->d_hid2b, t->d_hid1b, t->d_inp2, t->dq2};
+    auto scratch_of = [&](int s) -> const InputScratch& { return (two && (s & 1)) ? sc_side : sc_main; };
+    launch_head_loss(t->head, t->logits, labels, N, K, t->d_logits, t->loss_rows, st);
     if (loss_dev) hipLaunchKernelGGL(k_mean, dim3(1), b256, 0, st, t->loss_rows, N, loss_dev);
     RL4RS_LAUNCH_CHECK();
     // ---------------------------------------------------------------- backward
@@ -583,6 +644,18 @@ int rl4rs_dientrain_step(rl4rs_dientrain* t, int32_t N, const float* dense, cons
     int rc = rl4rs_dientrain_grad(t, N, dense, cat, seq, labels, dropout_rate, seed, step, loss_dev, stream);
     if (rc) return rc;
     adam_step(t->opt, t->opt.grad, ADAM_TF, lr, beta1, beta2, eps, nullptr, 0.f, nullptr, (hipStream_t)stream);
+    RL4RS_LAUNCH_CHECK();
+    return RL4RS_OK;
+}
+
+// as rl4rs_simtrain_eval
+int rl4rs_dientrain_eval(rl4rs_dientrain* t, int32_t N, const float* dense, const int32_t* cat, const int32_t* const* seq,
+                         const int32_t* labels, float* pred_dev, float* loss_rows_dev, void* stream) {
+    RL4RS_REQUIRE(t && pred_dev && (labels || !loss_rows_dev), "dientrain_eval: bad argument (the row losses need the labels)");
+    hipStream_t st = (hipStream_t)stream;
+    int rc;
+    if ((rc = dientrain_forward(t, N, dense, cat, seq, 0.f, 0u, 0u, st))) return rc;
+    launch_head_eval(t->head, t->logits, labels, N, t->K, t->d_logits, pred_dev, loss_rows_dev, st);
     RL4RS_LAUNCH_CHECK();
     return RL4RS_OK;
 }

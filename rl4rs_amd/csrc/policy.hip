@@ -1590,6 +1590,7 @@ int rl4rs_policy_set_option(rl4rs_policy* p, int32_t which, int32_t value) {
 
 #include "simtrain.hpp"
 #include "dientrain.hpp"
+#include "clfmetrics.hpp"
 #include "rawtrain.hpp"
 #include "qlearn.hpp"
 #include "contirl.hpp"

@@ -9,6 +9,9 @@
 //   [ cat_emb H*E | seq_emb H*E (widedeep) | dense_w1 Dn*U | dense_b1 U | dense_w2 U*U | dense_b2 U |
 //     fc_w (dnn: (E+U)*256, widedeep: S*E*256) | fc_b 256 | obs_w 256*256 (dnn) | obs_b 256 (dnn) | out_w OD*K | out_b K ]
 //   OD = 256 (dnn) or 256 + U + Cn*E (widedeep: 'simulator_obs' is the concat itself)
+// rl4rs_simtrain_create_head: the same trunks under the slate-wise output layers of *_slate.py / *_slate_multiclass.py (K = 9 / 22
+// instead of class_num, labels [N, 9]; k_slate_head) and the adversarial_slate.py model (algo 4: [ cat_emb | seq_emb | dense tower |
+// out_w (S*E + U + E) * 9 | out_b 9 ]); rl4rs_simtrain_eval: the same forward without dropout, no backward (validation).
 #pragma once
 
 namespace rl4rs {
@@ -60,6 +63,83 @@ __global__ void k_bce_softmax(const float* __restrict__ logits, const int32_t* _
     }
     loss_rows[n] = loss / (float)K;
     for (int k = 0; k < K; ++k) dlogits[(size_t)n * K + k] = p[k] * (dp[k] - dot) / (float)N;
+}
+
+// ---- the slate-wise heads (rl4rs/nets/*_slate.py, *_slate_multiclass.py, adversarial_slate.py): labels int32 [N, 9] of 0 / 1.
+// One thread per row.  Every output is optional: dlogits = d loss_mean / d logits (inv_n = 1 / N), pred = the model output
+// (sigmoid / softmax), loss_rows; labels may be NULL when only pred is asked for.  All losses are taken from the LOGITS, as keras
+// does for a Sigmoid / Softmax output op - nothing is clipped, so they stay finite and differentiable at any logit.
+constexpr int SLATE_ITEMS = 9, SLATE_CLASSES = 22;
+
+// sigmoid(x) and 1 - sigmoid(x), each to full relative precision
+__device__ __forceinline__ void sigmoid_pair(float x, float& s, float& c) {
+    const float e = expf(-fabsf(x)), a = 1.0f / (1.0f + e), b = e / (1.0f + e);
+    s = x >= 0.f ? a : b;
+    c = x >= 0.f ? b : a;
+}
+// sigmoid cross-entropy from the logit: max(x, 0) - x y + log1p(exp(-|x|))
+__device__ __forceinline__ float sigmoid_xent(float x, float y) { return fmaxf(x, 0.f) - x * y + log1pf(expf(-fabsf(x))); }
+
+__global__ void k_slate_head(const float* __restrict__ logits, const int32_t* __restrict__ labels, int N, int head, float inv_n,
+                             float* __restrict__ dlogits, float* __restrict__ pred, float* __restrict__ loss_rows) {
+    const int n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= N) return;
+    float y[SLATE_ITEMS];
+    for (int j = 0; j < SLATE_ITEMS; ++j) y[j] = labels && labels[(size_t)n * SLATE_ITEMS + j] != 0 ? 1.f : 0.f;
+    if (head == RL4RS_HEAD_SLATE_MULTICLASS) {
+        const int K = SLATE_CLASSES;
+        const float* x = logits + (size_t)n * K;
+        int c = 0;
+        for (int j = 0; j < SLATE_ITEMS; ++j) c += y[j] != 0.f ? (1 << (j % 3)) : 0;          // y . [1, 2, 4, 1, 2, 4, 1, 2, 4]
+        float mx = x[0];
+        for (int k = 1; k < K; ++k) mx = fmaxf(mx, x[k]);
+        float se = 0.f;
+        for (int k = 0; k < K; ++k) se += expf(x[k] - mx);
+        if (loss_rows) loss_rows[n] = logf(se) + (mx - x[c]);
+        for (int k = 0; k < K; ++k) {
+            const float p = expf(x[k] - mx) / se;
+            if (pred) pred[(size_t)n * K + k] = p;
+            if (dlogits) dlogits[(size_t)n * K + k] = (p - (k == c ? 1.f : 0.f)) * inv_n;
+        }
+        return;
+    }
+    const int K = SLATE_ITEMS;
+    const float* x = logits + (size_t)n * K;
+    float s[SLATE_ITEMS], cs[SLATE_ITEMS], bce = 0.f, smax = 0.f;
+    for (int j = 0; j < K; ++j) {
+        sigmoid_pair(x[j], s[j], cs[j]);
+        bce += sigmoid_xent(x[j], y[j]);
+        smax = fmaxf(smax, s[j]);
+        if (pred) pred[(size_t)n * K + j] = s[j];
+    }
+    bce /= (float)K;
+    if (head == RL4RS_HEAD_SLATE) {
+        if (loss_rows) loss_rows[n] = bce;
+        if (dlogits)
+            for (int j = 0; j < K; ++j) dlogits[(size_t)n * K + j] = (y[j] != 0.f ? -cs[j] : s[j]) / (float)K * inv_n;
+        return;
+    }
+    // adversarial: 0.1 * bce + sum_j softmax(s)_j (1 - y_j); the second term's gradient runs through the softmax and the sigmoid
+    float q[SLATE_ITEMS], se = 0.f, ext = 0.f;
+    for (int j = 0; j < K; ++j) { q[j] = expf(s[j] - smax); se += q[j]; }
+    for (int j = 0; j < K; ++j) { q[j] /= se; ext += q[j] * (1.f - y[j]); }
+    if (loss_rows) loss_rows[n] = 0.1f * bce + ext;
+    if (dlogits)
+        for (int j = 0; j < K; ++j) {
+            const float d_bce = (y[j] != 0.f ? -cs[j] : s[j]) / (float)K;
+            const float d_ext = q[j] * ((1.f - y[j]) - ext) * s[j] * cs[j];
+            dlogits[(size_t)n * K + j] = (0.1f * d_bce + d_ext) * inv_n;
+        }
+}
+
+// the item-wise head's output: softmax over class_num <= 8 logits
+__global__ void k_softmax_rows(const float* __restrict__ logits, int N, int K, float* __restrict__ pred) {
+    const int n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= N) return;
+    float p[8], mx = -3.4028235e38f, se = 0.f;
+    for (int k = 0; k < K; ++k) mx = fmaxf(mx, logits[(size_t)n * K + k]);
+    for (int k = 0; k < K; ++k) { p[k] = expf(logits[(size_t)n * K + k] - mx); se += p[k]; }
+    for (int k = 0; k < K; ++k) pred[(size_t)n * K + k] = p[k] / se;
 }
 
 __global__ void k_transpose(const float* __restrict__ w, int64_t ldw, int rows, int cols, float* __restrict__ wt) {
@@ -202,6 +282,8 @@ struct rl4rs_simtrain {
     int64_t off[SP_COUNT], size[SP_COUNT];       // offsets / sizes in the flat buffers (size 0 = the family has no such array)
     size_t part_cap;                             // floats behind `part`
     int max_batch, chunk, nz, OD, FCK;           // OD = width of 'simulator_obs', FCK = input width of the fc layer
+    int head, K;                                 // RL4RS_HEAD_*; width of the output layer (class_num, 9 or 22)
+    int32_t* ids_adv;                            // adversarial: the first category_feature_num - 1 ids of every row, contiguous
     OptBlock opt;
     float *feat, *h1, *h1d, *h2, *a1, *obs, *logits;            // activations (feat = input of fc, a1 = its output for dnn)
     float *d_logits, *d_obs, *d_a, *d_feat, *d_h1, *d_h2, *wt, *part, *loss_rows;
@@ -222,6 +304,29 @@ struct rl4rs_simtrain {
 struct GruScratch { float *dX, *hprev, *tmpw, *wt, *part; size_t part_cap; };
 
 namespace {
+
+inline int head_width(int head, int class_num) {
+    return head == RL4RS_HEAD_ITEM ? class_num : (head == RL4RS_HEAD_SLATE_MULTICLASS ? SLATE_CLASSES : SLATE_ITEMS);
+}
+// row losses and d loss_mean / d logits of a head (the trainers' grad)
+inline void launch_head_loss(int head, const float* logits, const int32_t* labels, int N, int K, float* dlogits, float* loss_rows,
+                             hipStream_t st) {
+    const dim3 grid((N + 255) / 256), b256(256);
+    if (head == RL4RS_HEAD_ITEM) hipLaunchKernelGGL(k_bce_softmax, grid, b256, 0, st, logits, labels, N, K, dlogits, loss_rows);
+    else hipLaunchKernelGGL(k_slate_head, grid, b256, 0, st, logits, labels, N, head, 1.0f / (float)N, dlogits, (float*)nullptr, loss_rows);
+}
+// the model output and (labels != NULL) the row losses of a head (the trainers' eval); dl_scratch [N, K]: the item-wise loss kernel
+// writes its gradient there
+inline void launch_head_eval(int head, const float* logits, const int32_t* labels, int N, int K, float* dl_scratch, float* pred,
+                             float* loss_rows, hipStream_t st) {
+    const dim3 grid((N + 255) / 256), b256(256);
+    if (head == RL4RS_HEAD_ITEM) {
+        hipLaunchKernelGGL(k_softmax_rows, grid, b256, 0, st, logits, N, K, pred);
+        if (loss_rows) hipLaunchKernelGGL(k_bce_softmax, grid, b256, 0, st, logits, labels, N, K, dl_scratch, loss_rows);
+    } else {
+        hipLaunchKernelGGL(k_slate_head, grid, b256, 0, st, logits, labels, N, head, 0.f, (float*)nullptr, pred, loss_rows);
+    }
+}
 
 // sample-axis reductions / transposed-weight GEMM over an explicit number of samples
 struct TrainCtx { int chunk; float* part; float* wt; size_t part_cap = 0; };       // part_cap: floats behind `part` (0 = sized for `chunk` only)
@@ -444,20 +549,30 @@ int rl4rs_simtrain_destroy(rl4rs_simtrain* t) {
     return RL4RS_OK;
 }
 
-int rl4rs_simtrain_create(const rl4rs_simnet_cfg* c, const rl4rs_simnet_weights* w, int32_t max_batch, void* stream,
-                          rl4rs_simtrain** out) {
+// head = RL4RS_HEAD_ITEM: rl4rs_simtrain_create itself.  The other heads replace the output layer by [obs_dim, 9] / [obs_dim, 22]
+// (cfg->class_num is not read) and take int32 [N, 9] labels; RL4RS_SIMNET_ADVERSARIAL comes with RL4RS_HEAD_ADVERSARIAL only.
+static int simtrain_create_impl(const rl4rs_simnet_cfg* c, const rl4rs_simnet_weights* w, int head, int32_t max_batch, void* stream,
+                                rl4rs_simtrain** out) {
     RL4RS_REQUIRE(c && w && out && max_batch > 0, "simtrain_create: bad argument");
-    RL4RS_REQUIRE(c->algo >= RL4RS_SIMNET_DNN && c->algo <= RL4RS_SIMNET_LSTM,
-                  "simtrain: algo must be 1 (dnn), 2 (widedeep) or 3 (lstm), got %d", c->algo);
+    RL4RS_REQUIRE(head >= RL4RS_HEAD_ITEM && head <= RL4RS_HEAD_ADVERSARIAL, "simtrain_create_head: head must be 0 .. 3, got %d", head);
+    const bool adv = c->algo == RL4RS_SIMNET_ADVERSARIAL;
+    if (head == RL4RS_HEAD_ITEM)
+        RL4RS_REQUIRE(c->algo >= RL4RS_SIMNET_DNN && c->algo <= RL4RS_SIMNET_LSTM,
+                      "simtrain: algo must be 1 (dnn), 2 (widedeep) or 3 (lstm), got %d", c->algo);
+    else
+        RL4RS_REQUIRE(c->algo >= RL4RS_SIMNET_DNN && c->algo <= RL4RS_SIMNET_ADVERSARIAL && adv == (head == RL4RS_HEAD_ADVERSARIAL),
+                      "simtrain_create_head: algo %d does not go with head %d (the adversarial model and the adversarial head come together)",
+                      c->algo, head);
     RL4RS_REQUIRE(c->emb_size > 0 && c->hidden_units > 0 && c->dense_feature_num > 0 && c->category_feature_num > 0 &&
-                  c->category_hash_size > 0 && c->class_num >= 2 && c->class_num <= 8 && c->seq_num >= 1 && c->seq_num <= 4 &&
-                  c->maxlen >= 1, "simtrain: bad sizes");
+                  c->category_hash_size > 0 && (head != RL4RS_HEAD_ITEM || (c->class_num >= 2 && c->class_num <= 8)) && c->seq_num >= 1 &&
+                  c->seq_num <= 4 && c->maxlen >= 1, "simtrain: bad sizes");
+    RL4RS_REQUIRE(!adv || c->category_feature_num >= 2, "simtrain: the adversarial model drops the last category id, so it needs two");
     const bool wd = c->algo == RL4RS_SIMNET_WIDEDEEP, ls = c->algo == RL4RS_SIMNET_LSTM;
     RL4RS_REQUIRE(w->cat_emb && w->dense_w1 && w->dense_b1 && w->dense_w2 && w->dense_b2 && w->out_w && w->out_b,
                   "simtrain_create: weights missing");
-    RL4RS_REQUIRE(ls || (w->fc_w && w->fc_b), "simtrain_create: fc weights missing");
-    RL4RS_REQUIRE(wd || (w->obs_w && w->obs_b), "simtrain_create: obs weights missing");
-    RL4RS_REQUIRE(!(wd || ls) || w->seq_emb, "simtrain_create: seq_emb missing");
+    RL4RS_REQUIRE(ls || adv || (w->fc_w && w->fc_b), "simtrain_create: fc weights missing");
+    RL4RS_REQUIRE(wd || adv || (w->obs_w && w->obs_b), "simtrain_create: obs weights missing");
+    RL4RS_REQUIRE(!(wd || ls || adv) || w->seq_emb, "simtrain_create: seq_emb missing");
     if (ls) {
         RL4RS_REQUIRE(w->cat_gru_kernel && w->cat_gru_recurrent && w->cat_gru_bias, "simtrain_create: category GRU weights missing");
         for (int s2 = 0; s2 < c->seq_num; ++s2)
@@ -469,19 +584,25 @@ int rl4rs_simtrain_create(const rl4rs_simnet_cfg* c, const rl4rs_simnet_weights*
         return RL4RS_EHIP;
     }
     hipStream_t st = (hipStream_t)stream;
-    const int64_t E = c->emb_size, U = c->hidden_units, H = c->category_hash_size, Dn = c->dense_feature_num, K = c->class_num;
+    const int64_t E = c->emb_size, U = c->hidden_units, H = c->category_hash_size, Dn = c->dense_feature_num;
+    const int64_t K = head_width(head, c->class_num);
     const int64_t S = c->seq_num, Cn = c->category_feature_num;
     rl4rs_simtrain* t = new rl4rs_simtrain();
     t->c = *c;
+    t->head = head;
+    t->K = (int)K;
+    t->ids_adv = nullptr;
     t->max_batch = max_batch;
     t->chunk = 512;
     t->nz = (max_batch + t->chunk - 1) / t->chunk;
     t->opt.t = 0;
-    t->OD = wd ? (int)(256 + U + Cn * E) : 256;
-    // FCK = width of the concat that feeds the first dense layer above the branches (fc for dnn / widedeep, obs for lstm)
-    t->FCK = wd ? (int)(S * E) : (ls ? (int)(S * U + 2 * U + Cn * E) : (int)(E + U));
-    int64_t sizes[SP_COUNT] = {H * E, (wd || ls) ? H * E : 0, Dn * U, U, U * U, U, ls ? 0 : (int64_t)t->FCK * 256, ls ? 0 : 256,
-                               wd ? 0 : (ls ? (int64_t)t->FCK * 256 : 256 * 256), wd ? 0 : 256, (int64_t)t->OD * K, K};
+    // FCK = width of the concat that feeds the first dense layer above the branches (fc for dnn / widedeep, obs for lstm; the
+    // adversarial model has no such layer: its concat [pooled sequences | tower | pooled categories] feeds the output layer)
+    t->FCK = wd ? (int)(S * E) : (ls ? (int)(S * U + 2 * U + Cn * E) : (adv ? (int)(S * E + U + E) : (int)(E + U)));
+    t->OD = wd ? (int)(256 + U + Cn * E) : (adv ? t->FCK : 256);
+    int64_t sizes[SP_COUNT] = {H * E, (wd || ls || adv) ? H * E : 0, Dn * U, U, U * U, U, (ls || adv) ? 0 : (int64_t)t->FCK * 256,
+                               (ls || adv) ? 0 : 256, (wd || adv) ? 0 : (ls ? (int64_t)t->FCK * 256 : 256 * 256), (wd || adv) ? 0 : 256,
+                               (int64_t)t->OD * K, K};
     const float* src[SP_COUNT] = {w->cat_emb, w->seq_emb, w->dense_w1, w->dense_b1, w->dense_w2, w->dense_b2, w->fc_w, w->fc_b,
                                   w->obs_w, w->obs_b, w->out_w, w->out_b};
     for (int i = SP_GRU0; i < SP_COUNT; ++i) { sizes[i] = 0; src[i] = nullptr; }
@@ -580,6 +701,7 @@ int rl4rs_simtrain_create(const rl4rs_simnet_cfg* c, const rl4rs_simnet_weights*
         }
     }
     ST_FAIL(al(&t->loss_rows, B));
+    if (adv) { float* p; ST_FAIL(al(&p, B * (Cn - 1))); t->ids_adv = reinterpret_cast<int32_t*>(p); }
     {
         float* m;
         ST_FAIL(al(&m, (B * U + 3) / 4 + 1));
@@ -594,6 +716,20 @@ int rl4rs_simtrain_create(const rl4rs_simnet_cfg* c, const rl4rs_simnet_weights*
     return RL4RS_OK;
 }
 
+int rl4rs_simtrain_create(const rl4rs_simnet_cfg* c, const rl4rs_simnet_weights* w, int32_t max_batch, void* stream,
+                          rl4rs_simtrain** out) {
+    return simtrain_create_impl(c, w, RL4RS_HEAD_ITEM, max_batch, stream, out);
+}
+
+int rl4rs_simtrain_create_head(const rl4rs_simnet_cfg* c, const rl4rs_simnet_weights* w, int32_t head, int32_t max_batch, void* stream,
+                               rl4rs_simtrain** out) {
+    return simtrain_create_impl(c, w, head, max_batch, stream, out);
+}
+
+int rl4rs_simtrain_adam_state(rl4rs_simtrain* t, float** m_dev, float** v_dev, int64_t* step) {
+    return opt_adam_state(RL4RS_OPT(t), m_dev, v_dev, step, "simtrain_adam_state");
+}
+
 int rl4rs_simtrain_params(rl4rs_simtrain* t, float** params_dev, float** grad_dev, int64_t* count) {
     return opt_params(RL4RS_OPT(t), params_dev, grad_dev, count, "simtrain_params");
 }
@@ -606,33 +742,28 @@ int rl4rs_simtrain_masks(rl4rs_simtrain* t, uint8_t** mask1_dev, uint8_t** mask2
     return RL4RS_OK;
 }
 
-// forward (training mode) + loss + backward into the handle's flat gradient buffer; loss_dev[0] = mean loss (may be NULL).
-// seq: seq_num device pointers of int32 [N, maxlen] (widedeep; ignored for dnn, whose model never reads its sequences).
-int rl4rs_simtrain_grad(rl4rs_simtrain* t, int32_t N, const float* dense, const int32_t* cat, const int32_t* const* seq,
-                        const int32_t* labels, float dropout_rate, uint32_t seed, uint32_t step, float* loss_dev, void* stream) {
-    RL4RS_REQUIRE(t && dense && cat && labels && N > 0 && N <= t->max_batch, "simtrain_grad: bad argument (N=%d, max_batch=%d)", N,
-                  t ? t->max_batch : -1);
+// The forward of grad (training mode: dropout_rate > 0 draws the masks) and of eval (dropout_rate = 0: the inference forward) up to
+// the logits [N, K]; keeps every activation the backward needs.  Checks the arguments the two share.
+static int simtrain_forward(rl4rs_simtrain* t, int32_t N, const float* dense, const int32_t* cat, const int32_t* const* seq,
+                            float dropout_rate, uint32_t seed, uint32_t step, hipStream_t st) {
+    RL4RS_REQUIRE(t && dense && cat && N > 0 && N <= t->max_batch, "simtrain: bad argument (N=%d, max_batch=%d)", N, t ? t->max_batch : -1);
     RL4RS_REQUIRE(dropout_rate >= 0.f && dropout_rate < 1.f, "simtrain_grad: dropout_rate must be in [0, 1)");
-    const bool wd = t->c.algo == RL4RS_SIMNET_WIDEDEEP, ls = t->c.algo == RL4RS_SIMNET_LSTM;
-    if (wd || ls) {
-        RL4RS_REQUIRE(seq, "simtrain_grad: widedeep / lstm need the sequence inputs");
+    const bool wd = t->c.algo == RL4RS_SIMNET_WIDEDEEP, ls = t->c.algo == RL4RS_SIMNET_LSTM, adv = t->c.algo == RL4RS_SIMNET_ADVERSARIAL;
+    if (wd || ls || adv) {
+        RL4RS_REQUIRE(seq, "simtrain_grad: widedeep / lstm / adversarial need the sequence inputs");
         for (int s = 0; s < t->c.seq_num; ++s) RL4RS_REQUIRE(seq[s], "simtrain_grad: sequence input %d is NULL", s);
     }
-    hipStream_t st = (hipStream_t)stream;
     const int E = t->c.emb_size, U = t->c.hidden_units, H = t->c.category_hash_size, Dn = t->c.dense_feature_num;
-    const int Cn = t->c.category_feature_num, K = t->c.class_num, S = t->c.seq_num, L = t->c.maxlen;
+    const int Cn = t->c.category_feature_num, K = t->K, S = t->c.seq_num, L = t->c.maxlen;
     const int FCK = t->FCK, OD = t->OD;
     float* P = t->opt.params;
-    float* G = t->opt.grad;
     const int64_t* o = t->off;
     int rc;
     auto ew = [](int n) { return dim3((n + 255) / 256); };
     const dim3 g4((N + 3) / 4), b256(256);
-    // where the (dropped-out) dense-tower output lives, and its gradient
-    float* tower_out = wd ? t->obs + 256 : (ls ? t->feat + S * U : t->feat + E);
+    // where the (dropped-out) dense-tower output lives
+    float* tower_out = wd ? t->obs + 256 : (ls ? t->feat + S * U : (adv ? t->feat + S * E : t->feat + E));
     const int tower_ld = wd ? OD : FCK;
-    float* d_tower = wd ? t->d_obs + 256 : (ls ? t->d_feat + S * U : t->d_feat + E);
-    // ---- forward
     if ((rc = launch_gemm_f32(dense, Dn, P + o[SP_DW1], U, P + o[SP_DB1], t->h1, U, N, U, Dn, 1, st))) return rc;
     RL4RS_HIP_TRY(hipMemcpyAsync(t->h1d, t->h1, (size_t)N * U * 4, hipMemcpyDeviceToDevice, st));
     hipLaunchKernelGGL(k_dropout, ew(N * U), b256, 0, st, t->h1d, t->mask1, N * U, U, dropout_rate, seed, step, 0u);
@@ -645,6 +776,12 @@ int rl4rs_simtrain_grad(rl4rs_simtrain* t, int32_t N, const float* dense, const 
             hipLaunchKernelGGL(k_emb_mean, g4, b256, 0, st, seq[s], N, L, H, E, P + o[SP_SEQ_EMB], t->feat, (int64_t)FCK, s * E);
         if ((rc = launch_gemm_f32(t->feat, FCK, P + o[SP_FC_W], 256, P + o[SP_FC_B], t->obs, OD, N, 256, FCK, 1, st))) return rc;
         hipLaunchKernelGGL(k_emb_flatten, g4, b256, 0, st, cat, N, Cn, H, E, P + o[SP_CAT_EMB], t->obs, (int64_t)OD, 256 + U);
+    } else if (adv) {
+        // [mean-pooled sequence embeddings | tower | mean of the category embeddings without the last id]: the output layer's input
+        for (int s = 0; s < S; ++s)
+            hipLaunchKernelGGL(k_emb_mean, g4, b256, 0, st, seq[s], N, L, H, E, P + o[SP_SEQ_EMB], t->feat, (int64_t)FCK, s * E);
+        RL4RS_HIP_TRY(hipMemcpy2DAsync(t->ids_adv, (size_t)(Cn - 1) * 4, cat, (size_t)Cn * 4, (size_t)(Cn - 1) * 4, N, hipMemcpyDeviceToDevice, st));
+        hipLaunchKernelGGL(k_emb_mean, g4, b256, 0, st, t->ids_adv, N, Cn - 1, H, E, P + o[SP_CAT_EMB], t->feat, (int64_t)FCK, S * E + U);
     } else if (ls) {
         // [GRU finals of the sequences | tower | GRU final of the category embeddings | Flatten(category emb)] -> obs (lstm.py:31-36)
         for (int g = 0; g <= S; ++g) t->gru[g].ids = g == 0 ? cat : seq[g - 1];
@@ -676,8 +813,33 @@ int rl4rs_simtrain_grad(rl4rs_simtrain* t, int32_t N, const float* dense, const 
         if ((rc = launch_gemm_f32(t->feat, FCK, P + o[SP_FC_W], 256, P + o[SP_FC_B], t->a1, 256, N, 256, FCK, 1, st))) return rc;
         if ((rc = launch_gemm_f32(t->a1, 256, P + o[SP_OBS_W], 256, P + o[SP_OBS_B], t->obs, 256, N, 256, 256, 1, st))) return rc;
     }
-    if ((rc = launch_gemm_f32(t->obs, OD, P + o[SP_OUT_W], K, P + o[SP_OUT_B], t->logits, K, N, K, OD, 0, st))) return rc;
-    hipLaunchKernelGGL(k_bce_softmax, ew(N), b256, 0, st, t->logits, labels, N, K, t->d_logits, t->loss_rows);
+    if ((rc = launch_gemm_f32(adv ? t->feat : t->obs, OD, P + o[SP_OUT_W], K, P + o[SP_OUT_B], t->logits, K, N, K, OD, 0, st))) return rc;
+    RL4RS_LAUNCH_CHECK();
+    return RL4RS_OK;
+}
+
+// forward (training mode) + loss + backward into the handle's flat gradient buffer; loss_dev[0] = mean loss (may be NULL).
+// seq: seq_num device pointers of int32 [N, maxlen] (widedeep; ignored for dnn, whose model never reads its sequences).
+int rl4rs_simtrain_grad(rl4rs_simtrain* t, int32_t N, const float* dense, const int32_t* cat, const int32_t* const* seq,
+                        const int32_t* labels, float dropout_rate, uint32_t seed, uint32_t step, float* loss_dev, void* stream) {
+    RL4RS_REQUIRE(t && dense && cat && labels && N > 0 && N <= t->max_batch, "simtrain_grad: bad argument (N=%d, max_batch=%d)", N,
+                  t ? t->max_batch : -1);
+    hipStream_t st = (hipStream_t)stream;
+    int rc;
+    if ((rc = simtrain_forward(t, N, dense, cat, seq, dropout_rate, seed, step, st))) return rc;
+    const bool wd = t->c.algo == RL4RS_SIMNET_WIDEDEEP, ls = t->c.algo == RL4RS_SIMNET_LSTM, adv = t->c.algo == RL4RS_SIMNET_ADVERSARIAL;
+    const int E = t->c.emb_size, U = t->c.hidden_units, H = t->c.category_hash_size, Dn = t->c.dense_feature_num;
+    const int Cn = t->c.category_feature_num, K = t->K, S = t->c.seq_num, L = t->c.maxlen;
+    const int FCK = t->FCK, OD = t->OD;
+    float* P = t->opt.params;
+    float* G = t->opt.grad;
+    const int64_t* o = t->off;
+    auto ew = [](int n) { return dim3((n + 255) / 256); };
+    const dim3 g4((N + 3) / 4), b256(256);
+    // the gradient of the (dropped-out) dense-tower output
+    const int tower_ld = wd ? OD : FCK;
+    float* d_tower = wd ? t->d_obs + 256 : (ls ? t->d_feat + S * U : (adv ? t->d_feat + S * E : t->d_feat + E));
+    launch_head_loss(t->head, t->logits, labels, N, K, t->d_logits, t->loss_rows, st);
     if (loss_dev) hipLaunchKernelGGL(k_mean, dim3(1), b256, 0, st, t->loss_rows, N, loss_dev);
     RL4RS_LAUNCH_CHECK();
     // ---- backward
@@ -696,10 +858,15 @@ int rl4rs_simtrain_grad(rl4rs_simtrain* t, int32_t N, const float* dense, const 
         return launch_gemm_f32(dY, ldy, t->wt, Kin, nullptr, dX, ldx, N, Kin, Nout, 0, st);
     };
     RL4RS_HIP_TRY(hipMemsetAsync(G + o[SP_CAT_EMB], 0, (size_t)H * E * 4, st));
-    tn(t->obs, OD, OD, t->d_logits, K, K, G + o[SP_OUT_W]);
+    tn(adv ? t->feat : t->obs, OD, OD, t->d_logits, K, K, G + o[SP_OUT_W]);
     cs(t->d_logits, K, K, G + o[SP_OUT_B]);
-    if ((rc = back(t->d_logits, K, K, P + o[SP_OUT_W], OD, t->d_obs, OD))) return rc;
-    if (wd) {
+    if ((rc = back(t->d_logits, K, K, P + o[SP_OUT_W], OD, adv ? t->d_feat : t->d_obs, OD))) return rc;
+    if (adv) {
+        RL4RS_HIP_TRY(hipMemsetAsync(G + o[SP_SEQ_EMB], 0, (size_t)H * E * 4, st));
+        for (int s = 0; s < S; ++s)
+            hipLaunchKernelGGL(k_emb_mean_bwd, g4, b256, 0, st, seq[s], N, L, H, E, t->d_feat + s * E, (int64_t)FCK, G + o[SP_SEQ_EMB]);
+        hipLaunchKernelGGL(k_emb_mean_bwd, g4, b256, 0, st, t->ids_adv, N, Cn - 1, H, E, t->d_feat + S * E + U, (int64_t)FCK, G + o[SP_CAT_EMB]);
+    } else if (wd) {
         // 'simulator_obs' = [ELU(fc(pooled sequences)) | tower | Flatten(category emb)]: three gradient slices of d_obs
         hipLaunchKernelGGL(k_elu_bwd, ew(N * 256), b256, 0, st, t->d_obs, (int64_t)OD, t->obs, (int64_t)OD, (const uint8_t*)nullptr, 0.f, N * 256, 256);
         tn(t->feat, FCK, FCK, t->d_obs, OD, 256, G + o[SP_FC_W]);
@@ -772,6 +939,20 @@ int rl4rs_simtrain_step(rl4rs_simtrain* t, int32_t N, const float* dense, const 
     int rc = rl4rs_simtrain_grad(t, N, dense, cat, seq, labels, dropout_rate, seed, step, loss_dev, stream);
     if (rc) return rc;
     adam_step(t->opt, t->opt.grad, ADAM_TF, lr, beta1, beta2, eps, nullptr, 0.f, nullptr, (hipStream_t)stream);
+    RL4RS_LAUNCH_CHECK();
+    return RL4RS_OK;
+}
+
+// Inference pass on a trainer handle: forward without dropout, no backward; parameters, gradient buffer and Adam state untouched
+// (the activations and the dropout masks of the last grad are overwritten).  pred_dev [N, K]: the model output (softmax / sigmoid);
+// loss_rows_dev [N] (may be NULL; needs labels_dev): the row losses of the head.
+int rl4rs_simtrain_eval(rl4rs_simtrain* t, int32_t N, const float* dense, const int32_t* cat, const int32_t* const* seq,
+                        const int32_t* labels, float* pred_dev, float* loss_rows_dev, void* stream) {
+    RL4RS_REQUIRE(t && pred_dev && (labels || !loss_rows_dev), "simtrain_eval: bad argument (the row losses need the labels)");
+    hipStream_t st = (hipStream_t)stream;
+    int rc;
+    if ((rc = simtrain_forward(t, N, dense, cat, seq, 0.f, 0u, 0u, st))) return rc;
+    launch_head_eval(t->head, t->logits, labels, N, t->K, t->d_logits, pred_dev, loss_rows_dev, st);
     RL4RS_LAUNCH_CHECK();
     return RL4RS_OK;
 }

@@ -826,7 +826,13 @@ SIMTRAIN_ORDER = {
     # lstm: + the keras GRUs (category GRU, then one per sequence input; the names carry the sequence index)
     'lstm': ('cat_emb', 'seq_emb', 'dense_w1', 'dense_b1', 'dense_w2', 'dense_b2', 'obs_w', 'obs_b', 'out_w', 'out_b',
              'cat_gru_kernel', 'cat_gru_recurrent', 'cat_gru_bias'),
+    # adversarial_slate.py (trainer only, head 'adversarial'): the concat feeds the output layer directly
+    'adversarial_slate': ('cat_emb', 'seq_emb', 'dense_w1', 'dense_b1', 'dense_w2', 'dense_b2', 'out_w', 'out_b'),
 }
+
+
+SIMTRAIN_ALGOS = dict(SIMNET_ALGOS, adversarial_slate=4)       # include/rl4rs_hip.h RL4RS_SIMNET_ADVERSARIAL: trainer only
+TRAIN_HEADS = {'item': 0, 'slate': 1, 'multiclass': 2, 'adversarial': 3}       # include/rl4rs_hip.h RL4RS_HEAD_*
 
 
 def _simtrain_names(algo, seq_num):
@@ -946,10 +952,20 @@ class _FlatNet(object):
 class DeviceSimTrainer(_FlatNet):
     """rl4rs_simtrain handle: supervised training of the 'dnn' / 'widedeep' / 'lstm' simulators on the device
     (script/supervised_train.py): forward with dropout, keras binary_crossentropy, backward, Adam.  ``weights()`` carries the
-    names of rl4rs_amd.nets.simnets.simnet_spec; ``grad`` is the forward + backward here, the flat gradient is ``flat_gradient()``."""
+    names of rl4rs_amd.nets.simnets.simnet_spec; ``grad`` is the forward + backward here, the flat gradient is ``flat_gradient()``.
+    ``head``: 'item' (labels [N]), or the slate-wise output layers 'slate' / 'multiclass' (the *_slate.py / *_slate_multiclass.py
+    models; labels [N, 9] of 0 / 1), or 'adversarial' with algo 'adversarial_slate'."""
     _prefix = 'rl4rs_simtrain_'
 
-    def __init__(self, config, weights, max_batch=256, algo=None, device=None):
+    def _set_head(self, head):
+        if head not in TRAIN_HEADS:
+            raise ValueError("head must be one of %s (got %r)" % (sorted(TRAIN_HEADS), head))
+        if (head == 'adversarial') != (self.algo == 'adversarial_slate'):
+            raise ValueError("head 'adversarial' and algo 'adversarial_slate' come as a pair (got head %r, algo %r)" % (head, self.algo))
+        self.head = head
+        self.K = int(self.config['class_num']) if head == 'item' else (22 if head == 'multiclass' else 9)
+
+    def __init__(self, config, weights, max_batch=256, algo=None, device=None, head='item'):
         _lib.require_device()
         self.lib = _lib.load()
         self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
@@ -957,10 +973,11 @@ class DeviceSimTrainer(_FlatNet):
         self.algo = str(algo if algo is not None else config.get('algo', 'dnn')).lower()
         if self.algo not in SIMTRAIN_ORDER:
             raise NotImplementedError("device-side simulator training exists for %s (got %r)" % (sorted(SIMTRAIN_ORDER), self.algo))
+        self._set_head(head)
         self.Cn, self.Dn = int(config['category_feature_num']), int(config['dense_feature_num'])
         self.S, self.L = int(config['seq_num']), int(config['maxlen'])
         self.max_batch = int(max_batch)
-        cfg = _lib.SimnetCfg(SIMNET_ALGOS[self.algo], self.L, int(config['emb_size']), int(config['hidden_units']),
+        cfg = _lib.SimnetCfg(SIMTRAIN_ALGOS[self.algo], self.L, int(config['emb_size']), int(config['hidden_units']),
                              self.Dn, self.Cn, int(config['category_hash_size']), self.S,
                              int(config['class_num']), self.max_batch, 1)
         w = _lib.SimnetWeights()
@@ -977,9 +994,11 @@ class DeviceSimTrainer(_FlatNet):
                 setattr(w, name, ptr)
         h = C.c_void_p()
         with torch.cuda.device(self.device):
-            check(self.lib.rl4rs_simtrain_create(C.byref(cfg), C.byref(w), self.max_batch, _stream(), C.byref(h)))
+            check(self.lib.rl4rs_simtrain_create_head(C.byref(cfg), C.byref(w), TRAIN_HEADS[self.head], self.max_batch, _stream(),
+                                                      C.byref(h)))
         self.h = h
         self.iteration = 0
+        self.n_params = self._ptrs()[2]
 
     def masks(self, N):
         """The dropout keep-masks [N, hidden_units] (uint8) of the last grad / step call."""
@@ -997,8 +1016,9 @@ class DeviceSimTrainer(_FlatNet):
         N = dense.shape[0]
         assert dense.dtype == torch.float32 and dense.shape == (N, self.Dn) and dense.is_contiguous()
         assert cat.dtype == torch.int32 and cat.shape == (N, self.Cn) and cat.is_contiguous()
-        labels = labels.to(torch.int32).contiguous()
-        assert labels.shape == (N,)
+        if labels is not None:
+            labels = labels.to(torch.int32).contiguous()
+            assert labels.shape == ((N,) if self.head == 'item' else (N, 9)), (self.head, tuple(labels.shape))
         sp = None
         if self.algo != 'dnn':
             assert seqs is not None and len(seqs) == self.S, "every family but dnn needs the seq_num sequence inputs"
@@ -1023,6 +1043,16 @@ class DeviceSimTrainer(_FlatNet):
         self.iteration += 1
         return loss
 
+    def evaluate(self, dense, cat, labels=None, seqs=None):
+        """Inference forward (no dropout, no backward; parameters, gradient and Adam state untouched) -> (pred [N, K], loss_rows
+        [N]): the model output - softmax for 'item' (K = class_num) and 'multiclass' (K = 22), sigmoid (K = 9) otherwise - and the
+        head's row losses (None without labels).  Device tensors; nothing waits for the host."""
+        N, labels, sp = self._batch(dense, cat, labels, seqs)
+        pred = torch.empty((N, self.K), dtype=torch.float32, device=self.device)
+        rows = torch.empty(N, dtype=torch.float32, device=self.device) if labels is not None else None
+        check(self._call('eval')(self.h, N, _ptr(dense), _ptr(cat), sp, _ptr(labels), _ptr(pred), _ptr(rows), _stream()))
+        return pred, rows
+
 
 DIENTRAIN_BASE = ('cat_emb', 'seq_emb', 'dense_w1', 'dense_b1', 'dense_w2', 'dense_b2', 'obs_w', 'obs_b', 'out_w', 'out_b')
 DIENTRAIN_SEQ = ('gru%d_gate_w', 'gru%d_gate_b', 'gru%d_cand_w', 'gru%d_cand_b', 'att%d_w1', 'att%d_b1', 'att%d_w2', 'att%d_b2',
@@ -1033,12 +1063,13 @@ class DeviceDienTrainer(DeviceSimTrainer):
     """rl4rs_dientrain handle: supervised training of the DIEN simulator on the device (same interface as DeviceSimTrainer)."""
     _prefix = 'rl4rs_dientrain_'
 
-    def __init__(self, config, weights, max_batch=256, device=None):
+    def __init__(self, config, weights, max_batch=256, device=None, head='item'):
         _lib.require_device()
         self.lib = _lib.load()
         self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
         self.config = dict(config)
         self.algo = 'dien'
+        self._set_head(head)
         self.Cn, self.Dn = int(config['category_feature_num']), int(config['dense_feature_num'])
         self.S, self.L = int(config['seq_num']), int(config['maxlen'])
         self.max_batch = int(max_batch)
@@ -1061,9 +1092,11 @@ class DeviceDienTrainer(DeviceSimTrainer):
                 getattr(w, ''.join(ch for ch in head if not ch.isdigit()) + '_' + tail)[idx] = ptr
         h = C.c_void_p()
         with torch.cuda.device(self.device):
-            check(self.lib.rl4rs_dientrain_create(C.byref(cfg), C.byref(w), self.max_batch, _stream(), C.byref(h)))
+            check(self.lib.rl4rs_dientrain_create_head(C.byref(cfg), C.byref(w), TRAIN_HEADS[self.head], self.max_batch, _stream(),
+                                                       C.byref(h)))
         self.h = h
         self.iteration = 0
+        self.n_params = self._ptrs()[2]
 
 
 class DeviceRawPolicy(object):

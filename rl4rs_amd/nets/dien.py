@@ -34,14 +34,15 @@ ATT_H1 = 64
 ATT_H2 = 16
 
 
-def dien_spec(config):
+def dien_spec(config, head='item'):
     H = config['category_hash_size']
     E = config['emb_size']
     U = config['hidden_units']
     Dn = config['dense_feature_num']
     Cn = config['category_feature_num']
     S = config['seq_num']
-    K = config['class_num']
+    from .simnets import head_width
+    K = head_width(config, head)           # 'item', 'slate' (9) or 'multiclass' (22): dien.py, dien_slate.py, dien_slate_multiclass.py
     spec = OrderedDict()
     spec['cat_emb'] = (H, E)
     spec['dense_w1'] = (Dn, U)
@@ -71,7 +72,7 @@ def dien_spec(config):
     return spec
 
 
-def init_dien_weights(config, seed=7, emb_scale=0.05, gain=1.0, bias_noise=0.0):
+def init_dien_weights(config, seed=7, emb_scale=0.05, gain=1.0, bias_noise=0.0, head='item'):
     """Seeded synthetic weights with the Keras/TF default initialisers.
 
     Dense/GRU kernels: glorot-uniform (x ``gain``); embeddings: U(-emb_scale, emb_scale); GRU gate
@@ -79,7 +80,7 @@ def init_dien_weights(config, seed=7, emb_scale=0.05, gain=1.0, bias_noise=0.0):
     """
     rs = np.random.RandomState(seed)
     out = OrderedDict()
-    for name, shape in dien_spec(config).items():
+    for name, shape in dien_spec(config, head).items():
         if name.endswith('_emb'):
             w = rs.uniform(-emb_scale, emb_scale, size=shape)
         elif name.endswith('_w3'):

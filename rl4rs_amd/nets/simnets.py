@@ -33,33 +33,60 @@ import numpy as np
 
 ALGOS = ('dnn', 'widedeep', 'lstm')
 FC_DIM = 256
+# The output layers of script/supervised_train.py's model_types (include/rl4rs_hip.h RL4RS_HEAD_*): 'item' = Dense(class_num, softmax)
+# of the four item-wise families; 'slate' = Dense(9, sigmoid) (*_slate.py); 'multiclass' = Dense(22, softmax) over the classes
+# y . SLATE_CLASS_WEIGHTS (*_slate_multiclass.py); 'adversarial' = Dense(9, sigmoid) of adversarial_slate.py, a model of its own
+# (algo 'adversarial_slate', trainer only): [mean of each sequence's embeddings | dense tower | mean of the category embeddings
+# without the last id] -> out.
+HEADS = {'item': 0, 'slate': 1, 'multiclass': 2, 'adversarial': 3}
+ADVERSARIAL = 'adversarial_slate'
+SLATE_ITEMS = 9
+SLATE_CLASSES = 22
+SLATE_CLASS_WEIGHTS = (1, 2, 4, 1, 2, 4, 1, 2, 4)
+
+
+def head_width(config, head='item'):
+    if head not in HEADS:
+        raise ValueError('head must be one of %r (got %r)' % (sorted(HEADS), head))
+    return config['class_num'] if head == 'item' else (SLATE_CLASSES if head == 'multiclass' else SLATE_ITEMS)
+
+
+def slate_class(labels):
+    """[n, 9] slate labels of 0 / 1 -> the class in [0, 21] the multiclass models train on (my_loss_fn's slate2label)"""
+    return (np.asarray(labels) != 0).astype(np.int64) @ np.asarray(SLATE_CLASS_WEIGHTS, dtype=np.int64)
 
 
 def obs_dim(config, algo):
     if algo == 'widedeep':
         return FC_DIM + config['hidden_units'] + config['category_feature_num'] * config['emb_size']
+    if algo == ADVERSARIAL:
+        return config['seq_num'] * config['emb_size'] + config['hidden_units'] + config['emb_size']
     return 256
 
 
-def simnet_spec(config, algo):
-    if algo not in ALGOS:
-        raise ValueError('algo must be one of %r (got %r)' % (ALGOS, algo))
+def simnet_spec(config, algo, head='item'):
+    if algo not in ALGOS + (ADVERSARIAL,):
+        raise ValueError('algo must be one of %r (got %r)' % (ALGOS + (ADVERSARIAL,), algo))
+    if (algo == ADVERSARIAL) != (head == 'adversarial'):
+        raise ValueError("algo %r and head %r do not go together: the adversarial model and head come as a pair" % (algo, head))
     H = config['category_hash_size']
     E = config['emb_size']
     U = config['hidden_units']
     Dn = config['dense_feature_num']
     Cn = config['category_feature_num']
     S = config['seq_num']
-    K = config['class_num']
+    K = head_width(config, head)
     spec = OrderedDict()
     spec['cat_emb'] = (H, E)
     spec['dense_w1'] = (Dn, U)
     spec['dense_b1'] = (U,)
     spec['dense_w2'] = (U, U)
     spec['dense_b2'] = (U,)
-    if algo in ('widedeep', 'lstm'):
+    if algo in ('widedeep', 'lstm', ADVERSARIAL):
         spec['seq_emb'] = (H, E)
-    if algo == 'dnn':
+    if algo == ADVERSARIAL:
+        pass
+    elif algo == 'dnn':
         spec['fc_w'] = (E + U, FC_DIM)
         spec['fc_b'] = (FC_DIM,)
         spec['obs_w'] = (FC_DIM, 256)
@@ -82,12 +109,12 @@ def simnet_spec(config, algo):
     return spec
 
 
-def init_simnet_weights(config, algo, seed=7, emb_scale=0.05, bias_noise=0.0):
+def init_simnet_weights(config, algo, seed=7, emb_scale=0.05, bias_noise=0.0, head='item'):
     """Seeded synthetic weights: glorot-uniform kernels, U(-emb_scale, emb_scale) embeddings, zero biases
     (+ optional noise so parity tests exercise every bias)."""
     rs = np.random.RandomState(seed)
     out = OrderedDict()
-    for name, shape in simnet_spec(config, algo).items():
+    for name, shape in simnet_spec(config, algo, head).items():
         if name.endswith('_emb'):
             w = rs.uniform(-emb_scale, emb_scale, size=shape)
         elif len(shape) == 2:

@@ -1,13 +1,18 @@
-"""Supervised training of the simulator from the logs, on the device (all four simulator families - dien, dnn, widedeep, lstm).
+"""Supervised training of the simulator from the logs, on the device: every ``model_type`` of the reference's
+``script/supervised_train.py`` - the four item-wise families dien, dnn, widedeep, lstm, their ``*_slate`` and
+``*_slate_multiclass`` variants and ``adversarial_slate`` - with the validation pass, the keras metrics and the early stopping of
+``supervised_train.py:38-42``.
 
-The reference builds its supervised set in ``script/data_preprocess.py:91-131``: one sample per (page record, slot j) with
+The reference builds its supervised set in ``script/data_preprocess.py:91-131``.  Item-wise: one sample per (page record, slot j) with
 ``category = user_cat(10) + [sequence_id] + exposed_items(9) + [item_j]``, ``dense = user_dense(32) + item_feature(9 x 40)
 + item_feature_j`` and ``label = user_feedback[j]`` - exactly the complete-state rows the env scores at the reward step
 (``SlateState.get_complete_states``, slate.py:117-131) when the logged slate is replayed.  So a training batch is: sample
 records (``RecDataBase``), replay ``offline_action`` through the device state machine, take the complete-state rows and the
-logged feedback.  The model, loss and optimiser are those of ``script/supervised_train.py:37-42`` with
-any ``model_type`` (``DeviceSimTrainer`` / ``rl4rs_simtrain_*`` for dnn / widedeep / lstm, ``DeviceDienTrainer`` /
-``rl4rs_dientrain_*`` for dien).
+logged feedback.  Slate-wise (``is_slate=True``, data_preprocess.py:105-115): one sample per page record, without the per-item
+tail - ``category = user_cat + [sequence_id] + exposed_items`` (20 ids) and ``dense = user_dense + item_feature`` (392 values),
+which the TFRecord reader pads with zeros to category_feature_num / dense_feature_num - and ``label = user_feedback`` (9).
+The model, loss and optimiser are those of ``script/supervised_train.py:37-42`` (``DeviceSimTrainer`` / ``rl4rs_simtrain_*`` for
+dnn / widedeep / lstm / adversarial_slate, ``DeviceDienTrainer`` / ``rl4rs_dientrain_*`` for dien).
 """
 import numpy as np
 import torch
@@ -15,28 +20,87 @@ import torch
 from . import device as D
 from collections import OrderedDict
 
+FAMILIES = ('dien', 'dnn', 'widedeep', 'lstm')
+MODEL_TYPES = FAMILIES + tuple(f + s for s in ('_slate', '_slate_multiclass') for f in FAMILIES) + ('adversarial_slate',)
+USER_DENSE = 32           # dense = user_dense(32) | page_items item vectors | the slot's item vector (device.py EnvCfg)
+
+
+def parse_model_type(model_type):
+    """one of the thirteen ``model_type`` names of script/supervised_train.py -> (algo, head)"""
+    if model_type not in MODEL_TYPES:
+        raise NotImplementedError("model_type must be one of %s (got %r)" % (', '.join(MODEL_TYPES), model_type))
+    if model_type == 'adversarial_slate':
+        return model_type, 'adversarial'
+    for suffix, head in (('_slate_multiclass', 'multiclass'), ('_slate', 'slate')):
+        if model_type.endswith(suffix):
+            return model_type[:-len(suffix)], head
+    return model_type, 'item'
+
+
+def run_epochs(epoch, epochs, patience):
+    """``model.fit(..., epochs, validation_data, callbacks=[EarlyStopping(monitor='val_loss', patience, mode='min')])``:
+    ``epoch(e)`` trains and validates one epoch -> its logs, a dict with 'loss', 'val_loss' and the metrics.  Stops after the
+    ``patience``-th consecutive epoch whose val_loss is not below the best so far (a NaN never is); like keras' default the best
+    weights are not restored.  -> keras-shaped history: {name: [one value per epoch run]}."""
+    history = OrderedDict()
+    best, wait = np.inf, 0
+    for e in range(int(epochs)):
+        logs = epoch(e)
+        for k, v in logs.items():
+            history.setdefault(k, []).append(v)
+        if logs['val_loss'] < best:
+            best, wait = logs['val_loss'], 0
+        else:
+            wait += 1
+            if wait >= patience:
+                break
+    return history
+
 
 class SimulatorTrainer(object):
-    def __init__(self, sim, weights=None, minibatch=256, seed=0, lr=1e-3, dropout_rate=0.2):
-        """sim: a ``SlateRecEnv`` (its config names the log / catalogue files and the model sizes)."""
+    def __init__(self, sim, weights=None, minibatch=256, seed=0, lr=1e-3, dropout_rate=0.2, model_type=None, trainer=None,
+                 metrics=None):
+        """sim: a ``SlateRecEnv`` (its config names the log / catalogue files and the model sizes).  model_type: one of
+        ``MODEL_TYPES`` (default: config['algo'], item-wise).  weights: the initial parameters (default: the env's own model for an
+        item-wise type of the env's family, else a seeded keras-style initialisation).  trainer / metrics: ready-made objects with
+        the interface of ``DeviceSimTrainer`` / ``metrics.ClassifierMetrics`` to use instead of creating them."""
         cfg = sim.config
-        self.algo = cfg.get('algo', 'dien')
-        if self.algo != 'dien' and self.algo not in D.SIMTRAIN_ORDER:
-            raise NotImplementedError("config['algo'] must be dien, dnn, widedeep or lstm (got %r)" % (self.algo,))
+        if model_type is None:
+            model_type = cfg.get('algo', 'dien')
+            if model_type not in FAMILIES:
+                raise NotImplementedError("config['algo'] must be dien, dnn, widedeep or lstm (got %r)" % (model_type,))
+        self.model_type = model_type
+        self.algo, self.head = parse_model_type(model_type)
+        self.P = int(cfg.get('page_items', 9))
+        if self.head != 'item' and self.P != 9:
+            raise ValueError("the slate-wise models label a page of 9 items (Dense(9) / the 22 classes of 3 x 3 slots): "
+                             "page_items = %d cannot train %s" % (self.P, model_type))
         self.sim = sim
         self.minibatch, self.seed, self.lr, self.dropout_rate = int(minibatch), int(seed), lr, dropout_rate
+        self._metrics = metrics
+        if trainer is not None:
+            self.trainer = trainer
+            return
         if weights is None:
-            weights = sim.model.weights
+            if self.head == 'item' and self.algo == cfg.get('algo', 'dien'):
+                weights = sim.model.weights
+            elif self.algo == 'dien':
+                from .nets.dien import init_dien_weights
+                weights = init_dien_weights(cfg, seed=int(cfg.get('model_seed', seed)), head=self.head)
+            else:
+                from .nets.simnets import init_simnet_weights
+                weights = init_simnet_weights(cfg, self.algo, seed=int(cfg.get('model_seed', seed)), head=self.head)
         if self.algo == 'dien':
-            self.trainer = D.DeviceDienTrainer(cfg, weights, max_batch=self.minibatch)
+            self.trainer = D.DeviceDienTrainer(cfg, weights, max_batch=self.minibatch, head=self.head)
         else:
-            self.trainer = D.DeviceSimTrainer(cfg, weights, max_batch=self.minibatch)
-        self.P = int(cfg.get('page_items', 9))
+            self.trainer = D.DeviceSimTrainer(cfg, weights, max_batch=self.minibatch, algo=self.algo, head=self.head)
 
     def dataset_from_logs(self):
-        """One cache window of the log -> (dense [B*P, Dn] f32, cat [B*P, Cn] i32, labels [B*P] i32, seqs) on the device;
-        seqs = the seq_num sequence inputs [B*P, maxlen] i32 (user history, then the constant [0] sequence of page 1,
-        data_preprocess.py:103-105)."""
+        """One cache window of the log -> (dense [n, Dn] f32, cat [n, Cn] i32, labels, seqs) on the device;
+        seqs = the seq_num sequence inputs [n, maxlen] i32 (user history, then the constant [0] sequence of page 1,
+        data_preprocess.py:103-105).  Item-wise: n = B * P samples, labels [n] i32.  Slate-wise: n = B, one sample per page record
+        (``feature_construct(is_slate=True)``): the record's first complete-state row without its per-item tail - the last
+        category id and the last item vector of dense are the reader's zero padding - and labels [n, 9] = the page's feedback."""
         data = self.sim._recData
         data.reset()
         samples = data.sample(self.sim.batch_size)
@@ -47,8 +111,18 @@ class SimulatorTrainer(object):
         env.build_complete()
         dense = env.snapshot(D.BUF_C_DENSE)
         cat = env.snapshot(D.BUF_C_CATEGORY)
-        labels = samples._feedback[:, :self.P].reshape(-1).to(torch.int32).contiguous()
-        hist = env.snapshot(D.BUF_SEQ0).repeat_interleave(self.P, dim=0).contiguous()
+        hist = env.snapshot(D.BUF_SEQ0)
+        if self.head == 'item':
+            labels = samples._feedback[:, :self.P].reshape(-1).to(torch.int32).contiguous()
+            hist = hist.repeat_interleave(self.P, dim=0).contiguous()
+        else:
+            item_w = (dense.shape[1] - USER_DENSE) // (self.P + 1)
+            dense = dense[::self.P].clone()
+            cat = cat[::self.P].clone()
+            dense[:, dense.shape[1] - item_w:] = 0
+            cat[:, -1] = 0
+            labels = samples._feedback[:, :self.P].to(torch.int32).contiguous()
+            hist = hist.contiguous()
         seqs = [hist] + [torch.zeros_like(hist) for _ in range(int(self.sim.config['seq_num']) - 1)]
         return dense, cat, labels, seqs
 
@@ -69,22 +143,89 @@ class SimulatorTrainer(object):
                                                     lr=self.lr, dropout_rate=self.dropout_rate, seed=self.seed))
         return [float(x.item()) for x in losses]
 
-    def fit_tfrecord(self, filenames, steps, seed=None):
-        """``model.fit(featureutil.read_tfrecord(files), steps_per_epoch=steps)`` of script/supervised_train.py:34-42: `steps`
-        Adam steps on shuffled batches of the reference's TFRecord training set (rl4rs_amd/utils/tfrecord.py reads it)."""
+    def _batches(self, filenames, seed):
+        """device batches (dense, cat, labels, seqs) of ``FeatureUtil.read_tfrecord`` in training mode (shuffled, endless)"""
         from .utils.datautil import FeatureUtil
         fu = FeatureUtil(dict(self.sim.config, batch_size=self.minibatch))
-        it = fu.read_tfrecord(filenames, is_pred=False, seed=self.seed if seed is None else seed)
         dev = self.trainer.device
-        losses = []
-        for _ in range(steps):
-            (seq, dense, cat, _), target = next(it)
+        slate = self.head != 'item'
+        for (seq, dense, cat, _), target in fu.read_tfrecord(filenames, is_pred=False, is_slate_label=slate, seed=seed):
             seqs = None if self.algo == 'dnn' else [torch.from_numpy(np.ascontiguousarray(seq[:, s])).to(dev)
                                                     for s in range(seq.shape[1])]
-            losses.append(self.trainer.step(torch.from_numpy(dense).to(dev), torch.from_numpy(cat).to(dev),
-                                            torch.from_numpy(target.argmax(axis=1).astype(np.int32)).to(dev), seqs, lr=self.lr,
-                                            dropout_rate=self.dropout_rate, seed=self.seed))
-        return [float(x.item()) for x in losses]
+            labels = np.asarray(target).astype(np.int32) if slate else target.argmax(axis=1).astype(np.int32)
+            yield torch.from_numpy(dense).to(dev), torch.from_numpy(cat).to(dev), torch.from_numpy(labels).to(dev), seqs
+
+    def _step(self, batch):
+        dense, cat, labels, seqs = batch
+        return self.trainer.step(dense, cat, labels, seqs, lr=self.lr, dropout_rate=self.dropout_rate, seed=self.seed)
+
+    def fit_tfrecord(self, filenames, steps, seed=None, validation_files=None, validation_steps=None, epochs=1, patience=3):
+        """``model.fit(featureutil.read_tfrecord(files), steps_per_epoch=steps)`` of script/supervised_train.py:34-42: `steps`
+        Adam steps on shuffled batches of the reference's TFRecord training set (rl4rs_amd/utils/tfrecord.py reads it); returns
+        the step losses.
+
+        With ``validation_files`` it is the whole call - ``epochs=, validation_data=read_tfrecord(validation_files),
+        validation_steps=, callbacks=[EarlyStopping(monitor='val_loss', patience=patience)]`` - and returns the keras-shaped history
+        (``run_epochs``): 'loss' (mean step loss of the epoch), 'val_loss', and by model type 'val_auc', 'val_precision',
+        'val_recall' (item-wise and sigmoid-output types), 'val_acc' (item-wise: binary accuracy; multiclass: categorical accuracy),
+        'val_no_click_score' (adversarial_slate: the mean of its ``my_metrics``, sum_j score_j (1 - y_j)).  An epoch is ``steps``
+        Adam steps, then ``validation_steps`` inference batches (``evaluate``: no dropout) into a ``ClassifierMetrics``; the host
+        reads the device once per epoch, after the validation pass."""
+        seed = self.seed if seed is None else seed
+        train = self._batches(filenames, seed)
+        if validation_files is None:
+            if validation_steps is not None or epochs != 1:
+                raise ValueError('validation_steps / epochs need validation_files')
+            return [float(x.item()) for x in [self._step(next(train)) for _ in range(steps)]]
+        if not validation_steps or validation_steps < 1:
+            raise ValueError('validation_files needs validation_steps >= 1')
+        val = self._batches(validation_files, seed + 1)
+
+        def epoch(_):
+            losses = [self._step(next(train)).reshape(()) for _ in range(steps)]
+            return self.validate(val, validation_steps, train_loss=torch.stack(losses).mean())
+
+        return run_epochs(epoch, epochs, patience)
+
+    def validate(self, batches, steps, train_loss=None):
+        """``steps`` inference batches from the iterator ``batches`` (``_batches``) -> OrderedDict of 'val_loss' and the model
+        type's metrics.  train_loss: a device scalar that comes back in the same read, as 'loss'."""
+        if self._metrics is None:
+            from .metrics import ClassifierMetrics
+            self._metrics = ClassifierMetrics(device=self.trainer.device)
+        m = self._metrics
+        m.reset()
+        dev = self.trainer.device
+        acc = torch.zeros(3, dtype=torch.float64, device=dev)             # sum of batch losses, sum of no-click scores, rows
+        for _ in range(int(steps)):
+            dense, cat, labels, seqs = next(batches)
+            pred, rows = self.trainer.evaluate(dense, cat, labels, seqs)
+            acc[0] += rows.double().mean()
+            if self.head == 'item':
+                m.update_binary(pred, torch.nn.functional.one_hot(labels.long(), pred.shape[1]))
+            elif self.head == 'multiclass':
+                w = torch.tensor([1, 2, 4, 1, 2, 4, 1, 2, 4], dtype=torch.int64, device=dev)
+                m.update_multiclass(pred, ((labels != 0).long() * w).sum(dim=1))
+            else:
+                m.update_binary(pred, labels)
+            if self.head == 'adversarial':
+                acc[1] += (pred.double() * (1.0 - (labels != 0).double())).sum()
+                acc[2] += pred.shape[0]
+        r = m.result()                                                    # the epoch's host read
+        host = torch.cat([acc, torch.zeros(1, dtype=torch.float64, device=dev) if train_loss is None else train_loss.double().reshape(1)]).cpu()
+        logs = OrderedDict()
+        if train_loss is not None:
+            logs['loss'] = float(host[3])
+        logs['val_loss'] = float(host[0]) / int(steps)
+        if self.head != 'multiclass':
+            logs['val_auc'], logs['val_precision'], logs['val_recall'] = r['auc'], r['precision'], r['recall']
+        if self.head == 'item':
+            logs['val_acc'] = r['acc']
+        elif self.head == 'multiclass':
+            logs['val_acc'] = r['categorical_acc']
+        elif self.head == 'adversarial':
+            logs['val_no_click_score'] = float(host[1]) / max(float(host[2]), 1.0)
+        return logs
 
     def export_weights(self):
         """Trained parameters as numpy arrays (``rl4rs_amd.nets.simnets.simnet_spec`` names) - what ``model_file`` takes."""
@@ -92,16 +233,24 @@ class SimulatorTrainer(object):
 
     def save(self, model_file):
         """``saver.save(sess, model_file)`` (supervised_train.py:44-46): an ``.npz`` of this package's weight names, or -
-        any other path - a TF checkpoint prefix under the reference's graph variable names (``utils.tfckpt``)."""
+        any other path - a TF checkpoint prefix under the reference's graph variable names (``utils.tfckpt``): a ``*_slate`` /
+        ``*_slate_multiclass`` model under those of its item-wise family (the same layers in the same creation order).
+        ``adversarial_slate`` has no such table: ``.npz`` only."""
+        if not str(model_file).endswith('.npz') and self.algo == 'adversarial_slate':
+            raise NotImplementedError("adversarial_slate saves as .npz only: there is no table of its graph's variable names "
+                                      "(got %r)" % (model_file,))
         w = self.export_weights()
         if str(model_file).endswith('.npz'):
             np.savez(model_file, **w)
         else:
             from .utils import tfckpt
-            tfckpt.save_simulator_weights(model_file, w, self.sim.config, self.algo)
+            tfckpt.save_simulator_weights(model_file, w, self.sim.config, self.algo, self.head)
 
     def install(self):
-        """Put the trained weights into the simulator the env scores with."""
+        """Put the trained weights into the simulator the env scores with (item-wise types only: the env scores single items)."""
+        if self.head != 'item':
+            raise NotImplementedError("%s is a slate-wise model: the env scores one item per row with the item-wise families, "
+                                      "so there is nothing to install it into" % self.model_type)
         self.sim.model.weights = OrderedDict((k, np.ascontiguousarray(v, dtype=np.float32))
                                                      for k, v in self.export_weights().items())
         if self.sim.model.device_net is not None:

@@ -476,12 +476,12 @@ def variable_names(config, algo='dien'):
 _OPTIMIZER_SLOT = re.compile(r'Adam|beta\d_power|training/|/(m|v)$')
 
 
-def _spec(config, algo):
+def _spec(config, algo, head='item'):
     if algo == 'dien':
         from ..nets import dien
-        return dien.dien_spec(config)
+        return dien.dien_spec(config, head)
     from ..nets import simnets
-    return simnets.simnet_spec(config, algo)
+    return simnets.simnet_spec(config, algo, head)
 
 
 def load_simulator_weights(model_file, config, algo='dien', name_map=None, verify=True):
@@ -523,12 +523,14 @@ def load_simulator_weights(model_file, config, algo='dien', name_map=None, verif
     return out
 
 
-def save_simulator_weights(prefix, weights, config, algo='dien'):
+def save_simulator_weights(prefix, weights, config, algo='dien', head='item'):
     """Write weights (this package's names) as a checkpoint under the reference's graph variable names - the
     counterpart of ``saver.save(sess, model_file)`` (supervised_train.py:44-46) for the model variables.  Variables
     of the reference's graph that carry no model state (the unconnected embedding of dnn.py, metric accumulators of
-    ``model.compile``) are written as zeros where their shape is known and otherwise left out."""
-    spec = _spec(config, algo)
+    ``model.compile``) are written as zeros where their shape is known and otherwise left out.
+    ``head``: 'slate' / 'multiclass' for the *_slate.py / *_slate_multiclass.py models - the graph of the item-wise family with a
+    9- / 22-wide 'simulator_reward' layer (same layer creation order, so the same variable names)."""
+    spec = _spec(config, algo, head)
     out = {}
     for var, w in variable_names(config, algo).items():
         if w is None:

@@ -1,0 +1,110 @@
+"""The streaming metrics handle rl4rs_clfmetrics_* against the numpy restatement of the keras definitions (rl4rs_amd/metrics.py,
+checked on its own in tests/test_clfmetrics_host.py): the int64 counts are compared EXACTLY."""
+import numpy as np
+import pytest
+
+from rl4rs_amd import metrics as M
+
+pytestmark = pytest.mark.gpu
+
+T = 200
+
+
+def _edge_predictions(n, seed):
+    """0, 1, 0.5, float32(k / 199) for several k, the float32 neighbours of each, NaN, values outside [0, 1]; then uniform noise"""
+    rs = np.random.RandomState(seed)
+    base = np.asarray([0.0, 1.0, 0.5] + [k / 199.0 for k in (1, 2, 50, 99, 100, 101, 150, 197, 198)], dtype=np.float32)
+    edge = np.concatenate([base, np.nextafter(base, np.float32(2)), np.nextafter(base, np.float32(-1)),
+                           np.asarray([np.nan, -0.25, 1.5, -1e-7, 1.0 + 1e-7], dtype=np.float32)]).astype(np.float32)
+    pred = rs.rand(n).astype(np.float32)
+    k = min(n, len(edge))
+    pred[:k] = rs.permutation(edge)[:k] if n < len(edge) else edge
+    label = rs.randint(0, 2, size=n).astype(np.int32)
+    return pred, label
+
+
+def _dev(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+@pytest.fixture(scope='module')
+def handle():
+    m = M.ClassifierMetrics(T)
+    yield m
+    m.close()
+
+
+@pytest.mark.parametrize('n', [1, 255, 256, 257, 4099])
+def test_binary_counts_are_exact(handle, n):
+    pred, label = _edge_predictions(n, n)
+    if n >= 255:
+        assert np.isnan(pred).any() and (pred == np.float32(0.5)).any()
+    handle.reset()
+    handle.update_binary(_dev(pred), _dev(label))
+    got = handle.counts()
+    ref = M.confusion_counts(pred, label, handle.thresholds)
+    assert got.dtype == np.int64 and np.array_equal(got, ref)
+    assert (got[:T] + got[3 * T:4 * T] == int(label.sum())).all()          # TP + FN = positives at every threshold
+    assert handle.result() == M.metrics_from_counts(ref, T)
+
+
+def test_two_updates_equal_one_of_the_concatenation_and_reset(handle):
+    p1, y1 = _edge_predictions(257, 1)
+    p2, y2 = _edge_predictions(4099, 2)
+    handle.reset()
+    handle.update_binary(_dev(p1), _dev(y1))
+    handle.update_binary(_dev(p2.reshape(-1, 1)), _dev(y2.reshape(-1, 1)))
+    two = handle.counts()
+    handle.reset()
+    assert not handle.counts().any()
+    handle.update_binary(_dev(np.concatenate([p1, p2])), _dev(np.concatenate([y1, y2])))
+    one = handle.counts()
+    assert np.array_equal(one, two)
+    assert np.array_equal(one, M.confusion_counts(np.concatenate([p1, p2]), np.concatenate([y1, y2]), handle.thresholds))
+    handle.reset()
+    handle.update_binary(_dev(np.concatenate([p1, p2])), _dev(np.concatenate([y1, y2])))
+    assert np.array_equal(handle.counts(), one)                               # the same from run to run
+
+
+def test_all_negative_labels_give_auc_zero(handle):
+    pred, label = _edge_predictions(257, 5)
+    handle.reset()
+    handle.update_binary(_dev(pred), _dev(np.zeros_like(label)))
+    r = handle.result()
+    assert r['auc'] == 0.0 and r['recall'] == 0.0
+    assert np.array_equal(handle.counts(), M.confusion_counts(pred, np.zeros_like(label), handle.thresholds))
+
+
+def test_other_threshold_counts():
+    for t in (2, 3, 1000):
+        m = M.ClassifierMetrics(t)
+        pred, label = _edge_predictions(257, t)
+        m.update_binary(_dev(pred), _dev(label))
+        assert np.array_equal(m.counts(), M.confusion_counts(pred, label, m.thresholds)), t
+        m.close()
+
+
+@pytest.mark.parametrize('K', [22, 3])
+@pytest.mark.parametrize('N', [1, 257])
+def test_multiclass_takes_the_first_maximum(handle, N, K):
+    rs = np.random.RandomState(N + K)
+    pred = rs.rand(N, K).astype(np.float32)
+    pred[::3] = np.round(pred[::3] * 2) / 2            # many ties: values in {0, 0.5, 1}
+    pred[0] = 0.25                                     # every class tied: class 0 wins
+    label = rs.randint(0, K, size=N).astype(np.int32)
+    label[::2] = np.argmax(pred[::2], axis=1)
+    label[0] = 0
+    handle.reset()
+    handle.update_multiclass(_dev(pred), _dev(label))
+    got = handle.counts()
+    assert got[4 * T + 4:].tolist() == list(M.categorical_counts(pred, label))
+    assert not got[:4 * T + 4].any()
+    # the last of several tied maxima is NOT a hit
+    tied = np.zeros((N, K), dtype=np.float32)
+    handle.reset()
+    handle.update_multiclass(_dev(tied), _dev(np.full(N, K - 1, dtype=np.int32)))
+    assert handle.counts()[4 * T + 4:].tolist() == [0, N]
+    handle.update_multiclass(_dev(tied), _dev(np.zeros(N, dtype=np.int32)))
+    assert handle.counts()[4 * T + 4:].tolist() == [N, 2 * N]
+    assert handle.result()['categorical_acc'] == 0.5
