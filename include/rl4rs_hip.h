@@ -377,6 +377,29 @@ int rl4rs_dien_forward(rl4rs_dien* net, int32_t R, int32_t group, const float* d
  * values are the head's own rows: bit-identical to a group-1 forward of that row.  NULL disarms. */
 int rl4rs_dien_set_obs_last(rl4rs_dien* net, float* obs_last_dev);
 
+/* The NEXT rl4rs_dien_forward of this handle (one call, as with rl4rs_dien_set_obs_last) takes the duplicate row groups of its
+ * input from the caller instead of looking for them: it launches no k_row_dedup and hands the three buffers to everything that
+ * reads the handle's own partition otherwise (k_din_x / k_din_xq, k_augru_x / k_augru_xs, the mapped GEMMs, the category kernels,
+ * k_row_expand).  int32 device memory the caller owns and keeps unchanged until the forward has run:
+ *   rep_dev      [n_groups]  representative of every row group; rep[g] == g: g is one
+ *   active_dev   [n_active]  the representatives in processing order (rl4rs_dien_set_row_order; none: ascending)
+ *   n_active_dev [1]         their number
+ * That forward must have R / group == n_groups and the row dedup on (and not the dup_store form): anything else is an error.
+ * The caller's contract, which the scorer does NOT check:
+ *   - rep[rep[g]] == rep[g] for every g;
+ *   - active lists exactly the groups with rep[g] == g, in processing order;
+ *   - the rows of g and of rep[g] (category ids and dense values, `group` rows each) are bitwise equal and their cache slots are
+ *     equal for every sequence input.
+ * Under it the forward's outputs are bit-identical to those of a forward that compares the rows itself; a partition that merges
+ * rows which differ gives the duplicates the representative's results.  rep_dev == NULL disarms.  rl4rs_env_step_* carry the
+ * partition of the env batch from step to step this way (rl4rs_stepper_set_partition_carry). */
+int rl4rs_dien_set_row_partition(rl4rs_dien* net, const int32_t* rep_dev, const int32_t* active_dev, const int32_t* n_active_dev,
+                                 int32_t n_groups);
+/* Forwards since the last rl4rs_dien_profile_reset that launched k_row_dedup / that took a caller's partition instead (host
+ * counters, kept whether profiling is on or not; the profile class of k_row_dedup keeps one empty entry for a launch not issued,
+ * so that its counts stay comparable between handles). */
+int rl4rs_dien_dedup_counts(rl4rs_dien* net, int64_t* launched, int64_t* carried);
+
 /* softmax(obs @ out_w + out_b)[:, 1] of already computed 'simulator_obs' activations (dien.py:36):
  * obs_dev [R, 256] -> prob_dev [R]. */
 int rl4rs_dien_head_prob(rl4rs_dien* net, int32_t R, const float* obs_dev, float* prob_dev, void* stream);
@@ -391,8 +414,11 @@ enum {
     RL4RS_DIEN_H1 = 3,            /* float32 [seq_num, max_slots, maxlen, E] first-GRU states */
     RL4RS_DIEN_N_ACTIVE = 4,      /* int32 [1] row groups k_din_x / k_augru_x scored in the last forward (row dedup; an error
                                      on a handle where it is off) */
-    RL4RS_DIEN_ROW_REP = 5        /* int32 [max_rows] representative group of every row group of the last forward, first
+    RL4RS_DIEN_ROW_REP = 5,       /* int32 [max_rows] representative group of every row group of the last forward, first
                                      R / group entries (rep[g] == g: scored itself) */
+    RL4RS_DIEN_ROW_ACTIVE = 6     /* int32 [max_rows] the representatives of the last forward in processing order, first
+                                     N_ACTIVE entries.  After a forward that took its partition from the caller
+                                     (rl4rs_dien_set_row_partition) the three ids give the caller's buffers, n_bytes = 4 n_groups */
 };
 int rl4rs_dien_buffer(rl4rs_dien* net, int which, void** dev_ptr, int64_t* n_bytes);
 
@@ -522,6 +548,15 @@ int rl4rs_stepper_set_act_tail(rl4rs_stepper* s, int32_t on);
  * as it was; bit-identical outputs either way.  rl4rs_env_step_record* keep the two-forward order. */
 int rl4rs_stepper_set_obs_fold(rl4rs_stepper* s, int32_t on);
 int rl4rs_stepper_set_distinct_hint(rl4rs_stepper* s, int32_t n_distinct);
+/* With the DIEN scorer and its row dedup on, rl4rs_env_step_* carry the duplicate-row partition of the env batch from one forward
+ * of an episode to the next instead of letting every forward compare whole rows: two envs whose state rows were equal are equal
+ * now iff they have just taken the same (resolved) action, so the act kernel refines the partition by one integer per env and the
+ * forwards of the transition take it through rl4rs_dien_set_row_partition.  Seeded by the scorer's last content dedup when that
+ * ran on exactly the env's current state rows (the reset observation forward); dropped - the next forward compares rows again -
+ * by a reset, by any other call that writes the env's rows, by the first act of a SeqSlate page (the slot table changes) and by
+ * a changed row order.  The slot table and the row order must not be rewritten in place between two steps of an episode.
+ * Outputs are bit-identical either way.  rl4rs_stepper_set_partition_carry(s, 0): every forward launches k_row_dedup as before. */
+int rl4rs_stepper_set_partition_carry(rl4rs_stepper* s, int32_t on);
 /* Click probabilities of the complete-state rows of the LAST reward step, slate order: out_dev [B, n_complete] f32 - the same
  * numbers in either order of the forwards (the record form's click_p part, for rl4rs_env_step_discrete / _conti). */
 int rl4rs_stepper_click_probs(rl4rs_stepper* s, float* out_dev, void* stream);

@@ -270,6 +270,8 @@ SIGNATURES = {
     'rl4rs_policy_ppo_epoch': (_I, [_P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P] + [C.c_float] * 10 + [_P, _P, _P]),
     'rl4rs_dien_set_row_order': (_I, [_P, _P, _I32]),
     'rl4rs_dien_set_obs_last': (_I, [_P, _P]),
+    'rl4rs_dien_set_row_partition': (_I, [_P, _P, _P, _P, _I32]),
+    'rl4rs_dien_dedup_counts': (_I, [_P, C.POINTER(_I64), C.POINTER(_I64)]),
     'rl4rs_dien_set_augru_rows': (_I, [_P, _I32]),
     'rl4rs_dien_set_distinct_hint': (_I, [_P, _I32]),
     'rl4rs_dien_status_word': (_I, [_P, C.POINTER(_P)]),
@@ -286,6 +288,7 @@ SIGNATURES = {
     'rl4rs_stepper_destroy': (_I, [_P]),
     'rl4rs_stepper_set_act_tail': (_I, [_P, _I32]),
     'rl4rs_stepper_set_obs_fold': (_I, [_P, _I32]),
+    'rl4rs_stepper_set_partition_carry': (_I, [_P, _I32]),
     'rl4rs_stepper_set_distinct_hint': (_I, [_P, _I32]),
     'rl4rs_stepper_click_probs': (_I, [_P, _P, _P]),
     'rl4rs_stepper_reward_rows': (_I, [_P]),

@@ -142,8 +142,26 @@ struct ActTail {
     double* zero_reward;                 // zero_reward[b] = 0.0: the reward of a step on which none is due
     int32_t* next_action; int next_cur;  // next_action[b] = the logged item id of step next_cur (the rule of rl4rs_env_offline_action)
 };
-// rl4rs_env_act_discrete with that tail (defined in env.hip)
-int env_act_discrete_tail(rl4rs_env* e, const int32_t* actions, const ActTail& tail, void* stream);
+// rl4rs_env_act_discrete with that tail (defined in env.hip).  rf != NULL: the act also carries the duplicate-row partition of the
+// batch over to the rows it builds (row_refine.hpp; the key of an env is its resolved action id) - env_refine_fits: that launch's LDS fits
+struct RowRefineArgs;
+int env_act_discrete_tail(rl4rs_env* e, const int32_t* actions, const ActTail& tail, void* stream, const RowRefineArgs* rf = nullptr);
+int env_act_conti_refine(rl4rs_env* e, const void* actions, int is_f64, int32_t* chosen, void* stream, const RowRefineArgs* rf);
+bool env_refine_fits(const rl4rs_env* e);
+// Process-wide order of the calls that write an env's state rows (or the data they are built from) and of the scorer forwards that
+// looked for duplicate rows: a forward's partition describes an env's rows iff its stamp is the later one (step.hip)
+uint64_t next_stamp();
+uint64_t env_rows_stamp(const rl4rs_env* e);
+// What the last content dedup (k_row_dedup) of a scorer handle ran on, and where it left the partition
+struct DienPartition {
+    uint64_t stamp;                      // 0 = none
+    int n_groups, group;
+    const float* dense; const int32_t* cat; const int32_t* slots; const int32_t* order;
+    const int32_t* rep; const int32_t* active; const int32_t* n_active;
+};
+void dien_last_partition(const rl4rs_dien* n, DienPartition* out);
+bool dien_takes_partition(const rl4rs_dien* n);                          // row dedup on, in a form rl4rs_dien_set_row_partition serves
+const int32_t* dien_row_order(const rl4rs_dien* n, int n_groups);         // the order a forward of n_groups groups would process them in
 
 // The NEXT rl4rs_dien_forward's observation also goes to `host_visible` (device-visible pinned host memory, [R, 256] floats) from
 // the head GEMM's epilogue - step.hip's reference-shaped records (dien.hip); dien_obs_mirror_used: did that forward take it?

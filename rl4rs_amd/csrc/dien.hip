@@ -1517,6 +1517,7 @@ __global__ __launch_bounds__(256) void k_din_scores(DinArgs a) {
 #endif
 #include "din_x.hpp"
 #include "row_dedup.hpp"
+#include "row_refine.hpp"
 namespace rl4rs {
 
 // softmax(obs @ out_w + out_b)[:, 1]  (dien.py:36, slate.py:298).  One wave per row.
@@ -1641,6 +1642,12 @@ struct rl4rs_dien {
     int32_t* dd_rep;       // [max_rows] representative of every row group of the last forward
     int32_t* dd_active;    // [max_rows] the representatives in processing order
     int32_t* dd_nact;      // [0] their number, [1] k_row_dedup's workgroup ticket
+    // rl4rs_dien_set_row_partition: the caller's partition for the NEXT forward (one call), which then launches no k_row_dedup
+    const int32_t* part_rep; const int32_t* part_active; const int32_t* part_nact; int part_groups;
+    // the partition the last forward worked on (rl4rs_dien_buffer): dd_* or a caller's buffers of last_groups entries
+    const int32_t* last_rep; const int32_t* last_active; const int32_t* last_nact; int last_groups;
+    DienPartition dd_info; // what the last k_row_dedup ran on (step.hip adopts its partition)
+    int64_t dedup_launched, dedup_carried;      // forwards that launched k_row_dedup / took a caller's partition (rl4rs_dien_dedup_counts)
     float* augru_wg[4];    // packed [2*NH2/32][NH2/8][64][4]
     float* augru_wc[4];
     // caches
@@ -2032,6 +2039,12 @@ int rl4rs_dien_create(const rl4rs_dien_cfg* c, const rl4rs_dien_weights* w, void
     // row dedup: only where both kernels that read the active list are the selected ones
     n->row_dedup = !(opts & RL4RS_DIEN_OPT_NO_ROW_DEDUP) && n->fp16x2 && n->augru_x && n->din16 && n->h1f[0] != nullptr;
     n->dd_rep = n->dd_active = n->dd_nact = nullptr;
+    n->part_rep = n->part_active = n->part_nact = nullptr;
+    n->part_groups = 0;
+    n->last_rep = n->last_active = n->last_nact = nullptr;
+    n->last_groups = 0;
+    memset(&n->dd_info, 0, sizeof(n->dd_info));
+    n->dedup_launched = n->dedup_carried = 0;
     n->dd_dstart = n->dd_dlist = n->dd_dcur = nullptr;
     n->dup_store = n->row_dedup && (opts & RL4RS_DIEN_OPT_DUP_STORE) != 0;
     n->tier2_rows = n->row_dedup && !(opts & RL4RS_DIEN_OPT_NO_TIER2_ROWS);
@@ -2214,7 +2227,14 @@ int rl4rs_dien_forward(rl4rs_dien* n, int32_t R, int32_t group, const float* den
     const int ngroups = R / group;
     int rc;
     n->obs_mirror_used = false;
-    struct MirrorOnce { rl4rs_dien* n; ~MirrorOnce() { n->obs_mirror = nullptr; n->obs_last = nullptr; } } mirror_once{n};       // one forward only
+    struct MirrorOnce { rl4rs_dien* n; ~MirrorOnce() { n->obs_mirror = nullptr; n->obs_last = nullptr; n->part_rep = nullptr; } } mirror_once{n};       // one forward only
+    // rl4rs_dien_set_row_partition: the duplicate row groups of this forward are the caller's, nothing is compared
+    const bool carried = n->part_rep != nullptr;
+    RL4RS_REQUIRE(!carried || (n->row_dedup && !n->dup_store && n->part_groups == ngroups),
+                  "dien_forward: the row partition set for this forward is for %d groups with the row dedup on (forward: %d groups)", n->part_groups, ngroups);
+    const int32_t* const p_rep = carried ? n->part_rep : n->dd_rep;
+    const int32_t* const p_active = carried ? n->part_active : n->dd_active;
+    const int32_t* const p_nact = carried ? n->part_nact : n->dd_nact;
     RL4RS_REQUIRE(!n->obs_last || prob, "dien_forward: rl4rs_dien_set_obs_last needs a forward that returns probabilities");
     // Second tier on the active rows only: with the row dedup on, the category kernel, the dense tower, the q-side term
     // and the head GEMM take the active list too and k_row_expand, behind the head GEMM, gives a duplicate everything it lacks.
@@ -2232,9 +2252,9 @@ int rl4rs_dien_forward(rl4rs_dien* n, int32_t R, int32_t group, const float* den
                         n->din_x && n->din_rows_auto && n->gemm_group && !augru_rows64(n, R, group) && n->augru_rows != 64 &&
                         dien_gemm_grouped(n) && (int64_t)((hint_groups + 31) / 32) * (S + 1) <= n->n_cu &&
                         g16_shadow_fits(R, n->Dn, F, U);
-    const G16RowMap rmap = {n->dd_active, n->dd_nact, group};
+    const G16RowMap rmap = {p_active, p_nact, group};
     const G16RowMap* const map2 = tier2 ? &rmap : nullptr;
-    const int32_t* const t2_order = tier2 ? n->dd_active : nullptr;
+    const int32_t* const t2_order = tier2 ? p_active : nullptr;
     auto dense_tower = [&](hipStream_t s2) -> int {
         int r2;
         if (n->gemm16 && n->dense_chain && U <= 128 && U % 16 == 0) {      // both layers in one launch, the hidden tile stays in LDS
@@ -2265,6 +2285,12 @@ int rl4rs_dien_forward(rl4rs_dien* n, int32_t R, int32_t group, const float* den
     const int32_t* order_in = (n->row_order && n->row_order_n == ngroups) ? n->row_order : nullptr;
     const bool dedup = n->row_dedup;
     if (dedup) {
+        n->last_rep = p_rep; n->last_active = p_active; n->last_nact = p_nact; n->last_groups = carried ? ngroups : n->c.max_rows;
+    }
+    if (carried) {
+        { Prof p(n, KID_DEDUP, st); }       // the class keeps one (empty) entry for the launch it did not issue
+        n->dedup_carried += 1;
+    } else if (dedup) {
         Prof p(n, KID_DEDUP, st);
         RowDedupArgs a;
         memset(&a, 0, sizeof(a));
@@ -2275,6 +2301,8 @@ int rl4rs_dien_forward(rl4rs_dien* n, int32_t R, int32_t group, const float* den
         constexpr int per_wg = ROW_DEDUP_THREADS / 64;
         hipLaunchKernelGGL(k_row_dedup, dim3((ngroups + per_wg - 1) / per_wg), dim3(ROW_DEDUP_THREADS), 0, st, a);
         RL4RS_LAUNCH_CHECK();
+        n->dedup_launched += 1;
+        n->dd_info = DienPartition{next_stamp(), ngroups, group, dense, cat, slots, order_in, n->dd_rep, n->dd_active, n->dd_nact};
     }
     n->last_shadow = shadow;
     if (shadow) {
@@ -2289,20 +2317,20 @@ int rl4rs_dien_forward(rl4rs_dien* n, int32_t R, int32_t group, const float* den
             const size_t smem = cat_attn2g_smem(group, Cn);
             if (group == 8)
                 hipLaunchKernelGGL((k_cat_attn2g<8, 8>), dim3(ngroups), dim3(512), smem, st, cat, Cn, n->H, n->cat_emb, n->seq_emb, n->allf, F,
-                                   off_c, n->q, n->ptab ? 0 : 1, (n->fp16x2 && n->cat16) ? 1 : 0, n->ptab, n->obs_b, n->tsum, t2_order, n->dd_nact);
+                                   off_c, n->q, n->ptab ? 0 : 1, (n->fp16x2 && n->cat16) ? 1 : 0, n->ptab, n->obs_b, n->tsum, t2_order, p_nact);
             else
                 hipLaunchKernelGGL((k_cat_attn2g<9, RL4RS_CAT9_WAVES>), dim3(ngroups), dim3(64 * RL4RS_CAT9_WAVES), smem, st, cat, Cn, n->H, n->cat_emb, n->seq_emb, n->allf, F,
-                                   off_c, n->q, n->ptab ? 0 : 1, (n->fp16x2 && n->cat16) ? 1 : 0, n->ptab, n->obs_b, n->tsum, t2_order, n->dd_nact);
+                                   off_c, n->q, n->ptab ? 0 : 1, (n->fp16x2 && n->cat16) ? 1 : 0, n->ptab, n->obs_b, n->tsum, t2_order, p_nact);
         } else if (n->cat_v2 && E == 128 && Cn <= 24) {
             size_t smem = (size_t)4 * (Cn * (64 + 4) + 32) * 4;
             if (Cn == 21)
                 hipLaunchKernelGGL((k_cat_attn2<21, true>), dim3((R + 3) / 4), dim3(256), smem, st, cat, R, Cn, n->H, n->cat_emb,
                                    n->seq_emb, n->allf, F, off_c, n->q, n->ptab ? 0 : 1, (n->fp16x2 && n->cat16) ? 1 : 0,
-                                   n->ptab, n->obs_b, n->tsum, t2_order, n->dd_nact, group);
+                                   n->ptab, n->obs_b, n->tsum, t2_order, p_nact, group);
             else
                 hipLaunchKernelGGL((k_cat_attn2<24, false>), dim3((R + 3) / 4), dim3(256), smem, st, cat, R, Cn, n->H, n->cat_emb,
                                    n->seq_emb, n->allf, F, off_c, n->q, n->ptab ? 0 : 1, (n->fp16x2 && n->cat16) ? 1 : 0,
-                                   n->ptab, n->obs_b, n->tsum, t2_order, n->dd_nact, group);
+                                   n->ptab, n->obs_b, n->tsum, t2_order, p_nact, group);
         } else {
             size_t smem = (size_t)4 * (Cn * (E + 4) + 32) * 4;
             hipLaunchKernelGGL(k_cat_attn, dim3((R + 3) / 4), dim3(256), smem, st, cat, R, Cn, E, n->H, n->cat_emb,
@@ -2347,7 +2375,7 @@ int rl4rs_dien_forward(rl4rs_dien* n, int32_t R, int32_t group, const float* den
         }
         a.scores = n->scores; a.scores_stride = (int64_t)n->c.max_rows * L;
         a.order = order_in;
-        if (dedup && h16 && n->h1f[0]) { a.order = n->dd_active; a.n_active = n->dd_nact; }
+        if (dedup && h16 && n->h1f[0]) { a.order = p_active; a.n_active = p_nact; }
         if (dedup && n->dup_store) { a.dup_start = n->dd_dstart; a.dup_list = n->dd_dlist; }
         for (int s = 0; s < S; ++s) a.lead[s] = n->lead[s];
         a.pad_slot = n->c.max_slots;
@@ -2412,7 +2440,7 @@ int rl4rs_dien_forward(rl4rs_dien* n, int32_t R, int32_t group, const float* den
                     a.k_c[s][t] = 2.8853900817779268f / n->augru_s[s][2][t];
                 }
             a.order = n->augru_x ? order_in : nullptr;
-            if (dedup) { a.order = n->dd_active; a.n_active = n->dd_nact; }
+            if (dedup) { a.order = p_active; a.n_active = p_nact; }
             if (dedup && n->dup_store && n->augru_x) { a.dup_start = n->dd_dstart; a.dup_list = n->dd_dlist; }
             a.steps = 0;
 #if defined(RL4RS_H16_TRACE) || defined(RL4RS_X_TRACE)
@@ -2468,7 +2496,7 @@ int rl4rs_dien_forward(rl4rs_dien* n, int32_t R, int32_t group, const float* den
         RowExpandArgs a;
         memset(&a, 0, sizeof(a));
         a.R = R; a.group = group; a.n_groups = ngroups; a.S = S; a.L = L; a.ncol = tier2 ? S * NH2 + U + E : S * NH2;
-        a.rep = n->dd_rep; a.n_active = n->dd_nact;
+        a.rep = p_rep; a.n_active = p_nact;
         a.allf = n->allf; a.ld = F; a.scores = n->scores; a.scores_stride = (int64_t)n->c.max_rows * L;
         if (tier2) { a.q = n->q; a.E = E; a.obs = obs_out; a.obs_dim = OBS_DIM; }
         hipLaunchKernelGGL(k_row_expand, dim3((R + 3) / 4), dim3(256), 0, st, a);
@@ -2527,10 +2555,15 @@ int rl4rs_dien_buffer(rl4rs_dien* n, int which, void** p, int64_t* bytes) {
         case RL4RS_DIEN_H1: ptr = n->h1[0]; b = (int64_t)n->c.max_slots * n->L * n->E * 4; break;
         case RL4RS_DIEN_N_ACTIVE:
         case RL4RS_DIEN_ROW_REP:
+        case RL4RS_DIEN_ROW_ACTIVE: {
             if (!n->row_dedup) { set_error("dien_buffer: row dedup is off on this handle"); return RL4RS_EINVAL; }
-            if (which == RL4RS_DIEN_N_ACTIVE) { ptr = n->dd_nact; b = 4; }
-            else { ptr = n->dd_rep; b = (int64_t)n->c.max_rows * 4; }
+            // the partition of the LAST forward: the handle's own, or the buffers its caller handed in (rl4rs_dien_set_row_partition)
+            const int64_t groups = n->last_rep ? n->last_groups : n->c.max_rows;
+            if (which == RL4RS_DIEN_N_ACTIVE) { ptr = const_cast<int32_t*>(n->last_rep ? n->last_nact : n->dd_nact); b = 4; }
+            else if (which == RL4RS_DIEN_ROW_REP) { ptr = const_cast<int32_t*>(n->last_rep ? n->last_rep : n->dd_rep); b = groups * 4; }
+            else { ptr = const_cast<int32_t*>(n->last_rep ? n->last_active : n->dd_active); b = groups * 4; }
             break;
+        }
         default: set_error("dien_buffer: unknown buffer id %d", which); return RL4RS_EINVAL;
     }
     *p = ptr;
@@ -2567,6 +2600,16 @@ int rl4rs_dien_set_distinct_hint(rl4rs_dien* n, int32_t n_groups) {
     return RL4RS_OK;
 }
 
+static_assert(rl4rs::ROW_REFINE_CAP == rl4rs::ROW_DEDUP_CAP, "the carried partition's search window is k_row_dedup's");
+int rl4rs_dien_set_row_partition(rl4rs_dien* n, const int32_t* rep_dev, const int32_t* active_dev, const int32_t* n_active_dev, int32_t n_groups) {
+    RL4RS_REQUIRE(n, "dien_set_row_partition: null handle");
+    if (!rep_dev) { n->part_rep = nullptr; return RL4RS_OK; }      // disarm
+    RL4RS_REQUIRE(active_dev && n_active_dev && n_groups > 0 && n_groups <= n->c.max_rows, "dien_set_row_partition: bad argument");
+    RL4RS_REQUIRE(n->row_dedup && !n->dup_store, "dien_set_row_partition: this handle's forward does not take a partition (row dedup off, or dup_store)");
+    n->part_rep = rep_dev; n->part_active = active_dev; n->part_nact = n_active_dev; n->part_groups = n_groups;
+    return RL4RS_OK;
+}
+
 int rl4rs_dien_set_obs_last(rl4rs_dien* n, float* obs_last_dev) {
     RL4RS_REQUIRE(n, "dien_set_obs_last: null handle");
     n->obs_last = obs_last_dev;
@@ -2597,6 +2640,9 @@ int rl4rs_dien_status(rl4rs_dien* n, int32_t* flags, void* stream) {
 }  // extern "C"
 namespace rl4rs {
 void dien_set_obs_mirror(rl4rs_dien* n, float* host_visible) { if (n) n->obs_mirror = host_visible; }
+void dien_last_partition(const rl4rs_dien* n, DienPartition* out) { *out = n->dd_info; }
+bool dien_takes_partition(const rl4rs_dien* n) { return n && n->row_dedup && !n->dup_store; }
+const int32_t* dien_row_order(const rl4rs_dien* n, int n_groups) { return (n->row_order && n->row_order_n == n_groups) ? n->row_order : nullptr; }
 bool dien_obs_mirror_used(const rl4rs_dien* n) { return n && n->obs_mirror_used; }
 bool dien_augru_rows64(const rl4rs_dien* n, int B, int group) {
     return n && n->fp16x2 && n->augru_x && (int64_t)B * group <= n->c.max_rows && augru_rows64(n, B * group, group);
@@ -2679,7 +2725,16 @@ int rl4rs_dien_profile_reset(rl4rs_dien* n) {
     double d; int64_t l;
     int rc = rl4rs_dien_profile_read(n, 0, &d, &l);
     for (int i = 0; i < KID_COUNT; ++i) { n->ms_total[i] = 0; n->launches[i] = 0; }
+    n->dedup_launched = n->dedup_carried = 0;
     return rc;
+}
+// Forwards since the last rl4rs_dien_profile_reset (counted whether profiling is on or not) that launched k_row_dedup, and that
+// took their partition from the caller instead: the profile class of k_row_dedup counts an (empty) entry for those as well
+int rl4rs_dien_dedup_counts(rl4rs_dien* n, int64_t* launched, int64_t* carried) {
+    RL4RS_REQUIRE(n, "dien_dedup_counts: null handle");
+    if (launched) *launched = n->dedup_launched;
+    if (carried) *carried = n->dedup_carried;
+    return RL4RS_OK;
 }
 
 }  // extern "C"

@@ -11,10 +11,12 @@
 //
 // Bound: HBM writes.  Algorithmic bytes per built row = Dn*4 + Cn*4 written + UD*4 + UC*4 + 36 read
 // = 2016 B at the reference config.
+#include <atomic>
 #include <cstdlib>
 #include <mutex>
 
 #include "common.hpp"
+#include "row_refine.hpp"
 
 namespace rl4rs {
 
@@ -143,121 +145,36 @@ __device__ __forceinline__ int offline_action_id(const EnvDev& e, int b, int cur
     return (cur < e.T && cur < e.logT) ? e.exposed[(size_t)b * e.logT + cur] : 0;
 }
 
+#define ENV_ROWS_BEGIN(b)
+#define ENV_ROWS_ACTED(b, a, lane)
+#define ENV_ROWS_BUILT(b, a, lane)
+#define ENV_ROWS_DONE(smem)
 template <int MODE, bool USE_LDS>
 __global__ __launch_bounds__(1024) void k_env_rows(EnvDev e, const int32_t* __restrict__ actions,
                                                    int cur, int n_complete, int j_base, ActTail tail) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    float* s_item_lds = reinterpret_cast<float*>(smem);
-    const size_t item_bytes = USE_LDS ? (((size_t)e.A * e.D * 4 + 15) & ~size_t(15)) : 0;
-    int32_t* s_prev_all = reinterpret_cast<int32_t*>(smem + item_bytes);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
-    int32_t* s_prev = s_prev_all + wave * e.T;
-    if (USE_LDS && MODE != 0) {
-        stage_items(e, s_item_lds);
-        __syncthreads();
-    }
-    const float* s_item = USE_LDS ? s_item_lds : e.item_vec;
-    const int R = (MODE == 2) ? e.B * n_complete : e.B;
-    const int total_waves = gridDim.x * nw;
-    if (MODE == 2 && RL4RS_ROWS_PER_ENV) {
-        // complete rows: one wave writes ALL n_complete rows of its env - prev_actions and the user columns are fetched once,
-        // then the wave only issues stores (a row per wave paid one dependent global round trip per 1.8 KB row)
-        for (int b = blockIdx.x * nw + wave; b < e.B; b += total_waves) {
-            for (int j = lane; j < e.T; j += 64) s_prev[j] = e.prev[(size_t)b * e.T + j];
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            for (int jj = 0; jj < n_complete; ++jj) {
-                const int j = j_base + jj;
-                const size_t r = (size_t)b * n_complete + jj;
-                int page_init = 0, npage = e.T, seq_id = 1;
-                if (e.is_seq) {
-                    page_init = j / e.P * e.P;
-                    npage = min(e.P, e.T - page_init);
-                    seq_id = j / e.P + 1;
-                }
-                build_row(e, s_item, s_prev, b, page_init, npage, seq_id, s_prev[j], e.c_dense + r * e.Dn, e.c_cat + r * e.Cn, lane);
-            }
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // s_prev is rewritten for the next env
-        }
-        return;
-    }
-    for (int r = blockIdx.x * nw + wave; r < R; r += total_waves) {
-        const int b = (MODE == 2) ? r / n_complete : r;
-        int a = 0;
-        for (int j = lane; j < e.T; j += 64) s_prev[j] = e.prev[(size_t)b * e.T + j];
-        if (MODE == 1) {
-            a = actions[b];
-            if (a < 0 || a >= e.A) {      // numpy would raise IndexError (slate.py:199)
-                if (lane == 0) atomicExch(e.err, 1);
-                a = 0;
-            }
-            s_prev[cur] = a;   // every lane writes the same value
-        }
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        if (MODE == 0) {
-            // RecState.__init__: dense = user_dense, category = user_cat, both padded (base.py:30-31)
-            build_row(e, s_item, s_prev, b, 0, -1, 0, 0, e.dense + (size_t)b * e.Dn, e.cat + (size_t)b * e.Cn, lane);
-            for (int l = lane; l < e.L; l += 64) e.seq1[(size_t)b * e.L + l] = 0;
-        } else if (MODE == 1) {
-            // ---- act (slate.py:198-202 / seqslate.py:98-102)
-            if (lane == 0) {
-                e.prev[(size_t)b * e.T + cur] = a;
-                e.amask[(size_t)b * e.W + (a >> 5)] &= ~(1u << (a & 31));
-                // the transition's constant outputs and the next step's logged action (ActTail): this wave owns env b
-                if (tail.done) tail.done[b] = tail.done_v;
-                if (tail.zero_reward) tail.zero_reward[b] = 0.0;
-                if (tail.next_action) tail.next_action[b] = offline_action_id(e, b, tail.next_cur);
-            }
-            bool hit = false;
-            for (int j = lane; j < e.T; j += 64) hit |= (e.is_special[s_prev[j]] != 0);
-            const bool any_hit = __any(hit);
-            const bool page_end = e.is_seq && ((cur + 1) % e.P == 0);
-            for (int w = lane; w < e.W; w += 64) {
-                if (page_end) {          // seqslate.py:124-126
-                    uint32_t f = full_word(e.A, w);
-                    e.amask[(size_t)b * e.W + w] = f;
-                    e.smask[(size_t)b * e.W + w] = f;
-                } else if (any_hit) {
-                    e.smask[(size_t)b * e.W + w] &= ~e.special_bits[w];
-                }
-            }
-            // ---- rebuild the state row (slate.py:203-213 / seqslate.py:103-122)
-            int page_init = 0, npage = e.T, seq_id = 1;
-            if (e.is_seq) {
-                page_init = cur / e.P * e.P;
-                npage = min(e.P, e.T - page_init);
-                seq_id = cur / e.P + 1;
-                // second sequence = items of the previous pages, pre-padded (seqslate.py:107-108)
-                for (int l = lane; l < e.L; l += 64) {
-                    int v = 0;
-                    if (page_init > 0) {
-                        int idx = page_init - e.L + l;
-                        if (idx >= 0) v = s_prev[idx];
-                    }
-                    e.seq1[(size_t)b * e.L + l] = v;
-                }
-            }
-            build_row(e, s_item, s_prev, b, page_init, npage, seq_id, a, e.dense + (size_t)b * e.Dn,
-                      e.cat + (size_t)b * e.Cn, lane);
-        } else {
-            // ---- complete-state row j of env b (slate.py:117-131 / seqslate.py:27-50)
-            const int j = j_base + (r - b * n_complete);
-            int page_init = 0, npage = e.T, seq_id = 1;
-            if (e.is_seq) {
-                page_init = j / e.P * e.P;
-                npage = min(e.P, e.T - page_init);
-                seq_id = j / e.P + 1;
-            }
-            a = s_prev[j];
-            build_row(e, s_item, s_prev, b, page_init, npage, seq_id, a, e.c_dense + (size_t)r * e.Dn,
-                      e.c_cat + (size_t)r * e.Cn, lane);
-        }
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // s_prev is rewritten by the next row
-    }
+#include "env_rows_body.inc"
 }
+#undef ENV_ROWS_BEGIN
+#undef ENV_ROWS_ACTED
+#undef ENV_ROWS_BUILT
+#undef ENV_ROWS_DONE
+// k_env_rows<1, USE_LDS> that also carries the duplicate-row partition over the act (row_refine.hpp): the wave that acts for env b
+// decides whether b stays with its representative of the previous forward, and the workgroup that finishes last rebuilds the
+// active list when some env did not
+#define ENV_ROWS_BEGIN(b) const int rf_r = rf.rep_prev[b]; int rf_ar = 0
+#define ENV_ROWS_ACTED(b, a, lane) rf_ar = row_refine_key(actions, e.A, rf_r)
+#define ENV_ROWS_BUILT(b, a, lane) row_refine_env(rf, b, a, rf_r, rf_ar, lane)
+#define ENV_ROWS_DONE(smem) row_refine_finish(rf, actions, e.A, smem)
+template <bool USE_LDS>
+__global__ __launch_bounds__(1024) void k_env_rows_refine(EnvDev e, const int32_t* __restrict__ actions, int cur, ActTail tail, RowRefineArgs rf) {
+    constexpr int MODE = 1;
+    const int n_complete = 0, j_base = 0;
+#include "env_rows_body.inc"
+}
+#undef ENV_ROWS_BEGIN
+#undef ENV_ROWS_ACTED
+#undef ENV_ROWS_BUILT
+#undef ENV_ROWS_DONE
 
 // ---------------------------------------------------------------------------------------------
 // masked K-NN argmax in float64 (slate.py:186-191): one wave per env.
@@ -573,6 +490,7 @@ struct rl4rs_env {
     bool catalog_set, batch_set;
     bool state_fresh;          // rl4rs_env_load_lines already wrote prev_actions = 0 and the all-ones masks: reset skips its memsets
     int rows_variant;          // rl4rs_env_set_option(RL4RS_ENV_OPT_ROWS_VARIANT)
+    uint64_t rows_stamp;       // rl4rs::next_stamp() of the last call that wrote the state rows or the data they are built from
     // owned device memory
     float* item_vec; double* price; double* action_emb; uint32_t* special_bits; uint32_t* loc_bits;
     uint8_t* is_special;
@@ -614,9 +532,22 @@ static RowsLaunch rows_launch(const rl4rs_env* e, int R, int mode) {
 }
 template <int MODE>
 static int launch_rows(rl4rs_env* e, int R, const int32_t* actions, int cur, int n_complete, int j_base, hipStream_t st,
-                       const ActTail& tail = ActTail()) {
+                       const ActTail& tail = ActTail(), const RowRefineArgs* rf = nullptr) {
     if (MODE == 1) e->state_fresh = false;      // an act writes prev_actions / the masks: the next reset must clear them again
+    if (MODE != 2) e->rows_stamp = next_stamp();
     RowsLaunch L = rows_launch(e, R, MODE);
+    if (MODE == 1 && rf) {
+        // the act that also carries the duplicate-row partition (row_refine.hpp): the last workgroup's resolve pass works in the
+        // dynamic LDS the row loop has left
+        const size_t smem = L.smem > row_refine_smem(L.threads) ? L.smem : row_refine_smem(L.threads);
+        RL4RS_REQUIRE(smem <= 65536, "act: no LDS left for the partition refinement (%zu bytes)", smem);
+        if (L.lds)
+            hipLaunchKernelGGL((k_env_rows_refine<true>), dim3(L.grid), dim3(L.threads), smem, st, e->d, actions, cur, tail, *rf);
+        else
+            hipLaunchKernelGGL((k_env_rows_refine<false>), dim3(L.grid), dim3(L.threads), smem, st, e->d, actions, cur, tail, *rf);
+        RL4RS_LAUNCH_CHECK();
+        return RL4RS_OK;
+    }
     if (L.lds)
         hipLaunchKernelGGL((k_env_rows<MODE, true>), dim3(L.grid), dim3(L.threads), L.smem, st, e->d, actions, cur, n_complete, j_base, tail);
     else
@@ -626,6 +557,15 @@ static int launch_rows(rl4rs_env* e, int R, const int32_t* actions, int cur, int
 }
 
 namespace rl4rs {
+uint64_t next_stamp() {
+    static std::atomic<uint64_t> stamp{0};
+    return ++stamp;
+}
+uint64_t env_rows_stamp(const rl4rs_env* e) { return e ? e->rows_stamp : 0; }
+bool env_refine_fits(const rl4rs_env* e) {
+    const RowsLaunch L = rows_launch(e, e->cfg.batch_size, 1);
+    return (L.smem > row_refine_smem(L.threads) ? L.smem : row_refine_smem(L.threads)) <= 65536;
+}
 // The attribute is a property of (device, function): the cache is keyed by both and guarded, so handles created on a second
 // device or from another thread of the process still opt in (a process normally drives one device).
 int current_device() {
@@ -790,6 +730,7 @@ int rl4rs_env_load_batch(rl4rs_env* e, const int32_t* exposed, const int32_t* fe
     if (d.UC) RL4RS_HIP_TRY(hipMemcpyAsync(e->ucat, ucat, (size_t)d.B * d.UC * 4, hipMemcpyDeviceToDevice, st));
     e->batch_set = true;
     e->state_fresh = false;
+    e->rows_stamp = next_stamp();
     return RL4RS_OK;
 }
 
@@ -806,6 +747,7 @@ int rl4rs_env_load_lines(rl4rs_env* e, const int32_t* s_exposed, const int32_t* 
     RL4RS_LAUNCH_CHECK();
     e->batch_set = true;
     e->state_fresh = true;
+    e->rows_stamp = next_stamp();
     return RL4RS_OK;
 }
 
@@ -829,21 +771,21 @@ int rl4rs_env_reset(rl4rs_env* e, void* stream) {
 }
 
 }  // extern "C"
-int rl4rs::env_act_discrete_tail(rl4rs_env* e, const int32_t* actions, const ActTail& tail, void* stream) {
+int rl4rs::env_act_discrete_tail(rl4rs_env* e, const int32_t* actions, const ActTail& tail, void* stream, const RowRefineArgs* rf) {
     RL4RS_REQUIRE(e && actions, "act_discrete: null argument");
     if (e->cur_steps >= e->d.T) {    // prev_actions[:, cur_steps] would raise IndexError (slate.py:198)
         set_error("act at cur_steps=%d >= max_steps=%d", e->cur_steps, e->d.T);
         return RL4RS_ESTATE;
     }
     hipStream_t st = (hipStream_t)stream;
-    int rc = launch_rows<1>(e, e->d.B, actions, e->cur_steps, 0, 0, st, tail);
+    int rc = launch_rows<1>(e, e->d.B, actions, e->cur_steps, 0, 0, st, tail, rf);
     if (rc) return rc;
     e->cur_steps += 1;
     return RL4RS_OK;
 }
 extern "C" {
 int rl4rs_env_act_discrete(rl4rs_env* e, const int32_t* actions, void* stream) {
-    return rl4rs::env_act_discrete_tail(e, actions, ActTail(), stream);
+    return rl4rs::env_act_discrete_tail(e, actions, ActTail(), stream, nullptr);
 }
 
 static int knn_launch(const void* actions, int is_f64, int n, const double* emb, int A, int E,
@@ -881,6 +823,11 @@ static int knn_launch(const void* actions, int is_f64, int n, const double* emb,
 }
 
 int rl4rs_env_act_conti(rl4rs_env* e, const void* actions, int is_f64, int32_t* chosen, void* stream) {
+    return rl4rs::env_act_conti_refine(e, actions, is_f64, chosen, stream, nullptr);
+}
+}  // extern "C"
+// the key of the refinement is the id the K-NN resolved (knn_tmp): the act kernel reads it as its action
+int rl4rs::env_act_conti_refine(rl4rs_env* e, const void* actions, int is_f64, int32_t* chosen, void* stream, const RowRefineArgs* rf) {
     RL4RS_REQUIRE(e && actions, "act_conti: null argument");
     if (e->cur_steps >= e->d.T) {
         set_error("act at cur_steps=%d >= max_steps=%d", e->cur_steps, e->d.T);
@@ -894,8 +841,9 @@ int rl4rs_env_act_conti(rl4rs_env* e, const void* actions, int is_f64, int32_t* 
                         d.W, nullptr, e->knn_tmp, st);
     if (rc) return rc;
     if (chosen) RL4RS_HIP_TRY(hipMemcpyAsync(chosen, e->knn_tmp, (size_t)d.B * 4, hipMemcpyDeviceToDevice, st));
-    return rl4rs_env_act_discrete(e, e->knn_tmp, stream);
+    return rl4rs::env_act_discrete_tail(e, e->knn_tmp, ActTail(), stream, rf);
 }
+extern "C" {
 
 int rl4rs_knn(const void* actions, int is_f64, int32_t n, const double* emb, int32_t A, int32_t E,
               const uint8_t* mask, int32_t* out, void* stream) {

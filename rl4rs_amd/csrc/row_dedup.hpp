@@ -18,6 +18,9 @@
 // chains to their root (equality is transitive), so no representative points to another one.  A duplicate further away than
 // the cap from every equal group is simply kept as distinct.  `dense` and `cat` are read only at positions whose predecessor has
 // the same slots: a batch without shared slots costs the look at the slot table alone.
+//
+// A forward whose caller hands it the partition (rl4rs_dien_set_row_partition; step.hip carries the env batch's partition from step to
+// step, row_refine.hpp) launches no k_row_dedup: its consumers read the caller's rep / active / n_active instead.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -9,6 +9,7 @@
 // exception in order, not in results: a reward step may score the state row inside the reward forward (fold_obs below).  Nothing is
 // allocated and nothing synchronises inside: all scratch belongs to the binding created by rl4rs_env_attach_scorer.
 #include "common.hpp"
+#include "row_refine.hpp"
 
 using namespace rl4rs;
 
@@ -32,6 +33,18 @@ struct rl4rs_stepper {
     int32_t* next_off;         // [max_steps + 1][B]: row c = the logged item ids of step c, written by the step that led to it - a row
                                // of its own per step of an episode, so a caller may hold what it was handed until the episode ends
     int next_off_cur;          // the step whose row the last transition wrote, -1 = none
+    // The duplicate-row partition of the env batch, carried from forward to forward (row_refine.hpp): valid from the act
+    // behind a content dedup of the state rows (the reset observation) until a reset, a page turn (the slot table changes) or a
+    // changed row order.  While it is valid every scorer forward of a transition gets it (rl4rs_dien_set_row_partition).
+    bool carry;                // rl4rs_stepper_set_partition_carry (default on)
+    bool part_valid;           // part_rep[part_cur] / part_active / part_cnt describe the rows the last act built
+    bool part_now;             // ... and the transition in flight hands them to its forwards
+    int part_cur;
+    int32_t* part_rep[2];      // [B] each, used in turn: an act reads one and writes the other
+    int32_t* part_active;      // [B]
+    int32_t* part_cnt;         // [0] n_active, [1] ticket, [2] envs that split off in the act in flight
+    const int32_t* part_order; // the scorer's row order the active list was built in
+    uint64_t part_stamp;       // the env's row stamp behind the act that left the partition
     hipStream_t copy_stream;   // rl4rs_env_step_record_host: early device-to-host copies run here, beside the scorer's kernels
     hipEvent_t ev_ready, ev_copied;
 };
@@ -39,6 +52,10 @@ struct rl4rs_stepper {
 namespace {
 
 int scorer_forward(rl4rs_stepper* s, int R, int group, const float* dense, const int32_t* cat, float* obs, float* prob, void* stream) {
+    if (s->part_now && s->dien) {      // groups are per env in every forward of a transition: the env partition is the group partition
+        int rc = rl4rs_dien_set_row_partition(s->dien, s->part_rep[s->part_cur], s->part_active, s->part_cnt, s->cfg.batch_size);
+        if (rc) return rc;
+    }
     return s->dien ? rl4rs_dien_forward(s->dien, R, group, dense, cat, s->slots, obs, prob, stream)
                    : rl4rs_simnet_forward(s->simnet, R, group, dense, cat, s->slots, obs, prob, stream);
 }
@@ -84,6 +101,44 @@ struct NoHook { int operator()() const { return RL4RS_OK; } };
 // scorer is the DIEN with k_augru_x, the n-row forward runs the 64-row form of k_augru_x (where a row costs about a quarter of what it
 // costs in the chain-bound observation launch: the regime the fold was measured in; a small batch, whose n-row launch falls to 32-row
 // workgroups, keeps the two-forward order) and the n-row launch needs no more rounds over the chip than the (n - 1)-row one.
+// What the act of the transition about to start does for the partition: *rf filled and true = it refines (the partition the last
+// act left, or the one the scorer's last content dedup found on exactly these rows: the reset observation forward).  False: the
+// forwards of this transition look for duplicates themselves.
+bool plan_refine(rl4rs_stepper* s, int cur, RowRefineArgs* rf) {
+    s->part_now = false;
+    const int B = s->cfg.batch_size;
+    const bool was_valid = s->part_valid;
+    s->part_valid = false;
+    if (!s->carry || !s->dien || !s->part_cnt || !dien_takes_partition(s->dien) || !env_refine_fits(s->env)) return false;
+    // the first act of a page re-encodes the second sequence input into a slot per env: the slot table changes under the partition
+    if (s->cfg.is_seq && cur > 0 && cur % s->cfg.page_items == 0) return false;
+    const int32_t* order = dien_row_order(s->dien, B);
+    memset(rf, 0, sizeof(*rf));
+    if (was_valid && s->part_stamp == env_rows_stamp(s->env) && s->part_order == order) {
+        rf->rep_prev = s->part_rep[s->part_cur];
+    } else {
+        DienPartition d;
+        dien_last_partition(s->dien, &d);
+        if (!(d.stamp > env_rows_stamp(s->env) && d.n_groups == B && d.group == 1 && d.dense == s->dense && d.cat == s->cat &&
+              d.slots == s->slots && d.order == order)) return false;
+        rf->rep_prev = d.rep;           // adopted where it lies: this act writes the stepper's own copy of everything
+        rf->active_src = d.active;
+        rf->n_active_src = d.n_active;
+    }
+    rf->n = B;
+    rf->rep = s->part_rep[s->part_cur ^ 1];
+    rf->active = s->part_active;
+    rf->cnt = s->part_cnt;
+    rf->order = order;
+    return true;
+}
+void refined(rl4rs_stepper* s) {
+    s->part_cur ^= 1;
+    s->part_order = dien_row_order(s->dien, s->cfg.batch_size);
+    s->part_stamp = env_rows_stamp(s->env);
+    s->part_valid = s->part_now = true;
+}
+
 bool fold_obs(const rl4rs_stepper* s) {
     const int n = s->n_complete, B = s->cfg.batch_size;
     if (!s->obs_fold || !s->dien || n < 2) return false;
@@ -196,6 +251,16 @@ int attach(rl4rs_env* env, rl4rs_dien* dien, rl4rs_simnet* simnet, const int32_t
     }
     s->next_off = reinterpret_cast<int32_t*>(ring);
     s->next_off_cur = -1;
+    if (dien) {
+        float* part = nullptr;          // rep x 2, active, counters
+        if ((rc = dev_alloc(&part, 3 * B + 4))) { rl4rs_stepper_destroy(s); return rc; }
+        s->part_rep[0] = reinterpret_cast<int32_t*>(part);
+        s->part_rep[1] = s->part_rep[0] + B;
+        s->part_active = s->part_rep[1] + B;
+        s->part_cnt = s->part_active + B;
+        if (hipMemset(s->part_cnt, 0, 16) != hipSuccess) { rl4rs_stepper_destroy(s); set_error("env_attach_scorer: hipMemset failed"); return RL4RS_EHIP; }
+        s->carry = true;
+    }
     s->act_tail = true;
     s->obs_fold = true;
     s->distinct_hint = s->cfg.batch_size;
@@ -228,6 +293,7 @@ int rl4rs_stepper_destroy(rl4rs_stepper* s) {
     if (s->probs) (void)hipFree(s->probs);
     if (s->p_last) (void)hipFree(s->p_last);
     if (s->next_off) (void)hipFree(s->next_off);
+    if (s->part_rep[0]) (void)hipFree(s->part_rep[0]);
     if (s->ev_ready) (void)hipEventDestroy(s->ev_ready);
     if (s->ev_copied) (void)hipEventDestroy(s->ev_copied);
     if (s->copy_stream) (void)hipStreamDestroy(s->copy_stream);
@@ -240,9 +306,12 @@ int rl4rs_env_step_discrete(rl4rs_stepper* s, const int32_t* actions_dev, float*
     RL4RS_REQUIRE(s && actions_dev && obs_dev, "env_step_discrete: null argument");
     const int cur = rl4rs_env_cur_steps(s->env);
     s->next_off_cur = -1;
+    RowRefineArgs rf;
+    const bool refine = plan_refine(s, cur, &rf);
     if (!s->act_tail) {
-        int rc = rl4rs_env_act_discrete(s->env, actions_dev, stream);
+        int rc = rl4rs::env_act_discrete_tail(s->env, actions_dev, ActTail(), stream, refine ? &rf : nullptr);
         if (rc) return rc;
+        if (refine) refined(s);
         return after_act(s, cur, obs_dev, reward_dev, done_dev, mask_bits_dev, stream, NoHook(), false, true);
     }
     // is a reward due after this act?  (rl4rs_env_is_reward_step at cur + 1; checked against it below)
@@ -253,8 +322,9 @@ int rl4rs_env_step_discrete(rl4rs_stepper* s, const int32_t* actions_dev, float*
     tail.zero_reward = (reward_dev && !due) ? reward_dev : nullptr;
     tail.next_action = (cur + 1 <= T) ? s->next_off + (size_t)(cur + 1) * s->cfg.batch_size : nullptr;
     tail.next_cur = cur + 1;
-    int rc = rl4rs::env_act_discrete_tail(s->env, actions_dev, tail, stream);
+    int rc = rl4rs::env_act_discrete_tail(s->env, actions_dev, tail, stream, refine ? &rf : nullptr);
     if (rc) return rc;
+    if (refine) refined(s);
     if (tail.next_action) s->next_off_cur = cur + 1;
     // (a different answer from the env itself: k_step_tail runs as before and has the last word)
     const bool covered = rl4rs_env_is_reward_step(s->env) == due;
@@ -271,6 +341,13 @@ int rl4rs_stepper_set_act_tail(rl4rs_stepper* s, int32_t on) {
 int rl4rs_stepper_set_obs_fold(rl4rs_stepper* s, int32_t on) {
     RL4RS_REQUIRE(s, "stepper_set_obs_fold: null argument");
     s->obs_fold = on != 0;
+    return RL4RS_OK;
+}
+
+int rl4rs_stepper_set_partition_carry(rl4rs_stepper* s, int32_t on) {
+    RL4RS_REQUIRE(s, "stepper_set_partition_carry: null argument");
+    s->carry = on != 0 && s->part_cnt != nullptr;
+    s->part_valid = s->part_now = false;
     return RL4RS_OK;
 }
 
@@ -309,8 +386,11 @@ int rl4rs_env_step_conti(rl4rs_stepper* s, const void* actions_dev, int is_f64, 
     RL4RS_REQUIRE(s && actions_dev && obs_dev, "env_step_conti: null argument");
     const int cur = rl4rs_env_cur_steps(s->env);
     s->next_off_cur = -1;
-    int rc = rl4rs_env_act_conti(s->env, actions_dev, is_f64, chosen_dev, stream);
+    RowRefineArgs rf;
+    const bool refine = plan_refine(s, cur, &rf);
+    int rc = rl4rs::env_act_conti_refine(s->env, actions_dev, is_f64, chosen_dev, stream, refine ? &rf : nullptr);
     if (rc) return rc;
+    if (refine) refined(s);
     return after_act(s, cur, obs_dev, reward_dev, done_dev, mask_bits_dev, stream, NoHook(), false, true);
 }
 
@@ -366,16 +446,22 @@ static int step_record(rl4rs_stepper* s, bool observe, const void* actions_dev, 
     float* obs = reinterpret_cast<float*>(R + L.obs);
     int32_t* chosen = reinterpret_cast<int32_t*>(R + L.chosen);
     const int cur = rl4rs_env_cur_steps(s->env) - (observe ? 1 : 0);      // `cur + 1` below = the step counter the record describes
+    RowRefineArgs rf;
+    bool refine = false;
     if (observe) {
+        s->part_now = false;            // the rows of a state nobody acted on: this forward compares them (and seeds the next act)
         rc = RL4RS_OK;
     } else if (action_kind == 0) {
         RL4RS_HIP_TRY(hipMemcpyAsync(chosen, actions_dev, (size_t)B * 4, hipMemcpyDeviceToDevice, st));
         s->next_off_cur = -1;
-        rc = rl4rs_env_act_discrete(s->env, reinterpret_cast<const int32_t*>(actions_dev), stream);
+        refine = plan_refine(s, cur, &rf);
+        rc = rl4rs::env_act_discrete_tail(s->env, reinterpret_cast<const int32_t*>(actions_dev), ActTail(), stream, refine ? &rf : nullptr);
     } else {
-        rc = rl4rs_env_act_conti(s->env, actions_dev, action_kind == 2 ? 1 : 0, chosen, stream);
+        refine = plan_refine(s, cur, &rf);
+        rc = rl4rs::env_act_conti_refine(s->env, actions_dev, action_kind == 2 ? 1 : 0, chosen, stream, refine ? &rf : nullptr);
     }
     if (rc) return rc;
+    if (refine) refined(s);
     const int reward_step = observe ? 0 : rl4rs_env_is_reward_step(s->env);
     // the observation-side mask is a function of the env state the act just left (slate.py:90-97); nothing below changes that state
     if (L.mask_i64 >= 0 && (rc = rl4rs_env_obs_mask(s->env, R + L.mask_i64, 2, stream))) return rc;

@@ -15,7 +15,7 @@ from ._lib import check
 # rl4rs_env_buffer ids (include/rl4rs_hip.h)
 BUF_PREV_ACTIONS, BUF_ACTION_MASK, BUF_SPECIAL_MASK, BUF_DENSE, BUF_CATEGORY, BUF_SEQ0, BUF_SEQ1, \
     BUF_C_DENSE, BUF_C_CATEGORY, BUF_ERROR_FLAG = range(10)
-DIEN_ALL_FEATURE, DIEN_SCORES, DIEN_QUERY, DIEN_H1, DIEN_N_ACTIVE, DIEN_ROW_REP = range(6)
+DIEN_ALL_FEATURE, DIEN_SCORES, DIEN_QUERY, DIEN_H1, DIEN_N_ACTIVE, DIEN_ROW_REP, DIEN_ROW_ACTIVE = range(7)
 
 _MASK_DTYPES = {torch.uint8: 0, torch.int32: 1, torch.int64: 2, torch.float32: 3}
 
@@ -331,11 +331,13 @@ class DeviceStepper(object):
     """rl4rs_stepper handle: an env bound to its scorer so that one call runs a whole transition
     (rl4rs_env_step_discrete / rl4rs_env_step_conti = RecSimBase._step, base.py:157-170)."""
 
-    def __init__(self, env, net, slots, act_tail=True, obs_fold=True):
+    def __init__(self, env, net, slots, act_tail=True, obs_fold=True, partition_carry=True):
         """``act_tail=False`` (config['no_act_tail'] / RL4RS_NO_ACT_TAIL=1): rl4rs_env_step_discrete launches k_step_tail as it
         did and leaves no next-step logged actions (rl4rs_stepper_set_act_tail).  ``obs_fold=False``
         (config['no_reward_obs_fold'] / RL4RS_NO_REWARD_OBS_FOLD=1): a reward step runs its observation forward and then the
-        reward forward of n - 1 rows per env, as it did (rl4rs_stepper_set_obs_fold)."""
+        reward forward of n - 1 rows per env, as it did (rl4rs_stepper_set_obs_fold).  ``partition_carry=False``
+        (config['no_partition_carry'] / RL4RS_NO_PARTITION_CARRY=1): every scorer forward of a transition looks for its duplicate
+        rows itself, as it did (rl4rs_stepper_set_partition_carry)."""
         self.lib = _lib.load()
         self.env, self.net, self.slots = env, net, slots          # keep the handles and the slot table alive
         assert slots.dtype == torch.int32 and slots.is_contiguous() and slots.shape[1] == env.B
@@ -348,6 +350,8 @@ class DeviceStepper(object):
             check(self.lib.rl4rs_stepper_set_act_tail(self.h, 0))
         if not obs_fold:
             check(self.lib.rl4rs_stepper_set_obs_fold(self.h, 0))
+        if not partition_carry:
+            check(self.lib.rl4rs_stepper_set_partition_carry(self.h, 0))
         self._distinct_hint = None
         self.B, self.A, self.E, self.W, self.device = env.B, env.A, env.E, env.W, env.device
         self.obs_dim = int(getattr(net, 'obs_dim', 256))         # 256 for DIEN / dnn / lstm, 256 + U + Cn*E for widedeep
@@ -642,7 +646,7 @@ class DeviceDien(object):
         p = C.c_void_p()
         n = C.c_int64()
         check(self.lib.rl4rs_dien_buffer(self.h, which, C.byref(p), C.byref(n)))
-        if which in (DIEN_N_ACTIVE, DIEN_ROW_REP):      # int32: row dedup of the last forward (an error where it is off)
+        if which in (DIEN_N_ACTIVE, DIEN_ROW_REP, DIEN_ROW_ACTIVE):      # int32: row dedup of the last forward (an error where it is off)
             out = torch.empty(n.value // 4, dtype=torch.int32, device=self.device)
             check(self.lib.rl4rs_copy_d2d(_ptr(out), p, n.value, _stream()))
             return out
@@ -682,6 +686,19 @@ class DeviceDien(object):
 
     def profile_reset(self):
         check(self.lib.rl4rs_dien_profile_reset(self.h))
+
+    def dedup_counts(self):
+        """-> (forwards since profile_reset that launched k_row_dedup, forwards that took a carried partition instead)."""
+        a, b = C.c_int64(), C.c_int64()
+        check(self.lib.rl4rs_dien_dedup_counts(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def set_row_partition(self, rep, active, n_active):
+        """The NEXT forward takes its duplicate row groups from these int32 device tensors (rl4rs_dien_set_row_partition)."""
+        for t in (rep, active, n_active):
+            assert t.dtype == torch.int32 and t.is_contiguous() and t.is_cuda
+        self._partition = (rep, active, n_active)       # keep them alive
+        check(self.lib.rl4rs_dien_set_row_partition(self.h, _ptr(rep), _ptr(active), _ptr(n_active), int(rep.numel())))
 
     def profile(self):
         out = {}

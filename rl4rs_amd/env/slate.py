@@ -611,7 +611,9 @@ class SlateRecEnv(RecSimBase):
             no_tail = self.config.get('no_act_tail', os.environ.get('RL4RS_NO_ACT_TAIL', '') not in ('', '0'))
             # config['no_reward_obs_fold'] (RL4RS_NO_REWARD_OBS_FOLD=1): the observation forward of a reward step as a forward of its own
             no_fold = self.config.get('no_reward_obs_fold', os.environ.get('RL4RS_NO_REWARD_OBS_FOLD', '') not in ('', '0'))
-            self._stepper = D.DeviceStepper(env, net, slots, act_tail=not no_tail, obs_fold=not no_fold)
+            # config['no_partition_carry'] (RL4RS_NO_PARTITION_CARRY=1): every forward of a transition compares whole rows again
+            no_carry = self.config.get('no_partition_carry', os.environ.get('RL4RS_NO_PARTITION_CARRY', '') not in ('', '0'))
+            self._stepper = D.DeviceStepper(env, net, slots, act_tail=not no_tail, obs_fold=not no_fold, partition_carry=not no_carry)
             self._stepper_key = key
         # envs the scorer's row dedup is expected to leave: the batch's distinct log lines - but SeqSlate gives every env a slot of
         # its own for the second sequence input from the second page on (_seq_slots_own): no two envs are duplicates there
