@@ -55,8 +55,31 @@ def test_allowed_sets_equal_the_oracle_envs_masks():
     assert saw_special                                  # the special-item rule was exercised
 
 
+def test_shapes_are_in_the_forms_they_were_chosen_for():
+    """exactk_ref.sample_axis_forms restates the chunk rules of csrc/exactk.hip: shapes 0 - 3 and the tiny shape stay in the single-chunk
+    form of every reduction, shapes 4 - 6 cross the thresholds they were chosen for (and no smaller N does)."""
+    forms = lambda s: R.sample_axis_forms(s[0], s[4])
+    for s in R.GPU_SHAPES[:4] + (R.TINY_SHAPE,):
+        assert forms(s) == dict(colsum_rows_chunks=1, tn_rows_chunks=1, loss_trips=1, tn_items_chunk=256, colsum_items_chunk=64,
+                                tn_decoder_chunk=256), s
+    assert R.GPU_SHAPES[4:] == ((75, 32, 2, 1, 900), (40, 16, 2, 1, 1900), (284, 64, 4, 2, 66))
+    f = forms(R.GPU_SHAPES[4])                                     # every row of the table but the decoder's
+    assert f['colsum_rows_chunks'] > 1 and f['tn_rows_chunks'] > 1 and f['loss_trips'] > 1 and f['tn_items_chunk'] > 256
+    assert f['colsum_items_chunk'] > 64 and f['colsum_items_chunk'] % 8 != 0 and f['tn_decoder_chunk'] == 256
+    assert R.sample_axis_forms(75, 873)['colsum_items_chunk'] == 64            # M = 65 475: N = 874 is the first past 65 536
+    f = forms(R.GPU_SHAPES[5])                                     # the decoder's as well
+    assert f['tn_decoder_chunk'] > 256 and f['colsum_items_chunk'] > 64 and f['colsum_items_chunk'] % 8 != 0
+    assert f['colsum_rows_chunks'] > 1 and f['tn_rows_chunks'] > 1 and f['loss_trips'] > 1 and f['tn_items_chunk'] > 256
+    assert R.sample_axis_forms(40, 1820)['tn_decoder_chunk'] == 256            # 9 N = 16 380
+    f = forms(R.GPU_SHAPES[6])                                     # the reference's widths: M > 16384 and N > 64, nothing else
+    assert f == dict(colsum_rows_chunks=2, tn_rows_chunks=1, loss_trips=1, tn_items_chunk=304, colsum_items_chunk=64, tn_decoder_chunk=256)
+    assert R.sample_axis_forms(284, 57)['tn_items_chunk'] == 256               # M = 16 188: N = 58 is the first past 16 384
+    # the critic's extra row counts (tests/test_gpu_exactk.py): 2 and 17 chunks, the last of 4099 ragged
+    assert [R.sample_axis_forms(1, n)['tn_rows_chunks'] for n in (37, 1, 300, 4099)] == [1, 1, 2, 17] and 4099 % 256 == 3
+
+
 def _keys():
-    return [(i, rate) for i in range(len(R.GPU_SHAPES)) for rate in R.RATES] + ['crafted']
+    return list(R.CASE_KEYS) + ['crafted']
 
 
 @pytest.mark.parametrize('key', _keys(), ids=str)
@@ -82,7 +105,34 @@ def test_case_seeds_do_not_sit_on_a_relu_kink(key):
     assert max(errs) < R.BAR_FACTOR * R.MEASURED[key]['grad_rel'], (key, errs)
 
 
-@pytest.mark.parametrize('i', range(len(R.GPU_SHAPES)))
+@pytest.mark.parametrize('key', R.KINK_KEYS, ids=str)
+def test_large_case_seeds_keep_their_relu_units_off_zero(key):
+    """The third condition on a seed, for the shapes of millions of relu units per layer: every unit that carries at least the
+    gradient bar lies farther from 0 (float64) than KINK_MARGIN x the rms float32 error of its layer's pre-activations."""
+    c = R.case(*key)
+    bar = R.BAR_FACTOR * R.MEASURED[key]['grad_rel']
+    for s in R.relu_sites(c, seed=5, step=7):
+        heavy = s['g'] >= bar
+        nearest = float(s['z'][heavy].min()) if heavy.any() else np.inf
+        print(key, '%-9s %d units, %d carry the bar, nearest to 0 at %.3g = %.2f rms (rms %.3g)'
+              % (s['name'], s['z'].size, int(heavy.sum()), nearest, nearest / s['rms'], s['rms']))
+        assert nearest >= R.KINK_MARGIN * s['rms'], (key, s['name'], nearest, s['rms'])
+
+
+@pytest.mark.parametrize('N', sorted(R.CRITIC_SEEDS))
+def test_critic_inputs_keep_their_relu_units_off_zero(N):
+    """The critic comparisons' inputs (tests/test_gpu_exactk.py): no hidden unit whose flip would show above the rounding level sits
+    within CRITIC_KINK_MARGIN rms of a float32 pre-activation error of 0, so the float32 yardstick is the rounding level on any CPU."""
+    for s in R.critic_relu_sites(*R.critic_case(N)):
+        heavy = s['g'] >= 2.0 ** -23
+        nearest = float(s['z'][heavy].min())
+        print(N, '%s %d units, %d carry 2^-23, nearest to 0 at %.3g = %.2f rms' % (s['name'], s['z'].size, int(heavy.sum()), nearest, nearest / s['rms']))
+        assert nearest >= R.CRITIC_KINK_MARGIN * s['rms'], (N, s['name'], nearest, s['rms'])
+    # the inputs of the row counts that came first are the draws of RandomState(70 + N), as they always were
+    assert all(R.CRITIC_SEEDS[n] == 70 + n for n in (37, 1, 300))
+
+
+@pytest.mark.parametrize('i', R.DECODE_SHAPES)
 def test_exclusion_caps_hold_with_the_restatement_alone(i):
     """The restatement's own slates at the seeds of tests/test_gpu_exactk.py (decode pass, dropout 0.1): rows with a top-two gap
     under 10 x the logit bar at some step and sampled picks within the CDF-edge bar stay under 1 %."""
