@@ -11,6 +11,7 @@
 #include "common.hpp"
 #include "recur_args.hpp"
 #include "augru_x.hpp"
+#include "dien_plan.hpp"      // augru_tiles: the row-tile rule
 
 namespace rl4rs {
 
@@ -24,18 +25,18 @@ int augru_x_prepare() {
     return 0;
 }
 
-// rows_per_wg = 32: grid (ceil(n_rows / 32), S);  64: grid (n_rows / 64, S), or with 9 rows per cache slot (a.group == 9) 63 stored
-// rows per workgroup, grid (ceil(n_rows / 63), S) - the caller has checked the 64-row form's conditions
+// grid (augru_tiles, S): 32-row tiles; 64-row tiles, or with 9 rows per cache slot (a.group == 9) 63 stored rows per workgroup - the
+// caller has checked the 64-row form's conditions (dien_plan.hpp)
 void augru_x_launch(int rows_per_wg, int n_seq, hipStream_t st, const RecurArgs& a) {
-    const dim3 block(512);
+    const dim3 grid((unsigned)augru_tiles(rows_per_wg == 64, a.n_rows, a.group), n_seq), block(512);
     if (rows_per_wg == 64 && a.group == 9)
-        hipLaunchKernelGGL((k_augru_x<2, RL4RS_X2_NRES, RL4RS_X2_RING, false, 9>), dim3((a.n_rows + 62) / 63, n_seq), block, augru_x_smem(2), st, a);
+        hipLaunchKernelGGL((k_augru_x<2, RL4RS_X2_NRES, RL4RS_X2_RING, false, 9>), grid, block, augru_x_smem(2), st, a);
     else if (rows_per_wg == 64)      // (the 64-row form with the redirect - 256 registers, no spill - measured flat on SeqSlate and 0.3 % slower on the headline: not instantiated)
-        hipLaunchKernelGGL((k_augru_x<2, RL4RS_X2_NRES, RL4RS_X2_RING>), dim3(a.n_rows / 64, n_seq), block, augru_x_smem(2), st, a);
+        hipLaunchKernelGGL((k_augru_x<2, RL4RS_X2_NRES, RL4RS_X2_RING>), grid, block, augru_x_smem(2), st, a);
     else if (a.lead[0])       // the handle keeps a pad slot and the leading-zero counts of its cache slots (RecurArgs::lead)
-        hipLaunchKernelGGL((k_augru_x<1, RL4RS_X_NRES, RL4RS_X_RING, true>), dim3((a.n_rows + 31) / 32, n_seq), block, augru_x_smem(1), st, a);
+        hipLaunchKernelGGL((k_augru_x<1, RL4RS_X_NRES, RL4RS_X_RING, true>), grid, block, augru_x_smem(1), st, a);
     else
-        hipLaunchKernelGGL((k_augru_x<1, RL4RS_X_NRES, RL4RS_X_RING>), dim3((a.n_rows + 31) / 32, n_seq), block, augru_x_smem(1), st, a);
+        hipLaunchKernelGGL((k_augru_x<1, RL4RS_X_NRES, RL4RS_X_RING>), grid, block, augru_x_smem(1), st, a);
 }
 
 }  // namespace rl4rs

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "augru_xs.hpp"
+#include "dien_plan.hpp"      // augru_tiles: the row-tile rule
 
 namespace rl4rs {
 
@@ -16,9 +17,9 @@ int augru_xs_prepare() {
     return 0;
 }
 
-// grid (ceil(n_rows / 32), S + 1); the caller has checked the conditions (rl4rs_dien_forward: shadow)
+// grid (32-row tiles, S + 1); the caller has checked the conditions (dien_plan: shadow)
 void augru_xs_launch(int n_seq, hipStream_t st, const RecurArgs& a, const AugruShadowArgs& sh) {
-    const dim3 grid((a.n_rows + 31) / 32, n_seq + 1), block(512);
+    const dim3 grid((unsigned)augru_tiles(false, a.n_rows, 1), n_seq + 1), block(512);
     if (a.lead[0]) hipLaunchKernelGGL((k_augru_xs<true>), grid, block, augru_x_smem(1), st, a, sh);
     else hipLaunchKernelGGL((k_augru_xs<false>), grid, block, augru_x_smem(1), st, a, sh);
 }

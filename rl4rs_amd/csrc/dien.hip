@@ -18,6 +18,7 @@
 #include "common.hpp"
 #include "recur_args.hpp"
 #include "cat_attn2_row.hpp"
+#include "dien_plan.hpp"
 #include "augru_xs.hpp"      // AugruShadowArgs (the kernels themselves are instantiated in augru_x.hip / augru_xs.hip)
 
 namespace rl4rs {
@@ -1586,6 +1587,7 @@ static size_t augru_h16_smem(int mt, int nh2, int L) {
 
 struct rl4rs_dien {
     rl4rs_dien_cfg c;
+    DienTraits t;          // modes, shape numbers and the predicates derived from them (dien_plan.hpp): fixed at create
     int n_cu;
     int E, U, L, S, Cn, Dn, H, K, F, PLD, NH2;
     int Fld;               // row stride of allf: F, or only the Kh columns that exist in the table form of the head
@@ -1610,35 +1612,17 @@ struct rl4rs_dien {
     int32_t* lead[4];      // [max_slots + 1] leading zero ids of the sequence in every cache slot (k_gru_h16 writes, k_augru_x<.., PAD> reads); slot max_slots = the all-zero sequence
     float* gru_wc16[4];
     bool gru16, gru16_attr;
-    bool fp16x2;
-    bool augru_x;          // fp16x2 mode: k_augru_x (default) or the first-generation k_augru_h16 (RL4RS_DIEN_OPT_AUGRU_H16)
     int augru_rows;        // k_augru_x row-tile form: 0 automatic, 32, 64 (rl4rs_dien_set_augru_rows)
     float augru_s[4][3][8];   // fp16x2: power-of-two prescale of the AUGRU's reset / update / candidate column tiles (1 in fp32 mode)
-    bool din_x;            // fp16x2 DIN scores through k_din_x (RL4RS_DIN=v1 keeps k_din_scores<*, true>)
-    bool dense_chain;      // fp16x2 mode: both dense-tower layers in one launch (RL4RS_DENSE_FUSED=0 at create: two GEMMs)
     float* tsum;           // [max_rows, 256]: obs_b + the per-slot head tables' rows, built by k_cat_attn (table form, Cn <= 24)
                            // (internal; second tier on the active rows, DESIGN 25: rows of duplicate groups are stale)
-    bool gemm_group;       // fp16x2 mode: the chained dense tower and the q-side term of the DIN scores in one launch (RL4RS_DIEN_OPT_NO_GEMM_GROUP: two)
-    bool dense_fork;       // RL4RS_DIEN_OPT_DENSE_FORK: the dense tower (depends on nothing before the head) on side_stream, beside the category / DIN / AUGRU launches
-    hipStream_t side_stream; hipEvent_t ev_fork, ev_join;
-    bool cat_group;        // reward-sized launches (rows in groups of 8 / 9): k_cat_attn2g, one workgroup per group (RL4RS_DIEN_OPT_NO_CAT_GROUP: per row)
-    bool cat_v2;           // category branch through k_cat_attn2 (half-K LDS image) when the shape allows (RL4RS_DIEN_OPT_CAT_V1: first form)
-    bool cat16;            // fp16x2 mode: the Gram matrix of k_cat_attn in the split form (cat_emb inside the fp16 range)
-    bool gemm16;           // fp16x2 mode: the plain GEMMs (dense tower, q-side DIN term, cache projections, head) through k_gemm_h16
-    bool din16;            // fp16x2 mode: the DIN layer-1 operands (q*h1 bounded by the embedding table, W1d) fit fp16 too
+    hipStream_t side_stream; hipEvent_t ev_fork, ev_join;      // RL4RS_DIEN_OPT_DENSE_FORK: created by the first forward that forks
     int* range_flag;       // device int: a k_augru_h16 state left the fp16 range (sticky until read)
     const int32_t* row_order; int row_order_n;    // processing order of the row groups of a forward (caller-owned), or NULL
     // row dedup (row_dedup.hpp): k_din_x and k_augru_x score one representative per set of bit-identical row groups
-    bool dup_store;        // row dedup: k_din_x / k_augru_x store a representative's rows to its duplicates (RL4RS_DIEN_OPT_DUP_STORE; default: k_row_expand copies them)
-    bool augru_shadow;     // observation-sized forwards: k_din_xq + k_augru_xs (category branch and dense tower as a shadow plane of the AUGRU launch;
-                           // DESIGN 26; RL4RS_DIEN_OPT_NO_AUGRU_SHADOW: off).  Decided per forward (rl4rs_dien_forward: shadow)
-    bool last_shadow;      // the last forward took the shadow-plane order (rl4rs_dien_kernel_label reports it)
+    DienPlan last_plan;    // what the last forward issued (rl4rs_dien_kernel_label reports its shadow-plane order)
     int distinct_hint;     // rl4rs_dien_set_distinct_hint: row groups the dedup is expected to leave (0 = the forward's)
-    bool din_rows_auto;    // k_din_x at group == 1: 8 or 16 rows per workgroup from the active row count, on the device (RL4RS_DIEN_OPT_DIN_ROWS16: always 16)
     int32_t *dd_dstart, *dd_dlist, *dd_dcur;      // duplicate lists of the last forward (RowDedupArgs)
-    bool row_dedup;        // on wherever k_din_x and k_augru_x are the selected kernels (RL4RS_DIEN_OPT_NO_ROW_DEDUP: off)
-    bool tier2_rows;       // row dedup: the category kernel, the dense / q-side GEMMs and the head GEMM on the active rows too (DESIGN 25;
-                           // RL4RS_DIEN_OPT_NO_TIER2_ROWS: over all R rows).  Decided per forward (rl4rs_dien_forward: tier2)
     int32_t* dd_rep;       // [max_rows] representative of every row group of the last forward
     int32_t* dd_active;    // [max_rows] the representatives in processing order
     int32_t* dd_nact;      // [0] their number, [1] k_row_dedup's workgroup ticket
@@ -1722,7 +1706,7 @@ std::vector<float> pack_frag_h16(const float* w, int ld, int k_off, int K, int N
 
 static int scorer_gemm(rl4rs_dien* n, const float* a, int64_t lda, const float* wp, const float* bias, float* c, int64_t ldc,
                        int M, int N, int K, int act, hipStream_t st) {
-    return n->gemm16 ? launch_gemm_h16(a, lda, wp, bias, c, ldc, M, N, K, act, st)
+    return n->t.gemm16 ? launch_gemm_h16(a, lda, wp, bias, c, ldc, M, N, K, act, st)
                      : launch_gemm_packed(a, lda, wp, bias, c, ldc, M, N, K, act, st);
 }
 
@@ -1806,7 +1790,7 @@ int rl4rs_dien_create(const rl4rs_dien_cfg* c, const rl4rs_dien_weights* w, void
     n->E = E; n->U = U; n->L = L; n->S = S; n->Cn = Cn; n->Dn = Dn; n->H = H; n->K = K; n->F = F;
     n->PLD = PLD; n->NH2 = NH2;
     n->profiling = 0;
-    n->fp16x2 = want_fp16x2;
+    n->t.fp16x2 = want_fp16x2;
     n->row_order = nullptr;
     n->row_order_n = 0;
     // kernel-path selection: fields of the configuration (RL4RS_DIEN_OPT_*), never the process environment - a test or an A/B
@@ -1816,18 +1800,18 @@ int rl4rs_dien_create(const rl4rs_dien_cfg* c, const rl4rs_dien_weights* w, void
     RL4RS_REQUIRE(!((opts & RL4RS_DIEN_OPT_DUP_STORE) && (opts & RL4RS_DIEN_OPT_NO_DUP_STORE)), "dien: dup_store and no_dup_store are exclusive");
     RL4RS_REQUIRE(!((opts & RL4RS_DIEN_OPT_AUGRU_ROWS32) && (opts & RL4RS_DIEN_OPT_AUGRU_ROWS64)),
                   "dien: kernel_opts asks for both the 32-row and the 64-row AUGRU form");
-    n->augru_x = !(opts & RL4RS_DIEN_OPT_AUGRU_H16);
+    n->t.augru_x = !(opts & RL4RS_DIEN_OPT_AUGRU_H16);
     n->augru_rows = (opts & RL4RS_DIEN_OPT_AUGRU_ROWS32) ? 32 : ((opts & RL4RS_DIEN_OPT_AUGRU_ROWS64) ? 64 : 0);
-    n->din16 = false;
-    n->din_x = !(opts & RL4RS_DIEN_OPT_DIN_V1);
-    n->gemm16 = false;
-    n->cat16 = false;
-    n->cat_v2 = !(opts & RL4RS_DIEN_OPT_CAT_V1);
-    n->cat_group = !(opts & RL4RS_DIEN_OPT_NO_CAT_GROUP);
-    n->dense_fork = (opts & RL4RS_DIEN_OPT_DENSE_FORK) != 0;
+    n->t.din16 = false;
+    n->t.din_x = !(opts & RL4RS_DIEN_OPT_DIN_V1);
+    n->t.gemm16 = false;
+    n->t.cat16 = false;
+    n->t.cat_v2 = !(opts & RL4RS_DIEN_OPT_CAT_V1);
+    n->t.cat_group = !(opts & RL4RS_DIEN_OPT_NO_CAT_GROUP);
+    n->t.dense_fork = (opts & RL4RS_DIEN_OPT_DENSE_FORK) != 0;
     n->side_stream = nullptr; n->ev_fork = nullptr; n->ev_join = nullptr;
-    n->dense_chain = !(opts & RL4RS_DIEN_OPT_NO_DENSE_CHAIN);
-    n->gemm_group = !(opts & RL4RS_DIEN_OPT_NO_GEMM_GROUP);
+    n->t.dense_chain = !(opts & RL4RS_DIEN_OPT_NO_DENSE_CHAIN);
+    n->t.gemm_group = !(opts & RL4RS_DIEN_OPT_NO_GEMM_GROUP);
     n->gru16 = false;
     n->gru16_attr = false;
     if (want_fp16x2) {      // the DIN layer-1 split needs |q * h1| <= max |seq_emb| and the q*k rows of att_w1 inside fp16 range
@@ -1847,7 +1831,7 @@ int rl4rs_dien_create(const rl4rs_dien_cfg* c, const rl4rs_dien_weights* w, void
                 const float v = fabsf(w->att_w2[s][i]);
                 fin = fin && v == v; mx = fmaxf(mx, v);
             }
-        n->din16 = fin && mx < 6.0e4f && !(opts & RL4RS_DIEN_OPT_NO_DIN16);
+        n->t.din16 = fin && mx < 6.0e4f && !(opts & RL4RS_DIEN_OPT_NO_DIN16);
         // the first GRU in the same split form: E = 128 only, h-side weights inside fp16 range
         float gmx = 0.f;
         bool gfin = true;
@@ -1877,10 +1861,10 @@ int rl4rs_dien_create(const rl4rs_dien_cfg* c, const rl4rs_dien_weights* w, void
             chk(w->augru_gate_w[s], (size_t)c->emb_size * 4 * c->emb_size);
             chk(w->augru_cand_w[s], (size_t)c->emb_size * 2 * c->emb_size);
         }
-        n->gemm16 = wfin && !(opts & RL4RS_DIEN_OPT_NO_GEMM16);
+        n->t.gemm16 = wfin && !(opts & RL4RS_DIEN_OPT_NO_GEMM16);
         bool cfin = true;
         for (size_t i = 0; i < (size_t)c->category_hash_size * c->emb_size; ++i) cfin = cfin && fabsf(w->cat_emb[i]) < 6.0e4f;
-        n->cat16 = cfin && !(opts & RL4RS_DIEN_OPT_NO_CAT16);
+        n->t.cat16 = cfin && !(opts & RL4RS_DIEN_OPT_NO_CAT16);
     }
     {
         float* f = nullptr;
@@ -1905,7 +1889,7 @@ int rl4rs_dien_create(const rl4rs_dien_cfg* c, const rl4rs_dien_weights* w, void
     UP(seq_emb, w->seq_emb, (size_t)H * E);
     // GEMM weights in the fragment order of the form that will run them (k_gemm_h16 in fp16x2 mode, else k_gemm_pk)
     auto pack_w = [&](const float* src, int64_t ldw, int kk, int nn) {
-        return n->gemm16 ? pack_gemm_weight_h16(src, ldw, kk, nn) : pack_gemm_weight(src, ldw, kk, nn);
+        return n->t.gemm16 ? pack_gemm_weight_h16(src, ldw, kk, nn) : pack_gemm_weight(src, ldw, kk, nn);
     };
     { auto pk = pack_w(w->dense_w1, U, Dn, U); keep.push_back(std::move(pk)); UP(dense_w1, keep.back().data(), keep.back().size()); }
     UP(dense_b1, w->dense_b1, U);
@@ -1961,7 +1945,7 @@ int rl4rs_dien_create(const rl4rs_dien_cfg* c, const rl4rs_dien_weights* w, void
         std::vector<float> sgc(2 * NH2, 1.f), scc(NH2, 1.f);          // per-column view of the tile scales
         for (int g = 0; g < 3; ++g)
             for (int t = 0; t < 8; ++t) n->augru_s[s][g][t] = 1.f;
-        if (n->fp16x2) {
+        if (n->t.fp16x2) {
             RL4RS_REQUIRE(NH2 == 256, "dien: the fp16x2 recurrence is built for 2 * emb_size = 256 hidden units");
             for (int g = 0; g < 3; ++g)
                 for (int t = 0; t < NH2 / 32; ++t) {
@@ -1997,7 +1981,7 @@ int rl4rs_dien_create(const rl4rs_dien_cfg* c, const rl4rs_dien_weights* w, void
         keep.push_back(pack_frag(w1, ATT_H1, 3 * E, E, ATT_H1));
         UP(w1d[s], keep.back().data(), keep.back().size());
         n->w1d16[s] = nullptr;
-        if (n->fp16x2 && n->din16) {
+        if (n->t.din_h16()) {
             keep.push_back(pack_frag_h16(w1, ATT_H1, 3 * E, E, ATT_H1));
             UP(w1d16[s], keep.back().data(), keep.back().size());
         }
@@ -2010,7 +1994,7 @@ int rl4rs_dien_create(const rl4rs_dien_cfg* c, const rl4rs_dien_weights* w, void
         keep.push_back(pack_frag(w->augru_cand_w[s], NH2, E, NH2, NH2));
         UP(augru_wc[s], keep.back().data(), keep.back().size());
         n->augru_wg16[s] = n->augru_wc16[s] = nullptr;
-        if (n->fp16x2) {
+        if (n->t.fp16x2) {
             std::vector<float> hs((size_t)NH2 * 2 * NH2);
             for (size_t i = 0; i < hs.size(); ++i) hs[i] = w->augru_gate_w[s][(size_t)E * 2 * NH2 + i] * sgc[i % (2 * NH2)];
             keep.push_back(pack_frag_h16(hs.data(), 2 * NH2, 0, NH2, 2 * NH2));
@@ -2022,7 +2006,7 @@ int rl4rs_dien_create(const rl4rs_dien_cfg* c, const rl4rs_dien_weights* w, void
         }
         AL(h1[s], ((size_t)c->max_slots + 1) * L * E);                  // (+ 1 everywhere: slot max_slots holds the all-zero sequence)
         n->h1f[s] = nullptr;
-        if (n->fp16x2 && n->din16 && n->din_x && E == 128 && L <= 64) AL(h1f[s], ((size_t)c->max_slots + 1) * ((L + 31) / 32) * 32 * E);
+        if (n->t.din_h16() && n->t.din_x && E == 128 && L <= 64) AL(h1f[s], ((size_t)c->max_slots + 1) * ((L + 31) / 32) * 32 * E);
         AL(proj[s], ((size_t)c->max_slots + 1) * L * PLD);
     }
     keep.push_back(pack_w(wac_all.data(), S * ATT_H1, E, S * ATT_H1));
@@ -2037,7 +2021,8 @@ int rl4rs_dien_create(const rl4rs_dien_cfg* c, const rl4rs_dien_weights* w, void
     AL(scores, (size_t)S * c->max_rows * L);
     AL(obs_tmp, (size_t)c->max_rows * OBS_DIM);
     // row dedup: only where both kernels that read the active list are the selected ones
-    n->row_dedup = !(opts & RL4RS_DIEN_OPT_NO_ROW_DEDUP) && n->fp16x2 && n->augru_x && n->din16 && n->h1f[0] != nullptr;
+    n->t.h1f = n->h1f[0] != nullptr;
+    n->t.row_dedup = !(opts & RL4RS_DIEN_OPT_NO_ROW_DEDUP) && n->t.augru_x && n->t.din_x_selected();
     n->dd_rep = n->dd_active = n->dd_nact = nullptr;
     n->part_rep = n->part_active = n->part_nact = nullptr;
     n->part_groups = 0;
@@ -2046,13 +2031,13 @@ int rl4rs_dien_create(const rl4rs_dien_cfg* c, const rl4rs_dien_weights* w, void
     memset(&n->dd_info, 0, sizeof(n->dd_info));
     n->dedup_launched = n->dedup_carried = 0;
     n->dd_dstart = n->dd_dlist = n->dd_dcur = nullptr;
-    n->dup_store = n->row_dedup && (opts & RL4RS_DIEN_OPT_DUP_STORE) != 0;
-    n->tier2_rows = n->row_dedup && !(opts & RL4RS_DIEN_OPT_NO_TIER2_ROWS);
-    n->din_rows_auto = !(opts & RL4RS_DIEN_OPT_DIN_ROWS16);
-    n->augru_shadow = !(opts & RL4RS_DIEN_OPT_NO_AUGRU_SHADOW);
+    n->t.dup_store = n->t.row_dedup && (opts & RL4RS_DIEN_OPT_DUP_STORE) != 0;
+    n->t.tier2_rows = n->t.row_dedup && !(opts & RL4RS_DIEN_OPT_NO_TIER2_ROWS);
+    n->t.din_rows_auto = !(opts & RL4RS_DIEN_OPT_DIN_ROWS16);
+    n->t.augru_shadow = !(opts & RL4RS_DIEN_OPT_NO_AUGRU_SHADOW);
     n->distinct_hint = 0;
-    n->last_shadow = false;
-    if (n->row_dedup) {
+    n->last_plan = DienPlan{};
+    if (n->t.row_dedup) {
         float* f = nullptr;
         if ((rc = alloc_f(n, &f, (size_t)2 * c->max_rows + 2)) != RL4RS_OK) return rc;
         n->dd_rep = reinterpret_cast<int32_t*>(f);
@@ -2060,7 +2045,7 @@ int rl4rs_dien_create(const rl4rs_dien_cfg* c, const rl4rs_dien_weights* w, void
         n->dd_nact = n->dd_active + c->max_rows;
         RL4RS_HIP_TRY(hipMemsetAsync(f, 0, ((size_t)2 * c->max_rows + 2) * 4, st));
     }
-    if (n->dup_store) {
+    if (n->t.dup_store) {
         float* f = nullptr;
         if ((rc = alloc_f(n, &f, (size_t)3 * c->max_rows + 1)) != RL4RS_OK) return rc;
         n->dd_dlist = reinterpret_cast<int32_t*>(f);
@@ -2070,6 +2055,9 @@ int rl4rs_dien_create(const rl4rs_dien_cfg* c, const rl4rs_dien_weights* w, void
     }
     n->tsum = nullptr;
     if (n->ptab && Cn <= 24 && !(opts & RL4RS_DIEN_OPT_NO_HEAD_FUSED)) AL(tsum, (size_t)c->max_rows * OBS_DIM);
+    n->t.ptab = n->ptab != nullptr; n->t.tsum = n->tsum != nullptr;
+    n->t.E = E; n->t.U = U; n->t.L = L; n->t.S = S; n->t.Cn = Cn; n->t.Dn = Dn; n->t.Fld = n->Fld; n->t.NH2 = NH2;
+    n->t.n_cu = n->n_cu; n->t.max_rows = c->max_rows;
     // first GRU: the states after 1 .. L leading zero ids, per sequence input (RecurArgs::pad) - the kernel itself on ONE all-zero row
     for (int s = 0; s < 4; ++s) { n->gru_pad[s] = nullptr; n->lead[s] = nullptr; }
     if (n->gru16 && !(opts & RL4RS_DIEN_OPT_NO_GRU_PAD)) {
@@ -2193,27 +2181,303 @@ int rl4rs_dien_encode(rl4rs_dien* n, int32_t s, const int32_t* ids, int32_t cnt,
     return RL4RS_OK;
 }
 
-// fp16x2 GEMMs, the dense tower chained, no second stream: the forward issues the dense tower and the q-side term as one launch
-static bool dien_gemm_grouped(const rl4rs_dien* n) {
-    return n->fp16x2 && n->gemm16 && n->gemm_group && n->dense_chain && n->U <= 128 && n->U % 16 == 0 && !n->dense_fork;
+#if defined(RL4RS_DINX_TRACE) || defined(RL4RS_H16_TRACE) || defined(RL4RS_X_TRACE)
+// timing experiments only (tools/dinx_trace.py, x_trace.py, h16_trace.py): a kernel's buffer of `words` 64-bit marks, created on
+// first use; where the environment variable `dump_env` names a file, the marks of the PREVIOUS launch are written there first
+static unsigned long long* trace_marks(unsigned long long** buf, size_t words, const char* dump_env) {
+    if (!*buf) { (void)hipMalloc((void**)buf, words * 8); (void)hipMemset(*buf, 0, words * 8); }
+    if (const char* path = getenv(dump_env)) {
+        std::vector<unsigned long long> host(words);
+        (void)hipDeviceSynchronize();
+        (void)hipMemcpy(host.data(), *buf, words * 8, hipMemcpyDeviceToHost);
+        FILE* f = fopen(path, "wb");
+        if (f) { fwrite(host.data(), 1, words * 8, f); fclose(f); }
+    }
+    return *buf;
+}
+#endif
+
+// ---- rl4rs_dien_forward: the stages.  Each takes the handle, the forward's plan (dien_plan.hpp) and its pointers, owns
+// its profile scope and switches on its plan field - the options were read once, by dien_plan
+struct DienFwd {
+    int R, group, n_groups;
+    const float* dense; const int32_t* cat; const int32_t* slots;
+    float* obs_out; float* prob;
+    const int32_t* order_in;                    // the caller's processing order of the row groups, or NULL
+    const int32_t *rep, *active, *nact;         // the duplicate row groups: the handle's own partition (k_row_dedup) or the caller's
+    G16RowMap rmap; const G16RowMap* map2;      // the active-row map; the same for the launches of the second tier (NULL: tier off)
+    hipStream_t st;
+};
+
+static int dense_tower(rl4rs_dien* n, const DienPlan& p, const DienFwd& f, hipStream_t s2) {
+    const int U = n->U, F = n->Fld, off_d = n->S * n->NH2;
+    if (p.dense == PlanDense::Chain)      // both layers in one launch, the hidden tile stays in LDS
+        return launch_gemm_h16_chain(f.dense, n->Dn, n->dense_w1, n->dense_b1, U, n->Dn, 1, n->dense_w2, n->dense_b2,
+                                     n->allf + off_d, F, U, 1, f.R, s2, f.map2);
+    int rc = scorer_gemm(n, f.dense, n->Dn, n->dense_w1, n->dense_b1, n->dh, U, f.R, U, n->Dn, 1, s2);
+    if (rc) return rc;
+    return scorer_gemm(n, n->dh, U, n->dense_w2, n->dense_b2, n->allf + off_d, F, f.R, U, U, 1, s2);
 }
 
-// k_augru_x: 64-row workgroups when the rows come in whole groups of 8 per cache slot (the reward forward), or in groups of 9 (the
-// reward forward that also scores the state row: 7 groups = 63 rows per workgroup), and there are enough workgroups to fill the chip
-// twice over; 32-row workgroups otherwise (obs-sized launches: one 32-row tile per CU)
-// (n->augru_rows = 32 / 64 pins the form: rl4rs_dien_cfg.kernel_opts, rl4rs_dien_set_augru_rows)
-static bool augru_rows64(const rl4rs_dien* n, int R, int group) {
-    if (n->augru_rows == 32) return false;
-    int64_t tiles;
-    if (group == 9) tiles = (R / 9 + 6) / 7;
-    else if (group % 8 == 0 && R % 64 == 0) tiles = R / 64;
-    else return false;
-    return n->augru_rows == 64 || tiles * n->S >= 2 * (int64_t)n->n_cu;
+// RL4RS_DIEN_OPT_DENSE_FORK: the dense tower reads only `dense` and writes its own columns of allf - it runs on a second stream
+// of the handle from the top of the forward and is joined in front of the head GEMM (event pair owned by the handle)
+static int stage_dense_fork(rl4rs_dien* n, const DienPlan& p, const DienFwd& f) {
+    if (!n->side_stream) {
+        RL4RS_HIP_TRY(hipStreamCreateWithFlags(&n->side_stream, hipStreamNonBlocking));
+        RL4RS_HIP_TRY(hipEventCreateWithFlags(&n->ev_fork, hipEventDisableTiming));
+        RL4RS_HIP_TRY(hipEventCreateWithFlags(&n->ev_join, hipEventDisableTiming));
+    }
+    RL4RS_HIP_TRY(hipEventRecord(n->ev_fork, f.st));                     // (the inputs - and the previous forward's readers of allf - are ordered before this point)
+    RL4RS_HIP_TRY(hipStreamWaitEvent(n->side_stream, n->ev_fork, 0));
+    int rc = dense_tower(n, p, f, n->side_stream);
+    if (rc) return rc;
+    RL4RS_HIP_TRY(hipEventRecord(n->ev_join, n->side_stream));
+    return RL4RS_OK;
 }
 
-// the shadow plane's dense tile addresses `dense` and allf through one buffer descriptor each (as k_gemm_h16_map does)
-static bool g16_shadow_fits(int R, int Dn, int F, int U) {
-    return ((int64_t)R - 1) * Dn + Dn < ((int64_t)1 << 29) && ((int64_t)R - 1) * F + U < ((int64_t)1 << 29);
+// duplicate row groups of this forward (row_dedup.hpp): k_din_x and k_augru_x then work on the representatives only
+static int stage_dedup(rl4rs_dien* n, const DienPlan& p, const DienFwd& f) {
+    if (p.dedup == PlanDedup::None) return RL4RS_OK;
+    const bool carried = p.dedup == PlanDedup::Carried;
+    n->last_rep = f.rep; n->last_active = f.active; n->last_nact = f.nact; n->last_groups = carried ? f.n_groups : n->c.max_rows;
+    Prof pr(n, KID_DEDUP, f.st);
+    if (carried) {      // nothing is compared: the class keeps one (empty) entry for the launch it did not issue
+        n->dedup_carried += 1;
+        return RL4RS_OK;
+    }
+    RowDedupArgs a;
+    memset(&a, 0, sizeof(a));
+    a.n_groups = f.n_groups; a.group = f.group; a.Cn = n->Cn; a.Dn = n->Dn; a.S = n->S;
+    a.slots = f.slots; a.slots_stride = f.n_groups; a.cat = f.cat; a.dense = f.dense; a.order = f.order_in;
+    a.rep = n->dd_rep; a.active = n->dd_active; a.n_active = n->dd_nact;
+    if (p.dup_lists) { a.dup_start = n->dd_dstart; a.dup_list = n->dd_dlist; a.dup_cur = n->dd_dcur; }
+    constexpr int per_wg = ROW_DEDUP_THREADS / 64;
+    hipLaunchKernelGGL(k_row_dedup, dim3((f.n_groups + per_wg - 1) / per_wg), dim3(ROW_DEDUP_THREADS), 0, f.st, a);
+    RL4RS_LAUNCH_CHECK();
+    n->dedup_launched += 1;
+    n->dd_info = DienPartition{next_stamp(), f.n_groups, f.group, f.dense, f.cat, f.slots, f.order_in, n->dd_rep, n->dd_active, n->dd_nact};
+    return RL4RS_OK;
+}
+
+// PlanCat::Shadow (and PlanDense::Shadow below): the category branch and the dense tower are part of the AUGRU launch, the q-side
+// term of k_din_xq - their profile classes keep one (empty) entry per forward, so that a class still counts the forwards it took part in
+static int stage_cat(rl4rs_dien* n, const DienPlan& p, const DienFwd& f) {
+    Prof pr(n, KID_CAT, f.st);
+    const int E = n->E, Cn = n->Cn, F = n->Fld, R = f.R, off_c = n->S * n->NH2 + n->U;
+    const int flat = n->ptab ? 0 : 1, h16 = p.cat_h16 ? 1 : 0;
+    const int32_t* const t2_order = p.tier2 ? f.active : nullptr;
+    switch (p.cat) {
+        case PlanCat::Shadow: return RL4RS_OK;
+        // rows in groups that (normally) share all but the last category id: one workgroup per group, shared gathers once
+        case PlanCat::G8:
+            hipLaunchKernelGGL((k_cat_attn2g<8, 8>), dim3(f.n_groups), dim3(512), cat_attn2g_smem(8, Cn), f.st, f.cat, Cn, n->H, n->cat_emb, n->seq_emb,
+                               n->allf, F, off_c, n->q, flat, h16, n->ptab, n->obs_b, n->tsum, t2_order, f.nact);
+            break;
+        case PlanCat::G9:
+            hipLaunchKernelGGL((k_cat_attn2g<9, RL4RS_CAT9_WAVES>), dim3(f.n_groups), dim3(64 * RL4RS_CAT9_WAVES), cat_attn2g_smem(9, Cn), f.st, f.cat, Cn,
+                               n->H, n->cat_emb, n->seq_emb, n->allf, F, off_c, n->q, flat, h16, n->ptab, n->obs_b, n->tsum, t2_order, f.nact);
+            break;
+        case PlanCat::V2_21:
+            hipLaunchKernelGGL((k_cat_attn2<21, true>), dim3((R + 3) / 4), dim3(256), (size_t)4 * (Cn * (64 + 4) + 32) * 4, f.st, f.cat, R, Cn, n->H,
+                               n->cat_emb, n->seq_emb, n->allf, F, off_c, n->q, flat, h16, n->ptab, n->obs_b, n->tsum, t2_order, f.nact, f.group);
+            break;
+        case PlanCat::V2_24:
+            hipLaunchKernelGGL((k_cat_attn2<24, false>), dim3((R + 3) / 4), dim3(256), (size_t)4 * (Cn * (64 + 4) + 32) * 4, f.st, f.cat, R, Cn, n->H,
+                               n->cat_emb, n->seq_emb, n->allf, F, off_c, n->q, flat, h16, n->ptab, n->obs_b, n->tsum, t2_order, f.nact, f.group);
+            break;
+        case PlanCat::V1:
+            hipLaunchKernelGGL(k_cat_attn, dim3((R + 3) / 4), dim3(256), (size_t)4 * (Cn * (E + 4) + 32) * 4, f.st, f.cat, R, Cn, E, n->H,
+                               n->cat_emb, n->seq_emb, n->allf, F, off_c, n->q, flat, h16, n->ptab, n->obs_b, n->tsum);
+            break;
+    }
+    RL4RS_LAUNCH_CHECK();
+    return RL4RS_OK;
+}
+
+// PlanDense::Pair: the dense tower and the q-side term of the DIN scores (qa = q W1ac_all, q written by the category kernel) are
+// independent and, at observation size, half-chip grids of the same kernel: one launch for both (launch_gemm_h16_pair)
+static int stage_dense(rl4rs_dien* n, const DienPlan& p, const DienFwd& f) {
+    if (p.dense_side) return RL4RS_OK;       // issued by stage_dense_fork
+    Prof pr(n, KID_DENSE, f.st);
+    if (p.dense == PlanDense::Shadow) return RL4RS_OK;
+    if (p.dense != PlanDense::Pair) return dense_tower(n, p, f, f.st);
+    const int E = n->E, U = n->U, S = n->S;
+    GemmH16Desc dt, qs;
+    memset(&dt, 0, sizeof(dt));
+    memset(&qs, 0, sizeof(qs));
+    dt.a = f.dense; dt.lda = n->Dn; dt.wp = n->dense_w1; dt.bias = n->dense_b1; dt.M = f.R; dt.N = U; dt.K = n->Dn; dt.act = 1;
+    dt.wp2 = n->dense_w2; dt.bias2 = n->dense_b2; dt.c2 = n->allf + S * n->NH2; dt.ldc2 = n->Fld; dt.N2 = U; dt.act2 = 1;
+    qs.a = n->q; qs.lda = E; qs.wp = n->w1ac_all; qs.c = n->qa; qs.ldc = S * ATT_H1; qs.M = f.R; qs.N = S * ATT_H1; qs.K = E; qs.act = 0;
+    return launch_gemm_h16_pair(dt, qs, f.st, f.map2);
+}
+
+// the q-side term where no earlier launch formed it, then the DIN scores
+static int stage_din(rl4rs_dien* n, const DienPlan& p, const DienFwd& f) {
+    Prof pr(n, KID_DIN, f.st);
+    const int E = n->E, L = n->L, S = n->S, R = f.R;
+    int rc = RL4RS_OK;
+    if (p.qside == PlanQside::MappedH16)
+        rc = launch_gemm_h16(n->q, E, n->w1ac_all, nullptr, n->qa, S * ATT_H1, R, S * ATT_H1, E, 0, f.st, nullptr, 0, nullptr, 0, f.map2);
+    else if (p.qside == PlanQside::ScorerGemm)
+        rc = scorer_gemm(n, n->q, E, n->w1ac_all, nullptr, n->qa, S * ATT_H1, R, S * ATT_H1, E, 0, f.st);
+    if (rc) return rc;
+    DinArgs a;
+    memset(&a, 0, sizeof(a));
+    a.R = R; a.L = L; a.E = E; a.group = f.group; a.n_groups = f.n_groups;
+    a.slots = f.slots; a.slots_stride = f.n_groups; a.pld = n->PLD; a.q = n->q;
+    a.qa = n->qa; a.qa_stride = ATT_H1; a.qa_ld = S * ATT_H1;       // one GEMM for the q-side term of every input: [R, S*64]
+    for (int s = 0; s < S; ++s) {
+        a.h1[s] = n->h1[s]; a.h1f[s] = n->h1f[s]; a.proj[s] = n->proj[s]; a.w1ac[s] = n->w1ac[s]; a.w1d[s] = n->w1d[s]; a.w1d16[s] = n->w1d16[s];
+        a.w2[s] = n->att_w2[s]; a.b2[s] = n->att_b2[s]; a.w3[s] = n->att_w3[s]; a.b3[s] = n->att_b3[s];
+        a.lead[s] = n->lead[s];
+    }
+    a.scores = n->scores; a.scores_stride = (int64_t)n->c.max_rows * L;
+    a.order = f.order_in;
+    if (p.dedup != PlanDedup::None) { a.order = f.active; a.n_active = f.nact; }
+    if (p.dup_lists) { a.dup_start = n->dd_dstart; a.dup_list = n->dd_dlist; }
+    a.pad_slot = n->c.max_slots;
+#ifdef RL4RS_DINX_TRACE
+    static unsigned long long* din_trace = nullptr;
+    a.trace = trace_marks(&din_trace, 8 * 5 * 8, "RL4RS_DINX_TRACE_DUMP");
+#endif
+    switch (p.din) {
+        case PlanDin::Xq: {
+            const DinQArgs qx = {f.cat, n->Cn, n->H, n->seq_emb, reinterpret_cast<const char*>(n->w1ac_all), n->q, n->qa};
+            hipLaunchKernelGGL(k_din_xq, dim3((R + 7) / 8, S), dim3(512), din_x_smem(), f.st, a, 16, n->n_cu, qx);
+            break;
+        }
+        // 16 rows per 8-wave workgroup: an obs-sized launch (R = 4096, two inputs) is two workgroups per CU, one round.
+        // XAuto (group == 1): the grid is sized for 8 and the kernel picks 8 or 16 from the rows the dedup left (din_x.hpp)
+        case PlanDin::XAuto: hipLaunchKernelGGL(k_din_x, dim3((R + 7) / 8, S), dim3(512), din_x_smem(), f.st, a, 16, n->n_cu); break;
+        case PlanDin::X16: hipLaunchKernelGGL(k_din_x, dim3((R + 15) / 16, S), dim3(512), din_x_smem(), f.st, a, 16, 0); break;
+        case PlanDin::Scores: {
+            const int nw = p.din_waves;
+            const size_t smem = ((size_t)(p.din_stage ? L * (E + 4) : 0) + 2 * 16 * 64 + 48 + (size_t)nw * (E + ATT_H1)) * 4;
+            const dim3 grid(p.din_stage ? f.n_groups : (R + nw - 1) / nw, S), block(64 * nw);
+            if (p.din_stage && p.din_h16) hipLaunchKernelGGL((k_din_scores<true, true>), grid, block, smem, f.st, a);
+            else if (p.din_stage) hipLaunchKernelGGL((k_din_scores<true, false>), grid, block, smem, f.st, a);
+            else if (p.din_h16) hipLaunchKernelGGL((k_din_scores<false, true>), grid, block, smem, f.st, a);
+            else hipLaunchKernelGGL((k_din_scores<false, false>), grid, block, smem, f.st, a);
+            break;
+        }
+    }
+    RL4RS_LAUNCH_CHECK();
+    return RL4RS_OK;
+}
+
+static int stage_augru(rl4rs_dien* n, const DienPlan& p, const DienFwd& f) {
+    Prof pr(n, KID_AUGRU, f.st);
+    const int U = n->U, L = n->L, S = n->S, F = n->Fld, NH2 = n->NH2, R = f.R;
+    RecurArgs a;
+    memset(&a, 0, sizeof(a));
+    a.n_rows = R; a.L = L; a.group = f.group;
+    a.xld = n->PLD; a.xoff = ATT_H1; a.xbytes = ((int64_t)n->c.max_slots + 1) * L * n->PLD * 4;
+    a.ids = nullptr; a.slots = f.slots; a.slots_stride = f.n_groups;
+    for (int s = 0; s < S; ++s) a.lead[s] = n->lead[s];
+    a.pad_slot = n->c.max_slots;
+    for (int s = 0; s < S; ++s) { a.xbase[s] = n->proj[s]; a.wg[s] = n->augru_wg[s]; a.wc[s] = n->augru_wc[s]; }
+    a.att = n->scores; a.att_stride = (int64_t)n->c.max_rows * L;
+    a.out = n->allf; a.out_ld = F; a.out_off = 0; a.out_seq_off = NH2; a.slot_base = 0;
+    const dim3 grid((R + 31) / 32, S), block(512);
+    if (p.augru == PlanAugru::Recur32) {
+        const size_t smem = (size_t)(2 * 32 * (NH2 + 4) + 32 * (L + 1) + 32) * 4;
+#ifdef RL4RS_ABLATE      // timing experiments only (tools/ablate_augru.sh builds with -DRL4RS_ABLATE)
+        static const int ablate = getenv("RL4RS_AUGRU_ABLATE") ? atoi(getenv("RL4RS_AUGRU_ABLATE")) : 0;
+        switch (ablate) {
+            case 1: hipLaunchKernelGGL((k_recur<256, true, AUGRU_U, 1>), grid, block, smem, f.st, a); break;
+            case 2: hipLaunchKernelGGL((k_recur<256, true, AUGRU_U, 2>), grid, block, smem, f.st, a); break;
+            case 4: hipLaunchKernelGGL((k_recur<256, true, AUGRU_U, 4>), grid, block, smem, f.st, a); break;
+            case 8: hipLaunchKernelGGL((k_recur<256, true, AUGRU_U, 8>), grid, block, smem, f.st, a); break;
+            case 15: hipLaunchKernelGGL((k_recur<256, true, AUGRU_U, 15>), grid, block, smem, f.st, a); break;
+            default: hipLaunchKernelGGL((k_recur<256, true, AUGRU_U, 0>), grid, block, smem, f.st, a); break;
+        }
+#else
+        hipLaunchKernelGGL((k_recur<256, true, AUGRU_U, 0>), grid, block, smem, f.st, a);
+#endif
+        RL4RS_LAUNCH_CHECK();
+        return RL4RS_OK;
+    }
+    for (int s = 0; s < S; ++s) { a.wg[s] = n->augru_wg16[s]; a.wc[s] = n->augru_wc16[s]; }
+    a.range_flag = n->range_flag;
+    for (int s = 0; s < S; ++s)
+        for (int t = 0; t < 8; ++t) {
+            a.k_r[s][t] = -1.4426950408889634f / n->augru_s[s][0][t];
+            a.k_u[s][t] = -1.4426950408889634f / n->augru_s[s][1][t];
+            a.k_c[s][t] = 2.8853900817779268f / n->augru_s[s][2][t];
+        }
+    a.order = p.augru == PlanAugru::H16 ? nullptr : f.order_in;
+    if (p.dedup != PlanDedup::None) { a.order = f.active; a.n_active = f.nact; }
+    if (p.dup_lists) { a.dup_start = n->dd_dstart; a.dup_list = n->dd_dlist; }
+    a.steps = 0;
+#if defined(RL4RS_H16_TRACE) || defined(RL4RS_X_TRACE)
+    static unsigned long long* trace_buf = nullptr;
+    a.trace = trace_marks(&trace_buf, 8 * 4 * 8, "RL4RS_H16_TRACE_DUMP");
+#endif
+    switch (p.augru) {
+        case PlanAugru::Xs: {
+            AugruShadowArgs sh;
+            memset(&sh, 0, sizeof(sh));
+            sh.cat = f.cat; sh.Cn = n->Cn; sh.H = n->H; sh.cat_emb = n->cat_emb; sh.seq_emb = n->seq_emb; sh.allf = n->allf; sh.ldf = F; sh.off_c = S * NH2 + U;
+            sh.q = n->q; sh.write_flat = n->ptab ? 0 : 1; sh.h16 = p.cat_h16 ? 1 : 0; sh.ptab = n->ptab; sh.obs_b = n->obs_b; sh.tsum = n->tsum;
+            sh.dense = f.dense; sh.lda = n->Dn; sh.w1 = reinterpret_cast<const char*>(n->dense_w1); sh.kb1 = (n->Dn + 15) / 16; sh.b1 = n->dense_b1;
+            sh.N1 = U; sh.K1 = n->Dn; sh.act1 = 1;
+            sh.vec = p.dense_vec ? 1 : 0;
+            sh.chain = G16Chain{reinterpret_cast<const char*>(n->dense_w2), (U + 15) / 16, n->dense_b2, n->allf + S * NH2, F, U, 1, nullptr, 0};
+            sh.R = R; sh.rmap = f.rmap;
+            augru_xs_launch(S, f.st, a, sh);
+            break;
+        }
+        case PlanAugru::X32: augru_x_launch(32, S, f.st, a); break;
+        case PlanAugru::X64: augru_x_launch(64, S, f.st, a); break;
+        default: hipLaunchKernelGGL((k_augru_h16<1, RL4RS_H16_RING1, RL4RS_H16_NRES>), grid, block, augru_h16_smem(1, NH2, L), f.st, a); break;
+    }
+    RL4RS_LAUNCH_CHECK();
+    return RL4RS_OK;
+}
+
+// the duplicates' rows (PlanExpand::Front / Behind the head GEMM: dien_plan)
+static int stage_expand(rl4rs_dien* n, const DienPlan& p, const DienFwd& f) {
+    Prof pr(n, KID_DEDUP, f.st);
+    RowExpandArgs a;
+    memset(&a, 0, sizeof(a));
+    a.R = f.R; a.group = f.group; a.n_groups = f.n_groups; a.S = n->S; a.L = n->L; a.ncol = p.expand_ncol;
+    a.rep = f.rep; a.n_active = f.nact;
+    a.allf = n->allf; a.ld = n->Fld; a.scores = n->scores; a.scores_stride = (int64_t)n->c.max_rows * n->L;
+    if (p.expand == PlanExpand::Behind) { a.q = n->q; a.E = n->E; a.obs = f.obs_out; a.obs_dim = OBS_DIM; }
+    hipLaunchKernelGGL(k_row_expand, dim3((f.R + 3) / 4), dim3(256), 0, f.st, a);
+    RL4RS_LAUNCH_CHECK();
+    return RL4RS_OK;
+}
+
+static int stage_head(rl4rs_dien* n, const DienPlan& p, const DienFwd& f) {
+    Prof pr(n, KID_HEAD, f.st);
+    const int F = n->Fld, R = f.R, Kh = n->S * n->NH2 + n->U + n->E;
+    int rc;
+    switch (p.head) {
+        case PlanHead::TsumH16:          // obs = ELU(allf W + [b + table rows]): the addend was built inside the category kernel
+        case PlanHead::TsumH16Mirror: {
+            float* const mirror = p.head == PlanHead::TsumH16Mirror ? n->obs_mirror : nullptr;
+            rc = launch_gemm_h16(n->allf, F, n->obs_w, nullptr, f.obs_out, OBS_DIM, R, OBS_DIM, Kh, 1, f.st, n->tsum, OBS_DIM, mirror, OBS_DIM, f.map2);
+            n->obs_mirror_used = mirror != nullptr;
+            return rc;
+        }
+        case PlanHead::TsumPacked:
+            return launch_gemm_packed(n->allf, F, n->obs_w, nullptr, f.obs_out, OBS_DIM, R, OBS_DIM, Kh, 1, f.st, n->tsum, OBS_DIM);
+        case PlanHead::TablesFinish:
+            if ((rc = scorer_gemm(n, n->allf, F, n->obs_w, nullptr, f.obs_out, OBS_DIM, R, OBS_DIM, Kh, 0, f.st))) return rc;
+            hipLaunchKernelGGL(k_head_finish, dim3((R + 3) / 4), dim3(256), 0, f.st, f.obs_out, R, f.cat, n->Cn, n->H, n->ptab, n->obs_b);
+            RL4RS_LAUNCH_CHECK();
+            return RL4RS_OK;
+        case PlanHead::Plain: break;
+    }
+    return scorer_gemm(n, n->allf, F, n->obs_w, n->obs_b, f.obs_out, OBS_DIM, R, OBS_DIM, n->F, 1, f.st);
+}
+
+static int stage_prob(rl4rs_dien* n, const DienFwd& f) {
+    Prof pr(n, KID_PROB, f.st);
+    hipLaunchKernelGGL(k_head_prob, dim3((f.R + 3) / 4), dim3(256), 0, f.st, f.obs_out, f.R, OBS_DIM, n->K, n->out_w, n->out_b, f.prob, f.group, n->obs_last);
+    RL4RS_LAUNCH_CHECK();
+    return RL4RS_OK;
 }
 
 int rl4rs_dien_forward(rl4rs_dien* n, int32_t R, int32_t group, const float* dense, const int32_t* cat,
@@ -2221,317 +2485,43 @@ int rl4rs_dien_forward(rl4rs_dien* n, int32_t R, int32_t group, const float* den
     RL4RS_REQUIRE(n && dense && cat && slots, "dien_forward: null argument");
     RL4RS_REQUIRE(R > 0 && R <= n->c.max_rows, "dien_forward: R=%d exceeds max_rows=%d", R, n->c.max_rows);
     RL4RS_REQUIRE(group >= 1 && R % group == 0, "dien_forward: R=%d is not a multiple of group=%d", R, group);
-    hipStream_t st = (hipStream_t)stream;
-    const int E = n->E, U = n->U, L = n->L, S = n->S, Cn = n->Cn, F = n->Fld, NH2 = n->NH2;
-    const int off_d = S * NH2, off_c = off_d + U;
     const int ngroups = R / group;
-    int rc;
     n->obs_mirror_used = false;
     struct MirrorOnce { rl4rs_dien* n; ~MirrorOnce() { n->obs_mirror = nullptr; n->obs_last = nullptr; n->part_rep = nullptr; } } mirror_once{n};       // one forward only
+    DienCall c{};
+    c.R = R; c.group = group; c.obs = obs != nullptr; c.prob = prob != nullptr;
+    c.mirror = n->obs_mirror != nullptr; c.obs_last = n->obs_last != nullptr;
     // rl4rs_dien_set_row_partition: the duplicate row groups of this forward are the caller's, nothing is compared
-    const bool carried = n->part_rep != nullptr;
-    RL4RS_REQUIRE(!carried || (n->row_dedup && !n->dup_store && n->part_groups == ngroups),
+    c.carried = n->part_rep != nullptr; c.part_groups = n->part_groups;
+    c.row_order = n->row_order && n->row_order_n == ngroups;
+    c.augru_rows = n->augru_rows; c.distinct_hint = n->distinct_hint;
+    c.dense_vec = (n->Dn & 3) == 0 && (reinterpret_cast<uintptr_t>(dense) & 15) == 0;
+    RL4RS_REQUIRE(!c.carried || (dien_takes_partition(n) && c.part_groups == ngroups),
                   "dien_forward: the row partition set for this forward is for %d groups with the row dedup on (forward: %d groups)", n->part_groups, ngroups);
-    const int32_t* const p_rep = carried ? n->part_rep : n->dd_rep;
-    const int32_t* const p_active = carried ? n->part_active : n->dd_active;
-    const int32_t* const p_nact = carried ? n->part_nact : n->dd_nact;
-    RL4RS_REQUIRE(!n->obs_last || prob, "dien_forward: rl4rs_dien_set_obs_last needs a forward that returns probabilities");
-    // Second tier on the active rows only: with the row dedup on, the category kernel, the dense tower, the q-side term
-    // and the head GEMM take the active list too and k_row_expand, behind the head GEMM, gives a duplicate everything it lacks.
-    // Only in the default forms of those launches, and never with the head's host mirror armed, dup_store or dense_fork:
-    // everywhere else the forward issues the launches it issued before (as with RL4RS_DIEN_OPT_NO_TIER2_ROWS)
-    const bool tier2 = n->row_dedup && n->tier2_rows && !n->dup_store && !n->dense_fork && !(obs && n->obs_mirror) &&
-                       n->gemm16 && n->ptab && n->tsum && n->cat_v2 && E == 128 && Cn <= 24 && n->dense_chain && U <= 128 && U % 16 == 0;
-    // Shadow-plane order of an observation-sized forward: k_din_xq forms q and qa for its own rows, the category branch and
-    // the dense tower run on the CUs the 32-row AUGRU launch leaves idle (k_augru_xs) - k_row_dedup, k_din_xq, k_augru_xs, head GEMM,
-    // k_row_expand.  Only on top of the second tier above, in the default forms of every launch involved, and only where the
-    // expected tiles * (S + 1) workgroups (one per CU: the launch's dynamic LDS) fit the chip; everywhere else - the reward forward,
-    // a handle without a useful hint, every non-default option - the forward issues what it issued before
-    const int hint_groups = n->distinct_hint > 0 && n->distinct_hint < ngroups ? n->distinct_hint : ngroups;
-    const bool shadow = tier2 && n->augru_shadow && group == 1 && Cn == 21 && S <= 2 && n->fp16x2 && n->augru_x && n->din16 && n->h1f[0] &&
-                        n->din_x && n->din_rows_auto && n->gemm_group && !augru_rows64(n, R, group) && n->augru_rows != 64 &&
-                        dien_gemm_grouped(n) && (int64_t)((hint_groups + 31) / 32) * (S + 1) <= n->n_cu &&
-                        g16_shadow_fits(R, n->Dn, F, U);
-    const G16RowMap rmap = {p_active, p_nact, group};
-    const G16RowMap* const map2 = tier2 ? &rmap : nullptr;
-    const int32_t* const t2_order = tier2 ? p_active : nullptr;
-    auto dense_tower = [&](hipStream_t s2) -> int {
-        int r2;
-        if (n->gemm16 && n->dense_chain && U <= 128 && U % 16 == 0) {      // both layers in one launch, the hidden tile stays in LDS
-            if ((r2 = launch_gemm_h16_chain(dense, n->Dn, n->dense_w1, n->dense_b1, U, n->Dn, 1, n->dense_w2, n->dense_b2,
-                                            n->allf + off_d, F, U, 1, R, s2, map2))) return r2;
-        } else {
-            if ((r2 = scorer_gemm(n, dense, n->Dn, n->dense_w1, n->dense_b1, n->dh, U, R, U, n->Dn, 1, s2))) return r2;
-            if ((r2 = scorer_gemm(n, n->dh, U, n->dense_w2, n->dense_b2, n->allf + off_d, F, R, U, U, 1, s2))) return r2;
-        }
-        return RL4RS_OK;
-    };
-    // RL4RS_DIEN_OPT_DENSE_FORK: the dense tower reads only `dense` and writes its own columns of allf - it runs on a second stream
-    // of the handle from the top of the forward and is joined in front of the head GEMM (event pair owned by the handle)
-    bool forked = false;
-    if (n->dense_fork) {
-        if (!n->side_stream) {
-            RL4RS_HIP_TRY(hipStreamCreateWithFlags(&n->side_stream, hipStreamNonBlocking));
-            RL4RS_HIP_TRY(hipEventCreateWithFlags(&n->ev_fork, hipEventDisableTiming));
-            RL4RS_HIP_TRY(hipEventCreateWithFlags(&n->ev_join, hipEventDisableTiming));
-        }
-        RL4RS_HIP_TRY(hipEventRecord(n->ev_fork, st));                       // (the inputs - and the previous forward's readers of allf - are ordered before this point)
-        RL4RS_HIP_TRY(hipStreamWaitEvent(n->side_stream, n->ev_fork, 0));
-        if ((rc = dense_tower(n->side_stream))) return rc;
-        RL4RS_HIP_TRY(hipEventRecord(n->ev_join, n->side_stream));
-        forked = true;
-    }
-    // duplicate row groups of this forward (row_dedup.hpp): k_din_x and k_augru_x then work on the representatives only
-    const int32_t* order_in = (n->row_order && n->row_order_n == ngroups) ? n->row_order : nullptr;
-    const bool dedup = n->row_dedup;
-    if (dedup) {
-        n->last_rep = p_rep; n->last_active = p_active; n->last_nact = p_nact; n->last_groups = carried ? ngroups : n->c.max_rows;
-    }
-    if (carried) {
-        { Prof p(n, KID_DEDUP, st); }       // the class keeps one (empty) entry for the launch it did not issue
-        n->dedup_carried += 1;
-    } else if (dedup) {
-        Prof p(n, KID_DEDUP, st);
-        RowDedupArgs a;
-        memset(&a, 0, sizeof(a));
-        a.n_groups = ngroups; a.group = group; a.Cn = Cn; a.Dn = n->Dn; a.S = S;
-        a.slots = slots; a.slots_stride = ngroups; a.cat = cat; a.dense = dense; a.order = order_in;
-        a.rep = n->dd_rep; a.active = n->dd_active; a.n_active = n->dd_nact;
-        if (n->dup_store) { a.dup_start = n->dd_dstart; a.dup_list = n->dd_dlist; a.dup_cur = n->dd_dcur; }
-        constexpr int per_wg = ROW_DEDUP_THREADS / 64;
-        hipLaunchKernelGGL(k_row_dedup, dim3((ngroups + per_wg - 1) / per_wg), dim3(ROW_DEDUP_THREADS), 0, st, a);
-        RL4RS_LAUNCH_CHECK();
-        n->dedup_launched += 1;
-        n->dd_info = DienPartition{next_stamp(), ngroups, group, dense, cat, slots, order_in, n->dd_rep, n->dd_active, n->dd_nact};
-    }
-    n->last_shadow = shadow;
-    if (shadow) {
-        // the category branch and the dense tower are part of the AUGRU launch below, the q-side term of k_din_xq: their profile
-        // classes keep one (empty) entry per forward, so that a class still counts the forwards it took part in
-        { Prof p(n, KID_CAT, st); }
-        { Prof p(n, KID_DENSE, st); }
-    } else {
-        Prof p(n, KID_CAT, st);
-        if (n->cat_v2 && n->cat_group && E == 128 && Cn >= 11 && Cn <= 24 && (group == 8 || group == 9)) {
-            // rows in groups that (normally) share all but the last category id: one workgroup per group, shared gathers once
-            const size_t smem = cat_attn2g_smem(group, Cn);
-            if (group == 8)
-                hipLaunchKernelGGL((k_cat_attn2g<8, 8>), dim3(ngroups), dim3(512), smem, st, cat, Cn, n->H, n->cat_emb, n->seq_emb, n->allf, F,
-                                   off_c, n->q, n->ptab ? 0 : 1, (n->fp16x2 && n->cat16) ? 1 : 0, n->ptab, n->obs_b, n->tsum, t2_order, p_nact);
-            else
-                hipLaunchKernelGGL((k_cat_attn2g<9, RL4RS_CAT9_WAVES>), dim3(ngroups), dim3(64 * RL4RS_CAT9_WAVES), smem, st, cat, Cn, n->H, n->cat_emb, n->seq_emb, n->allf, F,
-                                   off_c, n->q, n->ptab ? 0 : 1, (n->fp16x2 && n->cat16) ? 1 : 0, n->ptab, n->obs_b, n->tsum, t2_order, p_nact);
-        } else if (n->cat_v2 && E == 128 && Cn <= 24) {
-            size_t smem = (size_t)4 * (Cn * (64 + 4) + 32) * 4;
-            if (Cn == 21)
-                hipLaunchKernelGGL((k_cat_attn2<21, true>), dim3((R + 3) / 4), dim3(256), smem, st, cat, R, Cn, n->H, n->cat_emb,
-                                   n->seq_emb, n->allf, F, off_c, n->q, n->ptab ? 0 : 1, (n->fp16x2 && n->cat16) ? 1 : 0,
-                                   n->ptab, n->obs_b, n->tsum, t2_order, p_nact, group);
-            else
-                hipLaunchKernelGGL((k_cat_attn2<24, false>), dim3((R + 3) / 4), dim3(256), smem, st, cat, R, Cn, n->H, n->cat_emb,
-                                   n->seq_emb, n->allf, F, off_c, n->q, n->ptab ? 0 : 1, (n->fp16x2 && n->cat16) ? 1 : 0,
-                                   n->ptab, n->obs_b, n->tsum, t2_order, p_nact, group);
-        } else {
-            size_t smem = (size_t)4 * (Cn * (E + 4) + 32) * 4;
-            hipLaunchKernelGGL(k_cat_attn, dim3((R + 3) / 4), dim3(256), smem, st, cat, R, Cn, E, n->H, n->cat_emb,
-                               n->seq_emb, n->allf, F, off_c, n->q, n->ptab ? 0 : 1, (n->fp16x2 && n->cat16) ? 1 : 0,
-                               n->ptab, n->obs_b, n->tsum);
-        }
-        RL4RS_LAUNCH_CHECK();
-    }
-    // The dense tower and the q-side term of the DIN scores (qa = q W1ac_all, q written by the category kernel above) are
-    // independent and, at observation size, half-chip grids of the same kernel: one launch for both (launch_gemm_h16_pair)
-    const bool grouped = dien_gemm_grouped(n) && !forked;
-    if (shadow) {
-    } else if (grouped) {
-        Prof p(n, KID_DENSE, st);
-        GemmH16Desc dt, qs;
-        memset(&dt, 0, sizeof(dt));
-        memset(&qs, 0, sizeof(qs));
-        dt.a = dense; dt.lda = n->Dn; dt.wp = n->dense_w1; dt.bias = n->dense_b1; dt.M = R; dt.N = U; dt.K = n->Dn; dt.act = 1;
-        dt.wp2 = n->dense_w2; dt.bias2 = n->dense_b2; dt.c2 = n->allf + off_d; dt.ldc2 = F; dt.N2 = U; dt.act2 = 1;
-        qs.a = n->q; qs.lda = E; qs.wp = n->w1ac_all; qs.c = n->qa; qs.ldc = S * ATT_H1; qs.M = R; qs.N = S * ATT_H1; qs.K = E; qs.act = 0;
-        if ((rc = launch_gemm_h16_pair(dt, qs, st, map2))) return rc;
-    } else if (!forked) {
-        Prof p(n, KID_DENSE, st);
-        if ((rc = dense_tower(st))) return rc;
-    }
-    {
-        Prof p(n, KID_DIN, st);
-        DinArgs a;
-        memset(&a, 0, sizeof(a));
-        a.R = R; a.L = L; a.E = E; a.group = group; a.n_groups = ngroups;
-        a.slots = slots; a.slots_stride = ngroups; a.pld = n->PLD; a.q = n->q;
-        a.qa = n->qa; a.qa_stride = ATT_H1; a.qa_ld = S * ATT_H1;       // one GEMM for the q-side term of every input: [R, S*64]
-        const bool h16 = n->fp16x2 && n->din16;
-        if (!grouped && !shadow) {
-            rc = tier2 ? launch_gemm_h16(n->q, E, n->w1ac_all, nullptr, n->qa, S * ATT_H1, R, S * ATT_H1, E, 0, st, nullptr, 0, nullptr, 0, map2)
-                       : scorer_gemm(n, n->q, E, n->w1ac_all, nullptr, n->qa, S * ATT_H1, R, S * ATT_H1, E, 0, st);
-            if (rc) return rc;
-        }
-        for (int s = 0; s < S; ++s) {
-            a.h1[s] = n->h1[s]; a.h1f[s] = n->h1f[s]; a.proj[s] = n->proj[s]; a.w1ac[s] = n->w1ac[s]; a.w1d[s] = n->w1d[s]; a.w1d16[s] = n->w1d16[s];
-            a.w2[s] = n->att_w2[s]; a.b2[s] = n->att_b2[s]; a.w3[s] = n->att_w3[s]; a.b3[s] = n->att_b3[s];
-        }
-        a.scores = n->scores; a.scores_stride = (int64_t)n->c.max_rows * L;
-        a.order = order_in;
-        if (dedup && h16 && n->h1f[0]) { a.order = p_active; a.n_active = p_nact; }
-        if (dedup && n->dup_store) { a.dup_start = n->dd_dstart; a.dup_list = n->dd_dlist; }
-        for (int s = 0; s < S; ++s) a.lead[s] = n->lead[s];
-        a.pad_slot = n->c.max_slots;
-#ifdef RL4RS_DINX_TRACE      // timing experiments only (tools/dinx_trace.py)
-        {
-            static unsigned long long* din_trace = nullptr;
-            if (!din_trace) { (void)hipMalloc((void**)&din_trace, 8 * 5 * 8 * 8); (void)hipMemset(din_trace, 0, 8 * 5 * 8 * 8); }
-            a.trace = din_trace;
-            if (getenv("RL4RS_DINX_TRACE_DUMP")) {       // the marks of the PREVIOUS launch
-                unsigned long long host[8 * 5 * 8];
-                (void)hipDeviceSynchronize();
-                (void)hipMemcpy(host, din_trace, sizeof(host), hipMemcpyDeviceToHost);
-                FILE* f = fopen(getenv("RL4RS_DINX_TRACE_DUMP"), "wb");
-                if (f) { fwrite(host, 1, sizeof(host), f); fclose(f); }
-            }
-        }
-#endif
-        if (shadow) {
-            const DinQArgs qx = {cat, Cn, n->H, n->seq_emb, reinterpret_cast<const char*>(n->w1ac_all), n->q, n->qa};
-            hipLaunchKernelGGL(k_din_xq, dim3((R + 7) / 8, S), dim3(512), din_x_smem(), st, a, 16, n->n_cu, qx);
-        } else if (h16 && n->h1f[0]) {
-            // 16 rows per 8-wave workgroup: an obs-sized launch (R = 4096, two inputs) is two workgroups per CU, one round.
-            // group == 1: the grid is sized for 8 and the kernel picks 8 or 16 from the rows the dedup left (din_x.hpp)
-            if (group == 1 && n->din_rows_auto)
-                hipLaunchKernelGGL(k_din_x, dim3((R + 7) / 8, S), dim3(512), din_x_smem(), st, a, 16, n->n_cu);
-            else
-                hipLaunchKernelGGL(k_din_x, dim3((R + 15) / 16, S), dim3(512), din_x_smem(), st, a, 16, 0);
-        } else if (group == 1) {
-            const int nw = 4;
-            size_t smem = ((size_t)2 * 16 * 64 + 48 + (size_t)nw * (E + ATT_H1)) * 4;
-            if (h16) hipLaunchKernelGGL((k_din_scores<false, true>), dim3((R + nw - 1) / nw, S), dim3(64 * nw), smem, st, a);
-            else hipLaunchKernelGGL((k_din_scores<false, false>), dim3((R + nw - 1) / nw, S), dim3(64 * nw), smem, st, a);
-        } else {
-            int nw = group % 4 == 0 ? 4 : (group % 3 == 0 ? 3 : (group % 2 == 0 ? 2 : (group < 4 ? group : 4)));
-            size_t smem = ((size_t)L * (E + 4) + 2 * 16 * 64 + 48 + (size_t)nw * (E + ATT_H1)) * 4;
-            if (h16) hipLaunchKernelGGL((k_din_scores<true, true>), dim3(ngroups, S), dim3(64 * nw), smem, st, a);
-            else hipLaunchKernelGGL((k_din_scores<true, false>), dim3(ngroups, S), dim3(64 * nw), smem, st, a);
-        }
-        RL4RS_LAUNCH_CHECK();
-    }
-    {
-        Prof p(n, KID_AUGRU, st);
-        size_t smem = (size_t)(2 * 32 * (NH2 + 4) + 32 * (L + 1) + 32) * 4;
-        RecurArgs a;
-        memset(&a, 0, sizeof(a));
-        a.n_rows = R; a.L = L; a.group = group;
-        a.xld = n->PLD; a.xoff = ATT_H1; a.xbytes = ((int64_t)n->c.max_slots + 1) * L * n->PLD * 4;
-        a.ids = nullptr; a.slots = slots; a.slots_stride = ngroups;
-        for (int s = 0; s < S; ++s) a.lead[s] = n->lead[s];
-        a.pad_slot = n->c.max_slots;
-        for (int s = 0; s < S; ++s) { a.xbase[s] = n->proj[s]; a.wg[s] = n->augru_wg[s]; a.wc[s] = n->augru_wc[s]; }
-        a.att = n->scores; a.att_stride = (int64_t)n->c.max_rows * L;
-        a.out = n->allf; a.out_ld = F; a.out_off = 0; a.out_seq_off = NH2; a.slot_base = 0;
-        dim3 grid((R + 31) / 32, S), block(512);
-        if (n->fp16x2) {
-            for (int s = 0; s < S; ++s) { a.wg[s] = n->augru_wg16[s]; a.wc[s] = n->augru_wc16[s]; }
-            a.range_flag = n->range_flag;
-            for (int s = 0; s < S; ++s)
-                for (int t = 0; t < 8; ++t) {
-                    a.k_r[s][t] = -1.4426950408889634f / n->augru_s[s][0][t];
-                    a.k_u[s][t] = -1.4426950408889634f / n->augru_s[s][1][t];
-                    a.k_c[s][t] = 2.8853900817779268f / n->augru_s[s][2][t];
-                }
-            a.order = n->augru_x ? order_in : nullptr;
-            if (dedup) { a.order = p_active; a.n_active = p_nact; }
-            if (dedup && n->dup_store && n->augru_x) { a.dup_start = n->dd_dstart; a.dup_list = n->dd_dlist; }
-            a.steps = 0;
-#if defined(RL4RS_H16_TRACE) || defined(RL4RS_X_TRACE)
-            static unsigned long long* trace_buf = nullptr;
-            if (!trace_buf) { (void)hipMalloc((void**)&trace_buf, 8 * 4 * 8 * 8); (void)hipMemset(trace_buf, 0, 8 * 4 * 8 * 8); }
-            a.trace = trace_buf;
-            if (getenv("RL4RS_H16_TRACE_DUMP")) {
-                unsigned long long host[8 * 4 * 8];
-                (void)hipDeviceSynchronize();
-                (void)hipMemcpy(host, trace_buf, sizeof(host), hipMemcpyDeviceToHost);
-                FILE* f = fopen(getenv("RL4RS_H16_TRACE_DUMP"), "wb");
-                if (f) { fwrite(host, 1, sizeof(host), f); fclose(f); }
-            }
-#endif
-            const bool mt2 = augru_rows64(n, R, group);
-            if (shadow) {
-                AugruShadowArgs sh;
-                memset(&sh, 0, sizeof(sh));
-                sh.cat = cat; sh.Cn = Cn; sh.H = n->H; sh.cat_emb = n->cat_emb; sh.seq_emb = n->seq_emb; sh.allf = n->allf; sh.ldf = F; sh.off_c = off_c;
-                sh.q = n->q; sh.write_flat = n->ptab ? 0 : 1; sh.h16 = (n->fp16x2 && n->cat16) ? 1 : 0; sh.ptab = n->ptab; sh.obs_b = n->obs_b; sh.tsum = n->tsum;
-                sh.dense = dense; sh.lda = n->Dn; sh.w1 = reinterpret_cast<const char*>(n->dense_w1); sh.kb1 = (n->Dn + 15) / 16; sh.b1 = n->dense_b1;
-                sh.N1 = U; sh.K1 = n->Dn; sh.act1 = 1;
-                sh.vec = ((n->Dn & 3) == 0 && (reinterpret_cast<uintptr_t>(dense) & 15) == 0) ? 1 : 0;
-                sh.chain = G16Chain{reinterpret_cast<const char*>(n->dense_w2), (U + 15) / 16, n->dense_b2, n->allf + off_d, F, U, 1, nullptr, 0};
-                sh.R = R; sh.rmap = rmap;
-                augru_xs_launch(S, st, a, sh);
-            } else if (n->augru_x)
-                augru_x_launch(mt2 ? 64 : 32, S, st, a);
-            else
-                hipLaunchKernelGGL((k_augru_h16<1, RL4RS_H16_RING1, RL4RS_H16_NRES>), grid, block, augru_h16_smem(1, NH2, L), st, a);
-        } else
-#ifdef RL4RS_ABLATE      // timing experiments only (tools/ablate_augru.sh builds with -DRL4RS_ABLATE)
-        static const int ablate = getenv("RL4RS_AUGRU_ABLATE") ? atoi(getenv("RL4RS_AUGRU_ABLATE")) : 0;
-        switch (ablate) {
-            case 1: hipLaunchKernelGGL((k_recur<256, true, AUGRU_U, 1>), grid, block, smem, st, a); break;
-            case 2: hipLaunchKernelGGL((k_recur<256, true, AUGRU_U, 2>), grid, block, smem, st, a); break;
-            case 4: hipLaunchKernelGGL((k_recur<256, true, AUGRU_U, 4>), grid, block, smem, st, a); break;
-            case 8: hipLaunchKernelGGL((k_recur<256, true, AUGRU_U, 8>), grid, block, smem, st, a); break;
-            case 15: hipLaunchKernelGGL((k_recur<256, true, AUGRU_U, 15>), grid, block, smem, st, a); break;
-            default: hipLaunchKernelGGL((k_recur<256, true, AUGRU_U, 0>), grid, block, smem, st, a); break;
-        }
-#else
-        hipLaunchKernelGGL((k_recur<256, true, AUGRU_U, 0>), grid, block, smem, st, a);
-#endif
-        ;
-        RL4RS_LAUNCH_CHECK();
-    }
-    float* obs_out = obs ? obs : n->obs_tmp;
-    // the duplicates' rows: in front of the head GEMM (AUGRU states and attention scores), or - second tier on the active rows -
-    // behind it (the whole all-feature row, the scores, q and the head output)
-    auto row_expand = [&]() -> int {
-        Prof p(n, KID_DEDUP, st);
-        RowExpandArgs a;
-        memset(&a, 0, sizeof(a));
-        a.R = R; a.group = group; a.n_groups = ngroups; a.S = S; a.L = L; a.ncol = tier2 ? S * NH2 + U + E : S * NH2;
-        a.rep = p_rep; a.n_active = p_nact;
-        a.allf = n->allf; a.ld = F; a.scores = n->scores; a.scores_stride = (int64_t)n->c.max_rows * L;
-        if (tier2) { a.q = n->q; a.E = E; a.obs = obs_out; a.obs_dim = OBS_DIM; }
-        hipLaunchKernelGGL(k_row_expand, dim3((R + 3) / 4), dim3(256), 0, st, a);
-        RL4RS_LAUNCH_CHECK();
-        return RL4RS_OK;
-    };
-    if (dedup && !n->dup_store && !tier2 && (rc = row_expand())) return rc;
-    if (forked) RL4RS_HIP_TRY(hipStreamWaitEvent(st, n->ev_join, 0));
-    {
-        Prof p(n, KID_HEAD, st);
-        if (n->ptab && n->tsum) {     // obs = ELU(allf W + [b + table rows]): the addend was built inside k_cat_attn
-            const int Kh = S * NH2 + U + E;
-            if (n->gemm16) {
-                float* mirror = (obs && n->obs_mirror) ? n->obs_mirror : nullptr;
-                rc = launch_gemm_h16(n->allf, F, n->obs_w, nullptr, obs_out, OBS_DIM, R, OBS_DIM, Kh, 1, st, n->tsum, OBS_DIM, mirror, OBS_DIM, map2);
-                n->obs_mirror_used = mirror != nullptr;
-            }
-            else rc = launch_gemm_packed(n->allf, F, n->obs_w, nullptr, obs_out, OBS_DIM, R, OBS_DIM, Kh, 1, st, n->tsum, OBS_DIM);
-            if (rc) return rc;
-        } else if (n->ptab) {
-            const int Kh = S * NH2 + U + E;
-            if ((rc = scorer_gemm(n, n->allf, F, n->obs_w, nullptr, obs_out, OBS_DIM, R, OBS_DIM, Kh, 0, st))) return rc;
-            hipLaunchKernelGGL(k_head_finish, dim3((R + 3) / 4), dim3(256), 0, st, obs_out, R, cat, Cn, n->H, n->ptab, n->obs_b);
-            RL4RS_LAUNCH_CHECK();
-        } else {
-            if ((rc = scorer_gemm(n, n->allf, F, n->obs_w, n->obs_b, obs_out, OBS_DIM, R, OBS_DIM, n->F, 1, st))) return rc;
-        }
-    }
-    if (tier2 && (rc = row_expand())) return rc;
-    if (prob) {
-        Prof p(n, KID_PROB, st);
-        hipLaunchKernelGGL(k_head_prob, dim3((R + 3) / 4), dim3(256), 0, st, obs_out, R, OBS_DIM, n->K, n->out_w,
-                           n->out_b, prob, group, n->obs_last);
-        RL4RS_LAUNCH_CHECK();
-    }
+    RL4RS_REQUIRE(!c.obs_last || c.prob, "dien_forward: rl4rs_dien_set_obs_last needs a forward that returns probabilities");
+    const DienPlan p = dien_plan(n->t, c);
+    DienFwd f;
+    f.R = R; f.group = group; f.n_groups = ngroups; f.dense = dense; f.cat = cat; f.slots = slots;
+    f.obs_out = obs ? obs : n->obs_tmp; f.prob = prob; f.st = (hipStream_t)stream;
+    f.order_in = c.row_order ? n->row_order : nullptr;
+    f.rep = c.carried ? n->part_rep : n->dd_rep;
+    f.active = c.carried ? n->part_active : n->dd_active;
+    f.nact = c.carried ? n->part_nact : n->dd_nact;
+    f.rmap = G16RowMap{f.active, f.nact, group};
+    f.map2 = p.tier2 ? &f.rmap : nullptr;
+    int rc;
+    if (p.dense_side && (rc = stage_dense_fork(n, p, f))) return rc;
+    if ((rc = stage_dedup(n, p, f))) return rc;
+    n->last_plan = p;
+    if ((rc = stage_cat(n, p, f))) return rc;
+    if ((rc = stage_dense(n, p, f))) return rc;
+    if ((rc = stage_din(n, p, f))) return rc;
+    if ((rc = stage_augru(n, p, f))) return rc;
+    if (p.expand == PlanExpand::Front && (rc = stage_expand(n, p, f))) return rc;
+    if (p.dense_side) RL4RS_HIP_TRY(hipStreamWaitEvent(f.st, n->ev_join, 0));
+    if ((rc = stage_head(n, p, f))) return rc;
+    if (p.expand == PlanExpand::Behind && (rc = stage_expand(n, p, f))) return rc;
+    if (p.prob && (rc = stage_prob(n, f))) return rc;
     return RL4RS_OK;
 }
 
@@ -2556,7 +2546,7 @@ int rl4rs_dien_buffer(rl4rs_dien* n, int which, void** p, int64_t* bytes) {
         case RL4RS_DIEN_N_ACTIVE:
         case RL4RS_DIEN_ROW_REP:
         case RL4RS_DIEN_ROW_ACTIVE: {
-            if (!n->row_dedup) { set_error("dien_buffer: row dedup is off on this handle"); return RL4RS_EINVAL; }
+            if (!n->t.row_dedup) { set_error("dien_buffer: row dedup is off on this handle"); return RL4RS_EINVAL; }
             // the partition of the LAST forward: the handle's own, or the buffers its caller handed in (rl4rs_dien_set_row_partition)
             const int64_t groups = n->last_rep ? n->last_groups : n->c.max_rows;
             if (which == RL4RS_DIEN_N_ACTIVE) { ptr = const_cast<int32_t*>(n->last_rep ? n->last_nact : n->dd_nact); b = 4; }
@@ -2605,7 +2595,7 @@ int rl4rs_dien_set_row_partition(rl4rs_dien* n, const int32_t* rep_dev, const in
     RL4RS_REQUIRE(n, "dien_set_row_partition: null handle");
     if (!rep_dev) { n->part_rep = nullptr; return RL4RS_OK; }      // disarm
     RL4RS_REQUIRE(active_dev && n_active_dev && n_groups > 0 && n_groups <= n->c.max_rows, "dien_set_row_partition: bad argument");
-    RL4RS_REQUIRE(n->row_dedup && !n->dup_store, "dien_set_row_partition: this handle's forward does not take a partition (row dedup off, or dup_store)");
+    RL4RS_REQUIRE(n->t.row_dedup && !n->t.dup_store, "dien_set_row_partition: this handle's forward does not take a partition (row dedup off, or dup_store)");
     n->part_rep = rep_dev; n->part_active = active_dev; n->part_nact = n_active_dev; n->part_groups = n_groups;
     return RL4RS_OK;
 }
@@ -2623,7 +2613,7 @@ int rl4rs_dien_set_profiling(rl4rs_dien* n, int enable) {
 }
 int rl4rs_dien_scorer_mode(rl4rs_dien* n, int32_t* mode) {
     RL4RS_REQUIRE(n && mode, "dien_scorer_mode: null argument");
-    *mode = n->fp16x2 ? RL4RS_SCORER_FP16X2 : RL4RS_SCORER_FP32;
+    *mode = n->t.fp16x2 ? RL4RS_SCORER_FP16X2 : RL4RS_SCORER_FP32;
     return RL4RS_OK;
 }
 // Synchronises the stream, returns and clears the handle's status bits (include/rl4rs_hip.h RL4RS_DIEN_STATUS_*).
@@ -2641,16 +2631,16 @@ int rl4rs_dien_status(rl4rs_dien* n, int32_t* flags, void* stream) {
 namespace rl4rs {
 void dien_set_obs_mirror(rl4rs_dien* n, float* host_visible) { if (n) n->obs_mirror = host_visible; }
 void dien_last_partition(const rl4rs_dien* n, DienPartition* out) { *out = n->dd_info; }
-bool dien_takes_partition(const rl4rs_dien* n) { return n && n->row_dedup && !n->dup_store; }
+bool dien_takes_partition(const rl4rs_dien* n) { return n && n->t.row_dedup && !n->t.dup_store; }
 const int32_t* dien_row_order(const rl4rs_dien* n, int n_groups) { return (n->row_order && n->row_order_n == n_groups) ? n->row_order : nullptr; }
 bool dien_obs_mirror_used(const rl4rs_dien* n) { return n && n->obs_mirror_used; }
 bool dien_augru_rows64(const rl4rs_dien* n, int B, int group) {
-    return n && n->fp16x2 && n->augru_x && (int64_t)B * group <= n->c.max_rows && augru_rows64(n, B * group, group);
+    return n && n->t.fp16x2 && n->t.augru_x && (int64_t)B * group <= n->c.max_rows && augru_rows64(n->augru_rows, B * group, group, n->S, n->n_cu);
 }
 int64_t dien_augru_rounds(const rl4rs_dien* n, int B, int live, int group) {
-    if (!n || !n->fp16x2 || !n->augru_x || (int64_t)B * group > n->c.max_rows) return -1;
-    const int64_t G = n->row_dedup ? (live < B ? live : B) : B;
-    const int64_t tiles = !augru_rows64(n, B * group, group) ? (G * group + 31) / 32 : (group == 9 ? (G + 6) / 7 : (G * group + 63) / 64);
+    if (!n || !n->t.fp16x2 || !n->t.augru_x || (int64_t)B * group > n->c.max_rows) return -1;
+    const int64_t G = n->t.row_dedup ? (live < B ? live : B) : B;
+    const int64_t tiles = augru_tiles(augru_rows64(n->augru_rows, B * group, group, n->S, n->n_cu), G * group, group);
     return (tiles * n->S + n->n_cu - 1) / n->n_cu;
 }
 }  // namespace rl4rs
@@ -2667,23 +2657,22 @@ int rl4rs_dien_kernel_count(void) { return KID_COUNT; }
 // appear in a rocprofv3 kernel trace - the static class names of rl4rs_dien_kernel_name are those of the fp32 build.
 int rl4rs_dien_kernel_label(rl4rs_dien* n, int which, char* buf, int32_t cap) {
     RL4RS_REQUIRE(n && buf && cap > 0 && which >= 0 && which < KID_COUNT, "dien_kernel_label: bad argument");
-    const char* gemm = n->gemm16 ? "k_gemm_h16" : "k_gemm_pk";
-    const bool din_x = n->fp16x2 && n->din16 && n->h1f[0];
+    const char* gemm = n->t.gemm16 ? "k_gemm_h16" : "k_gemm_pk";
+    const DienTraits& t = n->t;
     std::string s;
     switch (which) {
-        case KID_CAT: s = (n->cat_v2 && n->E == 128 && n->Cn <= 24) ? (n->cat_group ? "k_cat_attn2 / k_cat_attn2g (grouped rows)" : "k_cat_attn2") : "k_cat_attn"; break;
+        case KID_CAT: s = t.cat_v2_shape() ? (t.cat_group ? "k_cat_attn2 / k_cat_attn2g (grouped rows)" : "k_cat_attn2") : "k_cat_attn"; break;
         case KID_DENSE:
-            s = dien_gemm_grouped(n) ? "k_gemm_h16_pair(dense tower, both layers + q-side term of the DIN scores)"
-                : (n->gemm16 && n->dense_chain && n->U <= 128 && n->U % 16 == 0) ? "k_gemm_h16<chain>(dense tower, both layers)"
-                                                                                  : std::string(gemm) + " x2 (dense tower)";
+            s = t.dense_grouped() ? "k_gemm_h16_pair(dense tower, both layers + q-side term of the DIN scores)"
+                : t.dense_chained() ? "k_gemm_h16<chain>(dense tower, both layers)" : std::string(gemm) + " x2 (dense tower)";
             break;
         case KID_DIN:
-            s = std::string(din_x ? "k_din_x" : (n->fp16x2 && n->din16 ? "k_din_scores<h16>" : "k_din_scores"));
-            if (!dien_gemm_grouped(n)) s += std::string(" + ") + gemm + "(q-side term)";
+            s = std::string(t.din_x_selected() ? "k_din_x" : (t.din_h16() ? "k_din_scores<h16>" : "k_din_scores"));
+            if (!t.dense_grouped()) s += std::string(" + ") + gemm + "(q-side term)";
             break;
         case KID_AUGRU:
-            s = !n->fp16x2 ? "k_recur<256,augru>" : (n->augru_x ? "k_augru_x" : "k_augru_h16");
-            if (n->last_shadow) s = "k_augru_xs (last forward: category branch and dense tower in the shadow plane)";
+            s = !t.fp16x2 ? "k_recur<256,augru>" : (t.augru_x ? "k_augru_x" : "k_augru_h16");
+            if (n->last_plan.shadow) s = "k_augru_xs (last forward: category branch and dense tower in the shadow plane)";
             break;
         case KID_HEAD:
             s = std::string(gemm) + "(simulator_obs)" + ((n->ptab && !n->tsum) ? " + k_head_finish" : "");
@@ -2693,8 +2682,8 @@ int rl4rs_dien_kernel_label(rl4rs_dien* n, int which, char* buf, int32_t cap) {
             s = n->gru16 ? "k_gru_h16" : "k_recur<128,gru>";
             if (n->h1f[0]) s += " + k_h1_frag";
             break;
-        case KID_DEDUP: s = n->row_dedup ? "k_row_dedup + k_row_expand" : "k_row_dedup (off)"; break;
-        case KID_PROJ: s = n->gemm16 ? "k_gemm_h16 / k_gemm_h16_wres(seq projections)" : "k_gemm_pk(seq projections)"; break;
+        case KID_DEDUP: s = n->t.row_dedup ? "k_row_dedup + k_row_expand" : "k_row_dedup (off)"; break;
+        case KID_PROJ: s = n->t.gemm16 ? "k_gemm_h16 / k_gemm_h16_wres(seq projections)" : "k_gemm_pk(seq projections)"; break;
     }
     snprintf(buf, (size_t)cap, "%s", s.c_str());
     return RL4RS_OK;

@@ -7,6 +7,8 @@ import os
 import sys
 import tempfile
 
+import numpy as np
+
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench  # noqa: E402
 
@@ -17,6 +19,8 @@ def main():
     with tempfile.TemporaryDirectory() as d:
         cfg, _ = bench.make_config(args, d, 0)
         env = bench.build_env(cfg, False)
+        env.seed(1000)              # (as bench.py; the batch itself is drawn with numpy's global generator)
+        np.random.seed(1000)
         h = hashlib.sha256()
         for _ in range(2):
             obs = env.reset()
