@@ -19,6 +19,10 @@ rl4rs_replay_sample_nstep, everything else is ``DQNTrainer``'s loop.
 ``TD3Trainer`` is the continuous actor-critic learner of that driver (script/modelfree_train.py:46-48,79-105: RLlib TD3 / DDPG on
 support_conti_env): OU exploration, a replay ring of float actions and the whole update (rl4rs_td3_update) stay on the device.
 
+All of them hang on one skeleton: ``_DeferredStats`` (a train call's statistics are copied asynchronously and
+settled one call later), ``_OnPolicy`` (PPO's KL rule, for ``Trainer`` and ``RawStateTrainer`` only), ``_Evaluated`` (the evaluation
+frame) and ``_ReplayTrainer`` (rollout, push, updates of DQN / Rainbow / TD3); a trainer states what differs.
+
 Data parallelism: every rank owns its own env batch and sampling stream (``seed`` differs per rank) and a replica
 of the policy that is IDENTICAL on all ranks: initialised from the shared ``init_seed``, rank 0's parameters / Adam state are
 broadcast at construction, and every optimiser step applies the rank-mean gradient.  A2C: one all-reduce per iteration.
@@ -59,6 +63,44 @@ def _returns(rew, R, T, B):
     """gamma = 1, lambda = 1: reward-to-go within each rollout ([R, T, B] layout of the flat buffers)."""
     r = rew.view(R, T, B)
     return torch.flip(torch.cumsum(torch.flip(r, dims=[1]), dim=1), dims=[1]).reshape(-1).to(torch.float32)
+
+
+DISCRETE_ENV_MESSAGE = "%s needs the zero-copy discrete-action env (config['return_tensors'] = True)"
+
+
+def _require_env(cfg, message, conti=False, error=AssertionError):
+    """Every trainer here runs the zero-copy env, discrete-action unless ``conti``; raises ``error(message)`` otherwise."""
+    if not cfg.get('return_tensors', False) or bool(cfg.get('support_conti_env', False)) != conti:
+        raise error(message)
+
+
+def _obs_width(env):
+    """The observation width the env reports (base.py:206-213): 256 for the DIEN / dnn / lstm simulators, 3072 for widedeep."""
+    space = env.observation_space
+    space = space.spaces['obs'] if hasattr(space, 'spaces') else space
+    return int(space.shape[0])
+
+
+def _default_minibatch(batch_size, max_steps, train_batch_size=None):
+    """modelfree_train.py:409: train_batch_size = min(B * T, 1024) sampled rows per update unless one is given."""
+    return int(train_batch_size) if train_batch_size is not None else min(batch_size * max_steps, 1024)
+
+
+def sync_policy_replicas(policy, src=0):
+    """Make every rank's parameters, Adam moments and step counter of ``policy`` those of rank ``src``."""
+    p = policy.params()
+    m, v, t = policy.adam_state()
+    rdist.broadcast_(p, src)
+    rdist.broadcast_(m, src)
+    rdist.broadcast_(v, src)
+    step = torch.tensor([t], dtype=torch.int64)
+    if rdist.collectives_active():
+        import torch.distributed as dist
+        if dist.get_backend() != 'gloo':
+            step = step.to(p.device)
+        dist.broadcast(step, src=src)
+    policy.set_params(p)
+    policy.set_adam_state(m, v, int(step.item()))
 
 
 class LazyStats(object):
@@ -110,7 +152,89 @@ class LazyStats(object):
 
 
 class _DeferredStats(object):
-    """Shared by the trainers: statistics of a train call are copied asynchronously and settled one call later (LazyStats)."""
+    """The skeleton every trainer hangs on: the statistics of a train call are copied asynchronously (``_submit``) and settled one
+    call later (``_settle``, ``LazyStats``).  A trainer keeps ``_pending`` (a list) and ``iteration``, and fills ``_values``; one
+    whose networks run a persistent pass is recognised by its ``policy`` handle's status words."""
+
+    def _status_word(self, dev):
+        """float64 [1]: non-zero when a persistent pass of this call timed out.  Reads the policy handle's status words; a trainer
+        whose networks have none reports zero."""
+        policy = getattr(self, 'policy', None)
+        if hasattr(policy, 'status_words'):
+            return policy.status_words()[1:2].to(torch.float64)
+        return torch.zeros(1, dtype=torch.float64, device=dev)
+
+    def _submit(self, mean_reward, stats, **extra):
+        """Enqueue the device -> pinned copy of one train call's numbers [mean_reward, stats..., status word] and an event.
+        ``extra``: host values of this call that ``_values`` wants back."""
+        dev = stats.device
+        status = self._status_word(dev)
+        overflow = rdist.take_row_overflow(dev)
+        if overflow is not None:
+            status = status + 1000.0 * overflow.to(torch.float64)
+        vec = torch.cat([mean_reward.reshape(1).to(torch.float64), stats.reshape(-1).to(torch.float64), status])
+        pin = torch.empty(vec.shape, dtype=torch.float64, pin_memory=True)
+        pin.copy_(vec, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(dev))
+        token = dict(pin=pin, ev=ev, values=None, iteration=self.iteration, **extra)
+        self._pending.append(token)
+        return LazyStats(self, token)
+
+    def _settle(self):
+        """Finish every outstanding train call in order: wait for its numbers, validate the pass, build its mapping."""
+        while self._pending:
+            tok = self._pending.pop(0)
+            tok['ev'].synchronize()
+            v = tok['pin'].numpy().copy()
+            if v[-1] >= 1000.0:
+                raise RuntimeError(rdist.ROW_OVERFLOW_MESSAGE)
+            if v[-1] != 0.0:
+                self.policy.check_status()                  # clears the flag and raises
+                raise RuntimeError(D.DevicePolicy.PASS_TIMEOUT_MESSAGE)
+            tok['values'] = dict(self._values(tok, float(v[0]), v[1:-1]), iteration=tok['iteration'])
+
+    def _values(self, tok, mean_reward, s):
+        """The trainer's hook: one settled call's token, mean episode reward and float64 statistics ``s`` -> its mapping."""
+        raise NotImplementedError
+
+    def _resolve(self, token):
+        if token['values'] is None:
+            self._settle()
+        return token['values']
+
+
+class _Evaluated(_DeferredStats):
+    """A trainer with an evaluation pass (``_eval_batch``) and device handles of its own to close (``_owned``, ``device``)."""
+
+    def close(self):
+        try:
+            self._settle()
+        finally:
+            for handle in self._owned:
+                handle.close()
+
+    def evaluate(self, episodes=None, seed=0):
+        """Mean episode reward of ceil(episodes / B) evaluation batches (``_eval_batch``: no exploration) from the start of the record
+        file with the env's record sampling seeded by ``seed``, so two calls on the same parameters give the same number.  Leaves
+        the global numpy RNG as it found it; the env's record cursor restarts."""
+        self._settle()
+        n = 1 if episodes is None else max(1, int(math.ceil(float(episodes) / self.B)))
+        state = np.random.get_state()
+        try:
+            np.random.seed(seed)
+            total = torch.zeros((), dtype=torch.float64, device=self.device)
+            for k in range(n):
+                total += self._eval_batch(k)
+        finally:
+            np.random.set_state(state)
+        return float(total.item()) / n
+
+
+class _OnPolicy(_DeferredStats):
+    """What ``Trainer`` and ``RawStateTrainer`` share: the A2C / PPO statistics, PPO's adaptive KL coefficient and the statistics
+    vector of a data-parallel PPO pass."""
+
     @property
     def kl_coeff(self):
         """PPO's adaptive KL coefficient AFTER every finished train call (waits for the last call's statistics)."""
@@ -122,59 +246,31 @@ class _DeferredStats(object):
         self._settle()
         self._kl_coeff = float(v)
 
-    def _status_word(self, dev):
-        """float64 [1]: non-zero when a persistent pass of this call timed out.  The default reads the policy handle's status words;
-        a trainer whose networks have none returns zero."""
-        if hasattr(self.policy, 'status_words'):
-            return self.policy.status_words()[1:2].to(torch.float64)
-        return torch.zeros(1, dtype=torch.float64, device=dev)
+    def _values(self, tok, mean_reward, s):
+        """A token with ``kl_div`` is a PPO call: s[7] / kl_div is the pass-mean KL that RLlib's rule sees."""
+        kl_mean = 0.0
+        if tok.get('kl_div'):
+            kl_mean = float(s[7]) / tok['kl_div']
+            self._kl_coeff = update_kl_coeff(self._kl_coeff, kl_mean, self.kl_target)
+        values = {'episode_reward_mean': mean_reward, 'policy_loss': float(s[0]), 'vf_loss': float(s[1]), 'entropy': float(s[2]),
+                  'kl': float(s[3]), 'kl_mean': kl_mean, 'kl_coeff': self._kl_coeff}
+        if tok.get('vtrace_rows'):                      # IMPALA: s[4:8] = sums of {rho, min(rho, clip_rho), vs, pg_adv} over the kept rows
+            n = float(tok['vtrace_rows'])
+            values.update(rho_mean=float(s[4]) / n, rho_clipped_mean=float(s[5]) / n, vs_mean=float(s[6]) / n)
+        return values
 
-    def _submit(self, mean_reward, stats, kl_div, extra):
-        """Enqueue the device -> pinned copy of one train call's numbers [mean_reward, stats..., status word] and an event."""
-        dev = stats.device
-        status = self._status_word(dev)
-        overflow = rdist.take_row_overflow(dev)
-        if overflow is not None:
-            status = status + 1000.0 * overflow.to(torch.float64)
-        vec = torch.cat([mean_reward.reshape(1).to(torch.float64), stats.reshape(-1).to(torch.float64), status])
-        pin = torch.empty(vec.shape, dtype=torch.float64, pin_memory=True)
-        pin.copy_(vec, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(dev))
-        token = dict(pin=pin, ev=ev, kl_div=kl_div, values=None, iteration=self.iteration, **extra)
-        self._pending.append(token)
-        return token
+    def _submit_ppo_minibatches(self, mean_reward, stats, kl_sum, rows):
+        """Data-parallel PPO (one gradient / all-reduce / Adam per minibatch): the last minibatch's statistics and the KL sum over
+        this rank's ``rows`` samples, laid out like the single-launch pass's eight.  Every rank must take the same kl_coeff
+        decision: the rule sees the mean over ALL ranks' samples.  The sum is all-reduced ON THE DEVICE and travels with the
+        deferred statistics: no rank reads a device scalar in a train call."""
+        stats8 = torch.cat([stats.reshape(-1)[:4].to(torch.float32), torch.zeros(3, dtype=torch.float32, device=kl_sum.device),
+                            kl_sum.reshape(1)])
+        rdist.allreduce_sum_(stats8[7:8])
+        return self._submit(mean_reward, stats8, kl_div=rows * rdist.world_size())
 
-    def _settle(self):
-        """Finish every outstanding train call in order: wait for its numbers, validate the pass, apply RLlib's KL rule."""
-        while self._pending:
-            tok = self._pending.pop(0)
-            tok['ev'].synchronize()
-            v = tok['pin'].numpy().copy()
-            if v[-1] >= 1000.0:
-                raise RuntimeError(rdist.ROW_OVERFLOW_MESSAGE)
-            if v[-1] != 0.0:
-                self.policy.check_status()                  # clears the flag and raises
-                raise RuntimeError(D.DevicePolicy.PASS_TIMEOUT_MESSAGE)
-            s = v[1:-1]
-            kl_mean = 0.0
-            if tok['ppo']:
-                kl_mean = float(s[7]) / tok['kl_div'] if tok['kl_mean'] is None else tok['kl_mean']
-                if tok['kl_mean'] is None:
-                    self._kl_coeff = update_kl_coeff(self._kl_coeff, kl_mean, self.kl_target)
-            tok['values'] = {'episode_reward_mean': float(v[0]), 'policy_loss': float(s[0]), 'vf_loss': float(s[1]),
-                             'entropy': float(s[2]), 'kl': float(s[3]), 'kl_mean': kl_mean, 'kl_coeff': self._kl_coeff,
-                             'iteration': tok['iteration']}
-            if tok.get('vtrace_rows'):                      # IMPALA: s[4:8] = sums of {rho, min(rho, clip_rho), vs, pg_adv} over the kept rows
-                n = float(tok['vtrace_rows'])
-                tok['values'].update(rho_mean=float(s[4]) / n, rho_clipped_mean=float(s[5]) / n, vs_mean=float(s[6]) / n)
 
-    def _resolve(self, token):
-        if token['values'] is None:
-            self._settle()
-        return token['values']
-
-class RawStateTrainer(_DeferredStats):
+class RawStateTrainer(_OnPolicy):
     """The same loop for an env with config['rawstate_as_obs'] (+ support_rllib_mask, return_tensors): the policy is the
     raw-state encoder (rllib_rawstate_model.py; modelfree_train.py 'rawstate' variants) acting on the device tensors of the
     raw features; loss, backward and Adam run through rl4rs_rawtrain_*.
@@ -281,7 +377,7 @@ class RawStateTrainer(_DeferredStats):
                                           vf_coeff=0.5, ent_coeff=0.01)
             self._allreduce_gradient(b['cat'], b['seqs'])
             self.policy.adam_step(lr=self.lr, grad_clip=10.0)
-            return LazyStats(self, self._submit(mean_reward, stats[:4], 1, dict(ppo=False, kl_mean=None)))
+            return self._submit(mean_reward, stats[:4])
         adv_n = (adv - adv.mean()) / adv.std().clamp_min(1e-4)
         perm = torch.from_numpy(np.random.RandomState(self.seed + self.iteration - 1).permutation(N)).to(b['cat'].device)
         sh = dict((k, b[k][perm]) for k in ('cat', 'dense', 'mask', 'act', 'logp', 'val', 'logits'))
@@ -300,18 +396,10 @@ class RawStateTrainer(_DeferredStats):
             self.policy.adam_step(lr=self.lr)
             kl_sum += stats[3]
             nmb += 1
-        stats8 = torch.cat([stats.reshape(-1)[:4].to(torch.float32), torch.zeros(3, dtype=torch.float32, device=kl_sum.device),
-                            kl_sum.reshape(1)])
-        if rdist.collectives_active():
-            # every rank must take the same kl_coeff decision: the rule sees the mean over ALL ranks' samples.  The sum is
-            # all-reduced ON THE DEVICE and travels with the deferred statistics: no rank reads a device scalar in a train call
-            rdist.allreduce_sum_(stats8[7:8])
-            return LazyStats(self, self._submit(mean_reward, stats8, max(nmb * self.minibatch, 1) * rdist.world_size(),
-                                                dict(ppo=True, kl_mean=None)))
-        return LazyStats(self, self._submit(mean_reward, stats8, max(nmb * self.minibatch, 1), dict(ppo=True, kl_mean=None)))
+        return self._submit_ppo_minibatches(mean_reward, stats, kl_sum, nmb * self.minibatch)
 
 
-class Trainer(_DeferredStats):
+class Trainer(_OnPolicy):
     """A2C / PPO / PG / IMPALA on the action-masked FC policy (rllib_mask_model.py:7-64) over the zero-copy discrete-action env.
 
     seed       sampling stream of this rank (Gumbel noise, PPO shuffle): pass a different value per rank
@@ -343,8 +431,7 @@ class Trainer(_DeferredStats):
                  train_batch_size=None, keep_last_batch=False, broadcast_interval=1, vtrace_clip_rho=1.0, vtrace_clip_pg_rho=1.0,
                  drop_last=True, vf_coeff=0.5, ent_coeff=0.01, grad_clip=10.0):
         cfg = env.config
-        assert cfg.get('return_tensors', False) and not cfg.get('support_conti_env', False), \
-            "Trainer needs the zero-copy discrete-action env (config['return_tensors'] = True)"
+        _require_env(cfg, DISCRETE_ENV_MESSAGE % 'Trainer')
         self.env = env
         # PG and IMPALA run on the A2C form of the loss kernels
         self.algo = {'A2C': D.DevicePolicy.A2C, 'PPO': D.DevicePolicy.PPO, 'PG': D.DevicePolicy.A2C, 'IMPALA': D.DevicePolicy.A2C}[algo]
@@ -372,10 +459,7 @@ class Trainer(_DeferredStats):
             # by zero, ranks failing at different points around a collective)
             raise ValueError("PPO needs at least one full minibatch per train call: %d rollouts x batch_size x max_steps = %d < "
                              "minibatch = %d" % (self.R, N, minibatch))
-        # the observation width the env reports (base.py:206-213): 256 for the DIEN / dnn / lstm simulators, 3072 for widedeep
-        space = env.observation_space
-        space = space.spaces['obs'] if hasattr(space, 'spaces') else space
-        self.OD = int(space.shape[0])
+        self.OD = _obs_width(env)
         self.policy = D.DevicePolicy(self.OD, hidden, self.A, max_rows=N, seed=init_seed)
         share = rdist.ranks_sharing_device()
         if share > 1:
@@ -407,19 +491,7 @@ class Trainer(_DeferredStats):
 
     def sync_replicas(self, src=0):
         """Make every rank's parameters, Adam moments and step counter those of rank ``src``."""
-        p = self.policy.params()
-        m, v, t = self.policy.adam_state()
-        rdist.broadcast_(p, src)
-        rdist.broadcast_(m, src)
-        rdist.broadcast_(v, src)
-        step = torch.tensor([t], dtype=torch.int64)
-        if rdist.collectives_active():
-            import torch.distributed as dist
-            if dist.get_backend() != 'gloo':
-                step = step.to(p.device)
-            dist.broadcast(step, src=src)
-        self.policy.set_params(p)
-        self.policy.set_adam_state(m, v, int(step.item()))
+        sync_policy_replicas(self.policy, src)
 
     def params(self):
         """Flat parameters (validated: raises if a persistent pass was cut short)."""
@@ -471,7 +543,6 @@ class Trainer(_DeferredStats):
         self._settle()                       # previous call: statistics, pass status, kl_coeff (the GPU is busy with the rollout)
         b = self.buf
         N = self.R * self.B * self.T
-        world = rdist.world_size()
         self.iteration += 1
         if self.algo_name == 'IMPALA':
             # V-trace needs neither the returns nor the actor's values: the learner re-evaluates every row
@@ -481,33 +552,27 @@ class Trainer(_DeferredStats):
                                                                vf_coeff=self.vf_coeff, ent_coeff=self.ent_coeff, grad_out=self.grad,
                                                                stats_out=self._mb_stats, vtrace_stats_out=self._vt_stats)
             if self.keep_last_batch:
-                self.last_batch = dict(obs=b['obs'].clone(), act=b['act'].clone(), mask=b['mask'].clone(), logp=b['logp'].clone(),
-                                       rew=b['rew'].clone())
+                self.last_batch = dict((k, b[k].clone()) for k in ('obs', 'act', 'mask', 'logp', 'rew'))
             rdist.allreduce_mean_(g)
             self.policy.adam_step(g, lr=self.lr, grad_clip=self.grad_clip)
             self.num_updates += 1
             if self.num_updates % self.broadcast_interval == 0:
                 self.actor.copy_params_from(self.policy)            # device to device, in stream order behind the Adam step
             kept = self.R * (self.T - 1 if self.drop_last else self.T) * self.B
-            return LazyStats(self, self._submit(mean_reward, torch.cat([stats.to(torch.float64), vstats]), 1,
-                                                dict(ppo=False, kl_mean=None, vtrace_rows=kept)))
-        if self.algo_name == 'PG':
-            # -mean(logp * return): the A2C kernels with the critic and the entropy term off and the 1 / N folded into the advantages
-            g, stats = self.policy.loss_grad(self.algo, b['obs'], b['act'], ret * (1.0 / N), ret, mask_bits=b['mask'],
-                                             vf_coeff=0.0, ent_coeff=0.0, grad_out=self.grad)
-            if self.keep_last_batch:
-                self.last_batch = dict(obs=b['obs'].clone(), act=b['act'].clone(), mask=b['mask'].clone(), adv=ret * (1.0 / N), ret=ret.clone())
-            rdist.allreduce_mean_(g)
-            self.policy.adam_step(g, lr=self.lr, grad_clip=0.0)
-            return LazyStats(self, self._submit(mean_reward, stats[:4], 1, dict(ppo=False, kl_mean=None)))
+            return self._submit(mean_reward, torch.cat([stats.to(torch.float64), vstats]), vtrace_rows=kept)
         if self.algo == D.DevicePolicy.A2C:
+            if self.algo_name == 'PG':
+                # -mean(logp * return): the A2C kernels with the critic and the entropy term off and the 1 / N folded into the advantages
+                adv, vf_coeff, ent_coeff, grad_clip = ret * (1.0 / N), 0.0, 0.0, 0.0
+            else:
+                vf_coeff, ent_coeff, grad_clip = 0.5, 0.01, 10.0
             g, stats = self.policy.loss_grad(self.algo, b['obs'], b['act'], adv, ret, mask_bits=b['mask'],
-                                             vf_coeff=0.5, ent_coeff=0.01, grad_out=self.grad)
+                                             vf_coeff=vf_coeff, ent_coeff=ent_coeff, grad_out=self.grad)
             if self.keep_last_batch:
                 self.last_batch = dict(obs=b['obs'].clone(), act=b['act'].clone(), mask=b['mask'].clone(), adv=adv.clone(), ret=ret.clone())
             rdist.allreduce_mean_(g)                         # the ONE collective: flat policy gradient over RCCL
-            self.policy.adam_step(g, lr=self.lr, grad_clip=10.0)
-            return LazyStats(self, self._submit(mean_reward, stats[:4], 1, dict(ppo=False, kl_mean=None)))
+            self.policy.adam_step(g, lr=self.lr, grad_clip=grad_clip)
+            return self._submit(mean_reward, stats[:4])
         adv_n = (adv - adv.mean()) / adv.std().clamp_min(1e-4)      # RLlib standardises PPO advantages
         perm = torch.from_numpy(np.random.RandomState(self.seed + self.iteration - 1).permutation(N)).to(b['obs'].device)
         # shuffle every buffer ONCE (7 gathers per iteration instead of 7 per minibatch): minibatches are then
@@ -523,7 +588,7 @@ class Trainer(_DeferredStats):
             stats = self.policy.ppo_epoch(sh['obs'], sh['act'], adv_s, ret_s, sh['mask'], sh['logp'], sh['val'],
                                           sh['logits'], minibatch=MB, vf_coeff=0.5, ent_coeff=0.0,
                                           clip=0.3, vf_clip=500.0, kl_coeff=self._kl_coeff, lr=self.lr, grad_out=self.grad)
-            return LazyStats(self, self._submit(mean_reward, stats, nmb * MB, dict(ppo=True, kl_mean=None)))
+            return self._submit(mean_reward, stats, kl_div=nmb * MB)
         # data parallel: per minibatch ONE fused gradient launch, ONE all-reduce, ONE Adam launch
         kl_sum = torch.zeros((), dtype=torch.float32, device=b['obs'].device)
         for mb in range(nmb):
@@ -534,15 +599,83 @@ class Trainer(_DeferredStats):
             rdist.allreduce_mean_(g)
             self.policy.adam_step(g, lr=self.lr)
             kl_sum += stats[3]
-        # every rank must take the same kl_coeff decision: the rule sees the mean over ALL ranks' samples.  The KL sum is
-        # all-reduced on the device and settles with the deferred statistics like the single-GPU path (ADVICE / VERDICT r3: this
-        # path used to read kl_sum on the host - one queue drain per train call and rank)
-        stats8 = torch.cat([stats.reshape(-1)[:4], torch.zeros(3, dtype=stats.dtype, device=stats.device), kl_sum.reshape(1).to(stats.dtype)])
-        rdist.allreduce_sum_(stats8[7:8])
-        return LazyStats(self, self._submit(mean_reward, stats8, nmb * MB * world, dict(ppo=True, kl_mean=None)))
+        # (the KL sum settles with the deferred statistics like the single-GPU path; ADVICE / VERDICT r3: this path used to read
+        # kl_sum on the host - one queue drain per train call and rank)
+        return self._submit_ppo_minibatches(mean_reward, stats, kl_sum, nmb * MB)
 
 
-class DQNTrainer(_DeferredStats):
+class _ReplayTrainer(_Evaluated):
+    """The loop of the replay learners (DQN, Rainbow, TD3 / DDPG): one complete-episode rollout into ``buf``, the push of its
+    ``_columns`` into the replay ring, ``updates_per_rollout`` updates once ``learning_starts`` sampled steps are reached.  A trainer
+    fills ``_act`` (and ``_step_mask``), ``update``, ``_stats0``, ``_after_updates``, ``_extras`` and ``_values``."""
+
+    def _init_loop(self, env, seed, train_batch_size, learning_starts, updates_per_rollout, prioritized_replay, beta, keep_last_batch):
+        cfg = env.config
+        self.env, self.seed = env, seed
+        self.B, self.T = cfg['batch_size'], cfg['max_steps']
+        self.M = _default_minibatch(self.B, self.T, train_batch_size)
+        self.OD = _obs_width(env)
+        self.learning_starts, self.updates_per_rollout = int(learning_starts), int(updates_per_rollout)
+        self.prioritized, self.beta = bool(prioritized_replay), float(beta)
+        self.keep_last_batch, self.last_batch = keep_last_batch, None
+        self._pending = []
+        self.iteration = 0
+        self._rollouts = 0
+        self.timesteps = 0                  # sampled env steps (RLlib's num_steps_sampled)
+        self.num_updates = 0
+
+    def _step_mask(self, sl):
+        """The packed action mask of the current observation, written into rows ``sl`` of the rollout buffer (None: no mask)."""
+        return None
+
+    def _episode(self, explore, step0, reset_file=False):
+        """One complete-episode rollout into the rollout buffers -> mean episode reward (device scalar)."""
+        B, T = self.B, self.T
+        b = self.buf
+        obs = self.env.reset(reset_file=True) if reset_file else self.env.reset()
+        for t in range(T):
+            obs_t = obs['obs'] if isinstance(obs, dict) else obs
+            sl = slice(t * B, (t + 1) * B)
+            mask = self._step_mask(sl)
+            b['obs'][sl] = obs_t
+            a = self._act(explore, sl, mask, t, step0 + t)
+            obs, reward, done, info = self.env.step(a)
+            b['rew'][sl] = reward
+        return b['rew'].view(T, B).sum(dim=0).mean()
+
+    def _eval_batch(self, k):
+        return self._episode(False, 0, reset_file=k == 0)
+
+    def _sample(self, **kw):
+        # (the replay draws share the counter RNG of the action noise: a seed of their own keeps them apart from the noise of row = draw)
+        return self.replay.sample(self.M, prioritized=self.prioritized, beta=self.beta, seed=self.seed + 0x5bd1e995, step=self.num_updates,
+                                  out=self._batch, **kw)
+
+    def _keep(self, b):
+        self.last_batch = dict((k, v.clone()) for k, v in b.items() if v is not None)
+
+    def _after_updates(self):
+        pass
+
+    def train_iteration(self):
+        """One rollout, one push, ``updates_per_rollout`` updates once ``learning_starts`` sampled steps are reached, then
+        ``_after_updates``.  Returns a ``LazyStats`` mapping (``_values``); nothing here waits for the GPU."""
+        mean_reward = self._episode(True, self._rollouts * self.T)
+        self._rollouts += 1
+        self._settle()
+        self.replay.push(*[self.buf[k] for k in self._columns])
+        self.timesteps += self.B * self.T
+        self.iteration += 1
+        stats = self._stats0()
+        trained = self.timesteps >= self.learning_starts
+        if trained:
+            for _ in range(self.updates_per_rollout):
+                stats = self.update()
+        self._after_updates()
+        return self._submit(mean_reward, stats, buffer_rows=self.replay.rows, num_updates=self.num_updates, **self._extras(trained))
+
+
+class DQNTrainer(_ReplayTrainer):
     """Online DQN on the action-masked FC net (rllib_mask_model.py:7-64) over the zero-copy discrete-action env, with the
     reference's merged RLlib 1.5.1 configuration (script/modelfree_train.py:106-133 over the DQN defaults) as defaults: gamma 1,
     lr 5e-4, Adam eps 1e-8, grad_clip 40 per variable, double_q, n_step 1, buffer_size 100000, target_network_update_freq 200
@@ -557,81 +690,59 @@ class DQNTrainer(_DeferredStats):
     The replay ring holds whole rollouts: max(1, buffer_size // (B * T)) of them (the one deviation from RLlib's per-timestep
     ring)."""
 
+    _columns = ('obs', 'mask', 'act', 'rew')
+
     def __init__(self, env, hidden=64, seed=0, init_seed=0, lr=5e-4, gamma=1.0, adam_eps=1e-8, grad_clip=40.0, double_q=True, n_step=1,
                  buffer_size=100000, target_network_update_freq=200, learning_starts=1000, train_batch_size=None,
                  prioritized_replay=True, prioritized_replay_alpha=0.6, prioritized_replay_beta=0.4, softq_temperature=1.0,
                  updates_per_rollout=1, keep_last_batch=False):
-        cfg = env.config
-        assert cfg.get('return_tensors', False) and not cfg.get('support_conti_env', False), \
-            "DQNTrainer needs the zero-copy discrete-action env (config['return_tensors'] = True)"
+        _require_env(env.config, DISCRETE_ENV_MESSAGE % 'DQNTrainer')
         if n_step != 1:
             raise ValueError("DQNTrainer implements n_step = 1 (the reference's setting, modelfree_train.py:117); got %r" % (n_step,))
         if softq_temperature != 1.0:
             raise ValueError("DQNTrainer explores with SoftQ at temperature 1.0 (RLlib's default); got %r" % (softq_temperature,))
-        self.env = env
-        self.B, self.T, self.A = cfg['batch_size'], cfg['max_steps'], cfg['action_size']
-        self.seed, self.lr, self.gamma, self.adam_eps, self.grad_clip = seed, float(lr), float(gamma), float(adam_eps), float(grad_clip)
-        self.double_q, self.prioritized, self.beta = bool(double_q), bool(prioritized_replay), float(prioritized_replay_beta)
-        self.target_network_update_freq, self.learning_starts = int(target_network_update_freq), int(learning_starts)
-        self.updates_per_rollout = int(updates_per_rollout)
-        self.M = int(train_batch_size) if train_batch_size is not None else min(self.B * self.T, 1024)
-        self.keep_last_batch, self.last_batch = keep_last_batch, None
-        self._pending = []
-        self._kl_coeff, self.kl_target = 0.0, 0.0            # (unused: the deferred-statistics base carries PPO's)
-        space = env.observation_space
-        space = space.spaces['obs'] if hasattr(space, 'spaces') else space
-        self.OD = int(space.shape[0])
-        self.policy = D.DevicePolicy(self.OD, hidden, self.A, max_rows=max(self.M, self.B), seed=init_seed)
-        dev = self.policy.device
+        self._init_loop(env, seed, train_batch_size, learning_starts, updates_per_rollout, prioritized_replay, prioritized_replay_beta,
+                        keep_last_batch)
+        self.A, self.n_step = env.config['action_size'], 1
+        self.lr, self.gamma, self.adam_eps, self.grad_clip = float(lr), float(gamma), float(adam_eps), float(grad_clip)
+        self.double_q, self.target_network_update_freq = bool(double_q), int(target_network_update_freq)
+        self._make_net(hidden, init_seed)
+        dev = self.device = self.policy.device
         self.replay = D.DeviceReplay(self.OD, self.A, self.T, self.B, buffer_size=buffer_size, alpha=prioritized_replay_alpha, device=dev)
+        self._owned = (self.policy, self.replay)
         N = self.B * self.T
         self.buf = dict(obs=torch.empty((N, self.OD), dtype=torch.float32, device=dev),
                         mask=torch.empty((N, self.policy.W), dtype=torch.int32, device=dev),
                         act=torch.empty(N, dtype=torch.int32, device=dev),
                         rew=torch.empty(N, dtype=torch.float64, device=dev))
-        self._logp = torch.empty(self.B, dtype=torch.float32, device=dev)
-        self._val = torch.empty(self.B, dtype=torch.float32, device=dev)
         self._batch = self.replay.new_batch(self.M)
         self._td = torch.empty(self.M, dtype=torch.float32, device=dev)
         self.grad = torch.empty(self.policy.n_params, dtype=torch.float32, device=dev)
-        self.iteration = 0
-        self._rollouts = 0
-        self.timesteps = 0                  # sampled env steps (RLlib's num_steps_sampled)
-        self.num_updates = 0
         self.num_target_updates = 0
         self._last_target_sync = 0
         if rdist.collectives_active():
-            Trainer.sync_replicas(self)
+            sync_policy_replicas(self.policy)
         self.target = self.policy.params()                  # the target net starts as a copy of the online one
+
+    def _make_net(self, hidden, init_seed):
+        """The online network ``policy`` and what its act call writes besides the action."""
+        self.policy = D.DevicePolicy(self.OD, hidden, self.A, max_rows=max(self.M, self.B), seed=init_seed)
+        self._logp = torch.empty(self.B, dtype=torch.float32, device=self.policy.device)
+        self._val = torch.empty(self.B, dtype=torch.float32, device=self.policy.device)
 
     def params(self):
         self._settle()
         return self.policy.params()
 
-    def close(self):
-        try:
-            self._settle()
-        finally:
-            self.policy.close()
-            self.replay.close()
+    def _step_mask(self, sl):
+        return self.env.samples._live().obs_mask_bits(out=self.buf['mask'][sl])
 
-    def _episode(self, greedy, step0, reset_file=False):
-        """One complete-episode rollout into the rollout buffers -> mean episode reward (device scalar)."""
-        B, T = self.B, self.T
+    def _act(self, explore, sl, mask, t, step):
+        """SoftQ at temperature 1 (= the net's own categorical draw), or the greedy action."""
         b = self.buf
-        obs = self.env.reset(reset_file=True) if reset_file else self.env.reset()
-        for t in range(T):
-            obs_t = obs['obs'] if isinstance(obs, dict) else obs
-            sl = slice(t * B, (t + 1) * B)
-            mask = self.env.samples._live().obs_mask_bits(out=b['mask'][sl])
-            b['obs'][sl] = obs_t
-            if greedy:
-                a = self.policy.greedy(b['obs'][sl], mask, out=b['act'][sl])[0]
-            else:
-                a = self.policy.act(b['obs'][sl], mask, seed=self.seed, step=step0 + t, out=(b['act'][sl], self._logp, self._val, None))[0]
-            obs, reward, done, info = self.env.step(a)
-            b['rew'][sl] = reward
-        return b['rew'].view(T, B).sum(dim=0).mean()
+        if explore:
+            return self.policy.act(b['obs'][sl], mask, seed=self.seed, step=step, out=(b['act'][sl], self._logp, self._val, None))[0]
+        return self.policy.greedy(b['obs'][sl], mask, out=b['act'][sl])[0]
 
     def sync_target(self):
         """target <- online, a device-to-device copy."""
@@ -639,18 +750,19 @@ class DQNTrainer(_DeferredStats):
         self._last_target_sync = self.timesteps
         self.num_target_updates += 1
 
+    def _loss_grad(self, b, w):
+        """-> (grad, td, stats[4] device sums of {w * huber, Q(s)[a], y, |td|} over the minibatch, a* or None)."""
+        return self.policy.dqn_loss_grad(self.target, b['obs'], b['action'], b['reward'], b['done'], b['next_obs'], b['next_mask'],
+                                         weights=w, gamma=self.gamma, double_q=self.double_q, grad_out=self.grad, td_out=self._td,
+                                         want_next_action=self.keep_last_batch)
+
     def update(self):
-        """One learner step: sample -> loss / gradient -> all-reduce (data parallel) -> per-variable-clipped Adam -> priorities.
-        -> stats[4] device sums of {w * huber, Q(s)[a], y, |td|} over the minibatch."""
-        # (the replay draws share the policy's counter RNG: a seed of their own keeps them apart from the action noise of row = draw)
-        b = self.replay.sample(self.M, prioritized=self.prioritized, beta=self.beta, seed=self.seed + 0x5bd1e995, step=self.num_updates,
-                               out=self._batch)
-        w = b['weight'] if self.prioritized else None
-        g, td, stats, astar = self.policy.dqn_loss_grad(self.target, b['obs'], b['action'], b['reward'], b['done'], b['next_obs'],
-                                                        b['next_mask'], weights=w, gamma=self.gamma, double_q=self.double_q,
-                                                        grad_out=self.grad, td_out=self._td, want_next_action=self.keep_last_batch)
+        """One learner step: (n-step) sample -> loss / gradient (``_loss_grad``) -> all-reduce (data parallel) -> per-variable-clipped
+        Adam -> priorities.  -> the loss call's stats[4]."""
+        b = self._sample(n_step=self.n_step, gamma=self.gamma)
+        g, td, stats, astar = self._loss_grad(b, b['weight'] if self.prioritized else None)
         if self.keep_last_batch:
-            self.last_batch = dict((k, v.clone()) for k, v in b.items() if v is not None)
+            self._keep(b)
             self.last_batch.update(td=td.clone(), next_action=astar)
         if rdist.collectives_active():
             rdist.allreduce_mean_(g)
@@ -660,55 +772,23 @@ class DQNTrainer(_DeferredStats):
         self.num_updates += 1
         return stats
 
-    def train_iteration(self):
-        """One rollout, one push, ``updates_per_rollout`` updates once ``learning_starts`` sampled steps are reached, the target copy
-        when due.  Returns a ``LazyStats`` mapping (episode_reward_mean, td_loss, mean_q, mean_td_abs of the last update - 0 before the
-        first -, buffer_rows, num_updates, num_target_updates, iteration); nothing here waits for the GPU."""
-        mean_reward = self._episode(False, self._rollouts * self.T)
-        self._rollouts += 1
-        self._settle()
-        b = self.buf
-        self.replay.push(b['obs'], b['mask'], b['act'], b['rew'])
-        self.timesteps += self.B * self.T
-        self.iteration += 1
-        stats = torch.zeros(4, dtype=torch.float32, device=b['obs'].device)
-        trained = self.timesteps >= self.learning_starts
-        if trained:
-            for _ in range(self.updates_per_rollout):
-                stats = self.update()
+    def _stats0(self):
+        return torch.zeros(4, dtype=torch.float32, device=self.device)
+
+    def _after_updates(self):
+        """The target copy when due."""
         if self.timesteps - self._last_target_sync >= self.target_network_update_freq:
             self.sync_target()
-        extra = dict(ppo=False, kl_mean=None, rows=self.M if trained and self.updates_per_rollout > 0 else 0,
-                     buffer_rows=self.replay.rows, num_updates=self.num_updates, num_target_updates=self.num_target_updates)
-        return LazyStats(self, self._submit(mean_reward, stats, 1, extra))
 
-    def _settle(self):
-        while self._pending:
-            tok = self._pending.pop(0)
-            tok['ev'].synchronize()
-            v = tok['pin'].numpy().copy()
-            if v[-1] >= 1000.0:
-                raise RuntimeError(rdist.ROW_OVERFLOW_MESSAGE)
-            s, n = v[1:-1], max(tok['rows'], 1)
-            tok['values'] = {'episode_reward_mean': float(v[0]), 'td_loss': float(s[0]) / n, 'mean_q': float(s[1]) / n,
-                             'mean_td_abs': float(s[3]) / n, 'buffer_rows': tok['buffer_rows'], 'num_updates': tok['num_updates'],
-                             'num_target_updates': tok['num_target_updates'], 'iteration': tok['iteration']}
+    def _extras(self, trained):
+        return dict(rows=self.M if trained and self.updates_per_rollout > 0 else 0, num_target_updates=self.num_target_updates)
 
-    def evaluate(self, episodes=None, seed=0):
-        """Mean episode reward of greedy (explore: False) episodes: ceil(episodes / B) batches from the start of the record file
-        with the env's record sampling seeded by ``seed``, so two calls on the same parameters give the same number.  Leaves the
-        global numpy RNG as it found it; the env's record cursor restarts."""
-        self._settle()
-        n = 1 if episodes is None else max(1, int(math.ceil(float(episodes) / self.B)))
-        state = np.random.get_state()
-        try:
-            np.random.seed(seed)
-            total = torch.zeros((), dtype=torch.float64, device=self.buf['obs'].device)
-            for k in range(n):
-                total += self._episode(True, 0, reset_file=k == 0)
-        finally:
-            np.random.set_state(state)
-        return float(total.item()) / n
+    def _values(self, tok, mean_reward, s):
+        """episode_reward_mean, td_loss, mean_q, mean_td_abs of the last update - 0 before the first -, buffer_rows, num_updates,
+        num_target_updates (and iteration)."""
+        n = max(tok['rows'], 1)
+        return {'episode_reward_mean': mean_reward, 'td_loss': float(s[0]) / n, 'mean_q': float(s[1]) / n, 'mean_td_abs': float(s[3]) / n,
+                'buffer_rows': tok['buffer_rows'], 'num_updates': tok['num_updates'], 'num_target_updates': tok['num_target_updates']}
 
 
 class RainbowTrainer(DQNTrainer):
@@ -734,103 +814,45 @@ class RainbowTrainer(DQNTrainer):
                  target_network_update_freq=500, learning_starts=1000, train_batch_size=None, prioritized_replay=True,
                  prioritized_replay_alpha=0.6, prioritized_replay_beta=0.4, softq_temperature=1.0, updates_per_rollout=1,
                  keep_last_batch=False):
-        cfg = env.config
-        assert cfg.get('return_tensors', False) and not cfg.get('support_conti_env', False), \
-            "RainbowTrainer needs the zero-copy discrete-action env (config['return_tensors'] = True)"
+        _require_env(env.config, DISCRETE_ENV_MESSAGE % 'RainbowTrainer')
         if noisy:
             raise ValueError("RainbowTrainer: noisy layers are not implemented (the reference leaves RLlib's noisy = False)")
         if int(num_atoms) < 2:
             raise ValueError("RainbowTrainer is the distributional learner (num_atoms >= 2); num_atoms = 1 is DQNTrainer")
         if int(n_step) < 1 or float(softq_temperature) <= 0.0:
             raise ValueError("RainbowTrainer: n_step >= 1 and softq_temperature > 0 (got %r, %r)" % (n_step, softq_temperature))
-        self.env = env
-        self.B, self.T, self.A = cfg['batch_size'], cfg['max_steps'], cfg['action_size']
-        self.seed, self.lr, self.gamma, self.adam_eps, self.grad_clip = seed, float(lr), float(gamma), float(adam_eps), float(grad_clip)
-        self.double_q, self.prioritized, self.beta = bool(double_q), bool(prioritized_replay), float(prioritized_replay_beta)
+        self._net_kw = dict(num_atoms=num_atoms, v_min=v_min, v_max=v_max, dueling=dueling, trunk=trunk, stream_hidden=stream_hidden)
+        DQNTrainer.__init__(self, env, seed=seed, init_seed=init_seed, lr=lr, gamma=gamma, adam_eps=adam_eps, grad_clip=grad_clip,
+                            double_q=double_q, buffer_size=buffer_size, target_network_update_freq=target_network_update_freq,
+                            learning_starts=learning_starts, train_batch_size=train_batch_size, prioritized_replay=prioritized_replay,
+                            prioritized_replay_alpha=prioritized_replay_alpha, prioritized_replay_beta=prioritized_replay_beta,
+                            updates_per_rollout=updates_per_rollout, keep_last_batch=keep_last_batch)
         self.n_step, self.masked, self.temperature = int(n_step), bool(masked), float(softq_temperature)
         self.gamma_n = float(np.float32(self.gamma ** self.n_step))
-        self.target_network_update_freq, self.learning_starts = int(target_network_update_freq), int(learning_starts)
-        self.updates_per_rollout = int(updates_per_rollout)
-        self.M = int(train_batch_size) if train_batch_size is not None else min(self.B * self.T, 1024)
-        self.keep_last_batch, self.last_batch = keep_last_batch, None
-        self._pending = []
-        self._kl_coeff, self.kl_target = 0.0, 0.0            # (unused: the deferred-statistics base carries PPO's)
-        space = env.observation_space
-        space = space.spaces['obs'] if hasattr(space, 'spaces') else space
-        self.OD = int(space.shape[0])
-        self.policy = D.DeviceDistQ(self.OD, self.A, max_rows=max(self.M, self.B), num_atoms=num_atoms, v_min=v_min, v_max=v_max,
-                                    dueling=dueling, trunk=trunk, stream_hidden=stream_hidden, seed=init_seed)
-        dev = self.policy.device
-        self.replay = D.DeviceReplay(self.OD, self.A, self.T, self.B, buffer_size=buffer_size, alpha=prioritized_replay_alpha, device=dev)
-        N = self.B * self.T
-        self.buf = dict(obs=torch.empty((N, self.OD), dtype=torch.float32, device=dev),
-                        mask=torch.full((N, self.policy.W), -1, dtype=torch.int32, device=dev),       # all ones unless ``masked``
-                        act=torch.empty(N, dtype=torch.int32, device=dev),
-                        rew=torch.empty(N, dtype=torch.float64, device=dev))
-        self._batch = self.replay.new_batch(self.M)
-        self._td = torch.empty(self.M, dtype=torch.float32, device=dev)
-        self.grad = torch.empty(self.policy.n_params, dtype=torch.float32, device=dev)
-        self.iteration = 0
-        self._rollouts = 0
-        self.timesteps = 0
-        self.num_updates = 0
-        self.num_target_updates = 0
-        self._last_target_sync = 0
-        if rdist.collectives_active():
-            Trainer.sync_replicas(self)
-        self.target = self.policy.params()                  # the target net starts as a copy of the online one
+        self.buf['mask'].fill_(-1)                          # all ones unless ``masked``
 
-    def _episode(self, greedy, step0, reset_file=False):
-        """One complete-episode rollout into the rollout buffers -> mean episode reward (device scalar)."""
-        B, T = self.B, self.T
+    def _make_net(self, hidden, init_seed):
+        self.policy = D.DeviceDistQ(self.OD, self.A, max_rows=max(self.M, self.B), seed=init_seed, **self._net_kw)
+
+    def _step_mask(self, sl):
+        return DQNTrainer._step_mask(self, sl) if self.masked else None
+
+    def _act(self, explore, sl, mask, t, step):
+        """SoftQ over Q at ``temperature``, or the greedy action."""
+        if not explore:
+            return DQNTrainer._act(self, False, sl, mask, t, step)
         b = self.buf
-        obs = self.env.reset(reset_file=True) if reset_file else self.env.reset()
-        for t in range(T):
-            obs_t = obs['obs'] if isinstance(obs, dict) else obs
-            sl = slice(t * B, (t + 1) * B)
-            mask = self.env.samples._live().obs_mask_bits(out=b['mask'][sl]) if self.masked else None
-            b['obs'][sl] = obs_t
-            if greedy:
-                a = self.policy.greedy(b['obs'][sl], mask, out=b['act'][sl])[0]
-            else:
-                a = self.policy.act(b['obs'][sl], mask, temperature=self.temperature, seed=self.seed, step=step0 + t, out=b['act'][sl])[0]
-            obs, reward, done, info = self.env.step(a)
-            b['rew'][sl] = reward
-        return b['rew'].view(T, B).sum(dim=0).mean()
+        return self.policy.act(b['obs'][sl], mask, temperature=self.temperature, seed=self.seed, step=step, out=b['act'][sl])[0]
 
-    def update(self):
-        """One learner step: n-step sample -> loss / gradient -> all-reduce (data parallel) -> per-variable-clipped Adam ->
-        priorities.  -> stats[4] device sums of {w * td, Q(s)[a], sum_i z_i m_i, td} over the minibatch."""
-        b = self.replay.sample(self.M, prioritized=self.prioritized, beta=self.beta, seed=self.seed + 0x5bd1e995, step=self.num_updates,
-                               out=self._batch, n_step=self.n_step, gamma=self.gamma)
-        w = b['weight'] if self.prioritized else None
-        g, td, stats, astar = self.policy.loss_grad(self.target, b['obs'], b['action'], b['reward'], b['done'], b['next_obs'],
-                                                    b['next_mask'] if self.masked else None, weights=w, gamma_n=self.gamma_n,
-                                                    double_q=self.double_q, grad_out=self.grad, td_out=self._td,
-                                                    want_next_action=self.keep_last_batch)
-        if self.keep_last_batch:
-            self.last_batch = dict((k, v.clone()) for k, v in b.items() if v is not None)
-            self.last_batch.update(td=td.clone(), next_action=astar)
-        if rdist.collectives_active():
-            rdist.allreduce_mean_(g)
-        self.policy.adam_step_clip_by_var(g, lr=self.lr, eps=self.adam_eps, var_clip=self.grad_clip)
-        if self.prioritized:
-            self.replay.update_priorities(b['idx'], td)
-        self.num_updates += 1
-        return stats
+    def _loss_grad(self, b, w):
+        """-> (grad, td, stats[4] device sums of {w * td, Q(s)[a], sum_i z_i m_i, td} over the minibatch, a* or None)."""
+        return self.policy.loss_grad(self.target, b['obs'], b['action'], b['reward'], b['done'], b['next_obs'],
+                                     b['next_mask'] if self.masked else None, weights=w, gamma_n=self.gamma_n, double_q=self.double_q,
+                                     grad_out=self.grad, td_out=self._td, want_next_action=self.keep_last_batch)
 
-    def _settle(self):
-        while self._pending:
-            tok = self._pending.pop(0)
-            tok['ev'].synchronize()
-            v = tok['pin'].numpy().copy()
-            if v[-1] >= 1000.0:
-                raise RuntimeError(rdist.ROW_OVERFLOW_MESSAGE)
-            s, n = v[1:-1], max(tok['rows'], 1)
-            tok['values'] = {'episode_reward_mean': float(v[0]), 'td_loss': float(s[0]) / n, 'mean_q': float(s[1]) / n,
-                             'mean_target': float(s[2]) / n, 'mean_td_abs': float(s[3]) / n, 'buffer_rows': tok['buffer_rows'],
-                             'num_updates': tok['num_updates'], 'num_target_updates': tok['num_target_updates'],
-                             'iteration': tok['iteration']}
+    def _values(self, tok, mean_reward, s):
+        """``DQNTrainer``'s and mean_target, the mean of the projected target distribution."""
+        return dict(DQNTrainer._values(self, tok, mean_reward, s), mean_target=float(s[2]) / max(tok['rows'], 1))
 
 
 # ---- TD3 / DDPG -----------------------------------------------------------------------------------------------------------------
@@ -980,7 +1002,7 @@ class TD3Learner(object):
         return self.metrics
 
 
-class TD3Trainer(_DeferredStats):
+class TD3Trainer(_ReplayTrainer):
     """Online TD3 / DDPG over the zero-copy continuous-action env (``support_conti_env``, plain 256-wide observations): the third
     learner family of script/modelfree_train.py (:46-48, :79-105; modelfree_trainer.py:25-28).  The action is the 32-d vector in
     Box(-1, 1) that the env resolves with its masked K-NN.  Defaults are the reference's merged RLlib 1.5.1 configuration
@@ -998,6 +1020,8 @@ class TD3Trainer(_DeferredStats):
     Deviations from RLlib: the replay ring holds whole rollouts (max(1, buffer_size // (B * T)) of them); the OU state is one [E]
     vector PER ENV (RLlib: one variable shaped like a single action), never reset between episodes."""
 
+    _columns = ('obs', 'act', 'rew')
+
     def __init__(self, env, algo='TD3', actor_hiddens=(400, 300), critic_hiddens=(400, 300), seed=0, init_seed=0, actor_lr=1e-3,
                  critic_lr=1e-3, gamma=1.0, twin_q=None, policy_delay=None, smooth_target_policy=None, target_noise=None,
                  target_noise_clip=None, tau=None, l2_reg=None, use_huber=False, huber_threshold=1.0, n_step=1, buffer_size=None,
@@ -1009,28 +1033,19 @@ class TD3Trainer(_DeferredStats):
         if n_step != 1:
             raise ValueError("TD3Trainer implements n_step = 1 (the reference's setting); got %r" % (n_step,))
         cfg = env.config
-        assert cfg.get('return_tensors', False) and cfg.get('support_conti_env', False), \
-            "TD3Trainer needs the zero-copy continuous-action env (config['return_tensors'] and ['support_conti_env'] = True)"
+        _require_env(cfg, "TD3Trainer needs the zero-copy continuous-action env (config['return_tensors'] and ['support_conti_env'] = True)",
+                     conti=True)
         pre = dict(TD3_PRESETS[algo])
         given = dict(twin_q=twin_q, policy_delay=policy_delay, smooth_target_policy=smooth_target_policy, target_noise=target_noise,
                      target_noise_clip=target_noise_clip, tau=tau, l2_reg=l2_reg, buffer_size=buffer_size,
                      prioritized_replay=prioritized_replay, learning_starts=learning_starts, random_timesteps=random_timesteps)
         pre.update((k, v) for k, v in given.items() if v is not None)
-        self.algo, self.env = algo, env
-        self.policy_delay, self.buffer_size = int(pre['policy_delay']), int(pre['buffer_size'])
-        self.prioritized, self.beta = bool(pre['prioritized_replay']), float(prioritized_replay_beta)
-        self.learning_starts, self.random_timesteps = int(pre['learning_starts']), int(pre['random_timesteps'])
+        self._init_loop(env, seed, train_batch_size, pre['learning_starts'], updates_per_rollout, pre['prioritized_replay'],
+                        prioritized_replay_beta, keep_last_batch)
+        self.algo, self.E = algo, cfg['action_emb_size']
+        self.policy_delay, self.buffer_size, self.random_timesteps = int(pre['policy_delay']), int(pre['buffer_size']), int(pre['random_timesteps'])
         self.ou_theta, self.ou_sigma, self.ou_base_scale = float(ou_theta), float(ou_sigma), float(ou_base_scale)
         self.initial_scale, self.final_scale, self.scale_timesteps = float(initial_scale), float(final_scale), int(scale_timesteps)
-        self.updates_per_rollout = int(updates_per_rollout)
-        self.B, self.T, self.E = cfg['batch_size'], cfg['max_steps'], cfg['action_emb_size']
-        self.M = int(train_batch_size) if train_batch_size is not None else min(self.B * self.T, 1024)
-        self.seed = seed
-        self.keep_last_batch, self.last_batch = keep_last_batch, None
-        self._pending = []
-        space = env.observation_space
-        space = space.spaces['obs'] if hasattr(space, 'spaces') else space
-        self.OD = int(space.shape[0])
         OD, E, M = self.OD, self.E, self.M
         self.learner = TD3Learner(OD, E, M, twin_q=pre['twin_q'], smooth_target_policy=pre['smooth_target_policy'],
                                   target_noise=pre['target_noise'], target_noise_clip=pre['target_noise_clip'], tau=pre['tau'],
@@ -1040,6 +1055,7 @@ class TD3Trainer(_DeferredStats):
         self.actor = self.learner.actor
         dev = self.device = self.actor.device
         self.replay = D.DeviceContiReplay(OD, E, self.T, self.B, buffer_size=self.buffer_size, alpha=prioritized_replay_alpha, device=dev)
+        self._owned = (self.learner, self.replay)
         N = self.B * self.T
         self.buf = dict(obs=torch.empty((N, OD), dtype=torch.float32, device=dev), act=torch.empty((N, E), dtype=torch.float32, device=dev),
                         rew=torch.empty(N, dtype=torch.float64, device=dev))
@@ -1048,10 +1064,6 @@ class TD3Trainer(_DeferredStats):
         self._batch = self.replay.new_batch(M)
         self._gen = torch.Generator(device=dev)
         self._gen.manual_seed(int(seed) * 7919 + 17)
-        self.iteration = 0
-        self._rollouts = 0
-        self.timesteps = 0                  # sampled env steps (RLlib's num_steps_sampled)
-        self.num_updates = 0
         if rdist.collectives_active():
             self.learner.sync_replicas(0)                   # replicas start identical (shared init_seed; the Adam state is zero)
         self.learner.sync_targets()
@@ -1061,50 +1073,33 @@ class TD3Trainer(_DeferredStats):
         self._settle()
         return self.learner.flat_params()
 
-    def close(self):
-        try:
-            self._settle()
-        finally:
-            self.learner.close()
-            self.replay.close()
-
     def scale_at(self, timestep):
         """ou_base_scale x the annealed scale at a sampled timestep: the ``scale`` of rl4rs_explore_ou, computed on the host."""
         return self.ou_base_scale * ou_scale(timestep, self.random_timesteps, self.initial_scale, self.final_scale, self.scale_timesteps)
 
-    def _episode(self, explore, step0, reset_file=False):
-        """One complete-episode rollout into the rollout buffers -> mean episode reward (device scalar)."""
-        B, T = self.B, self.T
+    def _act(self, explore, sl, mask, t, step):
+        """The actor's own action; exploring: plus OU noise, or uniformly random during the first ``random_timesteps``."""
         b = self.buf
-        obs = self.env.reset(reset_file=True) if reset_file else self.env.reset()
-        for t in range(T):
-            obs_t = obs['obs'] if isinstance(obs, dict) else obs
-            sl = slice(t * B, (t + 1) * B)
-            b['obs'][sl] = obs_t
-            a = b['act'][sl]
-            if explore:
-                ts = self.timesteps + t * B
-                random_phase = ts < self.random_timesteps
-                if not random_phase:
-                    self.actor.forward(b['obs'][sl], out=self._det)
-                D.explore_ou(self._det, self.ou_state, self.ou_theta, self.ou_sigma, self.scale_at(ts), seed=self.seed, step=step0 + t,
-                             random_phase=random_phase, out=a)
-            else:
-                self.actor.forward(b['obs'][sl], out=a)
-            obs, reward, done, info = self.env.step(a)
-            b['rew'][sl] = reward
-        return b['rew'].view(T, B).sum(dim=0).mean()
+        a = b['act'][sl]
+        if explore:
+            ts = self.timesteps + t * self.B
+            random_phase = ts < self.random_timesteps
+            if not random_phase:
+                self.actor.forward(b['obs'][sl], out=self._det)
+            D.explore_ou(self._det, self.ou_state, self.ou_theta, self.ou_sigma, self.scale_at(ts), seed=self.seed, step=step,
+                         random_phase=random_phase, out=a)
+        else:
+            self.actor.forward(b['obs'][sl], out=a)
+        return a
 
     def update(self):
         """One learner step: sample -> ``TD3Learner.update`` -> priorities.  -> the learner's metrics buffer."""
         M, L = self.M, self.learner
-        # (the replay draws share the counter RNG of the exploration noise: a seed of their own keeps them apart)
-        b = self.replay.sample(M, prioritized=self.prioritized, beta=self.beta, seed=self.seed + 0x5bd1e995, step=self.num_updates,
-                               out=self._batch)
+        b = self._sample()
         noise = torch.randn((M, self.E), generator=self._gen, device=self.device, dtype=torch.float32) if L.smooth else None
         do_actor = self.num_updates % self.policy_delay == 0
         if self.keep_last_batch:
-            self.last_batch = dict((k, v.clone()) for k, v in b.items() if v is not None)
+            self._keep(b)
             self.last_batch.update(noise=noise.clone() if noise is not None else None, do_actor=do_actor)
         L.update(b, noise=noise, weights=b['weight'] if self.prioritized else None, do_actor=do_actor)
         if self.prioritized:
@@ -1114,56 +1109,21 @@ class TD3Trainer(_DeferredStats):
         self.num_updates += 1
         return L.metrics
 
-    def train_iteration(self):
-        """One rollout, one push, ``updates_per_rollout`` updates once ``learning_starts`` sampled steps are reached.  Returns a
-        ``LazyStats`` mapping (episode_reward_mean; critic_loss, mean_q, mean_td_abs of the last update and actor_loss of the last
-        actor step, without the L2 terms, 0 before the first; buffer_rows, num_updates, iteration); nothing here waits for the GPU."""
-        mean_reward = self._episode(True, self._rollouts * self.T)
-        self._rollouts += 1
-        self._settle()
-        b = self.buf
-        self.replay.push(b['obs'], b['act'], b['rew'])
-        self.timesteps += self.B * self.T
-        self.iteration += 1
-        if self.timesteps >= self.learning_starts:
-            for _ in range(self.updates_per_rollout):
-                self.update()
-        extra = dict(rows=self.M, buffer_rows=self.replay.rows, num_updates=self.num_updates)
-        return LazyStats(self, self._submit(mean_reward, self.learner.metrics, 1, extra))
+    def _stats0(self):
+        return self.learner.metrics
 
-    def _status_word(self, dev):
-        return torch.zeros(1, dtype=torch.float64, device=dev)      # (the amlp networks run no persistent pass)
+    def _extras(self, trained):
+        return dict(rows=self.M)
 
-    def _settle(self):
-        while self._pending:
-            tok = self._pending.pop(0)
-            tok['ev'].synchronize()
-            v = tok['pin'].numpy().copy()
-            if v[-1] >= 1000.0:
-                raise RuntimeError(rdist.ROW_OVERFLOW_MESSAGE)
-            s, n = v[1:-1], float(tok['rows'])
-            tok['values'] = {'episode_reward_mean': float(v[0]), 'critic_loss': float(s[0]) / n, 'actor_loss': float(s[4]) / n,
-                             'mean_q': float(s[1]) / n, 'mean_td_abs': float(s[3]) / n, 'buffer_rows': tok['buffer_rows'],
-                             'num_updates': tok['num_updates'], 'iteration': tok['iteration']}
-
-    def evaluate(self, episodes=None, seed=0):
-        """Mean episode reward of deterministic episodes (the actor's own action, no noise): ceil(episodes / B) batches from the start
-        of the record file with the env's record sampling seeded by ``seed``, so two calls on the same parameters give the same
-        number.  Leaves the global numpy RNG as it found it; the env's record cursor restarts."""
-        self._settle()
-        n = 1 if episodes is None else max(1, int(math.ceil(float(episodes) / self.B)))
-        state = np.random.get_state()
-        try:
-            np.random.seed(seed)
-            total = torch.zeros((), dtype=torch.float64, device=self.device)
-            for k in range(n):
-                total += self._episode(False, 0, reset_file=k == 0)
-        finally:
-            np.random.set_state(state)
-        return float(total.item()) / n
+    def _values(self, tok, mean_reward, s):
+        """episode_reward_mean; critic_loss, mean_q, mean_td_abs of the last update and actor_loss of the last actor step, without the
+        L2 terms, 0 before the first; buffer_rows, num_updates (and iteration)."""
+        n = float(tok['rows'])
+        return {'episode_reward_mean': mean_reward, 'critic_loss': float(s[0]) / n, 'actor_loss': float(s[4]) / n, 'mean_q': float(s[1]) / n,
+                'mean_td_abs': float(s[3]) / n, 'buffer_rows': tok['buffer_rows'], 'num_updates': tok['num_updates']}
 
 
-class ExactKTrainer(_DeferredStats):
+class ExactKTrainer(_Evaluated):
     """Exact-K (script/exact_k_train.py, rl4rs/nets/exact_k) over the zero-copy discrete ``SlateRecEnv-v0`` (T = 9): the pointer-network
     generator emits the whole 9-item slate from the first observation, REINFORCE with the critic's prediction of the batch reward as
     baseline and a hill climb over ``samples`` sampled slates per user.  Defaults are the reference's: hidden_units 64, 4 heads,
@@ -1189,8 +1149,8 @@ class ExactKTrainer(_DeferredStats):
         if getattr(getattr(env, 'samples', None), 'is_seq', False) or cfg['max_steps'] != D.DeviceExactK.SLATE:
             raise ValueError("ExactKTrainer runs SlateRecEnv-v0 (max_steps 9) only: on SeqSlateRecEnv-v0 the reference script indexes its "
                              "9-wide slate with 36 steps and cannot run either")
-        if not cfg.get('return_tensors', False) or cfg.get('support_conti_env', False):
-            raise ValueError("ExactKTrainer needs the zero-copy discrete-action env (config['return_tensors'] = True, no conti env)")
+        _require_env(cfg, "ExactKTrainer needs the zero-copy discrete-action env (config['return_tensors'] = True, no conti env)",
+                     error=ValueError)
         for name, val, want in (('temperature', temperature, 1), ('num_glimpse', num_glimpse, 1), ('num_layers', num_layers, 1),
                                 ('use_mha', bool(use_mha), True)):
             if val != want:
@@ -1204,15 +1164,14 @@ class ExactKTrainer(_DeferredStats):
         self.seed, self.lr, self.critic_lr = seed, float(lr), float(critic_lr)
         self.samples, self.same_users = int(samples), bool(same_users)
         self._pending = []
-        self._kl_coeff, self.kl_target = 0.0, 0.0            # (unused: the deferred-statistics base carries PPO's)
-        space = env.observation_space
-        space = space.spaces['obs'] if hasattr(space, 'spaces') else space
-        self.OD = int(space.shape[0])
+        self.OD = _obs_width(env)
         catalog = env.samples._catalog
         self.policy = D.DeviceExactK(catalog.location_mask[:3], catalog.is_special, max_rows=self.B, obs_dim=self.OD, action_size=self.A,
                                      hidden_units=hidden_units, num_heads=num_heads, num_blocks=num_blocks, vocab=max(vocab, self.A),
                                      dropout_rate=dropout_rate, seed=init_seed)
-        self.critic = D.DeviceExactKCritic(self.B, obs_dim=self.OD, hidden=critic_hidden, seed=init_seed + 1, device=self.policy.device)
+        self.device = self.policy.device
+        self.critic = D.DeviceExactKCritic(self.B, obs_dim=self.OD, hidden=critic_hidden, seed=init_seed + 1, device=self.device)
+        self._owned = (self.policy, self.critic)
         self.iteration = 0
         self._decodes = 0
         self.skipped_total = 0
@@ -1221,13 +1180,6 @@ class ExactKTrainer(_DeferredStats):
     def params(self):
         self._settle()
         return self.policy.params()
-
-    def close(self):
-        try:
-            self._settle()
-        finally:
-            self.policy.close()
-            self.critic.close()
 
     def _obs(self, obs):
         obs = obs['obs'] if isinstance(obs, dict) else obs
@@ -1292,38 +1244,16 @@ class ExactKTrainer(_DeferredStats):
         self.iteration += 1
         self.last = dict(rewards=rewards, paths=paths, reward=reward, path=path, baseline=baseline, weights=w, states=states, obs0=obs0)
         vec = torch.stack([rewards[0].mean(), baseline.mean(), err.mean(), stats[0], stats[1], skip[0].to(torch.float32)])
-        return LazyStats(self, self._submit(reward.mean(), vec, 1, {}))
+        return self._submit(reward.mean(), vec)
 
-    def _status_word(self, dev):
-        return torch.zeros(1, dtype=torch.float64, device=dev)
+    def _values(self, tok, mean_reward, s):
+        self.skipped_total += int(s[5] != 0)
+        return {'episode_reward_mean': mean_reward, 'reward_first_climb': float(s[0]), 'baseline_mean': float(s[1]),
+                'critic_loss': float(s[2]), 'policy_loss': float(s[3]), 'invalid_targets': int(s[4]), 'skipped': int(s[5] != 0),
+                'skipped_total': self.skipped_total}
 
-    def _settle(self):
-        while self._pending:
-            tok = self._pending.pop(0)
-            tok['ev'].synchronize()
-            v = tok['pin'].numpy().copy()
-            if v[-1] >= 1000.0:
-                raise RuntimeError(rdist.ROW_OVERFLOW_MESSAGE)
-            s = v[1:-1]
-            self.skipped_total += int(s[5] != 0)
-            tok['values'] = {'episode_reward_mean': float(v[0]), 'reward_first_climb': float(s[0]), 'baseline_mean': float(s[1]),
-                             'critic_loss': float(s[2]), 'policy_loss': float(s[3]), 'invalid_targets': int(s[4]),
-                             'skipped': int(s[5] != 0), 'skipped_total': self.skipped_total, 'iteration': tok['iteration']}
-
-    def evaluate(self, episodes=None, seed=0):
-        """Mean episode reward of greedy slates: ceil(episodes / B) batches from the start of the record file with the env's record
-        sampling seeded by ``seed``; dropout stays on (as in the reference's eval stage) with a fixed mask stream, so two calls on the
-        same parameters give the same number.  Leaves the global numpy RNG as it found it; the env's record cursor restarts."""
-        self._settle()
-        n = 1 if episodes is None else max(1, int(math.ceil(float(episodes) / self.B)))
-        state = np.random.get_state()
-        try:
-            np.random.seed(seed)
-            total = torch.zeros((), dtype=torch.float64, device=self.policy.device)
-            for k in range(n):
-                obs0 = self._obs(self.env.reset(reset_file=True) if k == 0 else self.env.reset())
-                path, _ = self.policy.decode(obs0, greedy=True, seed=self.seed, step=k)
-                total += self._play(path).to(torch.float64).mean()
-        finally:
-            np.random.set_state(state)
-        return float(total.item()) / n
+    def _eval_batch(self, k):
+        """One batch of greedy slates; dropout stays on (as in the reference's eval stage) with a fixed mask stream."""
+        obs0 = self._obs(self.env.reset(reset_file=True) if k == 0 else self.env.reset())
+        path, _ = self.policy.decode(obs0, greedy=True, seed=self.seed, step=k)
+        return self._play(path).to(torch.float64).mean()
