@@ -298,7 +298,10 @@ enum {
                                                   in front of the head GEMM (bit-identical either way) */
     RL4RS_DIEN_OPT_NO_AUGRU_SHADOW = 1 << 21,  /* observation-sized forwards: category kernel and dense / q-side pair as launches of their own
                                                   in front of k_din_x, no shadow plane in the AUGRU launch (bit-identical either way) */
-    RL4RS_DIEN_OPT_ALL = (1 << 22) - 1
+    RL4RS_DIEN_OPT_NO_LAZY_EXPAND = 1 << 22,   /* row dedup, second tier: k_row_expand behind the head GEMM in every forward, instead of
+                                                  outputs that read the representative's row and internal rows completed by
+                                                  rl4rs_dien_buffer (bit-identical either way) */
+    RL4RS_DIEN_OPT_ALL = (1 << 23) - 1
 };
 
 /* Every mode accumulates in fp32 and meets the fp32 parity bar against the fp64 oracle (same measured error):
@@ -400,6 +403,10 @@ int rl4rs_dien_set_row_partition(rl4rs_dien* net, const int32_t* rep_dev, const 
  * so that its counts stay comparable between handles). */
 int rl4rs_dien_dedup_counts(rl4rs_dien* net, int64_t* launched, int64_t* carried);
 
+/* The launch plan of the last forward as one line of key=value tokens (which form every stage took: csrc/dien_plan.hpp,
+ * dien_plan_str); "" before the first forward. */
+int rl4rs_dien_last_plan(rl4rs_dien* net, char* buf, int32_t cap);
+
 /* softmax(obs @ out_w + out_b)[:, 1] of already computed 'simulator_obs' activations (dien.py:36):
  * obs_dev [R, 256] -> prob_dev [R]. */
 int rl4rs_dien_head_prob(rl4rs_dien* net, int32_t R, const float* obs_dev, float* prob_dev, void* stream);
@@ -420,6 +427,13 @@ enum {
                                      N_ACTIVE entries.  After a forward that took its partition from the caller
                                      (rl4rs_dien_set_row_partition) the three ids give the caller's buffers, n_bytes = 4 n_groups */
 };
+/* ALL_FEATURE, SCORES and QUERY: with the row dedup on, a forward computes these rows for the representatives only and (unless
+ * RL4RS_DIEN_OPT_NO_LAZY_EXPAND, or a form of the forward that keeps k_row_expand) no longer copies them to the duplicates.
+ * This call then issues that copy on the last forward's stream - once, a second call does nothing - before it returns the
+ * pointer, so every row reads as before.  It must come before the handle's next forward and, for a handle driven by a stepper,
+ * before the env's next act (the act rewrites the partition the forward ran on; the pending copy is then dropped and the
+ * duplicates' internal rows stay what earlier forwards left there).  The forward's outputs (obs, prob, obs_last) are always
+ * complete. */
 int rl4rs_dien_buffer(rl4rs_dien* net, int which, void** dev_ptr, int64_t* n_bytes);
 
 /* Processing order of the row groups (envs) of the following forwards: order_dev[i] = group handled at position i, a

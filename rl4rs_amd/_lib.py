@@ -36,7 +36,7 @@ DIEN_OPTS = {'augru_h16': 1 << 0, 'augru_rows32': 1 << 1, 'augru_rows64': 1 << 2
              'no_head_fused': 1 << 10, 'cat_v1': 1 << 11, 'no_cat_group': 1 << 12, 'dense_fork': 1 << 13, 'no_gru_pad': 1 << 14,
              'no_gemm_group': 1 << 15, 'no_row_dedup': 1 << 16, 'no_dup_store': 1 << 17, 'din_rows16': 1 << 18, 'dup_store': 1 << 19,
              'no_tier2_rows': 1 << 20,
-             'no_augru_shadow': 1 << 21}
+             'no_augru_shadow': 1 << 21, 'no_lazy_expand': 1 << 22}
 POLICY_OPTS = {'tile': 0, 'ppo_fused': 1, 'ppo_rows': 2, 'resident_wgs': 3, 'ppo_std': 4}          # RL4RS_POLICY_OPT_*
 ENV_OPTS = {'rows_variant': 0}                                                       # RL4RS_ENV_OPT_*
 
@@ -206,6 +206,7 @@ SIGNATURES = {
     'rl4rs_dien_forward': (_I, [_P, _I32, _I32, _P, _P, _P, _P, _P, _P]),
     'rl4rs_dien_head_prob': (_I, [_P, _I32, _P, _P, _P]),
     'rl4rs_dien_buffer': (_I, [_P, _I, C.POINTER(_P), C.POINTER(_I64)]),
+    'rl4rs_dien_last_plan': (_I, [_P, C.c_char_p, _I32]),
     'rl4rs_simnet_create': (_I, [C.POINTER(SimnetCfg), C.POINTER(SimnetWeights), _P, C.POINTER(_P)]),
     'rl4rs_simnet_destroy': (_I, [_P]),
     'rl4rs_simnet_obs_dim': (_I, [_P, C.POINTER(_I32)]),

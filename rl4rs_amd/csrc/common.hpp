@@ -102,6 +102,10 @@ struct G16RowMap { const int32_t* active; const int32_t* n_active; int group; };
 int launch_gemm_h16(const float* a, int64_t lda, const float* wp16, const float* bias, float* c, int64_t ldc,
                     int M, int N, int K, int act, hipStream_t st, const float* addend = nullptr, int64_t ldadd = 0,
                     float* mirror = nullptr, int64_t ldm = 0, const G16RowMap* map = nullptr);
+// gather form: c[i] = act(a[rep[i]] W + addend[rep[i]]) for EVERY row i of [0, M) - rep: a scorer forward's
+// representative map at group 1 (device, M entries in [0, M)).  RL4RS_EINVAL where the matrices do not fit the form
+int launch_gemm_h16_gather(const float* a, int64_t lda, const float* wp16, float* c, int64_t ldc, int M, int N, int K, int act,
+                           hipStream_t st, const float* addend, int64_t ldadd, const int32_t* rep);
 std::vector<float> pack_gemm_weight_h16(const float* w, int64_t ldw, int K, int N);
 // two chained layers in one launch (N1 <= 128, N1 % 16 == 0, N2 <= 128): c2 = act2(act1(a W1 + b1) W2 + b2)
 int launch_gemm_h16_chain(const float* a, int64_t lda, const float* wp1, const float* bias1, int N1, int K1, int act1,
@@ -167,6 +171,9 @@ const int32_t* dien_row_order(const rl4rs_dien* n, int n_groups);         // the
 // the head GEMM's epilogue - step.hip's reference-shaped records (dien.hip); dien_obs_mirror_used: did that forward take it?
 void dien_set_obs_mirror(rl4rs_dien* n, float* host_visible);
 bool dien_obs_mirror_used(const rl4rs_dien* n);
+// The last forward left the duplicates' internal rows (all-feature, scores, query) to rl4rs_dien_buffer (PlanExpand::Lazy): forget
+// that - the caller is about to rewrite the partition arrays that forward ran on (step.hip, in front of an act that refines them)
+void dien_drop_pending_expand(rl4rs_dien* n);
 // Rounds (waves of workgroups over the chip's CUs) of the k_augru_x launch of a forward of B groups of `group` rows of which `live`
 // are expected to be distinct (row_dedup.hpp), under the row-tile form rl4rs_dien_forward would pick for it; -1: the forward does not
 // run k_augru_x (fp32 mode, augru_h16) or does not fit the handle's max_rows.  step.hip decides with it whether a reward step

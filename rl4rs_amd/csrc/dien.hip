@@ -1545,6 +1545,34 @@ __global__ __launch_bounds__(256) void k_head_prob(const float* __restrict__ obs
     if (lane == 0) prob[row] = expf(logit[K > 1 ? 1 : 0] - m) / sum;
 }
 
+// k_head_prob for a reward-shaped forward whose head GEMM ran on the active row groups only (PlanExpand::Lazy): row r of
+// group g reads the head output of the same row of g's representative - the operations of k_head_prob on the bits k_row_expand
+// would have copied.  A kernel of its own: k_head_prob (rl4rs_dien_head_prob, the simulators) keeps its code.
+__global__ __launch_bounds__(256) void k_head_prob_rep(const float* __restrict__ obs, int R, int D, int K,
+                                                       const float* __restrict__ w, const float* __restrict__ b,
+                                                       float* __restrict__ prob, int group, float* __restrict__ obs_last,
+                                                       const int32_t* __restrict__ rep) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + wave;
+    if (row >= R) return;
+    const int g = row / group;
+    const int src = rep[g] * group + (row - g * group);
+    if (obs_last && row - g * group == group - 1)
+        for (int k = lane; k < D; k += 64) obs_last[(size_t)g * D + k] = obs[(size_t)src * D + k];
+    float logit[8];
+    for (int c = 0; c < K; ++c) {
+        float s = 0.f;
+        for (int k = lane; k < D; k += 64) s = fmaf(obs[(size_t)src * D + k], w[(size_t)k * K + c], s);
+        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+        logit[c] = s + b[c];
+    }
+    float m = logit[0];
+    for (int c = 1; c < K; ++c) m = fmaxf(m, logit[c]);
+    float sum = 0.f;
+    for (int c = 0; c < K; ++c) sum += expf(logit[c] - m);
+    if (lane == 0) prob[row] = expf(logit[K > 1 ? 1 : 0] - m) / sum;
+}
+
 // 'simulator_obs' epilogue for the table form of the head (dien.py:35):
 //   obs[row] = ELU( pre[row] + b + sum_j P_j[cat[row, j]] ),   P_j = cat_emb @ W_obs[flatten slot j]  ([H, 256], built at load)
 // i.e. the Flatten(category_emb) slice of the concat (Cn*E of the 3456 inputs) never goes through the GEMM: its
@@ -1632,6 +1660,9 @@ struct rl4rs_dien {
     const int32_t* last_rep; const int32_t* last_active; const int32_t* last_nact; int last_groups;
     DienPartition dd_info; // what the last k_row_dedup ran on (step.hip adopts its partition)
     int64_t dedup_launched, dedup_carried;      // forwards that launched k_row_dedup / took a caller's partition (rl4rs_dien_dedup_counts)
+    // PlanExpand::Lazy: the last forward launched no k_row_expand - the internal rows (all-feature, scores, query) of
+    // its duplicates are completed by dien_settle_expand when rl4rs_dien_buffer hands one of them out, from these
+    struct LazyExpand { bool pending; hipStream_t st; int R, group, n_groups, ncol; const int32_t* rep; const int32_t* nact; } lazy;
     float* augru_wg[4];    // packed [2*NH2/32][NH2/8][64][4]
     float* augru_wc[4];
     // caches
@@ -2035,6 +2066,8 @@ int rl4rs_dien_create(const rl4rs_dien_cfg* c, const rl4rs_dien_weights* w, void
     n->t.tier2_rows = n->t.row_dedup && !(opts & RL4RS_DIEN_OPT_NO_TIER2_ROWS);
     n->t.din_rows_auto = !(opts & RL4RS_DIEN_OPT_DIN_ROWS16);
     n->t.augru_shadow = !(opts & RL4RS_DIEN_OPT_NO_AUGRU_SHADOW);
+    n->t.lazy_expand = n->t.tier2_rows && !(opts & RL4RS_DIEN_OPT_NO_LAZY_EXPAND);
+    memset(&n->lazy, 0, sizeof(n->lazy));
     n->distinct_hint = 0;
     n->last_plan = DienPlan{};
     if (n->t.row_dedup) {
@@ -2435,9 +2468,14 @@ static int stage_augru(rl4rs_dien* n, const DienPlan& p, const DienFwd& f) {
     return RL4RS_OK;
 }
 
-// the duplicates' rows (PlanExpand::Front / Behind the head GEMM: dien_plan)
+// the duplicates' rows (PlanExpand::Front / Behind the head GEMM: dien_plan).  Lazy: nothing is launched - the class keeps one (empty)
+// entry for the launch, the handle remembers what dien_settle_expand needs
 static int stage_expand(rl4rs_dien* n, const DienPlan& p, const DienFwd& f) {
     Prof pr(n, KID_DEDUP, f.st);
+    if (p.expand == PlanExpand::Lazy) {
+        n->lazy = rl4rs_dien::LazyExpand{true, f.st, f.R, f.group, f.n_groups, p.expand_ncol, f.rep, f.nact};
+        return RL4RS_OK;
+    }
     RowExpandArgs a;
     memset(&a, 0, sizeof(a));
     a.R = f.R; a.group = f.group; a.n_groups = f.n_groups; a.S = n->S; a.L = n->L; a.ncol = p.expand_ncol;
@@ -2456,6 +2494,9 @@ static int stage_head(rl4rs_dien* n, const DienPlan& p, const DienFwd& f) {
     switch (p.head) {
         case PlanHead::TsumH16:          // obs = ELU(allf W + [b + table rows]): the addend was built inside the category kernel
         case PlanHead::TsumH16Mirror: {
+            // Lazy, observation-shaped: every row from its representative's all-feature row and addend (k_gemm_h16_gather)
+            if (p.expand == PlanExpand::Lazy && f.group == 1)
+                return launch_gemm_h16_gather(n->allf, F, n->obs_w, f.obs_out, OBS_DIM, R, OBS_DIM, Kh, 1, f.st, n->tsum, OBS_DIM, f.rep);
             float* const mirror = p.head == PlanHead::TsumH16Mirror ? n->obs_mirror : nullptr;
             rc = launch_gemm_h16(n->allf, F, n->obs_w, nullptr, f.obs_out, OBS_DIM, R, OBS_DIM, Kh, 1, f.st, n->tsum, OBS_DIM, mirror, OBS_DIM, f.map2);
             n->obs_mirror_used = mirror != nullptr;
@@ -2473,9 +2514,13 @@ static int stage_head(rl4rs_dien* n, const DienPlan& p, const DienFwd& f) {
     return scorer_gemm(n, n->allf, F, n->obs_w, n->obs_b, f.obs_out, OBS_DIM, R, OBS_DIM, n->F, 1, f.st);
 }
 
-static int stage_prob(rl4rs_dien* n, const DienFwd& f) {
+static int stage_prob(rl4rs_dien* n, const DienPlan& p, const DienFwd& f) {
     Prof pr(n, KID_PROB, f.st);
-    hipLaunchKernelGGL(k_head_prob, dim3((f.R + 3) / 4), dim3(256), 0, f.st, f.obs_out, f.R, OBS_DIM, n->K, n->out_w, n->out_b, f.prob, f.group, n->obs_last);
+    if (p.expand == PlanExpand::Lazy && f.group > 1)       // the head output holds the representatives' rows only
+        hipLaunchKernelGGL(k_head_prob_rep, dim3((f.R + 3) / 4), dim3(256), 0, f.st, f.obs_out, f.R, OBS_DIM, n->K, n->out_w, n->out_b, f.prob, f.group,
+                           n->obs_last, f.rep);
+    else
+        hipLaunchKernelGGL(k_head_prob, dim3((f.R + 3) / 4), dim3(256), 0, f.st, f.obs_out, f.R, OBS_DIM, n->K, n->out_w, n->out_b, f.prob, f.group, n->obs_last);
     RL4RS_LAUNCH_CHECK();
     return RL4RS_OK;
 }
@@ -2487,6 +2532,7 @@ int rl4rs_dien_forward(rl4rs_dien* n, int32_t R, int32_t group, const float* den
     RL4RS_REQUIRE(group >= 1 && R % group == 0, "dien_forward: R=%d is not a multiple of group=%d", R, group);
     const int ngroups = R / group;
     n->obs_mirror_used = false;
+    n->lazy.pending = false;       // the last forward's pending expansion: its rows are about to be overwritten
     struct MirrorOnce { rl4rs_dien* n; ~MirrorOnce() { n->obs_mirror = nullptr; n->obs_last = nullptr; n->part_rep = nullptr; } } mirror_once{n};       // one forward only
     DienCall c{};
     c.R = R; c.group = group; c.obs = obs != nullptr; c.prob = prob != nullptr;
@@ -2520,8 +2566,8 @@ int rl4rs_dien_forward(rl4rs_dien* n, int32_t R, int32_t group, const float* den
     if (p.expand == PlanExpand::Front && (rc = stage_expand(n, p, f))) return rc;
     if (p.dense_side) RL4RS_HIP_TRY(hipStreamWaitEvent(f.st, n->ev_join, 0));
     if ((rc = stage_head(n, p, f))) return rc;
-    if (p.expand == PlanExpand::Behind && (rc = stage_expand(n, p, f))) return rc;
-    if (p.prob && (rc = stage_prob(n, f))) return rc;
+    if ((p.expand == PlanExpand::Behind || p.expand == PlanExpand::Lazy) && (rc = stage_expand(n, p, f))) return rc;
+    if (p.prob && (rc = stage_prob(n, p, f))) return rc;
     return RL4RS_OK;
 }
 
@@ -2534,8 +2580,29 @@ int rl4rs_dien_head_prob(rl4rs_dien* n, int32_t R, const float* obs, float* prob
     return RL4RS_OK;
 }
 
+// PlanExpand::Lazy: the internal rows of the last forward's duplicates, on that forward's stream, once (no profile entry: the
+// forward has recorded the class's entry).  The head output is complete already (group 1) or was not asked for
+static int dien_settle_expand(rl4rs_dien* n) {
+    if (!n->lazy.pending) return RL4RS_OK;
+    n->lazy.pending = false;
+    const rl4rs_dien::LazyExpand& z = n->lazy;
+    RowExpandArgs a;
+    memset(&a, 0, sizeof(a));
+    a.R = z.R; a.group = z.group; a.n_groups = z.n_groups; a.S = n->S; a.L = n->L; a.ncol = z.ncol;
+    a.rep = z.rep; a.n_active = z.nact;
+    a.allf = n->allf; a.ld = n->Fld; a.scores = n->scores; a.scores_stride = (int64_t)n->c.max_rows * n->L;
+    a.q = n->q; a.E = n->E;
+    hipLaunchKernelGGL(k_row_expand, dim3((z.R + 3) / 4), dim3(256), 0, z.st, a);
+    RL4RS_LAUNCH_CHECK();
+    return RL4RS_OK;
+}
+
 int rl4rs_dien_buffer(rl4rs_dien* n, int which, void** p, int64_t* bytes) {
     RL4RS_REQUIRE(n && p, "dien_buffer: null argument");
+    if (which == RL4RS_DIEN_ALL_FEATURE || which == RL4RS_DIEN_SCORES || which == RL4RS_DIEN_QUERY) {
+        const int rc = dien_settle_expand(n);
+        if (rc) return rc;
+    }
     int64_t b = 0;
     void* ptr = nullptr;
     switch (which) {
@@ -2634,6 +2701,7 @@ void dien_last_partition(const rl4rs_dien* n, DienPartition* out) { *out = n->dd
 bool dien_takes_partition(const rl4rs_dien* n) { return n && n->t.row_dedup && !n->t.dup_store; }
 const int32_t* dien_row_order(const rl4rs_dien* n, int n_groups) { return (n->row_order && n->row_order_n == n_groups) ? n->row_order : nullptr; }
 bool dien_obs_mirror_used(const rl4rs_dien* n) { return n && n->obs_mirror_used; }
+void dien_drop_pending_expand(rl4rs_dien* n) { if (n) n->lazy.pending = false; }
 bool dien_augru_rows64(const rl4rs_dien* n, int B, int group) {
     return n && n->t.fp16x2 && n->t.augru_x && (int64_t)B * group <= n->c.max_rows && augru_rows64(n->augru_rows, B * group, group, n->S, n->n_cu);
 }
@@ -2650,6 +2718,13 @@ extern "C" {
 int rl4rs_dien_status_word(rl4rs_dien* n, int32_t** word_dev) {
     RL4RS_REQUIRE(n && word_dev, "dien_status_word: null argument");
     *word_dev = n->range_flag;
+    return RL4RS_OK;
+}
+// The launch plan of the last forward, as dien_plan_str prints it (dien_plan.hpp; "" before the first forward)
+int rl4rs_dien_last_plan(rl4rs_dien* n, char* buf, int32_t cap) {
+    RL4RS_REQUIRE(n && buf && cap > 0, "dien_last_plan: bad argument");
+    buf[0] = 0;
+    if (n->last_plan.din_waves) dien_plan_str(n->last_plan, buf, (size_t)cap);
     return RL4RS_OK;
 }
 int rl4rs_dien_kernel_count(void) { return KID_COUNT; }

@@ -31,6 +31,10 @@ inline bool augru_shadow_room(int hint, int n_groups, int S, int n_cu) {
 inline bool g16_shadow_fits(int R, int Dn, int F, int U) {
     return ((int64_t)R - 1) * Dn + Dn < ((int64_t)1 << 29) && ((int64_t)R - 1) * F + U < ((int64_t)1 << 29);
 }
+// the gather form of the head GEMM (k_gemm_h16_gather) addresses allf, the table addend and the 256-wide output the same way
+inline bool g16_gather_fits(int R, int F, int Kh) {
+    return ((int64_t)R - 1) * F + Kh < ((int64_t)1 << 29) && (int64_t)R * 256 < ((int64_t)1 << 29);
+}
 
 // ---- what rl4rs_dien_create fixes
 struct DienTraits {
@@ -53,6 +57,8 @@ struct DienTraits {
     bool tier2_rows;       // row dedup: second tier on the active rows
     bool augru_shadow;     // observation-sized forwards may take the shadow-plane order
     bool h1f;              // the fragment-order copy of the first-GRU states exists (what k_din_x reads)
+    bool lazy_expand;      // second tier: no k_row_expand behind the head - the outputs read the representative's row, the duplicates'
+                           // internal rows are completed when somebody asks for them (RL4RS_DIEN_OPT_NO_LAZY_EXPAND: off)
     bool ptab, tsum;       // head tables built / their per-row sum buffer exists
     int E, U, L, S, Cn, Dn, Fld, NH2, n_cu, max_rows;
 
@@ -84,7 +90,7 @@ enum class PlanDense { Shadow, Pair, Chain, TwoGemm };
 enum class PlanQside { InPair, InDinXq, MappedH16, ScorerGemm };
 enum class PlanDin { Xq, XAuto, X16, Scores };
 enum class PlanAugru { Xs, X32, X64, H16, Recur32 };
-enum class PlanExpand { None, Front, Behind };
+enum class PlanExpand { None, Front, Behind, Lazy };
 enum class PlanHead { TsumH16, TsumH16Mirror, TsumPacked, TablesFinish, Plain };
 
 struct DienPlan {
@@ -101,7 +107,9 @@ struct DienPlan {
     PlanDin din;
     bool din_stage, din_h16; int din_waves;      // k_din_scores<STAGE, H16> and its waves per workgroup
     PlanAugru augru;
-    PlanExpand expand; int expand_ncol;          // k_row_expand and the columns of allf it copies
+    PlanExpand expand; int expand_ncol;          // k_row_expand and the columns of allf it copies (Lazy: not launched by the forward -
+                                                 // group == 1: the head GEMM computes every row from its representative's all-feature
+                                                 // row; group > 1: k_head_prob_rep reads the representative's head output)
     PlanHead head;
     bool prob;
 };
@@ -147,6 +155,12 @@ inline DienPlan dien_plan(const DienTraits& t, const DienCall& c) {
     if (p.dedup == PlanDedup::None || t.dup_store) p.expand = PlanExpand::None;
     else p.expand = p.tier2 ? PlanExpand::Behind : PlanExpand::Front;
     p.expand_ncol = p.expand == PlanExpand::None ? 0 : (p.tier2 ? t.S * t.NH2 + t.U + t.E : t.S * t.NH2);
+    // lazy form, only in place of Behind (so: second tier, the head is the mapped k_gemm_h16 with the table addend and
+    // no mirror): observation-shaped forwards - the head's gather form addresses allf, the addend and the output through one
+    // buffer descriptor each - and reward-shaped forwards whose head output stays inside the handle
+    if (p.expand == PlanExpand::Behind && t.lazy_expand &&
+        (c.group == 1 ? g16_gather_fits(c.R, t.Fld, p.expand_ncol) : !c.obs))
+        p.expand = PlanExpand::Lazy;
     if (t.head_tsum()) p.head = !t.gemm16 ? PlanHead::TsumPacked : ((c.obs && c.mirror) ? PlanHead::TsumH16Mirror : PlanHead::TsumH16);
     else p.head = t.ptab ? PlanHead::TablesFinish : PlanHead::Plain;
     p.prob = c.prob;
@@ -161,7 +175,7 @@ inline int dien_plan_str(const DienPlan& p, char* buf, size_t cap) {
     static const char* const qs[] = {"in_pair", "in_k_din_xq", "mapped_k_gemm_h16", "scorer_gemm"};
     static const char* const di[] = {"k_din_xq", "k_din_x_auto", "k_din_x_16", "k_din_scores"};
     static const char* const au[] = {"k_augru_xs", "k_augru_x_32", "k_augru_x_64", "k_augru_h16", "k_recur_fp32"};
-    static const char* const ex[] = {"none", "front", "behind"};
+    static const char* const ex[] = {"none", "front", "behind", "lazy"};
     static const char* const hd[] = {"tsum+k_gemm_h16", "tsum+k_gemm_h16+mirror", "tsum+packed", "tables+k_head_finish", "plain"};
     char din[48];
     if (p.din == PlanDin::Scores) snprintf(din, sizeof(din), "k_din_scores<%d,%d>x%d", (int)p.din_stage, (int)p.din_h16, p.din_waves);

@@ -569,6 +569,25 @@ __global__ __launch_bounds__(256) void k_gemm_h16_map(const float* __restrict__ 
 #undef RL4RS_G16_BX
 }
 
+// The head GEMM of an observation-shaped scorer forward in its GATHER form: every row of [0, M) is an output row, its A
+// row and its addend row are those of its representative (rmap.active = the forward's rep array, rmap.n_active unused) - a
+// duplicate's output is bit for bit its representative's (an MFMA output row depends on its own A row only) and nothing has to
+// copy it.  The tile text with RL4RS_G16_GATHER; its own instantiations, k_gemm_h16_map keeps its code.
+template <int WM, bool VEC>
+__global__ __launch_bounds__(256) void k_gemm_h16_gather(const float* __restrict__ A, int64_t lda,
+                                                         const char* __restrict__ Wp, int KB,
+                                                         const float* __restrict__ bias, float* __restrict__ C,
+                                                         int64_t ldc, int M, int N, int K, int act,
+                                                         const float* __restrict__ addend, int64_t ldadd, G16Chain chain, G16RowMap rmap) {
+    constexpr bool MAP = true;
+    __shared__ int s_row[32 * WM];
+#define RL4RS_G16_BX blockIdx.x
+#define RL4RS_G16_GATHER 1
+#include "gemm_h16_tile.inc"
+#undef RL4RS_G16_GATHER
+#undef RL4RS_G16_BX
+}
+
 // Two INDEPENDENT problems in one launch (launch_gemm_h16_pair: the dense tower and the q-side term of the DIN scores, each a
 // half-chip grid at observation size): the grid is the concatenation of both problems' row-tile ranges, a workgroup picks its
 // problem by comparing blockIdx.x with the first problem's tile count - wave-uniform, the selected arguments come out of the
@@ -916,6 +935,31 @@ static int launch_gemm_h16_impl(const float* a, int64_t lda, const float* wp16, 
     }
 #define RL4RS_G16_LAUNCH(WM_, VEC_) hipLaunchKernelGGL((k_gemm_h16<WM_, VEC_>), grid, dim3(256), 0, st, a, lda, wp, KB, bias, c, ldc, M, N, K, act, addend, ldadd, chain)
     if (small) { if (vec) RL4RS_G16_LAUNCH(1, true); else RL4RS_G16_LAUNCH(1, false); }
+    else { if (vec) RL4RS_G16_LAUNCH(2, true); else RL4RS_G16_LAUNCH(2, false); }
+#undef RL4RS_G16_LAUNCH
+    RL4RS_LAUNCH_CHECK();
+    return RL4RS_OK;
+}
+
+// c[i] = act(a[rep[i]] W + addend[rep[i]]) for every row i of [0, M): k_gemm_h16_gather.  No bias, no chain, no mirror; an error
+// where the matrices do not fit the form's buffer descriptors (the scorer's plan has checked: g16_gather_fits)
+int launch_gemm_h16_gather(const float* a, int64_t lda, const float* wp16, float* c, int64_t ldc, int M, int N, int K, int act,
+                           hipStream_t st, const float* addend, int64_t ldadd, const int32_t* rep) {
+    if (M <= 0 || N <= 0 || K <= 0) return RL4RS_OK;
+    const G16RowMap map = {rep, rep, 1};
+    const G16Chain none = {};
+    bool vec;
+    int ny;
+    const int wm = gemm_h16_route(a, lda, M, N, K, addend != nullptr, false, &vec, &ny);
+    if (wm == 0 || !g16_map_ok(&map, a, lda, c, ldc, M, N, K, addend, ldadd, none)) {
+        set_error("gemm_h16_gather: unsupported problem %d x %d x %d", M, N, K);
+        return RL4RS_EINVAL;
+    }
+    const int KB = (K + 15) / 16;
+    const char* wp = reinterpret_cast<const char*>(wp16);
+    const dim3 grid(wm == 1 ? (M + 31) / 32 : (M + 63) / 64, ny);
+#define RL4RS_G16_LAUNCH(WM_, VEC_) hipLaunchKernelGGL((k_gemm_h16_gather<WM_, VEC_>), grid, dim3(256), 0, st, a, lda, wp, KB, (const float*)nullptr, c, ldc, M, N, K, act, addend, ldadd, none, map)
+    if (wm == 1) { if (vec) RL4RS_G16_LAUNCH(1, true); else RL4RS_G16_LAUNCH(1, false); }
     else { if (vec) RL4RS_G16_LAUNCH(2, true); else RL4RS_G16_LAUNCH(2, false); }
 #undef RL4RS_G16_LAUNCH
     RL4RS_LAUNCH_CHECK();

@@ -8,6 +8,8 @@
 // bound is min(M, n_active * group) read here, a workgroup whose first position lies behind it leaves before its first barrier,
 // positions of a partial last tile behind the bound recompute the last active row and store nothing.  Per output element the
 // k-blocks, the MFMA order and the epilogue expression are those of the unmapped form.
+// RL4RS_G16_GATHER (optional, with MAP; k_gemm_h16_gather, DESIGN 31; no chain): rmap.active is the REPRESENTATIVE map of all M
+// rows (group 1) - tile position p reads row active[p] of A and of the addend and writes row p of C, the row bound is M itself.
     constexpr int BM = 32 * WM, BK = 64, KBT = BK / 16;
     constexpr int SLAB = BM * 16 + 16, PLANE = 2 * KBT * SLAB;
 #ifdef RL4RS_G16_AS_LDS        // the shadow plane of k_augru_xs: the tile buffers are a piece of the launch's dynamic LDS
@@ -31,7 +33,11 @@
             agrp[p] = rmap.group == 1 ? apos[p] : apos[p] / rmap.group;
             aent[p] = rmap.active[agrp[p]];
         }
+#ifdef RL4RS_G16_GATHER
+        Mb = M;
+#else
         Mb = min(M, rmap.n_active[0] * rmap.group);
+#endif
         if (m0 >= Mb) return;
 #pragma unroll
         for (int p = 0; p < WM; ++p) {
@@ -251,6 +257,11 @@
         const float bv = bias ? bias[col] : 0.f;
         if constexpr (MAP) {                       // (no mirror in this form: the launcher keeps such launches unmapped)
             const __amdgpu_buffer_rsrc_t rs_c = __builtin_amdgcn_make_buffer_rsrc(C, 0, (int)((((int64_t)M - 1) * ldc + N) * 4), 0x00020000);
+#ifdef RL4RS_G16_GATHER                            // the C row of tile row rl: the position itself / the physical row its A row came from
+#define RL4RS_G16_CROW(rl) (m0 + (rl))
+#else
+#define RL4RS_G16_CROW(rl) s_row[rl]
+#endif
             float add[WM][16];
             if (addend) {
                 const __amdgpu_buffer_rsrc_t rs_d = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(addend), 0, (int)((((int64_t)M - 1) * ldadd + N) * 4), 0x00020000);
@@ -273,8 +284,9 @@
                     const int rl = 32 * w + (r & 3) + 8 * (r >> 2) + 4 * half;
                     if (m0 + rl < Mb)
                         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, apply_act(acc[w][r] * inv_s + bv + add[w][r], act)), rs_c,
-                                                              (s_row[rl] * (int)ldc + col) * 4, 0, 0);
+                                                              (RL4RS_G16_CROW(rl) * (int)ldc + col) * 4, 0, 0);
                 }
+#undef RL4RS_G16_CROW
             return;
         }
         const __amdgpu_buffer_rsrc_t rs_c = __builtin_amdgcn_make_buffer_rsrc(C + (size_t)m0 * ldc, 0, (int)((((int64_t)rows_here - 1) * ldc + N) * 4), 0x00020000);

@@ -125,6 +125,9 @@ bool plan_refine(rl4rs_stepper* s, int cur, RowRefineArgs* rf) {
         rf->active_src = d.active;
         rf->n_active_src = d.n_active;
     }
+    // the act rewrites the active list and the count in place (and, one act later, the rep array) the scorer's last forward ran
+    // on: what that forward left to rl4rs_dien_buffer (PlanExpand::Lazy) can no longer be completed from them
+    dien_drop_pending_expand(s->dien);
     rf->n = B;
     rf->rep = s->part_rep[s->part_cur ^ 1];
     rf->active = s->part_active;

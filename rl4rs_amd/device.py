@@ -693,6 +693,12 @@ class DeviceDien(object):
         check(self.lib.rl4rs_dien_dedup_counts(self.h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def last_plan(self):
+        """The launch plan of the last forward as a dict of its key=value tokens (rl4rs_dien_last_plan; {} before the first)."""
+        buf = C.create_string_buffer(512)
+        check(self.lib.rl4rs_dien_last_plan(self.h, buf, 512))
+        return dict(tok.split('=', 1) for tok in buf.value.decode().split())
+
     def set_row_partition(self, rep, active, n_active):
         """The NEXT forward takes its duplicate row groups from these int32 device tensors (rl4rs_dien_set_row_partition)."""
         for t in (rep, active, n_active):

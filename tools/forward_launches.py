@@ -28,7 +28,8 @@ ARMS = [('default', 'fp16x2', '', {}), ('fp32', 'fp32', '', {})] + [(o, 'fp16x2'
     'no_row_dedup', 'no_tier2_rows', 'no_augru_shadow', 'dup_store', 'dense_fork', 'no_gemm_group', 'no_dense_chain', 'no_gemm16',
     'din_v1', 'no_din16', 'augru_h16', 'cat_v1', 'no_cat_group', 'no_head_tables', 'no_head_fused', 'din_rows16')] + [
     ('cn24', 'fp16x2', '', {'category_feature_num': 24}), ('cn25', 'fp16x2', '', {'category_feature_num': 25}),
-    ('u160', 'fp16x2', '', {'hidden_units': 160})]      # (hidden_units is a multiple of 32: 160 is the smallest the chain does not take)
+    ('u160', 'fp16x2', '', {'hidden_units': 160}),      # (hidden_units is a multiple of 32: 160 is the smallest the chain does not take)
+    ('no_lazy_expand', 'fp16x2', 'no_lazy_expand', {})]  # (a tree from before DESIGN 31 does not know the name: its defaults then)
 # (name, R, group, k_augru_x rows pin, distinct hint, row order, partition handed in)
 FORWARDS = [('R96 g1 hint32', 96, 1, 0, 32, False, False), ('R96 g1', 96, 1, 0, 0, False, False),
             ('R192 g8 rows32', 192, 8, 32, 0, False, False), ('R192 g8 rows64', 192, 8, 64, 0, False, False),
@@ -83,7 +84,12 @@ def run():
     for arm, precision, kernels, over in ARMS:
         cfg = dict(CFG, scorer_precision=precision, scorer_kernels=kernels, **over)
         rs = np.random.RandomState(3)
-        net = DeviceDien(cfg, init_dien_weights(cfg, seed=9, emb_scale=0.5, bias_noise=0.2), max_rows=ROWS, max_slots=SLOTS)
+        try:
+            net = DeviceDien(cfg, init_dien_weights(cfg, seed=9, emb_scale=0.5, bias_noise=0.2), max_rows=ROWS, max_slots=SLOTS)
+        except (KeyError, ValueError):
+            if kernels != 'no_lazy_expand':
+                raise
+            net = DeviceDien(dict(cfg, scorer_kernels=''), init_dien_weights(cfg, seed=9, emb_scale=0.5, bias_noise=0.2), max_rows=ROWS, max_slots=SLOTS)
         seq = rs.randint(1, 284, size=(SLOTS, 2, 16)).astype(np.int32)
         seq[::2, 1, :] = 0
         for s in range(2):
