@@ -1598,6 +1598,18 @@ int rl4rs_exactk_set_adam_step(rl4rs_exactk* net, int64_t step);
  * u * total, u = uniform01(seed, step, row, t); greedy = 1: the first maximum.  logits_out_dev [N, 9, A] optional. */
 int rl4rs_exactk_decode(rl4rs_exactk* net, int32_t N, const float* obs_dev, int32_t greedy, uint32_t seed, uint32_t step,
                         int32_t* path_dev, float* logits_out_dev, void* stream);
+/* Beam search over the pointer decoder: path_dev int32 [N, beam, 9], score_dev float [N, beam] (sum of the 9 log-probabilities,
+ * descending; ties by parent * A + token).  Optional trace, each [N, 9, beam]: parent_dev int32 (index of the beam of step t - 1
+ * that beam k of step t extends; 0 at t = 0), token_dev int32, step_score_dev float.  Dropout pass 1, masks of rl4rs_exactk_decode.
+ * The beams of a row share the encoder output; each carries its own LSTM state, intra-attention history and prefix, hence its own
+ * allowed set.  Step t scores every allowed candidate a of every live beam b as acc[b] + logit[b, a] - logsumexp_allowed(logit[b, :])
+ * and keeps the best `beam`; one beam is live at step 0, so the first picks are distinct.  1 <= beam <= 8.  The per-beam decoder
+ * arrays are the handle's own, allocated on the first call (and again by a call with a larger N * beam), apart from what the other
+ * calls use.  Refused: beam outside [1, 8], N outside [1, max_rows], a null path_dev / score_dev, a (beam, action_size, hidden)
+ * whose per-user kernels need more than 160 KiB of LDS. */
+int rl4rs_exactk_decode_beam(rl4rs_exactk* net, int32_t N, const float* obs_dev, int32_t beam, uint32_t seed, uint32_t step,
+                             int32_t* path_dev, float* score_dev, int32_t* parent_dev, int32_t* token_dev, float* step_score_dev,
+                             void* stream);
 /* Teacher-forced forward along path_dev [N, 9], loss = mean_n(w_n * sum_t CE(logits[n, t], path[n, t])) and its full gradient into
  * the handle's flat gradient buffer (bit-identical between identical calls).  loss_dev float[2] = {loss, number of (row, step)
  * targets outside the allowed set (such a path is the caller's error; indices are clamped into range)}. */

@@ -411,6 +411,7 @@ SIGNATURES = {
     'rl4rs_exactk_adam_state': (_I, [_P, _P, _P, _P]),
     'rl4rs_exactk_set_adam_step': (_I, [_P, _I64]),
     'rl4rs_exactk_decode': (_I, [_P, _I32, _P, _I32, C.c_uint32, C.c_uint32, _P, _P, _P]),
+    'rl4rs_exactk_decode_beam': (_I, [_P, _I32, _P, _I32, C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P, _P]),
     'rl4rs_exactk_loss_grad': (_I, [_P, _I32, _P, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P]),
     'rl4rs_exactk_adam_step': (_I, [_P, C.c_float, C.c_float, C.c_float, C.c_float, _P, _P]),
     'rl4rs_exactk_critic_param_count': (_I64, [_I32, _I32]),

@@ -13,6 +13,8 @@
 // Decoder layout: one launch sequence per step t = 0..8; each per-row kernel streams the row's encoded references
 // R = enc W_ref [A, D] from global memory (145 KB per row at A = 284, D = 128: it would fill a CU's LDS on its own, and the
 // LSTM / query products of a step are batched over the rows as GEMMs between the per-row kernels, so nothing stays resident).
+// Beam search (rl4rs_exactk_decode_beam) runs the same sequence over N * beam decoder rows; its per-USER kernels, which read a
+// user's R tile once for all of its beams, are in exactk_beam.hpp.
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -730,6 +732,8 @@ __global__ void k_xk_critic_err(const float* __restrict__ v, const float* __rest
     if (err) err[i] = e * e;
 }
 
+#include "exactk_beam.hpp"
+
 inline dim3 ew(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
 
 }  // namespace
@@ -775,6 +779,14 @@ static XkLayout xk_layout(const XkDims& d) {
 
 struct XkBlockAct { float *Q, *K, *V, *P, *xhat1, *rstd1, *Y, *Hf, *xhat2, *rstd2, *Xout; uint8_t* flag; };
 
+// beam search's own scratch (rl4rs_exactk_decode_beam): one allocation, apart from the arena, sized by the N * beam of the largest call
+struct XkBeamScratch {
+    void* mem = nullptr;
+    size_t bytes = 0;
+    float *XH, *G, *C, *Cin, *Hout, *Bef, *Qb, *intra, *tmp1, *Cg, *q, *Cp, *acc[2];
+    int32_t *prefix[2], *anc[2];
+};
+
 struct rl4rs_exactk {
     rl4rs_exactk_cfg c;
     XkDims d;
@@ -792,6 +804,7 @@ struct rl4rs_exactk {
         *part3, *dA, *dB, *dC3, *dF, *tA, *tB, *part, *part_b;
     int32_t* path_tmp;
     int chunk_cap;
+    XkBeamScratch beam;
 };
 
 struct rl4rs_exactk_critic {
@@ -851,9 +864,9 @@ static int xk_tn(rl4rs_exactk* p, const float* A_, int lda, int M, const float* 
 static size_t xk_attn_lds(const XkDims& d) { return ((size_t)2 * d.A * (d.dh + 1) + 4 * (size_t)(d.A + d.dh)) * 4; }
 static size_t xk_dec_lds(const XkDims& d) { return ((size_t)d.A + 3 * d.D + 16 + 2 * (size_t)std::max(d.D, 256)) * 4; }
 
-// encoder + decoder forward.  mode 0 sample / 1 greedy (path written) / 2 teacher-forced (path read; ce, dlogit written)
-static int xk_forward(rl4rs_exactk* p, int N, const float* obs, int mode, int32_t* path, const float* w, uint32_t seed, uint32_t step,
-                      uint32_t pass, float* logits_out, hipStream_t st) {
+// encoder forward of N rows and the two W_ref products (p->Rg, p->Rp) -> *enc_out = enc [N * A, D]
+static int xk_encode(rl4rs_exactk* p, int N, const float* obs, uint32_t seed, uint32_t step, uint32_t pass, const float** enc_out,
+                     hipStream_t st) {
     const XkDims& d = p->d;
     const XkLayout& L = p->L;
     const float* P = p->opt.params;
@@ -885,9 +898,22 @@ static int xk_forward(rl4rs_exactk* p, int N, const float* obs, int mode, int32_
         X = a.Xout;
     }
     RL4RS_LAUNCH_CHECK();
-    const float* enc = X;
-    if ((rc = launch_gemm_f32(enc, D, P + L.a_wref[0], D, nullptr, p->Rg, D, M, D, D, ACT_NONE, st))) return rc;
-    if ((rc = launch_gemm_f32(enc, D, P + L.a_wref[1], D, nullptr, p->Rp, D, M, D, D, ACT_NONE, st))) return rc;
+    if ((rc = launch_gemm_f32(X, D, P + L.a_wref[0], D, nullptr, p->Rg, D, M, D, D, ACT_NONE, st))) return rc;
+    if ((rc = launch_gemm_f32(X, D, P + L.a_wref[1], D, nullptr, p->Rp, D, M, D, D, ACT_NONE, st))) return rc;
+    *enc_out = X;
+    return RL4RS_OK;
+}
+
+// encoder + decoder forward.  mode 0 sample / 1 greedy (path written) / 2 teacher-forced (path read; ce, dlogit written)
+static int xk_forward(rl4rs_exactk* p, int N, const float* obs, int mode, int32_t* path, const float* w, uint32_t seed, uint32_t step,
+                      uint32_t pass, float* logits_out, hipStream_t st) {
+    const XkDims& d = p->d;
+    const XkLayout& L = p->L;
+    const float* P = p->opt.params;
+    const int A = d.A, D = d.D;
+    int rc;
+    const float* enc = nullptr;
+    if ((rc = xk_encode(p, N, obs, seed, step, pass, &enc, st))) return rc;
     const size_t lds_d = xk_dec_lds(d);
     if ((rc = raise_dyn_smem(reinterpret_cast<const void*>(&k_xk_glimpse_fwd), lds_d))) return rc;
     if ((rc = raise_dyn_smem(reinterpret_cast<const void*>(&k_xk_pointer_fwd), lds_d))) return rc;
@@ -915,6 +941,89 @@ static int xk_forward(rl4rs_exactk* p, int N, const float* obs, int mode, int32_
         hipLaunchKernelGGL(k_xk_pointer_fwd, dim3(N), dim3(256), lds_d, st, t, N, A, D, p->Rp, p->Cp + t * ND, P + L.a_v[1], p->loc,
                            p->special, path, mode, seed, step, logits_out, mode == 2 ? p->dlogit + (size_t)t * N * A : (float*)nullptr, w,
                            p->ce + (size_t)t * N, p->invalid + (size_t)t * N);
+    }
+    RL4RS_LAUNCH_CHECK();
+    return RL4RS_OK;
+}
+
+// LDS of the per-user beam kernels for `beam` live beams (the glimpse kernel's, the larger of the two)
+static size_t xk_beam_lds(const XkDims& d, int beam) {
+    return ((size_t)beam * d.A + (size_t)beam * d.D + d.D + 16 + (size_t)beam * std::max(d.D, 256)) * 4;
+}
+
+// carve the beam scratch for rows = N * beam decoder rows, (re)allocating when the call needs more than the handle holds
+static int xk_beam_reserve(rl4rs_exactk* p, size_t rows) {
+    XkBeamScratch& s = p->beam;
+    const size_t D = p->d.D, T = XK_T;
+    std::vector<std::pair<void**, size_t>> reqs;
+    auto req = [&](auto** slot, size_t n) { reqs.emplace_back(reinterpret_cast<void**>(slot), n * sizeof(**slot)); };
+    req(&s.XH, rows * 2 * D); req(&s.G, rows * 4 * D); req(&s.C, rows * D); req(&s.Cin, rows * D); req(&s.Hout, T * rows * D);
+    req(&s.Bef, T * rows * D); req(&s.Qb, rows * D); req(&s.intra, rows * D); req(&s.tmp1, rows * D); req(&s.Cg, rows * D);
+    req(&s.q, rows * D); req(&s.Cp, rows * D);
+    for (int k = 0; k < 2; ++k) { req(&s.acc[k], rows); req(&s.prefix[k], rows * T); req(&s.anc[k], rows * T); }
+    size_t total = 0;
+    for (auto& r : reqs) total += (r.second + 255) / 256 * 256;
+    if (total > s.bytes) {
+        if (s.mem) (void)hipFree(s.mem);           // (waits for the work that still reads it)
+        s.mem = nullptr;
+        s.bytes = 0;
+        hipError_t e = hipMalloc(&s.mem, total);
+        if (e != hipSuccess) {
+            set_error("exactk_decode_beam: hipMalloc(%zu bytes) failed: %s", total, hipGetErrorString(e));
+            s.mem = nullptr;
+            return RL4RS_ENOMEM;
+        }
+        s.bytes = total;
+    }
+    size_t off = 0;
+    for (auto& r : reqs) { *r.first = static_cast<char*>(s.mem) + off; off += (r.second + 255) / 256 * 256; }
+    return RL4RS_OK;
+}
+
+// encoder (pass 1, as rl4rs_exactk_decode) + beam search over the decoder: rows r = n * live + b, live = 1 at step 0, B afterwards
+static int xk_beam_forward(rl4rs_exactk* p, int N, const float* obs, int B, uint32_t seed, uint32_t step, int32_t* path, float* score,
+                           int32_t* parent_tr, int32_t* token_tr, float* score_tr, hipStream_t st) {
+    const XkDims& d = p->d;
+    const XkLayout& L = p->L;
+    const float* P = p->opt.params;
+    const int A = d.A, D = d.D, NB = N * B;
+    int rc;
+    if ((rc = xk_beam_reserve(p, (size_t)NB))) return rc;
+    XkBeamScratch& s = p->beam;
+    const float* enc = nullptr;
+    if ((rc = xk_encode(p, N, obs, seed, step, 1u, &enc, st))) return rc;
+    const size_t lds = xk_beam_lds(d, B);
+    if ((rc = raise_dyn_smem(reinterpret_cast<const void*>(&k_xk_beam_glimpse), lds))) return rc;
+    if ((rc = raise_dyn_smem(reinterpret_cast<const void*>(&k_xk_beam_select), lds))) return rc;
+    for (int t = 0; t < XK_T; ++t) {
+        const int live = t == 0 ? 1 : B, rows = N * live;
+        const int in = t & 1, out = in ^ 1;                    // ping-pong of prefix / acc / anc: step t reads [in], writes [out]
+        const size_t RD = (size_t)rows * D;
+        float* Ht = s.Hout + (size_t)t * NB * D;
+        float* Bt = s.Bef + (size_t)t * NB * D;
+        if (t == 0)
+            hipLaunchKernelGGL(k_xk_gather_x, ew(RD), dim3(256), 0, st, 0, rows, A, D, enc, (const int32_t*)nullptr, P + L.first, P + L.init_h,
+                               s.XH);
+        else
+            hipLaunchKernelGGL(k_xk_beam_gather, ew(RD), dim3(256), 0, st, t, rows, B, NB, A, D, enc, s.prefix[in], s.anc[in],
+                               s.Hout + (size_t)(t - 1) * NB * D, s.C, s.XH, s.Cin);
+        if ((rc = launch_gemm_f32(s.XH, 2 * D, P + L.wl, 4 * D, P + L.bl, s.G, 4 * D, rows, 4 * D, 2 * D, ACT_NONE, st))) return rc;
+        hipLaunchKernelGGL(k_xk_cell_fwd, ew(RD), dim3(256), 0, st, rows, D, s.G, t == 0 ? P + L.init_c : s.Cin, t == 0 ? 0 : D, s.C, Ht,
+                           (float*)nullptr);
+        if ((rc = launch_gemm_f32(Ht, D, P + L.ia_wbef, D, nullptr, Bt, D, rows, D, D, ACT_NONE, st))) return rc;
+        if ((rc = launch_gemm_f32(Ht, D, P + L.ia_wb, D, P + L.ia_bias, s.Qb, D, rows, D, D, ACT_NONE, st))) return rc;
+        hipLaunchKernelGGL(k_xk_beam_intra, dim3(rows), dim3(256), 0, st, t, NB, D, s.Bef, s.Qb, s.Hout, s.anc[in], P + L.ia_v, s.intra);
+        // glimpse
+        if ((rc = launch_gemm_f32(Ht, D, P + L.a_wq[0], D, P + L.a_bias[0], s.tmp1, D, rows, D, D, ACT_NONE, st))) return rc;
+        if ((rc = launch_gemm_f32(s.intra, D, P + L.a_wdec[0], D, nullptr, s.Cg, D, rows, D, D, ACT_NONE, st, s.tmp1, D, 1))) return rc;
+        hipLaunchKernelGGL(k_xk_beam_glimpse, dim3(N), dim3(256), lds, st, A, D, live, p->Rg, s.Cg, P + L.a_v[0], enc, s.q);
+        // pointer, selection and the new beams' prefixes / ancestor rows; the last step writes the caller's arrays
+        if ((rc = launch_gemm_f32(s.q, D, P + L.a_wq[1], D, P + L.a_bias[1], s.tmp1, D, rows, D, D, ACT_NONE, st))) return rc;
+        if ((rc = launch_gemm_f32(s.intra, D, P + L.a_wdec[1], D, nullptr, s.Cp, D, rows, D, D, ACT_NONE, st, s.tmp1, D, 1))) return rc;
+        const bool last = t + 1 == XK_T;
+        hipLaunchKernelGGL(k_xk_beam_select, dim3(N), dim3(256), lds, st, t, A, D, live, B, NB, p->Rp, s.Cp, P + L.a_v[1], p->loc, p->special,
+                           s.prefix[in], s.acc[in], s.anc[in], last ? path : s.prefix[out], last ? score : s.acc[out], s.anc[out], parent_tr,
+                           token_tr, score_tr);
     }
     RL4RS_LAUNCH_CHECK();
     return RL4RS_OK;
@@ -1051,6 +1160,7 @@ int64_t rl4rs_exactk_param_count(const rl4rs_exactk_cfg* cfg) {
 int rl4rs_exactk_destroy(rl4rs_exactk* p) {
     if (!p) return RL4RS_OK;
     if (p->arena) (void)hipFree(p->arena);
+    if (p->beam.mem) (void)hipFree(p->beam.mem);
     delete p;
     return RL4RS_OK;
 }
@@ -1140,6 +1250,18 @@ int rl4rs_exactk_decode(rl4rs_exactk* p, int32_t N, const float* obs_dev, int32_
     RL4RS_REQUIRE(p && obs_dev && path_dev && N > 0 && N <= p->c.max_rows, "exactk_decode: bad argument (N=%d, max_rows=%d)", N,
                   p ? p->c.max_rows : -1);
     return xk_forward(p, N, obs_dev, greedy ? 1 : 0, path_dev, nullptr, seed, step, 1u, logits_out_dev, (hipStream_t)stream);
+}
+
+int rl4rs_exactk_decode_beam(rl4rs_exactk* p, int32_t N, const float* obs_dev, int32_t beam, uint32_t seed, uint32_t step, int32_t* path_dev,
+                             float* score_dev, int32_t* parent_dev, int32_t* token_dev, float* step_score_dev, void* stream) {
+    RL4RS_REQUIRE(p && obs_dev, "exactk_decode_beam: null handle or observations");
+    RL4RS_REQUIRE(beam >= 1 && beam <= XK_BEAM_MAX, "exactk_decode_beam: beam %d outside [1, %d]", beam, XK_BEAM_MAX);
+    RL4RS_REQUIRE(N >= 1 && N <= p->c.max_rows, "exactk_decode_beam: N %d outside [1, max_rows = %d]", N, p->c.max_rows);
+    RL4RS_REQUIRE(path_dev && score_dev, "exactk_decode_beam: null output (path_dev, score_dev)");
+    const size_t lds = xk_beam_lds(p->d, beam);
+    RL4RS_REQUIRE(lds <= XK_LDS_MAX, "exactk_decode_beam: beam %d over action_size %d, width %d needs %zu bytes of LDS per workgroup "
+                  "(limit %zu)", beam, p->d.A, p->d.D, lds, XK_LDS_MAX);
+    return xk_beam_forward(p, N, obs_dev, beam, seed, step, path_dev, score_dev, parent_dev, token_dev, step_score_dev, (hipStream_t)stream);
 }
 
 int rl4rs_exactk_loss_grad(rl4rs_exactk* p, int32_t N, const float* obs_dev, const int32_t* path_dev, const float* weights_dev, uint32_t seed,

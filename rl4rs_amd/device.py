@@ -2339,6 +2339,27 @@ class DeviceExactK(_FlatNet):
                                            _ptr(lg), _stream()))
         return path, lg
 
+    BEAM_MAX = 8
+
+    def decode_beam(self, obs, beam_size=3, seed=0, step=0, want_trace=False):
+        """Beam search over the pointer decoder -> (paths int32 [N, beam_size, 9], scores float32 [N, beam_size]: the sum of the 9
+        log-probabilities, beam 0 the best, equal scores by the smaller parent * A + token), with the keep masks of ``decode`` at the
+        same (seed, step).  ``want_trace``: also a dict of [N, 9, beam_size] tensors ``parent`` (the beam of step t - 1 that beam k of
+        step t extends), ``token`` and ``score``."""
+        N, B = obs.shape[0], int(beam_size)               # (the library refuses a beam_size or N out of range, with the reason)
+        assert obs.dtype == torch.float32 and obs.shape == (N, self.obs_dim) and obs.is_contiguous() and obs.is_cuda
+        paths = torch.empty((N, max(B, 0), self.SLATE), dtype=torch.int32, device=self.device)
+        scores = torch.empty((N, max(B, 0)), dtype=torch.float32, device=self.device)
+        trace = None
+        if want_trace:
+            trace = dict(parent=torch.empty((N, self.SLATE, max(B, 0)), dtype=torch.int32, device=self.device),
+                         token=torch.empty((N, self.SLATE, max(B, 0)), dtype=torch.int32, device=self.device),
+                         score=torch.empty((N, self.SLATE, max(B, 0)), dtype=torch.float32, device=self.device))
+        tr = trace or dict(parent=None, token=None, score=None)
+        check(self.lib.rl4rs_exactk_decode_beam(self.h, N, _ptr(obs), B, seed & 0xffffffff, step & 0xffffffff, _ptr(paths), _ptr(scores),
+                                                _ptr(tr['parent']), _ptr(tr['token']), _ptr(tr['score']), _stream()))
+        return (paths, scores, trace) if want_trace else (paths, scores)
+
     def loss_grad(self, obs, path, weights, seed=0, step=0, want_logits=False):
         """Teacher-forced loss mean_n(w_n sum_t CE) and its gradient into the handle's buffer (``grad()``)
         -> (stats float32[2] = {loss, targets outside the allowed set}, logits [N, 9, A] or None)."""

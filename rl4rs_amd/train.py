@@ -1141,11 +1141,20 @@ class ExactKTrainer(_Evaluated):
     its two climbs and keeps the old observation, so its second slate is scored on different users than it was generated for;
     ``same_users=False`` is the reference as written.  (2) A batch whose advantage has zero or non-finite std skips the generator
     update (the reference would divide by zero); the decision is a device flag that gates the Adam step, counted in the statistics
-    (``skipped``, ``skipped_total``)."""
+    (``skipped``, ``skipped_total``).
+
+    ``eval_mode='beam'`` evaluates beam 0 of ``DeviceExactK.decode_beam(beam_size=...)`` in place of the greedy slate, at the same
+    (seed, step); training is the same in both modes."""
 
     def __init__(self, env, seed=0, init_seed=0, lr=1e-3, critic_lr=5e-3, dropout_rate=0.1, samples=2, same_users=True, hidden_units=64,
-                 num_heads=4, num_blocks=2, vocab=500, critic_hidden=128, temperature=1, num_glimpse=1, num_layers=1, use_mha=True):
+                 num_heads=4, num_blocks=2, vocab=500, critic_hidden=128, temperature=1, num_glimpse=1, num_layers=1, use_mha=True,
+                 eval_mode='greedy', beam_size=3):
         cfg = env.config
+        if eval_mode not in ('greedy', 'beam'):
+            raise ValueError("eval_mode must be 'greedy' or 'beam'; got %r" % (eval_mode,))
+        if not 1 <= int(beam_size) <= D.DeviceExactK.BEAM_MAX:
+            raise ValueError('beam_size must be in [1, %d]; got %r' % (D.DeviceExactK.BEAM_MAX, beam_size))
+        self.eval_mode, self.beam_size = eval_mode, int(beam_size)
         if getattr(getattr(env, 'samples', None), 'is_seq', False) or cfg['max_steps'] != D.DeviceExactK.SLATE:
             raise ValueError("ExactKTrainer runs SlateRecEnv-v0 (max_steps 9) only: on SeqSlateRecEnv-v0 the reference script indexes its "
                              "9-wide slate with 36 steps and cannot run either")
@@ -1253,7 +1262,11 @@ class ExactKTrainer(_Evaluated):
                 'skipped_total': self.skipped_total}
 
     def _eval_batch(self, k):
-        """One batch of greedy slates; dropout stays on (as in the reference's eval stage) with a fixed mask stream."""
+        """One batch of greedy slates (``eval_mode='beam'``: the best of ``beam_size`` beams); dropout stays on (as in the reference's
+        eval stage) with a fixed mask stream."""
         obs0 = self._obs(self.env.reset(reset_file=True) if k == 0 else self.env.reset())
-        path, _ = self.policy.decode(obs0, greedy=True, seed=self.seed, step=k)
+        if self.eval_mode == 'beam':
+            path = self.policy.decode_beam(obs0, beam_size=self.beam_size, seed=self.seed, step=k)[0][:, 0].contiguous()
+        else:
+            path, _ = self.policy.decode(obs0, greedy=True, seed=self.seed, step=k)
         return self._play(path).to(torch.float64).mean()

@@ -7,6 +7,9 @@
            alternate in one process, ``--pairs`` pairs, every sample = ``--updates`` updates between two synchronisations.
   decode   the sampled and the greedy decode (rl4rs_exactk_decode) at the same sizes against the eager-torch decoder
            (torch.multinomial / argmax per step), the same way.
+  beam     beam search (rl4rs_exactk_decode_beam, B = 3) at the same sizes against the greedy decode of N rows on the same handle (the
+           price of beam search over greedy) and against the greedy decode of 3 N rows (what 3 N replicated decoder rows would cost
+           with the encoder run for each; one call where max_rows allows, otherwise chunks of N rows), the same way.
   loop     SlateRecEnv-v0 B = 4096 env-steps/s with ExactKTrainer in the loop (two climbs of 9 steps per iteration).
 
 One JSON line on stdout (and --out FILE).  Needs a GPU: there is no CPU path."""
@@ -176,6 +179,57 @@ def net_legs(args, N):
     return out
 
 
+def paired_ab(a, b, name_a, name_b, pairs, updates):
+    """``paired`` for two device paths: alternating samples of a and b"""
+    for _ in range(3):
+        a()
+        b()
+    ps = [(timed(a, updates) * 1e6, timed(b, updates) * 1e6) for _ in range(pairs)]
+    x, y = np.array([p[0] for p in ps]), np.array([p[1] for p in ps])
+    return {'unit': 'us per call', 'pairs': [[round(u, 1), round(v, 1)] for u, v in ps], name_a + '_median': round(float(np.median(x)), 1),
+            name_b + '_median': round(float(np.median(y)), 1),
+            'ratio_%s_over_%s' % (name_a, name_b): round(float(np.median(x) / np.median(y)), 2)}
+
+
+def beam_legs(args, N, B=3):
+    import torch
+    from rl4rs_amd import synth
+    from rl4rs_amd.data import CatalogTables
+    from rl4rs_amd.device import DeviceExactK
+    from rl4rs_amd.nets.exactk import init_exactk_params
+    d = tempfile.mkdtemp(prefix='exactk_rate_')
+    synth.write_text(os.path.join(d, 'item_info.csv'), synth.make_catalog_text(seed=1234))
+    cat = CatalogTables(os.path.join(d, 'item_info.csv'), A)
+    rs = np.random.RandomState(0)
+    rows = B * N if B * N <= 1024 else N                   # the handle's max_rows: 3 N rows in one call where that stays small
+    net = DeviceExactK(cat.location_mask[:3], cat.is_special, max_rows=rows, obs_dim=OD, action_size=A, hidden_units=H, num_heads=HEADS,
+                       num_blocks=BLOCKS, vocab=VOCAB, dropout_rate=RATE, params=init_exactk_params(OD, H, BLOCKS, VOCAB, seed=1))
+    obs3 = torch.from_numpy(rs.randn(B * N, OD).astype(np.float32)).cuda()
+    obs = obs3[:N].contiguous()
+    chunks = [obs3[i:i + rows].contiguous() for i in range(0, B * N, rows)]
+    path = torch.empty((rows, T), dtype=torch.int32, device='cuda')
+    step = [0]
+
+    def beam():
+        step[0] += 1
+        net.decode_beam(obs, beam_size=B, seed=1, step=step[0])
+
+    def greedy():
+        step[0] += 1
+        net.decode(obs, greedy=True, seed=1, step=step[0], out=path[:N])
+
+    def greedy_replicated():
+        step[0] += 1
+        for c in chunks:
+            net.decode(c, greedy=True, seed=1, step=step[0], out=path[:c.shape[0]])
+
+    out = dict(rows=N, beam=B, updates_per_sample=args.updates, replicated_rows=B * N, replicated_calls=len(chunks))
+    out['beam_vs_greedy'] = paired_ab(beam, greedy, 'beam', 'greedy', args.pairs, args.updates)
+    out['beam_vs_replicated_greedy'] = paired_ab(beam, greedy_replicated, 'beam', 'replicated', args.pairs, args.updates)
+    net.close()
+    return out
+
+
 def loop_leg(args, steps=3):
     import torch
     import rl4rs_amd
@@ -212,7 +266,7 @@ def loop_leg(args, steps=3):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--legs', default='net,loop')
+    ap.add_argument('--legs', default='net,beam,loop')
     ap.add_argument('--rows', default='256,4096')
     ap.add_argument('--pairs', type=int, default=5)
     ap.add_argument('--updates', type=int, default=5)
@@ -226,6 +280,8 @@ def main():
     legs = args.legs.split(',')
     if 'net' in legs:
         result['net'] = [net_legs(args, int(n)) for n in args.rows.split(',')]
+    if 'beam' in legs:
+        result['beam'] = [beam_legs(args, int(n)) for n in args.rows.split(',')]
     if 'loop' in legs:
         result['loop'] = loop_leg(args)
     line = json.dumps(result)
