@@ -193,27 +193,25 @@ int rl4rs_combo_critic_loss(int32_t B, int32_t n_real, int32_t k, const float* q
 }
 
 namespace {
-struct ComboWs {
-    float *head_nxt, *head_obs, *a_next, *q1n, *q2n, *yq, *acts, *offs, *q1t, *q2t, *dq1t, *dq2t, *q1c, *q2c, *dq1c, *dq2c, *rows, *sums, *w,
-          *a_pi, *logp, *q1p, *q2p, *qmin, *dqa, *dqb, *g1, *g2, *d_head, *head_new, *a_tmp, *logp_t;
+struct ComboWs : SacWs {
+    float *acts, *offs, *q1t, *q2t, *dq1t, *dq2t, *q1c, *q2c, *dq1c, *dq2c, *rows, *sums, *w, *head_new, *logp_t;
     int64_t total, off_y, off_sums;
+    ComboWs(float* base, int64_t B, int64_t n_real, int64_t n, int64_t A);
 };
-ComboWs combo_ws(float* base, int64_t B, int64_t n_real, int64_t n, int64_t A) {
-    ComboWs w;
-    int64_t o = 0;
-    auto take = [&](int64_t cnt) { float* p = base ? base + o : nullptr; o += (cnt + 3) / 4 * 4; return p; };
+ComboWs::ComboWs(float* base, int64_t B, int64_t n_real, int64_t n, int64_t A) {
+    ComboWs& w = *this;
+    WsTake take{base};
     const int64_t F = B - n_real, R = F * 3 * n;
     w.head_nxt = take(B * 2 * A); w.head_obs = take(B * 2 * A); w.a_next = take(B * A); w.q1n = take(B); w.q2n = take(B);
-    w.off_y = o; w.yq = take(B);
+    w.off_y = take.o; w.yq = take(B);
     w.acts = take(R * A); w.offs = take(R);
     w.q1t = take(B); w.q2t = take(B); w.dq1t = take(B); w.dq2t = take(B);
     w.q1c = take(R); w.q2c = take(R); w.dq1c = take(R); w.dq2c = take(R);
     w.rows = take(B * 4 + F * 2);
-    w.off_sums = o; w.sums = take(8); w.w = take(4);
+    w.off_sums = take.o; w.sums = take(8); w.w = take(4);
     w.a_pi = take(B * A); w.logp = take(B); w.q1p = take(B); w.q2p = take(B); w.qmin = take(B); w.dqa = take(B); w.dqb = take(B);
     w.g1 = take(B * A); w.g2 = take(B * A); w.d_head = take(B * 2 * A); w.head_new = take(B * 2 * A); w.a_tmp = take(B * A); w.logp_t = take(B);
-    w.total = o;
-    return w;
+    w.total = take.o;
 }
 }  // namespace
 
@@ -222,12 +220,12 @@ int64_t rl4rs_combo_workspace_floats(int32_t B, int32_t n_real, int32_t n, int32
         set_error("combo_workspace_floats: bad sizes (B=%d, n_real=%d, n=%d, A=%d)", B, n_real, n, A);
         return -1;
     }
-    return combo_ws(nullptr, B, n_real, n, A).total;
+    return ComboWs(nullptr, B, n_real, n, A).total;
 }
 
 int64_t rl4rs_combo_workspace_offset(int32_t B, int32_t n_real, int32_t n, int32_t A, int32_t what) {
     if (rl4rs_combo_workspace_floats(B, n_real, n, A) < 0) return -1;
-    const ComboWs w = combo_ws(nullptr, B, n_real, n, A);
+    const ComboWs w(nullptr, B, n_real, n, A);
     if (what == 0) return w.off_y;
     if (what == 1) return w.off_sums;
     set_error("combo_workspace_offset: what=%d (0 = y, 1 = the six sums)", what);
@@ -247,8 +245,8 @@ int rl4rs_combo_update(const rl4rs_combo_step* s, void* stream) {
                   "combo_update: the critics do not match each other or the policy");
     hipStream_t st = (hipStream_t)stream;
     const int B = s->B, n_real = s->n_real, n = s->n, A = s->A, D = s->policy->c.obs_dim, F = B - n_real, k = 3 * n, R = F * k;
-    const ComboWs w = combo_ws(s->workspace_dev, B, n_real, n, A);
-    const float lo = -20.f, hi = 2.f;
+    const ComboWs w(s->workspace_dev, B, n_real, n, A);
+    const float lo = SAC_MIN_LOGSTD, hi = SAC_MAX_LOGSTD;
     const float* eps_t = s->normal_dev;
     const float* eps_tp1 = eps_t + (size_t)F * n * A;
     const float* eps_actor = eps_tp1 + (size_t)F * n * A;
@@ -256,84 +254,47 @@ int rl4rs_combo_update(const rl4rs_combo_step* s, void* stream) {
     const float* obs_f = s->obs_dev + (size_t)n_real * D;
     const float log_uniform = (float)((double)A * log(0.5));
     rl4rs_amlp* twin[2] = {s->q1, s->q2};
-    int rc;
-#define CU(expr) do { if ((rc = (expr)) != RL4RS_OK) return rc; } while (0)
-    // the policy does not change until the actor step: its heads on s' and s are computed once (s last: the handle keeps the
-    // activations of s for the actor's backward).  The generated rows' heads are rows n_real .. B - 1 of these two forwards.
-    CU(rl4rs_amlp_forward(s->policy, B, 1, s->nxt_dev, nullptr, w.head_nxt, stream));
-    CU(rl4rs_amlp_forward(s->policy, B, 1, s->obs_dev, nullptr, w.head_obs, stream));
-    // --- target (deterministic backup): y = r + gamma (1 - ter) min_c Qtarg_c(s', tanh(mu(s')))
-    CU(rl4rs_squashed_sample(B, 1, A, w.head_nxt, nullptr, lo, hi, 1, 0, w.a_next, nullptr, stream));
-    {
-        rl4rs_amlp* targ[2] = {s->q1_targ, s->q2_targ};
-        float* qn[2] = {w.q1n, w.q2n};
-        CU(rl4rs_amlp_forward_multi(2, targ, B, s->nxt_dev, w.a_next, qn, stream));
-    }
-    CU(rl4rs_bcq_target(B, 1, w.q1n, w.q2n, 1.0f, s->rew_dev, s->ter_dev, s->gamma, w.yq, nullptr, stream));
+    // (the generated rows' heads are rows n_real .. B - 1 of the two forwards)
+    RL4RS_TRY(sac_policy_heads(s, w, stream));
+    RL4RS_TRY(sac_deterministic_target(s, w, stream));
     // --- the F * 3n rows of pass C: [pi(s_f) | pi(s'_f) | uniform] with their importance offsets
     hipLaunchKernelGGL(k_combo_fill_rows, dim3((F * n * A + 255) / 256), dim3(256), 0, st, w.acts, w.offs, s->uniform_dev, F, n, A, log_uniform,
                        s->conservative_weight, w.w);
-    CU(rl4rs_squashed_sample(F * n, n, A, w.head_obs + (size_t)n_real * 2 * A, eps_t, lo, hi, k, 0, w.acts, w.offs, stream));
-    CU(rl4rs_squashed_sample(F * n, n, A, w.head_nxt + (size_t)n_real * 2 * A, eps_tp1, lo, hi, k, n, w.acts, w.offs, stream));
+    RL4RS_TRY(rl4rs_squashed_sample(F * n, n, A, w.head_obs + (size_t)n_real * 2 * A, eps_t, lo, hi, k, 0, w.acts, w.offs, stream));
+    RL4RS_TRY(rl4rs_squashed_sample(F * n, n, A, w.head_nxt + (size_t)n_real * 2 * A, eps_tp1, lo, hi, k, n, w.acts, w.offs, stream));
     // --- critic, pass T
     {
         float* qv[2] = {w.q1t, w.q2t};
-        CU(rl4rs_amlp_forward_multi(2, twin, B, s->obs_dev, s->act_dev, qv, stream));
-        CU(rl4rs_combo_critic_loss(B, n_real, k, w.q1t, w.q2t, w.yq, nullptr, nullptr, nullptr, w.w, w.dq1t, w.dq2t, nullptr, nullptr, w.rows, nullptr, stream));
+        RL4RS_TRY(rl4rs_amlp_forward_multi(2, twin, B, s->obs_dev, s->act_dev, qv, stream));
+        RL4RS_TRY(rl4rs_combo_critic_loss(B, n_real, k, w.q1t, w.q2t, w.yq, nullptr, nullptr, nullptr, w.w, w.dq1t, w.dq2t, nullptr, nullptr, w.rows, nullptr, stream));
         const float* dq[2] = {w.dq1t, w.dq2t};
-        CU(rl4rs_amlp_backward_multi(2, twin, B, s->obs_dev, s->act_dev, dq, nullptr, 1, stream));
+        RL4RS_TRY(rl4rs_amlp_backward_multi(2, twin, B, s->obs_dev, s->act_dev, dq, nullptr, 1, stream));
     }
     float* stash[2] = {s->stash_dev, s->stash_dev + (s->q1->opt.n + 3) / 4 * 4};
-    CU(rl4rs_amlp_grad_stash(2, twin, stash, 0, stream));
+    RL4RS_TRY(rl4rs_amlp_grad_stash(2, twin, stash, 0, stream));
     // --- critic, pass C
-    CU(rl4rs_amlp_forward(s->q1, R, k, obs_f, w.acts, w.q1c, stream));
-    CU(rl4rs_amlp_forward(s->q2, R, k, obs_f, w.acts, w.q2c, stream));
-    CU(rl4rs_combo_critic_loss(B, n_real, k, nullptr, nullptr, nullptr, w.q1c, w.q2c, w.offs, w.w, nullptr, nullptr, w.dq1c, w.dq2c, w.rows, w.sums, stream));
-    CU(rl4rs_amlp_backward(s->q1, R, k, obs_f, w.acts, w.dq1c, nullptr, 1, stream));
-    CU(rl4rs_amlp_backward(s->q2, R, k, obs_f, w.acts, w.dq2c, nullptr, 1, stream));
-    CU(rl4rs_amlp_grad_stash(2, twin, stash, 1, stream));
-    {
-        const float lr[2] = {s->critic_lr, s->critic_lr};
-        const int32_t on[2] = {1, 1};
-        CU(rl4rs_amlp_adam_multi(2, twin, lr, on, nullptr, 0.9f, 0.999f, 1e-8f, 0.f, stream));
-    }
+    RL4RS_TRY(rl4rs_amlp_forward(s->q1, R, k, obs_f, w.acts, w.q1c, stream));
+    RL4RS_TRY(rl4rs_amlp_forward(s->q2, R, k, obs_f, w.acts, w.q2c, stream));
+    RL4RS_TRY(rl4rs_combo_critic_loss(B, n_real, k, nullptr, nullptr, nullptr, w.q1c, w.q2c, w.offs, w.w, nullptr, nullptr, w.dq1c, w.dq2c, w.rows, w.sums, stream));
+    RL4RS_TRY(rl4rs_amlp_backward(s->q1, R, k, obs_f, w.acts, w.dq1c, nullptr, 1, stream));
+    RL4RS_TRY(rl4rs_amlp_backward(s->q2, R, k, obs_f, w.acts, w.dq2c, nullptr, 1, stream));
+    RL4RS_TRY(rl4rs_amlp_grad_stash(2, twin, stash, 1, stream));
+    RL4RS_TRY(amlp_adam_pair(s->q1, s->q2, s->critic_lr, stream));
     if (!s->do_actor) {
         hipLaunchKernelGGL(k_combo_metrics, dim3(1), dim3(256), 0, st, w.sums, B, n_real, w.w, s->log_temp_dev, nullptr, nullptr, s->metrics_dev);
         RL4RS_LAUNCH_CHECK();
         return RL4RS_OK;
     }
-    // --- actor (SACImpl.compute_actor_loss): (exp(log_temp) * logp - min_c Q_c(s, a)).mean() through the stepped critics
-    CU(rl4rs_squashed_sample(B, 1, A, w.head_obs, eps_actor, lo, hi, 1, 0, w.a_pi, w.logp, stream));
-    {
-        float* qp[2] = {w.q1p, w.q2p};
-        CU(rl4rs_amlp_forward_multi(2, twin, B, s->obs_dev, w.a_pi, qp, stream));
-        CU(rl4rs_twin_min(B, w.q1p, w.q2p, w.qmin, w.dqa, w.dqb, stream));
-        const float* dq[2] = {w.dqa, w.dqb};
-        float* ga[2] = {w.g1, w.g2};
-        CU(rl4rs_amlp_backward_multi(2, twin, B, s->obs_dev, w.a_pi, dq, ga, 0, stream));
-    }
-    hipLaunchKernelGGL(k_add2, dim3((B * A + 255) / 256), dim3(256), 0, st, w.g1, w.g2, w.g1, B * A);
-    CU(rl4rs_sac_actor_grad(B, A, w.head_obs, eps_actor, w.a_pi, w.g1, s->log_temp_dev, lo, hi, w.d_head, stream));
-    // (the policy handle's activations are those of the forward on obs, its last one above)
-    CU(rl4rs_amlp_backward(s->policy, B, 1, s->obs_dev, nullptr, w.d_head, nullptr, 1, stream));
+    // --- actor through the stepped critics; the metrics read logp and qmin before the Adam (which reads neither, nor what the
+    // temperature step writes)
+    RL4RS_TRY(sac_actor_phase(s, w, eps_actor, stream));
     hipLaunchKernelGGL(k_combo_metrics, dim3(1), dim3(256), 0, st, w.sums, B, n_real, w.w, s->log_temp_dev, w.logp, w.qmin, s->metrics_dev);
-    {
-        // the policy's Adam and the soft critic-target update in one launch (neither reads what the temperature step writes)
-        rl4rs_amlp* nets[3] = {s->policy, s->q1, s->q2};
-        rl4rs_amlp* targ[3] = {nullptr, s->q1_targ, s->q2_targ};
-        const float lr3[3] = {s->actor_lr, 0.f, 0.f};
-        const int32_t on3[3] = {1, 0, 0};
-        CU(rl4rs_amlp_adam_multi(3, nets, lr3, on3, targ, 0.9f, 0.999f, 1e-8f, s->tau, stream));
-    }
+    RL4RS_TRY(sac_actor_adam(s, stream));
     // --- temperature (SACImpl.update_temp) on the STEPPED policy, as MOPO.update orders it
     if (s->temp_lr > 0.f) {
-        auto adam_c = [](int64_t step_after, double beta) { return (float)(1.0 / (1.0 - pow(beta, (double)step_after))); };
-        CU(rl4rs_amlp_forward(s->policy, B, 1, s->obs_dev, nullptr, w.head_new, stream));
-        CU(rl4rs_squashed_sample(B, 1, A, w.head_new, eps_temp, lo, hi, 1, 0, w.a_tmp, w.logp_t, stream));
-        hipLaunchKernelGGL(k_sac_temp_step, dim3(1), dim3(256), 0, st, w.logp_t, B, A, s->log_temp_dev, s->log_temp_dev + 1, s->log_temp_dev + 2, s->temp_lr,
-                           adam_c(s->temp_step + 1, 0.9), adam_c(s->temp_step + 1, 0.999), s->metrics_dev + 2);
+        RL4RS_TRY(rl4rs_amlp_forward(s->policy, B, 1, s->obs_dev, nullptr, w.head_new, stream));
+        RL4RS_TRY(sac_temp_step(s, w.head_new, eps_temp, w.a_tmp, w.logp_t, stream));
     }
-#undef CU
     RL4RS_LAUNCH_CHECK();
     return RL4RS_OK;
 }

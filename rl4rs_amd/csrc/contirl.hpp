@@ -811,6 +811,97 @@ int rl4rs_cql_critic_loss(int32_t B, int32_t m, const float* q1, const float* q2
 }
 
 
+}  // extern "C"
+
+// ---- what the one-call updates below (and rl4rs_combo_update in combo.hpp) share
+namespace {
+#define RL4RS_TRY(expr) do { const int rc_ = (expr); if (rc_ != RL4RS_OK) return rc_; } while (0)
+
+// bump allocator of the *_ws layouts: every buffer starts on a 16-byte boundary; a null base only sizes
+struct WsTake {
+    float* base;
+    int64_t o = 0;
+    float* operator()(int64_t cnt) { float* p = base ? base + o : nullptr; o += (cnt + 3) / 4 * 4; return p; }
+};
+
+// a forward that no backward follows: the fused fp16x2 form when the step asks for it, the network has one, there are at least
+// h16_min_rows rows and every pointer or-ed into `aligned` sits on a 16-byte boundary; else the fp32 forward
+int amlp_nograd_forward(rl4rs_amlp* p, int R, int rep, const float* obs, const float* act, float* out, int nograd_h16, int h16_min_rows,
+                        uintptr_t aligned, void* stream) {
+    if (nograd_h16 && p->w1p && R >= h16_min_rows && (aligned & 15) == 0) return rl4rs_amlp_forward_h16(p, R, rep, obs, act, out, stream);
+    return rl4rs_amlp_forward(p, R, rep, obs, act, out, stream);
+}
+
+// torch.optim.Adam of two networks at one rate in one launch, no targets (the imitator pair, the twin critics)
+int amlp_adam_pair(rl4rs_amlp* a, rl4rs_amlp* b, float lr, void* stream) {
+    rl4rs_amlp* nets[2] = {a, b};
+    const float lrs[2] = {lr, lr};
+    const int32_t on[2] = {1, 1};
+    return rl4rs_amlp_adam_multi(2, nets, lrs, on, nullptr, 0.9f, 0.999f, 1e-8f, 0.f, stream);
+}
+
+// the buffers of the SAC phases inside a learner's workspace (CqlWs and ComboWs place them); Step below is rl4rs_cql_step or
+// rl4rs_combo_step, which name the handles, rows and scalars alike
+struct SacWs {
+    float *head_nxt, *head_obs, *a_next, *q1n, *q2n, *yq, *a_pi, *logp, *q1p, *q2p, *qmin, *dqa, *dqb, *g1, *g2, *d_head, *a_tmp;
+};
+constexpr float SAC_MIN_LOGSTD = -20.f, SAC_MAX_LOGSTD = 2.f;
+
+// the policy does not change until the actor step: its heads on s' and s are computed once (s last: the handle keeps the
+// activations of s for the actor's backward)
+template <class Step> int sac_policy_heads(const Step* s, const SacWs& w, void* stream) {
+    RL4RS_TRY(rl4rs_amlp_forward(s->policy, s->B, 1, s->nxt_dev, nullptr, w.head_nxt, stream));
+    return rl4rs_amlp_forward(s->policy, s->B, 1, s->obs_dev, nullptr, w.head_obs, stream);
+}
+
+// deterministic backup: y = r + gamma (1 - ter) min_c Qtarg_c(s', tanh(mu(s')))
+template <class Step> int sac_deterministic_target(const Step* s, const SacWs& w, void* stream) {
+    RL4RS_TRY(rl4rs_squashed_sample(s->B, 1, s->A, w.head_nxt, nullptr, SAC_MIN_LOGSTD, SAC_MAX_LOGSTD, 1, 0, w.a_next, nullptr, stream));
+    rl4rs_amlp* targ[2] = {s->q1_targ, s->q2_targ};
+    float* qn[2] = {w.q1n, w.q2n};
+    RL4RS_TRY(rl4rs_amlp_forward_multi(2, targ, s->B, s->nxt_dev, w.a_next, qn, stream));
+    return rl4rs_bcq_target(s->B, 1, w.q1n, w.q2n, 1.0f, s->rew_dev, s->ter_dev, s->gamma, w.yq, nullptr, stream);
+}
+
+// actor (SACImpl.compute_actor_loss): the gradient of (exp(log_temp) * logp - min_c Q_c(s, a)).mean() in the policy handle; leaves logp
+// and qmin for the caller's metrics kernel.  sac_actor_adam follows (COMBO launches its metrics in between).
+template <class Step> int sac_actor_phase(const Step* s, const SacWs& w, const float* eps_actor, void* stream) {
+    const int B = s->B, A = s->A;
+    rl4rs_amlp* twin[2] = {s->q1, s->q2};
+    float* qp[2] = {w.q1p, w.q2p};
+    const float* dq[2] = {w.dqa, w.dqb};
+    float* ga[2] = {w.g1, w.g2};
+    RL4RS_TRY(rl4rs_squashed_sample(B, 1, A, w.head_obs, eps_actor, SAC_MIN_LOGSTD, SAC_MAX_LOGSTD, 1, 0, w.a_pi, w.logp, stream));
+    RL4RS_TRY(rl4rs_amlp_forward_multi(2, twin, B, s->obs_dev, w.a_pi, qp, stream));
+    RL4RS_TRY(rl4rs_twin_min(B, w.q1p, w.q2p, w.qmin, w.dqa, w.dqb, stream));
+    RL4RS_TRY(rl4rs_amlp_backward_multi(2, twin, B, s->obs_dev, w.a_pi, dq, ga, 0, stream));
+    hipLaunchKernelGGL(k_add2, dim3((B * A + 255) / 256), dim3(256), 0, (hipStream_t)stream, w.g1, w.g2, w.g1, B * A);
+    RL4RS_TRY(rl4rs_sac_actor_grad(B, A, w.head_obs, eps_actor, w.a_pi, w.g1, s->log_temp_dev, SAC_MIN_LOGSTD, SAC_MAX_LOGSTD, w.d_head, stream));
+    // (the policy handle's activations are those of the forward on obs, its last one in sac_policy_heads)
+    return rl4rs_amlp_backward(s->policy, B, 1, s->obs_dev, nullptr, w.d_head, nullptr, 1, stream);
+}
+
+// the policy's Adam and the soft critic-target update in one launch
+template <class Step> int sac_actor_adam(const Step* s, void* stream) {
+    rl4rs_amlp* nets[3] = {s->policy, s->q1, s->q2};
+    rl4rs_amlp* targ[3] = {nullptr, s->q1_targ, s->q2_targ};
+    const float lr3[3] = {s->actor_lr, 0.f, 0.f};
+    const int32_t on3[3] = {1, 0, 0};
+    return rl4rs_amlp_adam_multi(3, nets, lr3, on3, targ, 0.9f, 0.999f, 1e-8f, s->tau, stream);
+}
+
+// temperature (SACImpl.update_temp): one sample from `head`, then Adam on log_temp of -(exp(log_temp) * (logp - A)).mean()
+template <class Step> int sac_temp_step(const Step* s, const float* head, const float* eps, float* a_tmp, float* logp, void* stream) {
+    auto adam_c = [](int64_t step_after, double beta) { return (float)(1.0 / (1.0 - pow(beta, (double)step_after))); };
+    RL4RS_TRY(rl4rs_squashed_sample(s->B, 1, s->A, head, eps, SAC_MIN_LOGSTD, SAC_MAX_LOGSTD, 1, 0, a_tmp, logp, stream));
+    hipLaunchKernelGGL(k_sac_temp_step, dim3(1), dim3(256), 0, (hipStream_t)stream, logp, s->B, s->A, s->log_temp_dev, s->log_temp_dev + 1,
+                       s->log_temp_dev + 2, s->temp_lr, adam_c(s->temp_step + 1, 0.9), adam_c(s->temp_step + 1, 0.999), s->metrics_dev + 2);
+    return RL4RS_OK;
+}
+}  // namespace
+
+extern "C" {
+
 // ---- one whole BCQ update as one host call (include/rl4rs_hip.h: rl4rs_bcq_step)
 namespace {
 struct BcqWs {
@@ -820,8 +911,7 @@ struct BcqWs {
 };
 BcqWs bcq_ws(float* base, int64_t B, int64_t n, int64_t E, int64_t L) {
     BcqWs w;
-    int64_t o = 0;
-    auto take = [&](int64_t cnt) { float* p = base ? base + o : nullptr; o += (cnt + 3) / 4 * 4; return p; };
+    WsTake take{base};
     const int64_t R = B * n;
     w.enc_out = take(B * 2 * L); w.z = take(B * L); w.y = take(B * E); w.d_dec = take(B * E); w.rows = take(B * 2); w.loss2 = take(2);
     w.dz = take(B * L); w.d_enc = take(B * 2 * L);
@@ -829,7 +919,7 @@ BcqWs bcq_ws(float* base, int64_t B, int64_t n, int64_t E, int64_t L) {
     w.q1v = take(B); w.q2v = take(B); w.dq1 = take(B); w.dq2 = take(B); w.closs2 = take(2);
     w.sampled2 = take(B * E); w.t2 = take(B * E); w.a_pi = take(B * E); w.qv = take(B); w.minus_inv_b = take(B); w.da = take(B * E);
     w.d_pre = take(B * E);
-    w.total = o;
+    w.total = take.o;
     return w;
 }
 }  // namespace
@@ -848,65 +938,53 @@ int rl4rs_bcq_update(const rl4rs_bcq_step* s, void* stream) {
     float* zt = s->noise_dev + (size_t)B * L;
     float* za = zt + (size_t)R * L;
     const float lo = -20.f, hi = 2.f;
-    int rc;
-#define BU(expr) do { if ((rc = (expr)) != RL4RS_OK) return rc; } while (0)
     {
         const long long nz = (long long)(R + B) * L;
         hipLaunchKernelGGL(k_bcq_prep, dim3((unsigned)((std::max<long long>(nz, B) + 255) / 256)), dim3(256), 0, st, zt, nz, w.minus_inv_b, B);
     }
     // --- imitator (BCQImpl.update_imitator: ConditionalVAE.compute_error)
-    BU(rl4rs_amlp_forward(s->imit_enc, B, 1, s->obs_dev, s->act_dev, w.enc_out, stream));
-    BU(rl4rs_cvae_sample(B, L, w.enc_out, eps, lo, hi, w.z, stream));
-    BU(rl4rs_amlp_forward(s->imit_dec, B, 1, s->obs_dev, w.z, w.y, stream));
-    BU(rl4rs_cvae_loss(B, E, L, w.y, s->act_dev, w.enc_out, lo, hi, w.d_dec, w.rows, w.loss2, stream));
-    BU(rl4rs_amlp_backward(s->imit_dec, B, 1, s->obs_dev, w.z, w.d_dec, w.dz, 1, stream));
-    BU(rl4rs_cvae_encoder_grad(B, L, w.enc_out, eps, w.dz, s->beta, lo, hi, w.d_enc, stream));
-    BU(rl4rs_amlp_backward(s->imit_enc, B, 1, s->obs_dev, s->act_dev, w.d_enc, nullptr, 1, stream));
-    {
-        rl4rs_amlp* nets[2] = {s->imit_enc, s->imit_dec};
-        const float lr[2] = {s->imitator_lr, s->imitator_lr};
-        const int32_t on[2] = {1, 1};
-        BU(rl4rs_amlp_adam_multi(2, nets, lr, on, nullptr, 0.9f, 0.999f, 1e-8f, 0.f, stream));
-    }
+    RL4RS_TRY(rl4rs_amlp_forward(s->imit_enc, B, 1, s->obs_dev, s->act_dev, w.enc_out, stream));
+    RL4RS_TRY(rl4rs_cvae_sample(B, L, w.enc_out, eps, lo, hi, w.z, stream));
+    RL4RS_TRY(rl4rs_amlp_forward(s->imit_dec, B, 1, s->obs_dev, w.z, w.y, stream));
+    RL4RS_TRY(rl4rs_cvae_loss(B, E, L, w.y, s->act_dev, w.enc_out, lo, hi, w.d_dec, w.rows, w.loss2, stream));
+    RL4RS_TRY(rl4rs_amlp_backward(s->imit_dec, B, 1, s->obs_dev, w.z, w.d_dec, w.dz, 1, stream));
+    RL4RS_TRY(rl4rs_cvae_encoder_grad(B, L, w.enc_out, eps, w.dz, s->beta, lo, hi, w.d_enc, stream));
+    RL4RS_TRY(rl4rs_amlp_backward(s->imit_enc, B, 1, s->obs_dev, s->act_dev, w.d_enc, nullptr, 1, stream));
+    RL4RS_TRY(amlp_adam_pair(s->imit_enc, s->imit_dec, s->imitator_lr, stream));
     if (s->do_rl) {
         // --- critic (DDPGBaseImpl.update_critic with BCQImpl.compute_target): the B * n target rows are never differentiated
         auto nograd_forward = [&](rl4rs_amlp* p, const float* act, float* out) {
-            if (s->nograd_h16 && p->w1p && R >= s->h16_min_rows && ((uintptr_t)act & 15) == 0 && ((uintptr_t)out & 15) == 0)
-                return rl4rs_amlp_forward_h16(p, R, n, s->nxt_dev, act, out, stream);
-            return rl4rs_amlp_forward(p, R, n, s->nxt_dev, act, out, stream);
+            return amlp_nograd_forward(p, R, n, s->nxt_dev, act, out, s->nograd_h16, s->h16_min_rows, (uintptr_t)act | (uintptr_t)out, stream);
         };
-        BU(nograd_forward(s->imit_dec, zt, w.sampled));
-        BU(nograd_forward(s->policy_targ, w.sampled, w.t));
-        BU(rl4rs_residual_action(R, E, w.sampled, w.t, s->action_flexibility, w.a_next, stream));
-        BU(nograd_forward(s->q1_targ, w.a_next, w.q1n));
-        BU(nograd_forward(s->q2_targ, w.a_next, w.q2n));
-        BU(rl4rs_bcq_target(B, n, w.q1n, w.q2n, s->lam, s->rew_dev, s->ter_dev, s->gamma, w.yq, nullptr, stream));
+        RL4RS_TRY(nograd_forward(s->imit_dec, zt, w.sampled));
+        RL4RS_TRY(nograd_forward(s->policy_targ, w.sampled, w.t));
+        RL4RS_TRY(rl4rs_residual_action(R, E, w.sampled, w.t, s->action_flexibility, w.a_next, stream));
+        RL4RS_TRY(nograd_forward(s->q1_targ, w.a_next, w.q1n));
+        RL4RS_TRY(nograd_forward(s->q2_targ, w.a_next, w.q2n));
+        RL4RS_TRY(rl4rs_bcq_target(B, n, w.q1n, w.q2n, s->lam, s->rew_dev, s->ter_dev, s->gamma, w.yq, nullptr, stream));
         rl4rs_amlp* twin[2] = {s->q1, s->q2};
         float* qv2[2] = {w.q1v, w.q2v};
-        BU(rl4rs_amlp_forward_multi(2, twin, B, s->obs_dev, s->act_dev, qv2, stream));
-        BU(rl4rs_critic_mse(B, w.q1v, w.q2v, w.yq, w.dq1, w.dq2, w.closs2, stream));
+        RL4RS_TRY(rl4rs_amlp_forward_multi(2, twin, B, s->obs_dev, s->act_dev, qv2, stream));
+        RL4RS_TRY(rl4rs_critic_mse(B, w.q1v, w.q2v, w.yq, w.dq1, w.dq2, w.closs2, stream));
         const float* dq[2] = {w.dq1, w.dq2};
-        BU(rl4rs_amlp_backward_multi(2, twin, B, s->obs_dev, s->act_dev, dq, nullptr, 1, stream));
-        const float lr[2] = {s->critic_lr, s->critic_lr};
-        const int32_t on[2] = {1, 1};
-        BU(rl4rs_amlp_adam_multi(2, twin, lr, on, nullptr, 0.9f, 0.999f, 1e-8f, 0.f, stream));
+        RL4RS_TRY(rl4rs_amlp_backward_multi(2, twin, B, s->obs_dev, s->act_dev, dq, nullptr, 1, stream));
+        RL4RS_TRY(amlp_adam_pair(s->q1, s->q2, s->critic_lr, stream));
         if (s->do_actor) {
             // --- actor (BCQImpl.compute_actor_loss: -Q_1(s, pi(s, decode(s, z))).mean()) + the soft target updates
-            BU(rl4rs_amlp_forward(s->imit_dec, B, 1, s->obs_dev, za, w.sampled2, stream));
-            BU(rl4rs_amlp_forward(s->policy, B, 1, s->obs_dev, w.sampled2, w.t2, stream));
-            BU(rl4rs_residual_action(B, E, w.sampled2, w.t2, s->action_flexibility, w.a_pi, stream));
-            BU(rl4rs_amlp_forward(s->q1, B, 1, s->obs_dev, w.a_pi, w.qv, stream));
-            BU(rl4rs_amlp_backward(s->q1, B, 1, s->obs_dev, w.a_pi, w.minus_inv_b, w.da, 0, stream));
-            BU(rl4rs_residual_grad(B, E, w.sampled2, w.t2, s->action_flexibility, w.da, w.d_pre, stream));
-            BU(rl4rs_amlp_backward(s->policy, B, 1, s->obs_dev, w.sampled2, w.d_pre, nullptr, 1, stream));
+            RL4RS_TRY(rl4rs_amlp_forward(s->imit_dec, B, 1, s->obs_dev, za, w.sampled2, stream));
+            RL4RS_TRY(rl4rs_amlp_forward(s->policy, B, 1, s->obs_dev, w.sampled2, w.t2, stream));
+            RL4RS_TRY(rl4rs_residual_action(B, E, w.sampled2, w.t2, s->action_flexibility, w.a_pi, stream));
+            RL4RS_TRY(rl4rs_amlp_forward(s->q1, B, 1, s->obs_dev, w.a_pi, w.qv, stream));
+            RL4RS_TRY(rl4rs_amlp_backward(s->q1, B, 1, s->obs_dev, w.a_pi, w.minus_inv_b, w.da, 0, stream));
+            RL4RS_TRY(rl4rs_residual_grad(B, E, w.sampled2, w.t2, s->action_flexibility, w.da, w.d_pre, stream));
+            RL4RS_TRY(rl4rs_amlp_backward(s->policy, B, 1, s->obs_dev, w.sampled2, w.d_pre, nullptr, 1, stream));
             rl4rs_amlp* nets[3] = {s->policy, s->q1, s->q2};
             rl4rs_amlp* targ[3] = {s->policy_targ, s->q1_targ, s->q2_targ};
             const float lr3[3] = {s->actor_lr, 0.f, 0.f};
             const int32_t on3[3] = {1, 0, 0};
-            BU(rl4rs_amlp_adam_multi(3, nets, lr3, on3, targ, 0.9f, 0.999f, 1e-8f, s->tau, stream));
+            RL4RS_TRY(rl4rs_amlp_adam_multi(3, nets, lr3, on3, targ, 0.9f, 0.999f, 1e-8f, s->tau, stream));
         }
     }
-#undef BU
     hipLaunchKernelGGL(k_bcq_metrics, dim3(1), dim3(256), 0, st, w.loss2, 1.0f / (float)E, s->beta / (float)L, s->do_rl ? w.closs2 : nullptr,
                        (s->do_rl && s->do_actor) ? w.qv : nullptr, B, s->metrics_dev);
     RL4RS_LAUNCH_CHECK();
@@ -916,27 +994,25 @@ int rl4rs_bcq_update(const rl4rs_bcq_step* s, void* stream) {
 
 // ---- one whole continuous-CQL update as one host call (include/rl4rs_hip.h: rl4rs_cql_step)
 namespace {
-struct CqlWs {
-    float *head_nxt, *head_obs, *a_tmp, *logp, *acts, *offs, *q1m, *q2m, *rows, *sums, *aw, *a_next, *q1n, *q2n, *yq, *dq1, *dq2, *a_pi, *q1p, *q2p,
-          *qmin, *dqa, *dqb, *g1, *g2, *d_head;
+struct CqlWs : SacWs {
+    float *acts, *offs, *q1m, *q2m, *rows, *sums, *aw, *dq1, *dq2;
     int64_t total;
+    CqlWs(float* base, int64_t B, int64_t n, int64_t A);
 };
-CqlWs cql_ws(float* base, int64_t B, int64_t n, int64_t A) {
-    CqlWs w;
-    int64_t o = 0;
-    auto take = [&](int64_t cnt) { float* p = base ? base + o : nullptr; o += (cnt + 3) / 4 * 4; return p; };
+CqlWs::CqlWs(float* base, int64_t B, int64_t n, int64_t A) {
+    CqlWs& w = *this;
+    WsTake take{base};
     const int64_t m = 1 + 3 * n;
     w.head_nxt = take(B * 2 * A); w.head_obs = take(B * 2 * A); w.a_tmp = take(B * A); w.logp = take(B);
     w.acts = take(B * m * A); w.offs = take(B * m); w.q1m = take(B * m); w.q2m = take(B * m); w.rows = take(B * 6); w.sums = take(8); w.aw = take(4);
     w.a_next = take(B * A); w.q1n = take(B); w.q2n = take(B); w.yq = take(B); w.dq1 = take(B * m); w.dq2 = take(B * m);
     w.a_pi = take(B * A); w.q1p = take(B); w.q2p = take(B); w.qmin = take(B); w.dqa = take(B); w.dqb = take(B); w.g1 = take(B * A); w.g2 = take(B * A);
     w.d_head = take(B * 2 * A);
-    w.total = o;
-    return w;
+    w.total = take.o;
 }
 }  // namespace
 
-int64_t rl4rs_cql_workspace_floats(int32_t B, int32_t n, int32_t A) { return cql_ws(nullptr, B, n, A).total; }
+int64_t rl4rs_cql_workspace_floats(int32_t B, int32_t n, int32_t A) { return CqlWs(nullptr, B, n, A).total; }
 
 int rl4rs_cql_update(const rl4rs_cql_step* s, void* stream) {
     RL4RS_REQUIRE(s && s->policy && s->q1 && s->q2 && s->q1_targ && s->q2_targ && s->log_temp_dev && s->log_alpha_dev, "cql_update: null handle");
@@ -946,8 +1022,8 @@ int rl4rs_cql_update(const rl4rs_cql_step* s, void* stream) {
     RL4RS_REQUIRE(s->policy->c.act_dim == 0 && s->policy->c.out_dim == 2 * s->A, "cql_update: the policy must be a plain encoder with a [mu | logstd] head");
     hipStream_t st = (hipStream_t)stream;
     const int B = s->B, n = s->n, A = s->A, m = 1 + 3 * n, R = B * m;
-    const CqlWs w = cql_ws(s->workspace_dev, B, n, A);
-    const float lo = -20.f, hi = 2.f;
+    const CqlWs w(s->workspace_dev, B, n, A);
+    const float lo = SAC_MIN_LOGSTD, hi = SAC_MAX_LOGSTD;
     const float* eps_temp = s->normal_dev;
     const float* eps_alpha_t = eps_temp + (size_t)B * A;
     const float* eps_alpha_tp1 = eps_alpha_t + (size_t)B * n * A;
@@ -957,83 +1033,39 @@ int rl4rs_cql_update(const rl4rs_cql_step* s, void* stream) {
     const float* uni_alpha = s->uniform_dev;
     const float* uni_critic = uni_alpha + (size_t)B * n * A;
     const float log_uniform = (float)((double)A * log(0.5));
-    int rc;
-#define CU(expr) do { if ((rc = (expr)) != RL4RS_OK) return rc; } while (0)
     auto adam_c = [](int64_t step_after, double beta) { return (float)(1.0 / (1.0 - pow(beta, (double)step_after))); };
     // the [B, m, A] actions and [B, m] importance offsets of the conservative term (CQLImpl._compute_policy_is_values / _compute_random_is_values)
     auto conservative_rows = [&](const float* e_t, const float* e_tp1, const float* uni) {
         hipLaunchKernelGGL(k_cql_fill_rows, dim3((B * (1 + n) * A + 255) / 256), dim3(256), 0, st, w.acts, w.offs, s->act_dev, uni, B, m, n, A, log_uniform);
-        int r2;
-        if ((r2 = rl4rs_squashed_sample(B * n, n, A, w.head_obs, e_t, lo, hi, m, 1, w.acts, w.offs, stream))) return r2;
+        RL4RS_TRY(rl4rs_squashed_sample(B * n, n, A, w.head_obs, e_t, lo, hi, m, 1, w.acts, w.offs, stream));
         return rl4rs_squashed_sample(B * n, n, A, w.head_nxt, e_tp1, lo, hi, m, 1 + n, w.acts, w.offs, stream);
     };
-    // the policy does not change until the actor step: its heads on s' and s are computed once (s last: the handle keeps the
-    // activations of s for the actor's backward)
-    CU(rl4rs_amlp_forward(s->policy, B, 1, s->nxt_dev, nullptr, w.head_nxt, stream));
-    CU(rl4rs_amlp_forward(s->policy, B, 1, s->obs_dev, nullptr, w.head_obs, stream));
-    // --- temperature (SACImpl.update_temp)
-    if (s->temp_lr > 0.f) {
-        CU(rl4rs_squashed_sample(B, 1, A, w.head_obs, eps_temp, lo, hi, 1, 0, w.a_tmp, w.logp, stream));
-        hipLaunchKernelGGL(k_sac_temp_step, dim3(1), dim3(256), 0, st, w.logp, B, A, s->log_temp_dev, s->log_temp_dev + 1, s->log_temp_dev + 2, s->temp_lr,
-                           adam_c(s->temp_step + 1, 0.9), adam_c(s->temp_step + 1, 0.999), s->metrics_dev + 2);
-    }
+    RL4RS_TRY(sac_policy_heads(s, w, stream));
+    // --- temperature (SACImpl.update_temp), on the un-stepped policy
+    if (s->temp_lr > 0.f) RL4RS_TRY(sac_temp_step(s, w.head_obs, eps_temp, w.a_tmp, w.logp, stream));
     // --- alpha (CQLImpl.update_alpha): the critics' values of the 31 rows are never differentiated here
     const bool alpha_on = s->alpha_lr > 0.f;
     if (alpha_on) {
-        CU(conservative_rows(eps_alpha_t, eps_alpha_tp1, uni_alpha));
-        auto nograd_forward = [&](rl4rs_amlp* p, float* out) {
-            if (s->nograd_h16 && p->w1p && R >= s->h16_min_rows && ((uintptr_t)out & 15) == 0) return rl4rs_amlp_forward_h16(p, R, m, s->obs_dev, w.acts, out, stream);
-            return rl4rs_amlp_forward(p, R, m, s->obs_dev, w.acts, out, stream);
-        };
-        CU(nograd_forward(s->q1, w.q1m));
-        CU(nograd_forward(s->q2, w.q2m));
-        CU(rl4rs_cql_critic_loss(B, m, w.q1m, w.q2m, w.offs, nullptr, nullptr, nullptr, nullptr, w.rows, w.sums, stream));
+        RL4RS_TRY(conservative_rows(eps_alpha_t, eps_alpha_tp1, uni_alpha));
+        RL4RS_TRY(amlp_nograd_forward(s->q1, R, m, s->obs_dev, w.acts, w.q1m, s->nograd_h16, s->h16_min_rows, (uintptr_t)w.q1m, stream));
+        RL4RS_TRY(amlp_nograd_forward(s->q2, R, m, s->obs_dev, w.acts, w.q2m, s->nograd_h16, s->h16_min_rows, (uintptr_t)w.q2m, stream));
+        RL4RS_TRY(rl4rs_cql_critic_loss(B, m, w.q1m, w.q2m, w.offs, nullptr, nullptr, nullptr, nullptr, w.rows, w.sums, stream));
     }
     hipLaunchKernelGGL(k_cql_alpha_step, dim3(1), dim3(64), 0, st, w.sums, B, s->conservative_weight, s->alpha_threshold, s->log_alpha_dev,
                        s->log_alpha_dev + 1, s->log_alpha_dev + 2, s->alpha_lr, adam_c(s->alpha_step + 1, 0.9), adam_c(s->alpha_step + 1, 0.999),
                        alpha_on ? 1 : 0, s->metrics_dev + 3, w.aw);
     // --- critic (DDPGBaseImpl.update_critic with CQLImpl.compute_critic_loss / _compute_deterministic_target)
-    CU(rl4rs_squashed_sample(B, 1, A, w.head_nxt, nullptr, lo, hi, 1, 0, w.a_next, nullptr, stream));
-    {
-        rl4rs_amlp* targ[2] = {s->q1_targ, s->q2_targ};
-        float* qn[2] = {w.q1n, w.q2n};
-        CU(rl4rs_amlp_forward_multi(2, targ, B, s->nxt_dev, w.a_next, qn, stream));
-    }
-    CU(rl4rs_bcq_target(B, 1, w.q1n, w.q2n, 1.0f, s->rew_dev, s->ter_dev, s->gamma, w.yq, nullptr, stream));
-    CU(conservative_rows(eps_critic_t, eps_critic_tp1, uni_critic));
-    CU(rl4rs_amlp_forward(s->q1, R, m, s->obs_dev, w.acts, w.q1m, stream));
-    CU(rl4rs_amlp_forward(s->q2, R, m, s->obs_dev, w.acts, w.q2m, stream));
-    CU(rl4rs_cql_critic_loss(B, m, w.q1m, w.q2m, w.offs, w.yq, w.aw, w.dq1, w.dq2, w.rows, w.sums, stream));
-    CU(rl4rs_amlp_backward(s->q1, R, m, s->obs_dev, w.acts, w.dq1, nullptr, 1, stream));
-    CU(rl4rs_amlp_backward(s->q2, R, m, s->obs_dev, w.acts, w.dq2, nullptr, 1, stream));
-    rl4rs_amlp* twin[2] = {s->q1, s->q2};
-    {
-        const float lr[2] = {s->critic_lr, s->critic_lr};
-        const int32_t on[2] = {1, 1};
-        CU(rl4rs_amlp_adam_multi(2, twin, lr, on, nullptr, 0.9f, 0.999f, 1e-8f, 0.f, stream));
-    }
-    // --- actor (SACImpl.compute_actor_loss): (exp(log_temp) * logp - min_c Q_c(s, a)).mean()
-    CU(rl4rs_squashed_sample(B, 1, A, w.head_obs, eps_actor, lo, hi, 1, 0, w.a_pi, w.logp, stream));
-    {
-        float* qp[2] = {w.q1p, w.q2p};
-        CU(rl4rs_amlp_forward_multi(2, twin, B, s->obs_dev, w.a_pi, qp, stream));
-        CU(rl4rs_twin_min(B, w.q1p, w.q2p, w.qmin, w.dqa, w.dqb, stream));
-        const float* dq[2] = {w.dqa, w.dqb};
-        float* ga[2] = {w.g1, w.g2};
-        CU(rl4rs_amlp_backward_multi(2, twin, B, s->obs_dev, w.a_pi, dq, ga, 0, stream));
-    }
-    hipLaunchKernelGGL(k_add2, dim3((B * A + 255) / 256), dim3(256), 0, st, w.g1, w.g2, w.g1, B * A);
-    CU(rl4rs_sac_actor_grad(B, A, w.head_obs, eps_actor, w.a_pi, w.g1, s->log_temp_dev, lo, hi, w.d_head, stream));
-    // (the policy handle's activations are those of the forward on obs, the last one above)
-    CU(rl4rs_amlp_backward(s->policy, B, 1, s->obs_dev, nullptr, w.d_head, nullptr, 1, stream));
-    {
-        rl4rs_amlp* nets[3] = {s->policy, s->q1, s->q2};
-        rl4rs_amlp* targ[3] = {nullptr, s->q1_targ, s->q2_targ};
-        const float lr3[3] = {s->actor_lr, 0.f, 0.f};
-        const int32_t on3[3] = {1, 0, 0};
-        CU(rl4rs_amlp_adam_multi(3, nets, lr3, on3, targ, 0.9f, 0.999f, 1e-8f, s->tau, stream));
-    }
-#undef CU
+    RL4RS_TRY(sac_deterministic_target(s, w, stream));
+    RL4RS_TRY(conservative_rows(eps_critic_t, eps_critic_tp1, uni_critic));
+    RL4RS_TRY(rl4rs_amlp_forward(s->q1, R, m, s->obs_dev, w.acts, w.q1m, stream));
+    RL4RS_TRY(rl4rs_amlp_forward(s->q2, R, m, s->obs_dev, w.acts, w.q2m, stream));
+    RL4RS_TRY(rl4rs_cql_critic_loss(B, m, w.q1m, w.q2m, w.offs, w.yq, w.aw, w.dq1, w.dq2, w.rows, w.sums, stream));
+    RL4RS_TRY(rl4rs_amlp_backward(s->q1, R, m, s->obs_dev, w.acts, w.dq1, nullptr, 1, stream));
+    RL4RS_TRY(rl4rs_amlp_backward(s->q2, R, m, s->obs_dev, w.acts, w.dq2, nullptr, 1, stream));
+    RL4RS_TRY(amlp_adam_pair(s->q1, s->q2, s->critic_lr, stream));
+    // --- actor, its Adam and the soft critic-target update
+    RL4RS_TRY(sac_actor_phase(s, w, eps_actor, stream));
+    RL4RS_TRY(sac_actor_adam(s, stream));
     hipLaunchKernelGGL(k_cql_metrics, dim3(1), dim3(256), 0, st, w.sums, B, s->conservative_weight, s->alpha_threshold, s->log_alpha_dev, s->log_temp_dev,
                        w.logp, w.qmin, s->metrics_dev, s->metrics_dev + 1);
     RL4RS_LAUNCH_CHECK();
@@ -1043,3 +1075,4 @@ int rl4rs_cql_update(const rl4rs_cql_step* s, void* stream) {
 }  // extern "C"
 
 #include "combo.hpp"
+#undef RL4RS_TRY

@@ -33,6 +33,7 @@ import ctypes as C
 import numpy as np
 import torch
 
+from . import _lib
 from . import device as D
 from . import device as D_
 from . import dist as rdist
@@ -82,6 +83,25 @@ def init_qnet_params(obs_dim, action_size, mask_size=0, emb_size=32, hidden1=256
     return p
 
 
+def _epoch_minibatches(columns, batch_size, n_steps, seed):
+    """``n_steps`` minibatches over the rows of ``columns`` with an epoch-wise random permutation like d3rlpy's ``fit``.  The epoch's
+    permutation is applied to the columns ONCE: minibatches are then contiguous row ranges (views), not one gather per column
+    and update."""
+    n = columns[0].shape[0]
+    assert n >= batch_size, 'dataset smaller than one minibatch'
+
+    def batches():
+        rs = np.random.RandomState(seed)
+        ep, pos = None, n
+        for _ in range(n_steps):
+            if pos + batch_size > n:
+                perm = torch.from_numpy(rs.permutation(n)).to(columns[0].device)
+                ep = [t[perm] for t in columns]
+                pos = 0
+            yield [t[pos:pos + batch_size] for t in ep]
+            pos += batch_size
+    return batches()
+
 
 class _ModelIO(object):
     """``save_model`` / ``load_model`` / ``fit_mdp`` shared by every learner of this module: what ``script/batchrl_train.py`` calls
@@ -97,9 +117,11 @@ class _ModelIO(object):
                 out.append((name, v))
         return out
 
+    def check_status(self):
+        """Raise what a ``fit`` so far left pending (nothing here: the learners that keep a flag on the device override it)."""
+
     def save_model(self, fname):
-        if hasattr(self, 'check_status'):
-            self.check_status()
+        self.check_status()
         blob = {'__class__': np.array(type(self).__name__), 'total_step': np.array(self.total_step, dtype=np.int64)}
         for name, net in self._io_nets():
             blob['net.' + name] = net.flat_params().cpu().numpy()
@@ -204,21 +226,9 @@ class _Learner(_ModelIO):
     def fit(self, transitions, n_steps, shuffle_seed=None):
         """``n_steps`` minibatch updates over ``transitions`` (tuple of tensors from ``transitions_from_mdp``), epoch-wise
         random permutation like d3rlpy's ``fit``; returns the list of losses."""
-        obs, act, rew, nxt, ter = [t.to(self.nets[0].device) for t in transitions]
-        n = obs.shape[0]
-        assert n >= self.batch_size, 'dataset smaller than one minibatch'
-        rs = np.random.RandomState(self.seed if shuffle_seed is None else shuffle_seed)
-        losses, ep, pos = [], None, n
-        for _ in range(n_steps):
-            if pos + self.batch_size > n:
-                # the epoch's permutation is applied to the five arrays ONCE: minibatches are then contiguous row ranges (views),
-                # not five gathers per update
-                perm = torch.from_numpy(rs.permutation(n)).to(obs.device)
-                ep = [t[perm] for t in (obs, act, rew, nxt, ter)]
-                pos = 0
-            lo, hi = pos, pos + self.batch_size
-            pos = hi
-            losses.append(self.update(*[t[lo:hi] for t in ep]))
+        columns = [t.to(self.nets[0].device) for t in transitions]
+        seed = self.seed if shuffle_seed is None else shuffle_seed
+        losses = [self.update(*batch) for batch in _epoch_minibatches(columns, self.batch_size, n_steps, seed)]
         out = [float(x) for x in torch.stack(losses).cpu()]
         for net in self.nets:
             net.check_status()
@@ -386,7 +396,105 @@ def _allreduce_group(nets):
         o += f.numel()
 
 
-class BCQ(_ModelIO):
+class _ContinuousLearner(_ModelIO):
+    """What the four continuous-action learners share: the size bookkeeping (``A`` is the action width ``fit``
+    checks), the ``DeviceAMLP`` factory, the seeded generator and ``_randn``, the workspace cache of the one-call updates, the
+    epoch-wise ``fit`` and the collection of its history.  A learner states its networks, its ``update`` and ``_LOSS_KEYS``."""
+
+    def __init__(self, config, obs_dim, action_size, batch_size, predict_rows, seed, device):
+        self.config = config
+        self.D = int(obs_dim)
+        self.A = int(action_size if action_size is not None else config['action_emb_size'])
+        self.batch_size = int(batch_size)
+        self.predict_rows = max(int(predict_rows), 1)
+        self.seed = int(seed)
+        self.total_step = 0
+        self.device = device
+        self.nets = []
+        self.one_call = True             # update() as one library call on a single rank (False: the per-phase calls; tests compare the two)
+        self._ws = {}                    # minibatch shape -> workspace of the learner's one-call update
+
+    def _net(self, act_dim, out_dim, seed_off, max_rows, grad_rows, head_act='none', heads=1):
+        params = init_amlp_params(self.D, act_dim, out_dim, seed=self.seed + seed_off, heads=heads)
+        net = D_.DeviceAMLP(self.D, act_dim, out_dim, params, head_act=head_act, max_rows=max_rows, max_grad_rows=grad_rows, device=self.device)
+        self.device = net.device
+        self.nets.append(net)
+        return net
+
+    def _seed_generator(self):
+        self._gen = torch.Generator(device=self.device)
+        self._gen.manual_seed(self.seed + 1000003 * rdist.rank())
+
+    def _randn(self, shape, given):
+        """N(0, 1) of ``shape`` from the learner's generator, or the caller's tensor (tests) on the device"""
+        if given is not None:
+            return given.to(device=self.device, dtype=torch.float32).contiguous()
+        return torch.randn(shape, generator=self._gen, device=self.device, dtype=torch.float32)
+
+    def _workspace(self, key, size_fn, *dims):
+        ws = self._ws.get(key)
+        if ws is None:
+            ws = self._ws[key] = torch.empty(int(size_fn(*dims)), dtype=torch.float32, device=self.device)
+        return ws
+
+    def _single_call(self):
+        return self.one_call and not rdist.collectives_active()
+
+    def _watch_losses(self, stacked):
+        """(hook of ``_history``: the learners with an fp16x2 no-grad path keep a non-finite flag)"""
+
+    def _history(self, hist, to_host):
+        """dict of per-step loss lists from the per-update dicts (``to_host=False``: of stacked device tensors, nothing waits for the GPU)"""
+        out = {}
+        for k in self._LOSS_KEYS:
+            vals = [h[k] for h in hist if k in h]
+            if not vals:
+                out[k] = []
+                continue
+            st = torch.stack(vals)
+            self._watch_losses(st)
+            out[k] = [float(x) for x in st.cpu()] if to_host else st
+        return out
+
+    def fit(self, transitions, n_steps, shuffle_seed=None, to_host=True):
+        """``n_steps`` updates over ``transitions`` (``transitions_from_mdp(..., discrete_action=False)``), epoch-wise random
+        permutation like d3rlpy's ``fit``; returns dict of per-step loss lists (``to_host=False``: of stacked device tensors,
+        nothing waits for the GPU)."""
+        columns = [t.to(self.device) for t in transitions]
+        batches = _epoch_minibatches(columns, self.batch_size, n_steps, self.seed if shuffle_seed is None else shuffle_seed)
+        act = columns[1]
+        assert act.dim() == 2 and act.shape[1] == self.A and act.dtype == torch.float32, 'continuous actions [N, %d] needed' % self.A
+        out = self._history([self.update(*batch) for batch in batches], to_host)
+        if to_host:
+            self.check_status()
+        return out
+
+    def close(self):
+        for net in self.nets:
+            net.close()
+
+
+class _NonFiniteFlag(object):
+    """For the learners with an fp16x2 no-grad path (BCQ, CQL): a non-finite loss poisons Adam for good (the fused fp16x2 forward
+    turns a row whose hidden activation leaves the fp16 range into NaN).  The flag stays on the device; ``check_status`` reads it."""
+
+    NONFINITE_MESSAGE = ("a training loss of this learner became non-finite; with nograd_precision='fp16x2' a hidden activation that "
+                         "leaves the fp16 range does that - rebuild the learner with nograd_precision='fp32'")
+    _nonfinite = None
+
+    def _watch_losses(self, stacked):
+        bad = ~torch.isfinite(stacked).all()
+        self._nonfinite = bad if self._nonfinite is None else (self._nonfinite | bad)
+
+    def check_status(self):
+        """Raise if any loss of a ``fit`` so far was NaN / inf (one host read; ``fit(to_host=True)`` and ``save_model`` call it)."""
+        flag = self._nonfinite
+        if flag is not None and bool(flag.item()):
+            self._nonfinite = None
+            raise RuntimeError(self.NONFINITE_MESSAGE)
+
+
+class BCQ(_NonFiniteFlag, _ContinuousLearner):
     """d3rlpy.algos.BCQ(batch_size=256) as 'BCQ-conti' instantiates it (script/batchrl_trainer.py:61-73): default
     ``VectorEncoderWithAction([256, 256])`` everywhere, Adam 1e-3 for actor / critic / imitator, gamma 0.99, tau 0.005, two
     critics, lam 0.75, 100 sampled actions, action_flexibility 0.05, latent_size 32, beta 0.5, update_actor_interval 1,
@@ -403,60 +511,43 @@ class BCQ(_ModelIO):
                  imitator_learning_rate=1e-3, gamma=0.99, tau=0.005, update_actor_interval=1, lam=0.75, n_action_samples=100,
                  action_flexibility=0.05, rl_start_step=0, latent_size=32, beta=0.5, predict_rows=512, seed=0, device=None,
                  nograd_precision='fp16x2'):
-        self.config = config
-        self.D = int(obs_dim)
-        self.E = int(action_size if action_size is not None else config['action_emb_size'])
+        super(BCQ, self).__init__(config, obs_dim, action_size, batch_size, predict_rows, seed, device)
+        self.E = self.A                  # (d3rlpy's BCQ code calls the action width E)
         self.L = int(latent_size)
-        self.batch_size = int(batch_size)
         self.n = int(n_action_samples)
         self.actor_lr, self.critic_lr, self.imitator_lr = float(actor_learning_rate), float(critic_learning_rate), float(imitator_learning_rate)
         self.gamma, self.tau, self.lam = float(gamma), float(tau), float(lam)
         self.update_actor_interval, self.rl_start_step = int(update_actor_interval), int(rl_start_step)
         self.scale, self.beta = float(action_flexibility), float(beta)
-        self.predict_rows = max(int(predict_rows), 1)
         # arithmetic of the forwards that never see a backward (the batch x n_action_samples rows of compute_target and of
         # _predict_best_action): 'fp16x2' = the scorer's split form, one fused launch per network (DeviceAMLP.forward), or 'fp32'
         assert nograd_precision in ('fp16x2', 'fp32')
         self.nograd = nograd_precision
-        self.seed = int(seed)
-        self.total_step = 0
-        B, n, D, E, L = self.batch_size, self.n, self.D, self.E, self.L
+        B, n, E, L = self.batch_size, self.n, self.E, self.L
         big = max(B, self.predict_rows) * n
-
-        def net(act_dim, out_dim, seed_off, max_rows, grad_rows, head_act='none', heads=1):
-            return D_.DeviceAMLP(D, act_dim, out_dim, init_amlp_params(D, act_dim, out_dim, seed=seed + seed_off, heads=heads),
-                                 head_act=head_act, max_rows=max_rows, max_grad_rows=grad_rows, device=device)
-
-        self.imit_enc = net(E, 2 * L, 0, B, B, heads=2)                 # ConditionalVAE._encoder_encoder + _mu | _logstd
-        self.imit_dec = net(L, E, 1, big, B, head_act='tanh')           # ConditionalVAE._decoder_encoder + _fc, tanh
-        self.policy = net(E, E, 2, big, B, head_act='tanh')             # DeterministicResidualPolicy
-        self.policy_targ = net(E, E, 2, B * n, 0, head_act='tanh')
-        self.q1 = net(E, 1, 3, big, B)                                  # ContinuousMeanQFunction x 2
-        self.q2 = net(E, 1, 4, big, B)
-        self.q1_targ = net(E, 1, 3, B * n, 0)
-        self.q2_targ = net(E, 1, 4, B * n, 0)
+        self.imit_enc = self._net(E, 2 * L, 0, B, B, heads=2)                 # ConditionalVAE._encoder_encoder + _mu | _logstd
+        self.imit_dec = self._net(L, E, 1, big, B, head_act='tanh')           # ConditionalVAE._decoder_encoder + _fc, tanh
+        self.policy = self._net(E, E, 2, big, B, head_act='tanh')             # DeterministicResidualPolicy
+        self.policy_targ = self._net(E, E, 2, B * n, 0, head_act='tanh')
+        self.q1 = self._net(E, 1, 3, big, B)                                  # ContinuousMeanQFunction x 2
+        self.q2 = self._net(E, 1, 4, big, B)
+        self.q1_targ = self._net(E, 1, 3, B * n, 0)
+        self.q2_targ = self._net(E, 1, 4, B * n, 0)
         self.policy_targ.copy_from(self.policy)
         self.q1_targ.copy_from(self.q1)
         self.q2_targ.copy_from(self.q2)
-        self.nets = [self.imit_enc, self.imit_dec, self.policy, self.policy_targ, self.q1, self.q2, self.q1_targ, self.q2_targ]
-        self.device = self.q1.device
-        self._gen = torch.Generator(device=self.device)
-        self._gen.manual_seed(self.seed + 1000003 * rdist.rank())
+        self._seed_generator()
         self._minus_inv_b = None
         self._imit_w = torch.tensor([1.0 / self.E, self.beta / self.L], dtype=torch.float32, device=self.device)
-        self.one_call = True             # update() as one library call on a single rank (False: the per-phase calls; tests compare the two)
-        self._ws = {}                    # minibatch size -> workspace of rl4rs_bcq_update
 
-    def _randn(self, rows, noise, key):
-        if noise is not None and key in noise:
-            return noise[key].to(device=self.device, dtype=torch.float32).contiguous()
-        return torch.randn((rows, self.L), generator=self._gen, device=self.device, dtype=torch.float32)
+    def _latent(self, rows, noise, key):
+        return self._randn((rows, self.L), None if noise is None else noise.get(key))
 
     def _clipped_latent(self, rows, noise, key):
         """clamp(randn, -0.5, 0.5) (BCQImpl: the decoder's latent is clipped when actions are sampled); a caller-supplied noise
         tensor is never modified"""
         own = noise is None or key not in noise
-        z = self._randn(rows, noise, key)
+        z = self._latent(rows, noise, key)
         return z.clamp_(-0.5, 0.5) if own else z.clamp(-0.5, 0.5)
 
     def _sample_actions(self, obs, z, policy, rep, nograd=False):
@@ -468,17 +559,14 @@ class BCQ(_ModelIO):
     def _update_one_call(self, obs, act, rew, nxt, ter, noise):
         """The whole update as ONE library call (rl4rs_bcq_update: the same launches with the same arguments as ``update`` below
         issues one by one - after the fused kernels the update was bound by its ~55 Python -> C calls, not by the GPU)."""
-        from . import _lib
         B, n, E, L = obs.shape[0], self.n, self.E, self.L
         lib = _lib.load()
-        ws = self._ws.get(B)
-        if ws is None:
-            ws = self._ws[B] = torch.empty(int(lib.rl4rs_bcq_workspace_floats(B, n, E, L)), dtype=torch.float32, device=self.device)
+        ws = self._workspace(B, lib.rl4rs_bcq_workspace_floats, B, n, E, L)
         total = (B + B * n + B) * L
         if noise is None:
             nz = torch.randn(total, generator=self._gen, device=self.device, dtype=torch.float32)      # eps | z_target | z_actor: one draw
         else:
-            parts = [self._randn(B, noise, 'eps'), self._randn(B * n, noise, 'z_target'), self._randn(B, noise, 'z_actor')]
+            parts = [self._latent(B, noise, 'eps'), self._latent(B * n, noise, 'z_target'), self._latent(B, noise, 'z_actor')]
             nz = torch.cat([p.reshape(-1) for p in parts])                                           # (a copy: the caller's noise is never modified)
         metrics = torch.zeros(3, dtype=torch.float32, device=self.device)
         do_rl = self.total_step >= self.rl_start_step
@@ -498,12 +586,12 @@ class BCQ(_ModelIO):
         return out
 
     def update(self, obs, act, rew, nxt, ter, noise=None):
-        if self.one_call and not rdist.collectives_active():
+        if self._single_call():
             return self._update_one_call(obs, act, rew, nxt, ter, noise)
         B, n = obs.shape[0], self.n
         metrics = {}
         # --- imitator (BCQImpl.update_imitator: ConditionalVAE.compute_error) ---
-        eps = self._randn(B, noise, 'eps')
+        eps = self._latent(B, noise, 'eps')
         enc_out = self.imit_enc.forward(obs, act)
         z = D_.cvae_sample(enc_out, eps)
         y = self.imit_dec.forward(obs, z)
@@ -545,51 +633,6 @@ class BCQ(_ModelIO):
         self.total_step += 1
         return metrics
 
-    def fit(self, transitions, n_steps, shuffle_seed=None, to_host=True):
-        """``n_steps`` updates over ``transitions`` (``transitions_from_mdp(..., discrete_action=False)``), epoch-wise random
-        permutation like d3rlpy's ``fit``; returns dict of per-step loss lists (``to_host=False``: of stacked device tensors,
-        nothing waits for the GPU)."""
-        obs, act, rew, nxt, ter = [t.to(self.device) for t in transitions]
-        n = obs.shape[0]
-        assert n >= self.batch_size, 'dataset smaller than one minibatch'
-        E = getattr(self, 'E', None) or self.A
-        assert act.dim() == 2 and act.shape[1] == E and act.dtype == torch.float32, 'continuous actions [N, %d] needed' % E
-        rs = np.random.RandomState(self.seed if shuffle_seed is None else shuffle_seed)
-        hist, ep, pos = [], None, n
-        for _ in range(n_steps):
-            if pos + self.batch_size > n:
-                perm = torch.from_numpy(rs.permutation(n)).to(obs.device)          # applied once per epoch: minibatches are views
-                ep = [t[perm] for t in (obs, act, rew, nxt, ter)]
-                pos = 0
-            lo, hi = pos, pos + self.batch_size
-            pos = hi
-            hist.append(self.update(*[t[lo:hi] for t in ep]))
-        out = {}
-        for k in self._LOSS_KEYS:
-            vals = [h[k] for h in hist if k in h]
-            if not vals:
-                out[k] = []
-                continue
-            st = torch.stack(vals)
-            # a non-finite loss poisons Adam for good (the fused fp16x2 no-grad forward turns a row whose hidden activation
-            # leaves the fp16 range into NaN): the flag stays on the device, check_status() / to_host reads it
-            bad = ~torch.isfinite(st).all()
-            self._nonfinite = bad if getattr(self, '_nonfinite', None) is None else (self._nonfinite | bad)
-            out[k] = [float(x) for x in st.cpu()] if to_host else st
-        if to_host:
-            self.check_status()
-        return out
-
-    NONFINITE_MESSAGE = ("a training loss of this learner became non-finite; with nograd_precision='fp16x2' a hidden activation that "
-                         "leaves the fp16 range does that - rebuild the learner with nograd_precision='fp32'")
-
-    def check_status(self):
-        """Raise if any loss of a ``fit`` so far was NaN / inf (one host read; ``fit(to_host=True)`` and ``save_model`` call it)."""
-        flag = getattr(self, '_nonfinite', None)
-        if flag is not None and bool(flag.item()):
-            self._nonfinite = None
-            raise RuntimeError(self.NONFINITE_MESSAGE)
-
     _LOSS_KEYS = ('imitator_loss', 'critic_loss', 'actor_loss')
 
     def predict(self, obs, noise=None):
@@ -621,10 +664,6 @@ class BCQ(_ModelIO):
             x, a = obs[lo:lo + rows].contiguous(), actions[lo:lo + rows].contiguous()
             out[lo:lo + x.shape[0]] = 0.5 * (self.q1.forward(x, a, nograd=self.nograd)[:, 0] + self.q2.forward(x, a, nograd=self.nograd)[:, 0])
         return out
-
-    def close(self):
-        for net in self.nets:
-            net.close()
 
 
 class StandardRewardScaler(object):
@@ -668,7 +707,133 @@ class _ScalarParam(object):
         self.p.addcdiv_(self.m, denom, value=-lr / (1.0 - beta1 ** self.t))
 
 
-class CQL(_ModelIO):
+class _SAC(_ContinuousLearner):
+    """The SAC half of CQL, MOPO and COMBO: the squashed-Gaussian ``policy``, the twin critics and their targets,
+    ``log_temp``, the reward scaler, and the steps every one of them composes its ``update`` from.  A learner states the rows its
+    critics see (``_critic_rows``) and the order of the steps; each step issues the same library calls wherever it is used."""
+
+    def __init__(self, config, obs_dim, action_size, batch_size, actor_lr, critic_lr, temp_lr, gamma, tau, initial_temperature, reward_scaler,
+                 predict_rows, seed, device):
+        super(_SAC, self).__init__(config, obs_dim, action_size, batch_size, predict_rows, seed, device)
+        self.actor_lr, self.critic_lr, self.temp_lr = float(actor_lr), float(critic_lr), float(temp_lr)
+        self.gamma, self.tau = float(gamma), float(tau)
+        self.reward_scaler = reward_scaler
+        B, A = self.batch_size, self.A
+        rows, grad_rows = self._critic_rows()
+        self.policy = self._net(0, 2 * A, 0, max(B, self.predict_rows), B, heads=2)        # SquashedNormalPolicy: encoder + _mu | _logstd
+        self.q1 = self._net(A, 1, 1, rows, grad_rows)
+        self.q2 = self._net(A, 1, 2, rows, grad_rows)
+        self.q1_targ = self._net(A, 1, 1, B, 0)
+        self.q2_targ = self._net(A, 1, 2, B, 0)
+        self.q1_targ.copy_from(self.q1)
+        self.q2_targ.copy_from(self.q2)
+        self.log_temp = _ScalarParam(np.log(initial_temperature), self.device)
+        self._seed_generator()
+
+    def _critic_rows(self):
+        """(the most rows a critic sees in one forward, in one backward)"""
+        return self.batch_size, self.batch_size
+
+    def _scaled(self, rew):
+        if self.reward_scaler is None:
+            return rew
+        if isinstance(self.reward_scaler, str):
+            raise ValueError("reward_scaler=%r is fitted by fit_mdp(dataset); pass StandardRewardScaler(rewards) to use update / fit "
+                             "directly" % self.reward_scaler)
+        return self.reward_scaler.transform(rew)
+
+    def _normal_part(self, rows, given):
+        """[rows, A] of N(0, 1) for a one-call update: the caller's tensor (tests), else drawn"""
+        assert given is None or given.numel() == rows * self.A, 'noise of %d values where %d x %d are needed' % (given.numel(), rows, self.A)
+        return self._randn((rows, self.A), given)
+
+    def _uniform_part(self, shape, given):
+        if given is None:
+            return torch.empty(shape, dtype=torch.float32, device=self.device).uniform_(-1.0, 1.0, generator=self._gen)
+        assert given.numel() == int(np.prod(shape)), 'uniform noise of %d values where %s are needed' % (given.numel(), shape)
+        return given.to(device=self.device, dtype=torch.float32).reshape(shape).contiguous()
+
+    def _temp_step(self, head, eps):
+        """SACImpl.update_temp: -(exp(log_temp) * (logp - A)).mean() and its Adam step on log_temp; returns the loss"""
+        _, logp = D_.squashed_sample(head, eps)
+        targ = (logp - self.A).mean()
+        temp = self.log_temp.p.exp()
+        loss = -(temp * targ)[0]
+        self.log_temp.adam_step(-(temp * targ), self.temp_lr)
+        return loss
+
+    def _deterministic_target(self, head_nxt, rew, nxt, ter, one_launch):
+        """y = r + gamma (1 - ter) min_c Qtarg_c(s', tanh(mu(s'))).  ``one_launch``: the twin targets through ``amlp_forward_multi``
+        (COMBO) or one forward each (CQL) - what each learner's per-phase path has always issued"""
+        a_next, _ = D_.squashed_sample(head_nxt, None)
+        if one_launch:
+            q1n, q2n = D_.amlp_forward_multi([self.q1_targ, self.q2_targ], nxt, a_next)
+        else:
+            q1n, q2n = self.q1_targ.forward(nxt, a_next), self.q2_targ.forward(nxt, a_next)
+        return D_.bcq_target(q1n, q2n, 1, 1.0, rew.reshape(-1), ter.reshape(-1), self.gamma)[0]
+
+    def _sampled_rows(self, head_obs, head_nxt, given, acts, offs, first):
+        """Columns ``first`` .. ``first + 3n`` of ``acts`` [R, k, A] and the first 2n of them of ``offs`` [R, k]: n samples of pi(. | s)
+        and n of pi(. | s') with their log-probabilities, n uniform on [-1, 1]^A (CQLImpl._compute_policy_is_values /
+        _compute_random_is_values).  ``given`` = (eps_t, eps_tp1, uniform), each a tensor or None (drawn).  -> the two as flat rows"""
+        R, k, A = acts.shape
+        n = self.n
+        e_t, e_tp1, uni = given if given is not None else (None, None, None)
+        flat_a, flat_o = acts.view(R * k, A), offs.view(R * k)
+        D_.squashed_sample(head_obs, self._randn((R * n, A), e_t), rep=n, act_out=flat_a, logp_out=flat_o, out_rep=k, out_off=first)
+        D_.squashed_sample(head_nxt, self._randn((R * n, A), e_tp1), rep=n, act_out=flat_a, logp_out=flat_o, out_rep=k, out_off=first + n)
+        if uni is not None:
+            acts[:, first + 2 * n:] = uni.to(device=self.device, dtype=torch.float32)
+        else:
+            acts[:, first + 2 * n:].uniform_(-1.0, 1.0, generator=self._gen)
+        return flat_a, flat_o
+
+    def _actor_step(self, obs, head_obs, eps):
+        """SACImpl.compute_actor_loss, (exp(log_temp) * logp - min_c Q_c(s, a)).mean(): its gradient into the policy handle (all-reduced);
+        returns the loss.  The policy's Adam is the learner's (CQL fuses it with the soft target update)."""
+        B, twin = obs.shape[0], [self.q1, self.q2]
+        a_pi, logp = D_.squashed_sample(head_obs, eps)
+        q1p, q2p = D_.amlp_forward_multi(twin, obs, a_pi)
+        qmin, dq1, dq2 = D_.twin_min(q1p, q2p, want_grad=True)
+        g1, g2 = D_.amlp_backward_multi(twin, obs, a_pi, [dq1.view(B, 1), dq2.view(B, 1)], want_dact=True, want_param_grad=False)
+        d_head = D_.sac_actor_grad(head_obs, eps, a_pi, g1.add_(g2), self.log_temp.p)
+        self.policy.backward(obs, None, d_head)
+        _allreduce_group([self.policy])
+        return (self.log_temp.p.exp() * logp - qmin).mean()
+
+    def sample_action(self, obs, eps=None):
+        """a ~ pi(. | obs) for any number of rows"""
+        out = torch.empty((obs.shape[0], self.A), dtype=torch.float32, device=self.device)
+        rows = self.policy.max_rows
+        for lo in range(0, obs.shape[0], rows):
+            x = obs[lo:lo + rows].contiguous()
+            e = self._randn((x.shape[0], self.A), None if eps is None else eps[lo:lo + rows])
+            D_.squashed_sample(self.policy.forward(x), e, act_out=out[lo:lo + x.shape[0]])
+        return out
+
+    def predict(self, obs):
+        """SquashedNormalPolicy.best_action: tanh(mu(s)) - the embedding the env's K-NN resolves."""
+        obs = D_._dev_tensor(obs, torch.float32, self.device)
+        out = torch.empty((obs.shape[0], self.A), dtype=torch.float32, device=self.device)
+        rows = self.policy.max_rows
+        for lo in range(0, obs.shape[0], rows):
+            x = obs[lo:lo + rows].contiguous()
+            D_.squashed_sample(self.policy.forward(x), None, act_out=out[lo:lo + x.shape[0]])
+        return out
+
+    def predict_value(self, obs, actions):
+        """AlgoBase.predict_value: the mean of the critics' values of (obs, action)."""
+        obs = D_._dev_tensor(obs, torch.float32, self.device)
+        actions = D_._dev_tensor(actions, torch.float32, self.device)
+        out = torch.empty(obs.shape[0], dtype=torch.float32, device=self.device)
+        rows = self.q1.max_rows
+        for lo in range(0, obs.shape[0], rows):
+            x, a = obs[lo:lo + rows].contiguous(), actions[lo:lo + rows].contiguous()
+            out[lo:lo + x.shape[0]] = 0.5 * (self.q1.forward(x, a)[:, 0] + self.q2.forward(x, a)[:, 0])
+        return out
+
+
+class CQL(_NonFiniteFlag, _SAC):
     """d3rlpy.algos.CQL (continuous) as 'CQL-conti' instantiates it (script/batchrl_trainer.py:91-107): default encoders,
     actor lr 1e-4, critic lr 3e-4, temperature / alpha lr 1e-4, tau 0.005, two critics, initial temperature 1, initial alpha 1,
     alpha threshold 10, conservative weight 5, 10 action samples, deterministic (non-soft) backup; the script sets gamma = 1 and
@@ -689,65 +854,28 @@ class CQL(_ModelIO):
                  device=None, nograd_precision='fp16x2'):
         assert nograd_precision in ('fp16x2', 'fp32')
         self.nograd = nograd_precision               # the alpha step's critic forwards (never differentiated): see BCQ
-        self.config = config
-        self.D = int(obs_dim)
-        self.A = int(action_size if action_size is not None else config['action_emb_size'])
-        self.batch_size, self.n = int(batch_size), int(n_action_samples)
+        self.n = int(n_action_samples)
         self.m = 1 + 3 * self.n
-        self.actor_lr, self.critic_lr = float(actor_learning_rate), float(critic_learning_rate)
-        self.temp_lr, self.alpha_lr = float(temp_learning_rate), float(alpha_learning_rate)
-        self.gamma, self.tau = float(gamma), float(tau)
+        super(CQL, self).__init__(config, obs_dim, action_size, batch_size, actor_learning_rate, critic_learning_rate, temp_learning_rate, gamma,
+                                  tau, initial_temperature, reward_scaler, predict_rows, seed, device)
+        self.alpha_lr = float(alpha_learning_rate)
         self.alpha_threshold, self.conservative_weight = float(alpha_threshold), float(conservative_weight)
-        self.reward_scaler = reward_scaler
-        self.predict_rows = max(int(predict_rows), 1)
-        self.seed = int(seed)
-        self.total_step = 0
-        B, D, A, m = self.batch_size, self.D, self.A, self.m
-        rows = max(B * m, self.predict_rows)
-
-        def net(act_dim, out_dim, seed_off, max_rows, grad_rows, heads=1):
-            return D_.DeviceAMLP(D, act_dim, out_dim, init_amlp_params(D, act_dim, out_dim, seed=seed + seed_off, heads=heads),
-                                 max_rows=max_rows, max_grad_rows=grad_rows, device=device)
-
-        self.policy = net(0, 2 * A, 0, max(B, self.predict_rows), B, heads=2)        # SquashedNormalPolicy: encoder + _mu | _logstd
-        self.q1 = net(A, 1, 1, rows, B * m)
-        self.q2 = net(A, 1, 2, rows, B * m)
-        self.q1_targ = net(A, 1, 1, B, 0)
-        self.q2_targ = net(A, 1, 2, B, 0)
-        self.q1_targ.copy_from(self.q1)
-        self.q2_targ.copy_from(self.q2)
-        self.nets = [self.policy, self.q1, self.q2, self.q1_targ, self.q2_targ]
-        self.device = self.q1.device
-        self.log_temp = _ScalarParam(np.log(initial_temperature), self.device)
+        B, A, m = self.batch_size, self.A, self.m
         self.log_alpha = _ScalarParam(np.log(initial_alpha), self.device)
-        self._gen = torch.Generator(device=self.device)
-        self._gen.manual_seed(self.seed + 1000003 * rdist.rank())
         self._acts = torch.zeros((B, m, A), dtype=torch.float32, device=self.device)
         self._offs = torch.zeros((B, m), dtype=torch.float32, device=self.device)
         self._offs[:, 1 + 2 * self.n:] = float(A * np.log(0.5))                       # log of the uniform density on [-1, 1]^A
-        self.one_call = True             # update() as one library call on a single rank (False: the per-phase calls; tests compare the two)
-        self._ws = {}
 
-    def _randn(self, shape, given):
-        if given is not None:
-            return given.to(device=self.device, dtype=torch.float32).contiguous()
-        return torch.randn(shape, generator=self._gen, device=self.device, dtype=torch.float32)
+    def _critic_rows(self):
+        return max(self.batch_size * self.m, self.predict_rows), self.batch_size * self.m
 
     def _conservative_rows(self, head_obs, head_nxt, act, given):
-        """[B, m, A] actions and [B, m] importance offsets of the conservative term: column 0 the dataset action, then n samples of
-        pi(. | s), n of pi(. | s'), n uniform on [-1, 1]^A (CQLImpl._compute_policy_is_values / _compute_random_is_values)."""
-        B, n, A = act.shape[0], self.n, self.A
+        """[B, m, A] actions and [B, m] importance offsets of the conservative term: column 0 the dataset action, then the 3n
+        columns of ``_sampled_rows``"""
+        B = act.shape[0]
         acts, offs = self._acts[:B], self._offs[:B]
         acts[:, 0] = act
-        e_t, e_tp1, uni = given if given is not None else (None, None, None)
-        flat_a, flat_o = acts.view(B * self.m, A), offs.view(B * self.m)
-        D_.squashed_sample(head_obs, self._randn((B * n, A), e_t), rep=n, act_out=flat_a, logp_out=flat_o, out_rep=self.m, out_off=1)
-        D_.squashed_sample(head_nxt, self._randn((B * n, A), e_tp1), rep=n, act_out=flat_a, logp_out=flat_o, out_rep=self.m, out_off=1 + n)
-        if uni is not None:
-            acts[:, 1 + 2 * n:] = uni.to(device=self.device, dtype=torch.float32)
-        else:
-            acts[:, 1 + 2 * n:].uniform_(-1.0, 1.0, generator=self._gen)
-        return flat_a, flat_o
+        return self._sampled_rows(head_obs, head_nxt, given, acts, offs, 1)
 
     def _conservative_value(self, sums, B):
         """conservative_weight * (mean_c mean_b logsumexp - mean_c mean_b Q(s, a))"""
@@ -756,29 +884,16 @@ class CQL(_ModelIO):
     def _update_one_call(self, obs, act, rew, nxt, ter, noise):
         """The whole update as ONE library call (rl4rs_cql_update: the launches of ``update`` below, the two learned scalars' Adam on
         the device)."""
-        from . import _lib
         B, n, A = obs.shape[0], self.n, self.A
         lib = _lib.load()
-        ws = self._ws.get(B)
-        if ws is None:
-            ws = self._ws[B] = torch.empty(int(lib.rl4rs_cql_workspace_floats(B, n, A)), dtype=torch.float32, device=self.device)
+        ws = self._workspace(B, lib.rl4rs_cql_workspace_floats, B, n, A)
         if noise:
             # any subset of the keys, like the per-phase path's noise.get(...): what is not given is drawn from the generator
-            def normal_part(x, rows):
-                assert x is None or x.numel() == rows * A, 'noise tensor of %d values where %d x %d are needed' % (x.numel(), rows, A)
-                return self._randn((rows, A), x).reshape(-1)
-
-            def uniform_part(x):
-                if x is None:
-                    return torch.empty(B * n * A, dtype=torch.float32, device=self.device).uniform_(-1.0, 1.0, generator=self._gen)
-                assert x.numel() == B * n * A, 'uniform noise of %d values where %d are needed' % (x.numel(), B * n * A)
-                return x.to(device=self.device, dtype=torch.float32).reshape(-1)
-
             a_t, a_tp1, a_u = noise.get('alpha') or (None, None, None)
             c_t, c_tp1, c_u = noise.get('critic') or (None, None, None)
-            normal = torch.cat([normal_part(noise.get('eps_temp'), B), normal_part(a_t, B * n), normal_part(a_tp1, B * n),
-                                normal_part(c_t, B * n), normal_part(c_tp1, B * n), normal_part(noise.get('eps_actor'), B)])
-            uniform = torch.cat([uniform_part(a_u), uniform_part(c_u)])
+            rows = ((noise.get('eps_temp'), B), (a_t, B * n), (a_tp1, B * n), (c_t, B * n), (c_tp1, B * n), (noise.get('eps_actor'), B))
+            normal = torch.cat([self._normal_part(r, x).reshape(-1) for x, r in rows])
+            uniform = torch.cat([self._uniform_part((B * n * A,), x) for x in (a_u, c_u)])
         else:
             normal = torch.randn((2 * B + 4 * B * n) * A, generator=self._gen, device=self.device, dtype=torch.float32)
             uniform = torch.empty(2 * B * n * A, dtype=torch.float32, device=self.device).uniform_(-1.0, 1.0, generator=self._gen)
@@ -803,25 +918,17 @@ class CQL(_ModelIO):
     def update(self, obs, act, rew, nxt, ter, noise=None):
         noise = noise or {}
         B, A, m = obs.shape[0], self.A, self.m
-        if self.reward_scaler is not None:
-            if isinstance(self.reward_scaler, str):
-                raise ValueError("reward_scaler=%r is fitted by fit_mdp(dataset); pass StandardRewardScaler(rewards) to use update / fit "
-                                 "directly" % self.reward_scaler)
-            rew = self.reward_scaler.transform(rew)
-        if self.one_call and not rdist.collectives_active():
+        rew = self._scaled(rew)
+        if self._single_call():
             return self._update_one_call(obs, act, rew, nxt, ter, noise)
         metrics = {}
         # the policy does not change until the actor step: its heads on s' and s are computed once (s last: the handle keeps the
         # activations of s for the actor's backward)
         head_nxt = self.policy.forward(nxt)
         head_obs = self.policy.forward(obs)
-        # --- temperature (SACImpl.update_temp): -(exp(log_temp) * (logp - A)).mean(), gradient wrt log_temp
+        # --- temperature (SACImpl.update_temp), before the critic and on the un-stepped policy
         if self.temp_lr > 0:
-            _, logp = D_.squashed_sample(head_obs, self._randn((B, A), noise.get('eps_temp')))
-            targ = (logp - A).mean()
-            temp = self.log_temp.p.exp()
-            metrics['temp_loss'] = -(temp * targ)[0]
-            self.log_temp.adam_step(-(temp * targ), self.temp_lr)
+            metrics['temp_loss'] = self._temp_step(head_obs, self._randn((B, A), noise.get('eps_temp')))
         # --- alpha (CQLImpl.update_alpha): -conservative loss, gradient wrt log_alpha
         if self.alpha_lr > 0:
             fa, fo = self._conservative_rows(head_obs, head_nxt, act, noise.get('alpha'))
@@ -831,8 +938,7 @@ class CQL(_ModelIO):
             metrics['alpha_loss'] = -(ea.clamp(0.0, 1e6) * gap)[0]
             self.log_alpha.adam_step(torch.where(ea <= 1e6, -(ea * gap), torch.zeros_like(ea)), self.alpha_lr)
         # --- critic (DDPGBaseImpl.update_critic with CQLImpl.compute_critic_loss / _compute_deterministic_target)
-        a_next, _ = D_.squashed_sample(head_nxt, None)
-        yq, _ = D_.bcq_target(self.q1_targ.forward(nxt, a_next), self.q2_targ.forward(nxt, a_next), 1, 1.0, rew, ter, self.gamma)
+        yq = self._deterministic_target(head_nxt, rew, nxt, ter, one_launch=False)
         fa, fo = self._conservative_rows(head_obs, head_nxt, act, noise.get('critic'))
         clipped_alpha = self.log_alpha.p.exp().clamp(0.0, 1e6)
         aw = (clipped_alpha * self.conservative_weight).contiguous()
@@ -844,50 +950,14 @@ class CQL(_ModelIO):
         _allreduce_group([self.q1, self.q2])
         D_.amlp_adam_multi([self.q1, self.q2], [self.critic_lr] * 2)
         metrics['critic_loss'] = (sums[0] + sums[1]) / B + (clipped_alpha * (self._conservative_value(sums, B) - self.alpha_threshold))[0]
-        # --- actor (SACImpl.compute_actor_loss): (exp(log_temp) * logp - min_c Q_c(s, a)).mean()
-        eps = self._randn((B, A), noise.get('eps_actor'))
-        a_pi, logp = D_.squashed_sample(head_obs, eps)
-        q1p, q2p = D_.amlp_forward_multi([self.q1, self.q2], obs, a_pi)
-        qmin, dq1, dq2 = D_.twin_min(q1p, q2p, want_grad=True)
-        g1, g2 = D_.amlp_backward_multi([self.q1, self.q2], obs, a_pi, [dq1.view(B, 1), dq2.view(B, 1)], want_dact=True, want_param_grad=False)
-        g_a = g1.add_(g2)
-        d_head = D_.sac_actor_grad(head_obs, eps, a_pi, g_a, self.log_temp.p)
-        self.policy.backward(obs, None, d_head)
-        _allreduce_group([self.policy])
+        # --- actor; its Adam and the soft critic-target update are one launch
+        metrics['actor_loss'] = self._actor_step(obs, head_obs, self._randn((B, A), noise.get('eps_actor')))
         D_.amlp_adam_multi([self.policy, self.q1, self.q2], [self.actor_lr, 0.0, 0.0], targets=[None, self.q1_targ, self.q2_targ], tau=self.tau,
                            step=[True, False, False])
-        metrics['actor_loss'] = (self.log_temp.p.exp() * logp - qmin).mean()
         self.total_step += 1
         return metrics
 
-    fit = BCQ.fit
-    check_status = BCQ.check_status
-    NONFINITE_MESSAGE = BCQ.NONFINITE_MESSAGE
     _LOSS_KEYS = ('critic_loss', 'actor_loss', 'temp_loss', 'alpha_loss')
-
-    def predict(self, obs):
-        """SquashedNormalPolicy.best_action: tanh(mu(s)) - the embedding the env's K-NN resolves."""
-        obs = D_._dev_tensor(obs, torch.float32, self.device)
-        out = torch.empty((obs.shape[0], self.A), dtype=torch.float32, device=self.device)
-        rows = self.policy.max_rows
-        for lo in range(0, obs.shape[0], rows):
-            x = obs[lo:lo + rows].contiguous()
-            D_.squashed_sample(self.policy.forward(x), None, act_out=out[lo:lo + x.shape[0]])
-        return out
-
-    def predict_value(self, obs, actions):
-        obs = D_._dev_tensor(obs, torch.float32, self.device)
-        actions = D_._dev_tensor(actions, torch.float32, self.device)
-        out = torch.empty(obs.shape[0], dtype=torch.float32, device=self.device)
-        rows = self.q1.max_rows
-        for lo in range(0, obs.shape[0], rows):
-            x, a = obs[lo:lo + rows].contiguous(), actions[lo:lo + rows].contiguous()
-            out[lo:lo + x.shape[0]] = 0.5 * (self.q1.forward(x, a)[:, 0] + self.q2.forward(x, a)[:, 0])
-        return out
-
-    def close(self):
-        for net in self.nets:
-            net.close()
 
 
 class GeneratedFIFO(object):
@@ -973,7 +1043,7 @@ def model_rollout(sample_action, dynamics, start_obs, horizon, lam, fifo, step0=
     return s
 
 
-class MOPO(_ModelIO):
+class MOPO(_SAC):
     """d3rlpy.algos.MOPO as 'MOPO' instantiates it (script/batchrl_trainer.py:108-129; the script passes batch_size=256, gamma=1.0,
     update_actor_interval=2000): SAC on default ``[256, 256]`` encoders - actor / critic / temperature lr 3e-4, tau 0.005, two
     critics, initial temperature 1 - trained on minibatches of ``real_ratio`` real and 1 - ``real_ratio`` model-generated rows.
@@ -990,55 +1060,19 @@ class MOPO(_ModelIO):
                  temp_learning_rate=3e-4, gamma=0.99, tau=0.005, initial_temperature=1.0, update_actor_interval=1, rollout_interval=1000,
                  rollout_horizon=5, rollout_batch_size=50000, lam=1.0, real_ratio=0.05, generated_maxlen=50000 * 5 * 5,
                  reward_scaler=None, predict_rows=4096, seed=0, device=None):
-        self.config = config
+        super(MOPO, self).__init__(config, obs_dim, action_size, batch_size, actor_learning_rate, critic_learning_rate, temp_learning_rate, gamma,
+                                   tau, initial_temperature, reward_scaler, predict_rows, seed, device)
         self.dynamics = dynamics
-        self.D = int(obs_dim)
-        self.A = int(action_size if action_size is not None else config['action_emb_size'])
-        self.batch_size = int(batch_size)
-        self.actor_lr, self.critic_lr, self.temp_lr = float(actor_learning_rate), float(critic_learning_rate), float(temp_learning_rate)
-        self.gamma, self.tau = float(gamma), float(tau)
         self.update_actor_interval = max(int(update_actor_interval), 1)
         self.rollout_interval, self.rollout_horizon = max(int(rollout_interval), 1), int(rollout_horizon)
         self.rollout_batch_size, self.lam, self.real_ratio = int(rollout_batch_size), float(lam), float(real_ratio)
-        self.reward_scaler = reward_scaler
-        self.predict_rows = max(int(predict_rows), 1)
-        self.seed = int(seed)
-        self.total_step = 0
-        B, D, A = self.batch_size, self.D, self.A
-
-        def net(act_dim, out_dim, seed_off, max_rows, grad_rows, heads=1):
-            return D_.DeviceAMLP(D, act_dim, out_dim, init_amlp_params(D, act_dim, out_dim, seed=seed + seed_off, heads=heads),
-                                 max_rows=max_rows, max_grad_rows=grad_rows, device=device)
-
-        self.policy = net(0, 2 * A, 0, max(B, self.predict_rows), B, heads=2)
-        critic_rows = self._critic_rows()
-        self.q1 = net(A, 1, 1, critic_rows, critic_rows)
-        self.q2 = net(A, 1, 2, critic_rows, critic_rows)
-        self.q1_targ = net(A, 1, 1, B, 0)
-        self.q2_targ = net(A, 1, 2, B, 0)
-        self.q1_targ.copy_from(self.q1)
-        self.q2_targ.copy_from(self.q2)
-        self.nets = [self.policy, self.q1, self.q2, self.q1_targ, self.q2_targ]
-        self.device = self.q1.device
-        self.log_temp = _ScalarParam(np.log(initial_temperature), self.device)
-        self._gen = torch.Generator(device=self.device)
-        self._gen.manual_seed(self.seed + 1000003 * rdist.rank())
         self.generated = GeneratedFIFO(generated_maxlen, self.device)
-
-    def _critic_rows(self):
-        """the most rows a critic sees in one forward / backward"""
-        return self.batch_size
 
     def _rollout_due(self):
         return self.total_step % self.rollout_interval == 0
 
     def _update_minibatch(self, batch, n_real):
         return self.update(*batch)
-
-    def _randn(self, shape, given):
-        if given is not None:
-            return given.to(device=self.device, dtype=torch.float32).contiguous()
-        return torch.randn(shape, generator=self._gen, device=self.device, dtype=torch.float32)
 
     def soft_target(self, rew, nxt, ter, eps_next=None):
         """y [B] of the critic step"""
@@ -1049,13 +1083,7 @@ class MOPO(_ModelIO):
 
     def update(self, obs, act, rew, nxt, ter, noise=None):
         noise = noise or {}
-        B, A = obs.shape[0], self.A
-        if self.reward_scaler is not None:
-            if isinstance(self.reward_scaler, str):
-                raise ValueError("reward_scaler=%r is fitted by fit_mdp(dataset); pass StandardRewardScaler(rewards) to use update / fit "
-                                 "directly" % self.reward_scaler)
-            rew = self.reward_scaler.transform(rew)
-        obs, act, rew, nxt, ter = _check_transitions(self.device, self.D, self.A, obs, act, rew, nxt, ter)
+        obs, act, rew, nxt, ter = _check_transitions(self.device, self.D, self.A, obs, act, self._scaled(rew), nxt, ter)
         metrics = {}
         # --- critic (SACImpl.compute_target / DDPGBaseImpl.update_critic)
         y = self.soft_target(rew, nxt, ter, noise.get('eps_next'))
@@ -1066,40 +1094,18 @@ class MOPO(_ModelIO):
         D_.amlp_adam_multi([self.q1, self.q2], [self.critic_lr] * 2)
         metrics['critic_loss'] = loss2[0] + loss2[1]
         if self.total_step % self.update_actor_interval == 0:
-            # --- actor (SACImpl.compute_actor_loss): (exp(log_temp) * logp - min_c Q_c(s, a)).mean()
-            head_obs = self.policy.forward(obs)
-            eps = self._randn((B, A), noise.get('eps_actor'))
-            a_pi, logp = D_.squashed_sample(head_obs, eps)
-            q1p, q2p = D_.amlp_forward_multi([self.q1, self.q2], obs, a_pi)
-            qmin, dq1, dq2 = D_.twin_min(q1p, q2p, want_grad=True)
-            g1, g2 = D_.amlp_backward_multi([self.q1, self.q2], obs, a_pi, [dq1.view(B, 1), dq2.view(B, 1)], want_dact=True,
-                                            want_param_grad=False)
-            d_head = D_.sac_actor_grad(head_obs, eps, a_pi, g1.add_(g2), self.log_temp.p)
-            self.policy.backward(obs, None, d_head)
-            _allreduce_group([self.policy])
-            metrics['actor_loss'] = (self.log_temp.p.exp() * logp - qmin).mean()
-            D_.amlp_adam_multi([self.policy], [self.actor_lr])
-            # --- temperature (SACImpl.update_temp, on the stepped policy): -(exp(log_temp) * (logp - A)).mean(), gradient wrt log_temp
-            if self.temp_lr > 0:
-                _, logp_t = D_.squashed_sample(self.policy.forward(obs), self._randn((B, A), noise.get('eps_temp')))
-                targ = (logp_t - A).mean()
-                temp = self.log_temp.p.exp()
-                metrics['temp_loss'] = -(temp * targ)[0]
-                self.log_temp.adam_step(-(temp * targ), self.temp_lr)
-            # --- soft target update
-            D_.amlp_adam_multi([self.q1, self.q2], [0.0, 0.0], targets=[self.q1_targ, self.q2_targ], tau=self.tau, step=[False, False])
+            self._actor_phase(obs, self.policy.forward(obs), noise, metrics)
         self.total_step += 1
         return metrics
 
-    def sample_action(self, obs, eps=None):
-        """a ~ pi(. | obs) for any number of rows"""
-        out = torch.empty((obs.shape[0], self.A), dtype=torch.float32, device=self.device)
-        rows = self.policy.max_rows
-        for lo in range(0, obs.shape[0], rows):
-            x = obs[lo:lo + rows].contiguous()
-            e = self._randn((x.shape[0], self.A), None if eps is None else eps[lo:lo + rows])
-            D_.squashed_sample(self.policy.forward(x), e, act_out=out[lo:lo + x.shape[0]])
-        return out
+    def _actor_phase(self, obs, head_obs, noise, metrics):
+        """the actor step and its Adam, the temperature step on the STEPPED policy (a fresh forward), the soft target update"""
+        B, A = obs.shape[0], self.A
+        metrics['actor_loss'] = self._actor_step(obs, head_obs, self._randn((B, A), noise.get('eps_actor')))
+        D_.amlp_adam_multi([self.policy], [self.actor_lr])
+        if self.temp_lr > 0:
+            metrics['temp_loss'] = self._temp_step(self.policy.forward(obs), self._randn((B, A), noise.get('eps_temp')))
+        D_.amlp_adam_multi([self.q1, self.q2], [0.0, 0.0], targets=[self.q1_targ, self.q2_targ], tau=self.tau, step=[False, False])
 
     def generate_new_data(self, real_obs, given=None):
         """One rollout of ``rollout_batch_size`` start observations drawn with replacement from ``real_obs`` into ``self.generated``.
@@ -1123,11 +1129,7 @@ class MOPO(_ModelIO):
                 self.generate_new_data(real[0])
             batch, n_real = mixed_minibatch(real, self.generated, self.batch_size, self.real_ratio, self._gen)
             hist.append(self._update_minibatch(batch, n_real))
-        out = {}
-        for k in self._LOSS_KEYS:
-            vals = [h[k] for h in hist if k in h]
-            out[k] = ([float(x) for x in torch.stack(vals).cpu()] if to_host else torch.stack(vals)) if vals else []
-        return out
+        return self._history(hist, to_host)
 
     _LOSS_KEYS = ('critic_loss', 'actor_loss', 'temp_loss')
 
@@ -1136,13 +1138,6 @@ class MOPO(_ModelIO):
         if self.reward_scaler == 'standard':
             self.reward_scaler = StandardRewardScaler(tr[2])
         return self.fit(tr, int(n_epochs) * max(tr[0].shape[0] // self.batch_size, 1), **kw)
-
-    predict = CQL.predict
-    predict_value = CQL.predict_value
-
-    def close(self):
-        for net in self.nets:
-            net.close()
 
 
 class COMBO(MOPO):
@@ -1200,12 +1195,11 @@ class COMBO(MOPO):
         self._log_uniform = float(self.A * np.log(0.5))          # log of the uniform density on [-1, 1]^A
         self._stash_n = (self.q1.n_params + 3) // 4 * 4
         self._stash = torch.empty(2 * self._stash_n, dtype=torch.float32, device=self.device)
-        self.one_call = True             # update() as one library call on a single rank (False: the per-phase calls; tests compare the two)
-        self._ws = {}                    # (B, n_real) -> workspace of rl4rs_combo_update
 
     def _critic_rows(self):
         # pass C: at most batch_size - 1 generated rows with 3n samples each
-        return max(self.batch_size, (self.batch_size - 1) * 3 * self.n)
+        rows = max(self.batch_size, (self.batch_size - 1) * 3 * self.n)
+        return rows, rows
 
     def _rollout_due(self):
         # (a learner restored in the middle of an interval has no generated rows yet: the generated half is never empty in fit)
@@ -1216,32 +1210,18 @@ class COMBO(MOPO):
 
     def _noise(self, noise, B, F):
         """(eps_t, eps_tp1, uniform) of the critic step: what ``noise['critic']`` gives, the rest drawn"""
-        n, A = self.n, self.A
         e_t, e_tp1, uni = noise.get('critic') or (None, None, None)
-        for x in (e_t, e_tp1, uni):
-            assert x is None or x.numel() == F * n * A, 'critic noise of %d values where %d x %d x %d are needed' % (x.numel(), F, n, A)
-        e_t, e_tp1 = self._randn((F * n, A), e_t), self._randn((F * n, A), e_tp1)
-        if uni is None:
-            uni = torch.empty((F, n, A), dtype=torch.float32, device=self.device).uniform_(-1.0, 1.0, generator=self._gen)
-        else:
-            uni = uni.to(device=self.device, dtype=torch.float32).reshape(F, n, A).contiguous()
-        return e_t, e_tp1, uni
+        return self._normal_part(F * self.n, e_t), self._normal_part(F * self.n, e_tp1), self._uniform_part((F, self.n, self.A), uni)
 
     def _update_one_call(self, obs, act, rew, nxt, ter, n_real, noise, do_actor):
-        from . import _lib
         B, n, A, F = obs.shape[0], self.n, self.A, obs.shape[0] - n_real
         lib = _lib.load()
-        ws = self._ws.get((B, n_real))
-        if ws is None:
-            ws = self._ws[(B, n_real)] = torch.empty(int(lib.rl4rs_combo_workspace_floats(B, n_real, n, A)), dtype=torch.float32, device=self.device)
+        ws = self._workspace((B, n_real), lib.rl4rs_combo_workspace_floats, B, n_real, n, A)
         if noise:
             e_t, e_tp1, uniform = self._noise(noise, B, F)
             parts = [e_t.reshape(-1), e_tp1.reshape(-1)]
             if do_actor:
-                for key in ('eps_actor', 'eps_temp'):
-                    x = noise.get(key)
-                    assert x is None or x.numel() == B * A, '%s of %d values where %d x %d are needed' % (key, x.numel(), B, A)
-                    parts.append(self._randn((B, A), x).reshape(-1))
+                parts += [self._normal_part(B, noise.get(key)).reshape(-1) for key in ('eps_actor', 'eps_temp')]
             normal = torch.cat(parts)
         else:
             normal = torch.randn((2 * F * n + (2 * B if do_actor else 0)) * A, generator=self._gen, device=self.device, dtype=torch.float32)
@@ -1270,14 +1250,9 @@ class COMBO(MOPO):
             raise ValueError('COMBO.update: n_real=%d of %d rows: the data term needs real rows and the logsumexp term generated ones' % (n_real, B))
         if max(B, F * k) > self.q1.max_rows:
             raise ValueError('COMBO.update: a minibatch of %d rows (%d generated) where the learner was built for batch_size=%d' % (B, F, self.batch_size))
-        if self.reward_scaler is not None:
-            if isinstance(self.reward_scaler, str):
-                raise ValueError("reward_scaler=%r is fitted by fit_mdp(dataset); pass StandardRewardScaler(rewards) to use update / fit "
-                                 "directly" % self.reward_scaler)
-            rew = self.reward_scaler.transform(rew)
-        obs, act, rew, nxt, ter = _check_transitions(self.device, self.D, self.A, obs, act, rew, nxt, ter)
+        obs, act, rew, nxt, ter = _check_transitions(self.device, self.D, self.A, obs, act, self._scaled(rew), nxt, ter)
         do_actor = self.total_step % self.update_actor_interval == 0
-        if self.one_call and not rdist.collectives_active():
+        if self._single_call():
             return self._update_one_call(obs, act, rew, nxt, ter, n_real, noise, do_actor)
         metrics = {}
         twin = [self.q1, self.q2]
@@ -1285,18 +1260,12 @@ class COMBO(MOPO):
         # activations of s for the actor's backward); the generated rows' heads are rows n_real .. of these
         head_nxt = self.policy.forward(nxt)
         head_obs = self.policy.forward(obs)
-        # --- target (deterministic backup)
-        a_next, _ = D_.squashed_sample(head_nxt, None)
-        q1n, q2n = D_.amlp_forward_multi([self.q1_targ, self.q2_targ], nxt, a_next)
-        yq, _ = D_.bcq_target(q1n, q2n, 1, 1.0, rew.reshape(-1), ter.reshape(-1), self.gamma)
+        yq = self._deterministic_target(head_nxt, rew, nxt, ter, one_launch=True)
         # --- the F * 3n rows of pass C: [pi(s_f) | pi(s'_f) | uniform] and their importance offsets
-        e_t, e_tp1, uni = self._noise(noise, B, F)
+        given = self._noise(noise, B, F)
         acts = torch.empty((F, k, A), dtype=torch.float32, device=self.device)
         offs = torch.empty((F, k), dtype=torch.float32, device=self.device)
-        flat_a, flat_o = acts.view(F * k, A), offs.view(F * k)
-        D_.squashed_sample(head_obs[n_real:], e_t, rep=n, act_out=flat_a, logp_out=flat_o, out_rep=k, out_off=0)
-        D_.squashed_sample(head_nxt[n_real:], e_tp1, rep=n, act_out=flat_a, logp_out=flat_o, out_rep=k, out_off=n)
-        acts[:, 2 * n:] = uni
+        flat_a, flat_o = self._sampled_rows(head_obs[n_real:], head_nxt[n_real:], given, acts, offs, 0)
         offs[:, 2 * n:] = self._log_uniform
         # --- critic: forward T, backward T, stash, forward C, backward C, add (a backward WRITES the handle's gradient)
         rows = torch.empty(4 * B + 2 * F, dtype=torch.float32, device=self.device)
@@ -1319,34 +1288,14 @@ class COMBO(MOPO):
         metrics['conservative_loss'] = cons.float()
         metrics['critic_loss'] = ((s64[0] + s64[1]) / B + cons).float()
         if do_actor:
-            # --- actor (SACImpl.compute_actor_loss): (exp(log_temp) * logp - min_c Q_c(s, a)).mean()
-            eps = self._randn((B, A), noise.get('eps_actor'))
-            a_pi, logp = D_.squashed_sample(head_obs, eps)
-            q1p, q2p = D_.amlp_forward_multi(twin, obs, a_pi)
-            qmin, dq1, dq2 = D_.twin_min(q1p, q2p, want_grad=True)
-            g1, g2 = D_.amlp_backward_multi(twin, obs, a_pi, [dq1.view(B, 1), dq2.view(B, 1)], want_dact=True, want_param_grad=False)
-            d_head = D_.sac_actor_grad(head_obs, eps, a_pi, g1.add_(g2), self.log_temp.p)
-            self.policy.backward(obs, None, d_head)
-            _allreduce_group([self.policy])
-            metrics['actor_loss'] = (self.log_temp.p.exp() * logp - qmin).mean()
-            D_.amlp_adam_multi([self.policy], [self.actor_lr])
-            # --- temperature (SACImpl.update_temp, on the stepped policy)
-            if self.temp_lr > 0:
-                _, logp_t = D_.squashed_sample(self.policy.forward(obs), self._randn((B, A), noise.get('eps_temp')))
-                targ = (logp_t - A).mean()
-                temp = self.log_temp.p.exp()
-                metrics['temp_loss'] = -(temp * targ)[0]
-                self.log_temp.adam_step(-(temp * targ), self.temp_lr)
-            # --- soft target update
-            D_.amlp_adam_multi(twin, [0.0, 0.0], targets=[self.q1_targ, self.q2_targ], tau=self.tau, step=[False, False])
+            self._actor_phase(obs, head_obs, noise, metrics)
         self.total_step += 1
         return metrics
 
     def critic_step_outputs(self, B, n_real):
         """(y [B], sums6) of the LAST update's critic step (tests; the one-call path leaves them in its workspace)"""
-        if not (self.one_call and not rdist.collectives_active()):
+        if not self._single_call():
             return self.last_y, self.last_sums
-        from . import _lib
         lib, ws = _lib.load(), self._ws[(B, n_real)]
         y0, s0 = [int(lib.rl4rs_combo_workspace_offset(B, n_real, self.n, self.A, what)) for what in (0, 1)]
         return ws[y0:y0 + B], ws[s0:s0 + 6]
