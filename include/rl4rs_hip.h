@@ -1692,6 +1692,62 @@ int rl4rs_dyn_predict(rl4rs_dyn* net, int32_t N, const float* x_dev, const float
 int rl4rs_sac_target(const float* q1_dev, const float* q2_dev, const float* logp_dev, const float* log_temp_dev, const float* rew_dev,
                      const float* ter_dev, float gamma, int32_t N, float* y_dev, void* stream);
 
+/* The MDP checker's model (script/mdpchecker/mdp_checker.py:93-102, keras_transformer.get_model with encoder_num = decoder_num =
+ * head_num = 1, use_same_embed = False), its training pass and its beam search (rl4rs/mdpchecker/decoder.py:50-82).  The model is restated
+ * from the published form of keras_transformer in DESIGN 33; parity with it is unpinned, the beam search is pinned to the
+ * reference's own function.  Tokens: 0 = <PAD>, 1 = <START>, 2 = <END>.
+ *
+ * Embedding + trigonometric position (added, no sqrt(d) scale; column 2 i = sin(pos / 10000^(2 i / d)), 2 i + 1 = cos); every block
+ * is LayerNorm(x + f(x)) with the biased variance and eps 1e-14 under the root; attention has one head of width d, scores / sqrt(d),
+ * e = exp(s - max over all keys), e = 0 at a PAD key (and behind the query in the decoder's self-attention), e / (sum e + 1e-7);
+ * feed-forward d -> hidden_dim relu -> d; output softmax(h E_dec^T + b), tied to the decoder table.
+ * Flat float32 parameters, matrices stored [in, out]:
+ *     [ E_enc [V, d] | E_dec [V, d] | enc attention | enc ffn | dec self-attention | dec cross-attention | dec ffn | out bias [V] ]
+ *     attention = Wq bq Wk bk Wv bv Wo bo gamma beta;   ffn = W1 [d, hidden] b1 W2 [hidden, d] b2 gamma beta
+ * max_rows bounds the rows of every activation matrix of a call: N * max(L, src_len) of a forward, N * max(beam, src_len) of a
+ * beam search (the caller splits its users into chunks).  Refused by rl4rs_seq2seq_create (rl4rs_seq2seq_param_count = -1), before a
+ * device is looked for: token_num < 4, an odd embed_dim, src_len or tgt_len outside [1, 64], a max_rows whose widest fp32
+ * activation row set [max_rows, max(token_num, 2 embed_dim, hidden_dim)] reaches 2^31 bytes, max_rows * 64 >= 2^31. */
+typedef struct rl4rs_seq2seq rl4rs_seq2seq;
+typedef struct rl4rs_seq2seq_cfg {
+    int32_t token_num /* V */, embed_dim /* d */, hidden_dim, src_len, tgt_len /* most decoder positions */, max_rows;
+} rl4rs_seq2seq_cfg;
+int64_t rl4rs_seq2seq_param_count(const rl4rs_seq2seq_cfg* cfg);
+int rl4rs_seq2seq_create(const rl4rs_seq2seq_cfg* cfg, const float* params_host, void* stream, rl4rs_seq2seq** out);
+int rl4rs_seq2seq_destroy(rl4rs_seq2seq* net);
+int rl4rs_seq2seq_params(rl4rs_seq2seq* net, float** params_dev, float** grad_dev, int64_t* count);
+int rl4rs_seq2seq_adam_state(rl4rs_seq2seq* net, float** m_dev, float** v_dev, int64_t* step);
+int rl4rs_seq2seq_set_adam_step(rl4rs_seq2seq* net, int64_t step);
+/* Teacher-forced training pass: dec_in_dev / dec_out_dev int32 [N, L]; loss_dev float[1] = mean over the positions whose decoder
+ * INPUT token is not PAD of -log p[dec_out] (no clipping of p), and its full gradient into the handle's flat gradient buffer
+ * (hand-written reverse pass; fixed-order reductions, no float atomics: two identical calls give identical bits, both tables'
+ * row gradients included; the tied decoder table sums its output-layer and its embedding term).  Dropout as keras_transformer's
+ * block wrapper, LayerNorm(x + Dropout(f(x))): element (row, col) of the [rows, d] output of block `site` (0 encoder attention,
+ * 1 encoder ffn, 2 decoder self-attention, 3 decoder cross-attention, 4 decoder ffn) is kept when
+ * uniform01(seed, step, row, site * 65536 + col) >= dropout_rate and then scaled by 1 / (1 - dropout_rate).  The training
+ * activations are allocated by the first call ([max_rows, .] each).  N * max(L, src_len) <= max_rows. */
+int rl4rs_seq2seq_loss_grad(rl4rs_seq2seq* net, int32_t N, const int32_t* enc_tokens_dev, const int32_t* dec_in_dev,
+                            const int32_t* dec_out_dev, int32_t L, float dropout_rate, uint32_t seed, uint32_t step, float* loss_dev,
+                            void* stream);
+/* Adam in tf.train.AdamOptimizer's form (= Keras 'adam': lr_t = lr sqrt(1 - b2^t) / (1 - b1^t), p -= lr_t m / (sqrt(v) + eps)) on
+ * the handle's gradient; Keras' defaults are lr 1e-3, 0.9, 0.999, eps 1e-7. */
+int rl4rs_seq2seq_adam_step(rl4rs_seq2seq* net, float lr, float beta1, float beta2, float eps, void* stream);
+/* enc_tokens_dev int32 [N, src_len], dec_tokens_dev int32 [N, L] -> probs_dev float [N, L, V] (position l: the distribution of the
+ * token after dec_tokens[:, :l + 1]).  No dropout. */
+int rl4rs_seq2seq_forward(rl4rs_seq2seq* net, int32_t N, const int32_t* enc_tokens_dev, const int32_t* dec_tokens_dev, int32_t L,
+                          float* probs_dev, void* stream);
+/* Beam search as the reference's beam_search runs it: one live beam (<START>) at step 0, at every step the `beam` best of all
+ * live * V continuations, score = PRODUCT of the probabilities carried in float64, beam 0 the best, equal scores by the smaller
+ * beam * V + token; <END> and <PAD> are ordinary tokens, nothing ends early.  paths_dev int32 [N, beam, target_len + 1] (column 0 =
+ * 1), scores_dev double [N, beam], step_probs_dev (optional) float [N, beam, target_len]: the probability of each chosen token along
+ * the surviving path (their product is the score).  cand_bits_dev (optional) uint32 [N, ceil(V / 32)]: bit v of user n clear =
+ * the probability of token v counts as 0 from step 1 on (step 0 is unmasked, as in the reference).
+ * Refused: beam outside [1, 128], beam >= V, target_len outside [1, min(tgt_len, 63)], N * max(beam, src_len) > max_rows, a user whose
+ * candidate bits hold fewer than `beam` tokens (candidates_size < beam; the bits are counted on the device and the count read back,
+ * so a call with candidates synchronises the stream once before it decodes). */
+int rl4rs_seq2seq_beam(rl4rs_seq2seq* net, int32_t N, const int32_t* enc_tokens_dev, int32_t beam, int32_t target_len,
+                       const uint32_t* cand_bits_dev, int32_t* paths_dev, double* scores_dev, float* step_probs_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -101,6 +101,11 @@ class ExactKCfg(C.Structure):
                 [('dropout_rate', C.c_float)])
 
 
+class Seq2SeqCfg(C.Structure):
+    """rl4rs_seq2seq_cfg (include/rl4rs_hip.h)"""
+    _fields_ = [(n, C.c_int32) for n in ('token_num', 'embed_dim', 'hidden_dim', 'src_len', 'tgt_len', 'max_rows')]
+
+
 class BcqStep(C.Structure):
     """rl4rs_bcq_step (include/rl4rs_hip.h)"""
     _fields_ = ([(n, C.c_void_p) for n in ('imit_enc', 'imit_dec', 'policy', 'policy_targ', 'q1', 'q2', 'q1_targ', 'q2_targ')] +
@@ -437,6 +442,16 @@ SIGNATURES = {
     'rl4rs_dyn_adam_step': (_I, [_P, C.c_float, C.c_float, C.c_float, C.c_float, _P]),
     'rl4rs_dyn_predict': (_I, [_P, _I32, _P, _P, _P, _P, C.c_uint32, C.c_uint32, _I32, _I32, _I32, C.c_float, _P, _P, _P, _P, _P]),
     'rl4rs_sac_target': (_I, [_P, _P, _P, _P, _P, _P, C.c_float, _I32, _P, _P]),
+    'rl4rs_seq2seq_param_count': (_I64, [C.POINTER(Seq2SeqCfg)]),
+    'rl4rs_seq2seq_create': (_I, [C.POINTER(Seq2SeqCfg), _P, _P, C.POINTER(_P)]),
+    'rl4rs_seq2seq_destroy': (_I, [_P]),
+    'rl4rs_seq2seq_params': (_I, [_P, _P, _P, _P]),
+    'rl4rs_seq2seq_adam_state': (_I, [_P, _P, _P, _P]),
+    'rl4rs_seq2seq_set_adam_step': (_I, [_P, _I64]),
+    'rl4rs_seq2seq_loss_grad': (_I, [_P, _I32, _P, _P, _P, _I32, C.c_float, C.c_uint32, C.c_uint32, _P, _P]),
+    'rl4rs_seq2seq_adam_step': (_I, [_P, C.c_float, C.c_float, C.c_float, C.c_float, _P]),
+    'rl4rs_seq2seq_forward': (_I, [_P, _I32, _P, _P, _I32, _P, _P]),
+    'rl4rs_seq2seq_beam': (_I, [_P, _I32, _P, _I32, _I32, _P, _P, _P, _P, _P]),
 }
 
 # include/rl4rs_hip.h RL4RS_REPLAY_BUF_*

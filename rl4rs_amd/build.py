@@ -6,14 +6,14 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(CSRC, 'librl4rs_hip.so')
-SOURCES = ['env.hip', 'gemm.hip', 'dien.hip', 'augru_x.hip', 'augru_xs.hip', 'policy.hip', 'records.hip', 'step.hip', 'ope.hip', 'exactk.hip', 'dynamics.hip']
+SOURCES = ['env.hip', 'gemm.hip', 'dien.hip', 'augru_x.hip', 'augru_xs.hip', 'policy.hip', 'records.hip', 'step.hip', 'ope.hip', 'exactk.hip', 'dynamics.hip', 'seq2seq.hip']
 # Units whose MFMA kernels run VALU epilogues beside another wave's MFMAs are compiled without SLP vectorisation: packed fp32 VALU
 # (v_pk_fma / add / mul_f32) serialises with the matrix pipe (tools/mfma_valu_overlap.hip, profiles/r04p_mfma_valu_overlap.txt;
 # same-box A/B: k_cat_attn2 -8 %, k_din_x -2 %, end to end +0.7 %).  The other units keep it (the learners' element-wise and
 # reduction kernels are 1 - 4 % faster with it) - and so does augru_x.hip: k_augru_x<2,4,2> sits at the register limit and spills without it
 # (augru_xs.hip, the same recurrence text beside its shadow plane, is built like augru_x.hip).
 NO_SLP = ('dien.hip', 'gemm.hip')
-HEADERS = ['common.hpp', 'optim.hpp', 'recur_args.hpp', 'augru_x.hpp', 'din_x.hpp', 'row_dedup.hpp', 'row_refine.hpp', 'recur_train.hpp', 'recur8.hpp', 'mfma4.hpp', 'simnet.hpp', 'gather_kernels.hpp', 'simtrain.hpp', 'dientrain.hpp', 'clfmetrics.hpp', 'rawtrain.hpp', 'qlearn.hpp', 'contirl.hpp', 'amlp_fused.hpp', 'combo.hpp', 'ppo_pass.hpp', 'policy_tile_std.hpp', 'dqn.hpp', 'td3.hpp', 'rainbow.hpp', 'vtrace.hpp', 'gemm_h16_tile.inc', 'augru_x_body.inc', 'din_x_body.inc', 'env_rows_body.inc', 'augru_xs.hpp', 'gemm_h16_defs.hpp', 'cat_attn2_row.hpp', 'dien_plan.hpp', 'exactk_beam.hpp', os.path.join('..', '..', 'include', 'rl4rs_hip.h')]
+HEADERS = ['common.hpp', 'optim.hpp', 'recur_args.hpp', 'augru_x.hpp', 'din_x.hpp', 'row_dedup.hpp', 'row_refine.hpp', 'recur_train.hpp', 'recur8.hpp', 'mfma4.hpp', 'simnet.hpp', 'gather_kernels.hpp', 'simtrain.hpp', 'dientrain.hpp', 'clfmetrics.hpp', 'rawtrain.hpp', 'qlearn.hpp', 'contirl.hpp', 'amlp_fused.hpp', 'combo.hpp', 'ppo_pass.hpp', 'policy_tile_std.hpp', 'dqn.hpp', 'td3.hpp', 'rainbow.hpp', 'vtrace.hpp', 'gemm_h16_tile.inc', 'augru_x_body.inc', 'din_x_body.inc', 'env_rows_body.inc', 'augru_xs.hpp', 'gemm_h16_defs.hpp', 'cat_attn2_row.hpp', 'dien_plan.hpp', 'exactk_beam.hpp', 'seq2seq_train.hpp', os.path.join('..', '..', 'include', 'rl4rs_hip.h')]
 
 
 def _stale():

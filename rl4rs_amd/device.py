@@ -2535,3 +2535,115 @@ class DeviceDynamics(_FlatNet):
                                          1 if deterministic else 0, self.VARIANCE_TYPES[variance_type], 0 if lam is None else 1,
                                          0.0 if lam is None else float(lam), _ptr(nx), _ptr(r), _ptr(var), _ptr(used), _stream()))
         return nx, r, var, used
+
+
+class DeviceSeq2Seq(object):
+    """rl4rs_seq2seq handle: the MDP checker's one-layer encoder-decoder transformer and its beam search (include/rl4rs_hip.h,
+    "The MDP checker's model"; flat layout and initialiser in ``rl4rs_amd/mdpchecker.py``).  Training pass, inference and beam search.  ``max_rows`` bounds the
+    activation rows of a call: N * max(L, src_len) of ``forward``, N * max(beam, src_len) of ``beam``."""
+    BEAM_MAX = 128
+
+    def __init__(self, token_num, embed_dim, hidden_dim, src_len, tgt_len, max_rows, params, device=None):
+        self.lib = _lib.load()
+        self.token_num, self.embed_dim, self.hidden_dim = int(token_num), int(embed_dim), int(hidden_dim)
+        self.src_len, self.tgt_len, self.max_rows = int(src_len), int(tgt_len), int(max_rows)
+        self.cfg = _lib.Seq2SeqCfg(self.token_num, self.embed_dim, self.hidden_dim, self.src_len, self.tgt_len, self.max_rows)
+        n = self.lib.rl4rs_seq2seq_param_count(C.byref(self.cfg))
+        if n < 0:
+            raise _lib.Rl4rsHipError(self.lib.rl4rs_last_error().decode())
+        self.n_params = int(n)
+        params = np.ascontiguousarray(params, dtype=np.float32)
+        assert params.shape == (self.n_params,), (params.shape, self.n_params)
+        self.h = None
+        _lib.require_device()
+        self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            check(self.lib.rl4rs_seq2seq_create(C.byref(self.cfg), params.ctypes.data_as(C.c_void_p), _stream(), C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, 'h', None):
+            torch.cuda.synchronize(self.device)
+            self.lib.rl4rs_seq2seq_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def params(self):
+        """the handle's flat parameters as a float32 device tensor (a view: writes go to the handle)"""
+        p, n = C.c_void_p(), C.c_int64()
+        check(self.lib.rl4rs_seq2seq_params(self.h, C.byref(p), None, C.byref(n)))
+        return _alias_f32(p.value, n.value, self.device, self)
+
+    def grad(self):
+        g, n = C.c_void_p(), C.c_int64()
+        check(self.lib.rl4rs_seq2seq_params(self.h, None, C.byref(g), C.byref(n)))
+        return _alias_f32(g.value, n.value, self.device, self)
+
+    def adam_state(self):
+        """(m, v) views and the number of steps taken"""
+        m, v, t = C.c_void_p(), C.c_void_p(), C.c_int64()
+        check(self.lib.rl4rs_seq2seq_adam_state(self.h, C.byref(m), C.byref(v), C.byref(t)))
+        return _alias_f32(m.value, self.n_params, self.device, self), _alias_f32(v.value, self.n_params, self.device, self), int(t.value)
+
+    def set_adam_step(self, t):
+        check(self.lib.rl4rs_seq2seq_set_adam_step(self.h, int(t)))
+
+    def loss_grad(self, enc, dec_in, dec_out, dropout_rate=0.0, seed=0, step=0):
+        """masked cross-entropy (device tensor [1]) and its gradient into ``grad()``"""
+        enc = self._tokens(enc, self.src_len)
+        N, L = enc.shape[0], int(dec_in.shape[1] if hasattr(dec_in, 'shape') else len(dec_in[0]))
+        dec_in, dec_out = self._tokens(dec_in, L), self._tokens(dec_out, L)
+        assert dec_in.shape[0] == N and dec_out.shape[0] == N
+        loss = torch.empty(1, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            check(self.lib.rl4rs_seq2seq_loss_grad(self.h, N, _ptr(enc), _ptr(dec_in), _ptr(dec_out), L, float(dropout_rate),
+                                                   seed & 0xffffffff, step & 0xffffffff, _ptr(loss), _stream()))
+        return loss
+
+    def adam_step(self, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-7):
+        with torch.cuda.device(self.device):
+            check(self.lib.rl4rs_seq2seq_adam_step(self.h, lr, beta1, beta2, eps, _stream()))
+
+    def set_params(self, flat):
+        flat = np.ascontiguousarray(flat, dtype=np.float32)
+        assert flat.shape == (self.n_params,), (flat.shape, self.n_params)
+        self.params().copy_(torch.from_numpy(flat))
+
+    def _tokens(self, x, width):
+        t = _dev_tensor(x if isinstance(x, torch.Tensor) else np.asarray(x), torch.int32, self.device)
+        assert t.dim() == 2 and t.shape[1] == width, (tuple(t.shape), width)
+        return t
+
+    def forward(self, enc, dec):
+        """enc int [N, src_len], dec int [N, L] -> probabilities float32 [N, L, V] (device)"""
+        enc = self._tokens(enc, self.src_len)
+        N, L = enc.shape[0], int(np.shape(dec)[1])
+        dec = self._tokens(dec, L)
+        assert dec.shape[0] == N
+        out = torch.empty((N, L, self.token_num), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            check(self.lib.rl4rs_seq2seq_forward(self.h, N, _ptr(enc), _ptr(dec), L, _ptr(out), _stream()))
+        return out
+
+    def beam(self, enc, beam, target_len, cand_bits=None, want_step_probs=False):
+        """-> (paths int32 [N, beam, target_len + 1], scores float64 [N, beam], step_probs float32 [N, beam, target_len] or None),
+        device tensors; ``cand_bits`` uint32 [N, ceil(V / 32)] (numpy).  The library refuses a beam, target_len or N out of range."""
+        enc = self._tokens(enc, self.src_len)
+        N, B, T = enc.shape[0], int(beam), int(target_len)
+        bits = None
+        if cand_bits is not None:
+            cand_bits = np.ascontiguousarray(cand_bits, dtype=np.uint32)
+            assert cand_bits.shape == (N, (self.token_num + 31) // 32), cand_bits.shape
+            bits = _dev_tensor(cand_bits.view(np.int32), torch.int32, self.device)
+        paths = torch.empty((N, max(B, 0), max(T, 0) + 1), dtype=torch.int32, device=self.device)
+        scores = torch.empty((N, max(B, 0)), dtype=torch.float64, device=self.device)
+        sp = torch.empty((N, max(B, 0), max(T, 0)), dtype=torch.float32, device=self.device) if want_step_probs else None
+        with torch.cuda.device(self.device):
+            check(self.lib.rl4rs_seq2seq_beam(self.h, N, _ptr(enc), B, T, _ptr(bits), _ptr(paths), _ptr(scores), _ptr(sp), _stream()))
+        return paths, scores, sp
