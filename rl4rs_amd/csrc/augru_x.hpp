@@ -20,7 +20,8 @@
 //         all    R of the NEXT step on the early k-blocks;  late: || candidate + blend -> late columns of h'
 //         -- barrier b
 //     so whenever one wave of a SIMD is in an epilogue its partner keeps the matrix pipe busy, and the next step's reset-gate
-//     product starts on the half of the new state that is already written.
+//     product starts on the half of the new state that is already written.  RL4RS_X_USPLIT: between barrier a and barrier b the
+//     early waves - whose blend, and with it acc_u, is done - also run the next step's update-gate products on that half (role_item).
 //   * cached input projections through LDS-DMA: one issue window per step (right in front of the register-resident weight
 //     items, i.e. in front of a stretch without vector-memory waits) requests the three gates' rows of step t+1 with
 //     buffer_load ... lds: 4 instructions per gate, each one 8 rows x 128 contiguous bytes (8 cache lines instead of the 32 a
@@ -79,6 +80,12 @@ constexpr bool after_barrier(int i) { return i == 0 || i == 24 || i == 40; }
 #ifndef RL4RS_X_PEEL_MT2
 #define RL4RS_X_PEEL_MT2 RL4RS_X_PEEL
 #endif
+#ifndef RL4RS_X_USPLIT
+#define RL4RS_X_USPLIT 2        // role-specialised step (needs the rotated loop of RL4RS_X_PEEL): the early waves run the NEXT step's update-gate
+#endif                          // items on k-blocks 0..7 between barrier a and barrier b (see role_item).  0: one schedule for both roles,
+                                // 1: the 64-row form alone, 2: both forms and k_augru_xs.  Same-box A/B, 5 alternating rounds
+                                // (profiles/r22_ab.md): value 1 flat (7.405 -> 7.384 ms per episode-batch, inside the noise), value 2
+                                // 7.405 -> 7.184 ms (-3.0 %): the gain is the 32-row form's
 #ifndef RL4RS_X_AMAX
 #define RL4RS_X_AMAX 0          // 1: track max |h| over the steps for the range check (0: the final state alone decides, see the epilogue)
 #endif
@@ -92,24 +99,34 @@ template <int NRES> constexpr bool is_res(int i) {
 #endif
     return RL4RS_X_SPREAD ? ((i % (NI / NRES)) == (NI / NRES) - 1 && i / (NI / NRES) < NRES) : (i >= 40 - NRES && i < 40);
 }
+// order of a step's items by role (RL4RS_X_USPLIT).  Sequence position s of a step counts from barrier b: positions [0, SB) run
+// between barrier b and barrier a, positions [SB, 48) between barrier a and barrier b (SB = role_stretch).  One schedule for both
+// roles (split = false): position = item.  The early role of the split schedule: the update-gate items on k-blocks 0..7 (items
+// 8..15: the early half of the new state is complete at barrier a and the early waves' acc_u is dead from their blend on) run
+// behind the reset-gate items of the same - next - step, and the stretch behind barrier b keeps the update-gate items 16..23:
+//     0..7 (R late)  16..23 (U late)  24..39 (C)  |  40..47 (R early of step t+1)  8..15 (U early of step t+1)
+// Every accumulator keeps its operation order (C-in projection, then k-blocks 0..15 ascending); all moves are by multiples of 8, so
+// the parity of an item (its state-fragment buffer) still alternates along the sequence.
+constexpr int role_item(bool split, int s) { return !split ? s : (s < 8 ? s : (s < 40 ? s + 8 : s - 32)); }
+constexpr int role_stretch(bool split) { return split ? 32 : 40; }
 // compile-time tables of a step's schedule: index of a resident item in the register file, position of a streamed item in
-// the (cyclic) streamed sequence that starts at the first streamed item >= 40, and its inverse
+// the (cyclic) streamed sequence that starts at the first streamed item behind barrier a, and its inverse
 struct Sched { int res_idx[NI]; int js_of[NI]; int item_of[NI]; int js_first; };
-template <int NRES> constexpr Sched make_sched() {
+template <int NRES> constexpr Sched make_sched(bool split = false) {
     Sched s = {};
     int n = 0;
     for (int i = 0; i < NI; ++i) { s.res_idx[i] = n; n += is_res<NRES>(i) ? 1 : 0; }
-    int k = 40;
-    while (is_res<NRES>(k % NI)) ++k;
+    int k = role_stretch(split);
+    while (is_res<NRES>(role_item(split, k % NI))) ++k;
     int js = 0;
     for (int c = 0; c < NI; ++c) {
-        const int i = (k + c) % NI;
+        const int i = role_item(split, (k + c) % NI);
         s.js_of[i] = js;
         if (!is_res<NRES>(i)) { s.item_of[js] = i; ++js; }
     }
     int f = 0;
-    while (is_res<NRES>(f)) ++f;
-    s.js_first = s.js_of[f];                               // step 0 enters the sequence at its first streamed item >= 0
+    while (is_res<NRES>(role_item(split, f))) ++f;
+    s.js_first = s.js_of[role_item(split, f)];             // step 0 enters the sequence at its first streamed item >= 0
     return s;
 }
 }  // namespace xk

@@ -9,6 +9,10 @@
 #endif
     constexpr Sched SC = make_sched<NRES>();
     constexpr bool PEEL = MT == 1 ? RL4RS_X_PEEL != 0 : RL4RS_X_PEEL_MT2 != 0;
+    constexpr bool USPLIT = RL4RS_X_USPLIT == 2 || (RL4RS_X_USPLIT == 1 && MT == 2);      // role-specialised step (role_item, augru_x.hpp)
+    constexpr Sched SE = make_sched<NRES>(true);                   // the early role's streamed sequence under USPLIT
+    static_assert(!USPLIT || (PEEL && !RL4RS_X_SPREAD && !is_res<NRES>(40) && !is_res<NRES>(23) && RING <= 8 && RL4RS_X_XU_AT == 8),
+                  "the split schedule: rotated loop, resident items in front of item 40, look-ahead inside a stretch of 8");
     static_assert(GRP == 8 || (GRP == 9 && MT == 2 && !PAD), "rows per cache slot of the 64-row form");
     constexpr int ROWS = GRP == 9 ? 63 : 32 * MT;                  // positions a workgroup stores
     static_assert(NS > 0 && NS % RING == 0 && RING >= 2 && NRES >= 1 && NRES <= 14 && (!RL4RS_X_SPREAD || NI % NRES == 0), "weight ring / resident items");
@@ -133,8 +137,8 @@
 #pragma unroll
     for (int m = 0; m < MT; ++m) {
         att_cur[m] = att_row[m][0];
-        x_read(acc_r[m], 0, m);                                    // h = 0: the R products of step 0 vanish, acc_r = x_r(0)
-    }
+        if constexpr (!USPLIT) x_read(acc_r[m], 0, m);             // h = 0: the R products of step 0 vanish, acc_r = x_r(0)
+    }                                                              // (USPLIT: read per role, see `recur`)
     __syncthreads();
 
     auto hfrag = [&](int buf, int i) {                             // state fragments (B operand) of item i's k-block
@@ -216,12 +220,18 @@
     // items [lo, hi) of step t.  light: the items' matrix products are known to vanish or to be dead (BOUNDARY STEPS below) - no
     // MFMAs, no state-fragment reads and no weight requests for them; projections, epilogues, plane stores, barriers and the
     // projection issue window stay in their slots
-    auto items = [&](const int t, const int lo, const int hi, const bool light) __attribute__((always_inline)) {
+    // role: 0 = one schedule, the role is the run-time value `early`; 1 / 2 = the early / late role of the split schedule (USPLIT), known
+    // at compile time: [lo, hi) are sequence positions of role_item (for roles 0 and 2 position = item)
+    auto items = [&](const int t, const int lo, const int hi, const bool light, const int role) __attribute__((always_inline)) {
+        const bool ea = role == 0 ? early : role == 1;
+        const bool se = role == 1;
 #pragma unroll
-        for (int i = lo; i < hi; ++i) {
+        for (int s = lo; s < hi; ++s) {
+            const int i = role_item(se, s), nxt = s + 1 < NI ? role_item(se, s + 1) : NI;
             const int g = gate(i), cur = i & 1;
-            if (i == 8) RL4RS_XT(1);
-            if (i == RL4RS_X_XU_AT) {
+            if (i == (se ? 16 : 8)) RL4RS_XT(1);
+            // (split early role: x_u(t) was read behind barrier a of the step before - except in step 0, which has no such window)
+            if (se ? i == 16 && light : i == RL4RS_X_XU_AT) {
                 if (!(RL4RS_X_AB & (4 | 128))) {                  // x_u(t)   (128: no staging reads, DMA keeps going): staged one step ago
 #pragma unroll
                     for (int m = 0; m < MT; ++m) x_read(acc_u[m], 1, m);
@@ -241,7 +251,7 @@
 #pragma unroll
                     for (int m = 0; m < MT; ++m) x_read(acc_c[m], 2, m);
                 }
-                if (!early && !RL4RS_X_LATE_UPD_SHADOW) {
+                if (!ea && !RL4RS_X_LATE_UPD_SHADOW) {
                     // late role: the whole update gate first (VALU only) - its partner on the SIMD is already in its C items
 #pragma unroll
                     for (int r = 0; r < 16; ++r) update_gate(r);
@@ -252,20 +262,24 @@
                 if (!light) hfrag(cur, i);
             }
             if (i == 40) {
-                if (early) {
+                if (ea) {
                     // early role: candidate + blend after its C items, while its partner runs C on the matrix pipe
 #pragma unroll
                     for (int r = 0; r < 16; ++r) blend(r);
                 }
                 RL4RS_XT(4);
 #if RL4RS_X_PRIO == 3
-                if (!early) __builtin_amdgcn_s_setprio(0);
+                if (!ea) __builtin_amdgcn_s_setprio(0);
 #endif
                 if (!(RL4RS_X_AB & 16)) __syncthreads();           // early half of the new state complete
                 RL4RS_XT(5);
                 if (!(RL4RS_X_AB & (4 | 128)) && !light) {        // x_r(t+1) (requested 12+ items ago)
 #pragma unroll
                     for (int m = 0; m < MT; ++m) x_read(acc_r[m], 0, m);
+                }
+                if (se && !light && !(RL4RS_X_AB & (4 | 128))) {  // x_u(t+1) behind the same wait: acc_u is dead since the blend above
+#pragma unroll
+                    for (int m = 0; m < MT; ++m) x_read(acc_u[m], 1, m);
                 }
                 if (!light) hfrag(cur, i);
             }
@@ -278,13 +292,14 @@
                 for (int m = 0; m < MT; ++m) att_next[m] = att_row[m][t + 1];
             }
             // ---- fetch ahead: state fragments of the next item, streamed weights LA items ahead
-            if (i + 1 < NI && !after_barrier(i + 1) && !(RL4RS_X_AB & 8) && !light) hfrag(cur ^ 1, i + 1);
+            if (nxt < NI && !after_barrier(nxt) && !(RL4RS_X_AB & 8) && !light) hfrag(cur ^ 1, nxt);
             const bool resident = is_res<NRES>(i);
-            const int js = resident ? 0 : SC.js_of[i];             // position in the streamed sequence (if streamed)
+            const int js = resident ? 0 : (se ? SE.js_of[i] : SC.js_of[i]);      // position in the streamed sequence (if streamed)
             const int ridx = resident ? SC.res_idx[i] : 0;
-            const int ahead = resident ? 0 : SC.item_of[(js + LA) % NS];
+            const int ahead = resident ? 0 : (se ? SE.item_of[(js + LA) % NS] : SC.item_of[(js + LA) % NS]);
             // light: nothing for an item that is skipped itself (below 40 in the first step; the last step's tail requests nothing at all)
-            const bool fetch = !resident && !(RL4RS_X_AB & 2) && !(light && (i >= 40 || (ahead > i && ahead < 40)));
+            // (split early role: step 0's stretch ends in front of item 40 as well and its look-ahead stays inside it or reaches 40 ..)
+            const bool fetch = !resident && !(RL4RS_X_AB & 2) && !(light && (i >= 40 || (se ? ahead < 40 : ahead > i && ahead < 40)));
             if (fetch) wload(ahead, ring_h[(js + LA) % RING], ring_l[(js + LA) % RING]);
             __builtin_amdgcn_sched_barrier(0);
             const half8_t wh = resident ? res_h[ridx] : ring_h[js % RING];
@@ -298,17 +313,20 @@
                     acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(term == 1 ? wl : wh, term == 2 ? bl[cur][m] : bh[cur][m], acc, 0, 0, 0);
                 }
             // ---- epilogue work in this item's MFMA shadow
-            if (i >= 8 && i < 24) {
+            if (se && i >= 16 && i < 24) {                         // the eight U items the stretch keeps carry the reset gate, two elements each
+                reset_gate(2 * (i - 16));
+                reset_gate(2 * (i - 16) + 1);
+            } else if (!se && i >= 8 && i < 24) {
                 reset_gate(i - 8);
-            } else if ((early || RL4RS_X_LATE_UPD_SHADOW) && i >= 24 && i < 32) {
+            } else if ((ea || RL4RS_X_LATE_UPD_SHADOW) && i >= 24 && i < 32) {
                 update_gate(2 * (i - 24));
                 update_gate(2 * (i - 24) + 1);
-            } else if (!early && i >= 40) {
+            } else if (!ea && i >= 40) {
                 blend(2 * (i - 40));
                 blend(2 * (i - 40) + 1);
             }
 #if RL4RS_X_SGB
-            if ((i >= 8 && i < 24) || (early && i >= 24 && i < 32) || (!early && i >= 40)) {
+            if ((i >= (se ? 16 : 8) && i < 24) || (ea && i >= 24 && i < 32) || (!ea && i >= 40)) {
                 // a wave issues in order: spread the VALU chunk over the item's three MFMAs instead of behind the last one
 #pragma unroll
                 for (int q = 0; q < 3 * MT; ++q) {
@@ -346,26 +364,59 @@
         // streamed weight sequence at item 40 (position 0): the LA requests in front of it are the ones the slots below 40 issue
         // in every step, so the ring reaches the loop in its steady state and no slot index depends on the step.  One step
         // (maxlen 1, RecurArgs::steps = 1) is both stretches back to back.
-        int t = 0;
-        step_begin(0, true);
-        items(0, 0, 40, true);
+        // USPLIT: the recurrence exists once per role behind ONE wave-uniform branch (with a branch per stretch the values that live
+        // across the joins - accumulators, state, weight ring - must agree on their registers between the roles: 100 spilled
+        // registers in the 64-row form, DESIGN 34).  Both roles count the same three barriers per step.  `sb`: the role's first
+        // position behind barrier a (role_stretch).  The early role's first stretch has no U items on k-blocks 0..7 at all (they were
+        // light in step 0 anyway) and reads x_u(0) in front of item 16; its tail (`tail`: end position) is items 40-47 alone - no U
+        // items, and no weight requests, of a step that does not exist.
+        auto recur = [&](const int role, const int sb, const int tail) __attribute__((always_inline)) {
+            // x_r(0) behind the branch: read in front of it, the 16 MT registers that the other role's step 0 still reads stay
+            // live through this role's whole loop (the two paths are laid out one behind the other) and are spilled around it
+            // (the two markers differ, so that the reads - and the reset gate's prescale behind them - are not hoisted back as common code)
+            if (role == 1) asm volatile("; early role"); else asm volatile("; late role");
+#pragma unroll
+            for (int m = 0; m < MT; ++m) x_read(acc_r[m], 0, m);
+            int t = 0;
+            step_begin(0, true);
+            items(0, 0, sb, true, role);
 #pragma unroll 1
-        while (t + 1 < TL) {
-            asm volatile("" : "+s"(sb_r), "+s"(sb_u), "+s"(sb_c));     // keep the per-item scalar offsets out of SGPR-hoisting
-            items(t, 40, NI, false);
+            while (t + 1 < TL) {
+                asm volatile("" : "+s"(sb_r), "+s"(sb_u), "+s"(sb_c));     // keep the per-item scalar offsets out of SGPR-hoisting
+                items(t, sb, NI, false, role);
+                step_end(t);
+                ++t;
+                step_begin(t, false);
+                items(t, 0, sb, false, role);
+            }
+            items(t, sb, tail, true, role);
             step_end(t);
-            ++t;
-            step_begin(t, false);
-            items(t, 0, 40, false);
+        };
+        if constexpr (USPLIT) {
+            if (early) recur(1, role_stretch(true), 40);
+            else recur(2, 40, NI);
+        } else {
+            int t = 0;
+            step_begin(0, true);
+            items(0, 0, 40, true, 0);
+#pragma unroll 1
+            while (t + 1 < TL) {
+                asm volatile("" : "+s"(sb_r), "+s"(sb_u), "+s"(sb_c));     // keep the per-item scalar offsets out of SGPR-hoisting
+                items(t, 40, NI, false, 0);
+                step_end(t);
+                ++t;
+                step_begin(t, false);
+                items(t, 0, 40, false, 0);
+            }
+            items(t, 40, NI, true, 0);
+            step_end(t);
         }
-        items(t, 40, NI, true);
-        step_end(t);
     } else {
 #pragma unroll 1
         for (int t = 0; t < TL; ++t) {
             asm volatile("" : "+s"(sb_r), "+s"(sb_u), "+s"(sb_c));     // keep the per-item scalar offsets out of SGPR-hoisting
             step_begin(t, false);
-            items(t, 0, NI, false);
+            items(t, 0, NI, false, 0);
             step_end(t);
         }
     }

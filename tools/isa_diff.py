@@ -2,7 +2,8 @@
 """Per-kernel comparison of the gfx950 instruction text of two source trees (the check behind "existing kernels keep their text"):
     python tools/isa_diff.py <other csrc dir> env.hip dien.hip step.hip
 compiles each unit of <other> and of this tree with the flags of rl4rs_amd/build.py (hipcc -S --offload-device-only), strips comments,
-directives and local label numbers, and prints one row per kernel: same / CHANGED / NEW / GONE, instruction lines, VGPRs, scratch."""
+directives and local label numbers, and prints one row per kernel: same / CHANGED / NEW / GONE, instruction lines, VGPRs, scratch.
+ISA_DIFF_FLAGS="-DRL4RS_X_USPLIT=0 ..." adds flags to THIS tree's compile only (a switch set back to what the other tree has)."""
 import os
 import re
 import subprocess
@@ -13,11 +14,11 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from rl4rs_amd.build import CSRC, NO_SLP  # noqa: E402
 
 
-def asm(csrc, unit, out):
+def asm(csrc, unit, out, extra=()):
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
     cmd = [hipcc, '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-function', '-ffp-contract=off', '-mllvm',
            '-pragma-unroll-threshold=200000', '-S', '--offload-device-only', os.path.join(csrc, unit), '-o', out]
-    subprocess.check_call(cmd + (['-fno-slp-vectorize'] if unit in NO_SLP else []))
+    subprocess.check_call(cmd + (['-fno-slp-vectorize'] if unit in NO_SLP else []) + list(extra))
     return open(out).read()
 
 
@@ -47,7 +48,7 @@ def main():
     with tempfile.TemporaryDirectory() as d:
         for u in units:
             a = kernels(asm(other, u, os.path.join(d, 'a.s')))
-            b = kernels(asm(CSRC, u, os.path.join(d, 'b.s')))
+            b = kernels(asm(CSRC, u, os.path.join(d, 'b.s'), os.environ.get('ISA_DIFF_FLAGS', '').split()))
             print('## %s' % u)
             names = sorted(set(a) | set(b))
             dem = subprocess.run(['c++filt'], input='\n'.join(names) + '\n', capture_output=True, text=True).stdout.splitlines()
