@@ -111,9 +111,14 @@ __global__ __launch_bounds__(256) void k_s2s_attn_bwd_q(const float* __restrict_
         s = s2s_wave_sum(s);
         if (lane == k) da = s;
     }
-    const float dot = s2s_wave_sum(a * da), sa = s2s_wave_sum(a);
+    // (1 - sum a) dot is taken as the sum of the first terms, which it equals: sum_k a_k (da_k - dot) = dot - dot sum a.  The row's
+    // dsc then cancel to the rounding of that one sum, and with a single key - where the scores cannot matter - dsc is exactly 0.
+    // As (1.f - sa) * dot the two terms each carried a rounding of da's size and left a gradient of noise in Wq / Wk at src_len = 1
+    // or L = 1 (1e-8 of the gradient's largest element), which Adam would have stepped by +- lr like any other.
+    const float dot = s2s_wave_sum(a * da);
     float ds = a * (da - dot);
-    if (lane == amax) ds -= (1.f - sa) * dot;
+    const float shift = s2s_wave_sum(ds);
+    if (lane == amax) ds -= shift;
     ds = ds / sqrtf((float)D);
     if (lane < Lk) dsc[(size_t)r * S2S_PA + lane] = ds;
     for (int d0 = 0; d0 < D; d0 += 64) {

@@ -343,10 +343,9 @@ LOSS_REL_BAR = {64: 4 * 1.1e-7, 256: 4 * 1.9e-7}
 GRAD_BAR = {64: 4 * 2.2e-6, 256: 4 * 3.4e-6}
 
 
-def forward_case(i):
-    """-> (V, d, h, flat parameters, enc [N, S], dec [N, L]) of FORWARD_CASES[i]"""
-    N, S, L, V, d, h = FORWARD_CASES[i]
-    rs = np.random.RandomState(50 + i)
+def _tokens_with_pad(shape, seed):
+    N, S, L, V, d, h = shape
+    rs = np.random.RandomState(seed)
     enc = rs.randint(1, V, size=(N, S)).astype(np.int32)
     dec = rs.randint(1, V, size=(N, L)).astype(np.int32)
     dec[:, 0] = START
@@ -354,16 +353,194 @@ def forward_case(i):
     dec[1, -1] = PAD
     if L > 2:
         dec[2, 1] = PAD              # a PAD key in front of later queries
+    return enc, dec
+
+
+def _targets(dec, V, seed):
+    out = np.random.RandomState(seed).randint(1, V, size=dec.shape).astype(np.int32)
+    out[:, :-1] = np.where(dec[:, 1:] != PAD, dec[:, 1:], out[:, :-1])
+    return out
+
+
+def forward_case(i):
+    """-> (V, d, h, flat parameters, enc [N, S], dec [N, L]) of FORWARD_CASES[i]"""
+    N, S, L, V, d, h = FORWARD_CASES[i]
+    enc, dec = _tokens_with_pad(FORWARD_CASES[i], 50 + i)
     return V, d, h, random_params(V, d, h, 3 + i), enc, dec
 
 
 def train_targets(i):
     """decoder outputs [N, L] for forward_case(i): the inputs shifted by one, PAD where the input is PAD's successor"""
-    N, S, L, V, d, h = FORWARD_CASES[i]
-    _, _, _, _, _, dec = forward_case(i)
-    out = np.random.RandomState(70 + i).randint(1, V, size=(N, L)).astype(np.int32)
-    out[:, :-1] = np.where(dec[:, 1:] != PAD, dec[:, 1:], out[:, :-1])
-    return out
+    return _targets(forward_case(i)[5], FORWARD_CASES[i][3], 70 + i)
+
+
+# ---------------------------------------------------------------- off the two default shapes (tests/test_gpu_mdp_shapes.py)
+# (N, src_len, L, V, d, hidden), each with the path of csrc/seq2seq.hip, seq2seq_train.hpp and gemm.hip it enters.  launch_gemm_f32
+# has three forms: k_gemm_small below 96 workgroups of 128 x 64 (or N <= 32), k_gemm_f32_t128 from 2048 rows with N >= 96 and every
+# size and pointer a multiple of 4 floats, k_gemm_f32 otherwise.  With d = 128 a d-wide product has two column tiles, so it leaves
+# k_gemm_small only from 6017 rows; the tied output layer at V = 292 has five and leaves it from 2433 rows.  Cases 9 and 10 are
+# sized by that: they, not 6 .. 8, reach the two large forms.
+SHAPE_CASES = (
+    # 0: every lane of a wave is a key, in both self-attentions and in cross-attention; the causal mask at 64 queries
+    (3, 64, 64, 37, 64, 48),
+    # 1: L > S: k_s2s_attn_bwd_kv of the cross-attention loops over more queries than there are keys, max_rows = N * L
+    (4, 3, 9, 37, 64, 48),
+    # 2: one key, one query, in training too; user 0's only source token and user 1's only decoder input are PAD
+    (5, 1, 1, 37, 64, 48),
+    # 3: d % 4 == 2: the tail guard of every per-row kernel is live in the second 64-stride, no row of an activation is 16-byte
+    #    aligned (scalar loads in every GEMM); odd hidden width: every matrix behind ef.b1 lies off 16-byte alignment
+    (5, 7, 5, 41, 66, 7),
+    # 4: d % 64 != 0 with d % 4 == 0: tail guard live, vector loads stay; carries dropout 0.5
+    (5, 7, 5, 41, 100, 33),
+    # 5: the narrowest widths s2s_check_cfg admits, but for d = 2 and 4 (there a row is one pair of position columns)
+    (5, 7, 5, 41, 6, 1),
+    # 6: 2304 encoder rows: s2s_chunk = 256 with 9 partials in every encoder weight gradient, 18 row tiles per GEMM (k_gemm_small:
+    #    36 workgroups), strided KV + D outputs (ldc = 2 d) at many rows
+    (36, 64, 8, 292, 128, 100),
+    # 7: the same rows with hidden % 4 == 2: every matrix behind ef.b1 off 16-byte alignment (scalar weight loads in k_gemm_nt)
+    (36, 64, 8, 292, 128, 102),
+    # 8: 4480 encoder rows: s2s_chunk = ceil(4480 / 16) = 280, no multiple of the 16-sample trip of k_gemm_tn, 16 partials; 2310
+    #    decoder rows through the tied output layer (ldw = Vp) and its weight gradient: 19 x 5 = 95 workgroups, the last k_gemm_small
+    (70, 64, 33, 292, 128, 100),
+    # 9: 6080 encoder rows: 48 x 2 = 96 workgroups, so every d-wide projection of the encoder (N = 128) and its FFN (N = 100) run
+    #    k_gemm_f32_t128, with the strided KV + D outputs; 2470 decoder rows: 20 x 5 = 100, the tied output layer (N = 292, ldw = Vp)
+    #    runs it too; s2s_chunk = 380
+    (95, 64, 26, 292, 128, 100),
+    # 10: the same rows with hidden % 4 == 2: ef.W1 (N = 102) and everything behind it, off alignment, run k_gemm_f32; the encoder
+    #    attention's projections and the output layer (the transposed table is a buffer of its own) stay in k_gemm_f32_t128
+    (95, 64, 26, 292, 128, 102),
+)
+SHAPE_DROP = (0.05, 7, 3)
+SHAPE_DROP_HALF = {4: (0.5, 7, 3)}               # case -> a second dropout setting
+
+# Per case: 4 x what `python tests/mdp_ref.py shapes` prints (the float32 restatement against float64 at the case's own inputs; for
+# the loss and the gradient the largest of the case's dropout settings).  The measured maxima stand in the comments.  A figure
+# below float32's unit roundoff 2^-24 is luck, not a property of the format - the loss is ONE float32 number, and a probability near
+# 1 cannot be stored closer than that - so a measured figure counts as at least F32_ROUND.  Never taken from the kernels.
+F32_ROUND = 6.0e-8
+
+
+def _bars(p_abs, p_rel, loss, grad):
+    return dict(abs=4 * max(p_abs, F32_ROUND), rel=4 * p_rel, loss=4 * max(loss, F32_ROUND), grad=4 * grad)
+
+
+SHAPE_BARS = {                                   # |p32 - p64|, the same / p64 where p > 1e-6, loss relative, worst grad_errors tensor
+    0: _bars(7.2e-7, 4.3e-6, 8.4e-8, 3.1e-6),    # 7.13e-7  4.24e-6  8.35e-8  3.00e-6 (dc.bk)
+    1: _bars(5.0e-7, 3.2e-6, 4.7e-8, 4.4e-6),    # 4.99e-7  3.14e-6  4.67e-8  4.31e-6 (dc.bk)
+    2: _bars(5.7e-7, 2.6e-6, 3.2e-8, 1.2e-6),    # 5.62e-7  2.56e-6  3.20e-8  1.11e-6 (E_dec)
+    3: _bars(4.6e-7, 4.4e-6, 1.0e-7, 3.1e-6),    # 4.52e-7  4.35e-6  9.93e-8  3.08e-6 (dc.bk)
+    4: _bars(6.8e-7, 4.6e-6, 5.5e-8, 4.6e-6),    # 6.74e-7  4.55e-6  5.48e-8  4.59e-6 (dc.bk)
+    5: _bars(2.2e-8, 3.8e-7, 2.9e-8, 9.1e-6),    # 2.14e-8  3.78e-7  2.84e-8  9.07e-6 (ef.b1)
+    6: _bars(1.8e-6, 8.6e-6, 3.6e-8, 1.1e-6),    # 1.73e-6  8.53e-6  3.52e-8  1.00e-6 (ea.bk)
+    7: _bars(2.0e-6, 1.2e-5, 5.2e-8, 1.6e-6),    # 1.93e-6  1.19e-5  5.15e-8  1.55e-6 (ds.Wq)
+    8: _bars(1.7e-6, 1.1e-5, 6.8e-8, 9.2e-7),    # 1.64e-6  1.03e-5  6.74e-8  9.18e-7 (ds.Wq)
+    9: _bars(2.3e-6, 1.2e-5, 8.8e-8, 5.4e-7),    # 2.24e-6  1.14e-5  8.78e-8  5.37e-7 (ds.Wv)
+    10: _bars(2.1e-6, 1.1e-5, 1.1e-7, 6.3e-7),   # 2.00e-6  1.08e-5  1.00e-7  6.22e-7 (ds.Wq)
+}
+
+
+def shape_case(i):
+    """-> (V, d, h, flat parameters, enc [N, S], dec [N, L]) of SHAPE_CASES[i], PAD keys placed as forward_case places them"""
+    N, S, L, V, d, h = SHAPE_CASES[i]
+    enc, dec = _tokens_with_pad(SHAPE_CASES[i], 150 + i)
+    return V, d, h, random_params(V, d, h, 30 + i), enc, dec
+
+
+def shape_targets(i):
+    return _targets(shape_case(i)[5], SHAPE_CASES[i][3], 170 + i)
+
+
+def shape_drops(i):
+    return [None, SHAPE_DROP] + ([SHAPE_DROP_HALF[i]] if i in SHAPE_DROP_HALF else [])
+
+
+def masked_rows_case():
+    """FORWARD_CASES[0] with user 3's source all PAD and user 4's decoder input all PAD behind <START>
+    -> (V, d, h, flat, enc, dec, targets, lost): lost = the tokens that only user 3's source held"""
+    V, d, h, flat, enc, dec = forward_case(0)
+    enc, dec = enc.copy(), dec.copy()
+    others = np.delete(enc, 3, axis=0)
+    lost = sorted(int(v) for v in set(enc[3].tolist()) if not (others == v).any())
+    enc[3] = PAD
+    dec[4, 1:] = PAD
+    return V, d, h, flat, enc, dec, _targets(dec, V, 70), lost
+
+
+def masked_max_case(causal=False):
+    """Masked keys that tower over the open ones, so that sum e comes near the normaliser's 1e-7 and the max-shift term of the
+    attention's reverse pass carries weight: ea and ds score by q . k of the bare inputs (Wq = Wk = 1, the biases stay), column
+    d - 1 of both tables is 3 for every token and 25 for PAD (the position table adds about 1 there), so for an open query a PAD key
+    outscores an open key by about 4 * (26 - 4) / sqrt(64) = 11 before the max.  causal: the towering key is token 9 instead of PAD,
+    in the last but one decoder position - future, under the causal mask, for all queries before it - and PAD is placed as
+    forward_case places it.  -> (V, d, h, flat, enc, dec, targets)"""
+    V, d, h = 37, 64, 48
+    flat = random_params(V, d, h, 27).copy()
+    o = 0
+    at = {}
+    for name, shape in layout(V, d, h):
+        at[name] = (o, shape)
+        o += int(np.prod(shape))
+    for name in ('ea.Wq', 'ea.Wk', 'ds.Wq', 'ds.Wk'):
+        flat[at[name][0]:at[name][0] + d * d] = np.eye(d, dtype=np.float32).ravel()
+    for name in ('E_enc', 'E_dec'):
+        E = flat[at[name][0]:at[name][0] + V * d].reshape(V, d)        # a view: writes go to flat
+        E[:, d - 1] = 3.0
+        E[9 if causal else PAD, d - 1] = 25.0
+    N, S, L = 5, 18, 7
+    rs = np.random.RandomState(28)
+    enc = rs.randint(1, V, size=(N, S)).astype(np.int32)
+    dec = rs.randint(1, V, size=(N, L)).astype(np.int32)
+    dec[:, 0] = START
+    if causal:
+        enc[enc == 9] = 10
+        dec[dec == 9] = 10
+        dec[:, L - 2] = 9                        # future for the queries 0 .. L - 3
+        enc[0, -2:] = PAD
+        dec[1, -1] = PAD
+    else:
+        enc[:, 1::3] = PAD
+        dec[:, 2::3] = PAD
+    return V, d, h, flat, enc, dec, _targets(dec, V, 29)
+
+
+MASKED_ROWS_BARS = _bars(4.6e-7, 4.1e-6, 1.8e-8, 1.9e-6)            # 4.59e-7  4.04e-6  1.75e-8  1.82e-6 (ds.bk); dropout 0 and SHAPE_DROP
+# (the probabilities of the masked-max cases are not compared: PAD's output logit towers too, the rest is below 1e-6)
+MASKED_MAX_BARS = {False: _bars(0, 0, 5.5e-8, 2.2e-6),              # loss 5.49e-8, gradient 2.19e-6 (ds.Wk)
+                   True: _bars(0, 0, 1.5e-8, 6.1e-6)}               # loss 1.49e-8, gradient 6.02e-6 (ds.Wq)
+
+
+# beam-search edges: (N, S, V, K, T, candidates_size, seed); weights random_params(V, 64, 48, seed), sources
+# RandomState(seed + 1).randint(3, V) between <START> and <END>
+BEAM_CASES = (
+    # 0: beam 64, the last width at which one list head per lane suffices in k_s2s_merge
+    (4, 6, 70, 64, 3, None, 12),
+    # 1: beam 65, the first width at which lane 0 keeps a second head
+    (4, 6, 70, 65, 3, None, 12),
+    # 2: the same under candidate sets of beam + 3 tokens: all but 3 of a row's V - 65 unkept items are zero products, which tie
+    (4, 6, 70, 65, 3, 68, 12),
+    # 3: S2S_BEAM_MAX with V = beam + 1, the smallest vocabulary `beam < token_num` admits: a row's list drops one token
+    (8, 6, 129, 128, 3, None, 19),
+    # 4: target_len 63: T1 = 64, the stride the prefix and sp buffers are allocated with; table attention over up to 63 prefix keys
+    (4, 6, 37, 4, 63, None, 13),
+    # 5: 2400 beam rows, V % 4 == 0: 19 x 5 = 95 workgroups, the output layer's last k_gemm_small
+    (24, 6, 292, 100, 3, None, 14),
+    # 6: 2500 beam rows: 20 x 5 = 100 workgroups, the output layer runs k_gemm_f32_t128 (ldw = Vp); candidate sets of beam + 4
+    (25, 6, 292, 100, 3, 104, 14),
+)
+# 4 x the float32 search's scores against the float64 search's, relative; the share of users whose every float64 selection margin
+# exceeds that bar is 0.75, 0.75, 0.75, 0.875, 1, 0.83, 0.84 (tests/test_mdp_host.py asserts >= 0.75)
+BEAM_BARS = {0: 4 * 3.9e-6, 1: 4 * 3.9e-6, 2: 4 * 3.9e-6,           # 3.89e-6 each
+             3: 4 * 3.9e-6,                                          # 3.85e-6
+             4: 4 * 3.8e-6,                                          # 3.78e-6; the smallest score is 2.5e-5
+             5: 4 * 4.7e-6, 6: 4 * 4.7e-6}                           # 4.60e-6 each
+
+
+def beam_case(i):
+    N, S, V, K, T, Cn, seed = BEAM_CASES[i]
+    d, h = 64, 48
+    enc = np.random.RandomState(seed + 1).randint(3, V, size=(N, S)).astype(np.int32)
+    enc[:, 0], enc[:, -1] = START, END
+    return dict(N=N, S=S, V=V, K=K, T=T, C=Cn, d=d, h=h, seed=seed, enc=enc, flat=random_params(V, d, h, seed))
 
 
 def load_case(golden_dir, name):
@@ -372,6 +549,47 @@ def load_case(golden_dir, name):
     N, V, K, Cn, S, T, d, h, seed = (int(v) for v in z['cfg'])
     return dict(N=N, V=V, K=K, C=Cn or None, S=S, T=T, d=d, h=h, seed=seed, enc=z['encode_input'], paths=z['output_topk'].astype(np.int64),
                 scores=z['beam_score'], flat=random_params(V, d, h, seed))
+
+
+def probs_errors(got, want):
+    """-> (max |got - want|, max |got - want| / want where want > 1e-6)"""
+    err = np.abs(got - want)
+    big = want > 1e-6
+    return float(err.max()), float((err[big] / want[big]).max())
+
+
+def train_errors(V, d, h, flat, enc, dec, out, drops):
+    """float32 restatement against float64 -> (loss relative, worst grad_errors figure, its tensor), the largest over `drops`"""
+    loss, grad, name = 0.0, 0.0, None
+    for drop in drops:
+        l64, g64 = RefSeq2Seq(V, d, h, flat).loss_and_grad(enc, dec, out, drop)
+        l32, g32 = RefSeq2Seq(V, d, h, flat, torch.float32).loss_and_grad(enc, dec, out, drop)
+        e = grad_errors(g32, g64, V, d, h)
+        loss = max(loss, abs(l32 - l64) / l64)
+        if max(e.values()) > grad:
+            grad, name = max(e.values()), max(e, key=e.get)
+    return loss, grad, name
+
+
+def measure_shapes():
+    """the figures behind SHAPE_BARS, MASKED_ROWS_BARS, MASKED_MAX_BARS and BEAM_BARS"""
+    def one(tag, V, d, h, flat, enc, dec, out, drops):
+        a = RefSeq2Seq(V, d, h, flat).predict([enc, dec])
+        b = RefSeq2Seq(V, d, h, flat, torch.float32).predict([enc, dec])
+        loss, grad, name = train_errors(V, d, h, flat, enc, dec, out, drops)
+        print(tag, 'abs %.3g rel (p > 1e-6) %.3g loss rel %.3g grad %.3g (%s)' % (probs_errors(b, a) + (loss, grad, name)), flush=True)
+    for i, shape in enumerate(SHAPE_CASES):
+        one('shape %d %s' % (i, shape), *shape_case(i), shape_targets(i), shape_drops(i))
+    one('masked rows', *masked_rows_case()[:7], [None, SHAPE_DROP])
+    one('masked max', *masked_max_case(), [None])
+    one('masked max, causal', *masked_max_case(True), [None])
+    for i, shape in enumerate(BEAM_CASES):
+        c = beam_case(i)
+        _, s64, _, margin = beam_search_ref(RefSeq2Seq(c['V'], c['d'], c['h'], c['flat']), c['enc'], c['K'], c['T'], c['C'])
+        _, s32, _, _ = beam_search_ref(RefSeq2Seq(c['V'], c['d'], c['h'], c['flat'], torch.float32), c['enc'], c['K'], c['T'], c['C'])
+        rel = (np.abs(s32 - s64) / s64).max()
+        print('beam %d %s' % (i, shape), 'score rel %.3g' % rel, 'clear share at 4 x that %.3f' % (margin > 4 * rel).mean(),
+              'smallest score %.3g' % s64.min(), flush=True)
 
 
 if __name__ == '__main__':
@@ -389,6 +607,10 @@ if __name__ == '__main__':
             print('epoch %d exact-match %.4f' % (e, rate), flush=True)
             return rate >= 0.95
         train_ref(init_params(c['V'], c['d'], c['h'], c['seed']), 200, report)
+        sys.exit(0)
+    if sys.argv[1:] in ([], ['shapes']):
+        measure_shapes()
+    if sys.argv[1:] == ['shapes']:
         sys.exit(0)
     golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
     for i, shape in enumerate(FORWARD_CASES):

@@ -211,3 +211,172 @@ def test_header_declares_the_seq2seq_symbols():
                         'rl4rs_seq2seq_adam_state', 'rl4rs_seq2seq_set_adam_step', 'rl4rs_seq2seq_loss_grad', 'rl4rs_seq2seq_adam_step',
                         'rl4rs_seq2seq_forward', 'rl4rs_seq2seq_beam'}
     assert declared <= set(_lib.SIGNATURES)
+
+
+# ---------------------------------------------------------------- the cases of tests/test_gpu_mdp_shapes.py, checked without a device
+def _offsets(V, d, h):
+    out, o = {}, 0
+    for name, shape in mdp_ref.layout(V, d, h):
+        out[name] = o
+        o += int(np.prod(shape))
+    return out
+
+
+def _gemm_constants():
+    """the tiering constants of launch_gemm_f32, read from the source: a change there has to revisit the shape table"""
+    text = open(os.path.join(REPO, 'rl4rs_amd', 'csrc', 'gemm.hip')).read()
+    gbm, gbn = (int(v) for v in re.search(r'constexpr int GBM = (\d+), GBN = (\d+),', text).groups())
+    small = int(re.search(r'SMALL_GEMM_MAX_BIG_BLOCKS = (\d+);', text).group(1))
+    assert re.search(r'grid\.x \* grid\.y < SMALL_GEMM_MAX_BIG_BLOCKS \|\| N <= 32', text)
+    assert re.search(r'if \(M >= 2048 && N >= 96 && K >= 32 && \(K & 3\) == 0 && \(N & 3\) == 0 && \(lda & 3\) == 0 && \(ldw & 3\) == 0', text)
+    return gbm, gbn, small
+
+
+def _gemm_form(M, N, K, lda, ldw, aligned=True):
+    """the form launch_gemm_f32 takes (gemm.hip), restated"""
+    gbm, gbn, small = _gemm_constants()
+    if -(-M // gbm) * -(-N // gbn) < small or N <= 32:
+        return 'small'
+    if M >= 2048 and N >= 96 and K >= 32 and K % 4 == 0 and N % 4 == 0 and lda % 4 == 0 and ldw % 4 == 0 and aligned:
+        return 't128'
+    return 'f32'
+
+
+def test_shape_cases_enter_the_paths_their_comments_name():
+    cases = mdp_ref.SHAPE_CASES
+    assert cases[:9] == ((3, 64, 64, 37, 64, 48), (4, 3, 9, 37, 64, 48), (5, 1, 1, 37, 64, 48), (5, 7, 5, 41, 66, 7), (5, 7, 5, 41, 100, 33),
+                         (5, 7, 5, 41, 6, 1), (36, 64, 8, 292, 128, 100), (36, 64, 8, 292, 128, 102), (70, 64, 33, 292, 128, 100))
+    assert sorted(mdp_ref.SHAPE_BARS) == list(range(len(cases))) and list(mdp_ref.SHAPE_DROP_HALF) == [4]
+    text = open(os.path.join(REPO, 'rl4rs_amd', 'csrc', 'seq2seq.hip')).read()
+    assert 'constexpr int S2S_MAXLEN = 64;' in text and 'constexpr int S2S_BEAM_MAX = 128;' in text
+    assert 'return std::max(256, (Ns + 15) / 16);' in text                       # s2s_chunk
+    chunk = lambda rows: max(256, (rows + 15) // 16)
+    for i, (N, S, L, V, d, h) in enumerate(cases):
+        V_, d_, h_, flat, enc, dec = mdp_ref.shape_case(i)
+        assert (V_, d_, h_) == (V, d, h) and enc.shape == (N, S) and dec.shape == (N, L)
+        assert (enc == 0).any() and (dec == 0).any() and enc.max() < V and dec.max() < V             # PAD keys on both sides
+        out = mdp_ref.shape_targets(i)
+        assert out.shape == dec.shape and ((dec != 0) & (out != 0)).any()
+    assert cases[0][1] == cases[0][2] == 64                                          # every lane a key
+    assert cases[1][2] > cases[1][1] and cases[2][1:3] == (1, 1)
+    assert (mdp_ref.shape_case(2)[4][0] == 0).all() and mdp_ref.shape_case(2)[5][1, 0] == 0          # S = 1, L = 1: whole rows masked
+    # widths: the tail guard of the 64-strides, and what the flat offsets do to 16-byte alignment
+    for i, tail, d4, aligned_after_ffn in ((3, True, 2, False), (4, True, 0, False), (5, True, 2, False), (6, False, 0, True), (7, False, 0, False)):
+        N, S, L, V, d, h = cases[i]
+        o = _offsets(V, d, h)
+        assert (d % 64 != 0) == tail and d % 4 == d4
+        later = [o[k] % 4 == 0 for k in ('ef.W2', 'ds.Wq', 'dc.Wk', 'df.W1')]
+        assert all(later) if aligned_after_ffn else not any(later), (i, later)
+    assert all(_offsets(41, 66, 7)[k] % 4 for k in ('ds.Wq', 'dc.Wv', 'df.W2'))      # d % 4 == 2 and odd hidden: nothing behind ef.b1 aligned
+    # row tiers
+    form = lambda rows, n, k, **kw: _gemm_form(rows, n, k, k, n, **kw)
+    for i in (6, 7):
+        N, S, L, V, d, h = cases[i]
+        assert N * S == 2304 and chunk(N * S) == 256 and -(-N * S // 256) == 9 and form(N * S, d, d) == 'small'
+    N, S, L, V, d, h = cases[8]
+    assert N * S == 4480 and chunk(N * S) == 280 and 280 % 16 and -(-N * S // 280) == 16
+    assert N * L == 2310 and _gemm_form(N * L, V, d, d, (V + 3) & ~3) == 'small' and form(N * S, d, d) == 'small'
+    for i, aligned in ((9, True), (10, False)):
+        N, S, L, V, d, h = cases[i]
+        assert chunk(N * S) == 380 and form(N * S, d, d) == 't128' and form(N * S, 2 * d // 2, d) == 't128'                  # ea, KV + D
+        assert form(N * S, h, d, aligned=aligned) == ('t128' if aligned else 'f32')                                          # ef.W1
+        assert form(N * S, d, h, aligned=aligned) == ('t128' if aligned else 'f32')                                          # ef.W2, K = hidden
+        assert form(N * S, d, d, aligned=aligned) == ('t128' if aligned else 'f32')                                          # dc.Wk / Wv on the encoder rows
+        assert V % 4 == 0 and _gemm_form(N * L, V, d, d, (V + 3) & ~3) == 't128'                                             # tied output layer
+        assert (_offsets(V, d, h)['dc.Wk'] % 4 == 0) == aligned
+    # every case stays inside what s2s_check_cfg admits
+    assert all(S <= 64 and L <= 64 and d % 2 == 0 and d >= 2 and h >= 1 and V >= 4 for N, S, L, V, d, h in cases)
+
+
+class _DetachedMax(mdp_ref.RefSeq2Seq):
+    """the restatement with the max of the scores taken as a constant: its gradient lacks the max-shift term"""
+
+    def _att(self, pre, xq, xkv, key_open, causal):
+        import torch
+        p = self.p
+        q = xq @ p[pre + 'Wq'] + p[pre + 'bq']
+        k = xkv @ p[pre + 'Wk'] + p[pre + 'bk']
+        v = xkv @ p[pre + 'Wv'] + p[pre + 'bv']
+        s = q @ k.transpose(1, 2) / np.sqrt(self.d)
+        e = torch.exp(s - s.max(-1, keepdim=True).values.detach())
+        mask = key_open[:, None, :].to(self.dtype)
+        if causal:
+            L = xq.shape[1]
+            mask = mask * torch.tril(torch.ones(L, L, dtype=self.dtype))[None]
+        e = e * mask
+        a = e / (e.sum(-1, keepdim=True) + 1e-7)
+        return self._ln(xq + self._drop((a @ v) @ p[pre + 'Wo'] + p[pre + 'bo'], pre), pre)
+
+
+@pytest.mark.parametrize('causal', [False, True], ids=['pad', 'future'])
+def test_masked_max_case_has_teeth(causal):
+    """a reverse pass without the max-shift term misses the true gradient of this case by at least 100 bars in some tensor
+    (measured: about 1.0 in ds.Wk under PAD, 0.38 under the causal mask), and the key biases' gradients are nothing"""
+    V, d, h, flat, enc, dec, out = mdp_ref.masked_max_case(causal)
+    assert (enc == 0).any() and (dec == 0).any()
+    bar = mdp_ref.MASKED_MAX_BARS[causal]['grad']
+    loss, want = mdp_ref.RefSeq2Seq(V, d, h, flat).loss_and_grad(enc, dec, out)
+    loss_d, got = _DetachedMax(V, d, h, flat).loss_and_grad(enc, dec, out)
+    assert loss_d == loss and np.isfinite(want).all()                               # the same forward
+    err = mdp_ref.grad_errors(got, want, V, d, h)
+    print('without the max shift: worst %s %.3g (bar %.3g), %d tensors above the bar' % (max(err, key=err.get), max(err.values()), bar,
+                                                                                        sum(v > bar for v in err.values())))
+    assert max(err.values()) >= 100 * bar
+    o, top = _offsets(V, d, h), np.abs(want).max()
+    for k in ('ea.bk', 'ds.bk', 'dc.bk'):
+        assert np.abs(want[o[k]:o[k] + d]).max() < 1e-9 * top, k
+    if not causal:                                                                  # the construction as specified
+        E = flat[:V * d].reshape(V, d)
+        assert E[0, d - 1] == 25 and (E[1:, d - 1] == 3).all() and (enc[:, 1::3] == 0).all() and (dec[:, 2::3] == 0).all()
+        assert enc.shape == (5, 18) and dec.shape == (5, 7)
+        assert np.array_equal(flat[o['ds.Wk']:o['ds.Wk'] + d * d].reshape(d, d), np.eye(d))
+    else:
+        assert (dec[:, -2] == 9).all() and not (dec[:, :-2] == 9).any() and not (enc == 9).any()
+
+
+def test_masked_rows_case_in_the_restatement():
+    V, d, h, flat, enc, dec, out, lost = mdp_ref.masked_rows_case()
+    assert (enc[3] == 0).all() and dec[4, 0] == 1 and (dec[4, 1:] == 0).all() and lost
+    assert not np.isin(enc, lost).any()
+    _, g = mdp_ref.RefSeq2Seq(V, d, h, flat).loss_and_grad(enc, dec, out)
+    assert np.isfinite(g).all()
+    E = g[:V * d].reshape(V, d)
+    assert not E[lost].any() and E[0].any()              # a token no source holds has no gradient; PAD's own row has one
+    # a batch whose decoder inputs are all PAD has no position to average over: 0 / 0 in the restatement, where the library
+    # promises loss 0 and a zero gradient (it divides by max(count, 1))
+    with np.errstate(all='ignore'):
+        loss, _ = mdp_ref.RefSeq2Seq(V, d, h, flat).loss_and_grad(enc, np.zeros_like(dec), out)
+    assert np.isnan(loss)
+
+
+@pytest.fixture(scope='module')
+def shape_beam_refs():
+    out = []
+    for i in range(len(mdp_ref.BEAM_CASES)):
+        c = mdp_ref.beam_case(i)
+        c['margin'] = mdp_ref.beam_search_ref(mdp_ref.RefSeq2Seq(c['V'], c['d'], c['h'], c['flat']), c['enc'], c['K'], c['T'], c['C'])[3]
+        out.append(c)
+    return out
+
+
+def test_beam_cases_leave_three_quarters_of_their_users_clear(shape_beam_refs):
+    """at 4 x the float32 restatement's own error at least 75 % of a case's users keep every selection margin: the GPU test's
+    `clear.mean() >= 0.5` is then a condition with room, not a measurement"""
+    for i, c in enumerate(shape_beam_refs):
+        share = (c['margin'] > mdp_ref.BEAM_BARS[i]).mean()
+        print(mdp_ref.BEAM_CASES[i], 'clear share %.3f' % share)
+        assert share >= 0.75, i
+
+
+def test_beam_cases_sit_on_the_edges_their_comments_name():
+    cases = {c[:6] for c in mdp_ref.BEAM_CASES}
+    assert {(4, 6, 70, 64, 3, None), (4, 6, 70, 65, 3, None), (4, 6, 37, 4, 63, None), (24, 6, 292, 100, 3, None)} <= cases
+    assert sorted(mdp_ref.BEAM_BARS) == list(range(len(mdp_ref.BEAM_CASES)))
+    widest = [c for c in mdp_ref.BEAM_CASES if c[3] == 128]
+    assert widest and all(c[0] >= 4 and c[2] == 129 and c[4] <= 3 for c in widest)
+    assert any(c[5] is not None and c[3] in (65, 100) and c[3] <= c[5] <= c[3] + 4 for c in mdp_ref.BEAM_CASES)
+    assert all(c[4] + 1 <= 64 and c[3] < c[2] for c in mdp_ref.BEAM_CASES)
+    d = 64
+    rows = {c[0]: c[0] * c[3] for c in mdp_ref.BEAM_CASES if c[2] == 292}
+    assert rows == {24: 2400, 25: 2500}
+    assert _gemm_form(2400, 292, d, d, 292) == 'small' and _gemm_form(2500, 292, d, d, 292) == 't128'
