@@ -301,7 +301,10 @@ enum {
     RL4RS_DIEN_OPT_NO_LAZY_EXPAND = 1 << 22,   /* row dedup, second tier: k_row_expand behind the head GEMM in every forward, instead of
                                                   outputs that read the representative's row and internal rows completed by
                                                   rl4rs_dien_buffer (bit-identical either way) */
-    RL4RS_DIEN_OPT_ALL = (1 << 23) - 1
+    RL4RS_DIEN_OPT_GRU_H16_V1 = 1 << 23,       /* fp16x2 mode, first GRU: the 4-wave k_gru_h16 and a k_h1_frag launch per encode instead of
+                                                  k_gru_h16r (two wave roles per SIMD, writes the fragment-order copy itself;
+                                                  bit-identical either way) */
+    RL4RS_DIEN_OPT_ALL = (1 << 24) - 1
 };
 
 /* Every mode accumulates in fp32 and meets the fp32 parity bar against the fp64 oracle (same measured error):
@@ -423,9 +426,13 @@ enum {
                                      on a handle where it is off) */
     RL4RS_DIEN_ROW_REP = 5,       /* int32 [max_rows] representative group of every row group of the last forward, first
                                      R / group entries (rep[g] == g: scored itself) */
-    RL4RS_DIEN_ROW_ACTIVE = 6     /* int32 [max_rows] the representatives of the last forward in processing order, first
+    RL4RS_DIEN_ROW_ACTIVE = 6,    /* int32 [max_rows] the representatives of the last forward in processing order, first
                                      N_ACTIVE entries.  After a forward that took its partition from the caller
                                      (rl4rs_dien_set_row_partition) the three ids give the caller's buffers, n_bytes = 4 n_groups */
+    RL4RS_DIEN_H1_FRAG = 7,       /* float32 [max_slots + 1, ceil(maxlen / 32), 8, 64, 8] sequence input 0's first-GRU states in the
+                                     fragment order k_din_x reads (an error on a handle that keeps none) */
+    RL4RS_DIEN_LEAD = 8           /* int32 [max_slots + 1] leading zero ids of sequence input 0's history in every cache slot (an
+                                     error on a handle without the pad table) */
 };
 /* ALL_FEATURE, SCORES and QUERY: with the row dedup on, a forward computes these rows for the representatives only and (unless
  * RL4RS_DIEN_OPT_NO_LAZY_EXPAND, or a form of the forward that keeps k_row_expand) no longer copies them to the duplicates.

@@ -36,7 +36,7 @@ DIEN_OPTS = {'augru_h16': 1 << 0, 'augru_rows32': 1 << 1, 'augru_rows64': 1 << 2
              'no_head_fused': 1 << 10, 'cat_v1': 1 << 11, 'no_cat_group': 1 << 12, 'dense_fork': 1 << 13, 'no_gru_pad': 1 << 14,
              'no_gemm_group': 1 << 15, 'no_row_dedup': 1 << 16, 'no_dup_store': 1 << 17, 'din_rows16': 1 << 18, 'dup_store': 1 << 19,
              'no_tier2_rows': 1 << 20,
-             'no_augru_shadow': 1 << 21, 'no_lazy_expand': 1 << 22}
+             'no_augru_shadow': 1 << 21, 'no_lazy_expand': 1 << 22, 'gru_h16_v1': 1 << 23}
 POLICY_OPTS = {'tile': 0, 'ppo_fused': 1, 'ppo_rows': 2, 'resident_wgs': 3, 'ppo_std': 4}          # RL4RS_POLICY_OPT_*
 ENV_OPTS = {'rows_variant': 0}                                                       # RL4RS_ENV_OPT_*
 

@@ -1055,6 +1055,12 @@ void augru_xs_launch(int n_seq, hipStream_t st, const RecurArgs& a, const AugruS
 // slot or more ahead).  Per step 24 items x 3 v_mfma_f32_32x32x16_f16 = 2.3K cycles of matrix pipe against 12.3K for the
 // exact-fp32 form (k_recur<128, false>), with the same schedule of epilogues: reset gate in the shadow of slot U,
 // update gate in the shadow of slot C, candidate + blend exposed.  h stays in (-1, 1): no range flag needed.
+#ifdef RL4RS_H16_TRACE     // s_memtime marks of workgroup 0 of the first-GRU kernels, steps 8..11: [wave 0..7][step][mark] (tools/h16_trace.py --gru)
+#define RL4RS_TRG(k) do { if (a.trace && blockIdx.x == 0 && lane == 0 && t >= 8 && t < 12) \
+        a.trace[(wave * 4 + (t - 8)) * 8 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
+#else
+#define RL4RS_TRG(k) do { } while (0)
+#endif
 __global__ __launch_bounds__(256) void k_gru_h16(RecurArgs a) {
     constexpr int NH = 128, NW = 4, KB = NH / 16, LDP = NH + 8;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1167,6 +1173,7 @@ __global__ __launch_bounds__(256) void k_gru_h16(RecurArgs a) {
 
 #pragma unroll 1
     for (int t = t0; t < L; ++t) {
+        RL4RS_TRG(0);
         // ---- slot R: acc_r += h Wr
 #pragma unroll
         for (int kb = 0; kb < KB; ++kb) {
@@ -1176,6 +1183,7 @@ __global__ __launch_bounds__(256) void k_gru_h16(RecurArgs a) {
             acc_r = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, wr_l[kb], acc_r, 0, 0, 0);
             acc_r = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, wr_h[kb], acc_r, 0, 0, 0);
         }
+        RL4RS_TRG(1);
         // ---- slot U: acc_u += h Wu   ||   reset gate: item kb retires accumulator registers 2kb, 2kb + 1
 #pragma unroll
         for (int kb = 0; kb < KB; ++kb) {
@@ -1193,7 +1201,9 @@ __global__ __launch_bounds__(256) void k_gru_h16(RecurArgs a) {
             }
         }
         if (t + 1 < L) load_x(acc_r, t + 1, 0);              // next step's r projection into the retired accumulators
+        RL4RS_TRG(2);
         __syncthreads();
+        RL4RS_TRG(3);
         // ---- slot C: acc_c += (r*h) Wc (LDS, one item ahead)   ||   update gate
         half8_t wc_h[2], wc_l[2];
         wc_h[0] = *reinterpret_cast<const half8_t*>(lds_wc + vl16);
@@ -1214,6 +1224,7 @@ __global__ __launch_bounds__(256) void k_gru_h16(RecurArgs a) {
             ug[2 * kb + 1] = gate_sigmoid(acc_u[2 * kb + 1]);
         }
         if (t + 1 < L) load_x(acc_u, t + 1, 1);
+        RL4RS_TRG(4);
         // ---- exposed: candidate, blend, new state planes, h1 cache row
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -1234,9 +1245,15 @@ __global__ __launch_bounds__(256) void k_gru_h16(RecurArgs a) {
             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, hn), rs_o, o_voff, (((r & 3) + 8 * (r >> 2)) * L + t) * old4, 0);
         }
         if (t + 1 < L) load_x(acc_c, t + 1, 2);
+        RL4RS_TRG(5);
         __syncthreads();
+        RL4RS_TRG(6);
     }
 }
+
+}  // namespace rl4rs
+#include "gru_roles.hpp"     // k_gru_h16r: the same recurrence in two wave roles, writes the fragment-order copy itself (the default)
+namespace rl4rs {
 
 // -------------------------------------------------------------------------------------------------
 // DIN attention scores (deepctr LocalActivationUnit, att_hidden_units=(64,16), sigmoid, raw scores).
@@ -1640,7 +1657,8 @@ struct rl4rs_dien {
     int32_t* lead[4];      // [max_slots + 1] leading zero ids of the sequence in every cache slot (k_gru_h16 writes, k_augru_x<.., PAD> reads); slot max_slots = the all-zero sequence
     float* gru_wc16[4];
     bool gru16, gru16_attr;
-    int augru_rows;        // k_augru_x row-tile form: 0 automatic, 32, 64 (rl4rs_dien_set_augru_rows)
+    bool gru_roles;        // first GRU through k_gru_h16r (two wave roles, writes h1f itself); RL4RS_DIEN_OPT_GRU_H16_V1: k_gru_h16 + k_h1_frag
+    int augru_rows;       // k_augru_x row-tile form: 0 automatic, 32, 64 (rl4rs_dien_set_augru_rows)
     float augru_s[4][3][8];   // fp16x2: power-of-two prescale of the AUGRU's reset / update / candidate column tiles (1 in fp32 mode)
     float* tsum;           // [max_rows, 256]: obs_b + the per-slot head tables' rows, built by k_cat_attn (table form, Cn <= 24)
                            // (internal; second tier on the active rows, DESIGN 25: rows of duplicate groups are stale)
@@ -1696,6 +1714,22 @@ int alloc_f(rl4rs_dien* n, float** dst, size_t count) {
     int rc = dev_alloc(dst, count);
     if (rc) return rc;
     n->owned.push_back(*dst);
+    return RL4RS_OK;
+}
+
+// First GRU of the fp16x2 mode on the rows of `a`: k_gru_h16r (writes a.h1f itself) or, RL4RS_DIEN_OPT_GRU_H16_V1, the 4-wave k_gru_h16
+// (a.h1f unused: the caller launches k_h1_frag behind it).
+int launch_gru16(rl4rs_dien* n, const RecurArgs& a, hipStream_t st) {
+    const size_t smem_v1 = (((size_t)4 * 32 * (128 + 8) * 2 + (size_t)32 * (a.L + 1) * 4 + 15) & ~(size_t)15) + (size_t)4 * 8 * 2048;
+    const size_t smem = n->gru_roles ? gru_h16r_smem(a.L) : smem_v1;
+    const void* fn = n->gru_roles ? reinterpret_cast<const void*>(&k_gru_h16r) : reinterpret_cast<const void*>(&k_gru_h16);
+    if (!n->gru16_attr) {
+        const int rc = raise_dyn_smem(fn, smem);
+        if (rc) return rc;
+        n->gru16_attr = true;
+    }
+    if (n->gru_roles) hipLaunchKernelGGL(k_gru_h16r, dim3((a.n_rows + 31) / 32, 1), dim3(512), smem, st, a);
+    else hipLaunchKernelGGL(k_gru_h16, dim3((a.n_rows + 31) / 32, 1), dim3(256), smem, st, a);
     return RL4RS_OK;
 }
 
@@ -1845,6 +1879,7 @@ int rl4rs_dien_create(const rl4rs_dien_cfg* c, const rl4rs_dien_weights* w, void
     n->t.gemm_group = !(opts & RL4RS_DIEN_OPT_NO_GEMM_GROUP);
     n->gru16 = false;
     n->gru16_attr = false;
+    n->gru_roles = !(opts & RL4RS_DIEN_OPT_GRU_H16_V1);
     if (want_fp16x2) {      // the DIN layer-1 split needs |q * h1| <= max |seq_emb| and the q*k rows of att_w1 inside fp16 range
         float mx = 0.f;
         bool fin = true;
@@ -2097,10 +2132,8 @@ int rl4rs_dien_create(const rl4rs_dien_cfg* c, const rl4rs_dien_weights* w, void
         float* zero_ids = nullptr;                       // L zero int32 ids (all-zero bits either way)
         if ((rc = alloc_f(n, &zero_ids, (size_t)L)) != RL4RS_OK) return rc;
         RL4RS_HIP_TRY(hipMemsetAsync(zero_ids, 0, (size_t)L * 4, st));
-        const size_t smem16 = (((size_t)4 * 32 * (128 + 8) * 2 + (size_t)32 * (L + 1) * 4 + 15) & ~(size_t)15) + (size_t)4 * 8 * 2048;
-        if ((rc = raise_dyn_smem(reinterpret_cast<const void*>(&k_gru_h16), smem16))) return rc;
-        n->gru16_attr = true;
         for (int s = 0; s < S; ++s) {
+            const int P = c->max_slots;
             AL(gru_pad[s], (size_t)L * E);
             RecurArgs a;
             memset(&a, 0, sizeof(a));
@@ -2109,12 +2142,13 @@ int rl4rs_dien_create(const rl4rs_dien_cfg* c, const rl4rs_dien_weights* w, void
             a.ids = reinterpret_cast<const int32_t*>(zero_ids);
             a.wg[0] = n->gru_wg16[s]; a.wc[0] = n->gru_wc16[s];
             a.out = n->gru_pad[s]; a.out_ld = E; a.slot_base = 0;
-            hipLaunchKernelGGL(k_gru_h16, dim3(1, 1), dim3(256), smem16, st, a);
+            // (k_gru_h16r writes the fragment copy of the all-zero sequence's slot beside the table)
+            if (n->gru_roles && n->h1f[s]) a.h1f = n->h1f[s] + (size_t)P * ((L + 31) / 32) * 4096;
+            if ((rc = launch_gru16(n, a, st))) return rc;
             RL4RS_LAUNCH_CHECK();
             // ... and the cache slot of the all-zero sequence (slot max_slots): states, fragment copy, projections - what encode does
-            const int P = c->max_slots;
             RL4RS_HIP_TRY(hipMemcpyAsync(n->h1[s] + (size_t)P * L * E, n->gru_pad[s], (size_t)L * E * 4, hipMemcpyDeviceToDevice, st));
-            if (n->h1f[s]) {
+            if (n->h1f[s] && !n->gru_roles) {
                 const int64_t pieces = (int64_t)((L + 31) / 32) * 1024;
                 hipLaunchKernelGGL(k_h1_frag, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, st, n->h1[s], n->h1f[s], P, 1, L);
                 RL4RS_LAUNCH_CHECK();
@@ -2168,6 +2202,10 @@ int rl4rs_dien_destroy(rl4rs_dien* n) {
     return RL4RS_OK;
 }
 
+#ifdef RL4RS_H16_TRACE
+static unsigned long long* trace_marks(unsigned long long** buf, size_t words, const char* dump_env);
+#endif
+
 int rl4rs_dien_encode(rl4rs_dien* n, int32_t s, const int32_t* ids, int32_t cnt, int32_t slot_base, void* stream) {
     RL4RS_REQUIRE(n && ids, "dien_encode: null argument");
     RL4RS_REQUIRE(s >= 0 && s < n->S, "dien_encode: sequence input %d out of range", s);
@@ -2187,18 +2225,18 @@ int rl4rs_dien_encode(rl4rs_dien* n, int32_t s, const int32_t* ids, int32_t cnt,
         if (n->gru16) {
             a.wg[0] = n->gru_wg16[s]; a.wc[0] = n->gru_wc16[s];
             a.pad = n->gru_pad[s]; a.lead_out = n->lead[s];
-            const size_t smem16 = (((size_t)4 * 32 * (128 + 8) * 2 + (size_t)32 * (L + 1) * 4 + 15) & ~(size_t)15) + (size_t)4 * 8 * 2048;
-            if (!n->gru16_attr) {
-                int rc16 = raise_dyn_smem(reinterpret_cast<const void*>(&k_gru_h16), smem16);
-                if (rc16) return rc16;
-                n->gru16_attr = true;
-            }
-            hipLaunchKernelGGL(k_gru_h16, dim3((cnt + 31) / 32, 1), dim3(256), smem16, st, a);
+            if (n->gru_roles) a.h1f = n->h1f[s];
+#ifdef RL4RS_H16_TRACE      // tools/h16_trace.py --gru (the marks of the PREVIOUS encode are dumped first)
+            static unsigned long long* gru_trace = nullptr;
+            a.trace = trace_marks(&gru_trace, 8 * 4 * 8, "RL4RS_GRU_TRACE_DUMP");
+#endif
+            const int rc16 = launch_gru16(n, a, st);
+            if (rc16) return rc16;
         } else {
             size_t smem = (size_t)(2 * 32 * (E + 4) + 32 * (L + 1) + 32) * 4;
             hipLaunchKernelGGL((k_recur<128, false, GRU_U>), dim3((cnt + 31) / 32, 1), dim3(256), smem, st, a);
         }
-        if (n->h1f[s]) {
+        if (n->h1f[s] && !(n->gru16 && n->gru_roles)) {
             const int64_t pieces = (int64_t)cnt * ((L + 31) / 32) * 1024;
             hipLaunchKernelGGL(k_h1_frag, dim3((unsigned)((pieces + 255) / 256 < 8192 ? (pieces + 255) / 256 : 8192)), dim3(256), 0, st,
                                n->h1[s], n->h1f[s], slot_base, cnt, L);
@@ -2610,6 +2648,12 @@ int rl4rs_dien_buffer(rl4rs_dien* n, int which, void** p, int64_t* bytes) {
         case RL4RS_DIEN_SCORES: ptr = n->scores; b = (int64_t)n->S * n->c.max_rows * n->L * 4; break;
         case RL4RS_DIEN_QUERY: ptr = n->q; b = (int64_t)n->c.max_rows * n->E * 4; break;
         case RL4RS_DIEN_H1: ptr = n->h1[0]; b = (int64_t)n->c.max_slots * n->L * n->E * 4; break;
+        case RL4RS_DIEN_H1_FRAG:
+            if (!n->h1f[0]) { set_error("dien_buffer: this handle keeps no fragment-order copy of the first-GRU states"); return RL4RS_EINVAL; }
+            ptr = n->h1f[0]; b = ((int64_t)n->c.max_slots + 1) * ((n->L + 31) / 32) * 32 * n->E * 4; break;
+        case RL4RS_DIEN_LEAD:
+            if (!n->lead[0]) { set_error("dien_buffer: this handle keeps no pad table (no lead[])"); return RL4RS_EINVAL; }
+            ptr = n->lead[0]; b = ((int64_t)n->c.max_slots + 1) * 4; break;
         case RL4RS_DIEN_N_ACTIVE:
         case RL4RS_DIEN_ROW_REP:
         case RL4RS_DIEN_ROW_ACTIVE: {
@@ -2754,8 +2798,8 @@ int rl4rs_dien_kernel_label(rl4rs_dien* n, int which, char* buf, int32_t cap) {
             break;
         case KID_PROB: s = "k_head_prob"; break;
         case KID_GRU1:
-            s = n->gru16 ? "k_gru_h16" : "k_recur<128,gru>";
-            if (n->h1f[0]) s += " + k_h1_frag";
+            s = n->gru16 ? (n->gru_roles ? "k_gru_h16r" : "k_gru_h16") : "k_recur<128,gru>";
+            if (n->h1f[0] && !(n->gru16 && n->gru_roles)) s += " + k_h1_frag";
             break;
         case KID_DEDUP: s = n->t.row_dedup ? "k_row_dedup + k_row_expand" : "k_row_dedup (off)"; break;
         case KID_PROJ: s = n->t.gemm16 ? "k_gemm_h16 / k_gemm_h16_wres(seq projections)" : "k_gemm_pk(seq projections)"; break;

@@ -83,6 +83,7 @@ struct RecurArgs {
     const float* sv_att[4];
     float *sv_r[4], *sv_u[4], *sv_c[4], *sv_h[4], *sv_rh[4];
     int sv_blk[3];               // SAVE: column block of the r / u / c pre-activations inside a row of xbase (TF cells 0,1,2; keras GRU 1,0,2)
+    float* h1f;                  // k_gru_h16r: fragment-order copy of `out` for k_din_x (din_x.hpp), written by the kernel itself; NULL = none
 };
 
 // activations of a pre-activation that is stored scaled by a power of two (k = -log2(e) / s resp. 2 log2(e) / s, RecurArgs)

@@ -16,6 +16,7 @@ from ._lib import check
 BUF_PREV_ACTIONS, BUF_ACTION_MASK, BUF_SPECIAL_MASK, BUF_DENSE, BUF_CATEGORY, BUF_SEQ0, BUF_SEQ1, \
     BUF_C_DENSE, BUF_C_CATEGORY, BUF_ERROR_FLAG = range(10)
 DIEN_ALL_FEATURE, DIEN_SCORES, DIEN_QUERY, DIEN_H1, DIEN_N_ACTIVE, DIEN_ROW_REP, DIEN_ROW_ACTIVE = range(7)
+DIEN_H1_FRAG, DIEN_LEAD = 7, 8
 
 _MASK_DTYPES = {torch.uint8: 0, torch.int32: 1, torch.int64: 2, torch.float32: 3}
 
@@ -646,7 +647,12 @@ class DeviceDien(object):
         p = C.c_void_p()
         n = C.c_int64()
         check(self.lib.rl4rs_dien_buffer(self.h, which, C.byref(p), C.byref(n)))
-        if which in (DIEN_N_ACTIVE, DIEN_ROW_REP, DIEN_ROW_ACTIVE):      # int32: row dedup of the last forward (an error where it is off)
+        if which == DIEN_H1_FRAG:                     # [max_slots + 1, step tiles, k-block, lane, 8], sequence input 0
+            out = torch.empty((self.max_slots + 1, (self.L + 31) // 32, 8, 64, 8), dtype=torch.float32, device=self.device)
+            assert out.numel() * 4 == n.value
+            check(self.lib.rl4rs_copy_d2d(_ptr(out), p, n.value, _stream()))
+            return out
+        if which in (DIEN_N_ACTIVE, DIEN_ROW_REP, DIEN_ROW_ACTIVE, DIEN_LEAD):      # int32: row dedup of the last forward (an error where it is off); lead[]
             out = torch.empty(n.value // 4, dtype=torch.int32, device=self.device)
             check(self.lib.rl4rs_copy_d2d(_ptr(out), p, n.value, _stream()))
             return out
