@@ -1755,6 +1755,66 @@ int rl4rs_seq2seq_forward(rl4rs_seq2seq* net, int32_t N, const int32_t* enc_toke
 int rl4rs_seq2seq_beam(rl4rs_seq2seq* net, int32_t N, const int32_t* enc_tokens_dev, int32_t beam, int32_t target_len,
                        const uint32_t* cand_bits_dev, int32_t* paths_dev, double* scores_dev, float* step_probs_dev, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Gaussian policy: the stochastic continuous actor-critic of the on-policy learners on support_conti_env
+ * (script/modelfree_train.py:219-234,271-286,315-330,362-377, the `is_conti` branches of A2C / PPO / PG / IMPALA).  RLlib 1.5.1's
+ * FullyConnectedNetwork under MODEL_DEFAULTS and its DiagGaussian are restated from their published form (ray is absent: parity
+ * unpinned), checked against tests/gauss_ref.py.
+ *   actor   head = tanh(tanh(x W1 + b1) W2 + b2) W3 + b3 = [mean (E) | log_std (E)]      critic  V = tanh(tanh(x V1 + c1) V2 + c2) V3 + c3
+ *   flat    [W1 | b1 | W2 | b2 | W3 (H x 2E) | b3 | V1 | c1 | V2 | c2 | V3 (H x 1) | c3], matrices [in, out], float32
+ *   with z = (a - mean) exp(-log_std):   logp = sum_e (-z^2 / 2 - log_std) - E log(2 pi) / 2,   entropy = sum_e (log_std + log(2 pi e) / 2),
+ *   KL(old || new) = sum_e [ls_n - ls_o + (exp(2 ls_o) + (mu_o - mu_n)^2) / (2 exp(2 ls_n)) - 1 / 2];   log_std is not clamped.
+ * Limits: 1 <= obs_dim <= 4096, hidden in {64, 128, 256}, 1 <= act_dim <= 64; create refuses other shapes.  Every call takes at most
+ * max_rows rows.  All arithmetic is fp32 (f32 MFMA); gradients and statistics are bit-identical from call to call.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct rl4rs_gpolicy rl4rs_gpolicy;
+
+int64_t rl4rs_gpolicy_param_count(int32_t obs_dim, int32_t hidden, int32_t act_dim);
+int rl4rs_gpolicy_create(int32_t obs_dim, int32_t hidden, int32_t act_dim, int32_t max_rows, const float* params_host, void* stream,
+                         rl4rs_gpolicy** out);
+int rl4rs_gpolicy_destroy(rl4rs_gpolicy* pol);
+/* Flat parameters (grad_dev receives NULL: the gradient is the caller's buffer), the Adam moments and step counter. */
+int rl4rs_gpolicy_params(rl4rs_gpolicy* pol, float** params_dev, float** grad_dev, int64_t* count);
+int rl4rs_gpolicy_adam_state(rl4rs_gpolicy* pol, float** m_dev, float** v_dev, int64_t* step);
+int rl4rs_gpolicy_set_adam_step(rl4rs_gpolicy* pol, int64_t step);
+/* dst's parameters <- src's (IMPALA's learner -> actor broadcast); the handles must have one shape. */
+int rl4rs_gpolicy_copy_params(rl4rs_gpolicy* dst, const rl4rs_gpolicy* src, void* stream);
+/* One launch: a = mean + exp(log_std) * normal01(seed, step, row, e) (row = position in the call; deterministic != 0: a = mean).
+ * action_dev [N, E] is the unclipped draw, env_action_dev [N, E] = clip(a, -1, 1) is what the env receives; logp / value / entropy
+ * [N], head_dev [N, 2E] = [mean | log_std], eps_dev [N, E] the noise.  Every output but action_dev may be NULL. */
+int rl4rs_gpolicy_act(rl4rs_gpolicy* pol, int32_t N, const float* obs_dev, uint32_t seed, uint32_t step, int32_t deterministic,
+                      float* action_dev, float* env_action_dev, float* logp_dev, float* value_dev, float* entropy_dev, float* head_dev,
+                      float* eps_dev, void* stream);
+/* The same forward for given (unclipped) actions [N, E]; on rl4rs_gpolicy_act's own actions logp is bit-identical to its logp. */
+int rl4rs_gpolicy_evaluate(rl4rs_gpolicy* pol, int32_t N, const float* obs_dev, const float* actions_dev, float* logp_dev,
+                           float* value_dev, float* entropy_dev, float* head_dev, void* stream);
+/* Loss and flat gradient, the formulas of rl4rs_policy_loss_grad with this distribution: algo 0 = A2C (sums over rows), algo 1 = PPO
+ * (means; KL(old || new); value clipping around old_value; needs old_logp [N], old_value [N], old_head [N, 2E]).
+ * stats_dev (optional) float[4] = sums of {policy loss, value loss, entropy, kl}. */
+int rl4rs_gpolicy_loss_grad(rl4rs_gpolicy* pol, int32_t algo, int32_t N, const float* obs_dev, const float* actions_dev,
+                            const float* adv_dev, const float* ret_dev, const float* old_logp_dev, const float* old_value_dev,
+                            const float* old_head_dev, float vf_coeff, float ent_coeff, float clip, float vf_clip, float kl_coeff,
+                            float* grad_dev, float* stats_dev, void* stream);
+/* Adam (tf.train.AdamOptimizer form) from grad_dev; grad_clip > 0 applies tf.clip_by_global_norm first. */
+int rl4rs_gpolicy_adam_step(rl4rs_gpolicy* pol, const float* grad_dev, float lr, float beta1, float beta2, float eps, float grad_clip,
+                            void* stream);
+/* One PPO pass over N shuffled rows in minibatches of `minibatch` consecutive rows (the trailing N % minibatch rows are dropped): one
+ * host call, bit-identical to rl4rs_gpolicy_loss_grad(algo 1) + rl4rs_gpolicy_adam_step per minibatch.  stats_dev (optional)
+ * float[8] as rl4rs_policy_ppo_epoch: [0..3] sums over the LAST minibatch, [4..7] sums over every row of the pass. */
+int rl4rs_gpolicy_ppo_epoch(rl4rs_gpolicy* pol, int32_t N, int32_t minibatch, const float* obs_dev, const float* actions_dev,
+                            const float* adv_dev, const float* ret_dev, const float* old_logp_dev, const float* old_value_dev,
+                            const float* old_head_dev, float vf_coeff, float ent_coeff, float clip, float vf_clip, float kl_coeff,
+                            float lr, float beta1, float beta2, float eps, float grad_clip, float* grad_dev, float* stats_dev,
+                            void* stream);
+/* One-call IMPALA update as rl4rs_policy_vtrace_loss_grad: evaluate every row of R rollouts of [T, B] time-major rows, the float64
+ * scan of rl4rs_vtrace per rollout (no dones: episodes end with the rollout), then the A2C-form loss with adv = pg_adv, ret = vs on
+ * the kept rows (drop_last: the last step only supplies the bootstrap value).  rewards_dev float64; stats_dev float[4];
+ * vtrace_stats_dev (optional) double[4] = sums of {rho, min(rho, clip_rho), vs, pg_adv}. */
+int rl4rs_gpolicy_vtrace_loss_grad(rl4rs_gpolicy* pol, int32_t R, int32_t T, int32_t B, const float* obs_dev, const float* actions_dev,
+                                   const float* behaviour_logp_dev, const double* rewards_dev, float gamma, float clip_rho,
+                                   float clip_pg_rho, int32_t drop_last, float vf_coeff, float ent_coeff, float* grad_dev,
+                                   float* stats_dev, double* vtrace_stats_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -452,6 +452,20 @@ SIGNATURES = {
     'rl4rs_seq2seq_adam_step': (_I, [_P, C.c_float, C.c_float, C.c_float, C.c_float, _P]),
     'rl4rs_seq2seq_forward': (_I, [_P, _I32, _P, _P, _I32, _P, _P]),
     'rl4rs_seq2seq_beam': (_I, [_P, _I32, _P, _I32, _I32, _P, _P, _P, _P, _P]),
+    'rl4rs_gpolicy_param_count': (_I64, [_I32, _I32, _I32]),
+    'rl4rs_gpolicy_create': (_I, [_I32, _I32, _I32, _I32, _P, _P, C.POINTER(_P)]),
+    'rl4rs_gpolicy_destroy': (_I, [_P]),
+    'rl4rs_gpolicy_params': (_I, [_P, _P, _P, _P]),
+    'rl4rs_gpolicy_adam_state': (_I, [_P, _P, _P, _P]),
+    'rl4rs_gpolicy_set_adam_step': (_I, [_P, _I64]),
+    'rl4rs_gpolicy_copy_params': (_I, [_P, _P, _P]),
+    'rl4rs_gpolicy_act': (_I, [_P, _I32, _P, C.c_uint32, C.c_uint32, _I32, _P, _P, _P, _P, _P, _P, _P, _P]),
+    'rl4rs_gpolicy_evaluate': (_I, [_P, _I32, _P, _P, _P, _P, _P, _P, _P]),
+    'rl4rs_gpolicy_loss_grad': (_I, [_P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P] + [C.c_float] * 5 + [_P, _P, _P]),
+    'rl4rs_gpolicy_adam_step': (_I, [_P, _P, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _P]),
+    'rl4rs_gpolicy_ppo_epoch': (_I, [_P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P] + [C.c_float] * 10 + [_P, _P, _P]),
+    'rl4rs_gpolicy_vtrace_loss_grad': (_I, [_P, _I32, _I32, _I32, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float, _I32, C.c_float,
+                                            C.c_float, _P, _P, _P, _P]),
 }
 
 # include/rl4rs_hip.h RL4RS_REPLAY_BUF_*

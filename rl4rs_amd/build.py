@@ -6,7 +6,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(CSRC, 'librl4rs_hip.so')
-SOURCES = ['env.hip', 'gemm.hip', 'dien.hip', 'augru_x.hip', 'augru_xs.hip', 'policy.hip', 'records.hip', 'step.hip', 'ope.hip', 'exactk.hip', 'dynamics.hip', 'seq2seq.hip']
+SOURCES = ['env.hip', 'gemm.hip', 'dien.hip', 'augru_x.hip', 'augru_xs.hip', 'policy.hip', 'records.hip', 'step.hip', 'ope.hip', 'exactk.hip', 'dynamics.hip', 'seq2seq.hip', 'gausspolicy.hip']
 # Units whose MFMA kernels run VALU epilogues beside another wave's MFMAs are compiled without SLP vectorisation: packed fp32 VALU
 # (v_pk_fma / add / mul_f32) serialises with the matrix pipe (tools/mfma_valu_overlap.hip, profiles/r04p_mfma_valu_overlap.txt;
 # same-box A/B: k_cat_attn2 -8 %, k_din_x -2 %, end to end +0.7 %).  The other units keep it (the learners' element-wise and

@@ -61,6 +61,12 @@ __device__ __forceinline__ float uniform01(uint32_t seed, uint32_t step, uint32_
     h = mix32(h + a);
     return ((float)(h >> 9) + 0.5f) * (1.0f / 8388608.0f);
 }
+// N(0, 1) from the counter RNG by Box-Muller: a pure function of (seed, step, row, column).  u1 is strictly inside (0, 1).
+__device__ __forceinline__ float normal01(uint32_t seed, uint32_t step, uint32_t row, uint32_t col) {
+    const float u1 = uniform01(seed, step, row, 2u * col);
+    const float u2 = uniform01(seed, step, row, 2u * col + 1u);
+    return sqrtf(-2.f * logf(u1)) * cosf(6.28318530717958647692f * u2);
+}
 
 inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 

@@ -17,12 +17,7 @@
 
 namespace rl4rs {
 
-// N(0, 1) from the counter RNG by Box-Muller: a pure function of (seed, step, row, column).  u1 is strictly inside (0, 1).
-__device__ __forceinline__ float normal01(uint32_t seed, uint32_t step, uint32_t row, uint32_t col) {
-    const float u1 = uniform01(seed, step, row, 2u * col);
-    const float u2 = uniform01(seed, step, row, 2u * col + 1u);
-    return sqrtf(-2.f * logf(u1)) * cosf(6.28318530717958647692f * u2);
-}
+// (normal01, the Box-Muller draw on the counter RNG, lives beside uniform01 in common.hpp: gausspolicy.hip draws from it too)
 
 struct ExploreOu {
     int N, E, state_rows, random_phase, advance;

@@ -1574,6 +1574,135 @@ class DevicePolicy(_FlatNet):
     PASS_TIMEOUT_MESSAGE = ("the persistent PPO pass timed out at a grid barrier (workgroups not co-resident: the GPU is shared or "
                             "partitioned); the pass is incomplete - use DevicePolicy.set_option('ppo_fused', 0) for the per-minibatch kernels")
 
+
+class DeviceGaussPolicy(_FlatNet):
+    """rl4rs_gpolicy handle: the Gaussian actor-critic of the continuous on-policy learners (two tanh towers, a diagonal Gaussian
+    over ``act_dim`` action components; rl4rs_amd/nets/gausspolicy.py has the flat layout)."""
+    A2C, PPO = 0, 1
+    _prefix = 'rl4rs_gpolicy_'
+
+    def __init__(self, obs_dim, act_dim, max_rows, hidden=256, params=None, seed=0, device=None):
+        from .nets import gausspolicy as G
+        _lib.require_device()
+        self.lib = _lib.load()
+        self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        self.obs_dim, self.hidden, self.act_dim, self.max_rows = int(obs_dim), int(hidden), int(act_dim), int(max_rows)
+        self.n_params = int(self.lib.rl4rs_gpolicy_param_count(self.obs_dim, self.hidden, self.act_dim))
+        self.shapes = G.shapes(self.obs_dim, self.act_dim, self.hidden)
+        if params is None:
+            params = G.init_gausspolicy_params(self.obs_dim, self.act_dim, self.hidden, seed)
+        params = np.ascontiguousarray(params, dtype=np.float32)
+        assert params.shape == (self.n_params,), (params.shape, self.n_params)
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            check(self.lib.rl4rs_gpolicy_create(self.obs_dim, self.hidden, self.act_dim, self.max_rows,
+                                                params.ctypes.data_as(C.c_void_p), _stream(), C.byref(h)))
+        self.h = h
+
+    def _ptrs(self):
+        p, g, n = _FlatNet._ptrs(self)
+        return p, None, n                       # the gradient is the caller's buffer
+
+    def _f32(self, t, shape):
+        assert t.dtype == torch.float32 and tuple(t.shape) == tuple(shape) and t.is_contiguous() and t.is_cuda, (t.dtype, t.shape, shape)
+        return t
+
+    def _new(self, *shape):
+        return torch.empty(shape, dtype=torch.float32, device=self.device)
+
+    def act(self, obs, seed=0, step=0, deterministic=False, want_head=False, want_eps=False, out=None):
+        """Draw actions (one launch).  ``out`` = (action [N, E], env_action [N, E], logp [N], value [N], head [N, 2E] or None):
+        contiguous tensors to fill in place (slices of a rollout buffer).
+        -> (action, env_action = clip(action, -1, 1), logp, value, entropy, head or None, eps or None)."""
+        N, E = obs.shape[0], self.act_dim
+        self._f32(obs, (N, self.obs_dim))
+        if out is not None:
+            a, ea, lp, v, hd = out
+            self._f32(a, (N, E)); self._f32(ea, (N, E)); self._f32(lp, (N,)); self._f32(v, (N,))
+            if hd is not None:
+                self._f32(hd, (N, 2 * E))
+        else:
+            a, ea, lp, v = self._new(N, E), self._new(N, E), self._new(N), self._new(N)
+            hd = self._new(N, 2 * E) if want_head else None
+        ent = self._new(N)
+        eps = self._new(N, E) if want_eps else None
+        check(self.lib.rl4rs_gpolicy_act(self.h, N, _ptr(obs), seed & 0xffffffff, step & 0xffffffff, 1 if deterministic else 0, _ptr(a),
+                                         _ptr(ea), _ptr(lp), _ptr(v), _ptr(ent), _ptr(hd), _ptr(eps), _stream()))
+        return a, ea, lp, v, ent, hd, eps
+
+    def evaluate(self, obs, actions, want_head=False):
+        """-> (logp, value, entropy, head or None) of given (unclipped) actions [N, E]"""
+        N, E = obs.shape[0], self.act_dim
+        self._f32(obs, (N, self.obs_dim)); self._f32(actions, (N, E))
+        lp, v, ent = self._new(N), self._new(N), self._new(N)
+        hd = self._new(N, 2 * E) if want_head else None
+        check(self.lib.rl4rs_gpolicy_evaluate(self.h, N, _ptr(obs), _ptr(actions), _ptr(lp), _ptr(v), _ptr(ent), _ptr(hd), _stream()))
+        return lp, v, ent, hd
+
+    def loss_grad(self, algo, obs, actions, adv, ret, old_logp=None, old_value=None, old_head=None, vf_coeff=0.5, ent_coeff=0.01,
+                  clip=0.3, vf_clip=500.0, kl_coeff=0.2, grad_out=None, stats_out=None):
+        """-> (flat gradient, stats[4] sums of {policy loss, value loss, entropy, kl})"""
+        N = obs.shape[0]
+        g = grad_out if grad_out is not None else self._new(self.n_params)
+        stats = stats_out if stats_out is not None else self._new(4)
+        f = lambda t: None if t is None else t.to(torch.float32).contiguous()
+        obs, actions, adv, ret, old_logp, old_value, old_head = f(obs), f(actions), f(adv), f(ret), f(old_logp), f(old_value), f(old_head)
+        check(self.lib.rl4rs_gpolicy_loss_grad(self.h, algo, N, _ptr(obs), _ptr(actions), _ptr(adv), _ptr(ret), _ptr(old_logp),
+                                               _ptr(old_value), _ptr(old_head), vf_coeff, ent_coeff, clip, vf_clip, kl_coeff, _ptr(g),
+                                               _ptr(stats), _stream()))
+        return g, stats
+
+    def ppo_epoch(self, obs, actions, adv, ret, old_logp, old_value, old_head, minibatch=256, vf_coeff=0.5, ent_coeff=0.0, clip=0.3,
+                  vf_clip=500.0, kl_coeff=0.2, lr=1e-4, beta1=0.9, beta2=0.999, eps=1e-8, grad_clip=0.0, grad_out=None):
+        """One SGD pass over already shuffled rows (rl4rs_gpolicy_ppo_epoch).  Returns 8 floats: [0:4] sums of
+        {pi_loss, vf_loss, entropy, kl} over the last minibatch, [4:8] the same sums over every row of the pass."""
+        N = obs.shape[0]
+        g = grad_out if grad_out is not None else self._new(self.n_params)
+        stats = self._new(8)
+        f = lambda t: t.to(torch.float32).contiguous()
+        obs, actions, adv, ret, old_logp, old_value, old_head = f(obs), f(actions), f(adv), f(ret), f(old_logp), f(old_value), f(old_head)
+        check(self.lib.rl4rs_gpolicy_ppo_epoch(self.h, N, minibatch, _ptr(obs), _ptr(actions), _ptr(adv), _ptr(ret), _ptr(old_logp),
+                                               _ptr(old_value), _ptr(old_head), vf_coeff, ent_coeff, clip, vf_clip, kl_coeff, lr, beta1,
+                                               beta2, eps, grad_clip, _ptr(g), _ptr(stats), _stream()))
+        return stats
+
+    def ppo_minibatch_grad(self, mb_index, obs, actions, adv, ret, old_logp, old_value, old_head, minibatch=256, vf_coeff=0.5,
+                           ent_coeff=0.0, clip=0.3, vf_clip=500.0, kl_coeff=0.2, grad_out=None, stats_out=None):
+        """Data-parallel form of the pass: the gradient of minibatch ``mb_index`` of the shuffled rows, parameters untouched - the
+        loss of rl4rs_gpolicy_loss_grad on that row range, which is what rl4rs_gpolicy_ppo_epoch runs per minibatch.  Inputs are
+        contiguous float32 device tensors of the whole pass.  -> (grad, stats[4] sums)."""
+        lo, hi = mb_index * minibatch, (mb_index + 1) * minibatch
+        assert 0 <= lo and hi <= obs.shape[0]
+        for t in (obs, actions, adv, ret, old_logp, old_value, old_head):
+            assert t.dtype == torch.float32 and t.is_contiguous()
+        return self.loss_grad(self.PPO, obs[lo:hi], actions[lo:hi], adv[lo:hi], ret[lo:hi], old_logp[lo:hi], old_value[lo:hi],
+                              old_head[lo:hi], vf_coeff, ent_coeff, clip, vf_clip, kl_coeff, grad_out, stats_out)
+
+    def adam_step(self, grad, lr=1e-4, beta1=0.9, beta2=0.999, eps=1e-8, grad_clip=0.0):
+        check(self.lib.rl4rs_gpolicy_adam_step(self.h, _ptr(grad), lr, beta1, beta2, eps, grad_clip, _stream()))
+
+    def vtrace_loss_grad(self, R, T, B, obs, actions, behaviour_logp, rewards, gamma=1.0, clip_rho=1.0, clip_pg_rho=1.0, drop_last=True,
+                         vf_coeff=0.5, ent_coeff=0.01, grad_out=None, stats_out=None, vtrace_stats_out=None):
+        """V-trace loss and gradient over R rollouts of [T, B] time-major rows (rl4rs_gpolicy_vtrace_loss_grad): obs / actions /
+        behaviour_logp float32, rewards float64.  -> (grad, stats[4] sums of {policy loss, value loss, entropy, 0} over the kept
+        rows, vtrace_stats float64 [4] sums of {rho, min(rho, clip_rho), vs, pg_adv})."""
+        N = R * T * B
+        self._f32(obs, (N, self.obs_dim)); self._f32(actions, (N, self.act_dim)); self._f32(behaviour_logp, (N,))
+        assert rewards.dtype == torch.float64 and rewards.shape == (N,) and rewards.is_contiguous()
+        g = grad_out if grad_out is not None else self._new(self.n_params)
+        stats = stats_out if stats_out is not None else self._new(4)
+        vstats = vtrace_stats_out if vtrace_stats_out is not None else torch.empty(4, dtype=torch.float64, device=self.device)
+        assert stats.dtype == torch.float32 and stats.numel() == 4 and vstats.dtype == torch.float64 and vstats.numel() == 4
+        check(self.lib.rl4rs_gpolicy_vtrace_loss_grad(self.h, R, T, B, _ptr(obs), _ptr(actions), _ptr(behaviour_logp), _ptr(rewards), gamma,
+                                                      clip_rho, clip_pg_rho, 1 if drop_last else 0, vf_coeff, ent_coeff, _ptr(g),
+                                                      _ptr(stats), _ptr(vstats), _stream()))
+        return g, stats, vstats
+
+    def copy_params_from(self, other):
+        """This handle's parameters <- ``other``'s, a device-to-device copy (IMPALA's learner -> actor broadcast)."""
+        self.copy_from(other)
+
+
 class DeviceReplay(object):
     """rl4rs_replay handle: a ring of whole rollouts on the device with uniform / proportional-prioritized sampling."""
     _DTYPES = {'obs': torch.float32, 'mask': torch.int32, 'action': torch.int32, 'reward': torch.float32, 'done': torch.int32,

@@ -8,6 +8,10 @@ the policy that trails the learner by a fixed number of updates).
 Rollout, policy forward/backward and Adam run through librl4rs_hip.so; torch is used for buffers, the reversed
 cumulative sum of rewards and (data-parallel) the RCCL all-reduce of the flat gradient buffer.
 
+``ContiTrainer`` is the same loop on the continuous-action env (that driver's ``is_conti`` branches, :219-234,271-286,315-330,362-377):
+the Gaussian actor-critic of ``DeviceGaussPolicy`` (rl4rs_gpolicy_*) in place of the masked policy, a float action column, the env
+stepped with the clipped draw.
+
 ``DQNTrainer`` is the value-based learner of the same driver (script/modelfree_train.py:106-133: RLlib DQN with double_q, n_step 1,
 target_network_update_freq 200, buffer_size 100000 on the mask model): replay memory, TD loss, per-variable-clipped Adam and
 the target copy all stay on the device (rl4rs_replay_*, rl4rs_policy_dqn_loss_grad).
@@ -431,12 +435,15 @@ class Trainer(_OnPolicy):
                  train_batch_size=None, keep_last_batch=False, broadcast_interval=1, vtrace_clip_rho=1.0, vtrace_clip_pg_rho=1.0,
                  drop_last=True, vf_coeff=0.5, ent_coeff=0.01, grad_clip=10.0):
         cfg = env.config
-        _require_env(cfg, DISCRETE_ENV_MESSAGE % 'Trainer')
+        self._check_env(cfg)
         self.env = env
+        if algo not in self.DRIVER_LR:
+            raise ValueError("%s runs A2C, PPO, PG or IMPALA; got algo = %r" % (type(self).__name__, algo))
         # PG and IMPALA run on the A2C form of the loss kernels
         self.algo = {'A2C': D.DevicePolicy.A2C, 'PPO': D.DevicePolicy.PPO, 'PG': D.DevicePolicy.A2C, 'IMPALA': D.DevicePolicy.A2C}[algo]
         self.algo_name = algo
         self.B, self.T, self.A = cfg['batch_size'], cfg['max_steps'], cfg['action_size']
+        self.hidden = int(hidden)
         self.R = rollouts_per_train_call(self.B, self.T, train_batch_size)
         if lr is None:
             lr = self.DRIVER_LR[algo]
@@ -460,9 +467,9 @@ class Trainer(_OnPolicy):
             raise ValueError("PPO needs at least one full minibatch per train call: %d rollouts x batch_size x max_steps = %d < "
                              "minibatch = %d" % (self.R, N, minibatch))
         self.OD = _obs_width(env)
-        self.policy = D.DevicePolicy(self.OD, hidden, self.A, max_rows=N, seed=init_seed)
+        self.policy = self._new_policy(N, init_seed)
         share = rdist.ranks_sharing_device()
-        if share > 1:
+        if share > 1 and hasattr(self.policy, 'set_option'):
             # several ranks on ONE GPU (gloo dry runs only): the persistent PPO pass may use its grid barrier only while the grids of
             # all the processes on the device fit together, one workgroup per CU; beyond that the per-minibatch kernels run
             n_cu = torch.cuda.get_device_properties(self.policy.device).multi_processor_count
@@ -470,13 +477,7 @@ class Trainer(_OnPolicy):
         self.iteration = 0
         self._rollouts = 0
         dev = self.policy.device
-        self.buf = dict(obs=torch.empty((N, self.OD), dtype=torch.float32, device=dev),
-                        mask=torch.empty((N, self.policy.W), dtype=torch.int32, device=dev),
-                        act=torch.empty(N, dtype=torch.int32, device=dev),
-                        logp=torch.empty(N, dtype=torch.float32, device=dev),
-                        val=torch.empty(N, dtype=torch.float32, device=dev),
-                        rew=torch.empty(N, dtype=torch.float64, device=dev),
-                        logits=torch.empty((N, self.A), dtype=torch.float32, device=dev))
+        self.buf = self._new_buffers(N, dev)
         self.grad = torch.empty(self.policy.n_params, dtype=torch.float32, device=dev)
         self._mb_stats = torch.empty(4, dtype=torch.float32, device=dev)
         self.actor = None
@@ -485,9 +486,31 @@ class Trainer(_OnPolicy):
             self.sync_replicas()
         if algo == 'IMPALA':
             # the actor: the handle rollouts sample from; it only ever sees one env batch per call
-            self.actor = D.DevicePolicy(self.OD, hidden, self.A, max_rows=self.B, seed=init_seed)
+            self.actor = self._new_policy(self.B, init_seed)
             self.actor.copy_params_from(self.policy)
             self._vt_stats = torch.empty(4, dtype=torch.float64, device=dev)
+
+    # ---- what ContiTrainer states differently: the env it takes, the policy handle, the rollout columns (and ``rollout``)
+    _old = 'logits'                     # the rollout column PPO's KL term reads: the old distribution's parameters
+    _masked = True                      # the policy calls take the packed action mask of the rollout
+
+    def _check_env(self, cfg):
+        _require_env(cfg, DISCRETE_ENV_MESSAGE % 'Trainer' + "; the continuous-action env (support_conti_env) is ContiTrainer's")
+
+    def _new_policy(self, max_rows, init_seed):
+        return D.DevicePolicy(self.OD, self.hidden, self.A, max_rows=max_rows, seed=init_seed)
+
+    def _new_buffers(self, N, dev):
+        return dict(obs=torch.empty((N, self.OD), dtype=torch.float32, device=dev),
+                    mask=torch.empty((N, self.policy.W), dtype=torch.int32, device=dev),
+                    act=torch.empty(N, dtype=torch.int32, device=dev),
+                    logp=torch.empty(N, dtype=torch.float32, device=dev),
+                    val=torch.empty(N, dtype=torch.float32, device=dev),
+                    rew=torch.empty(N, dtype=torch.float64, device=dev),
+                    logits=torch.empty((N, self.A), dtype=torch.float32, device=dev))
+
+    def _mask_kw(self, b):
+        return dict(mask_bits=b['mask']) if self._masked else {}
 
     def sync_replicas(self, src=0):
         """Make every rank's parameters, Adam moments and step counter those of rank ``src``."""
@@ -546,13 +569,14 @@ class Trainer(_OnPolicy):
         self.iteration += 1
         if self.algo_name == 'IMPALA':
             # V-trace needs neither the returns nor the actor's values: the learner re-evaluates every row
-            g, stats, vstats, _ = self.policy.vtrace_loss_grad(self.R, self.T, self.B, b['obs'], b['act'], b['logp'], b['rew'],
-                                                               mask_bits=b['mask'], gamma=1.0, clip_rho=self.vtrace_clip_rho,
-                                                               clip_pg_rho=self.vtrace_clip_pg_rho, drop_last=self.drop_last,
-                                                               vf_coeff=self.vf_coeff, ent_coeff=self.ent_coeff, grad_out=self.grad,
-                                                               stats_out=self._mb_stats, vtrace_stats_out=self._vt_stats)
+            g, stats, vstats = self.policy.vtrace_loss_grad(self.R, self.T, self.B, b['obs'], b['act'], b['logp'], b['rew'],
+                                                            gamma=1.0, clip_rho=self.vtrace_clip_rho,
+                                                            clip_pg_rho=self.vtrace_clip_pg_rho, drop_last=self.drop_last,
+                                                            vf_coeff=self.vf_coeff, ent_coeff=self.ent_coeff, grad_out=self.grad,
+                                                            stats_out=self._mb_stats, vtrace_stats_out=self._vt_stats,
+                                                            **self._mask_kw(b))[:3]
             if self.keep_last_batch:
-                self.last_batch = dict((k, b[k].clone()) for k in ('obs', 'act', 'mask', 'logp', 'rew'))
+                self.last_batch = dict((k, b[k].clone()) for k in ('obs', 'act', 'mask', 'logp', 'rew') if k in b)
             rdist.allreduce_mean_(g)
             self.policy.adam_step(g, lr=self.lr, grad_clip=self.grad_clip)
             self.num_updates += 1
@@ -566,10 +590,10 @@ class Trainer(_OnPolicy):
                 adv, vf_coeff, ent_coeff, grad_clip = ret * (1.0 / N), 0.0, 0.0, 0.0
             else:
                 vf_coeff, ent_coeff, grad_clip = 0.5, 0.01, 10.0
-            g, stats = self.policy.loss_grad(self.algo, b['obs'], b['act'], adv, ret, mask_bits=b['mask'],
-                                             vf_coeff=vf_coeff, ent_coeff=ent_coeff, grad_out=self.grad)
+            g, stats = self.policy.loss_grad(self.algo, b['obs'], b['act'], adv, ret, vf_coeff=vf_coeff, ent_coeff=ent_coeff,
+                                             grad_out=self.grad, **self._mask_kw(b))
             if self.keep_last_batch:
-                self.last_batch = dict(obs=b['obs'].clone(), act=b['act'].clone(), mask=b['mask'].clone(), adv=adv.clone(), ret=ret.clone())
+                self.last_batch = dict(((k, b[k].clone()) for k in ('obs', 'act', 'mask') if k in b), adv=adv.clone(), ret=ret.clone())
             rdist.allreduce_mean_(g)                         # the ONE collective: flat policy gradient over RCCL
             self.policy.adam_step(g, lr=self.lr, grad_clip=grad_clip)
             return self._submit(mean_reward, stats[:4])
@@ -577,23 +601,22 @@ class Trainer(_OnPolicy):
         perm = torch.from_numpy(np.random.RandomState(self.seed + self.iteration - 1).permutation(N)).to(b['obs'].device)
         # shuffle every buffer ONCE (7 gathers per iteration instead of 7 per minibatch): minibatches are then
         # contiguous row ranges that go to the library as plain pointers
-        sh = dict((k, b[k][perm]) for k in ('obs', 'act', 'mask', 'logp', 'val', 'logits'))
+        sh = dict((k, b[k][perm]) for k in ('obs', 'act', 'mask', 'logp', 'val', self._old) if k in b)
         adv_s, ret_s = adv_n[perm].contiguous(), ret[perm].contiguous()
         if self.keep_last_batch:
             self.last_batch = dict(sh, adv=adv_s, ret=ret_s, kl_coeff=self._kl_coeff)
         MB = self.minibatch
         nmb = N // MB
+        old = ((sh['mask'],) if self._masked else ()) + (sh['logp'], sh['val'], sh[self._old])
         if not rdist.collectives_active():
             # single GPU: the whole pass is one library call (no per-minibatch collective to interleave)
-            stats = self.policy.ppo_epoch(sh['obs'], sh['act'], adv_s, ret_s, sh['mask'], sh['logp'], sh['val'],
-                                          sh['logits'], minibatch=MB, vf_coeff=0.5, ent_coeff=0.0,
+            stats = self.policy.ppo_epoch(sh['obs'], sh['act'], adv_s, ret_s, *old, minibatch=MB, vf_coeff=0.5, ent_coeff=0.0,
                                           clip=0.3, vf_clip=500.0, kl_coeff=self._kl_coeff, lr=self.lr, grad_out=self.grad)
             return self._submit(mean_reward, stats, kl_div=nmb * MB)
         # data parallel: per minibatch ONE fused gradient launch, ONE all-reduce, ONE Adam launch
         kl_sum = torch.zeros((), dtype=torch.float32, device=b['obs'].device)
         for mb in range(nmb):
-            g, stats = self.policy.ppo_minibatch_grad(mb, sh['obs'], sh['act'], adv_s, ret_s, sh['mask'], sh['logp'],
-                                                      sh['val'], sh['logits'], minibatch=MB, vf_coeff=0.5, ent_coeff=0.0,
+            g, stats = self.policy.ppo_minibatch_grad(mb, sh['obs'], sh['act'], adv_s, ret_s, *old, minibatch=MB, vf_coeff=0.5, ent_coeff=0.0,
                                                       clip=0.3, vf_clip=500.0, kl_coeff=self._kl_coeff,
                                                       grad_out=self.grad, stats_out=self._mb_stats)
             rdist.allreduce_mean_(g)
@@ -602,6 +625,94 @@ class Trainer(_OnPolicy):
         # (the KL sum settles with the deferred statistics like the single-GPU path; ADVICE / VERDICT r3: this path used to read
         # kl_sum on the host - one queue drain per train call and rank)
         return self._submit_ppo_minibatches(mean_reward, stats, kl_sum, nmb * MB)
+
+
+class ContiTrainer(Trainer, _Evaluated):
+    """A2C / PPO / PG / IMPALA on the Gaussian actor-critic (``DeviceGaussPolicy``: RLlib's default FullyConnectedNetwork and its
+    DiagGaussian, restated, parity unpinned) over the zero-copy continuous-action env - the ``is_conti`` branches of
+    script/modelfree_train.py:219-234,271-286,315-330,362-377.  Constructor arguments, defaults, ``DRIVER_LR`` and ``train_iteration``
+    are ``Trainer``'s, branch for branch; what differs is the policy handle and the action column: the rollout stores the unclipped
+    action [N, E] (the log-probability and every loss use it) and steps the env with ``clip(a, -1, 1)``, which the env's masked K-NN
+    turns into an item; PPO keeps the old head [N, 2E] where ``Trainer`` keeps the old logits.  ``hidden`` is the width of both
+    hidden layers of both towers (64, 128 or 256).
+
+    Deviations, as in ``Trainer``: IMPALA's actor lag is the deterministic ``broadcast_interval``, and a train call consumes whole
+    rollouts.  ``support_onehot_action`` (a 284-wide action) and ``rawstate_as_obs`` are refused.
+
+    ``evaluate(episodes, seed)`` plays the deterministic action (the mean)."""
+
+    _old = 'head'
+    _masked = False
+
+    def __init__(self, env, algo='A2C', hidden=256, seed=0, lr=None, minibatch=256, init_seed=0, kl_coeff=0.2, kl_target=0.01,
+                 train_batch_size=None, keep_last_batch=False, broadcast_interval=1, vtrace_clip_rho=1.0, vtrace_clip_pg_rho=1.0,
+                 drop_last=True, vf_coeff=0.5, ent_coeff=0.01, grad_clip=10.0):
+        Trainer.__init__(self, env, algo=algo, hidden=hidden, seed=seed, lr=lr, minibatch=minibatch, init_seed=init_seed, kl_coeff=kl_coeff,
+                         kl_target=kl_target, train_batch_size=train_batch_size, keep_last_batch=keep_last_batch,
+                         broadcast_interval=broadcast_interval, vtrace_clip_rho=vtrace_clip_rho, vtrace_clip_pg_rho=vtrace_clip_pg_rho,
+                         drop_last=drop_last, vf_coeff=vf_coeff, ent_coeff=ent_coeff, grad_clip=grad_clip)
+        self.device = self.policy.device
+        self._owned = (self.policy,) + ((self.actor,) if self.actor is not None else ())
+        f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.device)
+        self._env_act = f(self.B, self.E)                   # the clipped draw of the current step: what the env receives
+        self._eval = (f(self.B, self.E), f(self.B, self.E), f(self.B), f(self.B), None)
+
+    def _check_env(self, cfg):
+        _require_env(cfg, "ContiTrainer needs the zero-copy continuous-action env (config['return_tensors'] and ['support_conti_env'] = True)",
+                     conti=True)
+        if cfg.get('support_onehot_action', False):
+            raise ValueError("ContiTrainer: support_onehot_action (an action as wide as the catalogue) is out of scope: the Gaussian "
+                             "policy takes act_dim <= 64")
+        if cfg.get('rawstate_as_obs', False):
+            raise ValueError("ContiTrainer: rawstate_as_obs is out of scope (the *_rawstate variants of the continuous learners)")
+        self.E = int(cfg.get('action_emb_size', 32))
+
+    def _new_policy(self, max_rows, init_seed):
+        return D.DeviceGaussPolicy(self.OD, self.E, max_rows=max_rows, hidden=self.hidden, seed=init_seed)
+
+    def _new_buffers(self, N, dev):
+        f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        b = dict(obs=f(N, self.OD), act=f(N, self.E), logp=f(N), val=f(N), rew=torch.empty(N, dtype=torch.float64, device=dev))
+        if self.algo == D.DeviceGaussPolicy.PPO:
+            b['head'] = f(N, 2 * self.E)
+        return b
+
+    def params(self):
+        self._settle()
+        return self.policy.params()
+
+    def close(self):
+        _Evaluated.close(self)
+
+    def rollout(self):
+        B, T, R = self.B, self.T, self.R
+        b = self.buf
+        actor = self.actor if self.actor is not None else self.policy          # IMPALA samples from the (possibly stale) actor
+        for r in range(R):
+            obs = self.env.reset()
+            for t in range(T):
+                obs_t = obs['obs'] if isinstance(obs, dict) else obs
+                sl = slice((r * T + t) * B, (r * T + t + 1) * B)
+                b['obs'][sl] = obs_t
+                # the draw, its log-prob, the value (and PPO's head) go straight into the rollout buffers; the env gets the clipped draw
+                actor.act(b['obs'][sl], seed=self.seed, step=self._rollouts * T + t,
+                          out=(b['act'][sl], self._env_act, b['logp'][sl], b['val'][sl], b['head'][sl] if 'head' in b else None))
+                obs, reward, done, info = self.env.step(self._env_act)
+                b['rew'][sl] = reward
+            self._rollouts += 1
+        ret = _returns(b['rew'], R, T, B)
+        return ret, ret - b['val'], b['rew'].view(R, T, B).sum(dim=1).mean()
+
+    def _eval_batch(self, k):
+        """One episode batch on the mean action -> mean episode reward (device scalar)."""
+        obs = self.env.reset(reset_file=True) if k == 0 else self.env.reset()
+        total = torch.zeros(self.B, dtype=torch.float64, device=self.device)
+        for t in range(self.T):
+            obs_t = (obs['obs'] if isinstance(obs, dict) else obs).contiguous()
+            self.policy.act(obs_t, deterministic=True, out=self._eval)
+            obs, reward, done, info = self.env.step(self._eval[1])
+            total += reward
+        return total.mean()
 
 
 class _ReplayTrainer(_Evaluated):
