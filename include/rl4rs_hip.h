@@ -819,6 +819,11 @@ int rl4rs_policy_dqn_loss_grad(rl4rs_policy* pol, const float* target_params_dev
  * [N, action_size].  A row that allows nothing returns action 0. */
 int rl4rs_policy_greedy(rl4rs_policy* pol, int32_t N, const float* obs_dev, const uint32_t* mask_bits_dev,
                         int32_t* actions_dev, float* q_dev, void* stream);
+/* forward exactly as rl4rs_policy_greedy's GEMM path (q_mode 1: the A logit columns; q_mode 0: all A + 1, column A = the value head),
+ * then rl4rs_ope_greedy_rows on the handle's own [N, A + 1] buffer: q_mode 1 -> q = masked Q of the chosen action (DQN),
+ * q_mode 0 -> q = V(s) (A2C / PPO / PG / IMPALA: 'vf_preds').  N <= max_rows; any shape rl4rs_policy_create admits. */
+int rl4rs_policy_ope_step(rl4rs_policy* pol, int32_t N, const float* obs_dev, const uint32_t* mask_bits_dev, const int32_t* logged_dev,
+                          int32_t q_mode, int32_t* actions_dev, double* pi_dev, double* q_dev, float* masked_out_dev, void* stream);
 /* rl4rs_policy_adam_step with tf.clip_by_norm applied to EACH variable (W1, b1, W2e, b2e) by its own norm - RLlib DQN's
  * minimize_and_clip (grad_clip 40) - instead of the global norm; var_clip <= 0: no clipping. */
 int rl4rs_policy_adam_step_clip_by_var(rl4rs_policy* pol, const float* grad_dev, float lr, float beta1, float beta2,
@@ -1540,6 +1545,9 @@ int rl4rs_ope_record_q(rl4rs_ope* h, int32_t t, const float* scores_dev, int32_t
                        void* stream);
 /* Device address of one column's [T, B] float64 log (T, B of the last rl4rs_ope_begin). */
 int rl4rs_ope_log(rl4rs_ope* h, int32_t col, double** dev_out, int64_t* n_out);
+/* Step t of column col was written through rl4rs_ope_log's address (+ t * B) by the caller - rl4rs_ope_greedy_rows /
+ * rl4rs_policy_ope_step take such addresses as pi_dev and q_dev: rl4rs_ope_estimate counts it as recorded.  Host state only. */
+int rl4rs_ope_mark_recorded(rl4rs_ope* h, int32_t t, int32_t col);
 
 /* One epoch's estimators from the log, assembled like offline_evaluation.py:38-67: the per-episode products of probs * 100, the
  * summed logged reward, the summed simulator reward as DR's action_rhat_rewards and the per-episode mean Q as its
@@ -1556,6 +1564,21 @@ int rl4rs_ope_episode_stats(int32_t B, const double* rewards_dev, const double* 
 int rl4rs_ope_step_stats(int32_t B, int32_t T, const double* step_rewards_dev, const double* policy_prob_dev,
                          const double* behavior_prob_dev, const double* rhat_dev, const double* state_dev, double gamma,
                          double* stats_host, void* stream);
+
+/* One OPE step of a score-matrix policy: what ope_eval needs of the evaluated policy per episode (offline_evaluation.py:24-29,
+ * policy_model.py:43-87, RLlib-trainer branch), one launch, no handle.
+ * One wave per row, four rows per workgroup.  m[c] = scores[b, c], or for a column the mask forbids
+ *   mask_set 0: scores[b, c] + (-3.4028235e38f) in float32 (the mask-model rule, as k_greedy_rows / rl4rs_policy_evaluate form it)
+ *   mask_set 1: -3.4028235e38f                              (the Rainbow rule)
+ * actions[b] = first maximum of m (a row that allows nothing: 0)
+ * pi[b]      = exp(m[l] - max) / sum_c exp(m[c] - max) in float64, l = logged[b]; l outside [0, A): NaN
+ * q[b]       = value_dev ? (double)value_dev[b * value_ld] : (double)m[actions[b]]
+ * masked_out (optional, [N, A] float32) receives m: what the tests recompute everything from.
+ * mask_bits_dev (optional): (A + 31) / 32 words per row, bit c of a row = column c is allowed.  pi_dev, q_dev, logged_dev are
+ * optional (pi_dev needs logged_dev).  A row of up to 4092 columns is read from memory once; a longer one twice. */
+int rl4rs_ope_greedy_rows(int32_t N, const float* scores_dev, int32_t A, int64_t ld, const uint32_t* mask_bits_dev, int32_t mask_set,
+                          const int32_t* logged_dev, const float* value_dev, int64_t value_ld, int32_t* actions_dev,
+                          double* pi_dev, double* q_dev, float* masked_out_dev, void* stream);
 
 /* ---- On-device Exact-K (rl4rs/nets/exact_k, script/exact_k_train.py): the pointer-network slate generator and its critic ----
  *

@@ -370,6 +370,7 @@ SIGNATURES = {
     'rl4rs_ope_record_column': (_I, [_P, _I32, _I32, _P, _I32, _P]),
     'rl4rs_ope_record_q': (_I, [_P, _I32, _P, _I32, _I64, _P, _P]),
     'rl4rs_ope_log': (_I, [_P, _I32, C.POINTER(_P), C.POINTER(_I64)]),
+    'rl4rs_ope_mark_recorded': (_I, [_P, _I32, _I32]),
     'rl4rs_ope_estimate': (_I, [_P, C.c_double, C.POINTER(C.c_double), _P]),
     'rl4rs_ope_episode_stats': (_I, [_I32, _P, _P, _P, _P, _P, C.POINTER(C.c_double), _P]),
     'rl4rs_ope_step_stats': (_I, [_I32, _I32, _P, _P, _P, _P, _P, C.c_double, C.POINTER(C.c_double), _P]),
@@ -393,6 +394,8 @@ SIGNATURES = {
     'rl4rs_policy_dqn_loss_grad': (_I, [_P, _P, _I32, _P, _P, _P, _P, _P, _P, _P, C.c_float, _I32, _P, _P, _P, _P, _P]),
     'rl4rs_policy_greedy': (_I, [_P, _I32, _P, _P, _P, _P, _P]),
     'rl4rs_policy_adam_step_clip_by_var': (_I, [_P, _P, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _P]),
+    'rl4rs_policy_ope_step': (_I, [_P, _I32, _P, _P, _P, _I32, _P, _P, _P, _P, _P]),
+    'rl4rs_ope_greedy_rows': (_I, [_I32, _P, _I32, _I64, _P, _I32, _P, _P, _I64, _P, _P, _P, _P, _P]),
     'rl4rs_distq_param_count': (_I64, [C.POINTER(DistqCfg)]),
     'rl4rs_distq_create': (_I, [C.POINTER(DistqCfg), _P, _P, C.POINTER(_P)]),
     'rl4rs_distq_destroy': (_I, [_P]),

@@ -699,6 +699,24 @@ int rl4rs_policy_greedy(rl4rs_policy* p, int32_t N, const float* obs, const uint
     return RL4RS_OK;
 }
 
+int rl4rs_policy_ope_step(rl4rs_policy* p, int32_t N, const float* obs, const uint32_t* mask_bits, const int32_t* logged, int32_t q_mode,
+                          int32_t* actions, double* pi, double* q, float* masked_out, void* stream) {
+    RL4RS_REQUIRE(p && obs && actions && N > 0, "policy_ope_step: bad argument");
+    RL4RS_REQUIRE(q_mode == 0 || q_mode == 1, "policy_ope_step: q_mode %d is neither 0 (value head) nor 1 (masked Q)", q_mode);
+    RL4RS_REQUIRE(N <= p->max_rows, "policy_ope_step: %d rows exceed the handle's max_rows %d", N, p->max_rows);
+    hipStream_t st = (hipStream_t)stream;
+    const PolDims& d = p->d;
+    const float* W1 = p->opt.params;
+    const float* b1 = W1 + (size_t)d.OD * d.HID;
+    const float* W2 = b1 + d.HID;
+    const float* b2 = W2 + (size_t)d.HID * d.AE;
+    int rc;
+    if ((rc = launch_gemm_f32(obs, d.OD, W1, d.HID, b1, p->H, d.HID, N, d.HID, d.OD, ACT_TANH, st))) return rc;
+    if ((rc = launch_gemm_f32(p->H, d.HID, W2, d.AE, b2, p->dOut, d.AE, N, q_mode ? d.A : d.AE, d.HID, ACT_NONE, st))) return rc;
+    return rl4rs_ope_greedy_rows(N, p->dOut, d.A, d.AE, mask_bits, 0, logged, q_mode ? nullptr : p->dOut + d.A, d.AE, actions, pi, q,
+                                 masked_out, stream);
+}
+
 int rl4rs_policy_adam_step_clip_by_var(rl4rs_policy* p, const float* grad_dev, float lr, float beta1, float beta2, float eps,
                                        float var_clip, void* stream) {
     RL4RS_REQUIRE(p && grad_dev, "policy_adam_step_clip_by_var: null argument");

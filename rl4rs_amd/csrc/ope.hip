@@ -231,6 +231,80 @@ __global__ __launch_bounds__(OPE_BLOCK) void k_ope_propensity(const float* __res
     }
 }
 
+// One OPE step of a score-matrix policy (rl4rs_ope_greedy_rows): masked row m, its first maximum, softmax(m)[logged] in float64 and
+// the value, a wave per row.  STAGED: the row is read from memory once - a scalar head up to the row's first 16-byte boundary, float4
+// chunks, a scalar tail - into the wave's share of LDS, element c at s[mis + c] with mis = the row's misalignment in floats, so a
+// chunk lands on a 16-byte LDS slot whatever the row stride is; the only cross-lane hand-off is that staging (one barrier).  Every
+// later pass walks c = lane, lane + 64, ...: a lane re-reads what it wrote itself.  !STAGED (a row beyond the LDS share): the
+// same passes recompute m from memory.  Sums: lane (increasing c), then the shuffle tree of wave_sum; no atomics.
+constexpr int OPE_ROW_LDS_FLOATS = 4096;          // per wave: 4 waves x 16 KB = the 64 KB a workgroup gets without asking
+
+__device__ __forceinline__ float ope_masked(float v, const uint32_t* mrow, int c, int mask_set) {
+    if (mrow && !((mrow[c >> 5] >> (c & 31)) & 1u)) v = mask_set ? -3.4028235e38f : v + (-3.4028235e38f);
+    return v;
+}
+
+template <bool STAGED>
+__global__ __launch_bounds__(OPE_BLOCK) void k_ope_greedy_rows(int N, const float* __restrict__ scores, int A, int64_t ld, int stride,
+                                                               const uint32_t* __restrict__ mask, int mask_set,
+                                                               const int32_t* __restrict__ logged, const float* __restrict__ value,
+                                                               int64_t value_ld, int32_t* __restrict__ actions,
+                                                               double* __restrict__ pi, double* __restrict__ q,
+                                                               float* __restrict__ masked_out) {
+    extern __shared__ __attribute__((aligned(16))) float ope_lds[];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int b = blockIdx.x * OPE_WAVES + wave;
+    const bool live = b < N;                         // (no early return: the staging barrier is the workgroup's)
+    const float* row = scores + (int64_t)(live ? b : 0) * ld;
+    const uint32_t* mrow = mask ? mask + (int64_t)(live ? b : 0) * ((A + 31) >> 5) : nullptr;
+    float* s = ope_lds;
+    if (STAGED) {
+        const int mis = (int)((reinterpret_cast<uintptr_t>(row) >> 2) & 3);
+        s = ope_lds + (size_t)wave * stride + mis;
+        if (live) {
+            const int head = min(A, (4 - mis) & 3), nchunk = (A - head) >> 2, tail = head + 4 * nchunk;
+            if (lane < head) s[lane] = row[lane];
+            for (int k = lane; k < nchunk; k += 64)
+                *reinterpret_cast<float4*>(s + head + 4 * k) = *reinterpret_cast<const float4*>(row + head + 4 * k);
+            if (tail + lane < A) s[tail + lane] = row[tail + lane];
+        }
+        __syncthreads();
+    }
+    if (!live) return;
+    // pass 1: the masked row (kept in LDS, written out on request), its first maximum
+    float best = 0.f;
+    int best_a = 0x7fffffff;
+    for (int c = lane; c < A; c += 64) {
+        const float v = ope_masked(STAGED ? s[c] : row[c], mrow, c, mask_set);
+        if (STAGED) s[c] = v;
+        if (masked_out) masked_out[(int64_t)b * A + c] = v;
+        if (best_a == 0x7fffffff || v > best) { best = v; best_a = c; }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const float ob = __shfl_xor(best, off, 64);
+        const int oa = __shfl_xor(best_a, off, 64);
+        if (oa != 0x7fffffff && (best_a == 0x7fffffff || ob > best || (ob == best && oa < best_a))) { best = ob; best_a = oa; }
+    }
+    // pass 2: sum_c exp(m[c] - max) in float64, and m[l] from the lane that holds it
+    const int l = logged ? logged[b] : -1;
+    const bool ok = l >= 0 && l < A;
+    double sum = 0.0;
+    float ml = 0.f;
+    for (int c = lane; c < A; c += 64) {
+        const float v = STAGED ? s[c] : ope_masked(row[c], mrow, c, mask_set);
+        if (c == l) ml = v;
+        sum += exp((double)v - (double)best);
+    }
+    sum = wave_sum(sum);
+    ml = __shfl(ml, ok ? (l & 63) : 0, 64);
+    if (lane == 0) {
+        actions[b] = best_a;
+        if (pi) pi[b] = ok ? exp((double)ml - (double)best) / sum : __longlong_as_double(0x7ff8000000000000LL);
+        if (q) q[b] = value ? (double)value[(int64_t)b * value_ld] : (double)best;
+    }
+}
+
 template <typename T>
 __global__ void k_ope_column(const T* __restrict__ src, int B, double* __restrict__ out) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -508,10 +582,39 @@ int rl4rs_ope_record_column(rl4rs_ope* h, int32_t t, int32_t col, const void* sr
     return RL4RS_OK;
 }
 
+int rl4rs_ope_greedy_rows(int32_t N, const float* scores_dev, int32_t A, int64_t ld, const uint32_t* mask_bits_dev, int32_t mask_set,
+                          const int32_t* logged_dev, const float* value_dev, int64_t value_ld, int32_t* actions_dev,
+                          double* pi_dev, double* q_dev, float* masked_out_dev, void* stream) {
+    RL4RS_REQUIRE(N >= 1 && scores_dev && actions_dev && A >= 1 && ld >= A, "ope_greedy_rows: bad scores (N %d, A %d, ld %lld)", N, A,
+                  (long long)ld);
+    RL4RS_REQUIRE(mask_set == 0 || mask_set == 1, "ope_greedy_rows: mask_set %d is neither 0 (add) nor 1 (set)", mask_set);
+    RL4RS_REQUIRE(!pi_dev || logged_dev, "ope_greedy_rows: pi needs the logged actions");
+    RL4RS_REQUIRE(!value_dev || value_ld >= 1, "ope_greedy_rows: value stride %lld < 1", (long long)value_ld);
+    RL4RS_REQUIRE(reinterpret_cast<uintptr_t>(scores_dev) % 4 == 0, "ope_greedy_rows: scores not aligned to a float");
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid(ceil_div(N, OPE_WAVES)), block(OPE_BLOCK);
+    const int stride = (A + 3) / 4 * 4 + 4;              // floats of one wave's LDS share: the row behind its misalignment (<= 3)
+    if (stride <= OPE_ROW_LDS_FLOATS)
+        hipLaunchKernelGGL(k_ope_greedy_rows<true>, grid, block, (size_t)OPE_WAVES * stride * sizeof(float), st, N, scores_dev, A, ld, stride,
+                           mask_bits_dev, mask_set, logged_dev, value_dev, value_ld, actions_dev, pi_dev, q_dev, masked_out_dev);
+    else
+        hipLaunchKernelGGL(k_ope_greedy_rows<false>, grid, block, 0, st, N, scores_dev, A, ld, 0, mask_bits_dev, mask_set, logged_dev,
+                           value_dev, value_ld, actions_dev, pi_dev, q_dev, masked_out_dev);
+    RL4RS_LAUNCH_CHECK();
+    return RL4RS_OK;
+}
+
 int rl4rs_ope_log(rl4rs_ope* h, int32_t col, double** dev_out, int64_t* n_out) {
     RL4RS_REQUIRE(h && dev_out && n_out && col >= 0 && col < RL4RS_OPE_N_COLS, "ope_log: bad argument");
     *dev_out = h->col(col, 0);
     *n_out = (int64_t)h->T * h->B;
+    return RL4RS_OK;
+}
+
+int rl4rs_ope_mark_recorded(rl4rs_ope* h, int32_t t, int32_t col) {
+    OPE_STEP_CHECK("ope_mark_recorded");
+    RL4RS_REQUIRE(col >= 0 && col < RL4RS_OPE_N_COLS, "ope_mark_recorded: bad column %d", col);
+    h->seen[col][t] = 1;
     return RL4RS_OK;
 }
 

@@ -1357,6 +1357,47 @@ def vtrace(behaviour_logp, target_logp, values, rewards, bootstrap_value=None, d
     return vs, pg, stats
 
 
+def _ope_outputs(N, A, device, logged, pi, q, actions_out, masked_out):
+    """The outputs of one OPE step: fresh tensors, the caller's, or (pi / q) a device address -> (actions, pi, q, pi pointer, q pointer)."""
+    assert logged is None or (logged.dtype == torch.int32 and logged.shape == (N,) and logged.is_contiguous() and logged.is_cuda)
+    a = actions_out if actions_out is not None else torch.empty(N, dtype=torch.int32, device=device)
+    assert a.dtype == torch.int32 and a.shape == (N,) and a.is_contiguous() and a.is_cuda
+    assert masked_out is None or (masked_out.dtype == torch.float32 and tuple(masked_out.shape) == (N, A) and masked_out.is_contiguous()
+                                  and masked_out.is_cuda)
+    ptrs = []
+    cols = []
+    for col, needed in ((pi, logged is not None), (q, True)):
+        if isinstance(col, int):
+            ptrs.append(C.c_void_p(col))
+            cols.append(None)
+            continue
+        if col is None and needed:
+            col = torch.empty(N, dtype=torch.float64, device=device)
+        assert col is None or (col.dtype == torch.float64 and col.shape == (N,) and col.is_contiguous() and col.is_cuda)
+        ptrs.append(_ptr(col))
+        cols.append(col)
+    return a, cols[0], cols[1], ptrs[0], ptrs[1]
+
+
+def ope_greedy_rows(scores, logged, mask_bits=None, mask_set=0, value=None, pi=None, q=None, actions_out=None, masked_out=None):
+    """One OPE step of a score matrix (rl4rs_ope_greedy_rows): ``scores`` float32 [N, A] device tensor whose rows may be a view of a
+    wider matrix (unit column stride), ``mask_bits`` int32 [N, (A + 31) // 32] or None, ``mask_set`` 0 (a forbidden column gets
+    -3.4e38 added) or 1 (it is set to -3.4e38), ``value`` float32 [N] (any stride) or None -> (first-maximum actions int32 [N], pi
+    float64 [N] = softmax(masked row)[logged], q float64 [N] = value, or the masked score of the chosen action).  ``pi`` / ``q`` /
+    ``actions_out`` / ``masked_out`` as in ``DevicePolicy.ope_step``."""
+    assert scores.is_cuda and scores.dtype == torch.float32 and scores.dim() == 2 and scores.stride(1) == 1
+    N, A = scores.shape
+    W = (A + 31) // 32
+    assert mask_bits is None or (mask_bits.dtype == torch.int32 and tuple(mask_bits.shape) == (N, W) and mask_bits.is_contiguous())
+    assert value is None or (value.is_cuda and value.dtype == torch.float32 and value.shape == (N,))
+    a, pi, q, pi_p, q_p = _ope_outputs(N, A, scores.device, logged, pi, q, actions_out, masked_out)
+    with torch.cuda.device(scores.device):
+        check(_lib.load().rl4rs_ope_greedy_rows(N, _ptr(scores), A, scores.stride(0) if N > 1 else A, _ptr(mask_bits), int(mask_set),
+                                                _ptr(logged), _ptr(value), value.stride(0) if value is not None and N > 1 else 1, _ptr(a),
+                                                pi_p, q_p, _ptr(masked_out), _stream()))
+    return a, pi, q
+
+
 class DevicePolicy(_FlatNet):
     """rl4rs_policy handle: action-masked policy net (rllib_mask_model.py:7-64) with flat parameters."""
     A2C, PPO = 0, 1
@@ -1550,6 +1591,19 @@ class DevicePolicy(_FlatNet):
         q = torch.empty((N, self.action_size), dtype=torch.float32, device=self.device) if want_q else None
         check(self.lib.rl4rs_policy_greedy(self.h, N, _ptr(obs), _ptr(m), _ptr(a), _ptr(q), _stream()))
         return a, q
+
+    def ope_step(self, obs, mask_bits, logged, q_mode, pi=None, q=None, actions_out=None, masked_out=None):
+        """One OPE step (rl4rs_policy_ope_step): two GEMMs and one row launch -> (greedy actions int32 [N], pi float64 [N] =
+        softmax(masked logits)[logged], q float64 [N] = the masked Q of the chosen action (``q_mode`` 1) or the value head (0)).
+        ``pi`` / ``q``: float64 [N] tensors to fill, or device addresses (a step of an ``OpeLog`` column; nothing is returned for
+        them); ``masked_out``: float32 [N, A] to receive the masked row."""
+        N = obs.shape[0]
+        assert obs.dtype == torch.float32 and obs.shape == (N, self.obs_dim) and obs.is_contiguous()
+        m = self._mask(mask_bits, N)
+        a, pi, q, pi_p, q_p = _ope_outputs(N, self.action_size, self.device, logged, pi, q, actions_out, masked_out)
+        check(self.lib.rl4rs_policy_ope_step(self.h, N, _ptr(obs), _ptr(m), _ptr(logged), int(q_mode), _ptr(a), pi_p, q_p, _ptr(masked_out),
+                                             _stream()))
+        return a, pi, q
 
     def adam_step_clip_by_var(self, grad, lr=5e-4, beta1=0.9, beta2=0.999, eps=1e-8, var_clip=40.0):
         """Adam with every variable (W1, b1, W2e, b2e) clipped by its own norm (rl4rs_policy_adam_step_clip_by_var)."""

@@ -72,6 +72,39 @@ class OpeLog(object):
         s, a = self._scores(scores, action)
         check(self.lib.rl4rs_ope_record_q(self.h, int(t), D._ptr(s), s.shape[1], s.stride(0), D._ptr(a), self._stream()))
 
+    def _step_address(self, t, col):
+        """device address of step ``t`` of one column (rl4rs_ope_log + t * B)"""
+        if not 0 <= int(t) < self.T:
+            raise ValueError('step %d outside the epoch\'s [0, %d)' % (t, self.T))
+        p, n = C.c_void_p(), C.c_int64()
+        check(self.lib.rl4rs_ope_log(self.h, OPE_COLS[col], C.byref(p), C.byref(n)))
+        return int(p.value) + int(t) * self.B * 8
+
+    def _mark(self, t):
+        for col in ('pi', 'q'):
+            check(self.lib.rl4rs_ope_mark_recorded(self.h, int(t), OPE_COLS[col]))
+
+    def record_step(self, t, policy_handle, obs, mask_bits, logged_action, q_mode, actions_out=None, masked_out=None):
+        """One OPE step of a mask-model handle (``DevicePolicy.ope_step``: two GEMMs and one row launch): writes pi[t] =
+        softmax(masked logits)[logged_action] and q[t] (``q_mode`` 1: the masked Q of the greedy action, 0: the value head) in place
+        and returns the greedy actions (int32 [B] device tensor)."""
+        a = D.to_device_async(logged_action, torch.int32, self.device).reshape(-1)
+        if obs.shape[0] != self.B or a.shape[0] != self.B:
+            raise ValueError('observations %r / actions %r do not fit the epoch\'s batch size %d' % (tuple(obs.shape), tuple(a.shape), self.B))
+        out = policy_handle.ope_step(obs, mask_bits, a, q_mode, pi=self._step_address(t, 'pi'), q=self._step_address(t, 'q'),
+                                     actions_out=actions_out, masked_out=masked_out)[0]
+        self._mark(t)
+        return out
+
+    def record_scores_step(self, t, scores, logged_action, mask_bits=None, mask_set=0, value=None, actions_out=None, masked_out=None):
+        """The same step from a score matrix (``device.ope_greedy_rows``): ``scores`` float32 [B, A] (rows of a wider device matrix are
+        read in place), ``value`` float32 [B] or None (q[t] is then the masked score of the greedy action)."""
+        s, a = self._scores(scores, logged_action)
+        out = D.ope_greedy_rows(s, a, mask_bits=mask_bits, mask_set=mask_set, value=value, pi=self._step_address(t, 'pi'),
+                                q=self._step_address(t, 'q'), actions_out=actions_out, masked_out=masked_out)[0]
+        self._mark(t)
+        return out
+
     def record_column(self, t, col, values):
         """one [B] column of step ``t`` from a device tensor (float32 / float64 as they are) or host data"""
         if _is_zero_list(values, self.B):
@@ -130,10 +163,12 @@ def _q_learner(policy):
 
 def ope_eval(config, eval_env, algo, sample_model=None, on_epoch=None):
     """script/offline_evaluation.py:9-73.  ``eval_env``: anything with ``reset`` / ``step`` / ``offline_action`` /
-    ``offline_reward`` / ``samples.records``; ``algo``: a learner of ``offline_rl`` or a ``policy_model`` (anything with
+    ``offline_reward`` / ``samples.records``; ``algo``: a learner of ``offline_rl``, an online trainer of ``train`` (``Trainer``,
+    ``DQNTrainer``, ``RainbowTrainer`` - the ope stage of modelfree_train.py:498-514; wrapped in ``policy_model(algo, config,
+    env=eval_env)``, and with a device observation every step is one ``OpeLog.record_step``) or a ``policy_model`` (anything with
     ``predict_with_mask`` / ``action_probs`` / ``predict_q``); ``sample_model``: a ``behavior_model`` (anything with
-    ``action_probs(record, action, layer, page=)``; one whose ``takes_observation`` is true is handed the observation instead of
-    ``eval_env.samples.records``) or None.
+    ``action_probs(record, action, layer, page=)``; one whose ``takes_observation`` is true is handed the observation the policy's network
+    receives (``obs['obs']`` of a mask-mode dict) instead of ``eval_env.samples.records``) or None.
 
     Prints the reference's lines and returns what it only prints: ``dict(metrics [epoch, 4, 2] (IS, DR, WIPS, SeqDR) x (value,
     second), mean, std (over the epochs), episode_reward (mean simulated episode reward), stats (per epoch, every statistic))``.
@@ -146,14 +181,19 @@ def ope_eval(config, eval_env, algo, sample_model=None, on_epoch=None):
     if sample_model is not None and isinstance(learner, R.DiscreteBC):
         raise ValueError("ope_eval: DiscreteBC has no predict_value, so the evaluated policy's Q values (DR / SeqDR state rewards, "
                          "offline_evaluation.py:29) do not exist; evaluate a DiscreteBCQ / DiscreteCQL, or pass sample_model=None")
+    from . import train as T
     if hasattr(algo, 'predict_with_mask'):
         policy = algo
+    elif isinstance(algo, (T.Trainer, T.DQNTrainer)):
+        # the model-free driver's ope stage (modelfree_train.py:498-514): the trainer's greedy policy under the env's own mask
+        policy = policy_model(algo, config, env=eval_env)
     else:
         env_ok = hasattr(getattr(eval_env, 'samples', None), '_live')
         policy = policy_model(algo, config, env=eval_env if env_ok and 'iteminfo_file' not in config else None)
     epoch, batch_size, max_steps = int(config['epoch']), int(config['batch_size']), int(config['max_steps'])
     page_items = config.get('page_items', 9)
     qlearner = _q_learner(policy)
+    scores = getattr(policy, '_scores', None) if isinstance(policy, policy_model) else None      # an online trainer's
     log = OpeLog(batch_size, max_steps)
     metrics, stats = [], []
     try:
@@ -164,23 +204,31 @@ def ope_eval(config, eval_env, algo, sample_model=None, on_epoch=None):
             actions, off_actions = [], []
             for j in range(max_steps):
                 fused = qlearner is not None and sample_model is not None and isinstance(obs, torch.Tensor) and obs.is_cuda
-                if fused:
+                obs_2d = obs['obs'] if isinstance(obs, dict) else obs           # what the policy's network receives
+                step = (scores is not None and sample_model is not None and isinstance(obs_2d, torch.Tensor) and obs_2d.is_cuda
+                        and obs_2d.shape[0] <= scores.handle.max_rows)
+                if step:
+                    # an online trainer: its forward, the masked arg-max, pi and q of this step are one record_step
+                    off_action = eval_env.offline_action
+                    action = scores.record_step(log, j, *scores.split(obs), off_action).to(torch.int64)
+                elif fused:
                     # one forward of the Q network serves the masked arg-max, pi (fused softmax gather) and Q(s, a)
                     x = policy._obs(obs)
                     qmat = policy._chunks(qlearner.q, x)
                     action = policy._handle().predict_with_mask(torch.softmax(qmat, dim=1), x[:, -policy.mask_size:]).to(torch.int64)
                 else:
                     action = policy.predict_with_mask(obs)
-                off_action = eval_env.offline_action
+                if not step:
+                    off_action = eval_env.offline_action
                 if sample_model is not None:
                     if fused:
                         log.record_policy(j, qmat, off_action, logits=True)
                         log.record_q(j, qmat, action)
-                    else:
+                    elif not step:
                         log.record_policy(j, policy.action_probs(obs), off_action, logits=False)
                         log.record_column(j, 'q', policy.predict_q(obs, action))
                     layer, page = j // 3 + 1, j // page_items
-                    record = obs if getattr(sample_model, 'takes_observation', False) else eval_env.samples.records
+                    record = obs_2d if getattr(sample_model, 'takes_observation', False) else eval_env.samples.records
                     if hasattr(sample_model, 'record_into'):
                         sample_model.record_into(log, j, record, off_action, layer)
                     else:

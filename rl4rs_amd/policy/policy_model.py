@@ -11,8 +11,15 @@
   masked by the rule the observation tail encodes (previous actions | cur_step -> location_mask row, chosen items, special items;
   :22-33, fill value -2**15) and arg-maxed - on the device (``rl4rs_env_predict_with_mask``), first maximum like numpy.
 Observations and results stay device tensors when they come in as device tensors; numpy in -> numpy out like the reference.
-The RLlib-trainer branch of the reference (``compute_actions``) has no counterpart here: the on-device trainers act through
-``train.Trainer``."""
+
+The RLlib-trainer branch of the reference (``compute_actions``, policy_model.py:43-87) is ``policy_model(trainer, config, env=env)``
+over ``train.Trainer`` (A2C / PPO / PG / IMPALA), ``train.DQNTrainer`` and ``train.RainbowTrainer``:
+* ``predict`` = ``predict_with_mask`` = the greedy action (first maximum of the masked score row);
+* ``action_probs`` = the float32 softmax of that row - logits for the on-policy learners, Q for DQN / RAINBOW;
+* ``predict_q(obs, action)`` = ``Q[range, action]`` for DQN / RAINBOW, the value head otherwise.
+The mask is the ``'action_mask'`` of a ``support_rllib_mask`` dict observation (packed on the device) or, for a plain observation,
+the packed observation mask of ``env`` (the env being stepped); ``RainbowTrainer(masked=False)`` passes none.  The continuous
+trainers go through ``predict`` only."""
 import numpy as np
 import torch
 
@@ -20,8 +27,86 @@ from .. import device as D
 from .. import offline_rl as R
 
 
+def pack_mask_bits(mask, device):
+    """A dense action mask [B, A] (non-zero = allowed; numpy or tensor) -> the packed int32 [B, (A + 31) // 32] words the policy
+    handles take (bit c of a row = column c), packed on the device."""
+    m = D._dev_tensor(mask if isinstance(mask, torch.Tensor) else np.asarray(mask), torch.int64, device)
+    m = (m != 0).to(torch.int64)
+    B, A = m.shape
+    W = (A + 31) // 32
+    if W * 32 != A:
+        m = torch.nn.functional.pad(m, (0, W * 32 - A))
+    w = (m.view(B, W, 32) << torch.arange(32, device=m.device, dtype=torch.int64)).sum(dim=2)
+    return torch.where(w >= 2 ** 31, w - 2 ** 32, w).to(torch.int32).contiguous()
+
+
+class _TrainerScores(object):
+    """The RLlib-trainer branch (policy_model.py:43-87: ``compute_actions(explore=False)``, ``action_dist_inputs``, ``q_values`` /
+    ``vf_preds``) over an online trainer of ``rl4rs_amd.train``: ``Trainer`` (A2C / PPO / PG / IMPALA - the learner's logits and value
+    head), ``DQNTrainer`` (the mask model's Q) and ``RainbowTrainer`` (the expected Q of the distributional net; ``masked=False``
+    passes no mask, as the reference does).  Everything is computed from the masked score row of the handle's greedy call."""
+
+    def __init__(self, trainer, env):
+        from .. import train as T
+        self.handle = trainer.policy                    # the learner (IMPALA's actor is a sampling device, not the policy)
+        self.has_q = isinstance(trainer, T.DQNTrainer)
+        self.use_mask = trainer.masked if isinstance(trainer, T.RainbowTrainer) else True
+        self.q_mode = 1 if self.has_q else 0
+        self.fused = isinstance(self.handle, D.DevicePolicy)      # rl4rs_policy_ope_step; Rainbow: greedy + rl4rs_ope_greedy_rows
+        self.env = env
+        self.device = self.handle.device
+
+    def split(self, obs):
+        """-> (x float32 [B, obs_dim] device tensor, packed mask or None)"""
+        if isinstance(obs, (list, tuple)) and len(obs) and isinstance(obs[0], dict):         # the host form: one dict per env
+            obs = {'obs': np.stack([np.asarray(o['obs']) for o in obs]), 'action_mask': np.stack([np.asarray(o['action_mask']) for o in obs])}
+        if isinstance(obs, dict):
+            x, dense = obs['obs'], obs['action_mask']
+        else:
+            x, dense = obs, None
+        x = D._dev_tensor(x if isinstance(x, torch.Tensor) else np.asarray(x), torch.float32, self.device)
+        if not self.use_mask:
+            return x, None
+        if dense is not None:
+            return x, pack_mask_bits(dense, self.device)
+        live = getattr(getattr(self.env, 'samples', None), '_live', None)
+        if live is None:
+            raise ValueError("policy_model: a plain observation carries no action mask - pass the support_rllib_mask dict observation "
+                             "(its 'action_mask') or env=<the env being stepped> (its packed observation mask is read on the device)")
+        bits = live().obs_mask_bits()
+        if bits.shape[0] != x.shape[0]:
+            raise ValueError('policy_model: %d observations, the env\'s mask has %d rows' % (x.shape[0], bits.shape[0]))
+        return x, bits
+
+    def _chunked(self, x, bits, fn):
+        n = self.handle.max_rows
+        parts = [fn(x[lo:lo + n].contiguous(), None if bits is None else bits[lo:lo + n].contiguous()) for lo in range(0, x.shape[0], n)]
+        if len(parts) == 1:
+            return parts[0]
+        return tuple(None if p[0] is None else torch.cat(p) for p in zip(*parts))
+
+    def greedy(self, x, bits, want_row=False):
+        """-> (actions int32 [B], masked score row float32 [B, A] or None)"""
+        return self._chunked(x, bits, lambda xs, bs: self.handle.greedy(xs, bs, want_q=want_row))
+
+    def value(self, x, bits):
+        """the value head, float32 [B] ('vf_preds')"""
+        return self._chunked(x, bits, lambda xs, bs: (self.handle.ope_step(xs, bs, None, 0)[2],))[0].to(torch.float32)
+
+    def record_step(self, log, t, x, bits, logged):
+        """pi[t], q[t] of ``log`` and the greedy action in one step (``ope_eval``'s device path); x: one chunk (B <= max_rows)."""
+        if self.fused:
+            return log.record_step(t, self.handle, x, bits, logged, self.q_mode)
+        a, row = self.handle.greedy(x, bits, want_q=True)
+        return log.record_scores_step(t, row, logged, actions_out=a)
+
+
 class policy_model(object):
     def __init__(self, model, config={}, env=None):
+        from .. import train as T
+        self._scores = None
+        if isinstance(model, (T.Trainer, T.DQNTrainer)) and not isinstance(model, T.ContiTrainer):
+            self._scores = _TrainerScores(model, env)
         self.policy = model
         self.config = config
         self.page_items = int(config.get('page_items', 9))
@@ -45,6 +130,7 @@ class policy_model(object):
 
     @staticmethod
     def _out(t, like):
+        like = like['obs'] if isinstance(like, dict) else like
         return t if isinstance(like, torch.Tensor) and like.is_cuda else t.cpu().numpy()
 
     def _obs(self, obs):
@@ -52,8 +138,8 @@ class policy_model(object):
         return D._dev_tensor(np.asarray(obs) if not isinstance(obs, torch.Tensor) else obs, torch.float32, dev)
 
     def predict_with_mask(self, obs):
-        if self.config.get('support_conti_env', False):
-            return self.predict(obs)
+        if self.config.get('support_conti_env', False) or self._scores is not None:
+            return self.predict(obs)             # (policy_model.py:18-19, :37-38, :46-48: the trainer's model masks its own scores)
         if not isinstance(self.policy, R._Learner):
             raise NotImplementedError('policy_model: %r is not one of this package\'s offline learners' % type(self.policy).__name__)
         x = self._obs(obs)
@@ -66,6 +152,8 @@ class policy_model(object):
         return self.policy.batch_size if isinstance(self.policy, R._Learner) else 1 << 30
 
     def predict(self, obs):
+        if self._scores is not None:
+            return self._out(self._scores.greedy(*self._scores.split(obs))[0].to(torch.int64), obs)
         x = self._obs(obs)
         n = self._rows()
         out = [self.policy.predict(x[lo:lo + n].contiguous()) for lo in range(0, x.shape[0], n)]
@@ -73,7 +161,14 @@ class policy_model(object):
 
     def predict_q(self, obs, action):
         """AlgoBase.predict_value(obs, action), back on the reward's own scale when the learner has a reward scaler
-        (policy_model.py:55-61; 'CQL-conti' is built with reward_scaler='standard', batchrl_trainer.py:91-107)."""
+        (policy_model.py:55-61; 'CQL-conti' is built with reward_scaler='standard', batchrl_trainer.py:91-107).  A trainer:
+        ``Q[range, action]`` of the masked Q row for DQN / RAINBOW, the value head otherwise (policy_model.py:62-73), float32."""
+        if self._scores is not None:
+            x, bits = self._scores.split(obs)
+            if not self._scores.has_q:
+                return self._out(self._scores.value(x, bits), obs)
+            a = D._dev_tensor(action if isinstance(action, torch.Tensor) else np.asarray(action), torch.int64, x.device).reshape(-1, 1)
+            return self._out(self._scores.greedy(x, bits, want_row=True)[1].gather(1, a).reshape(-1), obs)
         x = self._obs(obs)
         a = torch.as_tensor(np.asarray(action) if not isinstance(action, torch.Tensor) else action).to(x.device)
         n = self._rows()
@@ -98,4 +193,7 @@ class policy_model(object):
         return out[0] if len(out) == 1 else torch.cat(out)
 
     def action_probs(self, obs):
+        if self._scores is not None:
+            # float32 softmax of the masked score row: logits (A2C / PPO / PG / IMPALA) or Q (DQN / RAINBOW), policy_model.py:75-87
+            return self._out(torch.softmax(self._scores.greedy(*self._scores.split(obs), want_row=True)[1], dim=1), obs)
         return self._out(self._action_probs(self._obs(obs)), obs)

@@ -25,7 +25,8 @@ support_conti_env): OU exploration, a replay ring of float actions and the whole
 
 All of them hang on one skeleton: ``_DeferredStats`` (a train call's statistics are copied asynchronously and
 settled one call later), ``_OnPolicy`` (PPO's KL rule, for ``Trainer`` and ``RawStateTrainer`` only), ``_Evaluated`` (the evaluation
-frame) and ``_ReplayTrainer`` (rollout, push, updates of DQN / Rainbow / TD3); a trainer states what differs.
+frame) and ``_ReplayTrainer`` (rollout, push, updates of DQN / Rainbow / TD3); a trainer states what differs.  ``_Checkpoint`` gives
+``Trainer``, ``ContiTrainer``, ``DQNTrainer``, ``RainbowTrainer`` and ``TD3Trainer`` ``save(path)`` / ``restore(path)``.
 
 Data parallelism: every rank owns its own env batch and sampling stream (``seed`` differs per rank) and a replica
 of the policy that is IDENTICAL on all ranks: initialised from the shared ``init_seed``, rank 0's parameters / Adam state are
@@ -33,6 +34,7 @@ broadcast at construction, and every optimiser step applies the rank-mean gradie
 PPO: one per minibatch (synchronous SGD over the global minibatch of world_size x 256 samples): phase A + the gradient
 tiles of the persistent pass run as ONE launch per minibatch (rl4rs_policy_ppo_minibatch_grad), then all-reduce, then Adam.
 """
+import json
 import math
 
 import numpy as np
@@ -235,6 +237,127 @@ class _Evaluated(_DeferredStats):
         return float(total.item()) / n
 
 
+def _host_array(x):
+    return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+
+
+def _like(dst, arr):
+    """``arr`` as what ``dst`` takes: a tensor on ``dst``'s device for a device handle / tensor, the array itself for a host stand-in."""
+    dev = getattr(dst, 'device', None)
+    return torch.from_numpy(np.ascontiguousarray(arr)).to(dev) if isinstance(dev, torch.device) else arr
+
+
+class _Checkpoint(object):
+    """``save`` / ``restore`` of the online trainers - what ``trainer.save(...)`` and the ``trainer.restore(...)`` at the head of the
+    eval / eval_v2 / ope stages of script/modelfree_train.py (:434, :437-514) are to an RLlib trainer - in the style of
+    ``offline_rl._ModelIO``.  The file is one ``numpy.savez``:
+
+        class, algo_name, seed      the trainer's class name, ``algo_name`` ('' where a class has one algorithm), the constructor's seed
+                                    (recorded, NOT restored: ranks differ in it)
+        shapes                      json: handle name -> its shape tuple (``_HANDLE_DIMS`` and the parameter count)
+        net.<name>.params           flat float32 parameters of every handle (``_ckpt_nets``)
+        net.<name>.adam_m/_v/_t     Adam moments and step counter of the handles that are stepped (not of IMPALA's actor, not of a target)
+        tensor.<name>               device tensors restored in place (``_ckpt_tensors``: DQN / Rainbow's target, TD3's OU state)
+        host.<name>                 the host state that decides what the next call does (``_ckpt_host``)
+        extra.<name>                what a trainer adds (``_ckpt_extra``: TD3's noise generator)
+
+    A trainer states ``_ckpt_nets`` and ``_ckpt_host`` (and the optional hooks).  ``restore`` reads and checks the WHOLE file before it
+    touches the trainer: a class, algo or shape mismatch raises ``ValueError`` naming both sides, a truncated file raises what numpy /
+    zipfile raise, and in both cases nothing has changed.  Deviation from RLlib's checkpoint: none for the on-policy learners (their
+    continuation is bit-identical); the replay ring is not saved (RLlib 1.5.1 does not save it either) - it is EMPTY after
+    ``restore`` and refills from the next rollout, which ``train_iteration`` pushes before it samples."""
+
+    _HANDLE_DIMS = ('obs_dim', 'hidden', 'action_size', 'act_dim', 'out_dim', 'hidden1', 'hidden2', 'num_atoms', 'trunk', 'stream_hidden',
+                    'dueling', 'v_min', 'v_max', 'D', 'E', 'K', 'H1', 'H2', 'n_params')        # (D .. H2: DeviceAMLP's names)
+    _ckpt_host = ()
+
+    def _ckpt_nets(self):
+        """[(name, handle, has Adam state)]"""
+        raise NotImplementedError
+
+    def _ckpt_tensors(self):
+        return {}
+
+    def _ckpt_extra(self):
+        return {}
+
+    def _ckpt_set_extra(self, extra):
+        pass
+
+    def _ckpt_after_restore(self):
+        pass
+
+    def _ckpt_meta(self):
+        shapes = dict((name, [[d, getattr(net, d)] for d in self._HANDLE_DIMS if hasattr(net, d)]) for name, net, _ in self._ckpt_nets())
+        return {'class': type(self).__name__, 'algo_name': str(getattr(self, 'algo_name', getattr(self, 'algo', '')) or ''),
+                'shapes': json.dumps(shapes, sort_keys=True)}
+
+    def save(self, path):
+        """Write the checkpoint; every finished train call is in it (the deferred statistics are settled and the passes validated first)."""
+        self._settle()
+        for _, net, _ in self._ckpt_nets():
+            if hasattr(net, 'check_status'):
+                net.check_status()
+        blob = dict((k, np.array(v)) for k, v in self._ckpt_meta().items())
+        blob['seed'] = np.array(int(getattr(self, 'seed', 0)), dtype=np.int64)
+        for name, net, adam in self._ckpt_nets():
+            blob['net.%s.params' % name] = _host_array(net.params())
+            if adam:
+                m, v, t = net.adam_state()
+                blob['net.%s.adam_m' % name], blob['net.%s.adam_v' % name] = _host_array(m), _host_array(v)
+                blob['net.%s.adam_t' % name] = np.array(int(t), dtype=np.int64)
+        for name, t in self._ckpt_tensors().items():
+            blob['tensor.' + name] = _host_array(t)
+        for name in self._ckpt_host:
+            blob['host.' + name] = np.array(getattr(self, name))
+        for name, v in self._ckpt_extra().items():
+            blob['extra.' + name] = _host_array(v)
+        with open(path, 'wb') as f:
+            np.savez(f, **blob)
+
+    def restore(self, path):
+        """Load a checkpoint written by ``save`` of the same class, algorithm and shapes; under ``torch.distributed`` every rank's
+        replica is then made rank 0's (``sync_replicas``)."""
+        self._settle()
+        with np.load(path) as z:
+            blob = dict((k, z[k]) for k in z.files)                 # the whole file, before anything is touched
+        here = self._ckpt_meta()
+        for key, what in (('class', 'a %s'), ('algo_name', 'algo %r'), ('shapes', 'handles %s')):
+            there = str(blob[key])
+            if there != here[key]:
+                raise ValueError('%s holds %s, this trainer is %s' % (path, what % there, what % here[key]))
+        want = ['net.%s.%s' % (name, part) for name, _, adam in self._ckpt_nets()
+                for part in (('params', 'adam_m', 'adam_v', 'adam_t') if adam else ('params',))]
+        want += (['tensor.' + k for k in self._ckpt_tensors()] + ['host.' + k for k in self._ckpt_host] +
+                 ['extra.' + k for k in self._ckpt_extra()])
+        missing = [k for k in want if k not in blob]
+        if missing:
+            raise ValueError('%s lacks %s' % (path, ', '.join(missing)))
+        for name, net, _ in self._ckpt_nets():
+            n = _host_array(net.params()).size
+            if blob['net.%s.params' % name].size != n:
+                raise ValueError('%s: handle %r has %d parameters in the file, %d here' % (path, name, blob['net.%s.params' % name].size, n))
+        for name, t in self._ckpt_tensors().items():
+            if tuple(blob['tensor.' + name].shape) != tuple(t.shape):
+                raise ValueError('%s: %r is %r in the file, %r here' % (path, name, tuple(blob['tensor.' + name].shape), tuple(t.shape)))
+        for name, net, adam in self._ckpt_nets():
+            net.set_params(_like(net, blob['net.%s.params' % name]))
+            if adam:
+                net.set_adam_state(_like(net, blob['net.%s.adam_m' % name]), _like(net, blob['net.%s.adam_v' % name]),
+                                   int(blob['net.%s.adam_t' % name]))
+        for name, t in self._ckpt_tensors().items():
+            if isinstance(t, torch.Tensor):
+                t.copy_(torch.from_numpy(blob['tensor.' + name]))
+            else:
+                t[...] = blob['tensor.' + name]
+        for name in self._ckpt_host:
+            setattr(self, name, type(getattr(self, name))(blob['host.' + name].item()))
+        self._ckpt_set_extra(dict((k, blob['extra.' + k]) for k in self._ckpt_extra()))
+        self._ckpt_after_restore()
+        if rdist.collectives_active():
+            self.sync_replicas()
+
+
 class _OnPolicy(_DeferredStats):
     """What ``Trainer`` and ``RawStateTrainer`` share: the A2C / PPO statistics, PPO's adaptive KL coefficient and the statistics
     vector of a data-parallel PPO pass."""
@@ -281,7 +404,10 @@ class RawStateTrainer(_OnPolicy):
 
     Data-parallel: the gradient lives in the handle's flat buffer [cat_emb | seq_emb | dense layers]; the dense tail
     (~280 K floats) is mean-all-reduced in place, the two 100000 x 128 embedding tables exchange only the rows the minibatch
-    touched (``dist.allreduce_rows_mean_``)."""
+    touched (``dist.allreduce_rows_mean_``).
+
+    No ``save`` / ``restore`` and no ``evaluate``: ``_Checkpoint`` covers the trainers of the flat policy networks only (this one's two
+    100000 x 128 tables are 100 MB of parameters, three times that with Adam's moments)."""
 
     def __init__(self, env, algo='A2C', seed=0, lr=1e-4, minibatch=256, weights=None, init_seed=0, kl_coeff=0.2, kl_target=0.01):
         from .nets.rawpolicy import init_rawpolicy_weights
@@ -403,7 +529,7 @@ class RawStateTrainer(_OnPolicy):
         return self._submit_ppo_minibatches(mean_reward, stats, kl_sum, nmb * self.minibatch)
 
 
-class Trainer(_OnPolicy):
+class Trainer(_OnPolicy, _Evaluated, _Checkpoint):
     """A2C / PPO / PG / IMPALA on the action-masked FC policy (rllib_mask_model.py:7-64) over the zero-copy discrete-action env.
 
     seed       sampling stream of this rank (Gumbel noise, PPO shuffle): pass a different value per rank
@@ -427,7 +553,10 @@ class Trainer(_OnPolicy):
     vf_loss_coeff / entropy_coeff.  ``drop_last=True`` is RLlib's behaviour: the last step of every rollout only supplies the
     bootstrap value.  On SlateRecEnv-v0 the only reward arrives at that last step, so with drop_last=True THE LEARNER SEES NO REWARD
     (what the reference's IMPALA branch does as written); pass drop_last=False (all T steps, zero bootstrap) to train on it.
-    ``train_iteration`` adds rho_mean, rho_clipped_mean and vs_mean (means over the kept rows) to the A2C statistics."""
+    ``train_iteration`` adds rho_mean, rho_clipped_mean and vs_mean (means over the kept rows) to the A2C statistics.
+
+    ``evaluate(episodes, seed)`` (the driver's eval stage) plays the learner's greedy action under the env's mask; ``save(path)`` /
+    ``restore(path)`` are ``_Checkpoint``'s: a restored trainer with the same ``seed`` continues bit for bit."""
 
     DRIVER_LR = {'A2C': 1e-4, 'PPO': 1e-4, 'IMPALA': 1e-4, 'PG': 4e-4}          # script/modelfree_train.py:204,261,354,309
 
@@ -489,6 +618,14 @@ class Trainer(_OnPolicy):
             self.actor = self._new_policy(self.B, init_seed)
             self.actor.copy_params_from(self.policy)
             self._vt_stats = torch.empty(4, dtype=torch.float64, device=dev)
+        self.device = dev
+        self._owned = (self.policy,) + ((self.actor,) if self.actor is not None else ())
+        self._eval_act = torch.empty(self.B, dtype=torch.int32, device=dev)
+
+    _ckpt_host = ('iteration', '_rollouts', 'num_updates', '_kl_coeff')
+
+    def _ckpt_nets(self):
+        return [('policy', self.policy, True)] + ([('actor', self.actor, False)] if self.actor is not None else [])
 
     # ---- what ContiTrainer states differently: the env it takes, the policy handle, the rollout columns (and ``rollout``)
     _old = 'logits'                     # the rollout column PPO's KL term reads: the old distribution's parameters
@@ -534,6 +671,18 @@ class Trainer(_OnPolicy):
     def _mask_bits(self):
         """Packed obs-side action mask (action_mask & location_mask[layer] & special_mask, slate.py:92-97)."""
         return self.env.samples._live().obs_mask_bits()          # packed on the device: no dense [B, A] round trip
+
+    def _eval_batch(self, k):
+        """One episode batch on the LEARNER's greedy action (the first maximum of its masked logits; IMPALA's actor only samples
+        rollouts) under the env's mask -> mean episode reward (device scalar)."""
+        obs = self.env.reset(reset_file=True) if k == 0 else self.env.reset()
+        total = torch.zeros(self.B, dtype=torch.float64, device=self.device)
+        for t in range(self.T):
+            obs_t = (obs['obs'] if isinstance(obs, dict) else obs).contiguous()
+            a = self.policy.greedy(obs_t, self._mask_bits(), out=self._eval_act)[0]
+            obs, reward, done, info = self.env.step(a)
+            total += reward
+        return total.mean()
 
     def rollout(self):
         B, T, R = self.B, self.T, self.R
@@ -651,8 +800,6 @@ class ContiTrainer(Trainer, _Evaluated):
                          kl_target=kl_target, train_batch_size=train_batch_size, keep_last_batch=keep_last_batch,
                          broadcast_interval=broadcast_interval, vtrace_clip_rho=vtrace_clip_rho, vtrace_clip_pg_rho=vtrace_clip_pg_rho,
                          drop_last=drop_last, vf_coeff=vf_coeff, ent_coeff=ent_coeff, grad_clip=grad_clip)
-        self.device = self.policy.device
-        self._owned = (self.policy,) + ((self.actor,) if self.actor is not None else ())
         f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.device)
         self._env_act = f(self.B, self.E)                   # the clipped draw of the current step: what the env receives
         self._eval = (f(self.B, self.E), f(self.B, self.E), f(self.B), f(self.B), None)
@@ -715,10 +862,18 @@ class ContiTrainer(Trainer, _Evaluated):
         return total.mean()
 
 
-class _ReplayTrainer(_Evaluated):
+class _ReplayTrainer(_Evaluated, _Checkpoint):
     """The loop of the replay learners (DQN, Rainbow, TD3 / DDPG): one complete-episode rollout into ``buf``, the push of its
     ``_columns`` into the replay ring, ``updates_per_rollout`` updates once ``learning_starts`` sampled steps are reached.  A trainer
-    fills ``_act`` (and ``_step_mask``), ``update``, ``_stats0``, ``_after_updates``, ``_extras`` and ``_values``."""
+    fills ``_act`` (and ``_step_mask``), ``update``, ``_stats0``, ``_after_updates``, ``_extras`` and ``_values``, and ``_new_replay``
+    (a fresh, empty ring: what ``restore`` leaves, see ``_Checkpoint``)."""
+
+    _ckpt_host = ('iteration', '_rollouts', 'timesteps', 'num_updates')
+
+    def _ckpt_after_restore(self):
+        old, self.replay = self.replay, self._new_replay()
+        self._owned = tuple(self.replay if h is old else h for h in self._owned)
+        old.close()
 
     def _init_loop(self, env, seed, train_batch_size, learning_starts, updates_per_rollout, prioritized_replay, beta, keep_last_batch):
         cfg = env.config
@@ -819,7 +974,9 @@ class DQNTrainer(_ReplayTrainer):
         self.double_q, self.target_network_update_freq = bool(double_q), int(target_network_update_freq)
         self._make_net(hidden, init_seed)
         dev = self.device = self.policy.device
-        self.replay = D.DeviceReplay(self.OD, self.A, self.T, self.B, buffer_size=buffer_size, alpha=prioritized_replay_alpha, device=dev)
+        self._new_replay = lambda: D.DeviceReplay(self.OD, self.A, self.T, self.B, buffer_size=buffer_size, alpha=prioritized_replay_alpha,
+                                                  device=dev)
+        self.replay = self._new_replay()
         self._owned = (self.policy, self.replay)
         N = self.B * self.T
         self.buf = dict(obs=torch.empty((N, self.OD), dtype=torch.float32, device=dev),
@@ -834,6 +991,19 @@ class DQNTrainer(_ReplayTrainer):
         if rdist.collectives_active():
             sync_policy_replicas(self.policy)
         self.target = self.policy.params()                  # the target net starts as a copy of the online one
+
+    _ckpt_host = _ReplayTrainer._ckpt_host + ('_last_target_sync', 'num_target_updates')
+
+    def _ckpt_nets(self):
+        return [('policy', self.policy, True)]
+
+    def _ckpt_tensors(self):
+        return {'target': self.target}
+
+    def sync_replicas(self, src=0):
+        """Make every rank's online parameters, Adam state and target those of rank ``src``."""
+        sync_policy_replicas(self.policy, src)
+        rdist.broadcast_(self.target, src)
 
     def _make_net(self, hidden, init_seed):
         """The online network ``policy`` and what its act call writes besides the action."""
@@ -1165,7 +1335,9 @@ class TD3Trainer(_ReplayTrainer):
                                   init_seed=init_seed, max_act_rows=self.B)
         self.actor = self.learner.actor
         dev = self.device = self.actor.device
-        self.replay = D.DeviceContiReplay(OD, E, self.T, self.B, buffer_size=self.buffer_size, alpha=prioritized_replay_alpha, device=dev)
+        self._new_replay = lambda: D.DeviceContiReplay(OD, E, self.T, self.B, buffer_size=self.buffer_size, alpha=prioritized_replay_alpha,
+                                                       device=dev)
+        self.replay = self._new_replay()
         self._owned = (self.learner, self.replay)
         N = self.B * self.T
         self.buf = dict(obs=torch.empty((N, OD), dtype=torch.float32, device=dev), act=torch.empty((N, E), dtype=torch.float32, device=dev),
@@ -1183,6 +1355,22 @@ class TD3Trainer(_ReplayTrainer):
         """dict name -> flat float32 parameters of every network (``TD3Learner.flat_params``)."""
         self._settle()
         return self.learner.flat_params()
+
+    def _ckpt_nets(self):
+        """actor, critics (with their Adam state) and the targets (parameters only)"""
+        return [(name, net, not name.endswith('_targ')) for name, net in self.learner.named]
+
+    def _ckpt_tensors(self):
+        return {'ou_state': self.ou_state}              # the annealed scale reads ``timesteps``, which is host state
+
+    def _ckpt_extra(self):
+        return {'noise_generator': self._gen.get_state()}           # the target-smoothing noise stream
+
+    def _ckpt_set_extra(self, extra):
+        self._gen.set_state(torch.from_numpy(extra['noise_generator']))
+
+    def sync_replicas(self, src=0):
+        self.learner.sync_replicas(src)
 
     def scale_at(self, timestep):
         """ou_base_scale x the annealed scale at a sampled timestep: the ``scale`` of rl4rs_explore_ou, computed on the host."""
@@ -1255,7 +1443,11 @@ class ExactKTrainer(_Evaluated):
     (``skipped``, ``skipped_total``).
 
     ``eval_mode='beam'`` evaluates beam 0 of ``DeviceExactK.decode_beam(beam_size=...)`` in place of the greedy slate, at the same
-    (seed, step); training is the same in both modes."""
+    (seed, step); training is the same in both modes.
+
+    No ``save`` / ``restore`` yet: ``_Checkpoint`` covers the learners of script/modelfree_train.py.  The reference's Exact-K script
+    does checkpoint (a tf.train.Saver, exact_k_train.py:118-132); here the generator's and the critic's parameters and Adam state are
+    read with ``policy.params()`` / ``adam_state()``."""
 
     def __init__(self, env, seed=0, init_seed=0, lr=1e-3, critic_lr=5e-3, dropout_rate=0.1, samples=2, same_users=True, hidden_units=64,
                  num_heads=4, num_blocks=2, vocab=500, critic_hidden=128, temperature=1, num_glimpse=1, num_layers=1, use_mha=True,
