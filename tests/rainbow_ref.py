@@ -322,24 +322,27 @@ def relu_margin(flat, obs, dm):
     return m
 
 
-def make_case(shape, seed=0):
+def make_case(shape, seed=0, trunk=256, sh=128, support=None, margin=None):
     """Inputs of one loss / gradient case.  Rewards: a fifth of the rows sit where every b_j is an exact integer (R0 and R0 + dz;
     with gamma_n 0.5 every other j), some exceed v_max, some are below v_min, the rest spread over the support.  In the masked
-    cases one non-terminal successor allows nothing (row ``k``)."""
+    cases one non-terminal successor allows nothing (row ``k``).  ``support`` = (v_min, v_max, gamma_n, R0), default SUPPORT[atoms];
+    ``margin``: how far every stream pre-activation of s stays from 0, default RELU_MARGIN.  A one-row case is set by hand: the
+    row bootstraps and its reward is R0 + dz."""
     from rl4rs_amd.nets.distq import init_distq_params
     od, A, atoms, N, dueling, double_q, masked = shape
-    v_min, v_max, gamma_n, r0 = SUPPORT[atoms]
-    dm = Dims(od, A, atoms, 256, 128, bool(dueling), v_min, v_max)
+    v_min, v_max, gamma_n, r0 = SUPPORT[atoms] if support is None else support
+    margin = RELU_MARGIN if margin is None else margin
+    dm = Dims(od, A, atoms, trunk, sh, bool(dueling), v_min, v_max)
     rs = np.random.RandomState(N + A + atoms + seed)
     n = dm.n_params()
-    flat = init_distq_params(od, A, atoms, 256, 128, bool(dueling), seed=1) + (rs.randn(n) * 0.03).astype(np.float32)
+    flat = init_distq_params(od, A, atoms, trunk, sh, bool(dueling), seed=1) + (rs.randn(n) * 0.03).astype(np.float32)
     tflat = flat + (rs.randn(n) * 0.02).astype(np.float32)
     obs, nobs = rs.randn(N, od).astype(np.float32), rs.randn(N, od).astype(np.float32)
     # the loss is not differentiable where a stream unit's pre-activation is 0, and fp32 decides the sign of a value within its
     # rounding of 0 either way: rows of s with such a unit are drawn again (RELU_MARGIN exceeds 4 x the largest fp32 error of these
-    # pre-activations, which fp32_yardstick measures at 1.9e-6)
+    # pre-activations, which fp32_yardstick measures at 1.9e-6 on GPU_SHAPES; a wider trunk passes its own margin, shape_margin)
     while True:
-        near = relu_margin(flat, obs, dm) < RELU_MARGIN
+        near = relu_margin(flat, obs, dm) < margin
         if not near.any():
             break
         obs[near] = rs.randn(int(near.sum()), od).astype(np.float32)
@@ -347,6 +350,8 @@ def make_case(shape, seed=0):
     mask[np.arange(N), rs.randint(0, A, size=N)] = 1
     done = (rs.rand(N) < 0.15).astype(np.int32)
     done[-1] = 1
+    if N == 1:
+        done[0] = 0
     k = int(np.nonzero(done == 0)[0][0])
     if masked:
         mask[k] = 0
@@ -359,16 +364,19 @@ def make_case(shape, seed=0):
     rew[(kind >= 0.1) & (kind < 0.2)] = r0 + dm.dz
     rew[(kind >= 0.2) & (kind < 0.25)] = v_max + 0.3 * span
     rew[(kind >= 0.25) & (kind < 0.3)] = v_min - 0.2 * span - 1.0
+    if N == 1:
+        rew[0] = r0 + dm.dz
     act = rs.randint(0, A, size=N).astype(np.int32)
     w = (rs.rand(N) + 0.1).astype(np.float32)
     return dict(dm=dm, flat=flat, tflat=tflat, obs=obs, nobs=nobs, mask=mask, bits=None if mask is None else pack_bits(mask), done=done,
-                act=act, rew=rew, w=w, k=k, gamma_n=gamma_n, double_q=bool(double_q), masked=bool(masked), N=N)
+                act=act, rew=rew, w=w, k=k, gamma_n=gamma_n, double_q=bool(double_q), masked=bool(masked), N=N, margin=margin)
 
 
 def fp32_yardstick(c):
     """Max errors of an fp32 eager-torch CPU forward / backward of the restatement against the float64 restatement on the inputs
-    of case ``c`` -> dict(q, td, grad_rel, left_out): Q(s') abs, td abs, gradient relative to the reference gradient's max-norm,
-    and the fraction of bootstrapping rows whose float64 top-two gap is under ten times ``q``."""
+    of case ``c`` -> dict(q, pre, td, grad_rel, left_out, td_max): Q(s') abs, the advantage stream's pre-activations abs, td abs,
+    gradient relative to the reference gradient's max-norm, the fraction of bootstrapping rows whose float64 top-two gap is under
+    ten times the Q bar, and the largest float64 |td| (the scale of the td figure)."""
     import torch
     dm = c['dm']
     ref = loss_and_grad(c['flat'], c['tflat'], c['obs'], c['act'], c['rew'], c['done'], c['nobs'], c['mask'], c['w'], c['gamma_n'],
@@ -388,7 +396,51 @@ def fp32_yardstick(c):
     boot = ref['boot']
     left = float((boot & (ref['gap'] < 10.0 * BAR_FACTOR * q_err)).sum()) / max(1, int(boot.sum()))
     return dict(q=q_err, pre=float(np.abs(pre32 - pre64).max()), td=float(np.abs(td32 - ref['td']).max()), grad_rel=float(np.abs(g32 - ref['grad']).max() / np.abs(ref['grad']).max()),
-                left_out=left)
+                left_out=left, td_max=float(np.abs(ref['td']).max()))
+
+
+# ---- cases off the one net width ---------------------------------------------------------------------------------------------
+# ((od, A, atoms, N, dueling, double_q, masked, trunk, sh), (v_min, v_max, gamma_n, R0)): the ends of what rl4rs_distq_create admits
+SHAPE_CASES = [
+    ((24, 2, 64, 33, 1, 1, 0, 32, 32), (0.0, 1000.0, 1.0, 0.0)),       # A = 2, atoms = 64, narrowest net, one row in a second head tile
+    ((100, 512, 3, 65, 1, 1, 1, 64, 256), (-2.0, 6.0, 1.0, 0.0)),      # A = 512, widest stream, AP = 4 with an idle lane, masked
+    ((2048, 65, 33, 31, 0, 0, 1, 1024, 64), (-2.0, 6.0, 0.5, -1.0)),   # widest obs and trunk, atoms = 33, no value stream, target picks a*
+    ((40, 130, 16, 1, 1, 1, 0, 96, 96), (0.0, 1000.0, 1.0, 0.0)),      # one row, AT == AP, widths that are no power of two
+    ((8, 4, 2, 16500, 1, 1, 0, 32, 32), (0.0, 1000.0, 1.0, 0.0)),      # more than 64 chunks of 256 rows: the re-chunked reductions
+]
+SHAPE_SEEDS = [0, 0, 1, 0, 0]           # (seed 0 of the third case draws no reward above v_max among its 31 rows)
+YARD_SEEDS = (0, 1, 2)
+# shape_yardstick of every case: the worst of fp32_yardstick over YARD_SEEDS (a single row can land on its float64 value by luck),
+# no figure counted for less than one fp32 rounding (2^-24) of the quantity's scale: max |z| for Q, max(1, |td|) for td, 1 for the
+# relative gradient error.  Bars as for MEASURED: BAR_FACTOR x these.  ``pre``: the error of the advantage stream's pre-activations.
+MEASURED_SHAPES = [dict(q=9.25e-5, td=1.54e-6, grad_rel=9.19e-7, pre=5.24e-7), dict(q=1.17e-6, td=4.18e-7, grad_rel=3.02e-7, pre=5.39e-7),
+                   dict(q=5.98e-7, td=9.58e-7, grad_rel=1.25e-6, pre=3.25e-6), dict(q=1.25e-4, td=1.90e-7, grad_rel=1.54e-6, pre=3.49e-7),
+                   dict(q=2.12e-4, td=4.46e-7, grad_rel=5.96e-8, pre=5.79e-7)]
+U32 = 2.0 ** -24
+
+
+def shape_margin(i):
+    """RELU_MARGIN rests on a 1.9e-6 pre-activation error; a 1024-wide trunk measures more, so every case keeps its stream
+    pre-activations 4 x its own measured error away from 0 (never less than RELU_MARGIN)."""
+    return max(RELU_MARGIN, 4.0 * MEASURED_SHAPES[i]['pre'])
+
+
+def shape_case(i, seed=None, margin=None):
+    shape, support = SHAPE_CASES[i]
+    return make_case(shape[:7], SHAPE_SEEDS[i] if seed is None else seed, trunk=shape[7], sh=shape[8], support=support,
+                     margin=shape_margin(i) if margin is None else margin)
+
+
+def shape_yardstick(i, margin=None):
+    """-> dict(q, td, grad_rel, pre): the worst of fp32_yardstick over YARD_SEEDS with the floors stated at MEASURED_SHAPES"""
+    out = dict(q=0.0, td=0.0, grad_rel=0.0, pre=0.0)
+    for seed in YARD_SEEDS:
+        c = shape_case(i, seed, margin)
+        y = fp32_yardstick(c)
+        td_scale = max(1.0, y['td_max'])
+        floors = dict(q=U32 * float(np.abs(c['dm'].z).max()), td=U32 * td_scale, grad_rel=U32, pre=0.0)
+        out = dict((k, max(out[k], y[k], floors[k])) for k in out)
+    return out
 
 
 def softq_edge_bar(q_bar, temperature):

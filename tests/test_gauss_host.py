@@ -70,6 +70,27 @@ def test_param_count_and_flat_layout(D, H, E):
     assert not np.array_equal(flat, G.init_gausspolicy_params(D, E, H, seed=4))
 
 
+@pytest.mark.parametrize('dims', [(260, 64, 3), (515, 128, 5)], ids=lambda d: 'D%d-H%d-E%d' % d)
+def test_a_forward_that_drops_the_last_staging_pass_would_show(dims):
+    """k_gp_fwd stages the observation 256 columns at a time; at D = 260 and D = 515 the last pass holds 4 and 3 columns.  On the
+    inputs and with the bars of tests/test_gpu_gauss_policy.py, a forward that ignores the columns from 256 on - and one that
+    ignores the last pass alone - misses head and value by more than ten times their bars: the GPU test can tell."""
+    import test_gpu_gauss_policy as GT
+    D = dims[0]
+    b = GT._base(dims)
+    assert b['obs'].shape == (33, D) and D % 256 in (3, 4)
+    for first_dropped in sorted({256, D - D % 256}):
+        obs = b['obs'].copy()
+        obs[:, first_dropped:] = 0.0
+        with torch.no_grad():
+            head, value = R.forward(b['flat'], obs, dims)
+        for k, got in (('head', head), ('value', value)):
+            for n in (1, 33):                                               # at both row counts the shape runs at
+                miss = np.abs(got.numpy()[:n] - b['ref'][k][:n]).max()
+                print('D%d columns from %d on dropped, %d rows: %s misses by %.3g (bar %.3g)' % (D, first_dropped, n, k, miss, b['bars'][k]))
+                assert miss > 10.0 * b['bars'][k], (k, n, miss, b['bars'][k])
+
+
 def test_entry_points_refuse_bad_arguments_before_touching_a_device():
     from rl4rs_amd import _lib
     lib = _lib.load()

@@ -49,6 +49,48 @@ def test_binary_counts_are_exact(handle, n):
     assert handle.result() == M.metrics_from_counts(ref, T)
 
 
+N_STRIDE = 1024 * 256 + 257            # the grid is capped at 1024 workgroups of 256 threads: the last 257 elements are second trips
+
+
+def test_binary_counts_are_exact_on_the_second_trip_of_the_grid_stride(handle):
+    n = N_STRIDE
+    pred, label = _edge_predictions(n, 7)
+    edge, edge_label = _edge_predictions(257, 8)
+    assert np.isnan(edge).any() and (edge == np.float32(0.5)).any() and (edge > 1).any() and (edge < 0).any()
+    pred[-257:], label[-257:] = edge, edge_label              # the edge values are counted by threads on their second trip
+    handle.reset()
+    handle.update_binary(_dev(pred), _dev(label))
+    got = handle.counts()
+    ref = M.confusion_counts(pred, label, handle.thresholds)
+    assert np.array_equal(got, ref)
+    tp, fp, tn, fn = (got[k * T:(k + 1) * T] for k in range(4))
+    assert (tp + fp + tn + fn == n).all()                       # every element is counted once at every threshold
+    assert (tp + fn == int(label.sum())).all()
+    assert got[4 * T:4 * T + 4].sum() == n
+    # the tail alone accounts for the difference to the first 1024 * 256 elements
+    handle.reset()
+    handle.update_binary(_dev(pred[:-257]), _dev(label[:-257]))
+    assert np.array_equal(got - handle.counts(), M.confusion_counts(edge, edge_label, handle.thresholds))
+
+
+def test_multiclass_counts_are_exact_on_the_second_trip_of_the_grid_stride(handle):
+    N, K = N_STRIDE, 2
+    rs = np.random.RandomState(9)
+    pred = rs.rand(N, K).astype(np.float32)
+    pred[::3] = np.round(pred[::3] * 2) / 2                     # many ties: class 0 wins them
+    label = rs.randint(0, K, size=N).astype(np.int32)
+    label[-257:] = np.argmax(pred[-257:], axis=1)              # the second-trip rows are all hits ...
+    label[-257::2] ^= 1                                         # ... but every other one: 128 of them are hits
+    handle.reset()
+    handle.update_multiclass(_dev(pred), _dev(label))
+    got = handle.counts()
+    assert got[4 * T + 4:].tolist() == list(M.categorical_counts(pred, label)) and got[4 * T + 5] == N
+    assert not got[:4 * T + 4].any()
+    handle.reset()
+    handle.update_multiclass(_dev(pred[:-257]), _dev(label[:-257]))
+    assert (got - handle.counts())[4 * T + 4:].tolist() == [128, 257]
+
+
 def test_two_updates_equal_one_of_the_concatenation_and_reset(handle):
     p1, y1 = _edge_predictions(257, 1)
     p2, y2 = _edge_predictions(4099, 2)

@@ -60,6 +60,9 @@ def _dev(c):
     (100, 48, 75, 333, True, 0, True),            # the one-wave-per-row path, at a shape no tiled kernel takes
     (256, 64, 284, 1024, False, 1, True),         # double_q off: the target net picks a*
     (256, 64, 284, 601, False, 0, False),
+    (10, 48, 40, 16500, True, 0, True),           # 33 chunks of the sample-axis reductions (the handle's chunk is 512 rows)
+    (256, 64, 284, 16500, True, 1, True),
+    (10, 48, 40, 32800, True, 0, True),           # ceil(N / 512) = 65 > 64: the reductions re-chunk to 576 rows
 ])
 def test_loss_and_gradient_match_the_restatement(od, hid, A, N, double_q, tile, weighted):
     import torch

@@ -10,7 +10,11 @@ there (the 3072-wide shape runs on the device at 33 rows only; its yardstick is 
 yardstick figure counts for less than one float32 rounding of the quantity's scale, 2^-24 relative: a float32 result is not defined
 more finely than that, and a float32 run that lands closer to the float64 value did so by luck.  Gradients are held relative to the
 reference gradient's max-norm per parameter block, statistics relative to max(1, |reference|) per row.  Each test prints the
-device's error beside its bar."""
+device's error beside its bar.
+
+Shapes beside the default ones: D = 260 and D = 515 leave k_gp_fwd's last 256-column staging pass with 4 and 3 columns (1 and 33
+rows; tests/test_gauss_host.py shows that a dropped pass would miss the bars by far); the 4099-row batch of the (40, 64, 3) shape
+makes the loss's gradient reductions take 320-row chunks, its yardstick taken at its own row count."""
 import functools
 
 import numpy as np
@@ -22,8 +26,10 @@ import vtrace_ref as VR
 
 pytestmark = pytest.mark.gpu
 
-SHAPES = [(256, 256, 32), (40, 64, 3), (7, 128, 1), (3072, 256, 32), (256, 256, 64)]
+SHAPES = [(256, 256, 32), (40, 64, 3), (7, 128, 1), (3072, 256, 32), (256, 256, 64), (260, 64, 3), (515, 128, 5)]
 ROWS = (1, 5, 33, 256, 257)
+RAGGED = (260, 515)                    # obs widths whose last 256-column staging pass of k_gp_fwd is a ragged one (4 and 3 columns)
+BIG = ((40, 64, 3), 4099)              # a batch whose gradient reductions take 320-row chunks (64 up to 1024 rows)
 SEED, STEP = 12345, 7
 F32, F64 = torch.float32, torch.float64
 
@@ -32,12 +38,12 @@ U32 = 2.0 ** -24                       # one float32 rounding, relative: the lea
 
 
 def _rows(dims):
-    return (33,) if dims[0] == 3072 else ROWS
+    return (33,) if dims[0] == 3072 else (1, 33) if dims[0] in RAGGED else ROWS
 
 
-def _yard_rows(dims):
-    """the row counts the float32 yardstick of a shape is taken over"""
-    return (1, 5, 33) if dims[0] == 3072 else ROWS
+def _yard_rows(dims, rows=0):
+    """the row counts the float32 yardstick of a shape is taken over (``rows``: of a batch that is a case of its own)"""
+    return (rows,) if rows else (1, 5, 33) if dims[0] == 3072 else _rows(dims)
 
 
 CASES = [(dims, N) for dims in SHAPES for N in _rows(dims)]
@@ -63,12 +69,13 @@ def _dev(a, b):
 
 
 @functools.lru_cache(maxsize=None)
-def _base(dims):
-    """Parameters, observations and the forward's reference for the largest row count of a shape (smaller calls take its first rows);
+def _base(dims, rows=0):
+    """Parameters, observations and the forward's reference for the largest row count of a shape (smaller calls take its first rows;
+    ``rows``: for a batch of that many rows instead, a case of its own);
     the float32 run of the same rows gives the forward bars.  logp is compared on GIVEN actions (the float64 draw rounded to float32):
     what is measured is the error of the evaluation, not of two different draws."""
     D, H, E = dims
-    N = max(_rows(dims))
+    N = rows or max(_rows(dims))
     flat = R.make_params(dims, seed=D + E)
     obs = np.random.RandomState(D * 7 + E).randn(N, D).astype(np.float32)
     ref = R.act(flat, obs, dims, SEED, STEP)
@@ -128,7 +135,7 @@ def test_act_and_evaluate_follow_the_restatement(case):
     pol.close()
 
 
-@pytest.mark.parametrize('dims', [d for d in SHAPES if d[0] != 3072], ids=lambda d: 'D%d-H%d-E%d' % d)
+@pytest.mark.parametrize('dims', [d for d in SHAPES if max(_rows(d)) >= 257], ids=lambda d: 'D%d-H%d-E%d' % d)
 def test_a_row_does_not_depend_on_the_rows_beside_it(dims):
     b = _base(dims)
     pol = _policy(dims, b['flat'])
@@ -160,12 +167,12 @@ LOSSES = {'a2c': dict(algo=0, vf_coeff=0.5, ent_coeff=0.01), 'pg': dict(algo=0, 
 
 
 @functools.lru_cache(maxsize=None)
-def _loss_inputs(dims):
+def _loss_inputs(dims, rows=0):
     """Rollout-like inputs on the base rows: actions drawn from a STALE policy (the old head: means shifted by 0.6 / sqrt(E) standard
     deviations, log_std by 0.2 / sqrt(E), so that log(ratio) has a spread of about 0.6 whatever E is), advantages of both signs,
     returns around the values, old values 0.1 away from the new ones."""
     D, H, E = dims
-    b = _base(dims)
+    b = _base(dims, rows)
     N = b['obs'].shape[0]
     rs = np.random.RandomState(D + 31 * E)
     head = b['ref']['head']
@@ -189,9 +196,9 @@ def _variant(flat, v):
 
 
 @functools.lru_cache(maxsize=None)
-def _loss_ref(dims, name, N):
+def _loss_ref(dims, name, N, rows=0):
     """(float64 gradient, stats, clip masks, float32 yardstick per block, float32 yardstick of stats per row)"""
-    b, x, kw = _base(dims), _loss_inputs(dims), LOSSES[name]
+    b, x, kw = _base(dims, rows), _loss_inputs(dims, rows), LOSSES[name]
     adv = x['adv'][:N] * (1.0 / N) if name == 'pg' else x['adv'][:N]
     args = (kw['algo'], b['flat'], b['obs'][:N], x['act'][:N], adv, x['ret'][:N], dims)
     extra = dict((k, v) for k, v in kw.items() if k != 'algo')
@@ -211,20 +218,31 @@ def _loss_ref(dims, name, N):
     return g64, s64, masks, gdev, sdev
 
 
-def _loss_bars(dims, name):
-    per = [_loss_ref(dims, name, n) for n in _yard_rows(dims)]
+def _loss_bars(dims, name, rows=0):
+    per = [_loss_ref(dims, name, n, rows) for n in _yard_rows(dims, rows)]
     return (dict((k, 4.0 * max([U32] + [p[3][k] for p in per])) for k in R.NAMES), 4.0 * np.maximum(U32, np.max([p[4] for p in per], axis=0)))
 
 
 @pytest.mark.parametrize('name', sorted(LOSSES))
 @pytest.mark.parametrize('case', CASES, ids=_id)
 def test_loss_and_gradient_follow_the_restatement(case, name):
+    _check_loss(case, name)
+
+
+@pytest.mark.parametrize('name', ['a2c', 'ppo'])
+def test_loss_and_gradient_follow_the_restatement_in_320_row_chunks(name):
+    """gp_loss_grad reduces the sample axis in at most 16 chunks of a multiple of 64 rows: 64 up to 1024 rows, 320 at 4099.  The
+    batch is a case of its own (its inputs, and its float32 yardstick at its own row count)."""
+    _check_loss(BIG, name, rows=BIG[1])
+
+
+def _check_loss(case, name, rows=0):
     dims, N = case
     D, H, E = dims
-    b, x, kw = _base(dims), _loss_inputs(dims), LOSSES[name]
+    b, x, kw = _base(dims, rows), _loss_inputs(dims, rows), LOSSES[name]
     if kw['algo'] == 1:
         # what the case exercises, from the restatement on the shape's full batch, before the device is looked at
-        full = _loss_ref(dims, name, max(_rows(dims)))[2]
+        full = _loss_ref(dims, name, rows or max(_rows(dims)), rows)[2]
         share = full['ratio_clipped'].mean()
         assert 0.2 <= share <= 0.8, share
         if kw['vf_clip'] < 1.0:
@@ -234,9 +252,9 @@ def test_loss_and_gradient_follow_the_restatement(case, name):
     assert 0.2 <= (x['adv'] > 0).mean() <= 0.8
     ls = b['ref']['head'][:, E:]
     assert E == 1 or (ls.min() < -2.5 and ls.max() > 0.5)
-    g64, s64, _, _, _ = _loss_ref(dims, name, N)
-    gbar, sbar = _loss_bars(dims, name)
-    pol = _policy(dims, b['flat'])
+    g64, s64, _, _, _ = _loss_ref(dims, name, N, rows)
+    gbar, sbar = _loss_bars(dims, name, rows)
+    pol = _policy(dims, b['flat'], max_rows=max(257, N))
     adv = x['adv'][:N] * np.float32(1.0 / N) if name == 'pg' else x['adv'][:N]
     extra = dict((k, v) for k, v in kw.items() if k != 'algo')
     if kw['algo'] == 1:
