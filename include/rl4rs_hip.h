@@ -578,6 +578,21 @@ int rl4rs_stepper_set_distinct_hint(rl4rs_stepper* s, int32_t n_distinct);
  * a changed row order.  The slot table and the row order must not be rewritten in place between two steps of an episode.
  * Outputs are bit-identical either way.  rl4rs_stepper_set_partition_carry(s, 0): every forward launches k_row_dedup as before. */
 int rl4rs_stepper_set_partition_carry(rl4rs_stepper* s, int32_t on);
+/* Consecutive transitions on two streams (default on).  A transition of rl4rs_env_step_discrete that scores with the DIEN
+ * on its k_augru_x path, carries the partition, has no reward due, asks for neither done_dev nor mask_bits_dev and whose
+ * observation-sized launch leaves half of the chip free (2 * seq_num * ceil(distinct hint / 32) <= CUs) runs on one of two streams
+ * of the stepper, in turn: its act waits for the previous transition's ACT only, so its forward runs beside the previous forward
+ * when the caller hands back the logged-action row it was given (rl4rs_stepper_next_offline_action); any other action makes it
+ * wait for the caller's stream first.  obs_dev / reward_dev are filled on the caller's stream, behind the lane's last launch:
+ * what the caller sees on its stream is what it saw before, bit for bit.  Every other entry point of the stepper, its env and its
+ * scorer first lets the stream it is given wait for both lanes (those that are given none: the host waits).
+ * rl4rs_stepper_set_step_overlap(s, 0): every call runs on the caller's stream with the launches it had.
+ * Cost: a stepper on a DIEN owns two streams, four events and 2 * B * 1032 bytes of device memory for its life, its scorer a second
+ * scratch set of about 6 KB per env (reserved once per batch size, freed with the scorer).  Env, scorer and stepper may be destroyed
+ * in any order. */
+int rl4rs_stepper_set_step_overlap(rl4rs_stepper* s, int32_t on);
+/* Lane transitions issued on each lane and joins carried out since the stepper was created (read-only; any pointer may be NULL). */
+int rl4rs_stepper_lane_stats(const rl4rs_stepper* s, int64_t* lane0, int64_t* lane1, int64_t* joins);
 /* Click probabilities of the complete-state rows of the LAST reward step, slate order: out_dev [B, n_complete] f32 - the same
  * numbers in either order of the forwards (the record form's click_p part, for rl4rs_env_step_discrete / _conti). */
 int rl4rs_stepper_click_probs(rl4rs_stepper* s, float* out_dev, void* stream);

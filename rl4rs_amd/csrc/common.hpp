@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/rl4rs_hip.h"
+#include "step_lanes.hpp"      // LaneHook, lanes_join, lanes_gone (plain C++)
 
 namespace rl4rs {
 
@@ -187,6 +188,27 @@ void dien_drop_pending_expand(rl4rs_dien* n);
 int64_t dien_augru_rounds(const rl4rs_dien* n, int B, int live, int group);
 // Would that forward's k_augru_x launch run the 64-row form (automatic rule or pinned)?
 bool dien_augru_rows64(const rl4rs_dien* n, int B, int group);
+
+// The stepper's two lanes (step.hip, step_lanes.hpp) may have a transition in flight on streams of their own.  The env and
+// the scorer a stepper is attached to hold a pointer to its hook, and every entry point that reads or writes what a lane may still
+// touch calls lanes_join first: with a stream, that stream waits for the lanes (nothing blocks); without one (an entry point that
+// is given none) the host waits.  Idle lanes cost a null check and a flag.  LaneHook and the rules of who tells whom when a handle
+// or the stepper is destroyed: step_lanes.hpp.  These return where the handle keeps its pointer to the hook
+const LaneHook** env_lane_slot(rl4rs_env* e);
+const LaneHook** dien_lane_slot(rl4rs_dien* n);
+// The env keeps two sets of state rows (BUF_DENSE / BUF_CATEGORY): env_flip_rows makes the other one current for the acts that
+// follow, so that an act may build its rows while the previous transition's forward still reads the set before.  *dense / *cat: the
+// current set (what rl4rs_env_buffer returns)
+void env_flip_rows(rl4rs_env* e);
+void env_rows_current(const rl4rs_env* e, const float** dense, const int32_t** cat);
+// A second set of the scratch an observation-sized forward writes (query, q-side term, scores, all-feature rows, table addend), for
+// `rows` rows: dien_forward_lane(.., set = 1, ..) runs on it, beside a forward on the handle's first set.  The lane forwards join
+// nothing themselves (the stepper orders them); `home`: the caller's stream, on which rl4rs_dien_buffer completes what they left
+int dien_reserve_lane_scratch(rl4rs_dien* n, int rows);
+int dien_forward_lane(rl4rs_dien* n, int set, int32_t R, const float* dense, const int32_t* cat, const int32_t* slots, float* obs,
+                      void* stream, void* home);
+bool dien_lane_path(const rl4rs_dien* n, int rows);      // fp16x2 on k_augru_x / k_augru_xs, and the second set holds `rows` rows
+int dien_n_cu(const rl4rs_dien* n);
 
 // Training-mode recurrences as persistent kernels (recur_train.hpp, compiled into dien.hip; called from dientrain.hpp).
 // Arrays are per sequence input (S <= 4 inputs run in ONE launch, grid.y = S); saved tensors are [N * L, Hd] row-major.

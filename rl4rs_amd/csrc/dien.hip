@@ -1680,7 +1680,7 @@ struct rl4rs_dien {
     int64_t dedup_launched, dedup_carried;      // forwards that launched k_row_dedup / took a caller's partition (rl4rs_dien_dedup_counts)
     // PlanExpand::Lazy: the last forward launched no k_row_expand - the internal rows (all-feature, scores, query) of
     // its duplicates are completed by dien_settle_expand when rl4rs_dien_buffer hands one of them out, from these
-    struct LazyExpand { bool pending; hipStream_t st; int R, group, n_groups, ncol; const int32_t* rep; const int32_t* nact; } lazy;
+    struct LazyExpand { bool pending; hipStream_t st; int R, group, n_groups, ncol; const int32_t* rep; const int32_t* nact; int set; } lazy;
     float* augru_wg[4];    // packed [2*NH2/32][NH2/8][64][4]
     float* augru_wc[4];
     // caches
@@ -1689,7 +1689,14 @@ struct rl4rs_dien {
     float* proj[4];        // [max_slots*L, PLD]
     // scratch
     float *allf, *dh, *q, *scores, *obs_tmp;
-    float* obs_mirror;     // rl4rs_dien_set_obs_mirror: device-visible host memory [R, OBS_DIM] for the NEXT forward's observation
+    int srows;             // rows the scratch set in use was allocated for (stride of scores): max_rows on the handle's own set
+    // the second scratch set (dien_reserve_lane_scratch): swapped in for the length of a dien_forward_lane(set = 1) call
+    struct ScratchSet { float *allf, *dh, *q, *scores, *qa, *tsum; int rows; } alt;
+    int last_set;          // the set the last forward ran on; 1: rl4rs_dien_buffer first copies its rows to the handle's own set
+    int last_rows;         // ... and how many rows that forward had
+    hipStream_t last_home; // ... on the stream of the lane forward's caller
+    const LaneHook* lanes; // the stepper whose lanes may have a forward of this handle in flight
+    float* obs_mirror;    // rl4rs_dien_set_obs_mirror: device-visible host memory [R, OBS_DIM] for the NEXT forward's observation
     bool obs_mirror_used;  // ... whether that forward's head kernel took it (only the fp16x2 GEMM with the table addend writes mirrors)
     float* obs_last;       // rl4rs_dien_set_obs_last: [R / group, OBS_DIM] for the NEXT forward's observation of each group's last row
     std::vector<void*> owned;
@@ -2086,6 +2093,7 @@ int rl4rs_dien_create(const rl4rs_dien_cfg* c, const rl4rs_dien_weights* w, void
     AL(qa, (size_t)S * c->max_rows * ATT_H1);
     AL(scores, (size_t)S * c->max_rows * L);
     AL(obs_tmp, (size_t)c->max_rows * OBS_DIM);
+    n->srows = c->max_rows;
     // row dedup: only where both kernels that read the active list are the selected ones
     n->t.h1f = n->h1f[0] != nullptr;
     n->t.row_dedup = !(opts & RL4RS_DIEN_OPT_NO_ROW_DEDUP) && n->t.augru_x && n->t.din_x_selected();
@@ -2194,6 +2202,8 @@ int rl4rs_dien_create(const rl4rs_dien_cfg* c, const rl4rs_dien_weights* w, void
 
 int rl4rs_dien_destroy(rl4rs_dien* n) {
     if (!n) return RL4RS_OK;
+    (void)lanes_join(n->lanes, nullptr, false);
+    lanes_gone(n->lanes, LANE_LINK_SCORER);      // the stepper forgets this scorer: it may be destroyed later
     for (void* p : n->owned) (void)hipFree(p);
     for (auto& e : n->pending) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     for (auto e : n->pool) (void)hipEventDestroy(e);
@@ -2213,6 +2223,10 @@ int rl4rs_dien_encode(rl4rs_dien* n, int32_t s, const int32_t* ids, int32_t cnt,
                   "dien_encode: slots [%d,%d) exceed max_slots=%d", slot_base, slot_base + cnt, n->c.max_slots);
     hipStream_t st = (hipStream_t)stream;
     const int E = n->E, L = n->L;
+    {   // the cache slots a lane forward in flight may read
+        const int rc = lanes_join(n->lanes, stream);
+        if (rc) return rc;
+    }
     {
         Prof p(n, KID_GRU1, st);
         RecurArgs a;
@@ -2278,6 +2292,7 @@ struct DienFwd {
     const int32_t *rep, *active, *nact;         // the duplicate row groups: the handle's own partition (k_row_dedup) or the caller's
     G16RowMap rmap; const G16RowMap* map2;      // the active-row map; the same for the launches of the second tier (NULL: tier off)
     hipStream_t st;
+    int set; hipStream_t home;                  // the scratch set the forward runs on; the stream rl4rs_dien_buffer completes it on
 };
 
 static int dense_tower(rl4rs_dien* n, const DienPlan& p, const DienFwd& f, hipStream_t s2) {
@@ -2402,7 +2417,7 @@ static int stage_din(rl4rs_dien* n, const DienPlan& p, const DienFwd& f) {
         a.w2[s] = n->att_w2[s]; a.b2[s] = n->att_b2[s]; a.w3[s] = n->att_w3[s]; a.b3[s] = n->att_b3[s];
         a.lead[s] = n->lead[s];
     }
-    a.scores = n->scores; a.scores_stride = (int64_t)n->c.max_rows * L;
+    a.scores = n->scores; a.scores_stride = (int64_t)n->srows * L;
     a.order = f.order_in;
     if (p.dedup != PlanDedup::None) { a.order = f.active; a.n_active = f.nact; }
     if (p.dup_lists) { a.dup_start = n->dd_dstart; a.dup_list = n->dd_dlist; }
@@ -2447,7 +2462,7 @@ static int stage_augru(rl4rs_dien* n, const DienPlan& p, const DienFwd& f) {
     for (int s = 0; s < S; ++s) a.lead[s] = n->lead[s];
     a.pad_slot = n->c.max_slots;
     for (int s = 0; s < S; ++s) { a.xbase[s] = n->proj[s]; a.wg[s] = n->augru_wg[s]; a.wc[s] = n->augru_wc[s]; }
-    a.att = n->scores; a.att_stride = (int64_t)n->c.max_rows * L;
+    a.att = n->scores; a.att_stride = (int64_t)n->srows * L;
     a.out = n->allf; a.out_ld = F; a.out_off = 0; a.out_seq_off = NH2; a.slot_base = 0;
     const dim3 grid((R + 31) / 32, S), block(512);
     if (p.augru == PlanAugru::Recur32) {
@@ -2511,14 +2526,14 @@ static int stage_augru(rl4rs_dien* n, const DienPlan& p, const DienFwd& f) {
 static int stage_expand(rl4rs_dien* n, const DienPlan& p, const DienFwd& f) {
     Prof pr(n, KID_DEDUP, f.st);
     if (p.expand == PlanExpand::Lazy) {
-        n->lazy = rl4rs_dien::LazyExpand{true, f.st, f.R, f.group, f.n_groups, p.expand_ncol, f.rep, f.nact};
+        n->lazy = rl4rs_dien::LazyExpand{true, f.home, f.R, f.group, f.n_groups, p.expand_ncol, f.rep, f.nact, f.set};
         return RL4RS_OK;
     }
     RowExpandArgs a;
     memset(&a, 0, sizeof(a));
     a.R = f.R; a.group = f.group; a.n_groups = f.n_groups; a.S = n->S; a.L = n->L; a.ncol = p.expand_ncol;
     a.rep = f.rep; a.n_active = f.nact;
-    a.allf = n->allf; a.ld = n->Fld; a.scores = n->scores; a.scores_stride = (int64_t)n->c.max_rows * n->L;
+    a.allf = n->allf; a.ld = n->Fld; a.scores = n->scores; a.scores_stride = (int64_t)n->srows * n->L;
     if (p.expand == PlanExpand::Behind) { a.q = n->q; a.E = n->E; a.obs = f.obs_out; a.obs_dim = OBS_DIM; }
     hipLaunchKernelGGL(k_row_expand, dim3((f.R + 3) / 4), dim3(256), 0, f.st, a);
     RL4RS_LAUNCH_CHECK();
@@ -2563,14 +2578,24 @@ static int stage_prob(rl4rs_dien* n, const DienPlan& p, const DienFwd& f) {
     return RL4RS_OK;
 }
 
-int rl4rs_dien_forward(rl4rs_dien* n, int32_t R, int32_t group, const float* dense, const int32_t* cat,
-                       const int32_t* slots, float* obs, float* prob, void* stream) {
+// the scratch a forward writes, exchanged with the handle's second set for the length of a lane forward on it
+static void swap_scratch(rl4rs_dien* n) {
+    rl4rs_dien::ScratchSet& a = n->alt;
+    std::swap(n->allf, a.allf); std::swap(n->dh, a.dh); std::swap(n->q, a.q); std::swap(n->scores, a.scores);
+    std::swap(n->qa, a.qa); std::swap(n->tsum, a.tsum); std::swap(n->srows, a.rows);
+}
+
+static int dien_forward_on(rl4rs_dien* n, int set, hipStream_t home, int32_t R, int32_t group, const float* dense, const int32_t* cat,
+                           const int32_t* slots, float* obs, float* prob, void* stream) {
     RL4RS_REQUIRE(n && dense && cat && slots, "dien_forward: null argument");
     RL4RS_REQUIRE(R > 0 && R <= n->c.max_rows, "dien_forward: R=%d exceeds max_rows=%d", R, n->c.max_rows);
     RL4RS_REQUIRE(group >= 1 && R % group == 0, "dien_forward: R=%d is not a multiple of group=%d", R, group);
     const int ngroups = R / group;
     n->obs_mirror_used = false;
     n->lazy.pending = false;       // the last forward's pending expansion: its rows are about to be overwritten
+    struct SetGuard { rl4rs_dien* n; bool on; ~SetGuard() { if (on) swap_scratch(n); } } set_guard{n, set == 1};
+    if (set == 1) swap_scratch(n);
+    n->last_set = set; n->last_rows = R; n->last_home = home;
     struct MirrorOnce { rl4rs_dien* n; ~MirrorOnce() { n->obs_mirror = nullptr; n->obs_last = nullptr; n->part_rep = nullptr; } } mirror_once{n};       // one forward only
     DienCall c{};
     c.R = R; c.group = group; c.obs = obs != nullptr; c.prob = prob != nullptr;
@@ -2587,6 +2612,7 @@ int rl4rs_dien_forward(rl4rs_dien* n, int32_t R, int32_t group, const float* den
     DienFwd f;
     f.R = R; f.group = group; f.n_groups = ngroups; f.dense = dense; f.cat = cat; f.slots = slots;
     f.obs_out = obs ? obs : n->obs_tmp; f.prob = prob; f.st = (hipStream_t)stream;
+    f.set = set; f.home = home;
     f.order_in = c.row_order ? n->row_order : nullptr;
     f.rep = c.carried ? n->part_rep : n->dd_rep;
     f.active = c.carried ? n->part_active : n->dd_active;
@@ -2609,6 +2635,14 @@ int rl4rs_dien_forward(rl4rs_dien* n, int32_t R, int32_t group, const float* den
     return RL4RS_OK;
 }
 
+int rl4rs_dien_forward(rl4rs_dien* n, int32_t R, int32_t group, const float* dense, const int32_t* cat,
+                       const int32_t* slots, float* obs, float* prob, void* stream) {
+    RL4RS_REQUIRE(n, "dien_forward: null argument");
+    const int rc = lanes_join(n->lanes, stream);
+    if (rc) return rc;
+    return dien_forward_on(n, 0, (hipStream_t)stream, R, group, dense, cat, slots, obs, prob, stream);
+}
+
 int rl4rs_dien_head_prob(rl4rs_dien* n, int32_t R, const float* obs, float* prob, void* stream) {
     RL4RS_REQUIRE(n && obs && prob && R > 0, "dien_head_prob: bad argument");
     hipStream_t st = (hipStream_t)stream;
@@ -2620,15 +2654,33 @@ int rl4rs_dien_head_prob(rl4rs_dien* n, int32_t R, const float* obs, float* prob
 
 // PlanExpand::Lazy: the internal rows of the last forward's duplicates, on that forward's stream, once (no profile entry: the
 // forward has recorded the class's entry).  The head output is complete already (group 1) or was not asked for
+// The last forward ran on the second scratch set (a lane forward): its internal rows go to the handle's own set, where
+// rl4rs_dien_buffer's callers look for them - once, on the stream of that forward's caller (the lanes have been joined)
+static int dien_settle_set(rl4rs_dien* n) {
+    if (n->last_set != 1) return RL4RS_OK;
+    n->last_set = 0;
+    const rl4rs_dien::ScratchSet& a = n->alt;
+    const size_t R = (size_t)n->last_rows;
+    hipStream_t st = n->last_home;
+    RL4RS_HIP_TRY(hipMemcpyAsync(n->allf, a.allf, R * n->Fld * 4, hipMemcpyDeviceToDevice, st));
+    RL4RS_HIP_TRY(hipMemcpyAsync(n->q, a.q, R * n->E * 4, hipMemcpyDeviceToDevice, st));
+    for (int s = 0; s < n->S; ++s)
+        RL4RS_HIP_TRY(hipMemcpyAsync(n->scores + (size_t)s * n->srows * n->L, a.scores + (size_t)s * a.rows * n->L, R * n->L * 4,
+                                     hipMemcpyDeviceToDevice, st));
+    return RL4RS_OK;
+}
+
 static int dien_settle_expand(rl4rs_dien* n) {
     if (!n->lazy.pending) return RL4RS_OK;
     n->lazy.pending = false;
     const rl4rs_dien::LazyExpand& z = n->lazy;
+    struct SetGuard { rl4rs_dien* n; bool on; ~SetGuard() { if (on) swap_scratch(n); } } set_guard{n, z.set == 1};
+    if (z.set == 1) swap_scratch(n);
     RowExpandArgs a;
     memset(&a, 0, sizeof(a));
     a.R = z.R; a.group = z.group; a.n_groups = z.n_groups; a.S = n->S; a.L = n->L; a.ncol = z.ncol;
     a.rep = z.rep; a.n_active = z.nact;
-    a.allf = n->allf; a.ld = n->Fld; a.scores = n->scores; a.scores_stride = (int64_t)n->c.max_rows * n->L;
+    a.allf = n->allf; a.ld = n->Fld; a.scores = n->scores; a.scores_stride = (int64_t)n->srows * n->L;
     a.q = n->q; a.E = n->E;
     hipLaunchKernelGGL(k_row_expand, dim3((z.R + 3) / 4), dim3(256), 0, z.st, a);
     RL4RS_LAUNCH_CHECK();
@@ -2637,9 +2689,14 @@ static int dien_settle_expand(rl4rs_dien* n) {
 
 int rl4rs_dien_buffer(rl4rs_dien* n, int which, void** p, int64_t* bytes) {
     RL4RS_REQUIRE(n && p, "dien_buffer: null argument");
-    if (which == RL4RS_DIEN_ALL_FEATURE || which == RL4RS_DIEN_SCORES || which == RL4RS_DIEN_QUERY) {
-        const int rc = dien_settle_expand(n);
+    {   // no stream is given here: the host waits for a lane forward in flight
+        const int rc = lanes_join(n->lanes, nullptr, false);
         if (rc) return rc;
+    }
+    if (which == RL4RS_DIEN_ALL_FEATURE || which == RL4RS_DIEN_SCORES || which == RL4RS_DIEN_QUERY) {
+        int rc = dien_settle_expand(n);
+        if (rc) return rc;
+        if ((rc = dien_settle_set(n))) return rc;
     }
     int64_t b = 0;
     void* ptr = nullptr;
@@ -2732,6 +2789,10 @@ int rl4rs_dien_status(rl4rs_dien* n, int32_t* flags, void* stream) {
     RL4RS_REQUIRE(n && flags, "dien_status: null argument");
     hipStream_t st = (hipStream_t)stream;
     int v = 0;
+    {
+        const int rc = lanes_join(n->lanes, stream);
+        if (rc) return rc;
+    }
     RL4RS_HIP_TRY(hipMemcpyAsync(&v, n->range_flag, 4, hipMemcpyDeviceToHost, st));
     RL4RS_HIP_TRY(hipStreamSynchronize(st));
     if (v) RL4RS_HIP_TRY(hipMemsetAsync(n->range_flag, 0, 4, st));
@@ -2746,6 +2807,33 @@ bool dien_takes_partition(const rl4rs_dien* n) { return n && n->t.row_dedup && !
 const int32_t* dien_row_order(const rl4rs_dien* n, int n_groups) { return (n->row_order && n->row_order_n == n_groups) ? n->row_order : nullptr; }
 bool dien_obs_mirror_used(const rl4rs_dien* n) { return n && n->obs_mirror_used; }
 void dien_drop_pending_expand(rl4rs_dien* n) { if (n) n->lazy.pending = false; }
+const LaneHook** dien_lane_slot(rl4rs_dien* n) { return &n->lanes; }
+int dien_n_cu(const rl4rs_dien* n) { return n ? n->n_cu : 0; }
+bool dien_lane_path(const rl4rs_dien* n, int rows) {
+    return n && n->t.fp16x2 && n->t.augru_x && n->t.row_dedup && n->alt.allf && n->alt.rows >= rows;
+}
+int dien_reserve_lane_scratch(rl4rs_dien* n, int rows) {
+    RL4RS_REQUIRE(n && rows > 0 && rows <= n->c.max_rows, "dien_reserve_lane_scratch: bad argument");
+    if (n->alt.allf && n->alt.rows >= rows) return RL4RS_OK;
+    // (a smaller set reserved earlier stays in `owned` until the handle goes: a forward may still be reading it.  Steppers of one
+    // batch size - the package's use - reserve once per scorer)
+    rl4rs_dien::ScratchSet a;
+    memset(&a, 0, sizeof(a));
+    const int padded = (rows + 63) / 64 * 64 + 64;      // whole row tiles and one to spare, as the first set has behind an observation-sized forward
+    const size_t R = (size_t)padded;
+    int rc;
+    if ((rc = alloc_f(n, &a.allf, R * n->Fld)) || (rc = alloc_f(n, &a.dh, R * n->U)) || (rc = alloc_f(n, &a.q, R * n->E)) ||
+        (rc = alloc_f(n, &a.qa, (size_t)n->S * R * ATT_H1)) || (rc = alloc_f(n, &a.scores, (size_t)n->S * R * n->L))) return rc;
+    if (n->tsum && (rc = alloc_f(n, &a.tsum, R * OBS_DIM))) return rc;
+    a.rows = padded;
+    n->alt = a;
+    return RL4RS_OK;
+}
+int dien_forward_lane(rl4rs_dien* n, int set, int32_t R, const float* dense, const int32_t* cat, const int32_t* slots, float* obs,
+                      void* stream, void* home) {
+    RL4RS_REQUIRE(n && (set == 0 || (set == 1 && n->alt.allf && R <= n->alt.rows)), "dien_forward_lane: no second scratch set of %d rows", R);
+    return dien_forward_on(n, set, (hipStream_t)home, R, 1, dense, cat, slots, obs, nullptr, stream);
+}
 bool dien_augru_rows64(const rl4rs_dien* n, int B, int group) {
     return n && n->t.fp16x2 && n->t.augru_x && (int64_t)B * group <= n->c.max_rows && augru_rows64(n->augru_rows, B * group, group, n->S, n->n_cu);
 }
@@ -2814,6 +2902,10 @@ const char* rl4rs_dien_kernel_name(int which) {
 // of kernel class `which` since the last rl4rs_dien_profile_reset.
 int rl4rs_dien_profile_read(rl4rs_dien* n, int which, double* ms_total, int64_t* launches) {
     RL4RS_REQUIRE(n && which >= 0 && which < KID_COUNT, "dien_profile_read: bad argument");
+    {   // (the pairs were recorded on the stream each kernel ran on, a lane's included)
+        const int rc = lanes_join(n->lanes, nullptr, false);
+        if (rc) return rc;
+    }
     for (auto& e : n->pending) {
         RL4RS_HIP_TRY(hipEventSynchronize(e.b));
         float ms = 0.f;

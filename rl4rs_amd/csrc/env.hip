@@ -497,7 +497,12 @@ struct rl4rs_env {
     int32_t* exposed; int32_t* feedback; int32_t* hist; float* ud; int32_t* ucat;
     int32_t* prev; uint32_t* amask; uint32_t* smask; float* dense; int32_t* cat; int32_t* seq1;
     float* c_dense; int32_t* c_cat; int32_t* err; int32_t* knn_tmp;
+    // the second set of state rows (env_flip_rows): d.dense / d.cat point at the current one of {dense, dense2} / {cat, cat2}
+    float* dense2; int32_t* cat2;
+    const rl4rs::LaneHook* lanes;      // the stepper whose lanes may have an act or a forward on this env's state in flight
 };
+// every entry point that is given a stream and touches what a lane may have in flight
+#define ENV_JOIN(e, stream) do { const int rc_join_ = rl4rs::lanes_join((e)->lanes, (stream)); if (rc_join_) return rc_join_; } while (0)
 
 static size_t rows_smem(const rl4rs_env* e, int waves, bool lds) {
     return (lds ? (((size_t)e->d.A * e->d.D * 4 + 15) & ~size_t(15)) : 0) + (size_t)waves * e->d.T * 4;
@@ -562,6 +567,16 @@ uint64_t next_stamp() {
     return ++stamp;
 }
 uint64_t env_rows_stamp(const rl4rs_env* e) { return e ? e->rows_stamp : 0; }
+const LaneHook** env_lane_slot(rl4rs_env* e) { return &e->lanes; }
+void env_flip_rows(rl4rs_env* e) {
+    const bool first = e->d.dense == e->dense;
+    e->d.dense = first ? e->dense2 : e->dense;
+    e->d.cat = first ? e->cat2 : e->cat;
+}
+void env_rows_current(const rl4rs_env* e, const float** dense, const int32_t** cat) {
+    *dense = e->d.dense;
+    *cat = e->d.cat;
+}
 bool env_refine_fits(const rl4rs_env* e) {
     const RowsLaunch L = rows_launch(e, e->cfg.batch_size, 1);
     return (L.smem > row_refine_smem(L.threads) ? L.smem : row_refine_smem(L.threads)) <= 65536;
@@ -651,6 +666,8 @@ int rl4rs_env_create(const rl4rs_env_cfg* c, rl4rs_env** out) {
     ALLOC(smask, (size_t)B * W);
     ALLOC(dense, (size_t)B * c->dense_feature_num);
     ALLOC(cat, (size_t)B * c->category_feature_num);
+    ALLOC(dense2, (size_t)B * c->dense_feature_num);
+    ALLOC(cat2, (size_t)B * c->category_feature_num);
     ALLOC(seq1, (size_t)B * c->maxlen);
     ALLOC(c_dense, (size_t)B * e->n_complete * c->dense_feature_num);
     ALLOC(c_cat, (size_t)B * e->n_complete * c->category_feature_num);
@@ -688,7 +705,9 @@ int rl4rs_env_destroy(rl4rs_env* e) {
     if (!e) return RL4RS_OK;
     void* ptrs[] = {e->item_vec, e->price, e->action_emb, e->special_bits, e->loc_bits, e->is_special,
                     e->exposed, e->feedback, e->hist, e->ud, e->ucat, e->prev, e->amask, e->smask,
-                    e->dense, e->cat, e->seq1, e->c_dense, e->c_cat, e->err, e->knn_tmp};
+                    e->dense, e->cat, e->seq1, e->c_dense, e->c_cat, e->err, e->knn_tmp, e->dense2, e->cat2};
+    (void)rl4rs::lanes_join(e->lanes, nullptr, false);
+    rl4rs::lanes_gone(e->lanes, rl4rs::LANE_LINK_ENV);      // the stepper forgets this env: it may be destroyed later
     for (void* p : ptrs) if (p) (void)hipFree(p);
     delete e;
     return RL4RS_OK;
@@ -697,6 +716,7 @@ int rl4rs_env_destroy(rl4rs_env* e) {
 int rl4rs_env_set_catalog(rl4rs_env* e, const float* item_vec, const double* price, const double* action_emb,
                           const uint8_t* is_special, const uint8_t* location_mask, void* stream) {
     RL4RS_REQUIRE(e && item_vec && price && action_emb && is_special && location_mask, "set_catalog: null argument");
+    ENV_JOIN(e, stream);
     hipStream_t st = (hipStream_t)stream;
     const int A = e->d.A, W = e->d.W;
     std::string bits((size_t)5 * W * 4, '\0');
@@ -721,6 +741,7 @@ int rl4rs_env_set_catalog(rl4rs_env* e, const float* item_vec, const double* pri
 int rl4rs_env_load_batch(rl4rs_env* e, const int32_t* exposed, const int32_t* feedback, const int32_t* hist,
                          const float* ud, const int32_t* ucat, void* stream) {
     RL4RS_REQUIRE(e && exposed && feedback && hist && ud && ucat, "load_batch: null argument");
+    ENV_JOIN(e, stream);
     hipStream_t st = (hipStream_t)stream;
     const EnvDev& d = e->d;
     RL4RS_HIP_TRY(hipMemcpyAsync(e->exposed, exposed, (size_t)d.B * d.logT * 4, hipMemcpyDeviceToDevice, st));
@@ -738,6 +759,7 @@ int rl4rs_env_load_lines(rl4rs_env* e, const int32_t* s_exposed, const int32_t* 
                          const int32_t* s_ucat, int32_t n_lines, int32_t store_log_steps, const int32_t* line_idx_dev,
                          const int32_t* uniq_idx_dev, int32_t n_uniq, int32_t* hist_unique_dev, void* stream) {
     RL4RS_REQUIRE(e && s_exposed && s_feedback && s_hist && s_ud && s_ucat && line_idx_dev && n_lines > 0, "load_lines: null argument");
+    ENV_JOIN(e, stream);
     RL4RS_REQUIRE(store_log_steps == e->d.logT, "load_lines: the log tables have %d logged steps per line, the env was created for %d",
                   store_log_steps, e->d.logT);
     RL4RS_REQUIRE(n_uniq >= 0 && (n_uniq == 0 || (uniq_idx_dev && hist_unique_dev)), "load_lines: distinct-history outputs missing");
@@ -753,6 +775,7 @@ int rl4rs_env_load_lines(rl4rs_env* e, const int32_t* s_exposed, const int32_t* 
 
 int rl4rs_env_reset(rl4rs_env* e, void* stream) {
     RL4RS_REQUIRE(e, "reset: null env");
+    ENV_JOIN(e, stream);
     if (!e->catalog_set || !e->batch_set) {
         set_error("rl4rs_env_reset: catalogue and batch must be loaded first");
         return RL4RS_ESTATE;
@@ -785,6 +808,8 @@ int rl4rs::env_act_discrete_tail(rl4rs_env* e, const int32_t* actions, const Act
 }
 extern "C" {
 int rl4rs_env_act_discrete(rl4rs_env* e, const int32_t* actions, void* stream) {
+    RL4RS_REQUIRE(e, "act_discrete: null argument");
+    ENV_JOIN(e, stream);
     return rl4rs::env_act_discrete_tail(e, actions, ActTail(), stream, nullptr);
 }
 
@@ -823,6 +848,8 @@ static int knn_launch(const void* actions, int is_f64, int n, const double* emb,
 }
 
 int rl4rs_env_act_conti(rl4rs_env* e, const void* actions, int is_f64, int32_t* chosen, void* stream) {
+    RL4RS_REQUIRE(e, "act_conti: null argument");
+    ENV_JOIN(e, stream);
     return rl4rs::env_act_conti_refine(e, actions, is_f64, chosen, stream, nullptr);
 }
 }  // extern "C"
@@ -879,6 +906,7 @@ int rl4rs_env_build_complete_rows(rl4rs_env* e, int32_t rows_per_env, void* stre
     RL4RS_REQUIRE(e, "build_complete: null env");
     RL4RS_REQUIRE(rows_per_env >= 1 && rows_per_env <= e->n_complete, "build_complete: rows_per_env=%d not in 1..%d",
                   rows_per_env, e->n_complete);
+    ENV_JOIN(e, stream);
     int jb = complete_base(e);
     if (jb < 0 || jb + e->n_complete > e->d.T) {
         set_error("build_complete: cur_steps=%d has no complete page", e->cur_steps);
@@ -896,6 +924,7 @@ int rl4rs_env_reward(rl4rs_env* e, const float* probs, double* reward, void* str
 
 int rl4rs_env_reward_split(rl4rs_env* e, const float* probs, const float* p_last, double* reward, void* stream) {
     RL4RS_REQUIRE(e && probs && reward, "reward: null argument");
+    ENV_JOIN(e, stream);
     int jb = complete_base(e);
     if (jb < 0 || jb + e->n_complete > e->d.T) {
         set_error("reward: cur_steps=%d has no complete page", e->cur_steps);
@@ -909,6 +938,7 @@ int rl4rs_env_reward_split(rl4rs_env* e, const float* probs, const float* p_last
 
 int rl4rs_env_violation(rl4rs_env* e, int32_t* out, void* stream) {
     RL4RS_REQUIRE(e && out, "violation: null argument");
+    ENV_JOIN(e, stream);
     hipLaunchKernelGGL(k_violation, dim3((e->d.B + 127) / 128), dim3(128), 0, (hipStream_t)stream, e->d,
                        e->cur_steps, out);
     RL4RS_LAUNCH_CHECK();
@@ -917,6 +947,7 @@ int rl4rs_env_violation(rl4rs_env* e, int32_t* out, void* stream) {
 
 int rl4rs_env_obs_mask(rl4rs_env* e, void* out, int dtype, void* stream) {
     RL4RS_REQUIRE(e && out && dtype >= 0 && dtype <= 4, "obs_mask: bad argument");
+    ENV_JOIN(e, stream);
     const EnvDev& d = e->d;
     int layer = d.is_seq ? (e->cur_steps % d.P) / 3 : e->cur_steps / 3;   // POST-increment (slate.py:93)
     RL4RS_REQUIRE(layer < 4, "location layer %d out of range (cur_steps=%d)", layer, e->cur_steps);
@@ -935,6 +966,7 @@ int rl4rs_env_obs_mask(rl4rs_env* e, void* out, int dtype, void* stream) {
 
 int rl4rs_env_offline_action(rl4rs_env* e, int32_t* ids, double* emb, void* stream) {
     RL4RS_REQUIRE(e && (ids || emb), "offline_action: null argument");
+    ENV_JOIN(e, stream);
     hipLaunchKernelGGL(k_offline_action, dim3((e->d.B + 127) / 128), dim3(128), 0, (hipStream_t)stream, e->d,
                        e->cur_steps, ids, emb);
     RL4RS_LAUNCH_CHECK();
@@ -943,6 +975,7 @@ int rl4rs_env_offline_action(rl4rs_env* e, int32_t* ids, double* emb, void* stre
 
 int rl4rs_env_offline_reward(rl4rs_env* e, double* out, void* stream) {
     RL4RS_REQUIRE(e && out, "offline_reward: null argument");
+    ENV_JOIN(e, stream);
     hipLaunchKernelGGL(k_offline_reward, dim3((e->d.B + 127) / 128), dim3(128), 0, (hipStream_t)stream, e->d,
                        e->cur_steps, out);
     RL4RS_LAUNCH_CHECK();
@@ -952,6 +985,7 @@ int rl4rs_env_offline_reward(rl4rs_env* e, double* out, void* stream) {
 int rl4rs_env_predict_with_mask(rl4rs_env* e, int32_t N, const float* scores, const int32_t* prev, int32_t prev_cols,
                                 const int32_t* cur_step, int32_t* out, void* stream) {
     RL4RS_REQUIRE(e && scores && prev && cur_step && out && N > 0 && prev_cols > 0, "predict_with_mask: bad argument");
+    ENV_JOIN(e, stream);
     if (!e->catalog_set) {
         set_error("predict_with_mask: catalogue not loaded");
         return RL4RS_ESTATE;
@@ -964,6 +998,10 @@ int rl4rs_env_predict_with_mask(rl4rs_env* e, int32_t N, const float* scores, co
 
 int rl4rs_env_buffer(rl4rs_env* e, int which, void** p, int64_t* n) {
     RL4RS_REQUIRE(e && p, "env_buffer: null argument");
+    {   // no stream is given here: the host waits for a lane transition in flight
+        const int rc_join = rl4rs::lanes_join(e->lanes, nullptr, false);
+        if (rc_join) return rc_join;
+    }
     const EnvDev& d = e->d;
     int64_t bytes = 0;
     void* ptr = nullptr;
@@ -971,8 +1009,8 @@ int rl4rs_env_buffer(rl4rs_env* e, int which, void** p, int64_t* n) {
         case RL4RS_BUF_PREV_ACTIONS: ptr = e->prev; bytes = (int64_t)d.B * d.T * 4; break;
         case RL4RS_BUF_ACTION_MASK: ptr = e->amask; bytes = (int64_t)d.B * d.W * 4; break;
         case RL4RS_BUF_SPECIAL_MASK: ptr = e->smask; bytes = (int64_t)d.B * d.W * 4; break;
-        case RL4RS_BUF_DENSE: ptr = e->dense; bytes = (int64_t)d.B * d.Dn * 4; break;
-        case RL4RS_BUF_CATEGORY: ptr = e->cat; bytes = (int64_t)d.B * d.Cn * 4; break;
+        case RL4RS_BUF_DENSE: ptr = e->d.dense; bytes = (int64_t)d.B * d.Dn * 4; break;
+        case RL4RS_BUF_CATEGORY: ptr = e->d.cat; bytes = (int64_t)d.B * d.Cn * 4; break;
         case RL4RS_BUF_SEQ0: ptr = e->hist; bytes = (int64_t)d.B * d.L * 4; break;
         case RL4RS_BUF_SEQ1: ptr = e->seq1; bytes = (int64_t)d.B * d.L * 4; break;
         case RL4RS_BUF_C_DENSE: ptr = e->c_dense; bytes = (int64_t)d.B * e->n_complete * d.Dn * 4; break;

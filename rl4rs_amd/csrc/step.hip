@@ -10,8 +10,19 @@
 // allocated and nothing synchronises inside: all scratch belongs to the binding created by rl4rs_env_attach_scorer.
 #include "common.hpp"
 #include "row_refine.hpp"
+#include "step_lanes.hpp"
 
 using namespace rl4rs;
+
+// One of the stepper's two lanes (step_lanes.hpp): a stream, its events and its own copy of what a transition hands out
+struct StepLane {
+    hipStream_t st;
+    hipEvent_t act_done;       // behind the act: env state, partition and logged-action row of the transition are written
+    hipEvent_t done;           // behind the lane's last launch
+    hipEvent_t handed;         // on the CALLER's stream, behind the copy of obs / reward out of the lane's buffers
+    float* obs;                // [B, 256]
+    double* reward;            // [B]
+};
 
 struct rl4rs_stepper {
     rl4rs_env* env;
@@ -45,6 +56,17 @@ struct rl4rs_stepper {
     int32_t* part_cnt;         // [0] n_active, [1] ticket, [2] envs that split off in the act in flight
     const int32_t* part_order; // the scorer's row order the active list was built in
     uint64_t part_stamp;       // the env's row stamp behind the act that left the partition
+    // Two lanes for consecutive transitions (rl4rs_stepper_set_step_overlap, default on).  A lane transition flips the env's state-row
+    // set and the active list / counter pair below, so that its act writes none of what the previous forward still reads.
+    bool overlap;
+    bool lanes_made;
+    StepLane lane[2];
+    hipEvent_t ev_entry;       // recorded on the caller's stream where a lane has to wait for it
+    LaneState lstate;
+    LaneHook hook;             // what the env and the scorer call before they touch anything a lane may have in flight
+    LaneLinks links;           // where the env / the scorer keep their pointer to `hook`; forgotten when that handle goes first
+    int32_t* part_active_alt;  // [B]   the pair a lane transition's act writes (then exchanged with part_active / part_cnt)
+    int32_t* part_cnt_alt;     // [4]
     hipStream_t copy_stream;   // rl4rs_env_step_record_host: early device-to-host copies run here, beside the scorer's kernels
     hipEvent_t ev_ready, ev_copied;
 };
@@ -90,6 +112,51 @@ __global__ void k_step_tail(uint8_t* done, uint8_t v, double* zero_reward, int n
     }
 }
 
+// what a lane transition hands out: observation and reward from the lane's buffers into the caller's, on the caller's stream
+__global__ void k_lane_handout(const float* __restrict__ obs_src, float* __restrict__ obs_dst, int64_t n_obs,
+                               const double* __restrict__ reward_src, double* __restrict__ reward_dst, int B) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_obs) obs_dst[i] = obs_src[i];
+    if (reward_dst && i < B) reward_dst[i] = reward_src[i];
+}
+
+// ---- lanes
+// the stream a caller gave waits for everything in flight on the lanes (have_stream == 0: the host does)
+int lanes_wait(rl4rs_stepper* s, void* stream, int have_stream) {
+    const bool used[2] = {s->lstate.used[0], s->lstate.used[1]};
+    if (!lane_join(s->lstate)) return RL4RS_OK;
+    for (int i = 0; i < 2; ++i) {
+        if (!used[i]) continue;
+        if (have_stream) RL4RS_HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, s->lane[i].done, 0));
+        else RL4RS_HIP_TRY(hipStreamSynchronize(s->lane[i].st));
+    }
+    return RL4RS_OK;
+}
+int hook_join(void* ctx, void* stream, int have_stream) { return lanes_wait(reinterpret_cast<rl4rs_stepper*>(ctx), stream, have_stream); }
+// the env or the scorer is being destroyed, or another stepper took it over (it has joined the lanes first): this stepper no longer
+// touches that handle - not in its own destroy either - and runs no lane transition from here on
+void hook_gone(void* ctx, int which) {
+    rl4rs_stepper* s = reinterpret_cast<rl4rs_stepper*>(ctx);
+    lane_links_gone(s->links, which);
+    s->overlap = false;
+}
+
+int make_lanes(rl4rs_stepper* s) {
+    const size_t B = (size_t)s->cfg.batch_size;
+    RL4RS_HIP_TRY(hipEventCreateWithFlags(&s->ev_entry, hipEventDisableTiming));
+    for (int i = 0; i < 2; ++i) {
+        StepLane& l = s->lane[i];
+        RL4RS_HIP_TRY(hipStreamCreateWithFlags(&l.st, hipStreamNonBlocking));
+        RL4RS_HIP_TRY(hipEventCreateWithFlags(&l.act_done, hipEventDisableTiming));
+        RL4RS_HIP_TRY(hipEventCreateWithFlags(&l.done, hipEventDisableTiming));
+        RL4RS_HIP_TRY(hipEventCreateWithFlags(&l.handed, hipEventDisableTiming));
+        int rc;
+        if ((rc = dev_alloc(&l.obs, B * 256)) || (rc = dev_alloc(&l.reward, B))) return rc;
+    }
+    s->lanes_made = true;
+    return RL4RS_OK;
+}
+
 // everything after the act: observation, reward (when due), done, packed obs-side mask.  `on_obs` runs right after the
 // observation forward has been enqueued (the record form sends the observation home from there on a reward step, beside the
 // reward forward).
@@ -106,6 +173,7 @@ struct NoHook { int operator()() const { return RL4RS_OK; } };
 // forwards of this transition look for duplicates themselves.
 bool plan_refine(rl4rs_stepper* s, int cur, RowRefineArgs* rf) {
     s->part_now = false;
+    env_rows_current(s->env, &s->dense, &s->cat);
     const int B = s->cfg.batch_size;
     const bool was_valid = s->part_valid;
     s->part_valid = false;
@@ -235,6 +303,63 @@ __global__ void k_record_status(const int32_t* env_err, int32_t* range_flag, int
     }
 }
 
+// A transition on lane lp.on (step_lanes.hpp decided that, and what it waits for): the act and the observation forward of
+// rl4rs_env_step_discrete, the same launches with the same arguments but for the stream, the state-row set, the active list /
+// counter pair, the scorer's scratch set and the head's output pointer.
+int lane_transition(rl4rs_stepper* s, const LanePlan& lp, const LaneState& before, int cur, RowRefineArgs* rf, const int32_t* actions_dev, float* obs_dev,
+                    double* reward_dev, void* stream) {
+    hipStream_t home = (hipStream_t)stream;
+    StepLane& l = s->lane[lp.on];
+    const int B = s->cfg.batch_size;
+    if (lp.wait_entry) {
+        RL4RS_HIP_TRY(hipEventRecord(s->ev_entry, home));
+        RL4RS_HIP_TRY(hipStreamWaitEvent(l.st, s->ev_entry, 0));
+    }
+    if (lp.wait_act) RL4RS_HIP_TRY(hipStreamWaitEvent(l.st, s->lane[lp.on ^ 1].act_done, 0));
+    if (lp.wait_handout) RL4RS_HIP_TRY(hipStreamWaitEvent(l.st, l.handed, 0));
+    // the act writes the other row set and the other active list / counter pair: the previous forward (other lane) reads the current
+    // ones, the forward before it (this lane, stream order) has finished with those the act now writes
+    if (!rf->active_src) { rf->active_src = s->part_active; rf->n_active_src = s->part_cnt; }
+    rf->active = s->part_active_alt;
+    rf->cnt = s->part_cnt_alt;
+    env_flip_rows(s->env);             // (the act kernel takes the env's current set: flipped in front of it, back if nothing was enqueued)
+    ActTail tail;
+    tail.done = nullptr; tail.done_v = 0;
+    tail.zero_reward = reward_dev ? l.reward : nullptr;
+    tail.next_action = s->next_off + (size_t)(cur + 1) * B;      // (cur + 1 <= T: a lane transition has no reward due)
+    tail.next_cur = cur + 1;
+    int rc = rl4rs::env_act_discrete_tail(s->env, actions_dev, tail, l.st, rf);
+    if (rc) {
+        // nothing of the transition was enqueued: the row set, the partition pairs and the lane state stand as they were
+        env_flip_rows(s->env);
+        env_rows_current(s->env, &s->dense, &s->cat);
+        lane_undo(s->lstate, before);
+        return rc;
+    }
+    // the act is on the lane: from here on the pairs it wrote are the current ones
+    std::swap(s->part_active, s->part_active_alt);
+    std::swap(s->part_cnt, s->part_cnt_alt);
+    env_rows_current(s->env, &s->dense, &s->cat);
+    refined(s);
+    s->next_off_cur = cur + 1;
+    RL4RS_HIP_TRY(hipEventRecord(l.act_done, l.st));
+    if ((rc = rl4rs_dien_set_row_partition(s->dien, s->part_rep[s->part_cur], s->part_active, s->part_cnt, B)) ||
+        (rc = dien_forward_lane(s->dien, lp.on, B, s->dense, s->cat, s->slots, l.obs, l.st, stream))) {
+        // the act happened, the observation did not: the lane still gets its `done` (the state says it is in flight, a join waits
+        // for that event) and the caller the error; the env is where the act left it, as after a failed forward on the caller's stream
+        (void)hipEventRecord(l.done, l.st);
+        return rc;
+    }
+    RL4RS_HIP_TRY(hipEventRecord(l.done, l.st));
+    // hand-out: the caller's blocks are written on the caller's stream only
+    RL4RS_HIP_TRY(hipStreamWaitEvent(home, l.done, 0));
+    const int64_t n_obs = (int64_t)B * 256;
+    hipLaunchKernelGGL(k_lane_handout, dim3((unsigned)((n_obs + 255) / 256)), dim3(256), 0, home, l.obs, obs_dev, n_obs, l.reward, reward_dev, B);
+    RL4RS_LAUNCH_CHECK();
+    RL4RS_HIP_TRY(hipEventRecord(l.handed, home));
+    return RL4RS_OK;
+}
+
 int attach(rl4rs_env* env, rl4rs_dien* dien, rl4rs_simnet* simnet, const int32_t* slots_dev, int32_t seq_num, rl4rs_stepper** out) {
     RL4RS_REQUIRE(env && (dien || simnet) && slots_dev && out && seq_num >= 1 && seq_num <= 4, "env_attach_scorer: bad argument");
     rl4rs_stepper* s = new rl4rs_stepper();
@@ -255,14 +380,29 @@ int attach(rl4rs_env* env, rl4rs_dien* dien, rl4rs_simnet* simnet, const int32_t
     s->next_off = reinterpret_cast<int32_t*>(ring);
     s->next_off_cur = -1;
     if (dien) {
-        float* part = nullptr;          // rep x 2, active, counters
-        if ((rc = dev_alloc(&part, 3 * B + 4))) { rl4rs_stepper_destroy(s); return rc; }
+        float* part = nullptr;          // rep x 2, active x 2, counters x 2
+        if ((rc = dev_alloc(&part, 4 * B + 8))) { rl4rs_stepper_destroy(s); return rc; }
         s->part_rep[0] = reinterpret_cast<int32_t*>(part);
         s->part_rep[1] = s->part_rep[0] + B;
         s->part_active = s->part_rep[1] + B;
-        s->part_cnt = s->part_active + B;
-        if (hipMemset(s->part_cnt, 0, 16) != hipSuccess) { rl4rs_stepper_destroy(s); set_error("env_attach_scorer: hipMemset failed"); return RL4RS_EHIP; }
+        s->part_active_alt = s->part_active + B;
+        s->part_cnt = s->part_active_alt + B;
+        s->part_cnt_alt = s->part_cnt + 4;
+        if (hipMemset(s->part_cnt, 0, 32) != hipSuccess) { rl4rs_stepper_destroy(s); set_error("env_attach_scorer: hipMemset failed"); return RL4RS_EHIP; }
         s->carry = true;
+    }
+    // the lanes: a stepper attached earlier to this env or scorer may still have a transition in flight (the host waits, once)
+    s->hook.ctx = s;
+    s->hook.join = hook_join;
+    s->hook.gone = hook_gone;
+    lane_links_attach(s->links, LANE_LINK_ENV, env_lane_slot(env), &s->hook);
+    if (dien) {
+        lane_links_attach(s->links, LANE_LINK_SCORER, dien_lane_slot(dien), &s->hook);
+        if (dien_takes_partition(dien) && ((rc = make_lanes(s)) || (rc = dien_reserve_lane_scratch(dien, s->cfg.batch_size)))) {
+            rl4rs_stepper_destroy(s);
+            return rc;
+        }
+        s->overlap = s->lanes_made;
     }
     s->act_tail = true;
     s->obs_fold = true;
@@ -293,6 +433,20 @@ int rl4rs_env_attach_simnet(rl4rs_env* env, rl4rs_simnet* net, const int32_t* sl
 
 int rl4rs_stepper_destroy(rl4rs_stepper* s) {
     if (!s) return RL4RS_OK;
+    (void)lanes_wait(s, nullptr, 0);
+    lane_links_release(s->links, &s->hook);      // (neither handle is touched if it went first: hook_gone has been told)
+    if (s->lanes_made || s->ev_entry) {
+        if (s->ev_entry) (void)hipEventDestroy(s->ev_entry);
+        for (int i = 0; i < 2; ++i) {
+            StepLane& l = s->lane[i];
+            if (l.st) { (void)hipStreamSynchronize(l.st); (void)hipStreamDestroy(l.st); }
+            if (l.act_done) (void)hipEventDestroy(l.act_done);
+            if (l.done) (void)hipEventDestroy(l.done);
+            if (l.handed) (void)hipEventDestroy(l.handed);
+            if (l.obs) (void)hipFree(l.obs);
+            if (l.reward) (void)hipFree(l.reward);
+        }
+    }
     if (s->probs) (void)hipFree(s->probs);
     if (s->p_last) (void)hipFree(s->p_last);
     if (s->next_off) (void)hipFree(s->next_off);
@@ -308,9 +462,31 @@ int rl4rs_env_step_discrete(rl4rs_stepper* s, const int32_t* actions_dev, float*
                             uint32_t* mask_bits_dev, void* stream) {
     RL4RS_REQUIRE(s && actions_dev && obs_dev, "env_step_discrete: null argument");
     const int cur = rl4rs_env_cur_steps(s->env);
+    // the caller hands back the logged-action row the previous transition's act wrote: nothing of its own stream is needed
+    const bool own_row = s->next_off_cur == cur && cur >= 0 && actions_dev == s->next_off + (size_t)cur * s->cfg.batch_size;
     s->next_off_cur = -1;
     RowRefineArgs rf;
     const bool refine = plan_refine(s, cur, &rf);
+    {
+        const int T = s->cfg.max_steps;
+        LaneCall c;
+        memset(&c, 0, sizeof(c));
+        c.overlap = s->overlap && s->act_tail && cur < T && lane_links_mine(s->links, LANE_LINK_ENV, &s->hook) &&
+                    lane_links_mine(s->links, LANE_LINK_SCORER, &s->hook);
+        c.dien_x = s->dien && dien_lane_path(s->dien, s->cfg.batch_size);
+        c.carried = refine;
+        c.reward_due = s->cfg.is_seq ? (cur + 1) % s->cfg.page_items == 0 : cur + 1 >= T;
+        c.extra_outputs = mask_bits_dev != nullptr || done_dev != nullptr;
+        c.own_row = own_row;
+        c.seq_num = s->seq_num; c.distinct_hint = s->distinct_hint; c.n_cu = s->dien ? dien_n_cu(s->dien) : 0;
+        const LaneState before = s->lstate;
+        const LanePlan lp = lane_decide(s->lstate, c);
+        if (lp.lane) return lane_transition(s, lp, before, cur, &rf, actions_dev, obs_dev, reward_dev, stream);
+        // (lane_decide has joined the state; the waits go to the caller's stream)
+        if (lp.join) {
+            for (int i = 0; i < 2; ++i) RL4RS_HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, s->lane[i].done, 0));
+        }
+    }
     if (!s->act_tail) {
         int rc = rl4rs::env_act_discrete_tail(s->env, actions_dev, ActTail(), stream, refine ? &rf : nullptr);
         if (rc) return rc;
@@ -354,10 +530,25 @@ int rl4rs_stepper_set_partition_carry(rl4rs_stepper* s, int32_t on) {
     return RL4RS_OK;
 }
 
+int rl4rs_stepper_set_step_overlap(rl4rs_stepper* s, int32_t on) {
+    RL4RS_REQUIRE(s, "stepper_set_step_overlap: null argument");
+    s->overlap = on != 0 && s->lanes_made;
+    return RL4RS_OK;
+}
+
+int rl4rs_stepper_lane_stats(const rl4rs_stepper* s, int64_t* lane0, int64_t* lane1, int64_t* joins) {
+    RL4RS_REQUIRE(s, "stepper_lane_stats: null argument");
+    if (lane0) *lane0 = s->lstate.ran[0];
+    if (lane1) *lane1 = s->lstate.ran[1];
+    if (joins) *joins = s->lstate.joins;
+    return RL4RS_OK;
+}
+
 int rl4rs_stepper_reward_rows(const rl4rs_stepper* s) { return s ? s->probs_rows : RL4RS_EINVAL; }
 
 int rl4rs_stepper_click_probs(rl4rs_stepper* s, float* out_dev, void* stream) {
     RL4RS_REQUIRE(s && out_dev, "stepper_click_probs: null argument");
+    { const int rcj = lanes_wait(s, stream, 1); if (rcj) return rcj; }
     RL4RS_REQUIRE(s->n_complete >= 2 && s->probs_rows > 0, "stepper_click_probs: no reward step yet");
     const int B = s->cfg.batch_size, n = s->n_complete;
     hipStream_t st = (hipStream_t)stream;
@@ -387,6 +578,7 @@ int rl4rs_stepper_next_offline_action(rl4rs_stepper* s, const int32_t** ids_dev,
 int rl4rs_env_step_conti(rl4rs_stepper* s, const void* actions_dev, int is_f64, int32_t* chosen_dev, float* obs_dev,
                          double* reward_dev, uint8_t* done_dev, uint32_t* mask_bits_dev, void* stream) {
     RL4RS_REQUIRE(s && actions_dev && obs_dev, "env_step_conti: null argument");
+    { const int rcj = lanes_wait(s, stream, 1); if (rcj) return rcj; }
     const int cur = rl4rs_env_cur_steps(s->env);
     s->next_off_cur = -1;
     RowRefineArgs rf;
@@ -443,6 +635,8 @@ static int step_record(rl4rs_stepper* s, bool observe, const void* actions_dev, 
     rl4rs_step_record L;
     int rc = rl4rs_stepper_record_layout(s, want, action_kind != 0, &L);
     if (rc) return rc;
+    if ((rc = lanes_wait(s, stream, 1))) return rc;
+    env_rows_current(s->env, &s->dense, &s->cat);
     hipStream_t st = (hipStream_t)stream;
     char* R = reinterpret_cast<char*>(record_dev);
     const int B = s->cfg.batch_size;

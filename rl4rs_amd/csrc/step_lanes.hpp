@@ -1,0 +1,124 @@
+// Which stream a transition of rl4rs_env_step_discrete runs on, and what it waits for.  The observation-sized AUGRU
+// launch is bound by one workgroup's 64-step chain and fills less than half of the chip once the row dedup has run;
+// in a replay loop transition k + 1 needs nothing of transition k's scorer forward - only the env state, the partition and the
+// logged-action row the ACT of k left.  The stepper therefore owns two lanes (a stream and its events each) and runs consecutive
+// eligible transitions on them in turn: the forward of k + 1 starts beside the forward of k.
+// Host code only, nothing from HIP (as dien_plan.hpp): step.hip carries out what lane_decide returns, tests/test_step_lanes_host.py
+// replays call sequences through it without a device.
+#pragma once
+#include <stdint.h>
+
+namespace rl4rs {
+
+// the workgroups two observation-sized k_augru_xs / k_augru_x launches bring: they co-run only where both fit the chip at once
+inline int64_t lane_pair_workgroups(int seq_num, int distinct_hint) { return 2 * (int64_t)seq_num * ((distinct_hint + 31) / 32); }
+
+// what step.hip knows about the call in front of its act
+struct LaneCall {
+    bool overlap;          // rl4rs_stepper_set_step_overlap (and the env / scorer handles still point at this stepper's lanes)
+    bool dien_x;           // the scorer is the DIEN on the k_augru_x / k_augru_xs path (fp16x2)
+    bool carried;          // plan_refine returned true: the act carries the partition (false on a SeqSlate page turn)
+    bool reward_due;       // a reward is due after this act
+    bool extra_outputs;    // mask_bits_dev or done_dev asked for
+    bool own_row;          // actions_dev is the logged-action row the previous transition's act wrote
+    int seq_num, distinct_hint, n_cu;
+};
+
+inline bool lane_eligible(const LaneCall& c) {
+    return c.overlap && c.dien_x && c.carried && !c.reward_due && !c.extra_outputs &&
+           lane_pair_workgroups(c.seq_num, c.distinct_hint) <= c.n_cu;
+}
+
+// host-side record of what is in flight
+struct LaneState {
+    int next;              // the lane of the next lane transition (they alternate)
+    bool in_flight;        // a lane transition was issued since the last join
+    bool used[2];          // ... on this lane: its `done` and hand-out events are recorded
+    int last;              // the lane of the last lane transition (valid while in_flight)
+    int64_t ran[2];        // lane transitions issued on each lane, joins carried out (rl4rs_stepper_lane_stats)
+    int64_t joins;
+};
+
+struct LanePlan {
+    bool lane;             // true: the transition runs on lane `on`; false: on the caller's stream, with today's launches
+    int on;
+    bool join;             // (lane == false) the caller's stream first waits for `done` of every lane in flight
+    bool wait_entry;       // record the entry event on the caller's stream, the lane waits for it: a foreign action, or the
+                           // first lane transition behind work on the caller's stream
+    bool wait_act;         // the lane waits for `act_done` of lane `on ^ 1` (env state, partition, logged-action row of k - 1)
+    bool wait_handout;     // the lane waits for the hand-out copy of its own previous transition (it rewrites the lane's
+                           // observation and reward buffers); implied by wait_entry, which the caller's stream records behind it
+};
+
+// join: everything in flight is waited for by the stream the caller gave (step.hip issues the waits when this returns true)
+inline bool lane_join(LaneState& s) {
+    const bool any = s.in_flight;
+    if (any) s.joins += 1;
+    s.in_flight = false;
+    s.used[0] = s.used[1] = false;
+    return any;
+}
+
+// a transition that lane_decide placed on a lane could not be enqueued (its act failed before anything was launched): the state
+// as it was in front of lane_decide (the caller kept a copy) stands again
+inline void lane_undo(LaneState& s, const LaneState& before) { s = before; }
+
+// ---- the links between a stepper and the env / scorer handles it is attached to
+// The env and the scorer hold a pointer to the stepper's hook and call lanes_join through it in front of everything that touches what
+// a lane may have in flight.  Any of the three may be destroyed first, and a later stepper may take a handle over: whoever goes (or
+// is replaced) tells the other side, so that nobody keeps a pointer into freed memory.
+//   - a handle that is destroyed: lanes_join (the host waits), then lanes_gone - the stepper forgets the handle;
+//   - a stepper that is destroyed: lane_links_release - the handles that still point at its hook forget it;
+//   - a stepper that attaches to a handle another stepper holds: lane_links_attach joins the old one and tells it the handle is gone.
+// A stepper runs lanes only while lane_links_mine holds for its env and its scorer.
+enum { LANE_LINK_ENV = 0, LANE_LINK_SCORER = 1 };
+struct LaneHook {
+    void* ctx;
+    int (*join)(void* ctx, void* stream, int have_stream);      // 0 = ok
+    void (*gone)(void* ctx, int which);                         // the handle `which` no longer points at this hook
+};
+inline int lanes_join(const LaneHook* h, void* stream, bool have_stream = true) {
+    return h ? h->join(h->ctx, stream, have_stream ? 1 : 0) : 0;
+}
+inline void lanes_gone(const LaneHook* h, int which) {
+    if (h && h->gone) h->gone(h->ctx, which);
+}
+// the stepper's side: where each handle keeps its pointer to the hook, NULL = never attached, gone or taken over
+struct LaneLinks { const LaneHook** slot[2]; };
+inline void lane_links_attach(LaneLinks& l, int which, const LaneHook** slot, const LaneHook* hook) {
+    if (*slot && *slot != hook) {
+        (void)lanes_join(*slot, nullptr, false);
+        lanes_gone(*slot, which);
+    }
+    *slot = hook;
+    l.slot[which] = slot;
+}
+inline void lane_links_gone(LaneLinks& l, int which) { l.slot[which] = nullptr; }
+inline bool lane_links_mine(const LaneLinks& l, int which, const LaneHook* hook) { return l.slot[which] && *l.slot[which] == hook; }
+inline void lane_links_release(LaneLinks& l, const LaneHook* hook) {
+    for (int w = 0; w < 2; ++w) {
+        if (lane_links_mine(l, w, hook)) *l.slot[w] = nullptr;
+        l.slot[w] = nullptr;
+    }
+}
+
+inline LanePlan lane_decide(LaneState& s, const LaneCall& c) {
+    LanePlan p = {};
+    if (!lane_eligible(c)) {
+        p.join = lane_join(s);
+        return p;
+    }
+    p.lane = true;
+    p.on = s.next;
+    p.wait_act = s.in_flight;                       // transition k - 1 ran on the other lane: lanes alternate
+    p.wait_entry = !s.in_flight || !c.own_row;
+    p.wait_handout = !p.wait_entry && s.used[p.on];
+    s.in_flight = true;
+    s.used[p.on] = true;
+    s.last = p.on;
+    s.ran[p.on] += 1;
+    s.next = p.on ^ 1;
+    return p;
+}
+
+}  // namespace rl4rs

@@ -332,13 +332,14 @@ class DeviceStepper(object):
     """rl4rs_stepper handle: an env bound to its scorer so that one call runs a whole transition
     (rl4rs_env_step_discrete / rl4rs_env_step_conti = RecSimBase._step, base.py:157-170)."""
 
-    def __init__(self, env, net, slots, act_tail=True, obs_fold=True, partition_carry=True):
+    def __init__(self, env, net, slots, act_tail=True, obs_fold=True, partition_carry=True, step_overlap=True):
         """``act_tail=False`` (config['no_act_tail'] / RL4RS_NO_ACT_TAIL=1): rl4rs_env_step_discrete launches k_step_tail as it
         did and leaves no next-step logged actions (rl4rs_stepper_set_act_tail).  ``obs_fold=False``
         (config['no_reward_obs_fold'] / RL4RS_NO_REWARD_OBS_FOLD=1): a reward step runs its observation forward and then the
         reward forward of n - 1 rows per env, as it did (rl4rs_stepper_set_obs_fold).  ``partition_carry=False``
         (config['no_partition_carry'] / RL4RS_NO_PARTITION_CARRY=1): every scorer forward of a transition looks for its duplicate
-        rows itself, as it did (rl4rs_stepper_set_partition_carry)."""
+        rows itself, as it did (rl4rs_stepper_set_partition_carry).  ``step_overlap=False`` (config['no_step_overlap'] /
+        RL4RS_NO_STEP_OVERLAP=1): every transition runs on the caller's stream (rl4rs_stepper_set_step_overlap)."""
         self.lib = _lib.load()
         self.env, self.net, self.slots = env, net, slots          # keep the handles and the slot table alive
         assert slots.dtype == torch.int32 and slots.is_contiguous() and slots.shape[1] == env.B
@@ -353,6 +354,8 @@ class DeviceStepper(object):
             check(self.lib.rl4rs_stepper_set_obs_fold(self.h, 0))
         if not partition_carry:
             check(self.lib.rl4rs_stepper_set_partition_carry(self.h, 0))
+        if not step_overlap:
+            check(self.lib.rl4rs_stepper_set_step_overlap(self.h, 0))
         self._distinct_hint = None
         self.B, self.A, self.E, self.W, self.device = env.B, env.A, env.E, env.W, env.device
         self.obs_dim = int(getattr(net, 'obs_dim', 256))         # 256 for DIEN / dnn / lstm, 256 + U + Cn*E for widedeep
@@ -375,6 +378,12 @@ class DeviceStepper(object):
         if n != self._distinct_hint:
             check(self.lib.rl4rs_stepper_set_distinct_hint(self.h, n))
             self._distinct_hint = n
+
+    def lane_stats(self):
+        """(transitions run on lane 0, on lane 1, joins) since the stepper was created (rl4rs_stepper_lane_stats)."""
+        a, b, j = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        check(self.lib.rl4rs_stepper_lane_stats(self.h, C.byref(a), C.byref(b), C.byref(j)))
+        return int(a.value), int(b.value), int(j.value)
 
     def reward_rows(self):
         """Rows per env the last reward step's reward forward scored (rl4rs_stepper_reward_rows)."""

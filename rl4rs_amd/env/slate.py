@@ -613,7 +613,10 @@ class SlateRecEnv(RecSimBase):
             no_fold = self.config.get('no_reward_obs_fold', os.environ.get('RL4RS_NO_REWARD_OBS_FOLD', '') not in ('', '0'))
             # config['no_partition_carry'] (RL4RS_NO_PARTITION_CARRY=1): every forward of a transition compares whole rows again
             no_carry = self.config.get('no_partition_carry', os.environ.get('RL4RS_NO_PARTITION_CARRY', '') not in ('', '0'))
-            self._stepper = D.DeviceStepper(env, net, slots, act_tail=not no_tail, obs_fold=not no_fold, partition_carry=not no_carry)
+            # config['no_step_overlap'] (RL4RS_NO_STEP_OVERLAP=1): consecutive transitions on the caller's stream, one behind the other
+            no_overlap = self.config.get('no_step_overlap', os.environ.get('RL4RS_NO_STEP_OVERLAP', '') not in ('', '0'))
+            self._stepper = D.DeviceStepper(env, net, slots, act_tail=not no_tail, obs_fold=not no_fold, partition_carry=not no_carry,
+                                            step_overlap=not no_overlap)
             self._stepper_key = key
         # envs the scorer's row dedup is expected to leave: the batch's distinct log lines - but SeqSlate gives every env a slot of
         # its own for the second sequence input from the second page on (_seq_slots_own): no two envs are duplicates there

@@ -9,6 +9,7 @@ make_config / build_env and times, between two synchronisations (bench.timed_epi
 Prints one line `ARM <name> <workload> <ms per episode-batch>` per workload.
     python tools/ab_carry.py --name branch
     python tools/ab_carry.py --name off --no-carry                      (r19: --name off --kernels no_lazy_expand)
+    python tools/ab_carry.py --name serial --no-step-overlap            (r26: consecutive transitions on the caller's stream)
     python tools/ab_carry.py --name parent --tree tools/_ab/parent      (another tree with its own library and Python)"""
 import argparse
 import os
@@ -21,6 +22,7 @@ def main():
     ap.add_argument('--tree', default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     ap.add_argument('--workloads', default='default,distinct,random')
     ap.add_argument('--no-carry', action='store_true', help="config['no_partition_carry']")
+    ap.add_argument('--no-step-overlap', action='store_true', help="config['no_step_overlap'] (profiles/r26_ab.md)")
     ap.add_argument('--kernels', default=None, help="config['scorer_kernels'] (e.g. no_lazy_expand: the `off` arm of profiles/r19_lazy_ab.md)")
     a = ap.parse_args()
     sys.path.insert(0, os.path.abspath(a.tree))
@@ -36,6 +38,8 @@ def main():
             cfg.update({'is_eval': True, 'cache_size': args.batch})
         if a.no_carry:
             cfg['no_partition_carry'] = True
+        if a.no_step_overlap:
+            cfg['no_step_overlap'] = True
         if a.kernels is not None:
             cfg['scorer_kernels'] = a.kernels
         env = bench.build_env(cfg, False)
