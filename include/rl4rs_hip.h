@@ -593,6 +593,22 @@ int rl4rs_stepper_set_partition_carry(rl4rs_stepper* s, int32_t on);
 int rl4rs_stepper_set_step_overlap(rl4rs_stepper* s, int32_t on);
 /* Lane transitions issued on each lane and joins carried out since the stepper was created (read-only; any pointer may be NULL). */
 int rl4rs_stepper_lane_stats(const rl4rs_stepper* s, int64_t* lane0, int64_t* lane1, int64_t* joins);
+/* The two ends of an episode on the same two lanes (default on where the step overlap is).
+ * rl4rs_stepper_observe: the observation of the state behind a reset (cur_steps == 0) as a lane transition without an act.  Under the
+ * rule of rl4rs_stepper_set_step_overlap (less the act's conditions) the scorer forward runs on a lane behind everything the caller's
+ * stream holds, obs_dev [B, 256] is filled on the caller's stream, the logged action of step 0 is written to the row
+ * rl4rs_stepper_next_offline_action then returns (step 0) and *taken = 1: a first transition that hands that row back starts beside
+ * this forward.  *taken = 0: the rule says no, nothing was enqueued - compose the observation with rl4rs_dien_forward as before.
+ * A reward step that scores the state row inside the reward forward (rl4rs_stepper_set_obs_fold) runs on lane 0 when the
+ * transition before it is in flight on lane 1 (the scorer's second scratch set holds B rows only; the lane of the first transition
+ * behind a join is chosen so that this is the case) and joins otherwise; its front kernels run beside that transition, its AUGRU
+ * launch waits for that transition's last kernel (whole rounds over every CU).  rl4rs_stepper_set_reset_lane(s, 0) /
+ * rl4rs_stepper_set_reward_lane(s, 0) turn each half off alone; rl4rs_stepper_set_step_overlap(s, 0) turns off both.
+ * rl4rs_stepper_lane_stats_ex: reset forwards and reward steps issued on a lane (rl4rs_stepper_lane_stats counts neither). */
+int rl4rs_stepper_observe(rl4rs_stepper* s, float* obs_dev, int32_t* taken, void* stream);
+int rl4rs_stepper_set_reset_lane(rl4rs_stepper* s, int32_t on);
+int rl4rs_stepper_set_reward_lane(rl4rs_stepper* s, int32_t on);
+int rl4rs_stepper_lane_stats_ex(const rl4rs_stepper* s, int64_t* reset_runs, int64_t* reward_runs);
 /* Click probabilities of the complete-state rows of the LAST reward step, slate order: out_dev [B, n_complete] f32 - the same
  * numbers in either order of the forwards (the record form's click_p part, for rl4rs_env_step_discrete / _conti). */
 int rl4rs_stepper_click_probs(rl4rs_stepper* s, float* out_dev, void* stream);

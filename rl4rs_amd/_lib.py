@@ -298,6 +298,10 @@ SIGNATURES = {
     'rl4rs_stepper_set_distinct_hint': (_I, [_P, _I32]),
     'rl4rs_stepper_set_step_overlap': (_I, [_P, _I32]),
     'rl4rs_stepper_lane_stats': (_I, [_P, _P, _P, _P]),
+    'rl4rs_stepper_observe': (_I, [_P, _P, _P, _P]),
+    'rl4rs_stepper_set_reset_lane': (_I, [_P, _I32]),
+    'rl4rs_stepper_set_reward_lane': (_I, [_P, _I32]),
+    'rl4rs_stepper_lane_stats_ex': (_I, [_P, _P, _P]),
     'rl4rs_stepper_click_probs': (_I, [_P, _P, _P]),
     'rl4rs_stepper_reward_rows': (_I, [_P]),
     'rl4rs_stepper_next_offline_action': (_I, [_P, _P, _P]),

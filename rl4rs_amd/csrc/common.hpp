@@ -207,6 +207,15 @@ void env_rows_current(const rl4rs_env* e, const float** dense, const int32_t** c
 int dien_reserve_lane_scratch(rl4rs_dien* n, int rows);
 int dien_forward_lane(rl4rs_dien* n, int set, int32_t R, const float* dense, const int32_t* cat, const int32_t* slots, float* obs,
                       void* stream, void* home);
+// The same with every argument of a forward: `group` rows per env and probabilities for the reward step's forward (set 0
+// only: the second set holds an observation-sized forward), and `after_dedup` (a hipEvent_t, or NULL) recorded on `stream` behind the
+// duplicate-row stage - the reset's observation forward looks for its duplicates itself, and the partition is all the next act needs;
+// `before_augru` (a hipEvent_t, or NULL): `stream` waits for it in front of the AUGRU launch (the reward step's, which wants the whole chip)
+int dien_forward_lane_full(rl4rs_dien* n, int set, int32_t R, int32_t group, const float* dense, const int32_t* cat, const int32_t* slots,
+                           float* obs, float* prob, void* stream, void* home, void* after_dedup, void* before_augru);
+// rl4rs_env_build_complete_rows / rl4rs_env_reward_split without the join of the lanes (env.hip): a lane's own launches
+int env_build_complete_rows_lane(rl4rs_env* e, int32_t rows_per_env, void* stream);
+int env_reward_split_lane(rl4rs_env* e, const float* probs, const float* p_last, double* reward, void* stream);
 bool dien_lane_path(const rl4rs_dien* n, int rows);      // fp16x2 on k_augru_x / k_augru_xs, and the second set holds `rows` rows
 int dien_n_cu(const rl4rs_dien* n);
 

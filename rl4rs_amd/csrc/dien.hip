@@ -2586,7 +2586,8 @@ static void swap_scratch(rl4rs_dien* n) {
 }
 
 static int dien_forward_on(rl4rs_dien* n, int set, hipStream_t home, int32_t R, int32_t group, const float* dense, const int32_t* cat,
-                           const int32_t* slots, float* obs, float* prob, void* stream) {
+                           const int32_t* slots, float* obs, float* prob, void* stream, hipEvent_t after_dedup = nullptr,
+                           hipEvent_t before_augru = nullptr) {
     RL4RS_REQUIRE(n && dense && cat && slots, "dien_forward: null argument");
     RL4RS_REQUIRE(R > 0 && R <= n->c.max_rows, "dien_forward: R=%d exceeds max_rows=%d", R, n->c.max_rows);
     RL4RS_REQUIRE(group >= 1 && R % group == 0, "dien_forward: R=%d is not a multiple of group=%d", R, group);
@@ -2622,10 +2623,14 @@ static int dien_forward_on(rl4rs_dien* n, int set, hipStream_t home, int32_t R, 
     int rc;
     if (p.dense_side && (rc = stage_dense_fork(n, p, f))) return rc;
     if ((rc = stage_dedup(n, p, f))) return rc;
+    if (after_dedup) RL4RS_HIP_TRY(hipEventRecord(after_dedup, f.st));     // (a lane's `act_done`: the partition is written)
     n->last_plan = p;
     if ((rc = stage_cat(n, p, f))) return rc;
     if ((rc = stage_dense(n, p, f))) return rc;
     if ((rc = stage_din(n, p, f))) return rc;
+    // (the reward step on a lane, DESIGN 39: its front kernels run beside the observation transition in flight, its AUGRU launch -
+    // whole rounds of 64-row workgroups over every CU - starts when that transition has left the chip)
+    if (before_augru) RL4RS_HIP_TRY(hipStreamWaitEvent(f.st, before_augru, 0));
     if ((rc = stage_augru(n, p, f))) return rc;
     if (p.expand == PlanExpand::Front && (rc = stage_expand(n, p, f))) return rc;
     if (p.dense_side) RL4RS_HIP_TRY(hipStreamWaitEvent(f.st, n->ev_join, 0));
@@ -2833,6 +2838,11 @@ int dien_forward_lane(rl4rs_dien* n, int set, int32_t R, const float* dense, con
                       void* stream, void* home) {
     RL4RS_REQUIRE(n && (set == 0 || (set == 1 && n->alt.allf && R <= n->alt.rows)), "dien_forward_lane: no second scratch set of %d rows", R);
     return dien_forward_on(n, set, (hipStream_t)home, R, 1, dense, cat, slots, obs, nullptr, stream);
+}
+int dien_forward_lane_full(rl4rs_dien* n, int set, int32_t R, int32_t group, const float* dense, const int32_t* cat, const int32_t* slots,
+                           float* obs, float* prob, void* stream, void* home, void* after_dedup, void* before_augru) {
+    RL4RS_REQUIRE(n && (set == 0 || (set == 1 && n->alt.allf && R <= n->alt.rows)), "dien_forward_lane: no second scratch set of %d rows", R);
+    return dien_forward_on(n, set, (hipStream_t)home, R, group, dense, cat, slots, obs, prob, stream, (hipEvent_t)after_dedup, (hipEvent_t)before_augru);
 }
 bool dien_augru_rows64(const rl4rs_dien* n, int B, int group) {
     return n && n->t.fp16x2 && n->t.augru_x && (int64_t)B * group <= n->c.max_rows && augru_rows64(n->augru_rows, B * group, group, n->S, n->n_cu);

@@ -904,9 +904,15 @@ int rl4rs_env_build_complete(rl4rs_env* e, void* stream) {
 
 int rl4rs_env_build_complete_rows(rl4rs_env* e, int32_t rows_per_env, void* stream) {
     RL4RS_REQUIRE(e, "build_complete: null env");
+    ENV_JOIN(e, stream);
+    return rl4rs::env_build_complete_rows_lane(e, rows_per_env, stream);
+}
+}  // extern "C"
+// the same launch without the join: the stepper's reward step on a lane (step.hip) orders it itself
+int rl4rs::env_build_complete_rows_lane(rl4rs_env* e, int32_t rows_per_env, void* stream) {
+    RL4RS_REQUIRE(e, "build_complete: null env");
     RL4RS_REQUIRE(rows_per_env >= 1 && rows_per_env <= e->n_complete, "build_complete: rows_per_env=%d not in 1..%d",
                   rows_per_env, e->n_complete);
-    ENV_JOIN(e, stream);
     int jb = complete_base(e);
     if (jb < 0 || jb + e->n_complete > e->d.T) {
         set_error("build_complete: cur_steps=%d has no complete page", e->cur_steps);
@@ -916,6 +922,7 @@ int rl4rs_env_build_complete_rows(rl4rs_env* e, int32_t rows_per_env, void* stre
     int R = e->d.B * rows_per_env;
     return launch_rows<2>(e, R, nullptr, e->cur_steps, rows_per_env, jb, st);
 }
+extern "C" {
 
 int rl4rs_env_reward_split(rl4rs_env* e, const float* probs, const float* p_last, double* reward, void* stream);
 int rl4rs_env_reward(rl4rs_env* e, const float* probs, double* reward, void* stream) {
@@ -925,6 +932,11 @@ int rl4rs_env_reward(rl4rs_env* e, const float* probs, double* reward, void* str
 int rl4rs_env_reward_split(rl4rs_env* e, const float* probs, const float* p_last, double* reward, void* stream) {
     RL4RS_REQUIRE(e && probs && reward, "reward: null argument");
     ENV_JOIN(e, stream);
+    return rl4rs::env_reward_split_lane(e, probs, p_last, reward, stream);
+}
+}  // extern "C"
+int rl4rs::env_reward_split_lane(rl4rs_env* e, const float* probs, const float* p_last, double* reward, void* stream) {
+    RL4RS_REQUIRE(e && probs && reward, "reward: null argument");
     int jb = complete_base(e);
     if (jb < 0 || jb + e->n_complete > e->d.T) {
         set_error("reward: cur_steps=%d has no complete page", e->cur_steps);
@@ -935,6 +947,7 @@ int rl4rs_env_reward_split(rl4rs_env* e, const float* probs, const float* p_last
     RL4RS_LAUNCH_CHECK();
     return RL4RS_OK;
 }
+extern "C" {
 
 int rl4rs_env_violation(rl4rs_env* e, int32_t* out, void* stream) {
     RL4RS_REQUIRE(e && out, "violation: null argument");

@@ -59,6 +59,8 @@ struct rl4rs_stepper {
     // Two lanes for consecutive transitions (rl4rs_stepper_set_step_overlap, default on).  A lane transition flips the env's state-row
     // set and the active list / counter pair below, so that its act writes none of what the previous forward still reads.
     bool overlap;
+    bool reset_lane;           // rl4rs_stepper_set_reset_lane (default on): rl4rs_stepper_observe runs the reset's forward on a lane
+    bool reward_lane;          // rl4rs_stepper_set_reward_lane (default on): a folded reward step runs on lane 0 beside the transition before it
     bool lanes_made;
     StepLane lane[2];
     hipEvent_t ev_entry;       // recorded on the caller's stream where a lane has to wait for it
@@ -305,7 +307,9 @@ __global__ void k_record_status(const int32_t* env_err, int32_t* range_flag, int
 
 // A transition on lane lp.on (step_lanes.hpp decided that, and what it waits for): the act and the observation forward of
 // rl4rs_env_step_discrete, the same launches with the same arguments but for the stream, the state-row set, the active list /
-// counter pair, the scorer's scratch set and the head's output pointer.
+// counter pair, the scorer's scratch set and the head's output pointer.  lp.reward: the folded reward step of after_act,
+// launch for launch - the act, the complete rows, the forward of n_complete rows per env on the scorer's first scratch set (lane 0)
+// with the observation rows into the lane's buffer, the reward into the lane's reward block.
 int lane_transition(rl4rs_stepper* s, const LanePlan& lp, const LaneState& before, int cur, RowRefineArgs* rf, const int32_t* actions_dev, float* obs_dev,
                     double* reward_dev, void* stream) {
     hipStream_t home = (hipStream_t)stream;
@@ -325,8 +329,8 @@ int lane_transition(rl4rs_stepper* s, const LanePlan& lp, const LaneState& befor
     env_flip_rows(s->env);             // (the act kernel takes the env's current set: flipped in front of it, back if nothing was enqueued)
     ActTail tail;
     tail.done = nullptr; tail.done_v = 0;
-    tail.zero_reward = reward_dev ? l.reward : nullptr;
-    tail.next_action = s->next_off + (size_t)(cur + 1) * B;      // (cur + 1 <= T: a lane transition has no reward due)
+    tail.zero_reward = (reward_dev && !lp.reward) ? l.reward : nullptr;
+    tail.next_action = s->next_off + (size_t)(cur + 1) * B;      // (cur + 1 <= T: the ring has max_steps + 1 rows)
     tail.next_cur = cur + 1;
     int rc = rl4rs::env_act_discrete_tail(s->env, actions_dev, tail, l.st, rf);
     if (rc) {
@@ -343,7 +347,19 @@ int lane_transition(rl4rs_stepper* s, const LanePlan& lp, const LaneState& befor
     refined(s);
     s->next_off_cur = cur + 1;
     RL4RS_HIP_TRY(hipEventRecord(l.act_done, l.st));
-    if ((rc = rl4rs_dien_set_row_partition(s->dien, s->part_rep[s->part_cur], s->part_active, s->part_cnt, B)) ||
+    if (lp.reward) {
+        const int n = s->n_complete;
+        if ((rc = rl4rs::env_build_complete_rows_lane(s->env, n, l.st)) ||
+            (rc = rl4rs_dien_set_obs_last(s->dien, l.obs)) ||
+            (rc = rl4rs_dien_set_row_partition(s->dien, s->part_rep[s->part_cur], s->part_active, s->part_cnt, B)) ||
+            (rc = dien_forward_lane_full(s->dien, 0, B * n, n, s->c_dense, s->c_cat, s->slots, nullptr, s->probs, l.st, stream, nullptr,
+                                         s->lane[1].done)) ||      // (lane_reward_eligible: the transition in flight is lane 1's)
+            (rc = rl4rs::env_reward_split_lane(s->env, s->probs, nullptr, l.reward, l.st))) {
+            (void)hipEventRecord(l.done, l.st);
+            return rc;
+        }
+        s->probs_rows = n;
+    } else if ((rc = rl4rs_dien_set_row_partition(s->dien, s->part_rep[s->part_cur], s->part_active, s->part_cnt, B)) ||
         (rc = dien_forward_lane(s->dien, lp.on, B, s->dense, s->cat, s->slots, l.obs, l.st, stream))) {
         // the act happened, the observation did not: the lane still gets its `done` (the state says it is in flight, a join waits
         // for that event) and the caller the error; the env is where the act left it, as after a failed forward on the caller's stream
@@ -358,6 +374,14 @@ int lane_transition(rl4rs_stepper* s, const LanePlan& lp, const LaneState& befor
     RL4RS_LAUNCH_CHECK();
     RL4RS_HIP_TRY(hipEventRecord(l.handed, home));
     return RL4RS_OK;
+}
+
+// the step counter in front of the act behind which the next reward is due (the rule of rl4rs_env_is_reward_step at cur + 1)
+int reward_act(const rl4rs_stepper* s, int cur) {
+    const int T = s->cfg.max_steps;
+    if (!s->cfg.is_seq) return T - 1;
+    const int d = cur / s->cfg.page_items * s->cfg.page_items + s->cfg.page_items - 1;
+    return d < T - 1 ? d : T - 1;
 }
 
 int attach(rl4rs_env* env, rl4rs_dien* dien, rl4rs_simnet* simnet, const int32_t* slots_dev, int32_t seq_num, rl4rs_stepper** out) {
@@ -402,7 +426,7 @@ int attach(rl4rs_env* env, rl4rs_dien* dien, rl4rs_simnet* simnet, const int32_t
             rl4rs_stepper_destroy(s);
             return rc;
         }
-        s->overlap = s->lanes_made;
+        s->overlap = s->reset_lane = s->reward_lane = s->lanes_made;
     }
     s->act_tail = true;
     s->obs_fold = true;
@@ -479,6 +503,10 @@ int rl4rs_env_step_discrete(rl4rs_stepper* s, const int32_t* actions_dev, float*
         c.extra_outputs = mask_bits_dev != nullptr || done_dev != nullptr;
         c.own_row = own_row;
         c.seq_num = s->seq_num; c.distinct_hint = s->distinct_hint; c.n_cu = s->dien ? dien_n_cu(s->dien) : 0;
+        // (with both halves of DESIGN 39 off the lanes alternate from where they were)
+        c.to_reward = (c.reward_due || !(s->reset_lane || s->reward_lane)) ? 0 : reward_act(s, cur) - cur;
+        c.no_reward_lane = !s->reward_lane;
+        c.reward_fold = c.reward_due && reward_dev && c.overlap && c.dien_x && refine && fold_obs(s);
         const LaneState before = s->lstate;
         const LanePlan lp = lane_decide(s->lstate, c);
         if (lp.lane) return lane_transition(s, lp, before, cur, &rf, actions_dev, obs_dev, reward_dev, stream);
@@ -533,6 +561,73 @@ int rl4rs_stepper_set_partition_carry(rl4rs_stepper* s, int32_t on) {
 int rl4rs_stepper_set_step_overlap(rl4rs_stepper* s, int32_t on) {
     RL4RS_REQUIRE(s, "stepper_set_step_overlap: null argument");
     s->overlap = on != 0 && s->lanes_made;
+    return RL4RS_OK;
+}
+
+int rl4rs_stepper_set_reset_lane(rl4rs_stepper* s, int32_t on) {
+    RL4RS_REQUIRE(s, "stepper_set_reset_lane: null argument");
+    s->reset_lane = on != 0 && s->lanes_made;
+    return RL4RS_OK;
+}
+
+int rl4rs_stepper_set_reward_lane(rl4rs_stepper* s, int32_t on) {
+    RL4RS_REQUIRE(s, "stepper_set_reward_lane: null argument");
+    s->reward_lane = on != 0 && s->lanes_made;
+    return RL4RS_OK;
+}
+
+int rl4rs_stepper_lane_stats_ex(const rl4rs_stepper* s, int64_t* reset_runs, int64_t* reward_runs) {
+    RL4RS_REQUIRE(s, "stepper_lane_stats_ex: null argument");
+    if (reset_runs) *reset_runs = s->lstate.ran_reset;
+    if (reward_runs) *reward_runs = s->lstate.ran_reward;
+    return RL4RS_OK;
+}
+
+// The observation of the state the env is in behind a reset, as a lane transition without an act: *taken = 1 and obs_dev
+// is filled on the caller's stream (the hand-out of every lane transition); the logged action of step 0 is row 0 of the stepper's
+// ring (rl4rs_stepper_next_offline_action), so that the first transition hands back the stepper's own row and waits for the
+// partition only.  *taken = 0: the rule of step_lanes.hpp says no, nothing was enqueued or changed - the caller composes the
+// observation as it did (rl4rs_dien_forward on its own stream).
+int rl4rs_stepper_observe(rl4rs_stepper* s, float* obs_dev, int32_t* taken, void* stream) {
+    RL4RS_REQUIRE(s && obs_dev && taken, "stepper_observe: null argument");
+    *taken = 0;
+    const int cur = rl4rs_env_cur_steps(s->env);
+    const int B = s->cfg.batch_size;
+    LaneCall c;
+    memset(&c, 0, sizeof(c));
+    c.overlap = s->overlap && s->act_tail && cur == 0 && lane_links_mine(s->links, LANE_LINK_ENV, &s->hook) &&
+                lane_links_mine(s->links, LANE_LINK_SCORER, &s->hook);
+    c.dien_x = s->dien && dien_lane_path(s->dien, B);
+    c.seq_num = s->seq_num; c.distinct_hint = s->distinct_hint; c.n_cu = s->dien ? dien_n_cu(s->dien) : 0;
+    c.observe = true;
+    c.no_reset_lane = !s->reset_lane;
+    c.to_reward = 1 + reward_act(s, cur) - cur;
+    if (!lane_observe_eligible(c)) return RL4RS_OK;
+    hipStream_t home = (hipStream_t)stream;
+    int rc = lanes_wait(s, stream, 1);                  // (behind a reset nothing is in flight: the load has joined)
+    if (rc) return rc;
+    s->next_off_cur = -1;
+    if ((rc = rl4rs_env_offline_action(s->env, s->next_off, nullptr, stream))) return rc;
+    const LanePlan lp = lane_decide(s->lstate, c);
+    StepLane& l = s->lane[lp.on];
+    s->part_now = false;                                // the rows of a state nobody acted on: this forward compares them (and seeds the next act)
+    env_rows_current(s->env, &s->dense, &s->cat);
+    RL4RS_HIP_TRY(hipEventRecord(s->ev_entry, home));
+    RL4RS_HIP_TRY(hipStreamWaitEvent(l.st, s->ev_entry, 0));
+    if ((rc = dien_forward_lane_full(s->dien, lp.on, B, 1, s->dense, s->cat, s->slots, l.obs, nullptr, l.st, stream, l.act_done, nullptr))) {
+        // the state says the lane is in flight: a join waits for `done`, a transition behind this one for `act_done`
+        (void)hipEventRecord(l.act_done, l.st);
+        (void)hipEventRecord(l.done, l.st);
+        return rc;
+    }
+    RL4RS_HIP_TRY(hipEventRecord(l.done, l.st));
+    RL4RS_HIP_TRY(hipStreamWaitEvent(home, l.done, 0));
+    const int64_t n_obs = (int64_t)B * 256;
+    hipLaunchKernelGGL(k_lane_handout, dim3((unsigned)((n_obs + 255) / 256)), dim3(256), 0, home, l.obs, obs_dev, n_obs, l.reward, (double*)nullptr, B);
+    RL4RS_LAUNCH_CHECK();
+    RL4RS_HIP_TRY(hipEventRecord(l.handed, home));
+    s->next_off_cur = 0;
+    *taken = 1;
     return RL4RS_OK;
 }
 

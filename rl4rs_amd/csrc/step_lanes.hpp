@@ -3,6 +3,9 @@
 // in a replay loop transition k + 1 needs nothing of transition k's scorer forward - only the env state, the partition and the
 // logged-action row the ACT of k left.  The stepper therefore owns two lanes (a stream and its events each) and runs consecutive
 // eligible transitions on them in turn: the forward of k + 1 starts beside the forward of k.
+// The two ends of an episode use the same two lanes: the reset's observation forward is a lane transition without an act
+// (rl4rs_stepper_observe), and a reward step that is ONE forward of n_complete rows per env takes lane 0 beside the last observation
+// transition on lane 1 (tests/test_step_lanes_episode_host.py).
 // Host code only, nothing from HIP (as dien_plan.hpp): step.hip carries out what lane_decide returns, tests/test_step_lanes_host.py
 // replays call sequences through it without a device.
 #pragma once
@@ -22,12 +25,20 @@ struct LaneCall {
     bool extra_outputs;    // mask_bits_dev or done_dev asked for
     bool own_row;          // actions_dev is the logged-action row the previous transition's act wrote
     int seq_num, distinct_hint, n_cu;
+    // DESIGN 39 - every field below is zero in a call built the way DESIGN 38's callers build it, and lane_decide then answers as it did
+    bool observe;          // rl4rs_stepper_observe: the reset's observation forward - no act, its own k_row_dedup (carried is not asked for)
+    bool no_reset_lane;    // rl4rs_stepper_set_reset_lane(s, 0): that forward stays on the caller's stream
+    bool reward_fold;      // the reward step is ONE forward of n_complete rows per env (fold_obs) and a reward block was given
+    bool no_reward_lane;   // rl4rs_stepper_set_reward_lane(s, 0): the reward step joins
+    int to_reward;         // lane transitions from this one up to the reward step, this one included, the reward step not; 0 = unknown
 };
 
-inline bool lane_eligible(const LaneCall& c) {
-    return c.overlap && c.dien_x && c.carried && !c.reward_due && !c.extra_outputs &&
-           lane_pair_workgroups(c.seq_num, c.distinct_hint) <= c.n_cu;
+inline bool lane_room(const LaneCall& c) {
+    return c.overlap && c.dien_x && !c.extra_outputs && lane_pair_workgroups(c.seq_num, c.distinct_hint) <= c.n_cu;
 }
+inline bool lane_eligible(const LaneCall& c) { return lane_room(c) && !c.observe && c.carried && !c.reward_due; }
+// the reset's observation forward: the same rule without the act's conditions
+inline bool lane_observe_eligible(const LaneCall& c) { return lane_room(c) && c.observe && !c.no_reset_lane; }
 
 // host-side record of what is in flight
 struct LaneState {
@@ -37,6 +48,7 @@ struct LaneState {
     int last;              // the lane of the last lane transition (valid while in_flight)
     int64_t ran[2];        // lane transitions issued on each lane, joins carried out (rl4rs_stepper_lane_stats)
     int64_t joins;
+    int64_t ran_reset, ran_reward;   // reset forwards and reward steps issued on a lane (rl4rs_stepper_lane_stats_ex): not part of ran[]
 };
 
 struct LanePlan {
@@ -48,6 +60,8 @@ struct LanePlan {
     bool wait_act;         // the lane waits for `act_done` of lane `on ^ 1` (env state, partition, logged-action row of k - 1)
     bool wait_handout;     // the lane waits for the hand-out copy of its own previous transition (it rewrites the lane's
                            // observation and reward buffers); implied by wait_entry, which the caller's stream records behind it
+    bool observe;          // (lane == true) the reset's observation forward: no act; `act_done` is recorded behind its k_row_dedup
+    bool reward;           // (lane == true) the folded reward step: act, complete rows, the n_complete-row forward, the reward
 };
 
 // join: everything in flight is waited for by the stream the caller gave (step.hip issues the waits when this returns true)
@@ -102,14 +116,50 @@ inline void lane_links_release(LaneLinks& l, const LaneHook* hook) {
     }
 }
 
+// The scorer's second scratch set holds an observation-sized forward only: the reward forward runs on lane 0 (set 0) and the
+// observation transition still in flight beside it must be the one on lane 1.  Lanes alternate while something is in flight, so
+// the lane is chosen where nothing is: the first of `to_reward` lane transitions in a row starts on the lane that puts the last on 1.
+inline int lane_first(int to_reward) { return 1 ^ ((to_reward - 1) & 1); }
+
+// the folded reward step takes lane 0 beside the observation transition in flight on lane 1 - and joins in every other case
+inline bool lane_reward_eligible(const LaneState& s, const LaneCall& c) {
+    return lane_room(c) && !c.observe && c.carried && c.reward_due && c.reward_fold && !c.no_reward_lane && s.in_flight && s.last == 1;
+}
+
 inline LanePlan lane_decide(LaneState& s, const LaneCall& c) {
     LanePlan p = {};
+    if (lane_reward_eligible(s, c)) {
+        p.lane = p.reward = true;
+        p.on = 0;
+        p.wait_act = true;
+        p.wait_entry = !c.own_row;
+        p.wait_handout = !p.wait_entry && s.used[0];
+        s.used[0] = true;
+        s.last = 0;
+        s.ran_reward += 1;
+        s.next = 1;
+        return p;
+    }
+    if (lane_observe_eligible(c)) {
+        // behind the load, the reset and the encode on the caller's stream: whatever is still in flight is joined first (step.hip
+        // issues the waits), then the lane waits for the entry event
+        p.join = lane_join(s);
+        p.lane = p.observe = true;
+        p.on = c.to_reward > 0 ? lane_first(c.to_reward) : s.next;
+        p.wait_entry = true;
+        s.in_flight = true;
+        s.used[p.on] = true;
+        s.last = p.on;
+        s.ran_reset += 1;
+        s.next = p.on ^ 1;
+        return p;
+    }
     if (!lane_eligible(c)) {
         p.join = lane_join(s);
         return p;
     }
     p.lane = true;
-    p.on = s.next;
+    p.on = (!s.in_flight && c.to_reward > 0) ? lane_first(c.to_reward) : s.next;
     p.wait_act = s.in_flight;                       // transition k - 1 ran on the other lane: lanes alternate
     p.wait_entry = !s.in_flight || !c.own_row;
     p.wait_handout = !p.wait_entry && s.used[p.on];

@@ -332,14 +332,17 @@ class DeviceStepper(object):
     """rl4rs_stepper handle: an env bound to its scorer so that one call runs a whole transition
     (rl4rs_env_step_discrete / rl4rs_env_step_conti = RecSimBase._step, base.py:157-170)."""
 
-    def __init__(self, env, net, slots, act_tail=True, obs_fold=True, partition_carry=True, step_overlap=True):
+    def __init__(self, env, net, slots, act_tail=True, obs_fold=True, partition_carry=True, step_overlap=True, reset_lane=True,
+                 reward_lane=True):
         """``act_tail=False`` (config['no_act_tail'] / RL4RS_NO_ACT_TAIL=1): rl4rs_env_step_discrete launches k_step_tail as it
         did and leaves no next-step logged actions (rl4rs_stepper_set_act_tail).  ``obs_fold=False``
         (config['no_reward_obs_fold'] / RL4RS_NO_REWARD_OBS_FOLD=1): a reward step runs its observation forward and then the
         reward forward of n - 1 rows per env, as it did (rl4rs_stepper_set_obs_fold).  ``partition_carry=False``
         (config['no_partition_carry'] / RL4RS_NO_PARTITION_CARRY=1): every scorer forward of a transition looks for its duplicate
         rows itself, as it did (rl4rs_stepper_set_partition_carry).  ``step_overlap=False`` (config['no_step_overlap'] /
-        RL4RS_NO_STEP_OVERLAP=1): every transition runs on the caller's stream (rl4rs_stepper_set_step_overlap)."""
+        RL4RS_NO_STEP_OVERLAP=1): every transition runs on the caller's stream (rl4rs_stepper_set_step_overlap).
+        ``reset_lane=False`` (config['no_reset_lane'] / RL4RS_NO_RESET_LANE=1): ``observe`` takes no lane;
+        ``reward_lane=False`` (config['no_reward_lane'] / RL4RS_NO_REWARD_LANE=1): every reward step joins."""
         self.lib = _lib.load()
         self.env, self.net, self.slots = env, net, slots          # keep the handles and the slot table alive
         assert slots.dtype == torch.int32 and slots.is_contiguous() and slots.shape[1] == env.B
@@ -356,6 +359,11 @@ class DeviceStepper(object):
             check(self.lib.rl4rs_stepper_set_partition_carry(self.h, 0))
         if not step_overlap:
             check(self.lib.rl4rs_stepper_set_step_overlap(self.h, 0))
+        if not reset_lane:
+            check(self.lib.rl4rs_stepper_set_reset_lane(self.h, 0))
+        if not reward_lane:
+            check(self.lib.rl4rs_stepper_set_reward_lane(self.h, 0))
+        self.reset_lane = bool(step_overlap and reset_lane)
         self._distinct_hint = None
         self.B, self.A, self.E, self.W, self.device = env.B, env.A, env.E, env.W, env.device
         self.obs_dim = int(getattr(net, 'obs_dim', 256))         # 256 for DIEN / dnn / lstm, 256 + U + Cn*E for widedeep
@@ -384,6 +392,24 @@ class DeviceStepper(object):
         a, b, j = C.c_int64(0), C.c_int64(0), C.c_int64(0)
         check(self.lib.rl4rs_stepper_lane_stats(self.h, C.byref(a), C.byref(b), C.byref(j)))
         return int(a.value), int(b.value), int(j.value)
+
+    def lane_stats_ex(self):
+        """(reset forwards, reward steps) issued on a lane since the stepper was created (rl4rs_stepper_lane_stats_ex);
+        ``lane_stats`` counts neither."""
+        a, b = C.c_int64(0), C.c_int64(0)
+        check(self.lib.rl4rs_stepper_lane_stats_ex(self.h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
+    def observe(self):
+        """rl4rs_stepper_observe: the observation behind a reset as a lane transition -> obs f32 [B, 256], or None where the lane
+        rule says no (nothing was enqueued: the caller composes it).  The logged action of step 0 is then the stepper's own row
+        (``next_offline_action``)."""
+        if not self.reset_lane or not self.act_tail:
+            return None
+        obs = torch.empty((self.B, self.obs_dim), dtype=torch.float32, device=self.device)
+        taken = C.c_int32(0)
+        check(self.lib.rl4rs_stepper_observe(self.h, _ptr(obs), C.byref(taken), _stream()))
+        return obs if taken.value else None
 
     def reward_rows(self):
         """Rows per env the last reward step's reward forward scored (rl4rs_stepper_reward_rows)."""

@@ -598,6 +598,21 @@ class SlateRecEnv(RecSimBase):
                 and not (samples._tensor_mode() and (cfg.get("support_d3rl_mask", False) or cfg.get("simulator_info_fetch", False)))
                 and self._stock_methods(samples))
 
+    def _lane_switch(self, name):
+        """On unless config['no_' + name] / RL4RS_NO_<NAME>=1 says otherwise."""
+        key = 'no_' + name
+        return not self.config.get(key, os.environ.get('RL4RS_' + key.upper(), '') not in ('', '0'))
+
+    def _reset_lane_ok(self, samples):
+        """The plain zero-copy observation only (a tensor; the mask and raw-state forms compose
+        as they did), discrete actions, and none of config['no_reset_lane'], config['no_step_overlap'], config['no_act_tail']: those
+        arms issue exactly the calls they issued."""
+        cfg = self.config
+        off = any(cfg.get(k, os.environ.get(v, '') not in ('', '0'))
+                  for k, v in (('no_step_overlap', 'RL4RS_NO_STEP_OVERLAP'), ('no_act_tail', 'RL4RS_NO_ACT_TAIL')))
+        return (not off and self._lane_switch('reset_lane') and self._fused_ok(samples) and not cfg.get("support_conti_env", False)
+                and not cfg.get("support_rllib_mask", False) and not cfg.get("support_d3rl_mask", False))
+
     def _stepper_for(self, samples):
         env = samples._live()
         net, slots = self._net_for(samples)                 # history encoded for this batch, slot table current
@@ -615,8 +630,11 @@ class SlateRecEnv(RecSimBase):
             no_carry = self.config.get('no_partition_carry', os.environ.get('RL4RS_NO_PARTITION_CARRY', '') not in ('', '0'))
             # config['no_step_overlap'] (RL4RS_NO_STEP_OVERLAP=1): consecutive transitions on the caller's stream, one behind the other
             no_overlap = self.config.get('no_step_overlap', os.environ.get('RL4RS_NO_STEP_OVERLAP', '') not in ('', '0'))
+            # config['no_reset_lane'] (RL4RS_NO_RESET_LANE=1) / config['no_reward_lane'] (RL4RS_NO_REWARD_LANE=1): the reset's
+            # observation forward / the folded reward step on the caller's stream, each alone
             self._stepper = D.DeviceStepper(env, net, slots, act_tail=not no_tail, obs_fold=not no_fold, partition_carry=not no_carry,
-                                            step_overlap=not no_overlap)
+                                            step_overlap=not no_overlap, reset_lane=self._lane_switch('reset_lane'),
+                                            reward_lane=self._lane_switch('reward_lane'))
             self._stepper_key = key
         # envs the scorer's row dedup is expected to leave: the batch's distinct log lines - but SeqSlate gives every env a slot of
         # its own for the second sequence input from the second page on (_seq_slots_own): no two envs are duplicates there
@@ -662,6 +680,16 @@ class SlateRecEnv(RecSimBase):
         (rl4rs_env_observe_record_host) whose record - obs, the int64 mask or the float64 d3rl rows, the first logged action -
         is in pinned memory after one wait, the python objects around it built while the scorer runs."""
         samples = self._recData.sample(batch_size)
+        if samples._tensor_mode() and self._reset_lane_ok(samples):
+            # zero-copy mode: the observation forward as a lane transition of the stepper (rl4rs_stepper_observe, DESIGN 39) - the
+            # first step's forward then starts beside it.  None: the lane rule says no, the composed path below serves it
+            env, net, stepper = self._stepper_for(samples)
+            obs = stepper.observe()
+            if obs is not None:
+                nxt = stepper.next_offline_action(self.__dict__.setdefault('_next_rows', {}))
+                samples._next_offline_dev = None if nxt is None else ((samples._batch_version, nxt[0]), nxt[1])
+                self._last_obs = None
+                return samples, obs
         if samples._tensor_mode() or not self._fused_ok(samples):
             return samples, self.obs_fn(samples.state)
         env, net, stepper = self._stepper_for(samples)

@@ -10,6 +10,7 @@ Prints one line `ARM <name> <workload> <ms per episode-batch>` per workload.
     python tools/ab_carry.py --name branch
     python tools/ab_carry.py --name off --no-carry                      (r19: --name off --kernels no_lazy_expand)
     python tools/ab_carry.py --name serial --no-step-overlap            (r26: consecutive transitions on the caller's stream)
+    python tools/ab_carry.py --name noreset --no-reset-lane             (r27: each half of DESIGN 39 off alone; --no-reward-lane)
     python tools/ab_carry.py --name parent --tree tools/_ab/parent      (another tree with its own library and Python)"""
 import argparse
 import os
@@ -23,6 +24,8 @@ def main():
     ap.add_argument('--workloads', default='default,distinct,random')
     ap.add_argument('--no-carry', action='store_true', help="config['no_partition_carry']")
     ap.add_argument('--no-step-overlap', action='store_true', help="config['no_step_overlap'] (profiles/r26_ab.md)")
+    ap.add_argument('--no-reset-lane', action='store_true', help="config['no_reset_lane'] (profiles/r27_ab.md)")
+    ap.add_argument('--no-reward-lane', action='store_true', help="config['no_reward_lane'] (profiles/r27_ab.md)")
     ap.add_argument('--kernels', default=None, help="config['scorer_kernels'] (e.g. no_lazy_expand: the `off` arm of profiles/r19_lazy_ab.md)")
     a = ap.parse_args()
     sys.path.insert(0, os.path.abspath(a.tree))
@@ -40,6 +43,10 @@ def main():
             cfg['no_partition_carry'] = True
         if a.no_step_overlap:
             cfg['no_step_overlap'] = True
+        if a.no_reset_lane:
+            cfg['no_reset_lane'] = True
+        if a.no_reward_lane:
+            cfg['no_reward_lane'] = True
         if a.kernels is not None:
             cfg['scorer_kernels'] = a.kernels
         env = bench.build_env(cfg, False)
