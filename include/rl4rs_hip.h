@@ -609,6 +609,25 @@ int rl4rs_stepper_observe(rl4rs_stepper* s, float* obs_dev, int32_t* taken, void
 int rl4rs_stepper_set_reset_lane(rl4rs_stepper* s, int32_t on);
 int rl4rs_stepper_set_reward_lane(rl4rs_stepper* s, int32_t on);
 int rl4rs_stepper_lane_stats_ex(const rl4rs_stepper* s, int64_t* reset_runs, int64_t* reward_runs);
+/* Replay-ahead (default on with a DIEN scorer).  When rl4rs_env_step_discrete of a Slate env is handed the stepper's own
+ * logged-action row (rl4rs_stepper_next_offline_action) at act index c0 with n = max_steps - 1 - c0 equal to 8 or 9, neither done_dev
+ * nor mask_bits_dev, and a forward of n rows per env runs the 64-row form of k_augru_x - by the automatic rule (on = 1, the default:
+ * enough workgroups to fill the chip twice over) or also by the pin (on = 2; on = 0: never) -, the observation rows of the transitions
+ * c0 .. max_steps - 2 under the logged actions are scored in ONE forward; every later transition that hands back the stepper's row again
+ * runs its act alone and receives its row (and the zero reward).  Any other call - a foreign action pointer, another entry point of
+ * the env, the scorer or the stepper, a reset - drops the rows not handed out yet and proceeds as without the switch: wasted work, the
+ * same results.  rl4rs_stepper_replay_stats: forwards started, rows per env handed out, rows per env dropped, since attach. */
+int rl4rs_stepper_set_replay_ahead(rl4rs_stepper* s, int32_t on);
+/* The rows that forward scores, on their own (Slate envs, behind at least one act): row k of env b (out row b * n + k) is the state
+ * row the act of step c0 + k builds when the env plays its logged actions from c0 + 1 on, c0 = cur_steps - 1 the act just taken;
+ * dense_out [B * n, dense_feature_num] f32, cat_out [B * n, category_feature_num] i32, c0 + n <= max_steps.  Env state is not touched.
+ * rep != NULL: the duplicate-row partition of the envs behind the act just taken (rep [B] with rep[rep[b]] == rep[b], active
+ * [n_active[0]] the representatives, as rl4rs_dien_set_row_partition takes them) is copied to rep_out [B] / active_out [B] /
+ * n_active_out [1] for a forward of these rows: an env whose logged actions c0 + 1 .. c0 + n - 1 differ from its representative's is
+ * its own representative in the copy, appended to active_out behind the copied entries (in no fixed order) and counted. */
+int rl4rs_env_build_ahead_rows(rl4rs_env* e, int32_t n, float* dense_out, int32_t* cat_out, const int32_t* rep, const int32_t* active,
+                               const int32_t* n_active, int32_t* rep_out, int32_t* active_out, int32_t* n_active_out, void* stream);
+int rl4rs_stepper_replay_stats(const rl4rs_stepper* s, int64_t* started, int64_t* handed, int64_t* dropped);
 /* Click probabilities of the complete-state rows of the LAST reward step, slate order: out_dev [B, n_complete] f32 - the same
  * numbers in either order of the forwards (the record form's click_p part, for rl4rs_env_step_discrete / _conti). */
 int rl4rs_stepper_click_probs(rl4rs_stepper* s, float* out_dev, void* stream);

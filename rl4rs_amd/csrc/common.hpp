@@ -178,6 +178,10 @@ const int32_t* dien_row_order(const rl4rs_dien* n, int n_groups);         // the
 // the head GEMM's epilogue - step.hip's reference-shaped records (dien.hip); dien_obs_mirror_used: did that forward take it?
 void dien_set_obs_mirror(rl4rs_dien* n, float* host_visible);
 bool dien_obs_mirror_used(const rl4rs_dien* n);
+// The NEXT forward (one call) scores groups whose rows share the cache slot but not the category columns - the observation rows of
+// one env at consecutive steps of a replay (step.hip): the per-row category kernel runs, and with obs == NULL the head
+// output of the representatives' rows lands in `head_out` [R, 256] (row rep * group + k), not in the handle's own scratch
+void dien_set_group_rows(rl4rs_dien* n, float* head_out);
 // The last forward left the duplicates' internal rows (all-feature, scores, query) to rl4rs_dien_buffer (PlanExpand::Lazy): forget
 // that - the caller is about to rewrite the partition arrays that forward ran on (step.hip, in front of an act that refines them)
 void dien_drop_pending_expand(rl4rs_dien* n);
@@ -188,6 +192,8 @@ void dien_drop_pending_expand(rl4rs_dien* n);
 int64_t dien_augru_rounds(const rl4rs_dien* n, int B, int live, int group);
 // Would that forward's k_augru_x launch run the 64-row form (automatic rule or pinned)?
 bool dien_augru_rows64(const rl4rs_dien* n, int B, int group);
+// ... and would the automatic rule alone choose it (enough workgroups to fill the chip twice over), whatever the pin says?
+bool dien_augru_rows64_auto(const rl4rs_dien* n, int B, int group);
 
 // The stepper's two lanes (step.hip, step_lanes.hpp) may have a transition in flight on streams of their own.  The env and
 // the scorer a stepper is attached to hold a pointer to its hook, and every entry point that reads or writes what a lane may still
@@ -216,6 +222,15 @@ int dien_forward_lane_full(rl4rs_dien* n, int set, int32_t R, int32_t group, con
 // rl4rs_env_build_complete_rows / rl4rs_env_reward_split without the join of the lanes (env.hip): a lane's own launches
 int env_build_complete_rows_lane(rl4rs_env* e, int32_t rows_per_env, void* stream);
 int env_reward_split_lane(rl4rs_env* e, const float* probs, const float* p_last, double* reward, void* stream);
+// The state rows "after act c under the logged actions" of every env for c in [c0, c0 + n), env-major [B * n] (env.hip, DESIGN 40;
+// Slate only, no join: step.hip orders it behind the act of c0).  prev_actions up to c0 are the env's, behind c0 the log's.
+// `part` (or NULL): the partition the act of c0 left, copied for the forward of these rows - an env whose logged actions behind c0
+// differ from its representative's becomes a representative of its own (appended to the copy of the active list)
+struct AheadPart {
+    const int32_t* rep; const int32_t* active; const int32_t* cnt;      // [B], [cnt[0]], [0] n_active
+    int32_t* rep_out; int32_t* active_out; int32_t* cnt_out;            // the copies; cnt_out[0] holds cnt[0] when the kernel starts
+};
+int env_build_ahead_rows_lane(rl4rs_env* e, int32_t c0, int32_t n, float* dense_out, int32_t* cat_out, const AheadPart* part, void* stream);
 bool dien_lane_path(const rl4rs_dien* n, int rows);      // fp16x2 on k_augru_x / k_augru_xs, and the second set holds `rows` rows
 int dien_n_cu(const rl4rs_dien* n);
 

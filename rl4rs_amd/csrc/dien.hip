@@ -1699,6 +1699,9 @@ struct rl4rs_dien {
     float* obs_mirror;    // rl4rs_dien_set_obs_mirror: device-visible host memory [R, OBS_DIM] for the NEXT forward's observation
     bool obs_mirror_used;  // ... whether that forward's head kernel took it (only the fp16x2 GEMM with the table addend writes mirrors)
     float* obs_last;       // rl4rs_dien_set_obs_last: [R / group, OBS_DIM] for the NEXT forward's observation of each group's last row
+    // rl4rs::dien_set_group_rows: the NEXT forward's rows share their group's cache slot but not its category columns, and
+    // its head output (obs == NULL: the representatives' rows) goes to head_out [R, OBS_DIM] instead of obs_tmp
+    bool group_rows; float* head_out;
     std::vector<void*> owned;
     // profiling
     int profiling;         // 0 off, 1 every kernel class, 2 only the AUGRU recurrence (two event records per forward)
@@ -2597,7 +2600,7 @@ static int dien_forward_on(rl4rs_dien* n, int set, hipStream_t home, int32_t R, 
     struct SetGuard { rl4rs_dien* n; bool on; ~SetGuard() { if (on) swap_scratch(n); } } set_guard{n, set == 1};
     if (set == 1) swap_scratch(n);
     n->last_set = set; n->last_rows = R; n->last_home = home;
-    struct MirrorOnce { rl4rs_dien* n; ~MirrorOnce() { n->obs_mirror = nullptr; n->obs_last = nullptr; n->part_rep = nullptr; } } mirror_once{n};       // one forward only
+    struct MirrorOnce { rl4rs_dien* n; ~MirrorOnce() { n->obs_mirror = nullptr; n->obs_last = nullptr; n->part_rep = nullptr; n->group_rows = false; n->head_out = nullptr; } } mirror_once{n};       // one forward only
     DienCall c{};
     c.R = R; c.group = group; c.obs = obs != nullptr; c.prob = prob != nullptr;
     c.mirror = n->obs_mirror != nullptr; c.obs_last = n->obs_last != nullptr;
@@ -2606,13 +2609,14 @@ static int dien_forward_on(rl4rs_dien* n, int set, hipStream_t home, int32_t R, 
     c.row_order = n->row_order && n->row_order_n == ngroups;
     c.augru_rows = n->augru_rows; c.distinct_hint = n->distinct_hint;
     c.dense_vec = (n->Dn & 3) == 0 && (reinterpret_cast<uintptr_t>(dense) & 15) == 0;
+    c.rows_differ = n->group_rows;
     RL4RS_REQUIRE(!c.carried || (dien_takes_partition(n) && c.part_groups == ngroups),
                   "dien_forward: the row partition set for this forward is for %d groups with the row dedup on (forward: %d groups)", n->part_groups, ngroups);
     RL4RS_REQUIRE(!c.obs_last || c.prob, "dien_forward: rl4rs_dien_set_obs_last needs a forward that returns probabilities");
     const DienPlan p = dien_plan(n->t, c);
     DienFwd f;
     f.R = R; f.group = group; f.n_groups = ngroups; f.dense = dense; f.cat = cat; f.slots = slots;
-    f.obs_out = obs ? obs : n->obs_tmp; f.prob = prob; f.st = (hipStream_t)stream;
+    f.obs_out = obs ? obs : (n->head_out ? n->head_out : n->obs_tmp); f.prob = prob; f.st = (hipStream_t)stream;
     f.set = set; f.home = home;
     f.order_in = c.row_order ? n->row_order : nullptr;
     f.rep = c.carried ? n->part_rep : n->dd_rep;
@@ -2807,6 +2811,7 @@ int rl4rs_dien_status(rl4rs_dien* n, int32_t* flags, void* stream) {
 }  // extern "C"
 namespace rl4rs {
 void dien_set_obs_mirror(rl4rs_dien* n, float* host_visible) { if (n) n->obs_mirror = host_visible; }
+void dien_set_group_rows(rl4rs_dien* n, float* head_out) { if (n) { n->group_rows = true; n->head_out = head_out; } }
 void dien_last_partition(const rl4rs_dien* n, DienPartition* out) { *out = n->dd_info; }
 bool dien_takes_partition(const rl4rs_dien* n) { return n && n->t.row_dedup && !n->t.dup_store; }
 const int32_t* dien_row_order(const rl4rs_dien* n, int n_groups) { return (n->row_order && n->row_order_n == n_groups) ? n->row_order : nullptr; }
@@ -2846,6 +2851,9 @@ int dien_forward_lane_full(rl4rs_dien* n, int set, int32_t R, int32_t group, con
 }
 bool dien_augru_rows64(const rl4rs_dien* n, int B, int group) {
     return n && n->t.fp16x2 && n->t.augru_x && (int64_t)B * group <= n->c.max_rows && augru_rows64(n->augru_rows, B * group, group, n->S, n->n_cu);
+}
+bool dien_augru_rows64_auto(const rl4rs_dien* n, int B, int group) {
+    return dien_augru_rows64(n, B, group) && augru_rows64(0, B * group, group, n->S, n->n_cu);
 }
 int64_t dien_augru_rounds(const rl4rs_dien* n, int B, int live, int group) {
     if (!n || !n->t.fp16x2 || !n->t.augru_x || (int64_t)B * group > n->c.max_rows) return -1;

@@ -82,6 +82,8 @@ struct DienCall {
     int augru_rows;        // 0 / 32 / 64: the pin of the k_augru_x row-tile form
     int distinct_hint;     // rl4rs_dien_set_distinct_hint (0 = none)
     bool dense_vec;        // `dense` and Dn admit 16-byte loads (AugruShadowArgs::vec)
+    bool rows_differ;      // rl4rs::dien_set_group_rows armed: the rows of a group share the cache slot but not the category
+                           // columns - the group kernels k_cat_attn2g (every id but the last shared) are not selected
 };
 
 enum class PlanDedup { None, Launch, Carried };
@@ -129,7 +131,7 @@ inline DienPlan dien_plan(const DienTraits& t, const DienCall& c) {
                c.augru_rows != 64 && augru_shadow_room(c.distinct_hint, n_groups, t.S, t.n_cu) && g16_shadow_fits(c.R, t.Dn, t.Fld, t.U);
     p.cat_h16 = t.fp16x2 && t.cat16;
     if (p.shadow) p.cat = PlanCat::Shadow;
-    else if (t.cat_v2_shape() && t.cat_group && t.Cn >= 11 && (c.group == 8 || c.group == 9)) p.cat = c.group == 8 ? PlanCat::G8 : PlanCat::G9;
+    else if (t.cat_v2_shape() && t.cat_group && t.Cn >= 11 && (c.group == 8 || c.group == 9) && !c.rows_differ) p.cat = c.group == 8 ? PlanCat::G8 : PlanCat::G9;
     else if (t.cat_v2_shape()) p.cat = t.Cn == 21 ? PlanCat::V2_21 : PlanCat::V2_24;
     else p.cat = PlanCat::V1;
     p.dense_side = t.dense_fork;

@@ -176,6 +176,64 @@ __global__ __launch_bounds__(1024) void k_env_rows_refine(EnvDev e, const int32_
 #undef ENV_ROWS_BUILT
 #undef ENV_ROWS_DONE
 
+// Replay-ahead (step.hip): the state rows a Slate env goes through when it plays its logged actions from step c0 on -
+// row k of env b (out row b * n + k) is the row the act of step c0 + k builds: prev_actions filled up to c0 + k (the env's own up to
+// c0, which the act of c0 has written; the log's behind it, resolved as the act resolves an id out of range), zero behind, the action
+// that step's.  One wave per env, as the complete rows: the user columns and the ids are fetched once.  The rows are written last
+// step first, so that the wave's copy of prev_actions only ever loses its last entry.
+// part.rep != NULL: the wave also copies its env's entry of the partition the act of c0 left; an env whose logged actions behind
+// c0 differ from its representative's (two log lines with equal rows so far) is its own representative in the copy.
+template <bool USE_LDS>
+__global__ __launch_bounds__(1024) void k_env_rows_ahead(EnvDev e, int c0, int n, float* __restrict__ dense_out, int32_t* __restrict__ cat_out,
+                                                         AheadPart part) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float* s_item_lds = reinterpret_cast<float*>(smem);
+    const size_t item_bytes = USE_LDS ? (((size_t)e.A * e.D * 4 + 15) & ~size_t(15)) : 0;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
+    int32_t* s_prev = reinterpret_cast<int32_t*>(smem + item_bytes) + wave * e.T;
+    if (USE_LDS) {
+        stage_items(e, s_item_lds);
+        __syncthreads();
+    }
+    const float* s_item = USE_LDS ? s_item_lds : e.item_vec;
+    auto logged = [&](int b, int j) {
+        const int a = offline_action_id(e, b, j);
+        return (a < 0 || a >= e.A) ? 0 : a;
+    };
+    const int total_waves = gridDim.x * nw;
+    for (int b = blockIdx.x * nw + wave; b < e.B; b += total_waves) {
+        for (int j = lane; j < e.T; j += 64)
+            s_prev[j] = j <= c0 ? e.prev[(size_t)b * e.T + j] : (j < c0 + n ? logged(b, j) : 0);
+        if (part.rep) {
+            const int r = part.rep[b];
+            bool differs = false;
+            if (r != b)
+                for (int j = c0 + 1 + lane; j < c0 + n; j += 64) differs |= logged(b, j) != logged(r, j);
+            const bool split = __any(differs);
+            if (lane == 0) {
+                if (b < part.cnt[0]) part.active_out[b] = part.active[b];
+                if (split) {
+                    const int pos = atomicAdd(part.cnt_out, 1);      // (at most B - n_active envs split: pos < B)
+                    if (pos < e.B) part.active_out[pos] = b;
+                }
+                part.rep_out[b] = split ? b : r;
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        for (int k = n - 1; k >= 0; --k) {
+            const int c = c0 + k;
+            const size_t r = (size_t)b * n + k;
+            build_row(e, s_item, s_prev, b, 0, e.T, 1, s_prev[c], dense_out + r * e.Dn, cat_out + r * e.Cn, lane);
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            if (lane == 0) s_prev[c] = 0;
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // masked K-NN argmax in float64 (slate.py:186-191): one wave per env.
 template <typename TA>
@@ -921,6 +979,35 @@ int rl4rs::env_build_complete_rows_lane(rl4rs_env* e, int32_t rows_per_env, void
     hipStream_t st = (hipStream_t)stream;
     int R = e->d.B * rows_per_env;
     return launch_rows<2>(e, R, nullptr, e->cur_steps, rows_per_env, jb, st);
+}
+extern "C" int rl4rs_env_build_ahead_rows(rl4rs_env* e, int32_t n, float* dense_out, int32_t* cat_out, const int32_t* rep, const int32_t* active,
+                                          const int32_t* n_active, int32_t* rep_out, int32_t* active_out, int32_t* n_active_out, void* stream) {
+    RL4RS_REQUIRE(e, "build_ahead_rows: null env");
+    ENV_JOIN(e, stream);
+    const rl4rs::AheadPart part = {rep, active, n_active, rep_out, active_out, n_active_out};
+    return rl4rs::env_build_ahead_rows_lane(e, e->cur_steps - 1, n, dense_out, cat_out, rep ? &part : nullptr, stream);
+}
+// replay-ahead rows (k_env_rows_ahead), no join either: behind the act of c0 = cur_steps - 1 on the stream that ran it
+int rl4rs::env_build_ahead_rows_lane(rl4rs_env* e, int32_t c0, int32_t n, float* dense_out, int32_t* cat_out, const AheadPart* part, void* stream) {
+    RL4RS_REQUIRE(e && dense_out && cat_out, "build_ahead_rows: null argument");
+    RL4RS_REQUIRE(!e->d.is_seq, "build_ahead_rows: Slate envs only");
+    RL4RS_REQUIRE(c0 >= 0 && n >= 1 && c0 + n <= e->d.T && c0 == e->cur_steps - 1, "build_ahead_rows: steps %d..%d behind cur_steps=%d of %d",
+                  c0, c0 + n - 1, e->cur_steps, e->d.T);
+    hipStream_t st = (hipStream_t)stream;
+    AheadPart p;
+    memset(&p, 0, sizeof(p));
+    if (part) {
+        p = *part;
+        RL4RS_REQUIRE(p.rep && p.active && p.cnt && p.rep_out && p.active_out && p.cnt_out, "build_ahead_rows: incomplete partition");
+        RL4RS_HIP_TRY(hipMemcpyAsync(p.cnt_out, p.cnt, 4, hipMemcpyDeviceToDevice, st));
+    }
+    const RowsLaunch L = rows_launch(e, e->d.B * n, 2);      // one wave per env
+    if (L.lds)
+        hipLaunchKernelGGL((k_env_rows_ahead<true>), dim3(L.grid), dim3(L.threads), L.smem, st, e->d, c0, n, dense_out, cat_out, p);
+    else
+        hipLaunchKernelGGL((k_env_rows_ahead<false>), dim3(L.grid), dim3(L.threads), L.smem, st, e->d, c0, n, dense_out, cat_out, p);
+    RL4RS_LAUNCH_CHECK();
+    return RL4RS_OK;
 }
 extern "C" {
 

@@ -69,6 +69,16 @@ struct rl4rs_stepper {
     LaneLinks links;           // where the env / the scorer keep their pointer to `hook`; forgotten when that handle goes first
     int32_t* part_active_alt;  // [B]   the pair a lane transition's act writes (then exchanged with part_active / part_cnt)
     int32_t* part_cnt_alt;     // [4]
+    // Replay-ahead (step_lanes.hpp): the observation rows of the remaining transitions of a replay episode in one forward.
+    // Buffers of their own, made by the first forward (ensure_ahead): nothing the acts, the lanes' forwards or the reward step write.
+    int replay_ahead;          // rl4rs_stepper_set_replay_ahead: 0 off, 1 where the automatic rule runs the 64-row form (default), 2 also where it is pinned
+    AheadState ahead;
+    float* ah_dense;           // [B * 9, Dn]   the rows (k_env_rows_ahead)
+    int32_t* ah_cat;           // [B * 9, Cn]
+    float* ah_obs;             // [B * 9, 256]  the head output of the representatives' rows, until the last hand-out
+    int32_t* ah_rep;           // [B]  the partition the forward ran on: the act's, envs whose logged actions part later split off
+    int32_t* ah_active;        // [B]
+    int32_t* ah_cnt;           // [4]
     hipStream_t copy_stream;   // rl4rs_env_step_record_host: early device-to-host copies run here, beside the scorer's kernels
     hipEvent_t ev_ready, ev_copied;
 };
@@ -122,9 +132,21 @@ __global__ void k_lane_handout(const float* __restrict__ obs_src, float* __restr
     if (reward_dst && i < B) reward_dst[i] = reward_src[i];
 }
 
+// what a replay-ahead transition hands out: row k of every env's representative in the group forward's head output, and
+// the zero reward of a step on which none is due.  One float4 per thread, 64 threads per env.
+__global__ void k_ahead_handout(const float* __restrict__ src, const int32_t* __restrict__ rep, int n, int k, float* __restrict__ obs_dst,
+                                double* __restrict__ reward_dst, int B) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)B * 64) return;
+    const int b = (int)(i >> 6), q = (int)(i & 63);
+    reinterpret_cast<float4*>(obs_dst)[i] = reinterpret_cast<const float4*>(src + ((size_t)rep[b] * n + k) * 256)[q];
+    if (reward_dst && i < B) reward_dst[i] = 0.0;
+}
+
 // ---- lanes
 // the stream a caller gave waits for everything in flight on the lanes (have_stream == 0: the host does)
 int lanes_wait(rl4rs_stepper* s, void* stream, int have_stream) {
+    (void)ahead_cancel(s->ahead);      // whoever joins is about to touch the env or the scorer: the rows not handed out yet are dropped
     const bool used[2] = {s->lstate.used[0], s->lstate.used[1]};
     if (!lane_join(s->lstate)) return RL4RS_OK;
     for (int i = 0; i < 2; ++i) {
@@ -376,6 +398,156 @@ int lane_transition(rl4rs_stepper* s, const LanePlan& lp, const LaneState& befor
     return RL4RS_OK;
 }
 
+// ---- replay-ahead (step_lanes.hpp)
+// the buffers of the group forward, made once by the first transition that may start one (9 rows per env: the larger group)
+int ensure_ahead(rl4rs_stepper* s) {
+    if (s->ah_obs) return RL4RS_OK;
+    const size_t R = (size_t)s->cfg.batch_size * 9, B = (size_t)s->cfg.batch_size;
+    float *cat = nullptr, *part = nullptr;
+    int rc;
+    if ((rc = dev_alloc(&s->ah_dense, R * (size_t)s->cfg.dense_feature_num)) || (rc = dev_alloc(&cat, R * (size_t)s->cfg.category_feature_num)) ||
+        (rc = dev_alloc(&part, 2 * B + 4)) || (rc = dev_alloc(&s->ah_obs, R * 256))) {
+        if (s->ah_dense) (void)hipFree(s->ah_dense);
+        if (cat) (void)hipFree(cat);
+        if (part) (void)hipFree(part);
+        s->ah_dense = nullptr;
+        return rc;
+    }
+    s->ah_cat = reinterpret_cast<int32_t*>(cat);
+    s->ah_rep = reinterpret_cast<int32_t*>(part);
+    s->ah_active = s->ah_rep + B;
+    s->ah_cnt = s->ah_active + B;
+    return RL4RS_OK;
+}
+
+int ahead_handout(rl4rs_stepper* s, int k, float* obs_dev, double* reward_dev, hipStream_t home) {
+    const int B = s->cfg.batch_size;
+    hipLaunchKernelGGL(k_ahead_handout, dim3((unsigned)(((int64_t)B * 64 + 255) / 256)), dim3(256), 0, home, s->ah_obs, s->ah_rep, s->ahead.n, k,
+                       obs_dev, reward_dev, B);
+    RL4RS_LAUNCH_CHECK();
+    return RL4RS_OK;
+}
+
+// The transition that starts a group forward (ahead_decide said Start; `was`: the state in front of it): its act as a lane transition
+// on lane 0 runs it (or, without lanes, on the caller's stream, which has joined), the rows of the act indices cur .. T - 2 with a
+// copy of the partition the act left, ONE forward of n rows per env on the scorer's first scratch set - its head output into ah_obs -
+// and the hand-out of row 0 on the caller's stream.
+int ahead_start(rl4rs_stepper* s, const AheadState& was, int cur, RowRefineArgs* rf, const int32_t* actions_dev, float* obs_dev, double* reward_dev,
+                void* stream) {
+    hipStream_t home = (hipStream_t)stream;
+    const int B = s->cfg.batch_size, n = s->ahead.n;
+    const bool lanes = s->ahead.lanes;
+    const LaneState before = s->lstate;
+    hipStream_t st = home;
+    hipEvent_t before_augru = nullptr;
+    if (lanes) {
+        const LanePlan lp = lane_ahead_start(s->lstate);
+        StepLane& l = s->lane[0];
+        st = l.st;
+        // (a wait that cannot be enqueued: nothing of the transition has been, the state in front of it stands again)
+        hipError_t he = hipSuccess;
+        if (lp.wait_entry && (he = hipEventRecord(s->ev_entry, home)) == hipSuccess) he = hipStreamWaitEvent(st, s->ev_entry, 0);
+        if (he == hipSuccess && lp.wait_act) he = hipStreamWaitEvent(st, s->lane[1].act_done, 0);
+        if (he != hipSuccess) {
+            lane_undo(s->lstate, before);
+            s->ahead = was;
+            set_error("env_step_discrete: %s", hipGetErrorString(he));
+            return RL4RS_EHIP;
+        }
+        if (lp.wait_act) before_augru = s->lane[1].done;      // the forward in flight on lane 1 leaves the chip first
+        // as every lane transition: the act writes the other row set and the other active list / counter pair
+        if (!rf->active_src) { rf->active_src = s->part_active; rf->n_active_src = s->part_cnt; }
+        rf->active = s->part_active_alt;
+        rf->cnt = s->part_cnt_alt;
+        env_flip_rows(s->env);
+    } else {
+        const AheadState now = s->ahead;
+        const int rcj = lanes_wait(s, stream, 1);      // (a join drops the rows of a forward in flight: not those of the one about to start)
+        s->ahead = now;
+        if (rcj) { s->ahead = was; return rcj; }
+    }
+    ActTail tail;
+    tail.done = nullptr; tail.done_v = 0;
+    tail.zero_reward = nullptr;                  // (the hand-out writes the caller's block on the caller's stream)
+    tail.next_action = s->next_off + (size_t)(cur + 1) * B;
+    tail.next_cur = cur + 1;
+    int rc = rl4rs::env_act_discrete_tail(s->env, actions_dev, tail, st, rf);
+    if (rc) {      // nothing was enqueued
+        if (lanes) { env_flip_rows(s->env); lane_undo(s->lstate, before); }
+        env_rows_current(s->env, &s->dense, &s->cat);
+        s->ahead = was;
+        return rc;
+    }
+    if (lanes) {
+        std::swap(s->part_active, s->part_active_alt);
+        std::swap(s->part_cnt, s->part_cnt_alt);
+    }
+    env_rows_current(s->env, &s->dense, &s->cat);
+    refined(s);
+    s->next_off_cur = cur + 1;
+    AheadPart part = {s->part_rep[s->part_cur], s->part_active, s->part_cnt, s->ah_rep, s->ah_active, s->ah_cnt};
+    rc = rl4rs::env_build_ahead_rows_lane(s->env, cur, n, s->ah_dense, s->ah_cat, &part, st);
+    // (lane 1's later acts rewrite the partition the builder read: `act_done` stands behind the builder)
+    if (lanes && hipEventRecord(s->lane[0].act_done, st) != hipSuccess && !rc) {
+        set_error("env_step_discrete: hipEventRecord failed");
+        rc = RL4RS_EHIP;
+    }
+    if (!rc) {
+        rl4rs::dien_set_group_rows(s->dien, s->ah_obs);
+        rc = rl4rs_dien_set_row_partition(s->dien, s->ah_rep, s->ah_active, s->ah_cnt, B);
+    }
+    if (!rc) rc = dien_forward_lane_full(s->dien, 0, B * n, n, s->ah_dense, s->ah_cat, s->slots, nullptr, nullptr, st, stream, nullptr, before_augru);
+    if (lanes) (void)hipEventRecord(s->lane[0].done, st);
+    if (!rc && lanes && hipStreamWaitEvent(home, s->lane[0].done, 0) != hipSuccess) {
+        set_error("env_step_discrete: hipStreamWaitEvent failed");
+        rc = RL4RS_EHIP;
+    }
+    if (rc) {      // the act happened, the forward did not: no row to hand out, the env is where the act left it
+        s->ahead.active = false;
+        s->ahead.handed -= 1;
+        s->ahead.started -= 1;
+        return rc;
+    }
+    return ahead_handout(s, 0, obs_dev, reward_dev, home);
+}
+
+// A later transition of the replay (ahead_decide said Next): its act alone - on lane 1 behind the row builder, or on the caller's
+// stream - and row cur - c0 of the forward's output, handed out on the caller's stream behind the forward.
+int ahead_next(rl4rs_stepper* s, const AheadState& was, int cur, RowRefineArgs* rf, const int32_t* actions_dev, float* obs_dev, double* reward_dev,
+               void* stream) {
+    hipStream_t home = (hipStream_t)stream;
+    const int B = s->cfg.batch_size;
+    const bool lanes = s->ahead.lanes;
+    const LaneState before = s->lstate;
+    hipStream_t st = home;
+    if (lanes) {
+        (void)lane_ahead_next(s->lstate);
+        st = s->lane[1].st;
+        RL4RS_HIP_TRY(hipStreamWaitEvent(st, s->lane[0].act_done, 0));
+    }
+    ActTail tail;
+    tail.done = nullptr; tail.done_v = 0;
+    tail.zero_reward = nullptr;
+    tail.next_action = s->next_off + (size_t)(cur + 1) * B;      // (cur + 1 <= T - 1)
+    tail.next_cur = cur + 1;
+    const int rc = rl4rs::env_act_discrete_tail(s->env, actions_dev, tail, st, rf);
+    if (rc) {
+        if (lanes) lane_undo(s->lstate, before);
+        s->ahead = was;
+        return rc;
+    }
+    if (rf) refined(s);
+    s->next_off_cur = cur + 1;
+    if (lanes) {
+        RL4RS_HIP_TRY(hipEventRecord(s->lane[1].act_done, st));
+        RL4RS_HIP_TRY(hipEventRecord(s->lane[1].done, st));
+        // the caller's stream: behind the forward (the row) and behind the act (the logged-action row the caller reads next)
+        RL4RS_HIP_TRY(hipStreamWaitEvent(home, s->lane[0].done, 0));
+        RL4RS_HIP_TRY(hipStreamWaitEvent(home, s->lane[1].done, 0));
+    }
+    return ahead_handout(s, cur - s->ahead.c0, obs_dev, reward_dev, home);
+}
+
 // the step counter in front of the act behind which the next reward is due (the rule of rl4rs_env_is_reward_step at cur + 1)
 int reward_act(const rl4rs_stepper* s, int cur) {
     const int T = s->cfg.max_steps;
@@ -429,6 +601,7 @@ int attach(rl4rs_env* env, rl4rs_dien* dien, rl4rs_simnet* simnet, const int32_t
         s->overlap = s->reset_lane = s->reward_lane = s->lanes_made;
     }
     s->act_tail = true;
+    s->replay_ahead = dien != nullptr ? 1 : 0;
     s->obs_fold = true;
     s->distinct_hint = s->cfg.batch_size;
     void* p;
@@ -473,6 +646,10 @@ int rl4rs_stepper_destroy(rl4rs_stepper* s) {
     }
     if (s->probs) (void)hipFree(s->probs);
     if (s->p_last) (void)hipFree(s->p_last);
+    if (s->ah_dense) (void)hipFree(s->ah_dense);
+    if (s->ah_cat) (void)hipFree(s->ah_cat);
+    if (s->ah_obs) (void)hipFree(s->ah_obs);
+    if (s->ah_rep) (void)hipFree(s->ah_rep);
     if (s->next_off) (void)hipFree(s->next_off);
     if (s->part_rep[0]) (void)hipFree(s->part_rep[0]);
     if (s->ev_ready) (void)hipEventDestroy(s->ev_ready);
@@ -507,6 +684,37 @@ int rl4rs_env_step_discrete(rl4rs_stepper* s, const int32_t* actions_dev, float*
         c.to_reward = (c.reward_due || !(s->reset_lane || s->reward_lane)) ? 0 : reward_act(s, cur) - cur;
         c.no_reward_lane = !s->reward_lane;
         c.reward_fold = c.reward_due && reward_dev && c.overlap && c.dien_x && refine && fold_obs(s);
+        {
+            // replay-ahead: the start of a group forward, the hand-out of its next row, or a transition like any other
+            AheadCall a;
+            memset(&a, 0, sizeof(a));
+            a.on = s->replay_ahead != 0 && s->act_tail;
+            a.own_row = own_row;
+            a.slate = !s->cfg.is_seq && !done_dev && !mask_bits_dev && (reinterpret_cast<uintptr_t>(obs_dev) & 15) == 0;
+            a.dien_x = s->dien != nullptr;
+            a.carried = refine;
+            a.cur = cur; a.T = T;
+            if (a.on && a.dien_x && (s->ahead.active || ahead_rows(cur, T) == 8 || ahead_rows(cur, T) == 9)) {
+                // (1: only where the group forward fills the chip twice over, the regime the gain was reasoned and measured in - a
+                // forward of a few workgroups is no faster than the launches it replaces and its first row arrives later)
+                for (int i = 0; i < 2; ++i)
+                    a.rows64[i] = s->replay_ahead == 2 ? rl4rs::dien_augru_rows64(s->dien, s->cfg.batch_size, 8 + i)
+                                                       : rl4rs::dien_augru_rows64_auto(s->dien, s->cfg.batch_size, 8 + i);
+            }
+            a.lanes = lane_room(c);
+            // (no memory for the forward's buffers: this stepper goes on without replay-ahead, every transition as it was)
+            if (!s->ahead.active && ahead_trigger(a) && ensure_ahead(s) != RL4RS_OK) {
+                (void)hipGetLastError();
+                s->replay_ahead = 0;
+                a.on = false;
+            }
+            const AheadState was = s->ahead;
+            bool dropped = false;
+            const AheadStep step = ahead_decide(s->ahead, a, &dropped);
+            if (dropped) { const int rcj = lanes_wait(s, stream, 1); if (rcj) return rcj; }
+            if (step == AheadStep::Start) return ahead_start(s, was, cur, &rf, actions_dev, obs_dev, reward_dev, stream);
+            if (step == AheadStep::Next) return ahead_next(s, was, cur, refine ? &rf : nullptr, actions_dev, obs_dev, reward_dev, stream);
+        }
         const LaneState before = s->lstate;
         const LanePlan lp = lane_decide(s->lstate, c);
         if (lp.lane) return lane_transition(s, lp, before, cur, &rf, actions_dev, obs_dev, reward_dev, stream);
@@ -573,6 +781,23 @@ int rl4rs_stepper_set_reset_lane(rl4rs_stepper* s, int32_t on) {
 int rl4rs_stepper_set_reward_lane(rl4rs_stepper* s, int32_t on) {
     RL4RS_REQUIRE(s, "stepper_set_reward_lane: null argument");
     s->reward_lane = on != 0 && s->lanes_made;
+    return RL4RS_OK;
+}
+
+// Replay-ahead: 0 off - every transition issues the launches it issued without it; 1 (default) where a forward of 8 / 9
+// rows per env takes the 64-row form of k_augru_x by the automatic rule; 2 also where that form is pinned (small batches: tests).
+// A forward in flight keeps the rows it has (they are dropped like any others when the next transition finds the switch off).
+int rl4rs_stepper_set_replay_ahead(rl4rs_stepper* s, int32_t on) {
+    RL4RS_REQUIRE(s && on >= 0 && on <= 2, "stepper_set_replay_ahead: bad argument");
+    s->replay_ahead = s->dien != nullptr ? on : 0;
+    return RL4RS_OK;
+}
+
+int rl4rs_stepper_replay_stats(const rl4rs_stepper* s, int64_t* started, int64_t* handed, int64_t* dropped) {
+    RL4RS_REQUIRE(s, "stepper_replay_stats: null argument");
+    if (started) *started = s->ahead.started;
+    if (handed) *handed = s->ahead.handed;
+    if (dropped) *dropped = s->ahead.dropped;
     return RL4RS_OK;
 }
 

@@ -171,4 +171,94 @@ inline LanePlan lane_decide(LaneState& s, const LaneCall& c) {
     return p;
 }
 
+// ---- replay-ahead.  In a replay loop the observation row of transition k is a function of the log line and the logged
+// actions up to k, all of which the stepper knows: once the caller hands back the stepper's own logged-action row (own_row) at act
+// index c0, the rows of the transitions c0 .. T - 2 are scored in ONE forward of n = T - 1 - c0 rows per env - the 64-row form of
+// k_augru_x, where a row costs about two thirds of what it costs in an observation-sized launch - and every later transition runs its
+// act alone and is handed its row.  A caller that deviates (a foreign action pointer, any other entry point, a reset) wastes the rows
+// not handed out yet, nothing else: env state was only ever advanced by real acts.
+struct AheadCall {
+    bool on;               // rl4rs_stepper_set_replay_ahead
+    bool own_row;          // as LaneCall::own_row
+    bool slate;            // a Slate env (no SeqSlate), discrete actions, neither done_dev nor mask_bits_dev asked for
+    bool dien_x;           // the scorer is the DIEN on the k_augru_x path ...
+    bool carried;          // ... and the act of this transition carries the partition
+    bool rows64[2];        // dien_augru_rows64(dien, B, 8) / (dien, B, 9): the forward of 8 / 9 rows per env runs the 64-row form
+    bool lanes;            // the two lanes may be used (lane_room, both handles linked): the forward runs on lane 0, the later acts
+                           // on lane 1; false: everything on the caller's stream
+    int cur, T;            // the act index of this transition, the horizon
+};
+struct AheadState {
+    bool active;           // rows of a forward are still to be handed out
+    bool lanes;            // the forward in flight was issued on the lanes
+    int c0, n;             // its first act index, its rows per env
+    int next;              // the act index whose row is handed out next
+    int64_t started, handed, dropped;      // forwards started; rows per env handed out / dropped (rl4rs_stepper_replay_stats)
+};
+enum class AheadStep { None, Start, Next };
+
+inline int ahead_rows(int cur, int T) { return T - 1 - cur; }
+inline bool ahead_trigger(const AheadCall& c) {
+    const int n = ahead_rows(c.cur, c.T);
+    return c.on && c.own_row && c.slate && c.dien_x && c.carried && (n == 8 || n == 9) && c.rows64[n - 8];
+}
+// every way out but the last hand-out: the rows not handed out yet are dropped (step.hip joins where it has to)
+inline bool ahead_cancel(AheadState& s) {
+    if (!s.active) return false;
+    s.dropped += s.c0 + s.n - s.next;
+    s.active = false;
+    return true;
+}
+// what this transition is: the start of a forward (row 0 is handed out with it), the hand-out of the next row behind its act alone,
+// or a transition like any other (*dropped: a forward was in flight and the caller deviated - join first)
+inline AheadStep ahead_decide(AheadState& s, const AheadCall& c, bool* dropped) {
+    *dropped = false;
+    if (s.active) {
+        if (c.on && c.own_row && c.slate && c.cur == s.next && c.cur < s.c0 + s.n) {
+            s.next += 1;
+            s.handed += 1;
+            if (s.next == s.c0 + s.n) s.active = false;
+            return AheadStep::Next;
+        }
+        *dropped = ahead_cancel(s);
+    }
+    if (!ahead_trigger(c)) return AheadStep::None;
+    s.active = true;
+    s.lanes = c.lanes;
+    s.c0 = c.cur;
+    s.n = ahead_rows(c.cur, c.T);
+    s.next = c.cur + 1;
+    s.started += 1;
+    s.handed += 1;
+    return AheadStep::Start;
+}
+// the lane side of a start on the lanes: the act of c0, the row builder and the forward take lane 0 (the scorer's full-size scratch
+// set), behind `act_done` of a transition in flight on lane 1 (the reset's forward) or, on lane 0, in stream order; the lane's own
+// buffers are not written, so no hand-out is waited for
+inline LanePlan lane_ahead_start(LaneState& s) {
+    LanePlan p = {};
+    p.lane = true;
+    p.on = 0;
+    p.wait_entry = !s.in_flight;
+    p.wait_act = s.in_flight && s.last == 1;
+    s.in_flight = true;
+    s.used[0] = true;
+    s.last = 0;
+    s.next = 1;
+    return p;
+}
+// a later act: lane 1, behind lane 0's `act_done` (recorded behind the row builder: the act rewrites what it read).  It leaves the
+// state a reward step looks for: the transition in flight last is lane 1's, so the folded reward step takes lane 0 behind the forward
+inline LanePlan lane_ahead_next(LaneState& s) {
+    LanePlan p = {};
+    p.lane = true;
+    p.on = 1;
+    p.wait_act = true;
+    s.in_flight = true;
+    s.used[1] = true;
+    s.last = 1;
+    s.next = 0;
+    return p;
+}
+
 }  // namespace rl4rs

@@ -250,6 +250,24 @@ class DeviceEnv(object):
         else:
             check(self.lib.rl4rs_env_build_complete_rows(self.h, rows_per_env, _stream()))
 
+    def build_ahead_rows(self, n, partition=None):
+        """-> (dense f32 [B * n, Dn], cat i32 [B * n, Cn]): the state rows of the act just taken and of the n - 1 acts behind it under
+        the logged actions (rl4rs_env_build_ahead_rows).  ``partition`` = (rep i32 [B], active i32 [n_active], n_active
+        i32 [1]) device tensors: also -> (rep, active [B], n_active [1]), the copy in which envs whose later logged actions part
+        from their representative's stand for themselves."""
+        dense = torch.empty((self.B * n, self.Dn), dtype=torch.float32, device=self.device)
+        cat = torch.empty((self.B * n, self.Cn), dtype=torch.int32, device=self.device)
+        if partition is None:
+            check(self.lib.rl4rs_env_build_ahead_rows(self.h, n, _ptr(dense), _ptr(cat), None, None, None, None, None, None, _stream()))
+            return dense, cat
+        rep, active, cnt = partition
+        assert all(t.dtype == torch.int32 and t.is_cuda and t.is_contiguous() for t in partition) and rep.numel() == self.B
+        out = (torch.empty(self.B, dtype=torch.int32, device=self.device), torch.full((self.B,), -1, dtype=torch.int32, device=self.device),
+               torch.zeros(1, dtype=torch.int32, device=self.device))
+        check(self.lib.rl4rs_env_build_ahead_rows(self.h, n, _ptr(dense), _ptr(cat), _ptr(rep), _ptr(active), _ptr(cnt), _ptr(out[0]),
+                                                  _ptr(out[1]), _ptr(out[2]), _stream()))
+        return dense, cat, out
+
     def reward(self, probs, p_last=None):
         out = torch.empty(self.B, dtype=torch.float64, device=self.device)
         m = self.n_complete - (1 if p_last is not None else 0)
@@ -333,7 +351,7 @@ class DeviceStepper(object):
     (rl4rs_env_step_discrete / rl4rs_env_step_conti = RecSimBase._step, base.py:157-170)."""
 
     def __init__(self, env, net, slots, act_tail=True, obs_fold=True, partition_carry=True, step_overlap=True, reset_lane=True,
-                 reward_lane=True):
+                 reward_lane=True, replay_ahead=True):
         """``act_tail=False`` (config['no_act_tail'] / RL4RS_NO_ACT_TAIL=1): rl4rs_env_step_discrete launches k_step_tail as it
         did and leaves no next-step logged actions (rl4rs_stepper_set_act_tail).  ``obs_fold=False``
         (config['no_reward_obs_fold'] / RL4RS_NO_REWARD_OBS_FOLD=1): a reward step runs its observation forward and then the
@@ -342,7 +360,10 @@ class DeviceStepper(object):
         rows itself, as it did (rl4rs_stepper_set_partition_carry).  ``step_overlap=False`` (config['no_step_overlap'] /
         RL4RS_NO_STEP_OVERLAP=1): every transition runs on the caller's stream (rl4rs_stepper_set_step_overlap).
         ``reset_lane=False`` (config['no_reset_lane'] / RL4RS_NO_RESET_LANE=1): ``observe`` takes no lane;
-        ``reward_lane=False`` (config['no_reward_lane'] / RL4RS_NO_REWARD_LANE=1): every reward step joins."""
+        ``reward_lane=False`` (config['no_reward_lane'] / RL4RS_NO_REWARD_LANE=1): every reward step joins.
+        ``replay_ahead=False`` (config['no_replay_ahead'] / RL4RS_NO_REPLAY_AHEAD=1): no transition scores the rows of the ones behind
+        it (rl4rs_stepper_set_replay_ahead); ``'pinned'`` (config['replay_ahead'] = 'pinned' / RL4RS_REPLAY_AHEAD=pinned):
+        also where the 64-row form of the AUGRU launch is pinned and not chosen by the automatic rule (small batches)."""
         self.lib = _lib.load()
         self.env, self.net, self.slots = env, net, slots          # keep the handles and the slot table alive
         assert slots.dtype == torch.int32 and slots.is_contiguous() and slots.shape[1] == env.B
@@ -363,6 +384,8 @@ class DeviceStepper(object):
             check(self.lib.rl4rs_stepper_set_reset_lane(self.h, 0))
         if not reward_lane:
             check(self.lib.rl4rs_stepper_set_reward_lane(self.h, 0))
+        if replay_ahead is not True:         # False: off; 'pinned': also where the 64-row AUGRU form is pinned, not chosen
+            check(self.lib.rl4rs_stepper_set_replay_ahead(self.h, 2 if replay_ahead == 'pinned' else 0))
         self.reset_lane = bool(step_overlap and reset_lane)
         self._distinct_hint = None
         self.B, self.A, self.E, self.W, self.device = env.B, env.A, env.E, env.W, env.device
@@ -399,6 +422,13 @@ class DeviceStepper(object):
         a, b = C.c_int64(0), C.c_int64(0)
         check(self.lib.rl4rs_stepper_lane_stats_ex(self.h, C.byref(a), C.byref(b)))
         return int(a.value), int(b.value)
+
+    def replay_stats(self):
+        """(group forwards started, rows per env handed out, rows per env dropped) since the stepper was created
+        (rl4rs_stepper_replay_stats)."""
+        a, b, d = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        check(self.lib.rl4rs_stepper_replay_stats(self.h, C.byref(a), C.byref(b), C.byref(d)))
+        return int(a.value), int(b.value), int(d.value)
 
     def observe(self):
         """rl4rs_stepper_observe: the observation behind a reset as a lane transition -> obs f32 [B, 256], or None where the lane

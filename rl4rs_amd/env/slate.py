@@ -634,7 +634,10 @@ class SlateRecEnv(RecSimBase):
             # observation forward / the folded reward step on the caller's stream, each alone
             self._stepper = D.DeviceStepper(env, net, slots, act_tail=not no_tail, obs_fold=not no_fold, partition_carry=not no_carry,
                                             step_overlap=not no_overlap, reset_lane=self._lane_switch('reset_lane'),
-                                            reward_lane=self._lane_switch('reward_lane'))
+                                            reward_lane=self._lane_switch('reward_lane'),
+                                            # config['no_replay_ahead'] (RL4RS_NO_REPLAY_AHEAD=1): every replay transition scores its own row
+                                            replay_ahead=self._lane_switch('replay_ahead') and (
+                                                'pinned' if self.config.get('replay_ahead', os.environ.get('RL4RS_REPLAY_AHEAD', '')) == 'pinned' else True))
             self._stepper_key = key
         # envs the scorer's row dedup is expected to leave: the batch's distinct log lines - but SeqSlate gives every env a slot of
         # its own for the second sequence input from the second page on (_seq_slots_own): no two envs are duplicates there

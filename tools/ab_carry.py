@@ -11,6 +11,7 @@ Prints one line `ARM <name> <workload> <ms per episode-batch>` per workload.
     python tools/ab_carry.py --name off --no-carry                      (r19: --name off --kernels no_lazy_expand)
     python tools/ab_carry.py --name serial --no-step-overlap            (r26: consecutive transitions on the caller's stream)
     python tools/ab_carry.py --name noreset --no-reset-lane             (r27: each half of DESIGN 39 off alone; --no-reward-lane)
+    python tools/ab_carry.py --name noahead --no-replay-ahead           (r28: every replay transition scores its own row)
     python tools/ab_carry.py --name parent --tree tools/_ab/parent      (another tree with its own library and Python)"""
 import argparse
 import os
@@ -26,6 +27,7 @@ def main():
     ap.add_argument('--no-step-overlap', action='store_true', help="config['no_step_overlap'] (profiles/r26_ab.md)")
     ap.add_argument('--no-reset-lane', action='store_true', help="config['no_reset_lane'] (profiles/r27_ab.md)")
     ap.add_argument('--no-reward-lane', action='store_true', help="config['no_reward_lane'] (profiles/r27_ab.md)")
+    ap.add_argument('--no-replay-ahead', action='store_true', help="config['no_replay_ahead'] (profiles/r28_ab.md)")
     ap.add_argument('--kernels', default=None, help="config['scorer_kernels'] (e.g. no_lazy_expand: the `off` arm of profiles/r19_lazy_ab.md)")
     a = ap.parse_args()
     sys.path.insert(0, os.path.abspath(a.tree))
@@ -47,6 +49,8 @@ def main():
             cfg['no_reset_lane'] = True
         if a.no_reward_lane:
             cfg['no_reward_lane'] = True
+        if a.no_replay_ahead:
+            cfg['no_replay_ahead'] = True
         if a.kernels is not None:
             cfg['scorer_kernels'] = a.kernels
         env = bench.build_env(cfg, False)
