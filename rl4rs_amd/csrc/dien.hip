@@ -2888,7 +2888,8 @@ int rl4rs_dien_kernel_label(rl4rs_dien* n, int which, char* buf, int32_t cap) {
     switch (which) {
         case KID_CAT: s = t.cat_v2_shape() ? (t.cat_group ? "k_cat_attn2 / k_cat_attn2g (grouped rows)" : "k_cat_attn2") : "k_cat_attn"; break;
         case KID_DENSE:
-            s = t.dense_grouped() ? "k_gemm_h16_pair(dense tower, both layers + q-side term of the DIN scores)"
+            s = t.pair_one_grid() ? "k_gemm_h16_pair(dense tower, both layers + q-side term of the DIN scores)"
+                : t.dense_grouped() ? "k_gemm_h16<chain>(dense tower, both layers) + k_gemm_h16(q-side term of the DIN scores): the pair's two launches"
                 : t.dense_chained() ? "k_gemm_h16<chain>(dense tower, both layers)" : std::string(gemm) + " x2 (dense tower)";
             break;
         case KID_DIN:

@@ -65,6 +65,11 @@ struct DienTraits {
     // the derived predicates, each in this one place
     bool dense_chained() const { return gemm16 && dense_chain && U <= 128 && U % 16 == 0; }       // the tower is one chained launch
     bool dense_grouped() const { return fp16x2 && dense_chained() && gemm_group && !dense_fork; } // ... issued as a pair with the q-side term
+    // ... and that pair as ONE grid (k_gemm_h16_pair).  launch_gemm_h16_pair needs both problems one block of columns wide
+    // (gemm_h16_route: up to 128 columns; the q-side term is S * 64 wide) and loading their rows alike (dense rows of Dn % 4 != 0
+    // take scalar loads, the query rows never do); otherwise it issues its two launches, bit-identical.  An unaligned `dense`
+    // pointer of a call does the same to that call.
+    bool pair_one_grid() const { return dense_grouped() && S * 64 <= 128 && (Dn & 3) == 0; }
     bool din_h16() const { return fp16x2 && din16; }
     bool din_x_selected() const { return din_h16() && h1f; }
     bool cat_v2_shape() const { return cat_v2 && E == 128 && Cn <= 24; }
