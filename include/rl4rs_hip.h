@@ -1630,6 +1630,62 @@ int rl4rs_ope_greedy_rows(int32_t N, const float* scores_dev, int32_t A, int64_t
                           const int32_t* logged_dev, const float* value_dev, int64_t value_ld, int32_t* actions_dev,
                           double* pi_dev, double* q_dev, float* masked_out_dev, void* stream);
 
+/* ---- Offline scorers (d3rlpy 0.91 metrics/scorer.py as published - parity unpinned; rl4rs/utils/d3rlpy_scorer.py) ----
+ *
+ * One pass over evaluation episodes: the caller runs each network once per row and hands the score rows to rl4rs_score_rows, which
+ * writes the few scalars every scorer needs; rl4rs_score_episodes turns those columns into every score at once.
+ *
+ * rl4rs_score_rows: one wave per row, four rows per workgroup; scores_dev [N, A] float32 with row stride ld (Q values, or the
+ * imitator's logits for a learner without Q).  A row (and its imitator row) of up to 4096 floats together is read from memory once.
+ *   a_pi[n]   the learners' greedy rule (rl4rs_q_best_action's own device function): first maximum of the row, or the BCQ rule
+ *             when imitator_dev [N, A] (row stride imitator_ld) and action_flexibility are given
+ *   qp[n]     scores[n, a_pi[n]]
+ *   qd[n]     scores[n, logged[n]]; a logged action outside [0, A) gives NaN
+ *   a_mask[n] rl4rs_env_predict_with_mask on the same row: the catalogue tables of `env`, the previous actions and cur_step taken
+ *             from the last page_items + 1 columns of the observation row obs_dev[n * obs_ld .. + obs_dim), converted by truncation
+ * Every output is optional (NULL); qd needs logged_dev, a_mask needs env and obs_dev. */
+int rl4rs_score_rows(int32_t N, const float* scores_dev, int32_t A, int64_t ld, const float* imitator_dev, int64_t imitator_ld,
+                     float action_flexibility, const int32_t* logged_dev, const rl4rs_env* env, const float* obs_dev, int32_t obs_dim,
+                     int64_t obs_ld, float* qd_dev, int32_t* a_pi_dev, float* qp_dev, int32_t* a_mask_dev, void* stream);
+/* diff[n] = sum_k (actions[n, k] - predicted[n, k])^2 in float64 (continuous_action_diff_scorer); both [N, E] float32, contiguous */
+int rl4rs_score_action_diff(int32_t N, int32_t E, const float* actions_dev, const float* predicted_dev, double* diff_dev, void* stream);
+
+/* The per-transition columns of a pass, device arrays of `rows` entries; any may be NULL (the slots that need it are NaN). */
+typedef struct rl4rs_score_cols {
+    const float* qd;       /* Q(o, a), reverse-transformed by the caller where the learner has a reward scaler */
+    const float* qp;       /* Q(o, pi(o)) */
+    const float* qn;       /* Q(o', pi(o')) */
+    const float* r_td;     /* next reward on the scale the critic was trained on */
+    const float* r_raw;    /* next reward as logged */
+    const float* ter;      /* terminal flag */
+    const int32_t* a;      /* logged action */
+    const int32_t* a_pi;   /* predict(o) */
+    const int32_t* a_mask; /* predict_with_mask(o) */
+    const double* diff;    /* rl4rs_score_action_diff */
+} rl4rs_score_cols;
+enum {
+    RL4RS_SCORE_TD_ERROR = 0,          /* mean (qd - (r_td + gamma qn (1 - ter)))^2                       td_error_scorer */
+    RL4RS_SCORE_DSA = 1,               /* mean S, S_last = adv, S_j = adv_j + gamma S_{j+1} inside each window of 1024 rows of an
+                                          episode, adv = qd - qp                                           discounted_sum_of_advantage_scorer */
+    RL4RS_SCORE_AVG_VALUE = 2,         /* mean qp                                                         average_value_estimation_scorer */
+    RL4RS_SCORE_INIT_VALUE = 3,        /* mean over episodes of qp at the episode's first row            initial_state_value_estimation_scorer */
+    RL4RS_SCORE_SOFT_OPC = 4,          /* mean qd over rows of episodes with return >= threshold - mean qd; NaN when none succeeds */
+    RL4RS_SCORE_ACTION_MATCH = 5,      /* mean [a_pi == a]                                                d3rlpy's discrete_action_match_scorer */
+    RL4RS_SCORE_ACTION_MATCH_MASK = 6, /* mean [a_mask == a]                                              the reference's */
+    RL4RS_SCORE_ACTION_DIFF = 7,       /* mean diff                                                       continuous_action_diff_scorer */
+    RL4RS_SCORE_N_ROWS = 8,
+    RL4RS_SCORE_N_EPISODES = 9,
+    RL4RS_SCORE_N_SUCCESS_ROWS = 10,   /* rows of successful episodes (NaN without a threshold) */
+    RL4RS_SCORE_N_STATS = 11
+};
+/* Every score of E episodes at once: episode e is rows [starts[e], starts[e + 1]) of the columns (starts_dev int64 [E + 1],
+ * clamped to [0, rows]).  One lane walks an episode of any length: its return (the float64 sum of r_raw), the success flag, the
+ * first-row value and the backward scan with its 1024-row restarts, all float64; then a fixed-order float64 reduction (lane, wave,
+ * block, blocks in order - no float atomics), so two runs give the same bytes.  Waits for `stream`; stats_host
+ * double[RL4RS_SCORE_N_STATS].  A slot whose columns were not supplied is NaN. */
+int rl4rs_score_episodes(int32_t E, const int64_t* starts_dev, int64_t rows, const rl4rs_score_cols* cols, double gamma,
+                         int32_t has_threshold, double threshold, double* stats_host, void* stream);
+
 /* ---- On-device Exact-K (rl4rs/nets/exact_k, script/exact_k_train.py): the pointer-network slate generator and its critic ----
  *
  * Generator: enc_user = relu(obs W + b) [hidden]; enc[n, a] = dropout(concat(enc_user[n], item_table[a] * sqrt(hidden))) over the

@@ -165,6 +165,12 @@ class StepRecord(C.Structure):
                                          'offline_action', 'host_bytes', 'total_bytes')] + [('obs_dim', C.c_int32), ('d3rl_cols', C.c_int32)]
 
 
+class ScoreCols(C.Structure):
+    """rl4rs_score_cols: device addresses of the per-transition columns of a scorer pass (0 = not supplied)."""
+    SCORE_COLS = ('qd', 'qp', 'qn', 'r_td', 'r_raw', 'ter', 'a', 'a_pi', 'a_mask', 'diff')
+    _fields_ = [(n, C.c_void_p) for n in SCORE_COLS]
+
+
 STEP_WANT = {'mask_i64': 1, 'mask_bits': 2, 'd3rl_obs': 4, 'click_p': 8, 'offline_action': 16}      # RL4RS_STEP_WANT_*
 
 _lib = None
@@ -405,6 +411,9 @@ SIGNATURES = {
     'rl4rs_policy_adam_step_clip_by_var': (_I, [_P, _P, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _P]),
     'rl4rs_policy_ope_step': (_I, [_P, _I32, _P, _P, _P, _I32, _P, _P, _P, _P, _P]),
     'rl4rs_ope_greedy_rows': (_I, [_I32, _P, _I32, _I64, _P, _I32, _P, _P, _I64, _P, _P, _P, _P, _P]),
+    'rl4rs_score_rows': (_I, [_I32, _P, _I32, _I64, _P, _I64, C.c_float, _P, _P, _P, _I32, _I64, _P, _P, _P, _P, _P]),
+    'rl4rs_score_action_diff': (_I, [_I32, _I32, _P, _P, _P, _P]),
+    'rl4rs_score_episodes': (_I, [_I32, _P, _I64, C.POINTER(ScoreCols), C.c_double, _I32, C.c_double, _P, _P]),
     'rl4rs_distq_param_count': (_I64, [C.POINTER(DistqCfg)]),
     'rl4rs_distq_create': (_I, [C.POINTER(DistqCfg), _P, _P, C.POINTER(_P)]),
     'rl4rs_distq_destroy': (_I, [_P]),
@@ -487,6 +496,10 @@ REPLAY_BUFS = {'obs': 0, 'mask': 1, 'action': 2, 'reward': 3, 'done': 4, 'priori
 OPE_COLS = {'pi': 0, 'mu': 1, 'q': 2, 'reward': 3, 'logged_reward': 4}
 OPE_STATS = ('cips', 'cips_c', 'ips', 'ips_c', 'snips', 'snips_c', 'dr', 'dr_se', 'wips', 'wips_2', 'seqdr', 'seqdr_2', 'n_e', 'cv',
              'n_e_raw', 'cv_raw', 'sim_reward')
+
+# include/rl4rs_hip.h RL4RS_SCORE_* (statistics slots)
+SCORE_STATS = ('td_error', 'discounted_sum_of_advantage', 'average_value_estimation', 'initial_state_value_estimation', 'soft_opc',
+               'discrete_action_match', 'discrete_action_match_mask', 'continuous_action_diff', 'n_rows', 'n_episodes', 'n_success_rows')
 
 
 def load():

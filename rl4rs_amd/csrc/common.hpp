@@ -159,6 +159,10 @@ struct RowRefineArgs;
 int env_act_discrete_tail(rl4rs_env* e, const int32_t* actions, const ActTail& tail, void* stream, const RowRefineArgs* rf = nullptr);
 int env_act_conti_refine(rl4rs_env* e, const void* actions, int is_f64, int32_t* chosen, void* stream, const RowRefineArgs* rf);
 bool env_refine_fits(const rl4rs_env* e);
+// The catalogue tables of the predict_with_mask rule (env.hip k_predict_with_mask), read-only after rl4rs_env_set_catalog: what the
+// offline scorers' row kernel (scorers.hpp) masks a score row with.  RL4RS_ESTATE before the catalogue is loaded
+struct EnvMaskTables { int A, W, P; const uint32_t* loc_bits; const uint8_t* is_special; };      // loc_bits [4, W], is_special [A]
+int env_mask_tables(const rl4rs_env* e, EnvMaskTables* out);
 // Process-wide order of the calls that write an env's state rows (or the data they are built from) and of the scorer forwards that
 // looked for duplicate rows: a forward's partition describes an env's rows iff its stamp is the later one (step.hip)
 uint64_t next_stamp();

@@ -635,6 +635,17 @@ void env_rows_current(const rl4rs_env* e, const float** dense, const int32_t** c
     *dense = e->d.dense;
     *cat = e->d.cat;
 }
+int env_mask_tables(const rl4rs_env* e, EnvMaskTables* out) {
+    RL4RS_REQUIRE(e && out, "env_mask_tables: null argument");
+    if (!e->catalog_set) {
+        set_error("env_mask_tables: catalogue not loaded");
+        return RL4RS_ESTATE;
+    }
+    out->A = e->d.A; out->W = e->d.W; out->P = e->d.P;
+    out->loc_bits = e->d.loc_bits;
+    out->is_special = e->d.is_special;
+    return RL4RS_OK;
+}
 bool env_refine_fits(const rl4rs_env* e) {
     const RowsLaunch L = rows_launch(e, e->cfg.batch_size, 1);
     return (L.smem > row_refine_smem(L.threads) ? L.smem : row_refine_smem(L.threads)) <= 65536;

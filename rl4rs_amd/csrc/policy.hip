@@ -1593,6 +1593,7 @@ int rl4rs_policy_set_option(rl4rs_policy* p, int32_t which, int32_t value) {
 #include "clfmetrics.hpp"
 #include "rawtrain.hpp"
 #include "qlearn.hpp"
+#include "scorers.hpp"
 #include "contirl.hpp"
 #include "dqn.hpp"
 #include "td3.hpp"

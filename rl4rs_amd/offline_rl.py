@@ -83,24 +83,42 @@ def init_qnet_params(obs_dim, action_size, mask_size=0, emb_size=32, hidden1=256
     return p
 
 
-def _epoch_minibatches(columns, batch_size, n_steps, seed):
+def _epoch_minibatches(columns, batch_size, n_steps, seed, epoch_hook=None):
     """``n_steps`` minibatches over the rows of ``columns`` with an epoch-wise random permutation like d3rlpy's ``fit``.  The epoch's
     permutation is applied to the columns ONCE: minibatches are then contiguous row ranges (views), not one gather per column
-    and update."""
+    and update.  ``epoch_hook`` = (steps per epoch, f): f(epoch) runs once the consumer has used the last minibatch of an epoch
+    (1-based) - the minibatches themselves are the same with and without it."""
     n = columns[0].shape[0]
     assert n >= batch_size, 'dataset smaller than one minibatch'
 
     def batches():
         rs = np.random.RandomState(seed)
         ep, pos = None, n
-        for _ in range(n_steps):
+        for k in range(n_steps):
             if pos + batch_size > n:
                 perm = torch.from_numpy(rs.permutation(n)).to(columns[0].device)
                 ep = [t[perm] for t in columns]
                 pos = 0
             yield [t[pos:pos + batch_size] for t in ep]
             pos += batch_size
+            if epoch_hook is not None and (k + 1) % epoch_hook[0] == 0:
+                epoch_hook[1]((k + 1) // epoch_hook[0])
     return batches()
+
+
+def _score_hook(algo, per_epoch, eval_episodes, scorers):
+    """(``epoch_hook`` of a ``fit``, the dict it fills): the scorer pass after every epoch (d3rlpy's ``fit(eval_episodes=, scorers=)``)"""
+    if (eval_episodes is None) != (scorers is None):
+        raise ValueError('fit_mdp: eval_episodes and scorers go together')
+    if scorers is None:
+        return None, None
+    from . import scorers as S
+    scores = {name: [] for name in scorers}
+
+    def hook(epoch):
+        for name, value in S.run_scorers(algo, eval_episodes, scorers).items():
+            scores[name].append(value)
+    return (max(int(per_epoch), 1), hook), scores
 
 
 class _ModelIO(object):
@@ -176,17 +194,23 @@ class _ModelIO(object):
                 warnings.warn('%s was saved without a reward scaler; keeping this learner\'s (mean %.6g, std %.6g) - make sure it is the '
                               'scale the file was trained on' % (fname, self.reward_scaler.mean, self.reward_scaler.std))
 
-    def fit_mdp(self, data, n_epochs=1, discrete_action=None, **kw):
+    def fit_mdp(self, data, n_epochs=1, discrete_action=None, eval_episodes=None, scorers=None, **kw):
         """``fit`` on MDPDataset-style arrays (the dict ``offline.generate_offline_dataset`` returns) for ``n_epochs`` passes over its
-        transitions - d3rlpy's ``fit(dataset, n_epochs=...)``."""
+        transitions - d3rlpy's ``fit(dataset, n_epochs=...)``.  With ``eval_episodes`` (a ``scorers.EvalEpisodes``) and ``scorers``
+        (``{name: callable}``, see ``scorers.run_scorers``) the scorers run after every epoch and the call returns
+        ``(history, {name: [value per epoch]})``."""
         if discrete_action is None:
             discrete_action = isinstance(self, _Learner)
         tr = transitions_from_mdp(data['observations'], data['actions'], data['rewards'], data['terminals'], discrete_action=discrete_action)
         if getattr(self, 'reward_scaler', None) == 'standard':
             # d3rlpy: a scaler given by name is fitted on the dataset when fit() builds the algorithm
             self.reward_scaler = StandardRewardScaler(tr[2])
-        steps = int(n_epochs) * (tr[0].shape[0] // self.batch_size)
-        return self.fit(tr, steps, **kw)
+        per_epoch = tr[0].shape[0] // self.batch_size
+        steps = int(n_epochs) * per_epoch
+        hook, scores = _score_hook(self, per_epoch, eval_episodes, scorers)
+        if hook is None:
+            return self.fit(tr, steps, **kw)
+        return self.fit(tr, steps, epoch_hook=hook, **kw), scores
 
 
 class _Learner(_ModelIO):
@@ -201,7 +225,7 @@ class _Learner(_ModelIO):
         self.device = device
         self.total_step = 0
 
-    def _net(self, seed):
+    def _net(self, seed, max_rows=None):
         kw = {}
         M = 0
         if self.custom:                                   # batchrl_trainer.py:35-41: mask_size = page_items + 1
@@ -214,7 +238,7 @@ class _Learner(_ModelIO):
                 loc, special = tab.location_mask, tab.special_items
             kw = dict(location_mask=loc, special_items=special)
         params = init_qnet_params(self.D, self.A, M, seed=seed)
-        return D.DeviceQNet(self.D, self.A, params, mask_size=M, max_rows=self.batch_size, device=self.device, **kw)
+        return D.DeviceQNet(self.D, self.A, params, mask_size=M, max_rows=max_rows or self.batch_size, device=self.device, **kw)
 
     def _apply(self, net):
         if rdist.collectives_active():
@@ -223,12 +247,12 @@ class _Learner(_ModelIO):
             net.set_flat_gradient(g)
         net.adam_step(self.lr)
 
-    def fit(self, transitions, n_steps, shuffle_seed=None):
+    def fit(self, transitions, n_steps, shuffle_seed=None, epoch_hook=None):
         """``n_steps`` minibatch updates over ``transitions`` (tuple of tensors from ``transitions_from_mdp``), epoch-wise
-        random permutation like d3rlpy's ``fit``; returns the list of losses."""
+        random permutation like d3rlpy's ``fit``; returns the list of losses.  ``epoch_hook``: see ``_epoch_minibatches``."""
         columns = [t.to(self.nets[0].device) for t in transitions]
         seed = self.seed if shuffle_seed is None else shuffle_seed
-        losses = [self.update(*batch) for batch in _epoch_minibatches(columns, self.batch_size, n_steps, seed)]
+        losses = [self.update(*batch) for batch in _epoch_minibatches(columns, self.batch_size, n_steps, seed, epoch_hook)]
         out = [float(x) for x in torch.stack(losses).cpu()]
         for net in self.nets:
             net.check_status()
@@ -456,12 +480,12 @@ class _ContinuousLearner(_ModelIO):
             out[k] = [float(x) for x in st.cpu()] if to_host else st
         return out
 
-    def fit(self, transitions, n_steps, shuffle_seed=None, to_host=True):
+    def fit(self, transitions, n_steps, shuffle_seed=None, to_host=True, epoch_hook=None):
         """``n_steps`` updates over ``transitions`` (``transitions_from_mdp(..., discrete_action=False)``), epoch-wise random
         permutation like d3rlpy's ``fit``; returns dict of per-step loss lists (``to_host=False``: of stacked device tensors,
-        nothing waits for the GPU)."""
+        nothing waits for the GPU).  ``epoch_hook``: see ``_epoch_minibatches``."""
         columns = [t.to(self.device) for t in transitions]
-        batches = _epoch_minibatches(columns, self.batch_size, n_steps, self.seed if shuffle_seed is None else shuffle_seed)
+        batches = _epoch_minibatches(columns, self.batch_size, n_steps, self.seed if shuffle_seed is None else shuffle_seed, epoch_hook)
         act = columns[1]
         assert act.dim() == 2 and act.shape[1] == self.A and act.dtype == torch.float32, 'continuous actions [N, %d] needed' % self.A
         out = self._history([self.update(*batch) for batch in batches], to_host)
@@ -1119,25 +1143,32 @@ class MOPO(_SAC):
         return model_rollout(sample, self.dynamics, start, self.rollout_horizon, self.lam, self.generated,
                              step0=self.total_step * 64, given=given)
 
-    def fit(self, transitions, n_steps, shuffle_seed=None, to_host=True):
-        """``n_steps`` updates on mixed minibatches; a rollout before every ``rollout_interval``-th update (the first included)."""
+    def fit(self, transitions, n_steps, shuffle_seed=None, to_host=True, epoch_hook=None):
+        """``n_steps`` updates on mixed minibatches; a rollout before every ``rollout_interval``-th update (the first included).
+        ``epoch_hook`` = (steps per epoch, f): f(epoch) after the last update of an epoch."""
         real = [t.to(self.device) for t in transitions]
         assert real[1].dim() == 2 and real[1].shape[1] == self.A and real[1].dtype == torch.float32, 'continuous actions [N, %d] needed' % self.A
         hist = []
-        for _ in range(n_steps):
+        for k in range(n_steps):
             if self._rollout_due():
                 self.generate_new_data(real[0])
             batch, n_real = mixed_minibatch(real, self.generated, self.batch_size, self.real_ratio, self._gen)
             hist.append(self._update_minibatch(batch, n_real))
+            if epoch_hook is not None and (k + 1) % epoch_hook[0] == 0:
+                epoch_hook[1]((k + 1) // epoch_hook[0])
         return self._history(hist, to_host)
 
     _LOSS_KEYS = ('critic_loss', 'actor_loss', 'temp_loss')
 
-    def fit_mdp(self, data, n_epochs=1, **kw):
+    def fit_mdp(self, data, n_epochs=1, eval_episodes=None, scorers=None, **kw):
         tr = transitions_from_mdp(data['observations'], data['actions'], data['rewards'], data['terminals'], discrete_action=False)
         if self.reward_scaler == 'standard':
             self.reward_scaler = StandardRewardScaler(tr[2])
-        return self.fit(tr, int(n_epochs) * max(tr[0].shape[0] // self.batch_size, 1), **kw)
+        per_epoch = max(tr[0].shape[0] // self.batch_size, 1)
+        hook, scores = _score_hook(self, per_epoch, eval_episodes, scorers)
+        if hook is None:
+            return self.fit(tr, int(n_epochs) * per_epoch, **kw)
+        return self.fit(tr, int(n_epochs) * per_epoch, epoch_hook=hook, **kw), scores
 
 
 class COMBO(MOPO):

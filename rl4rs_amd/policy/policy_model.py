@@ -169,6 +169,12 @@ class policy_model(object):
                 return self._out(self._scores.value(x, bits), obs)
             a = D._dev_tensor(action if isinstance(action, torch.Tensor) else np.asarray(action), torch.int64, x.device).reshape(-1, 1)
             return self._out(self._scores.greedy(x, bits, want_row=True)[1].gather(1, a).reshape(-1), obs)
+        from ..dynamics import ProbabilisticEnsembleDynamics
+        if isinstance(self.policy, ProbabilisticEnsembleDynamics):
+            # the reference's dynamics scorers read pred[1] of predict_q on a wrapped dynamics model (rl4rs/utils/d3rlpy_scorer.py:100):
+            # its predict, (next_obs, reward)
+            nx, r = self.policy.predict(self._obs(obs), action)
+            return self._out(nx, obs), self._out(r, obs)
         x = self._obs(obs)
         a = torch.as_tensor(np.asarray(action) if not isinstance(action, torch.Tensor) else action).to(x.device)
         n = self._rows()
