@@ -628,6 +628,16 @@ int rl4rs_stepper_set_replay_ahead(rl4rs_stepper* s, int32_t on);
 int rl4rs_env_build_ahead_rows(rl4rs_env* e, int32_t n, float* dense_out, int32_t* cat_out, const int32_t* rep, const int32_t* active,
                                const int32_t* n_active, int32_t* rep_out, int32_t* active_out, int32_t* n_active_out, void* stream);
 int rl4rs_stepper_replay_stats(const rl4rs_stepper* s, int64_t* started, int64_t* handed, int64_t* dropped);
+/* The reward step beside the replay-ahead forward (default on where the step overlap is).  The first transition that may
+ * start a replay-ahead forward on the lanes also grows the scorer's second scratch set to B * n_complete rows (reserved once, freed with
+ * the scorer; no memory for it: the switch stays off for good and nothing fails).  A folded reward step that rl4rs_stepper_set_reward_lane
+ * would run on lane 0 then runs on lane 1 and that set when the forward in flight on lane 0 is a replay-ahead forward nothing has
+ * joined since: its act, row builder and front kernels no longer wait for that forward, its AUGRU launch still does.  Same kernels, same
+ * arguments but for the scratch pointers, same results.  on = 0: that reward step runs on lane 0 behind the forward, as it did.
+ * rl4rs_stepper_reward_beside_stats: reward steps that took lane 1 since attach, and the bytes the scorer's second scratch set holds
+ * now (read-only; either pointer may be NULL). */
+int rl4rs_stepper_set_reward_beside(rl4rs_stepper* s, int32_t on);
+int rl4rs_stepper_reward_beside_stats(const rl4rs_stepper* s, int64_t* ran, int64_t* scratch_bytes);
 /* Click probabilities of the complete-state rows of the LAST reward step, slate order: out_dev [B, n_complete] f32 - the same
  * numbers in either order of the forwards (the record form's click_p part, for rl4rs_env_step_discrete / _conti). */
 int rl4rs_stepper_click_probs(rl4rs_stepper* s, float* out_dev, void* stream);

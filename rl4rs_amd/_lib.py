@@ -311,6 +311,8 @@ SIGNATURES = {
     'rl4rs_stepper_set_replay_ahead': (_I, [_P, _I32]),
     'rl4rs_env_build_ahead_rows': (_I, [_P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'rl4rs_stepper_replay_stats': (_I, [_P, _P, _P, _P]),
+    'rl4rs_stepper_set_reward_beside': (_I, [_P, _I32]),
+    'rl4rs_stepper_reward_beside_stats': (_I, [_P, _P, _P]),
     'rl4rs_stepper_click_probs': (_I, [_P, _P, _P]),
     'rl4rs_stepper_reward_rows': (_I, [_P]),
     'rl4rs_stepper_next_offline_action': (_I, [_P, _P, _P]),

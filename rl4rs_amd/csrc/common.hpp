@@ -215,10 +215,12 @@ void env_rows_current(const rl4rs_env* e, const float** dense, const int32_t** c
 // `rows` rows: dien_forward_lane(.., set = 1, ..) runs on it, beside a forward on the handle's first set.  The lane forwards join
 // nothing themselves (the stepper orders them); `home`: the caller's stream, on which rl4rs_dien_buffer completes what they left
 int dien_reserve_lane_scratch(rl4rs_dien* n, int rows);
+// what that set holds, in bytes: padded rows x (Fld + U + E + S * ATT_H1 + S * L [+ OBS_DIM]) floats; 0 = none reserved
+int64_t dien_lane_scratch_bytes(const rl4rs_dien* n);
 int dien_forward_lane(rl4rs_dien* n, int set, int32_t R, const float* dense, const int32_t* cat, const int32_t* slots, float* obs,
                       void* stream, void* home);
-// The same with every argument of a forward: `group` rows per env and probabilities for the reward step's forward (set 0
-// only: the second set holds an observation-sized forward), and `after_dedup` (a hipEvent_t, or NULL) recorded on `stream` behind the
+// The same with every argument of a forward: `group` rows per env and probabilities for the reward step's forward (set 0,
+// or set 1 once the stepper has reserved it at that forward's size: DESIGN 42), and `after_dedup` (a hipEvent_t, or NULL) recorded on `stream` behind the
 // duplicate-row stage - the reset's observation forward looks for its duplicates itself, and the partition is all the next act needs;
 // `before_augru` (a hipEvent_t, or NULL): `stream` waits for it in front of the AUGRU launch (the reward step's, which wants the whole chip)
 int dien_forward_lane_full(rl4rs_dien* n, int set, int32_t R, int32_t group, const float* dense, const int32_t* cat, const int32_t* slots,

@@ -2836,8 +2836,24 @@ int dien_reserve_lane_scratch(rl4rs_dien* n, int rows) {
         (rc = alloc_f(n, &a.qa, (size_t)n->S * R * ATT_H1)) || (rc = alloc_f(n, &a.scores, (size_t)n->S * R * n->L))) return rc;
     if (n->tsum && (rc = alloc_f(n, &a.tsum, R * OBS_DIM))) return rc;
     a.rows = padded;
+    // What rl4rs_dien_buffer may still be asked for lies in the smaller set (the last forward ran on it: dien_settle_set, dien_settle_expand):
+    // its rows move to the new one.  Once per growth, where the allocation above has made the host wait already
+    const rl4rs_dien::ScratchSet& o = n->alt;
+    if (o.allf && (n->last_set == 1 || (n->lazy.pending && n->lazy.set == 1))) {
+        const size_t Ro = (size_t)o.rows;
+        RL4RS_HIP_TRY(hipDeviceSynchronize());
+        RL4RS_HIP_TRY(hipMemcpy(a.allf, o.allf, Ro * n->Fld * 4, hipMemcpyDeviceToDevice));
+        RL4RS_HIP_TRY(hipMemcpy(a.q, o.q, Ro * n->E * 4, hipMemcpyDeviceToDevice));
+        for (int s = 0; s < n->S; ++s)
+            RL4RS_HIP_TRY(hipMemcpy(a.scores + (size_t)s * R * n->L, o.scores + (size_t)s * Ro * n->L, Ro * n->L * 4, hipMemcpyDeviceToDevice));
+    }
     n->alt = a;
     return RL4RS_OK;
+}
+int64_t dien_lane_scratch_bytes(const rl4rs_dien* n) {
+    if (!n || !n->alt.allf) return 0;
+    const int64_t per_row = (int64_t)n->Fld + n->U + n->E + (int64_t)n->S * ATT_H1 + (int64_t)n->S * n->L + (n->tsum ? OBS_DIM : 0);
+    return (int64_t)n->alt.rows * per_row * 4;
 }
 int dien_forward_lane(rl4rs_dien* n, int set, int32_t R, const float* dense, const int32_t* cat, const int32_t* slots, float* obs,
                       void* stream, void* home) {

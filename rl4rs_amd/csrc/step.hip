@@ -79,6 +79,11 @@ struct rl4rs_stepper {
     int32_t* ah_rep;           // [B]  the partition the forward ran on: the act's, envs whose logged actions part later split off
     int32_t* ah_active;        // [B]
     int32_t* ah_cnt;           // [4]
+    // The reward step beside the group forward (step_lanes.hpp): with the scorer's second scratch set at B * n_complete
+    // rows the folded reward step behind a group forward takes lane 1 and set 1
+    bool reward_beside;        // rl4rs_stepper_set_reward_beside (default on)
+    bool beside_tried;         // ensure_ahead has asked for the full-size set ...
+    bool beside_ready;         // ... and got it; false for good where the allocation failed
     hipStream_t copy_stream;   // rl4rs_env_step_record_host: early device-to-host copies run here, beside the scorer's kernels
     hipEvent_t ev_ready, ev_copied;
 };
@@ -330,8 +335,9 @@ __global__ void k_record_status(const int32_t* env_err, int32_t* range_flag, int
 // A transition on lane lp.on (step_lanes.hpp decided that, and what it waits for): the act and the observation forward of
 // rl4rs_env_step_discrete, the same launches with the same arguments but for the stream, the state-row set, the active list /
 // counter pair, the scorer's scratch set and the head's output pointer.  lp.reward: the folded reward step of after_act,
-// launch for launch - the act, the complete rows, the forward of n_complete rows per env on the scorer's first scratch set (lane 0)
-// with the observation rows into the lane's buffer, the reward into the lane's reward block.
+// launch for launch - the act, the complete rows, the forward of n_complete rows per env on the scratch set of its lane (lane 0, set 0;
+// lane 1, set 1 beside a replay-ahead forward) with the observation rows into the lane's buffer, the reward into the lane's
+// reward block; its AUGRU launch waits for the other lane's `done`.
 int lane_transition(rl4rs_stepper* s, const LanePlan& lp, const LaneState& before, int cur, RowRefineArgs* rf, const int32_t* actions_dev, float* obs_dev,
                     double* reward_dev, void* stream) {
     hipStream_t home = (hipStream_t)stream;
@@ -374,8 +380,8 @@ int lane_transition(rl4rs_stepper* s, const LanePlan& lp, const LaneState& befor
         if ((rc = rl4rs::env_build_complete_rows_lane(s->env, n, l.st)) ||
             (rc = rl4rs_dien_set_obs_last(s->dien, l.obs)) ||
             (rc = rl4rs_dien_set_row_partition(s->dien, s->part_rep[s->part_cur], s->part_active, s->part_cnt, B)) ||
-            (rc = dien_forward_lane_full(s->dien, 0, B * n, n, s->c_dense, s->c_cat, s->slots, nullptr, s->probs, l.st, stream, nullptr,
-                                         s->lane[1].done)) ||      // (lane_reward_eligible: the transition in flight is lane 1's)
+            (rc = dien_forward_lane_full(s->dien, lane_reward_set(lp.on), B * n, n, s->c_dense, s->c_cat, s->slots, nullptr, s->probs, l.st, stream,
+                                         nullptr, s->lane[lp.on ^ 1].done)) ||      // (what is in flight beside it is the other lane's)
             (rc = rl4rs::env_reward_split_lane(s->env, s->probs, nullptr, l.reward, l.st))) {
             (void)hipEventRecord(l.done, l.st);
             return rc;
@@ -418,6 +424,15 @@ int ensure_ahead(rl4rs_stepper* s) {
     s->ah_active = s->ah_rep + B;
     s->ah_cnt = s->ah_active + B;
     return RL4RS_OK;
+}
+// ... and, once, the scorer's second scratch set at the reward forward's size.  No memory for it: the reward step stays
+// where it was, for good; replay-ahead and every transition go on as without it
+void ensure_beside(rl4rs_stepper* s) {
+    // (only where the reward step is ONE forward - fold_obs: where it is not it joins, and nothing would ever run on the larger set)
+    if (!s->reward_beside || s->beside_tried || !s->lanes_made || !fold_obs(s)) return;
+    s->beside_tried = true;
+    if (dien_reserve_lane_scratch(s->dien, s->cfg.batch_size * s->n_complete) == RL4RS_OK) s->beside_ready = true;
+    else (void)hipGetLastError();
 }
 
 int ahead_handout(rl4rs_stepper* s, int k, float* obs_dev, double* reward_dev, hipStream_t home) {
@@ -598,7 +613,7 @@ int attach(rl4rs_env* env, rl4rs_dien* dien, rl4rs_simnet* simnet, const int32_t
             rl4rs_stepper_destroy(s);
             return rc;
         }
-        s->overlap = s->reset_lane = s->reward_lane = s->lanes_made;
+        s->overlap = s->reset_lane = s->reward_lane = s->reward_beside = s->lanes_made;
     }
     s->act_tail = true;
     s->replay_ahead = dien != nullptr ? 1 : 0;
@@ -703,10 +718,14 @@ int rl4rs_env_step_discrete(rl4rs_stepper* s, const int32_t* actions_dev, float*
             }
             a.lanes = lane_room(c);
             // (no memory for the forward's buffers: this stepper goes on without replay-ahead, every transition as it was)
-            if (!s->ahead.active && ahead_trigger(a) && ensure_ahead(s) != RL4RS_OK) {
-                (void)hipGetLastError();
-                s->replay_ahead = 0;
-                a.on = false;
+            if (!s->ahead.active && ahead_trigger(a)) {
+                if (ensure_ahead(s) != RL4RS_OK) {
+                    (void)hipGetLastError();
+                    s->replay_ahead = 0;
+                    a.on = false;
+                } else if (a.lanes) {
+                    ensure_beside(s);
+                }
             }
             const AheadState was = s->ahead;
             bool dropped = false;
@@ -716,7 +735,8 @@ int rl4rs_env_step_discrete(rl4rs_stepper* s, const int32_t* actions_dev, float*
             if (step == AheadStep::Next) return ahead_next(s, was, cur, refine ? &rf : nullptr, actions_dev, obs_dev, reward_dev, stream);
         }
         const LaneState before = s->lstate;
-        const LanePlan lp = lane_decide(s->lstate, c);
+        // (a folded reward step behind a group forward takes lane 1 and the scorer's second set; else lane_decide alone)
+        const LanePlan lp = lane_decide_beside(s->lstate, c, s->reward_beside && s->beside_ready && dien_lane_path(s->dien, s->cfg.batch_size * s->n_complete));
         if (lp.lane) return lane_transition(s, lp, before, cur, &rf, actions_dev, obs_dev, reward_dev, stream);
         // (lane_decide has joined the state; the waits go to the caller's stream)
         if (lp.join) {
@@ -781,6 +801,21 @@ int rl4rs_stepper_set_reset_lane(rl4rs_stepper* s, int32_t on) {
 int rl4rs_stepper_set_reward_lane(rl4rs_stepper* s, int32_t on) {
     RL4RS_REQUIRE(s, "stepper_set_reward_lane: null argument");
     s->reward_lane = on != 0 && s->lanes_made;
+    return RL4RS_OK;
+}
+
+// off - a folded reward step behind a replay-ahead forward runs on lane 0 and the first scratch set, behind that forward,
+// as it did; the second set is then not grown (one that has been grown stays: a forward may be reading it)
+int rl4rs_stepper_set_reward_beside(rl4rs_stepper* s, int32_t on) {
+    RL4RS_REQUIRE(s, "stepper_set_reward_beside: null argument");
+    s->reward_beside = on != 0 && s->lanes_made;
+    return RL4RS_OK;
+}
+
+int rl4rs_stepper_reward_beside_stats(const rl4rs_stepper* s, int64_t* ran, int64_t* scratch_bytes) {
+    RL4RS_REQUIRE(s, "stepper_reward_beside_stats: null argument");
+    if (ran) *ran = s->lstate.ran_beside;
+    if (scratch_bytes) *scratch_bytes = s->dien ? dien_lane_scratch_bytes(s->dien) : 0;
     return RL4RS_OK;
 }
 

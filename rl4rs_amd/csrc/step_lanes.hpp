@@ -49,6 +49,10 @@ struct LaneState {
     int64_t ran[2];        // lane transitions issued on each lane, joins carried out (rl4rs_stepper_lane_stats)
     int64_t joins;
     int64_t ran_reset, ran_reward;   // reset forwards and reward steps issued on a lane (rl4rs_stepper_lane_stats_ex): not part of ran[]
+    // DESIGN 42 - the forward last issued on lane 0 is a replay-ahead group forward and nothing has joined since (set by
+    // lane_ahead_start, dropped by lane_join and by whatever lane_decide_beside is asked next)
+    bool group0;
+    int64_t ran_beside;    // reward steps issued on lane 1 beside that forward (rl4rs_stepper_reward_beside_stats): part of ran_reward
 };
 
 struct LanePlan {
@@ -70,6 +74,7 @@ inline bool lane_join(LaneState& s) {
     if (any) s.joins += 1;
     s.in_flight = false;
     s.used[0] = s.used[1] = false;
+    s.group0 = false;
     return any;
 }
 
@@ -245,6 +250,7 @@ inline LanePlan lane_ahead_start(LaneState& s) {
     s.used[0] = true;
     s.last = 0;
     s.next = 1;
+    s.group0 = true;
     return p;
 }
 // a later act: lane 1, behind lane 0's `act_done` (recorded behind the row builder: the act rewrites what it read).  It leaves the
@@ -260,5 +266,32 @@ inline LanePlan lane_ahead_next(LaneState& s) {
     s.next = 0;
     return p;
 }
+
+// ---- the reward step beside the group forward.  Behind a replay-ahead forward lane 0 holds that forward until it ends,
+// and a folded reward step placed there (lane_decide) starts its act, its row builder and its front kernels only then - although none
+// of them needs anything of the forward.  With a second scratch set of full size (`on`: the switch, and the set was reserved) the
+// reward step takes LANE 1 and SET 1 instead: in stream order behind the later acts, so no act is waited for across lanes; its AUGRU
+// launch still waits for lane 0's `done` (step.hip).  Claimed only where lane_decide would have put the reward step on lane 0 AND the
+// forward in flight there is a group forward nothing has joined since; every other call is answered by lane_decide alone.
+// Whatever the answer, the transition asked about is either a join or the next thing issued on the lanes: the mark goes.
+inline bool lane_beside_eligible(const LaneState& s, const LaneCall& c, bool on) { return on && s.group0 && lane_reward_eligible(s, c); }
+inline LanePlan lane_decide_beside(LaneState& s, const LaneCall& c, bool on) {
+    const bool beside = lane_beside_eligible(s, c, on);
+    s.group0 = false;
+    if (!beside) return lane_decide(s, c);
+    LanePlan p = {};
+    p.lane = p.reward = true;
+    p.on = 1;
+    p.wait_entry = !c.own_row;
+    p.wait_handout = !p.wait_entry && s.used[1];
+    s.used[1] = true;
+    s.last = 1;
+    s.ran_reward += 1;
+    s.ran_beside += 1;
+    s.next = 0;
+    return p;
+}
+// the scratch set and the event in front of the AUGRU launch of a reward step on lane `on`: the set of its lane, the other lane's `done`
+inline int lane_reward_set(int on) { return on; }
 
 }  // namespace rl4rs

@@ -351,7 +351,7 @@ class DeviceStepper(object):
     (rl4rs_env_step_discrete / rl4rs_env_step_conti = RecSimBase._step, base.py:157-170)."""
 
     def __init__(self, env, net, slots, act_tail=True, obs_fold=True, partition_carry=True, step_overlap=True, reset_lane=True,
-                 reward_lane=True, replay_ahead=True):
+                 reward_lane=True, replay_ahead=True, reward_beside=True):
         """``act_tail=False`` (config['no_act_tail'] / RL4RS_NO_ACT_TAIL=1): rl4rs_env_step_discrete launches k_step_tail as it
         did and leaves no next-step logged actions (rl4rs_stepper_set_act_tail).  ``obs_fold=False``
         (config['no_reward_obs_fold'] / RL4RS_NO_REWARD_OBS_FOLD=1): a reward step runs its observation forward and then the
@@ -363,7 +363,10 @@ class DeviceStepper(object):
         ``reward_lane=False`` (config['no_reward_lane'] / RL4RS_NO_REWARD_LANE=1): every reward step joins.
         ``replay_ahead=False`` (config['no_replay_ahead'] / RL4RS_NO_REPLAY_AHEAD=1): no transition scores the rows of the ones behind
         it (rl4rs_stepper_set_replay_ahead); ``'pinned'`` (config['replay_ahead'] = 'pinned' / RL4RS_REPLAY_AHEAD=pinned):
-        also where the 64-row form of the AUGRU launch is pinned and not chosen by the automatic rule (small batches)."""
+        also where the 64-row form of the AUGRU launch is pinned and not chosen by the automatic rule (small batches).
+        ``reward_beside=False`` (config['no_reward_beside'] / RL4RS_NO_REWARD_BESIDE=1): the reward step behind a replay-ahead forward
+        runs on lane 0 behind it and the scorer's second scratch set stays observation-sized (rl4rs_stepper_set_reward_beside,
+        DESIGN 42)."""
         self.lib = _lib.load()
         self.env, self.net, self.slots = env, net, slots          # keep the handles and the slot table alive
         assert slots.dtype == torch.int32 and slots.is_contiguous() and slots.shape[1] == env.B
@@ -386,6 +389,8 @@ class DeviceStepper(object):
             check(self.lib.rl4rs_stepper_set_reward_lane(self.h, 0))
         if replay_ahead is not True:         # False: off; 'pinned': also where the 64-row AUGRU form is pinned, not chosen
             check(self.lib.rl4rs_stepper_set_replay_ahead(self.h, 2 if replay_ahead == 'pinned' else 0))
+        if not reward_beside:
+            check(self.lib.rl4rs_stepper_set_reward_beside(self.h, 0))
         self.reset_lane = bool(step_overlap and reset_lane)
         self._distinct_hint = None
         self.B, self.A, self.E, self.W, self.device = env.B, env.A, env.E, env.W, env.device
@@ -429,6 +434,13 @@ class DeviceStepper(object):
         a, b, d = C.c_int64(0), C.c_int64(0), C.c_int64(0)
         check(self.lib.rl4rs_stepper_replay_stats(self.h, C.byref(a), C.byref(b), C.byref(d)))
         return int(a.value), int(b.value), int(d.value)
+
+    def reward_beside_stats(self):
+        """(reward steps run on lane 1 beside a replay-ahead forward, bytes of the scorer's second scratch set) since the stepper was
+        created (rl4rs_stepper_reward_beside_stats)."""
+        a, b = C.c_int64(0), C.c_int64(0)
+        check(self.lib.rl4rs_stepper_reward_beside_stats(self.h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
 
     def observe(self):
         """rl4rs_stepper_observe: the observation behind a reset as a lane transition -> obs f32 [B, 256], or None where the lane

@@ -635,6 +635,8 @@ class SlateRecEnv(RecSimBase):
             self._stepper = D.DeviceStepper(env, net, slots, act_tail=not no_tail, obs_fold=not no_fold, partition_carry=not no_carry,
                                             step_overlap=not no_overlap, reset_lane=self._lane_switch('reset_lane'),
                                             reward_lane=self._lane_switch('reward_lane'),
+                                            # config['no_reward_beside'] (RL4RS_NO_REWARD_BESIDE=1): the reward step behind the group forward
+                                            reward_beside=self._lane_switch('reward_beside'),
                                             # config['no_replay_ahead'] (RL4RS_NO_REPLAY_AHEAD=1): every replay transition scores its own row
                                             replay_ahead=self._lane_switch('replay_ahead') and (
                                                 'pinned' if self.config.get('replay_ahead', os.environ.get('RL4RS_REPLAY_AHEAD', '')) == 'pinned' else True))

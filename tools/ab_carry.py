@@ -12,6 +12,7 @@ Prints one line `ARM <name> <workload> <ms per episode-batch>` per workload.
     python tools/ab_carry.py --name serial --no-step-overlap            (r26: consecutive transitions on the caller's stream)
     python tools/ab_carry.py --name noreset --no-reset-lane             (r27: each half of DESIGN 39 off alone; --no-reward-lane)
     python tools/ab_carry.py --name noahead --no-replay-ahead           (r28: every replay transition scores its own row)
+    python tools/ab_carry.py --name nobeside --no-reward-beside         (r29: the reward step behind the group forward, on lane 0)
     python tools/ab_carry.py --name parent --tree tools/_ab/parent      (another tree with its own library and Python)"""
 import argparse
 import os
@@ -28,6 +29,7 @@ def main():
     ap.add_argument('--no-reset-lane', action='store_true', help="config['no_reset_lane'] (profiles/r27_ab.md)")
     ap.add_argument('--no-reward-lane', action='store_true', help="config['no_reward_lane'] (profiles/r27_ab.md)")
     ap.add_argument('--no-replay-ahead', action='store_true', help="config['no_replay_ahead'] (profiles/r28_ab.md)")
+    ap.add_argument('--no-reward-beside', action='store_true', help="config['no_reward_beside'] (profiles/r29_ab.md)")
     ap.add_argument('--kernels', default=None, help="config['scorer_kernels'] (e.g. no_lazy_expand: the `off` arm of profiles/r19_lazy_ab.md)")
     a = ap.parse_args()
     sys.path.insert(0, os.path.abspath(a.tree))
@@ -51,6 +53,8 @@ def main():
             cfg['no_reward_lane'] = True
         if a.no_replay_ahead:
             cfg['no_replay_ahead'] = True
+        if a.no_reward_beside:
+            cfg['no_reward_beside'] = True
         if a.kernels is not None:
             cfg['scorer_kernels'] = a.kernels
         env = bench.build_env(cfg, False)
