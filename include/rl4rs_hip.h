@@ -825,7 +825,11 @@ enum { RL4RS_REPLAY_BUF_OBS = 0, RL4RS_REPLAY_BUF_MASK = 1, RL4RS_REPLAY_BUF_ACT
 int rl4rs_replay_buffer(rl4rs_replay* h, int32_t which, void** dev_out, int64_t* count_out);
 /* Append one rollout (T * B rows in row order t * B + b) from device pointers, no host round trip: obs float32, mask words,
  * actions int32, rewards float64 (what the env returns; stored as float32).  done = (t == T - 1).  New rows get priority
- * max_priority ^ alpha; max_priority starts at 1.0 and is the largest |td| + 1e-6 ever set. */
+ * max_priority ^ alpha; max_priority starts at 1.0 and is the largest |td| + 1e-6 ever set.
+ * The obs column is, by contract, OPAQUE 32-bit words: push (a device-to-device copy) and sample (a word gather, on its 16-byte
+ * path and on its scalar path alike) move them and do no arithmetic on them.  A ring created with obs_dim = REC therefore keeps
+ * packed raw-state records (rl4rs_rawstate_pack) bit for bit, although their int32 ids read as float32 are denormals (small ids)
+ * or NaNs (negative ids). */
 int rl4rs_replay_push(rl4rs_replay* h, const float* obs_dev, const uint32_t* mask_bits_dev, const int32_t* action_dev,
                       const double* reward_dev, void* stream);
 /* Draw M rows and gather them into contiguous minibatch buffers: obs / next obs float32 [M, obs_dim], next mask words [M, W],
@@ -1047,6 +1051,66 @@ int rl4rs_rawtrain_loss_grad(rl4rs_rawtrain* pol, int32_t algo, int32_t N, const
                              float clip, float vf_clip, float kl_coeff, float* stats_dev, void* stream);
 int rl4rs_rawtrain_adam_step(rl4rs_rawtrain* pol, float lr, float beta1, float beta2, float eps, float grad_clip,
                              void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * On-device raw-state DQN: script/modelfree_train.py:55-56,63-66,106-133 (algo "DQN_rawstate": the DQN settings above on
+ * mask_model_rawstate, rllib_mask_model.py:67-115 over rllib_rawstate_model.py:25-86).  The Q values are the masked logits of the
+ * rl4rs_rawtrain net; its value head takes no part.  RLlib parity is unpinned as for DQN.  Out of scope: RAINBOW_rawstate, the
+ * continuous model_rawstate learners (TD3 / DDPG / *_conti), PG / IMPALA on the raw handle.
+ *
+ * Packed raw-state record: one observation row as REC 32-bit words
+ *   [ dense: Dn float32 | cat: Cn int32 | seq_0: L int32 | ... | seq_{S-1}: L int32 | zero pad to a multiple of 4 words ]
+ * (Dn = dense_feature_num, Cn = category_feature_num, L = maxlen, S = seq_num; 432 + 21 + 2 * 64 = 581 -> REC 584 at the default
+ * configuration).  Dense comes first, so the dense part of a batch of records is a GEMM operand with lda = REC, 16-byte aligned.
+ * Ids are stored as they come, not clamped: every forward clamps them to [0, category_hash_size) where it uses them.  The
+ * buffer is typed float* only because the replay ring's obs column is; rl4rs_replay_* with obs_dim = REC stores such records
+ * unchanged (see rl4rs_replay_push). */
+int32_t rl4rs_rawstate_record_words(const rl4rs_rawpolicy_cfg* cfg);      /* REC; 0 for a NULL / impossible configuration */
+/* rec_out_dev [N, REC] from cat_dev int32 [N, Cn], dense_dev float32 [N, Dn], seq_dev: S device pointers of int32 [N, L].  One
+ * launch; only cfg's five layout fields are read. */
+int rl4rs_rawstate_pack(const rl4rs_rawpolicy_cfg* cfg, int32_t N, const int32_t* cat_dev, const float* dense_dev,
+                        const int32_t* const* seq_dev, float* rec_out_dev, void* stream);
+/* rl4rs_policy_dqn_loss_grad with the raw-state model as the network: the same a*, y (a select: nothing of a terminal row's
+ * successor record - NaN dense values, ids out of range - reaches any output), no bootstrap from a successor that allows no action,
+ * td, Huber loss (delta 1), loss = mean(w * huber), td_dev [N], next_action_dev [N] (optional: a*, -1 on terminal rows) and
+ * stats_dev float[4] (optional) = sums of {w * huber, Q(s)[a], y, |td|}.
+ *   rec_dev / next_rec_dev   float [N, REC]: the records of s and s', read in place (no unpacked copy is made)
+ *   target_params_dev        the target net: a device buffer in the handle's flat layout (rl4rs_rawtrain_params gives the count),
+ *                            with its own copy of the two embedding tables
+ * The gradient goes into the handle's flat gradient buffer, as in rl4rs_rawtrain_loss_grad: the value-head column and every
+ * action column nobody took are exactly 0, and so is every table row no id of the minibatch touches.  N <= max_rows; the first
+ * call allocates the scratch of the two s' forwards on the handle.
+ * Three forwards (s online, s' target, s' online when double_q), each one pooling launch for all S + 1 id fields and the GEMMs
+ * with lda = REC; one wave per row then picks a*, takes Q(s)[a] and Q_target(s')[a*] as single-column products over the 256-wide
+ * context and writes d loss / d (context pre-activation) = g * head_w[:, a] * ELU'(context) directly - no [N, A + 1] head gradient,
+ * no GEMM back through the head.  The head's gradient is gathered column by column; below the context layer the backward is
+ * rl4rs_rawtrain_loss_grad's, with one embedding scatter launch reading the ids from the records.
+ * Reproducibility: td, stats, a* and the gradients of the eight dense variables are bit-identical from run to run (fixed
+ * summation orders); the embedding scatter keeps the handle's float atomics, so the two tables' gradients are not. */
+int rl4rs_rawtrain_dqn_loss_grad(rl4rs_rawtrain* pol, const float* target_params_dev, int32_t N, const float* rec_dev,
+                                 const int32_t* actions_dev, const float* rewards_dev, const int32_t* dones_dev,
+                                 const float* next_rec_dev, const uint32_t* next_mask_bits_dev, const float* weights_dev,
+                                 float gamma, int32_t double_q, float* td_dev, int32_t* next_action_dev, float* stats_dev,
+                                 void* stream);
+/* Greedy action: the forward of rl4rs_rawtrain_act, then the first maximum of the masked Q row; q_dev (optional) receives the
+ * masked row [N, action_size].  A row that allows nothing returns action 0. */
+int rl4rs_rawtrain_greedy(rl4rs_rawtrain* pol, int32_t N, const int32_t* cat_dev, const float* dense_dev,
+                          const int32_t* const* seq_dev, const uint32_t* mask_bits_dev, int32_t* actions_dev, float* q_dev,
+                          void* stream);
+/* TF-form Adam on the handle's gradient with tf.clip_by_norm applied to EACH of the ten variables of the flat layout by its own
+ * norm (RLlib DQN's minimize_and_clip, grad_clip 40); var_clip <= 0: no clipping, bit-identical to rl4rs_rawtrain_adam_step with
+ * grad_clip 0.  The ten sums of squares are one two-stage pass: tiles of 16384 elements over as many workgroups (a tile that
+ * straddles variable boundaries gives one partial sum per variable it meets), then the tiles of a variable added in tile order -
+ * bit-identical from run to run for the same gradient buffer.  (rl4rs_rawtrain_adam_step's global-norm clip still reduces in one
+ * workgroup.) */
+int rl4rs_rawtrain_adam_step_clip_by_var(rl4rs_rawtrain* pol, float lr, float beta1, float beta2, float eps, float var_clip,
+                                         void* stream);
+/* Measurement aid (tools/rawdqn_rate.py): with profiling on, rl4rs_rawtrain_dqn_loss_grad and ..._adam_step_clip_by_var record
+ * events at their stage boundaries; rl4rs_rawtrain_profile waits for the last call of each and returns float[5] milliseconds:
+ * the three forwards, the row kernel, the backward (head gradient, chain, statistics), the sums of squares, the Adam kernel.
+ * Both calls must have run since profiling was switched on. */
+int rl4rs_rawtrain_set_profiling(rl4rs_rawtrain* pol, int32_t on);
+int rl4rs_rawtrain_profile(rl4rs_rawtrain* pol, float* ms_out);
 
 /* Supervised training of the 'dnn' / 'widedeep' / 'lstm' simulators (rl4rs/nets/dnn.py, widedeep.py, lstm.py) on the device: what
  * script/supervised_train.py:37-42 does with model.compile(loss='binary_crossentropy', optimizer='adam') + model.fit -

@@ -279,6 +279,13 @@ SIGNATURES = {
     'rl4rs_rawtrain_loss_grad': (_I, [_P, _I32, _I32, _P, _P, C.POINTER(_P), _P, _P, _P, _P, _P, _P, _P, C.c_float, C.c_float,
                                       C.c_float, C.c_float, C.c_float, _P, _P]),
     'rl4rs_rawtrain_adam_step': (_I, [_P, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _P]),
+    'rl4rs_rawstate_record_words': (_I32, [C.POINTER(RawPolicyCfg)]),
+    'rl4rs_rawstate_pack': (_I, [C.POINTER(RawPolicyCfg), _I32, _P, _P, C.POINTER(_P), _P, _P]),
+    'rl4rs_rawtrain_dqn_loss_grad': (_I, [_P, _P, _I32, _P, _P, _P, _P, _P, _P, _P, C.c_float, _I32, _P, _P, _P, _P]),
+    'rl4rs_rawtrain_greedy': (_I, [_P, _I32, _P, _P, C.POINTER(_P), _P, _P, _P, _P]),
+    'rl4rs_rawtrain_adam_step_clip_by_var': (_I, [_P, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _P]),
+    'rl4rs_rawtrain_set_profiling': (_I, [_P, _I32]),
+    'rl4rs_rawtrain_profile': (_I, [_P, _P]),
     'rl4rs_policy_ppo_epoch': (_I, [_P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P] + [C.c_float] * 10 + [_P, _P, _P]),
     'rl4rs_dien_set_row_order': (_I, [_P, _P, _I32]),
     'rl4rs_dien_set_obs_last': (_I, [_P, _P]),

@@ -1596,6 +1596,7 @@ int rl4rs_policy_set_option(rl4rs_policy* p, int32_t which, int32_t value) {
 #include "scorers.hpp"
 #include "contirl.hpp"
 #include "dqn.hpp"
+#include "rawdqn.hpp"
 #include "td3.hpp"
 #include "rainbow.hpp"
 #include "vtrace.hpp"

@@ -53,26 +53,108 @@ struct rl4rs_rawtrain {
     float* sumsq;
     float *feat, *h1, *ctx, *ext, *dOut, *d_ctx, *d_feat, *d_h1;
     float4* terms;
+    // DQN on the raw handle (rawdqn.hpp), allocated by the first call that needs them: activations of the two s' forwards, the
+    // per-row d loss / d Q, the per-tile sums of squares of the per-variable clip and its ten norms^2
+    float *dq_feat = nullptr, *dq_h1 = nullptr, *dq_ctx_t = nullptr, *dq_ctx_n = nullptr, *dq_g = nullptr;
+    float *vs_part = nullptr, *vs_sumsq = nullptr;
+    // rl4rs_rawtrain_set_profiling: events at the stage boundaries of the last dqn_loss_grad ([0..3]) and clipped Adam step ([4..6])
+    hipEvent_t prof_ev[7] = {};
+    bool prof = false;
     std::vector<void*> owned;
 };
 
 namespace {
 
+// the four GEMMs of a forward on the parameters at P: dense tower (rows of `dense` ldd floats apart) into feat's middle block,
+// context layer, and - ext != null - the first n_out head columns.  The pooled embeddings are in feat already.
+int rawtrain_layers(rl4rs_rawtrain* p, const float* P, int N, const float* dense, int64_t ldd, float* feat, float* h1, float* ctx, float* ext,
+                    int n_out, hipStream_t st) {
+    const int E = p->c.emb_size, U = p->c.hidden_units, S = p->c.seq_num, Dn = p->c.dense_feature_num, F = p->F, AE = p->d.AE;
+    const int64_t* o = p->off;
+    int rc;
+    if ((rc = launch_gemm_f32(dense, ldd, P + o[RT_DW1], U, P + o[RT_DB1], h1, U, N, U, Dn, 1, st))) return rc;
+    if ((rc = launch_gemm_f32(h1, U, P + o[RT_DW2], U, P + o[RT_DB2], feat + S * E, F, N, U, U, 1, st))) return rc;
+    if ((rc = launch_gemm_f32(feat, F, P + o[RT_CTX_W], 256, P + o[RT_CTX_B], ctx, 256, N, 256, F, 1, st))) return rc;
+    if (!ext) return RL4RS_OK;
+    return launch_gemm_f32(ctx, 256, P + o[RT_HEAD_W], AE, P + o[RT_HEAD_B], ext, AE, N, n_out, 256, 0, st);
+}
+
 int rawtrain_forward(rl4rs_rawtrain* p, int N, const int32_t* cat, const float* dense, const int32_t* const* seq, hipStream_t st) {
     const int E = p->c.emb_size, U = p->c.hidden_units, H = p->c.category_hash_size, S = p->c.seq_num, Dn = p->c.dense_feature_num;
-    const int F = p->F, L = p->c.maxlen, Cn = p->c.category_feature_num, AE = p->d.AE;
+    const int F = p->F, L = p->c.maxlen, Cn = p->c.category_feature_num;
     const float* P = p->opt.params;
     const int64_t* o = p->off;
     const dim3 g4((N + 3) / 4), b256(256);
-    int rc;
     for (int s = 0; s < S; ++s)
         hipLaunchKernelGGL(k_emb_mean, g4, b256, 0, st, seq[s], N, L, H, E, P + o[RT_SEQ_EMB], p->feat, (int64_t)F, s * E);
     hipLaunchKernelGGL(k_emb_mean, g4, b256, 0, st, cat, N, Cn, H, E, P + o[RT_CAT_EMB], p->feat, (int64_t)F, S * E + U);
     RL4RS_LAUNCH_CHECK();
-    if ((rc = launch_gemm_f32(dense, Dn, P + o[RT_DW1], U, P + o[RT_DB1], p->h1, U, N, U, Dn, 1, st))) return rc;
-    if ((rc = launch_gemm_f32(p->h1, U, P + o[RT_DW2], U, P + o[RT_DB2], p->feat + S * E, F, N, U, U, 1, st))) return rc;
-    if ((rc = launch_gemm_f32(p->feat, F, P + o[RT_CTX_W], 256, P + o[RT_CTX_B], p->ctx, 256, N, 256, F, 1, st))) return rc;
-    return launch_gemm_f32(p->ctx, 256, P + o[RT_HEAD_W], AE, P + o[RT_HEAD_B], p->ext, AE, N, AE, 256, 0, st);
+    return rawtrain_layers(p, P, N, dense, Dn, p->feat, p->h1, p->ctx, p->ext, p->d.AE, st);
+}
+
+// Packed raw-state record (include/rl4rs_hip.h): [ dense Dn | cat Cn | seq_0 L | ... | seq_{S-1} L | zero pad ] 32-bit words
+struct RecLayout { int Dn, Cn, L, S, REC; };
+inline RecLayout rec_layout(const rl4rs_rawpolicy_cfg& c) {
+    const int w = c.dense_feature_num + c.category_feature_num + c.seq_num * c.maxlen;
+    return {c.dense_feature_num, c.category_feature_num, c.maxlen, c.seq_num, (w + 3) / 4 * 4};
+}
+
+// gradient of the S + 1 mean-poolings of a forward in ONE launch, ids read from the records (grid.y = field: S sequences, then
+// the categories); the arithmetic of k_emb_mean_bwd (float atomics)
+__global__ __launch_bounds__(256) void k_rec_emb_mean_bwd(const float* __restrict__ rec, RecLayout r, int n, int H, int E, int U,
+                                                          const float* __restrict__ d_feat, int64_t ld, float* __restrict__ g_seq,
+                                                          float* __restrict__ g_cat) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + wave, f = blockIdx.y;
+    if (row >= n) return;
+    const bool is_cat = f == r.S;
+    const int len = is_cat ? r.Cn : r.L;
+    const int32_t* ids = reinterpret_cast<const int32_t*>(rec + (size_t)row * r.REC) + (is_cat ? r.Dn : r.Dn + r.Cn + f * r.L);
+    const float* d = d_feat + (size_t)row * ld + (is_cat ? r.S * E + U : f * E);
+    float* g_table = is_cat ? g_cat : g_seq;
+    const float inv = 1.0f / (float)len;
+    for (int j = 0; j < len; ++j) {
+        const int id = min(max(ids[j], 0), H - 1);
+        for (int k = lane; k < E; k += 64) atomicAdd(&g_table[(size_t)id * E + k], d[k] * inv);
+    }
+}
+
+// Backward from d_ctx (= d loss / d pre-activation of the context layer, in p->d_ctx) down to the tables, with the activations of
+// the last forward in p->feat / h1 / ctx.  The ids come from the unpacked arrays (cat / seq: one scatter launch per field) or -
+// rec != null - from the records in one launch; dense rows are ldd floats apart.
+int rawtrain_backward_from_ctx(rl4rs_rawtrain* p, int N, const float* dense, int ldd, const int32_t* cat, const int32_t* const* seq,
+                               const float* rec, hipStream_t st) {
+    const int E = p->c.emb_size, U = p->c.hidden_units, H = p->c.category_hash_size, S = p->c.seq_num, Dn = p->c.dense_feature_num;
+    const int F = p->F, L = p->c.maxlen, Cn = p->c.category_feature_num;
+    const float* P = p->opt.params;
+    float* G = p->opt.grad;
+    const int64_t* o = p->off;
+    const dim3 g4((N + 3) / 4), b256(256);
+    auto ew = [](int n) { return dim3((n + 255) / 256); };
+    int rc;
+    st_tn(p->cx, st, p->feat, F, F, p->d_ctx, 256, 256, N, G + o[RT_CTX_W]);
+    st_cs(p->cx, st, p->d_ctx, 256, 256, N, G + o[RT_CTX_B]);
+    if ((rc = st_back(p->cx, st, p->d_ctx, 256, 256, P + o[RT_CTX_W], 256, F, p->d_feat, F, N))) return rc;
+    RL4RS_HIP_TRY(hipMemsetAsync(G + o[RT_CAT_EMB], 0, (size_t)H * E * 4, st));
+    RL4RS_HIP_TRY(hipMemsetAsync(G + o[RT_SEQ_EMB], 0, (size_t)H * E * 4, st));
+    if (rec) {
+        hipLaunchKernelGGL(k_rec_emb_mean_bwd, dim3((N + 3) / 4, S + 1), b256, 0, st, rec, rec_layout(p->c), N, H, E, U, p->d_feat, (int64_t)F,
+                           G + o[RT_SEQ_EMB], G + o[RT_CAT_EMB]);
+    } else {
+        for (int s = 0; s < S; ++s)
+            hipLaunchKernelGGL(k_emb_mean_bwd, g4, b256, 0, st, seq[s], N, L, H, E, p->d_feat + s * E, (int64_t)F, G + o[RT_SEQ_EMB]);
+        hipLaunchKernelGGL(k_emb_mean_bwd, g4, b256, 0, st, cat, N, Cn, H, E, p->d_feat + S * E + U, (int64_t)F, G + o[RT_CAT_EMB]);
+    }
+    // dense tower (inference-mode Dropout: RLlib calls the keras base model without the training flag)
+    float* d_tower = p->d_feat + S * E;
+    hipLaunchKernelGGL(k_elu_bwd, ew(N * U), b256, 0, st, d_tower, (int64_t)F, p->feat + S * E, (int64_t)F, (const uint8_t*)nullptr, 0.f, N * U, U);
+    st_tn(p->cx, st, p->h1, U, U, d_tower, F, U, N, G + o[RT_DW2]);
+    st_cs(p->cx, st, d_tower, F, U, N, G + o[RT_DB2]);
+    if ((rc = st_back(p->cx, st, d_tower, F, U, P + o[RT_DW2], U, U, p->d_h1, U, N))) return rc;
+    hipLaunchKernelGGL(k_elu_bwd, ew(N * U), b256, 0, st, p->d_h1, (int64_t)U, p->h1, (int64_t)U, (const uint8_t*)nullptr, 0.f, N * U, U);
+    st_tn(p->cx, st, dense, ldd, Dn, p->d_h1, U, U, N, G + o[RT_DW1]);
+    st_cs(p->cx, st, p->d_h1, U, U, N, G + o[RT_DB1]);
+    return RL4RS_OK;
 }
 
 }  // namespace
@@ -82,6 +164,8 @@ extern "C" {
 int rl4rs_rawtrain_destroy(rl4rs_rawtrain* p) {
     if (!p) return RL4RS_OK;
     for (void* q : p->owned) (void)hipFree(q);
+    for (hipEvent_t e : p->prof_ev)
+        if (e) (void)hipEventDestroy(e);
     delete p;
     return RL4RS_OK;
 }
@@ -191,8 +275,7 @@ int rl4rs_rawtrain_loss_grad(rl4rs_rawtrain* p, int32_t algo, int32_t N, const i
                   "rawtrain_loss_grad: bad argument (N=%d, max_rows=%d)", N, p ? p->c.max_rows : -1);
     RL4RS_REQUIRE(algo == 0 || (algo == 1 && old_logp && old_value && old_logits), "rawtrain_loss_grad: PPO needs old_* inputs");
     hipStream_t st = (hipStream_t)stream;
-    const int E = p->c.emb_size, U = p->c.hidden_units, H = p->c.category_hash_size, S = p->c.seq_num, Dn = p->c.dense_feature_num;
-    const int F = p->F, L = p->c.maxlen, Cn = p->c.category_feature_num, AE = p->d.AE;
+    const int Dn = p->c.dense_feature_num, AE = p->d.AE;
     const float* P = p->opt.params;
     float* G = p->opt.grad;
     const int64_t* o = p->off;
@@ -204,29 +287,13 @@ int rl4rs_rawtrain_loss_grad(rl4rs_rawtrain* p, int32_t algo, int32_t N, const i
     La.actions = actions; La.adv = adv; La.ret = ret; La.old_logp = old_logp; La.old_value = old_value; La.old_logits = old_logits;
     hipLaunchKernelGGL(k_rawpolicy_loss, dim3((N + 3) / 4), dim3(256), (size_t)4 * 2 * AE * 4, st, p->d, N, p->ext, mask_bits, La, p->dOut,
                        p->terms);
-    const dim3 g4((N + 3) / 4), b256(256);
+    const dim3 b256(256);
     auto ew = [](int n) { return dim3((n + 255) / 256); };
     st_tn(p->cx, st, p->ctx, 256, 256, p->dOut, AE, AE, N, G + o[RT_HEAD_W]);
     st_cs(p->cx, st, p->dOut, AE, AE, N, G + o[RT_HEAD_B]);
     if ((rc = st_back(p->cx, st, p->dOut, AE, AE, P + o[RT_HEAD_W], AE, 256, p->d_ctx, 256, N))) return rc;
     hipLaunchKernelGGL(k_elu_bwd, ew(N * 256), b256, 0, st, p->d_ctx, (int64_t)256, p->ctx, (int64_t)256, (const uint8_t*)nullptr, 0.f, N * 256, 256);
-    st_tn(p->cx, st, p->feat, F, F, p->d_ctx, 256, 256, N, G + o[RT_CTX_W]);
-    st_cs(p->cx, st, p->d_ctx, 256, 256, N, G + o[RT_CTX_B]);
-    if ((rc = st_back(p->cx, st, p->d_ctx, 256, 256, P + o[RT_CTX_W], 256, F, p->d_feat, F, N))) return rc;
-    RL4RS_HIP_TRY(hipMemsetAsync(G + o[RT_CAT_EMB], 0, (size_t)H * E * 4, st));
-    RL4RS_HIP_TRY(hipMemsetAsync(G + o[RT_SEQ_EMB], 0, (size_t)H * E * 4, st));
-    for (int s = 0; s < S; ++s)
-        hipLaunchKernelGGL(k_emb_mean_bwd, g4, b256, 0, st, seq[s], N, L, H, E, p->d_feat + s * E, (int64_t)F, G + o[RT_SEQ_EMB]);
-    hipLaunchKernelGGL(k_emb_mean_bwd, g4, b256, 0, st, cat, N, Cn, H, E, p->d_feat + S * E + U, (int64_t)F, G + o[RT_CAT_EMB]);
-    // dense tower (inference-mode Dropout: RLlib calls the keras base model without the training flag)
-    float* d_tower = p->d_feat + S * E;
-    hipLaunchKernelGGL(k_elu_bwd, ew(N * U), b256, 0, st, d_tower, (int64_t)F, p->feat + S * E, (int64_t)F, (const uint8_t*)nullptr, 0.f, N * U, U);
-    st_tn(p->cx, st, p->h1, U, U, d_tower, F, U, N, G + o[RT_DW2]);
-    st_cs(p->cx, st, d_tower, F, U, N, G + o[RT_DB2]);
-    if ((rc = st_back(p->cx, st, d_tower, F, U, P + o[RT_DW2], U, U, p->d_h1, U, N))) return rc;
-    hipLaunchKernelGGL(k_elu_bwd, ew(N * U), b256, 0, st, p->d_h1, (int64_t)U, p->h1, (int64_t)U, (const uint8_t*)nullptr, 0.f, N * U, U);
-    st_tn(p->cx, st, dense, Dn, Dn, p->d_h1, U, U, N, G + o[RT_DW1]);
-    st_cs(p->cx, st, p->d_h1, U, U, N, G + o[RT_DB1]);
+    if ((rc = rawtrain_backward_from_ctx(p, N, dense, Dn, cat, seq, nullptr, st))) return rc;
     if (stats_dev) hipLaunchKernelGGL(k_reduce_terms, dim3(1), dim3(256), 0, st, p->terms, N, stats_dev);
     RL4RS_LAUNCH_CHECK();
     return RL4RS_OK;

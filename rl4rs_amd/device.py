@@ -1301,7 +1301,8 @@ def _alias_f32(ptr, count, device, owner):
 
 
 class DeviceRawTrainer(_FlatNet, DeviceRawPolicy):
-    """rl4rs_rawtrain handle: the raw-state policy with A2C / PPO loss, backward and Adam on the device."""
+    """rl4rs_rawtrain handle: the raw-state policy with A2C / PPO loss, backward and Adam on the device; as a Q network, the
+    (double-)DQN loss on packed raw-state records, the greedy action and the per-variable-clipped Adam step."""
     A2C, PPO = 0, 1
     ORDER = ('cat_emb', 'seq_emb', 'dense_w1', 'dense_b1', 'dense_w2', 'dense_b2', 'ctx_w', 'ctx_b', 'head_w', 'head_b')
     _prefix = 'rl4rs_rawtrain_'         # weights(): head_w = [out_w | value_w], head_b = [out_b | value_b]
@@ -1316,7 +1317,7 @@ class DeviceRawTrainer(_FlatNet, DeviceRawPolicy):
         self.max_rows = int(max_rows)
         E, U = int(config['emb_size']), int(config['hidden_units'])
         H = int(config['category_hash_size'])
-        cfg = _lib.RawPolicyCfg(self.L, E, U, self.Dn, self.Cn, H, self.S, self.A, self.max_rows)
+        cfg = self._cfg = _lib.RawPolicyCfg(self.L, E, U, self.Dn, self.Cn, H, self.S, self.A, self.max_rows)
         w = _lib.RawPolicyWeights()
         keep = []
         for name, _ in _lib.RawPolicyWeights._fields_:
@@ -1373,6 +1374,69 @@ class DeviceRawTrainer(_FlatNet, DeviceRawPolicy):
 
     def adam_step(self, lr=1e-4, beta1=0.9, beta2=0.999, eps=1e-8, grad_clip=0.0):
         check(self.lib.rl4rs_rawtrain_adam_step(self.h, lr, beta1, beta2, eps, grad_clip, _stream()))
+
+    # ---- DQN on the raw handle (rl4rs_rawstate_* / rl4rs_rawtrain_dqn_loss_grad / _greedy / _adam_step_clip_by_var)
+    @property
+    def n_params(self):
+        return self._ptrs()[2]
+
+    @property
+    def record_words(self):
+        """REC: 32-bit words of one packed raw-state record [dense | cat | seq_0 .. | zero pad to a multiple of 4]."""
+        return int(self.lib.rl4rs_rawstate_record_words(C.byref(self._cfg)))
+
+    def pack_records(self, cat, dense, seqs, out=None):
+        """The raw features of N rows as packed records float32 [N, REC] (the ids keep their int32 bit patterns)."""
+        N, sp = self._inputs(cat, dense, seqs, None)
+        REC = self.record_words
+        rec = out if out is not None else torch.empty((N, REC), dtype=torch.float32, device=self.device)
+        assert rec.dtype == torch.float32 and rec.shape == (N, REC) and rec.is_contiguous()
+        check(self.lib.rl4rs_rawstate_pack(C.byref(self._cfg), N, _ptr(cat), _ptr(dense), sp, _ptr(rec), _stream()))
+        return rec
+
+    def dqn_loss_grad(self, target, rec, action, reward, done, next_rec, next_mask=None, weights=None, gamma=1.0, double_q=True,
+                      td_out=None, want_next_action=False):
+        """(Double-)DQN Huber loss on packed records (rl4rs_rawtrain_dqn_loss_grad); ``target``: float32 [n_params] in the flat
+        layout.  The gradient stays in the handle (gradients() / flat_view('grad')).
+        -> (td [N], stats[4] sums of {w * huber, Q(s)[a], y, |td|}, a* [N] or None)."""
+        N, REC = rec.shape[0], self.record_words
+        for t in (target, rec, reward, next_rec) + ((weights,) if weights is not None else ()):
+            assert t.dtype == torch.float32 and t.is_contiguous()
+        assert action.dtype == torch.int32 and done.dtype == torch.int32 and action.is_contiguous() and done.is_contiguous()
+        assert target.numel() == self.n_params and rec.shape == (N, REC) and next_rec.shape == (N, REC)
+        assert action.shape == (N,) and reward.shape == (N,) and done.shape == (N,) and (weights is None or weights.shape == (N,))
+        if next_mask is not None:
+            assert next_mask.dtype == torch.int32 and next_mask.shape == (N, self.W) and next_mask.is_contiguous()
+        td = td_out if td_out is not None else torch.empty(N, dtype=torch.float32, device=self.device)
+        assert td.dtype == torch.float32 and td.shape == (N,) and td.is_contiguous()
+        stats = torch.empty(4, dtype=torch.float32, device=self.device)
+        astar = torch.empty(N, dtype=torch.int32, device=self.device) if want_next_action else None
+        check(self.lib.rl4rs_rawtrain_dqn_loss_grad(self.h, _ptr(target), N, _ptr(rec), _ptr(action), _ptr(reward), _ptr(done),
+                                                    _ptr(next_rec), _ptr(next_mask), _ptr(weights), gamma, 1 if double_q else 0, _ptr(td),
+                                                    _ptr(astar), _ptr(stats), _stream()))
+        return td, stats, astar
+
+    def greedy(self, cat, dense, seqs, mask_bits=None, want_q=False, out=None):
+        """First maximum of the masked Q row (rl4rs_rawtrain_greedy) -> (actions int32 [N], masked Q [N, A] or None)."""
+        N, sp = self._inputs(cat, dense, seqs, mask_bits)
+        a = out if out is not None else torch.empty(N, dtype=torch.int32, device=self.device)
+        assert a.dtype == torch.int32 and a.shape == (N,) and a.is_contiguous()
+        q = torch.empty((N, self.A), dtype=torch.float32, device=self.device) if want_q else None
+        check(self.lib.rl4rs_rawtrain_greedy(self.h, N, _ptr(cat), _ptr(dense), sp, _ptr(mask_bits), _ptr(a), _ptr(q), _stream()))
+        return a, q
+
+    def adam_step_clip_by_var(self, lr=5e-4, beta1=0.9, beta2=0.999, eps=1e-8, var_clip=40.0):
+        """Adam on the handle's gradient with each of the ten variables clipped by its own norm."""
+        check(self.lib.rl4rs_rawtrain_adam_step_clip_by_var(self.h, lr, beta1, beta2, eps, var_clip, _stream()))
+
+    def set_profiling(self, on):
+        check(self.lib.rl4rs_rawtrain_set_profiling(self.h, 1 if on else 0))
+
+    def profile(self):
+        """Event times of the last dqn_loss_grad and adam_step_clip_by_var, microseconds by stage (waits for both)."""
+        ms = (C.c_float * 5)()
+        check(self.lib.rl4rs_rawtrain_profile(self.h, ms))
+        return dict(zip(('forwards', 'rows', 'backward', 'sumsq', 'adam'), [1e3 * float(x) for x in ms]))
 
 
 def gemm_f32(a, w, bias=None, act=0):

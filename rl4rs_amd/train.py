@@ -16,6 +16,9 @@ stepped with the clipped draw.
 target_network_update_freq 200, buffer_size 100000 on the mask model): replay memory, TD loss, per-variable-clipped Adam and
 the target copy all stay on the device (rl4rs_replay_*, rl4rs_policy_dqn_loss_grad).
 
+``RawDQNTrainer`` is that driver's ``DQN_rawstate`` (script/modelfree_train.py:55-56,63-66): ``DQNTrainer``'s loop on the raw-state
+model (``DeviceRawTrainer``), the observations kept in the ring as packed records (rl4rs_rawstate_pack, rl4rs_rawtrain_dqn_loss_grad).
+
 ``RainbowTrainer`` is that driver's RAINBOW (script/modelfree_train.py:50-53,146-178: RLlib DQN with num_atoms 8, dueling, double_q,
 n_step 3 on RLlib's default model): the distributional network has a handle of its own (rl4rs_distq_*), the ring's n-step draw is
 rl4rs_replay_sample_nstep, everything else is ``DQNTrainer``'s loop.
@@ -880,7 +883,7 @@ class _ReplayTrainer(_Evaluated, _Checkpoint):
         self.env, self.seed = env, seed
         self.B, self.T = cfg['batch_size'], cfg['max_steps']
         self.M = _default_minibatch(self.B, self.T, train_batch_size)
-        self.OD = _obs_width(env)
+        self.OD = self._obs_dim(env)
         self.learning_starts, self.updates_per_rollout = int(learning_starts), int(updates_per_rollout)
         self.prioritized, self.beta = bool(prioritized_replay), float(beta)
         self.keep_last_batch, self.last_batch = keep_last_batch, None
@@ -889,6 +892,10 @@ class _ReplayTrainer(_Evaluated, _Checkpoint):
         self._rollouts = 0
         self.timesteps = 0                  # sampled env steps (RLlib's num_steps_sampled)
         self.num_updates = 0
+
+    def _obs_dim(self, env):
+        """Floats of one row of the rollout buffer's and the ring's observation column."""
+        return _obs_width(env)
 
     def _step_mask(self, sl):
         """The packed action mask of the current observation, written into rows ``sl`` of the rollout buffer (None: no mask)."""
@@ -985,7 +992,7 @@ class DQNTrainer(_ReplayTrainer):
                         rew=torch.empty(N, dtype=torch.float64, device=dev))
         self._batch = self.replay.new_batch(self.M)
         self._td = torch.empty(self.M, dtype=torch.float32, device=dev)
-        self.grad = torch.empty(self.policy.n_params, dtype=torch.float32, device=dev)
+        self.grad = self._new_grad()
         self.num_target_updates = 0
         self._last_target_sync = 0
         if rdist.collectives_active():
@@ -1010,6 +1017,13 @@ class DQNTrainer(_ReplayTrainer):
         self.policy = D.DevicePolicy(self.OD, hidden, self.A, max_rows=max(self.M, self.B), seed=init_seed)
         self._logp = torch.empty(self.B, dtype=torch.float32, device=self.policy.device)
         self._val = torch.empty(self.B, dtype=torch.float32, device=self.policy.device)
+
+    def _new_grad(self):
+        """The flat gradient buffer the loss calls fill (None: the network's handle keeps its own)."""
+        return torch.empty(self.policy.n_params, dtype=torch.float32, device=self.device)
+
+    def _adam_step(self, g):
+        self.policy.adam_step_clip_by_var(g, lr=self.lr, eps=self.adam_eps, var_clip=self.grad_clip)
 
     def params(self):
         self._settle()
@@ -1047,7 +1061,7 @@ class DQNTrainer(_ReplayTrainer):
             self.last_batch.update(td=td.clone(), next_action=astar)
         if rdist.collectives_active():
             rdist.allreduce_mean_(g)
-        self.policy.adam_step_clip_by_var(g, lr=self.lr, eps=self.adam_eps, var_clip=self.grad_clip)
+        self._adam_step(g)
         if self.prioritized:
             self.replay.update_priorities(b['idx'], td)
         self.num_updates += 1
@@ -1134,6 +1148,98 @@ class RainbowTrainer(DQNTrainer):
     def _values(self, tok, mean_reward, s):
         """``DQNTrainer``'s and mean_target, the mean of the projected target distribution."""
         return dict(DQNTrainer._values(self, tok, mean_reward, s), mean_target=float(s[2]) / max(tok['rows'], 1))
+
+
+class RawDQNTrainer(DQNTrainer):
+    """``DQNTrainer`` on the raw features - the driver's ``DQN_rawstate`` (script/modelfree_train.py:55-56,63-66,106-133: the DQN
+    settings on mask_model_rawstate) - for an env with config['rawstate_as_obs'] (+ support_rllib_mask, return_tensors), beside
+    ``RawStateTrainer``.  The network is the raw-state encoder of ``DeviceRawTrainer``; its Q values are the masked logits.
+
+    Every step's observation is packed into one record of ``policy.record_words`` 32-bit words ([dense | cat ids | sequence ids],
+    ``rl4rs_rawstate_pack``), so the rollout buffer and the replay ring are ``DQNTrainer``'s with obs_dim = REC; the loss reads the
+    sampled records in place (``rl4rs_rawtrain_dqn_loss_grad``), the gradient stays in the handle, Adam clips each of the ten
+    variables by its own norm, and the target is a torch copy of the flat parameters (both 100000 x 128 tables included: 104 MB at
+    the default configuration).  Arguments and defaults are ``DQNTrainer``'s without ``hidden``; ``weights`` defaults to
+    ``init_rawpolicy_weights(cfg, seed=init_seed)``.  Schedule and statistics are ``DQNTrainer``'s.
+
+    Not here: data-parallel training (the sparse table exchange of ``RawStateTrainer`` is not wired to this learner) and
+    ``save`` / ``restore`` (``_Checkpoint`` covers the flat policy networks only, see ``RawStateTrainer``)."""
+
+    def __init__(self, env, seed=0, init_seed=0, lr=5e-4, gamma=1.0, adam_eps=1e-8, grad_clip=40.0, double_q=True, n_step=1,
+                 buffer_size=100000, target_network_update_freq=200, learning_starts=1000, train_batch_size=None,
+                 prioritized_replay=True, prioritized_replay_alpha=0.6, prioritized_replay_beta=0.4, softq_temperature=1.0,
+                 updates_per_rollout=1, keep_last_batch=False, weights=None):
+        from .nets.rawpolicy import init_rawpolicy_weights
+        cfg = env.config
+        assert cfg.get('return_tensors', False) and cfg.get('rawstate_as_obs', False) and cfg.get('support_rllib_mask', False), \
+            "RawDQNTrainer needs config rawstate_as_obs + support_rllib_mask + return_tensors"
+        if rdist.collectives_active():
+            raise NotImplementedError("RawDQNTrainer is single-process: the sparse exchange of the two embedding tables' gradients "
+                                      "(RawStateTrainer's) is not wired to this learner, and a dense all-reduce of 25.9 M floats per "
+                                      "update is not offered in its place")
+        self._weights = weights if weights is not None else init_rawpolicy_weights(cfg, seed=init_seed)
+        self.S = cfg['seq_num']
+        DQNTrainer.__init__(self, env, seed=seed, init_seed=init_seed, lr=lr, gamma=gamma, adam_eps=adam_eps, grad_clip=grad_clip,
+                            double_q=double_q, n_step=n_step, buffer_size=buffer_size, target_network_update_freq=target_network_update_freq,
+                            learning_starts=learning_starts, train_batch_size=train_batch_size, prioritized_replay=prioritized_replay,
+                            prioritized_replay_alpha=prioritized_replay_alpha, prioritized_replay_beta=prioritized_replay_beta,
+                            softq_temperature=softq_temperature, updates_per_rollout=updates_per_rollout, keep_last_batch=keep_last_batch)
+        del self._weights
+        self._raw = None
+
+    def _obs_dim(self, env):
+        c = env.config
+        return (c['dense_feature_num'] + c['category_feature_num'] + c['seq_num'] * c['maxlen'] + 3) // 4 * 4
+
+    def _make_net(self, hidden, init_seed):
+        self.policy = D.DeviceRawTrainer(self.env.config, self._weights, max_rows=max(self.M, self.B))
+        assert self.policy.record_words == self.OD
+
+    def _new_grad(self):
+        return None                                         # the handle's own flat gradient buffer
+
+    def save(self, path):
+        raise NotImplementedError("RawDQNTrainer has no checkpoints: _Checkpoint covers the trainers of the flat policy networks only "
+                                  "(this one's two embedding tables are 100 MB of parameters, three times that with Adam's moments)")
+
+    restore = save
+
+    def sync_replicas(self, src=0):
+        raise NotImplementedError("RawDQNTrainer is single-process")
+
+    def _episode(self, explore, step0, reset_file=False):
+        """``_ReplayTrainer._episode`` with every step's raw features packed into the observation rows of the rollout buffer."""
+        B, T = self.B, self.T
+        b = self.buf
+        obs = self.env.reset(reset_file=True) if reset_file else self.env.reset()
+        for t in range(T):
+            sl = slice(t * B, (t + 1) * B)
+            mask = self._step_mask(sl)
+            self._raw = (obs['category_feature'], obs['dense_feature'], [q.contiguous() for q in obs['sequence_feature']])
+            self.policy.pack_records(*self._raw, out=b['obs'][sl])
+            a = self._act(explore, sl, mask, t, step0 + t)
+            obs, reward, done, info = self.env.step(a)
+            b['rew'][sl] = reward
+        self._raw = None
+        return b['rew'].view(T, B).sum(dim=0).mean()
+
+    def _act(self, explore, sl, mask, t, step):
+        """SoftQ at temperature 1 (the net's own categorical draw over the masked logits), or the greedy action."""
+        cat, dense, seqs = self._raw
+        if not explore:
+            return self.policy.greedy(cat, dense, seqs, mask, out=self.buf['act'][sl])[0]
+        a = self.policy.act(cat, dense, seqs, mask, seed=self.seed, step=step)[0]
+        self.buf['act'][sl] = a
+        return a
+
+    def _loss_grad(self, b, w):
+        td, stats, astar = self.policy.dqn_loss_grad(self.target, b['obs'], b['action'], b['reward'], b['done'], b['next_obs'], b['next_mask'],
+                                                     weights=w, gamma=self.gamma, double_q=self.double_q, td_out=self._td,
+                                                     want_next_action=self.keep_last_batch)
+        return None, td, stats, astar
+
+    def _adam_step(self, g):
+        self.policy.adam_step_clip_by_var(lr=self.lr, eps=self.adam_eps, var_clip=self.grad_clip)
 
 
 # ---- TD3 / DDPG -----------------------------------------------------------------------------------------------------------------
