@@ -13,7 +13,7 @@ SOURCES = ['env.hip', 'gemm.hip', 'dien.hip', 'augru_x.hip', 'augru_xs.hip', 'po
 # reduction kernels are 1 - 4 % faster with it) - and so does augru_x.hip: k_augru_x<2,4,2> sits at the register limit and spills without it
 # (augru_xs.hip, the same recurrence text beside its shadow plane, is built like augru_x.hip).
 NO_SLP = ('dien.hip', 'gemm.hip')
-HEADERS = ['common.hpp', 'optim.hpp', 'recur_args.hpp', 'augru_x.hpp', 'din_x.hpp', 'row_dedup.hpp', 'row_refine.hpp', 'recur_train.hpp', 'recur8.hpp', 'mfma4.hpp', 'simnet.hpp', 'gather_kernels.hpp', 'simtrain.hpp', 'dientrain.hpp', 'clfmetrics.hpp', 'rawtrain.hpp', 'qlearn.hpp', 'scorers.hpp', 'contirl.hpp', 'amlp_fused.hpp', 'combo.hpp', 'ppo_pass.hpp', 'policy_tile_std.hpp', 'dqn.hpp', 'rawdqn.hpp', 'td3.hpp', 'rainbow.hpp', 'vtrace.hpp', 'gemm_h16_tile.inc', 'augru_x_body.inc', 'din_x_body.inc', 'env_rows_body.inc', 'augru_xs.hpp', 'gemm_h16_defs.hpp', 'cat_attn2_row.hpp', 'dien_plan.hpp', 'step_lanes.hpp', 'exactk_beam.hpp', 'seq2seq_train.hpp', os.path.join('..', '..', 'include', 'rl4rs_hip.h')]
+HEADERS = ['common.hpp', 'optim.hpp', 'recur_args.hpp', 'augru_x.hpp', 'din_x.hpp', 'row_dedup.hpp', 'row_refine.hpp', 'recur_train.hpp', 'recur8.hpp', 'mfma4.hpp', 'simnet.hpp', 'gather_kernels.hpp', 'simtrain.hpp', 'dientrain.hpp', 'clfmetrics.hpp', 'rawtrain.hpp', 'qlearn.hpp', 'scorers.hpp', 'contirl.hpp', 'amlp_fused.hpp', 'combo.hpp', 'ppo_pass.hpp', 'policy_tile_std.hpp', 'dqn.hpp', 'rawdqn.hpp', 'td3.hpp', 'rainbow.hpp', 'vtrace.hpp', 'gemm_h16_tile.inc', 'augru_x_body.inc', 'din_x_body.inc', 'env_rows_body.inc', 'augru_xs.hpp', 'gemm_h16_defs.hpp', 'cat_attn2_row.hpp', 'dien_plan.hpp', 'step_lanes.hpp', 'exactk_beam.hpp', 'seq2seq_train.hpp', 'reduce_plan.hpp', 'rawtrain_scratch.hpp', os.path.join('..', '..', 'include', 'rl4rs_hip.h')]
 
 
 def _stale():

@@ -7,6 +7,8 @@
 //     head_b (A+1) ]
 #pragma once
 
+#include "rawtrain_scratch.hpp"      // RT_* variable indices, the ten sizes, the sizing of cx.wt / cx.part
+
 namespace rl4rs {
 
 // loss + gradient wrt [logits | value] of one sample per wave, from the head outputs `ext`
@@ -40,8 +42,6 @@ __global__ __launch_bounds__(256) void k_rawpolicy_loss(PolDims d, int N, const 
 }
 
 }  // namespace rl4rs
-
-enum { RT_CAT_EMB = 0, RT_SEQ_EMB, RT_DW1, RT_DB1, RT_DW2, RT_DB2, RT_CTX_W, RT_CTX_B, RT_HEAD_W, RT_HEAD_B, RT_COUNT };
 
 struct rl4rs_rawtrain {
     rl4rs_rawpolicy_cfg c;
@@ -189,7 +189,8 @@ int rl4rs_rawtrain_create(const rl4rs_rawpolicy_cfg* c, const rl4rs_rawpolicy_we
     p->d.OD = 256; p->d.HID = 0; p->d.A = (int)A; p->d.AE = (int)AE; p->d.W = (int)((A + 31) / 32);
     p->F = (int)(S * E + U + E);
     p->opt.t = 0;
-    const int64_t sizes[RT_COUNT] = {H * E, H * E, Dn * U, U, U * U, U, (int64_t)p->F * 256, 256, 256 * AE, AE};
+    const RawTrainScratch sc = rawtrain_scratch(RawTrainDims{E, U, H, S, Dn, c->category_feature_num, c->maxlen, A, c->max_rows});
+    const int64_t* sizes = sc.sizes;
     int64_t o = 0;
     for (int i = 0; i < RT_COUNT; ++i) { p->off[i] = o; o += sizes[i]; }
     p->opt.n = o;
@@ -221,12 +222,11 @@ int rl4rs_rawtrain_create(const rl4rs_rawpolicy_cfg* c, const rl4rs_rawpolicy_we
     RT_FAIL(al(&p->feat, B * p->F)); RT_FAIL(al(&p->h1, B * U)); RT_FAIL(al(&p->ctx, B * 256)); RT_FAIL(al(&p->ext, B * AE));
     RT_FAIL(al(&p->dOut, B * AE)); RT_FAIL(al(&p->d_ctx, B * 256)); RT_FAIL(al(&p->d_feat, B * p->F)); RT_FAIL(al(&p->d_h1, B * U));
     { float* t4; RT_FAIL(al(&t4, B * 4)); p->terms = reinterpret_cast<float4*>(t4); }
-    int64_t wmax = (int64_t)p->F * 256;
-    if (Dn * U > wmax) wmax = Dn * U;
-    if (256 * AE > wmax) wmax = 256 * AE;
-    p->cx.chunk = 512;
-    RT_FAIL(al(&p->cx.wt, wmax));
-    RT_FAIL(al(&p->cx.part, (size_t)((B + 511) / 512) * wmax));
+    // the widest of the four weights, dense_w2 [U, U] included: every chunked gradient and every transposed st_back of a call of
+    // up to max_rows rows fits (rawtrain_scratch.hpp)
+    p->cx.chunk = RAWTRAIN_CHUNK;
+    RT_FAIL(al(&p->cx.wt, (size_t)sc.wt_floats));
+    RT_FAIL(al(&p->cx.part, (size_t)sc.part_floats));
     RT_HIP(hipStreamSynchronize(st));
 #undef RT_HIP
 #undef RT_FAIL

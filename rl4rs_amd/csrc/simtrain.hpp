@@ -14,6 +14,8 @@
 // out_w (S*E + U + E) * 9 | out_b 9 ]); rl4rs_simtrain_eval: the same forward without dropout, no backward (validation).
 #pragma once
 
+#include "reduce_plan.hpp"
+
 namespace rl4rs {
 
 // y = ELU(x) was applied by the GEMM; training-mode dropout on top: keep with probability 1 - rate, scale 1/(1 - rate).
@@ -328,26 +330,8 @@ inline void launch_head_eval(int head, const float* logits, const int32_t* label
     }
 }
 
-// sample-axis reductions / transposed-weight GEMM over an explicit number of samples
-struct TrainCtx { int chunk; float* part; float* wt; size_t part_cap = 0; };       // part_cap: floats behind `part` (0 = sized for `chunk` only)
-
-// Long reductions with wide outputs go through the LDS-tiled 128 x 128 form (k_gemm_tn_t128, policy.hip); the chunk count is chosen
-// to give every CU a workgroup (at most 64 chunks: the partials are summed by k_reduce_chunks4) within what `part` holds.  Returns the chunk count, 0 = not applicable (caller: k_gemm_tn).
-inline int tn_t128_plan(const TrainCtx& x, const float* A, int lda, int M, const float* B, int ldb, int Nc, int Ns, bool bias, int* chunk_out) {
-    if (Ns < 4096 || M < 64 || Nc < 64 || (lda | ldb | M | Nc) % 4 != 0 || ((uintptr_t)A | (uintptr_t)B) % 16 != 0) return 0;
-    const int tiles = ((M + 127) / 128) * ((Nc + 127) / 128);
-    int nz = (256 + tiles - 1) / tiles;
-    if (nz > 64) nz = 64;
-    const size_t per = (size_t)M * Nc + (bias ? Nc : 0);
-    const size_t cap = x.part_cap ? x.part_cap : (size_t)((Ns + x.chunk - 1) / x.chunk) * per;
-    if ((size_t)nz * per > cap) nz = (int)(cap / per);
-    if (nz < 1) return 0;
-    int chunk = (((Ns + nz - 1) / nz) + 15) / 16 * 16;
-    if (chunk < 64) chunk = 64;
-    *chunk_out = chunk;
-    return (Ns + chunk - 1) / chunk;
-}
-constexpr int TN4_MAX_SAMPLES = 1024;      // up to here the whole sample axis is one workgroup's (four waves x Ns / 4 samples)
+// sample-axis reductions / transposed-weight GEMM over an explicit number of samples: TrainCtx and the choice of form are in
+// reduce_plan.hpp
 void st_tn(const TrainCtx& x, hipStream_t st, const float* A, int lda, int M, const float* B, int ldb, int Nc, int Ns, float* dst) {
     if (Ns <= TN4_MAX_SAMPLES) {
         hipLaunchKernelGGL(k_gemm_tn4, dim3(((M + 31) / 32) * ((Nc + 31) / 32)), dim3(256), 0, st, A, lda, M, B, ldb, Nc, Ns, dst, (float*)nullptr);
@@ -400,9 +384,7 @@ void st_tn_cs(const TrainCtx& x, hipStream_t st, const float* A, int lda, int M,
 }
 int st_back(const TrainCtx& x, hipStream_t st, const float* dY, int ldy, int Nout, const float* W, int ldw, int Kin, float* dX, int ldx,
             int Ns) {      // dX [Ns, Kin] = dY [Ns, Nout] W^T,  W [Kin, Nout] with leading dimension ldw
-    // minibatch-sized: no transposed weight copy, 32 x 32 tiles.  (Round 5: the bound is on the ROW count as well - the 16 384-row
-    // input gradients of the simulator trainers' recurrent layers took this form at up to 94 us a call)
-    if (Ns <= 2048 && (int64_t)((Ns + 127) / 128) * ((Kin + 63) / 64) < 512)
+    if (!st_back_transposes(Ns, Kin))      // minibatch-sized: no transposed weight copy, 32 x 32 tiles
         return launch_gemm_nt(dY, ldy, W, ldw, dX, ldx, Ns, Kin, Nout, st);
     hipLaunchKernelGGL(k_transpose, dim3((Kin * Nout + 255) / 256), dim3(256), 0, st, W, (int64_t)ldw, Kin, Nout, x.wt);
     return launch_gemm_f32(dY, ldy, x.wt, Kin, nullptr, dX, ldx, Ns, Kin, Nout, 0, st);

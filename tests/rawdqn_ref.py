@@ -129,8 +129,10 @@ def greedy(v, cfg, cat, dense, seqs, mask, dtype=np.float64):
 
 
 def loss_and_grad(v, tv, cfg, rec, act, rew, done, next_rec, next_mask, weights=None, gamma=1.0, double_q=True, dtype=np.float64,
-                  want_grad=True):
+                  want_grad=True, astar=None):
     """-> dict(loss, grad {variable: array}, td, y, qsa, astar (-1 on terminal rows), boot, gap, q_sel, stats).
+    astar: the a* to bootstrap from on the rows that do, instead of the first maximum found here (a caller that has settled a
+    near-tie some other way); ``gap`` and ``q_sel`` still describe the maxima found here.
     v / tv: the ten variables of the online / target net; rec / next_rec int32 [N, REC]; next_mask [N, A] of 0 / 1 or None.
     A terminal row's successor record is not read (zeros stand in for it); a non-terminal row whose successor allows no action gets
     y = r.  q_sel: the masked Q(s') rows of the selecting net, gap: their top-two gap on the rows that bootstrap (inf elsewhere)."""
@@ -149,8 +151,10 @@ def loss_and_grad(v, tv, cfg, rec, act, rew, done, next_rec, next_mask, weights=
         q_t = q_values(tg, cfg, *nxt, dtype=dtype).numpy()
         q_o = q_values(dict((k, x.detach()) for k, x in on.items()), cfg, *nxt, dtype=dtype).numpy() if double_q else q_t
     q_sel = masked(q_o, mask, dtype)
-    a_ref = q_sel.argmax(axis=1)
     boot = ~done_b & (mask > 0).any(axis=1)
+    a_ref = q_sel.argmax(axis=1)
+    if astar is not None:
+        a_ref = np.where(boot, np.asarray(astar, dtype=np.int64), a_ref)
     top = np.sort(q_sel.astype(np.float64), axis=1)[:, -2:]
     gap = np.where(boot, top[:, 1] - top[:, 0], np.inf)
     qt = np.where(boot, q_t[np.arange(N), a_ref], 0).astype(dtype)
